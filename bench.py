@@ -557,6 +557,27 @@ def ppo_leg(ctx, task: str, envs: int, steps: int, warmup: int, scaling: str = "
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(batch, out_dir: str):
+    """What the last timed env step handed its caller -- the step's output tensors and the env state -- as out_dir/<name>.npy (float32).
+    Row r of every file is the same env.  Over DUMP_MAX_BYTES in all, a fixed seeded sample of env rows (ascending ids, env_ids.npy)."""
+    import numpy as np
+    qpos, qvel, _ = batch.get_state()
+    arrs = {"obs": batch.obs, "priv": batch.priv, "reward": batch.reward, "done": batch.done, "truncation": batch.truncation,
+            "metrics": batch.metrics}
+    arrs = {k: v.detach().cpu().numpy() for k, v in arrs.items()}
+    arrs.update(qpos=qpos, qvel=qvel)
+    row_bytes = sum(a[0].nbytes for a in arrs.values()) + 8          # (+ its env_ids entry)
+    rows = min(batch.nenv, DUMP_MAX_BYTES // row_bytes)
+    ids = np.arange(batch.nenv) if rows == batch.nenv else np.sort(np.random.default_rng(0).choice(batch.nenv, rows, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a[ids], np.float32))
+    np.save(os.path.join(out_dir, "env_ids.npy"), ids.astype(np.float64))
+
+
 def physics_leg(ctx, args, envs: int):
     """The headline: W warm-up + K timed env steps (x repetitions) of the fused env-step launch on this rank's `envs` envs."""
     import torch
@@ -610,6 +631,8 @@ def physics_leg(ctx, args, envs: int):
         times.append(el)
     elapsed = sum(times) / len(times)
     kernel_ms, launches = batch.timing(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(batch, args.dump_outputs)
     done_frac = float(batch.done.mean().item())
     value = world * envs * args.steps / elapsed
     lanes = batch.cfg.lanes_per_env or 32
@@ -775,9 +798,14 @@ def main():
     ap.add_argument("--probe", action="store_true", help="ppo mode: two training steps, replicas compared bit for bit, one line {\"probe\": \"ok\"}; no timing")
     ap.add_argument("--force-split", action="store_true", help="ppo mode, 1 GPU: also time the data-parallel form of the minibatch step on a one-rank RCCL group "
                     "(graph A -> all-reduce -> graph B, and the all-reduce captured in one graph)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="physics mode: after the timed steps, write what the last one returned (obs, priv, reward, done, truncation, metrics, "
+                         "qpos, qvel; rank 0's envs) as DIR/<name>.npy, float32, at most 64 MB in all")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.dump_outputs and args.mode != "physics":
+        raise SystemExit("bench.py: --dump-outputs applies to the physics mode only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_spawn_ranks(args, sys.argv[1:]))          # nothing has touched the GPU yet in this process
 

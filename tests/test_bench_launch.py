@@ -175,3 +175,44 @@ dist.destroy_process_group()
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", "29717", str(script)],
                          capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert out.returncode == 0 and out.stdout.count("ok") == 2, out.stderr[-2000:]
+
+
+class _FakeBatch:
+    """The surface of engine.Batch that bench.dump_outputs reads (CPU tensors; row e of every output belongs to env e)."""
+
+    def __init__(self, nenv):
+        import numpy as np
+        import torch
+        self.nenv, self.nq, self.nv = nenv, 3, 2
+        col = lambda w: torch.arange(nenv, dtype=torch.float32)[:, None].repeat(1, w)
+        self.obs, self.priv, self.metrics = col(5), col(7), col(4)
+        self.reward, self.done, self.truncation = col(1)[:, 0], col(1)[:, 0].clone(), col(1)[:, 0].clone()
+        self._state = (np.repeat(np.arange(nenv, dtype=np.float32)[:, None], self.nq, 1), np.repeat(np.arange(nenv, dtype=np.float32)[:, None], self.nv, 1))
+
+    def get_state(self):
+        return self._state[0], self._state[1], None
+
+
+def test_dump_outputs_writes_every_output_row_aligned_and_capped(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per output of the step, row r of each is the same env; over the byte cap a fixed seeded
+    sample of envs, the same from run to run, with the total under the cap."""
+    import numpy as np
+    b = _bench_module()
+    names = ("obs", "priv", "reward", "done", "truncation", "metrics", "qpos", "qvel")
+    b.dump_outputs(_FakeBatch(50), str(tmp_path / "all"))
+    for k in names:
+        a = np.load(tmp_path / "all" / f"{k}.npy")
+        assert a.dtype == np.float32 and a.shape[0] == 50, k
+        np.testing.assert_array_equal(a.reshape(50, -1)[:, 0], np.arange(50), err_msg=k)
+    np.testing.assert_array_equal(np.load(tmp_path / "all" / "env_ids.npy"), np.arange(50))
+
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 3000)
+    for run in ("s1", "s2"):
+        b.dump_outputs(_FakeBatch(1000), str(tmp_path / run))
+    ids = np.load(tmp_path / "s1" / "env_ids.npy")
+    assert 0 < len(ids) < 1000 and (np.diff(ids) > 0).all()
+    np.testing.assert_array_equal(ids, np.load(tmp_path / "s2" / "env_ids.npy"))
+    assert sum(os.path.getsize(tmp_path / "s1" / f"{k}.npy") - 128 for k in names + ("env_ids",)) <= 3000
+    for k in names:
+        a = np.load(tmp_path / "s1" / f"{k}.npy")
+        np.testing.assert_array_equal(a.reshape(len(ids), -1)[:, 0], ids, err_msg=k)
