@@ -146,6 +146,31 @@ int odk_reset(odk_batch* b, uint32_t seed, uint32_t env_id_offset, const odk_out
 /* AutoReset.step -> Episode.step -> Joystick.step for all envs; action_dev is [nenv, nu]. */
 int odk_step(odk_batch* b, const float* action_dev, const odk_outputs* outs, void* stream);
 
+/* Caller-given commands (replaces mujoco_infer.py's keyboard `self.commands`).  cmd_dev: [nenv, row_stride] device floats on the
+ * batch's device, row e = env e's lin_vel_x, lin_vel_y, ang_vel_yaw, neck_pitch, head_pitch, head_yaw, head_roll (the order of
+ * cmd_range); row_stride >= 7.  NULL unbinds (sampled commands again).  While bound:
+ *   - every odk_step reads env e's row at the start of its step (before the reference motion, the reward and the observation), so a
+ *     stream-ordered write to the buffer between two steps is what the next step follows;
+ *   - odk_reset, the auto-reset inside odk_step and the resample after step 500 store the row where sample_command's value went;
+ *   - every random draw is still made, in the same order: noise, push and reset streams are those of an unbound run.
+ * The buffer stays the caller's and must outlive the binding.  The pointer is a kernel argument: a captured graph keeps the pointer it
+ * was captured with (and reads that buffer's current contents at every replay); bind before capturing. */
+int odk_batch_bind_commands(odk_batch* b, const float* cmd_dev, int row_stride);
+
+/* Velocity-tracking accumulator: one launch per evaluation step, after odk_step, graph-capturable.  For every env whose
+ * acc[e][ODK_TRACK_ENDED] is 0 (its first episode: the Evaluator's `active`) it adds 1 to STEPS and the step's reward to REWARD; on
+ * a done step it adds 1 to FALLS when truncation is 0 and sets ENDED; otherwise (a velocity sample: the observation of a done step is
+ * the auto-reset's first one) it adds 1 to SAMPLES, the achieved local linear velocity x, y and yaw rate to SUM + 0..2 and their
+ * squared errors against the bound command's first three entries to SQERR + 0..2.  The achieved values come from the noise-free
+ * privileged observation (priv_dev [nenv, npriv] of this step): gyro at row offset nobs, local linear velocity at nobs + 9
+ * (odk_model_obs_sizes).  reward_dev / done_dev / truncation_dev: [nenv]; acc_dev: [nenv, ODK_TRACK_NACC], zeroed by the caller
+ * before the first step.  Needs bound commands. */
+#define ODK_TRACK_NACC 12
+enum { ODK_TRACK_ENDED = 0, ODK_TRACK_STEPS = 1, ODK_TRACK_SAMPLES = 2, ODK_TRACK_FALLS = 3, ODK_TRACK_REWARD = 4, ODK_TRACK_SUM = 5,
+       ODK_TRACK_SQERR = 8 };
+int odk_tracking_accumulate(const odk_batch* b, const float* priv_dev, const float* reward_dev, const float* done_dev,
+                            const float* truncation_dev, float* acc_dev, void* stream);
+
 /* mjx_env.step alone (physics only, n_substeps, ctrl = ctrl_dev [nenv, nu]); for parity tests */
 int odk_physics_step(odk_batch* b, const float* ctrl_dev, int n_substeps, void* stream);
 

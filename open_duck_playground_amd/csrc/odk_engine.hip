@@ -142,6 +142,8 @@ struct KArgs {
   uint32_t seed, env_offset;
   int n_substeps;
   EnvCfg cfg;
+  const float* cmd;   // [nenv][cmd_stride] bound commands (odk_batch_bind_commands), or null: sampled ones.  (Last, so that the fields
+  int cmd_stride;     // above keep their argument offsets.)  A uniform pointer test: the unbound path only gains a scalar branch
 };
 
 // DR buffer layout per env
@@ -443,7 +445,12 @@ __global__ void __launch_bounds__(64) reset_kernel(KArgs a) {
     L[S::O_CTRL + u] = v;
     INFO[RL.MT + u] = c.kind != 0 ? 0.0f : m->key_ctrl[u];   // standing.py:279 starts from zeros
   }
-  if (lane < 7) sample_command(c, k0, kr, 0, 9 + NU, lane, INFO[RL.CMD + lane]);
+  if (lane < 7) {   // a bound row replaces the stored value only: the draw is made all the same (the reset stream stays the unbound one)
+    float v;
+    sample_command(c, k0, kr, 0, 9 + NU, lane, v);
+    if (a.cmd) v = a.cmd[(size_t)e * a.cmd_stride + lane];
+    INFO[RL.CMD + lane] = v;
+  }
   ODK_SYNC();
   forward_env<S, G, HF>(L, RT, m, a.hfield, st, lane, 1);
   if (a.dbg_lds && live) dump_lds<S, G>(a.dbg_lds, L, env, lane);
@@ -522,6 +529,10 @@ __global__ void __launch_bounds__(64, ODK_STEP_WAVES) step_kernel(KArgs a) {
     g_par.load(m, drp, lane);
     g_state.store(L + S::O_QPOS, lane); g_info.store(INFO, lane); g_act.store(ACT, lane);
     g_par.store(L, drp != nullptr, lane);   // syncs
+  }
+  if (a.cmd) {   // bound commands: env e's row, read before the reference motion, the reward and the observation use info["command"]
+    if (lane < 7) INFO[RL.CMD + lane] = a.cmd[(size_t)e * a.cmd_stride + lane];
+    ODK_SYNC();
   }
 #ifdef ODK_PROFILE
   for (int k = lane; k < 36; k += G) L[S::O_SCR + S::S_PROF + k] = 0;
@@ -714,7 +725,8 @@ __global__ void __launch_bounds__(64, ODK_STEP_WAVES) step_kernel(KArgs a) {
   for (int u = lane; u < NU; u += G) { la = INFO[RL.LAST + u]; lla = INFO[RL.LAST2 + u]; }
   ODK_SYNC();
   for (int u = lane; u < NU; u += G) { INFO[RL.LAST3 + u] = lla; INFO[RL.LAST2 + u] = la; INFO[RL.LAST + u] = ACT[u]; }
-  if (step_e > 500 && lane < 7) {   // sample_command (joystick.py:671-725) on draws 13 + 2 nu .. 20 + 2 nu of this step (the duck: 41 .. 48)
+  if (step_e > 500 && lane < 7 && !a.cmd) {   // sample_command (joystick.py:671-725) on draws 13 + 2 nu .. 20 + 2 nu of this step (the duck: 41 .. 48);
+                                              // bound: the row read in the prologue stays (the draws were made by draw_block all the same)
     constexpr int DC = draw_cmd(NU) - 4;
     const float z = NZ[DC + 7], u = NZ[DC + lane];
     INFO[RL.CMD + lane] = (z < 0.1f) ? 0.0f : c.cmd_range[lane][0] + u * (c.cmd_range[lane][1] - c.cmd_range[lane][0]);
@@ -749,6 +761,7 @@ __global__ void __launch_bounds__(64, ODK_STEP_WAVES) step_kernel(KArgs a) {
     for (int i = lane; i < S::NQ + 2 * S::NV; i += G) L[S::O_QPOS + i] = fs[i];
     for (int k = lane; k < R::NPRIV; k += G) L[E::O_PRIV + k] = fs[R::FOBS + R::NOBS + k];
     // first_obs["state"] == first_priv[:101] by construction; every lane re-reads only what it wrote: no barrier
+    if (a.cmd && lane >= 6 && lane < 13) L[E::O_PRIV + lane] = INFO[RL.CMD + lane - 6];   // bound: the command slots (obs 6 .. 12, both tasks) show the row
   }
   if (live) {
     // record store addresses recomputed here (opaque offset) instead of being shared with the prologue's loads and
@@ -828,6 +841,7 @@ struct odk_batch {
   int rec_size, frec_size, lds_total, dr_size, env_lds;
   static constexpr size_t ODK_TIMING_EVENT_PAIRS = 1024;
   int timing = 0; size_t timing_count = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> events; size_t ev_used = 0;   // timing: 0 off, n: every n-th launch
+  const float* d_cmd = nullptr; int cmd_stride = 0;   // odk_batch_bind_commands (caller-owned device rows), null: sampled commands
 };
 
 extern "C" const char* odk_last_error(void) { return g_err.c_str(); }
@@ -1831,6 +1845,7 @@ static void base_args(odk_batch* b, KArgs& a, const odk_outputs* o) {
   a.hfield = b->d_hfield;
   a.dr = b->dr_enabled ? b->d_dr : nullptr; a.nenv = b->nenv; a.n_substeps = b->cfg.n_substeps;
   a.dbg_lds = nullptr;
+  a.cmd = b->d_cmd; a.cmd_stride = b->cmd_stride;
   if (o) { a.obs = o->obs_dev; a.priv = o->priv_dev; a.reward = o->reward_dev; a.done = o->done_dev; a.trunc = o->truncation_dev; a.metrics = o->metrics_dev; }
   to_dev_cfg(b->cfg, a.cfg, b->model.h.nu);
 }
@@ -1880,6 +1895,55 @@ extern "C" int odk_step(odk_batch* b, const float* action_dev, const odk_outputs
   } else {
     HIPCHK(launch(b, K_STEP, a, st));
   }
+  return ODK_OK;
+}
+
+extern "C" int odk_batch_bind_commands(odk_batch* b, const float* cmd_dev, int row_stride) {
+  if (!b) return fail(ODK_ERR_INVALID, "null batch");
+  if (cmd_dev && row_stride < 7) return fail(ODK_ERR_INVALID, "command rows hold 7 floats: row_stride %d < 7", row_stride);
+  b->d_cmd = cmd_dev; b->cmd_stride = cmd_dev ? row_stride : 0;
+  return ODK_OK;
+}
+
+// Velocity-tracking sums of one evaluation step (one thread per env): the achieved values are the noise-free privileged observation's
+// gyro (row offset nobs) and local linear velocity (nobs + 9), joystick.py:596-604 / standing.py:549-556
+__global__ void __launch_bounds__(256) tracking_kernel(const float* __restrict__ priv, int npriv, int nobs, const float* __restrict__ reward,
+                                                       const float* __restrict__ done, const float* __restrict__ trunc, const float* __restrict__ cmd,
+                                                       int cmd_stride, float* __restrict__ acc, int nenv) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= nenv) return;
+  float* A = acc + (size_t)e * ODK_TRACK_NACC;
+  if (A[ODK_TRACK_ENDED] != 0.0f) return;       // past its first episode (the Evaluator's `active`)
+  const float d = done[e];
+  A[ODK_TRACK_STEPS] += 1.0f;
+  A[ODK_TRACK_REWARD] += reward[e];
+  if (d != 0.0f) {   // the observation of a done step is the auto-reset's first one: no velocity sample
+    if (trunc[e] == 0.0f) A[ODK_TRACK_FALLS] += 1.0f;
+    A[ODK_TRACK_ENDED] = 1.0f;
+    return;
+  }
+  const float* P = priv + (size_t)e * npriv;
+  const float* C = cmd + (size_t)e * cmd_stride;
+  const float v[3] = {P[nobs + 9], P[nobs + 10], P[nobs + 2]};
+  A[ODK_TRACK_SAMPLES] += 1.0f;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const float err = v[k] - C[k];
+    A[ODK_TRACK_SUM + k] += v[k];
+    A[ODK_TRACK_SQERR + k] += err * err;
+  }
+}
+
+extern "C" int odk_tracking_accumulate(const odk_batch* b, const float* priv_dev, const float* reward_dev, const float* done_dev,
+                                       const float* truncation_dev, float* acc_dev, void* stream) {
+  if (!b || !priv_dev || !reward_dev || !done_dev || !truncation_dev || !acc_dev) return fail(ODK_ERR_INVALID, "null argument");
+  if (!b->d_cmd) return fail(ODK_ERR_INVALID, "odk_tracking_accumulate: no commands bound (odk_batch_bind_commands)");
+  int nobs, npriv;
+  obs_sizes_nu(b->model.h.nu, b->cfg.env_kind, &nobs, &npriv);
+  HIPCHK(hipSetDevice(b->device));
+  hipLaunchKernelGGL(tracking_kernel, dim3((b->nenv + 255) / 256), dim3(256), 0, (hipStream_t)stream, priv_dev, npriv, nobs, reward_dev, done_dev,
+                     truncation_dev, b->d_cmd, b->cmd_stride, acc_dev, b->nenv);
+  HIPCHK(hipGetLastError());
   return ODK_OK;
 }
 

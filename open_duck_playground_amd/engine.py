@@ -137,6 +137,8 @@ def load_library() -> C.CDLL:
     L.odk_reset.argtypes = [P, C.c_uint32, C.c_uint32, C.POINTER(Outputs), P]
     L.odk_step.argtypes = [P, P, C.POINTER(Outputs), P]
     L.odk_physics_step.argtypes = [P, P, C.c_int, P]
+    L.odk_batch_bind_commands.argtypes = [P, P, C.c_int]
+    L.odk_tracking_accumulate.argtypes = [P, P, P, P, P, P, P]
     L.odk_batch_get_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_set_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_get_debug.argtypes = [P, FP, FP, FP, FP]
@@ -180,11 +182,33 @@ EXPORTED_SYMBOLS = (
     "odk_last_error", "odk_default_config", "odk_default_config_standing", "odk_obs_sizes", "odk_model_load", "odk_model_free", "odk_model_dims", "odk_model_obs_sizes", "odk_batch_lanes", "odk_model_reduced",
     "odk_model_env_lds_floats", "odk_batch_create",
     "odk_batch_destroy", "odk_batch_set_config", "odk_batch_set_param", "odk_reset", "odk_step", "odk_physics_step",
+    "odk_batch_bind_commands", "odk_tracking_accumulate",
     "odk_batch_get_state", "odk_batch_set_state", "odk_batch_get_debug", "odk_set_debug_dump", "odk_batch_lds_size",
     "odk_batch_get_lds", "odk_lds_offset", "odk_batch_record_size", "odk_batch_get_records", "odk_batch_set_records", "odk_batch_timing", "odk_gae", "odk_ppo_head",
     "odk_policy_sample", "odk_adam_clip", "odk_silu_bwd_colsum", "odk_colsum_partial", "odk_colsum_finalize", "odk_gather_rows", "odk_dw_gemm",
     "odk_mlp_forward", "odk_mlp_backward", "odk_mlp_set_profile", "odk_pack_weights", "odk_adam_clip_packed", "odk_colsum_fold",
     "odk_adam_clip_packed_tail", "odk_ppo_gae_head", "odk_col_moments", "odk_moments_update")
+
+
+# odk_tracking_accumulate's per-env slots (include/odk.h ODK_TRACK_*)
+TRACK_NACC = 12
+TRACK_ENDED, TRACK_STEPS, TRACK_SAMPLES, TRACK_FALLS, TRACK_REWARD, TRACK_SUM, TRACK_SQERR = 0, 1, 2, 3, 4, 5, 8
+NCOMMAND = 7    # lin_vel_x, lin_vel_y, ang_vel_yaw, neck_pitch, head_pitch, head_yaw, head_roll
+
+
+def check_commands(cmd, nenv: int, device: int) -> None:
+    """What `Batch.bind_commands` accepts: a contiguous float32 [nenv, 7] tensor on cuda:`device`; raises OdkError otherwise."""
+    import torch
+    if not torch.is_tensor(cmd):
+        raise OdkError(f"commands: expected a torch tensor or None, got {type(cmd).__name__}")
+    if tuple(cmd.shape) != (int(nenv), NCOMMAND):
+        raise OdkError(f"commands: shape must be ({nenv}, {NCOMMAND}), got {tuple(cmd.shape)}")
+    if cmd.dtype != torch.float32:
+        raise OdkError(f"commands: dtype must be torch.float32, got {cmd.dtype}")
+    if not cmd.is_contiguous():
+        raise OdkError("commands: the tensor must be contiguous")
+    if cmd.device.type != "cuda" or cmd.device.index != int(device):
+        raise OdkError(f"commands: the tensor must live on cuda:{device} (the env's device), got {cmd.device}")
 
 
 def _chk(rc: int):
@@ -790,6 +814,7 @@ class Batch:
         self.metrics = torch.zeros(self.nenv, NMETRIC, **f32)
         self._outs = Outputs(self.obs.data_ptr(), self.priv.data_ptr(), self.reward.data_ptr(), self.done.data_ptr(),
                              self.truncation.data_ptr(), self.metrics.data_ptr())
+        self.commands = None         # the tensor bound by bind_commands (kept alive while bound)
         self.generation = 0          # advanced by every call that rewrites the per-env records (reset / step / set_records): `State.info` checks it
 
     # -- streams: calls are ordered on torch's current stream
@@ -812,6 +837,30 @@ class Batch:
         assert action.is_cuda and action.dtype == self.torch.float32 and action.is_contiguous() and tuple(action.shape) == (self.nenv, self.model.nu)
         self.generation += 1
         _chk(self.L.odk_step(self._b, C.c_void_p(action.data_ptr()), C.byref(self._outs), self._stream()))
+
+    def bind_commands(self, cmd):
+        """Drive every env with the caller's command (`odk_batch_bind_commands`): `cmd` is a contiguous float32 [nenv, 7] tensor on
+        this batch's device, row e = env e's command (include/odk.h); None returns to sampled commands.  The batch keeps a reference
+        to the tensor while it is bound.  Write into it (stream-ordered) to change the command of the next step; a captured graph
+        keeps the buffer it was captured with, so rebind only before capturing."""
+        if cmd is None:
+            _chk(self.L.odk_batch_bind_commands(self._b, None, 0))
+            self.commands = None
+            return
+        check_commands(cmd, self.nenv, self.device)
+        _chk(self.L.odk_batch_bind_commands(self._b, C.c_void_p(cmd.data_ptr()), NCOMMAND))
+        self.commands = cmd
+
+    def tracking_accumulate(self, acc):
+        """One `odk_tracking_accumulate` launch over this step's outputs into `acc` ([nenv, TRACK_NACC] float32, zeroed before
+        the first step); needs bound commands."""
+        torch = self.torch
+        assert acc.is_cuda and acc.dtype == torch.float32 and acc.is_contiguous() and tuple(acc.shape) == (self.nenv, TRACK_NACC)
+        if self.commands is None:
+            raise OdkError("tracking_accumulate: no commands bound (bind_commands)")
+        _chk(self.L.odk_tracking_accumulate(self._b, C.c_void_p(self.priv.data_ptr()), C.c_void_p(self.reward.data_ptr()),
+                                            C.c_void_p(self.done.data_ptr()), C.c_void_p(self.truncation.data_ptr()),
+                                            C.c_void_p(acc.data_ptr()), self._stream()))
 
     def physics_step(self, ctrl, n_substeps: int = 10):
         assert ctrl.is_cuda and ctrl.dtype == self.torch.float32 and ctrl.is_contiguous() and tuple(ctrl.shape) == (self.nenv, self.model.nu)

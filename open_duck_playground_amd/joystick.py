@@ -293,6 +293,19 @@ class Joystick:
         self._batch.reset(int(rng), self._env_id_offset)
         return self._state()
 
+    def set_commands(self, cmd) -> None:
+        """Drive the envs with caller-given commands instead of sampled ones (what mujoco_infer.py's keyboard `self.commands` does for
+        one CPU env): `cmd` is a contiguous float32 [num_envs, 7] tensor on the env's device -- lin_vel_x, lin_vel_y, ang_vel_yaw,
+        neck_pitch, head_pitch, head_yaw, head_roll per env -- or None to return to sampled commands.  Every step, reset and auto-reset
+        uses env e's row as it is when that launch runs; the random streams stay those of an unbound run.  The env holds a reference to
+        the tensor while it is bound; write into it to change the commands (`Batch.bind_commands`)."""
+        self._batch.bind_commands(cmd)
+
+    @property
+    def commands(self):
+        """The tensor bound by `set_commands`, or None."""
+        return self._batch.commands
+
     def step(self, state: State, action) -> State:
         """reference joystick.py:323 (+ Episode/AutoReset wrappers): one fused kernel launch."""
         self._batch.step(action)
