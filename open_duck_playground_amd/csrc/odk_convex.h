@@ -395,7 +395,7 @@ template <int NFS> __device__ __forceinline__ void face_regs_from_rec(FaceRegs<N
 // faces / edges of this lane in FB / RB); PV: the prism's vertices in LDS for the polygon fetch
 template <int NFS, int NSLOT>
 __device__ __forceinline__ void sat_prism_row(const Prism& P, const float* pc, const float* PV, const Cvx& B, const FaceRegs<NFS>& FB, const EdgeRegs<NSLOT>& RB,
-                                              float sep_a, int face_a, const RowScratch& S, int j, bool act, float cidx0, int knock   // cidx0: candidate index of the pair's first contact; knock: 0 outside the timing experiment (ODK_HF_KNOCK)
+                                              float sep_a, int face_a, const RowScratch& S, int j, bool act, float cidx0   // cidx0: candidate index of the pair's first contact
 #ifdef ODK_PROFILE
                                               , float* prof, long long& tp
 #endif
@@ -412,8 +412,7 @@ __device__ __forceinline__ void sat_prism_row(const Prism& P, const float* pc, c
   float fn[NFS][3];   // this lane's hull face normals (slot s = face j + 16 s; lanes without a second face read face 0's)
 #pragma unroll
   for (int s = 0; s < NFS; s++) ld3(fn[s], B.N + 3 * (FB.on[s] ? j + 16 * s : 0));
-  HF_REP(11) {
-    HF_TOUCH(fn[0][0]);
+  {
     // (vertices 3..5 sit under 0..2 at z = -base: the x / y part of n . v is shared by a column, as in the cull pass)
     float best = -3.0e38f; int bi = 0x7FFFFFFF;
 #pragma unroll
@@ -434,12 +433,11 @@ __device__ __forceinline__ void sat_prism_row(const Prism& P, const float* pc, c
   {
     static_assert(NSLOT == 3, "pass bit = 9 slot + i");
     unsigned pass = 0;
-    if (!(knock & 8)) HF_REP(12) {
+    {
       // The prism's face normals are T = nt, (0, 0, -1), S0 = (0, a0, 0), S1 = (ux, uy, 0), S2 = (b2, 0, 0): written out, the nine
       // b x a and the projections lose their zero terms (the compiler may not drop x * 0), and the three vertical edges' b x a are
       // positive multiples of z -- only signs enter the test, so their c . (b x a) is c.z itself.
-      float tx = P.nt[0]; HF_TOUCH(tx);
-      const float ty = P.nt[1], tz = P.nt[2], a0 = P.ns[0][1], ux = P.ns[1][0], uy = P.ns[1][1], b2 = P.ns[2][0];
+      const float tx = P.nt[0], ty = P.nt[1], tz = P.nt[2], a0 = P.ns[0][1], ux = P.ns[1][0], uy = P.ns[1][1], b2 = P.ns[2][0];
       const float e0x = a0 * tz, e0z = -a0 * tx;                                   // S0 x T
       const float e1x = uy * tz, e1y = -ux * tz, e1z = ux * ty - uy * tx;          // S1 x T
       const float e8y = tz * b2, e8z = -ty * b2;                                   // T x S2
@@ -451,10 +449,9 @@ __device__ __forceinline__ void sat_prism_row(const Prism& P, const float* pc, c
         const float pr[5] = {tx * x[0] + ty * x[1] + tz * x[2], -x[2], a0 * x[1], ux * x[0] + uy * x[1], b2 * x[0]};   // face normal . (d x c)
         const float cb[9] = {c[0] * e0x + c[2] * e0z, c[0] * e1x + c[1] * e1y + c[2] * e1z, c[1] * b2, c[2], c[0] * a0, c[2], c[0] * uy - c[1] * ux, c[2], c[1] * e8y + c[2] * e8z};
         const float db[9] = {d[0] * e0x + d[2] * e0z, d[0] * e1x + d[1] * e1y + d[2] * e1z, d[1] * b2, d[2], d[0] * a0, d[2], d[0] * uy - d[1] * ux, d[2], d[1] * e8y + d[2] * e8z};
-#ifndef ODK_GAUSS_PRODUCTS
         // The three conditions are conditions on SIGNS: taken from the operands' sign bits -- two 3-input bit operations and one funnel shift per pair instead of three
-        // products, a max3, a compare, a select and an or (round 6: -1.9 % of the rough-terrain launch).  Where it differs from the products (-DODK_GAUSS_PRODUCTS builds
-        // those): an operand that is exactly +-0 counts as a signed infinitesimal instead of failing the test, i.e. two arcs that merely TOUCH may pass.  Such a pair's
+        // products, a max3, a compare, a select and an or (round 6: -1.9 % of the rough-terrain launch).  Where it differs from the products (the form it
+        // replaced: max(cb db, adc bdc, -(cb bdc)) < 0): an operand that is exactly +-0 counts as a signed infinitesimal instead of failing the test, i.e. two arcs that merely TOUCH may pass.  Such a pair's
         // edges still carry the support points along their common normal (the closed form of the same condition), so its separation is a true separation along a real
         // axis and cannot beat the exact maximum; it can only tie it (deviations).
         unsigned sp9 = 0u;
@@ -467,23 +464,11 @@ __device__ __forceinline__ void sat_prism_row(const Prism& P, const float* pc, c
           sp9 = __builtin_amdgcn_alignbit(sp9, r, 31);                   // (sp9 << 1) | sign(r): pair i ends at bit i
         }
         pass |= sp9 << (9 * s);
-#else
-#pragma unroll
-        for (int i = 0; i < 9; i++) {
-          const float adc = pr[FA[i]], bdc = pr[FBK[i]];
-          // cb db < 0 and adc bdc < 0 and cb bdc > 0  <=>  max(cb db, adc bdc, -(cb bdc)) < 0: one v_max3_f32 + one compare instead of three compares and
-          // two scalar ANDs per pair (round 6)
-          const bool ok = fmaxf(fmaxf(cb[i] * db[i], adc * bdc), -(cb[i] * bdc)) < 0.0f;
-          pass |= ok ? (1u << (9 * s + i)) : 0u;
-        }
-#endif
         pass &= RB.on[s] ? ~0u : ~(0x1FFu << (9 * s));      // (a lane without a hull edge in this slot passes nothing)
       }
     }
     SAT_PROF(2);
-    HF_REP(13) {
-    HF_TOUCH(pass);
-    HF_REP_SYNC();
+    {
     // The passing pairs of the ROW are shared out evenly: a lane's own count varies from 0 to a dozen, and worked off lane by lane
     // the loop ran as long as the unluckiest lane of the wave.  Every lane PUSHES its passing pairs into the row's list at its
     // place in the row's running count (prefix sum over the row by DPP): one word per pair -- prism edge << 22 | hull edge << 16 |
@@ -492,7 +477,7 @@ __device__ __forceinline__ void sat_prism_row(const Prism& P, const float* pc, c
     int incl = __popc(pass);
     const int cnt = incl;
     incl += (int)ODK_DPPU(incl, 0x111); incl += (int)ODK_DPPU(incl, 0x112); incl += (int)ODK_DPPU(incl, 0x114); incl += (int)ODK_DPPU(incl, 0x118);   // row_shr 1, 2, 4, 8
-    const int total = (knock & 16) ? 0 : __shfl(incl, ODK_ROWBASE | 15, 64);
+    const int total = __shfl(incl, ODK_ROWBASE | 15, 64);
     float* PL = S.PW;
 #ifdef ODK_PROFILE
     if (prof) prof[-6] += (float)total;   // (S_PROF2 + 2: passing edge pairs of the row, summed over the iterations)
@@ -623,7 +608,7 @@ __device__ __forceinline__ void sat_prism_row(const Prism& P, const float* pc, c
   }
   ODK_SYNC();
   SAT_PROF(4);
-  if (!(knock & 32)) HF_REP(14) { HF_TOUCH(n_ref[0]); manifold_row<true>(S, rcnt, icnt, n_ref, n_inc, ref_a ? 1.0f : -1.0f, is_edge, j, act, cidx0); }
+  manifold_row<true>(S, rcnt, icnt, n_ref, n_inc, ref_a ? 1.0f : -1.0f, is_edge, j, act, cidx0);
   SAT_PROF(5);
   if (is_edge) {   // row-uniform
     int ia = pair >> 22;

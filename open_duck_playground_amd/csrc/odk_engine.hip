@@ -491,11 +491,9 @@ __global__ void __launch_bounds__(64) reset_kernel(KArgs a) {
 
 // ================================================================================================
 // AutoReset.step -> Episode.step -> Joystick.step (joystick.py:323-481), all substeps fused
-#ifndef ODK_STEP_WAVES
-#define ODK_STEP_WAVES 2     // waves per SIMD the register allocation is held to (experiment builds: 4 = <= 128 VGPRs; profiles/r5/NOTES.md)
-#endif
+constexpr int STEP_WAVES = 2;     // waves per SIMD the register allocation is held to (3 and 4 spill and run slower: profiles/r5/NOTES.md)
 template <class S, int G, int HF>
-__global__ void __launch_bounds__(64, ODK_STEP_WAVES) step_kernel(KArgs a) {
+__global__ void __launch_bounds__(64, STEP_WAVES) step_kernel(KArgs a) {
   extern __shared__ float lds[];
   using E = EnvL<S>; using R = Rec<S>;
   constexpr int NU = S::NU;
@@ -1717,9 +1715,6 @@ extern "C" int odk_batch_create(const odk_model* m, const odk_env_config* cfg, i
   size_t tbytes = (size_t)nx * ny * nth * 640 * sizeof(float);
   HIPCHK(hipMalloc(&b->d_model, sizeof(DevModel)));
   { DevModel hm = m->h; hm.hfield_filter = cfg->hfield_up_normals_only ? 3 : 0;
-#ifdef ODK_HF_KNOCK   // timing experiment (make libodk_knock.so; WRONG results): parts of the height-field routine switched off by bit
-    if (const char* e = getenv("ODK_HF_KNOCK")) hm.hfield_filter |= atoi(e) << 8;
-#endif
     HIPCHK(hipMemcpy(b->d_model, &hm, sizeof(DevModel), hipMemcpyHostToDevice)); }   // (the batch's own copy: the filter is a batch setting)
   b->h_prm = hp;
   HIPCHK(hipMalloc(&b->d_table, tbytes)); HIPCHK(hipMemcpy(b->d_table, prm_table, tbytes, hipMemcpyHostToDevice));
@@ -1794,11 +1789,7 @@ enum { K_RESET = 0, K_STEP = 1, K_PHYS = 2 };
 template <class S, int G, int HF> static hipError_t launch_sg(int which, const KArgs& a, hipStream_t st) {
   const int per_block = 64 / G;
   const int grid = (a.nenv + per_block - 1) / per_block;
-  size_t lds = (size_t)EnvL<S>::wg_floats(per_block) * sizeof(float);
-#ifdef ODK_OCC_EXPERIMENT   // occupancy experiment (make libodk_occ.so): extra dynamic LDS per workgroup -> fewer workgroups per CU
-  static const size_t pad = getenv("ODK_LDS_PAD") ? (size_t)atol(getenv("ODK_LDS_PAD")) : 0;
-  lds += pad;
-#endif
+  const size_t lds = (size_t)EnvL<S>::wg_floats(per_block) * sizeof(float);
   if (which == K_RESET) hipLaunchKernelGGL((reset_kernel<S, G, HF>), dim3(grid), dim3(64), lds, st, a);
   else if (which == K_STEP) hipLaunchKernelGGL((step_kernel<S, G, HF>), dim3(grid), dim3(64), lds, st, a);
   else hipLaunchKernelGGL((physics_kernel<S, G, HF>), dim3(grid), dim3(64), lds, st, a);

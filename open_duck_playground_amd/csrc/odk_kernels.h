@@ -945,21 +945,6 @@ __device__ __forceinline__ void select4_rows(const float* w, bool has, float sup
 }
 
 }  // namespace odk
-// Timing experiment (make libodk_knock.so, tools/gpu_hf_knock.sh): bits 8.. of the batch's filter word switch parts of the routine
-// off (bits 0-6: the results are WRONG) or run them twice (bits 8-16: same results, the launch grows by that part's cost).
-#ifdef ODK_HF_KNOCK
-#define HF_KNOCK(bit) ((m->hfield_filter >> (8 + (bit))) & 1)
-#define HF_FILTER(m) ((m)->hfield_filter & 255)
-#define HF_REP(bit) for (int _rep = 0; _rep < 1 + ((knock >> (bit)) & 1); _rep++)
-#define HF_TOUCH(x) asm volatile("" : "+v"(x))
-#define HF_REP_SYNC() ODK_SYNC()
-#else
-#define HF_KNOCK(bit) 0
-#define HF_FILTER(m) ((m)->hfield_filter)
-#define HF_REP(bit)
-#define HF_TOUCH(x) do { } while (0)
-#define HF_REP_SYNC() do { } while (0)
-#endif
 #include "odk_convex.h"
 namespace odk {
 
@@ -1041,22 +1026,11 @@ __device__ __forceinline__ void hfield_contacts(float* L, const DevModel* __rest
   const float* XPOS = L + S::O_XPOS; const float* XQUAT = L + S::O_XQUAT; const float* QPOS = L + S::O_QPOS;
   const float ref[3] = {QPOS[0], QPOS[1], QPOS[2]};
   const int f = (lane >> 4) & 1, j = lane & 15;
-#ifdef ODK_HF_KNOCK
-  const int knock = m->hfield_filter >> 8;
-#else
-  constexpr int knock = 0;
-#endif
 #ifdef ODK_PROFILE
   long long _hp = clock64();
 #define HF_PROF(i) do { if (lane == 0) { const long long _t = clock64(); L[S::O_SCR + S::S_PROF2 + (i)] += (float)(_t - _hp); _hp = _t; } } while (0)
 #define HF_COUNT(i, v) do { if (lane == 0) L[S::O_SCR + S::S_PROF2 + (i)] += (float)(v); } while (0)
-#ifdef ODK_PROF_CULL      // (investigation build: the cull pass's own sub-phases in slots 8 .. 13, separate clock; the pair loop's sub-timers then mean nothing)
-#define HF_CULL(i) do { if (lane == 0) { const long long _t = clock64(); L[S::O_SCR + S::S_PROF2 + 8 + (i)] += (float)(_t - _hc); _hc = _t; } } while (0)
 #else
-#define HF_CULL(i) do { } while (0)
-#endif
-#else
-#define HF_CULL(i) do { } while (0)
 #define HF_PROF(i) do { } while (0)
 #define HF_COUNT(i, v) do { } while (0)
 #endif
@@ -1118,8 +1092,6 @@ __device__ __forceinline__ void hfield_contacts(float* L, const DevModel* __rest
     for (int k = 0; k < 3; k++) { hb_v[u][k] = m->foot_vert[f][vs][k]; hb_n[u][k] = m->foot_fnorm[f][ts][k]; }
     hb_off[u] = m->foot_foff[f][ts];
   }
-  HF_REP(8) {
-  HF_TOUCH(Pw[0]);
   // (the cull pass's loops run unmasked over 18 vertices / the faces in fives: the entries past a hull's last are copies of vertex 0 -- no change to
   // a minimum -- and face records that separate nothing)
   // A lane's two vertices (j, j + 16) and two faces; their body-frame data were read at the top of the routine (hb_*), all at once: as two rolled loops each
@@ -1137,7 +1109,6 @@ __device__ __forceinline__ void hfield_contacts(float* L, const DevModel* __rest
     const float4 rec = make_float4(real ? nw[0] : 0.0f, real ? nw[1] : 0.0f, real ? nw[2] : 0.0f, real ? hb_off[u] + dot3(nw, Pw) : 3.0e38f);
     if (u == 0 || v < 18) { FV[3 * v] = vw[0]; FV[3 * v + 1] = vw[1]; FV[3 * v + 2] = vw[2]; }
     if (u == 0 || t < HULL_MAXF) { FN[3 * t] = nw[0]; FN[3 * t + 1] = nw[1]; FN[3 * t + 2] = nw[2]; *reinterpret_cast<float4*>(FN4 + 4 * t) = rec; }      // (normals past the last face are never read)
-  }
   }
   float fc[3];
   for (int k = 0; k < 3; k++) fc[k] = Pw[k] + Rw[3 * k] * m->foot_centroid[f][0] + Rw[3 * k + 1] * m->foot_centroid[f][1] + Rw[3 * k + 2] * m->foot_centroid[f][2];
@@ -1198,15 +1169,10 @@ __device__ __forceinline__ void hfield_contacts(float* L, const DevModel* __rest
     constexpr int pass = 0;
     const int p = j;
     const bool valid = p < nprism;
-#if defined(ODK_PROFILE) && defined(ODK_PROF_CULL)
-    long long _hc = clock64();
-#endif
     float z[3] = {0.0f, 0.0f, 0.0f};
     if (valid) { int cc[3], rr[3]; corners(p, ncw, cc, rr); for (int k = 0; k < 3; k++) z[k] = hf[(rmin + rr[k]) * nc + cmin + cc[k]] * sz; }
-    HF_CULL(0);      // heights
     Prism P;
     prism(valid ? p : 0, ncw, z, P);
-    HF_CULL(1);      // prism
     // plane offsets n . v0 of the five faces (v0: vertex 0 / 3 / 0 / 1 / 2), then min over the hull's vertices of n . v - offset: the top face
     // in a loop over the vertices (batches of six: the LDS reads of a batch are in flight together), the other four from the hull's extents
     float d5[5], s5[5];
@@ -1220,8 +1186,6 @@ __device__ __forceinline__ void hfield_contacts(float* L, const DevModel* __rest
       s5[4] = up ? -e_xmax : e_xmin;      // normal (-sg, 0)
     }
     const int nvu = max(m->foot_nvert[0], m->foot_nvert[1]);   // (wave-uniform trip count, as for the faces below)
-    HF_REP(9) {
-    HF_TOUCH(P.nt[0]);
     float stop = 3.0e38f;
 #pragma unroll 1
     for (int q0 = 0; q0 < nvu; q0 += 6) {
@@ -1232,8 +1196,6 @@ __device__ __forceinline__ void hfield_contacts(float* L, const DevModel* __rest
       for (int t = 0; t < 6; t++) stop = fminf(stop, dot3(P.nt, vv[t]));
     }
     s5[0] = stop;
-    }
-    HF_CULL(2);      // vertex loop
     float sep = -3.0e38f; int face = 0;
 #pragma unroll
     for (int fa = 0; fa < 5; fa++) { const float sv = s5[fa] - d5[fa]; if (sv > sep) { sep = sv; face = fa; } }
@@ -1242,12 +1204,10 @@ __device__ __forceinline__ void hfield_contacts(float* L, const DevModel* __rest
     // one of the hull's side faces and never enters the list; the others are ranked by the larger of the two bounds.  (The six
     // faces of the hull's oriented box instead: a third of the cost, 0.4 more pairs per foot in the loop -- no gain.)
     float sep_b = -3.0e38f;
-    if (!HF_KNOCK(1)) {
+    {
       const float zb = -base;
       // (wave-uniform trip count: with this row's own face count the loop is divergent across the rows and costs three times as much)
       const int nfu = max(m->foot_npoly[0], m->foot_npoly[1]);
-      HF_REP(10) {
-      HF_TOUCH(z[0]);
 #pragma unroll 1
       for (int t0 = 0; t0 < nfu; t0 += 10) {      // (batches of ten faces: ten 16-byte LDS reads in flight together, three waits per pass)
         float4 fnv[10];
@@ -1262,21 +1222,18 @@ __device__ __forceinline__ void hfield_contacts(float* L, const DevModel* __rest
           sep_b = fmaxf(sep_b, sv);
         }
       }
-      }
     }
-    HF_CULL(3);      // face loop
     const float bound = fmaxf(sep, sep_b);
     const bool keep = valid && !(bound > 0.0f);
     const unsigned rowmask = (unsigned)((__builtin_amdgcn_ballot_w64(keep) >> (threadIdx.x & 48u)) & 0xFFFFull);
     const int pos = cnt + __popc(rowmask & ((1u << j) - 1u));
     if (keep) { float* o = LIST + 6 * pos; o[0] = __int_as_float(p | (face << 8)); o[1] = z[0]; o[2] = z[1]; o[3] = z[2]; o[4] = sep; o[5] = bound; }
     cnt += __popc(rowmask);
-    HF_CULL(4);      // list write
   }
   // Prisms 16 / 17 (a 3 x 3 window only): a second pass of the loops above would run them for two lanes of sixteen.  Here the prism is the ROW's
   // and the lanes are the hull's: lane = vertex for the top plane (row minimum), lane = two face records for the hull's query (row maximum) --
   // the same minima / maxima, ~150 instructions per prism instead of a ~1 000-instruction pass (round 6).
-  if (__builtin_amdgcn_ballot_w64(nprism > 16) != 0 && !HF_KNOCK(0)) {
+  if (__builtin_amdgcn_ballot_w64(nprism > 16) != 0) {
 #pragma unroll 1
     for (int p = 16; p < 18; p++) {
       const bool valid = p < nprism;      // (row-uniform)
@@ -1371,7 +1328,7 @@ __device__ __forceinline__ void hfield_contacts(float* L, const DevModel* __rest
   // LDS, no barrier, nothing of it on the vector pipe.
   unsigned long long taken01 = 0ull, taken23 = 0ull;
   int last_pk = 31;           // row-uniform: the entry this row took in the iteration before (foot << 8 | entry); none: entry 31 of foot 0, which no list has
-  const bool up_only = HF_FILTER(m) == 3;   // (read once: every compiler barrier in the loop would fetch it again)
+  const bool up_only = m->hfield_filter == 3;   // (read once: every compiler barrier in the loop would fetch it again)
 #ifdef ODK_PROFILE
   _hp = clock64();   // (slot 2 counts the passing edge pairs of lane 0's row: odk_convex.h)
 #endif
@@ -1399,7 +1356,7 @@ __device__ __forceinline__ void hfield_contacts(float* L, const DevModel* __rest
         n_pk |= (unsigned)__popc(open_t[t]) << (8 * t);
       }
     }
-    if (n_pk == 0u || HF_KNOCK(2)) break;
+    if (n_pk == 0u) break;
     // assignment: a row works its own foot while that has open entries, an idle row goes where most are left.  The rule is a function of the four
     // counts capped at four (a foot can use its own row and three helpers): ONE scalar load from a 625-entry table in constant memory
     // (odk_model.h make_hf_assign; the ~300 dependent scalar instructions that derived it in place were the largest single block of the loop's scalar work: round 6)
@@ -1455,9 +1412,9 @@ __device__ __forceinline__ void hfield_contacts(float* L, const DevModel* __rest
     float* prof = lane == 0 ? L + S::O_SCR + S::S_PROF2 + 8 : nullptr;
     long long tp = clock64();
     if (prof) { prof[0] += (float)(tp - _hp); }
-    sat_prism_row<2, 3>(P, pc, PV, B, FB, RB, sep_a, face_a, RSS, j, act, (float)(4 * p), 0, prof, tp);
+    sat_prism_row<2, 3>(P, pc, PV, B, FB, RB, sep_a, face_a, RSS, j, act, (float)(4 * p), prof, tp);
 #else
-    sat_prism_row<2, 3>(P, pc, PV, B, FB, RB, sep_a, face_a, RSS, j, act, (float)(4 * p), knock);
+    sat_prism_row<2, 3>(P, pc, PV, B, FB, RB, sep_a, face_a, RSS, j, act, (float)(4 * p));
 #endif
     // opt-in (odk_env_config.hfield_up_normals_only; oracle hfield_mode 3; default off): a pair's contacts count only when its
     // normal points up -- one wave-uniform flag from the batch's model, nothing on the default path but the test
@@ -1465,24 +1422,11 @@ __device__ __forceinline__ void hfield_contacts(float* L, const DevModel* __rest
       ODK_SYNC();
       if (act && j < 4 && !(NEW[8 * j + 6] > 0.5f)) NEW[8 * j] = 1.0f;
     }
-#if defined(ODK_HF_VARIANT) && ODK_HF_VARIANT == 4
-    // hypothesis sweep (make libodk_hfv4.so; oracle hfield_mode 4): one contact per prism, its deepest (first of equals)
-    ODK_SYNC();
-    {
-      const float d0 = NEW[0], d1 = NEW[8], d2 = NEW[16], d3 = NEW[24];
-      int kb = 0; float db = d0;
-      if (d1 < db) { db = d1; kb = 1; }
-      if (d2 < db) { db = d2; kb = 2; }
-      if (d3 < db) { db = d3; kb = 3; }
-      ODK_SYNC();
-      if (act && j < 4 && j != kb) NEW[8 * j] = 1.0f;
-    }
-#endif
     ODK_SYNC();
 #ifdef ODK_PROFILE
     if (prof) prof[7] += (float)(clock64() - tp);   // (of `writes + merge`: the edge contact and the writes, before the merges)
 #endif
-    if (!HF_KNOCK(6)) for (unsigned q = 0; q <= maxq; q++) merge_top4_row(TOPt, NEW, j, act && my_q == (int)q);
+    for (unsigned q = 0; q <= maxq; q++) merge_top4_row(TOPt, NEW, j, act && my_q == (int)q);
 #ifdef ODK_PROFILE
     { const long long t2 = clock64(); if (prof) prof[6] += (float)(t2 - tp); _hp = t2; }
 #endif

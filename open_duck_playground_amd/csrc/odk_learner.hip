@@ -518,9 +518,7 @@ __global__ void gather_rows_kernel(GatherArgs a, const long long* __restrict__ i
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int DW_MAX = 8;
-#ifndef DW_AHEAD
-#define DW_AHEAD 2
-#endif
+constexpr int DW_AHEAD = 2;     // row groups in flight under a full tile's MFMAs (deeper rings were no faster: profiles/r5/NOTES.md section 9)
 struct DwLayer { const float* dz; const float* h; int n_out, n_in, tj, tile0, ngroups; long long out_off; };   // ngroups = rows / 8
 // Schedule (round 4).  A wave alone on its SIMD runs a full tile slice in ~35 us; the first version launched ntiles x kslices = 68 x 16
 // = 1 088 single-wave workgroups on the chip's 1 024 SIMDs, so 64 SIMDs carried two and the launch lasted two wave-times (69 us,
@@ -536,10 +534,7 @@ struct DwLayer { const float* dz; const float* h; int n_out, n_in, tj, tile0, ng
 constexpr int DW_SLOTS = 64, DW_SLOT_ITEMS = 4, DW_WAVES = 2;
 struct DwArgs { DwLayer L[DW_MAX]; int nlayers, ntiles, kslices, nslots; float* ws; long long ws_stride; long long* prof; unsigned short item[DW_SLOTS][DW_SLOT_ITEMS]; };
 
-#ifndef DW_MI
-#define DW_MI 4      // output tile of a wave: DW_MI x DW_MJ blocks of 32 x 32 (rows = n_out side, columns = n_in side)
-#define DW_MJ 2
-#endif
+constexpr int DW_MI = 4, DW_MJ = 2;      // output tile of a wave: DW_MI x DW_MJ blocks of 32 x 32 (rows = n_out side, columns = n_in side)
 // One (tile, slice) item with NI x NJ blocks of 32 x 32 that exist (compile time: an edge tile of the matrix runs its own
 // instantiation -- loads and MFMAs for its blocks only; as one runtime-guarded loop the edge tiles ran 2.5x longer per MFMA than
 // full ones and their slots were the launch's tail).

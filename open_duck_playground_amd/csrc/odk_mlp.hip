@@ -45,9 +45,6 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef ODK_FWD_DBUF
-#define ODK_FWD_DBUF 0
-#endif
 constexpr int H1 = ODK_MLP_H1, H2 = ODK_MLP_H2, H3 = ODK_MLP_H3;
 constexpr int TM = ODK_MLP_TILE;       // samples per workgroup
 constexpr int CH = 128;                // layer-1 chunk width = K-slice of layer 2
@@ -57,11 +54,10 @@ constexpr int PX_MAX = KIN_MAX + 4;
 constexpr int SLACK = 64;              // the k loops fetch (never use) up to two batches past a row's end
 static_assert(TM == 16 && KIN_MAX % 16 == 0, "tile = one 16-row MFMA block, padded input width");
 // forward LDS (floats): X | chunk | layer-2 output | slack;  the layer-3 output aliases X, the output layer's partial blocks alias the chunk
-constexpr int NCBUF = ODK_FWD_DBUF ? 2 : 1;
-constexpr int F_X = 0, F_C = F_X + TM * PX_MAX, F_H2 = F_C + NCBUF * TM * PC, F_TOTAL = F_H2 + TM * P2 + SLACK;
+constexpr int F_X = 0, F_C = F_X + TM * PX_MAX, F_H2 = F_C + TM * PC, F_TOTAL = F_H2 + TM * P2 + SLACK;
 static_assert(TM * P3 <= TM * PX_MAX, "layer-3 output must fit in the X region");
 static_assert(3 * 2 * 4 * 64 <= TM * PC, "output-layer partial blocks must fit in the chunk region");
-static_assert(F_TOTAL * 4 <= (ODK_FWD_DBUF ? 53 : 40) * 1024, "four (three with two chunk buffers) forward workgroups per CU");
+static_assert(F_TOTAL * 4 <= 40 * 1024, "four forward workgroups per CU");
 // backward LDS: dz_top | dz3 | dz2 | slack
 constexpr int B_D4 = 0, B_D3 = B_D4 + TM * P4, B_D2 = B_D3 + TM * P3, B_TOTAL = B_D2 + TM * P2 + SLACK;
 
@@ -81,7 +77,7 @@ struct Net {
 // PPV x 64, PVV x 80, PV x 112.  `Map` deals the costly network's tiles to the two-tile CUs first and spreads the rest one per
 // three-tile CU: PPV x 112, PPP x 32, VV x 112 -- the longest CU 7 % shorter.  Only speed depends on the dispatch order.
 struct Map { int R, rounds, rem, vin2, pin2, v3, costly, on; };
-struct Args { Net net[2]; int nnets; int diag; long long* prof; long long* wgprof; Map map; };
+struct Args { Net net[2]; int nnets; long long* prof; long long* wgprof; Map map; };
 __device__ __forceinline__ void map_block(const Args& a, int b, int& net, int& tile) {
   const Map& m = a.map;
   if (!m.on) { net = (a.nnets > 1 && b >= a.net[1].tile0) ? 1 : 0; tile = b - a.net[net].tile0; return; }
@@ -106,51 +102,18 @@ __device__ __forceinline__ void map_block(const Args& a, int b, int& net, int& t
 // (minimum register pressure = one exposed L2 round trip per MFMA).  Groups >= ng are fetched from group 0 (in bounds) and
 // skipped.  NBLK >= 2 everywhere: a 16x16x4 MFMA has 40 cycles of dependent latency for 32 of issue.
 #define ODK_PIN() __builtin_amdgcn_sched_barrier(0)
-#ifndef ODK_MLP_WG_PER_CU
-#define ODK_MLP_WG_PER_CU 4       // resident workgroups per CU the register allocation is held to (4: <= 128 VGPRs, 3: <= 168)
-#endif
-#ifndef ODK_BWD_PREFETCH_G
-#define ODK_BWD_PREFETCH_G 0      // backward: a phase's swish' pieces are fetched one phase ahead instead of behind its MFMAs
-#endif
-#ifndef ODK_FWD_DBUF
-#define ODK_FWD_DBUF 0            // forward: two chunk buffers alternate, one barrier per chunk instead of two (three workgroups per CU)
-#endif
-#ifndef ODK_MLP_SETPRIO
-#define ODK_MLP_SETPRIO 0         // raise the wave's priority inside the MFMA loops
-#endif
-template <int NBLK, int U, bool RING = false>      // RING: the diagnostic build's forward kernel (weights from LDS: diag bits 5 / 6)
+constexpr int MLP_WG_PER_CU = 4;      // resident workgroups per CU the register allocation is held to (4: <= 128 VGPRs; 3 = <= 168 measured within 1 %: profiles/r5/NOTES.md)
+template <int NBLK, int U>
 struct Phase {
   f32x4 fb[U][NBLK];
   const f32x4* B; unsigned lane_off, blk_off; int N4, ng;
-#ifdef ODK_MLP_DIAG    // diagnostic build (make libodk_mlpdiag.so; tools/gpu_mlp_wg_profile.py): bit 0 = every group re-reads group 0 (L1 hits), bit 1 = no MFMAs,
-                       // bit 2 = no operand loads inside the loops, bit 3 = no activation stores, bit 4 = half of the weight loads,
-                       // bit 5 (round 6: what would a SHARED WEIGHT RING IN LDS buy at best?) = the weights come from LDS instead of global memory -- every B piece
-                       // is one ds_read_b128 from an 8 KB region behind the workgroup's image, with the real layout's bank pattern, no fill and no synchronisation --,
-                       // bit 6 = with bit 5, every third k-group is ALSO fetched from global memory and written to that region (a ring filled once per CU by the
-                       // three tile groups it serves: each group's share of the fill traffic)
-  int diag = 0;
-  float* ring = nullptr;
-#else
-  static constexpr int diag = 0;
-#endif
   __device__ __forceinline__ void load_b(int G0, f32x4 (*xb)[NBLK]) const {
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const int G = G0 + u;
-      const f32x4* bp = B + (size_t)((G < ng && !(diag & 1)) ? G : 0) * N4;   // wave-uniform base, 32-bit lane offset (diag 1, tools: every group re-reads group 0 -> L1 hits)
+      const f32x4* bp = B + (size_t)(G < ng ? G : 0) * N4;   // wave-uniform base, 32-bit lane offset
 #pragma unroll
-      for (int k = 0; k < NBLK; k++) {
-        if ((diag & 16) && (k & 1)) xb[u][k] = xb[u][k - 1];       // (diag 16, tools: half of the weight loads: what the launch would cost with twice the reuse per piece)
-#ifdef ODK_MLP_DIAG
-        else if (RING && (diag & 32)) {
-          f32x4* slot = reinterpret_cast<f32x4*>(ring) + ((G & 1) << 8);
-          const unsigned pi = (lane_off + blk_off * k) & 255u;
-          if ((diag & 64) && G % 3 == 0) slot[pi] = bp[lane_off + blk_off * k];
-          xb[u][k] = slot[pi];
-        }
-#endif
-        else xb[u][k] = bp[lane_off + blk_off * k];
-      }
+      for (int k = 0; k < NBLK; k++) xb[u][k] = bp[lane_off + blk_off * k];
     }
   }
   // Bp: the packed weight, ncols columns; this lane's column in block k: col + blk * k (blk = 16; the output layer, narrower
@@ -164,9 +127,6 @@ struct Phase {
   // A: LDS address of act[sample c][4 q] (16-byte aligned)
   __device__ __forceinline__ void run(f32x4 (&acc)[NBLK], const float* A) {
     f32x4 fa[U], ga[U], gb[U][NBLK];
-#if ODK_MLP_SETPRIO
-    __builtin_amdgcn_s_setprio(ODK_MLP_SETPRIO);
-#endif
     auto load_a = [&](int G0, f32x4* xa) {
 #pragma unroll
       for (int u = 0; u < U; u++) xa[u] = *reinterpret_cast<const f32x4*>(A + 16 * (G0 + u));   // in bounds of the LDS image (SLACK)
@@ -174,7 +134,7 @@ struct Phase {
     auto mma = [&](int G0, const f32x4* xa, const f32x4 (*xb)[NBLK]) {
 #pragma unroll
       for (int u = 0; u < U; u++) {
-        if (G0 + u < ng && !(diag & 2)) {     // (diag 2, tools: no MFMAs)
+        if (G0 + u < ng) {
 #pragma unroll
           for (int j = 0; j < 4; j++)
 #pragma unroll
@@ -185,24 +145,15 @@ struct Phase {
     load_a(0, fa);
     ODK_PIN();
     for (int G0 = 0; G0 < ng; G0 += 2 * U) {
-      if (!(diag & 4)) { load_b(G0 + U, gb); load_a(G0 + U, ga); }        // (diag 4, tools: no operand loads inside the loop: what the MFMAs alone cost)
-      else if (G0 == 0) {
-#pragma unroll
-        for (int u = 0; u < U; u++) { ga[u] = fa[u];
-#pragma unroll
-          for (int k = 0; k < NBLK; k++) gb[u][k] = fb[u][k]; }
-      }
+      load_b(G0 + U, gb); load_a(G0 + U, ga);
       ODK_PIN();
       mma(G0, fa, fb);
       ODK_PIN();
-      if (!(diag & 4)) { load_b(G0 + 2 * U, fb); load_a(G0 + 2 * U, fa); }
+      load_b(G0 + 2 * U, fb); load_a(G0 + 2 * U, fa);
       ODK_PIN();
       mma(G0 + U, ga, gb);
       ODK_PIN();
     }
-#if ODK_MLP_SETPRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
   }
 };
 
@@ -238,7 +189,7 @@ __device__ __forceinline__ void fwd_epilogue(const f32x4 (&acc)[NBLK], const flo
   }
 }
 
-__global__ void __launch_bounds__(256, ODK_MLP_WG_PER_CU) mlp_fwd_kernel(Args a) {
+__global__ void __launch_bounds__(256, MLP_WG_PER_CU) mlp_fwd_kernel(Args a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   int net_i, tile;
   map_block(a, blockIdx.x, net_i, tile);
@@ -248,17 +199,8 @@ __global__ void __launch_bounds__(256, ODK_MLP_WG_PER_CU) mlp_fwd_kernel(Args a)
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, q = lane >> 4, c = lane & 15;
   const int kin = N.n_in, k16 = pad16(kin), PX = k16 + 4;
   float* X = lds + F_X; float* C1 = lds + F_C; float* H2s = lds + F_H2; float* H3s = lds + F_X;
-#ifdef ODK_MLP_DIAG
-  Phase<2, 2, true> p1; Phase<4, 1, true> p2;
-#else
   Phase<2, 2> p1;     // layer 1 (32 columns of the current chunk), layer 3, output layer
   Phase<4, 1> p2;     // layer 2, K-slice = the chunk, 64 columns
-#endif
-#ifdef ODK_MLP_DIAG
-  p1.diag = p2.diag = a.diag;
-  p1.ring = p2.ring = lds + ((F_TOTAL + 3) & ~3);
-  if (a.diag & 32) { for (int i = threadIdx.x; i < 2048; i += 256) p1.ring[i] = 0.01f; __syncthreads(); }
-#endif
   ODK_WG_BEGIN();
   ODK_STAMP(0);
   p1.prefetch(N.wf[0], H1, w * 32 + c, q, 0, k16 >> 4);
@@ -316,11 +258,7 @@ __global__ void __launch_bounds__(256, ODK_MLP_WG_PER_CU) mlp_fwd_kernel(Args a)
   }
   __syncthreads();
   ODK_STAMP(1);
-#ifdef ODK_MLP_DIAG
-  const bool store = N.h[0] != nullptr && !(a.diag & 8);      // (diag 8, tools: no stores of the activations)
-#else
   const bool store = N.h[0] != nullptr;
-#endif
   const size_t q0 = (size_t)(m0 >> 2);   // the tile's first row quad
   if (store) {   // quad-row copy of the input (the weight-gradient launch's operand)
     for (int k = threadIdx.x; k < kin; k += 256)
@@ -340,24 +278,19 @@ __global__ void __launch_bounds__(256, ODK_MLP_WG_PER_CU) mlp_fwd_kernel(Args a)
     f32x4 acc1[2];
     zero(acc1);
     const int col = ch * CH + w * 32 + c;
-    float* Cc = C1 + (ODK_FWD_DBUF ? (ch & 1) * TM * PC : 0);    // this chunk's buffer
     p1.run(acc1, X + c * PX + 4 * q);
     ODK_STAMP(2 + 5 * ch);
     p2.prefetch(N.wf[1], H2, w * 64 + c, q, ch * (CH / 16), CH / 16);
-    fwd_epilogue<2>(acc1, bias1[ch], Cc + w * 32 + c, PC, store ? N.h[0] + (ql * H1 + col) * 4 : nullptr, store ? N.g[0] + (ql * H1 + col) * 4 : nullptr, q,
+    fwd_epilogue<2>(acc1, bias1[ch], C1 + w * 32 + c, PC, store ? N.h[0] + (ql * H1 + col) * 4 : nullptr, store ? N.g[0] + (ql * H1 + col) * 4 : nullptr, q,
                     rows_valid);
     ODK_STAMP(3 + 5 * ch);
     __syncthreads();
     ODK_STAMP(4 + 5 * ch);
-    p2.run(acc2, Cc + c * PC + 4 * q);
+    p2.run(acc2, C1 + c * PC + 4 * q);
     ODK_STAMP(5 + 5 * ch);
     if (ch + 1 < H1 / CH) p1.prefetch(N.wf[0], H1, col + CH, q, 0, k16 >> 4);
     else p1.prefetch(N.wf[2], H3, w * 32 + c, q, 0, H2 / 16);
-    // one buffer: nobody may overwrite the chunk before every wave has read it.  Two buffers: the next chunk goes to the other one, and the
-    // chunk after that is written behind the next chunk's barrier, which a wave passes only after this p2.run -- no barrier here (the last
-    // chunk keeps it: the layer-2 epilogue below writes H2s, which nobody reads before the barrier that follows it, but the output layer's
-    // partial blocks alias the chunk region)
-    if (!ODK_FWD_DBUF || ch + 1 == H1 / CH) __syncthreads();
+    __syncthreads();     // nobody may overwrite the chunk before every wave has read it
     ODK_STAMP(6 + 5 * ch);
   }
   {
@@ -440,7 +373,7 @@ __device__ __forceinline__ void bwd_epilogue(const f32x4 (&acc)[NBLK], const f32
   }
 }
 
-__global__ void __launch_bounds__(256, ODK_MLP_WG_PER_CU) mlp_bwd_kernel(Args a) {
+__global__ void __launch_bounds__(256, MLP_WG_PER_CU) mlp_bwd_kernel(Args a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   int net_i, tile;
   map_block(a, blockIdx.x, net_i, tile);
@@ -453,9 +386,6 @@ __global__ void __launch_bounds__(256, ODK_MLP_WG_PER_CU) mlp_bwd_kernel(Args a)
   Phase<2, 2> p3;     // dh3 = dout W4: columns w * 32 .. + 31, K = n_out
   Phase<4, 1> p2;     // dh2 = dz3 W3: columns w * 64 .. + 63, K = 128
   Phase<8, 1> p1;     // dh1 = dz2 W2: columns w * 128 .. + 127, K = 256
-#ifdef ODK_MLP_DIAG
-  p1.diag = p2.diag = p3.diag = a.diag;
-#endif
   ODK_WG_BEGIN();
   p3.prefetch(N.wb[3], H3, w * 32 + c, q, 0, pad16(nout) >> 4);
   // ---- the tile of dLoss/dout, zero beyond the tile's rows / the layer's columns
@@ -478,34 +408,23 @@ __global__ void __launch_bounds__(256, ODK_MLP_WG_PER_CU) mlp_bwd_kernel(Args a)
     *reinterpret_cast<f32x4*>(N.doutp + ((q0 + qq) * nout + k) * 4) = v;
   }
   f32x4 gv3[2], gv2[4], gv1[8];
-#if ODK_BWD_PREFETCH_G
-  load_g<2>(gv3, N.g[2] + (ql * H3 + w * 32 + c) * 4);       // (the row quads' swish' pieces do not depend on anything computed here)
-  load_g<4>(gv2, N.g[1] + (ql * H2 + w * 64 + c) * 4);
-#endif
   {
     f32x4 acc[2];
     zero(acc);
     const int col = w * 32 + c;
     p3.run(acc, D4 + c * P4 + 4 * q);
     p2.prefetch(N.wb[2], H2, w * 64 + c, q, 0, H3 / 16);
-#if !ODK_BWD_PREFETCH_G
     load_g<2>(gv3, N.g[2] + (ql * H3 + col) * 4);
-#endif
     bwd_epilogue<2>(acc, gv3, N.dz[2] + (ql * H3 + col) * 4, D3 + col, P3, N.bias_partial[2] + (size_t)tile * H3 + col, q);
   }
   __syncthreads();
-#if ODK_BWD_PREFETCH_G
-  load_g<8>(gv1, N.g[0] + (ql * H1 + w * 128 + c) * 4);
-#endif
   {
     f32x4 acc[4];
     zero(acc);
     const int col = w * 64 + c;
     p2.run(acc, D3 + c * P3 + 4 * q);
     p1.prefetch(N.wb[1], H1, w * 128 + c, q, 0, H2 / 16);
-#if !ODK_BWD_PREFETCH_G
     load_g<4>(gv2, N.g[1] + (ql * H2 + col) * 4);
-#endif
     bwd_epilogue<4>(acc, gv2, N.dz[1] + (ql * H2 + col) * 4, D2 + col, P2, N.bias_partial[1] + (size_t)tile * H2 + col, q);
   }
   __syncthreads();
@@ -514,9 +433,7 @@ __global__ void __launch_bounds__(256, ODK_MLP_WG_PER_CU) mlp_bwd_kernel(Args a)
     zero(acc);
     const int col = w * 128 + c;
     p1.run(acc, D2 + c * P2 + 4 * q);
-#if !ODK_BWD_PREFETCH_G
     load_g<8>(gv1, N.g[0] + (ql * H1 + col) * 4);
-#endif
     bwd_epilogue<8>(acc, gv1, N.dz[0] + (ql * H1 + col) * 4, nullptr, 0, N.bias_partial[0] + (size_t)tile * H1 + col, q);
   }
   ODK_WG_END();
@@ -724,10 +641,9 @@ int check_launch(const char* what) {
 
 long long* g_prof = nullptr;
 long long* g_wgprof = nullptr;
-int g_diag = 0;
 
 int fill_args(Args& a, const odk_mlp_desc* nets, int count, bool backward, int& tiles, const char*& err) {
-  a.nnets = count; tiles = 0; a.prof = backward ? nullptr : g_prof; a.wgprof = g_wgprof; a.diag = g_diag;
+  a.nnets = count; tiles = 0; a.prof = backward ? nullptr : g_prof; a.wgprof = g_wgprof;
   for (int k = 0; k < 2; k++) {
     Net& N = a.net[k];
     if (k >= count) { N = a.net[0]; N.tile0 = 1 << 30; continue; }
@@ -814,18 +730,12 @@ int odk_func_lds_attr_(const void* fn, int slot, int bytes) {
 extern "C" void odk_mlp_set_profile(long long* stamps_dev) { g_prof = stamps_dev; }
 // tools: device buffer of 4 x (workgroups of a network launch) int64: start / end (100 MHz wall clock), HW_ID | XCC_ID << 32, shader cycles
 extern "C" void odk_mlp_set_wg_profile(long long* dev) { g_wgprof = dev; }
-// tools: diagnostic variants of the network launches (WRONG results): bit 0 = every weight load re-reads the phase's first group (L1 hits), bit 1 = no MFMAs
-extern "C" void odk_mlp_set_diag(int bits) { g_diag = bits; }
 
 extern "C" int odk_mlp_forward(const odk_mlp_desc* nets, int count, void* stream) {
   if (!nets || count < 1 || count > 2) return odk_fail_(ODK_ERR_INVALID, "odk_mlp_forward: 1 or 2 networks");
   Args a; int tiles; const char* err = nullptr;
   if (fill_args(a, nets, count, false, tiles, err)) return odk_fail_(ODK_ERR_INVALID, err);
-#ifdef ODK_MLP_DIAG
-  const int fwd_lds = ((F_TOTAL + 3) & ~3) * 4 + 8192;      // (+ the stand-in for a weight ring: diag bits 5 / 6)
-#else
   const int fwd_lds = F_TOTAL * 4;
-#endif
   if (odk_func_lds_attr_((const void*)mlp_fwd_kernel, 1, fwd_lds)) return odk_fail_(ODK_ERR_HIP, "odk_mlp_forward: the device refuses the kernel's dynamic LDS size");
   hipLaunchKernelGGL(mlp_fwd_kernel, dim3(tiles), dim3(256), fwd_lds, (hipStream_t)stream, a);
   return check_launch("odk_mlp_forward: launch failed");

@@ -27,8 +27,6 @@ for n, n_in, n_out in specs:
     nets.append(dict(x=x, wf=[table.fwd_view(pf, k + l) for l in range(4)], wb=[table.bwd_view(pb, k + l) for l in range(4)], b=b, out=torch.empty(n, n_out, device="cuda"),
                      dout=torch.randn(n, n_out, device="cuda", generator=g) * 1e-3, **engine.FusedMLP.train_buffers(n, n_in, n_out, "cuda")))
     k += 4
-L.odk_mlp_set_diag.argtypes = [C.c_int]
-L.odk_mlp_set_diag(int(os.environ.get("ODK_MLP_DIAG", "0")))
 op = engine.FusedMLP(nets)
 fn = op.forward if which == "fwd" else op.backward
 op.forward()
