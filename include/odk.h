@@ -157,6 +157,46 @@ int odk_step(odk_batch* b, const float* action_dev, const odk_outputs* outs, voi
  * was captured with (and reads that buffer's current contents at every replay); bind before capturing. */
 int odk_batch_bind_commands(odk_batch* b, const float* cmd_dev, int row_stride);
 
+/* Reward-library terms (reference playground/common/rewards.py) computed by the step kernel on top of the seven native slots of
+ * odk_env_config.reward_scales.  A term is on when its scale is non-zero (the reference's reward_config.scales decide it the same
+ * way, joystick.py:304-311); the scaled term is added to the step's total before clip(total * dt, 0, 10000), and its metric is
+ * stored like the native ones: scale > 0 ? scaled : -scaled.  Inputs (the robot's own sensors, sites, actuators and limits):
+ *   LIN_VEL_Z        cost_lin_vel_z(global_linvel sensor of the imu site)       -- needs a `global_linvel` sensor (ODK_ERR_UNSUPPORTED otherwise)
+ *   ANG_VEL_XY       cost_ang_vel_xy(global_angvel sensor)
+ *   ORIENTATION      cost_orientation(upvector sensor)                          -- joystick.py:645 (commented there); Standing has it as a native slot
+ *   BASE_HEIGHT      cost_base_height(qpos[2], base_height_target)
+ *   ENERGY           cost_energy(|qvel| |qfrc_actuator|) over the actuated dofs (qfrc_actuator of a dof = its actuator's force)
+ *   JOINT_POS_LIMITS cost_joint_pos_limits(actuated qpos, soft limits c -+ 0.5 r soft_joint_pos_limit_factor of jnt_range, joystick.py:135-139)
+ *   TERMINATION      cost_termination(the step's termination: not the EpisodeWrapper's truncation)
+ *   POSE             cost_pose(actuated qpos, home keyframe ctrl, pose_weight[0 .. nu))
+ *   FEET_SLIP        cost_feet_slip(contact[2], feet *_global_linvel sensors [2][3])
+ *   FEET_CLEARANCE   cost_feet_clearance(feet linvel sensors, feet site z, max_foot_height)
+ *   FEET_HEIGHT      cost_feet_height(swing_peak after this step's max, first_contact, max_foot_height)
+ *   FEET_AIR_TIME    reward_feet_air_time(feet_air_time after += dt, first_contact, command, air_time_range)
+ * with first_contact = (feet_air_time before the increment > 0) * (contact | last_contact), joystick.py:430-431. */
+#define ODK_NXTERM 12
+enum odk_xterm {
+  ODK_XTERM_LIN_VEL_Z = 0, ODK_XTERM_ANG_VEL_XY = 1, ODK_XTERM_ORIENTATION = 2, ODK_XTERM_BASE_HEIGHT = 3, ODK_XTERM_ENERGY = 4,
+  ODK_XTERM_JOINT_POS_LIMITS = 5, ODK_XTERM_TERMINATION = 6, ODK_XTERM_POSE = 7, ODK_XTERM_FEET_SLIP = 8, ODK_XTERM_FEET_CLEARANCE = 9,
+  ODK_XTERM_FEET_HEIGHT = 10, ODK_XTERM_FEET_AIR_TIME = 11
+};
+typedef struct {
+  float scale[ODK_NXTERM];          /* by enum odk_xterm; 0 = off */
+  float base_height_target;         /* BASE_HEIGHT */
+  float max_foot_height;            /* FEET_CLEARANCE, FEET_HEIGHT */
+  float air_time_range[2];          /* FEET_AIR_TIME: threshold_min, threshold_max */
+  float soft_joint_pos_limit_factor;/* JOINT_POS_LIMITS */
+  float pose_weight[16];            /* POSE: one per actuator */
+} odk_reward_terms;
+/* Sets the terms (copied synchronously into a device buffer the batch owns).  NULL or all scales 0: off -- the step then computes
+ * exactly what it computes without this call.  A parameter of an enabled term that is not finite is ODK_ERR_INVALID.  The kernels
+ * receive the buffer's pointer while some term is on: a graph captured then reads the buffer's contents at every replay, so later
+ * calls that change scales or parameters (or set every scale to 0) are followed; a graph captured while all terms were off stays off. */
+int odk_batch_set_reward_terms(odk_batch* b, const odk_reward_terms* terms);
+/* Where every step writes the library metrics while some term is on: dev [nenv, ODK_NXTERM] (column = enum odk_xterm; 0 for a term
+ * that is off), or NULL (not written).  odk_reset writes zeros there.  Caller-owned, like odk_batch_bind_commands' buffer. */
+int odk_batch_bind_reward_metrics(odk_batch* b, float* dev);
+
 /* Velocity-tracking accumulator: one launch per evaluation step, after odk_step, graph-capturable.  For every env whose
  * acc[e][ODK_TRACK_ENDED] is 0 (its first episode: the Evaluator's `active`) it adds 1 to STEPS and the step's reward to REWARD; on
  * a done step it adds 1 to FALLS when truncation is 0 and sets ENDED; otherwise (a velocity sample: the observation of a done step is

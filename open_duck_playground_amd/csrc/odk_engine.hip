@@ -127,6 +127,14 @@ using ShapeD = Shape<19, 18, 16, 12, 13, 135, 171, 72, 12, 18, false, 6, true>; 
 #endif
 #define ODK_SHAPES(X) X(0, ShapeA) X(1, ShapeB) X(2, ShapeC) X(3, ShapeD) ODK_USER_SHAPES(X)
 
+// Device copy of odk_reward_terms, filled by the host: soft joint limits and the robot's global_linvel sensor address resolved there
+struct XTerms {
+  float scale[ODK_NXTERM];
+  float base_height_target, max_foot_height, air_lo, air_hi;
+  int adr_global_linvel, pad[3];
+  float soft_lo[MAXU], soft_hi[MAXU], pose_w[MAXU];
+};
+
 struct KArgs {
   const DevModel* m;
   DevPRM prm;         // by value (232 bytes of kernel arguments): the grid searches read scalar registers, not 20 dependent loads
@@ -144,6 +152,8 @@ struct KArgs {
   EnvCfg cfg;
   const float* cmd;   // [nenv][cmd_stride] bound commands (odk_batch_bind_commands), or null: sampled ones.  (Last, so that the fields
   int cmd_stride;     // above keep their argument offsets.)  A uniform pointer test: the unbound path only gains a scalar branch
+  const XTerms* xt;   // reward-library terms (odk_batch_set_reward_terms), null while every term is off: one uniform pointer test
+  float* xmet;        // [nenv][ODK_NXTERM] library metrics (odk_batch_bind_reward_metrics), or null
 };
 
 // DR buffer layout per env
@@ -398,6 +408,74 @@ __device__ __forceinline__ void write_outputs(const KArgs& a, const float* L, in
   if (a.metrics && lane < ODK_NMETRIC) a.metrics[(size_t)env * ODK_NMETRIC + lane] = metrics[lane];
 }
 
+// Reward-library terms (reference common/rewards.py; include/odk.h odk_xterm): called under the uniform test of a.xt, in the step's
+// epilogue, with every input in LDS (sensors, qpos / qvel, actuator forces, feet site z of the last forward pass) or in registers
+// (contact, air time after += dt, swing peak after this step's max, first_contact bits, termination).  Adds the scaled terms to
+// `total` in term order, after the native seven, and writes their metrics (lane 0 of a live env).
+template <class S, int G>
+__device__ __forceinline__ void reward_library(const KArgs& a, const float* L, const DevModel* mp, const float* contact, const float* air,
+                                               const float* peak, int fc_bits, bool done_env, float& total, int env, bool live, int lane) {
+  using E = EnvL<S>;
+  constexpr int NU = S::NU;
+  constexpr RecLay RL = rec_lay(NU);
+  static_assert(NU <= MAXU, "XTerms holds MAXU actuators");
+  const XTerms* xt = a.xt;
+  const float* SENS = L + S::O_SENS; const float* QPOS = L + S::O_QPOS; const float* QVEL = L + S::O_QVEL;
+  const float* cmd = L + E::O_INFO + RL.CMD;
+  // per-actuator sums: energy, joint_pos_limits, pose (lanes 0..NU-1)
+  float v[3] = {0.0f, 0.0f, 0.0f};
+  if (lane < NU) {
+    const int u = lane;
+    const float jq = QPOS[mp->act_qposadr[u]], jv = QVEL[mp->act_dofadr[u]], af = L[S::O_ACTF + u];
+    v[0] = fabsf(jv) * fabsf(af);
+    v[1] = -fminf(jq - xt->soft_lo[u], 0.0f) + fmaxf(jq - xt->soft_hi[u], 0.0f);
+    const float dp = jq - mp->key_ctrl[u];
+    v[2] = dp * dp * xt->pose_w[u];
+  }
+  gsum_n<G, 3>(v);
+  float r[ODK_NXTERM];
+  const float* gl = SENS + xt->adr_global_linvel;
+  const float* ga = SENS + mp->adr_global_angvel;
+  const float* up = SENS + mp->adr_upvector;
+  r[ODK_XTERM_LIN_VEL_Z] = nan_to_num(gl[2] * gl[2]);
+  r[ODK_XTERM_ANG_VEL_XY] = nan_to_num(ga[0] * ga[0] + ga[1] * ga[1]);
+  r[ODK_XTERM_ORIENTATION] = nan_to_num(up[0] * up[0] + up[1] * up[1]);
+  const float dh = QPOS[2] - xt->base_height_target;
+  r[ODK_XTERM_BASE_HEIGHT] = nan_to_num(dh * dh);
+  r[ODK_XTERM_ENERGY] = nan_to_num(v[0]);
+  r[ODK_XTERM_JOINT_POS_LIMITS] = nan_to_num(v[1]);
+  r[ODK_XTERM_TERMINATION] = done_env ? 1.0f : 0.0f;
+  r[ODK_XTERM_POSE] = nan_to_num(v[2]);
+  const float maxh = xt->max_foot_height, tmin = xt->air_lo, tmax = xt->air_hi;
+  float slip = 0.0f, clear = 0.0f, height = 0.0f, airt = 0.0f;
+#pragma unroll
+  for (int f = 0; f < 2; f++) {
+    const float* fv = SENS + mp->adr_foot_linvel[f];
+    const float fc = ((fc_bits >> f) & 1) ? 1.0f : 0.0f;
+    slip += sqrtf(fv[0] * fv[0] + fv[1] * fv[1] + fv[2] * fv[2]) * contact[f];
+    clear += fabsf(L[S::O_SCR + S::S_MISC + 8 + f] - maxh) * sqrtf(sqrtf(fv[0] * fv[0] + fv[1] * fv[1]));
+    const float he = peak[f] / maxh - 1.0f;
+    height += he * he * fc;
+    airt += fminf((air[f] - tmin) * fc, tmax - tmin);
+  }
+  const float cn = sqrtf(cmd[0] * cmd[0] + cmd[1] * cmd[1] + cmd[2] * cmd[2]);
+  r[ODK_XTERM_FEET_SLIP] = nan_to_num(slip);
+  r[ODK_XTERM_FEET_CLEARANCE] = nan_to_num(clear);
+  r[ODK_XTERM_FEET_HEIGHT] = nan_to_num(height);
+  r[ODK_XTERM_FEET_AIR_TIME] = nan_to_num(airt * (cn > 0.01f ? 1.0f : 0.0f));
+#pragma unroll
+  for (int k = 0; k < ODK_NXTERM; k++) {
+    const float sc = xt->scale[k], t = r[k] * sc;
+    total += t;
+    r[k] = sc > 0 ? t : -t;
+  }
+  if (a.xmet && live && lane == 0) {
+    float* o = a.xmet + (size_t)env * ODK_NXTERM;
+#pragma unroll
+    for (int k = 0; k < ODK_NXTERM; k++) o[k] = r[k];
+  }
+}
+
 // ================================================================================================
 // Joystick.reset (joystick.py:206-321) + Episode/AutoReset wrapper resets
 template <class S, int G, int HF>
@@ -486,6 +564,7 @@ __global__ void __launch_bounds__(64) reset_kernel(KArgs a) {
     for (int k = lane; k < RL.NINFO; k += G) rc[R::INFO + k] = INFO[k];
     float metrics[ODK_NMETRIC] = {0, 0, 0, 0, 0, 0, 0, 0};
     write_outputs<S, G>(a, L, env, 0.0f, 0.0f, 0.0f, metrics, lane);
+    if (a.xmet && lane < ODK_NXTERM) a.xmet[(size_t)env * ODK_NXTERM + lane] = 0.0f;
   }
 }
 
@@ -647,6 +726,11 @@ __global__ void __launch_bounds__(64, STEP_WAVES) step_kernel(KArgs a) {
     air[f] = INFO[RL.AIR + f] + dt;
     peak[f] = fmaxf(INFO[RL.PEAK + f], L[S::O_SCR + S::S_MISC + 8 + f]);
   }
+  int fc_bits = 0;   // first_contact (:430-431) for the reward library, from the air time before its increment is stored below
+  if (a.xt) {
+    const int lc = f2i(INFO[RL.LCON]);
+    for (int f = 0; f < 2; f++) fc_bits |= (INFO[RL.AIR + f] > 0.0f && (contact[f] != 0.0f || ((lc >> f) & 1))) ? 1 << f : 0;
+  }
   ODK_SYNC();
   if (lane < 2) INFO[RL.AIR + lane] = air[lane];
   ODK_SYNC();
@@ -713,6 +797,7 @@ __global__ void __launch_bounds__(64, STEP_WAVES) step_kernel(KArgs a) {
   }
   float total = 0;
   for (int k = 0; k < 7; k++) { rew[k] *= c.reward_scales[k]; total += rew[k]; }
+  if (a.xt) reward_library<S, G>(a, L, mp, contact, air, peak, fc_bits, done_env, total, env, live, lane);
   const float reward = fminf(fmaxf(total * dt, 0.0f), 10000.0f);
   // ---- obs (uses the pre-shift last_act and the post-increment air time; :437)
   const float* NZ = L + E::O_NZ;   // this step's draws 4 .. 49 (drawn above, before the reward block)
@@ -827,7 +912,8 @@ static int fail(int code, const char* fmt, ...) {
 int odk_fail_(int code, const char* msg) { return fail(code, "%s", msg); }   // for odk_learner.hip
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) return fail(ODK_ERR_HIP, "%s: %s", #x, hipGetErrorString(_e)); } while (0)
 
-struct odk_model { DevModel h; int shape; std::vector<float> hfield; };  // shape: 0 = A, 1 = B, 2 = C (physics only); hfield: [nrow][ncol] in [0, 1]
+struct odk_model { DevModel h; int shape; std::vector<float> hfield; int adr_global_linvel = -1; };  // shape: 0 = A, 1 = B, 2 = C (physics only); hfield: [nrow][ncol] in [0, 1];
+                                                                                                  // adr_global_linvel: the imu's global_linvel sensor (reward library), -1: none
 
 struct odk_batch {
   odk_model model;
@@ -840,6 +926,8 @@ struct odk_batch {
   static constexpr size_t ODK_TIMING_EVENT_PAIRS = 1024;
   int timing = 0; size_t timing_count = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> events; size_t ev_used = 0;   // timing: 0 off, n: every n-th launch
   const float* d_cmd = nullptr; int cmd_stride = 0;   // odk_batch_bind_commands (caller-owned device rows), null: sampled commands
+  XTerms* d_xt = nullptr; bool xt_on = false;         // odk_batch_set_reward_terms: the batch's device copy; passed to the kernels while some term is on
+  float* d_xmet = nullptr;                             // odk_batch_bind_reward_metrics (caller-owned)
 };
 
 extern "C" const char* odk_last_error(void) { return g_err.c_str(); }
@@ -1497,6 +1585,8 @@ extern "C" int odk_model_load(const void* blob, uint64_t len, odk_model** out) {
   B.I("k_adr", adr, 7);
   m.adr_gyro = adr[0]; m.adr_local_linvel = adr[1]; m.adr_accelerometer = adr[2]; m.adr_upvector = adr[3]; m.adr_global_angvel = adr[4];
   m.adr_foot_linvel[0] = adr[5]; m.adr_foot_linvel[1] = adr[6];
+  { const bool was_ok = B.ok; const std::string miss = B.missing; int g[1] = {-1};
+    B.I("k_adr_global_linvel", g, 1); mo->adr_global_linvel = g[0]; B.ok = was_ok; B.missing = miss; }   // optional: blobs written before the reward library have none
   int nsd[1]; B.I("nsensordata", nsd, 1);
   if (!B.ok) { delete mo; return fail(ODK_ERR_INVALID, "odk_model_load: missing %s", B.missing.c_str()); }
   if (nsd[0] != NSENSD) { delete mo; return fail(ODK_ERR_UNSUPPORTED, "sensordata size %d != %d", nsd[0], NSENSD); }
@@ -1721,6 +1811,7 @@ extern "C" int odk_batch_create(const odk_model* m, const odk_env_config* cfg, i
   HIPCHK(hipMalloc(&b->d_recs, (size_t)nenv * b->rec_size * sizeof(float))); HIPCHK(hipMemset(b->d_recs, 0, (size_t)nenv * b->rec_size * sizeof(float)));
   HIPCHK(hipMalloc(&b->d_first, (size_t)nenv * b->frec_size * sizeof(float))); HIPCHK(hipMemset(b->d_first, 0, (size_t)nenv * b->frec_size * sizeof(float)));
   HIPCHK(hipMalloc(&b->d_dbg, (size_t)nenv * b->lds_total * sizeof(float))); HIPCHK(hipMemset(b->d_dbg, 0, (size_t)nenv * b->lds_total * sizeof(float)));
+  HIPCHK(hipMalloc(&b->d_xt, sizeof(XTerms))); HIPCHK(hipMemset(b->d_xt, 0, sizeof(XTerms)));
   if (!m->hfield.empty()) {   // shared by all envs, L2-resident (256 KB)
     HIPCHK(hipMalloc(&b->d_hfield, m->hfield.size() * sizeof(float)));
     HIPCHK(hipMemcpy(b->d_hfield, m->hfield.data(), m->hfield.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -1731,7 +1822,7 @@ extern "C" int odk_batch_create(const odk_model* m, const odk_env_config* cfg, i
 extern "C" void odk_batch_destroy(odk_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
-  for (void* p : {(void*)b->d_model, (void*)b->d_table, (void*)b->d_recs, (void*)b->d_first, (void*)b->d_dr, (void*)b->d_dbg, (void*)b->d_hfield}) (void)hipFree(p);
+  for (void* p : {(void*)b->d_model, (void*)b->d_table, (void*)b->d_recs, (void*)b->d_first, (void*)b->d_dr, (void*)b->d_dbg, (void*)b->d_hfield, (void*)b->d_xt}) (void)hipFree(p);
   for (auto& ev : b->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
   delete b;
 }
@@ -1837,6 +1928,7 @@ static void base_args(odk_batch* b, KArgs& a, const odk_outputs* o) {
   a.dr = b->dr_enabled ? b->d_dr : nullptr; a.nenv = b->nenv; a.n_substeps = b->cfg.n_substeps;
   a.dbg_lds = nullptr;
   a.cmd = b->d_cmd; a.cmd_stride = b->cmd_stride;
+  a.xt = b->xt_on ? b->d_xt : nullptr; a.xmet = b->xt_on ? b->d_xmet : nullptr;
   if (o) { a.obs = o->obs_dev; a.priv = o->priv_dev; a.reward = o->reward_dev; a.done = o->done_dev; a.trunc = o->truncation_dev; a.metrics = o->metrics_dev; }
   to_dev_cfg(b->cfg, a.cfg, b->model.h.nu);
 }
@@ -1893,6 +1985,56 @@ extern "C" int odk_batch_bind_commands(odk_batch* b, const float* cmd_dev, int r
   if (!b) return fail(ODK_ERR_INVALID, "null batch");
   if (cmd_dev && row_stride < 7) return fail(ODK_ERR_INVALID, "command rows hold 7 floats: row_stride %d < 7", row_stride);
   b->d_cmd = cmd_dev; b->cmd_stride = cmd_dev ? row_stride : 0;
+  return ODK_OK;
+}
+
+extern "C" int odk_batch_set_reward_terms(odk_batch* b, const odk_reward_terms* t) {
+  if (!b) return fail(ODK_ERR_INVALID, "null batch");
+  static const char* const names[ODK_NXTERM] = {"lin_vel_z", "ang_vel_xy", "orientation", "base_height", "energy", "joint_pos_limits", "termination",
+                                                "pose", "feet_slip", "feet_clearance", "feet_height", "feet_air_time"};
+  XTerms h;
+  memset(&h, 0, sizeof(h));
+  bool on = false;
+  if (t) for (int k = 0; k < ODK_NXTERM; k++) {
+    if (!std::isfinite(t->scale[k])) return fail(ODK_ERR_INVALID, "odk_batch_set_reward_terms: scale of %s is not finite", names[k]);
+    on = on || t->scale[k] != 0.0f;
+  }
+  if (on) {
+    const DevModel& m = b->model.h;
+    auto is_on = [&](int k) { return t->scale[k] != 0.0f; };
+    auto need = [&](int k, const char* what, float v) { return !is_on(k) || std::isfinite(v) ? 0 : fail(ODK_ERR_INVALID, "odk_batch_set_reward_terms: %s needs a finite %s", names[k], what); };
+    if (int rc = need(ODK_XTERM_BASE_HEIGHT, "base_height_target", t->base_height_target)) return rc;
+    if (int rc = need(ODK_XTERM_FEET_CLEARANCE, "max_foot_height", t->max_foot_height)) return rc;
+    if (int rc = need(ODK_XTERM_FEET_HEIGHT, "max_foot_height", t->max_foot_height)) return rc;
+    if (int rc = need(ODK_XTERM_FEET_AIR_TIME, "air_time_range[0]", t->air_time_range[0])) return rc;
+    if (int rc = need(ODK_XTERM_FEET_AIR_TIME, "air_time_range[1]", t->air_time_range[1])) return rc;
+    if (int rc = need(ODK_XTERM_JOINT_POS_LIMITS, "soft_joint_pos_limit_factor", t->soft_joint_pos_limit_factor)) return rc;
+    for (int u = 0; u < m.nu; u++) if (int rc = need(ODK_XTERM_POSE, "pose_weight per actuator", t->pose_weight[u])) return rc;
+    if (is_on(ODK_XTERM_LIN_VEL_Z) && b->model.adr_global_linvel < 0)
+      return fail(ODK_ERR_UNSUPPORTED, "odk_batch_set_reward_terms: lin_vel_z reads the imu's global_linvel sensor, which this model does not have");
+    for (int k = 0; k < ODK_NXTERM; k++) h.scale[k] = t->scale[k];
+    h.base_height_target = t->base_height_target; h.max_foot_height = t->max_foot_height;
+    h.air_lo = t->air_time_range[0]; h.air_hi = t->air_time_range[1];
+    h.adr_global_linvel = b->model.adr_global_linvel >= 0 ? b->model.adr_global_linvel : 0;
+    for (int u = 0; u < m.nu; u++) {   // soft limits of the actuated joints (joystick.py:135-139), formed in double
+      int j = -1;
+      for (int k = 0; k < m.nj; k++) if (m.jnt_qposadr[k] == m.act_qposadr[u]) j = k;
+      const double lo = j >= 0 ? m.jnt_range[j][0] : 0.0, hi = j >= 0 ? m.jnt_range[j][1] : 0.0;
+      const double c = 0.5 * (lo + hi), r = hi - lo, f = t->soft_joint_pos_limit_factor;
+      h.soft_lo[u] = (float)(c - 0.5 * r * f); h.soft_hi[u] = (float)(c + 0.5 * r * f);
+      h.pose_w[u] = t->pose_weight[u];
+    }
+  }
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipDeviceSynchronize());   // no step in flight reads the buffer while it changes
+  HIPCHK(hipMemcpy(b->d_xt, &h, sizeof(h), hipMemcpyHostToDevice));
+  b->xt_on = on;
+  return ODK_OK;
+}
+
+extern "C" int odk_batch_bind_reward_metrics(odk_batch* b, float* dev) {
+  if (!b) return fail(ODK_ERR_INVALID, "null batch");
+  b->d_xmet = dev;
   return ODK_OK;
 }
 

@@ -24,6 +24,12 @@ ADAM_ACC_FLOATS = 2 + 1024   # ODK_ADAM_ACC_FLOATS (include/odk.h)
 METRIC_NAMES = ("reward/tracking_lin_vel", "reward/tracking_ang_vel", "cost/torques", "cost/action_rate", "cost/stand_still",
                 "reward/alive", "reward/imitation", "swing_peak")
 
+# reward-library terms of the step kernel (include/odk.h odk_xterm): scale keys of reward_config.scales, in column order of Batch.xmetrics;
+# each is the function of the same name in reference playground/common/rewards.py (cost_* / reward_*)
+XTERM_NAMES = ("lin_vel_z", "ang_vel_xy", "orientation", "base_height", "energy", "joint_pos_limits", "termination", "pose", "feet_slip",
+               "feet_clearance", "feet_height", "feet_air_time")
+NXTERM = len(XTERM_NAMES)
+
 PARAM_BODY_MASS, PARAM_BODY_IPOS_TORSO, PARAM_DOF_FRICTIONLOSS, PARAM_DOF_ARMATURE, PARAM_QPOS0, PARAM_KP = range(6)
 
 
@@ -45,6 +51,12 @@ class EnvConfig(C.Structure):
 class Outputs(C.Structure):
     _fields_ = [("obs_dev", C.c_void_p), ("priv_dev", C.c_void_p), ("reward_dev", C.c_void_p), ("done_dev", C.c_void_p),
                 ("truncation_dev", C.c_void_p), ("metrics_dev", C.c_void_p)]
+
+
+class RewardTerms(C.Structure):
+    """odk_reward_terms (include/odk.h): one scale per XTERM_NAMES entry (0 = off) and the terms' parameters."""
+    _fields_ = [("scale", C.c_float * NXTERM), ("base_height_target", C.c_float), ("max_foot_height", C.c_float),
+                ("air_time_range", C.c_float * 2), ("soft_joint_pos_limit_factor", C.c_float), ("pose_weight", C.c_float * 16)]
 
 
 class MlpDesc(C.Structure):
@@ -138,6 +150,8 @@ def load_library() -> C.CDLL:
     L.odk_step.argtypes = [P, P, C.POINTER(Outputs), P]
     L.odk_physics_step.argtypes = [P, P, C.c_int, P]
     L.odk_batch_bind_commands.argtypes = [P, P, C.c_int]
+    L.odk_batch_set_reward_terms.argtypes = [P, C.POINTER(RewardTerms)]
+    L.odk_batch_bind_reward_metrics.argtypes = [P, P]
     L.odk_tracking_accumulate.argtypes = [P, P, P, P, P, P, P]
     L.odk_batch_get_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_set_state.argtypes = [P, FP, FP, FP]
@@ -182,7 +196,7 @@ EXPORTED_SYMBOLS = (
     "odk_last_error", "odk_default_config", "odk_default_config_standing", "odk_obs_sizes", "odk_model_load", "odk_model_free", "odk_model_dims", "odk_model_obs_sizes", "odk_batch_lanes", "odk_model_reduced",
     "odk_model_env_lds_floats", "odk_batch_create",
     "odk_batch_destroy", "odk_batch_set_config", "odk_batch_set_param", "odk_reset", "odk_step", "odk_physics_step",
-    "odk_batch_bind_commands", "odk_tracking_accumulate",
+    "odk_batch_bind_commands", "odk_batch_set_reward_terms", "odk_batch_bind_reward_metrics", "odk_tracking_accumulate",
     "odk_batch_get_state", "odk_batch_set_state", "odk_batch_get_debug", "odk_set_debug_dump", "odk_batch_lds_size",
     "odk_batch_get_lds", "odk_lds_offset", "odk_batch_record_size", "odk_batch_get_records", "odk_batch_set_records", "odk_batch_timing", "odk_gae", "odk_ppo_head",
     "odk_policy_sample", "odk_adam_clip", "odk_silu_bwd_colsum", "odk_colsum_partial", "odk_colsum_finalize", "odk_gather_rows", "odk_dw_gemm",
@@ -815,6 +829,8 @@ class Batch:
         self._outs = Outputs(self.obs.data_ptr(), self.priv.data_ptr(), self.reward.data_ptr(), self.done.data_ptr(),
                              self.truncation.data_ptr(), self.metrics.data_ptr())
         self.commands = None         # the tensor bound by bind_commands (kept alive while bound)
+        self.xmetrics = None         # [nenv, NXTERM] reward-library metrics, allocated by the first set_reward_terms that turns a term on
+        self.reward_terms_on = False
         self.generation = 0          # advanced by every call that rewrites the per-env records (reset / step / set_records): `State.info` checks it
 
     # -- streams: calls are ordered on torch's current stream
@@ -850,6 +866,17 @@ class Batch:
         check_commands(cmd, self.nenv, self.device)
         _chk(self.L.odk_batch_bind_commands(self._b, C.c_void_p(cmd.data_ptr()), NCOMMAND))
         self.commands = cmd
+
+    def set_reward_terms(self, terms: Optional[RewardTerms]):
+        """Reward-library terms of the step kernel (`odk_batch_set_reward_terms`): None or all scales 0 turns them off.  While some
+        term is on every step writes `xmetrics` ([nenv, NXTERM], column = XTERM_NAMES index, 0 for a term that is off).  Synchronous;
+        a graph captured while a term was on follows later calls."""
+        on = terms is not None and any(float(terms.scale[i]) != 0.0 for i in range(NXTERM))
+        if on and self.xmetrics is None:
+            self.xmetrics = self.torch.zeros(self.nenv, NXTERM, dtype=self.torch.float32, device=self.torch.device("cuda", self.device))
+            _chk(self.L.odk_batch_bind_reward_metrics(self._b, C.c_void_p(self.xmetrics.data_ptr())))
+        _chk(self.L.odk_batch_set_reward_terms(self._b, C.byref(terms) if terms is not None else None))
+        self.reward_terms_on = on
 
     def tracking_accumulate(self, acc):
         """One `odk_tracking_accumulate` launch over this step's outputs into `acc` ([nenv, TRACK_NACC] float32, zeroed before

@@ -112,6 +112,62 @@ def to_engine_config(cfg: ConfigDict, autoreset: bool = True, lanes_per_env: int
     return c
 
 
+LIBRARY_TERMS = engine.XTERM_NAMES
+# parameters of the library terms: keys of reward_config (soft_joint_pos_limit_factor is a top-level key, joystick.py:57); no defaults
+# are invented except the one the reference's function signature carries (reward_feet_air_time's thresholds 0.1, 0.5)
+REWARD_PARAMS = ("base_height_target", "max_foot_height", "air_time_range", "pose_weights", "soft_joint_pos_limit_factor")
+AIR_TIME_RANGE_DEFAULT = (0.1, 0.5)
+
+
+def active_reward_terms(cfg: ConfigDict, reward_slots=REWARD_SLOTS):
+    """The library terms a config turns on: keys of reward_config.scales with a non-zero scale that are library names and not one of
+    the env's native slots (those keep their native meaning, e.g. Standing's `orientation`).  Other keys are ignored, as in the reference."""
+    s = cfg.reward_config.scales
+    native = {k for k in reward_slots if k is not None}
+    return [k for k in LIBRARY_TERMS if k not in native and float(s.get(k, 0.0)) != 0.0]
+
+
+def to_reward_terms(cfg: ConfigDict, nu: int, reward_slots=REWARD_SLOTS) -> Optional[engine.RewardTerms]:
+    """reference config -> odk_reward_terms (include/odk.h), or None when no library term is on.  ValueError names a parameter that an
+    enabled term needs and the config does not carry (base_height_target, max_foot_height, pose_weights with one weight per actuator,
+    soft_joint_pos_limit_factor)."""
+    active = active_reward_terms(cfg, reward_slots)
+    if not active:
+        return None
+    rc, s = cfg.reward_config, cfg.reward_config.scales
+    t = engine.RewardTerms()
+    for i, k in enumerate(LIBRARY_TERMS):
+        t.scale[i] = float(s[k]) if k in active else 0.0
+
+    def need(key, *terms, where=rc):
+        on = [k for k in terms if k in active]
+        if on and where.get(key, None) is None:
+            raise ValueError(f"reward term {on[0]} is on but the config has no {key}")
+        return bool(on)
+
+    if need("base_height_target", "base_height"):
+        t.base_height_target = float(rc.base_height_target)
+    if need("max_foot_height", "feet_clearance", "feet_height"):
+        t.max_foot_height = float(rc.max_foot_height)
+    if "feet_air_time" in active:
+        lo, hi = rc.get("air_time_range", None) or AIR_TIME_RANGE_DEFAULT
+        t.air_time_range[0], t.air_time_range[1] = float(lo), float(hi)
+    if need("soft_joint_pos_limit_factor", "joint_pos_limits", where=cfg):
+        t.soft_joint_pos_limit_factor = float(cfg.soft_joint_pos_limit_factor)
+    if need("pose_weights", "pose"):
+        w = [float(x) for x in rc.pose_weights]
+        if len(w) != int(nu):
+            raise ValueError(f"reward term pose: pose_weights has {len(w)} entries, the robot has {nu} actuators")
+        for i, x in enumerate(w):
+            t.pose_weight[i] = x
+    return t
+
+
+def reward_metric_name(key: str, scale: float) -> str:
+    """State.metrics key of a library term: reward/<k> or cost/<k> by the sign of its scale."""
+    return ("reward/" if float(scale) > 0 else "cost/") + key
+
+
 @dataclass
 class State:
     """mjx_env.State counterpart (reference joystick.py:321): tensors are views of the engine's output buffers,
@@ -238,6 +294,10 @@ class Joystick:
         self.num_envs = int(num_envs)
         self._env_id_offset = int(env_id_offset)
         self._batch = engine.Batch(self._model, self.num_envs, self._engine_config(autoreset, lanes_per_env), device=device)
+        self._batch.set_reward_terms(to_reward_terms(self._config, self._model.nu, self._reward_slots()))
+        scales = self._config.reward_config.scales
+        # State.metrics names of the Batch.xmetrics columns (None: the term is off)
+        self.XMETRIC_NAMES = tuple(reward_metric_name(k, scales[k]) if k in self.reward_terms() else None for k in LIBRARY_TERMS)
 
     def _default_config(self) -> ConfigDict:
         return default_config()
@@ -245,6 +305,13 @@ class Joystick:
     def _engine_config(self, autoreset: bool, lanes_per_env: int) -> engine.EnvConfig:
         return to_engine_config(self._config, autoreset, lanes_per_env, use_imitation=USE_IMITATION_REWARD and self._robot.is_open_duck,
                                 joints_order_no_head=self._robot.joints_order_no_head)
+
+    def _reward_slots(self):
+        return REWARD_SLOTS
+
+    def reward_terms(self):
+        """The reward-library terms this env computes (keys of reward_config.scales; include/odk.h odk_xterm), in column order."""
+        return active_reward_terms(self._config, self._reward_slots())
 
     # ---- reference accessors (base.py:277-291, MjxEnv)
     @property
@@ -285,6 +352,8 @@ class Joystick:
     def _state(self) -> State:
         b = self._batch
         metrics = {name: b.metrics[:, i] for i, name in enumerate(self.METRIC_NAMES) if name is not None}
+        if b.reward_terms_on:
+            metrics.update({name: b.xmetrics[:, i] for i, name in enumerate(self.XMETRIC_NAMES) if name is not None})
         return State(data=b, obs={"state": b.obs, "privileged_state": b.priv}, reward=b.reward, done=b.done, metrics=metrics,
                      info=_Info(b, b.truncation))
 

@@ -40,6 +40,8 @@ class Evaluator:
             # the engine hands the metrics over as one [N, K] tensor: 4 launches per step for the bookkeeping instead of
             # 2 per metric (the evaluation step is launch-bound)
             a["matrix"].addcmul_(st.data.metrics, a["active"].unsqueeze(1))
+            if a["xmatrix"] is not None:     # the reward-library terms' columns (Batch.xmetrics): one more launch
+                a["xmatrix"].addcmul_(st.data.xmetrics, a["active"].unsqueeze(1))
             a["sums"]["reward"].addcmul_(st.reward, a["active"])
         else:
             a["sums"]["reward"] += st.reward * a["active"]
@@ -62,13 +64,21 @@ class Evaluator:
             if torch.is_tensor(m) and m.dim() == 2 and names is not None and len(names) == m.shape[1]:
                 matrix = torch.zeros_like(m)     # column i accumulates METRIC_NAMES[i]; the dict entries are views of it
                 sums = {"reward": z(), **{nm: matrix[:, i] for i, nm in enumerate(names) if nm is not None}}
+                xm = getattr(self._state.data, "xmetrics", None)
+                xnames = getattr(self.env, "XMETRIC_NAMES", None)
+                xmatrix = None
+                if getattr(self._state.data, "reward_terms_on", False) and torch.is_tensor(xm) and xnames is not None:
+                    xmatrix = torch.zeros_like(xm)   # the same for the enabled reward-library terms (XMETRIC_NAMES)
+                    sums.update({nm: xmatrix[:, i] for i, nm in enumerate(xnames) if nm is not None})
             else:
-                matrix, sums = None, {"reward": z(), **{k: z() for k in self._state.metrics}}
-            self._acc = dict(active=z(), steps=z(), sums=sums, matrix=matrix)
+                matrix, xmatrix, sums = None, None, {"reward": z(), **{k: z() for k in self._state.metrics}}
+            self._acc = dict(active=z(), steps=z(), sums=sums, matrix=matrix, xmatrix=xmatrix)
         a = self._acc
         a["active"].fill_(1.0); a["steps"].zero_()
         if a["matrix"] is not None:
             a["matrix"].zero_(); a["sums"]["reward"].zero_()
+            if a["xmatrix"] is not None:
+                a["xmatrix"].zero_()
         else:
             for v in a["sums"].values():
                 v.zero_()

@@ -13,6 +13,41 @@ from datetime import datetime
 import numpy as np
 
 
+def _parse_kv(item: str, flag: str):
+    if "=" not in item:
+        raise ValueError(f"{flag} {item!r}: expected KEY=VALUE")
+    k, v = item.split("=", 1)
+    return k.strip(), v.strip()
+
+
+def reward_overrides(env: str, scales=None, params=None) -> dict:
+    """--reward_scale KEY=VALUE / --reward_param KEY=VALUE -> config overrides (`reward_config.scales.KEY`, `reward_config.KEY`;
+    soft_joint_pos_limit_factor is a top-level key).  A scale key must be one of the env's native reward slots or a reward-library term
+    (joystick.LIBRARY_TERMS); a parameter key one of joystick.REWARD_PARAMS: anything else is a ValueError (a typo on the command line
+    would otherwise train silently without the term).  air_time_range and pose_weights take comma-separated numbers."""
+    from . import joystick, standing
+    native = {"joystick": joystick.REWARD_SLOTS, "standing": standing.REWARD_SLOTS}.get(env, joystick.REWARD_SLOTS)
+    known = [k for k in native if k is not None] + [k for k in joystick.LIBRARY_TERMS if k not in native]
+    out = {}
+    for item in scales or ():
+        k, v = _parse_kv(item, "--reward_scale")
+        if k not in known:
+            raise ValueError(f"--reward_scale {k}: unknown reward key for env {env} (known: {', '.join(known)})")
+        out[f"reward_config.scales.{k}"] = float(v)
+    for item in params or ():
+        k, v = _parse_kv(item, "--reward_param")
+        if k not in joystick.REWARD_PARAMS:
+            raise ValueError(f"--reward_param {k}: unknown reward parameter (known: {', '.join(joystick.REWARD_PARAMS)})")
+        if k in ("air_time_range", "pose_weights"):
+            val = [float(x) for x in v.split(",") if x.strip()]
+            if k == "air_time_range" and len(val) != 2:
+                raise ValueError(f"--reward_param air_time_range={v}: expected two numbers MIN,MAX")
+        else:
+            val = float(v)
+        out[k if k == "soft_joint_pos_limit_factor" else f"reward_config.{k}"] = val
+    return out
+
+
 class OpenDuckMiniV2Runner:
     def __init__(self, args):
         import torch
@@ -35,6 +70,7 @@ class OpenDuckMiniV2Runner:
         overrides = {"hfield_up_normals_only": True} if getattr(args, "hfield_up_normals_only", False) else None
         if getattr(args, "cone", None):
             overrides = dict(overrides or {}, cone=args.cone)
+        overrides = dict(overrides or {}, **reward_overrides(args.env, getattr(args, "reward_scale", None), getattr(args, "reward_param", None))) or None
         extra = {}
         if getattr(args, "xml", None):      # a robot of one's own (reference README.md:74-85 "Adding a new robot"): its MJCF instead of a shipped task
             extra["xml_path"] = args.xml
@@ -84,7 +120,7 @@ class OpenDuckMiniV2Runner:
             dist.destroy_process_group()
 
 
-def main():
+def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(description="Open Duck Mini Runner Script")
     parser.add_argument("--output_dir", type=str, default="checkpoints", help="Where to save the checkpoints")
     parser.add_argument("--num_timesteps", type=int, default=150000000)
@@ -104,7 +140,17 @@ def main():
                         help="train a robot of your own: path of its MJCF (additive; the reference's recipe is a copy of this package per robot, README.md:74-85). "
                              "The XML carries the names constants.py looks up (sites imu / left_foot / right_foot, geoms left_foot_bottom_tpu / right_foot_bottom_tpu / "
                              "floor, the 15 sensors, keyframe home); its model shape needs a compiled kernel: tools/new_shape.py <xml> prints the lines to add")
-    args = parser.parse_args()
+    parser.add_argument("--reward_scale", action="append", default=[], metavar="KEY=VALUE",
+                        help="repeatable: set reward_config.scales[KEY]; a native slot of the env or a reward-library term (README: reward library), "
+                             "e.g. feet_air_time=2.0; a non-zero scale turns a library term on")
+    parser.add_argument("--reward_param", action="append", default=[], metavar="KEY=VALUE",
+                        help="repeatable: a parameter of the library terms: base_height_target, max_foot_height, air_time_range=MIN,MAX, "
+                             "pose_weights=W1,...,Wnu, soft_joint_pos_limit_factor")
+    return parser
+
+
+def main():
+    args = build_parser().parse_args()
     runner = OpenDuckMiniV2Runner(args)
     try:
         runner.train()

@@ -42,6 +42,9 @@ class Standing(Joystick):
     def _default_config(self) -> ConfigDict:
         return default_config()
 
+    def _reward_slots(self):
+        return REWARD_SLOTS   # `orientation` is native here: the library's copy of it is the Joystick's
+
     def _engine_config(self, autoreset: bool, lanes_per_env: int) -> engine.EnvConfig:
         return to_engine_config(self._config, autoreset, lanes_per_env, standing=True, reward_slots=REWARD_SLOTS,
                                 use_imitation=USE_IMITATION_REWARD, use_motor_speed_limits=False)

@@ -338,4 +338,6 @@ def build_kernel_tables(a: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
     sadr = lambda n: int(a["sensor_adr"][names_sensor.index(n)])
     out["k_adr"] = I([sadr("gyro"), sadr("local_linvel"), sadr("accelerometer"), sadr("upvector"), sadr("global_angvel"),
                       sadr("left_foot_global_linvel"), sadr("right_foot_global_linvel")])
+    # the imu's global_linvel sensor: read by the reward library's lin_vel_z only (-1: the model has none)
+    out["k_adr_global_linvel"] = I([sadr("global_linvel") if "global_linvel" in names_sensor else -1])
     return out
