@@ -126,6 +126,11 @@ int odk_model_obs_sizes(const odk_model* m, int env_kind, int* nobs, int* npriv)
  * tree layout and of its virtual (Hessian) tree, and per reduced dof the main dof and the twin dof (-1: none); arrays of
  * >= 32 ints, any pointer may be NULL.  Host-only (no GPU needed). */
 int odk_model_reduced(const odk_model* m, int* paired, int* nvr, int* nMr, int* nHr, int* red_main, int* red_twin);
+/* Body-to-lane layout of the kinematics / inertia sweeps at `lanes_per_env` (32 or 64) lanes per env: out[lane] = the body id
+ * that lane computes, -1 for a lane without a body, for the first min(n, lanes_per_env) lanes.  Every serial body chain sits
+ * in consecutive lanes of one 16-lane row, in chain order (its scans are DPP row shifts); a model without such a layout is
+ * refused by odk_model_load.  Host-only (no GPU needed). */
+int odk_model_body_lanes(const odk_model* m, int lanes_per_env, int* out, int n);
 /* floats of LDS one env occupies in the fused step kernel (8 single-wave workgroups of two envs per CU need <= 2560) */
 int odk_model_env_lds_floats(const odk_model* m);
 

@@ -1082,8 +1082,33 @@ void sparse_layout(const int* parent, int n, SparseLayout& L) {
   }
 }
 }  // namespace
-// DevModel::body_st: what forward_env's sweeps need of each body, flattened (index MAXB: the record of a lane without a body)
-static void fill_body_st(DevModel& m) {
+// Body-to-lane layout of forward_env's sweeps for G lanes per env: lane_body[lane] = body id, -1 for a lane without a body.
+// The chain scans shift by 1, 2 and 4 lanes with DPP row_shr / row_shl, which never cross a 16-lane row, so every serial
+// chain (body_is_path, from its body_path_head on) takes consecutive lanes of ONE row, in chain order: upmask / pathmask
+// (offsets along the chain) keep their meaning.  Greedy in body order: a chain starts at the first run of free lanes that
+// does not cross a row, every other body takes the lowest free lane.  false: no such layout.
+static bool build_body_lanes(const DevModel& m, int G, int* lane_body) {
+  for (int l = 0; l < 64; l++) lane_body[l] = -1;
+  for (int b = 0; b < m.nb; b++) {
+    if (m.body_is_path[b] && !m.body_path_head[b]) continue;   // placed with its chain's head
+    int len = 1;
+    if (m.body_is_path[b])
+      while (b + len < m.nb && m.body_is_path[b + len] && !m.body_path_head[b + len]) len++;
+    int at = -1;
+    for (int s = 0; s + len <= G && at < 0; s++) {
+      if ((s >> 4) != ((s + len - 1) >> 4)) continue;
+      bool free = true;
+      for (int k = 0; k < len; k++) free = free && lane_body[s + k] < 0;
+      if (free) at = s;
+    }
+    if (at < 0) return false;
+    for (int k = 0; k < len; k++) lane_body[at + k] = b + k;
+  }
+  return true;
+}
+// DevModel::body_st: what forward_env's sweeps need of each body, flattened, in lane order for G = 32 and G = 64 (a lane
+// without a body gets a record with level -2 and body -1).  false: a body-to-lane layout does not exist.
+static bool fill_body_st(DevModel& m) {
   auto fill = [&](BodySt& b, int bi, bool in) {
     memset(&b, 0, sizeof(b));
     b.level = in ? m.body_level[bi] : -2;
@@ -1107,8 +1132,16 @@ static void fill_body_st(DevModel& m) {
     for (int c = 0; c < 4; c++) b.quat[c] = m.body_quat[bi][c];
     for (int c = 0; c < 6; c++) b.inertia[c] = m.body_inertia[bi][c];
   };
-  for (int bi = 0; bi < m.nb; bi++) fill(m.body_st[bi], bi, true);
-  fill(m.body_st[MAXB], 0, false);
+  for (int g = 0; g < 2; g++) {
+    int lane_body[64];
+    if (!build_body_lanes(m, g ? 64 : 32, lane_body)) return false;
+    for (int l = 0; l < 64; l++) {
+      const int bi = lane_body[l];
+      fill(m.body_st[g][l], bi >= 0 ? bi : 0, bi >= 0);
+      m.body_st[g][l].body = bi;
+    }
+  }
+  return true;
 }
 
 static bool build_reduced_tables(DevModel& m) {
@@ -1614,7 +1647,9 @@ extern "C" int odk_model_load(const void* blob, uint64_t len, odk_model** out) {
     }
   }
   if (!build_reduced_tables(m)) { delete mo; return fail(ODK_ERR_UNSUPPORTED, "dof tree is not a floating base with up to three serial chains of <= 5 (twin-merged) dofs"); }
-  fill_body_st(m);
+  if (!fill_body_st(m)) {
+    delete mo; return fail(ODK_ERR_UNSUPPORTED, "no body-to-lane layout: every serial body chain must fit in one 16-lane row and all %d bodies in 32 lanes", m.nb);
+  }
   int dt_max = 0, dv_max = 0;
   for (int d = 0; d < m.nv; d++) { dt_max = m.dof_depth[d] > dt_max ? m.dof_depth[d] : dt_max; dv_max = m.vdof_depth[d] > dv_max ? m.vdof_depth[d] : dv_max; }
   mo->shape = -1;
@@ -1753,6 +1788,11 @@ extern "C" int odk_model_reduced(const odk_model* m, int* paired, int* nvr, int*
   if (!m) return fail(ODK_ERR_INVALID, "null model");
   if (paired) *paired = m->h.paired; if (nvr) *nvr = m->h.nvr; if (nMr) *nMr = m->h.nMr; if (nHr) *nHr = m->h.nHr;
   for (int r = 0; r < m->h.nvr; r++) { if (red_main) red_main[r] = m->h.red_main[r]; if (red_twin) red_twin[r] = m->h.red_twin[r]; }
+  return ODK_OK;
+}
+extern "C" int odk_model_body_lanes(const odk_model* m, int lanes_per_env, int* out, int n) {
+  if (!m || !out || (lanes_per_env != 32 && lanes_per_env != 64)) return fail(ODK_ERR_INVALID, "odk_model_body_lanes: bad arguments");
+  for (int l = 0; l < n && l < lanes_per_env; l++) out[l] = m->h.body_st[lanes_per_env == 64][l].body;
   return ODK_OK;
 }
 extern "C" int odk_model_env_lds_floats(const odk_model* m) {

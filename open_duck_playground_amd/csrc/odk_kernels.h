@@ -215,6 +215,11 @@ template <int G, class Op> __device__ __forceinline__ float greduce(float v) {
   return v;
 }
 template <int G> __device__ __forceinline__ float gsum(float v) { return greduce<G, OpSum>(v); }
+// Chain scans of forward_env (P1 / P2), step si = 0, 1, 2 shifts by 2^si lanes: row_shr (lane l reads lane l - 2^si) and
+// row_shl (l + 2^si) inside the lane's 16-lane row, 0 from beyond the row's edge (bound_ctrl).  The host's body-to-lane
+// layout keeps every serial body chain inside one row.  Uniform control flow only; si must fold to a constant.
+__device__ __forceinline__ float row_shr(float v, int si) { return si == 0 ? ODK_DPP(v, 0x111, 0xF) : si == 1 ? ODK_DPP(v, 0x112, 0xF) : ODK_DPP(v, 0x114, 0xF); }
+__device__ __forceinline__ float row_shl(float v, int si) { return si == 0 ? ODK_DPP(v, 0x101, 0xF) : si == 1 ? ODK_DPP(v, 0x102, 0xF) : ODK_DPP(v, 0x104, 0xF); }
 // N sums at once (G = 32): the four in-row butterfly stages on the VALU as above, then the two rows are exchanged by
 // ds_swizzle (xor 16 inside each 32-lane group: the LDS crossbar, no memory access and no VALU slot) instead of
 // v_permlane16_swap (~8 cycles of VALU issue each); the N swizzles are in flight together, so their latency is paid once.
@@ -430,9 +435,9 @@ __host__ __device__ inline void compute_statics(LaneSt& st, const DevModel* m, i
   st.d_tkind = (S::PAIRED && st.d_on) ? m->dof_tkind[i] : 0;
   st.d_red = S::PAIRED ? m->dof_red[i] : i;   // column of this dof's motion vector in CDOF / BUF6
 }
-template <class S>
+template <int G>
 __device__ __forceinline__ void load_body(BodySt& b, const DevModel* __restrict__ m, int lane) {
-  b = m->body_st[lane < S::NB ? lane : MAXB];   // one record per body, host-built (DevModel::body_st)
+  b = m->body_st[G == 64][lane];   // the record of the lane's body, host-built body-to-lane layout (DevModel::body_st)
 }
 __device__ __forceinline__ void load_act(ActSt& a, const DevModel* __restrict__ m, int act) {
   const int u = act >= 0 ? act : 0;
@@ -1910,7 +1915,8 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
   ODK_PROF_BEGIN();
 
   BodySt bs;
-  load_body<S>(bs, m, lane);   // issued first: the loads complete under the sin/cos phase
+  load_body<G>(bs, m, lane);   // issued first: the loads complete under the sin/cos phase
+  const int bid = bs.body;     // P1 / P2: lane = body bid (-1: none), chains in consecutive lanes of one row; LDS images by body id
   // ---------------- P0: half-angle sin/cos of every hinge (lane = joint)
   if (st.j_qadr >= 0) {
     float s, c;
@@ -1995,17 +2001,18 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
           qnormalize(q);
         }
 #pragma unroll
-        for (int k = 0; k < 3; k++) XPOS[k * NB + lane] = p[k];
+        for (int k = 0; k < 3; k++) XPOS[k * NB + bid] = p[k];
 #pragma unroll
-        for (int k = 0; k < 4; k++) XQUAT[k * NB + lane] = q[k];
+        for (int k = 0; k < 4; k++) XQUAT[k * NB + bid] = q[k];
 #pragma unroll
-        for (int k = 0; k < 6; k++) { CVEL[k * NB + lane] = cvel[k]; CACC[k * NB + lane] = cacc[k]; }
+        for (int k = 0; k < 6; k++) { CVEL[k * NB + bid] = cvel[k]; CACC[k * NB + bid] = cacc[k]; }
       }
       ODK_SYNC();
     }
     // serial body chains (legs, head): pose, velocity and bias acceleration as three prefix scans over neighbouring
     // lanes (Hillis-Steele from the chain head, 3 cross-lane steps each) instead of one dependent LDS round trip per
-    // tree level.  Every lane runs the shuffles (uniform control flow); only chain bodies use the results.
+    // tree level.  A chain sits in consecutive lanes of one 16-lane row, so each step is a DPP row shift (no LDS trip);
+    // every lane runs them (uniform control flow), only chain bodies use the results.
     {
       const bool isp = bs.is_path != 0, head = bs.path_head != 0;
       // local transform of the body relative to its parent, and the frames in which its joint axes are given
@@ -2033,23 +2040,25 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
         qmul(tq, ppq, tq);
       }
 #pragma unroll
-      for (int si = 0; si < 3; si++) {   // world pose: T[b] <- T[b - 2^si] o T[b]
+      for (int si = 0; si < 3; si++) {   // world pose: T[b] <- T[b - 2^si] o T[b] (composed by every lane, kept by a select)
         float up[3], uq[4];
 #pragma unroll
-        for (int k = 0; k < 3; k++) up[k] = __shfl_up(tp[k], 1 << si, G);
+        for (int k = 0; k < 3; k++) up[k] = row_shr(tp[k], si);
 #pragma unroll
-        for (int k = 0; k < 4; k++) uq[k] = __shfl_up(tq[k], 1 << si, G);
-        if ((bs.upmask >> si) & 1) {
-          float t[3];
-          qrot(t, uq, tp);
-          tp[0] = up[0] + t[0]; tp[1] = up[1] + t[1]; tp[2] = up[2] + t[2];
-          qmul(tq, uq, tq);
-        }
+        for (int k = 0; k < 4; k++) uq[k] = row_shr(tq[k], si);
+        const bool ok = (bs.upmask >> si) & 1;
+        float t[3], nq[4];
+        qrot(t, uq, tp);
+        qmul(nq, uq, tq);
+#pragma unroll
+        for (int k = 0; k < 3; k++) tp[k] = ok ? up[k] + t[k] : tp[k];
+#pragma unroll
+        for (int k = 0; k < 4; k++) tq[k] = ok ? nq[k] : tq[k];
       }
       {   // parent's world orientation: the lane above, except for chain heads (read from LDS above)
         float uq[4];
 #pragma unroll
-        for (int k = 0; k < 4; k++) uq[k] = __shfl_up(tq[k], 1, G);
+        for (int k = 0; k < 4; k++) uq[k] = row_shr(tq[k], 0);
         if (isp && !head) { ppq[0] = uq[0]; ppq[1] = uq[1]; ppq[2] = uq[2]; ppq[3] = uq[3]; }
       }
       // joint twists about the base origin and the body's own velocity / acceleration increments
@@ -2078,19 +2087,19 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
       float cv[6];
 #pragma unroll
       for (int k = 0; k < 6; k++) cv[k] = cinc[k] + pcv[k];   // heads start from their parent's velocity
+      // prefix sums: lane b adds lane b - 2^si's partial sum iff that lane is in b's chain above it (upmask bit si of b).
+      // The select sits on the SOURCE lane -- pathmask bit si of b - 2^si is the same predicate -- so the row shift folds
+      // into the add (v_add_f32_dpp); a lane whose source is not in its chain adds 0, as before.
 #pragma unroll
       for (int si = 0; si < 3; si++) {
-        float u[6];
+        const bool ok = (bs.pathmask >> si) & 1;
 #pragma unroll
-        for (int k = 0; k < 6; k++) u[k] = __shfl_up(cv[k], 1 << si, G);
-        const bool ok = (bs.upmask >> si) & 1;
-#pragma unroll
-        for (int k = 0; k < 6; k++) cv[k] += ok ? u[k] : 0.0f;
+        for (int k = 0; k < 6; k++) cv[k] += row_shr(ok ? cv[k] : 0.0f, si);
       }
       {   // velocity of the parent (= velocity before this body's first joint)
         float u[6];
 #pragma unroll
-        for (int k = 0; k < 6; k++) u[k] = __shfl_up(cv[k], 1, G);
+        for (int k = 0; k < 6; k++) u[k] = row_shr(cv[k], 0);
         if (isp && !head) {
 #pragma unroll
           for (int k = 0; k < 6; k++) pcv[k] = u[k];
@@ -2112,45 +2121,42 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
         }
       }
 #pragma unroll
-      for (int si = 0; si < 3; si++) {
-        float u[6];
+      for (int si = 0; si < 3; si++) {   // (source-side select, as for cvel)
+        const bool ok = (bs.pathmask >> si) & 1;
 #pragma unroll
-        for (int k = 0; k < 6; k++) u[k] = __shfl_up(ca[k], 1 << si, G);
-        const bool ok = (bs.upmask >> si) & 1;
-#pragma unroll
-        for (int k = 0; k < 6; k++) ca[k] += ok ? u[k] : 0.0f;
+        for (int k = 0; k < 6; k++) ca[k] += row_shr(ok ? ca[k] : 0.0f, si);
       }
       if (isp) {
         qnormalize(tq);
 #pragma unroll
-        for (int k = 0; k < 3; k++) { p[k] = tp[k]; XPOS[k * NB + lane] = tp[k]; }
+        for (int k = 0; k < 3; k++) { p[k] = tp[k]; XPOS[k * NB + bid] = tp[k]; }
 #pragma unroll
-        for (int k = 0; k < 4; k++) { q[k] = tq[k]; XQUAT[k * NB + lane] = tq[k]; }
+        for (int k = 0; k < 4; k++) { q[k] = tq[k]; XQUAT[k * NB + bid] = tq[k]; }
 #pragma unroll
-        for (int k = 0; k < 6; k++) { cvel[k] = cv[k]; cacc[k] = ca[k]; CVEL[k * NB + lane] = cv[k]; CACC[k * NB + lane] = ca[k]; }
+        for (int k = 0; k < 6; k++) { cvel[k] = cv[k]; cacc[k] = ca[k]; CVEL[k * NB + bid] = cv[k]; CACC[k * NB + bid] = ca[k]; }
       }
       ODK_SYNC();
     }
     float acc[16];   // cinert (10) | local bias force (6) of this lane's body, then their subtree sums
 #pragma unroll
     for (int k = 0; k < 16; k++) acc[k] = 0.0f;
-    if (lane < NB) {
+    if (bid >= 0) {
       if (bs.level < 0) {
 #pragma unroll
-        for (int k = 0; k < 3; k++) XPOS[k * NB + lane] = p[k];
+        for (int k = 0; k < 3; k++) XPOS[k * NB + bid] = p[k];
 #pragma unroll
-        for (int k = 0; k < 4; k++) XQUAT[k * NB + lane] = q[k];
+        for (int k = 0; k < 4; k++) XQUAT[k * NB + bid] = q[k];
 #pragma unroll
-        for (int k = 0; k < 6; k++) { CVEL[k * NB + lane] = 0; CACC[k * NB + lane] = 0; }
+        for (int k = 0; k < 6; k++) { CVEL[k * NB + bid] = 0; CACC[k * NB + bid] = 0; }
       }
       // cinert about the base origin, local bias force
       float R[9];
       q2mat(R, q);
       float ip[3] = {bs.ipos[0], bs.ipos[1], bs.ipos[2]};
-      {   // (body 1's per-env centre of mass: read by every lane -- a broadcast -- and pinned; as an `if (lane == 1)` the three reads became three blocks under their own exec mask)
+      {   // (body 1's per-env centre of mass: read by every lane -- a broadcast -- and pinned; as an `if (bid == 1)` the three reads became three blocks under their own exec mask)
         const float i0 = L[S::O_IPOS1], i1 = L[S::O_IPOS1 + 1], i2 = L[S::O_IPOS1 + 2];
         asm volatile("" :: "v"(i0), "v"(i1), "v"(i2));
-        ip[0] = lane == 1 ? i0 : ip[0]; ip[1] = lane == 1 ? i1 : ip[1]; ip[2] = lane == 1 ? i2 : ip[2];
+        ip[0] = bid == 1 ? i0 : ip[0]; ip[1] = bid == 1 ? i1 : ip[1]; ip[2] = bid == 1 ? i2 : ip[2];
       }
       float off[3];
       for (int k = 0; k < 3; k++) off[k] = p[k] + R[3 * k] * ip[0] + R[3 * k + 1] * ip[1] + R[3 * k + 2] * ip[2] - ref[k];
@@ -2161,7 +2167,7 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
         for (int j = 0; j < 3; j++) T[3 * i + j] = R[3 * i] * Ib[j] + R[3 * i + 1] * Ib[3 + j] + R[3 * i + 2] * Ib[6 + j];
       for (int i = 0; i < 3; i++)
         for (int j = 0; j < 3; j++) Iw[3 * i + j] = T[3 * i] * R[3 * j] + T[3 * i + 1] * R[3 * j + 1] + T[3 * i + 2] * R[3 * j + 2];
-      const float mb = MASS[lane], o2 = dot3(off, off);
+      const float mb = MASS[bid], o2 = dot3(off, off);
       float ci[10];
       ci[0] = Iw[0] + mb * (o2 - off[0] * off[0]);
       ci[1] = Iw[4] + mb * (o2 - off[1] * off[1]);
@@ -2188,20 +2194,19 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
     ODK_PROF(1);
     // ---------------- P2: composite inertia and subtree bias force.  Serial body chains (legs, head): suffix sums
     // over neighbouring lanes, three cross-lane steps in registers; the few bodies above them: one level per step.
+    // (lane b adds lane b + 2^si's sum iff that lane is in b's chain below it, pathmask bit si of b: the select sits on the
+    // source lane, upmask bit si of b + 2^si, so the DPP row shift folds into the add)
 #pragma unroll
     for (int si = 0; si < 3; si++) {
-      const bool ok = (bs.pathmask >> si) & 1;
-      float t[16];
+      const bool ok = (bs.upmask >> si) & 1;
 #pragma unroll
-      for (int k = 0; k < 16; k++) t[k] = __shfl_down(acc[k], 1 << si, G);
-#pragma unroll
-      for (int k = 0; k < 16; k++) acc[k] += ok ? t[k] : 0.0f;
+      for (int k = 0; k < 16; k++) acc[k] += row_shl(ok ? acc[k] : 0.0f, si);
     }
-    if (lane < NB) {
+    if (bid >= 0) {
 #pragma unroll
-      for (int k = 0; k < 10; k++) CRB[k * NB + lane] = acc[k];
+      for (int k = 0; k < 10; k++) CRB[k * NB + bid] = acc[k];
 #pragma unroll
-      for (int k = 0; k < 6; k++) CFRC[k * NB + lane] = acc[10 + k];
+      for (int k = 0; k < 6; k++) CFRC[k * NB + bid] = acc[10 + k];
     }
     ODK_SYNC();
   }

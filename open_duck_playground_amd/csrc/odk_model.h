@@ -29,13 +29,14 @@ constexpr int MAXSENS = 16;
 constexpr int NCON = 12;     // 3 geom pairs x 4 contacts
 constexpr int NSENSD = 46;
 
-// Per-body constants of the kinematics / inertia sweeps, one record per body (+ one "no body" record at index MAXB for the lanes
-// past the last body), filled on the host (odk_engine.hip fill_body_st): the kernel fetches a lane's record with ONE address
-// computation and no dependent loads (as separate tables the joint-derived fields were three dependent loads deep).
+// Per-body constants of the kinematics / inertia sweeps, one record per LANE of an env (body-to-lane layout: every serial body
+// chain in consecutive lanes of one 16-lane row, so its scans are DPP row shifts; lanes without a body hold a "no body" record),
+// filled on the host (odk_engine.hip fill_body_st): the kernel fetches a lane's record with ONE address computation and no
+// dependent loads (as separate tables the joint-derived fields were three dependent loads deep).
 struct BodySt {
   int level, parent, nchild, child[3], njnt, jd[2], jj[2], jr[2], pathmask, is_path, upmask, path_head;   // jr: CDOF column of the joint's dof (-1: twin, its main dof's column is the same vector)
   float pos[3], quat[4], ipos[3], inertia[6], ax[2][3];
-  int pad;   // 40 dwords
+  int body;   // the lane's body id (its column in the LDS body images), -1: no body.  40 dwords
 };
 
 // Per-lane statics of the step kernels (odk_kernels.h Statics = this + compile-time counts), host-built per lane like the body
@@ -56,7 +57,7 @@ struct LaneSt {
 };
 
 struct DevModel {
-  BodySt body_st[MAXB + 1];
+  BodySt body_st[2][64];   // [G == 64][lane]: the body record of each lane of an env (fill_body_st)
   LaneSt lane_st[64];
   int nq, nv, nu, nb, nj, nM, nH, nfl, nlim, nrow, nsite, nsensor;
   float dt, gravity[3], tolerance, ls_tolerance, impratio, meaninertia;

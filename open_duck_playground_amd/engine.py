@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 
@@ -141,6 +141,7 @@ def load_library() -> C.CDLL:
     L.odk_model_obs_sizes.argtypes = [P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.odk_batch_lanes.argtypes = [P]
     L.odk_model_reduced.argtypes = [P] + [C.POINTER(C.c_int)] * 6
+    L.odk_model_body_lanes.argtypes = [P, C.c_int, C.POINTER(C.c_int), C.c_int]
     L.odk_model_env_lds_floats.argtypes = [P]
     L.odk_batch_create.argtypes = [P, C.POINTER(EnvConfig), C.c_int, C.c_int, FP, DP, C.c_int, DP, C.c_int, DP, C.c_int, DP, C.c_int, PP]
     L.odk_batch_destroy.argtypes = [P]
@@ -193,7 +194,7 @@ def load_library() -> C.CDLL:
 
 
 EXPORTED_SYMBOLS = (
-    "odk_last_error", "odk_default_config", "odk_default_config_standing", "odk_obs_sizes", "odk_model_load", "odk_model_free", "odk_model_dims", "odk_model_obs_sizes", "odk_batch_lanes", "odk_model_reduced",
+    "odk_last_error", "odk_default_config", "odk_default_config_standing", "odk_obs_sizes", "odk_model_load", "odk_model_free", "odk_model_dims", "odk_model_obs_sizes", "odk_batch_lanes", "odk_model_reduced", "odk_model_body_lanes",
     "odk_model_env_lds_floats", "odk_batch_create",
     "odk_batch_destroy", "odk_batch_set_config", "odk_batch_set_param", "odk_reset", "odk_step", "odk_physics_step",
     "odk_batch_bind_commands", "odk_batch_set_reward_terms", "odk_batch_bind_reward_metrics", "odk_tracking_accumulate",
@@ -271,6 +272,21 @@ def model_reduction(model: Model) -> Dict:
         nvr = ints[1].value
         return dict(paired=ints[0].value, nvr=nvr, nMr=ints[2].value, nHr=ints[3].value, main=list(main)[:nvr], twin=list(twin)[:nvr],
                     env_lds_floats=L.odk_model_env_lds_floats(h))
+    finally:
+        L.odk_model_free(h)
+
+
+def model_body_lanes(model: Model, lanes_per_env: int) -> List[int]:
+    """Body id of each of an env's `lanes_per_env` lanes in the kinematics / inertia sweeps, -1 for a lane without a body
+    (odk_model_body_lanes); host-only, no GPU."""
+    L = load_library()
+    blob = model.blob()
+    h = C.c_void_p()
+    _chk(L.odk_model_load(blob, len(blob), C.byref(h)))
+    try:
+        out = (C.c_int * lanes_per_env)()
+        _chk(L.odk_model_body_lanes(h, int(lanes_per_env), out, lanes_per_env))
+        return list(out)
     finally:
         L.odk_model_free(h)
 
