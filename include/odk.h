@@ -202,6 +202,14 @@ int odk_batch_set_reward_terms(odk_batch* b, const odk_reward_terms* terms);
  * that is off), or NULL (not written).  odk_reset writes zeros there.  Caller-owned, like odk_batch_bind_commands' buffer. */
 int odk_batch_bind_reward_metrics(odk_batch* b, float* dev);
 
+/* Joint map of the imitation reward (custom_rewards.py:80-88): frame_joint[u] is the joint of the reference-motion frame (rows u and
+ * 16 + u of the canonical [.., 40, 16] table) that actuator u's position and velocity are compared with, or -1 for an actuator the
+ * reward does not compare.  nu must be the model's actuator count, every entry in [-1, 15], no frame joint used twice; otherwise
+ * ODK_ERR_INVALID.  The duck's model shapes start with the duck's map (joints[:5] ++ joints[9:] vs frame[:5] ++ frame[11:16]); other
+ * robots start without one, and their odk_reset / odk_step refuse use_imitation until it is set.  Synchronous; the map lives in a
+ * buffer of the batch, so a graph captured earlier follows later calls. */
+int odk_batch_set_imitation_joints(odk_batch* b, const int32_t* frame_joint, int nu);
+
 /* Velocity-tracking accumulator: one launch per evaluation step, after odk_step, graph-capturable.  For every env whose
  * acc[e][ODK_TRACK_ENDED] is 0 (its first episode: the Evaluator's `active`) it adds 1 to STEPS and the step's reward to REWARD; on
  * a done step it adds 1 to FALLS when truncation is 0 and sets ENDED; otherwise (a velocity sample: the observation of a done step is

@@ -105,7 +105,8 @@ using ShapeAE = Shape<21, 20, 18, 14, 15, 145, 170, 76, 10, 15, true>;
 using ShapeBE = Shape<31, 30, 18, 14, 25, 285, 385, 86, 15, 25, true>;
 // A robot that is not the duck (tests/assets/tail_biped.xml: biped with a five-link tail, 21 dofs, 15 actuators, 19 bodies,
 // box feet): reset / step / physics kernels -- the env kernels' task logic is joystick.py's with the robot's own tables (rec_lay, obs_nobs: sized
-// by Shape::NU; actuators, default pose, sites and sensor addresses from the ModelBlob), imitation and Standing stay the duck's.  What adding it
+// by Shape::NU; actuators, default pose, sites and sensor addresses from the ModelBlob), the imitation reward with a joint map of its own (odk_batch_set_imitation_joints), Standing
+// stays the duck's.  What adding it
 // took: this line, the dispatch lines below that name it (tools/new_shape.py prints both for an XML), and nothing in odk_kernels.h beyond
 // admitting nv = 21 to the chain solver.
 using ShapeC = Shape<22, 21, 19, 15, 16, 156, 181, 78, 10, 15>;
@@ -154,6 +155,7 @@ struct KArgs {
   int cmd_stride;     // above keep their argument offsets.)  A uniform pointer test: the unbound path only gains a scalar branch
   const XTerms* xt;   // reward-library terms (odk_batch_set_reward_terms), null while every term is off: one uniform pointer test
   float* xmet;        // [nenv][ODK_NXTERM] library metrics (odk_batch_bind_reward_metrics), or null
+  const int* imap;    // [nu] imitation joint map (odk_batch_set_imitation_joints): frame joint of actuator u, -1 = not compared
 };
 
 // DR buffer layout per env
@@ -754,10 +756,14 @@ __global__ void __launch_bounds__(64, STEP_WAVES) step_kernel(KArgs a) {
     t_pose = counted ? fabsf(jq - mp->key_ctrl[u]) : 0.0f;
     t_vel = counted ? fabsf(jv) : 0.0f;
     if (c.kind != 0 && !leg) { const float dh = jq - INFO[RL.CMD + 3 + (u - 5)]; t_jp = dh * dh; }   // cost_head_pos (rewards.py:131-147)
-    if (c.kind == 0 && leg) {  // joints[:5] ++ joints[9:] vs ref[:5] ++ ref[11:16]  (custom_rewards.py:80-88)
-      const int ri = u < 5 ? u : u + 2;
-      const float dp = jq - REF[ri], dv = jv - REF[16 + ri];
-      t_jp = dp * dp; t_jv = dv * dv;
+    if (c.kind == 0 && c.use_imitation) {   // joints vs the frame's joints through the batch's map (custom_rewards.py:80-88; the duck's:
+                                            // joints[:5] ++ joints[9:] vs ref[:5] ++ ref[11:16]).  Its address rides on the epilogue's opaque
+                                            // offset: the load stays here instead of being hoisted above the substep loop
+      const int ri = reinterpret_cast<const int*>(reinterpret_cast<const char*>(a.imap) + opaque1)[u];
+      if (ri >= 0) {
+        const float dp = jq - REF[ri], dv = jv - REF[16 + ri];
+        t_jp = dp * dp; t_jv = dv * dv;
+      }
     }
   }
   t_tq = gsum<G>(t_tq); t_ar = gsum<G>(t_ar); t_pose = gsum<G>(t_pose); t_vel = gsum<G>(t_vel); t_jp = gsum<G>(t_jp); t_jv = gsum<G>(t_jv);
@@ -928,6 +934,8 @@ struct odk_batch {
   const float* d_cmd = nullptr; int cmd_stride = 0;   // odk_batch_bind_commands (caller-owned device rows), null: sampled commands
   XTerms* d_xt = nullptr; bool xt_on = false;         // odk_batch_set_reward_terms: the batch's device copy; passed to the kernels while some term is on
   float* d_xmet = nullptr;                             // odk_batch_bind_reward_metrics (caller-owned)
+  int* d_imap = nullptr; bool imap_set = false;        // odk_batch_set_imitation_joints: the batch's device copy; set: a map was given (the duck's
+                                                       // shapes start with theirs)
 };
 
 extern "C" const char* odk_last_error(void) { return g_err.c_str(); }
@@ -1852,6 +1860,13 @@ extern "C" int odk_batch_create(const odk_model* m, const odk_env_config* cfg, i
   HIPCHK(hipMalloc(&b->d_first, (size_t)nenv * b->frec_size * sizeof(float))); HIPCHK(hipMemset(b->d_first, 0, (size_t)nenv * b->frec_size * sizeof(float)));
   HIPCHK(hipMalloc(&b->d_dbg, (size_t)nenv * b->lds_total * sizeof(float))); HIPCHK(hipMemset(b->d_dbg, 0, (size_t)nenv * b->lds_total * sizeof(float)));
   HIPCHK(hipMalloc(&b->d_xt, sizeof(XTerms))); HIPCHK(hipMemset(b->d_xt, 0, sizeof(XTerms)));
+  {   // imitation joint map: the duck's (custom_rewards.py:80-88) for its two shapes, none (every actuator -1) for another robot
+    int h[MAXU];
+    for (int u = 0; u < MAXU; u++) h[u] = -1;
+    if (m->shape < 2) for (int u = 0; u < m->h.nu; u++) h[u] = u < 5 ? u : (u >= 9 ? u + 2 : -1);
+    HIPCHK(hipMalloc(&b->d_imap, sizeof(h))); HIPCHK(hipMemcpy(b->d_imap, h, sizeof(h), hipMemcpyHostToDevice));
+    b->imap_set = m->shape < 2;
+  }
   if (!m->hfield.empty()) {   // shared by all envs, L2-resident (256 KB)
     HIPCHK(hipMalloc(&b->d_hfield, m->hfield.size() * sizeof(float)));
     HIPCHK(hipMemcpy(b->d_hfield, m->hfield.data(), m->hfield.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -1862,7 +1877,7 @@ extern "C" int odk_batch_create(const odk_model* m, const odk_env_config* cfg, i
 extern "C" void odk_batch_destroy(odk_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
-  for (void* p : {(void*)b->d_model, (void*)b->d_table, (void*)b->d_recs, (void*)b->d_first, (void*)b->d_dr, (void*)b->d_dbg, (void*)b->d_hfield, (void*)b->d_xt}) (void)hipFree(p);
+  for (void* p : {(void*)b->d_model, (void*)b->d_table, (void*)b->d_recs, (void*)b->d_first, (void*)b->d_dr, (void*)b->d_dbg, (void*)b->d_hfield, (void*)b->d_xt, (void*)b->d_imap}) (void)hipFree(p);
   for (auto& ev : b->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
   delete b;
 }
@@ -1969,16 +1984,18 @@ static void base_args(odk_batch* b, KArgs& a, const odk_outputs* o) {
   a.dbg_lds = nullptr;
   a.cmd = b->d_cmd; a.cmd_stride = b->cmd_stride;
   a.xt = b->xt_on ? b->d_xt : nullptr; a.xmet = b->xt_on ? b->d_xmet : nullptr;
+  a.imap = b->d_imap;
   if (o) { a.obs = o->obs_dev; a.priv = o->priv_dev; a.reward = o->reward_dev; a.done = o->done_dev; a.trunc = o->truncation_dev; a.metrics = o->metrics_dev; }
   to_dev_cfg(b->cfg, a.cfg, b->model.h.nu);
 }
 
 // The env kernels' task logic is joystick.py's with the robot's own tables (actuators, default pose, feet / imu sites, sensor addresses from the
-// ModelBlob).  What stays the duck's: the imitation reward (its reference-motion table and joint map: custom_rewards.py:80-88) and the Standing
-// task's head joints (standing.py:590-597, rewards.py:131-147 index the duck's actuators 5..8) -- refused by name for another robot's
-// odk_reset / odk_step (odk_physics_step has no task logic)
+// ModelBlob).  The imitation reward needs a joint map (custom_rewards.py:80-88) and a reference-motion table of the robot: the duck's shapes start
+// with the duck's map, another robot's odk_reset / odk_step refuse use_imitation until odk_batch_set_imitation_joints gave one.  What stays the
+// duck's: the Standing task's head joints (standing.py:590-597, rewards.py:131-147 index the duck's actuators 5..8) -- refused by name for
+// another robot (odk_physics_step has no task logic)
 static int env_logic_ok(const odk_batch* b) {
-  if (b->model.shape >= 2 && (b->cfg.use_imitation || b->cfg.env_kind != ODK_ENV_JOYSTICK))
+  if (b->model.shape >= 2 && ((b->cfg.use_imitation && !b->imap_set) || b->cfg.env_kind != ODK_ENV_JOYSTICK))
     return fail(ODK_ERR_UNSUPPORTED, "%s on a robot that is not the duck: the reference-motion table / the head joints are open_duck_mini_v2's (set use_imitation = 0, env_kind = ODK_ENV_JOYSTICK)",
                 b->cfg.use_imitation ? "use_imitation" : "the Standing task");
   return ODK_OK;
@@ -2069,6 +2086,26 @@ extern "C" int odk_batch_set_reward_terms(odk_batch* b, const odk_reward_terms* 
   HIPCHK(hipDeviceSynchronize());   // no step in flight reads the buffer while it changes
   HIPCHK(hipMemcpy(b->d_xt, &h, sizeof(h), hipMemcpyHostToDevice));
   b->xt_on = on;
+  return ODK_OK;
+}
+
+extern "C" int odk_batch_set_imitation_joints(odk_batch* b, const int32_t* frame_joint, int nu) {
+  if (!b || !frame_joint) return fail(ODK_ERR_INVALID, "null argument");
+  if (nu != b->model.h.nu) return fail(ODK_ERR_INVALID, "odk_batch_set_imitation_joints: %d entries, the model has %d actuators", nu, b->model.h.nu);
+  int h[MAXU];
+  for (int u = 0; u < MAXU; u++) h[u] = -1;
+  unsigned used = 0;
+  for (int u = 0; u < nu; u++) {
+    const int j = frame_joint[u];
+    if (j < -1 || j > 15) return fail(ODK_ERR_INVALID, "odk_batch_set_imitation_joints: actuator %d maps to frame joint %d (valid: -1 .. 15)", u, j);
+    if (j >= 0 && (used >> j & 1u)) return fail(ODK_ERR_INVALID, "odk_batch_set_imitation_joints: frame joint %d is used twice", j);
+    if (j >= 0) used |= 1u << j;
+    h[u] = j;
+  }
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipDeviceSynchronize());   // no step in flight reads the buffer while it changes
+  HIPCHK(hipMemcpy(b->d_imap, h, sizeof(h), hipMemcpyHostToDevice));
+  b->imap_set = true;
   return ODK_OK;
 }
 

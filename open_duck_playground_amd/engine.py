@@ -153,6 +153,7 @@ def load_library() -> C.CDLL:
     L.odk_batch_bind_commands.argtypes = [P, P, C.c_int]
     L.odk_batch_set_reward_terms.argtypes = [P, C.POINTER(RewardTerms)]
     L.odk_batch_bind_reward_metrics.argtypes = [P, P]
+    L.odk_batch_set_imitation_joints.argtypes = [P, C.POINTER(C.c_int32), C.c_int]
     L.odk_tracking_accumulate.argtypes = [P, P, P, P, P, P, P]
     L.odk_batch_get_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_set_state.argtypes = [P, FP, FP, FP]
@@ -197,7 +198,7 @@ EXPORTED_SYMBOLS = (
     "odk_last_error", "odk_default_config", "odk_default_config_standing", "odk_obs_sizes", "odk_model_load", "odk_model_free", "odk_model_dims", "odk_model_obs_sizes", "odk_batch_lanes", "odk_model_reduced", "odk_model_body_lanes",
     "odk_model_env_lds_floats", "odk_batch_create",
     "odk_batch_destroy", "odk_batch_set_config", "odk_batch_set_param", "odk_reset", "odk_step", "odk_physics_step",
-    "odk_batch_bind_commands", "odk_batch_set_reward_terms", "odk_batch_bind_reward_metrics", "odk_tracking_accumulate",
+    "odk_batch_bind_commands", "odk_batch_set_reward_terms", "odk_batch_bind_reward_metrics", "odk_batch_set_imitation_joints", "odk_tracking_accumulate",
     "odk_batch_get_state", "odk_batch_set_state", "odk_batch_get_debug", "odk_set_debug_dump", "odk_batch_lds_size",
     "odk_batch_get_lds", "odk_lds_offset", "odk_batch_record_size", "odk_batch_get_records", "odk_batch_set_records", "odk_batch_timing", "odk_gae", "odk_ppo_head",
     "odk_policy_sample", "odk_adam_clip", "odk_silu_bwd_colsum", "odk_colsum_partial", "odk_colsum_finalize", "odk_gather_rows", "odk_dw_gemm",
@@ -893,6 +894,13 @@ class Batch:
             _chk(self.L.odk_batch_bind_reward_metrics(self._b, C.c_void_p(self.xmetrics.data_ptr())))
         _chk(self.L.odk_batch_set_reward_terms(self._b, C.byref(terms) if terms is not None else None))
         self.reward_terms_on = on
+
+    def set_imitation_joints(self, seq):
+        """Joint map of the imitation reward (`odk_batch_set_imitation_joints`): entry u is the reference-motion frame joint actuator u is
+        compared with, -1 for an actuator the reward leaves out (reference_motion.imitation_joint_map makes one).  Synchronous; a graph
+        captured earlier follows it.  OdkError for a map of the wrong length, an entry outside [-1, 15] or a frame joint used twice."""
+        m = np.ascontiguousarray(np.asarray(seq).reshape(-1), np.int32)
+        _chk(self.L.odk_batch_set_imitation_joints(self._b, m.ctypes.data_as(C.POINTER(C.c_int32)), len(m)))
 
     def tracking_accumulate(self, acc):
         """One `odk_tracking_accumulate` launch over this step's outputs into `acc` ([nenv, TRACK_NACC] float32, zeroed before

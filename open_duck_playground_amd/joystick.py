@@ -268,7 +268,14 @@ class Joystick:
         The reference's recipe for a new robot (README.md:74-85) copies base.py / constants.py / joystick.py and edits names; here the names the
         reference looks up (constants.py: sites `imu`, `left_foot`, `right_foot`; geoms `left_foot_bottom_tpu`, `right_foot_bottom_tpu`, `floor`;
         the 15 sensors; keyframe `home`) are what the XML must carry, and the index tables of base.py:63-125 / joystick.py:121-200 come out of the
-        compiled model.  Such a robot runs the Joystick task without the imitation reward (the reference-motion table is the duck's)."""
+        compiled model.
+
+        Imitation reward (BUILD-DEFINED config keys; they travel in `config_overrides` and the evaluation sibling inherits them):
+        `reference_motion` -- a `polynomial_coefficients.pkl` (reference_motion.ReferenceMotion.from_pickle) -- turns the imitation reward on
+        for any robot, with that table; `imitation_joints` names the motion's frame joints in frame order and `imitation_ignore` the frame
+        joints to leave out (reference_motion.imitation_joint_map: the defaults are the duck's frame and custom_rewards.py:80-88's joints for
+        the duck, the actuated joints for another robot).  Without `reference_motion` the duck trains on the shipped table
+        (assets/prm_table.npz) and another robot without the imitation reward."""
         self._config = _merge(config if config is not None else self._default_config(), config_overrides)
         if model is not None:
             self._model = model
@@ -278,6 +285,7 @@ class Joystick:
         else:
             self._model = constants.task_to_model(task)      # KeyError for unknown task names
         self._robot = constants.robot_of(self._model)
+        self._motion = self._load_reference_motion()
         cone = self._config.get("cone", None)
         if cone is not None:      # BUILD-DEFINED switch (the reference edits the XML's <option cone=...>): "pyramidal" | "elliptic", optional "impratio"
             if cone not in ("pyramidal", "elliptic"):
@@ -293,7 +301,10 @@ class Joystick:
         self._task = task
         self.num_envs = int(num_envs)
         self._env_id_offset = int(env_id_offset)
-        self._batch = engine.Batch(self._model, self.num_envs, self._engine_config(autoreset, lanes_per_env), device=device)
+        self._batch = engine.Batch(self._model, self.num_envs, self._engine_config(autoreset, lanes_per_env), device=device,
+                                   prm=self._motion.prm() if self._motion is not None else None)
+        if self._motion is not None:
+            self._batch.set_imitation_joints(self._imitation_map)
         self._batch.set_reward_terms(to_reward_terms(self._config, self._model.nu, self._reward_slots()))
         scales = self._config.reward_config.scales
         # State.metrics names of the Batch.xmetrics columns (None: the term is off)
@@ -302,8 +313,28 @@ class Joystick:
     def _default_config(self) -> ConfigDict:
         return default_config()
 
+    def _load_reference_motion(self):
+        """The `reference_motion` config key's table and joint map, or None (keys: Joystick.__init__)."""
+        path = self._config.get("reference_motion", None)
+        if path is None:
+            for k in ("imitation_joints", "imitation_ignore"):
+                if self._config.get(k, None) is not None:
+                    raise ValueError(f"config {k} is set without reference_motion (the joint map belongs to a reference motion)")
+            return None
+        from .reference_motion import ReferenceMotion, imitation_joint_map
+        motion = ReferenceMotion.from_pickle(str(path))
+        self._imitation_map = imitation_joint_map(self._model, motion, self._config.get("imitation_joints", None),
+                                                  self._config.get("imitation_ignore", None))
+        return motion
+
+    @property
+    def reference_motion(self):
+        """The ReferenceMotion loaded from the `reference_motion` config key, or None (the duck's shipped table / no imitation)."""
+        return self._motion
+
     def _engine_config(self, autoreset: bool, lanes_per_env: int) -> engine.EnvConfig:
-        return to_engine_config(self._config, autoreset, lanes_per_env, use_imitation=USE_IMITATION_REWARD and self._robot.is_open_duck,
+        imitation = USE_IMITATION_REWARD and (self._robot.is_open_duck or self._motion is not None)
+        return to_engine_config(self._config, autoreset, lanes_per_env, use_imitation=imitation,
                                 joints_order_no_head=self._robot.joints_order_no_head)
 
     def _reward_slots(self):

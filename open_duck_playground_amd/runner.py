@@ -48,6 +48,42 @@ def reward_overrides(env: str, scales=None, params=None) -> dict:
     return out
 
 
+def _names(spec):
+    return [n.strip() for n in spec.split(",") if n.strip()] if spec else None
+
+
+def imitation_overrides(args) -> dict:
+    """--reference_motion PATH / --imitation_joints a,b,... / --imitation_ignore a,b,... -> the Joystick config keys reference_motion,
+    imitation_joints, imitation_ignore (those not given stay out)."""
+    out = {}
+    if getattr(args, "reference_motion", None):
+        out["reference_motion"] = args.reference_motion
+    for k in ("imitation_joints", "imitation_ignore"):
+        names = _names(getattr(args, k, None))
+        if names is not None:
+            out[k] = names
+    return out
+
+
+def config_overrides(args):
+    """The env's config_overrides from the command line (None when nothing is overridden)."""
+    overrides = {"hfield_up_normals_only": True} if getattr(args, "hfield_up_normals_only", False) else None
+    if getattr(args, "cone", None):
+        overrides = dict(overrides or {}, cone=args.cone)
+    overrides = dict(overrides or {}, **reward_overrides(args.env, getattr(args, "reward_scale", None), getattr(args, "reward_param", None)))
+    return dict(overrides, **imitation_overrides(args)) or None
+
+
+def add_imitation_flags(parser) -> None:
+    parser.add_argument("--reference_motion", type=str, default=None, metavar="PATH",
+                        help="train with the imitation reward on this reference motion (a polynomial_coefficients.pkl, reference README "
+                             "'imitation reward'); any robot.  Default: the duck's shipped table for the duck, no imitation reward otherwise")
+    parser.add_argument("--imitation_joints", type=str, default=None, metavar="A,B,...",
+                        help="the reference motion's frame joints in frame order (default: the duck's 16 for the duck, the actuated joints otherwise)")
+    parser.add_argument("--imitation_ignore", type=str, default=None, metavar="A,B,...",
+                        help="frame joints the imitation reward leaves out (default: the duck's antennas for the duck, none otherwise)")
+
+
 class OpenDuckMiniV2Runner:
     def __init__(self, args):
         import torch
@@ -67,14 +103,13 @@ class OpenDuckMiniV2Runner:
         device = args.device if self.world == 1 else local_rank
         torch.cuda.set_device(device)
         n_local = args.num_envs // self.world
-        overrides = {"hfield_up_normals_only": True} if getattr(args, "hfield_up_normals_only", False) else None
-        if getattr(args, "cone", None):
-            overrides = dict(overrides or {}, cone=args.cone)
-        overrides = dict(overrides or {}, **reward_overrides(args.env, getattr(args, "reward_scale", None), getattr(args, "reward_param", None))) or None
+        overrides = config_overrides(args)
         extra = {}
         if getattr(args, "xml", None):      # a robot of one's own (reference README.md:74-85 "Adding a new robot"): its MJCF instead of a shipped task
             extra["xml_path"] = args.xml
         self.env = available_envs[args.env](task=args.task, num_envs=n_local, device=device, env_id_offset=self.rank * n_local, config_overrides=overrides, **extra)
+        if getattr(self.env, "reference_motion", None) is not None:
+            print(self.env.reference_motion.describe())
         self.action_size = self.env.action_size
         self.obs_size = int(self.env.observation_size["state"][0])
         # one generator per (seed, rank, stream): stream 0 = training envs, 1 = evaluation envs (ppo/train.py)
@@ -146,6 +181,7 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--reward_param", action="append", default=[], metavar="KEY=VALUE",
                         help="repeatable: a parameter of the library terms: base_height_target, max_foot_height, air_time_range=MIN,MAX, "
                              "pose_weights=W1,...,Wnu, soft_joint_pos_limit_factor")
+    add_imitation_flags(parser)
     return parser
 
 

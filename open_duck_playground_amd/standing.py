@@ -45,6 +45,12 @@ class Standing(Joystick):
     def _reward_slots(self):
         return REWARD_SLOTS   # `orientation` is native here: the library's copy of it is the Joystick's
 
+    def _load_reference_motion(self):
+        for k in ("reference_motion", "imitation_joints", "imitation_ignore"):
+            if self._config.get(k, None) is not None:
+                raise ValueError(f"config {k}: the Standing task has no imitation reward (standing.py:42)")
+        return None
+
     def _engine_config(self, autoreset: bool, lanes_per_env: int) -> engine.EnvConfig:
         return to_engine_config(self._config, autoreset, lanes_per_env, standing=True, reward_slots=REWARD_SLOTS,
                                 use_imitation=USE_IMITATION_REWARD, use_motor_speed_limits=False)

@@ -117,16 +117,24 @@ def save_obs(path: str, obs: np.ndarray) -> None:
         pickle.dump([np.array(o, np.float32) for o in obs], f)
 
 
-def make_env(args, num_envs: int, device: int):
-    from . import joystick, standing
-    envs = {"joystick": joystick.Joystick, "standing": standing.Standing}     # runner.py's --env
-    if args.env not in envs:
-        raise ValueError(f"Unknown env {args.env}")
+def config_overrides(args) -> Dict:
+    """The env's config_overrides from the command line."""
+    from .runner import imitation_overrides
     overrides = {"episode_length": int(args.episode_length)}
     if args.hfield_up_normals_only:
         overrides["hfield_up_normals_only"] = True
     if args.cone:
         overrides["cone"] = args.cone
+    overrides.update(imitation_overrides(args))
+    return overrides
+
+
+def make_env(args, num_envs: int, device: int):
+    from . import joystick, standing
+    envs = {"joystick": joystick.Joystick, "standing": standing.Standing}     # runner.py's --env
+    if args.env not in envs:
+        raise ValueError(f"Unknown env {args.env}")
+    overrides = config_overrides(args)
     extra = {"xml_path": args.xml} if args.xml else {}
     # a few hundred envs: one env per wave finishes a step sooner (Joystick.make_eval_env)
     return envs[args.env](task=args.task, num_envs=num_envs, device=device, autoreset=True, lanes_per_env=64 if num_envs <= 1024 else 0,
@@ -204,6 +212,9 @@ def run(args, out=sys.stdout) -> Dict:
     torch.cuda.set_device(args.device)
     dev = torch.device("cuda", args.device)
     env = make_env(args, n, args.device)
+    motion = getattr(env, "reference_motion", None)
+    if motion is not None:
+        print(motion.describe(), file=sys.stderr)      # stdout may carry the JSON report
     net = load_networks(args.checkpoint, env, dev)
     cmd = torch.from_numpy(command_blocks(commands, E)).to(dev)
     env.set_commands(cmd)
@@ -227,7 +238,8 @@ def run(args, out=sys.stdout) -> Dict:
     rows = reduce_tracking(acc, commands, E)
     settings = dict(checkpoint=args.checkpoint, env=args.env, task=args.task, xml=args.xml, cone=args.cone,
                     hfield_up_normals_only=bool(args.hfield_up_normals_only), envs_per_command=E, episode_length=T, seed=int(args.seed),
-                    num_envs=n, dt=float(env.dt), policy="deterministic tanh(loc)", fused_policy=tr.fp is not None, graph=tr.graph is not None)
+                    num_envs=n, dt=float(env.dt), policy="deterministic tanh(loc)", fused_policy=tr.fp is not None, graph=tr.graph is not None,
+                    reference_motion=getattr(args, "reference_motion", None), reference_motion_sha256=motion.sha256 if motion is not None else None)
     report = make_report(settings, rows)
     if save_obs_path:
         save_obs(save_obs_path, obs_hist.cpu().numpy())
@@ -251,6 +263,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--xml", type=str, default=None, help="a robot of your own: its MJCF (as runner)")
     p.add_argument("--cone", choices=["pyramidal", "elliptic"], default=None, help="friction cone (as runner)")
     p.add_argument("--hfield_up_normals_only", action="store_true", help="height-field contact reading (as runner)")
+    from .runner import add_imitation_flags
+    add_imitation_flags(p)
     p.add_argument("--command", nargs="+", type=float, action="append", metavar="V",
                    help="vx vy wz [neck_pitch head_pitch head_yaw head_roll]; repeat for more commands")
     p.add_argument("--grid", type=str, default=None, help="a grid of commands: vx=a:b:n,wz=c:d:m (axes vx vy wz neck_pitch head_pitch head_yaw head_roll)")
