@@ -114,6 +114,10 @@ using ShapeC = Shape<22, 21, 19, 15, 16, 156, 181, 78, 10, 15>;
 // 16 bodies: serial chains of six (the chain solve's block size is the shape's CL), contact wrenches in their own floats (16 bodies' cfrc | crb
 // region is too small for them).  Env kernels as for ShapeC (12 actions, observations 89 / 194 floats).
 using ShapeD = Shape<19, 18, 16, 12, 13, 135, 171, 72, 12, 18, false, 6, true>;      // (chains of six; equality rows and elliptic cones compiled in, as ShapeC)
+// A biped with arms (tests/assets/biped_arms.xml): biped12's legs and two arms on the trunk (shoulder pitch, elbow), 22 dofs, 16 actuators, 20
+// bodies: FOUR serial chains below the floating base (6 / 6 / 2 / 2), the chain solve's fourth 8-lane group (Shape::NCH).  The same shape takes
+// tests/assets/biped_arms_between.xml (the arms declared between the legs).  Env kernels as for ShapeC (16 actions, observations 113 / 230 floats).
+using ShapeE = Shape<23, 22, 20, 16, 17, 165, 201, 80, 11, 17, false, 6, true, 4>;
 // The compiled model shapes, by the index odk_model carries: every per-shape dispatch of the host code below goes through this list, so a
 // new robot is ONE `using` line above and ONE entry here (tools/new_shape.py <xml> prints both).  Entries 0 and 1 are the duck's two models
 // (their cone / height-field / 64-lane instantiations are chosen in launch()); entries from 2 on run reset / step / physics kernels at 32
@@ -126,7 +130,9 @@ using ShapeD = Shape<19, 18, 16, 12, 13, 135, 171, 72, 12, 18, false, 6, true>; 
 #ifndef ODK_USER_SHAPES
 #define ODK_USER_SHAPES(X)
 #endif
-#define ODK_SHAPES(X) X(0, ShapeA) X(1, ShapeB) X(2, ShapeC) X(3, ShapeD) ODK_USER_SHAPES(X)
+// Further robots that ship with the library take indices from 16 on, clear of the user shapes (4, 5, ...: tools/new_shape.py --add).
+#define ODK_SHIPPED_SHAPES(X) X(16, ShapeE)
+#define ODK_SHAPES(X) X(0, ShapeA) X(1, ShapeB) X(2, ShapeC) X(3, ShapeD) ODK_SHIPPED_SHAPES(X) ODK_USER_SHAPES(X)
 
 // Device copy of odk_reward_terms, filled by the host: soft joint limits and the robot's global_linvel sensor address resolved there
 struct XTerms {
@@ -1069,7 +1075,7 @@ static void pack_imp(const float* solref, const float* solimp, float dt, float* 
 }
 
 // Twin-dof detection and the reduced (twins merged) tree layouts -- see DevModel::paired.  Called after the dof / joint /
-// foot tables are in place.  Returns false when the reduced tree is not "floating base + up to three serial chains of <= 5
+// foot tables are in place.  Returns false when the reduced tree is not "floating base + up to four serial chains of <= 6
 // dofs" (the form chain_solve is built for).
 namespace {
 struct SparseLayout { int depth[MAXV], adr[MAXV], ancmask[MAXV], descmask[MAXV], anc_at[MAXV][MAXV], nnz; };
@@ -1121,12 +1127,11 @@ static bool fill_body_st(DevModel& m) {
     memset(&b, 0, sizeof(b));
     b.level = in ? m.body_level[bi] : -2;
     b.parent = m.body_parent[bi];
-    b.nchild = in ? m.body_nchild[bi] : 0;
     b.pathmask = in ? m.body_pathmask[bi] : 0;
     b.is_path = in ? m.body_is_path[bi] : 0;
     b.upmask = in ? m.body_upmask[bi] : 0;
     b.path_head = in ? m.body_path_head[bi] : 0;
-    for (int k = 0; k < 3; k++) b.child[k] = m.body_children[bi][k];
+    for (int k = 0; k < 4; k++) b.child[k] = m.body_children[bi][k];
     b.njnt = (in && b.level > 0) ? m.body_jntnum[bi] : 0;
     for (int k = 0; k < 2; k++) {
       const bool on = k < b.njnt;
@@ -1215,7 +1220,7 @@ static bool build_reduced_tables(DevModel& m) {
   bool ok = nr > 6;
   for (int r = 0; r < 6 && ok; r++) ok = rparent[r] == r - 1;
   while (ok && d < nr) {
-    if (rparent[d] != 5 || m.nrchain == 3) { ok = false; break; }
+    if (rparent[d] != 5 || m.nrchain == 4) { ok = false; break; }
     int e = d;
     while (e + 1 < nr && rparent[e + 1] == e) e++;
     m.rchain_first[m.nrchain] = d; m.rchain_len[m.nrchain] = e - d + 1; m.nrchain++;
@@ -1382,8 +1387,9 @@ extern "C" int odk_model_load(const void* blob, uint64_t len, odk_model** out) {
   B.I2("k_body_chain", &m.body_chain[0][0], MAXB, MAXCHAIN); B.I("k_body_chain_len", m.body_chain_len, MAXB);
   B.I2("k_body_ancdof", &m.body_ancdof[0][0], MAXB, MAXV); B.I("k_body_nancdof", m.body_nancdof, MAXB);
   B.I2("k_body_sub", &m.body_sub[0][0], MAXB, MAXB); B.I("k_body_nsub", m.body_nsub, MAXB);
-  B.I("k_max_level", &m.max_level, 1); B.I("k_body_level", m.body_level, MAXB); B.I2("k_body_children", &m.body_children[0][0], MAXB, 3);
-  B.I("k_body_nchild", m.body_nchild, MAXB);
+  B.I("k_max_level", &m.max_level, 1); B.I("k_body_level", m.body_level, MAXB);
+  for (int b2 = 0; b2 < MAXB; b2++) for (int k = 0; k < 4; k++) m.body_children[b2][k] = -1;   // (a blob with three columns: no fourth child)
+  B.I2("k_body_children", &m.body_children[0][0], MAXB, 4);
   B.I("k_max_nonpath_level", &m.max_nonpath_level, 1); B.I("k_body_pathmask", m.body_pathmask, MAXB); B.I("k_body_is_path", m.body_is_path, MAXB);
   B.I("k_body_upmask", m.body_upmask, MAXB); B.I("k_body_path_head", m.body_path_head, MAXB);
   B.F("body_pos", &m.body_pos[0][0], MAXB * 3); B.F("body_quat", &m.body_quat[0][0], MAXB * 4); B.F("body_ipos", &m.body_ipos[0][0], MAXB * 3);
@@ -1404,7 +1410,6 @@ extern "C" int odk_model_load(const void* blob, uint64_t len, odk_model** out) {
   B.F("dof_armature", m.dof_armature, MAXV); B.F("dof_damping", m.dof_damping, MAXV); B.F("dof_frictionloss", m.dof_frictionloss, MAXV);
   B.F("dof_invweight0", m.dof_invweight0, MAXV);
   B.I("k_nM", &m.nM, 1); B.I("k_M_i", m.M_i, MAXNZ); B.I("k_M_j", m.M_j, MAXNZ);
-  B.I("k_nchain", &m.nchain, 1); B.I("k_chain_first", m.chain_first, 3); B.I("k_chain_len", m.chain_len, 3);
   for (int d = 0; d < MAXV; d++) { m.dof_qadr[d] = -1; m.dof_jnt[d] = -1; }
   for (int j = 1; j < m.nj; j++) {
     const int d = m.jnt_dofadr[j];
@@ -1640,7 +1645,7 @@ extern "C" int odk_model_load(const void* blob, uint64_t len, odk_model** out) {
   // bodies above the serial chains that have children: flattened source lists for the one-step subtree fold (P2)
   m.np_count = 0;
   for (int b2 = 0; b2 < m.nb; b2++) {
-    if (!(m.body_level[b2] >= 0 && m.body_nchild[b2] > 0 && !m.body_is_path[b2])) continue;
+    if (!(m.body_level[b2] >= 0 && m.body_children[b2][0] >= 0 && !m.body_is_path[b2])) continue;
     if (m.np_count == 4) { delete mo; return fail(ODK_ERR_UNSUPPORTED, "more than four branching bodies above the serial chains"); }
     const int i = m.np_count++;
     m.np_body[i] = b2; m.np_nsrc[i] = 0;
@@ -1654,7 +1659,7 @@ extern "C" int odk_model_load(const void* blob, uint64_t len, odk_model** out) {
       }
     }
   }
-  if (!build_reduced_tables(m)) { delete mo; return fail(ODK_ERR_UNSUPPORTED, "dof tree is not a floating base with up to three serial chains of <= 5 (twin-merged) dofs"); }
+  if (!build_reduced_tables(m)) { delete mo; return fail(ODK_ERR_UNSUPPORTED, "dof tree is not a floating base with up to four serial chains of <= 6 (twin-merged) dofs"); }
   if (!fill_body_st(m)) {
     delete mo; return fail(ODK_ERR_UNSUPPORTED, "no body-to-lane layout: every serial body chain must fit in one 16-lane row and all %d bodies in 32 lanes", m.nb);
   }
@@ -1671,12 +1676,13 @@ extern "C" int odk_model_load(const void* blob, uint64_t len, odk_model** out) {
     return fail(ODK_ERR_UNSUPPORTED, "model shape nq=%d nv=%d nb=%d nu=%d nj=%d nM=%d nH=%d nrow=%d depth=%d vdepth=%d has no compiled kernel (tools/new_shape.py <xml> prints the two lines to add to odk_engine.hip)",
                 m.nq, m.nv, m.nb, m.nu, m.nj, m.nM, m.nH, m.nrow, dtm, dvm);
   }
-  int shape_cl = 5; bool shape_eq = false;
-#define X(i, S) if (mo->shape == i) { shape_cl = S::CL; shape_eq = S::EQ; }
+  int shape_cl = 5, shape_nch = 3; bool shape_eq = false;
+#define X(i, S) if (mo->shape == i) { shape_cl = S::CL; shape_nch = S::NCH; shape_eq = S::EQ; }
   ODK_SHAPES(X)
 #undef X
   for (int c = 0; c < m.nrchain; c++)
     if (m.rchain_len[c] > shape_cl) { const int len = m.rchain_len[c]; delete mo; return fail(ODK_ERR_UNSUPPORTED, "a serial chain of %d (twin-merged) dofs: the kernels of this model shape solve chains of <= %d", len, shape_cl); }
+  if (m.nrchain > shape_nch) { const int n = m.nrchain; delete mo; return fail(ODK_ERR_UNSUPPORTED, "%d serial chains below the floating base: the kernels of this model shape solve <= %d", n, shape_nch); }
   if (!m.floor_is_plane && mo->shape != 1) { delete mo; return fail(ODK_ERR_UNSUPPORTED, "height-field floors are built for the backlash model only"); }
 
   if (m.cone && m.foot_prim != 0) {

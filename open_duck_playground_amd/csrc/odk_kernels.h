@@ -65,7 +65,7 @@ struct EnvCfg {  // device copy of odk_env_config
 
 // ------------------------------------------------------------------------------------------------
 // LDS layout (floats), per environment.  Component-major (SoA) arrays: X[k * N + item].
-template <int NQ_, int NV_, int NB_, int NU_, int NJ_, int NM_, int NH_, int NROW_, int DT_, int DV_, bool CONE_ = false, int CL_ = -1, bool OPT_ = false>
+template <int NQ_, int NV_, int NB_, int NU_, int NJ_, int NM_, int NH_, int NROW_, int DT_, int DV_, bool CONE_ = false, int CL_ = -1, bool OPT_ = false, int NCH_ = 3>
 struct Shape {
   static constexpr int NQ = NQ_, NV = NV_, NB = NB_, NU = NU_, NJ = NJ_, NM = NM_, NH = NH_, NROW = NROW_;
   static constexpr int DT = DT_;    // max dof depth, kinematic tree
@@ -89,7 +89,9 @@ struct Shape {
   // contact-row constants.  (Friction-loss rows, actuator constants and the foot hull were tried there too: no gain, their
   // loads from the L2-resident model are already covered.)
   static constexpr int SH_CT = NMR, SHARED = SH_CT + 42;
-  static constexpr int CL = CL_ >= 0 ? CL_ : ((NV_ == 20 || NV_ == 21 || PAIRED) ? 5 : 0);   // max (reduced) chain length for chain_solve: every compiled shape is a floating base + <= 3 serial chains of <= 5 (reduced) dofs (0: generic path)
+  static constexpr int CL = CL_ >= 0 ? CL_ : ((NV_ == 20 || NV_ == 21 || PAIRED) ? 5 : 0);   // max (reduced) chain length for chain_solve: every compiled shape is a floating base + <= NCH serial chains of <= CL (reduced) dofs (0: generic path)
+  static constexpr int NCH = NCH_;  // serial chains below the floating base that chain_solve eliminates: chain c on lanes 8 c .. 8 c + 6 (a biped with arms: 4)
+  static_assert(NCH >= 1 && NCH <= 4, "chain_solve: one 8-lane group per chain, 32 lanes");
   // persistent over the env step
   static constexpr int O_QPOS = 0;
   static constexpr int O_QVEL = O_QPOS + NQ;
@@ -144,9 +146,10 @@ struct Shape {
   static constexpr int S_VF2 = 132;   // [2][6] second foot twist (warmstart candidate)
   static constexpr int S_FFX = 144;   // [6] wrench sum of the foot-foot rows
   static constexpr int S_EQ = 150;    // [EQ_MAX] equality rows: the Hessian's off-diagonal addend -D c (force phase -> Hessian entries; the solve's scratch runs over it afterwards)
-  // the chain solve's scratch starts at S_K and takes 3 CL 7 + 27 floats (156 for chains of five: up to S_MISC; 177 for chains of six): it runs over
+  // the chain solve's scratch starts at S_K and takes NCH CL 7 + 27 floats (three chains: 156 for chains of five, up to S_MISC; 177 for chains of six;
+  // four chains of six: 219): it runs over
   // S_VF2 / S_FFX / S_EQ, which are dead by then -- but never over the misc scalars, which the env kernels' epilogue reads (foot heights, gravity)
-  static constexpr int S_SOLVE_END = S_K + 21 * CL + 27;
+  static constexpr int S_SOLVE_END = S_K + 7 * NCH * CL + 27;
   static constexpr int S_MISC = S_SOLVE_END > 156 ? S_SOLVE_END : 156;  // misc scalars (16)
   static constexpr int S_PROF = S_MISC + 16;   // [20] per-phase cycle counters (ODK_PROFILE builds)
   static constexpr int S_PROF2 = S_PROF + 20;  // [16] height-field contacts: hull setup, cull pass, register loads, pair loop, iterations, list length, -, -,
@@ -388,7 +391,7 @@ __host__ __device__ inline void compute_statics(LaneSt& st, const DevModel* m, i
   {
     st.cs_pk = 0;
     const int c = lane >> 3;
-    if (c < 3 && c < m->nrchain) {
+    if (c < S::NCH && c < m->nrchain) {
       const int f = m->rchain_first[c];
       st.cs_pk = m->rchain_len[c] | (m->red_depth[f] << 3) | (f << 8) | (m->red_Madr[f] << 14);
     }
@@ -398,7 +401,7 @@ __host__ __device__ inline void compute_statics(LaneSt& st, const DevModel* m, i
     st.cs_pk |= (tb << 24) | (tb2 << 27);
   }
   st.ch_first = 0; st.ch_len = 0;
-  for (int c = 0; c < 3; c++)
+  for (int c = 0; c < 4; c++)
     if (c < m->nrchain && lane >= m->rchain_first[c] && lane < m->rchain_first[c] + m->rchain_len[c]) { st.ch_first = m->rchain_first[c]; st.ch_len = m->rchain_len[c]; }
   {
     const int r = lane < S::NVR ? lane : 0;
@@ -624,23 +627,25 @@ __device__ __forceinline__ float solve_rows(const float* A, float xi, int lane, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// Solve of (L^T D L) x = b for a "tree of chains" (floating base + up to three serial chains), the shape of this
+// Solve of (L^T D L) x = b for a "tree of chains" (floating base + up to S::NCH <= 4 serial chains), the shape of this
 // robot.  The matrices are tiny (6 + 5 + 4 + 5): eliminating lane-parallel by dof is bound by ~19 dependent hand-offs, and
 // one lane per chain doing its whole block in registers (the previous version) issues ~600 VALU instructions per solve for
 // three busy lanes -- and the kernel is bound by VALU issue.  Now the block of chain c, [T | C | y] with T the chain's own
 // 5 x 5 part, C its 5 x 6 coupling to the base dofs and y its right-hand side, is eliminated by COLUMN: lane 8 c + b holds
-// column b of [C | y] (b = 6: y) and a private copy of T, so the seven columns of the three chains go through the same ~50
+// column b of [C | y] (b = 6: y) and a private copy of T, so the seven columns of every chain go through the same ~50
 // instructions at once.  Then 27 lanes form the base block's Schur complement and right-hand side (one entry each, 15
 // FMAs), every lane factors and solves the 6 x 6 base system (redundantly: no hand-off), and the y-lanes back-substitute.
-// Three LDS hand-offs.  A is the tree layout (read only); VEC holds b on entry and x on exit (LDS); XCH: 132 floats and
-// XSV: 105 floats of LDS scratch.  cs = Statics::cs_pk.
+// Three LDS hand-offs.  A is the tree layout (read only); VEC holds b on entry and x on exit (LDS); XCH: 7 NCH CL + 27 floats
+// and XSV: 7 NCH CL floats of LDS scratch (three chains of five: 132 and 105).  cs = Statics::cs_pk.  A fourth chain (a biped
+// with arms) takes lanes 24 .. 30, idle with three; the base entries stay on lanes 0 .. 26.
 template <class S, int G>
 __device__ __forceinline__ void chain_solve(const float* A, float* VEC, float* XCH, float* XSV, int cs, int lane) {
   constexpr int CL = S::CL > 0 ? S::CL : 1;
-  constexpr int NB6 = 6, P = 7, BASE = 3 * CL * P;   // P: pitch of one (chain, row) record; BASE: base block behind the records
+  constexpr int NCH = S::NCH, NB6 = 6, P = 7, BASE = NCH * CL * P;   // P: pitch of one (chain, row) record; BASE: base block behind the records
+  static_assert(NCH * CL * P <= 12 * S::NVR, "XSV runs over BUF6 | BUF6B");
   const int len = cs & 7, d0 = (cs >> 3) & 31, first = (cs >> 8) & 63, madr = (cs >> 14) & 1023;
-  const int c = (lane >> 3) < 3 ? (lane >> 3) : 0, bcol = lane & 7;
-  const bool col = lane < 24 && bcol < P;   // lanes that hold a column (all zeros when the chain does not exist: len = 0)
+  const int c = (lane >> 3) < NCH ? (lane >> 3) : 0, bcol = lane & 7;
+  const bool col = lane < 8 * NCH && bcol < P;   // lanes that hold a column (all zeros when the chain does not exist: len = 0)
   float T[CL][CL], v[CL], dinv[CL];
   // ---- load T and this lane's column (rows beyond the chain's length are identity padding)
   // (All reads first, unconditionally, and PINNED: left alone the optimiser turns every `valid ? read : constant` into a read under its own exec mask -- twenty blocks of
@@ -701,8 +706,13 @@ __device__ __forceinline__ void chain_solve(const float* A, float* VEC, float* X
   {
     const int tb = (cs >> 24) & 7, tb2 = (cs >> 27) & 7;
     float sum = 0.0f;
+    if constexpr (NCH > 3) {   // (four chains of six: 48 reads in flight at once took the step kernel past 256 VGPRs into scratch; six per batch do not)
+#pragma unroll 6
+      for (int r = 0; r < NCH * CL; r++) sum = fmaf(XSV[r * P + tb], XCH[r * P + tb2], sum);
+    } else {
 #pragma unroll
-    for (int r = 0; r < 3 * CL; r++) sum = fmaf(XSV[r * P + tb], XCH[r * P + tb2], sum);
+      for (int r = 0; r < NCH * CL; r++) sum = fmaf(XSV[r * P + tb], XCH[r * P + tb2], sum);
+    }
     const float* src = lane < 21 ? A + lane : VEC + (lane < 27 ? lane - 21 : 0);
     const float a0 = *src;
     if (lane < 27) XCH[BASE + lane] = a0 - sum;
@@ -749,7 +759,7 @@ __device__ __forceinline__ void chain_solve(const float* A, float* VEC, float* X
   // ---- the y-lanes back-substitute their chain with the base solution
   {
     float x[CL];
-    const bool ycol = lane < 24 && bcol == NB6;
+    const bool ycol = lane < 8 * NCH && bcol == NB6;
 #pragma unroll
     for (int k = 0; k < CL; k++) {
       float val = sv[k];

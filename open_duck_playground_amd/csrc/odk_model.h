@@ -34,9 +34,9 @@ constexpr int NSENSD = 46;
 // filled on the host (odk_engine.hip fill_body_st): the kernel fetches a lane's record with ONE address computation and no
 // dependent loads (as separate tables the joint-derived fields were three dependent loads deep).
 struct BodySt {
-  int level, parent, nchild, child[3], njnt, jd[2], jj[2], jr[2], pathmask, is_path, upmask, path_head;   // jr: CDOF column of the joint's dof (-1: twin, its main dof's column is the same vector)
+  int level, parent, child[4], njnt, jd[2], jj[2], jr[2], pathmask, is_path, upmask, path_head;   // jr: CDOF column of the joint's dof (-1: twin, its main dof's column is the same vector)
   float pos[3], quat[4], ipos[3], inertia[6], ax[2][3];
-  int body;   // the lane's body id (its column in the LDS body images), -1: no body.  40 dwords
+  int body;   // the lane's body id (its column in the LDS body images), -1: no body.  40 dwords (child: up to four, -1 past the body's last)
 };
 
 // Per-lane statics of the step kernels (odk_kernels.h Statics = this + compile-time counts), host-built per lane like the body
@@ -45,6 +45,7 @@ struct LaneSt {
   int j_qadr, j_dadr;                    // joint role (sin/cos phase, Euler)
   // reduced-dof role (lane = reduced dof, DevModel::paired; a model without twins: reduced dof = dof)
   int cs_pk;                             // chain_solve roles: lane 8 c + b -> chain c's length | head depth << 3 | first dof << 8 | row address << 14; lane q -> base entry (tb << 24 | tb2 << 27)
+                                         // (bits 0-23 and 24-29 are disjoint: lanes 24-26 of a fourth chain carry both roles)
   int ch_first, ch_len;                  // the serial chain this lane's reduced dof belongs to (ch_len 0: base dof / no chain)
   int r_on, r_depth, r_Madr, r_ancmask, r_descmask, r_foot;   // reduced tree layout (virtual-tree statics: fetched in the rare path)
   int m_adr[16];                         // M v product: byte offset (from the env's LDS image) of M's entry (lane, j), two per register; unrelated dofs -> a structural zero
@@ -64,7 +65,7 @@ struct DevModel {
   int ls_iterations, iterations;
   // bodies
   int base_body, body_in_tree[MAXB], body_parent[MAXB], body_jntadr[MAXB], body_jntnum[MAXB];
-  int max_level, body_level[MAXB], body_children[MAXB][3], body_nchild[MAXB];
+  int max_level, body_level[MAXB], body_children[MAXB][4];   // (a body's child count: its entries >= 0)
   int max_nonpath_level, body_pathmask[MAXB], body_is_path[MAXB], body_upmask[MAXB], body_path_head[MAXB];   // serial body chains (tables.py)
   // bodies above the serial chains that have children: the subtree sum of np_body[i] = sum over np_src[i][0 .. np_nsrc) of
   // own values (itself, non-chain bodies below it) and chain-head sums (chain heads below it)
@@ -88,7 +89,8 @@ struct DevModel {
   float dof_armature[MAXV], dof_damping[MAXV], dof_frictionloss[MAXV], dof_invweight0[MAXV];
   int M_i[MAXNZ], M_j[MAXNZ];
   int M_ent[MAXNZ];   // packed entry: i | j << 5 | feet moved by dof i << 10 | feet moved by dof j << 12
-  int nchain, chain_first[3], chain_len[3];   // tree of chains below the floating base (0 chains: generic tree)
+  int pad_chains[7];   // (unused: the loader derives the reduced chains below itself.  These and the padding below keep every field the kernels read
+                       // at the offset it had with three chains, so the existing shapes' kernels are the instruction streams they were.)
   // Twin dofs (backlash joints): a hinge v declared right after hinge u on the same body, same anchor, same axis, has the
   // same motion column, cdof_v == cdof_u, so M = P Mr P^T + diag(armature) with P copying each reduced column onto the
   // pair (and likewise the Newton Hessian: contact rows see the pair through the same column, friction-loss / limit rows are
@@ -100,7 +102,7 @@ struct DevModel {
   int red_main[MAXV], red_twin[MAXV];                                  // per reduced dof: main dof, twin dof (-1: none)
   int red_depth[MAXV], red_Madr[MAXV], red_ancmask[MAXV], red_descmask[MAXV], red_foot[MAXV];   // reduced tree layout (as dof_*); feet moved (bit f)
   int rv_depth[MAXV], rv_Madr[MAXV], rv_ancmask[MAXV], rv_descmask[MAXV];                     // reduced VIRTUAL tree (as vdof_*)
-  int nrchain, rchain_first[3], rchain_len[3];                         // serial chains of the reduced tree below the floating base
+  int nrchain; short rchain_first[4], rchain_len[4]; int pad_rchain[2];   // serial chains of the reduced tree below the floating base (<= Shape::NCH <= 4)
   int foot_rchain_first[2], foot_rchain_len[2];                        // the chain that carries foot f: the reduced dofs above the foot are 0..5 + this chain
   // packed entries of the reduced layouts: ri | rj << 5 | feet of ri << 10 | feet of rj << 12 | diagonal << 14 | pair << 15 |
   // main dof of ri << 16; virtual tree: | (address in the reduced M + 1) << 21 (0: structurally zero in M)

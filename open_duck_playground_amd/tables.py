@@ -153,14 +153,14 @@ def build_kernel_tables(a: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
         lst.reverse()
         ancdof[b, :len(lst)] = lst; nancdof[b] = len(lst)
     out["k_body_ancdof"] = ancdof; out["k_body_nancdof"] = nancdof
-    level = -np.ones(nb, np.int32); children = -np.ones((nb, 3), np.int32); nchild = np.zeros(nb, np.int32)
+    level = -np.ones(nb, np.int32); children = -np.ones((nb, 4), np.int32); nchild = np.zeros(nb, np.int32)
     for b in range(nb):
         if in_tree[b]:
             level[b] = chain_len[b]
             if b != base:
                 p_ = bparent[b]
-                if nchild[p_] >= 3:
-                    raise ValueError("more than three child bodies")
+                if nchild[p_] >= 4:
+                    raise ValueError("more than four child bodies")
                 children[p_, nchild[p_]] = b; nchild[p_] += 1
     out["k_body_level"] = level; out["k_body_children"] = children; out["k_body_nchild"] = nchild
     out["k_max_level"] = I([int(level.max())])
@@ -227,9 +227,11 @@ def build_kernel_tables(a: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
             e += 1
         chain_first.append(d); chain_len.append(e - d + 1)
         d = e + 1
-    if not is_chain_tree or len(chain_first) > 3:
+    if is_chain_tree and len(chain_first) > 4:
+        raise ValueError(f"{len(chain_first)} serial chains below the floating base: the kernels take at most four")
+    if not is_chain_tree:
         chain_first, chain_len = [], []
-    out["k_chain_first"] = I(chain_first + [0] * (3 - len(chain_first))); out["k_chain_len"] = I(chain_len + [0] * (3 - len(chain_len)))
+    out["k_chain_first"] = I(chain_first + [0] * (4 - len(chain_first))); out["k_chain_len"] = I(chain_len + [0] * (4 - len(chain_len)))
     out["k_nchain"] = I([len(chain_first)])
     # velocity prefix (mj_comVel): strict ancestors, except that the free joint's rotational dofs
     # see only its three translational dofs

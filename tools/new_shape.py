@@ -12,8 +12,8 @@ the loader (`odk_model_load`, host-only: no GPU needed) whether a compiled kerne
  * `--add`: does it for you -- appends the robot's shape to open_duck_playground_amd/csrc/odk_shapes_user.h (which odk_engine.hip includes when it
    exists: `using ShapeU<k> = Shape<...>;` lines + `#define ODK_USER_SHAPES(X) ...`), checks that the kernels' static_asserts take the shape
    (`hipcc -fsyntax-only`, seconds) and rebuilds the library; `--add --no-build` stops before the rebuild.
- * anything else the kernels do not model (a tree that is not a floating base + <= 3 serial chains of <= 6 dofs, tendons, more than two
-   foot colliders, ...): the loader's own message, by name.
+ * anything else the kernels do not model (a tree that is not a floating base + <= 4 serial chains of <= 6 dofs -- two legs with a foot
+   each, the others (arms, head, tail) without colliding geoms --, tendons, more than two foot colliders, ...): the loader's own message, by name.
 What the XML must carry (the names reference constants.py / base.py look up): sites `imu`, `left_foot`, `right_foot`; geoms
 `left_foot_bottom_tpu`, `right_foot_bottom_tpu`, `floor`; the 15 sensors of open_duck_mini_v2.xml:26-42; keyframe `home` with qpos and ctrl;
 gear-1 position actuators."""
@@ -26,7 +26,8 @@ sys.path.insert(0, ROOT)
 
 
 def shape_line(model, name="ShapeX"):
-    """the `using` line for a model: Shape<nq, nv, nbody, nu, njnt, nM, nH, nrow, depth, virtual depth, cone-only, chain length, optional constraint code>"""
+    """the `using` line for a model: Shape<nq, nv, nbody, nu, njnt, nM, nH, nrow, depth, virtual depth, cone-only, chain length, optional constraint code,
+    chain count> -- the chain count only where the default (three chains) cannot take the tree: a biped with arms (four)"""
     import numpy as np
     from open_duck_playground_amd.tables import build_kernel_tables
     t = build_kernel_tables(model.a)
@@ -36,7 +37,8 @@ def shape_line(model, name="ShapeX"):
     chains = [int(c) for c in np.asarray(t["k_chain_len"])[: int(t["k_nchain"][0])]]
     cl = max(chains) if chains else 0
     dims = (model.nq, model.nv, model.nbody, model.nu, model.njnt, nM, nH, nrow, dt, dv)
-    line = f"using {name} = Shape<{', '.join(str(d) for d in dims)}, false, {cl}, true>;"
+    nch = f", {len(chains)}" if len(chains) > 3 else ""
+    line = f"using {name} = Shape<{', '.join(str(d) for d in dims)}, false, {cl}, true{nch}>;"
     return line, dims, chains
 
 
@@ -114,8 +116,8 @@ def main():
                 engine.build_library(force=True)
                 import subprocess      # (a fresh process: this one holds the old library image)
                 return subprocess.call([sys.executable, os.path.abspath(__file__), xml])
-        if max(chains or [0]) > 6 or len(chains) > 3:
-            print("  NOTE: the chain solve handles a floating base with <= 3 serial chains of <= 6 dofs; this tree will be refused at load")
+        if max(chains or [0]) > 6 or len(chains) > 4:
+            print("  NOTE: the chain solve handles a floating base with <= 4 serial chains of <= 6 dofs; this tree will be refused at load")
         if dims[7] < 71:
             print(f"  NOTE: {dims[7]} constraint rows: the foot-foot routine borrows 282 floats from the four row arrays (4 nrow >= 282, i.e. a robot with >= 12 "
                   "limited hinges + friction-loss dofs in total); this shape will stop at a static_assert")
