@@ -210,6 +210,14 @@ int odk_batch_bind_reward_metrics(odk_batch* b, float* dev);
  * buffer of the batch, so a graph captured earlier follows later calls. */
 int odk_batch_set_imitation_joints(odk_batch* b, const int32_t* frame_joint, int nu);
 
+/* Head joints of the Standing task (standing.py:590-597, rewards.py:105-147): actuator[k] is the actuator that posture command k tracks,
+ * in cmd_range order 3..6 (neck_pitch, head_pitch, head_yaw, head_roll), or -1 for a slot with no joint.  cost_head_pos sums over the
+ * mapped slots; cost_stand_still(ignore_head=True) leaves the mapped actuators out (an all -1 map: a robot without a head, every actuator
+ * counted, head_pos 0).  n must be 4, every entry in [-1, nu - 1], no actuator used twice; otherwise ODK_ERR_INVALID.  The duck's model
+ * shapes start with {5, 6, 7, 8}; other robots start without a map, and their odk_reset / odk_step refuse env_kind = ODK_ENV_STANDING until
+ * it is set.  Synchronous; the map lives in a buffer of the batch, so a graph captured earlier follows later calls. */
+int odk_batch_set_head_joints(odk_batch* b, const int32_t* actuator, int n);
+
 /* Velocity-tracking accumulator: one launch per evaluation step, after odk_step, graph-capturable.  For every env whose
  * acc[e][ODK_TRACK_ENDED] is 0 (its first episode: the Evaluator's `active`) it adds 1 to STEPS and the step's reward to REWARD; on
  * a done step it adds 1 to FALLS when truncation is 0 and sets ENDED; otherwise (a velocity sample: the observation of a done step is

@@ -15,6 +15,8 @@ HIP_JOINT_NAMES = ["left_hip_yaw", "left_hip_roll", "left_hip_pitch", "right_hip
 KNEE_JOINT_NAMES = ["left_knee", "right_knee"]
 JOINTS_ORDER_NO_HEAD = ["left_hip_yaw", "left_hip_roll", "left_hip_pitch", "left_knee", "left_ankle",
                         "right_hip_yaw", "right_hip_roll", "right_hip_pitch", "right_knee", "right_ankle"]
+# the posture commands (cmd_range slots 3..6): the slots of the Standing task's head-joint map (standing.head_joint_map)
+HEAD_SLOTS = ("neck_pitch", "head_pitch", "head_yaw", "head_roll")
 FEET_POS_SENSOR = [f"{site}_pos" for site in FEET_SITES]
 ROOT_BODY = "trunk_assembly"
 GRAVITY_SENSOR = "upvector"

@@ -106,7 +106,7 @@ using ShapeBE = Shape<31, 30, 18, 14, 25, 285, 385, 86, 15, 25, true>;
 // A robot that is not the duck (tests/assets/tail_biped.xml: biped with a five-link tail, 21 dofs, 15 actuators, 19 bodies,
 // box feet): reset / step / physics kernels -- the env kernels' task logic is joystick.py's with the robot's own tables (rec_lay, obs_nobs: sized
 // by Shape::NU; actuators, default pose, sites and sensor addresses from the ModelBlob), the imitation reward with a joint map of its own (odk_batch_set_imitation_joints), Standing
-// stays the duck's.  What adding it
+// with head joints of its own (odk_batch_set_head_joints).  What adding it
 // took: this line, the dispatch lines below that name it (tools/new_shape.py prints both for an XML), and nothing in odk_kernels.h beyond
 // admitting nv = 21 to the chain solver.
 using ShapeC = Shape<22, 21, 19, 15, 16, 156, 181, 78, 10, 15>;
@@ -162,6 +162,7 @@ struct KArgs {
   const XTerms* xt;   // reward-library terms (odk_batch_set_reward_terms), null while every term is off: one uniform pointer test
   float* xmet;        // [nenv][ODK_NXTERM] library metrics (odk_batch_bind_reward_metrics), or null
   const int* imap;    // [nu] imitation joint map (odk_batch_set_imitation_joints): frame joint of actuator u, -1 = not compared
+  const int* hslot;   // [nu] Standing's head joints (odk_batch_set_head_joints): posture-command slot 0..3 of actuator u, -1 = not a head joint
 };
 
 // DR buffer layout per env
@@ -757,11 +758,13 @@ __global__ void __launch_bounds__(64, STEP_WAVES) step_kernel(KArgs a) {
     t_tq = af * af;
     const float da = ACT[u] - INFO[RL.LAST + u];
     t_ar = da * da;
-    const bool leg = u < 5 || u >= 9;
-    const bool counted = c.kind == 0 || leg;   // Standing: cost_stand_still(..., ignore_head=True) (standing.py:590-597)
+    int hs = -1;   // Standing: the posture-command slot of this actuator through the batch's head map (the duck's: actuators 5..8 -> slots
+                   // 0..3), -1 for a leg.  Loaded under the wave-uniform task test, at the epilogue's opaque offset like the imitation map's
+    if (c.kind != 0) hs = reinterpret_cast<const int*>(reinterpret_cast<const char*>(a.hslot) + opaque1)[u];
+    const bool counted = hs < 0;   // Standing: cost_stand_still(..., ignore_head=True) (standing.py:590-597); Joystick: every actuator
     t_pose = counted ? fabsf(jq - mp->key_ctrl[u]) : 0.0f;
     t_vel = counted ? fabsf(jv) : 0.0f;
-    if (c.kind != 0 && !leg) { const float dh = jq - INFO[RL.CMD + 3 + (u - 5)]; t_jp = dh * dh; }   // cost_head_pos (rewards.py:131-147)
+    if (hs >= 0) { const float dh = jq - INFO[RL.CMD + 3 + hs]; t_jp = dh * dh; }   // cost_head_pos (rewards.py:131-147)
     if (c.kind == 0 && c.use_imitation) {   // joints vs the frame's joints through the batch's map (custom_rewards.py:80-88; the duck's:
                                             // joints[:5] ++ joints[9:] vs ref[:5] ++ ref[11:16]).  Its address rides on the epilogue's opaque
                                             // offset: the load stays here instead of being hoisted above the substep loop
@@ -942,6 +945,7 @@ struct odk_batch {
   float* d_xmet = nullptr;                             // odk_batch_bind_reward_metrics (caller-owned)
   int* d_imap = nullptr; bool imap_set = false;        // odk_batch_set_imitation_joints: the batch's device copy; set: a map was given (the duck's
                                                        // shapes start with theirs)
+  int* d_hslot = nullptr; bool hmap_set = false;       // odk_batch_set_head_joints: per actuator, its posture-command slot (-1: none); set as d_imap
 };
 
 extern "C" const char* odk_last_error(void) { return g_err.c_str(); }
@@ -1873,6 +1877,13 @@ extern "C" int odk_batch_create(const odk_model* m, const odk_env_config* cfg, i
     HIPCHK(hipMalloc(&b->d_imap, sizeof(h))); HIPCHK(hipMemcpy(b->d_imap, h, sizeof(h), hipMemcpyHostToDevice));
     b->imap_set = m->shape < 2;
   }
+  {   // Standing's head joints: the duck's actuators 5..8 (neck_pitch, head_pitch, head_yaw, head_roll) for its two shapes, none for another robot
+    int h[MAXU];
+    for (int u = 0; u < MAXU; u++) h[u] = -1;
+    if (m->shape < 2) for (int k = 0; k < 4; k++) h[5 + k] = k;
+    HIPCHK(hipMalloc(&b->d_hslot, sizeof(h))); HIPCHK(hipMemcpy(b->d_hslot, h, sizeof(h), hipMemcpyHostToDevice));
+    b->hmap_set = m->shape < 2;
+  }
   if (!m->hfield.empty()) {   // shared by all envs, L2-resident (256 KB)
     HIPCHK(hipMalloc(&b->d_hfield, m->hfield.size() * sizeof(float)));
     HIPCHK(hipMemcpy(b->d_hfield, m->hfield.data(), m->hfield.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -1883,7 +1894,8 @@ extern "C" int odk_batch_create(const odk_model* m, const odk_env_config* cfg, i
 extern "C" void odk_batch_destroy(odk_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
-  for (void* p : {(void*)b->d_model, (void*)b->d_table, (void*)b->d_recs, (void*)b->d_first, (void*)b->d_dr, (void*)b->d_dbg, (void*)b->d_hfield, (void*)b->d_xt, (void*)b->d_imap}) (void)hipFree(p);
+  for (void* p : {(void*)b->d_model, (void*)b->d_table, (void*)b->d_recs, (void*)b->d_first, (void*)b->d_dr, (void*)b->d_dbg, (void*)b->d_hfield, (void*)b->d_xt, (void*)b->d_imap,
+                  (void*)b->d_hslot}) (void)hipFree(p);
   for (auto& ev : b->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
   delete b;
 }
@@ -1991,19 +2003,25 @@ static void base_args(odk_batch* b, KArgs& a, const odk_outputs* o) {
   a.cmd = b->d_cmd; a.cmd_stride = b->cmd_stride;
   a.xt = b->xt_on ? b->d_xt : nullptr; a.xmet = b->xt_on ? b->d_xmet : nullptr;
   a.imap = b->d_imap;
+  a.hslot = b->d_hslot;
   if (o) { a.obs = o->obs_dev; a.priv = o->priv_dev; a.reward = o->reward_dev; a.done = o->done_dev; a.trunc = o->truncation_dev; a.metrics = o->metrics_dev; }
   to_dev_cfg(b->cfg, a.cfg, b->model.h.nu);
 }
 
 // The env kernels' task logic is joystick.py's with the robot's own tables (actuators, default pose, feet / imu sites, sensor addresses from the
 // ModelBlob).  The imitation reward needs a joint map (custom_rewards.py:80-88) and a reference-motion table of the robot: the duck's shapes start
-// with the duck's map, another robot's odk_reset / odk_step refuse use_imitation until odk_batch_set_imitation_joints gave one.  What stays the
-// duck's: the Standing task's head joints (standing.py:590-597, rewards.py:131-147 index the duck's actuators 5..8) -- refused by name for
-// another robot (odk_physics_step has no task logic)
+// with the duck's map, another robot's odk_reset / odk_step refuse use_imitation until odk_batch_set_imitation_joints gave one.  The Standing task
+// needs a head-joint map (standing.py:590-597, rewards.py:105-147: the posture commands and the joints that cost_stand_still(ignore_head=True)
+// leaves out; the duck's are its actuators 5..8): the duck's shapes start with it, another robot's odk_reset / odk_step refuse Standing until
+// odk_batch_set_head_joints gave one (an all -1 map: a robot without a head).  odk_physics_step has no task logic
 static int env_logic_ok(const odk_batch* b) {
-  if (b->model.shape >= 2 && ((b->cfg.use_imitation && !b->imap_set) || b->cfg.env_kind != ODK_ENV_JOYSTICK))
-    return fail(ODK_ERR_UNSUPPORTED, "%s on a robot that is not the duck: the reference-motion table / the head joints are open_duck_mini_v2's (set use_imitation = 0, env_kind = ODK_ENV_JOYSTICK)",
-                b->cfg.use_imitation ? "use_imitation" : "the Standing task");
+  if (b->model.shape < 2) return ODK_OK;
+  if (b->cfg.use_imitation && !b->imap_set)
+    return fail(ODK_ERR_UNSUPPORTED, "use_imitation on a robot that is not the duck without an imitation joint map: the reference-motion table is open_duck_mini_v2's "
+                "(give the robot's map with odk_batch_set_imitation_joints, or set use_imitation = 0)");
+  if (b->cfg.env_kind != ODK_ENV_JOYSTICK && !b->hmap_set)
+    return fail(ODK_ERR_UNSUPPORTED, "the Standing task on a robot that is not the duck without a head-joint map: the head joints are open_duck_mini_v2's "
+                "(give the robot's with odk_batch_set_head_joints -- all -1 for none -- or set env_kind = ODK_ENV_JOYSTICK)");
   return ODK_OK;
 }
 
@@ -2112,6 +2130,25 @@ extern "C" int odk_batch_set_imitation_joints(odk_batch* b, const int32_t* frame
   HIPCHK(hipDeviceSynchronize());   // no step in flight reads the buffer while it changes
   HIPCHK(hipMemcpy(b->d_imap, h, sizeof(h), hipMemcpyHostToDevice));
   b->imap_set = true;
+  return ODK_OK;
+}
+
+extern "C" int odk_batch_set_head_joints(odk_batch* b, const int32_t* actuator, int n) {
+  if (!b || !actuator) return fail(ODK_ERR_INVALID, "null argument");
+  if (n != 4) return fail(ODK_ERR_INVALID, "odk_batch_set_head_joints: %d entries, the map has 4 (neck_pitch, head_pitch, head_yaw, head_roll)", n);
+  const int nu = b->model.h.nu;
+  int h[MAXU];
+  for (int u = 0; u < MAXU; u++) h[u] = -1;
+  for (int k = 0; k < 4; k++) {
+    const int u = actuator[k];
+    if (u < -1 || u >= nu) return fail(ODK_ERR_INVALID, "odk_batch_set_head_joints: slot %d maps to actuator %d (valid: -1 .. %d)", k, u, nu - 1);
+    if (u >= 0 && h[u] >= 0) return fail(ODK_ERR_INVALID, "odk_batch_set_head_joints: actuator %d is used twice (slots %d and %d)", u, h[u], k);
+    if (u >= 0) h[u] = k;
+  }
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipDeviceSynchronize());   // no step in flight reads the buffer while it changes
+  HIPCHK(hipMemcpy(b->d_hslot, h, sizeof(h), hipMemcpyHostToDevice));
+  b->hmap_set = true;
   return ODK_OK;
 }
 

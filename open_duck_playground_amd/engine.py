@@ -154,6 +154,7 @@ def load_library() -> C.CDLL:
     L.odk_batch_set_reward_terms.argtypes = [P, C.POINTER(RewardTerms)]
     L.odk_batch_bind_reward_metrics.argtypes = [P, P]
     L.odk_batch_set_imitation_joints.argtypes = [P, C.POINTER(C.c_int32), C.c_int]
+    L.odk_batch_set_head_joints.argtypes = [P, C.POINTER(C.c_int32), C.c_int]
     L.odk_tracking_accumulate.argtypes = [P, P, P, P, P, P, P]
     L.odk_batch_get_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_set_state.argtypes = [P, FP, FP, FP]
@@ -198,7 +199,8 @@ EXPORTED_SYMBOLS = (
     "odk_last_error", "odk_default_config", "odk_default_config_standing", "odk_obs_sizes", "odk_model_load", "odk_model_free", "odk_model_dims", "odk_model_obs_sizes", "odk_batch_lanes", "odk_model_reduced", "odk_model_body_lanes",
     "odk_model_env_lds_floats", "odk_batch_create",
     "odk_batch_destroy", "odk_batch_set_config", "odk_batch_set_param", "odk_reset", "odk_step", "odk_physics_step",
-    "odk_batch_bind_commands", "odk_batch_set_reward_terms", "odk_batch_bind_reward_metrics", "odk_batch_set_imitation_joints", "odk_tracking_accumulate",
+    "odk_batch_bind_commands", "odk_batch_set_reward_terms", "odk_batch_bind_reward_metrics", "odk_batch_set_imitation_joints", "odk_batch_set_head_joints",
+    "odk_tracking_accumulate",
     "odk_batch_get_state", "odk_batch_set_state", "odk_batch_get_debug", "odk_set_debug_dump", "odk_batch_lds_size",
     "odk_batch_get_lds", "odk_lds_offset", "odk_batch_record_size", "odk_batch_get_records", "odk_batch_set_records", "odk_batch_timing", "odk_gae", "odk_ppo_head",
     "odk_policy_sample", "odk_adam_clip", "odk_silu_bwd_colsum", "odk_colsum_partial", "odk_colsum_finalize", "odk_gather_rows", "odk_dw_gemm",
@@ -901,6 +903,13 @@ class Batch:
         captured earlier follows it.  OdkError for a map of the wrong length, an entry outside [-1, 15] or a frame joint used twice."""
         m = np.ascontiguousarray(np.asarray(seq).reshape(-1), np.int32)
         _chk(self.L.odk_batch_set_imitation_joints(self._b, m.ctypes.data_as(C.POINTER(C.c_int32)), len(m)))
+
+    def set_head_joints(self, seq):
+        """Head joints of the Standing task (`odk_batch_set_head_joints`): entry k is the actuator that posture command k tracks (neck_pitch,
+        head_pitch, head_yaw, head_roll), -1 for a slot with no joint (standing.head_joint_map makes one).  Synchronous; a graph captured earlier
+        follows it.  OdkError for a map that is not 4 entries long, an entry outside [-1, nu - 1] or an actuator used twice."""
+        m = np.ascontiguousarray(np.asarray(seq).reshape(-1), np.int32)
+        _chk(self.L.odk_batch_set_head_joints(self._b, m.ctypes.data_as(C.POINTER(C.c_int32)), len(m)))
 
     def tracking_accumulate(self, acc):
         """One `odk_tracking_accumulate` launch over this step's outputs into `acc` ([nenv, TRACK_NACC] float32, zeroed before

@@ -286,6 +286,7 @@ class Joystick:
             self._model = constants.task_to_model(task)      # KeyError for unknown task names
         self._robot = constants.robot_of(self._model)
         self._motion = self._load_reference_motion()
+        self._head_map = self._load_head_joints()
         cone = self._config.get("cone", None)
         if cone is not None:      # BUILD-DEFINED switch (the reference edits the XML's <option cone=...>): "pyramidal" | "elliptic", optional "impratio"
             if cone not in ("pyramidal", "elliptic"):
@@ -305,6 +306,8 @@ class Joystick:
                                    prm=self._motion.prm() if self._motion is not None else None)
         if self._motion is not None:
             self._batch.set_imitation_joints(self._imitation_map)
+        if self._head_map is not None:
+            self._batch.set_head_joints(self._head_map)
         self._batch.set_reward_terms(to_reward_terms(self._config, self._model.nu, self._reward_slots()))
         scales = self._config.reward_config.scales
         # State.metrics names of the Batch.xmetrics columns (None: the term is off)
@@ -326,6 +329,17 @@ class Joystick:
         self._imitation_map = imitation_joint_map(self._model, motion, self._config.get("imitation_joints", None),
                                                   self._config.get("imitation_ignore", None))
         return motion
+
+    def _load_head_joints(self):
+        """The Standing task's `head_joints` map (Standing.__init__), or None: the Joystick task has no posture cost (ignore_head=False)."""
+        if self._config.get("head_joints", None) is not None:
+            raise ValueError("config head_joints: the Joystick task has no head-joint map (cost_stand_still(ignore_head=False)); it is the Standing task's")
+        return None
+
+    @property
+    def head_joints(self):
+        """The Standing task's head-joint map set on the batch (actuator per posture-command slot, -1: none), or None (the model's default)."""
+        return self._head_map
 
     @property
     def reference_motion(self):

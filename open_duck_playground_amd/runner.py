@@ -65,13 +65,41 @@ def imitation_overrides(args) -> dict:
     return out
 
 
+def parse_head_joints(spec: str) -> dict:
+    """--head_joints SLOT=JOINT[,SLOT=JOINT...] | none -> the Standing config key head_joints ({} for `none`: no head joints).  The names
+    are resolved against the robot by standing.head_joint_map."""
+    if spec.strip().lower() == "none":
+        return {}
+    out = {}
+    for item in spec.split(","):
+        if not item.strip():
+            continue
+        k, v = _parse_kv(item, "--head_joints")
+        if k in out:
+            raise ValueError(f"--head_joints {k}: slot given twice")
+        out[k] = v
+    if not out:
+        raise ValueError(f"--head_joints {spec!r}: expected SLOT=JOINT[,SLOT=JOINT...] or none")
+    return out
+
+
+def head_joint_overrides(args) -> dict:
+    """--head_joints -> the Standing config key head_joints (nothing when the flag is not given); ValueError with another --env."""
+    spec = getattr(args, "head_joints", None)
+    if spec is None:
+        return {}
+    if args.env != "standing":
+        raise ValueError(f"--head_joints is a flag of --env standing (the {args.env} env has no head-joint map)")
+    return {"head_joints": parse_head_joints(spec)}
+
+
 def config_overrides(args):
     """The env's config_overrides from the command line (None when nothing is overridden)."""
     overrides = {"hfield_up_normals_only": True} if getattr(args, "hfield_up_normals_only", False) else None
     if getattr(args, "cone", None):
         overrides = dict(overrides or {}, cone=args.cone)
     overrides = dict(overrides or {}, **reward_overrides(args.env, getattr(args, "reward_scale", None), getattr(args, "reward_param", None)))
-    return dict(overrides, **imitation_overrides(args)) or None
+    return dict(overrides, **imitation_overrides(args), **head_joint_overrides(args)) or None
 
 
 def add_imitation_flags(parser) -> None:
@@ -82,6 +110,13 @@ def add_imitation_flags(parser) -> None:
                         help="the reference motion's frame joints in frame order (default: the duck's 16 for the duck, the actuated joints otherwise)")
     parser.add_argument("--imitation_ignore", type=str, default=None, metavar="A,B,...",
                         help="frame joints the imitation reward leaves out (default: the duck's antennas for the duck, none otherwise)")
+
+
+def add_head_joint_flag(parser) -> None:
+    parser.add_argument("--head_joints", type=str, default=None, metavar="SLOT=JOINT[,SLOT=JOINT...]|none",
+                        help="--env standing on a robot of your own: the joints that track the posture commands (slots neck_pitch, head_pitch, "
+                             "head_yaw, head_roll; a slot left out has none), or `none` for a robot without head joints.  Default: the duck's "
+                             "head for the duck; another robot needs the flag")
 
 
 class OpenDuckMiniV2Runner:
@@ -110,6 +145,8 @@ class OpenDuckMiniV2Runner:
         self.env = available_envs[args.env](task=args.task, num_envs=n_local, device=device, env_id_offset=self.rank * n_local, config_overrides=overrides, **extra)
         if getattr(self.env, "reference_motion", None) is not None:
             print(self.env.reference_motion.describe())
+        if hasattr(self.env, "describe_head_joints"):
+            print(self.env.describe_head_joints())
         self.action_size = self.env.action_size
         self.obs_size = int(self.env.observation_size["state"][0])
         # one generator per (seed, rank, stream): stream 0 = training envs, 1 = evaluation envs (ppo/train.py)
@@ -182,11 +219,22 @@ def build_parser() -> argparse.ArgumentParser:
                         help="repeatable: a parameter of the library terms: base_height_target, max_foot_height, air_time_range=MIN,MAX, "
                              "pose_weights=W1,...,Wnu, soft_joint_pos_limit_factor")
     add_imitation_flags(parser)
+    add_head_joint_flag(parser)
     return parser
 
 
-def main():
-    args = build_parser().parse_args()
+def check_env_flags(parser, args) -> None:
+    """Refuses a flag of another --env right after parsing, before any GPU or process-group set-up (argparse error, exit status 2)."""
+    try:
+        head_joint_overrides(args)
+    except ValueError as e:
+        parser.error(str(e))
+
+
+def main(argv=None):
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    check_env_flags(parser, args)
     runner = OpenDuckMiniV2Runner(args)
     try:
         runner.train()

@@ -8,7 +8,9 @@ command (:652-654), base-velocity reset noise +-0.5 (:247).
 """
 from __future__ import annotations
 
-from . import engine
+import numpy as np
+
+from . import constants, engine
 from .joystick import ConfigDict, Joystick, State, to_engine_config  # noqa: F401
 
 USE_IMITATION_REWARD = False      # reference standing.py:42
@@ -34,8 +36,68 @@ def default_config() -> ConfigDict:
     )
 
 
+def head_joint_map(model, head_joints):
+    """The `head_joints` config key -> odk_batch_set_head_joints' map: for each slot of constants.HEAD_SLOTS (neck_pitch, head_pitch,
+    head_yaw, head_roll) the actuator of the joint named for it, -1 for a slot without one ({} -> a robot without head joints).
+    ValueError names an unknown slot, a name that is not a joint, a joint no actuator drives, a joint that more than one actuator drives (the
+    map holds one actuator per slot: the others would stay in cost_stand_still), a joint used twice and a leg joint
+    (constants.robot_of(model).joints_order_no_head: cost_stand_still(ignore_head=True) leaves only head joints out)."""
+    if not isinstance(head_joints, dict):
+        raise ValueError(f"config head_joints = {head_joints!r}: a dict from head slot ({', '.join(constants.HEAD_SLOTS)}) to joint name")
+    a = model.a
+    jn = [str(n) for n in a["names_jnt"]]
+    trn = [int(j) for j in np.asarray(a["actuator_trnid"]).reshape(model.nu, -1)[:, 0]]
+    legs = set(constants.robot_of(model).joints_order_no_head)
+    out, used = [-1] * len(constants.HEAD_SLOTS), {}
+    for slot, joint in head_joints.items():
+        if slot not in constants.HEAD_SLOTS:
+            raise ValueError(f"head_joints: unknown slot {slot!r} (slots: {', '.join(constants.HEAD_SLOTS)})")
+        joint = str(joint)
+        if joint not in jn:
+            raise ValueError(f"head_joints {slot}={joint}: the robot has no joint {joint!r}")
+        drivers = [u for u, j in enumerate(trn) if j == jn.index(joint)]
+        if not drivers:
+            raise ValueError(f"head_joints {slot}={joint}: no actuator drives joint {joint!r}")
+        if len(drivers) > 1:
+            raise ValueError(f"head_joints {slot}={joint}: joint {joint!r} is driven by {len(drivers)} actuators ({', '.join(map(str, drivers))}); "
+                             "the map takes one actuator per slot")
+        if joint in used:
+            raise ValueError(f"head_joints {slot}={joint}: joint {joint!r} is used twice ({used[joint]} and {slot})")
+        if joint in legs:
+            raise ValueError(f"head_joints {slot}={joint}: {joint!r} is a leg joint (cost_stand_still(ignore_head=True) counts every leg joint)")
+        used[joint] = slot
+        out[constants.HEAD_SLOTS.index(slot)] = drivers[0]
+    return out
+
+
+def to_standing_engine_config(cfg: ConfigDict, autoreset: bool = True, lanes_per_env: int = 0, head_map=None) -> engine.EnvConfig:
+    """reference config -> odk_env_config for the Standing task; `head_map` (head_joint_map, or None: the model's default): a posture
+    command that no joint tracks keeps its draw, from the range [0, 0]."""
+    c = to_engine_config(cfg, autoreset, lanes_per_env, standing=True, reward_slots=REWARD_SLOTS,
+                         use_imitation=USE_IMITATION_REWARD, use_motor_speed_limits=False)
+    for k, u in enumerate(head_map or ()):
+        if u < 0:
+            c.cmd_range[3 + k][0] = c.cmd_range[3 + k][1] = 0.0
+    return c
+
+
+def describe_head_joint_map(model, hmap) -> str:
+    """One line: each slot with its joint and actuator, `-` for a slot without one."""
+    act = [str(n) for n in model.a["names_actuator"]]
+    jn = [str(n) for n in model.a["names_jnt"]]
+    trn = [int(j) for j in np.asarray(model.a["actuator_trnid"]).reshape(model.nu, -1)[:, 0]]
+    parts = [f"{slot}={jn[trn[u]]} (actuator {u} {act[u]})" if u >= 0 else f"{slot}=-" for slot, u in zip(constants.HEAD_SLOTS, hmap)]
+    return "head joints: " + ", ".join(parts)
+
+
 class Standing(Joystick):
-    """Standing policy (reference standing.py:103)."""
+    """Standing policy (reference standing.py:103).
+
+    Head joints (BUILD-DEFINED config key `head_joints`, not in default_config(); it travels in `config_overrides` and the evaluation
+    sibling inherits it): a dict from posture-command slot (neck_pitch, head_pitch, head_yaw, head_roll) to the joint that tracks it,
+    e.g. {"neck_pitch": "neck_a", "head_yaw": "neck_b"}; {} for a robot without head joints.  cost_head_pos compares the mapped joints
+    with their commands, cost_stand_still(ignore_head=True) leaves them out, and a slot without a joint samples the range [0, 0] (same
+    draws).  Without the key the duck keeps its own head (actuators 5..8) and another robot is refused."""
 
     METRIC_NAMES = METRIC_NAMES
 
@@ -51,6 +113,15 @@ class Standing(Joystick):
                 raise ValueError(f"config {k}: the Standing task has no imitation reward (standing.py:42)")
         return None
 
+    def _load_head_joints(self):
+        spec = self._config.get("head_joints", None)
+        return None if spec is None else head_joint_map(self._model, spec)
+
     def _engine_config(self, autoreset: bool, lanes_per_env: int) -> engine.EnvConfig:
-        return to_engine_config(self._config, autoreset, lanes_per_env, standing=True, reward_slots=REWARD_SLOTS,
-                                use_imitation=USE_IMITATION_REWARD, use_motor_speed_limits=False)
+        return to_standing_engine_config(self._config, autoreset, lanes_per_env, self._head_map)
+
+    def describe_head_joints(self) -> str:
+        """The head-joint map in use, one line."""
+        if self._head_map is None:
+            return "head joints: the duck's (actuators 5..8)" if self._robot.is_open_duck else "head joints: none set"
+        return describe_head_joint_map(self._model, self._head_map)

@@ -119,13 +119,14 @@ def save_obs(path: str, obs: np.ndarray) -> None:
 
 def config_overrides(args) -> Dict:
     """The env's config_overrides from the command line."""
-    from .runner import imitation_overrides
+    from .runner import head_joint_overrides, imitation_overrides
     overrides = {"episode_length": int(args.episode_length)}
     if args.hfield_up_normals_only:
         overrides["hfield_up_normals_only"] = True
     if args.cone:
         overrides["cone"] = args.cone
     overrides.update(imitation_overrides(args))
+    overrides.update(head_joint_overrides(args))
     return overrides
 
 
@@ -215,6 +216,8 @@ def run(args, out=sys.stdout) -> Dict:
     motion = getattr(env, "reference_motion", None)
     if motion is not None:
         print(motion.describe(), file=sys.stderr)      # stdout may carry the JSON report
+    if hasattr(env, "describe_head_joints"):
+        print(env.describe_head_joints(), file=sys.stderr)
     net = load_networks(args.checkpoint, env, dev)
     cmd = torch.from_numpy(command_blocks(commands, E)).to(dev)
     env.set_commands(cmd)
@@ -263,8 +266,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--xml", type=str, default=None, help="a robot of your own: its MJCF (as runner)")
     p.add_argument("--cone", choices=["pyramidal", "elliptic"], default=None, help="friction cone (as runner)")
     p.add_argument("--hfield_up_normals_only", action="store_true", help="height-field contact reading (as runner)")
-    from .runner import add_imitation_flags
+    from .runner import add_head_joint_flag, add_imitation_flags
     add_imitation_flags(p)
+    add_head_joint_flag(p)
     p.add_argument("--command", nargs="+", type=float, action="append", metavar="V",
                    help="vx vy wz [neck_pitch head_pitch head_yaw head_roll]; repeat for more commands")
     p.add_argument("--grid", type=str, default=None, help="a grid of commands: vx=a:b:n,wz=c:d:m (axes vx vy wz neck_pitch head_pitch head_yaw head_roll)")
@@ -279,7 +283,10 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    from .runner import check_env_flags
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    check_env_flags(parser, args)
     run(args)
 
 
