@@ -4,6 +4,8 @@ import copy
 import pytest
 import torch
 
+from test_learner_sizes_host import check_fused_mlp, mlp_params as _mlp_params, packed_reference as _packed_reference
+
 pytestmark = pytest.mark.gpu
 
 
@@ -83,93 +85,12 @@ def test_dw_gemm_matches_torch_mm_and_is_reproducible():
     assert abs(got - want) < 1e-5 * want and float((flat.view(o, i).double() - dz.double().t() @ h.double()).abs().max()) < 1e-3
 
 
-def _mlp_params(n_in, n_out, g):
-    """Random swish MLP n_in -> 512 -> 256 -> 128 -> n_out as the learner keeps it: one flat buffer (W1 b1 W2 b2 ...), the weight
-    table, and the two packed copies built by odk_pack_weights."""
-    from open_duck_playground_amd import engine
-    widths = (n_in,) + engine.MLP_HIDDEN + (n_out,)
-    W = [torch.randn(widths[l + 1], widths[l], device="cuda", generator=g) * (1.5 / widths[l] ** 0.5) for l in range(4)]
-    b = [0.3 * torch.randn(widths[l + 1], device="cuda", generator=g) for l in range(4)]
-    offs, off = [], 0
-    for l in range(4):
-        offs.append(off); off += W[l].numel() + b[l].numel()
-    flat = torch.cat([t.reshape(-1) for l in range(4) for t in (W[l], b[l])])
-    table = engine.WeightTable([(offs[l], widths[l + 1], widths[l], l > 0) for l in range(4)])
-    pf, pb = torch.zeros(table.fwd_size, device="cuda"), torch.zeros(table.bwd_size, device="cuda")
-    engine.pack_weights(flat, pf, pb, table)
-    return widths, W, b, flat, table, pf, pb
-
-
-def _packed_reference(Wk):
-    """[K, N] matrix (reduction index first) -> the packed layout [pad16(K) / 4][N][4], zero padding."""
-    K, N = Wk.shape
-    K16 = (K + 15) // 16 * 16
-    full = torch.zeros(K16, N, device=Wk.device)
-    full[:K] = Wk
-    return full.view(K16 // 4, 4, N).permute(0, 2, 1).contiguous().reshape(-1)
-
-
 @pytest.mark.parametrize("n, n_in, n_out", [(320, 101, 28), (336, 212, 1), (5120, 85, 28), (77, 153, 1)])   # whole / ragged tiles, odd and even K, Joystick and Standing sizes
 def test_fused_mlp_matches_torch(n, n_in, n_out):
     """odk_mlp_forward / odk_mlp_backward (one launch per direction for the whole swish MLP) vs float64 torch: output, hidden
     activations, swish', every dz, and the bias gradients through odk_colsum_fold; inference-only mode writes `out` alone;
-    the packed weight copies against their definition."""
-    from open_duck_playground_amd import engine
-    g = torch.Generator(device="cuda").manual_seed(n + n_in)
-    widths, W, b, flat, table, pf, pb = _mlp_params(n_in, n_out, g)
-    for l in range(4):
-        assert torch.equal(table.fwd_view(pf, l), _packed_reference(W[l].t()))
-        if l > 0:
-            assert torch.equal(table.bwd_view(pb, l), _packed_reference(W[l]))
-    assert table.bwd_view(pb, 0) is None
-    x = torch.randn(n, n_in, device="cuda", generator=g)
-    dout = torch.randn(n, n_out, device="cuda", generator=g)
-    tiles = (n + 15) // 16
-    buf = lambda w: torch.full((n, w), float("nan"), device="cuda")
-    wf, wb = [table.fwd_view(pf, l) for l in range(4)], [table.bwd_view(pb, l) for l in range(4)]
-    tb = engine.FusedMLP.train_buffers(n, n_in, n_out, "cuda")
-    for t in [tb["xp"], tb["doutp"]] + tb["h"] + tb["g"] + tb["dz"] + tb["bias_partial"]:
-        t.fill_(float("nan"))
-    raw = dict(x=x, wf=wf, wb=wb, b=b, out=buf(n_out), dout=dout, **tb)
-    op = engine.FusedMLP([raw])
-    op.forward(); op.backward()
-    # quad-row buffers: rows past the batch are zeros (the weight-gradient launch reads whole tiles); unpack the rest
-    np_ = engine.quad_rows(n)
-    for key in ("h", "g", "dz"):
-        for l, w in enumerate(engine.MLP_HIDDEN):
-            assert float(engine.quad_unpack(raw[key][l], np_, w)[n:].abs().sum()) == 0.0
-    assert torch.equal(engine.quad_unpack(raw["xp"], n, n_in), x) and torch.equal(engine.quad_unpack(raw["doutp"], n, n_out), dout)
-    assert float(engine.quad_unpack(raw["doutp"], np_, n_out)[n:].abs().sum()) == 0.0
-    net = dict(out=raw["out"], bias_partial=raw["bias_partial"], **{key: [engine.quad_unpack(raw[key][l], n, w) for l, w in enumerate(engine.MLP_HIDDEN)]
-                                                                    for key in ("h", "g", "dz")})
-    # float64 reference
-    zs, hs = [], [x.double()]
-    for l in range(4):
-        z = hs[-1] @ W[l].double().t() + b[l].double()
-        zs.append(z)
-        if l < 3:
-            hs.append(z * torch.sigmoid(z))
-    rel = lambda a, ref: float((a.double() - ref).abs().max() / ref.abs().max().clamp_min(1e-30))
-    assert rel(net["out"], zs[3]) < 2e-6
-    dz_ref, dzl = [None] * 3, dout.double()
-    for l in (2, 1, 0):
-        sg = torch.sigmoid(zs[l])
-        gref = sg * (1 + zs[l] * (1 - sg))
-        assert rel(net["h"][l], hs[l + 1]) < 2e-6 and rel(net["g"][l], gref) < 2e-6
-        dzl = (dzl @ W[l + 1].double()) * gref
-        dz_ref[l] = dzl
-        assert rel(net["dz"][l], dzl) < 3e-6
-    gb = [torch.empty(w, device="cuda") for w in widths[1:]]
-    engine.ColsumFold([(net["bias_partial"][l], gb[l]) for l in range(4)], tiles)()
-    for l in range(3):
-        assert rel(gb[l], dz_ref[l].sum(0)) < 3e-6
-    assert rel(gb[3], dout.double().sum(0)) < 3e-6
-    # inference only: nothing but `out`
-    inf = dict(x=x, wf=wf, b=b, out=buf(n_out))
-    engine.FusedMLP([inf]).forward()
-    assert torch.equal(inf["out"], net["out"])
-    with pytest.raises(engine.OdkError):
-        engine.FusedMLP([dict(x=torch.zeros(8, 300, device="cuda"), wf=wf, b=b, out=buf(n_out)[:8])])
+    the packed weight copies against their definition.  The body is shared with the size sweep of test_gpu_learner_sizes.py."""
+    check_fused_mlp(n, n_in, n_out)
 
 
 def test_fused_mlp_two_networks_one_launch_and_adam_keeps_the_packed_copies():
@@ -612,23 +533,27 @@ def test_gae_treats_any_nonzero_flag_as_set_in_every_kernel():
 
 
 def test_fused_policy_inference_matches_the_module():
-    """Rollout-side policy inference through the whole-network kernel == the torch module (same parameters, after an update too)."""
+    """Rollout-side policy inference through the whole-network kernel == the torch module (same parameters, after an update too), at the
+    duck's, biped12's and Standing biped_arms' sizes."""
     from open_duck_playground_amd.ppo.learner import fused_policy
     from open_duck_playground_amd.ppo.networks import PPONetworks
-    torch.manual_seed(2)
-    net = PPONetworks(101, 212, 14).cuda()
-    obs = torch.randn(300, 101, device="cuda")
-    net.norm_obs.update(obs * 3 + 1)
-    fp = fused_policy(net, 300)
-    assert fp is not None and fused_policy(net, 300) is fp
-    for rnd in range(2):
-        fp.refresh()
-        ref = net.policy(net.norm_obs(obs))
-        torch.testing.assert_close(fp(obs), ref, rtol=2e-5, atol=2e-6)      # raw observations in: the normaliser runs inside the kernel's load
-        with torch.no_grad():
-            for p_ in net.policy.parameters():
-                p_.mul_(1.01)
-    assert fused_policy(PPONetworks(101, 212, 14, policy_hidden=(64, 64)).cuda(), 8) is None
+    for obs_w, priv_w, A in ((101, 212, 14), (89, 194, 12), (95, 169, 16)):
+        torch.manual_seed(2)
+        net = PPONetworks(obs_w, priv_w, A).cuda()
+        obs = torch.randn(300, obs_w, device="cuda")
+        net.norm_obs.update(obs * 3 + 1)
+        fp = fused_policy(net, 300)
+        assert fp is not None and fused_policy(net, 300) is fp
+        for rnd in range(2):
+            fp.refresh()
+            ref = net.policy(net.norm_obs(obs))
+            torch.testing.assert_close(fp(obs), ref, rtol=2e-5, atol=2e-6)      # raw observations in: the normaliser runs inside the kernel's load
+            with torch.no_grad():
+                for p_ in net.policy.parameters():
+                    p_.mul_(1.01)
+        assert fused_policy(PPONetworks(obs_w, priv_w, A, policy_hidden=(64, 64)).cuda(), 8) is None
+    assert fused_policy(PPONetworks(230, 230, 16).cuda(), 8) is None          # an input wider than the kernel's 224 (ODK_MLP_MAX_IN)
+    assert fused_policy(PPONetworks(113, 230, 16).cuda(), 8) is not None      # Joystick biped_arms: the POLICY's 113 observations fit; it is the learner that falls back
 
 
 def test_tiny_minibatch_falls_back_to_the_library_path():
