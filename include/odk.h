@@ -232,6 +232,48 @@ enum { ODK_TRACK_ENDED = 0, ODK_TRACK_STEPS = 1, ODK_TRACK_SAMPLES = 2, ODK_TRAC
 int odk_tracking_accumulate(const odk_batch* b, const float* priv_dev, const float* reward_dev, const float* done_dev,
                             const float* truncation_dev, float* acc_dev, void* stream);
 
+/* Caller-given pushes (replaces the mouse of mujoco_infer.py's viewer: shove the robot, see whether the policy stays up).  push_dev:
+ * [nenv, row_stride] device floats on the batch's device, row e = the world-frame velocity kick (dvx, dvy) in m/s that env e's NEXT
+ * odk_step adds to qvel[0:2]; row_stride >= 2.  NULL unbinds (the sampled push of push_config again).  While bound:
+ *   - every odk_step reads env e's row where the sampled push * push_magnitude entered (joystick.py:381-398): before the motor targets
+ *     and the substeps, on the state the step starts from -- after a done step that is the auto-reset's state; a stream-ordered write to
+ *     the buffer between two steps is what the next step applies, and a row left non-zero is applied again by every step;
+ *   - the sampled push is not applied: push_enable and the interval gate do not matter;
+ *   - every random draw is still made, in the same order (theta and magnitude are drawn and dropped): push_step, push_interval_steps,
+ *     the rng counter and the noise, command and reset streams are those of an unbound run;
+ *   - info["push"] (record field `push`) holds the kick's unit direction, 0 0 for a zero row (the reference keeps a direction there, not
+ *     a velocity);
+ *   - odk_reset is untouched (push starts at 0).
+ * Only the floating base's planar velocity is touched, so this works for every robot the engine steps.  The buffer stays the caller's
+ * and must outlive the binding.  The pointer is a kernel argument: a captured graph keeps the pointer it was captured with (and reads
+ * that buffer's current contents at every replay); bind before capturing.  row_stride < 2, or memory that is not device memory of the
+ * batch's device: ODK_ERR_INVALID, and the binding stays as it was. */
+int odk_batch_bind_pushes(odk_batch* b, const float* push_dev, int row_stride);
+
+/* Push-recovery accumulator: one launch per evaluation step, graph-capturable, issued after odk_step and BEFORE odk_tracking_accumulate
+ * (track_acc_dev [nenv, ODK_TRACK_NACC] is that function's accumulator: its ENDED slot then still says whether env e's first episode was
+ * running when this step began, and its STEPS slot counts the first-episode steps before this one).  Env e's row of acc_dev
+ * [nenv, ODK_PUSH_NACC], zeroed by the caller before the first step, is updated only during e's first episode:
+ *   PUSHED          becomes 1 at the first step whose bound push row was non-zero (the pushed step; the row is read as the step left it)
+ *   PUSH_AT         number of first-episode steps before that step
+ *   FELL            1 when the first episode ends with done and no truncation, at or after the pushed step
+ *   STEPS_TO_FALL   steps from the pushed step to that done step, counting both (1: it fell in the pushed step)
+ *   LAST_OFF        steps from the pushed step, counting both, to the latest velocity sample at or after it whose planar velocity error
+ *                   hypot(vx - cmd_x, vy - cmd_y) exceeded lin_tol or whose yaw-rate error |wz - cmd_wz| exceeded ang_tol; 0 if none.
+ *                   The recovery time, causal: a running "last seen", final once the episode is over
+ *   PEAK_LIN_ERR, PEAK_ANG_ERR   the maxima of those two errors over the velocity samples at or after the pushed step
+ *   PRE_LIN_ERR_SUM, PRE_SAMPLES sum of the planar error over, and count of, the velocity samples before the pushed step: the policy's own
+ *                   tracking error, against which the tolerances can be judged.  The sum is compensated (Kahan), so that SUM stays within an ulp of
+ *                   the true sum over any number of samples; PRE_LIN_ERR_LOW holds the part SUM dropped (SUM + LOW in float64 is closer still)
+ * A velocity sample is odk_tracking_accumulate's (a step that is not done), the achieved velocities are the ones it reads (priv_dev
+ * [nenv, npriv] of this step: gyro at row offset nobs, local linear velocity at nobs + 9).  done_dev / truncation_dev: [nenv].  Needs bound
+ * commands and bound pushes: ODK_ERR_INVALID otherwise, and nothing is launched. */
+#define ODK_PUSH_NACC 10
+enum { ODK_PUSH_PUSHED = 0, ODK_PUSH_PUSH_AT = 1, ODK_PUSH_FELL = 2, ODK_PUSH_STEPS_TO_FALL = 3, ODK_PUSH_LAST_OFF = 4, ODK_PUSH_PEAK_LIN_ERR = 5,
+       ODK_PUSH_PEAK_ANG_ERR = 6, ODK_PUSH_PRE_LIN_ERR_SUM = 7, ODK_PUSH_PRE_SAMPLES = 8, ODK_PUSH_PRE_LIN_ERR_LOW = 9 };
+int odk_push_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
+                        const float* track_acc_dev, float lin_tol, float ang_tol, float* acc_dev, void* stream);
+
 /* mjx_env.step alone (physics only, n_substeps, ctrl = ctrl_dev [nenv, nu]); for parity tests */
 int odk_physics_step(odk_batch* b, const float* ctrl_dev, int n_substeps, void* stream);
 

@@ -163,6 +163,8 @@ struct KArgs {
   float* xmet;        // [nenv][ODK_NXTERM] library metrics (odk_batch_bind_reward_metrics), or null
   const int* imap;    // [nu] imitation joint map (odk_batch_set_imitation_joints): frame joint of actuator u, -1 = not compared
   const int* hslot;   // [nu] Standing's head joints (odk_batch_set_head_joints): posture-command slot 0..3 of actuator u, -1 = not a head joint
+  const float* push;  // [nenv][push_stride] bound pushes (odk_batch_bind_pushes): world-frame kick (dvx, dvy) of the next step, or null: the
+  int push_stride;    // sampled push.  A uniform pointer test like cmd's, placed behind every older field
 };
 
 // DR buffer layout per env
@@ -658,8 +660,19 @@ __global__ void __launch_bounds__(64, STEP_WAVES) step_kernel(KArgs a) {
   const float theta = (float)(w2 >> 8) * (1.0f / 16777216.0f) * (2.0f * PI_F);
   const float mag = c.push_magnitude_range[0] + (float)(w3 >> 8) * (1.0f / 16777216.0f) * (c.push_magnitude_range[1] - c.push_magnitude_range[0]);
   const float gate = (((push_step + 1) % push_int) == 0 ? 1.0f : 0.0f) * c.push_enable;
-  const float push[2] = {cosf(theta) * gate, sinf(theta) * gate};
-  if (lane < 2) L[S::O_QVEL + lane] += push[lane] * mag;
+  float push[2] = {cosf(theta) * gate, sinf(theta) * gate};
+  if (a.push) {   // bound pushes: env e's row is the kick (theta and mag were drawn and are dropped); info["push"] keeps its unit direction
+    if (lane < 2) {
+      const float* pr = a.push + (size_t)e * a.push_stride;
+      const float kx = pr[0], ky = pr[1];
+      L[S::O_QVEL + lane] += lane == 0 ? kx : ky;
+      const float n2 = kx * kx + ky * ky;
+      const float inv = n2 > 0.0f ? 1.0f / sqrtf(n2) : 0.0f;
+      push[0] = kx * inv; push[1] = ky * inv;
+    }
+  } else if (lane < 2) {
+    L[S::O_QVEL + lane] += push[lane] * mag;
+  }
   // values only the epilogue needs go back to LDS now instead of riding through the substep loop in scratch:
   // info["push"], the imitation counter, its phase (two spare floats behind the action), the episode step counter
   if (lane == 0) {
@@ -941,6 +954,7 @@ struct odk_batch {
   static constexpr size_t ODK_TIMING_EVENT_PAIRS = 1024;
   int timing = 0; size_t timing_count = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> events; size_t ev_used = 0;   // timing: 0 off, n: every n-th launch
   const float* d_cmd = nullptr; int cmd_stride = 0;   // odk_batch_bind_commands (caller-owned device rows), null: sampled commands
+  const float* d_push = nullptr; int push_stride = 0; // odk_batch_bind_pushes (caller-owned device rows), null: the sampled push
   XTerms* d_xt = nullptr; bool xt_on = false;         // odk_batch_set_reward_terms: the batch's device copy; passed to the kernels while some term is on
   float* d_xmet = nullptr;                             // odk_batch_bind_reward_metrics (caller-owned)
   int* d_imap = nullptr; bool imap_set = false;        // odk_batch_set_imitation_joints: the batch's device copy; set: a map was given (the duck's
@@ -2001,6 +2015,7 @@ static void base_args(odk_batch* b, KArgs& a, const odk_outputs* o) {
   a.dr = b->dr_enabled ? b->d_dr : nullptr; a.nenv = b->nenv; a.n_substeps = b->cfg.n_substeps;
   a.dbg_lds = nullptr;
   a.cmd = b->d_cmd; a.cmd_stride = b->cmd_stride;
+  a.push = b->d_push; a.push_stride = b->push_stride;
   a.xt = b->xt_on ? b->d_xt : nullptr; a.xmet = b->xt_on ? b->d_xmet : nullptr;
   a.imap = b->d_imap;
   a.hslot = b->d_hslot;
@@ -2066,6 +2081,23 @@ extern "C" int odk_batch_bind_commands(odk_batch* b, const float* cmd_dev, int r
   if (!b) return fail(ODK_ERR_INVALID, "null batch");
   if (cmd_dev && row_stride < 7) return fail(ODK_ERR_INVALID, "command rows hold 7 floats: row_stride %d < 7", row_stride);
   b->d_cmd = cmd_dev; b->cmd_stride = cmd_dev ? row_stride : 0;
+  return ODK_OK;
+}
+
+extern "C" int odk_batch_bind_pushes(odk_batch* b, const float* push_dev, int row_stride) {
+  if (!b) return fail(ODK_ERR_INVALID, "null batch");
+  if (!push_dev) { b->d_push = nullptr; b->push_stride = 0; return ODK_OK; }
+  if (row_stride < 2) return fail(ODK_ERR_INVALID, "odk_batch_bind_pushes: push rows hold 2 floats: row_stride %d < 2", row_stride);
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof(at));
+  if (hipPointerGetAttributes(&at, push_dev) != hipSuccess) {
+    (void)hipGetLastError();   // a pointer the runtime does not know: not this call's error to leave behind
+    return fail(ODK_ERR_INVALID, "odk_batch_bind_pushes: push_dev is not device memory");
+  }
+  if (at.type != hipMemoryTypeDevice || at.device != b->device)
+    return fail(ODK_ERR_INVALID, "odk_batch_bind_pushes: push_dev must be device memory of device %d (the batch's), it belongs to device %d", b->device,
+                at.device);
+  b->d_push = push_dev; b->push_stride = row_stride;
   return ODK_OK;
 }
 
@@ -2196,6 +2228,63 @@ extern "C" int odk_tracking_accumulate(const odk_batch* b, const float* priv_dev
   HIPCHK(hipSetDevice(b->device));
   hipLaunchKernelGGL(tracking_kernel, dim3((b->nenv + 255) / 256), dim3(256), 0, (hipStream_t)stream, priv_dev, npriv, nobs, reward_dev, done_dev,
                      truncation_dev, b->d_cmd, b->cmd_stride, acc_dev, b->nenv);
+  HIPCHK(hipGetLastError());
+  return ODK_OK;
+}
+
+// Push-recovery state of one evaluation step (one thread per env), issued between odk_step and odk_tracking_accumulate: the tracking
+// accumulator's ENDED slot still tells whether the env's first episode was running when this step began.  Achieved velocities as above.
+__global__ void __launch_bounds__(256) push_kernel(const float* __restrict__ priv, int npriv, int nobs, const float* __restrict__ done,
+                                                   const float* __restrict__ trunc, const float* __restrict__ cmd, int cmd_stride,
+                                                   const float* __restrict__ push, int push_stride, const float* __restrict__ track,
+                                                   float lin_tol, float ang_tol, float* __restrict__ acc, int nenv) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= nenv) return;
+  const float* T = track + (size_t)e * ODK_TRACK_NACC;
+  if (T[ODK_TRACK_ENDED] != 0.0f) return;       // past its first episode
+  float* A = acc + (size_t)e * ODK_PUSH_NACC;
+  const float* K = push + (size_t)e * push_stride;
+  bool pushed = A[ODK_PUSH_PUSHED] != 0.0f;
+  if (!pushed && (K[0] != 0.0f || K[1] != 0.0f)) {   // the step that just ran read this row: the pushed step
+    pushed = true;
+    A[ODK_PUSH_PUSHED] = 1.0f;
+    A[ODK_PUSH_PUSH_AT] = T[ODK_TRACK_STEPS];        // first-episode steps before this one
+  }
+  const float since = T[ODK_TRACK_STEPS] - A[ODK_PUSH_PUSH_AT] + 1.0f;   // steps from the pushed step to this one, counting both
+  if (done[e] != 0.0f) {   // ends the first episode; no velocity sample (the observation is the auto-reset's)
+    if (pushed && trunc[e] == 0.0f) { A[ODK_PUSH_FELL] = 1.0f; A[ODK_PUSH_STEPS_TO_FALL] = since; }
+    return;
+  }
+  const float* P = priv + (size_t)e * npriv;
+  const float* C = cmd + (size_t)e * cmd_stride;
+  const float ex = P[nobs + 9] - C[0], ey = P[nobs + 10] - C[1];
+  // the planar error through float64 (the squares are exact there, the root is correctly rounded, then one rounding to float32): a host
+  // restatement reproduces it, and with it LAST_OFF and the peaks, bit for bit whatever the compiler fuses
+  const float lin = (float)sqrt((double)ex * (double)ex + (double)ey * (double)ey), ang = fabsf(P[nobs + 2] - C[2]);
+  if (!pushed) {
+    // compensated (Kahan) sum: SUM stays within an ulp of the true sum however many samples come before the push; LOW keeps what SUM dropped
+    const float s = A[ODK_PUSH_PRE_LIN_ERR_SUM], y = lin + A[ODK_PUSH_PRE_LIN_ERR_LOW];
+    const float t = s + y;
+    A[ODK_PUSH_PRE_LIN_ERR_SUM] = t;
+    A[ODK_PUSH_PRE_LIN_ERR_LOW] = y - (t - s);
+    A[ODK_PUSH_PRE_SAMPLES] += 1.0f;
+    return;
+  }
+  if (lin > lin_tol || ang > ang_tol) A[ODK_PUSH_LAST_OFF] = since;
+  A[ODK_PUSH_PEAK_LIN_ERR] = fmaxf(A[ODK_PUSH_PEAK_LIN_ERR], lin);
+  A[ODK_PUSH_PEAK_ANG_ERR] = fmaxf(A[ODK_PUSH_PEAK_ANG_ERR], ang);
+}
+
+extern "C" int odk_push_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
+                                   const float* track_acc_dev, float lin_tol, float ang_tol, float* acc_dev, void* stream) {
+  if (!b || !priv_dev || !done_dev || !truncation_dev || !track_acc_dev || !acc_dev) return fail(ODK_ERR_INVALID, "null argument");
+  if (!b->d_cmd) return fail(ODK_ERR_INVALID, "odk_push_accumulate: no commands bound (odk_batch_bind_commands)");
+  if (!b->d_push) return fail(ODK_ERR_INVALID, "odk_push_accumulate: no pushes bound (odk_batch_bind_pushes)");
+  int nobs, npriv;
+  obs_sizes_nu(b->model.h.nu, b->cfg.env_kind, &nobs, &npriv);
+  HIPCHK(hipSetDevice(b->device));
+  hipLaunchKernelGGL(push_kernel, dim3((b->nenv + 255) / 256), dim3(256), 0, (hipStream_t)stream, priv_dev, npriv, nobs, done_dev, truncation_dev,
+                     b->d_cmd, b->cmd_stride, b->d_push, b->push_stride, track_acc_dev, lin_tol, ang_tol, acc_dev, b->nenv);
   HIPCHK(hipGetLastError());
   return ODK_OK;
 }

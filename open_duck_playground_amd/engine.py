@@ -151,11 +151,13 @@ def load_library() -> C.CDLL:
     L.odk_step.argtypes = [P, P, C.POINTER(Outputs), P]
     L.odk_physics_step.argtypes = [P, P, C.c_int, P]
     L.odk_batch_bind_commands.argtypes = [P, P, C.c_int]
+    L.odk_batch_bind_pushes.argtypes = [P, P, C.c_int]
     L.odk_batch_set_reward_terms.argtypes = [P, C.POINTER(RewardTerms)]
     L.odk_batch_bind_reward_metrics.argtypes = [P, P]
     L.odk_batch_set_imitation_joints.argtypes = [P, C.POINTER(C.c_int32), C.c_int]
     L.odk_batch_set_head_joints.argtypes = [P, C.POINTER(C.c_int32), C.c_int]
     L.odk_tracking_accumulate.argtypes = [P, P, P, P, P, P, P]
+    L.odk_push_accumulate.argtypes = [P, P, P, P, P, C.c_float, C.c_float, P, P]
     L.odk_batch_get_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_set_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_get_debug.argtypes = [P, FP, FP, FP, FP]
@@ -200,7 +202,7 @@ EXPORTED_SYMBOLS = (
     "odk_model_env_lds_floats", "odk_batch_create",
     "odk_batch_destroy", "odk_batch_set_config", "odk_batch_set_param", "odk_reset", "odk_step", "odk_physics_step",
     "odk_batch_bind_commands", "odk_batch_set_reward_terms", "odk_batch_bind_reward_metrics", "odk_batch_set_imitation_joints", "odk_batch_set_head_joints",
-    "odk_tracking_accumulate",
+    "odk_tracking_accumulate", "odk_batch_bind_pushes", "odk_push_accumulate",
     "odk_batch_get_state", "odk_batch_set_state", "odk_batch_get_debug", "odk_set_debug_dump", "odk_batch_lds_size",
     "odk_batch_get_lds", "odk_lds_offset", "odk_batch_record_size", "odk_batch_get_records", "odk_batch_set_records", "odk_batch_timing", "odk_gae", "odk_ppo_head",
     "odk_policy_sample", "odk_adam_clip", "odk_silu_bwd_colsum", "odk_colsum_partial", "odk_colsum_finalize", "odk_gather_rows", "odk_dw_gemm",
@@ -227,6 +229,42 @@ def check_commands(cmd, nenv: int, device: int) -> None:
         raise OdkError("commands: the tensor must be contiguous")
     if cmd.device.type != "cuda" or cmd.device.index != int(device):
         raise OdkError(f"commands: the tensor must live on cuda:{device} (the env's device), got {cmd.device}")
+
+
+# odk_push_accumulate's per-env slots (include/odk.h ODK_PUSH_*)
+PUSH_NACC = 10
+(PUSH_PUSHED, PUSH_PUSH_AT, PUSH_FELL, PUSH_STEPS_TO_FALL, PUSH_LAST_OFF, PUSH_PEAK_LIN_ERR, PUSH_PEAK_ANG_ERR, PUSH_PRE_LIN_ERR_SUM,
+ PUSH_PRE_SAMPLES, PUSH_PRE_LIN_ERR_LOW) = range(10)
+
+
+def check_pushes(push, nenv: int, device: int) -> None:
+    """What `Batch.bind_pushes` accepts: a contiguous float32 [nenv, >= 2] tensor on cuda:`device`; raises OdkError otherwise."""
+    import torch
+    if not torch.is_tensor(push):
+        raise OdkError(f"pushes: expected a torch tensor or None, got {type(push).__name__}")
+    if push.dim() != 2 or int(push.shape[0]) != int(nenv) or int(push.shape[1]) < 2:
+        raise OdkError(f"pushes: shape must be ({nenv}, >= 2), got {tuple(push.shape)}")
+    if push.dtype != torch.float32:
+        raise OdkError(f"pushes: dtype must be torch.float32, got {push.dtype}")
+    if not push.is_contiguous():
+        raise OdkError("pushes: the tensor must be contiguous")
+    if push.device.type != "cuda" or push.device.index != int(device):
+        raise OdkError(f"pushes: the tensor must live on cuda:{device} (the env's device), got {push.device}")
+
+
+def check_accumulator(name: str, acc, nenv: int, ncol: int, device: int) -> None:
+    """An accumulator argument of `Batch.push_accumulate`: a contiguous float32 [nenv, ncol] tensor on cuda:`device`; OdkError otherwise."""
+    import torch
+    if not torch.is_tensor(acc):
+        raise OdkError(f"{name}: expected a torch tensor, got {type(acc).__name__}")
+    if tuple(acc.shape) != (int(nenv), int(ncol)):
+        raise OdkError(f"{name}: shape must be ({nenv}, {ncol}), got {tuple(acc.shape)}")
+    if acc.dtype != torch.float32:
+        raise OdkError(f"{name}: dtype must be torch.float32, got {acc.dtype}")
+    if not acc.is_contiguous():
+        raise OdkError(f"{name}: the tensor must be contiguous")
+    if acc.device.type != "cuda" or acc.device.index != int(device):
+        raise OdkError(f"{name}: the tensor must live on cuda:{device} (the env's device), got {acc.device}")
 
 
 def _chk(rc: int):
@@ -848,6 +886,7 @@ class Batch:
         self._outs = Outputs(self.obs.data_ptr(), self.priv.data_ptr(), self.reward.data_ptr(), self.done.data_ptr(),
                              self.truncation.data_ptr(), self.metrics.data_ptr())
         self.commands = None         # the tensor bound by bind_commands (kept alive while bound)
+        self.pushes = None           # the tensor bound by bind_pushes (kept alive while bound)
         self.xmetrics = None         # [nenv, NXTERM] reward-library metrics, allocated by the first set_reward_terms that turns a term on
         self.reward_terms_on = False
         self.generation = 0          # advanced by every call that rewrites the per-env records (reset / step / set_records): `State.info` checks it
@@ -886,6 +925,20 @@ class Batch:
         _chk(self.L.odk_batch_bind_commands(self._b, C.c_void_p(cmd.data_ptr()), NCOMMAND))
         self.commands = cmd
 
+    def bind_pushes(self, push):
+        """Push every env with the caller's kick (`odk_batch_bind_pushes`): `push` is a contiguous float32 [nenv, >= 2] tensor on this
+        batch's device, row e = the world-frame velocity kick (dvx, dvy) in m/s that env e's next step adds to qvel[0:2] (include/odk.h);
+        None returns to the sampled push.  A row left non-zero is applied by every step: write it (stream-ordered) for the step that is to
+        be pushed and zero it afterwards.  The batch keeps a reference to the tensor while it is bound; a captured graph keeps the buffer
+        it was captured with, so rebind only before capturing."""
+        if push is None:
+            _chk(self.L.odk_batch_bind_pushes(self._b, None, 0))
+            self.pushes = None
+            return
+        check_pushes(push, self.nenv, self.device)
+        _chk(self.L.odk_batch_bind_pushes(self._b, C.c_void_p(push.data_ptr()), int(push.shape[1])))
+        self.pushes = push
+
     def set_reward_terms(self, terms: Optional[RewardTerms]):
         """Reward-library terms of the step kernel (`odk_batch_set_reward_terms`): None or all scales 0 turns them off.  While some
         term is on every step writes `xmetrics` ([nenv, NXTERM], column = XTERM_NAMES index, 0 for a term that is off).  Synchronous;
@@ -921,6 +974,19 @@ class Batch:
         _chk(self.L.odk_tracking_accumulate(self._b, C.c_void_p(self.priv.data_ptr()), C.c_void_p(self.reward.data_ptr()),
                                             C.c_void_p(self.done.data_ptr()), C.c_void_p(self.truncation.data_ptr()),
                                             C.c_void_p(acc.data_ptr()), self._stream()))
+
+    def push_accumulate(self, acc, track_acc, lin_tol: float, ang_tol: float):
+        """One `odk_push_accumulate` launch over this step's outputs into `acc` ([nenv, PUSH_NACC] float32, zeroed before the first
+        step), issued after `step` and BEFORE `tracking_accumulate(track_acc)`; needs bound commands and bound pushes."""
+        check_accumulator("push_accumulate: acc", acc, self.nenv, PUSH_NACC, self.device)
+        check_accumulator("push_accumulate: track_acc", track_acc, self.nenv, TRACK_NACC, self.device)
+        if self.commands is None:
+            raise OdkError("push_accumulate: no commands bound (bind_commands)")
+        if self.pushes is None:
+            raise OdkError("push_accumulate: no pushes bound (bind_pushes)")
+        _chk(self.L.odk_push_accumulate(self._b, C.c_void_p(self.priv.data_ptr()), C.c_void_p(self.done.data_ptr()),
+                                        C.c_void_p(self.truncation.data_ptr()), C.c_void_p(track_acc.data_ptr()), float(lin_tol), float(ang_tol),
+                                        C.c_void_p(acc.data_ptr()), self._stream()))
 
     def physics_step(self, ctrl, n_substeps: int = 10):
         assert ctrl.is_cuda and ctrl.dtype == self.torch.float32 and ctrl.is_contiguous() and tuple(ctrl.shape) == (self.nenv, self.model.nu)

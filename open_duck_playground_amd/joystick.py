@@ -420,6 +420,20 @@ class Joystick:
         """The tensor bound by `set_commands`, or None."""
         return self._batch.commands
 
+    def set_pushes(self, push) -> None:
+        """Push the envs with caller-given kicks instead of the sampled training push (what grabbing the robot with the mouse does in
+        mujoco_infer.py's viewer): `push` is a contiguous float32 [num_envs, >= 2] tensor on the env's device -- the world-frame
+        velocity kick (dvx, dvy) in m/s that env e's next step adds to qvel[0:2] -- or None to return to `push_config`.  Every step
+        applies env e's row as it is when that launch runs (zero it after the pushed step); `info["push"]` holds the kick's unit
+        direction; the random streams stay those of an unbound run.  The env holds a reference to the tensor while it is bound
+        (`Batch.bind_pushes`).  Standing inherits this."""
+        self._batch.bind_pushes(push)
+
+    @property
+    def pushes(self):
+        """The tensor bound by `set_pushes`, or None."""
+        return self._batch.pushes
+
     def step(self, state: State, action) -> State:
         """reference joystick.py:323 (+ Episode/AutoReset wrappers): one fused kernel launch."""
         self._batch.step(action)

@@ -12,6 +12,19 @@ tracking accumulator (`odk_tracking_accumulate`) -- is captured once as a HIP gr
 host.  Each env counts over its first episode (Evaluator semantics).  The report is one JSON document: per command the mean achieved
 local linear velocity x / y and yaw rate, the RMS error per axis against the command, the fall rate (episodes that ended with done and
 no truncation), the mean episode reward and the step counts, plus the run's settings.
+
+Pushes (what grabbing the robot with the mouse answers in that viewer: does the policy stay on its feet, and how long until it walks
+straight again?):
+
+    python -m open_duck_playground_amd.track --checkpoint <ckpt> --command 0.1 0 0 --push_grid magnitude=0:1.5:6,direction=0:315:8 --push_at 200
+
+`--push DVX DVY` (repeatable) and `--push_grid magnitude=a:b:n,direction=c:d:m` (degrees, world frame, 0 = +x) give world-frame velocity
+kicks in m/s; every (command, push) cell gets `--envs_per_command` envs, command blocks outermost.  The kick is added once, to the step of
+the first episode that `--push_at` names, through `set_pushes`: the push buffer is written inside the captured step from a device step
+counter, so the run stays one graph replay per step.  `odk_push_accumulate` follows each env until its first episode ends; every command
+row of the report gains "pushes" (per push: fall rate after the push, steps to the fall, recovery time -- the last step at which the
+velocity error exceeded `--push_tolerance` -- and the error peaks) and "max_push_survived" (per direction).  Without push flags the
+report, the graph and the JSON keys are exactly those above.
 """
 from __future__ import annotations
 
@@ -23,6 +36,10 @@ import sys
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
+
+from .engine import (PUSH_NACC, PUSH_PUSHED as P_PUSHED, PUSH_PUSH_AT as P_PUSH_AT, PUSH_FELL as P_FELL, PUSH_STEPS_TO_FALL as P_STEPS_TO_FALL,
+                     PUSH_LAST_OFF as P_LAST_OFF, PUSH_PEAK_LIN_ERR as P_PEAK_LIN, PUSH_PEAK_ANG_ERR as P_PEAK_ANG, PUSH_PRE_LIN_ERR_SUM as P_PRE_SUM,
+                     PUSH_PRE_SAMPLES as P_PRE_SAMPLES, PUSH_PRE_LIN_ERR_LOW as P_PRE_LOW)      # include/odk.h ODK_PUSH_*: one definition, engine.py's
 
 COMMAND_KEYS = ("vx", "vy", "wz", "neck_pitch", "head_pitch", "head_yaw", "head_roll")   # the order of cmd_range (include/odk.h)
 NACC = 12
@@ -72,6 +89,129 @@ def parse_grid(spec: str) -> List[List[float]]:
 def command_blocks(commands: Sequence[Sequence[float]], envs_per_command: int) -> np.ndarray:
     """[len(commands) * envs_per_command, 7] float32: command c drives envs c * envs_per_command .. (c + 1) * envs_per_command - 1."""
     return np.repeat(np.asarray(commands, np.float32).reshape(-1, 7), int(envs_per_command), axis=0)
+
+
+PUSH_AXES = ("magnitude", "direction")
+# BUILD-DEFINED defaults (the reference has no such measure): a velocity sample is "off" while its planar velocity error exceeds 0.05 m/s
+# (a third of the duck's top commanded speed) or its yaw-rate error 0.2 rad/s (a fifth of the top commanded yaw rate)
+DEFAULT_PUSH_TOLERANCE = (0.05, 0.2)
+DEFAULT_PUSH_AT = 200
+
+
+def push_entry(magnitude: float, direction_deg: float) -> Dict:
+    """One push of the sweep: the world-frame kick of `magnitude` m/s towards `direction_deg` (0 = +x, 90 = +y)."""
+    th = np.deg2rad(float(direction_deg))
+    return dict(push=[float(magnitude * np.cos(th)), float(magnitude * np.sin(th))], magnitude=float(magnitude), direction_deg=float(direction_deg))
+
+
+def push_row(values: Sequence[float]) -> Dict:
+    """`--push DVX DVY` -> the push with that kick; its magnitude and direction (degrees in [0, 360), 0 for a zero kick) are derived."""
+    v = [float(x) for x in values]
+    if len(v) != 2:
+        raise ValueError(f"a push is DVX DVY: 2 numbers, got {len(v)}")
+    mag = float(np.hypot(v[0], v[1]))
+    return dict(push=v, magnitude=mag, direction_deg=float(np.rad2deg(np.arctan2(v[1], v[0])) % 360.0) if mag > 0 else 0.0)
+
+
+def parse_push_grid(spec: str) -> List[Dict]:
+    """`magnitude=a:b:n,direction=c:d:m` -> the pushes of the grid, with `--grid`'s conventions: each axis takes n values from a to b
+    (numpy.linspace, ends included), rows in itertools.product order of the axes as written (the last axis varies fastest).  Magnitude in
+    m/s (required), direction in degrees (0 when not named)."""
+    axes = []
+    for part in spec.split(","):
+        part = part.strip()
+        if not part:
+            continue
+        name, _, rng = part.partition("=")
+        name = name.strip()
+        if name not in PUSH_AXES:
+            raise ValueError(f"--push_grid: unknown axis {name!r} (one of {', '.join(PUSH_AXES)})")
+        if any(name == a for a, _ in axes):
+            raise ValueError(f"--push_grid: axis {name!r} given twice")
+        bits = rng.split(":")
+        if len(bits) != 3:
+            raise ValueError(f"--push_grid: {part!r} is not {name}=start:stop:count")
+        lo, hi, n = float(bits[0]), float(bits[1]), int(bits[2])
+        if n < 1:
+            raise ValueError(f"--push_grid: {part!r} needs a count >= 1")
+        if name == "magnitude" and min(lo, hi) < 0:
+            raise ValueError(f"--push_grid: {part!r}: a magnitude is >= 0 (turn the direction instead)")
+        axes.append((name, np.linspace(lo, hi, n).tolist()))
+    if not any(name == "magnitude" for name, _ in axes):
+        raise ValueError("--push_grid: no magnitude axis given")
+    rows = []
+    for combo in itertools.product(*[vals for _, vals in axes]):
+        cell = {"magnitude": 0.0, "direction": 0.0}
+        cell.update({name: float(v) for (name, _), v in zip(axes, combo)})
+        rows.append(push_entry(cell["magnitude"], cell["direction"]))
+    return rows
+
+
+def cell_blocks(commands: Sequence[Sequence[float]], pushes: Sequence[Dict], envs_per_cell: int):
+    """(cmd [n, 7], kicks [n, 2]) float32 with n = len(commands) * len(pushes) * envs_per_cell: cell (c, p) drives envs
+    (c * len(pushes) + p) * envs_per_cell onwards -- command blocks outermost, so command c's envs stay one block of
+    len(pushes) * envs_per_cell (what `reduce_tracking` pools)."""
+    E, P = int(envs_per_cell), len(pushes)
+    cmd = command_blocks(commands, P * E)
+    kicks = np.tile(np.repeat(np.asarray([p["push"] for p in pushes], np.float32).reshape(-1, 2), E, axis=0), (len(commands), 1))
+    return cmd, kicks
+
+
+def _mean_or_none(x: np.ndarray) -> Optional[float]:
+    return float(x.mean()) if x.size else None
+
+
+def reduce_pushes(acc: np.ndarray, commands: Sequence[Sequence[float]], pushes: Sequence[Dict], envs_per_cell: int, dt: float) -> List[Dict]:
+    """Per command, what its rows of the report gain: {"pushes": [...], "max_push_survived": [...]}, from the push accumulator ([nenv, 10],
+    include/odk.h ODK_PUSH_*) in `cell_blocks` order.  Per cell: `pushed_envs` counts the envs whose first episode reached the pushed step
+    (the others ended before it and say nothing about the push); `fall_rate_after_push` is the share of the pushed envs that fell at or
+    after it (0 when nobody was pushed) and `mean_steps_to_fall` their mean step count from the pushed step to the fall; the recovery
+    statistics are over the survivors (pushed, did not fall): median and 90th percentile of the steps from the pushed step to the last
+    velocity sample outside the tolerance (0: never outside), `recovery_time_s` = median * dt; the error peaks are means over the pushed
+    envs; `pre_push_lin_err_mean` is the cell's mean planar velocity error over the samples before the push.  A figure over an empty set
+    is None.  `max_push_survived`: per direction of the sweep, in order of first appearance, the largest magnitude whose cell has
+    fall_rate_after_push == 0 among the cells where somebody was pushed (a cell whose envs all ended their first episode before the
+    pushed step says nothing; the zero kick counts as survived) -- None when no magnitude of that direction was survived; a smaller
+    magnitude with falls does not cap it."""
+    acc = np.asarray(acc, np.float64).reshape(-1, PUSH_NACC)
+    E, P = int(envs_per_cell), len(pushes)
+    out = []
+    for c, _ in enumerate(commands):
+        cells = []
+        for p, push in enumerate(pushes):
+            blk = acc[(c * P + p) * E:(c * P + p + 1) * E]
+            pushed = blk[:, P_PUSHED] != 0
+            fell = pushed & (blk[:, P_FELL] != 0)
+            ok = pushed & ~fell
+            rec = blk[ok, P_LAST_OFF]
+            med = float(np.median(rec)) if rec.size else None
+            pre_n = float(blk[:, P_PRE_SAMPLES].sum())
+            cells.append(dict(
+                push=[float(x) for x in push["push"]], magnitude=float(push["magnitude"]), direction_deg=float(push["direction_deg"]),
+                envs=E, pushed_envs=int(pushed.sum()),
+                fall_rate_after_push=float(fell.sum() / max(int(pushed.sum()), 1)),
+                mean_steps_to_fall=_mean_or_none(blk[fell, P_STEPS_TO_FALL]),
+                recovery_steps_median=med,
+                recovery_steps_p90=float(np.percentile(rec, 90)) if rec.size else None,
+                recovery_time_s=med * float(dt) if med is not None else None,
+                peak_lin_err_mean=_mean_or_none(blk[pushed, P_PEAK_LIN]),
+                peak_ang_err_mean=_mean_or_none(blk[pushed, P_PEAK_ANG]),
+                pre_push_lin_err_mean=float((blk[:, P_PRE_SUM] + blk[:, P_PRE_LOW]).sum() / pre_n) if pre_n > 0 else None,
+            ))
+        best: Dict[float, Optional[float]] = {}
+        for cell in cells:
+            d = cell["direction_deg"]
+            best.setdefault(d, None)
+            tried = cell["pushed_envs"] > 0 or cell["magnitude"] == 0.0      # a kick that reached nobody was not survived by anybody
+            if tried and cell["fall_rate_after_push"] == 0.0 and (best[d] is None or cell["magnitude"] > best[d]):
+                best[d] = cell["magnitude"]
+        out.append(dict(pushes=cells, max_push_survived=[dict(direction_deg=d, magnitude=m) for d, m in best.items()]))
+    return out
+
+
+PUSH_ROW_KEYS = ("pushes", "max_push_survived")
+PUSH_CELL_KEYS = ("push", "magnitude", "direction_deg", "envs", "pushed_envs", "fall_rate_after_push", "mean_steps_to_fall", "recovery_steps_median",
+                  "recovery_steps_p90", "recovery_time_s", "peak_lin_err_mean", "peak_ang_err_mean", "pre_push_lin_err_mean")
 
 
 def reduce_tracking(acc: np.ndarray, commands: Sequence[Sequence[float]], envs_per_command: int) -> List[Dict]:
@@ -155,13 +295,24 @@ def load_networks(path: Optional[str], env, device):
 
 
 class Tracker:
-    """One tracking run on a bound command buffer: `step()` = policy + env step + accumulator, captured as one graph."""
+    """One tracking run on a bound command buffer: `step()` = policy + env step + accumulator, captured as one graph.  With `kicks`
+    ([num_envs, 2] device floats, one world-frame kick per env) it is policy + push write + env step + push accumulator + tracking
+    accumulator: the Tracker binds a push buffer of its own (`set_pushes`) that holds env e's kick during the step at which the device
+    step counter -- the first-episode step, since first episodes start together at `reset` -- equals `push_at`, and zeros otherwise."""
 
-    def __init__(self, env, net, use_graph: bool = True):
+    def __init__(self, env, net, use_graph: bool = True, kicks=None, push_at: int = DEFAULT_PUSH_AT, push_tolerance=DEFAULT_PUSH_TOLERANCE):
         import torch
         self.env, self.net, self.torch = env, net, torch
         b = env.batch
         self.acc = torch.zeros(env.num_envs, NACC, device=b.obs.device)
+        self.kicks = self.push_buf = self.push_acc = self.counter = None
+        if kicks is not None:
+            self.kicks = kicks.to(device=b.obs.device, dtype=torch.float32).reshape(env.num_envs, 2).contiguous()
+            self.push_at, self.push_tolerance = int(push_at), (float(push_tolerance[0]), float(push_tolerance[1]))
+            self.push_buf = torch.zeros_like(self.kicks)
+            self.push_acc = torch.zeros(env.num_envs, PUSH_NACC, device=b.obs.device)
+            self.counter = torch.full((), -1, dtype=torch.int64, device=b.obs.device)
+            env.set_pushes(self.push_buf)
         from .ppo.learner import fused_policy
         self.fp = fused_policy(net, env.num_envs)
         self.use_graph = use_graph
@@ -174,12 +325,20 @@ class Tracker:
 
     def _one_step(self):
         b = self.env.batch
-        b.step(self.actions(b.obs))                 # Joystick.step without the State wrapper (nothing here reads it)
+        act = self.actions(b.obs)
+        if self.kicks is not None:                  # device ops only: the same graph replay serves every step
+            self.counter.add_(1)
+            self.torch.mul(self.kicks, (self.counter == self.push_at).to(self.kicks.dtype), out=self.push_buf)
+        b.step(act)                                 # Joystick.step without the State wrapper (nothing here reads it)
+        if self.kicks is not None:
+            b.push_accumulate(self.push_acc, self.acc, *self.push_tolerance)      # before the tracking accumulator sets ENDED
         b.tracking_accumulate(self.acc)
 
     def reset(self, seed: int):
         self.env.reset(int(seed))
         self.acc.zero_()
+        if self.kicks is not None:
+            self.push_acc.zero_(); self.push_buf.zero_(); self.counter.fill_(-1)
         if self.fp is not None:
             self.fp.refresh()                       # its packed weight copy <- the current parameters
 
@@ -208,8 +367,11 @@ def run(args, out=sys.stdout) -> Dict:
         commands += parse_grid(args.grid)
     if not commands:
         raise SystemExit("give at least one --command or a --grid")
+    pushes = [push_row(p) for p in (getattr(args, "push", None) or [])]
+    if getattr(args, "push_grid", None):
+        pushes += parse_push_grid(args.push_grid)
     E = int(args.envs_per_command)
-    n = len(commands) * E
+    n = len(commands) * max(len(pushes), 1) * E
     torch.cuda.set_device(args.device)
     dev = torch.device("cuda", args.device)
     env = make_env(args, n, args.device)
@@ -219,9 +381,19 @@ def run(args, out=sys.stdout) -> Dict:
     if hasattr(env, "describe_head_joints"):
         print(env.describe_head_joints(), file=sys.stderr)
     net = load_networks(args.checkpoint, env, dev)
-    cmd = torch.from_numpy(command_blocks(commands, E)).to(dev)
-    env.set_commands(cmd)
-    tr = Tracker(env, net)
+    if pushes:
+        push_at = int(args.push_at)
+        if push_at < 0:
+            raise SystemExit("--push_at is a step of the episode: >= 0")
+        tol = tuple(float(x) for x in args.push_tolerance)
+        cmd_np, kicks_np = cell_blocks(commands, pushes, E)
+        cmd = torch.from_numpy(cmd_np).to(dev)
+        env.set_commands(cmd)
+        tr = Tracker(env, net, kicks=torch.from_numpy(kicks_np).to(dev), push_at=push_at, push_tolerance=tol)
+    else:
+        cmd = torch.from_numpy(command_blocks(commands, E)).to(dev)
+        env.set_commands(cmd)
+        tr = Tracker(env, net)
     nobs = env.observation_size["state"][0]
     T = int(args.episode_length)
     save_obs_path, save_qpos_path = getattr(args, "save_obs", None), getattr(args, "save_qpos", None)
@@ -238,11 +410,18 @@ def run(args, out=sys.stdout) -> Dict:
             if save_qpos_path:
                 qpos_hist.append(env.batch.get_state()[0][0].copy())
         acc = tr.acc.cpu().numpy()
-    rows = reduce_tracking(acc, commands, E)
+        push_acc = tr.push_acc.cpu().numpy() if pushes else None
+    rows = reduce_tracking(acc, commands, max(len(pushes), 1) * E)
+    if pushes:
+        for row, extra in zip(rows, reduce_pushes(push_acc, commands, pushes, E, float(env.dt))):
+            row.update(extra)
     settings = dict(checkpoint=args.checkpoint, env=args.env, task=args.task, xml=args.xml, cone=args.cone,
                     hfield_up_normals_only=bool(args.hfield_up_normals_only), envs_per_command=E, episode_length=T, seed=int(args.seed),
                     num_envs=n, dt=float(env.dt), policy="deterministic tanh(loc)", fused_policy=tr.fp is not None, graph=tr.graph is not None,
                     reference_motion=getattr(args, "reference_motion", None), reference_motion_sha256=motion.sha256 if motion is not None else None)
+    if pushes:
+        settings.update(push=getattr(args, "push", None), push_grid=getattr(args, "push_grid", None), push_at=push_at,
+                        push_tolerance=list(tol), pushes_per_command=len(pushes))
     report = make_report(settings, rows)
     if save_obs_path:
         save_obs(save_obs_path, obs_hist.cpu().numpy())
@@ -255,6 +434,8 @@ def run(args, out=sys.stdout) -> Dict:
     else:
         print(text, file=out)
     env.set_commands(None)
+    if pushes:
+        env.set_pushes(None)
     return report
 
 
@@ -272,7 +453,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--command", nargs="+", type=float, action="append", metavar="V",
                    help="vx vy wz [neck_pitch head_pitch head_yaw head_roll]; repeat for more commands")
     p.add_argument("--grid", type=str, default=None, help="a grid of commands: vx=a:b:n,wz=c:d:m (axes vx vy wz neck_pitch head_pitch head_yaw head_roll)")
-    p.add_argument("--envs_per_command", type=int, default=128)
+    p.add_argument("--envs_per_command", type=int, default=128, help="envs per command, or per (command, push) cell when pushes are given")
+    p.add_argument("--push", nargs=2, type=float, action="append", metavar=("DVX", "DVY"),
+                   help="a world-frame velocity kick in m/s, added once to the base's planar velocity; repeat for more pushes")
+    p.add_argument("--push_grid", type=str, default=None, help="a grid of pushes: magnitude=a:b:n,direction=c:d:m (m/s; degrees, world frame, 0 = +x)")
+    p.add_argument("--push_at", type=int, default=DEFAULT_PUSH_AT, help="the step of the first episode (0 = its first) at which the kick is applied, once")
+    p.add_argument("--push_tolerance", nargs=2, type=float, default=list(DEFAULT_PUSH_TOLERANCE), metavar=("LIN", "ANG"),
+                   help="recovery: planar velocity error (m/s) and yaw-rate error (rad/s) above which a step counts as not recovered (BUILD-DEFINED defaults)")
     p.add_argument("--episode_length", type=int, default=1000)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--device", type=int, default=0)
