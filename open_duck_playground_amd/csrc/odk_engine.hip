@@ -299,101 +299,64 @@ __device__ __forceinline__ void draw_block(uint32_t k0, uint32_t k1, uint32_t ct
   ODK_SYNC();
 }
 
-// _get_obs (joystick.py:487-620): builds privileged_state[212] (whose first 101 entries are `state`) in LDS; NZ: draw_block
-// KIND (0 Joystick, 1 Standing) and the element loop are compile-time: element ks of pass `it` is lane + G it, so every
-// pass keeps only the few layout segments its 32 / 64 elements can fall into (as one runtime loop over c.npriv, each of the
-// seven passes walked all 23 segments' divergent branches).
-template <class S, int G, int KIND>
-__device__ __forceinline__ void build_obs_kind(float* L, const DevModel* m, const EnvCfg& c, const float* contact, const float* NZ,
-                          int imitation_i, const float* phase, int lane) {
+// _get_obs (joystick.py:487-620 / standing.py:524-565): builds privileged_state (whose first nobs entries are `state`) in LDS by ONE gather
+// over DevModel::obs_tab (built at model load by build_obs_table, below: the layouts are written down there).  Element ks of the task's layout is
+//   ((L[a] + (b >= 0 ? L[b] : zero)) + noise) - kc) * scale
+// with the entry's LDS offsets a, b, its constant kc, its draw and noise scale, `scale` = dof_vel_scale for a joint velocity and 1 elsewhere.  An
+// entry without a second offset adds -0, one without a constant subtracts +0, one without noise adds -0 * 1, one without a scale multiplies by 1:
+// each leaves every float as it is, so an element goes through the operations its own expression has, in that order.  The values the epilogue
+// holds in registers (foot contacts, imitation counter, imitation phase) are parked in the solver-diagnostic slots S_MISC + 1..5, which nobody
+// reads after the last forward pass.  NZ: draw_block (read only when `noisy`, i.e. noise_level != 0).
+template <class S, int G>
+__device__ __forceinline__ void build_obs(float* L, const DevModel* m, const EnvCfg& c, const float* contact, const float* NZ,
+                          int imitation_i, const float* phase, bool noisy, int lane) {
   using E = EnvL<S>;
-  float* P = L + E::O_PRIV; float* INFO = L + E::O_INFO; const float* SENS = L + S::O_SENS; const float* SCR = L + S::O_SCR;
-  const float* QPOS = L + S::O_QPOS; const float* QVEL = L + S::O_QVEL;
+  float* P = L + E::O_PRIV; float* INFO = L + E::O_INFO; float* SCR = L + S::O_SCR;
   const float lvl = c.noise_level;
   constexpr int NU = S::NU;
   constexpr RecLay RL = rec_lay(NU);
-  constexpr int NOBS = obs_nobs(NU, false), DQV = draw_qvel(NU) - 4;   // (draw i sits at NZ[i - 4])
-  const float con0 = contact[0], con1 = contact[1], ph0 = phase[0], ph1 = phase[1];
-  const int adr_gyro = m->adr_gyro, adr_acc = m->adr_accelerometer, adr_lin = m->adr_local_linvel, adr_ang = m->adr_global_angvel;   // (read once, up front)
+  constexpr int NT = (obs_npriv(NU, false) + G - 1) / G;   // passes of the longer layout (Joystick's)
+  static_assert(13 + NU <= G, "build_obs: the noisy joint angles (elements 13 .. 12 + nu) must lie in the first pass of G elements: nu <= G - 13 (see MAXU in odk_model.h)");
+  const ObsEnt* T = m->obs_tab[c.kind != 0 ? 1 : 0];
+  const int np = c.npriv;
+  ObsEnt ent[NT];   // every pass' entry up front: the loads are in flight together
+#pragma unroll
+  for (int it = 0; it < NT; it++) { const int ks = lane + it * G; ent[it] = T[ks < np ? ks : 0]; }
   // imu history ring (noisy gravity, never emitted: joystick.py:522-530)
   float ng = 0;
-  if (lane < 3) ng = SCR[S::S_MISC + 10 + lane] + (2.0f * NZ[10 - 4 + lane] - 1.0f) * lvl * c.noise_gravity;
+  if (lane < 3) { ng = SCR[S::S_MISC + 10 + lane]; if (noisy) ng = ng + (2.0f * NZ[10 - 4 + lane] - 1.0f) * lvl * c.noise_gravity; }
   float h0 = 0, h1 = 0;
   if (lane < 3) { h0 = INFO[RL.IMU + lane]; h1 = INFO[RL.IMU + 3 + lane]; }
+  if (lane == 0) {
+    SCR[S::S_MISC + OBS_PARK_CON] = contact[0]; SCR[S::S_MISC + OBS_PARK_CON + 1] = contact[1]; SCR[S::S_MISC + OBS_PARK_IMI] = (float)imitation_i;
+    SCR[S::S_MISC + OBS_PARK_PHASE] = phase[0]; SCR[S::S_MISC + OBS_PARK_PHASE + 1] = phase[1];
+  }
   ODK_SYNC();
   if (lane < 3) { INFO[RL.IMU + lane] = ng; INFO[RL.IMU + 3 + lane] = h0; INFO[RL.IMU + 6 + lane] = h1; }
-  // Standing (standing.py:524-565) = the Joystick layout minus motor_targets, imitation phase, reference motion, imitation_i
-  constexpr bool standing = KIND != 0;
-  constexpr int NP = obs_npriv(NU, standing);
 #pragma unroll
-  for (int it = 0; it < (NP + G - 1) / G; it++) {
+  for (int it = 0; it < NT; it++) {
     const int ks = lane + it * G;
-    __builtin_assume(ks >= it * G && ks < it * G + G);
-    if (ks >= NP) continue;
-    const int k = !standing ? ks : (ks < 13 + 5 * NU ? ks : (ks < 15 + 5 * NU ? ks + NU : ks + NOBS - (15 + 5 * NU)));
-    // This element's reads of the model's tables, ALL AT ONCE and before the case analysis (indices clamped: a lane outside a case reads a valid slot and drops the
-    // value; cases that cannot occur in this unrolled iteration lose their reads with them).  Inside the cases every read was a global load followed by its own
-    // wait -- ~40 exposed round trips per env step in this routine (round 6).
-    const int q = k - NOBS;   // privileged tail (joystick.py:596-615)
-    const int uA = min(max(k - 13, 0), NU - 1), uV = min(max(k - 13 - NU, 0), NU - 1), uQ = min(max(q - 15, 0), NU - 1), uQV = min(max(q - 15 - NU, 0), NU - 1);
-    const int tF = min(max(q - 18 - 3 * NU, 0), 5);
-    const int A_bq = m->act_backlash_qposadr[uA], A_aq = m->act_qposadr[uA], V_ad = m->act_dofadr[uV];
-    const float A_kc = m->key_ctrl[uA], A_ns = c.qpos_noise_scale[uA];
-    const int Q_bq = m->act_backlash_qposadr[uQ], Q_aq = m->act_qposadr[uQ], QV_ad = m->act_dofadr[uQV], F_adr = m->adr_foot_linvel[tF >= 3 ? 1 : 0];
-    const float Q_kc = m->key_ctrl[uQ];
-    {   // (the optimiser sinks a read into the one case that uses it, which is where it came from: the values a case of THIS unrolled iteration can use are pinned here,
-        // all in flight together; `it` is a constant after unrolling, so the tests below cost nothing)
-      const int k_lo = standing ? 0 : it * G, k_hi = standing ? NP + NOBS : it * G + G;      // (Standing re-maps ks: every case stays possible)
-      auto hits = [&](int lo, int hi) { return k_lo < hi && k_hi > lo; };
-      if (hits(13, 13 + NU)) asm volatile("" :: "v"(A_bq), "v"(A_aq), "v"(A_kc), "v"(A_ns));
-      if (hits(13 + NU, 13 + 2 * NU)) asm volatile("" :: "v"(V_ad));
-      if (hits(NOBS + 15, NOBS + 15 + NU)) asm volatile("" :: "v"(Q_bq), "v"(Q_aq), "v"(Q_kc));
-      if (hits(NOBS + 15 + NU, NOBS + 15 + 2 * NU)) asm volatile("" :: "v"(QV_ad));
-      if (hits(NOBS + 18 + 3 * NU, NOBS + 24 + 3 * NU)) asm volatile("" :: "v"(F_adr));
+    if (ks >= np) continue;
+    const ObsEnt e = ent[it];
+    const float second = L[e.b >= 0 ? e.b : 0];
+    float v = L[e.a] + (e.b >= 0 ? second : ((e.fl & OBS_FL_PLUS0) ? 0.0f : -0.0f));
+    if (noisy) {
+      const int slot = e.fl & 255, nk = (e.fl >> 8) & 31;
+      float nq = 0.0f;   // the joint-angle scale of the element's actuator, picked by compile-time indices (a lane-dependent index into the
+                         // kernel arguments would park all of them in scratch); the noisy joint angles are elements 13 .. 12 + nu: the first pass
+      if (it == 0) {
+#pragma unroll
+        for (int u = 0; u < NU; u++) nq = nk - 3 == u ? c.qpos_noise_scale[u] : nq;
+      }
+      const float ns = nk == 0 ? c.noise_gyro : (nk == 1 ? c.noise_accelerometer : (nk == 2 ? c.noise_joint_vel : nq));
+      const float t = (2.0f * NZ[slot ? slot - 1 : 0] - 1.0f) * lvl;
+      v = v + (slot ? t : -0.0f) * (slot ? ns : 1.0f);
     }
-    float v = 0;
-    if (k < 3) v = SENS[adr_gyro + k] + (2.0f * NZ[k] - 1.0f) * lvl * c.noise_gyro;
-    else if (k < 6) v = SENS[adr_acc + k - 3] + (2.0f * NZ[k] - 1.0f) * lvl * c.noise_accelerometer;
-    else if (k < 13) v = INFO[RL.CMD + k - 6];
-    else if (k < 13 + NU) {
-      const int u = k - 13;
-      const float ja = QPOS[A_aq] + (A_bq >= 0 ? QPOS[A_bq] : 0.0f);
-      v = ja + (2.0f * NZ[13 - 4 + u] - 1.0f) * lvl * A_ns - A_kc;
-    } else if (k < 13 + 2 * NU) {
-      const int u = k - 13 - NU;
-      v = (QVEL[V_ad] + (2.0f * NZ[DQV + u] - 1.0f) * lvl * c.noise_joint_vel) * c.dof_vel_scale;
-    } else if (k < 13 + 3 * NU) v = INFO[RL.LAST + k - 13 - 2 * NU];
-    else if (k < 13 + 4 * NU) v = INFO[RL.LAST2 + k - 13 - 3 * NU];
-    else if (k < 13 + 5 * NU) v = INFO[RL.LAST3 + k - 13 - 4 * NU];
-    else if (k < 13 + 6 * NU) v = INFO[RL.MT + k - 13 - 5 * NU];
-    else if (k < 15 + 6 * NU) v = (k - 13 - 6 * NU) ? con1 : con0;   // (scalars + selects: a runtime index parks the two-element arrays in scratch)
-    else if (k < 17 + 6 * NU) v = (k - 15 - 6 * NU) ? ph1 : ph0;
-    else {
-      if (q < 3) v = SENS[adr_gyro + q];
-      else if (q < 6) v = SENS[adr_acc + q - 3];
-      else if (q < 9) v = SCR[S::S_MISC + 10 + q - 6];
-      else if (q < 12) v = SENS[adr_lin + q - 9];
-      else if (q < 15) v = SENS[adr_ang + q - 12];
-      else if (q < 15 + NU) v = QPOS[Q_aq] + (Q_bq >= 0 ? QPOS[Q_bq] : 0.0f) - Q_kc;
-      else if (q < 15 + 2 * NU) v = QVEL[QV_ad];
-      else if (q == 15 + 2 * NU) v = QPOS[2];
-      else if (q < 16 + 3 * NU) v = L[S::O_ACTF + q - 16 - 2 * NU];
-      else if (q < 18 + 3 * NU) v = (q - 16 - 3 * NU) ? con1 : con0;
-      else if (q < 24 + 3 * NU) { const int t = q - 18 - 3 * NU; v = SENS[F_adr + (t >= 3 ? t - 3 : t)]; }
-      else if (q < 26 + 3 * NU) v = INFO[RL.AIR + q - 24 - 3 * NU];
-      else if (q < 66 + 3 * NU) v = L[E::O_REF + q - 26 - 3 * NU];
-      else if (q == 66 + 3 * NU) v = (float)imitation_i;
-      else v = (q - 67 - 3 * NU) ? ph1 : ph0;
-    }
+    v = v - e.kc;
+    v = v * ((e.fl & OBS_FL_VEL) ? c.dof_vel_scale : 1.0f);
     P[ks] = v;
   }
   ODK_SYNC();
-}
-template <class S, int G>
-__device__ __forceinline__ void build_obs(float* L, const DevModel* m, const EnvCfg& c, const float* contact, const float* NZ,
-                          int imitation_i, const float* phase, int lane) {
-  if (c.kind == 0) build_obs_kind<S, G, 0>(L, m, c, contact, NZ, imitation_i, phase, lane);
-  else build_obs_kind<S, G, 1>(L, m, c, contact, NZ, imitation_i, phase, lane);
 }
 
 __device__ __forceinline__ void foot_contact_flags(const float* CDIST, float* contact) {
@@ -553,7 +516,7 @@ __global__ void __launch_bounds__(64) reset_kernel(KArgs a) {
   const float phase[2] = {0, 0};
   // stash state before the obs overwrites the M|HL region?  (qpos/qvel/warm live elsewhere: safe)
   draw_block<E::NDRAW>(k0, k1, 0u, L + E::O_NZ, lane);   // the motion-column buffers are dead after the forward pass
-  build_obs<S, G>(L, m, c, contact, L + E::O_NZ, 0, phase, lane);
+  build_obs<S, G>(L, m, c, contact, L + E::O_NZ, 0, phase, c.noise_level != 0.0f, lane);
   if (lane == 0) {
     INFO[RL.KEY0] = i2f((int)k0); INFO[RL.KEY1] = i2f((int)k1); INFO[RL.CTR] = i2f(1);
     INFO[RL.STEP] = i2f(0); INFO[RL.PSTEP] = i2f(0); INFO[RL.PINT] = i2f(push_interval_steps);
@@ -582,8 +545,16 @@ __global__ void __launch_bounds__(64) reset_kernel(KArgs a) {
 // ================================================================================================
 // AutoReset.step -> Episode.step -> Joystick.step (joystick.py:323-481), all substeps fused
 constexpr int STEP_WAVES = 2;     // waves per SIMD the register allocation is held to (3 and 4 spill and run slower: profiles/r5/NOTES.md)
-template <class S, int G, int HF>
-__global__ void __launch_bounds__(64, STEP_WAVES) step_kernel(KArgs a) {
+// DBG: the instantiation that fills the debug image (a.dbg_lds: odk_set_debug_dump(1)): forward_env's debug-only stores are compiled in
+// and the image is dumped after the last forward pass; the product instantiation (DBG = false) has neither.  The profile build times the
+// product instruction stream and reads its counters through the image: its DBG = false kernel keeps the dump.
+#ifdef ODK_PROFILE
+constexpr bool STEP_DUMPS_ALWAYS = true;
+#else
+constexpr bool STEP_DUMPS_ALWAYS = false;
+#endif
+template <class S, int G, int HF, bool DBG>
+__device__ __forceinline__ void step_body(const KArgs& a) {
   extern __shared__ float lds[];
   using E = EnvL<S>; using R = Rec<S>;
   constexpr int NU = S::NU;
@@ -713,9 +684,11 @@ __global__ void __launch_bounds__(64, STEP_WAVES) step_kernel(KArgs a) {
     int lane_s = lane;
     asm volatile("" : "+v"(lane_s));
     __builtin_assume(lane_s >= 0 && lane_s < 64);
-    if constexpr (HF == 0) forward_env<S, G, HF, true>(L, RT, ms, a.hfield, st, lane_s, last ? 1 : 0, hot);
-    else forward_env<S, G, HF>(L, RT, ms, a.hfield, st, lane_s, last ? 1 : 0);
-    if (last && a.dbg_lds && live) dump_lds<S, G>(a.dbg_lds, L, env, lane);
+    if constexpr (HF == 0) forward_env<S, G, HF, true, DBG>(L, RT, ms, a.hfield, st, lane_s, last ? 1 : 0, hot);
+    else forward_env<S, G, HF, false, DBG>(L, RT, ms, a.hfield, st, lane_s, last ? 1 : 0);
+    if constexpr (DBG || STEP_DUMPS_ALWAYS) {
+      if (last && a.dbg_lds && live) dump_lds<S, G>(a.dbg_lds, L, env, lane);
+    }
     euler_env<S, G>(L, ms, st, lane_s);
   }
 #ifdef ODK_PROFILE
@@ -735,7 +708,14 @@ __global__ void __launch_bounds__(64, STEP_WAVES) step_kernel(KArgs a) {
   float ep_steps_e = INFO[RL.EPSTEPS];
   const float prev_done_e = INFO[RL.DONE];
   for (int u = lane; u < NU; u += G) INFO[RL.MT + u] = CTRL[u];  // info["motor_targets"] (:422)
-  draw_block<E::NDRAW>(k0e, k1e, ctre, L + E::O_NZ, lane);   // the motion-column buffers are dead after the last forward pass
+  // This step's draws 4 .. 3 + NDRAW feed the observation noise (every one scaled by noise_level) and, on a step that resamples a
+  // sampled command, the new command.  With noise off and no env of the wave resampling, nobody reads them: the generator block and the
+  // noise terms of the observation are skipped (a wave-uniform test; the key and the counter advance below as ever, so a run that turns
+  // noise on later draws from the same stream).  An exact-zero observation keeps its sign where the zero noise term made it +0.
+  const bool noisy = c.noise_level != 0.0f;
+  const bool resamples = !a.cmd && step_e + 1 > 500;
+  if (noisy || __builtin_amdgcn_ballot_w64(resamples) != 0)
+    draw_block<E::NDRAW>(k0e, k1e, ctre, L + E::O_NZ, lane);   // the motion-column buffers are dead after the last forward pass
   // reference motion of this step: evaluated in the prologue, parked here (reward and privileged obs are its only readers)
   if (lane < 40) L[E::O_REF + lane] = ref0;
   if (lane < 8) L[E::O_REF + 32 + lane] = ref1;
@@ -829,7 +809,7 @@ __global__ void __launch_bounds__(64, STEP_WAVES) step_kernel(KArgs a) {
   const float reward = fminf(fmaxf(total * dt, 0.0f), 10000.0f);
   // ---- obs (uses the pre-shift last_act and the post-increment air time; :437)
   const float* NZ = L + E::O_NZ;   // this step's draws 4 .. 49 (drawn above, before the reward block)
-  build_obs<S, G>(L, mp, c, contact, NZ, imi_e, phase_e, lane);
+  build_obs<S, G>(L, mp, c, contact, NZ, imi_e, phase_e, noisy, lane);
   // ---- info updates (:449-469)
   step_e += 1; push_step_e += 1;
   float la = 0, lla = 0;
@@ -890,6 +870,12 @@ __global__ void __launch_bounds__(64, STEP_WAVES) step_kernel(KArgs a) {
   if (a.dbg_lds && live && lane == 0) a.dbg_lds[(size_t)env * S::TOTAL + S::O_SCR + S::S_PROF + 19] = (float)(clock64() - t_k2);
 #endif
 }
+
+// the product step and the one that fills the debug image (kernels of their own names: the product kernels keep theirs)
+template <class S, int G, int HF>
+__global__ void __launch_bounds__(64, STEP_WAVES) step_kernel(KArgs a) { step_body<S, G, HF, false>(a); }
+template <class S, int G, int HF>
+__global__ void __launch_bounds__(64, STEP_WAVES) step_kernel_dbg(KArgs a) { step_body<S, G, HF, true>(a); }
 
 // mjx_env.step alone: ctrl = action buffer, no env logic (parity tests)
 template <class S, int G, int HF>
@@ -1351,6 +1337,65 @@ static bool build_convex_tables(const double (*v)[3], int nv, const int (*tri)[3
   return true;
 }
 
+// DevModel::obs_tab: the observation layouts (joystick.py:570-615 / standing.py:524-565) as gather entries, one per output
+// element, for both tasks.  Joystick, nu actuators: gyro 3 (noisy) | accelerometer 3 (noisy) | command 7 | joint angles - default nu (noisy; the
+// backlash twin's angle added where the actuator has one) | joint velocities nu (noisy, scaled) | last_act, last_last_act, last_last_last_act,
+// motor_targets nu each | contact 2 | phase 2; privileged tail: gyro, accelerometer, gravity, local linvel, global angvel 3 each | joint angles -
+// default nu | joint velocities nu | root height 1 | actuator forces nu | contact 2 | feet linvel 6 | air time 2 | reference motion 40 |
+// imitation counter 1 | phase 2.  Standing = the same minus motor_targets, the observed phase, reference motion, counter and privileged phase.
+template <class S> static void build_obs_table(DevModel& m) {
+  using E = EnvL<S>;
+  constexpr int NU = S::NU;
+  constexpr RecLay RL = rec_lay(NU);
+  constexpr int NOBS = obs_nobs(NU, false);
+  static_assert(obs_npriv(NU, false) <= OBS_MAX && draw_count(NU) < 255 && 3 + NU <= 32, "ObsEnt");
+  const int MISC = S::O_SCR + S::S_MISC, INFO = E::O_INFO, SENS = S::O_SENS;
+  for (int kind = 0; kind < 2; kind++) {
+    const bool standing = kind != 0;
+    const int NP = obs_npriv(NU, standing);
+    for (int ks = 0; ks < OBS_MAX; ks++) {
+      ObsEnt e = {0, -1, 0.0f, 0};
+      if (ks < NP) {
+        const int k = !standing ? ks : (ks < 13 + 5 * NU ? ks : (ks < 15 + 5 * NU ? ks + NU : ks + NOBS - (15 + 5 * NU)));
+        const int q = k - NOBS;
+        auto noise = [&](int draw, int kind_) { e.fl |= (draw - 4 + 1) | kind_ << 8; };   // (draw i sits at NZ[i - 4])
+        auto joint = [&](int u) {
+          e.a = S::O_QPOS + m.act_qposadr[u];
+          if (m.act_backlash_qposadr[u] >= 0) e.b = S::O_QPOS + m.act_backlash_qposadr[u]; else e.fl |= OBS_FL_PLUS0;
+          e.kc = m.key_ctrl[u];
+        };
+        if (k < 3) { e.a = SENS + m.adr_gyro + k; noise(4 + k, 0); }
+        else if (k < 6) { e.a = SENS + m.adr_accelerometer + k - 3; noise(4 + k, 1); }
+        else if (k < 13) e.a = INFO + RL.CMD + k - 6;
+        else if (k < 13 + NU) { const int u = k - 13; joint(u); noise(13 + u, 3 + u); }
+        else if (k < 13 + 2 * NU) { const int u = k - 13 - NU; e.a = S::O_QVEL + m.act_dofadr[u]; noise(draw_qvel(NU) + u, 2); e.fl |= OBS_FL_VEL; }
+        else if (k < 13 + 3 * NU) e.a = INFO + RL.LAST + k - 13 - 2 * NU;
+        else if (k < 13 + 4 * NU) e.a = INFO + RL.LAST2 + k - 13 - 3 * NU;
+        else if (k < 13 + 5 * NU) e.a = INFO + RL.LAST3 + k - 13 - 4 * NU;
+        else if (k < 13 + 6 * NU) e.a = INFO + RL.MT + k - 13 - 5 * NU;
+        else if (k < 15 + 6 * NU) e.a = MISC + OBS_PARK_CON + k - 13 - 6 * NU;
+        else if (k < 17 + 6 * NU) e.a = MISC + OBS_PARK_PHASE + k - 15 - 6 * NU;
+        else if (q < 3) e.a = SENS + m.adr_gyro + q;
+        else if (q < 6) e.a = SENS + m.adr_accelerometer + q - 3;
+        else if (q < 9) e.a = MISC + 10 + q - 6;
+        else if (q < 12) e.a = SENS + m.adr_local_linvel + q - 9;
+        else if (q < 15) e.a = SENS + m.adr_global_angvel + q - 12;
+        else if (q < 15 + NU) joint(q - 15);
+        else if (q < 15 + 2 * NU) e.a = S::O_QVEL + m.act_dofadr[q - 15 - NU];
+        else if (q == 15 + 2 * NU) e.a = S::O_QPOS + 2;
+        else if (q < 16 + 3 * NU) e.a = S::O_ACTF + q - 16 - 2 * NU;
+        else if (q < 18 + 3 * NU) e.a = MISC + OBS_PARK_CON + q - 16 - 3 * NU;
+        else if (q < 24 + 3 * NU) { const int t = q - 18 - 3 * NU; e.a = SENS + m.adr_foot_linvel[t >= 3 ? 1 : 0] + (t >= 3 ? t - 3 : t); }
+        else if (q < 26 + 3 * NU) e.a = INFO + RL.AIR + q - 24 - 3 * NU;
+        else if (q < 66 + 3 * NU) e.a = E::O_REF + q - 26 - 3 * NU;
+        else if (q == 66 + 3 * NU) e.a = MISC + OBS_PARK_IMI;
+        else e.a = MISC + OBS_PARK_PHASE + q - 67 - 3 * NU;
+      }
+      m.obs_tab[kind][ks] = e;
+    }
+  }
+}
+
 extern "C" int odk_model_load(const void* blob, uint64_t len, odk_model** out) {
   if (!blob || !out || len < 16 || memcmp(blob, "ODKM", 4) != 0) return fail(ODK_ERR_INVALID, "odk_model_load: not an ODKM blob");
   Blob B{(const unsigned char*)blob, len};
@@ -1796,6 +1841,9 @@ extern "C" int odk_model_load(const void* blob, uint64_t len, odk_model** out) {
     ODK_SHAPES(X)
 #undef X
   }
+#define X(i, S) if (mo->shape == i) build_obs_table<S>(m);
+  ODK_SHAPES(X)
+#undef X
   *out = mo;
   return ODK_OK;
 }
@@ -1969,7 +2017,12 @@ template <class S, int G, int HF> static hipError_t launch_sg(int which, const K
   const int grid = (a.nenv + per_block - 1) / per_block;
   const size_t lds = (size_t)EnvL<S>::wg_floats(per_block) * sizeof(float);
   if (which == K_RESET) hipLaunchKernelGGL((reset_kernel<S, G, HF>), dim3(grid), dim3(64), lds, st, a);
-  else if (which == K_STEP) hipLaunchKernelGGL((step_kernel<S, G, HF>), dim3(grid), dim3(64), lds, st, a);
+  else if (which == K_STEP) {   // reset and physics launches always carry the debug image (one instantiation each, debug stores compiled in)
+    if constexpr (!STEP_DUMPS_ALWAYS) {   // (the profile build never launches the debug kernels and does not instantiate them)
+      if (a.dbg_lds) { hipLaunchKernelGGL((step_kernel_dbg<S, G, HF>), dim3(grid), dim3(64), lds, st, a); return hipGetLastError(); }
+    }
+    hipLaunchKernelGGL((step_kernel<S, G, HF>), dim3(grid), dim3(64), lds, st, a);
+  }
   else hipLaunchKernelGGL((physics_kernel<S, G, HF>), dim3(grid), dim3(64), lds, st, a);
   return hipGetLastError();
 }
@@ -2397,6 +2450,7 @@ template <class S> static int lds_off(const char* name) {
   if (!strcmp(name, "contact_dist")) return S::O_CDIST;
   if (!strcmp(name, "contact_r")) return S::O_CR;
   if (!strcmp(name, "scr")) return S::O_SCR;
+  if (!strcmp(name, "misc")) return S::O_SCR + S::S_MISC;   // the 16 misc scalars (solver diagnostics of the debug image; feet heights, gravity)
   if (!strcmp(name, "sensordata")) return S::O_SENS;
   if (!strcmp(name, "actuator_force")) return S::O_ACTF;
   if (!strcmp(name, "qacc")) return S::O_QACC;

@@ -1901,7 +1901,9 @@ __device__ __forceinline__ void cone_line(float Dn, float Dt, float Dm, float mu
   d1 = e.zone == 0 ? 0.0f : (e.zone == 1 ? b1 : b2);
 }
 
-template <class S, int G, int HF, bool PRE = false>
+// DBG: the stores that only the debug image reads (dump_lds: Jaref / J search of the contact rows, the gradient at the starting point, the
+// solver diagnostics in S_MISC + 1..7, 13..15) are compiled in; the product step kernels take DBG = false.
+template <class S, int G, int HF, bool PRE = false, bool DBG = true>
 __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevModel* __restrict__ m, const float* __restrict__ hfield, const Statics<S, G>& st, int lane, int flags, const HotSt& hot = HotSt()) {
   // RT: the packed reduced entries (DevModel::R_ent) in LDS, one copy per workgroup (load_shared): every substep reads them
   // twice (inertia, Hessian), and a table load from the L2-resident model right behind a phase hand-off is ~300 exposed cycles.
@@ -2875,7 +2877,7 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
   for (int t = 0; t < NCL; t++) {
     cjar[t] = use_warm ? cjv[t] : cjar[t];
     const int rc = lane + t * G;
-    if (rc < S::NCROW) JAR[r0c + rc] = cjar[t];   // debug image only
+    if constexpr (DBG) { if (rc < S::NCROW) JAR[r0c + rc] = cjar[t]; }   // debug image only
   }
   ODK_PROF(10);
   // forces of the chosen point: friction / limit rows stay in registers, contact forces -> JV
@@ -3066,7 +3068,7 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
     }
     return v;
   };
-  if (st.d_on) { MA[lane] = grad; GRAD[lane] = grad; }   // MA: kept for the debug image (gradient at the starting point)
+  if (st.d_on) { if constexpr (DBG) MA[lane] = grad; GRAD[lane] = grad; }   // MA: debug image only (gradient at the starting point)
   // right-hand side of the reduced system on the reduced-dof lanes (twin-free model: the gradient itself)
   float rhs = grad;
   if constexpr (S::PAIRED) {
@@ -3217,7 +3219,7 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
     const bool on = rc < S::NCROW;
     cjv[t] = 0.0f;
     if (!(t * G >= 32 && !any_ff)) cjv[t] = (on && cD[t] > 0) ? contact_jx(rc, SCR + S::S_VF) : 0.0f;
-    if (on) JV[r0c + rc] = cjv[t];  // debug image only
+    if constexpr (DBG) { if (on) JV[r0c + rc] = cjv[t]; }  // debug image only
   }
   ODK_PROF(15);
   // elliptic cones: the contact's three Jaref and J search in every lane of its quad, once for the whole line search
@@ -3367,9 +3369,11 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
     X[lane] = xa;
     WARM[lane] = xa;
   }
-  if (lane == 0) { SCR[S::S_MISC + 13] = qg1; SCR[S::S_MISC + 14] = qg2; SCR[S::S_MISC + 15] = gauss; }
-  if (lane == 0) { SCR[S::S_MISC + 4] = p0_d0; SCR[S::S_MISC + 5] = p0_d1; SCR[S::S_MISC + 6] = p0_cost; SCR[S::S_MISC + 7] = gtol; }
-  if (lane == 0) { SCR[S::S_MISC + 1] = alpha; SCR[S::S_MISC + 2] = use_warm ? 1.0f : 0.0f; SCR[S::S_MISC + 3] = use_warm ? cost_w : cost_s; }
+  if constexpr (DBG) {   // solver diagnostics: debug image only (slots 8..12 belong to the env logic and are written below)
+    if (lane == 0) { SCR[S::S_MISC + 13] = qg1; SCR[S::S_MISC + 14] = qg2; SCR[S::S_MISC + 15] = gauss; }
+    if (lane == 0) { SCR[S::S_MISC + 4] = p0_d0; SCR[S::S_MISC + 5] = p0_d1; SCR[S::S_MISC + 6] = p0_cost; SCR[S::S_MISC + 7] = gtol; }
+    if (lane == 0) { SCR[S::S_MISC + 1] = alpha; SCR[S::S_MISC + 2] = use_warm ? 1.0f : 0.0f; SCR[S::S_MISC + 3] = use_warm ? cost_w : cost_s; }
+  }
   ODK_SYNC();
   ODK_PROF(16);
 

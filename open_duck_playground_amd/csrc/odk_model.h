@@ -11,7 +11,7 @@ constexpr int MAXV = 32;     // dofs
 constexpr int MAXQ = 32;     // qpos
 constexpr int MAXB = 20;     // bodies
 constexpr int MAXJ = 26;     // joints
-constexpr int MAXU = 16;     // actuators
+constexpr int MAXU = 16;     // actuators (build_obs in odk_engine.hip picks the joint-angle noise scale in its first pass: 13 + nu <= lanes per env, i.e. nu <= 19 at 32 lanes)
 constexpr int MAXNZ = 512;   // sparse matrix entries
 constexpr int MAXHV = 20;    // hull vertices per foot
 constexpr int MAXHF = 40;    // hull faces per foot
@@ -56,6 +56,16 @@ struct LaneSt {
   int d_tkind, d_red;                    // twin dofs (DevModel::paired): 0 unpaired / 1 main (twin = dof + 1) / 2 twin; reduced dof
   float d_damping, d_lo, d_hi;           // joint range of the dof's hinge
 };
+
+// One element of an observation layout (DevModel::obs_tab; odk_engine.hip build_obs_table fills it at model load, build_obs gathers through it):
+// a, b: offsets in the env's LDS image (floats) of the value and of a second one added to it (-1: none); kc: a constant subtracted (0: none);
+// fl: draw slot + 1 in NZ (bits 0-7; 0: no noise) | noise scale (bits 8-12: 0 gyro, 1 accelerometer, 2 joint velocity, 3 + u the joint angle of
+// actuator u) | OBS_FL_VEL: times dof_vel_scale | OBS_FL_PLUS0: a joint angle without a backlash twin (adds +0 where the twin's angle would go).
+struct ObsEnt { int a, b; float kc; int fl; };
+constexpr int OBS_FL_VEL = 1 << 13, OBS_FL_PLUS0 = 1 << 14;
+constexpr int OBS_MAX = 232;   // >= the privileged Joystick layout of MAXU actuators (17 + 6 nu + 26 + 3 nu + 43 = 230)
+// values the env epilogue holds in registers, parked for the gather in the solver-diagnostic slots of Shape::S_MISC (free after the last forward pass)
+constexpr int OBS_PARK_CON = 1, OBS_PARK_IMI = 3, OBS_PARK_PHASE = 4;
 
 struct DevModel {
   BodySt body_st[2][64];   // [G == 64][lane]: the body record of each lane of an env (fill_body_st)
@@ -171,6 +181,8 @@ struct DevModel {
   int cone;      // <option cone>: 0 pyramidal, 1 elliptic (shapes with S::ELL; odk_kernels.h "elliptic cones")
   int neq, eq_dof1[EQ_MAX], eq_dof2[EQ_MAX], eq_qadr1[EQ_MAX], eq_qadr2[EQ_MAX], eq_key[EQ_MAX], dof_eqrow[MAXV];
   float eq_poly[EQ_MAX][5], eq_imp[EQ_MAX][9], eq_invweight[EQ_MAX];
+  // observation layouts, [0] Joystick, [1] Standing (last: every older field keeps its offset)
+  alignas(16) ObsEnt obs_tab[2][OBS_MAX];
 };
 
 // Topology of a height-field prism (vertices 0..2 = top triangle counter-clockwise seen from above, 3..5 below them; faces: top,

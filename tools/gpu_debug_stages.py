@@ -58,7 +58,7 @@ for e in range(n):
     r["aref"] = _rel(Ag[both], d["efc_aref"][:nefc][both], 1.0).max()
     r["qacc"] = _rel(L[o["qacc"]: o["qacc"] + nv], d["qacc"][:nv], 5.0).max()
     r["sens"] = _rel(L[o["sensordata"]: o["sensordata"] + 46], d["sensordata"][:46], 1.0).max()
-    misc = L[o["scr"] + 156: o["scr"] + 160]
+    misc = L[b.lds_offset("misc"): b.lds_offset("misc") + 4]
     r["alpha"] = (float(misc[1]), float(d["ls_alpha"][0])); r["warm"] = (int(misc[2]), d.i("warm_used")); r["cost0"] = (float(misc[3]), float(d["solver_cost0"][0]))
     d2 = O.OracleData(om)
     d2["qpos"][: om.nq] = qpos[e]; d2["qvel"][:nv] = qvel[e]; d2["qacc_warmstart"][:nv] = warm[e]
@@ -100,6 +100,7 @@ for e in (0, 3):
 e = 1
 L = img[e]
 oW, oD, oJ, oJV, oS = b.lds_offset("W"), b.lds_offset("efc_D"), b.lds_offset("jar"), b.lds_offset("jv"), b.lds_offset("scr")
+oM = b.lds_offset("misc")
 W = L[oW: oW + 288].reshape(48, 6); Dr = L[oD + r0c: oD + r0c + 48]; jar = L[oJ + r0c: oJ + r0c + 48]
 act = np.where((Dr > 0) & (jar < 0), Dr, 0.0)
 for f in range(2):
@@ -181,12 +182,12 @@ for e in (0, 3):
             else: q1 += D[r] * jv[r] * jar[r]; q2 += 0.5 * D[r] * jv[r] ** 2
         elif jar[r] < 0 and np.abs(J[r]).sum() > 0:
             q1 += D[r] * jv[r] * jar[r]; q2 += 0.5 * D[r] * jv[r] ** 2
-    misc = img[e][oS + 156: oS + 164]
+    misc = img[e][oM: oM + 8]
     print("env", e, "p0 deriv0 gpu", misc[4], "exp", q1, "| deriv1 gpu", misc[5], "exp", 2 * q2, "| alpha gpu", misc[1], "newton", -q1 / (2 * q2), "gtol", misc[7])
     jvg = img[e][oJV + r0c: oJV + r0c + 48]; jarg = img[e][oJ + r0c: oJ + r0c + 48]; Dg = img[e][oD + r0c: oD + r0c + 48]
     print("  jv contact gpu", jvg[:32]); print("  jv contact exp", jv[r0c:r0c+32]); print("  jar gpu", jarg[:16]); print("  jar exp", jar[r0c:r0c+16])
     print("  twist gpu", img[e][oS: oS + 12])
-    misc = img[e][oS + 156: oS + 172]
+    misc = img[e][oM: oM + 16]
     print("  qg1 gpu", misc[13], "exp", sg @ Ma - sg @ qfs_, "qg2 gpu", misc[14], "exp", 0.5 * sg @ (d.M() @ sg))
     # friction + limit row contributions
     c1 = c2 = 0.0

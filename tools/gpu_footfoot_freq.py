@@ -10,7 +10,7 @@ cfg = engine.default_config(); cfg.noise_level = 0.0; cfg.push_enable = 0.0
 b = engine.Batch(model, 8192, cfg); b.reset(0)
 act = torch.empty(8192, 14, device="cuda")
 b.L.odk_set_debug_dump(1)
-o = b.lds_offset("scr") + 156
+o = b.lds_offset("misc")
 tot = ov = pen = 0
 for t in range(60):
     b.step(act.uniform_(-1, 1))

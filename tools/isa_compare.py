@@ -66,11 +66,11 @@ def normalise(lines):
 
 
 def short(name):
-    m = re.search(r"(reset_kernel|step_kernel|physics_kernel)IN3odk5ShapeI([^E]*)EE?ELi(\d+)ELi(\d+)", name)
+    m = re.search(r"(reset_kernel|step_kernel_dbg|step_kernel|physics_kernel)IN3odk5ShapeI(.*?)EEELi(\d+)ELi(\d+)", name)
     if m:
         dims = m.group(2).replace("ELi", ",").replace("Li", "").replace("ELb", ",b").replace("n1", "-1")
         return f"{m.group(1)}<Shape<{dims}>,{m.group(3)},{m.group(4)}>"
-    return name[:100]
+    return name
 
 
 def main():
