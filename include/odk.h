@@ -274,6 +274,51 @@ enum { ODK_PUSH_PUSHED = 0, ODK_PUSH_PUSH_AT = 1, ODK_PUSH_FELL = 2, ODK_PUSH_ST
 int odk_push_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
                         const float* track_acc_dev, float lin_tol, float ang_tol, float* acc_dev, void* stream);
 
+/* Gait and actuator-load accumulator (how does the policy walk, and what does that cost the motors): one launch per evaluation step,
+ * graph-capturable, issued after odk_step and BEFORE odk_tracking_accumulate (track_acc_dev [nenv, ODK_TRACK_NACC] is that function's
+ * accumulator: its ENDED slot then still says whether env e's first episode was running when this step began).  Independent of
+ * odk_push_accumulate; needs neither bound commands nor bound pushes.  Env e's row of acc_dev [nenv, ODK_GAIT_NACC], zeroed by the caller
+ * before the first step, is updated only on a gait sample: a step of e's first episode that is not done (odk_tracking_accumulate's
+ * velocity sample; a done step's observation is the auto-reset's first one).  Every other row keeps its bits.  All inputs are the
+ * noise-free privileged observation of this step (priv_dev [nenv, npriv]; nu, nobs, npriv: odk_model_obs_sizes), the same layout in
+ * both tasks, offsets from the start of the env's row:
+ *   last_act 13 + 2 nu (nu) | last_last_act 13 + 3 nu (nu) | gyro nobs (3) | local linvel nobs + 9 (3) | joint angles minus the default
+ *   pose nobs + 15 (nu) | joint_vel nobs + 15 + nu (nu) | root_height nobs + 15 + 2 nu (1) | actuator_force nobs + 16 + 2 nu (nu) |
+ *   contact nobs + 16 + 3 nu (2: left, right) | feet_vel nobs + 18 + 3 nu (2 x 3)
+ * Scalar slots ([2]: left foot, right foot):
+ *   SAMPLES               gait samples
+ *   SPEED_SUM             sum of hypot(vx, vy) of the local linear velocity
+ *   ABS_POWER_SUM         sum over samples and actuators of |actuator_force * joint_vel|
+ *   CONTACT[2], DOUBLE, FLIGHT   samples with that foot, both feet, no foot in contact
+ *   TOUCHDOWNS[2]         samples in contact whose previous sample was not; the env's first sample counts none
+ *   SWING_STEPS_SUM[2]    at a touchdown, the length in samples of the non-contact run that ended (counted from the env's first sample)
+ *   SLIP_SUM[2]           over the samples in contact, hypot of that foot's planar feet_vel
+ *   HEIGHT_SUM, HEIGHT_SQ_SUM    of root_height
+ *   ROLLPITCH_RATE_SQ_SUM gyro_x^2 + gyro_y^2
+ *   ACTION_RATE_SUM       sum over actuators of (last_act - last_last_act)^2
+ *   PREV_CONTACT[2], AIR_RUN[2]  bookkeeping: the last sample's contact, the length of the running non-contact run
+ * Per-actuator arrays, entry u at SLOT + u, ODK_GAIT_STRIDE = 16 apart (entries nu .. 15 stay 0):
+ *   TORQUE_SQ             sum of actuator_force^2
+ *   TORQUE_PEAK, VEL_PEAK max |actuator_force|, max |joint_vel|
+ *   SAT                   samples with |actuator_force| >= 0.99f * torque_limit[u] (float32); never counted when torque_limit_dev is NULL
+ *                         or torque_limit[u] <= 0
+ *   ABS_POWER             sum of |actuator_force * joint_vel|
+ *   RANGE_MIN, RANGE_MAX  of the joint angle minus the default pose; the env's first sample initialises both
+ * Every summed term is non-negative and added in float32 in step order.  done_dev / truncation_dev: [nenv] (a gait sample does not depend
+ * on the truncation flag; the argument keeps the three accumulators' call shape); torque_limit_dev: [nu] device floats or NULL.  A null
+ * pointer other than torque_limit_dev, or a model with more than ODK_GAIT_STRIDE actuators: ODK_ERR_INVALID, odk_last_error names the
+ * argument, nothing is launched. */
+#define ODK_GAIT_NACC 144
+#define ODK_GAIT_STRIDE 16
+enum { ODK_GAIT_SAMPLES = 0, ODK_GAIT_SPEED_SUM = 1, ODK_GAIT_ABS_POWER_SUM = 2, ODK_GAIT_CONTACT = 3, ODK_GAIT_DOUBLE = 5, ODK_GAIT_FLIGHT = 6,
+       ODK_GAIT_TOUCHDOWNS = 7, ODK_GAIT_SWING_STEPS_SUM = 9, ODK_GAIT_SLIP_SUM = 11, ODK_GAIT_HEIGHT_SUM = 13, ODK_GAIT_HEIGHT_SQ_SUM = 14,
+       ODK_GAIT_ROLLPITCH_RATE_SQ_SUM = 15, ODK_GAIT_ACTION_RATE_SUM = 16, ODK_GAIT_PREV_CONTACT = 17, ODK_GAIT_AIR_RUN = 19,
+       ODK_GAIT_TORQUE_SQ = 32, ODK_GAIT_TORQUE_PEAK = 48, ODK_GAIT_VEL_PEAK = 64, ODK_GAIT_SAT = 80, ODK_GAIT_ABS_POWER = 96,
+       ODK_GAIT_RANGE_MIN = 112, ODK_GAIT_RANGE_MAX = 128 };
+int odk_gait_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
+                        const float* track_acc_dev, const float* torque_limit_dev /* [nu] or NULL */, float* acc_dev /* [nenv, ODK_GAIT_NACC] */,
+                        void* stream);
+
 /* mjx_env.step alone (physics only, n_substeps, ctrl = ctrl_dev [nenv, nu]); for parity tests */
 int odk_physics_step(odk_batch* b, const float* ctrl_dev, int n_substeps, void* stream);
 

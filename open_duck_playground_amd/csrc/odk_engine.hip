@@ -2342,6 +2342,104 @@ extern "C" int odk_push_accumulate(const odk_batch* b, const float* priv_dev, co
   return ODK_OK;
 }
 
+// Gait and actuator-load sums of one evaluation step, issued between odk_step and odk_tracking_accumulate (the ENDED contract of push_kernel).
+// One 16-lane DPP row per env, lane = actuator, four envs per wave: the nu-wide reads of the privileged row and the per-actuator arrays of the
+// accumulator row (stride ODK_GAIT_STRIDE = 16) are contiguous 64-byte accesses, the per-env scalars are row sums (the four in-row butterfly
+// stages of greduce).  The 32 scalar slots are held two per lane (u and 16 + u); every lane computes the row-uniform terms and keeps its own.
+// Only a gait sample (first episode, not done) stores anything, so every other row keeps its bits.
+__device__ __forceinline__ float row_sum16(float x) {   // uniform control flow only
+  x += ODK_DPP(x, 0xB1, 0xF); x += ODK_DPP(x, 0x4E, 0xF); x += ODK_DPP(x, 0x141, 0xF); x += ODK_DPP(x, 0x140, 0xF);
+  return x;
+}
+__global__ void __launch_bounds__(256) gait_kernel(const float* __restrict__ priv, int npriv, int nobs, int nu, const float* __restrict__ done,
+                                                   const float* __restrict__ track, const float* __restrict__ limit, float* __restrict__ acc, int nenv) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int e = t >> 4, u = t & 15;
+  const bool sample = e < nenv && track[(size_t)(e < nenv ? e : 0) * ODK_TRACK_NACC + ODK_TRACK_ENDED] == 0.0f && done[e < nenv ? e : 0] == 0.0f;
+  const bool act = sample && u < nu;
+  const float* P = priv + (size_t)(sample ? e : 0) * npriv;   // row 0 for the rows that only take part in the row sums
+  float* A = acc + (size_t)(sample ? e : 0) * ODK_GAIT_NACC;
+  const float* Q = P + nobs;
+  // per actuator (0 in the lanes past nu and in the rows that are no sample)
+  const float a1 = act ? P[13 + 2 * nu + u] : 0.0f, a2 = act ? P[13 + 3 * nu + u] : 0.0f;
+  const float q = act ? Q[15 + u] : 0.0f, v = act ? Q[15 + nu + u] : 0.0f, f = act ? Q[16 + 2 * nu + u] : 0.0f;
+  const float lim = (act && limit) ? limit[u] : 0.0f;
+  const float af = fabsf(f), pw = fabsf(f * v), da = a1 - a2;
+  const float power = row_sum16(pw), arate = row_sum16(da * da);
+  if (!sample) return;
+  // per env (the same in the row's 16 lanes)
+  const float n0 = A[ODK_GAIT_SAMPLES];
+  const bool first = n0 == 0.0f;
+  const float h = Q[15 + 2 * nu];
+  float c[2], td[2], swing[2], slip[2], run[2];
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    const float* FV = Q + 18 + 3 * nu + 3 * k;
+    const bool con = Q[16 + 3 * nu + k] != 0.0f;
+    const float air = A[ODK_GAIT_AIR_RUN + k];
+    const bool touch = con && !first && A[ODK_GAIT_PREV_CONTACT + k] == 0.0f;
+    c[k] = con ? 1.0f : 0.0f;
+    td[k] = touch ? 1.0f : 0.0f;
+    swing[k] = touch ? air : 0.0f;               // the non-contact run that this touchdown ends
+    slip[k] = con ? hypotf(FV[0], FV[1]) : 0.0f;
+    run[k] = con ? 0.0f : air + 1.0f;
+  }
+  const float speed = hypotf(Q[9], Q[10]), wob = Q[0] * Q[0] + Q[1] * Q[1];
+  // scalar slot s: what it gains, or (bookkeeping) what it becomes
+  auto next = [&](int s, float old) {
+    float inc = 0.0f;
+    inc = s == ODK_GAIT_SAMPLES ? 1.0f : inc;
+    inc = s == ODK_GAIT_SPEED_SUM ? speed : inc;
+    inc = s == ODK_GAIT_ABS_POWER_SUM ? power : inc;
+    inc = s == ODK_GAIT_CONTACT ? c[0] : s == ODK_GAIT_CONTACT + 1 ? c[1] : inc;
+    inc = s == ODK_GAIT_DOUBLE ? c[0] * c[1] : inc;
+    inc = s == ODK_GAIT_FLIGHT ? (1.0f - c[0]) * (1.0f - c[1]) : inc;
+    inc = s == ODK_GAIT_TOUCHDOWNS ? td[0] : s == ODK_GAIT_TOUCHDOWNS + 1 ? td[1] : inc;
+    inc = s == ODK_GAIT_SWING_STEPS_SUM ? swing[0] : s == ODK_GAIT_SWING_STEPS_SUM + 1 ? swing[1] : inc;
+    inc = s == ODK_GAIT_SLIP_SUM ? slip[0] : s == ODK_GAIT_SLIP_SUM + 1 ? slip[1] : inc;
+    inc = s == ODK_GAIT_HEIGHT_SUM ? h : inc;
+    inc = s == ODK_GAIT_HEIGHT_SQ_SUM ? h * h : inc;
+    inc = s == ODK_GAIT_ROLLPITCH_RATE_SQ_SUM ? wob : inc;
+    inc = s == ODK_GAIT_ACTION_RATE_SUM ? arate : inc;
+    float nv = old + inc;
+    nv = s == ODK_GAIT_PREV_CONTACT ? c[0] : s == ODK_GAIT_PREV_CONTACT + 1 ? c[1] : nv;
+    nv = s == ODK_GAIT_AIR_RUN ? run[0] : s == ODK_GAIT_AIR_RUN + 1 ? run[1] : nv;
+    return nv;
+  };
+  const float s0 = next(u, A[u]), s1 = next(16 + u, A[16 + u]);
+  A[u] = s0;
+  A[16 + u] = s1;
+  if (u >= nu) return;
+  float* B = A + u;
+  B[ODK_GAIT_TORQUE_SQ] += f * f;
+  B[ODK_GAIT_TORQUE_PEAK] = fmaxf(B[ODK_GAIT_TORQUE_PEAK], af);
+  B[ODK_GAIT_VEL_PEAK] = fmaxf(B[ODK_GAIT_VEL_PEAK], fabsf(v));
+  B[ODK_GAIT_SAT] += (lim > 0.0f && af >= 0.99f * lim) ? 1.0f : 0.0f;
+  B[ODK_GAIT_ABS_POWER] += pw;
+  B[ODK_GAIT_RANGE_MIN] = first ? q : fminf(B[ODK_GAIT_RANGE_MIN], q);   // a zeroed row is no minimum: the first sample starts the range
+  B[ODK_GAIT_RANGE_MAX] = first ? q : fmaxf(B[ODK_GAIT_RANGE_MAX], q);
+}
+
+extern "C" int odk_gait_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
+                                   const float* track_acc_dev, const float* torque_limit_dev, float* acc_dev, void* stream) {
+  if (!b) return fail(ODK_ERR_INVALID, "odk_gait_accumulate: null batch");
+  if (!priv_dev) return fail(ODK_ERR_INVALID, "odk_gait_accumulate: null priv_dev");
+  if (!done_dev) return fail(ODK_ERR_INVALID, "odk_gait_accumulate: null done_dev");
+  if (!truncation_dev) return fail(ODK_ERR_INVALID, "odk_gait_accumulate: null truncation_dev");
+  if (!track_acc_dev) return fail(ODK_ERR_INVALID, "odk_gait_accumulate: null track_acc_dev");
+  if (!acc_dev) return fail(ODK_ERR_INVALID, "odk_gait_accumulate: null acc_dev");
+  const int nu = b->model.h.nu;
+  if (nu > ODK_GAIT_STRIDE) return fail(ODK_ERR_INVALID, "odk_gait_accumulate: the model has %d actuators, a row holds %d", nu, ODK_GAIT_STRIDE);
+  int nobs, npriv;
+  obs_sizes_nu(nu, b->cfg.env_kind, &nobs, &npriv);
+  HIPCHK(hipSetDevice(b->device));
+  const long long threads = (long long)b->nenv * 16;
+  hipLaunchKernelGGL(gait_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, priv_dev, npriv, nobs, nu, done_dev,
+                     track_acc_dev, torque_limit_dev, acc_dev, b->nenv);
+  HIPCHK(hipGetLastError());
+  return ODK_OK;
+}
+
 extern "C" int odk_physics_step(odk_batch* b, const float* ctrl_dev, int n_substeps, void* stream) {
   if (!b || !ctrl_dev) return fail(ODK_ERR_INVALID, "null argument");
   HIPCHK(hipSetDevice(b->device));

@@ -158,6 +158,7 @@ def load_library() -> C.CDLL:
     L.odk_batch_set_head_joints.argtypes = [P, C.POINTER(C.c_int32), C.c_int]
     L.odk_tracking_accumulate.argtypes = [P, P, P, P, P, P, P]
     L.odk_push_accumulate.argtypes = [P, P, P, P, P, C.c_float, C.c_float, P, P]
+    L.odk_gait_accumulate.argtypes = [P, P, P, P, P, P, P, P]
     L.odk_batch_get_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_set_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_get_debug.argtypes = [P, FP, FP, FP, FP]
@@ -202,7 +203,7 @@ EXPORTED_SYMBOLS = (
     "odk_model_env_lds_floats", "odk_batch_create",
     "odk_batch_destroy", "odk_batch_set_config", "odk_batch_set_param", "odk_reset", "odk_step", "odk_physics_step",
     "odk_batch_bind_commands", "odk_batch_set_reward_terms", "odk_batch_bind_reward_metrics", "odk_batch_set_imitation_joints", "odk_batch_set_head_joints",
-    "odk_tracking_accumulate", "odk_batch_bind_pushes", "odk_push_accumulate",
+    "odk_tracking_accumulate", "odk_batch_bind_pushes", "odk_push_accumulate", "odk_gait_accumulate",
     "odk_batch_get_state", "odk_batch_set_state", "odk_batch_get_debug", "odk_set_debug_dump", "odk_batch_lds_size",
     "odk_batch_get_lds", "odk_lds_offset", "odk_batch_record_size", "odk_batch_get_records", "odk_batch_set_records", "odk_batch_timing", "odk_gae", "odk_ppo_head",
     "odk_policy_sample", "odk_adam_clip", "odk_silu_bwd_colsum", "odk_colsum_partial", "odk_colsum_finalize", "odk_gather_rows", "odk_dw_gemm",
@@ -237,6 +238,15 @@ PUSH_NACC = 10
  PUSH_PRE_SAMPLES, PUSH_PRE_LIN_ERR_LOW) = range(10)
 
 
+# odk_gait_accumulate's per-env slots (include/odk.h ODK_GAIT_*): scalars, [2] = left / right foot, then per-actuator arrays GAIT_STRIDE apart
+GAIT_NACC = 144
+GAIT_STRIDE = 16
+(GAIT_SAMPLES, GAIT_SPEED_SUM, GAIT_ABS_POWER_SUM, GAIT_CONTACT, GAIT_DOUBLE, GAIT_FLIGHT, GAIT_TOUCHDOWNS, GAIT_SWING_STEPS_SUM, GAIT_SLIP_SUM,
+ GAIT_HEIGHT_SUM, GAIT_HEIGHT_SQ_SUM, GAIT_ROLLPITCH_RATE_SQ_SUM, GAIT_ACTION_RATE_SUM, GAIT_PREV_CONTACT, GAIT_AIR_RUN) = (
+    0, 1, 2, 3, 5, 6, 7, 9, 11, 13, 14, 15, 16, 17, 19)
+GAIT_TORQUE_SQ, GAIT_TORQUE_PEAK, GAIT_VEL_PEAK, GAIT_SAT, GAIT_ABS_POWER, GAIT_RANGE_MIN, GAIT_RANGE_MAX = 32, 48, 64, 80, 96, 112, 128
+
+
 def check_pushes(push, nenv: int, device: int) -> None:
     """What `Batch.bind_pushes` accepts: a contiguous float32 [nenv, >= 2] tensor on cuda:`device`; raises OdkError otherwise."""
     import torch
@@ -253,7 +263,7 @@ def check_pushes(push, nenv: int, device: int) -> None:
 
 
 def check_accumulator(name: str, acc, nenv: int, ncol: int, device: int) -> None:
-    """An accumulator argument of `Batch.push_accumulate`: a contiguous float32 [nenv, ncol] tensor on cuda:`device`; OdkError otherwise."""
+    """An accumulator argument of `Batch.push_accumulate` / `Batch.gait_accumulate`: a contiguous float32 [nenv, ncol] tensor on cuda:`device`; OdkError otherwise."""
     import torch
     if not torch.is_tensor(acc):
         raise OdkError(f"{name}: expected a torch tensor, got {type(acc).__name__}")
@@ -986,6 +996,21 @@ class Batch:
             raise OdkError("push_accumulate: no pushes bound (bind_pushes)")
         _chk(self.L.odk_push_accumulate(self._b, C.c_void_p(self.priv.data_ptr()), C.c_void_p(self.done.data_ptr()),
                                         C.c_void_p(self.truncation.data_ptr()), C.c_void_p(track_acc.data_ptr()), float(lin_tol), float(ang_tol),
+                                        C.c_void_p(acc.data_ptr()), self._stream()))
+
+    def gait_accumulate(self, acc, track_acc, torque_limit=None):
+        """One `odk_gait_accumulate` launch over this step's outputs into `acc` ([nenv, GAIT_NACC] float32, zeroed before the first step),
+        issued after `step` and BEFORE `tracking_accumulate(track_acc)`.  `torque_limit`: float32 [nu] on the batch's device (an entry <= 0:
+        that actuator never counts as saturated) or None (nobody does).  Needs neither bound commands nor bound pushes."""
+        check_accumulator("gait_accumulate: acc", acc, self.nenv, GAIT_NACC, self.device)
+        check_accumulator("gait_accumulate: track_acc", track_acc, self.nenv, TRACK_NACC, self.device)
+        if torque_limit is not None:
+            if not hasattr(torque_limit, "dim") or torque_limit.dim() != 1:
+                raise OdkError(f"gait_accumulate: torque_limit: expected a 1-D torch tensor or None, got {type(torque_limit).__name__}")
+            check_accumulator("gait_accumulate: torque_limit", torque_limit.unsqueeze(0), 1, self.model.nu, self.device)      # as one row of [1, nu]
+        _chk(self.L.odk_gait_accumulate(self._b, C.c_void_p(self.priv.data_ptr()), C.c_void_p(self.done.data_ptr()),
+                                        C.c_void_p(self.truncation.data_ptr()), C.c_void_p(track_acc.data_ptr()),
+                                        C.c_void_p(torque_limit.data_ptr()) if torque_limit is not None else None,
                                         C.c_void_p(acc.data_ptr()), self._stream()))
 
     def physics_step(self, ctrl, n_substeps: int = 10):

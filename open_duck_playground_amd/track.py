@@ -25,6 +25,16 @@ counter, so the run stays one graph replay per step.  `odk_push_accumulate` foll
 row of the report gains "pushes" (per push: fall rate after the push, steps to the fall, recovery time -- the last step at which the
 velocity error exceeded `--push_tolerance` -- and the error peaks) and "max_push_survived" (per direction).  Without push flags the
 report, the graph and the JSON keys are exactly those above.
+
+Gait and actuator load (how does it walk, and what does that cost the motors?):
+
+    python -m open_duck_playground_amd.track --checkpoint <ckpt> --command 0.1 0 0 --gait
+
+`--gait` adds one launch (`odk_gait_accumulate`) to the captured step, before the tracking accumulator; it reads the noise-free privileged
+observation the step wrote and touches nothing else.  Every command row (and, with pushes, every cell too) gains a "gait" object: duty
+factor, double support and flight, step frequency, swing time and foot slip per foot, root height, trunk wobble, action rate, mechanical
+power and cost of transport, and per actuator the torque RMS and peak against its force range, the saturation share, the speed peak, the
+power and the joint range used (`reduce_gait`).  Without `--gait` nothing changes.
 """
 from __future__ import annotations
 
@@ -40,6 +50,12 @@ import numpy as np
 from .engine import (PUSH_NACC, PUSH_PUSHED as P_PUSHED, PUSH_PUSH_AT as P_PUSH_AT, PUSH_FELL as P_FELL, PUSH_STEPS_TO_FALL as P_STEPS_TO_FALL,
                      PUSH_LAST_OFF as P_LAST_OFF, PUSH_PEAK_LIN_ERR as P_PEAK_LIN, PUSH_PEAK_ANG_ERR as P_PEAK_ANG, PUSH_PRE_LIN_ERR_SUM as P_PRE_SUM,
                      PUSH_PRE_SAMPLES as P_PRE_SAMPLES, PUSH_PRE_LIN_ERR_LOW as P_PRE_LOW)      # include/odk.h ODK_PUSH_*: one definition, engine.py's
+
+from .engine import (GAIT_NACC, GAIT_SAMPLES as G_SAMPLES, GAIT_SPEED_SUM as G_SPEED, GAIT_ABS_POWER_SUM as G_POWER, GAIT_CONTACT as G_CONTACT,
+                     GAIT_DOUBLE as G_DOUBLE, GAIT_FLIGHT as G_FLIGHT, GAIT_TOUCHDOWNS as G_TOUCH, GAIT_SWING_STEPS_SUM as G_SWING, GAIT_SLIP_SUM as G_SLIP,
+                     GAIT_HEIGHT_SUM as G_HEIGHT, GAIT_HEIGHT_SQ_SUM as G_HEIGHT_SQ, GAIT_ROLLPITCH_RATE_SQ_SUM as G_WOBBLE,
+                     GAIT_ACTION_RATE_SUM as G_ARATE, GAIT_TORQUE_SQ as G_TORQUE_SQ, GAIT_TORQUE_PEAK as G_TORQUE_PEAK, GAIT_VEL_PEAK as G_VEL_PEAK,
+                     GAIT_SAT as G_SAT, GAIT_ABS_POWER as G_ABS_POWER, GAIT_RANGE_MIN as G_RANGE_MIN, GAIT_RANGE_MAX as G_RANGE_MAX)      # ODK_GAIT_*
 
 COMMAND_KEYS = ("vx", "vy", "wz", "neck_pitch", "head_pitch", "head_yaw", "head_roll")   # the order of cmd_range (include/odk.h)
 NACC = 12
@@ -214,6 +230,81 @@ PUSH_CELL_KEYS = ("push", "magnitude", "direction_deg", "envs", "pushed_envs", "
                   "recovery_steps_p90", "recovery_time_s", "peak_lin_err_mean", "peak_ang_err_mean", "pre_push_lin_err_mean")
 
 
+def torque_limits(model) -> np.ndarray:
+    """[nu] float32: actuator u's torque limit, `actuator_forcerange[u, 1]` where `actuator_forcelimited` is set, 0 for an actuator without a
+    force range (`odk_gait_accumulate` never counts that one as saturated)."""
+    fr = np.asarray(model.a["actuator_forcerange"], np.float64).reshape(-1, 2)
+    on = np.asarray(model.a["actuator_forcelimited"]).reshape(-1) != 0
+    return np.where(on, fr[:, 1], 0.0).astype(np.float32)
+
+
+def nominal_weight(model) -> float:
+    """m * g of the cost of transport: the compiled model's total body mass (not a randomised one) times the norm of its gravity."""
+    return float(np.asarray(model.a["body_mass"], np.float64).sum() * np.linalg.norm(np.asarray(model.a["opt_gravity"], np.float64)))
+
+
+MIN_COT_DISTANCE = 0.01      # metres: below it the cost of transport is a ratio of noise and is reported as None
+
+
+def reduce_gait(acc: np.ndarray, commands: Sequence, envs_per_block: int, dt: float, model) -> List[Dict]:
+    """One "gait" object per block of `envs_per_block` envs (a block per entry of `commands`: the command blocks of `command_blocks`, or the
+    (command, push) cells of `cell_blocks`), from the gait accumulator ([nenv, 144], include/odk.h ODK_GAIT_*), in float64.  Sums are pooled
+    over the block's gait samples (the steps of the envs' first episodes that did not end them); [L, R] = left, right foot:
+    `duty_factor` the share of samples with the foot in contact; `double_support_fraction` / `flight_fraction` with both / no foot in
+    contact; `step_frequency_hz` = touchdowns / (samples * dt); `mean_swing_time_s` = mean non-contact run before a touchdown * dt (None
+    without a touchdown); `foot_slip_mps` the mean planar foot speed over the foot's contact samples (None without one);
+    `root_height_mean` / `root_height_std`; `roll_pitch_rate_rms` = sqrt(mean(gyro_x^2 + gyro_y^2)); `action_rate_mean` = mean over samples
+    of sum_u (last_act - last_last_act)^2; `mean_abs_power_w` = mean over samples of sum_u |force * joint_vel|; `cost_of_transport` =
+    ABS_POWER_SUM / (m g SPEED_SUM) with m the model's nominal total mass and g its gravity (`nominal_weight`), None when the distance
+    SPEED_SUM * dt is under 1 cm; `actuators`: by name, `torque_rms`, `torque_peak` (max over the block), `torque_limit` (`torque_limits`,
+    0 = none), `saturation_fraction` (share of samples at >= 99 % of the limit), `velocity_peak`, `mean_abs_power_w`, `range` [min, max] of
+    the joint angle minus the default pose ([None, None] without a sample).  A block without samples reports 0 for the means."""
+    acc = np.asarray(acc, np.float64).reshape(-1, GAIT_NACC)
+    E, dt = int(envs_per_block), float(dt)
+    nu = int(model.nu)
+    names = [str(n) for n in model.a["names_actuator"]]
+    limit = torque_limits(model).astype(np.float64)
+    weight = nominal_weight(model)
+    pair = lambda blk, s: blk[:, s:s + 2].sum(0)
+    out = []
+    for c, _ in enumerate(commands):
+        blk = acc[c * E:(c + 1) * E]
+        live = blk[:, G_SAMPLES] > 0
+        samples = float(blk[:, G_SAMPLES].sum())
+        den = max(samples, 1.0)
+        contact, touch, swing, slip = pair(blk, G_CONTACT), pair(blk, G_TOUCH), pair(blk, G_SWING), pair(blk, G_SLIP)
+        h_mean = float(blk[:, G_HEIGHT].sum() / den)
+        speed, power = float(blk[:, G_SPEED].sum()), float(blk[:, G_POWER].sum())
+        arr = lambda s: blk[:, s:s + nu]
+        actuators = {}
+        for u in range(nu):
+            actuators[names[u]] = dict(
+                torque_rms=float(np.sqrt(arr(G_TORQUE_SQ)[:, u].sum() / den)), torque_peak=float(arr(G_TORQUE_PEAK)[:, u].max()),
+                torque_limit=float(limit[u]), saturation_fraction=float(arr(G_SAT)[:, u].sum() / den),
+                velocity_peak=float(arr(G_VEL_PEAK)[:, u].max()), mean_abs_power_w=float(arr(G_ABS_POWER)[:, u].sum() / den),
+                range=[float(arr(G_RANGE_MIN)[live, u].min()), float(arr(G_RANGE_MAX)[live, u].max())] if live.any() else [None, None])
+        out.append(dict(
+            samples=int(round(samples)),
+            duty_factor=[float(x / den) for x in contact],
+            double_support_fraction=float(blk[:, G_DOUBLE].sum() / den), flight_fraction=float(blk[:, G_FLIGHT].sum() / den),
+            step_frequency_hz=[float(x / (den * dt)) for x in touch],
+            mean_swing_time_s=[float(s / n * dt) if n > 0 else None for s, n in zip(swing, touch)],
+            foot_slip_mps=[float(s / n) if n > 0 else None for s, n in zip(slip, contact)],
+            root_height_mean=h_mean, root_height_std=float(np.sqrt(max(blk[:, G_HEIGHT_SQ].sum() / den - h_mean * h_mean, 0.0))),
+            roll_pitch_rate_rms=float(np.sqrt(blk[:, G_WOBBLE].sum() / den)),
+            action_rate_mean=float(blk[:, G_ARATE].sum() / den),
+            mean_abs_power_w=power / den,
+            cost_of_transport=power / (weight * speed) if speed * dt >= MIN_COT_DISTANCE else None,
+            actuators=actuators,
+        ))
+    return out
+
+
+GAIT_KEYS = ("samples", "duty_factor", "double_support_fraction", "flight_fraction", "step_frequency_hz", "mean_swing_time_s", "foot_slip_mps",
+             "root_height_mean", "root_height_std", "roll_pitch_rate_rms", "action_rate_mean", "mean_abs_power_w", "cost_of_transport", "actuators")
+GAIT_ACTUATOR_KEYS = ("torque_rms", "torque_peak", "torque_limit", "saturation_fraction", "velocity_peak", "mean_abs_power_w", "range")
+
+
 def reduce_tracking(acc: np.ndarray, commands: Sequence[Sequence[float]], envs_per_command: int) -> List[Dict]:
     """The per-command rows of the report from the accumulator ([nenv, 12], include/odk.h ODK_TRACK_*).  Velocity statistics are over
     the velocity samples of the block's envs (the steps of their first episode that did not end it), pooled; the fall rate is the
@@ -298,9 +389,12 @@ class Tracker:
     """One tracking run on a bound command buffer: `step()` = policy + env step + accumulator, captured as one graph.  With `kicks`
     ([num_envs, 2] device floats, one world-frame kick per env) it is policy + push write + env step + push accumulator + tracking
     accumulator: the Tracker binds a push buffer of its own (`set_pushes`) that holds env e's kick during the step at which the device
-    step counter -- the first-episode step, since first episodes start together at `reset` -- equals `push_at`, and zeros otherwise."""
+    step counter -- the first-episode step, since first episodes start together at `reset` -- equals `push_at`, and zeros otherwise.
+    With `gait=True` it owns a gait accumulator and the model's torque limits on the device, and the step gains `odk_gait_accumulate`,
+    before the tracking accumulator."""
 
-    def __init__(self, env, net, use_graph: bool = True, kicks=None, push_at: int = DEFAULT_PUSH_AT, push_tolerance=DEFAULT_PUSH_TOLERANCE):
+    def __init__(self, env, net, use_graph: bool = True, kicks=None, push_at: int = DEFAULT_PUSH_AT, push_tolerance=DEFAULT_PUSH_TOLERANCE,
+                 gait: bool = False):
         import torch
         self.env, self.net, self.torch = env, net, torch
         b = env.batch
@@ -313,6 +407,10 @@ class Tracker:
             self.push_acc = torch.zeros(env.num_envs, PUSH_NACC, device=b.obs.device)
             self.counter = torch.full((), -1, dtype=torch.int64, device=b.obs.device)
             env.set_pushes(self.push_buf)
+        self.gait_acc = self.torque_limit = None
+        if gait:
+            self.gait_acc = torch.zeros(env.num_envs, GAIT_NACC, device=b.obs.device)
+            self.torque_limit = torch.from_numpy(torque_limits(env.mj_model)).to(b.obs.device)
         from .ppo.learner import fused_policy
         self.fp = fused_policy(net, env.num_envs)
         self.use_graph = use_graph
@@ -332,6 +430,8 @@ class Tracker:
         b.step(act)                                 # Joystick.step without the State wrapper (nothing here reads it)
         if self.kicks is not None:
             b.push_accumulate(self.push_acc, self.acc, *self.push_tolerance)      # before the tracking accumulator sets ENDED
+        if self.gait_acc is not None:
+            b.gait_accumulate(self.gait_acc, self.acc, self.torque_limit)         # likewise
         b.tracking_accumulate(self.acc)
 
     def reset(self, seed: int):
@@ -339,6 +439,8 @@ class Tracker:
         self.acc.zero_()
         if self.kicks is not None:
             self.push_acc.zero_(); self.push_buf.zero_(); self.counter.fill_(-1)
+        if self.gait_acc is not None:
+            self.gait_acc.zero_()
         if self.fp is not None:
             self.fp.refresh()                       # its packed weight copy <- the current parameters
 
@@ -370,6 +472,7 @@ def run(args, out=sys.stdout) -> Dict:
     pushes = [push_row(p) for p in (getattr(args, "push", None) or [])]
     if getattr(args, "push_grid", None):
         pushes += parse_push_grid(args.push_grid)
+    gait = bool(getattr(args, "gait", False))
     E = int(args.envs_per_command)
     n = len(commands) * max(len(pushes), 1) * E
     torch.cuda.set_device(args.device)
@@ -389,11 +492,11 @@ def run(args, out=sys.stdout) -> Dict:
         cmd_np, kicks_np = cell_blocks(commands, pushes, E)
         cmd = torch.from_numpy(cmd_np).to(dev)
         env.set_commands(cmd)
-        tr = Tracker(env, net, kicks=torch.from_numpy(kicks_np).to(dev), push_at=push_at, push_tolerance=tol)
+        tr = Tracker(env, net, kicks=torch.from_numpy(kicks_np).to(dev), push_at=push_at, push_tolerance=tol, gait=gait)
     else:
         cmd = torch.from_numpy(command_blocks(commands, E)).to(dev)
         env.set_commands(cmd)
-        tr = Tracker(env, net)
+        tr = Tracker(env, net, gait=gait)
     nobs = env.observation_size["state"][0]
     T = int(args.episode_length)
     save_obs_path, save_qpos_path = getattr(args, "save_obs", None), getattr(args, "save_qpos", None)
@@ -411,10 +514,18 @@ def run(args, out=sys.stdout) -> Dict:
                 qpos_hist.append(env.batch.get_state()[0][0].copy())
         acc = tr.acc.cpu().numpy()
         push_acc = tr.push_acc.cpu().numpy() if pushes else None
+        gait_acc = tr.gait_acc.cpu().numpy() if gait else None
     rows = reduce_tracking(acc, commands, max(len(pushes), 1) * E)
     if pushes:
         for row, extra in zip(rows, reduce_pushes(push_acc, commands, pushes, E, float(env.dt))):
             row.update(extra)
+    if gait:
+        for row, g in zip(rows, reduce_gait(gait_acc, commands, max(len(pushes), 1) * E, float(env.dt), env.mj_model)):
+            row["gait"] = g
+        if pushes:      # and one per (command, push) cell, in `cell_blocks` order
+            cells = [cell for row in rows for cell in row["pushes"]]
+            for cell, g in zip(cells, reduce_gait(gait_acc, cells, E, float(env.dt), env.mj_model)):
+                cell["gait"] = g
     settings = dict(checkpoint=args.checkpoint, env=args.env, task=args.task, xml=args.xml, cone=args.cone,
                     hfield_up_normals_only=bool(args.hfield_up_normals_only), envs_per_command=E, episode_length=T, seed=int(args.seed),
                     num_envs=n, dt=float(env.dt), policy="deterministic tanh(loc)", fused_policy=tr.fp is not None, graph=tr.graph is not None,
@@ -422,6 +533,8 @@ def run(args, out=sys.stdout) -> Dict:
     if pushes:
         settings.update(push=getattr(args, "push", None), push_grid=getattr(args, "push_grid", None), push_at=push_at,
                         push_tolerance=list(tol), pushes_per_command=len(pushes))
+    if gait:
+        settings.update(gait=True)
     report = make_report(settings, rows)
     if save_obs_path:
         save_obs(save_obs_path, obs_hist.cpu().numpy())
@@ -460,6 +573,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--push_at", type=int, default=DEFAULT_PUSH_AT, help="the step of the first episode (0 = its first) at which the kick is applied, once")
     p.add_argument("--push_tolerance", nargs=2, type=float, default=list(DEFAULT_PUSH_TOLERANCE), metavar=("LIN", "ANG"),
                    help="recovery: planar velocity error (m/s) and yaw-rate error (rad/s) above which a step counts as not recovered (BUILD-DEFINED defaults)")
+    p.add_argument("--gait", action="store_true",
+                   help="add a \"gait\" object to every command row (and push cell): duty factor, double support, flight, step frequency, swing time and "
+                        "foot slip per foot, root height, roll/pitch rate RMS, action rate, mean |torque * joint speed| and per-actuator torque RMS / peak "
+                        "against the force range, saturation share (>= 99 %% of the limit), speed peak, power and joint range.  cost_of_transport = "
+                        "sum |torque * joint speed| / (m g sum of planar speed): m is the model's nominal total mass (not a randomised one), g the model's "
+                        "gravity; null when the distance covered (sum of planar speed * dt) is under 1 cm")
     p.add_argument("--episode_length", type=int, default=1000)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--device", type=int, default=0)
