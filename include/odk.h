@@ -337,7 +337,7 @@ int odk_lds_offset(const odk_batch* b, const char* name);
 /* lanes per env the batch's kernels really run (odk_env_config.lanes_per_env is a hint: elliptic cones, height-field floors and robots that are
  * not the duck exist at 32 lanes per env only) */
 int odk_batch_lanes(const odk_batch* b);
-/* raw per-env info record (floats, layout in csrc/odk_engine.hip) for tests */
+/* raw per-env info record (floats, layout in csrc/odk_shapes.h) for tests */
 int odk_batch_record_size(const odk_batch* b);
 int odk_batch_get_records(odk_batch* b, float* host_records);
 /* writes the records back (synchronous): restores a saved batch, or presets carried `info` fields -- e.g. info["step"] = 500 so

@@ -8,7 +8,7 @@
 // query keeps the second polytope's edges in registers (3 per lane) and walks the first one's, the clipped manifold puts one
 // candidate point per lane, so every arg-max / arg-min is a row-local DPP reduction (no LDS, no readlane).  The two feet of an env
 // are two rows, i.e. they share every instruction.  Geometry sits in LDS that is dead between the inertia and the constraint
-// phases; topology tables (face polygons, unique edges with their two faces) are built at model load (odk_engine.hip).
+// phases; topology tables (face polygons, unique edges with their two faces) are built at model load (odk_model_load.hip).
 #pragma once
 
 namespace odk {
@@ -365,7 +365,7 @@ __device__ __forceinline__ void sat_pair_row(const Cvx& A, const Cvx& B, const f
 
 // ---- height-field prisms: the first polytope's topology is known at compile time and its geometry fits registers
 // vertices 0..2 = top triangle (counter-clockwise seen from above), 3..5 below them at z = -base; faces: top, bottom, the sides over
-// the edges 0-1, 1-2, 2-0 (what build_convex_tables makes of the prism's eight triangles: odk_engine.hip)
+// the edges 0-1, 1-2, 2-0 (what build_convex_tables makes of the prism's eight triangles: odk_model_load.hip)
 struct Prism {
   float x[3], y[3], z[3], base;
   float nt[3];      // top normal

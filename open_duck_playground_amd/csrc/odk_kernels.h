@@ -1,4 +1,4 @@
-// odk_kernels.h -- device code of the fused env step (included by odk_engine.hip only).
+// odk_kernels.h -- device code of the fused env step (odk_engine.hip; the host-only model loader takes Shape and compute_statics from it).
 //
 // Geometry: one workgroup = one wavefront (64 lanes) = 64/G environments, G lanes per env
 // (G = 32 or 64).  Every per-env array lives in LDS for the whole env step; HBM is touched once at
@@ -170,10 +170,10 @@ struct Shape {
   static constexpr int O_WX = O_EQP + N_EQP;         // the contact row wrenches of a robot with fewer than 18 bodies
   static constexpr int O_W = W_FITS ? O_CFRC : O_WX;
   static constexpr int TOTAL = O_WX + (W_FITS ? 0 : 6 * NCROW);
-  // the env logic's floats behind the physics image (odk_engine.hip EnvL): the carried info (43 + 7 NU floats, rec_lay) and this step's action + the
+  // the env logic's floats behind the physics image (odk_shapes.h EnvL): the carried info (43 + 7 NU floats, rec_lay) and this step's action + the
   // imitation phase, both rounded up to whole float4s (the duck: 144 + 16)
   static constexpr int N_INFO = ((43 + 7 * NU + 3) / 4) * 4, N_ACT = ((NU + 2 + 3) / 4) * 4;
-  static constexpr int ENV_STRIDE = TOTAL + N_INFO + N_ACT;   // floats between the images of the two envs of a workgroup (odk_engine.hip EnvL::TOTAL)
+  static constexpr int ENV_STRIDE = TOTAL + N_INFO + N_ACT;   // floats between the images of the two envs of a workgroup (odk_shapes.h EnvL::TOTAL)
 };
 
 // Phase timing (build with -DODK_PROFILE): lane 0 accumulates shader-clock deltas per phase into the
@@ -1026,7 +1026,11 @@ __device__ __noinline__ void foot_foot_sat(float* L, const DevModel* __restrict_
 // registers over the whole loop.  LDS: hull vertices / face normals in the height field's frame in cfrc | crb; per row the prism's
 // vertices + the two polygons of the face contact in BUF6 / BUF6B; per row prism list, running best four, current four in
 // D | aref | jar | jv; at the end the eight contact frames go to jv ([8][9], read by the constraint-row phase).
+#ifdef ODK_HOST_ONLY   // (the model loader: a translation unit without a device image has nothing to register the table with)
+extern const HfAssign ODK_HF_ASSIGN;
+#else
 __constant__ HfAssign ODK_HF_ASSIGN = make_hf_assign();
+#endif
 // index into that table from the four rows' open-entry counts (one byte each), each capped at four
 __host__ __device__ __forceinline__ int hf_assign_index(unsigned n_pk) {
   const unsigned c0 = min(n_pk & 255u, 4u), c1 = min((n_pk >> 8) & 255u, 4u), c2 = min((n_pk >> 16) & 255u, 4u), c3 = min(n_pk >> 24, 4u);

@@ -20,8 +20,8 @@
 #include <type_traits>
 
 #include "../../include/odk.h"
+#include "odk_host.h"
 
-int odk_fail_(int code, const char* msg);   // odk_engine.hip
 int odk_func_lds_attr_(const void* fn, int slot, int bytes);   // odk_mlp.hip
 
 namespace {

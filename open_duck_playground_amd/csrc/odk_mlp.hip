@@ -38,8 +38,7 @@
 #include <string.h>
 
 #include "../../include/odk.h"
-
-int odk_fail_(int code, const char* msg);   // odk_engine.hip
+#include "odk_host.h"
 
 namespace {
 

@@ -31,7 +31,7 @@ constexpr int NSENSD = 46;
 
 // Per-body constants of the kinematics / inertia sweeps, one record per LANE of an env (body-to-lane layout: every serial body
 // chain in consecutive lanes of one 16-lane row, so its scans are DPP row shifts; lanes without a body hold a "no body" record),
-// filled on the host (odk_engine.hip fill_body_st): the kernel fetches a lane's record with ONE address computation and no
+// filled on the host (odk_model_load.hip fill_body_st): the kernel fetches a lane's record with ONE address computation and no
 // dependent loads (as separate tables the joint-derived fields were three dependent loads deep).
 struct BodySt {
   int level, parent, child[4], njnt, jd[2], jj[2], jr[2], pathmask, is_path, upmask, path_head;   // jr: CDOF column of the joint's dof (-1: twin, its main dof's column is the same vector)
@@ -57,7 +57,7 @@ struct LaneSt {
   float d_damping, d_lo, d_hi;           // joint range of the dof's hinge
 };
 
-// One element of an observation layout (DevModel::obs_tab; odk_engine.hip build_obs_table fills it at model load, build_obs gathers through it):
+// One element of an observation layout (DevModel::obs_tab; odk_model_load.hip build_obs_table fills it at model load, build_obs gathers through it):
 // a, b: offsets in the env's LDS image (floats) of the value and of a second one added to it (-1: none); kc: a constant subtracted (0: none);
 // fl: draw slot + 1 in NZ (bits 0-7; 0: no noise) | noise scale (bits 8-12: 0 gyro, 1 accelerometer, 2 joint velocity, 3 + u the joint angle of
 // actuator u) | OBS_FL_VEL: times dof_vel_scale | OBS_FL_PLUS0: a joint angle without a backlash twin (adds +0 where the twin's angle would go).
@@ -105,7 +105,7 @@ struct DevModel {
   // same motion column, cdof_v == cdof_u, so M = P Mr P^T + diag(armature) with P copying each reduced column onto the
   // pair (and likewise the Newton Hessian: contact rows see the pair through the same column, friction-loss / limit rows are
   // diagonal).  All matrix work of the kernels runs on the REDUCED tree (twins merged into their main dof); a model without
-  // twins reduces to itself.  Built at load (odk_engine.hip: build_reduced_tables); kernel side: odk_kernels.h.
+  // twins reduces to itself.  Built at load (odk_model_load.hip: build_reduced_tables); kernel side: odk_kernels.h.
   int paired, nvr, nMr, nHr;
   int dof_tkind[MAXV];       // 0: unpaired, 1: main dof of a pair (its twin is dof + 1), 2: twin
   int dof_red[MAXV];         // reduced dof of this dof (a twin shares its main dof's)
@@ -132,7 +132,7 @@ struct DevModel {
   float fl_D[MAXV], fl_R[MAXV], fl_b[MAXV];             // friction-loss rows: pos = 0 -> constant impedance
   float lim_solref[MAXJ][2], lim_solimp[MAXJ][5], lim_invweight[MAXJ];
   float pair_solref[3][2], pair_solimp[3][5], pair_mu[3], pair_invweight[3];  // pairs: Lfoot-floor, Rfoot-floor, Lfoot-Rfoot
-  // solref / solimp folded into per-row constants at load (odk_engine.hip: pack_imp): k, b, dmin, dmax, 1/width, mid,
+  // solref / solimp folded into per-row constants at load (odk_model_load.hip: pack_imp): k, b, dmin, dmax, 1/width, mid,
   // power, 1/mid^(power-1), 1/(1-mid)^(power-1)
   float lim_imp[MAXJ][9], pair_imp[3][9];
   // feet / floor
@@ -143,7 +143,7 @@ struct DevModel {
   float foot_sphere_r[2];        // |foot_obb_half|: the bounding sphere of the foot-foot cull
   // convex-convex narrow phase (odk_convex.h): face polygons after the coplanar merge (count, then <= 4 vertices counter-clockwise
   // seen from outside), their outward normals in the BODY frame, unique edges (va, vb, face running va -> vb, face running
-  // vb -> va), an interior point; built at load (odk_engine.hip build_convex_tables).
+  // vb -> va), an interior point; built at load (odk_model_load.hip build_convex_tables).
   int foot_npoly[2], foot_nedge[2];
   int foot_poly[2][MAXHF][5];
   float foot_fnorm[2][MAXHF][3];

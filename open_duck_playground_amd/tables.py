@@ -3,7 +3,7 @@
 The kernels map one lane to one body / dof / matrix entry / constraint row; everything that
 would be a pointer chase (`parent[parent[...]]`) is flattened here once, at model-load time,
 into small integer tables that ride in the ModelBlob as `k_*` records (the native loader in
-csrc/odk_engine.hip copies them verbatim).  Layout conventions:
+csrc/odk_model_load.hip copies them verbatim).  Layout conventions:
 
 * Sparse inertia `M` uses MuJoCo's qM layout: row i starts at `Madr[i]` and holds
   M[i, anc_0(i)=i], M[i, anc_1(i)=parent], ... up to the root.
@@ -80,7 +80,7 @@ def _sparse_layout(parent: np.ndarray):
 
 
 def reduced_layout(a: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
-    """Python mirror of csrc/odk_engine.hip build_reduced_tables (twin dofs merged into their main dof): used by the
+    """Python mirror of csrc/odk_model_load.hip build_reduced_tables (twin dofs merged into their main dof): used by the
     parity tests to address the kernels' reduced inertia `M`.  A twin is a hinge declared right after another hinge on
     the same body with the same axis (backlash joints): identical motion column, so the kernels keep one column per
     pair and work on the twin-free tree.  Returns `main`, `twin` (-1: none) per reduced dof and, per entry of the

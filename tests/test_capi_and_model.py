@@ -450,3 +450,81 @@ def test_loader_takes_primitive_feet_on_a_height_field_but_not_beside_a_hull():
     assert a["cgeom_type"][1] == GEOM_MESH
     with pytest.raises(engine.OdkError, match="both feet are hulls"):
         engine.model_reduction(Model(a, prim.xml_path))
+
+
+def _load_rc(blob):
+    """(return code, error string) of odk_model_load on raw bytes; a model that loads is freed again"""
+    from open_duck_playground_amd import engine
+    L = engine.load_library()
+    h = ctypes.c_void_p()
+    rc = L.odk_model_load(blob, len(blob), ctypes.byref(h))
+    err = L.odk_last_error().decode() if rc else ""
+    if rc == 0:
+        L.odk_model_free(h)
+    return rc, err
+
+
+def _record_header(blob, name):
+    """offset of the 64-byte header of record `name` (model.py: name[32] dtype ndim shape[4] nbytes) and its nbytes"""
+    import struct
+    off = 16
+    for _ in range(struct.unpack_from("<I", blob, 8)[0]):
+        nm, nbytes = struct.unpack_from("<32s", blob, off)[0].rstrip(b"\0").decode(), struct.unpack_from("<Q", blob, off + 56)[0]
+        if nm == name:
+            return off, nbytes
+        off += 64 + nbytes + (-nbytes) % 8
+    raise KeyError(name)
+
+
+@pytest.fixture(scope="module")
+def equality_blob():
+    from open_duck_playground_amd.model import Model
+    return Model.from_xml(os.path.join(ROOT, "tests", "assets", "tail_biped_equality.xml")).blob()
+
+
+def test_loader_refuses_blobs_whose_records_leave_the_buffer(equality_blob):
+    """odk_model_load is the library's parser of caller-supplied bytes: a record whose header or payload does not lie inside the `len`
+    bytes given, or whose 2-D shape contradicts its size, is ODK_ERR_INVALID before anything is read through it."""
+    import struct
+    INVALID = -1
+    blob = equality_blob
+    assert _load_rc(blob) == (0, "")
+    off, nbytes = _record_header(blob, "k_dof_anc")                 # a 2-D int table in the middle of the blob
+    assert nbytes > 64
+    for cut in (off + 64 + nbytes // 2, off + 64 + 4, off + 64 + nbytes - 1):        # mid-payload
+        rc, err = _load_rc(blob[:cut])
+        assert rc == INVALID and "past the end" in err, (cut, rc, err)
+    for cut in (off + 8, off + 32, off + 63, 17):                                     # mid-header
+        rc, err = _load_rc(blob[:cut])
+        assert rc == INVALID and "past the end" in err, (cut, rc, err)
+    last_off, last_n = _record_header(blob, list(__import__("open_duck_playground_amd.model", fromlist=["x"]).unpack_blob(blob))[-1])
+    assert _load_rc(blob[:last_off + 64 + last_n - 1])[0] == INVALID                  # the last record, one byte short
+    for huge in (1 << 63, (1 << 64) - 64, (1 << 64) - 1, len(blob)):                  # oversized nbytes (two of them wrap an offset sum)
+        rc, err = _load_rc(blob[:off + 56] + struct.pack("<Q", huge) + blob[off + 64:])
+        assert rc == INVALID and "past the end" in err, (huge, rc, err)
+    rows = struct.unpack_from("<I", blob, off + 40)[0]
+    for shape0 in (2 * rows, rows - 1, 0xFFFFFFFF):                                   # 2-D shape against nbytes
+        rc, err = _load_rc(blob[:off + 40] + struct.pack("<I", shape0) + blob[off + 44:])
+        assert rc == INVALID and "shape disagrees" in err, (shape0, rc, err)
+    rc, err = _load_rc(blob[:off + 36] + struct.pack("<I", 5) + blob[off + 40:])      # ndim 5
+    assert rc == INVALID and "four dimensions" in err, (rc, err)
+
+
+@pytest.mark.parametrize("drop", [("opt_cone",), ("cgeom_size",), ("cgeom_margin",), ("cgeom_contype",), ("cgeom_conaffinity",),
+                                  ("cgeom_contype", "cgeom_conaffinity"), ("k_adr_global_linvel",), ("eq_type",)])
+def test_loader_takes_a_blob_without_an_optional_record(equality_blob, drop):
+    """The optional records and what the loader assumes without them: opt_cone (pyramidal), cgeom_size (0: no primitive collider),
+    cgeom_margin (0), cgeom_contype / cgeom_conaffinity (1: every pair collides), k_adr_global_linvel (-1: no such sensor), eq_type (no
+    equality constraint, whatever other eq_* records say).  A required record that is missing is ODK_ERR_INVALID, by name."""
+    from open_duck_playground_amd import engine
+    from open_duck_playground_amd.model import pack_blob, unpack_blob
+    arrays = unpack_blob(equality_blob)
+    assert all(k in arrays for k in drop)
+    less = {k: v for k, v in arrays.items() if k not in drop}
+    assert _load_rc(pack_blob(less)) == (0, "")
+    class _Raw:      # (model_reduction wants an object with .blob())
+        def __init__(self, a): self.a = a
+        def blob(self): return pack_blob(self.a)
+    assert engine.model_reduction(_Raw(less)) == engine.model_reduction(_Raw(arrays))
+    rc, err = _load_rc(pack_blob({k: v for k, v in less.items() if k != "cgeom_solmix"}))
+    assert rc == -1 and err == "odk_model_load: missing cgeom_solmix"

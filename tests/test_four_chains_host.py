@@ -109,7 +109,7 @@ def test_new_shape_emits_the_chain_count_of_the_compiled_shape():
     line, dims, chains = ns.shape_line(_model("biped_arms.xml"))
     assert chains == [6, 6, 2, 2] and line.endswith(", false, 6, true, 4>;"), line
     args = re.search(r"Shape<([^>]*)>", line).group(1)
-    src = open(os.path.join(ROOT, "open_duck_playground_amd", "csrc", "odk_engine.hip")).read()
+    src = open(os.path.join(ROOT, "open_duck_playground_amd", "csrc", "odk_shapes.h")).read()
     assert f"using ShapeE = Shape<{args}>;" in src and "X(16, ShapeE)" in src
     assert ns.shape_line(_model("biped_arms_between.xml"))[0] == line
     # three chains: the default, not spelled out

@@ -6,10 +6,10 @@
 Compiles the MJCF with the build's compiler (open_duck_playground_amd/mjcf.py), builds the kernels' topology tables (tables.py) and asks
 the loader (`odk_model_load`, host-only: no GPU needed) whether a compiled kernel shape takes the model.
  * yes: prints the shape it matched and the env's sizes -- `python -m open_duck_playground_amd.runner --xml robot.xml` trains it.
- * no compiled shape: prints the TWO lines to add to open_duck_playground_amd/csrc/odk_engine.hip -- the `using ShapeX = Shape<...>` line
+ * no compiled shape: prints the TWO lines to add to open_duck_playground_amd/csrc/odk_shapes.h -- the `using ShapeX = Shape<...>` line
    (model dimensions are template parameters: every loop of the fused step kernel is unrolled over them) and the entry of `ODK_SHAPES`, the
    list every per-shape dispatch of the host code goes through -- then `make -C open_duck_playground_amd/csrc` (~90 s).
- * `--add`: does it for you -- appends the robot's shape to open_duck_playground_amd/csrc/odk_shapes_user.h (which odk_engine.hip includes when it
+ * `--add`: does it for you -- appends the robot's shape to open_duck_playground_amd/csrc/odk_shapes_user.h (which odk_shapes.h includes when it
    exists: `using ShapeU<k> = Shape<...>;` lines + `#define ODK_USER_SHAPES(X) ...`), checks that the kernels' static_asserts take the shape
    (`hipcc -fsyntax-only`, seconds) and rebuilds the library; `--add --no-build` stops before the rebuild.
  * anything else the kernels do not model (a tree that is not a floating base + <= 4 serial chains of <= 6 dofs -- two legs with a foot
@@ -54,7 +54,7 @@ def add_user_shape(line_args: str, header: str = USER_HEADER) -> str:
     if line_args not in shapes:
         shapes.append(line_args)
     with open(header, "w") as f:
-        f.write("// written by tools/new_shape.py --add: robots added without editing odk_engine.hip (which includes this file when it exists)\n#pragma once\n")
+        f.write("// written by tools/new_shape.py --add: robots added without editing odk_shapes.h (which includes this file when it exists)\n#pragma once\n")
         for k, a in enumerate(shapes):
             f.write(f"using ShapeU{k} = Shape<{a}>;\n")
         f.write("#define ODK_USER_SHAPES(X) " + " ".join(f"X({FIRST_USER_INDEX + k}, ShapeU{k})" for k in range(len(shapes))) + "\n")
@@ -95,11 +95,11 @@ def main():
         if "has no compiled kernel" not in msg:
             print(f"  the loader refuses this model: {msg}")
             return 1
-        src = open(os.path.join(ROOT, "open_duck_playground_amd", "csrc", "odk_engine.hip")).read()
+        src = open(os.path.join(ROOT, "open_duck_playground_amd", "csrc", "odk_shapes.h")).read()
         m = re.search(r"#define ODK_SHAPES\(X\) (.*)", src)
         entries = m.group(1).strip() if m else "..."
         n = len(re.findall(r"X\(", entries))
-        print("  no compiled kernel shape takes it.  Add to open_duck_playground_amd/csrc/odk_engine.hip (next to ShapeD):")
+        print("  no compiled kernel shape takes it.  Add to open_duck_playground_amd/csrc/odk_shapes.h (next to ShapeD):")
         print(f"    {line}")
         print("  and extend the list every per-shape dispatch goes through:")
         print(f"    #define ODK_SHAPES(X) {entries} X({n}, ShapeX)")
