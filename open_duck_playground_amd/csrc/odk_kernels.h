@@ -1,4 +1,4 @@
-// odk_kernels.h -- device code of the fused env step (odk_engine.hip; the host-only model loader takes Shape and compute_statics from it).
+// odk_kernels.h -- device code of the fused env step (odk_env_kernels.h; the host-only model loader takes Shape and compute_statics from it).
 //
 // Geometry: one workgroup = one wavefront (64 lanes) = 64/G environments, G lanes per env
 // (G = 32 or 64).  Every per-env array lives in LDS for the whole env step; HBM is touched once at
@@ -85,7 +85,7 @@ struct Shape {
   static constexpr int NMR = PAIRED ? 145 : NM_;   // entries of the reduced tree layout
   static constexpr int NHR = PAIRED ? 170 : NH_;   // entries of the reduced virtual-tree layout
   static constexpr int DVR = PAIRED ? 15 : DV_;    // max dof depth, reduced virtual tree
-  // workgroup-shared LDS tables behind the envs' images (odk_engine.hip load_shared): the packed reduced entries and the
+  // workgroup-shared LDS tables behind the envs' images (odk_env_kernels.h load_shared): the packed reduced entries and the
   // contact-row constants.  (Friction-loss rows, actuator constants and the foot hull were tried there too: no gain, their
   // loads from the L2-resident model are already covered.)
   static constexpr int SH_CT = NMR, SHARED = SH_CT + 42;
@@ -1029,7 +1029,8 @@ __device__ __noinline__ void foot_foot_sat(float* L, const DevModel* __restrict_
 #ifdef ODK_HOST_ONLY   // (the model loader: a translation unit without a device image has nothing to register the table with)
 extern const HfAssign ODK_HF_ASSIGN;
 #else
-__constant__ HfAssign ODK_HF_ASSIGN = make_hf_assign();
+// (inline: several objects of libodk.so include this header, and only those with a height-field kernel -- the one reader -- emit the table)
+inline __constant__ HfAssign ODK_HF_ASSIGN = make_hf_assign();
 #endif
 // index into that table from the four rows' open-entry counts (one byte each), each capped at four
 __host__ __device__ __forceinline__ int hf_assign_index(unsigned n_pk) {

@@ -1,5 +1,5 @@
 // odk_model.h -- device-resident model: constants + static topology tables (tables.py).
-// Replaces mjx.Model (reference base.py:61) for the kernels in odk_engine.hip.
+// Replaces mjx.Model (reference base.py:61) for the kernels in odk_env_kernels.h.
 #pragma once
 #include <stdint.h>
 
@@ -11,7 +11,7 @@ constexpr int MAXV = 32;     // dofs
 constexpr int MAXQ = 32;     // qpos
 constexpr int MAXB = 20;     // bodies
 constexpr int MAXJ = 26;     // joints
-constexpr int MAXU = 16;     // actuators (build_obs in odk_engine.hip picks the joint-angle noise scale in its first pass: 13 + nu <= lanes per env, i.e. nu <= 19 at 32 lanes)
+constexpr int MAXU = 16;     // actuators (build_obs in odk_env_kernels.h picks the joint-angle noise scale in its first pass: 13 + nu <= lanes per env, i.e. nu <= 19 at 32 lanes)
 constexpr int MAXNZ = 512;   // sparse matrix entries
 constexpr int MAXHV = 20;    // hull vertices per foot
 constexpr int MAXHF = 40;    // hull faces per foot

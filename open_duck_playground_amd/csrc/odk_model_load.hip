@@ -1,5 +1,5 @@
 // odk_model_load.hip -- the model side of include/odk.h: ODKM blob -> odk_model (DevModel, shape, height field), the odk_model_* getters and
-// the thread's error string.  Host code only: no kernel, no HIP call (the kernels and the batch API: odk_engine.hip), so it builds without the
+// the thread's error string.  Host code only: no kernel, no HIP call (the kernels: odk_env_kernels.h, the batch API: odk_engine.hip), so it builds without the
 // engine's code-generation switches and, for the CPU, into tools/loader_check.cpp with the sanitizers on.
 //
 // The blob is the library's one caller-supplied byte stream (layout: model.py): Blob checks every record's bounds once, before anything
@@ -855,7 +855,7 @@ int select_shape(Load& c) {
 #undef X
   c.mo.shape = shape;
   if (shape < 0)
-    return fail(ODK_ERR_UNSUPPORTED, "model shape nq=%d nv=%d nb=%d nu=%d nj=%d nM=%d nH=%d nrow=%d depth=%d vdepth=%d has no compiled kernel (tools/new_shape.py <xml> prints the two lines to add to odk_shapes.h)",
+    return fail(ODK_ERR_UNSUPPORTED, "model shape nq=%d nv=%d nb=%d nu=%d nj=%d nM=%d nH=%d nrow=%d depth=%d vdepth=%d has no compiled kernel (tools/new_shape.py <xml> prints the three lines to add to odk_shapes.h)",
                 m.nq, m.nv, m.nb, m.nu, m.nj, m.nM, m.nH, m.nrow, dt_max, dv_max);
   for (int k = 0; k < m.nrchain; k++)
     if (m.rchain_len[k] > shape_cl) return fail(ODK_ERR_UNSUPPORTED, "a serial chain of %d (twin-merged) dofs: the kernels of this model shape solve chains of <= %d", m.rchain_len[k], shape_cl);

@@ -1,6 +1,7 @@
-// odk_shapes.h -- the compiled model shapes and the per-env layouts sized by them, shared by the kernels (odk_engine.hip) and the host-only
-// model loader (odk_model_load.hip): HBM record offsets, observation sizes, the random-draw streams, the env logic's LDS floats, the
-// `using Shape...` lines and ODK_SHAPES, the list every per-shape dispatch goes through.  A new robot's two lines go in HERE.
+// odk_shapes.h -- the compiled model shapes and the per-env layouts sized by them, shared by the env kernels (odk_env_kernels.h), the batch API
+// (odk_engine.hip) and the host-only model loader (odk_model_load.hip): HBM record offsets, observation sizes, the random-draw streams, the env
+// logic's LDS floats, the kernels' arguments, the `using Shape...` lines, ODK_SHAPES, the list every per-shape dispatch goes through, and the
+// kernel sets (ODK_ENV_SET_...), one object per shape.  A new robot's three lines go in HERE.
 #pragma once
 #include "../../include/odk.h"
 #include "odk_kernels.h"
@@ -64,6 +65,46 @@ template <class S> struct EnvL {
   static constexpr int wg_floats(int envs) { return envs * TOTAL + SHARED; }
 };
 
+// ================================================================================================
+// what the host passes to the env kernels
+// Device copy of odk_reward_terms, filled by the host: soft joint limits and the robot's global_linvel sensor address resolved there
+struct XTerms {
+  float scale[ODK_NXTERM];
+  float base_height_target, max_foot_height, air_lo, air_hi;
+  int adr_global_linvel, pad[3];
+  float soft_lo[MAXU], soft_hi[MAXU], pose_w[MAXU];
+};
+
+struct KArgs {
+  const DevModel* m;
+  DevPRM prm;         // by value (232 bytes of kernel arguments): the grid searches read scalar registers, not 20 dependent loads
+  const float* prm_table;
+  float* recs;        // [nenv][Rec::SIZE]
+  float* first;       // [nenv][Rec::FSIZE]
+  const float* dr;    // [nenv][NDR] or null
+  const float* action;  // [nenv][nu]
+  const float* hfield;  // [nrow][ncol] height-field samples in [0, 1], or null (plane floor)
+  float* obs; float* priv; float* reward; float* done; float* trunc; float* metrics;
+  float* dbg_lds;     // [nenv][TOTAL] or null: LDS image after the last forward
+  int nenv;
+  uint32_t seed, env_offset;
+  int n_substeps;
+  EnvCfg cfg;
+  const float* cmd;   // [nenv][cmd_stride] bound commands (odk_batch_bind_commands), or null: sampled ones.  (Last, so that the fields
+  int cmd_stride;     // above keep their argument offsets.)  A uniform pointer test: the unbound path only gains a scalar branch
+  const XTerms* xt;   // reward-library terms (odk_batch_set_reward_terms), null while every term is off: one uniform pointer test
+  float* xmet;        // [nenv][ODK_NXTERM] library metrics (odk_batch_bind_reward_metrics), or null
+  const int* imap;    // [nu] imitation joint map (odk_batch_set_imitation_joints): frame joint of actuator u, -1 = not compared
+  const int* hslot;   // [nu] Standing's head joints (odk_batch_set_head_joints): posture-command slot 0..3 of actuator u, -1 = not a head joint
+  const float* push;  // [nenv][push_stride] bound pushes (odk_batch_bind_pushes): world-frame kick (dvx, dvy) of the next step, or null: the
+  int push_stride;    // sampled push.  A uniform pointer test like cmd's, placed behind every older field
+};
+
+// DR buffer layout per env
+template <class S> struct DRL {
+  static constexpr int MASS = 0, IPOS = S::NB, FRL = S::NB + 3, ARM = FRL + S::NU, Q0 = ARM + S::NU, KP = Q0 + S::NU, SIZE = KP + S::NU;
+};
+
 using ShapeA = Shape<21, 20, 18, 14, 15, 145, 170, 76, 10, 15>;   // flat_terrain
 using ShapeB = Shape<31, 30, 18, 14, 25, 285, 385, 86, 15, 25>;   // *_backlash
 // the same two with the elliptic-cone code compiled in (Shape::ELL): launched for a duck model with <option cone="elliptic"> (plane floor, or
@@ -74,7 +115,7 @@ using ShapeBE = Shape<31, 30, 18, 14, 25, 285, 385, 86, 15, 25, true>;
 // box feet): reset / step / physics kernels -- the env kernels' task logic is joystick.py's with the robot's own tables (rec_lay, obs_nobs: sized
 // by Shape::NU; actuators, default pose, sites and sensor addresses from the ModelBlob), the imitation reward with a joint map of its own (odk_batch_set_imitation_joints), Standing
 // with head joints of its own (odk_batch_set_head_joints).  What adding it
-// took: this line, the dispatch lines below that name it (tools/new_shape.py prints both for an XML), and nothing in odk_kernels.h beyond
+// took: this line, the dispatch lines below that name it (tools/new_shape.py prints them for an XML), and nothing in odk_kernels.h beyond
 // admitting nv = 21 to the chain solver.
 using ShapeC = Shape<22, 21, 19, 15, 16, 156, 181, 78, 10, 15>;
 // A second one (tests/assets/biped12.xml): a biped with SIX-dof legs (hip yaw / roll / pitch, knee, ankle pitch / roll), 18 dofs, 12 actuators,
@@ -86,11 +127,12 @@ using ShapeD = Shape<19, 18, 16, 12, 13, 135, 171, 72, 12, 18, false, 6, true>; 
 // tests/assets/biped_arms_between.xml (the arms declared between the legs).  Env kernels as for ShapeC (16 actions, observations 113 / 230 floats).
 using ShapeE = Shape<23, 22, 20, 16, 17, 165, 201, 80, 11, 17, false, 6, true, 4>;
 // The compiled model shapes, by the index odk_model carries: every per-shape dispatch of the host code below goes through this list, so a
-// new robot is ONE `using` line above and ONE entry here (tools/new_shape.py <xml> prints both).  Entries 0 and 1 are the duck's two models
-// (their cone / height-field / 64-lane instantiations are chosen in launch()); entries from 2 on run reset / step / physics kernels at 32
-// lanes per env on a plane floor.
+// new robot is ONE `using` line above, ONE entry here and ONE kernel set below (tools/new_shape.py <xml> prints all three).  Entries 0 and 1
+// are the duck's two models (their cone / height-field / 64-lane instantiations are chosen in launch()); entries from 2 on run reset / step /
+// physics kernels at 32 lanes per env on a plane floor.
 // Robots added without editing this file: `python tools/new_shape.py robot.xml --add` writes csrc/odk_shapes_user.h -- one `using ShapeU<k> = Shape<...>;`
-// line per robot and `#define ODK_USER_SHAPES(X) X(4, ShapeU0) ...` -- and rebuilds the library.
+// line and one `#define ODK_ENV_SET_U<k>(X) X(ShapeU<k>, 32, 0)` per robot, and `#define ODK_USER_SHAPES(X) X(4, ShapeU0) ...` -- and builds the
+// new set's object.
 #if __has_include("odk_shapes_user.h")
 #include "odk_shapes_user.h"
 #endif
@@ -100,6 +142,28 @@ using ShapeE = Shape<23, 22, 20, 16, 17, 165, 201, 80, 11, 17, false, 6, true, 4
 // Further robots that ship with the library take indices from 16 on, clear of the user shapes (4, 5, ...: tools/new_shape.py --add).
 #define ODK_SHIPPED_SHAPES(X) X(16, ShapeE)
 #define ODK_SHAPES(X) X(0, ShapeA) X(1, ShapeB) X(2, ShapeC) X(3, ShapeD) ODK_SHIPPED_SHAPES(X) ODK_USER_SHAPES(X)
+
+// The kernel sets: one shape each, with all of its instantiations X(shape, lanes per env, HF) -- HF the floor: 0 plane, 1 height field under hull
+// feet, 2 height field under sphere / capsule feet.  Each set is ONE object: odk_env_unit.hip compiled with -DODK_ENV_SET=<name> instantiates
+// launch_sg, and with it the reset / step / debug step / physics kernels, for the set's entries; the Makefile reads the names off these
+// #define lines.  A shape's instantiations stay in one object because their code depends on each other's presence: the floor variants of one
+// (shape, lanes) share out-of-line device functions (foot_foot_sat, prim_contacts, hfield_prim_floor, dump_lds), compiled against the callers
+// the compiler sees next to them, and the 32-lane kernels of the duck's shapes A and B were observed to come out as other instruction streams
+// once their 64-lane kernels were compiled elsewhere (seen for these two shapes, the only ones with two lane counts; the cause was not
+// looked into: profiles/engine_units/NOTES.md).  launch() (odk_engine.hip) chooses among the entries; one it names that no set holds is an
+// undefined symbol when libodk.so links.  A new robot's third line is its set (32 lanes, plane floor); tools/new_shape.py --add writes a user
+// shape's next to its alias.
+#define ODK_ENV_SET_A(X) X(ShapeA, 32, 0) X(ShapeA, 64, 0)
+#define ODK_ENV_SET_B(X) X(ShapeB, 32, 0) X(ShapeB, 32, 1) X(ShapeB, 32, 2) X(ShapeB, 64, 0)
+#define ODK_ENV_SET_AE(X) X(ShapeAE, 32, 0)
+#define ODK_ENV_SET_BE(X) X(ShapeBE, 32, 0) X(ShapeBE, 32, 1)
+#define ODK_ENV_SET_C(X) X(ShapeC, 32, 0)
+#define ODK_ENV_SET_D(X) X(ShapeD, 32, 0)
+#define ODK_ENV_SET_E(X) X(ShapeE, 32, 0)
+
+// launch one instantiation's reset / step / physics kernel (`which`) on a stream: defined in odk_env_kernels.h, instantiated by the sets' objects
+enum { K_RESET = 0, K_STEP = 1, K_PHYS = 2 };
+template <class S, int G, int HF> hipError_t launch_sg(int which, const KArgs& a, hipStream_t st);
 
 // occupancy by construction: 2 waves / SIMD = 8 single-wave workgroups per CU need <= 160 KiB / 8 of LDS per workgroup (2 envs)
 #ifndef ODK_PROFILE   // (the phase-timing build carries 20 extra floats per env and may run 7 workgroups per CU)

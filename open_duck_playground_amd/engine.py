@@ -104,12 +104,18 @@ class OdkError(RuntimeError):
 
 
 def build_library(force: bool = False) -> str:
-    """Compiles csrc/ for gfx950 with hipcc (cross-compiles without a GPU)."""
+    """Compiles csrc/ for gfx950 with hipcc (cross-compiles without a GPU): the objects side by side (MAX_JOBS, else the CPU count; 16 at the
+    most).  force: everything again; otherwise what make's prerequisites say a newer source needs."""
     srcs = [os.path.join(_CSRC, f) for f in sorted(os.listdir(_CSRC)) if f.endswith((".hip", ".h", ".inc")) or f == "Makefile"]
     srcs.append(os.path.join(_CSRC, "..", "..", "include", "odk.h"))
     if not force and os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(s) for s in srcs):
         return LIB_PATH
-    subprocess.check_call(["make", "-C", _CSRC, "-B", "-s", "libodk.so"])
+    try:
+        jobs = int(os.environ.get("MAX_JOBS", ""))
+    except ValueError:       # unset or not a number
+        jobs = os.cpu_count() or 1
+    jobs = max(1, min(16, jobs))
+    subprocess.check_call(["make", "-C", _CSRC, "-s", f"-j{jobs}"] + (["-B"] if force else []) + ["libodk.so"])
     return LIB_PATH
 
 

@@ -460,7 +460,7 @@ def test_step_sequence_with_resync(oracle_mod, parity_log, task):
 @pytest.mark.parametrize("task", ["flat_terrain", "flat_terrain_backlash", "rough_terrain_backlash"])
 def test_step_sequence_of_the_duck_with_elliptic_cones(oracle_mod, parity_log, task):
     """`<option cone="elliptic">` on the duck itself: the model's `opt_cone` switched to 1 (impratio as in the file: 1), the env
-    kernels' own instantiation with the cone code (`ShapeAE` / `ShapeBE`, odk_engine.hip) against the oracle env with the same model: reset, then
+    kernels' own instantiation with the cone code (`ShapeAE` / `ShapeBE`, odk_shapes.h) against the oracle env with the same model: reset, then
     40 env steps with random actions, physics re-synchronised before every step as in the test above, at the same bounds."""
     def edit(cfg):
         cfg.episode_length = 25

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Control flow per region of one kernel of a `-DODK_MARK` listing: branches, if / else pairs (`s_andn2_saveexec` / `s_or_saveexec`: the "else" half of a
 structured if), exec-mask saves, per region between the phase / loop markers.
-    hipcc ... $(ENGINE_FLAGS) -DODK_DEV_HF -DODK_MARK --cuda-device-only -S -o mark.s odk_engine.hip
+    hipcc ... $(ENGINE_FLAGS) -DODK_ENV_SET=B -DODK_MARK --cuda-device-only -S -o mark.s odk_env_unit.hip      (the height-field kernels: ShapeB's set)
     python tools/isa_branch_census.py mark.s [kernel-name substring ...]
 Why: nested `a ? x : (b ? y : z)` chains and `p || (q && r)` conditions can come out of the compiler as basic blocks with exec-mask bookkeeping -- ~40
 instructions and four branches for one five-way select (round 6: two thirds of the rough-terrain kernel's gain was rewriting such lines as one select per

@@ -2,7 +2,7 @@
 """Instruction census of one kernel of an ISA listing, by region and by class (VERDICT r5 #2a: where do the rough-terrain kernel's moves,
 compares, selects and scalar instructions come from?).
 
-    hipcc ... -DODK_MARK --cuda-device-only -S -o mark.s odk_engine.hip
+    hipcc ... -DODK_ENV_SET=B -DODK_MARK --cuda-device-only -S -o mark.s odk_env_unit.hip
     python tools/isa_census.py mark.s [kernel-substring ...]          (default: step_kernel<ShapeB, 32, 1> -- the height-field instantiation)
 
 Regions are cut at the markers the -DODK_MARK build leaves in the listing (`; ODK_PHASE_END n` between the phases of forward_env, `; HF_LOOP_BEGIN /

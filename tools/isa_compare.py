@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Are two builds' instruction streams the same, function by function?
 
-    hipcc ... --cuda-device-only -S -o old.s odk_engine.hip      (before a change; `make -C open_duck_playground_amd/csrc engine.s`)
-    hipcc ... --cuda-device-only -S -o new.s odk_engine.hip      (after)
-    python tools/isa_compare.py old.s new.s [name-filter ...]
+    make -C open_duck_playground_amd/csrc -j8 engine.s      (before a change; keep it as old.s.  engine.s: the listings of every kernel set,
+    make -C open_duck_playground_amd/csrc -j8 engine.s       odk_env_<set>.s, and of odk_engine.hip's accumulator kernels, in one file; one set
+    python tools/isa_compare.py old.s engine.s [name-filter ...]      alone: make odk_env_B.s)
 
 For every function (kernel or out-of-line device function) present in both listings: the instruction lines with comments, labels and
 blank lines dropped and local labels renumbered in order of appearance.  Prints IDENTICAL / the number of differing lines (and, for small

@@ -1,14 +1,14 @@
 """Static per-phase instruction statistics of the fused step kernel (spill hunting):
     python tools/isa_phase_stats.py [A|B]
-Compiles csrc/odk_engine.hip with -DODK_MARK (phase-end comments in the ISA) and counts, between consecutive
+Compiles the shape's kernel set (csrc/odk_env_unit.hip -DODK_ENV_SET=A|B) with -DODK_MARK (phase-end comments in the ISA) and counts, between consecutive
 markers of step_kernel<Shape, 32>, VALU / LDS / scratch (spill) / global instructions."""
 import collections, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 shape = sys.argv[1] if len(sys.argv) > 1 else "A"
 key = "ILi21E" if shape == "A" else "ILi31E"
 out = os.path.join(tempfile.gettempdir(), "odk_mark.s")
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-load-store-vectorizer=0", "-DODK_MARK", *sys.argv[2:], "-S", "--cuda-device-only", "-o", out,
-                       os.path.join(ROOT, "open_duck_playground_amd/csrc/odk_engine.hip")], stderr=subprocess.DEVNULL)
+subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-load-store-vectorizer=0", "-DODK_MARK", f"-DODK_ENV_SET={shape}", *sys.argv[2:], "-S", "--cuda-device-only", "-o", out,
+                       os.path.join(ROOT, "open_duck_playground_amd/csrc/odk_env_unit.hip")], stderr=subprocess.DEVNULL)
 lines = open(out).read().split("\n")
 start = next(i for i, l in enumerate(lines) if l.startswith("_Z11step_kernel") and key in l and "Li32ELi0E" in l)
 end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))

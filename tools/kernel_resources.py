@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Table of every env / physics kernel's registers, scratch and occupancy from the compiler's own remarks:
-    make -C open_duck_playground_amd/csrc resource 2>&1 | python tools/kernel_resources.py > profiles/rN/kernel_resources.txt"""
+    make -C open_duck_playground_amd/csrc resource 2>&1 | python tools/kernel_resources.py > profiles/rN/kernel_resources.txt
+(`resource` compiles every kernel set's object, odk_env_unit.hip once per set, with the remarks on.)"""
 import re
 import sys
 

@@ -6,12 +6,14 @@
 Compiles the MJCF with the build's compiler (open_duck_playground_amd/mjcf.py), builds the kernels' topology tables (tables.py) and asks
 the loader (`odk_model_load`, host-only: no GPU needed) whether a compiled kernel shape takes the model.
  * yes: prints the shape it matched and the env's sizes -- `python -m open_duck_playground_amd.runner --xml robot.xml` trains it.
- * no compiled shape: prints the TWO lines to add to open_duck_playground_amd/csrc/odk_shapes.h -- the `using ShapeX = Shape<...>` line
+ * no compiled shape: prints the lines to add to open_duck_playground_amd/csrc/odk_shapes.h -- the `using ShapeX = Shape<...>` line
    (model dimensions are template parameters: every loop of the fused step kernel is unrolled over them) and the entry of `ODK_SHAPES`, the
-   list every per-shape dispatch of the host code goes through -- then `make -C open_duck_playground_amd/csrc` (~90 s).
+   list every per-shape dispatch of the host code goes through -- and the THIRD, its kernel set (`#define ODK_ENV_SET_X(X) X(ShapeX, 32, 0)`:
+   the robot's kernels, one object of the library); then `make -C open_duck_playground_amd/csrc` compiles that object and the host code.
  * `--add`: does it for you -- appends the robot's shape to open_duck_playground_amd/csrc/odk_shapes_user.h (which odk_shapes.h includes when it
-   exists: `using ShapeU<k> = Shape<...>;` lines + `#define ODK_USER_SHAPES(X) ...`), checks that the kernels' static_asserts take the shape
-   (`hipcc -fsyntax-only`, seconds) and rebuilds the library; `--add --no-build` stops before the rebuild.
+   exists: `using ShapeU<k> = Shape<...>;` and `#define ODK_ENV_SET_U<k>(X) ...` lines + `#define ODK_USER_SHAPES(X) ...`), checks that the
+   kernels' static_asserts take the shape (`hipcc -fsyntax-only` on the set's source) and builds the new set's object, the host objects and
+   the library (the other robots' kernels stay as they are); `--add --no-build` stops before the build.
  * anything else the kernels do not model (a tree that is not a floating base + <= 4 serial chains of <= 6 dofs -- two legs with a foot
    each, the others (arms, head, tail) without colliding geoms --, tendons, more than two foot colliders, ...): the loader's own message, by name.
 What the XML must carry (the names reference constants.py / base.py look up): sites `imu`, `left_foot`, `right_foot`; geoms
@@ -56,18 +58,26 @@ def add_user_shape(line_args: str, header: str = USER_HEADER) -> str:
     with open(header, "w") as f:
         f.write("// written by tools/new_shape.py --add: robots added without editing odk_shapes.h (which includes this file when it exists)\n#pragma once\n")
         for k, a in enumerate(shapes):
-            f.write(f"using ShapeU{k} = Shape<{a}>;\n")
+            f.write(f"using ShapeU{k} = Shape<{a}>;\n#define ODK_ENV_SET_U{k}(X) X(ShapeU{k}, 32, 0)\n")
         f.write("#define ODK_USER_SHAPES(X) " + " ".join(f"X({FIRST_USER_INDEX + k}, ShapeU{k})" for k in range(len(shapes))) + "\n")
     return f"ShapeU{shapes.index(line_args)}"
 
 
-def syntax_check(include_dir: str = None):
-    """do the kernels' static_asserts take every listed shape?  (hipcc -fsyntax-only: template instantiation without code generation, seconds)"""
+def syntax_check(include_dir: str = None, sets=None):
+    """do the kernels' static_asserts take the user shapes?  hipcc -fsyntax-only (template instantiation without code generation) on the kernel
+    sets' source, once per set: `sets` (names as in ODK_ENV_SET_<name>), default every set of the user header (include_dir's, else the tree's)"""
     import subprocess
     csrc = os.path.join(ROOT, "open_duck_playground_amd", "csrc")
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fsyntax-only"] + (["-I", include_dir] if include_dir else []) + [os.path.join(csrc, "odk_engine.hip")]
-    p = subprocess.run(cmd, capture_output=True, text=True)
-    return p.returncode == 0, "\n".join(l for l in p.stderr.splitlines() if "error" in l or "static assertion" in l)[:2000]
+    if sets is None:
+        sets = re.findall(r"#define ODK_ENV_SET_(\w+)\(X\)", open(os.path.join(include_dir, "odk_shapes_user.h") if include_dir else USER_HEADER).read())
+    errs = []
+    for name in sets:
+        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fsyntax-only", f"-DODK_ENV_SET={name}"] + \
+              (["-I", include_dir] if include_dir else []) + [os.path.join(csrc, "odk_env_unit.hip")]
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        if p.returncode != 0:
+            errs += [l for l in p.stderr.splitlines() if "error" in l or "static assertion" in l] or [f"hipcc -fsyntax-only -DODK_ENV_SET={name}: exit status {p.returncode}"]
+    return not errs, "\n".join(errs)[:2000]
 
 
 def main():
@@ -103,17 +113,20 @@ def main():
         print(f"    {line}")
         print("  and extend the list every per-shape dispatch goes through:")
         print(f"    #define ODK_SHAPES(X) {entries} X({n}, ShapeX)")
-        print("  then: make -C open_duck_playground_amd/csrc   (hipcc, ~90 s; a twin-dof (backlash) model must have nv = 30 like the duck's: Shape::PAIRED)")
+        print("  and give it its kernel set (next to ODK_ENV_SET_E):")
+        print("    #define ODK_ENV_SET_X(X) X(ShapeX, 32, 0)")
+        print("  then: make -C open_duck_playground_amd/csrc   (hipcc compiles the new set's object and the host code; a twin-dof (backlash) model must "
+              "have nv = 30 like the duck's: Shape::PAIRED)")
         print("  or let this tool do it: python tools/new_shape.py " + xml + " --add")
         if "--add" in flags:
             alias = add_user_shape(re.search(r"Shape<([^>]*)>", line).group(1))
-            ok, err = syntax_check()
+            ok, err = syntax_check(sets=[alias[len("Shape"):]])
             print(f"  --add: {alias} written to {os.path.relpath(USER_HEADER, ROOT)}; the kernels' static_asserts " + ("take it" if ok else "REFUSE it:\n" + err))
             if not ok:
                 return 1
             if "--no-build" not in flags:
-                print("  rebuilding csrc/libodk.so ...")
-                engine.build_library(force=True)
+                print("  building the new kernel set into csrc/libodk.so ...")
+                engine.build_library()
                 import subprocess      # (a fresh process: this one holds the old library image)
                 return subprocess.call([sys.executable, os.path.abspath(__file__), xml])
         if max(chains or [0]) > 6 or len(chains) > 4:
