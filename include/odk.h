@@ -319,6 +319,50 @@ int odk_gait_accumulate(const odk_batch* b, const float* priv_dev, const float* 
                         const float* track_acc_dev, const float* torque_limit_dev /* [nu] or NULL */, float* acc_dev /* [nenv, ODK_GAIT_NACC] */,
                         void* stream);
 
+/* Posture and stillness accumulator (does the head go where the posture commands send it, how fast does it settle, and does the rest of the
+ * robot keep still meanwhile): one launch per evaluation step, graph-capturable, issued after odk_step and BEFORE odk_tracking_accumulate
+ * (track_acc_dev [nenv, ODK_TRACK_NACC] is that function's accumulator: its ENDED slot then still says whether env e's first episode was
+ * running when this step began).  Independent of odk_push_accumulate and odk_gait_accumulate.  Env e's row of acc_dev
+ * [nenv, ODK_POSTURE_NACC], zeroed by the caller before the first step, is updated only on a sample: a step of e's first episode that is
+ * not done (odk_gait_accumulate's gait sample).  Every other row keeps its bits.  The measured values are the noise-free privileged
+ * observation of this step (priv_dev [nenv, npriv]; nu, nobs, npriv: odk_model_obs_sizes), the same layout in both tasks, offsets from the
+ * start of the env's row:
+ *   gyro nobs (3) | gravity nobs + 6 (3) | local linvel nobs + 9 (3) | joint angles minus the default pose nobs + 15 (nu) |
+ *   joint_vel nobs + 15 + nu (nu) | root_height nobs + 15 + 2 nu (1)
+ * The posture commands are entries 3 + k (k = 0..3: neck_pitch, head_pitch, head_yaw, head_roll) of the env's bound command row, the
+ * default pose is the home keyframe's ctrl, and the actuator of slot k is the batch's head-joint map (odk_batch_set_head_joints; the duck's
+ * shapes start with 5..8).  The head error of slot k, mapped to actuator u, in float32 and in this order:
+ *   angle = P[nobs + 15 + u] + key_ctrl[u];   err = angle - cmd[3 + k]          (the step kernel's jq - cmd, up to the re-added default)
+ * Scalar slots:
+ *   SAMPLES               samples
+ *   DRIFT_SPEED_SUM       sum of hypot(vx, vy) of the local linear velocity
+ *   YAW_RATE_SQ_SUM       sum of gyro_z^2
+ *   ROLLPITCH_RATE_SQ_SUM sum of gyro_x^2 + gyro_y^2
+ *   TILT_SUM, TILT_PEAK   sum and maximum of hypot(g_x, g_y) of the gravity vector: the sine of the lean
+ *   HEIGHT_SUM            sum of root_height
+ *   LEG_POSE_SUM          sum over samples and over the actuators no slot maps to of |joint angle - default|
+ *   LEG_VEL_SUM           likewise of |joint_vel|: the two parts of cost_stand_still(ignore_head=True)
+ *   HEAD_SQERR_SUM        sum over samples and mapped slots of err^2: cost_head_pos without its move-command gate
+ * Both hypots go through float64 (exact squares, a correctly rounded root, one rounding to float32), so a host restatement has TILT_PEAK's bits.
+ * Per-slot arrays, entry k at SLOT + k (k = 0..3; the entries of a slot without an actuator stay 0):
+ *   ANGLE_SUM             signed sum of angle
+ *   ERR_SQ_SUM            sum of err^2
+ *   ERR_PEAK              max |err|
+ *   LAST_OFF              1-based index, among the env's samples, of the latest one with |err| > tol; 0 if none.  The settle time: the
+ *                         episode starts at the home pose, so every run is a step response to the commanded posture
+ * Every sum is float32, added in step order.  done_dev / truncation_dev: [nenv] (a sample does not depend on the truncation flag; the
+ * argument keeps the accumulators' call shape).  ODK_ERR_INVALID, with the cause in odk_last_error and nothing launched: a null pointer
+ * (the message names the argument), no bound commands, a batch without a head-joint map (not a duck shape and odk_batch_set_head_joints
+ * never called; an all -1 map is a map: the head part of the row stays 0 and the stillness part is filled), a model with more than 16
+ * actuators, a tol that is negative or not finite. */
+#define ODK_POSTURE_NACC 32
+enum { ODK_POSTURE_SAMPLES = 0, ODK_POSTURE_DRIFT_SPEED_SUM = 1, ODK_POSTURE_YAW_RATE_SQ_SUM = 2, ODK_POSTURE_ROLLPITCH_RATE_SQ_SUM = 3,
+       ODK_POSTURE_TILT_SUM = 4, ODK_POSTURE_TILT_PEAK = 5, ODK_POSTURE_HEIGHT_SUM = 6, ODK_POSTURE_LEG_POSE_SUM = 7, ODK_POSTURE_LEG_VEL_SUM = 8,
+       ODK_POSTURE_HEAD_SQERR_SUM = 9, ODK_POSTURE_ANGLE_SUM = 16, ODK_POSTURE_ERR_SQ_SUM = 20, ODK_POSTURE_ERR_PEAK = 24,
+       ODK_POSTURE_LAST_OFF = 28 };
+int odk_posture_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
+                           const float* track_acc_dev, float tol, float* acc_dev /* [nenv, ODK_POSTURE_NACC] */, void* stream);
+
 /* mjx_env.step alone (physics only, n_substeps, ctrl = ctrl_dev [nenv, nu]); for parity tests */
 int odk_physics_step(odk_batch* b, const float* ctrl_dev, int n_substeps, void* stream);
 

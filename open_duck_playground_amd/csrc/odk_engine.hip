@@ -1,4 +1,4 @@
-// odk_engine.hip -- the batch C-ABI of include/odk.h (libodk.so) + the accumulator kernels of the tracking / push / gait reports.
+// odk_engine.hip -- the batch C-ABI of include/odk.h (libodk.so) + the accumulator kernels of the tracking / push / gait / posture reports.
 //
 // Host side: device buffers, launches on the caller's stream (blob -> DevModel, odk_model_load and the model getters: odk_model_load.hip).  Device side:
 // the reset / step / physics-only kernels live in odk_env_kernels.h and are compiled one object per kernel set (odk_env_unit.hip); this file
@@ -600,6 +600,85 @@ extern "C" int odk_gait_accumulate(const odk_batch* b, const float* priv_dev, co
   const long long threads = (long long)b->nenv * 16;
   hipLaunchKernelGGL(gait_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, priv_dev, npriv, nobs, nu, done_dev,
                      track_acc_dev, torque_limit_dev, acc_dev, b->nenv);
+  HIPCHK(hipGetLastError());
+  return ODK_OK;
+}
+
+// Posture and stillness sums of one evaluation step, issued between odk_step and odk_tracking_accumulate (the ENDED contract of push_kernel), in
+// gait_kernel's layout: one 16-lane DPP row per env, lane = actuator, four envs per wave.  Every actuator lane loads its posture-command slot
+// (hslot[u], -1: a leg) and its home pose; the per-env scalars are row sums, held one per lane (lanes 0 .. 9), and the lane whose hslot is
+// k >= 0 owns slot k's entries of the four per-slot arrays.  Inputs, offsets into the env's privileged row (both tasks: build_obs_table):
+// gyro nobs | gravity nobs + 6 | local linvel nobs + 9 | joint angle minus default nobs + 15 + u | joint_vel nobs + 15 + nu + u | root height
+// nobs + 15 + 2 nu.  Only a sample (first episode, not done) stores anything, so every other row keeps its bits.
+__device__ __forceinline__ float planar32(float x, float y) {   // hypot through float64: a host restatement has its bits (push_kernel's `lin`)
+  return (float)sqrt((double)x * (double)x + (double)y * (double)y);
+}
+__global__ void __launch_bounds__(256) posture_kernel(const float* __restrict__ priv, int npriv, int nobs, int nu, const float* __restrict__ done,
+                                                      const float* __restrict__ track, const float* __restrict__ cmd, int cmd_stride,
+                                                      const int* __restrict__ hslot, const DevModel* __restrict__ m, float tol,
+                                                      float* __restrict__ acc, int nenv) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int e = t >> 4, u = t & 15;
+  const bool sample = e < nenv && track[(size_t)(e < nenv ? e : 0) * ODK_TRACK_NACC + ODK_TRACK_ENDED] == 0.0f && done[e < nenv ? e : 0] == 0.0f;
+  const bool act = sample && u < nu;
+  const float* P = priv + (size_t)(sample ? e : 0) * npriv;   // row 0 for the rows that only take part in the row sums
+  const float* C = cmd + (size_t)(sample ? e : 0) * cmd_stride;
+  float* A = acc + (size_t)(sample ? e : 0) * ODK_POSTURE_NACC;
+  const float* Q = P + nobs;
+  // per actuator (0 in the lanes past nu and in the rows that are no sample)
+  const int k = act ? hslot[u] : -1;
+  const bool head = k >= 0, leg = act && k < 0;
+  const float dq = act ? Q[15 + u] : 0.0f, v = act ? Q[15 + nu + u] : 0.0f;
+  const float angle = head ? dq + m->key_ctrl[u] : 0.0f;
+  const float err = head ? angle - C[3 + k] : 0.0f, aerr = fabsf(err), sq = err * err;
+  const float leg_pose = row_sum16(leg ? fabsf(dq) : 0.0f), leg_vel = row_sum16(leg ? fabsf(v) : 0.0f), head_sq = row_sum16(sq);
+  if (!sample) return;
+  // per env (the same in the row's 16 lanes)
+  const float n0 = A[ODK_POSTURE_SAMPLES];
+  const float drift = planar32(Q[9], Q[10]), tilt = planar32(Q[6], Q[7]);
+  const float yaw = Q[2] * Q[2], wob = Q[0] * Q[0] + Q[1] * Q[1], h = Q[15 + 2 * nu];
+  if (u < 10) {   // scalar slot u: what it gains, or (the peak) what it becomes
+    const float old = A[u];
+    float inc = 0.0f;
+    inc = u == ODK_POSTURE_SAMPLES ? 1.0f : inc;
+    inc = u == ODK_POSTURE_DRIFT_SPEED_SUM ? drift : inc;
+    inc = u == ODK_POSTURE_YAW_RATE_SQ_SUM ? yaw : inc;
+    inc = u == ODK_POSTURE_ROLLPITCH_RATE_SQ_SUM ? wob : inc;
+    inc = u == ODK_POSTURE_TILT_SUM ? tilt : inc;
+    inc = u == ODK_POSTURE_HEIGHT_SUM ? h : inc;
+    inc = u == ODK_POSTURE_LEG_POSE_SUM ? leg_pose : inc;
+    inc = u == ODK_POSTURE_LEG_VEL_SUM ? leg_vel : inc;
+    inc = u == ODK_POSTURE_HEAD_SQERR_SUM ? head_sq : inc;
+    A[u] = u == ODK_POSTURE_TILT_PEAK ? fmaxf(old, tilt) : old + inc;
+  }
+  if (!head) return;
+  float* B = A + k;
+  B[ODK_POSTURE_ANGLE_SUM] += angle;
+  B[ODK_POSTURE_ERR_SQ_SUM] += sq;
+  B[ODK_POSTURE_ERR_PEAK] = fmaxf(B[ODK_POSTURE_ERR_PEAK], aerr);
+  if (aerr > tol) B[ODK_POSTURE_LAST_OFF] = n0 + 1.0f;   // this sample's 1-based index
+}
+
+extern "C" int odk_posture_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
+                                      const float* track_acc_dev, float tol, float* acc_dev, void* stream) {
+  if (!b) return fail(ODK_ERR_INVALID, "odk_posture_accumulate: null batch");
+  if (!priv_dev) return fail(ODK_ERR_INVALID, "odk_posture_accumulate: null priv_dev");
+  if (!done_dev) return fail(ODK_ERR_INVALID, "odk_posture_accumulate: null done_dev");
+  if (!truncation_dev) return fail(ODK_ERR_INVALID, "odk_posture_accumulate: null truncation_dev");
+  if (!track_acc_dev) return fail(ODK_ERR_INVALID, "odk_posture_accumulate: null track_acc_dev");
+  if (!acc_dev) return fail(ODK_ERR_INVALID, "odk_posture_accumulate: null acc_dev");
+  if (!b->d_cmd) return fail(ODK_ERR_INVALID, "odk_posture_accumulate: no commands bound (odk_batch_bind_commands)");
+  if (!b->hmap_set)
+    return fail(ODK_ERR_INVALID, "odk_posture_accumulate: the batch has no head-joint map (odk_batch_set_head_joints; an all -1 map is a map)");
+  const int nu = b->model.h.nu;
+  if (nu > 16) return fail(ODK_ERR_INVALID, "odk_posture_accumulate: the model has %d actuators, a row holds 16", nu);
+  if (!std::isfinite(tol) || tol < 0.0f) return fail(ODK_ERR_INVALID, "odk_posture_accumulate: tol = %g (a finite tolerance >= 0, in radians)", (double)tol);
+  int nobs, npriv;
+  obs_sizes_nu(nu, b->cfg.env_kind, &nobs, &npriv);
+  HIPCHK(hipSetDevice(b->device));
+  const long long threads = (long long)b->nenv * 16;
+  hipLaunchKernelGGL(posture_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, priv_dev, npriv, nobs, nu, done_dev,
+                     track_acc_dev, b->d_cmd, b->cmd_stride, b->d_hslot, b->d_model, tol, acc_dev, b->nenv);
   HIPCHK(hipGetLastError());
   return ODK_OK;
 }

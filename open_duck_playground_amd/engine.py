@@ -165,6 +165,7 @@ def load_library() -> C.CDLL:
     L.odk_tracking_accumulate.argtypes = [P, P, P, P, P, P, P]
     L.odk_push_accumulate.argtypes = [P, P, P, P, P, C.c_float, C.c_float, P, P]
     L.odk_gait_accumulate.argtypes = [P, P, P, P, P, P, P, P]
+    L.odk_posture_accumulate.argtypes = [P, P, P, P, P, C.c_float, P, P]
     L.odk_batch_get_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_set_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_get_debug.argtypes = [P, FP, FP, FP, FP]
@@ -209,7 +210,7 @@ EXPORTED_SYMBOLS = (
     "odk_model_env_lds_floats", "odk_batch_create",
     "odk_batch_destroy", "odk_batch_set_config", "odk_batch_set_param", "odk_reset", "odk_step", "odk_physics_step",
     "odk_batch_bind_commands", "odk_batch_set_reward_terms", "odk_batch_bind_reward_metrics", "odk_batch_set_imitation_joints", "odk_batch_set_head_joints",
-    "odk_tracking_accumulate", "odk_batch_bind_pushes", "odk_push_accumulate", "odk_gait_accumulate",
+    "odk_tracking_accumulate", "odk_batch_bind_pushes", "odk_push_accumulate", "odk_gait_accumulate", "odk_posture_accumulate",
     "odk_batch_get_state", "odk_batch_set_state", "odk_batch_get_debug", "odk_set_debug_dump", "odk_batch_lds_size",
     "odk_batch_get_lds", "odk_lds_offset", "odk_batch_record_size", "odk_batch_get_records", "odk_batch_set_records", "odk_batch_timing", "odk_gae", "odk_ppo_head",
     "odk_policy_sample", "odk_adam_clip", "odk_silu_bwd_colsum", "odk_colsum_partial", "odk_colsum_finalize", "odk_gather_rows", "odk_dw_gemm",
@@ -253,6 +254,13 @@ GAIT_STRIDE = 16
 GAIT_TORQUE_SQ, GAIT_TORQUE_PEAK, GAIT_VEL_PEAK, GAIT_SAT, GAIT_ABS_POWER, GAIT_RANGE_MIN, GAIT_RANGE_MAX = 32, 48, 64, 80, 96, 112, 128
 
 
+# odk_posture_accumulate's per-env slots (include/odk.h ODK_POSTURE_*): scalars, then per-slot arrays of 4 (neck_pitch, head_pitch, head_yaw, head_roll)
+POSTURE_NACC = 32
+(POSTURE_SAMPLES, POSTURE_DRIFT_SPEED_SUM, POSTURE_YAW_RATE_SQ_SUM, POSTURE_ROLLPITCH_RATE_SQ_SUM, POSTURE_TILT_SUM, POSTURE_TILT_PEAK,
+ POSTURE_HEIGHT_SUM, POSTURE_LEG_POSE_SUM, POSTURE_LEG_VEL_SUM, POSTURE_HEAD_SQERR_SUM) = range(10)
+POSTURE_ANGLE_SUM, POSTURE_ERR_SQ_SUM, POSTURE_ERR_PEAK, POSTURE_LAST_OFF = 16, 20, 24, 28
+
+
 def check_pushes(push, nenv: int, device: int) -> None:
     """What `Batch.bind_pushes` accepts: a contiguous float32 [nenv, >= 2] tensor on cuda:`device`; raises OdkError otherwise."""
     import torch
@@ -269,7 +277,7 @@ def check_pushes(push, nenv: int, device: int) -> None:
 
 
 def check_accumulator(name: str, acc, nenv: int, ncol: int, device: int) -> None:
-    """An accumulator argument of `Batch.push_accumulate` / `Batch.gait_accumulate`: a contiguous float32 [nenv, ncol] tensor on cuda:`device`; OdkError otherwise."""
+    """An accumulator argument of `Batch.push_accumulate` / `Batch.gait_accumulate` / `Batch.posture_accumulate`: a contiguous float32 [nenv, ncol] tensor on cuda:`device`; OdkError otherwise."""
     import torch
     if not torch.is_tensor(acc):
         raise OdkError(f"{name}: expected a torch tensor, got {type(acc).__name__}")
@@ -1018,6 +1026,18 @@ class Batch:
                                         C.c_void_p(self.truncation.data_ptr()), C.c_void_p(track_acc.data_ptr()),
                                         C.c_void_p(torque_limit.data_ptr()) if torque_limit is not None else None,
                                         C.c_void_p(acc.data_ptr()), self._stream()))
+
+    def posture_accumulate(self, acc, track_acc, tol: float):
+        """One `odk_posture_accumulate` launch over this step's outputs into `acc` ([nenv, POSTURE_NACC] float32, zeroed before the first
+        step), issued after `step` and BEFORE `tracking_accumulate(track_acc)`.  `tol`: the head error in radians above which a sample counts
+        as not settled (finite, >= 0).  Needs bound commands and a head-joint map (the duck has one; `set_head_joints` otherwise)."""
+        check_accumulator("posture_accumulate: acc", acc, self.nenv, POSTURE_NACC, self.device)
+        check_accumulator("posture_accumulate: track_acc", track_acc, self.nenv, TRACK_NACC, self.device)
+        if self.commands is None:
+            raise OdkError("posture_accumulate: no commands bound (bind_commands)")
+        _chk(self.L.odk_posture_accumulate(self._b, C.c_void_p(self.priv.data_ptr()), C.c_void_p(self.done.data_ptr()),
+                                           C.c_void_p(self.truncation.data_ptr()), C.c_void_p(track_acc.data_ptr()), float(tol),
+                                           C.c_void_p(acc.data_ptr()), self._stream()))
 
     def physics_step(self, ctrl, n_substeps: int = 10):
         assert ctrl.is_cuda and ctrl.dtype == self.torch.float32 and ctrl.is_contiguous() and tuple(ctrl.shape) == (self.nenv, self.model.nu)

@@ -35,6 +35,19 @@ observation the step wrote and touches nothing else.  Every command row (and, wi
 factor, double support and flight, step frequency, swing time and foot slip per foot, root height, trunk wobble, action rate, mechanical
 power and cost of transport, and per actuator the torque RMS and peak against its force range, the saturation share, the speed peak, the
 power and the joint range used (`reduce_gait`).  Without `--gait` nothing changes.
+
+Posture and stillness (does the head go where the posture commands send it, and does the rest of the robot keep still? -- the Standing
+task's whole purpose, and the four command entries the figures above never read):
+
+    python -m open_duck_playground_amd.track --checkpoint <ckpt> --env standing --grid head_yaw=-1:1:5 --posture
+
+`--posture` adds one launch (`odk_posture_accumulate`) to the captured step, before the tracking accumulator, with gait's contract.  Every
+command row (and, with pushes, every cell too) gains a "posture" object: per mapped head slot the joint, the command, the mean angle, the
+RMS and peak error against the command, the settle time (the last sample whose error exceeded `--posture_tolerance`: the episode starts at
+the home pose, so the run is a step response) and the share of envs that ended inside the tolerance; the mean of cost_head_pos; and under
+"stillness" the planar drift speed, yaw and roll/pitch rate RMS, lean, root height and the two parts of cost_stand_still over the joints
+that are not the head's (`reduce_posture`).  The head-joint map is the env's: the duck's own, or `--env standing --head_joints` for another
+robot.  Without `--posture` nothing changes.
 """
 from __future__ import annotations
 
@@ -56,6 +69,12 @@ from .engine import (GAIT_NACC, GAIT_SAMPLES as G_SAMPLES, GAIT_SPEED_SUM as G_S
                      GAIT_HEIGHT_SUM as G_HEIGHT, GAIT_HEIGHT_SQ_SUM as G_HEIGHT_SQ, GAIT_ROLLPITCH_RATE_SQ_SUM as G_WOBBLE,
                      GAIT_ACTION_RATE_SUM as G_ARATE, GAIT_TORQUE_SQ as G_TORQUE_SQ, GAIT_TORQUE_PEAK as G_TORQUE_PEAK, GAIT_VEL_PEAK as G_VEL_PEAK,
                      GAIT_SAT as G_SAT, GAIT_ABS_POWER as G_ABS_POWER, GAIT_RANGE_MIN as G_RANGE_MIN, GAIT_RANGE_MAX as G_RANGE_MAX)      # ODK_GAIT_*
+
+from .engine import (POSTURE_NACC, POSTURE_SAMPLES as S_SAMPLES, POSTURE_DRIFT_SPEED_SUM as S_DRIFT, POSTURE_YAW_RATE_SQ_SUM as S_YAW,
+                     POSTURE_ROLLPITCH_RATE_SQ_SUM as S_WOBBLE, POSTURE_TILT_SUM as S_TILT, POSTURE_TILT_PEAK as S_TILT_PEAK, POSTURE_HEIGHT_SUM as S_HEIGHT,
+                     POSTURE_LEG_POSE_SUM as S_LEG_POSE, POSTURE_LEG_VEL_SUM as S_LEG_VEL, POSTURE_HEAD_SQERR_SUM as S_HEAD_SQERR,
+                     POSTURE_ANGLE_SUM as S_ANGLE, POSTURE_ERR_SQ_SUM as S_ERR_SQ, POSTURE_ERR_PEAK as S_ERR_PEAK,
+                     POSTURE_LAST_OFF as S_LAST_OFF)      # ODK_POSTURE_*
 
 COMMAND_KEYS = ("vx", "vy", "wz", "neck_pitch", "head_pitch", "head_yaw", "head_roll")   # the order of cmd_range (include/odk.h)
 NACC = 12
@@ -305,6 +324,90 @@ GAIT_KEYS = ("samples", "duty_factor", "double_support_fraction", "flight_fracti
 GAIT_ACTUATOR_KEYS = ("torque_rms", "torque_peak", "torque_limit", "saturation_fraction", "velocity_peak", "mean_abs_power_w", "range")
 
 
+# BUILD-DEFINED default (the reference has no such measure): a head joint counts as settled within 0.1 rad (under 6 degrees) of its command
+DEFAULT_POSTURE_TOLERANCE = 0.1
+HEAD_SLOTS = COMMAND_KEYS[3:]      # constants.HEAD_SLOTS: the posture commands, in the order of the head-joint map
+
+
+def posture_tolerance(text: str) -> float:
+    """`--posture_tolerance RAD`: a finite number >= 0 (what odk_posture_accumulate accepts)."""
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is not a number")
+    if not np.isfinite(v) or v < 0:
+        raise argparse.ArgumentTypeError(f"{text}: a tolerance is a finite angle >= 0, in radians")
+    return v
+
+
+def posture_head_map(env):
+    """(head_map, joint_names) of `reduce_posture` for an env: the head-joint map its batch holds -- the Standing task's `head_joints`, the
+    duck's own actuators 5..8 otherwise -- and, per actuator, the name of the joint it drives.  ValueError for the Joystick task on another
+    robot: that batch has no head-joint map (odk_posture_accumulate would refuse it)."""
+    model = env.mj_model
+    hmap = env.head_joints
+    if hmap is None:
+        from . import constants
+        if not constants.robot_of(model).is_open_duck:
+            raise ValueError("--posture: the joystick env on a robot that is not the duck has no head-joint map; give it one with "
+                             "--env standing --head_joints SLOT=JOINT[,SLOT=JOINT...] (or --head_joints none for the stillness part alone)")
+        hmap = [5, 6, 7, 8]
+    jn = [str(n) for n in model.a["names_jnt"]]
+    trn = [int(j) for j in np.asarray(model.a["actuator_trnid"]).reshape(model.nu, -1)[:, 0]]
+    return [int(u) for u in hmap], [jn[j] for j in trn]
+
+
+def reduce_posture(acc: np.ndarray, commands: Sequence[Sequence[float]], envs_per_block: int, dt: float, head_map: Sequence[int],
+                   joint_names: Sequence[str]) -> List[Dict]:
+    """One "posture" object per block of `envs_per_block` envs (a block per entry of `commands`, whose entries 3..6 are the block's posture
+    commands: the command blocks of `command_blocks`, or the (command, push) cells of `cell_blocks`), from the posture accumulator
+    ([nenv, 32], include/odk.h ODK_POSTURE_*), in float64.  `head_map[k]` is the actuator of head slot k (-1: none), `joint_names[u]` the
+    joint actuator u drives.  Sums are pooled over the block's samples (the steps of the envs' first episodes that did not end them).
+    Per mapped slot, under the slot's name (an unmapped slot is absent): `joint`, `command`, `mean_angle` (the absolute joint angle),
+    `rms_error` and `peak_error` (max over the block) of angle - command; `settle_time_s` = the mean over the envs that settled of LAST_OFF
+    * dt -- the time of the last sample outside the tolerance, 0 for an env that never left it; `settled_fraction` = the share, among the
+    envs with a sample, of those whose LAST_OFF < SAMPLES: the last sample was inside the tolerance.  An env still outside at its last sample
+    has no settle time and is left out of that mean (None when nobody settled).  `head_cost_mean` = mean over samples of the summed squared
+    error (cost_head_pos without its move-command gate).  `stillness`: `drift_speed_mps` mean planar speed, `yaw_rate_rms`,
+    `roll_pitch_rate_rms` = sqrt(mean(gyro_x^2 + gyro_y^2)), `tilt_mean` / `tilt_peak` of the sine of the lean, `root_height_mean`,
+    `leg_pose_deviation_mean` / `leg_joint_speed_mean` = mean over samples of the sum over the joints no slot maps to of |angle - default| /
+    |joint_vel| (the two parts of cost_stand_still(ignore_head=True)).  A block without a sample has nothing to average: every figure is None."""
+    acc = np.asarray(acc, np.float64).reshape(-1, POSTURE_NACC)
+    E, dt = int(envs_per_block), float(dt)
+    out = []
+    for c, cmd in enumerate(commands):
+        blk = acc[c * E:(c + 1) * E]
+        n = blk[:, S_SAMPLES]
+        live = n > 0
+        samples = float(n.sum())
+        mean = lambda s: float(blk[:, s].sum() / samples) if samples > 0 else None
+        rms = lambda s: float(np.sqrt(blk[:, s].sum() / samples)) if samples > 0 else None
+        peak = lambda s: float(blk[live, s].max()) if samples > 0 else None
+        g = dict(samples=int(round(samples)))
+        for k, slot in enumerate(HEAD_SLOTS):
+            u = int(head_map[k])
+            if u < 0:
+                continue
+            off = blk[:, S_LAST_OFF + k]
+            settled = live & (off < n)
+            g[slot] = dict(
+                joint=str(joint_names[u]), command=float(cmd[3 + k]), mean_angle=mean(S_ANGLE + k), rms_error=rms(S_ERR_SQ + k),
+                peak_error=peak(S_ERR_PEAK + k), settle_time_s=float(off[settled].mean() * dt) if settled.any() else None,
+                settled_fraction=float(settled.sum() / live.sum()) if samples > 0 else None)
+        g["head_cost_mean"] = mean(S_HEAD_SQERR)
+        g["stillness"] = dict(
+            drift_speed_mps=mean(S_DRIFT), yaw_rate_rms=rms(S_YAW), roll_pitch_rate_rms=rms(S_WOBBLE), tilt_mean=mean(S_TILT),
+            tilt_peak=peak(S_TILT_PEAK), root_height_mean=mean(S_HEIGHT), leg_pose_deviation_mean=mean(S_LEG_POSE),
+            leg_joint_speed_mean=mean(S_LEG_VEL))
+        out.append(g)
+    return out
+
+
+POSTURE_SLOT_KEYS = ("joint", "command", "mean_angle", "rms_error", "peak_error", "settle_time_s", "settled_fraction")
+STILLNESS_KEYS = ("drift_speed_mps", "yaw_rate_rms", "roll_pitch_rate_rms", "tilt_mean", "tilt_peak", "root_height_mean", "leg_pose_deviation_mean",
+                  "leg_joint_speed_mean")
+
+
 def reduce_tracking(acc: np.ndarray, commands: Sequence[Sequence[float]], envs_per_command: int) -> List[Dict]:
     """The per-command rows of the report from the accumulator ([nenv, 12], include/odk.h ODK_TRACK_*).  Velocity statistics are over
     the velocity samples of the block's envs (the steps of their first episode that did not end it), pooled; the fall rate is the
@@ -391,10 +494,11 @@ class Tracker:
     accumulator: the Tracker binds a push buffer of its own (`set_pushes`) that holds env e's kick during the step at which the device
     step counter -- the first-episode step, since first episodes start together at `reset` -- equals `push_at`, and zeros otherwise.
     With `gait=True` it owns a gait accumulator and the model's torque limits on the device, and the step gains `odk_gait_accumulate`,
-    before the tracking accumulator."""
+    before the tracking accumulator.  With `posture=True` it owns a posture accumulator, and the step gains `odk_posture_accumulate`
+    (head error tolerance `posture_tolerance`, radians), next to gait's launch."""
 
     def __init__(self, env, net, use_graph: bool = True, kicks=None, push_at: int = DEFAULT_PUSH_AT, push_tolerance=DEFAULT_PUSH_TOLERANCE,
-                 gait: bool = False):
+                 gait: bool = False, posture: bool = False, posture_tolerance: float = DEFAULT_POSTURE_TOLERANCE):
         import torch
         self.env, self.net, self.torch = env, net, torch
         b = env.batch
@@ -411,6 +515,9 @@ class Tracker:
         if gait:
             self.gait_acc = torch.zeros(env.num_envs, GAIT_NACC, device=b.obs.device)
             self.torque_limit = torch.from_numpy(torque_limits(env.mj_model)).to(b.obs.device)
+        self.posture_acc, self.posture_tolerance = None, float(posture_tolerance)
+        if posture:
+            self.posture_acc = torch.zeros(env.num_envs, POSTURE_NACC, device=b.obs.device)
         from .ppo.learner import fused_policy
         self.fp = fused_policy(net, env.num_envs)
         self.use_graph = use_graph
@@ -432,6 +539,8 @@ class Tracker:
             b.push_accumulate(self.push_acc, self.acc, *self.push_tolerance)      # before the tracking accumulator sets ENDED
         if self.gait_acc is not None:
             b.gait_accumulate(self.gait_acc, self.acc, self.torque_limit)         # likewise
+        if self.posture_acc is not None:
+            b.posture_accumulate(self.posture_acc, self.acc, self.posture_tolerance)
         b.tracking_accumulate(self.acc)
 
     def reset(self, seed: int):
@@ -441,6 +550,8 @@ class Tracker:
             self.push_acc.zero_(); self.push_buf.zero_(); self.counter.fill_(-1)
         if self.gait_acc is not None:
             self.gait_acc.zero_()
+        if self.posture_acc is not None:
+            self.posture_acc.zero_()
         if self.fp is not None:
             self.fp.refresh()                       # its packed weight copy <- the current parameters
 
@@ -473,6 +584,8 @@ def run(args, out=sys.stdout) -> Dict:
     if getattr(args, "push_grid", None):
         pushes += parse_push_grid(args.push_grid)
     gait = bool(getattr(args, "gait", False))
+    posture = bool(getattr(args, "posture", False))
+    posture_tol = float(getattr(args, "posture_tolerance", DEFAULT_POSTURE_TOLERANCE))
     E = int(args.envs_per_command)
     n = len(commands) * max(len(pushes), 1) * E
     torch.cuda.set_device(args.device)
@@ -483,6 +596,11 @@ def run(args, out=sys.stdout) -> Dict:
         print(motion.describe(), file=sys.stderr)      # stdout may carry the JSON report
     if hasattr(env, "describe_head_joints"):
         print(env.describe_head_joints(), file=sys.stderr)
+    if posture:
+        try:
+            head_map, joint_names = posture_head_map(env)
+        except ValueError as err:
+            raise SystemExit(str(err))
     net = load_networks(args.checkpoint, env, dev)
     if pushes:
         push_at = int(args.push_at)
@@ -492,11 +610,12 @@ def run(args, out=sys.stdout) -> Dict:
         cmd_np, kicks_np = cell_blocks(commands, pushes, E)
         cmd = torch.from_numpy(cmd_np).to(dev)
         env.set_commands(cmd)
-        tr = Tracker(env, net, kicks=torch.from_numpy(kicks_np).to(dev), push_at=push_at, push_tolerance=tol, gait=gait)
+        tr = Tracker(env, net, kicks=torch.from_numpy(kicks_np).to(dev), push_at=push_at, push_tolerance=tol, gait=gait, posture=posture,
+                     posture_tolerance=posture_tol)
     else:
         cmd = torch.from_numpy(command_blocks(commands, E)).to(dev)
         env.set_commands(cmd)
-        tr = Tracker(env, net, gait=gait)
+        tr = Tracker(env, net, gait=gait, posture=posture, posture_tolerance=posture_tol)
     nobs = env.observation_size["state"][0]
     T = int(args.episode_length)
     save_obs_path, save_qpos_path = getattr(args, "save_obs", None), getattr(args, "save_qpos", None)
@@ -515,6 +634,7 @@ def run(args, out=sys.stdout) -> Dict:
         acc = tr.acc.cpu().numpy()
         push_acc = tr.push_acc.cpu().numpy() if pushes else None
         gait_acc = tr.gait_acc.cpu().numpy() if gait else None
+        posture_acc = tr.posture_acc.cpu().numpy() if posture else None
     rows = reduce_tracking(acc, commands, max(len(pushes), 1) * E)
     if pushes:
         for row, extra in zip(rows, reduce_pushes(push_acc, commands, pushes, E, float(env.dt))):
@@ -526,6 +646,14 @@ def run(args, out=sys.stdout) -> Dict:
             cells = [cell for row in rows for cell in row["pushes"]]
             for cell, g in zip(cells, reduce_gait(gait_acc, cells, E, float(env.dt), env.mj_model)):
                 cell["gait"] = g
+    if posture:
+        for row, g in zip(rows, reduce_posture(posture_acc, commands, max(len(pushes), 1) * E, float(env.dt), head_map, joint_names)):
+            row["posture"] = g
+        if pushes:      # and one per (command, push) cell, in `cell_blocks` order
+            cells = [cell for row in rows for cell in row["pushes"]]
+            cell_cmds = [row["command"] for row in rows for _ in row["pushes"]]
+            for cell, g in zip(cells, reduce_posture(posture_acc, cell_cmds, E, float(env.dt), head_map, joint_names)):
+                cell["posture"] = g
     settings = dict(checkpoint=args.checkpoint, env=args.env, task=args.task, xml=args.xml, cone=args.cone,
                     hfield_up_normals_only=bool(args.hfield_up_normals_only), envs_per_command=E, episode_length=T, seed=int(args.seed),
                     num_envs=n, dt=float(env.dt), policy="deterministic tanh(loc)", fused_policy=tr.fp is not None, graph=tr.graph is not None,
@@ -535,6 +663,8 @@ def run(args, out=sys.stdout) -> Dict:
                         push_tolerance=list(tol), pushes_per_command=len(pushes))
     if gait:
         settings.update(gait=True)
+    if posture:
+        settings.update(posture=True, posture_tolerance=posture_tol)
     report = make_report(settings, rows)
     if save_obs_path:
         save_obs(save_obs_path, obs_hist.cpu().numpy())
@@ -579,6 +709,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "against the force range, saturation share (>= 99 %% of the limit), speed peak, power and joint range.  cost_of_transport = "
                         "sum |torque * joint speed| / (m g sum of planar speed): m is the model's nominal total mass (not a randomised one), g the model's "
                         "gravity; null when the distance covered (sum of planar speed * dt) is under 1 cm")
+    p.add_argument("--posture", action="store_true",
+                   help="add a \"posture\" object to every command row (and push cell): per mapped head slot (neck_pitch, head_pitch, head_yaw, head_roll) "
+                        "the joint, the command, mean angle, RMS and peak error, settle time and settled fraction; the mean cost_head_pos; and the "
+                        "robot's stillness (drift speed, yaw and roll/pitch rate RMS, lean, root height, leg pose deviation and leg joint speed).  "
+                        "The head-joint map is the duck's own, or --env standing --head_joints for another robot")
+    p.add_argument("--posture_tolerance", type=posture_tolerance, default=DEFAULT_POSTURE_TOLERANCE, metavar="RAD",
+                   help="settling: the head joint error (rad) above which a step counts as not settled (BUILD-DEFINED default); read by --posture only")
     p.add_argument("--episode_length", type=int, default=1000)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--device", type=int, default=0)

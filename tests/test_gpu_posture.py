@@ -1,0 +1,498 @@
+"""GPU checks of the posture and stillness accumulator (odk_posture_accumulate / Batch.posture_accumulate) and of `track --posture`: every
+slot against a numpy restatement on synthetic privileged rows (four robots: nu 12, 14, 15 and 16; four head-joint maps; a tail wave), rows
+that are no sample keeping their bits, the report of a real run against the same restatement over the recorded outputs, eager against
+graph, with and without pushes and gait, Standing on another robot, and the refusals.
+
+One robot differs from the issue behind these tests.  It names `biped12_neck.xml` (nu 14, its two neck actuators on slots 3 and 0) for the
+fourth synthetic case and for the Standing run on another robot.  That robot has no compiled kernel shape in a plain build -- the loader
+refuses it by name, and a shape enters only through `tools/new_shape.py --add`, a git-ignored header and a rebuild -- so no batch of it can
+be made here (tests/test_gpu_standing_any_robot.py met the same wall).  On compiled shapes stand in: `biped12.xml` (nu 12: one more actuator
+count, four idle lanes) with two actuators on slots 3 and 0 for the synthetic case, and `tail_biped.xml` with its tail as the head for the
+Standing run.  biped12_neck's own map and joint names are resolved on the host in tests/test_posture_host.py."""
+import functools
+import json
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ASSETS = os.path.join(ROOT, "tests", "assets")
+ODK_ERR_INVALID = -1         # include/odk.h
+
+# include/odk.h ODK_POSTURE_*
+SAMPLES, DRIFT_SPEED_SUM, YAW_RATE_SQ_SUM, ROLLPITCH_RATE_SQ_SUM, TILT_SUM, TILT_PEAK, HEIGHT_SUM, LEG_POSE_SUM, LEG_VEL_SUM, HEAD_SQERR_SUM = range(10)
+ANGLE_SUM, ERR_SQ_SUM, ERR_PEAK, LAST_OFF = 16, 20, 24, 28
+NACC = 32
+# float32 running sums of non-negative terms; ANGLE_SUM is the one signed sum; the rest of the row is counts, peaks and LAST_OFF: exact
+SUM_SCALARS = (DRIFT_SPEED_SUM, YAW_RATE_SQ_SUM, ROLLPITCH_RATE_SQ_SUM, TILT_SUM, HEIGHT_SUM, LEG_POSE_SUM, LEG_VEL_SUM, HEAD_SQERR_SUM)
+TOL = 0.1
+
+
+def planar32(x, y):
+    """the kernel's hypot: float64 squares (exact for float32 inputs) and root, one rounding to float32"""
+    x, y = np.float64(x), np.float64(y)
+    return np.float32(np.sqrt(x * x + y * y))
+
+
+def restate(priv, done, ended, cmd, nobs, nu, hmap, kc, tol):
+    """odk_posture_accumulate restated over float32 inputs: priv [T, n, npriv], done [T, n], ended [T, n] (the tracking accumulator's ENDED
+    column as the launch of step t saw it), cmd [n, 7], hmap [4] (actuator per slot, -1: none), kc [nu] float32 home pose.  The head error
+    and its comparison with `tol` are float32, in the kernel's order; the sums are float64.  Returns the [n, 32] accumulator and, per slot,
+    the sum of |angle| (the scale of ANGLE_SUM's bound)."""
+    T, n = done.shape
+    A = np.zeros((n, NACC), np.float64)
+    absang = np.zeros((n, 4), np.float64)
+    tol32 = np.float32(tol)
+    kc = np.asarray(kc, np.float32)
+    cmd = np.asarray(cmd, np.float32)
+    leg = np.array([u not in list(hmap) for u in range(nu)])
+    for e in range(n):
+        R = A[e]
+        for t in range(T):
+            if ended[t, e] != 0 or done[t, e] != 0:
+                continue
+            P32 = priv[t, e]
+            Q = P32[nobs:].astype(np.float64)
+            dq, v = Q[15:15 + nu], Q[15 + nu:15 + 2 * nu]
+            N = R[SAMPLES]
+            R[SAMPLES] += 1
+            R[DRIFT_SPEED_SUM] += planar32(P32[nobs + 9], P32[nobs + 10])
+            R[YAW_RATE_SQ_SUM] += Q[2] * Q[2]
+            R[ROLLPITCH_RATE_SQ_SUM] += Q[0] * Q[0] + Q[1] * Q[1]
+            tilt = planar32(P32[nobs + 6], P32[nobs + 7])
+            R[TILT_SUM] += tilt
+            R[TILT_PEAK] = max(R[TILT_PEAK], float(tilt))
+            R[HEIGHT_SUM] += Q[15 + 2 * nu]
+            R[LEG_POSE_SUM] += np.abs(dq[leg]).sum()
+            R[LEG_VEL_SUM] += np.abs(v[leg]).sum()
+            for k, u in enumerate(hmap):
+                if u < 0:
+                    continue
+                angle = np.float32(P32[nobs + 15 + u] + kc[u])          # float32 + float32: one rounding, as the kernel's
+                err = np.float32(angle - cmd[e, 3 + k])
+                sq = np.float64(err) * np.float64(err)
+                R[ANGLE_SUM + k] += angle
+                absang[e, k] += abs(np.float64(angle))
+                R[ERR_SQ_SUM + k] += sq
+                R[HEAD_SQERR_SUM] += sq
+                R[ERR_PEAK + k] = max(R[ERR_PEAK + k], float(np.abs(err)))
+                if np.abs(err) > tol32:
+                    R[LAST_OFF + k] = N + 1
+    return A, absang
+
+
+def compare(got, want, absang, label):
+    """Counts, peaks and LAST_OFF exact; every float32 running sum of non-negative terms within (N + 4) * 2^-23 relative of the float64 sum,
+    N the env's sample count (the bound derived in tests/test_gpu_gait.py::compare: N sequential float32 additions, 2^-24 each, and terms
+    that carry at most a few roundings of their own -- a product, a root, a 16-lane tree sum: under 4 * 2^-23 together); the signed
+    ANGLE_SUM within (N + 4) * 2^-23 * sum |angle|."""
+    got = got.astype(np.float64)
+    N = want[:, SAMPLES]
+    sum_cols = list(SUM_SCALARS) + [ERR_SQ_SUM + k for k in range(4)]
+    angle_cols = [ANGLE_SUM + k for k in range(4)]
+    exact_cols = [c for c in range(NACC) if c not in sum_cols + angle_cols]
+    bounds = {c: (N + 4) * 2.0 ** -23 * want[:, c] for c in sum_cols}
+    bounds.update({ANGLE_SUM + k: (N + 4) * 2.0 ** -23 * absang[:, k] for k in range(4)})
+    worst = max(float(np.max(np.abs(got[:, c] - want[:, c]) / np.maximum(b, 1e-300))) for c, b in bounds.items())
+    print(f"{label}: float32 sums, worst error / bound {worst:.3f}")
+    for c in exact_cols:
+        np.testing.assert_array_equal(got[:, c], want[:, c], err_msg=f"{label}: slot {c}")
+    for c, b in bounds.items():
+        err = np.abs(got[:, c] - want[:, c])
+        assert np.all(err <= b), (label, c, float(err.max()), float(b[np.argmax(err - b)]))
+
+
+def _robot_env(robot, n):
+    from open_duck_playground_amd import joystick
+    if robot == "duck":
+        return joystick.Joystick(task="flat_terrain", num_envs=n)
+    return joystick.Joystick(xml_path=os.path.join(ASSETS, robot), num_envs=n)
+
+
+# robot, nu, the map given to Batch.set_head_joints (None: the batch's default)
+CASES = {
+    "duck": ("duck", 14, None),                                   # the duck's own 5..8
+    "tail_biped": ("tail_biped.xml", 15, [12, -1, 3, -1]),        # partial and not ascending: a slot-by-actuator mix-up shows
+    "biped_arms": ("biped_arms.xml", 16, [-1, -1, -1, -1]),       # no head: the head part is exactly 0 and every actuator counts as a leg
+    "biped12": ("biped12.xml", 12, [9, -1, -1, 4]),               # two actuators on slots 0 and 3 (biped12_neck's stand-in: the module docstring)
+}
+N_ENVS, T_STEPS = 37, 24
+OFF_UNTIL = 7         # patterns 1 and 2: outside the tolerance over the steps before this one
+
+
+@functools.lru_cache(maxsize=None)
+def synthetic(case):
+    """One run per case, shared by the tests below: 37 envs (two full waves of four rows ... and a tail wave with one live row), 24 steps of
+    seeded random privileged rows and command rows written straight into the batch's buffers -- no odk_step.  First episodes end at step 0,
+    mid-run or never, by done with and without truncation, and the run sets the tracking accumulator's ENDED column as
+    odk_tracking_accumulate would have.  The head error of slot k in env e follows pattern (e + k) % 3: 0 never outside the tolerance; 1
+    outside over the first 7 steps, then inside; 2 like 1 and outside again at the env's last sample.  |err| is below 0.08 inside and in
+    0.15 .. 0.5 outside: at least 0.02 from tol = 0.1, so the float32 comparison cannot tie."""
+    import torch
+    from open_duck_playground_amd import engine
+    robot, nu, given = CASES[case]
+    n, T = N_ENVS, T_STEPS
+    env = _robot_env(robot, n)
+    b = env.batch
+    assert b.model.nu == nu
+    if given is not None:
+        b.set_head_joints(given)
+    hmap = [5, 6, 7, 8] if given is None else list(given)
+    nobs, npriv = b.nobs, b.npriv
+    assert tuple(b.priv.shape) == (n, npriv) and nobs + 16 + 2 * nu <= npriv
+    kc = np.asarray(env.mj_model.a["key_ctrl"], np.float64).reshape(-1)[:nu].astype(np.float32)
+    rng = np.random.default_rng(300 + nu)
+    priv = rng.normal(0.0, 1.0, (T, n, npriv)).astype(np.float32)
+    priv[:, :, nobs + 15 + 2 * nu] = rng.uniform(0.1, 0.2, (T, n)).astype(np.float32)          # a root height is positive
+    cmd = rng.uniform(-1.0, 1.0, (n, 7)).astype(np.float32)
+    # first episodes: never ending; done at step 0 without / with truncation; done mid-run without / with truncation
+    end_at = np.array([(T + 1, 0, 0, 11, 17)[e % 5] for e in range(n)])
+    with_trunc = np.array([e % 5 in (2, 4) for e in range(n)])
+    done = (rng.uniform(size=(T, n)) < 0.1).astype(np.float32)       # stray done flags after the end must not matter ...
+    for e in range(n):
+        done[:min(end_at[e], T), e] = 0.0                            # ... and none before it
+        if end_at[e] < T:
+            done[end_at[e], e] = 1.0
+    trunc = (done * with_trunc[None]).astype(np.float32)
+    ended = (np.arange(T)[:, None] > end_at[None]).astype(np.float32)
+    last_sample = np.minimum(end_at, T) - 1
+    pattern = np.array([[(e + k) % 3 for k in range(4)] for e in range(n)])
+    for k, u in enumerate(hmap):
+        if u < 0:
+            continue
+        for e in range(n):
+            out = np.zeros(T, bool)
+            if pattern[e, k] >= 1:
+                out[:OFF_UNTIL] = True
+            if pattern[e, k] == 2 and last_sample[e] >= 0:
+                out[last_sample[e]] = True
+            mag = np.where(out, rng.uniform(0.15, 0.5, T), rng.uniform(0.0, 0.08, T)) * rng.choice([-1.0, 1.0], T)
+            target = (cmd[e, 3 + k] + mag.astype(np.float32)).astype(np.float32)
+            priv[:, e, nobs + 15 + u] = (target - kc[u]).astype(np.float32)
+    want, absang = restate(priv, done, ended, cmd, nobs, nu, hmap, kc, TOL)
+
+    guard = torch.full((n + 3, NACC), 7.0, device="cuda")            # rows past the batch: the tail wave's idle rows must not touch them
+    acc = guard[:n]
+    acc.zero_()
+    tacc = torch.zeros(n, engine.TRACK_NACC, device="cuda")
+    b.bind_commands(torch.tensor(cmd, device="cuda"))
+    priv_d, done_d, trunc_d, ended_d = (torch.tensor(x, device="cuda") for x in (priv, done, trunc, ended))
+    snaps = []
+    for t in range(T):
+        b.priv.copy_(priv_d[t]); b.done.copy_(done_d[t]); b.truncation.copy_(trunc_d[t])
+        tacc[:, engine.TRACK_ENDED] = ended_d[t]
+        b.posture_accumulate(acc, tacc, TOL)
+        snaps.append(acc.clone())
+    torch.cuda.synchronize()
+    res = dict(got=acc.cpu().numpy(), want=want, absang=absang, guard=guard[n:].cpu().numpy(), snaps=torch.stack(snaps).cpu().numpy(), hmap=hmap,
+               end_at=end_at, pattern=pattern, nu=nu)
+    b.bind_commands(None)
+    b.close()
+    return res
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_every_slot_matches_a_numpy_restatement_on_synthetic_rows(case):
+    r = synthetic(case)
+    got, want, hmap, pattern = r["got"], r["want"], r["hmap"], r["pattern"]
+    compare(got, want, r["absang"], f"{case} nu={r['nu']}")
+    np.testing.assert_array_equal(r["guard"], 7.0)
+    # the run covers what it claims to
+    N = want[:, SAMPLES]
+    assert set(N.astype(int)) == {0, 11, 17, T_STEPS}
+    assert np.all(got[N == 0] == 0.0)
+    assert np.all(got[:, 10:16] == 0.0)                                # no slot lives there
+    live = N > 0
+    for k, u in enumerate(hmap):
+        cols = [s + k for s in (ANGLE_SUM, ERR_SQ_SUM, ERR_PEAK, LAST_OFF)]
+        if u < 0:
+            assert np.all(got[:, cols] == 0.0)                         # an unmapped slot stays 0
+            continue
+        off = got[:, LAST_OFF + k]
+        for p, expect in ((0, np.zeros_like(N)), (1, np.full_like(N, OFF_UNTIL)), (2, N)):
+            sel = live & (pattern[:, k] == p)
+            assert sel.any(), (k, p)
+            np.testing.assert_array_equal(off[sel], expect[sel], err_msg=f"slot {k} pattern {p}")
+        assert np.all(got[live & (pattern[:, k] == 0), ERR_PEAK + k] < TOL) and np.all(got[live & (pattern[:, k] != 0), ERR_PEAK + k] > TOL)
+    if all(u < 0 for u in hmap):
+        assert np.all(got[:, HEAD_SQERR_SUM] == 0.0) and np.all(got[:, ANGLE_SUM:] == 0.0)
+    else:
+        assert np.all(got[live, HEAD_SQERR_SUM] > 0.0)
+    assert np.all(got[live, LEG_POSE_SUM] > 0.0) and np.all(got[live, LEG_VEL_SUM] > 0.0) and np.all(got[live, TILT_PEAK] > 0.0)
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_a_row_that_is_no_sample_keeps_its_bits(case):
+    """Rows of envs past their first episode (and of the done step that ends it): what step end_at - 1 left is what every later step leaves."""
+    r = synthetic(case)
+    snaps, end_at = r["snaps"].view(np.int32), r["end_at"]
+    checked = 0
+    for e in range(N_ENVS):
+        if end_at[e] >= T_STEPS:
+            continue
+        frozen = snaps[end_at[e] - 1, e] if end_at[e] > 0 else np.zeros(NACC, np.int32)
+        for t in range(end_at[e], T_STEPS):
+            np.testing.assert_array_equal(snaps[t, e], frozen, err_msg=f"env {e} step {t}")
+            checked += 1
+    assert checked > 100
+    # while a live row changes at every step
+    e = int(np.argmax(end_at > T_STEPS))
+    assert all(snaps[t, e, SAMPLES] != snaps[t - 1, e, SAMPLES] for t in range(1, T_STEPS))
+
+
+ENV_SIZES = {"joystick": (101, 212, 14), "standing": (85, 153, 14)}      # the duck's observation / privileged / action sizes
+
+
+def _checkpoint(tmp_path, sizes, name="fresh.pt"):
+    import torch
+    from open_duck_playground_amd.ppo.networks import PPONetworks
+    from open_duck_playground_amd.ppo.train import save_checkpoint
+    torch.manual_seed(0)
+    ckpt = str(tmp_path / name)
+    save_checkpoint(ckpt, PPONetworks(*sizes))
+    return ckpt
+
+
+def _run(track, monkeypatch, argv, eager=False):
+    """track.run with its Tracker caught; eager: no graph, and per step the ENDED column the step's launches saw and the step's outputs.
+    Returns (report, tracker, recording)."""
+    real = track.Tracker
+    caught, hist = [], []
+
+    class Caught(real):
+        def __init__(self, *a, **k):
+            if eager:
+                k["use_graph"] = False
+            super().__init__(*a, **k)
+            caught.append(self)
+
+        def step(self):
+            ended = self.acc[:, 0].cpu().numpy() if eager else None      # ODK_TRACK_ENDED, before this step's tracking launch sets it
+            super().step()
+            if eager:
+                bb = self.env.batch
+                hist.append((bb.priv.cpu().numpy(), bb.done.cpu().numpy(), ended))
+
+    monkeypatch.setattr(track, "Tracker", Caught)
+    try:
+        rep = track.run(track.build_parser().parse_args(argv))
+    finally:
+        monkeypatch.setattr(track, "Tracker", real)
+    assert len(caught) == 1
+    return rep, caught[0], hist
+
+
+def _flatten(g):
+    flat = {}
+    for k, v in g.items():
+        if isinstance(v, dict):
+            flat.update({f"{k}.{kk}": vv for kk, vv in v.items()})
+        else:
+            flat[k] = v
+    return flat
+
+
+EXACT_FIELDS = ("samples", "joint", "command", "peak_error", "settle_time_s", "settled_fraction", "tilt_peak")
+
+
+@pytest.mark.parametrize("env_name", ["joystick", "standing"])
+def test_track_posture_end_to_end(tmp_path, monkeypatch, env_name):
+    """A randomly initialised policy on the duck, two commands, 8 envs each, 40 steps.  The eager run's recording, pushed through the numpy
+    restatement and `reduce_posture`, reproduces the accumulator (the bounds of the synthetic test) and the report; the graph run's posture
+    and tracking accumulators have the eager run's bits; without --posture the tracking accumulator has the same bits and the report its
+    old keys."""
+    from open_duck_playground_amd import engine, track
+    ckpt = _checkpoint(tmp_path, ENV_SIZES[env_name])
+    E, T, tol = 8, 40, 0.15
+    out = tmp_path / "report.json"
+    argv = ["--checkpoint", ckpt, "--env", env_name, "--command", "0", "0", "0", "0.3", "0.2", "-0.5", "0.1", "--command", "0.05", "0", "0", "-0.2", "0", "0.8",
+            "0", "--envs_per_command", str(E), "--episode_length", str(T), "--seed", "1", "--output", str(out)]
+    on = ["--posture", "--posture_tolerance", str(tol)]
+    rep_e, tr_e, hist = _run(track, monkeypatch, argv + on, eager=True)
+    assert not rep_e["settings"]["graph"] and rep_e["settings"]["posture"] is True and rep_e["settings"]["posture_tolerance"] == tol and len(hist) == T
+    priv, done, ended = (np.stack([h[i] for h in hist]) for i in range(3))
+    np.testing.assert_array_equal(ended, np.concatenate([np.zeros((1, 2 * E)), (np.cumsum(done != 0, 0) > 0)[:-1]]))
+    model = tr_e.env.mj_model
+    nobs = tr_e.env.batch.nobs
+    hmap, joints = track.posture_head_map(tr_e.env)
+    assert hmap == [5, 6, 7, 8]
+    kc = np.asarray(model.a["key_ctrl"], np.float64).reshape(-1)[:14].astype(np.float32)
+    cmd = track.command_blocks([r["command"] for r in rep_e["commands"]], E)
+    want, absang = restate(priv, done, ended, cmd, nobs, 14, hmap, kc, tol)
+    got_e = tr_e.posture_acc.cpu().numpy()
+    compare(got_e, want, absang, f"track --posture --env {env_name}, eager")
+    track_e = tr_e.acc.cpu().numpy()
+    np.testing.assert_array_equal(got_e[:, SAMPLES], track_e[:, engine.TRACK_SAMPLES])     # a posture sample is a velocity sample
+    assert got_e[:, SAMPLES].sum() > 0
+
+    # the report is reduce_posture of that accumulator; against the restatement the exact slots give equal figures and every mean is a ratio
+    # of two sums (or its root): twice the sum bound -- for the signed mean_angle at the scale of the mean |angle|
+    rel = 2 * (T + 4) * 2.0 ** -23
+    ref = track.reduce_posture(want, [r["command"] for r in rep_e["commands"]], E, rep_e["settings"]["dt"], hmap, joints)
+    for c, (row, w) in enumerate(zip(rep_e["commands"], ref)):
+        assert tuple(row) == track.ROW_KEYS + ("posture",)
+        g = row["posture"]
+        assert tuple(g) == ("samples",) + track.HEAD_SLOTS + ("head_cost_mean", "stillness") and g["samples"] == w["samples"] > 0
+        assert tuple(g["stillness"]) == track.STILLNESS_KEYS
+        assert [g[s]["joint"] for s in track.HEAD_SLOTS] == list(track.HEAD_SLOTS) and [g[s]["command"] for s in track.HEAD_SLOTS] == row["command"][3:]
+        flat_g, flat_w = _flatten(g), _flatten(w)
+        assert list(flat_g) == list(flat_w)
+        blk = slice(c * E, (c + 1) * E)
+        for key in flat_g:
+            field = key.split(".")[-1]
+            if field in EXACT_FIELDS or flat_w[key] is None:
+                assert flat_g[key] == flat_w[key], (key, flat_g[key], flat_w[key])
+            elif field == "mean_angle":
+                k = track.HEAD_SLOTS.index(key.split(".")[0])
+                assert abs(flat_g[key] - flat_w[key]) <= rel * absang[blk, k].sum() / w["samples"], (key, flat_g[key], flat_w[key])
+            else:
+                assert flat_g[key] == pytest.approx(flat_w[key], rel=rel, abs=0), (key, flat_g[key], flat_w[key])
+    assert json.load(open(out)) == json.loads(json.dumps(rep_e))
+
+    # the graph: one more launch in the captured step, the same bits
+    rep_g, tr_g, _ = _run(track, monkeypatch, argv + on)
+    assert rep_g["settings"]["graph"]
+    np.testing.assert_array_equal(tr_g.posture_acc.cpu().numpy().view(np.int32), got_e.view(np.int32))
+    np.testing.assert_array_equal(tr_g.acc.cpu().numpy().view(np.int32), track_e.view(np.int32))
+    assert [r["posture"] for r in rep_g["commands"]] == [r["posture"] for r in rep_e["commands"]]
+
+    # without --posture (its tolerance alone is inert): no accumulator, no launch, the old report, the same tracking bits
+    calls = []
+    real = engine.Batch.posture_accumulate
+    monkeypatch.setattr(engine.Batch, "posture_accumulate", lambda self, *a, **k: (calls.append(1), real(self, *a, **k))[1])
+    rep_p, tr_p, _ = _run(track, monkeypatch, argv + ["--posture_tolerance", "0.3"])
+    assert calls == [] and tr_p.posture_acc is None
+    np.testing.assert_array_equal(tr_p.acc.cpu().numpy().view(np.int32), track_e.view(np.int32))
+    assert tuple(rep_p) == track.REPORT_KEYS and "posture" not in rep_p["settings"] and "posture_tolerance" not in rep_p["settings"]
+    assert all(tuple(r) == track.ROW_KEYS for r in rep_p["commands"])
+    assert [k for k in rep_g["settings"] if k not in rep_p["settings"]] == ["posture", "posture_tolerance"]
+    for a, bb in zip(rep_p["commands"], rep_g["commands"]):
+        assert a == {k: v for k, v in bb.items() if k != "posture"}
+
+
+def test_track_posture_with_a_push_grid_and_gait(tmp_path, monkeypatch):
+    """One command, a push grid of two magnitudes, 4 envs per cell, --gait: every cell and the command row get a "posture" object, the cells'
+    samples add up to the row's, and the push, gait and tracking accumulators have the bits of a run without --posture."""
+    from open_duck_playground_amd import track
+    ckpt = _checkpoint(tmp_path, ENV_SIZES["joystick"])
+    argv = ["--checkpoint", ckpt, "--command", "0.1", "0", "0", "0.2", "0", "0.4", "0", "--push_grid", "magnitude=0:1.5:2", "--push_at", "10",
+            "--envs_per_command", "4", "--episode_length", "40", "--seed", "2", "--gait", "--output", str(tmp_path / "r.json")]
+    rep_s, tr_s, _ = _run(track, monkeypatch, argv + ["--posture"])
+    rep_p, tr_p, _ = _run(track, monkeypatch, argv)
+    assert rep_s["settings"]["posture"] is True and rep_s["settings"]["posture_tolerance"] == track.DEFAULT_POSTURE_TOLERANCE
+    assert "posture" not in rep_p["settings"]
+    (row,), (plain,) = rep_s["commands"], rep_p["commands"]
+    assert tuple(row) == track.ROW_KEYS + track.PUSH_ROW_KEYS + ("gait", "posture") and tuple(plain) == track.ROW_KEYS + track.PUSH_ROW_KEYS + ("gait",)
+    assert len(row["pushes"]) == 2
+    for cell, old in zip(row["pushes"], plain["pushes"]):
+        assert tuple(cell) == track.PUSH_CELL_KEYS + ("gait", "posture")
+        assert {k: v for k, v in cell.items() if k != "posture"} == old
+        assert cell["posture"]["head_yaw"]["command"] == 0.4 and cell["posture"]["neck_pitch"]["command"] == 0.2
+    assert sum(c["posture"]["samples"] for c in row["pushes"]) == row["posture"]["samples"] == row["velocity_samples"] > 0
+    for name in ("push_acc", "gait_acc", "acc"):
+        np.testing.assert_array_equal(getattr(tr_s, name).cpu().numpy().view(np.int32), getattr(tr_p, name).cpu().numpy().view(np.int32), err_msg=name)
+    assert tuple(tr_s.posture_acc.shape) == (8, NACC) and tr_p.posture_acc is None
+
+
+def test_track_posture_standing_on_another_robot(tmp_path, monkeypatch):
+    """`--env standing --xml <robot> --head_joints ...` (tail_biped's tail as the head: the module docstring): the report's slots and joints
+    are the map's, the unmapped slots are absent and their accumulator entries 0.  The Joystick task on that robot has no map: --posture
+    says so and points to Standing's flag."""
+    from open_duck_playground_amd import track
+    xml = os.path.join(ASSETS, "tail_biped.xml")
+    ckpt = _checkpoint(tmp_path, (90, 161, 15))                      # Standing's sizes at nu = 15
+    argv = ["--checkpoint", ckpt, "--env", "standing", "--xml", xml, "--head_joints", "neck_pitch=tail_pitch_1,head_roll=tail_roll", "--command", "0", "0", "0",
+            "0.3", "0", "0", "-0.2", "--envs_per_command", "8", "--episode_length", "20", "--seed", "3", "--output", str(tmp_path / "r.json"), "--posture"]
+    rep, tr, _ = _run(track, monkeypatch, argv)
+    assert tr.env.head_joints == [6, -1, -1, 9]
+    (row,) = rep["commands"]
+    g = row["posture"]
+    assert tuple(g) == ("samples", "neck_pitch", "head_roll", "head_cost_mean", "stillness")
+    assert g["neck_pitch"]["joint"] == "tail_pitch_1" and g["head_roll"]["joint"] == "tail_roll"
+    assert g["neck_pitch"]["command"] == pytest.approx(0.3) and g["head_roll"]["command"] == pytest.approx(-0.2)
+    assert g["samples"] == row["velocity_samples"] > 0 and g["stillness"]["root_height_mean"] > 0
+    acc = tr.posture_acc.cpu().numpy()
+    for s in (ANGLE_SUM, ERR_SQ_SUM, ERR_PEAK, LAST_OFF):
+        assert np.all(acc[:, [s + 1, s + 2]] == 0.0)
+    assert np.all(acc[acc[:, SAMPLES] > 0][:, [ERR_SQ_SUM, ERR_SQ_SUM + 3]] > 0.0)
+    with pytest.raises(SystemExit, match="no head-joint map.*--env standing --head_joints"):
+        track.run(track.build_parser().parse_args(["--checkpoint", ckpt, "--xml", xml, "--command", "0", "0", "0", "--envs_per_command", "8",
+                                                   "--episode_length", "5", "--posture"]))
+
+
+def test_refusals_launch_nothing():
+    import ctypes as C
+    import torch
+    from open_duck_playground_amd import engine, joystick
+    n = 16
+    L = engine.load_library()
+    env = joystick.Joystick(task="flat_terrain", num_envs=n)
+    b = env.batch
+    env.reset(1)
+    b.step(torch.zeros(n, 14, device="cuda"))
+    acc = torch.zeros(n, engine.POSTURE_NACC, device="cuda")
+    tacc = torch.zeros(n, engine.TRACK_NACC, device="cuda")
+    good = dict(priv_dev=b.priv.data_ptr(), done_dev=b.done.data_ptr(), truncation_dev=b.truncation.data_ptr(), track_acc_dev=tacc.data_ptr(),
+                acc_dev=acc.data_ptr())
+
+    def raw(batch, tol=0.1, null=None):
+        a = {k: (None if k == null else C.c_void_p(v)) for k, v in good.items()}
+        rc = L.odk_posture_accumulate(batch, a["priv_dev"], a["done_dev"], a["truncation_dev"], a["track_acc_dev"], C.c_float(tol), a["acc_dev"], b._stream())
+        return rc, L.odk_last_error().decode()
+
+    # no commands bound: the C call and the Python surface
+    assert b.commands is None
+    rc, msg = raw(b._b)
+    assert rc == ODK_ERR_INVALID and "odk_posture_accumulate" in msg and "no commands bound" in msg, msg
+    with pytest.raises(engine.OdkError, match="posture_accumulate: no commands bound"):
+        b.posture_accumulate(acc, tacc, 0.1)
+    b.bind_commands(torch.zeros(n, 7, device="cuda"))
+    # each null pointer, by name
+    for null in ("acc_dev", "priv_dev", "done_dev", "truncation_dev", "track_acc_dev"):
+        rc, msg = raw(b._b, null=null)
+        assert rc == ODK_ERR_INVALID and "odk_posture_accumulate" in msg and null in msg, (null, msg)
+    rc, msg = raw(None)
+    assert rc == ODK_ERR_INVALID and "batch" in msg
+    # a tolerance that is negative or not finite
+    for tol in (-0.1, float("nan"), float("inf")):
+        rc, msg = raw(b._b, tol=tol)
+        assert rc == ODK_ERR_INVALID and "tol" in msg, (tol, msg)
+        with pytest.raises(engine.OdkError, match="tol"):
+            b.posture_accumulate(acc, tacc, tol)
+    # bad tensors are OdkErrors before anything is launched
+    bad = [(torch.zeros(n, engine.POSTURE_NACC - 1, device="cuda"), tacc), (torch.zeros(n, engine.POSTURE_NACC), tacc), (acc.double(), tacc),
+           (acc, torch.zeros(n, engine.TRACK_NACC + 1, device="cuda")), (acc, tacc.cpu())]
+    for args in bad:
+        with pytest.raises(engine.OdkError, match="posture_accumulate"):
+            b.posture_accumulate(*args, 0.1)
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(acc.cpu().numpy(), 0.0)
+    # ... and the good call counts
+    b.posture_accumulate(acc, tacc, 0.0)
+    torch.cuda.synchronize()
+    assert float(acc[:, engine.POSTURE_SAMPLES].sum()) > 0.0
+    b.bind_commands(None)
+    b.close()
+
+    # a Joystick batch of a robot that is not the duck has no head-joint map until it is given one; an all -1 map is a map
+    other = joystick.Joystick(xml_path=os.path.join(ASSETS, "tail_biped.xml"), num_envs=n)
+    ob = other.batch
+    other.reset(1)
+    ob.step(torch.zeros(n, 15, device="cuda"))
+    ob.bind_commands(torch.zeros(n, 7, device="cuda"))
+    acc.zero_()
+    with pytest.raises(engine.OdkError, match="odk_posture_accumulate.*no head-joint map.*odk_batch_set_head_joints"):
+        ob.posture_accumulate(acc, tacc, 0.1)
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(acc.cpu().numpy(), 0.0)
+    ob.set_head_joints([-1] * 4)
+    ob.posture_accumulate(acc, tacc, 0.1)
+    torch.cuda.synchronize()
+    got = acc.cpu().numpy()
+    assert got[:, SAMPLES].sum() > 0 and np.all(got[:, HEAD_SQERR_SUM] == 0.0) and np.all(got[:, ANGLE_SUM:] == 0.0)
+    assert np.all(got[got[:, SAMPLES] > 0, HEIGHT_SUM] > 0.0)
+    ob.bind_commands(None)
+    ob.close()
