@@ -363,6 +363,64 @@ enum { ODK_POSTURE_SAMPLES = 0, ODK_POSTURE_DRIFT_SPEED_SUM = 1, ODK_POSTURE_YAW
 int odk_posture_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
                            const float* track_acc_dev, float tol, float* acc_dev /* [nenv, ODK_POSTURE_NACC] */, void* stream);
 
+/* Imitation-fidelity accumulator (does the policy walk the reference gait: which joints follow the reference motion, are the feet down when
+ * the reference's are, does the robot touch down early or late in the cycle): one launch per evaluation step, graph-capturable, issued
+ * after odk_step and BEFORE odk_tracking_accumulate (track_acc_dev [nenv, ODK_TRACK_NACC] is that function's accumulator: its ENDED slot then
+ * still says whether env e's first episode was running when this step began).  Independent of odk_push_accumulate, odk_gait_accumulate and
+ * odk_posture_accumulate; needs neither bound commands nor bound pushes.  Env e's row of acc_dev [nenv, ODK_IMIT_NACC], zeroed by the caller
+ * before the first step, is updated only on a sample: a step of e's first episode that is not done (odk_gait_accumulate's gait sample).
+ * Every other row keeps its bits.  All inputs are this step's privileged observation of the Joystick task (priv_dev [nenv, npriv]; nu,
+ * nobs, npriv: odk_model_obs_sizes), offsets from the start of the env's row:
+ *   command 6 (3) | local linvel nobs + 9 (3) | joint angles minus the default pose nobs + 15 (nu) | joint_vel nobs + 15 + nu (nu) |
+ *   contact nobs + 16 + 3 nu (2: left, right) | F = current_reference_motion nobs + 26 + 3 nu (40)
+ * F is the canonical frame the step's reward read: F[j], F[16 + j] position and velocity of frame joint j, F[32 + f] foot f's reference
+ * contact, F[34 .. 36] the linear velocity.  Actuator u is compared with frame joint ri = imap[u], the batch's device copy of
+ * odk_batch_set_imitation_joints read when the launch runs (a graph captured earlier follows a later map; -1: not compared), in float32 and
+ * in this order, as the step kernel and odk_posture_accumulate do it (key_ctrl: the home keyframe's ctrl):
+ *   jq = P[nobs + 15 + u] + key_ctrl[u];   dp = jq - F[ri];   dv = P[nobs + 15 + nu + u] - F[16 + ri]
+ * Per foot f: c = contact[f] != 0, r = F[32 + f] > 0.5f.  Scalar slots ([2]: left foot, right foot):
+ *   SAMPLES               samples
+ *   GATED                 samples with sqrtf(c0 c0 + c1 c1 + c2 c2) > 0.01f of the command: the samples the imitation reward pays
+ *   SPEED_ERR_SQ_SUM      sum of (s - sr)^2, s = hypot of the local linvel's x, y and sr = hypot(F[34], F[35]), both through float64
+ *   REF_SPEED_SUM         sum of sr
+ *   JOINT_POS_SQ_SUM      sum over samples and compared actuators of dp^2: the reward's joint_pos term before its weight 15
+ *   JOINT_VEL_SQ_SUM      likewise of dv^2 (weight 1e-3)
+ *   BOTH[2]               samples with c && r
+ *   ROBOT_ONLY[2]         samples with c && !r
+ *   REF_ONLY[2]           samples with !c && r  (the rest, neither, is SAMPLES minus the three)
+ *   REF_TOUCHDOWNS[2]     samples with r whose previous sample had !r; the env's first sample counts none (odk_gait_accumulate's rule)
+ *   TOUCHDOWNS[2]         robot touchdowns (c, and !c at the previous sample) while REF_AGE[f] > 0: those that have a lag
+ *   LAG_SUM[2]            sum of lag over those touchdowns
+ *   LAG_ABS_SUM[2]        sum of |lag|
+ *   PREV_CONTACT[2], PREV_REF[2], REF_AGE[2]   bookkeeping: c and r of the previous sample; samples since the reference's latest touchdown
+ * REF_AGE[f] is 0 until the reference's first counted touchdown, which sets it to 1; every later sample adds 1, and a later reference
+ * touchdown sets it to 1 again.  Within a sample the reference is updated first, then lag = REF_AGE[f] - 1, and if period_steps > 0 and
+ * 2 lag > period_steps, lag -= period_steps: negative means the robot touched down before the reference's NEXT touchdown.  Lags are small
+ * integers in float32: LAG_SUM and LAG_ABS_SUM are exact.
+ * Per-actuator arrays, entry u at SLOT + u, ODK_IMIT_STRIDE = 16 apart (entries of actuators with imap[u] < 0 and entries nu .. 15 stay 0):
+ *   POS_ERR_SUM           signed sum of dp: the bias
+ *   POS_ERR_SQ            sum of dp^2
+ *   POS_ERR_PEAK          max |dp|
+ *   VEL_ERR_SQ            sum of dv^2
+ *   RANGE_MIN, RANGE_MAX  of jq; the env's first sample initialises both
+ *   REF_RANGE_MIN, REF_RANGE_MAX   of F[ri]; the env's first sample initialises both
+ * Every sum is float32, added in step order.  done_dev / truncation_dev: [nenv] (a sample does not depend on the truncation flag; the
+ * argument keeps the accumulators' call shape).  period_steps: the reference motion's nb_steps_in_period, or 0 for lags that are not folded.
+ * The reward's four base-velocity terms read world-frame qvel, which the privileged row does not carry: they are not measured here.
+ * ODK_ERR_INVALID, with the cause in odk_last_error and nothing launched: a null pointer (the message names the argument), a Standing batch
+ * (its privileged row has no frame), cfg.use_imitation == 0 (the frame is all zeros), a batch without an imitation joint map (not a duck
+ * shape and odk_batch_set_imitation_joints never called), a model with more than ODK_IMIT_STRIDE actuators, period_steps < 0. */
+#define ODK_IMIT_NACC 160
+#define ODK_IMIT_STRIDE 16
+enum { ODK_IMIT_SAMPLES = 0, ODK_IMIT_GATED = 1, ODK_IMIT_SPEED_ERR_SQ_SUM = 2, ODK_IMIT_REF_SPEED_SUM = 3, ODK_IMIT_JOINT_POS_SQ_SUM = 4,
+       ODK_IMIT_JOINT_VEL_SQ_SUM = 5, ODK_IMIT_BOTH = 6, ODK_IMIT_ROBOT_ONLY = 8, ODK_IMIT_REF_ONLY = 10, ODK_IMIT_REF_TOUCHDOWNS = 12,
+       ODK_IMIT_TOUCHDOWNS = 14, ODK_IMIT_LAG_SUM = 16, ODK_IMIT_LAG_ABS_SUM = 18, ODK_IMIT_PREV_CONTACT = 20, ODK_IMIT_PREV_REF = 22,
+       ODK_IMIT_REF_AGE = 24,
+       ODK_IMIT_POS_ERR_SUM = 32, ODK_IMIT_POS_ERR_SQ = 48, ODK_IMIT_POS_ERR_PEAK = 64, ODK_IMIT_VEL_ERR_SQ = 80, ODK_IMIT_RANGE_MIN = 96,
+       ODK_IMIT_RANGE_MAX = 112, ODK_IMIT_REF_RANGE_MIN = 128, ODK_IMIT_REF_RANGE_MAX = 144 };
+int odk_imitation_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
+                             const float* track_acc_dev, int period_steps, float* acc_dev /* [nenv, ODK_IMIT_NACC] */, void* stream);
+
 /* mjx_env.step alone (physics only, n_substeps, ctrl = ctrl_dev [nenv, nu]); for parity tests */
 int odk_physics_step(odk_batch* b, const float* ctrl_dev, int n_substeps, void* stream);
 

@@ -1,4 +1,4 @@
-// odk_engine.hip -- the batch C-ABI of include/odk.h (libodk.so) + the accumulator kernels of the tracking / push / gait / posture reports.
+// odk_engine.hip -- the batch C-ABI of include/odk.h (libodk.so) + the accumulator kernels of the tracking / push / gait / posture / imitation reports.
 //
 // Host side: device buffers, launches on the caller's stream (blob -> DevModel, odk_model_load and the model getters: odk_model_load.hip).  Device side:
 // the reset / step / physics-only kernels live in odk_env_kernels.h and are compiled one object per kernel set (odk_env_unit.hip); this file
@@ -679,6 +679,121 @@ extern "C" int odk_posture_accumulate(const odk_batch* b, const float* priv_dev,
   const long long threads = (long long)b->nenv * 16;
   hipLaunchKernelGGL(posture_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, priv_dev, npriv, nobs, nu, done_dev,
                      track_acc_dev, b->d_cmd, b->cmd_stride, b->d_hslot, b->d_model, tol, acc_dev, b->nenv);
+  HIPCHK(hipGetLastError());
+  return ODK_OK;
+}
+
+// Imitation-fidelity sums of one evaluation step, issued between odk_step and odk_tracking_accumulate (the ENDED contract of push_kernel), in
+// gait_kernel's layout: one 16-lane DPP row per env, lane = actuator, four envs per wave.  Every actuator lane loads its frame joint through
+// the batch's imitation map (imap[u], -1: not compared) and its home pose; the two reward terms are row sums, the 32 scalar slots are held two
+// per lane (u and 16 + u) as gait's, and a compared lane owns entry u of the eight per-actuator arrays.  Inputs, offsets into the env's
+// privileged Joystick row (build_obs_table): command 6 | local linvel nobs + 9 | joint angle minus default nobs + 15 + u | joint_vel nobs + 15
+// + nu + u | contact nobs + 16 + 3 nu | the frame the reward read (O_REF) nobs + 26 + 3 nu.  Only a sample (first episode, not done) stores
+// anything, so every other row keeps its bits.
+__global__ void __launch_bounds__(256) imitation_kernel(const float* __restrict__ priv, int npriv, int nobs, int nu, const float* __restrict__ done,
+                                                        const float* __restrict__ track, const int* __restrict__ imap,
+                                                        const DevModel* __restrict__ m, int period, float* __restrict__ acc, int nenv) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int e = t >> 4, u = t & 15;
+  const bool sample = e < nenv && track[(size_t)(e < nenv ? e : 0) * ODK_TRACK_NACC + ODK_TRACK_ENDED] == 0.0f && done[e < nenv ? e : 0] == 0.0f;
+  const bool act = sample && u < nu;
+  const float* P = priv + (size_t)(sample ? e : 0) * npriv;   // row 0 for the rows that only take part in the row sums
+  float* A = acc + (size_t)(sample ? e : 0) * ODK_IMIT_NACC;
+  const float* Q = P + nobs;
+  const float* F = Q + 26 + 3 * nu;
+  // per actuator (0 in the lanes past nu, in the lanes the map leaves out and in the rows that are no sample)
+  const int ri = act ? imap[u] : -1;
+  const bool cmp = ri >= 0;
+  const float jq = cmp ? Q[15 + u] + m->key_ctrl[u] : 0.0f, rq = cmp ? F[ri] : 0.0f;
+  const float dp = jq - rq, dv = cmp ? Q[15 + nu + u] - F[16 + ri] : 0.0f;
+  const float sp = dp * dp, sv = dv * dv;
+  const float jpos = row_sum16(sp), jvel = row_sum16(sv);
+  if (!sample) return;
+  // per env (the same in the row's 16 lanes)
+  const bool first = A[ODK_IMIT_SAMPLES] == 0.0f;
+  const float gated = sqrtf(P[6] * P[6] + P[7] * P[7] + P[8] * P[8]) > 0.01f ? 1.0f : 0.0f;   // the reward's gate (step_kernel's cn)
+  const float sr = planar32(F[34], F[35]), ds = planar32(Q[9], Q[10]) - sr;
+  const float per = (float)period;
+  float c[2], r[2], both[2], ronly[2], fonly[2], rtd[2], td[2], lag[2], age[2];
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    const bool con = Q[16 + 3 * nu + k] != 0.0f, ref = F[32 + k] > 0.5f;
+    const bool rtouch = ref && !first && A[ODK_IMIT_PREV_REF + k] == 0.0f;
+    const float a0 = A[ODK_IMIT_REF_AGE + k];
+    const float a1 = rtouch ? 1.0f : (a0 > 0.0f ? a0 + 1.0f : 0.0f);   // the reference first: a touchdown in the same sample has lag 0
+    const bool touch = con && !first && A[ODK_IMIT_PREV_CONTACT + k] == 0.0f && a1 > 0.0f;
+    float l = a1 - 1.0f;
+    if (period > 0 && 2.0f * l > per) l -= per;                        // past half a period: early for the reference's next touchdown
+    c[k] = con ? 1.0f : 0.0f;
+    r[k] = ref ? 1.0f : 0.0f;
+    both[k] = (con && ref) ? 1.0f : 0.0f;
+    ronly[k] = (con && !ref) ? 1.0f : 0.0f;
+    fonly[k] = (!con && ref) ? 1.0f : 0.0f;
+    rtd[k] = rtouch ? 1.0f : 0.0f;
+    td[k] = touch ? 1.0f : 0.0f;
+    lag[k] = touch ? l : 0.0f;
+    age[k] = a1;
+  }
+  // scalar slot s: what it gains, or (bookkeeping) what it becomes
+  auto next = [&](int s, float old) {
+    float inc = 0.0f;
+    inc = s == ODK_IMIT_SAMPLES ? 1.0f : inc;
+    inc = s == ODK_IMIT_GATED ? gated : inc;
+    inc = s == ODK_IMIT_SPEED_ERR_SQ_SUM ? ds * ds : inc;
+    inc = s == ODK_IMIT_REF_SPEED_SUM ? sr : inc;
+    inc = s == ODK_IMIT_JOINT_POS_SQ_SUM ? jpos : inc;
+    inc = s == ODK_IMIT_JOINT_VEL_SQ_SUM ? jvel : inc;
+    inc = s == ODK_IMIT_BOTH ? both[0] : s == ODK_IMIT_BOTH + 1 ? both[1] : inc;
+    inc = s == ODK_IMIT_ROBOT_ONLY ? ronly[0] : s == ODK_IMIT_ROBOT_ONLY + 1 ? ronly[1] : inc;
+    inc = s == ODK_IMIT_REF_ONLY ? fonly[0] : s == ODK_IMIT_REF_ONLY + 1 ? fonly[1] : inc;
+    inc = s == ODK_IMIT_REF_TOUCHDOWNS ? rtd[0] : s == ODK_IMIT_REF_TOUCHDOWNS + 1 ? rtd[1] : inc;
+    inc = s == ODK_IMIT_TOUCHDOWNS ? td[0] : s == ODK_IMIT_TOUCHDOWNS + 1 ? td[1] : inc;
+    inc = s == ODK_IMIT_LAG_SUM ? lag[0] : s == ODK_IMIT_LAG_SUM + 1 ? lag[1] : inc;
+    inc = s == ODK_IMIT_LAG_ABS_SUM ? fabsf(lag[0]) : s == ODK_IMIT_LAG_ABS_SUM + 1 ? fabsf(lag[1]) : inc;
+    float nv = old + inc;
+    nv = s == ODK_IMIT_PREV_CONTACT ? c[0] : s == ODK_IMIT_PREV_CONTACT + 1 ? c[1] : nv;
+    nv = s == ODK_IMIT_PREV_REF ? r[0] : s == ODK_IMIT_PREV_REF + 1 ? r[1] : nv;
+    nv = s == ODK_IMIT_REF_AGE ? age[0] : s == ODK_IMIT_REF_AGE + 1 ? age[1] : nv;
+    return nv;
+  };
+  const float s0 = next(u, A[u]), s1 = next(16 + u, A[16 + u]);
+  A[u] = s0;
+  A[16 + u] = s1;
+  if (!cmp) return;
+  float* B = A + u;
+  B[ODK_IMIT_POS_ERR_SUM] += dp;
+  B[ODK_IMIT_POS_ERR_SQ] += sp;
+  B[ODK_IMIT_POS_ERR_PEAK] = fmaxf(B[ODK_IMIT_POS_ERR_PEAK], fabsf(dp));
+  B[ODK_IMIT_VEL_ERR_SQ] += sv;
+  B[ODK_IMIT_RANGE_MIN] = first ? jq : fminf(B[ODK_IMIT_RANGE_MIN], jq);   // a zeroed row is no minimum: the first sample starts the ranges
+  B[ODK_IMIT_RANGE_MAX] = first ? jq : fmaxf(B[ODK_IMIT_RANGE_MAX], jq);
+  B[ODK_IMIT_REF_RANGE_MIN] = first ? rq : fminf(B[ODK_IMIT_REF_RANGE_MIN], rq);
+  B[ODK_IMIT_REF_RANGE_MAX] = first ? rq : fmaxf(B[ODK_IMIT_REF_RANGE_MAX], rq);
+}
+
+extern "C" int odk_imitation_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
+                                        const float* track_acc_dev, int period_steps, float* acc_dev, void* stream) {
+  if (!b) return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: null batch");
+  if (!priv_dev) return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: null priv_dev");
+  if (!done_dev) return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: null done_dev");
+  if (!truncation_dev) return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: null truncation_dev");
+  if (!track_acc_dev) return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: null track_acc_dev");
+  if (!acc_dev) return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: null acc_dev");
+  if (b->cfg.env_kind != ODK_ENV_JOYSTICK)
+    return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: a Standing batch's privileged row has no reference-motion frame (env_kind = ODK_ENV_JOYSTICK only)");
+  if (!b->cfg.use_imitation)
+    return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: use_imitation = 0: the frame of the privileged row is all zeros, there is nothing to compare with");
+  if (!b->imap_set)
+    return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: the batch has no imitation joint map (odk_batch_set_imitation_joints)");
+  const int nu = b->model.h.nu;
+  if (nu > ODK_IMIT_STRIDE) return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: the model has %d actuators, a row holds %d", nu, ODK_IMIT_STRIDE);
+  if (period_steps < 0) return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: period_steps = %d (the reference motion's nb_steps_in_period, or 0 for unfolded lags)", period_steps);
+  int nobs, npriv;
+  obs_sizes_nu(nu, b->cfg.env_kind, &nobs, &npriv);
+  HIPCHK(hipSetDevice(b->device));
+  const long long threads = (long long)b->nenv * 16;
+  hipLaunchKernelGGL(imitation_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, priv_dev, npriv, nobs, nu, done_dev,
+                     track_acc_dev, b->d_imap, b->d_model, period_steps, acc_dev, b->nenv);
   HIPCHK(hipGetLastError());
   return ODK_OK;
 }

@@ -166,6 +166,7 @@ def load_library() -> C.CDLL:
     L.odk_push_accumulate.argtypes = [P, P, P, P, P, C.c_float, C.c_float, P, P]
     L.odk_gait_accumulate.argtypes = [P, P, P, P, P, P, P, P]
     L.odk_posture_accumulate.argtypes = [P, P, P, P, P, C.c_float, P, P]
+    L.odk_imitation_accumulate.argtypes = [P, P, P, P, P, C.c_int, P, P]
     L.odk_batch_get_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_set_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_get_debug.argtypes = [P, FP, FP, FP, FP]
@@ -211,6 +212,7 @@ EXPORTED_SYMBOLS = (
     "odk_batch_destroy", "odk_batch_set_config", "odk_batch_set_param", "odk_reset", "odk_step", "odk_physics_step",
     "odk_batch_bind_commands", "odk_batch_set_reward_terms", "odk_batch_bind_reward_metrics", "odk_batch_set_imitation_joints", "odk_batch_set_head_joints",
     "odk_tracking_accumulate", "odk_batch_bind_pushes", "odk_push_accumulate", "odk_gait_accumulate", "odk_posture_accumulate",
+    "odk_imitation_accumulate",
     "odk_batch_get_state", "odk_batch_set_state", "odk_batch_get_debug", "odk_set_debug_dump", "odk_batch_lds_size",
     "odk_batch_get_lds", "odk_lds_offset", "odk_batch_record_size", "odk_batch_get_records", "odk_batch_set_records", "odk_batch_timing", "odk_gae", "odk_ppo_head",
     "odk_policy_sample", "odk_adam_clip", "odk_silu_bwd_colsum", "odk_colsum_partial", "odk_colsum_finalize", "odk_gather_rows", "odk_dw_gemm",
@@ -260,6 +262,15 @@ POSTURE_NACC = 32
  POSTURE_HEIGHT_SUM, POSTURE_LEG_POSE_SUM, POSTURE_LEG_VEL_SUM, POSTURE_HEAD_SQERR_SUM) = range(10)
 POSTURE_ANGLE_SUM, POSTURE_ERR_SQ_SUM, POSTURE_ERR_PEAK, POSTURE_LAST_OFF = 16, 20, 24, 28
 
+# odk_imitation_accumulate's per-env slots (include/odk.h ODK_IMIT_*): scalars ([2] = left, right foot), then per-actuator arrays, entry u at SLOT + u
+IMIT_NACC = 160
+IMIT_STRIDE = 16
+IMIT_SAMPLES, IMIT_GATED, IMIT_SPEED_ERR_SQ_SUM, IMIT_REF_SPEED_SUM, IMIT_JOINT_POS_SQ_SUM, IMIT_JOINT_VEL_SQ_SUM = range(6)
+(IMIT_BOTH, IMIT_ROBOT_ONLY, IMIT_REF_ONLY, IMIT_REF_TOUCHDOWNS, IMIT_TOUCHDOWNS, IMIT_LAG_SUM, IMIT_LAG_ABS_SUM, IMIT_PREV_CONTACT, IMIT_PREV_REF,
+ IMIT_REF_AGE) = range(6, 26, 2)
+(IMIT_POS_ERR_SUM, IMIT_POS_ERR_SQ, IMIT_POS_ERR_PEAK, IMIT_VEL_ERR_SQ, IMIT_RANGE_MIN, IMIT_RANGE_MAX, IMIT_REF_RANGE_MIN,
+ IMIT_REF_RANGE_MAX) = range(32, 160, 16)
+
 
 def check_pushes(push, nenv: int, device: int) -> None:
     """What `Batch.bind_pushes` accepts: a contiguous float32 [nenv, >= 2] tensor on cuda:`device`; raises OdkError otherwise."""
@@ -277,7 +288,7 @@ def check_pushes(push, nenv: int, device: int) -> None:
 
 
 def check_accumulator(name: str, acc, nenv: int, ncol: int, device: int) -> None:
-    """An accumulator argument of `Batch.push_accumulate` / `Batch.gait_accumulate` / `Batch.posture_accumulate`: a contiguous float32 [nenv, ncol] tensor on cuda:`device`; OdkError otherwise."""
+    """An accumulator argument of `Batch.push_accumulate` / `Batch.gait_accumulate` / `Batch.posture_accumulate` / `Batch.imitation_accumulate`: a contiguous float32 [nenv, ncol] tensor on cuda:`device`; OdkError otherwise."""
     import torch
     if not torch.is_tensor(acc):
         raise OdkError(f"{name}: expected a torch tensor, got {type(acc).__name__}")
@@ -1038,6 +1049,19 @@ class Batch:
         _chk(self.L.odk_posture_accumulate(self._b, C.c_void_p(self.priv.data_ptr()), C.c_void_p(self.done.data_ptr()),
                                            C.c_void_p(self.truncation.data_ptr()), C.c_void_p(track_acc.data_ptr()), float(tol),
                                            C.c_void_p(acc.data_ptr()), self._stream()))
+
+    def imitation_accumulate(self, acc, track_acc, period_steps: int):
+        """One `odk_imitation_accumulate` launch over this step's outputs into `acc` ([nenv, IMIT_NACC] float32, zeroed before the first
+        step), issued after `step` and BEFORE `tracking_accumulate(track_acc)`.  `period_steps`: the reference motion's nb_steps_in_period
+        (touchdown lags past half of it count as early for the next cycle), or 0 for lags that are not folded.  A Joystick batch that runs
+        the imitation reward with a joint map (the duck has one; `set_imitation_joints` otherwise); needs no bound commands."""
+        check_accumulator("imitation_accumulate: acc", acc, self.nenv, IMIT_NACC, self.device)
+        check_accumulator("imitation_accumulate: track_acc", track_acc, self.nenv, TRACK_NACC, self.device)
+        if int(period_steps) != period_steps:
+            raise OdkError(f"imitation_accumulate: period_steps = {period_steps!r} (a whole number of steps)")
+        _chk(self.L.odk_imitation_accumulate(self._b, C.c_void_p(self.priv.data_ptr()), C.c_void_p(self.done.data_ptr()),
+                                             C.c_void_p(self.truncation.data_ptr()), C.c_void_p(track_acc.data_ptr()), int(period_steps),
+                                             C.c_void_p(acc.data_ptr()), self._stream()))
 
     def physics_step(self, ctrl, n_substeps: int = 10):
         assert ctrl.is_cuda and ctrl.dtype == self.torch.float32 and ctrl.is_contiguous() and tuple(ctrl.shape) == (self.nenv, self.model.nu)

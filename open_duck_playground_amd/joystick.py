@@ -346,6 +346,16 @@ class Joystick:
         """The ReferenceMotion loaded from the `reference_motion` config key, or None (the duck's shipped table / no imitation)."""
         return self._motion
 
+    @property
+    def imitation_joints(self):
+        """The imitation joint map the batch compares with (frame joint per actuator, -1: not compared): the `reference_motion` key's, the
+        duck's own (custom_rewards.py:80-88) on the shipped table, or None for a robot that runs without the imitation reward."""
+        if self._motion is not None:
+            return [int(j) for j in self._imitation_map]
+        if not self._robot.is_open_duck:
+            return None
+        return [u if u < 5 else (u + 2 if u >= 9 else -1) for u in range(self._model.nu)]      # odk_batch_create's default
+
     def _engine_config(self, autoreset: bool, lanes_per_env: int) -> engine.EnvConfig:
         imitation = USE_IMITATION_REWARD and (self._robot.is_open_duck or self._motion is not None)
         return to_engine_config(self._config, autoreset, lanes_per_env, use_imitation=imitation,

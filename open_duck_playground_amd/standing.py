@@ -113,6 +113,10 @@ class Standing(Joystick):
                 raise ValueError(f"config {k}: the Standing task has no imitation reward (standing.py:42)")
         return None
 
+    @property
+    def imitation_joints(self):
+        return None      # no imitation reward, no frame in the privileged row
+
     def _load_head_joints(self):
         spec = self._config.get("head_joints", None)
         return None if spec is None else head_joint_map(self._model, spec)

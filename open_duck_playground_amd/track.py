@@ -48,6 +48,19 @@ the home pose, so the run is a step response) and the share of envs that ended i
 "stillness" the planar drift speed, yaw and roll/pitch rate RMS, lean, root height and the two parts of cost_stand_still over the joints
 that are not the head's (`reduce_posture`).  The head-joint map is the env's: the duck's own, or `--env standing --head_joints` for another
 robot.  Without `--posture` nothing changes.
+
+Imitation fidelity (does the policy walk the reference gait? -- the question behind `imitation=` and a `polynomial_coefficients.pkl` of one's
+own, which the reference answers with ref_motion_viewer.py and plot_saved_obs.py on one CPU robot, compared by eye):
+
+    python -m open_duck_playground_amd.track --checkpoint <ckpt> --command 0.1 0 0 --imitation_report
+
+`--imitation_report` adds one launch (`odk_imitation_accumulate`) to the captured step, before the tracking accumulator, with gait's
+contract.  It compares the step's noise-free privileged observation with the reference-motion frame the reward read in that step, through
+the batch's imitation joint map.  Every command row (and, with pushes, every cell too) gains an "imitation" object: per compared joint the
+bias, RMS and peak position error, the velocity RMS error and the range used against the reference's; the reward's joint_pos and joint_vel
+terms; per foot the contact agreement, stance shares, touchdown counts and the touchdown lag against the reference's touchdown; the
+reward's contact term; and the planar speed error (`reduce_imitation`).  The Joystick task with the imitation reward on: the duck, or
+another robot with `--reference_motion`.  Without the flag nothing changes.
 """
 from __future__ import annotations
 
@@ -75,6 +88,13 @@ from .engine import (POSTURE_NACC, POSTURE_SAMPLES as S_SAMPLES, POSTURE_DRIFT_S
                      POSTURE_LEG_POSE_SUM as S_LEG_POSE, POSTURE_LEG_VEL_SUM as S_LEG_VEL, POSTURE_HEAD_SQERR_SUM as S_HEAD_SQERR,
                      POSTURE_ANGLE_SUM as S_ANGLE, POSTURE_ERR_SQ_SUM as S_ERR_SQ, POSTURE_ERR_PEAK as S_ERR_PEAK,
                      POSTURE_LAST_OFF as S_LAST_OFF)      # ODK_POSTURE_*
+
+from .engine import (IMIT_NACC, IMIT_SAMPLES as I_SAMPLES, IMIT_GATED as I_GATED, IMIT_SPEED_ERR_SQ_SUM as I_SPEED_ERR_SQ, IMIT_REF_SPEED_SUM as I_REF_SPEED,
+                     IMIT_JOINT_POS_SQ_SUM as I_JOINT_POS_SQ, IMIT_JOINT_VEL_SQ_SUM as I_JOINT_VEL_SQ, IMIT_BOTH as I_BOTH, IMIT_ROBOT_ONLY as I_ROBOT_ONLY,
+                     IMIT_REF_ONLY as I_REF_ONLY, IMIT_REF_TOUCHDOWNS as I_REF_TOUCH, IMIT_TOUCHDOWNS as I_TOUCH, IMIT_LAG_SUM as I_LAG,
+                     IMIT_LAG_ABS_SUM as I_LAG_ABS, IMIT_POS_ERR_SUM as I_POS_ERR, IMIT_POS_ERR_SQ as I_POS_ERR_SQ, IMIT_POS_ERR_PEAK as I_POS_ERR_PEAK,
+                     IMIT_VEL_ERR_SQ as I_VEL_ERR_SQ, IMIT_RANGE_MIN as I_RANGE_MIN, IMIT_RANGE_MAX as I_RANGE_MAX, IMIT_REF_RANGE_MIN as I_REF_RANGE_MIN,
+                     IMIT_REF_RANGE_MAX as I_REF_RANGE_MAX)      # ODK_IMIT_*
 
 COMMAND_KEYS = ("vx", "vy", "wz", "neck_pitch", "head_pitch", "head_yaw", "head_roll")   # the order of cmd_range (include/odk.h)
 NACC = 12
@@ -408,6 +428,104 @@ STILLNESS_KEYS = ("drift_speed_mps", "yaw_rate_rms", "roll_pitch_rate_rms", "til
                   "leg_joint_speed_mean")
 
 
+JOINT_POS_WEIGHT, JOINT_VEL_WEIGHT = 15.0, 1.0e-3      # the imitation reward's weights of its joint terms (custom_rewards.py:127-128)
+FEET = ("left", "right")
+
+
+def imitation_refusal(args) -> Optional[str]:
+    """Why `--imitation_report` cannot run with these arguments, or None.  Host work only (at most the robot's MJCF is compiled), so `run`
+    asks before it makes a batch: the Standing task has no reference-motion frame in its privileged row, and a robot that is not the duck
+    runs without the imitation reward unless `--reference_motion` gives it a table."""
+    if args.env != "joystick":
+        return (f"--imitation_report: the {args.env} env has no imitation reward and no reference-motion frame in its privileged observation; "
+                "the report belongs to --env joystick")
+    if getattr(args, "xml", None) and not getattr(args, "reference_motion", None):
+        from . import constants
+        from .model import Model
+        if not constants.robot_of(Model.from_xml(args.xml)).is_open_duck:
+            return ("--imitation_report: a robot that is not the duck runs without the imitation reward (the shipped table is the duck's), so there "
+                    "is no reference motion to compare with; give the robot's own with --reference_motion polynomial_coefficients.pkl")
+    return None
+
+
+def imitation_joint_info(env):
+    """(imap, joint_names, period_steps) of `reduce_imitation` and `Tracker(imitation=True)` for an env: the imitation joint map its batch
+    holds (frame joint per actuator, -1: not compared), per actuator the name of the joint it drives, and the reference motion's
+    nb_steps_in_period -- the `reference_motion` key's, or the shipped table's for the duck.  ValueError for an env without the reward."""
+    from .reference_motion import ReferenceMotion, actuated_joint_names
+    imap = env.imitation_joints
+    if imap is None:
+        raise ValueError("--imitation_report: the env runs without the imitation reward (the Standing task, or a robot that is not the duck "
+                         "without --reference_motion)")
+    motion = env.reference_motion
+    period = motion.nb_steps_in_period if motion is not None else ReferenceMotion.from_npz().nb_steps_in_period
+    return [int(j) for j in imap], actuated_joint_names(env.mj_model), int(period)
+
+
+def reduce_imitation(acc: np.ndarray, commands: Sequence, envs_per_block: int, dt: float, imap: Sequence[int], joint_names: Sequence[str],
+                     period_steps: int) -> List[Dict]:
+    """One "imitation" object per block of `envs_per_block` envs (a block per entry of `commands`: the command blocks of `command_blocks`,
+    or the (command, push) cells of `cell_blocks`), from the imitation accumulator ([nenv, 160], include/odk.h ODK_IMIT_*), in float64.
+    `imap[u]` is the frame joint of actuator u (-1: not compared), `joint_names[u]` the joint it drives.  Sums are pooled over the block's
+    samples (the steps of the envs' first episodes that did not end them), so an env weighs by its samples.  `gated_share`: the share of
+    samples with a move command, those the reward pays.  `joints`: one entry per compared actuator, in actuator order -- `joint`,
+    `frame_joint`, `bias` (mean of angle - reference), `rms_error`, `peak_error` (max over the block), `vel_rms_error`, `range` and
+    `reference_range` ([min, max] over the block of the joint angle and of the reference's) and `amplitude_ratio` = the width of the former
+    over the latter's (None for a reference that does not move).  `joint_pos_term` / `joint_vel_term`: the mean over samples of the summed
+    squared position / velocity error times the reward's weights 15 and 1e-3.  `feet` (left, right): `contact_agreement` the share of
+    samples whose contact equals the reference's, `stance_share` / `reference_stance_share`, `touchdowns` (the robot's, from the reference's
+    first touchdown on: those with a lag) and `reference_touchdowns`, `touchdown_lag_steps` the mean signed lag behind the reference's
+    touchdown (negative: early for the next one; folded at half of `period_steps`), `touchdown_lag_s` = that times dt,
+    `touchdown_lag_abs_steps` the mean |lag|; None without a counted touchdown.  `contact_term`: the agreements of both feet added, the
+    mean of the reward's contact term.  `speed_rms_error` / `reference_speed_mean`: planar speed against the frame's.  A block without a
+    sample has nothing to average: its figures are None."""
+    acc = np.asarray(acc, np.float64).reshape(-1, IMIT_NACC)
+    E, dt = int(envs_per_block), float(dt)
+    out = []
+    for c, _ in enumerate(commands):
+        blk = acc[c * E:(c + 1) * E]
+        n = blk[:, I_SAMPLES]
+        live = n > 0
+        samples = float(n.sum())
+        some = samples > 0
+        mean = lambda s: float(blk[:, s].sum() / samples) if some else None
+        rms = lambda s: float(np.sqrt(blk[:, s].sum() / samples)) if some else None
+        joints = []
+        for u, ri in enumerate(imap):
+            if ri < 0:
+                continue
+            lo, hi = (float(blk[live, I_RANGE_MIN + u].min()), float(blk[live, I_RANGE_MAX + u].max())) if some else (None, None)
+            rlo, rhi = (float(blk[live, I_REF_RANGE_MIN + u].min()), float(blk[live, I_REF_RANGE_MAX + u].max())) if some else (None, None)
+            joints.append(dict(
+                joint=str(joint_names[u]), frame_joint=int(ri), bias=mean(I_POS_ERR + u), rms_error=rms(I_POS_ERR_SQ + u),
+                peak_error=float(blk[live, I_POS_ERR_PEAK + u].max()) if some else None, vel_rms_error=rms(I_VEL_ERR_SQ + u),
+                range=[lo, hi], reference_range=[rlo, rhi], amplitude_ratio=float((hi - lo) / (rhi - rlo)) if some and rhi > rlo else None))
+        feet = []
+        for f, name in enumerate(FEET):
+            both, ronly, fonly = (float(blk[:, s + f].sum()) for s in (I_BOTH, I_ROBOT_ONLY, I_REF_ONLY))
+            td, lag, lag_abs = (float(blk[:, s + f].sum()) for s in (I_TOUCH, I_LAG, I_LAG_ABS))
+            feet.append(dict(
+                foot=name, contact_agreement=float(1.0 - (ronly + fonly) / samples) if some else None,
+                stance_share=float((both + ronly) / samples) if some else None, reference_stance_share=float((both + fonly) / samples) if some else None,
+                touchdowns=int(round(td)), reference_touchdowns=int(round(float(blk[:, I_REF_TOUCH + f].sum()))),
+                touchdown_lag_steps=float(lag / td) if td > 0 else None, touchdown_lag_s=float(lag / td * dt) if td > 0 else None,
+                touchdown_lag_abs_steps=float(lag_abs / td) if td > 0 else None))
+        jp, jv = mean(I_JOINT_POS_SQ), mean(I_JOINT_VEL_SQ)
+        out.append(dict(
+            samples=int(round(samples)), gated_share=mean(I_GATED), period_steps=int(period_steps), joints=joints,
+            joint_pos_term=JOINT_POS_WEIGHT * jp if some else None, joint_vel_term=JOINT_VEL_WEIGHT * jv if some else None, feet=feet,
+            contact_term=float(sum(ft["contact_agreement"] for ft in feet)) if some else None,
+            speed_rms_error=rms(I_SPEED_ERR_SQ), reference_speed_mean=mean(I_REF_SPEED)))
+    return out
+
+
+IMITATION_KEYS = ("samples", "gated_share", "period_steps", "joints", "joint_pos_term", "joint_vel_term", "feet", "contact_term", "speed_rms_error",
+                  "reference_speed_mean")
+IMITATION_JOINT_KEYS = ("joint", "frame_joint", "bias", "rms_error", "peak_error", "vel_rms_error", "range", "reference_range", "amplitude_ratio")
+IMITATION_FOOT_KEYS = ("foot", "contact_agreement", "stance_share", "reference_stance_share", "touchdowns", "reference_touchdowns",
+                       "touchdown_lag_steps", "touchdown_lag_s", "touchdown_lag_abs_steps")
+
+
 def reduce_tracking(acc: np.ndarray, commands: Sequence[Sequence[float]], envs_per_command: int) -> List[Dict]:
     """The per-command rows of the report from the accumulator ([nenv, 12], include/odk.h ODK_TRACK_*).  Velocity statistics are over
     the velocity samples of the block's envs (the steps of their first episode that did not end it), pooled; the fall rate is the
@@ -495,10 +613,12 @@ class Tracker:
     step counter -- the first-episode step, since first episodes start together at `reset` -- equals `push_at`, and zeros otherwise.
     With `gait=True` it owns a gait accumulator and the model's torque limits on the device, and the step gains `odk_gait_accumulate`,
     before the tracking accumulator.  With `posture=True` it owns a posture accumulator, and the step gains `odk_posture_accumulate`
-    (head error tolerance `posture_tolerance`, radians), next to gait's launch."""
+    (head error tolerance `posture_tolerance`, radians), next to gait's launch.  With `imitation=True` it owns an imitation accumulator, and
+    the step gains `odk_imitation_accumulate` there too (`period_steps`: the reference motion's, `imitation_joint_info`)."""
 
     def __init__(self, env, net, use_graph: bool = True, kicks=None, push_at: int = DEFAULT_PUSH_AT, push_tolerance=DEFAULT_PUSH_TOLERANCE,
-                 gait: bool = False, posture: bool = False, posture_tolerance: float = DEFAULT_POSTURE_TOLERANCE):
+                 gait: bool = False, posture: bool = False, posture_tolerance: float = DEFAULT_POSTURE_TOLERANCE,
+                 imitation: bool = False):
         import torch
         self.env, self.net, self.torch = env, net, torch
         b = env.batch
@@ -518,6 +638,10 @@ class Tracker:
         self.posture_acc, self.posture_tolerance = None, float(posture_tolerance)
         if posture:
             self.posture_acc = torch.zeros(env.num_envs, POSTURE_NACC, device=b.obs.device)
+        self.imitation_acc = self.period_steps = None
+        if imitation:
+            self.period_steps = imitation_joint_info(env)[2]
+            self.imitation_acc = torch.zeros(env.num_envs, IMIT_NACC, device=b.obs.device)
         from .ppo.learner import fused_policy
         self.fp = fused_policy(net, env.num_envs)
         self.use_graph = use_graph
@@ -541,6 +665,8 @@ class Tracker:
             b.gait_accumulate(self.gait_acc, self.acc, self.torque_limit)         # likewise
         if self.posture_acc is not None:
             b.posture_accumulate(self.posture_acc, self.acc, self.posture_tolerance)
+        if self.imitation_acc is not None:
+            b.imitation_accumulate(self.imitation_acc, self.acc, self.period_steps)
         b.tracking_accumulate(self.acc)
 
     def reset(self, seed: int):
@@ -552,6 +678,8 @@ class Tracker:
             self.gait_acc.zero_()
         if self.posture_acc is not None:
             self.posture_acc.zero_()
+        if self.imitation_acc is not None:
+            self.imitation_acc.zero_()
         if self.fp is not None:
             self.fp.refresh()                       # its packed weight copy <- the current parameters
 
@@ -586,6 +714,11 @@ def run(args, out=sys.stdout) -> Dict:
     gait = bool(getattr(args, "gait", False))
     posture = bool(getattr(args, "posture", False))
     posture_tol = float(getattr(args, "posture_tolerance", DEFAULT_POSTURE_TOLERANCE))
+    imitation = bool(getattr(args, "imitation_report", False))
+    if imitation:      # before any batch work
+        why = imitation_refusal(args)
+        if why:
+            raise SystemExit(why)
     E = int(args.envs_per_command)
     n = len(commands) * max(len(pushes), 1) * E
     torch.cuda.set_device(args.device)
@@ -601,6 +734,11 @@ def run(args, out=sys.stdout) -> Dict:
             head_map, joint_names = posture_head_map(env)
         except ValueError as err:
             raise SystemExit(str(err))
+    if imitation:
+        try:
+            imap, imit_joint_names, period_steps = imitation_joint_info(env)
+        except ValueError as err:
+            raise SystemExit(str(err))
     net = load_networks(args.checkpoint, env, dev)
     if pushes:
         push_at = int(args.push_at)
@@ -611,11 +749,11 @@ def run(args, out=sys.stdout) -> Dict:
         cmd = torch.from_numpy(cmd_np).to(dev)
         env.set_commands(cmd)
         tr = Tracker(env, net, kicks=torch.from_numpy(kicks_np).to(dev), push_at=push_at, push_tolerance=tol, gait=gait, posture=posture,
-                     posture_tolerance=posture_tol)
+                     posture_tolerance=posture_tol, imitation=imitation)
     else:
         cmd = torch.from_numpy(command_blocks(commands, E)).to(dev)
         env.set_commands(cmd)
-        tr = Tracker(env, net, gait=gait, posture=posture, posture_tolerance=posture_tol)
+        tr = Tracker(env, net, gait=gait, posture=posture, posture_tolerance=posture_tol, imitation=imitation)
     nobs = env.observation_size["state"][0]
     T = int(args.episode_length)
     save_obs_path, save_qpos_path = getattr(args, "save_obs", None), getattr(args, "save_qpos", None)
@@ -635,6 +773,7 @@ def run(args, out=sys.stdout) -> Dict:
         push_acc = tr.push_acc.cpu().numpy() if pushes else None
         gait_acc = tr.gait_acc.cpu().numpy() if gait else None
         posture_acc = tr.posture_acc.cpu().numpy() if posture else None
+        imitation_acc = tr.imitation_acc.cpu().numpy() if imitation else None
     rows = reduce_tracking(acc, commands, max(len(pushes), 1) * E)
     if pushes:
         for row, extra in zip(rows, reduce_pushes(push_acc, commands, pushes, E, float(env.dt))):
@@ -654,6 +793,13 @@ def run(args, out=sys.stdout) -> Dict:
             cell_cmds = [row["command"] for row in rows for _ in row["pushes"]]
             for cell, g in zip(cells, reduce_posture(posture_acc, cell_cmds, E, float(env.dt), head_map, joint_names)):
                 cell["posture"] = g
+    if imitation:
+        for row, g in zip(rows, reduce_imitation(imitation_acc, commands, max(len(pushes), 1) * E, float(env.dt), imap, imit_joint_names, period_steps)):
+            row["imitation"] = g
+        if pushes:      # and one per (command, push) cell, in `cell_blocks` order
+            cells = [cell for row in rows for cell in row["pushes"]]
+            for cell, g in zip(cells, reduce_imitation(imitation_acc, cells, E, float(env.dt), imap, imit_joint_names, period_steps)):
+                cell["imitation"] = g
     settings = dict(checkpoint=args.checkpoint, env=args.env, task=args.task, xml=args.xml, cone=args.cone,
                     hfield_up_normals_only=bool(args.hfield_up_normals_only), envs_per_command=E, episode_length=T, seed=int(args.seed),
                     num_envs=n, dt=float(env.dt), policy="deterministic tanh(loc)", fused_policy=tr.fp is not None, graph=tr.graph is not None,
@@ -665,6 +811,8 @@ def run(args, out=sys.stdout) -> Dict:
         settings.update(gait=True)
     if posture:
         settings.update(posture=True, posture_tolerance=posture_tol)
+    if imitation:
+        settings.update(imitation_report=True, imitation_period_steps=period_steps)
     report = make_report(settings, rows)
     if save_obs_path:
         save_obs(save_obs_path, obs_hist.cpu().numpy())
@@ -716,6 +864,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "The head-joint map is the duck's own, or --env standing --head_joints for another robot")
     p.add_argument("--posture_tolerance", type=posture_tolerance, default=DEFAULT_POSTURE_TOLERANCE, metavar="RAD",
                    help="settling: the head joint error (rad) above which a step counts as not settled (BUILD-DEFINED default); read by --posture only")
+    p.add_argument("--imitation_report", action="store_true",
+                   help="add an \"imitation\" object to every command row (and push cell): does the policy walk the reference gait?  Per compared "
+                        "joint (the imitation joint map) the bias, RMS and peak error against the reference motion, the velocity RMS error, the range "
+                        "used against the reference's and their ratio; the reward's joint_pos, joint_vel and contact terms; per foot the contact "
+                        "agreement, stance shares, touchdowns and the touchdown lag behind the reference's (negative: early); the planar speed error.  "
+                        "The Joystick task with the imitation reward: the duck, or another robot with --reference_motion")
     p.add_argument("--episode_length", type=int, default=1000)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--device", type=int, default=0)
