@@ -421,6 +421,66 @@ enum { ODK_IMIT_SAMPLES = 0, ODK_IMIT_GATED = 1, ODK_IMIT_SPEED_ERR_SQ_SUM = 2, 
 int odk_imitation_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
                              const float* track_acc_dev, int period_steps, float* acc_dev /* [nenv, ODK_IMIT_NACC] */, void* stream);
 
+/* Command schedules (replaces the keyboard of mujoco_infer.py: walk, then stop; forward, then turn): the command of an env changes at given
+ * steps of its first episode, inside a captured evaluation step.  A schedule is nseg <= ODK_SCHED_MAX_SEGMENTS segments of
+ * ODK_SCHED_SEG_FLOATS floats: start_step, then the 7 command entries in cmd_range order.  Segment 0 starts at step 0, the starts are whole
+ * numbers and strictly increasing, and unused trailing segments carry ODK_SCHED_NEVER (above every float32 step count) as start_step.
+ * sched_dev: [nsched, nseg, ODK_SCHED_SEG_FLOATS] device floats; sched_of_env_dev: [nenv] int32, env e's schedule (clamped into
+ * 0 .. nsched - 1 by the kernels, which never read outside the table); track_acc_dev: [nenv, ODK_TRACK_NACC], odk_tracking_accumulate's.
+ * The host cannot see device tables: their contents are the caller's to validate.
+ *
+ * odk_command_schedule_apply: one launch, graph-capturable, issued BEFORE odk_step.  The tracking accumulator is the clock: STEPS of env e
+ * is then the index t of e's first-episode step that is about to run, the segment in force is the last one with start_step <= t, and its
+ * command overwrites entries 0..6 of env e's row in the BOUND command buffer (odk_batch_bind_commands: the batch holds the pointer and the
+ * stride; the buffer is the caller's, and binding it says that this launch may write it).  Columns beyond 6 of a wider row are left alone.
+ * An env whose ENDED is set has no step about to run in its first episode: it gets the command of the step that ended it (t = STEPS - 1),
+ * the segment it ended in; none of the accumulators reads it afterwards.  With a zeroed tracking accumulator the launch writes segment
+ * 0's command everywhere, which is what odk_reset must find: issue it once before the reset.  No counter, no per-env state: the launch is
+ * a pure function of its inputs.  ODK_ERR_INVALID, with the cause in odk_last_error and nothing launched: a null pointer (the message names
+ * the argument), no bound commands, nseg outside 1 .. ODK_SCHED_MAX_SEGMENTS, nsched < 1. */
+#define ODK_SCHED_MAX_SEGMENTS 8
+#define ODK_SCHED_SEG_FLOATS 8
+#define ODK_SCHED_NEVER 1.0e9f
+int odk_command_schedule_apply(const odk_batch* b, const float* sched_dev, int nsched, int nseg, const int32_t* sched_of_env_dev,
+                               const float* track_acc_dev, void* stream);
+
+/* Step-response accumulator (how fast does the policy follow a new command, how far does it overshoot, where does it settle): one launch
+ * per evaluation step, graph-capturable, issued after odk_step and BEFORE odk_tracking_accumulate (track_acc_dev's ENDED slot then still
+ * says whether env e's first episode was running when this step began, and its STEPS slot is the index t of the step that just ran), with
+ * odk_push_accumulate's contract.  Env e's row of acc_dev [nenv, ODK_RESP_NACC], zeroed by the caller before the first step, holds one block
+ * of ODK_RESP_STRIDE floats per segment; a launch touches only the block of the segment in force at step t (the last one with start_step
+ * <= t, as odk_command_schedule_apply chose it before the step), and only during e's first episode.  Every other float keeps its bits.
+ * A sample is odk_tracking_accumulate's velocity sample (a step that is not done), the achieved velocities and the errors are
+ * odk_push_accumulate's: local linear velocity at nobs + 9 and yaw rate at nobs + 2 of priv_dev [nenv, npriv]; the planar error
+ * hypot(vx - cx, vy - cy) through float64 with one rounding to float32, the yaw error |wz - cwz| in float32; the command c is the
+ * segment's, read from the bound row.  k = t - start_step + 1 is the 1-based index of step t among the steps of its segment.  Per segment:
+ *   ENTERED         1 once a first-episode step ran in the segment
+ *   SAMPLES         velocity samples in the segment
+ *   FELL            1 when the first episode ended in this segment with done and no truncation
+ *   STEPS_TO_FALL   k of that done step: the steps from the segment's first step to it, counting both
+ *   FIRST_IN        k of the first sample with planar error <= lin_tol AND yaw error <= ang_tol; 0 if none.  The response time
+ *   LAST_OFF        k of the latest sample beyond either tolerance; 0 if none.  The settle time, a running "last seen" as ODK_PUSH_LAST_OFF
+ *   PEAK_LIN_ERR, PEAK_ANG_ERR   maxima of the two errors over the samples at or after FIRST_IN's (0 while FIRST_IN is 0): how far the policy
+ *                   leaves the command again once it has reached it
+ *   SUM[3], SQERR[3]   of vx, vy, wz and of their squared errors against the segment's command, as ODK_TRACK_SUM / ODK_TRACK_SQERR
+ *   OVERSHOOT[3]    per axis the maximum over the samples of (v - c) * sign(c - c_prev), floored at 0; c_prev is the previous segment's
+ *                   command on that axis from the table, 0 for segment 0 (the episode starts at rest); an axis whose command did not change
+ *                   keeps 0
+ *   TAIL_SAMPLES, TAIL_SUM[3]   count of, and sum of the achieved velocities over, the samples with k > tail_after: the steady state after
+ *                   the transient
+ * Every sum is float32, added in step order, every product is rounded before it is added (no fused multiply-add), one thread owns an env's
+ * row and there are no atomics: a host restatement in float32 has the bits, and a replay is deterministic.  ODK_ERR_INVALID, with the
+ * cause in odk_last_error and nothing launched: a null pointer (the message names the argument), no bound commands, a tolerance that is
+ * negative or not finite, tail_after < 0, nseg outside 1 .. ODK_SCHED_MAX_SEGMENTS, nsched < 1. */
+#define ODK_RESP_STRIDE 24
+#define ODK_RESP_NACC (ODK_SCHED_MAX_SEGMENTS * ODK_RESP_STRIDE)
+enum { ODK_RESP_ENTERED = 0, ODK_RESP_SAMPLES = 1, ODK_RESP_FELL = 2, ODK_RESP_STEPS_TO_FALL = 3, ODK_RESP_FIRST_IN = 4, ODK_RESP_LAST_OFF = 5,
+       ODK_RESP_PEAK_LIN_ERR = 6, ODK_RESP_PEAK_ANG_ERR = 7, ODK_RESP_SUM = 8, ODK_RESP_SQERR = 11, ODK_RESP_OVERSHOOT = 14,
+       ODK_RESP_TAIL_SAMPLES = 17, ODK_RESP_TAIL_SUM = 18 };
+int odk_response_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
+                            const float* track_acc_dev, const float* sched_dev, int nsched, int nseg, const int32_t* sched_of_env_dev,
+                            float lin_tol, float ang_tol, int tail_after, float* acc_dev /* [nenv, ODK_RESP_NACC] */, void* stream);
+
 /* mjx_env.step alone (physics only, n_substeps, ctrl = ctrl_dev [nenv, nu]); for parity tests */
 int odk_physics_step(odk_batch* b, const float* ctrl_dev, int n_substeps, void* stream);
 

@@ -1,4 +1,5 @@
-// odk_engine.hip -- the batch C-ABI of include/odk.h (libodk.so) + the accumulator kernels of the tracking / push / gait / posture / imitation reports.
+// odk_engine.hip -- the batch C-ABI of include/odk.h (libodk.so) + the accumulator kernels of the tracking / push / gait / posture / imitation / response reports
+// and the command-schedule kernel.
 //
 // Host side: device buffers, launches on the caller's stream (blob -> DevModel, odk_model_load and the model getters: odk_model_load.hip).  Device side:
 // the reset / step / physics-only kernels live in odk_env_kernels.h and are compiled one object per kernel set (odk_env_unit.hip); this file
@@ -794,6 +795,132 @@ extern "C" int odk_imitation_accumulate(const odk_batch* b, const float* priv_de
   const long long threads = (long long)b->nenv * 16;
   hipLaunchKernelGGL(imitation_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, priv_dev, npriv, nobs, nu, done_dev,
                      track_acc_dev, b->d_imap, b->d_model, period_steps, acc_dev, b->nenv);
+  HIPCHK(hipGetLastError());
+  return ODK_OK;
+}
+
+// Command schedules.  The segment of schedule row S ([nseg, ODK_SCHED_SEG_FLOATS]) in force at first-episode step t: the last one whose
+// start_step is <= t (segment 0 when none is: a table whose first start is not 0 is the caller's mistake, not an out-of-range index)
+__device__ __forceinline__ int sched_segment(const float* __restrict__ S, int nseg, float t) {
+  int k = 0;
+  for (int i = 1; i < nseg; i++) k = S[i * ODK_SCHED_SEG_FLOATS] <= t ? i : k;
+  return k;
+}
+__device__ __forceinline__ const float* sched_row(const float* __restrict__ sched, int nsched, int nseg, const int* __restrict__ sched_of_env, int e) {
+  const int s = min(max(sched_of_env[e], 0), nsched - 1);   // a map entry outside the table reads a valid row, never past it
+  return sched + (size_t)s * nseg * ODK_SCHED_SEG_FLOATS;
+}
+
+// The command of the step about to run (one thread per env), issued before odk_step: the tracking accumulator's STEPS slot is the clock.
+// An env past its first episode keeps the command of the step that ended it (STEPS - 1; STEPS >= 1 once ENDED is set).
+__global__ void __launch_bounds__(256) sched_apply_kernel(const float* __restrict__ sched, int nsched, int nseg, const int* __restrict__ sched_of_env,
+                                                          const float* __restrict__ track, float* __restrict__ cmd, int cmd_stride, int nenv) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= nenv) return;
+  const float* T = track + (size_t)e * ODK_TRACK_NACC;
+  const float t = T[ODK_TRACK_ENDED] != 0.0f ? T[ODK_TRACK_STEPS] - 1.0f : T[ODK_TRACK_STEPS];
+  const float* S = sched_row(sched, nsched, nseg, sched_of_env, e);
+  const float* G = S + sched_segment(S, nseg, t) * ODK_SCHED_SEG_FLOATS + 1;
+  float* C = cmd + (size_t)e * cmd_stride;
+#pragma unroll
+  for (int k = 0; k < 7; k++) C[k] = G[k];
+}
+
+static int sched_args_ok(const char* fn, const odk_batch* b, const float* sched_dev, int nsched, int nseg, const int32_t* sched_of_env_dev,
+                         const float* track_acc_dev) {
+  if (!b) return fail(ODK_ERR_INVALID, "%s: null batch", fn);
+  if (!sched_dev) return fail(ODK_ERR_INVALID, "%s: null sched_dev", fn);
+  if (!sched_of_env_dev) return fail(ODK_ERR_INVALID, "%s: null sched_of_env_dev", fn);
+  if (!track_acc_dev) return fail(ODK_ERR_INVALID, "%s: null track_acc_dev", fn);
+  if (!b->d_cmd) return fail(ODK_ERR_INVALID, "%s: no commands bound (odk_batch_bind_commands)", fn);
+  if (nseg < 1 || nseg > ODK_SCHED_MAX_SEGMENTS) return fail(ODK_ERR_INVALID, "%s: nseg = %d (a schedule has 1 .. %d segments)", fn, nseg, ODK_SCHED_MAX_SEGMENTS);
+  if (nsched < 1) return fail(ODK_ERR_INVALID, "%s: nsched = %d (at least one schedule)", fn, nsched);
+  return ODK_OK;
+}
+
+extern "C" int odk_command_schedule_apply(const odk_batch* b, const float* sched_dev, int nsched, int nseg, const int32_t* sched_of_env_dev,
+                                          const float* track_acc_dev, void* stream) {
+  if (int rc = sched_args_ok("odk_command_schedule_apply", b, sched_dev, nsched, nseg, sched_of_env_dev, track_acc_dev)) return rc;
+  HIPCHK(hipSetDevice(b->device));
+  // the bound buffer is the caller's own device memory, handed over read-only for the step kernels; this launch is the one writer
+  hipLaunchKernelGGL(sched_apply_kernel, dim3((b->nenv + 255) / 256), dim3(256), 0, (hipStream_t)stream, sched_dev, nsched, nseg, sched_of_env_dev,
+                     track_acc_dev, const_cast<float*>(b->d_cmd), b->cmd_stride, b->nenv);
+  HIPCHK(hipGetLastError());
+  return ODK_OK;
+}
+
+// Step-response state of one evaluation step (one thread per env), issued between odk_step and odk_tracking_accumulate (the ENDED / STEPS
+// contract of push_kernel): only the block of the segment in force at the step that just ran is touched.  Velocities and errors as
+// push_kernel's.  Contraction is off: every product is rounded before it is added, so a float32 host restatement has the sums' bits.
+__global__ void __launch_bounds__(256) response_kernel(const float* __restrict__ priv, int npriv, int nobs, const float* __restrict__ done,
+                                                       const float* __restrict__ trunc, const float* __restrict__ cmd, int cmd_stride,
+                                                       const float* __restrict__ track, const float* __restrict__ sched, int nsched, int nseg,
+                                                       const int* __restrict__ sched_of_env, float lin_tol, float ang_tol, float tail_after,
+                                                       float* __restrict__ acc, int nenv) {
+#pragma clang fp contract(off)
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= nenv) return;
+  const float* T = track + (size_t)e * ODK_TRACK_NACC;
+  if (T[ODK_TRACK_ENDED] != 0.0f) return;       // past its first episode
+  const float t = T[ODK_TRACK_STEPS];           // first-episode steps before the one that just ran: its index
+  const float* S = sched_row(sched, nsched, nseg, sched_of_env, e);
+  const int seg = sched_segment(S, nseg, t);
+  const float* G = S + seg * ODK_SCHED_SEG_FLOATS;
+  float* A = acc + (size_t)e * ODK_RESP_NACC + seg * ODK_RESP_STRIDE;
+  const float k = t - G[0] + 1.0f;              // 1-based index of this step among the steps of its segment
+  A[ODK_RESP_ENTERED] = 1.0f;
+  if (done[e] != 0.0f) {   // ends the first episode; no velocity sample (the observation is the auto-reset's)
+    if (trunc[e] == 0.0f) { A[ODK_RESP_FELL] = 1.0f; A[ODK_RESP_STEPS_TO_FALL] = k; }
+    return;
+  }
+  const float* P = priv + (size_t)e * npriv;
+  const float* C = cmd + (size_t)e * cmd_stride;
+  const float v[3] = {P[nobs + 9], P[nobs + 10], P[nobs + 2]};
+  const float ex = v[0] - C[0], ey = v[1] - C[1];
+  const float lin = (float)sqrt((double)ex * (double)ex + (double)ey * (double)ey), ang = fabsf(v[2] - C[2]);   // push_kernel's
+  A[ODK_RESP_SAMPLES] += 1.0f;
+  float first_in = A[ODK_RESP_FIRST_IN];
+  if (lin > lin_tol || ang > ang_tol) A[ODK_RESP_LAST_OFF] = k;
+  else if (first_in == 0.0f) A[ODK_RESP_FIRST_IN] = first_in = k;
+  if (first_in != 0.0f) {
+    A[ODK_RESP_PEAK_LIN_ERR] = fmaxf(A[ODK_RESP_PEAK_LIN_ERR], lin);
+    A[ODK_RESP_PEAK_ANG_ERR] = fmaxf(A[ODK_RESP_PEAK_ANG_ERR], ang);
+  }
+  const bool tail = k > tail_after;
+  if (tail) A[ODK_RESP_TAIL_SAMPLES] += 1.0f;
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const float err = v[a] - C[a];
+    const float sq = err * err;
+    A[ODK_RESP_SUM + a] += v[a];
+    A[ODK_RESP_SQERR + a] += sq;
+    const float prev = seg > 0 ? S[(seg > 0 ? seg - 1 : 0) * ODK_SCHED_SEG_FLOATS + 1 + a] : 0.0f;   // segment 0: the episode starts at rest
+    const float dir = C[a] > prev ? 1.0f : (C[a] < prev ? -1.0f : 0.0f);
+    const float over = err * dir;
+    if (over > A[ODK_RESP_OVERSHOOT + a]) A[ODK_RESP_OVERSHOOT + a] = over;   // (a strict compare: a -0 product never replaces the zeroed slot's +0)
+    if (tail) A[ODK_RESP_TAIL_SUM + a] += v[a];
+  }
+}
+
+extern "C" int odk_response_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
+                                       const float* track_acc_dev, const float* sched_dev, int nsched, int nseg, const int32_t* sched_of_env_dev,
+                                       float lin_tol, float ang_tol, int tail_after, float* acc_dev, void* stream) {
+  const char* fn = "odk_response_accumulate";
+  if (!b) return fail(ODK_ERR_INVALID, "%s: null batch", fn);
+  if (!priv_dev) return fail(ODK_ERR_INVALID, "%s: null priv_dev", fn);
+  if (!done_dev) return fail(ODK_ERR_INVALID, "%s: null done_dev", fn);
+  if (!truncation_dev) return fail(ODK_ERR_INVALID, "%s: null truncation_dev", fn);
+  if (!acc_dev) return fail(ODK_ERR_INVALID, "%s: null acc_dev", fn);
+  if (int rc = sched_args_ok(fn, b, sched_dev, nsched, nseg, sched_of_env_dev, track_acc_dev)) return rc;
+  if (!std::isfinite(lin_tol) || lin_tol < 0.0f) return fail(ODK_ERR_INVALID, "%s: lin_tol = %g (a finite tolerance >= 0, in m/s)", fn, (double)lin_tol);
+  if (!std::isfinite(ang_tol) || ang_tol < 0.0f) return fail(ODK_ERR_INVALID, "%s: ang_tol = %g (a finite tolerance >= 0, in rad/s)", fn, (double)ang_tol);
+  if (tail_after < 0) return fail(ODK_ERR_INVALID, "%s: tail_after = %d (a number of steps >= 0)", fn, tail_after);
+  int nobs, npriv;
+  obs_sizes_nu(b->model.h.nu, b->cfg.env_kind, &nobs, &npriv);
+  HIPCHK(hipSetDevice(b->device));
+  hipLaunchKernelGGL(response_kernel, dim3((b->nenv + 255) / 256), dim3(256), 0, (hipStream_t)stream, priv_dev, npriv, nobs, done_dev, truncation_dev,
+                     b->d_cmd, b->cmd_stride, track_acc_dev, sched_dev, nsched, nseg, sched_of_env_dev, lin_tol, ang_tol, (float)tail_after, acc_dev,
+                     b->nenv);
   HIPCHK(hipGetLastError());
   return ODK_OK;
 }

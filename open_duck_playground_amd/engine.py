@@ -167,6 +167,8 @@ def load_library() -> C.CDLL:
     L.odk_gait_accumulate.argtypes = [P, P, P, P, P, P, P, P]
     L.odk_posture_accumulate.argtypes = [P, P, P, P, P, C.c_float, P, P]
     L.odk_imitation_accumulate.argtypes = [P, P, P, P, P, C.c_int, P, P]
+    L.odk_command_schedule_apply.argtypes = [P, P, C.c_int, C.c_int, P, P, P]
+    L.odk_response_accumulate.argtypes = [P, P, P, P, P, P, C.c_int, C.c_int, P, C.c_float, C.c_float, C.c_int, P, P]
     L.odk_batch_get_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_set_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_get_debug.argtypes = [P, FP, FP, FP, FP]
@@ -212,7 +214,7 @@ EXPORTED_SYMBOLS = (
     "odk_batch_destroy", "odk_batch_set_config", "odk_batch_set_param", "odk_reset", "odk_step", "odk_physics_step",
     "odk_batch_bind_commands", "odk_batch_set_reward_terms", "odk_batch_bind_reward_metrics", "odk_batch_set_imitation_joints", "odk_batch_set_head_joints",
     "odk_tracking_accumulate", "odk_batch_bind_pushes", "odk_push_accumulate", "odk_gait_accumulate", "odk_posture_accumulate",
-    "odk_imitation_accumulate",
+    "odk_imitation_accumulate", "odk_command_schedule_apply", "odk_response_accumulate",
     "odk_batch_get_state", "odk_batch_set_state", "odk_batch_get_debug", "odk_set_debug_dump", "odk_batch_lds_size",
     "odk_batch_get_lds", "odk_lds_offset", "odk_batch_record_size", "odk_batch_get_records", "odk_batch_set_records", "odk_batch_timing", "odk_gae", "odk_ppo_head",
     "odk_policy_sample", "odk_adam_clip", "odk_silu_bwd_colsum", "odk_colsum_partial", "odk_colsum_finalize", "odk_gather_rows", "odk_dw_gemm",
@@ -271,6 +273,17 @@ IMIT_SAMPLES, IMIT_GATED, IMIT_SPEED_ERR_SQ_SUM, IMIT_REF_SPEED_SUM, IMIT_JOINT_
 (IMIT_POS_ERR_SUM, IMIT_POS_ERR_SQ, IMIT_POS_ERR_PEAK, IMIT_VEL_ERR_SQ, IMIT_RANGE_MIN, IMIT_RANGE_MAX, IMIT_REF_RANGE_MIN,
  IMIT_REF_RANGE_MAX) = range(32, 160, 16)
 
+# command schedules (include/odk.h ODK_SCHED_*): up to SCHED_MAX_SEGMENTS segments of SCHED_SEG_FLOATS floats (start_step, then the 7 command entries);
+# unused trailing segments start at SCHED_NEVER
+SCHED_MAX_SEGMENTS = 8
+SCHED_SEG_FLOATS = 8
+SCHED_NEVER = 1.0e9
+# odk_response_accumulate's slots (include/odk.h ODK_RESP_*): one block of RESP_STRIDE floats per segment, [3] = vx, vy, wz
+RESP_STRIDE = 24
+RESP_NACC = SCHED_MAX_SEGMENTS * RESP_STRIDE
+(RESP_ENTERED, RESP_SAMPLES, RESP_FELL, RESP_STEPS_TO_FALL, RESP_FIRST_IN, RESP_LAST_OFF, RESP_PEAK_LIN_ERR, RESP_PEAK_ANG_ERR) = range(8)
+RESP_SUM, RESP_SQERR, RESP_OVERSHOOT, RESP_TAIL_SAMPLES, RESP_TAIL_SUM = 8, 11, 14, 17, 18
+
 
 def check_pushes(push, nenv: int, device: int) -> None:
     """What `Batch.bind_pushes` accepts: a contiguous float32 [nenv, >= 2] tensor on cuda:`device`; raises OdkError otherwise."""
@@ -288,7 +301,7 @@ def check_pushes(push, nenv: int, device: int) -> None:
 
 
 def check_accumulator(name: str, acc, nenv: int, ncol: int, device: int) -> None:
-    """An accumulator argument of `Batch.push_accumulate` / `Batch.gait_accumulate` / `Batch.posture_accumulate` / `Batch.imitation_accumulate`: a contiguous float32 [nenv, ncol] tensor on cuda:`device`; OdkError otherwise."""
+    """An accumulator argument of `Batch.push_accumulate` / `Batch.gait_accumulate` / `Batch.posture_accumulate` / `Batch.imitation_accumulate` / `Batch.response_accumulate`: a contiguous float32 [nenv, ncol] tensor on cuda:`device`; OdkError otherwise."""
     import torch
     if not torch.is_tensor(acc):
         raise OdkError(f"{name}: expected a torch tensor, got {type(acc).__name__}")
@@ -300,6 +313,35 @@ def check_accumulator(name: str, acc, nenv: int, ncol: int, device: int) -> None
         raise OdkError(f"{name}: the tensor must be contiguous")
     if acc.device.type != "cuda" or acc.device.index != int(device):
         raise OdkError(f"{name}: the tensor must live on cuda:{device} (the env's device), got {acc.device}")
+
+
+def check_schedule(name: str, sched, sched_of_env, nenv: int, device: int):
+    """The schedule arguments of `Batch.command_schedule_apply` / `Batch.response_accumulate`: `sched` a contiguous float32
+    [nsched >= 1, 1 .. SCHED_MAX_SEGMENTS, SCHED_SEG_FLOATS] tensor and `sched_of_env` a contiguous int32 [nenv] tensor, both on cuda:`device`;
+    OdkError otherwise.  Returns (nsched, nseg).  The contents (segment 0 at step 0, increasing starts, map entries in range) are the
+    builder's to check: track.schedule_table / track.schedule_blocks."""
+    import torch
+    if not torch.is_tensor(sched):
+        raise OdkError(f"{name}: sched: expected a torch tensor, got {type(sched).__name__}")
+    if sched.dim() != 3 or int(sched.shape[0]) < 1 or not 1 <= int(sched.shape[1]) <= SCHED_MAX_SEGMENTS or int(sched.shape[2]) != SCHED_SEG_FLOATS:
+        raise OdkError(f"{name}: sched: shape must be (nsched >= 1, 1 .. {SCHED_MAX_SEGMENTS}, {SCHED_SEG_FLOATS}), got {tuple(sched.shape)}")
+    if sched.dtype != torch.float32:
+        raise OdkError(f"{name}: sched: dtype must be torch.float32, got {sched.dtype}")
+    if not sched.is_contiguous():
+        raise OdkError(f"{name}: sched: the tensor must be contiguous")
+    if sched.device.type != "cuda" or sched.device.index != int(device):
+        raise OdkError(f"{name}: sched: the tensor must live on cuda:{device} (the env's device), got {sched.device}")
+    if not torch.is_tensor(sched_of_env):
+        raise OdkError(f"{name}: sched_of_env: expected a torch tensor, got {type(sched_of_env).__name__}")
+    if tuple(sched_of_env.shape) != (int(nenv),):
+        raise OdkError(f"{name}: sched_of_env: shape must be ({nenv},), got {tuple(sched_of_env.shape)}")
+    if sched_of_env.dtype != torch.int32:
+        raise OdkError(f"{name}: sched_of_env: dtype must be torch.int32, got {sched_of_env.dtype}")
+    if not sched_of_env.is_contiguous():
+        raise OdkError(f"{name}: sched_of_env: the tensor must be contiguous")
+    if sched_of_env.device.type != "cuda" or sched_of_env.device.index != int(device):
+        raise OdkError(f"{name}: sched_of_env: the tensor must live on cuda:{device} (the env's device), got {sched_of_env.device}")
+    return int(sched.shape[0]), int(sched.shape[1])
 
 
 def _chk(rc: int):
@@ -1062,6 +1104,36 @@ class Batch:
         _chk(self.L.odk_imitation_accumulate(self._b, C.c_void_p(self.priv.data_ptr()), C.c_void_p(self.done.data_ptr()),
                                              C.c_void_p(self.truncation.data_ptr()), C.c_void_p(track_acc.data_ptr()), int(period_steps),
                                              C.c_void_p(acc.data_ptr()), self._stream()))
+
+    def command_schedule_apply(self, sched, sched_of_env, track_acc):
+        """One `odk_command_schedule_apply` launch, issued BEFORE `step`: env e's row of the bound command tensor becomes the command of the
+        segment of schedule `sched_of_env[e]` in force at the first-episode step about to run (`track_acc`'s STEPS slot is the clock; a zeroed
+        `track_acc` gives segment 0, what `reset` must find).  `sched`: float32 [nsched, nseg <= SCHED_MAX_SEGMENTS, SCHED_SEG_FLOATS] (start_step
+        and the 7 command entries per segment, padded with SCHED_NEVER starts); `sched_of_env`: int32 [nenv].  Needs bound commands."""
+        nsched, nseg = check_schedule("command_schedule_apply", sched, sched_of_env, self.nenv, self.device)
+        check_accumulator("command_schedule_apply: track_acc", track_acc, self.nenv, TRACK_NACC, self.device)
+        if self.commands is None:
+            raise OdkError("command_schedule_apply: no commands bound (bind_commands)")
+        _chk(self.L.odk_command_schedule_apply(self._b, C.c_void_p(sched.data_ptr()), nsched, nseg, C.c_void_p(sched_of_env.data_ptr()),
+                                               C.c_void_p(track_acc.data_ptr()), self._stream()))
+
+    def response_accumulate(self, acc, track_acc, sched, sched_of_env, lin_tol: float, ang_tol: float, tail_after: int):
+        """One `odk_response_accumulate` launch over this step's outputs into `acc` ([nenv, RESP_NACC] float32, zeroed before the first step:
+        one block of RESP_STRIDE floats per segment), issued after `step` and BEFORE `tracking_accumulate(track_acc)`, with the schedule that
+        `command_schedule_apply` wrote this step's commands from.  `lin_tol` / `ang_tol`: the planar velocity error (m/s) and yaw-rate error
+        (rad/s) up to which a sample counts as following the command (finite, >= 0); `tail_after`: the samples past this many steps of a
+        segment are its steady state.  Needs bound commands."""
+        check_accumulator("response_accumulate: acc", acc, self.nenv, RESP_NACC, self.device)
+        check_accumulator("response_accumulate: track_acc", track_acc, self.nenv, TRACK_NACC, self.device)
+        nsched, nseg = check_schedule("response_accumulate", sched, sched_of_env, self.nenv, self.device)
+        if int(tail_after) != tail_after:
+            raise OdkError(f"response_accumulate: tail_after = {tail_after!r} (a whole number of steps)")
+        if self.commands is None:
+            raise OdkError("response_accumulate: no commands bound (bind_commands)")
+        _chk(self.L.odk_response_accumulate(self._b, C.c_void_p(self.priv.data_ptr()), C.c_void_p(self.done.data_ptr()),
+                                            C.c_void_p(self.truncation.data_ptr()), C.c_void_p(track_acc.data_ptr()), C.c_void_p(sched.data_ptr()),
+                                            nsched, nseg, C.c_void_p(sched_of_env.data_ptr()), float(lin_tol), float(ang_tol), int(tail_after),
+                                            C.c_void_p(acc.data_ptr()), self._stream()))
 
     def physics_step(self, ctrl, n_substeps: int = 10):
         assert ctrl.is_cuda and ctrl.dtype == self.torch.float32 and ctrl.is_contiguous() and tuple(ctrl.shape) == (self.nenv, self.model.nu)

@@ -61,6 +61,26 @@ bias, RMS and peak position error, the velocity RMS error and the range used aga
 terms; per foot the contact agreement, stance shares, touchdown counts and the touchdown lag against the reference's touchdown; the
 reward's contact term; and the planar speed error (`reduce_imitation`).  The Joystick task with the imitation reward on: the duck, or
 another robot with `--reference_motion`.  Without the flag nothing changes.
+
+Command schedules and the step response (walk to stop, forward to turn: how fast does the policy follow a NEW command? -- what changing the
+command with the keyboard shows in that viewer while the robot walks):
+
+    python -m open_duck_playground_amd.track --checkpoint <ckpt> --sequence "0: 0 0 0 | 150: 0.15 0 0 | 400: 0 0 0.5 | 700: 0 0 0"
+    python -m open_duck_playground_amd.track --checkpoint <ckpt> --grid vx=-0.15:0.15:3,wz=-1:1:3 --then 0 0 0 --switch_at 300 --output transitions.json
+
+`--sequence` (repeatable) is one schedule of up to 8 segments, `start_step: command` each, the first at step 0; `--then V...` (repeatable)
+with `--switch_at N` crosses every `--command` / `--grid` row with every then-command into two-segment schedules, from-commands outermost:
+the transition matrix of a grid.  Every schedule gets `--envs_per_command` envs and one row of the report.  Two launches join the captured
+step: `odk_command_schedule_apply` before the env step writes each env's row of the bound command tensor from the schedule table -- its
+clock is the tracking accumulator's step count, so there is no other counter -- and `odk_response_accumulate`, before the tracking
+accumulator, follows each segment.  A schedule row keeps every key above: `command` is segment 0's, and the velocity statistics are against
+the command in force at each step (the tracking accumulator reads the row the step read).  It gains "schedule" (the segments as given)
+and "segments": per segment the samples, mean velocities and RMS errors, the fall rate among the envs that entered it, the response time
+(the first sample within `--response_tolerance` of the new command), the settle time (the last sample outside it) and the settled share,
+the error peaks after the response, the overshoot per axis past the command in the direction of the change, and the steady-state error over
+the samples later than `--response_tail_after` steps into the segment (`reduce_response`).  `--gait` and `--imitation_report` combine with
+schedules, one object per schedule row; pushes and `--posture` do not (their figures assume one command per episode), and the response
+figures cover vx, vy and wz although all seven entries of a segment are applied.  Without `--sequence` / `--then` nothing changes.
 """
 from __future__ import annotations
 
@@ -95,6 +115,11 @@ from .engine import (IMIT_NACC, IMIT_SAMPLES as I_SAMPLES, IMIT_GATED as I_GATED
                      IMIT_LAG_ABS_SUM as I_LAG_ABS, IMIT_POS_ERR_SUM as I_POS_ERR, IMIT_POS_ERR_SQ as I_POS_ERR_SQ, IMIT_POS_ERR_PEAK as I_POS_ERR_PEAK,
                      IMIT_VEL_ERR_SQ as I_VEL_ERR_SQ, IMIT_RANGE_MIN as I_RANGE_MIN, IMIT_RANGE_MAX as I_RANGE_MAX, IMIT_REF_RANGE_MIN as I_REF_RANGE_MIN,
                      IMIT_REF_RANGE_MAX as I_REF_RANGE_MAX)      # ODK_IMIT_*
+
+from .engine import (SCHED_MAX_SEGMENTS, SCHED_SEG_FLOATS, SCHED_NEVER, RESP_NACC, RESP_STRIDE, RESP_ENTERED as R_ENTERED, RESP_SAMPLES as R_SAMPLES,
+                     RESP_FELL as R_FELL, RESP_STEPS_TO_FALL as R_STEPS_TO_FALL, RESP_FIRST_IN as R_FIRST_IN, RESP_LAST_OFF as R_LAST_OFF,
+                     RESP_PEAK_LIN_ERR as R_PEAK_LIN, RESP_PEAK_ANG_ERR as R_PEAK_ANG, RESP_SUM as R_SUM, RESP_SQERR as R_SQERR,
+                     RESP_OVERSHOOT as R_OVERSHOOT, RESP_TAIL_SAMPLES as R_TAIL_SAMPLES, RESP_TAIL_SUM as R_TAIL_SUM)      # ODK_SCHED_* / ODK_RESP_*
 
 COMMAND_KEYS = ("vx", "vy", "wz", "neck_pitch", "head_pitch", "head_yaw", "head_roll")   # the order of cmd_range (include/odk.h)
 NACC = 12
@@ -214,6 +239,192 @@ def cell_blocks(commands: Sequence[Sequence[float]], pushes: Sequence[Dict], env
 
 def _mean_or_none(x: np.ndarray) -> Optional[float]:
     return float(x.mean()) if x.size else None
+
+
+DEFAULT_SWITCH_AT = 300
+DEFAULT_RESPONSE_TAIL_AFTER = 100      # BUILD-DEFINED default: two seconds into a segment the transient counts as over
+
+
+def parse_sequence(text: str) -> List[Dict]:
+    """`--sequence "0: 0 0 0 | 150: 0.15 0 0 | 400: 0 0 0.5"` -> one schedule: a list of segments {start_step, command}, segments apart
+    by `|`, each `start_step: vx vy wz [neck_pitch head_pitch head_yaw head_roll]` with the command padded as `command_row` does.  Syntax
+    only (ValueError); what a schedule must satisfy is `check_schedule`'s."""
+    segs = []
+    for part in str(text).split("|"):
+        start, colon, values = part.partition(":")
+        if not colon or not start.strip():
+            raise ValueError(f"--sequence: {part.strip()!r} is not `start_step: vx vy wz [...]`")
+        try:
+            at = float(start)
+        except ValueError:
+            raise ValueError(f"--sequence: the start step {start.strip()!r} of {part.strip()!r} is not a number")
+        if not np.isfinite(at) or at != int(at):
+            raise ValueError(f"--sequence: the start step {start.strip()!r} of {part.strip()!r} is not a whole number of steps")
+        try:
+            cmd = command_row(values.split())
+        except ValueError as err:
+            raise ValueError(f"--sequence: segment {part.strip()!r}: {err}")
+        segs.append(dict(start_step=int(at), command=cmd))
+    return segs
+
+
+def check_schedule(schedule: Sequence[Dict], episode_length: Optional[int] = None) -> None:
+    """What a schedule must satisfy before it reaches the device (the kernels cannot report it): 1 to 8 segments, the first at step 0,
+    starts strictly increasing and below `episode_length` (when given), every command 7 finite values.  ValueError with the reason."""
+    if not 1 <= len(schedule) <= SCHED_MAX_SEGMENTS:
+        raise ValueError(f"a schedule has 1 to {SCHED_MAX_SEGMENTS} segments, this one has {len(schedule)}")
+    if int(schedule[0]["start_step"]) != 0:
+        raise ValueError(f"the first segment of a schedule starts at step 0 (the command the episode begins with), not at {schedule[0]['start_step']}")
+    for i, seg in enumerate(schedule):
+        at = int(seg["start_step"])
+        if i and at <= int(schedule[i - 1]["start_step"]):
+            raise ValueError(f"the start steps of a schedule increase: segment {i} starts at {at}, segment {i - 1} at {schedule[i - 1]['start_step']}")
+        if episode_length is not None and at >= int(episode_length):
+            raise ValueError(f"segment {i} starts at step {at}, at or beyond the episode's {int(episode_length)} steps (--episode_length): it would never run")
+        cmd = np.asarray(seg["command"], np.float64).reshape(-1)
+        with np.errstate(over="ignore"):      # a value past float32's range becomes inf there, which is the finding
+            fits = cmd.shape == (7,) and bool(np.all(np.isfinite(cmd.astype(np.float32))))
+        if not fits:
+            raise ValueError(f"the command of segment {i} is not 7 finite values: {list(seg['command'])}")
+
+
+def then_schedules(commands: Sequence[Sequence[float]], thens: Sequence[Sequence[float]], switch_at: int) -> List[List[Dict]]:
+    """Every from-command crossed with every `--then` command: two-segment schedules that switch at step `switch_at`, the from-commands
+    outermost (schedule c * len(thens) + k goes from commands[c] to thens[k]), like `cell_blocks`: the transition matrix of a grid."""
+    return [[dict(start_step=0, command=[float(x) for x in c]), dict(start_step=int(switch_at), command=[float(x) for x in t])]
+            for c in commands for t in thens]
+
+
+def schedule_table(schedules: Sequence[Sequence[Dict]]) -> np.ndarray:
+    """float32 [nsched, nseg, 8] for `Batch.command_schedule_apply`: nseg is the longest schedule's segment count, a row is start_step and
+    the 7 command entries, and the unused trailing segments of a shorter schedule start at SCHED_NEVER (zero commands).  Every schedule
+    is checked (`check_schedule`)."""
+    if not schedules:
+        raise ValueError("no schedule given")
+    for s in schedules:
+        check_schedule(s)
+    nseg = max(len(s) for s in schedules)
+    tab = np.zeros((len(schedules), nseg, SCHED_SEG_FLOATS), np.float32)
+    tab[:, :, 0] = SCHED_NEVER
+    for i, s in enumerate(schedules):
+        for k, seg in enumerate(s):
+            tab[i, k, 0] = float(int(seg["start_step"]))
+            tab[i, k, 1:] = np.asarray(seg["command"], np.float32)
+    return tab
+
+
+def schedule_blocks(nsched: int, envs_per_schedule: int) -> np.ndarray:
+    """int32 [nsched * envs_per_schedule], the env-to-schedule map: schedule s drives envs s * envs_per_schedule .. (s + 1) *
+    envs_per_schedule - 1 (the blocks of `command_blocks`)."""
+    return np.repeat(np.arange(int(nsched), dtype=np.int32), int(envs_per_schedule))
+
+
+def reduce_response(acc: np.ndarray, schedules: Sequence[Sequence[Dict]], envs_per_block: int, dt: float) -> List[List[Dict]]:
+    """Per schedule (a block of `envs_per_block` envs, in `schedule_blocks` order) the "segments" list of its row, from the response
+    accumulator ([nenv, 8 * 24], include/odk.h ODK_RESP_*), in float64.  Per segment: `start_step`, `command`; `envs_entered`, the envs
+    whose first episode ran a step in the segment; `velocity_samples` (steps that did not end the episode), pooled over the block;
+    `mean_*` / `rms_error_*` of vx, vy, wz over those samples against the segment's command; `fall_rate`, the share of the entered envs
+    whose first episode ended in the segment by falling, and `mean_steps_to_fall` from the segment's first step to the fall, counting
+    both; `responded_fraction`, the share of the envs with a sample that came inside both tolerances at some sample, and
+    `response_time_s`, the mean over those envs of the steps to the first such sample, times dt; `settled_fraction`, the share of the envs
+    with a sample whose last sample was inside (LAST_OFF < SAMPLES), and `settle_time_s`, the mean over those envs of the steps to the
+    last sample outside (0: never outside), times dt; `peak_lin_error` / `peak_ang_error`, the largest planar / yaw error any env of the
+    block showed from its first sample inside onwards; `overshoot_v*`, the mean over the envs with a sample of the farthest the axis went
+    past the command in the direction of the change (0 for an axis whose command did not change); `steady_state_error_v*`, the mean
+    velocity over the samples later than `--response_tail_after` steps into the segment, minus the command.  A figure over an empty set
+    is None: a segment without a sample has no means, one nobody responded to no response time, one without tail samples no steady state."""
+    acc = np.asarray(acc, np.float64).reshape(-1, RESP_NACC)
+    E, dt = int(envs_per_block), float(dt)
+    out = []
+    for s, sched in enumerate(schedules):
+        segs = []
+        for k, seg in enumerate(sched):
+            blk = acc[s * E:(s + 1) * E, k * RESP_STRIDE:(k + 1) * RESP_STRIDE]
+            cmd = [float(x) for x in seg["command"]]
+            entered = blk[:, R_ENTERED] != 0
+            n = blk[:, R_SAMPLES]
+            live = n > 0
+            samples = float(n.sum())
+            fell = entered & (blk[:, R_FELL] != 0)
+            responded = live & (blk[:, R_FIRST_IN] > 0)
+            settled = live & (blk[:, R_LAST_OFF] < n)
+            tail = float(blk[:, R_TAIL_SAMPLES].sum())
+            g = dict(start_step=int(seg["start_step"]), command=cmd, envs_entered=int(entered.sum()), velocity_samples=int(round(samples)))
+            for a, axis in enumerate(COMMAND_KEYS[:3]):
+                g["mean_" + axis] = float(blk[:, R_SUM + a].sum() / samples) if samples > 0 else None
+            for a, axis in enumerate(COMMAND_KEYS[:3]):
+                g["rms_error_" + axis] = float(np.sqrt(blk[:, R_SQERR + a].sum() / samples)) if samples > 0 else None
+            g.update(
+                fall_rate=float(fell.sum() / entered.sum()) if entered.any() else None,
+                mean_steps_to_fall=_mean_or_none(blk[fell, R_STEPS_TO_FALL]),
+                responded_fraction=float(responded.sum() / live.sum()) if live.any() else None,
+                response_time_s=float(blk[responded, R_FIRST_IN].mean() * dt) if responded.any() else None,
+                settle_time_s=float(blk[settled, R_LAST_OFF].mean() * dt) if settled.any() else None,
+                settled_fraction=float(settled.sum() / live.sum()) if live.any() else None,
+                peak_lin_error=float(blk[responded, R_PEAK_LIN].max()) if responded.any() else None,
+                peak_ang_error=float(blk[responded, R_PEAK_ANG].max()) if responded.any() else None)
+            for a, axis in enumerate(COMMAND_KEYS[:3]):
+                g["overshoot_" + axis] = float(blk[live, R_OVERSHOOT + a].mean()) if live.any() else None
+            for a, axis in enumerate(COMMAND_KEYS[:3]):
+                g["steady_state_error_" + axis] = float(blk[:, R_TAIL_SUM + a].sum() / tail - cmd[a]) if tail > 0 else None
+            segs.append(g)
+        out.append(segs)
+    return out
+
+
+SEGMENT_KEYS = ("start_step", "command", "envs_entered", "velocity_samples", "mean_vx", "mean_vy", "mean_wz", "rms_error_vx", "rms_error_vy",
+                "rms_error_wz", "fall_rate", "mean_steps_to_fall", "responded_fraction", "response_time_s", "settle_time_s", "settled_fraction",
+                "peak_lin_error", "peak_ang_error", "overshoot_vx", "overshoot_vy", "overshoot_wz", "steady_state_error_vx",
+                "steady_state_error_vy", "steady_state_error_wz")
+SCHEDULE_ROW_KEYS = ("schedule", "segments")
+
+
+def response_tolerance(args) -> tuple:
+    """`--response_tolerance LIN ANG` as odk_response_accumulate accepts it: two finite numbers >= 0; SystemExit otherwise."""
+    tol = tuple(float(x) for x in getattr(args, "response_tolerance", None) or DEFAULT_PUSH_TOLERANCE)
+    if len(tol) != 2 or not all(np.isfinite(x) and x >= 0 for x in tol):
+        raise SystemExit(f"--response_tolerance LIN ANG: two finite errors >= 0 (m/s, rad/s), got {list(tol)}")
+    return tol
+
+
+def schedules_from_args(args) -> Optional[List[List[Dict]]]:
+    """The schedules the command line asks for -- one per `--sequence`, or every `--command` / `--grid` row crossed with every `--then` --
+    or None without a schedule flag.  SystemExit with the reason for a schedule that cannot run (`check_schedule`, against
+    `--episode_length`), for `--then` without a from-command, for `--sequence` next to `--command` / `--grid` / `--then`, and for schedules next
+    to pushes or `--posture`, whose figures assume one command per episode."""
+    sequences, thens = getattr(args, "sequence", None) or [], getattr(args, "then", None) or []
+    if not sequences and not thens:
+        return None
+    given = bool(getattr(args, "command", None)) or bool(getattr(args, "grid", None))
+    if sequences and (given or thens):
+        raise SystemExit("--sequence is a whole schedule of its own: it does not combine with --command, --grid or --then (write the commands into the sequence)")
+    if thens and not given:
+        raise SystemExit("--then switches away from a command: give the from-commands with --command or --grid")
+    if getattr(args, "push", None) or getattr(args, "push_grid", None):
+        raise SystemExit("command schedules (--sequence / --then) do not combine with --push / --push_grid: the push figures assume one command per episode")
+    if getattr(args, "posture", False):
+        raise SystemExit("command schedules (--sequence / --then) do not combine with --posture: its settle times assume one command per episode "
+                         "(the response figures cover vx, vy and wz)")
+    try:
+        if sequences:
+            schedules = [parse_sequence(text) for text in sequences]
+        else:
+            commands = [command_row(c) for c in (getattr(args, "command", None) or [])]
+            if getattr(args, "grid", None):
+                commands += parse_grid(args.grid)
+            switch_at = int(getattr(args, "switch_at", DEFAULT_SWITCH_AT))
+            schedules = then_schedules(commands, [command_row(t) for t in thens], switch_at)
+        for i, sched in enumerate(schedules):
+            try:
+                check_schedule(sched, int(args.episode_length))
+            except ValueError as err:
+                raise ValueError(f"schedule {i}: {err}")
+    except ValueError as err:
+        raise SystemExit(str(err))
+    response_tolerance(args)
+    if int(getattr(args, "response_tail_after", DEFAULT_RESPONSE_TAIL_AFTER)) < 0:
+        raise SystemExit("--response_tail_after is a number of steps: >= 0")
+    return schedules
 
 
 def reduce_pushes(acc: np.ndarray, commands: Sequence[Sequence[float]], pushes: Sequence[Dict], envs_per_cell: int, dt: float) -> List[Dict]:
@@ -530,7 +741,8 @@ def reduce_tracking(acc: np.ndarray, commands: Sequence[Sequence[float]], envs_p
     """The per-command rows of the report from the accumulator ([nenv, 12], include/odk.h ODK_TRACK_*).  Velocity statistics are over
     the velocity samples of the block's envs (the steps of their first episode that did not end it), pooled; the fall rate is the
     share of the block's envs whose first episode ended by falling; the episode reward is the mean over envs of their first episode's
-    reward sum."""
+    reward sum.  Under a command schedule the block is a schedule's, `commands` holds segment 0's commands, and the errors are against the
+    command in force at each step (the accumulator reads the bound row as the step read it)."""
     acc = np.asarray(acc, np.float64).reshape(-1, NACC)
     E = int(envs_per_command)
     rows = []
@@ -614,11 +826,15 @@ class Tracker:
     With `gait=True` it owns a gait accumulator and the model's torque limits on the device, and the step gains `odk_gait_accumulate`,
     before the tracking accumulator.  With `posture=True` it owns a posture accumulator, and the step gains `odk_posture_accumulate`
     (head error tolerance `posture_tolerance`, radians), next to gait's launch.  With `imitation=True` it owns an imitation accumulator, and
-    the step gains `odk_imitation_accumulate` there too (`period_steps`: the reference motion's, `imitation_joint_info`)."""
+    the step gains `odk_imitation_accumulate` there too (`period_steps`: the reference motion's, `imitation_joint_info`).  With `schedule`
+    -- a dict of `table` (`schedule_table`), `map` (`schedule_blocks`), `tolerance` (lin, ang) and `tail_after` -- the commands change inside
+    the captured step: the Tracker keeps the table and the map on the device and owns a response accumulator; `reset` zeroes the
+    accumulators and issues `odk_command_schedule_apply` once before the env's reset, and the step issues it again before the env step and
+    `odk_response_accumulate` next to the other accumulators.  The bound command tensor is then written by the Tracker."""
 
     def __init__(self, env, net, use_graph: bool = True, kicks=None, push_at: int = DEFAULT_PUSH_AT, push_tolerance=DEFAULT_PUSH_TOLERANCE,
                  gait: bool = False, posture: bool = False, posture_tolerance: float = DEFAULT_POSTURE_TOLERANCE,
-                 imitation: bool = False):
+                 imitation: bool = False, schedule: Optional[Dict] = None):
         import torch
         self.env, self.net, self.torch = env, net, torch
         b = env.batch
@@ -642,6 +858,13 @@ class Tracker:
         if imitation:
             self.period_steps = imitation_joint_info(env)[2]
             self.imitation_acc = torch.zeros(env.num_envs, IMIT_NACC, device=b.obs.device)
+        self.sched = self.sched_map = self.response_acc = None
+        if schedule is not None:
+            self.sched = torch.as_tensor(np.ascontiguousarray(schedule["table"], np.float32)).to(b.obs.device).contiguous()
+            self.sched_map = torch.as_tensor(np.ascontiguousarray(schedule["map"], np.int32)).to(b.obs.device).contiguous()
+            self.response_tolerance = tuple(float(x) for x in schedule.get("tolerance", DEFAULT_PUSH_TOLERANCE))
+            self.response_tail_after = int(schedule.get("tail_after", DEFAULT_RESPONSE_TAIL_AFTER))
+            self.response_acc = torch.zeros(env.num_envs, RESP_NACC, device=b.obs.device)
         from .ppo.learner import fused_policy
         self.fp = fused_policy(net, env.num_envs)
         self.use_graph = use_graph
@@ -658,6 +881,8 @@ class Tracker:
         if self.kicks is not None:                  # device ops only: the same graph replay serves every step
             self.counter.add_(1)
             self.torch.mul(self.kicks, (self.counter == self.push_at).to(self.kicks.dtype), out=self.push_buf)
+        if self.sched is not None:
+            b.command_schedule_apply(self.sched, self.sched_map, self.acc)      # the command of the step about to run; the clock is acc's STEPS
         b.step(act)                                 # Joystick.step without the State wrapper (nothing here reads it)
         if self.kicks is not None:
             b.push_accumulate(self.push_acc, self.acc, *self.push_tolerance)      # before the tracking accumulator sets ENDED
@@ -667,9 +892,15 @@ class Tracker:
             b.posture_accumulate(self.posture_acc, self.acc, self.posture_tolerance)
         if self.imitation_acc is not None:
             b.imitation_accumulate(self.imitation_acc, self.acc, self.period_steps)
+        if self.response_acc is not None:
+            b.response_accumulate(self.response_acc, self.acc, self.sched, self.sched_map, *self.response_tolerance, self.response_tail_after)
         b.tracking_accumulate(self.acc)
 
     def reset(self, seed: int):
+        if self.sched is not None:                  # the reset must find segment 0's command: a zeroed clock, one apply launch, then the env
+            self.acc.zero_()
+            self.response_acc.zero_()
+            self.env.batch.command_schedule_apply(self.sched, self.sched_map, self.acc)
         self.env.reset(int(seed))
         self.acc.zero_()
         if self.kicks is not None:
@@ -703,9 +934,13 @@ class Tracker:
 
 def run(args, out=sys.stdout) -> Dict:
     import torch
-    commands = [command_row(c) for c in (args.command or [])]
-    if args.grid:
-        commands += parse_grid(args.grid)
+    schedules = schedules_from_args(args)      # None without --sequence / --then; refusals before any batch work
+    if schedules is not None:
+        commands = [list(s[0]["command"]) for s in schedules]      # a schedule row's `command` is segment 0's
+    else:
+        commands = [command_row(c) for c in (args.command or [])]
+        if args.grid:
+            commands += parse_grid(args.grid)
     if not commands:
         raise SystemExit("give at least one --command or a --grid")
     pushes = [push_row(p) for p in (getattr(args, "push", None) or [])]
@@ -750,6 +985,13 @@ def run(args, out=sys.stdout) -> Dict:
         env.set_commands(cmd)
         tr = Tracker(env, net, kicks=torch.from_numpy(kicks_np).to(dev), push_at=push_at, push_tolerance=tol, gait=gait, posture=posture,
                      posture_tolerance=posture_tol, imitation=imitation)
+    elif schedules is not None:
+        resp_tol = response_tolerance(args)
+        tail_after = int(getattr(args, "response_tail_after", DEFAULT_RESPONSE_TAIL_AFTER))
+        cmd = torch.from_numpy(command_blocks(commands, E)).to(dev)      # segment 0's; the Tracker's apply launch rewrites it every step
+        env.set_commands(cmd)
+        tr = Tracker(env, net, gait=gait, imitation=imitation,
+                     schedule=dict(table=schedule_table(schedules), map=schedule_blocks(len(schedules), E), tolerance=resp_tol, tail_after=tail_after))
     else:
         cmd = torch.from_numpy(command_blocks(commands, E)).to(dev)
         env.set_commands(cmd)
@@ -774,10 +1016,15 @@ def run(args, out=sys.stdout) -> Dict:
         gait_acc = tr.gait_acc.cpu().numpy() if gait else None
         posture_acc = tr.posture_acc.cpu().numpy() if posture else None
         imitation_acc = tr.imitation_acc.cpu().numpy() if imitation else None
+        response_acc = tr.response_acc.cpu().numpy() if schedules is not None else None
     rows = reduce_tracking(acc, commands, max(len(pushes), 1) * E)
     if pushes:
         for row, extra in zip(rows, reduce_pushes(push_acc, commands, pushes, E, float(env.dt))):
             row.update(extra)
+    if schedules is not None:
+        for row, sched, segs in zip(rows, schedules, reduce_response(response_acc, schedules, E, float(env.dt))):
+            row["schedule"] = [dict(start_step=int(seg["start_step"]), command=[float(x) for x in seg["command"]]) for seg in sched]
+            row["segments"] = segs
     if gait:
         for row, g in zip(rows, reduce_gait(gait_acc, commands, max(len(pushes), 1) * E, float(env.dt), env.mj_model)):
             row["gait"] = g
@@ -807,6 +1054,10 @@ def run(args, out=sys.stdout) -> Dict:
     if pushes:
         settings.update(push=getattr(args, "push", None), push_grid=getattr(args, "push_grid", None), push_at=push_at,
                         push_tolerance=list(tol), pushes_per_command=len(pushes))
+    if schedules is not None:
+        settings.update(sequence=getattr(args, "sequence", None), then=getattr(args, "then", None),
+                        switch_at=int(getattr(args, "switch_at", DEFAULT_SWITCH_AT)) if getattr(args, "then", None) else None,
+                        response_tolerance=list(resp_tol), response_tail_after=tail_after, schedules=len(schedules))
     if gait:
         settings.update(gait=True)
     if posture:
@@ -851,6 +1102,20 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--push_at", type=int, default=DEFAULT_PUSH_AT, help="the step of the first episode (0 = its first) at which the kick is applied, once")
     p.add_argument("--push_tolerance", nargs=2, type=float, default=list(DEFAULT_PUSH_TOLERANCE), metavar=("LIN", "ANG"),
                    help="recovery: planar velocity error (m/s) and yaw-rate error (rad/s) above which a step counts as not recovered (BUILD-DEFINED defaults)")
+    p.add_argument("--sequence", type=str, action="append", metavar="SCHEDULE",
+                   help="a command schedule: \"0: 0 0 0 | 150: 0.15 0 0 | 400: 0 0 0.5\" -- segments apart by |, each `start_step: vx vy wz "
+                        "[neck_pitch head_pitch head_yaw head_roll]`, the first at step 0, at most 8; repeat for more schedules.  Each is one row of "
+                        "the report with a \"segments\" list: per segment the response time, settle time, overshoot, steady-state error and fall rate "
+                        "after the change.  Not with --command / --grid / --then, pushes or --posture")
+    p.add_argument("--then", nargs="+", type=float, action="append", metavar="V",
+                   help="switch every --command / --grid row to this command (vx vy wz [...]) at step --switch_at; repeat for more targets: every "
+                        "(from, then) pair is a two-segment schedule and a row of the report, from-commands outermost")
+    p.add_argument("--switch_at", type=int, default=DEFAULT_SWITCH_AT, help="the step of the first episode at which --then takes over")
+    p.add_argument("--response_tolerance", nargs=2, type=float, default=list(DEFAULT_PUSH_TOLERANCE), metavar=("LIN", "ANG"),
+                   help="response: planar velocity error (m/s) and yaw-rate error (rad/s) within which a step counts as following the segment's "
+                        "command (BUILD-DEFINED defaults, --push_tolerance's); read with schedules only")
+    p.add_argument("--response_tail_after", type=int, default=DEFAULT_RESPONSE_TAIL_AFTER, metavar="STEPS",
+                   help="steady state: the samples later than this many steps into a segment give its steady-state error; read with schedules only")
     p.add_argument("--gait", action="store_true",
                    help="add a \"gait\" object to every command row (and push cell): duty factor, double support, flight, step frequency, swing time and "
                         "foot slip per foot, root height, roll/pitch rate RMS, action rate, mean |torque * joint speed| and per-actuator torque RMS / peak "

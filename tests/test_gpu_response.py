@@ -1,0 +1,605 @@
+"""GPU checks of command schedules (odk_command_schedule_apply / Batch.command_schedule_apply), the step-response accumulator
+(odk_response_accumulate / Batch.response_accumulate) and `track --sequence` / `--then`: the apply launch on synthetic clocks, every slot
+of the accumulator bit for bit against a numpy float32 restatement, the env step following the schedule, the report of a real run against
+the same restatement over the recorded outputs, eager against graph, the one-segment schedule against `--command`, a run without
+schedule flags, and the refusals.
+
+Small shapes on purpose.  The second command-buffer case of the apply test, rows 9 floats apart, goes through the C function: the C
+binding takes any row stride >= 7, `Batch.bind_commands` only [nenv, 7]."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ODK_ERR_INVALID = -1         # include/odk.h
+# include/odk.h ODK_RESP_* / ODK_SCHED_* / ODK_TRACK_*
+ENTERED, SAMPLES, FELL, STEPS_TO_FALL, FIRST_IN, LAST_OFF, PEAK_LIN, PEAK_ANG, SUM, SQERR, OVERSHOOT, TAIL_SAMPLES, TAIL_SUM = 0, 1, 2, 3, 4, 5, 6, 7, 8, 11, 14, 17, 18
+STRIDE, NACC, NEVER = 24, 192, np.float32(1.0e9)
+T_ENDED, T_STEPS, T_NACC = 0, 1, 12
+f32 = np.float32
+
+
+def segment_of(S, t):
+    """the last segment of schedule row S [nseg, 8] whose start_step is <= t"""
+    k = 0
+    for i in range(1, len(S)):
+        if S[i, 0] <= t:
+            k = i
+    return k
+
+
+def table(*schedules):
+    """[nsched, nseg, 8] float32 from lists of (start, 7 floats), padded with NEVER"""
+    nseg = max(len(s) for s in schedules)
+    tab = np.zeros((len(schedules), nseg, 8), f32)
+    tab[:, :, 0] = NEVER
+    for i, s in enumerate(schedules):
+        for k, (at, cmd) in enumerate(s):
+            tab[i, k, 0] = at
+            tab[i, k, 1:] = f32(cmd)
+    return tab
+
+
+def _duck(n):
+    from open_duck_playground_amd import joystick
+    return joystick.Joystick(task="flat_terrain", num_envs=n)
+
+
+def test_schedule_apply_on_synthetic_clocks():
+    """300 duck envs (two 256-thread blocks), schedules of 1, 2 and 8 segments, clocks at, just before and just after every boundary and
+    far beyond the last, some rows ENDED (they get the command of step STEPS - 1, the one that ended them), a few map entries outside the
+    table (clamped to its first / last row).  Every row equals the expected segment's command bit for bit; with rows 9 floats apart the
+    columns beyond 6 keep theirs; a zeroed accumulator gives segment 0 everywhere."""
+    import torch
+    from open_duck_playground_amd import engine
+    n = 300
+    rng = np.random.default_rng(11)
+    cmds = rng.uniform(-1, 1, (11, 7)).astype(f32)
+    bounds8 = [0, 3, 4, 10, 11, 50, 1000, 70000]
+    tab = table([(0, cmds[0])], [(0, cmds[1]), (5, cmds[2])], [(b, cmds[3 + k]) for k, b in enumerate(bounds8)])
+    cand = sorted({0.0, 1.0e6} | {float(b + d) for b in bounds8[1:] + [5] for d in (-1, 0, 1)})
+    assert 3 * len(cand) * 2 <= 290
+    smap = np.array([e % 3 for e in range(n)], np.int32)
+    smap[290:] = [-1, 7, 3, -5, 100, -1, 7, 3, -5, 100]                      # outside 0 .. 2: clamped, never read past the table
+    tacc = np.zeros((n, T_NACC), f32)
+    tacc[:, T_STEPS] = [cand[(e // 3) % len(cand)] for e in range(n)]
+    tacc[:, T_ENDED] = [1.0 if (e // (3 * len(cand))) % 2 == 1 and tacc[e, T_STEPS] >= 1 else 0.0 for e in range(n)]
+    tacc[:, 2:] = rng.normal(size=(n, T_NACC - 2)).astype(f32)                # the other slots are not the launch's business
+    assert tacc[:, T_ENDED].sum() > 40 and (tacc[:, T_ENDED] == 0).sum() > 100
+    want = np.zeros((n, 7), f32)
+    for e in range(n):
+        S = tab[min(max(int(smap[e]), 0), 2)]
+        t = tacc[e, T_STEPS] - 1 if tacc[e, T_ENDED] != 0 else tacc[e, T_STEPS]
+        want[e] = S[segment_of(S, t), 1:]
+    # every segment of every schedule is somebody's, and an ENDED row at a boundary differs from a live one
+    assert {tuple(w) for w in want} == {tuple(c) for c in cmds}
+
+    env = _duck(n)
+    b = env.batch
+    tab_d, smap_d, tacc_d = torch.tensor(tab, device="cuda"), torch.tensor(smap, device="cuda"), torch.tensor(tacc, device="cuda")
+    guard = torch.full((n + 2, 7), 9.0, device="cuda")                       # rows past the batch: the second block's idle threads leave them
+    cmd = guard[:n]
+    b.bind_commands(cmd)
+    b.command_schedule_apply(tab_d, smap_d, tacc_d)
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(cmd.cpu().numpy().view(np.int32), want.view(np.int32))
+    np.testing.assert_array_equal(guard[n:].cpu().numpy(), 9.0)
+    np.testing.assert_array_equal(tacc_d.cpu().numpy().view(np.int32), tacc.view(np.int32))      # the clock is read, not written
+    b.command_schedule_apply(tab_d, smap_d, torch.zeros(n, T_NACC, device="cuda"))
+    torch.cuda.synchronize()
+    seg0 = np.stack([tab[min(max(int(s), 0), 2), 0, 1:] for s in smap])
+    np.testing.assert_array_equal(cmd.cpu().numpy().view(np.int32), seg0.view(np.int32))
+
+    # rows 9 floats apart, through the C binding
+    L = engine.load_library()
+    wide = torch.full((n, 9), 9.0, device="cuda")
+    assert L.odk_batch_bind_commands(b._b, C.c_void_p(wide.data_ptr()), 9) == 0
+    rc = L.odk_command_schedule_apply(b._b, C.c_void_p(tab_d.data_ptr()), 3, 8, C.c_void_p(smap_d.data_ptr()), C.c_void_p(tacc_d.data_ptr()), b._stream())
+    assert rc == 0, L.odk_last_error().decode()
+    torch.cuda.synchronize()
+    got = wide.cpu().numpy()
+    np.testing.assert_array_equal(got[:, :7].view(np.int32), want.view(np.int32))
+    np.testing.assert_array_equal(got[:, 7:], 9.0)
+    b.bind_commands(None)
+    b.close()
+
+
+def restate(priv, done, trunc, tab, smap, nobs, lin_tol, ang_tol, tail_after, ended0=None, steps0=None):
+    """odk_response_accumulate restated in float32 over priv [T, n, npriv], done / trunc [T, n], with the tracking accumulator's clock
+    (STEPS, ENDED: odk_tracking_accumulate's rule) carried along.  Every operation is one float32 operation, in the kernel's order; the
+    planar error goes through float64.  Returns the [n, 192] accumulator and the final (steps, ended)."""
+    T, n = done.shape
+    A = np.zeros((n, NACC), f32)
+    ended = np.zeros(n, bool) if ended0 is None else np.array(ended0, bool)
+    steps = np.zeros(n, f32) if steps0 is None else np.array(steps0, f32)
+    lin_tol, ang_tol, tail_after = f32(lin_tol), f32(ang_tol), f32(tail_after)
+    one = f32(1)
+    for t in range(T):
+        for e in range(n):
+            if ended[e]:
+                continue
+            S = tab[min(max(int(smap[e]), 0), len(tab) - 1)]
+            seg = segment_of(S, steps[e])
+            B = A[e, seg * STRIDE:(seg + 1) * STRIDE]
+            k = f32(f32(steps[e] - S[seg, 0]) + one)
+            steps[e] += one
+            B[ENTERED] = one
+            if done[t, e] != 0:
+                ended[e] = True
+                if trunc[t, e] == 0:
+                    B[FELL], B[STEPS_TO_FALL] = one, k
+                continue
+            Cm = S[seg, 1:]
+            v = priv[t, e, [nobs + 9, nobs + 10, nobs + 2]]
+            ex, ey = np.float64(f32(v[0] - Cm[0])), np.float64(f32(v[1] - Cm[1]))
+            lin, ang = f32(np.sqrt(ex * ex + ey * ey)), f32(abs(f32(v[2] - Cm[2])))
+            B[SAMPLES] += one
+            if lin > lin_tol or ang > ang_tol:
+                B[LAST_OFF] = k
+            elif B[FIRST_IN] == 0:
+                B[FIRST_IN] = k
+            if B[FIRST_IN] != 0:
+                B[PEAK_LIN], B[PEAK_ANG] = max(B[PEAK_LIN], lin), max(B[PEAK_ANG], ang)
+            tail = k > tail_after
+            if tail:
+                B[TAIL_SAMPLES] += one
+            for a in range(3):
+                err = f32(v[a] - Cm[a])
+                B[SUM + a] = f32(B[SUM + a] + v[a])
+                B[SQERR + a] = f32(B[SQERR + a] + f32(err * err))
+                prev = S[seg - 1, 1 + a] if seg > 0 else f32(0)
+                d = f32(1) if Cm[a] > prev else (f32(-1) if Cm[a] < prev else f32(0))
+                B[OVERSHOOT + a] = max(B[OVERSHOOT + a], f32(err * d))
+                if tail:
+                    B[TAIL_SUM + a] = f32(B[TAIL_SUM + a] + v[a])
+    return A, steps, ended
+
+
+N_SYN, T_SYN = 64, 40
+LIN_TOL, ANG_TOL, TAIL_AFTER = 0.0625, 0.25, 4      # exact in float32, as the commands below: command + tolerance is exact, so an error can equal it
+PRE_ENDED = 63                                      # an env past its first episode before the first launch: its row keeps what it holds
+
+
+def synthetic_inputs(nobs, npriv):
+    """The host half of `synthetic`: 64 envs by 40 steps of seeded random privileged rows written straight into the batch's buffers (no
+    odk_step), three schedules with boundaries at steps 0, 7 and 19 (three, two and one segment; env e follows schedule e % 3), and per
+    step (in `synthetic`) the launches of a real evaluation step: apply, response, tracking -- so STEPS and ENDED evolve as in a run, and
+    the restatement carries the same clock.  The velocities of
+    env e are its command in force plus an error by pattern (e // 3) % 8:
+      0 never inside the tolerance;  1 inside at once, always;  2 per segment: inside for two samples, outside for two, inside again;
+      3 the planar and the yaw error EXACTLY the tolerances on odd steps of a segment (inside) and the next float32 error above on even ones;
+      4 a fall at step 10 (segment 1 of the three-segment schedule);  5 a truncation at step 25;  6 done at step 0: no sample at all;
+      7 errors of both signs around the tolerance: overshoot on every axis that changed, upwards and downwards.
+    Stray done flags after the end must not matter.  tail_after = 4: every segment has samples on both sides of it."""
+    n, T = N_SYN, T_SYN
+    c = lambda *v: list(v) + [0.0] * (7 - len(v))
+    tab = table([(0, c(0, 0, 0)), (7, c(0.125, -0.0625, 0)), (19, c(0.125, 0.0625, 0.5, 0.25))],      # vy: down, then up; vx, then wz unchanged
+                [(0, c(0.125, 0, 0.25)), (19, c(-0.125, 0, 0.25, 0, 0.5))],                          # vx changes downwards, wz does not change
+                [(0, c(0.0625, 0.03125, -0.25))])
+    smap = np.array([e % 3 for e in range(n)], np.int32)
+    pattern = np.array([(e // 3) % 8 for e in range(n)])
+    rng = np.random.default_rng(2024)
+    priv = rng.normal(0.0, 1.0, (T, n, npriv)).astype(f32)
+    end_at = np.where(pattern == 4, 10, np.where(pattern == 5, 25, np.where(pattern == 6, 0, T + 1)))
+    done = (rng.uniform(size=(T, n)) < 0.1).astype(f32)
+    for e in range(n):
+        done[:min(end_at[e], T), e] = 0.0
+        if end_at[e] < T:
+            done[end_at[e], e] = 1.0
+    trunc = (done * (pattern == 5)[None]).astype(f32)
+    lin32, ang32 = f32(LIN_TOL), f32(ANG_TOL)
+    for t in range(T):
+        for e in range(n):
+            S = tab[smap[e]]
+            seg = segment_of(S, t)                       # first episodes start together: while it lasts, the clock is t
+            k = t - int(S[seg, 0]) + 1
+            cx, cy, cw = S[seg, 1:4]
+            p = pattern[e]
+            if p == 0:
+                err = (0.2, 0.0, 0.0)
+            elif p == 2:
+                err = (0.2, 0.1, 0.4) if k in (3, 4) else tuple(rng.uniform(-0.02, 0.02, 3))
+            elif p == 3:
+                err = (lin32, 0.0, ang32)
+            elif p == 7:
+                err = tuple(rng.normal(0.0, 0.06, 2)) + (float(rng.normal(0.0, 0.2)),)
+            else:
+                err = tuple(rng.uniform(-0.02, 0.02, 3))
+            v = [f32(cx + f32(err[0])), f32(cy + f32(err[1])), f32(cw + f32(err[2]))]
+            if p == 3 and k % 2 == 0:                    # outside, by the least relative excess 2^-j whose float32 error exceeds the tolerance
+                v[0] = next(x for x in (f32(cx + f32(lin32 * (1 + 2.0 ** -j))) for j in range(23, 0, -1)) if f32(x - cx) > lin32)
+                v[2] = next(x for x in (f32(cw + f32(ang32 * (1 + 2.0 ** -j))) for j in range(23, 0, -1)) if f32(x - cw) > ang32)
+            priv[t, e, [nobs + 9, nobs + 10, nobs + 2]] = v
+    ended0 = np.zeros(n, bool); ended0[PRE_ENDED] = True
+    steps0 = np.zeros(n, f32); steps0[PRE_ENDED] = 3
+    want, steps, ended = restate(priv, done, trunc, tab, smap, nobs, LIN_TOL, ANG_TOL, TAIL_AFTER, ended0, steps0)
+    want[PRE_ENDED] = 7.0
+    return dict(priv=priv, done=done, trunc=trunc, want=want, steps=steps, ended=ended, tab=tab, smap=smap, pattern=pattern, end_at=end_at)
+
+
+@functools.lru_cache(maxsize=None)
+def synthetic():
+    """`synthetic_inputs` through the launches of an evaluation step, with a snapshot of the accumulator and of the command buffer after each."""
+    import torch
+    from open_duck_playground_amd import engine
+    n, T = N_SYN, T_SYN
+    env = _duck(n)
+    b = env.batch
+    r = synthetic_inputs(b.nobs, b.npriv)
+    priv, done, trunc, tab, smap = r["priv"], r["done"], r["trunc"], r["tab"], r["smap"]
+
+    guard = torch.full((n + 3, NACC), 7.0, device="cuda")          # rows past the batch stay as they are
+    acc = guard[:n]
+    acc[:PRE_ENDED].zero_()
+    tacc = torch.zeros(n, engine.TRACK_NACC, device="cuda")
+    tacc[PRE_ENDED, engine.TRACK_ENDED], tacc[PRE_ENDED, engine.TRACK_STEPS] = 1.0, 3.0
+    tab_d, smap_d = torch.tensor(tab, device="cuda"), torch.tensor(smap, device="cuda")
+    cmd = torch.full((n, 7), 9.0, device="cuda")
+    b.bind_commands(cmd)
+    priv_d, done_d, trunc_d = (torch.tensor(x, device="cuda") for x in (priv, done, trunc))
+    b.reward.zero_()
+    snaps, cmds = [], []
+    for t in range(T):
+        b.command_schedule_apply(tab_d, smap_d, tacc)
+        b.priv.copy_(priv_d[t]); b.done.copy_(done_d[t]); b.truncation.copy_(trunc_d[t])      # what the env step would have left
+        b.response_accumulate(acc, tacc, tab_d, smap_d, LIN_TOL, ANG_TOL, TAIL_AFTER)
+        b.tracking_accumulate(tacc)
+        snaps.append(acc.clone()); cmds.append(cmd.clone())
+    torch.cuda.synchronize()
+    res = dict(r, got=acc.cpu().numpy(), guard=guard[n:].cpu().numpy(), snaps=torch.stack(snaps).cpu().numpy(), cmds=torch.stack(cmds).cpu().numpy(),
+               tacc=tacc.cpu().numpy())
+    b.bind_commands(None)
+    b.close()
+    return res
+
+
+def test_every_slot_equals_a_float32_restatement_bit_for_bit():
+    r = synthetic()
+    got, want, tab, smap, pattern = r["got"], r["want"], r["tab"], r["smap"], r["pattern"]
+    np.testing.assert_array_equal(r["tacc"][:, T_STEPS], r["steps"])
+    np.testing.assert_array_equal(r["tacc"][:, T_ENDED] != 0, r["ended"])
+    for s, name in ((ENTERED, "ENTERED"), (SAMPLES, "SAMPLES"), (FELL, "FELL"), (STEPS_TO_FALL, "STEPS_TO_FALL"), (FIRST_IN, "FIRST_IN"), (LAST_OFF, "LAST_OFF"),
+                    (PEAK_LIN, "PEAK_LIN_ERR"), (PEAK_ANG, "PEAK_ANG_ERR"), (TAIL_SAMPLES, "TAIL_SAMPLES")):
+        np.testing.assert_array_equal(got[:, s::STRIDE].view(np.int32), want[:, s::STRIDE].view(np.int32), err_msg=name)
+    np.testing.assert_array_equal(got.view(np.int32), want.view(np.int32))          # the sums too: fixed order, float32, no fused multiply-add
+    np.testing.assert_array_equal(r["guard"], 7.0)
+
+    # the run covers what it claims to
+    blk = lambda e, seg: got[e, seg * STRIDE:(seg + 1) * STRIDE]
+    live = np.arange(N_SYN) != PRE_ENDED
+    seg_len = {0: [7, 12, 21], 1: [19, 21], 2: [40]}
+    for e in range(N_SYN):
+        if not live[e]:
+            continue
+        s, p = int(smap[e]), int(pattern[e])
+        nseg = len(seg_len[s])
+        assert np.all(got[e, nseg * STRIDE:] == 0.0)                                 # no block beyond the schedule's segments is touched
+        assert np.all(got[e].reshape(8, STRIDE)[:, 21:] == 0.0)                      # no slot lives there
+        for seg in range(nseg):
+            B, L = blk(e, seg), seg_len[s][seg]
+            if p == 0:
+                assert B[FIRST_IN] == 0 and B[LAST_OFF] == B[SAMPLES] == L and B[PEAK_LIN] == 0 and B[PEAK_ANG] == 0
+            if p == 1:
+                assert B[FIRST_IN] == 1 and B[LAST_OFF] == 0 and B[SAMPLES] == L and 0 < B[PEAK_LIN] < LIN_TOL
+                assert B[TAIL_SAMPLES] == L - TAIL_AFTER > 0
+            if p == 2:
+                assert B[FIRST_IN] == 1 and B[LAST_OFF] == 4 and B[PEAK_LIN] > LIN_TOL and B[PEAK_ANG] > ANG_TOL
+            if p == 3:      # exactly the tolerance is inside; one ulp above is outside
+                assert B[FIRST_IN] == 1 and B[LAST_OFF] == L - L % 2 and B[PEAK_LIN] > LIN_TOL and B[PEAK_ANG] > ANG_TOL
+    first = lambda p, s: next(e for e in range(N_SYN) if pattern[e] == p and smap[e] == s and live[e])
+    e = first(3, 2)                                                                   # a one-sample look at the tie itself
+    one = r["snaps"][0, e, :STRIDE]
+    assert one[FIRST_IN] == 1 and one[LAST_OFF] == 0 and one[PEAK_LIN] == f32(LIN_TOL) and one[PEAK_ANG] == f32(ANG_TOL)
+    e = first(4, 0)                                                                   # the fall at step 10: segment 1 (steps 7 ..), its 4th step
+    assert blk(e, 1)[FELL] == 1 and blk(e, 1)[STEPS_TO_FALL] == 4 and blk(e, 1)[SAMPLES] == 3 and blk(e, 0)[FELL] == 0 and blk(e, 2)[ENTERED] == 0
+    e = first(4, 1)
+    assert blk(e, 0)[FELL] == 1 and blk(e, 0)[STEPS_TO_FALL] == 11 and blk(e, 0)[SAMPLES] == 10
+    e = first(5, 0)                                                                   # the truncation at step 25: no fall
+    assert blk(e, 2)[ENTERED] == 1 and blk(e, 2)[FELL] == 0 and blk(e, 2)[STEPS_TO_FALL] == 0 and blk(e, 2)[SAMPLES] == 6
+    e = first(6, 0)                                                                   # done at step 0: entered, fell, no sample
+    assert blk(e, 0)[ENTERED] == 1 and blk(e, 0)[FELL] == 1 and blk(e, 0)[STEPS_TO_FALL] == 1 and np.all(blk(e, 0)[[SAMPLES, FIRST_IN, LAST_OFF] + list(range(6, 21))] == 0)
+    # overshoot: segment 0's unchanged axes keep 0; an axis that changed downwards overshoots below the command
+    e = first(7, 0)
+    assert np.all(blk(e, 0)[OVERSHOOT:OVERSHOOT + 3] == 0.0)                          # 0 0 0 from rest: nothing changed
+    assert blk(e, 1)[OVERSHOOT] > 0 and blk(e, 1)[OVERSHOOT + 1] > 0 and blk(e, 1)[OVERSHOOT + 2] == 0      # vx up, vy down, wz unchanged
+    assert blk(e, 2)[OVERSHOOT] == 0 and blk(e, 2)[OVERSHOOT + 1] > 0 and blk(e, 2)[OVERSHOOT + 2] > 0      # vx unchanged, vy up, wz up
+    e = first(7, 1)
+    assert blk(e, 1)[OVERSHOOT] > 0 and blk(e, 1)[OVERSHOOT + 1] == 0 and blk(e, 1)[OVERSHOOT + 2] == 0     # vx 0.125 -> -0.125
+    # the command buffer followed the schedules while the first episode ran, and froze where it ended
+    for t in (0, 6, 7, 18, 19, 39):
+        for e in (first(1, 0), first(1, 1), first(1, 2)):
+            S = tab[smap[e]]
+            np.testing.assert_array_equal(r["cmds"][t, e], S[segment_of(S, t), 1:])
+    e = first(4, 0)
+    np.testing.assert_array_equal(r["cmds"][39, e], tab[0, 1, 1:])                    # fell in segment 1: segment 2 never reached it
+
+
+def test_a_row_past_its_first_episode_keeps_its_bits():
+    r = synthetic()
+    snaps, end_at = r["snaps"].view(np.int32), r["end_at"]
+    checked = 0
+    for e in range(N_SYN):
+        if e == PRE_ENDED:
+            assert np.all(r["snaps"][:, e] == 7.0)
+            continue
+        for t in range(end_at[e] + 1, T_SYN):
+            np.testing.assert_array_equal(snaps[t, e], snaps[end_at[e], e], err_msg=f"env {e} step {t}")
+            checked += 1
+    assert checked > 300
+    # and within a live row only the block of the segment in force changes
+    e = next(e for e in range(N_SYN) if r["pattern"][e] == 1 and r["smap"][e] == 0)
+    for t in range(1, T_SYN):
+        seg = segment_of(r["tab"][0], t)
+        changed = np.nonzero((snaps[t, e] != snaps[t - 1, e]).reshape(8, STRIDE).any(1))[0]
+        assert list(changed) == [seg], (t, changed)
+
+
+def test_the_step_follows_the_schedule():
+    """16 duck envs, two schedules, 12 real steps with a boundary at step 5: after each step the record field `command` of every env, and
+    entries 6..12 of its observation, are the segment in force for that step -- the old command up to step 4, the new one from step 5."""
+    import torch
+    from open_duck_playground_amd import engine
+    n, T = 16, 12
+    tab = table([(0, [0.1, 0, 0, 0, 0, 0, 0]), (5, [0, 0.05, 0.5, 0.1, -0.2, 0.3, 0.05])], [(0, [-0.05, 0, -0.3, 0, 0, 0, 0]), (5, [0.0] * 7)])
+    smap = np.array([e % 2 for e in range(n)], np.int32)
+    env = _duck(n)
+    b = env.batch
+    off, cnt, kind = b.record_field("command")
+    assert cnt == 7 and kind == 0
+    tab_d, smap_d = torch.tensor(tab, device="cuda"), torch.tensor(smap, device="cuda")
+    tacc = torch.zeros(n, engine.TRACK_NACC, device="cuda")
+    cmd = torch.full((n, 7), 9.0, device="cuda")
+    b.bind_commands(cmd)
+    b.command_schedule_apply(tab_d, smap_d, tacc)
+    env.reset(4)
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(b.records()[:, off:off + 7], tab[smap, 0, 1:])                   # the reset found segment 0's command
+    act = torch.zeros(n, 14, device="cuda")
+    seen = set()
+    for t in range(T):
+        clock = tacc.cpu().numpy()
+        b.command_schedule_apply(tab_d, smap_d, tacc)
+        b.step(act)
+        b.tracking_accumulate(tacc)
+        torch.cuda.synchronize()
+        want = np.zeros((n, 7), f32)
+        for e in range(n):
+            tt = clock[e, T_STEPS] - 1 if clock[e, T_ENDED] != 0 else clock[e, T_STEPS]
+            seg = segment_of(tab[smap[e]], tt)
+            want[e] = tab[smap[e], seg, 1:]
+            if clock[e, T_ENDED] == 0:
+                assert clock[e, T_STEPS] == t and seg == (t >= 5)
+                seen.add((t, seg))
+        np.testing.assert_array_equal(b.records()[:, off:off + 7].view(np.int32), want.view(np.int32), err_msg=f"record, step {t}")
+        np.testing.assert_array_equal(b.obs[:, 6:13].cpu().numpy().view(np.int32), want.view(np.int32), err_msg=f"obs, step {t}")
+    assert {(4, 0), (5, 1), (11, 1)} <= seen
+    b.bind_commands(None)
+    b.close()
+
+
+ENV_SIZES = (101, 212, 14)      # the duck's observation / privileged / action sizes (Joystick)
+
+
+def _checkpoint(tmp_path, name="fresh.pt"):
+    import torch
+    from open_duck_playground_amd.ppo.networks import PPONetworks
+    from open_duck_playground_amd.ppo.train import save_checkpoint
+    torch.manual_seed(0)
+    ckpt = str(tmp_path / name)
+    save_checkpoint(ckpt, PPONetworks(*ENV_SIZES))
+    return ckpt
+
+
+def _run(track, monkeypatch, argv, eager=False):
+    """track.run with its Tracker caught; eager: no graph, and per step the step's privileged rows, done and truncation flags.
+    Returns (report, tracker, recording)."""
+    real = track.Tracker
+    caught, hist = [], []
+
+    class Caught(real):
+        def __init__(self, *a, **k):
+            if eager:
+                k["use_graph"] = False
+            super().__init__(*a, **k)
+            caught.append(self)
+
+        def step(self):
+            super().step()
+            if eager:
+                bb = self.env.batch
+                hist.append((bb.priv.cpu().numpy(), bb.done.cpu().numpy(), bb.truncation.cpu().numpy()))
+
+    monkeypatch.setattr(track, "Tracker", Caught)
+    try:
+        rep = track.run(track.build_parser().parse_args(argv))
+    finally:
+        monkeypatch.setattr(track, "Tracker", real)
+    assert len(caught) == 1
+    return rep, caught[0], hist
+
+
+def test_track_sequences_end_to_end(tmp_path, monkeypatch):
+    """A randomly initialised policy on the duck, two sequences, 8 envs each, 60 steps.  The eager run's recording, pushed through the
+    float32 restatement, has the accumulator's bits, so every figure of `segments` is `reduce_response` of the restatement; the graph
+    run has the eager run's bits and report."""
+    import json
+    from open_duck_playground_amd import engine, track
+    ckpt = _checkpoint(tmp_path)
+    E, T = 8, 60
+    out = tmp_path / "report.json"
+    seqs = ["0: 0 0 0 | 20: 0.1 0 0 | 40: 0 0 0.5", "0: 0.1 0 0.3 | 30: -0.1 0.05 0.3 0.2"]
+    argv = ["--checkpoint", ckpt, "--sequence", seqs[0], "--sequence", seqs[1], "--envs_per_command", str(E), "--episode_length", str(T),
+            "--response_tail_after", "10", "--seed", "1", "--output", str(out)]
+    rep_e, tr_e, hist = _run(track, monkeypatch, argv, eager=True)
+    st = rep_e["settings"]
+    assert not st["graph"] and st["sequence"] == seqs and st["then"] is None and st["response_tail_after"] == 10 and st["schedules"] == 2
+    assert st["response_tolerance"] == list(track.DEFAULT_PUSH_TOLERANCE) and len(hist) == T
+    priv, done, trunc = (np.stack([h[i] for h in hist]) for i in range(3))
+    schedules = [track.parse_sequence(s) for s in seqs]
+    tab, smap = track.schedule_table(schedules), track.schedule_blocks(2, E)
+    want, steps, ended = restate(priv, done, trunc, tab, smap, tr_e.env.batch.nobs, *track.DEFAULT_PUSH_TOLERANCE, 10)
+    got_e, track_e = tr_e.response_acc.cpu().numpy(), tr_e.acc.cpu().numpy()
+    np.testing.assert_array_equal(track_e[:, engine.TRACK_STEPS], steps)
+    np.testing.assert_array_equal(got_e.view(np.int32), want.view(np.int32))
+    np.testing.assert_array_equal(got_e[:, SAMPLES::STRIDE].sum(1), track_e[:, engine.TRACK_SAMPLES])      # the segments share out the velocity samples
+    assert got_e[:, SAMPLES].sum() > 0 and got_e[:, 2 * STRIDE + SAMPLES].sum() > 0
+
+    ref = track.reduce_response(want, schedules, E, st["dt"])
+    assert len(rep_e["commands"]) == 2
+    for row, sched, segs in zip(rep_e["commands"], schedules, ref):
+        assert tuple(row) == track.ROW_KEYS + track.SCHEDULE_ROW_KEYS
+        assert row["command"] == sched[0]["command"] and row["schedule"] == sched and row["envs"] == E
+        assert len(row["segments"]) == len(sched) and all(tuple(g) == track.SEGMENT_KEYS for g in row["segments"])
+        assert row["segments"] == segs
+        assert [g["start_step"] for g in row["segments"]] == [s["start_step"] for s in sched]
+        assert sum(g["velocity_samples"] for g in row["segments"]) == row["velocity_samples"] > 0
+        assert row["segments"][0]["envs_entered"] == E
+    assert json.load(open(out)) == json.loads(json.dumps(rep_e))
+
+    # the graph: two more launches in the captured step, the same bits
+    rep_g, tr_g, _ = _run(track, monkeypatch, argv)
+    assert rep_g["settings"]["graph"]
+    np.testing.assert_array_equal(tr_g.response_acc.cpu().numpy().view(np.int32), got_e.view(np.int32))
+    np.testing.assert_array_equal(tr_g.acc.cpu().numpy().view(np.int32), track_e.view(np.int32))
+    assert rep_g["commands"] == rep_e["commands"]
+    assert {k: v for k, v in rep_g["settings"].items() if k != "graph"} == {k: v for k, v in st.items() if k != "graph"}
+
+
+def test_track_then_gives_the_transition_matrix_and_combines_with_gait(tmp_path, monkeypatch):
+    """`--command` x2, `--then` x2, `--switch_at 30`: four rows, from-commands outermost; with `--gait` every schedule row has a gait object."""
+    from open_duck_playground_amd import track
+    ckpt = _checkpoint(tmp_path)
+    argv = ["--checkpoint", ckpt, "--command", "0.1", "0", "0", "--command", "0", "0", "0.5", "--then", "0", "0", "0", "--then", "0.05", "0.05", "0",
+            "--switch_at", "30", "--envs_per_command", "8", "--episode_length", "60", "--response_tail_after", "10", "--seed", "2", "--gait",
+            "--output", str(tmp_path / "r.json")]
+    rep, tr, _ = _run(track, monkeypatch, argv)
+    st = rep["settings"]
+    assert st["switch_at"] == 30 and st["schedules"] == 4 and st["num_envs"] == 32 and st["gait"] is True and st["graph"]
+    froms, thens = [[0.1, 0, 0] + [0.0] * 4, [0, 0, 0.5] + [0.0] * 4], [[0.0] * 7, [0.05, 0.05, 0] + [0.0] * 4]
+    assert len(rep["commands"]) == 4
+    for i, row in enumerate(rep["commands"]):
+        assert tuple(row) == track.ROW_KEYS + track.SCHEDULE_ROW_KEYS + ("gait",)
+        assert row["command"] == froms[i // 2]
+        assert row["schedule"] == [dict(start_step=0, command=froms[i // 2]), dict(start_step=30, command=thens[i % 2])]
+        assert [g["command"] for g in row["segments"]] == [froms[i // 2], thens[i % 2]]
+        assert tuple(row["gait"]) == track.GAIT_KEYS and row["gait"]["samples"] == row["velocity_samples"] > 0
+    assert tuple(tr.response_acc.shape) == (32, NACC) and tuple(tr.sched.shape) == (4, 2, 8)
+    np.testing.assert_array_equal(tr.sched_map.cpu().numpy(), np.repeat(np.arange(4), 8))
+
+
+def test_a_one_segment_sequence_is_the_plain_command_and_no_flag_means_no_launch(tmp_path, monkeypatch):
+    """`--sequence "0: 0.1 0 0"` gives, key by key and bit for bit, the ROW_KEYS values of `--command 0.1 0 0` with the same seed.  The
+    run without a schedule flag calls neither new Batch method, allocates no schedule tensor and has exactly the old keys."""
+    from open_duck_playground_amd import engine, track
+    ckpt = _checkpoint(tmp_path)
+    tail = ["--envs_per_command", "8", "--episode_length", "40", "--seed", "5", "--output", str(tmp_path / "r.json")]
+    calls = []
+    for name in ("command_schedule_apply", "response_accumulate"):
+        real = getattr(engine.Batch, name)
+        monkeypatch.setattr(engine.Batch, name, lambda self, *a, _real=real, _name=name, **k: (calls.append(_name), _real(self, *a, **k))[1])
+    rep_p, tr_p, _ = _run(track, monkeypatch, ["--checkpoint", ckpt, "--command", "0.1", "0", "0"] + tail)
+    assert calls == []
+    assert tr_p.sched is None and tr_p.sched_map is None and tr_p.response_acc is None
+    assert tuple(rep_p) == track.REPORT_KEYS and all(tuple(r) == track.ROW_KEYS for r in rep_p["commands"])
+    assert not [k for k in rep_p["settings"] if k in ("sequence", "then", "switch_at", "response_tolerance", "response_tail_after", "schedules")]
+    rep_s, tr_s, _ = _run(track, monkeypatch, ["--checkpoint", ckpt, "--sequence", "0: 0.1 0 0"] + tail)
+    # one apply launch at the reset, then per step one of each: the first step runs eagerly, the second is captured, the rest are replays
+    assert calls.count("command_schedule_apply") == 3 and calls.count("response_accumulate") == 2 and rep_s["settings"]["graph"]
+    (a,), (s,) = rep_p["commands"], rep_s["commands"]
+    for key in track.ROW_KEYS:
+        assert a[key] == s[key], key
+    np.testing.assert_array_equal(tr_s.acc.cpu().numpy().view(np.int32), tr_p.acc.cpu().numpy().view(np.int32))
+    assert [k for k in rep_s["settings"] if k not in rep_p["settings"]] == ["sequence", "then", "switch_at", "response_tolerance", "response_tail_after", "schedules"]
+    (seg,) = s["segments"]
+    assert seg["velocity_samples"] == s["velocity_samples"] and seg["mean_vx"] == s["mean_vx"] and seg["mean_wz"] == s["mean_wz"]
+
+
+def test_refusals_launch_nothing():
+    """Each ODK_ERR_INVALID case of both functions: the message names the argument, and the accumulator and the command buffer keep their bits."""
+    import torch
+    from open_duck_playground_amd import engine
+    n = 16
+    L = engine.load_library()
+    env = _duck(n)
+    b = env.batch
+    env.reset(1)
+    b.step(torch.zeros(n, 14, device="cuda"))
+    acc = torch.full((n, engine.RESP_NACC), 3.0, device="cuda")
+    tacc = torch.zeros(n, engine.TRACK_NACC, device="cuda")
+    tab = torch.tensor(table([(0, [0.1] * 7), (3, [0.2] * 7)]), device="cuda")
+    smap = torch.zeros(n, dtype=torch.int32, device="cuda")
+    cmd = torch.full((n, 7), 9.0, device="cuda")
+    good = dict(priv_dev=b.priv.data_ptr(), done_dev=b.done.data_ptr(), truncation_dev=b.truncation.data_ptr(), track_acc_dev=tacc.data_ptr(),
+                sched_dev=tab.data_ptr(), sched_of_env_dev=smap.data_ptr(), acc_dev=acc.data_ptr())
+
+    def apply(batch, null=None, nsched=1, nseg=2):
+        a = {k: (None if k == null else C.c_void_p(v)) for k, v in good.items()}
+        rc = L.odk_command_schedule_apply(batch, a["sched_dev"], nsched, nseg, a["sched_of_env_dev"], a["track_acc_dev"], b._stream())
+        return rc, L.odk_last_error().decode()
+
+    def resp(batch, null=None, nsched=1, nseg=2, lin=0.05, ang=0.2, tail=10):
+        a = {k: (None if k == null else C.c_void_p(v)) for k, v in good.items()}
+        rc = L.odk_response_accumulate(batch, a["priv_dev"], a["done_dev"], a["truncation_dev"], a["track_acc_dev"], a["sched_dev"], nsched, nseg,
+                                       a["sched_of_env_dev"], C.c_float(lin), C.c_float(ang), tail, a["acc_dev"], b._stream())
+        return rc, L.odk_last_error().decode()
+
+    # no commands bound: the C calls and the Python surface
+    assert b.commands is None
+    for fn, call in (("odk_command_schedule_apply", apply), ("odk_response_accumulate", resp)):
+        rc, msg = call(b._b)
+        assert rc == ODK_ERR_INVALID and fn in msg and "no commands bound" in msg, msg
+    with pytest.raises(engine.OdkError, match="command_schedule_apply: no commands bound"):
+        b.command_schedule_apply(tab, smap, tacc)
+    with pytest.raises(engine.OdkError, match="response_accumulate: no commands bound"):
+        b.response_accumulate(acc, tacc, tab, smap, 0.05, 0.2, 10)
+    b.bind_commands(cmd)
+    # each null pointer, by name
+    for null in ("sched_dev", "sched_of_env_dev", "track_acc_dev"):
+        rc, msg = apply(b._b, null=null)
+        assert rc == ODK_ERR_INVALID and "odk_command_schedule_apply" in msg and null in msg, (null, msg)
+    for null in ("priv_dev", "done_dev", "truncation_dev", "track_acc_dev", "sched_dev", "sched_of_env_dev", "acc_dev"):
+        rc, msg = resp(b._b, null=null)
+        assert rc == ODK_ERR_INVALID and "odk_response_accumulate" in msg and null in msg, (null, msg)
+    for call in (apply, resp):
+        rc, msg = call(None)
+        assert rc == ODK_ERR_INVALID and "batch" in msg
+        for nseg in (0, -1, 9):
+            rc, msg = call(b._b, nseg=nseg)
+            assert rc == ODK_ERR_INVALID and "nseg" in msg, (nseg, msg)
+        for nsched in (0, -3):
+            rc, msg = call(b._b, nsched=nsched)
+            assert rc == ODK_ERR_INVALID and "nsched" in msg, (nsched, msg)
+    # a tolerance that is negative or not finite, a negative tail
+    for bad in (-0.1, float("nan"), float("inf")):
+        rc, msg = resp(b._b, lin=bad)
+        assert rc == ODK_ERR_INVALID and "lin_tol" in msg, (bad, msg)
+        rc, msg = resp(b._b, ang=bad)
+        assert rc == ODK_ERR_INVALID and "ang_tol" in msg, (bad, msg)
+        with pytest.raises(engine.OdkError, match="lin_tol"):
+            b.response_accumulate(acc, tacc, tab, smap, bad, 0.2, 10)
+    rc, msg = resp(b._b, tail=-1)
+    assert rc == ODK_ERR_INVALID and "tail_after" in msg, msg
+    # bad tensors are OdkErrors before anything is launched
+    for args in ((tab[:, :, :7].contiguous(), smap, tacc), (tab.cpu(), smap, tacc), (tab, smap.long(), tacc), (tab, smap[:-1], tacc), (tab, smap, tacc.cpu())):
+        with pytest.raises(engine.OdkError, match="command_schedule_apply"):
+            b.command_schedule_apply(*args)
+    for args in ((acc[:, :-1].contiguous(), tacc, tab, smap), (acc.cpu(), tacc, tab, smap), (acc, tacc, tab.double(), smap), (acc, tacc, tab, smap.cpu())):
+        with pytest.raises(engine.OdkError, match="response_accumulate"):
+            b.response_accumulate(*args, 0.05, 0.2, 10)
+    with pytest.raises(engine.OdkError, match="tail_after"):
+        b.response_accumulate(acc, tacc, tab, smap, 0.05, 0.2, 2.5)
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(acc.cpu().numpy(), 3.0)
+    np.testing.assert_array_equal(cmd.cpu().numpy(), 9.0)
+    # ... and the good calls count
+    b.command_schedule_apply(tab, smap, tacc)
+    b.response_accumulate(acc, tacc, tab, smap, 0.05, 0.2, 10)
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(cmd.cpu().numpy(), f32(0.1))
+    got = acc.cpu().numpy()
+    assert np.all(got[:, ENTERED] == 1.0) and np.all(got[:, STRIDE:] == 3.0)
+    b.bind_commands(None)
+    b.close()
