@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "odk_shapes.h"
+#include "odk_poison.h"
 
 // per-env HBM records, observation strides, random-draw streams, the env logic's LDS floats (EnvL), the kernels' arguments (KArgs, XTerms, DRL)
 // and the compiled shapes: odk_shapes.h
@@ -322,11 +323,11 @@ __global__ void __launch_bounds__(64) reset_kernel(KArgs a) {
   const bool live = env < a.nenv;
   const int e = live ? env : a.nenv - 1;
   float* L = lds + slot * E::TOTAL;
-  const int* RT = load_shared<S>(lds, 64 / G, a.m);   // ordered before its first use by the ODK_SYNCs below
-#ifdef ODK_POISON_LDS   // debug build: every read of LDS that was not written by this launch surfaces as NaN
-  for (int k = lane; k < E::TOTAL; k += G) L[k] = __int_as_float(0x7fc00000);
+#ifdef ODK_POISON_LDS   // debug build: every read of LDS that was not written by this launch surfaces as NaN (the whole allocation:
+  odk_poison_fill(lds, E::wg_floats(64 / G));   // env images, padding, shared tables -- which load_shared then writes)
   ODK_SYNC();
 #endif
+  const int* RT = load_shared<S>(lds, 64 / G, a.m);   // ordered before its first use by the ODK_SYNCs below
   const DevModel* m = a.m;
   const EnvCfg& c = a.cfg;
   float* INFO = L + E::O_INFO;
@@ -426,11 +427,11 @@ __device__ __forceinline__ void step_body(const KArgs& a) {
 #ifdef ODK_PROFILE
   const long long t_k0 = clock64();   // kernel-level stamps (profile build): prologue / substeps / epilogue pieces -> S_PROF slots 18, 19 + dbg tail
 #endif
-  const int* RT = load_shared<S>(lds, 64 / G, a.m);   // ordered before its first use by the ODK_SYNCs below
-#ifdef ODK_POISON_LDS   // debug build: every read of LDS that was not written by this launch surfaces as NaN
-  for (int k = lane; k < E::TOTAL; k += G) L[k] = __int_as_float(0x7fc00000);
+#ifdef ODK_POISON_LDS   // debug build: every read of LDS that was not written by this launch surfaces as NaN (the whole allocation:
+  odk_poison_fill(lds, E::wg_floats(64 / G));   // env images, padding, shared tables -- which load_shared then writes)
   ODK_SYNC();
 #endif
+  const int* RT = load_shared<S>(lds, 64 / G, a.m);   // ordered before its first use by the ODK_SYNCs below
   const DevModel* m = a.m;
   const EnvCfg& c = a.cfg;
   float* INFO = L + E::O_INFO; float* ACT = L + E::O_ACT; float* CTRL = L + S::O_CTRL;
@@ -746,11 +747,11 @@ __global__ void __launch_bounds__(64) physics_kernel(KArgs a) {
   const bool live = env < a.nenv;
   const int e = live ? env : a.nenv - 1;
   float* L = lds + slot * E::TOTAL;
-  const int* RT = load_shared<S>(lds, 64 / G, a.m);   // ordered before its first use by the ODK_SYNCs below
-#ifdef ODK_POISON_LDS   // debug build: every read of LDS that was not written by this launch surfaces as NaN
-  for (int k = lane; k < E::TOTAL; k += G) L[k] = __int_as_float(0x7fc00000);
+#ifdef ODK_POISON_LDS   // debug build: every read of LDS that was not written by this launch surfaces as NaN (the whole allocation:
+  odk_poison_fill(lds, E::wg_floats(64 / G));   // env images, padding, shared tables -- which load_shared then writes)
   ODK_SYNC();
 #endif
+  const int* RT = load_shared<S>(lds, 64 / G, a.m);   // ordered before its first use by the ODK_SYNCs below
   float* rc = a.recs + (size_t)e * R::SIZE;
   for (int i = lane; i < S::NQ + 2 * S::NV; i += G) L[S::O_QPOS + i] = rc[i];
   for (int u = lane; u < S::NU; u += G) L[S::O_CTRL + u] = a.action[(size_t)e * S::NU + u];

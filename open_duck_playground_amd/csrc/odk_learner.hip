@@ -21,6 +21,7 @@
 
 #include "../../include/odk.h"
 #include "odk_host.h"
+#include "odk_poison.h"
 
 int odk_func_lds_attr_(const void* fn, int slot, int bytes);   // odk_mlp.hip
 
@@ -72,6 +73,10 @@ __global__ void gae_kernel(const float* __restrict__ trunc, const float* __restr
                            const float* __restrict__ val, const float* __restrict__ boot, float* __restrict__ vs,
                            float* __restrict__ adv, float* __restrict__ stats, int B, int T, float lambda_, float discount) {
   __shared__ float sh[16];
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(sh, sizeof(sh) / 4);
+  __syncthreads();
+#endif
   float s = 0.0f;
   for (int b = threadIdx.x; b < B; b += blockDim.x) {
     const size_t o = (size_t)b * T;
@@ -104,6 +109,10 @@ __global__ void gae_kernel_reg(const float* __restrict__ trunc, const float* __r
                                const float* __restrict__ val, const float* __restrict__ boot, float* __restrict__ vs,
                                float* __restrict__ adv, float* __restrict__ stats, int B, int T, float lambda_, float discount) {
   __shared__ float sh[16];
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(sh, sizeof(sh) / 4);
+  __syncthreads();
+#endif
   const int b = threadIdx.x;
   const bool live = b < B;
   const size_t o = (size_t)(live ? b : 0) * T;
@@ -148,6 +157,10 @@ __global__ void __launch_bounds__(1024) gae_kernel_lds(const float* __restrict__
                                                        float* __restrict__ stats, int B, int T, float lambda_, float discount) {
   __shared__ float s_r[GAE_LDS_N], s_v[GAE_LDS_N], s_f[GAE_LDS_N];   // s_f = trunc + 2 * term (both are 0 / 1 flags)
   __shared__ float sh[16];
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(s_r, sizeof(s_r) / 4); odk_poison_fill(s_v, sizeof(s_v) / 4); odk_poison_fill(s_f, sizeof(s_f) / 4); odk_poison_fill(sh, sizeof(sh) / 4);
+  __syncthreads();
+#endif
   const int N = B * T;
   for (int i = threadIdx.x; i < N; i += blockDim.x) { s_r[i] = rew[i]; s_v[i] = val[i]; s_f[i] = (trunc[i] != 0.0f ? 1.0f : 0.0f) + (term[i] != 0.0f ? 2.0f : 0.0f); }
   __syncthreads();
@@ -234,6 +247,10 @@ __global__ void ppo_head_kernel(const float* __restrict__ logits, const float* _
   // block totals first: one atomic per loss and workgroup (1 280 wave-level float atomics on four addresses serialised
   // into ~50 us; these sums are reporting only, the gradients above do not depend on them)
   __shared__ float sh[16];
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(sh, sizeof(sh) / 4);
+  __syncthreads();
+#endif
   lp = block_sum(lp, sh); lv = block_sum(lv, sh); le = block_sum(le, sh);
   if (threadIdx.x == 0) {
     atomicAdd(&losses[0], lp + lv + le); atomicAdd(&losses[1], lp); atomicAdd(&losses[2], lv); atomicAdd(&losses[3], le);
@@ -271,6 +288,10 @@ __global__ void __launch_bounds__(GH_THREADS) ppo_gae_head_kernel(GaeHead a) {
   __shared__ unsigned char s_f[GAE_LDS_N];           // trunc + 2 * term
   __shared__ int s_j[1024];                          // the minibatch's trajectory numbers, -1 = outside the rollout
   __shared__ float sh[16], sh3[3][16];
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(s_r, sizeof(s_r) / 4); odk_poison_fill(s_v, sizeof(s_v) / 4); odk_poison_fill(s_f, sizeof(s_f) / 4); odk_poison_fill(s_j, sizeof(s_j) / 4); odk_poison_fill(sh, sizeof(sh) / 4); odk_poison_fill(sh3, sizeof(sh3) / 4);
+  __syncthreads();
+#endif
   const int B = a.B, T = a.T, N = B * T, A = a.A;
   const int k = a.cursor ? *a.cursor : 0;
   const long long* idx = a.idx + (size_t)k * B;
@@ -379,6 +400,10 @@ __global__ void policy_sample_kernel(const float* __restrict__ logits, const flo
 // advances the step counter acc[1].
 __global__ void sqnorm_kernel(const float* __restrict__ g, float* __restrict__ acc, int64_t n) {
   __shared__ float sh[16];
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(sh, sizeof(sh) / 4);
+  __syncthreads();
+#endif
   float s = 0.0f;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) { const float v = g[i]; s += v * v; }
   s = block_sum(s, sh);
@@ -393,6 +418,10 @@ __global__ void sqnorm_kernel(const float* __restrict__ g, float* __restrict__ a
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                             float* __restrict__ acc, int nblocks, int64_t n, float lr, float b1, float b2, float eps, float max_norm) {
   __shared__ float sh[16];
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(sh, sizeof(sh) / 4);
+  __syncthreads();
+#endif
   float sq = 0.0f;
   for (int i = threadIdx.x; i < nblocks; i += blockDim.x) sq += acc[2 + i];
   sq = block_sum(sq, sh);
@@ -415,6 +444,10 @@ constexpr int SB_ROWS = 64;
 __global__ void silu_bwd_colsum_kernel(const float* __restrict__ dh, const float* __restrict__ z, float* __restrict__ dz,
                                        float* __restrict__ partial, int n, int w) {
   __shared__ float sh[4][64];
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(sh, sizeof(sh) / 4);
+  __syncthreads();
+#endif
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + tx;
   const int r0 = blockIdx.y * SB_ROWS, r1 = min(n, r0 + SB_ROWS);
@@ -436,6 +469,10 @@ __global__ void silu_bwd_colsum_kernel(const float* __restrict__ dh, const float
 // Tile sums of a plain [n, w] matrix in the same layout (the top layer's bias gradient: dz needs no activation derivative)
 __global__ void colsum_partial_kernel(const float* __restrict__ x, float* __restrict__ partial, int n, int w) {
   __shared__ float sh[4][64];
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(sh, sizeof(sh) / 4);
+  __syncthreads();
+#endif
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + tx;
   const int r0 = blockIdx.y * SB_ROWS, r1 = min(n, r0 + SB_ROWS);
@@ -448,6 +485,10 @@ __global__ void colsum_partial_kernel(const float* __restrict__ x, float* __rest
 }
 __global__ void colsum_final_kernel(const float* __restrict__ partial, float* __restrict__ out, int nblk, int w) {
   __shared__ float sh[4][64];
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(sh, sizeof(sh) / 4);
+  __syncthreads();
+#endif
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + tx;
   float s = 0.0f;
@@ -463,6 +504,10 @@ __global__ void colsum_final_kernel(const float* __restrict__ partial, float* __
 struct ColsumArgs { const float* partial[8]; float* out[8]; int w[8]; };
 __global__ void colsum_final_multi_kernel(ColsumArgs a, int nblk) {
   __shared__ float sh[4][64];
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(sh, sizeof(sh) / 4);
+  __syncthreads();
+#endif
   const int f = blockIdx.y, w = a.w[f];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + tx;
@@ -532,6 +577,7 @@ struct DwLayer { const float* dz; const float* h; int n_out, n_in, tj, tile0, ng
 // wave 1 hands its accumulators over through LDS and wave 0 adds and stores -- half the split-K workspace (8 slices instead of 16:
 // the finishing launch reads 16 MB instead of 32) for one 32 KB LDS round trip per tile.  A slot is now a workgroup slot: 64 per XCD.
 constexpr int DW_SLOTS = 64, DW_SLOT_ITEMS = 4, DW_WAVES = 2;
+constexpr int DW_LDS_BYTES = 80 * 1024;     // dynamic LDS per workgroup: the 32 KB fold buffer + the reservation that holds a CU to two workgroups
 struct DwArgs { DwLayer L[DW_MAX]; int nlayers, ntiles, kslices, nslots; float* ws; long long ws_stride; long long* prof; unsigned short item[DW_SLOTS][DW_SLOT_ITEMS]; };
 
 constexpr int DW_MI = 4, DW_MJ = 2;      // output tile of a wave: DW_MI x DW_MJ blocks of 32 x 32 (rows = n_out side, columns = n_in side)
@@ -648,6 +694,10 @@ __device__ __forceinline__ void dw_item(const DwArgs& a, const int tile, const i
 }
 __global__ void __launch_bounds__(64 * DW_WAVES) dw_gemm_kernel(DwArgs a) {
   extern __shared__ float dw_fold[];     // [DW_MI * DW_MJ * 16][64] floats = 32 KB (the launch reserves half a CU's LDS per workgroup)
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(dw_fold, DW_LDS_BYTES / 4);
+  __syncthreads();
+#endif
   const int b = blockIdx.x, xcd = b & 7, slot = b >> 3;
   const int per_xcd = a.kslices >> 3;                 // kslices is a multiple of 8
   long long t0 = 0, c0 = 0;
@@ -675,6 +725,10 @@ __global__ void __launch_bounds__(256) grad_finish_kernel(const float* __restric
                                                          FinishArgs fa) {
   __shared__ float sh[16][17];
   __shared__ float red[16];
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(sh, sizeof(sh) / 4); odk_poison_fill(red, sizeof(red) / 4);
+  __syncthreads();
+#endif
   float sq = 0.0f;
   if ((int)blockIdx.x < fa.nb_reduce) {
     long long total = 0;
@@ -741,6 +795,10 @@ __global__ void __launch_bounds__(256) grad_finish_kernel(const float* __restric
 // (column tiles, row slices); slice s walks rows s, s + slices, ... -- with 4 phases: rows s + slices (4 k + phase)
 __global__ void __launch_bounds__(256) col_moments_kernel(const float* __restrict__ x, long long rows, int w, int slices, double* __restrict__ partial) {
   __shared__ double sh[2][4][64];
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(sh, sizeof(sh) / 4);
+  __syncthreads();
+#endif
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + tx, sl = blockIdx.y;
   double s = 0.0, s2 = 0.0;
@@ -771,6 +829,10 @@ __global__ void __launch_bounds__(256) col_moments_kernel(const float* __restric
 __global__ void __launch_bounds__(256) moments_update_kernel(const double* __restrict__ partial, int slices, int w, double rows, double* __restrict__ count,
                                                             float* __restrict__ mean, float* __restrict__ sv, float* __restrict__ sd, float std_min, float std_max) {
   __shared__ double sh[2][4][64];
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(sh, sizeof(sh) / 4);
+  __syncthreads();
+#endif
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + tx;
   const double cnt0 = *count;
@@ -1002,8 +1064,8 @@ extern "C" int odk_dw_gemm(const float* const* dz_dev, const float* const* h_dev
   hipStream_t st = (hipStream_t)stream;
   // 80 KB of LDS per two-wave workgroup (32 KB used by the fold): at most two of them per CU, i.e. one wave per SIMD when the XCD's
   // slots are all taken
-  if (odk_func_lds_attr_((const void*)dw_gemm_kernel, 0, 80 * 1024)) return odk_fail_(ODK_ERR_HIP, "odk_dw_gemm: the device refuses 80 KB of dynamic LDS per workgroup");
-  hipLaunchKernelGGL(dw_gemm_kernel, dim3(a.nslots * 8), dim3(64 * DW_WAVES), 80 * 1024, st, a);
+  if (odk_func_lds_attr_((const void*)dw_gemm_kernel, 0, DW_LDS_BYTES)) return odk_fail_(ODK_ERR_HIP, "odk_dw_gemm: the device refuses 80 KB of dynamic LDS per workgroup");
+  hipLaunchKernelGGL(dw_gemm_kernel, dim3(a.nslots * 8), dim3(64 * DW_WAVES), DW_LDS_BYTES, st, a);
   long long total = 0;
   for (int l = 0; l < nlayers; l++) total += rg.count[l];
   int blocks = (int)((total / 4 + 255) / 256);

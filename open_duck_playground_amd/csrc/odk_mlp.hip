@@ -39,6 +39,7 @@
 
 #include "../../include/odk.h"
 #include "odk_host.h"
+#include "odk_poison.h"
 
 namespace {
 
@@ -190,6 +191,10 @@ __device__ __forceinline__ void fwd_epilogue(const f32x4 (&acc)[NBLK], const flo
 
 __global__ void __launch_bounds__(256, MLP_WG_PER_CU) mlp_fwd_kernel(Args a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(lds, F_TOTAL);
+  __syncthreads();
+#endif
   int net_i, tile;
   map_block(a, blockIdx.x, net_i, tile);
   const Net& N = a.net[net_i];
@@ -374,6 +379,10 @@ __device__ __forceinline__ void bwd_epilogue(const f32x4 (&acc)[NBLK], const f32
 
 __global__ void __launch_bounds__(256, MLP_WG_PER_CU) mlp_bwd_kernel(Args a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(lds, B_TOTAL);
+  __syncthreads();
+#endif
   int net_i, tile;
   map_block(a, blockIdx.x, net_i, tile);
   const Net& N = a.net[net_i];
@@ -500,6 +509,10 @@ __global__ void adam_packed_kernel(float* __restrict__ p, float* __restrict__ pf
                                    float* __restrict__ v, float* __restrict__ acc, int nblocks, int64_t n, float lr, float b1, float b2, float eps,
                                    float max_norm, WeightTable t_, Tail tail) {
   __shared__ float sh[16];
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(sh, sizeof(sh) / 4);
+  __syncthreads();
+#endif
   step_tail(tail);
   float sq = 0.0f;
   for (int i = threadIdx.x; i < nblocks; i += blockDim.x) sq += acc[2 + i];
@@ -549,6 +562,10 @@ __global__ void __launch_bounds__(256) adam_tiled_kernel(float* __restrict__ p, 
                                                          float b2, float eps, float max_norm, WeightTable t_, AdamTiles at, Tail tail) {
   __shared__ float sh[16];
   __shared__ float tile[16][65];
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(sh, sizeof(sh) / 4); odk_poison_fill(tile, sizeof(tile) / 4);
+  __syncthreads();
+#endif
   step_tail(tail);
   float sq = 0.0f;
   for (int i = threadIdx.x; i < nblocks; i += blockDim.x) sq += acc[2 + i];
@@ -604,6 +621,10 @@ __global__ void __launch_bounds__(256) adam_tiled_kernel(float* __restrict__ p, 
 }
 __global__ void sqnorm_p_kernel(const float* __restrict__ g, float* __restrict__ acc, int64_t n) {
   __shared__ float sh[16];
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(sh, sizeof(sh) / 4);
+  __syncthreads();
+#endif
   float s = 0.0f;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) { const float v = g[i]; s += v * v; }
   s = block_sum(s, sh);
@@ -614,6 +635,10 @@ __global__ void sqnorm_p_kernel(const float* __restrict__ g, float* __restrict__
 struct FoldArgs { const float* partial[8]; float* out[8]; int w[8], nblk[8]; };
 __global__ void __launch_bounds__(1024) colsum_fold_kernel(FoldArgs a) {   // 64 columns x 16 row phases per workgroup
   __shared__ float sh[16][64];
+#ifdef ODK_POISON_LDS
+  odk_poison_fill(sh, sizeof(sh) / 4);
+  __syncthreads();
+#endif
   const int f = blockIdx.y, w = a.w[f], nblk = a.nblk[f];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + tx;

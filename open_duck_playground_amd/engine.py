@@ -103,19 +103,30 @@ class OdkError(RuntimeError):
     pass
 
 
-def build_library(force: bool = False) -> str:
-    """Compiles csrc/ for gfx950 with hipcc (cross-compiles without a GPU): the objects side by side (MAX_JOBS, else the CPU count; 16 at the
-    most).  force: everything again; otherwise what make's prerequisites say a newer source needs."""
+POISON_LIB_PATH = os.path.join(_CSRC, "libodk_poison.so")   # the -DODK_POISON_LDS build (csrc/odk_poison.h): load it through ODK_LIB
+
+
+def library_sources() -> list:
+    """The files a library in csrc/ is built from (what build_library and the poison tests call stale against)."""
     srcs = [os.path.join(_CSRC, f) for f in sorted(os.listdir(_CSRC)) if f.endswith((".hip", ".h", ".inc")) or f == "Makefile"]
     srcs.append(os.path.join(_CSRC, "..", "..", "include", "odk.h"))
-    if not force and os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(s) for s in srcs):
+    return srcs
+
+
+def build_library(force: bool = False, poison: bool = False) -> str:
+    """Compiles csrc/ for gfx950 with hipcc (cross-compiles without a GPU): the objects side by side (MAX_JOBS, else the CPU count; 16 at the
+    most).  force: everything again; otherwise what make's prerequisites say a newer source needs.  poison: libodk_poison.so (every kernel
+    starts from NaN-filled LDS) as a second goal of the same make, so that both libraries' objects share the one job pool."""
+    goals = [LIB_PATH] + ([POISON_LIB_PATH] if poison else [])
+    newest = max(os.path.getmtime(s) for s in library_sources())
+    if not force and all(os.path.exists(g) and os.path.getmtime(g) >= newest for g in goals):
         return LIB_PATH
     try:
         jobs = int(os.environ.get("MAX_JOBS", ""))
     except ValueError:       # unset or not a number
         jobs = os.cpu_count() or 1
     jobs = max(1, min(16, jobs))
-    subprocess.check_call(["make", "-C", _CSRC, "-s", f"-j{jobs}"] + (["-B"] if force else []) + ["libodk.so"])
+    subprocess.check_call(["make", "-C", _CSRC, "-s", f"-j{jobs}"] + (["-B"] if force else []) + ["libodk.so"] + (["libodk_poison.so"] if poison else []))
     return LIB_PATH
 
 
