@@ -481,6 +481,55 @@ int odk_response_accumulate(const odk_batch* b, const float* priv_dev, const flo
                             const float* track_acc_dev, const float* sched_dev, int nsched, int nseg, const int32_t* sched_of_env_dev,
                             float lin_tol, float ang_tol, int tail_after, float* acc_dev /* [nenv, ODK_RESP_NACC] */, void* stream);
 
+/* Fall recorder (why, when and which way does the policy fall: the last second before the termination of every env, replayable): one launch
+ * per evaluation step, graph-capturable, issued after odk_step and BEFORE odk_tracking_accumulate (track_acc_dev's ENDED slot then still
+ * says whether env e's first episode was running when this step began, and its STEPS slot is the index t of the step that just ran), with
+ * odk_push_accumulate's contract.  Unlike the accumulators above it keeps samples, not sums: env e's row of acc_dev [nenv, row_stride],
+ * zeroed by the caller before the first step, is ODK_FALL_HEAD floats and then a ring of `ring` slots of ODK_FALL_SAMPLE + nq floats
+ * (odk_fall_row_floats; nq: odk_model_dims).  The row is touched only during e's first episode; every other float keeps its bits: rows of
+ * ended envs, slots not written this step, the floats between odk_fall_row_floats and a wider row_stride, rows past the batch.
+ * A sample is odk_gait_accumulate's: a first-episode step that is not done (a done step's observation and state are the auto-reset's), so
+ * the latest sample of a fall is the step before the termination.  Sample number s (0-based: SAMPLES before the step) goes to slot
+ * s % ring, all float32 copies of this step's outputs -- priv_dev [nenv, npriv] (nu, nobs, npriv: odk_model_obs_sizes; both tasks), the
+ * env's bound command row c and the batch's own state record:
+ *   S_STEP          t, the index of the step among the steps of the first episode
+ *   S_UP[3]         the up vector, priv nobs + 6 (the "gravity" sensor: the imu site's z axis in world coordinates)
+ *   S_GYRO[3]       priv nobs
+ *   S_LINVEL[3]     local linear velocity, priv nobs + 9
+ *   S_HEIGHT        root height, priv nobs + 15 + 2 nu
+ *   S_CONTACT[2]    left, right foot, priv nobs + 16 + 3 nu
+ *   S_LIN_ERR       hypot(vx - cx, vy - cy) through float64 with one rounding to float32 (odk_push_accumulate's planar error), against the
+ *                   bound command row as the step left it: under a command schedule the row odk_command_schedule_apply wrote
+ *   S_ANG_ERR       |wz - cwz| in float32, wz = priv nobs + 2
+ *   S_SAT           the number of actuators with |actuator_force| >= 0.99f * torque_limit[u] (actuator_force: priv nobs + 16 + 2 nu; float32;
+ *                   odk_gait_accumulate's rule: 0 when torque_limit_dev is NULL, an actuator with torque_limit[u] <= 0 never counts)
+ *   then qpos[0 .. nq) of the env, at ODK_FALL_SAMPLE
+ * Head slots:
+ *   SAMPLES         samples so far: a ring holds the last min(SAMPLES, ring) of them, the oldest in slot SAMPLES % ring once SAMPLES >= ring,
+ *                   in slot 0 before
+ *   FELL            1 when the first episode ended with done and no truncation
+ *   FALL_STEP       t of that done step (the first episode's length minus one)
+ *   LAST_UPRIGHT    1-based number of the latest sample with tilt <= tilt_tol, tilt = hypot(up_x, up_y) through float64
+ *                   (ODK_POSTURE_TILT_PEAK's: the sine of the lean); 0 if none
+ *   UPRIGHT_CONTACT[2]   S_CONTACT of that sample: the support the robot left the upright on
+ *   TILT_PEAK       maximum of tilt over the samples: how close a survivor came
+ * Slots 7 .. 15 stay 0.  A truncated first episode writes nothing at its done step.  No sums: every stored float is a copy, a small whole
+ * number or a correctly rounded root, so a host restatement has the row's bits; one 16-lane row owns an env's row and there are no atomics.
+ * ODK_ERR_INVALID, with the cause in odk_last_error and nothing launched: a null pointer other than torque_limit_dev (the message names the
+ * argument), no bound commands, ring outside 1 .. ODK_FALL_MAX_RING, row_stride < odk_fall_row_floats, a model with more than 16
+ * actuators, a tilt_tol that is negative or not finite. */
+#define ODK_FALL_HEAD 16        /* floats before the ring */
+#define ODK_FALL_SAMPLE 16      /* scalars of a ring slot, before its qpos */
+#define ODK_FALL_MAX_RING 64
+enum { ODK_FALL_SAMPLES = 0, ODK_FALL_FELL = 1, ODK_FALL_STEP = 2, ODK_FALL_LAST_UPRIGHT = 3, ODK_FALL_UPRIGHT_CONTACT = 4 /* [2] */,
+       ODK_FALL_TILT_PEAK = 6 /* 7..15 stay 0 */ };
+enum { ODK_FALL_S_STEP = 0, ODK_FALL_S_UP = 1 /* [3] */, ODK_FALL_S_GYRO = 4 /* [3] */, ODK_FALL_S_LINVEL = 7 /* [3] */, ODK_FALL_S_HEIGHT = 10,
+       ODK_FALL_S_CONTACT = 11 /* [2] */, ODK_FALL_S_LIN_ERR = 13, ODK_FALL_S_ANG_ERR = 14, ODK_FALL_S_SAT = 15 };
+int odk_fall_row_floats(const odk_batch* b, int ring);   /* ODK_FALL_HEAD + ring * (ODK_FALL_SAMPLE + nq); < 0 for a bad ring */
+int odk_fall_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
+                        const float* track_acc_dev, const float* torque_limit_dev /* [nu] or NULL */, float tilt_tol, int ring,
+                        float* acc_dev /* [nenv, row_stride] */, int row_stride, void* stream);
+
 /* mjx_env.step alone (physics only, n_substeps, ctrl = ctrl_dev [nenv, nu]); for parity tests */
 int odk_physics_step(odk_batch* b, const float* ctrl_dev, int n_substeps, void* stream);
 

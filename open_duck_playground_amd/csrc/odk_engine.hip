@@ -1,4 +1,4 @@
-// odk_engine.hip -- the batch C-ABI of include/odk.h (libodk.so) + the accumulator kernels of the tracking / push / gait / posture / imitation / response reports
+// odk_engine.hip -- the batch C-ABI of include/odk.h (libodk.so) + the accumulator kernels of the tracking / push / gait / posture / imitation / response / fall reports
 // and the command-schedule kernel.
 //
 // Host side: device buffers, launches on the caller's stream (blob -> DevModel, odk_model_load and the model getters: odk_model_load.hip).  Device side:
@@ -921,6 +921,99 @@ extern "C" int odk_response_accumulate(const odk_batch* b, const float* priv_dev
   hipLaunchKernelGGL(response_kernel, dim3((b->nenv + 255) / 256), dim3(256), 0, (hipStream_t)stream, priv_dev, npriv, nobs, done_dev, truncation_dev,
                      b->d_cmd, b->cmd_stride, track_acc_dev, sched_dev, nsched, nseg, sched_of_env_dev, lin_tol, ang_tol, (float)tail_after, acc_dev,
                      b->nenv);
+  HIPCHK(hipGetLastError());
+  return ODK_OK;
+}
+
+// Fall recorder of one evaluation step, issued between odk_step and odk_tracking_accumulate (the ENDED / STEPS contract of push_kernel), in
+// gait_kernel's layout: one 16-lane DPP row per env, four envs per wave.  For the saturation count lane = actuator (a row sum of 0 / 1 flags:
+// exact); for the stores lane = float: the 16 scalars of the ring slot are one contiguous 64-byte store of the row, the qpos copy from the
+// batch's record (offset 0 of the env's row of d_recs) is ceil(nq / 16) passes of consecutive lanes on consecutive floats, and the head's
+// slots are written by the lane of their number.  Only the slot of this sample and the head are stored to, and only during the first episode:
+// every other float keeps its bits.  Contraction is off and both hypots go through float64, so a host restatement has the row's bits.
+__global__ void __launch_bounds__(256) fall_kernel(const float* __restrict__ priv, int npriv, int nobs, int nu, const float* __restrict__ done,
+                                                   const float* __restrict__ trunc, const float* __restrict__ track, const float* __restrict__ cmd,
+                                                   int cmd_stride, const float* __restrict__ limit, const float* __restrict__ recs, int rec_size,
+                                                   int nq, float tilt_tol, int ring, float* __restrict__ acc, int row_stride, int nenv) {
+#pragma clang fp contract(off)
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int e = t >> 4, u = t & 15;
+  const int e0 = e < nenv ? e : 0;
+  const float* T = track + (size_t)e0 * ODK_TRACK_NACC;
+  const bool live = e < nenv && T[ODK_TRACK_ENDED] == 0.0f;       // the first episode was running when this step began
+  const bool sample = live && done[e0] == 0.0f;
+  const bool act = sample && u < nu;
+  const float* Q = priv + (size_t)(sample ? e : 0) * npriv + nobs;   // row 0 for the rows that only take part in the row sum
+  const float f = act ? Q[16 + 2 * nu + u] : 0.0f;
+  const float lim = (act && limit) ? limit[u] : 0.0f;
+  const float sat = row_sum16((lim > 0.0f && fabsf(f) >= 0.99f * lim) ? 1.0f : 0.0f);
+  if (!live) return;
+  float* A = acc + (size_t)e * row_stride;
+  const float step = T[ODK_TRACK_STEPS];                          // first-episode steps before the one that just ran: its index
+  if (!sample) {   // ends the first episode; no sample (the observation and the state are the auto-reset's)
+    if (trunc[e] == 0.0f && (u == ODK_FALL_FELL || u == ODK_FALL_STEP)) A[u] = u == ODK_FALL_FELL ? 1.0f : step;
+    return;
+  }
+  // per env (the same in the row's 16 lanes)
+  const float n0 = A[ODK_FALL_SAMPLES];
+  const float* C = cmd + (size_t)e * cmd_stride;
+  const float lin = planar32(Q[9] - C[0], Q[10] - C[1]), ang = fabsf(Q[2] - C[2]);   // push_kernel's
+  const float tilt = planar32(Q[6], Q[7]);                                            // posture_kernel's
+  const bool upright = tilt <= tilt_tol;
+  const float con[2] = {Q[16 + 3 * nu], Q[17 + 3 * nu]};
+  // lane u's scalar of the slot: a copy of the privileged row at `off`, or one of the four computed ones
+  int off = u + 5;                                                // S_UP: nobs + 6 ..
+  off = u >= ODK_FALL_S_GYRO ? u - ODK_FALL_S_GYRO : off;
+  off = u >= ODK_FALL_S_LINVEL ? u + 2 : off;                     // nobs + 9 ..
+  off = u == ODK_FALL_S_HEIGHT ? 15 + 2 * nu : off;
+  off = u >= ODK_FALL_S_CONTACT ? 16 + 3 * nu + (u - ODK_FALL_S_CONTACT) : off;
+  off = (u == ODK_FALL_S_STEP || u >= ODK_FALL_S_LIN_ERR) ? 0 : off;
+  float v = Q[off];
+  v = u == ODK_FALL_S_STEP ? step : v;
+  v = u == ODK_FALL_S_LIN_ERR ? lin : v;
+  v = u == ODK_FALL_S_ANG_ERR ? ang : v;
+  v = u == ODK_FALL_S_SAT ? sat : v;
+  const unsigned slot = (unsigned)(int)n0 % (unsigned)ring;       // (unsigned: a row the caller did not zero still lands inside its ring)
+  float* S = A + ODK_FALL_HEAD + (size_t)slot * (ODK_FALL_SAMPLE + nq);
+  S[u] = v;
+  const float* R = recs + (size_t)e * rec_size;
+  for (int j = u; j < nq; j += 16) S[ODK_FALL_SAMPLE + j] = R[j];
+  // the head: lane = slot
+  if (u == ODK_FALL_SAMPLES) A[u] = n0 + 1.0f;
+  if (u == ODK_FALL_LAST_UPRIGHT && upright) A[u] = n0 + 1.0f;   // this sample's 1-based number
+  if ((u == ODK_FALL_UPRIGHT_CONTACT || u == ODK_FALL_UPRIGHT_CONTACT + 1) && upright) A[u] = con[u - ODK_FALL_UPRIGHT_CONTACT];
+  if (u == ODK_FALL_TILT_PEAK) A[u] = fmaxf(A[u], tilt);
+}
+
+extern "C" int odk_fall_row_floats(const odk_batch* b, int ring) {
+  if (!b || ring < 1 || ring > ODK_FALL_MAX_RING) return -1;
+  return ODK_FALL_HEAD + ring * (ODK_FALL_SAMPLE + b->model.h.nq);
+}
+
+extern "C" int odk_fall_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
+                                   const float* track_acc_dev, const float* torque_limit_dev, float tilt_tol, int ring, float* acc_dev,
+                                   int row_stride, void* stream) {
+  const char* fn = "odk_fall_accumulate";
+  if (!b) return fail(ODK_ERR_INVALID, "%s: null batch", fn);
+  if (!priv_dev) return fail(ODK_ERR_INVALID, "%s: null priv_dev", fn);
+  if (!done_dev) return fail(ODK_ERR_INVALID, "%s: null done_dev", fn);
+  if (!truncation_dev) return fail(ODK_ERR_INVALID, "%s: null truncation_dev", fn);
+  if (!track_acc_dev) return fail(ODK_ERR_INVALID, "%s: null track_acc_dev", fn);
+  if (!acc_dev) return fail(ODK_ERR_INVALID, "%s: null acc_dev", fn);
+  if (!b->d_cmd) return fail(ODK_ERR_INVALID, "%s: no commands bound (odk_batch_bind_commands)", fn);
+  if (ring < 1 || ring > ODK_FALL_MAX_RING) return fail(ODK_ERR_INVALID, "%s: ring = %d (1 .. %d samples)", fn, ring, ODK_FALL_MAX_RING);
+  const int nu = b->model.h.nu, nq = b->model.h.nq, need = odk_fall_row_floats(b, ring);
+  if (row_stride < need) return fail(ODK_ERR_INVALID, "%s: row_stride = %d, a row of ring %d holds %d floats (odk_fall_row_floats)", fn, row_stride, ring, need);
+  if (nu > 16) return fail(ODK_ERR_INVALID, "%s: the model has %d actuators, a row holds 16", fn, nu);
+  if (!std::isfinite(tilt_tol) || tilt_tol < 0.0f)
+    return fail(ODK_ERR_INVALID, "%s: tilt_tol = %g (a finite sine of the lean >= 0)", fn, (double)tilt_tol);
+  int nobs, npriv;
+  obs_sizes_nu(nu, b->cfg.env_kind, &nobs, &npriv);
+  HIPCHK(hipSetDevice(b->device));
+  const long long threads = (long long)b->nenv * 16;
+  hipLaunchKernelGGL(fall_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, priv_dev, npriv, nobs, nu, done_dev,
+                     truncation_dev, track_acc_dev, b->d_cmd, b->cmd_stride, torque_limit_dev, b->d_recs, b->rec_size, nq, tilt_tol, ring, acc_dev,
+                     row_stride, b->nenv);
   HIPCHK(hipGetLastError());
   return ODK_OK;
 }

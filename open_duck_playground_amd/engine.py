@@ -180,6 +180,8 @@ def load_library() -> C.CDLL:
     L.odk_imitation_accumulate.argtypes = [P, P, P, P, P, C.c_int, P, P]
     L.odk_command_schedule_apply.argtypes = [P, P, C.c_int, C.c_int, P, P, P]
     L.odk_response_accumulate.argtypes = [P, P, P, P, P, P, C.c_int, C.c_int, P, C.c_float, C.c_float, C.c_int, P, P]
+    L.odk_fall_row_floats.argtypes = [P, C.c_int]
+    L.odk_fall_accumulate.argtypes = [P, P, P, P, P, P, C.c_float, C.c_int, P, C.c_int, P]
     L.odk_batch_get_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_set_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_get_debug.argtypes = [P, FP, FP, FP, FP]
@@ -225,7 +227,7 @@ EXPORTED_SYMBOLS = (
     "odk_batch_destroy", "odk_batch_set_config", "odk_batch_set_param", "odk_reset", "odk_step", "odk_physics_step",
     "odk_batch_bind_commands", "odk_batch_set_reward_terms", "odk_batch_bind_reward_metrics", "odk_batch_set_imitation_joints", "odk_batch_set_head_joints",
     "odk_tracking_accumulate", "odk_batch_bind_pushes", "odk_push_accumulate", "odk_gait_accumulate", "odk_posture_accumulate",
-    "odk_imitation_accumulate", "odk_command_schedule_apply", "odk_response_accumulate",
+    "odk_imitation_accumulate", "odk_command_schedule_apply", "odk_response_accumulate", "odk_fall_row_floats", "odk_fall_accumulate",
     "odk_batch_get_state", "odk_batch_set_state", "odk_batch_get_debug", "odk_set_debug_dump", "odk_batch_lds_size",
     "odk_batch_get_lds", "odk_lds_offset", "odk_batch_record_size", "odk_batch_get_records", "odk_batch_set_records", "odk_batch_timing", "odk_gae", "odk_ppo_head",
     "odk_policy_sample", "odk_adam_clip", "odk_silu_bwd_colsum", "odk_colsum_partial", "odk_colsum_finalize", "odk_gather_rows", "odk_dw_gemm",
@@ -295,6 +297,15 @@ RESP_NACC = SCHED_MAX_SEGMENTS * RESP_STRIDE
 (RESP_ENTERED, RESP_SAMPLES, RESP_FELL, RESP_STEPS_TO_FALL, RESP_FIRST_IN, RESP_LAST_OFF, RESP_PEAK_LIN_ERR, RESP_PEAK_ANG_ERR) = range(8)
 RESP_SUM, RESP_SQERR, RESP_OVERSHOOT, RESP_TAIL_SAMPLES, RESP_TAIL_SUM = 8, 11, 14, 17, 18
 
+# odk_fall_accumulate's row (include/odk.h ODK_FALL_*): FALL_HEAD head floats, then a ring of slots of FALL_SAMPLE scalars + nq qpos floats;
+# [2] = left / right foot, [3] = x, y, z
+FALL_HEAD = 16
+FALL_SAMPLE = 16
+FALL_MAX_RING = 64
+FALL_SAMPLES, FALL_FELL, FALL_STEP, FALL_LAST_UPRIGHT, FALL_UPRIGHT_CONTACT, FALL_TILT_PEAK = 0, 1, 2, 3, 4, 6
+(FALL_S_STEP, FALL_S_UP, FALL_S_GYRO, FALL_S_LINVEL, FALL_S_HEIGHT, FALL_S_CONTACT, FALL_S_LIN_ERR, FALL_S_ANG_ERR, FALL_S_SAT) = (
+    0, 1, 4, 7, 10, 11, 13, 14, 15)
+
 
 def check_pushes(push, nenv: int, device: int) -> None:
     """What `Batch.bind_pushes` accepts: a contiguous float32 [nenv, >= 2] tensor on cuda:`device`; raises OdkError otherwise."""
@@ -312,7 +323,7 @@ def check_pushes(push, nenv: int, device: int) -> None:
 
 
 def check_accumulator(name: str, acc, nenv: int, ncol: int, device: int) -> None:
-    """An accumulator argument of `Batch.push_accumulate` / `Batch.gait_accumulate` / `Batch.posture_accumulate` / `Batch.imitation_accumulate` / `Batch.response_accumulate`: a contiguous float32 [nenv, ncol] tensor on cuda:`device`; OdkError otherwise."""
+    """An accumulator argument of `Batch.push_accumulate` / `Batch.gait_accumulate` / `Batch.posture_accumulate` / `Batch.imitation_accumulate` / `Batch.response_accumulate` / `Batch.fall_accumulate`: a contiguous float32 [nenv, ncol] tensor on cuda:`device`; OdkError otherwise."""
     import torch
     if not torch.is_tensor(acc):
         raise OdkError(f"{name}: expected a torch tensor, got {type(acc).__name__}")
@@ -1145,6 +1156,38 @@ class Batch:
                                             C.c_void_p(self.truncation.data_ptr()), C.c_void_p(track_acc.data_ptr()), C.c_void_p(sched.data_ptr()),
                                             nsched, nseg, C.c_void_p(sched_of_env.data_ptr()), float(lin_tol), float(ang_tol), int(tail_after),
                                             C.c_void_p(acc.data_ptr()), self._stream()))
+
+    def fall_row_floats(self, ring: int) -> int:
+        """Floats of one env's row of the fall recorder with a ring of `ring` samples (`odk_fall_row_floats`): FALL_HEAD + ring * (FALL_SAMPLE +
+        nq).  OdkError for a ring outside 1 .. FALL_MAX_RING."""
+        if isinstance(ring, bool) or int(ring) != ring or not 1 <= int(ring) <= FALL_MAX_RING:
+            raise OdkError(f"fall_row_floats: ring = {ring!r} (a whole number of samples, 1 .. {FALL_MAX_RING})")
+        n = int(self.L.odk_fall_row_floats(self._b, int(ring)))
+        if n < 0:
+            raise OdkError(f"fall_row_floats: ring = {ring!r} refused")
+        return n
+
+    def fall_accumulate(self, acc, track_acc, tilt_tol: float, ring: int, torque_limit=None):
+        """One `odk_fall_accumulate` launch over this step's outputs into `acc` (float32 [nenv, row_stride] with row_stride >=
+        `fall_row_floats(ring)`, zeroed before the first step: per env a head and a ring of its last `ring` samples, frozen when its first
+        episode ends), issued after `step` and BEFORE `tracking_accumulate(track_acc)`.  `tilt_tol`: the sine of the lean up to which a sample
+        counts as upright (finite, >= 0); `torque_limit` as `gait_accumulate`'s.  Needs bound commands."""
+        nfl = self.fall_row_floats(ring)
+        if not hasattr(acc, "dim") or acc.dim() != 2 or int(acc.shape[1]) < nfl:
+            raise OdkError(f"fall_accumulate: acc: expected a torch tensor [{self.nenv}, >= {nfl}] (fall_row_floats({int(ring)})), got "
+                           f"{tuple(acc.shape) if hasattr(acc, 'shape') else type(acc).__name__}")
+        check_accumulator("fall_accumulate: acc", acc, self.nenv, int(acc.shape[1]), self.device)
+        check_accumulator("fall_accumulate: track_acc", track_acc, self.nenv, TRACK_NACC, self.device)
+        if torque_limit is not None:
+            if not hasattr(torque_limit, "dim") or torque_limit.dim() != 1:
+                raise OdkError(f"fall_accumulate: torque_limit: expected a 1-D torch tensor or None, got {type(torque_limit).__name__}")
+            check_accumulator("fall_accumulate: torque_limit", torque_limit.unsqueeze(0), 1, self.model.nu, self.device)      # as one row of [1, nu]
+        if self.commands is None:
+            raise OdkError("fall_accumulate: no commands bound (bind_commands)")
+        _chk(self.L.odk_fall_accumulate(self._b, C.c_void_p(self.priv.data_ptr()), C.c_void_p(self.done.data_ptr()),
+                                        C.c_void_p(self.truncation.data_ptr()), C.c_void_p(track_acc.data_ptr()),
+                                        C.c_void_p(torque_limit.data_ptr()) if torque_limit is not None else None, float(tilt_tol), int(ring),
+                                        C.c_void_p(acc.data_ptr()), int(acc.shape[1]), self._stream()))
 
     def physics_step(self, ctrl, n_substeps: int = 10):
         assert ctrl.is_cuda and ctrl.dtype == self.torch.float32 and ctrl.is_contiguous() and tuple(ctrl.shape) == (self.nenv, self.model.nu)

@@ -81,6 +81,22 @@ the error peaks after the response, the overshoot per axis past the command in t
 the samples later than `--response_tail_after` steps into the segment (`reduce_response`).  `--gait` and `--imitation_report` combine with
 schedules, one object per schedule row; pushes and `--posture` do not (their figures assume one command per episode), and the response
 figures cover vx, vy and wz although all seven entries of a segment are applied.  Without `--sequence` / `--then` nothing changes.
+
+Falls (why, when and which way does it go down? -- what watching one robot tip over in that viewer shows, for every env that falls):
+
+    python -m open_duck_playground_amd.track --checkpoint <ckpt> --command 0.15 0 0 --push_grid magnitude=0:1.5:6,direction=0:315:8 --falls --save_falls falls.npz
+
+`--falls` adds one launch (`odk_fall_accumulate`) to the captured step, before the tracking accumulator.  It is a recorder, not a sum: per
+env a ring of the last `--fall_ring` samples of its first episode -- the up vector, gyro, local velocity, root height, contacts, command
+errors, the number of saturated actuators and the whole `qpos`, read on the device from the batch's own state -- that freezes when the
+episode ends, plus the last sample at which the lean was within `--fall_tilt` and the contacts then.  Nothing comes to the host before the
+end of the run.  Every command row (with pushes every cell, with schedules every schedule row) gains a "falls" object: the fall rate and
+the fall step's quartiles, the direction of the fall in the base body's frame (forward / backward / left / right shares) and in the
+world, the onset (how long before the termination the robot left the upright, and on which foot it stood then), the share of falls with
+a saturated actuator in the ring, how close the survivors came, and the mean profile of lean, height, roll/pitch rate, command error and
+saturation over the samples before the termination (`reduce_falls`).  `--save_falls PATH` writes the rings of the first
+`--save_falls_max` falls of every row (cell) as an .npz of clips that replay like `--save_qpos` (`fall_clips`).  `--falls` combines with
+every flag above.  Without it nothing changes.
 """
 from __future__ import annotations
 
@@ -120,6 +136,11 @@ from .engine import (SCHED_MAX_SEGMENTS, SCHED_SEG_FLOATS, SCHED_NEVER, RESP_NAC
                      RESP_FELL as R_FELL, RESP_STEPS_TO_FALL as R_STEPS_TO_FALL, RESP_FIRST_IN as R_FIRST_IN, RESP_LAST_OFF as R_LAST_OFF,
                      RESP_PEAK_LIN_ERR as R_PEAK_LIN, RESP_PEAK_ANG_ERR as R_PEAK_ANG, RESP_SUM as R_SUM, RESP_SQERR as R_SQERR,
                      RESP_OVERSHOOT as R_OVERSHOOT, RESP_TAIL_SAMPLES as R_TAIL_SAMPLES, RESP_TAIL_SUM as R_TAIL_SUM)      # ODK_SCHED_* / ODK_RESP_*
+
+from .engine import (FALL_HEAD, FALL_SAMPLE, FALL_MAX_RING, FALL_SAMPLES as F_SAMPLES, FALL_FELL as F_FELL, FALL_STEP as F_STEP,
+                     FALL_LAST_UPRIGHT as F_LAST_UPRIGHT, FALL_UPRIGHT_CONTACT as F_UPRIGHT_CONTACT, FALL_TILT_PEAK as F_TILT_PEAK,
+                     FALL_S_STEP as FS_STEP, FALL_S_UP as FS_UP, FALL_S_GYRO as FS_GYRO, FALL_S_HEIGHT as FS_HEIGHT, FALL_S_LIN_ERR as FS_LIN_ERR,
+                     FALL_S_SAT as FS_SAT)      # ODK_FALL_*
 
 COMMAND_KEYS = ("vx", "vy", "wz", "neck_pitch", "head_pitch", "head_yaw", "head_roll")   # the order of cmd_range (include/odk.h)
 NACC = 12
@@ -737,6 +758,192 @@ IMITATION_FOOT_KEYS = ("foot", "contact_agreement", "stance_share", "reference_s
                        "touchdown_lag_steps", "touchdown_lag_s", "touchdown_lag_abs_steps")
 
 
+DEFAULT_FALL_RING = 50        # one second at the duck's ctrl_dt of 0.02 s
+DEFAULT_FALL_TILT = 0.35      # BUILD-DEFINED default (the reference has no such measure): a lean of 20 degrees still counts as upright
+DEFAULT_SAVE_FALLS_MAX = 16
+FALL_SECTORS = ("forward", "left", "backward", "right")      # 90-degree sectors of atan2(d_y, d_x), centred on +x, +y, -x, -y
+MIN_FALL_DIRECTION = 1e-6      # a body-frame lean shorter than this has no direction
+
+
+def falls_refusal(args) -> Optional[str]:
+    """Why the fall flags cannot run as given, or None.  Host work only, so `run` asks before it makes a batch."""
+    if getattr(args, "save_falls", None) and not getattr(args, "falls", False):
+        return "--save_falls writes the clips of the fall report: give --falls too"
+    ring = getattr(args, "fall_ring", DEFAULT_FALL_RING)
+    if int(ring) != ring or not 1 <= int(ring) <= FALL_MAX_RING:
+        return f"--fall_ring is a number of samples from 1 to {FALL_MAX_RING}, got {ring}"
+    tilt = float(getattr(args, "fall_tilt", DEFAULT_FALL_TILT))
+    if not np.isfinite(tilt) or tilt < 0 or tilt > np.pi / 2:
+        return f"--fall_tilt is a lean in radians: finite, >= 0 and at most pi / 2, got {tilt}"
+    if int(getattr(args, "save_falls_max", DEFAULT_SAVE_FALLS_MAX)) < 1:
+        return f"--save_falls_max is a number of clips >= 1, got {args.save_falls_max}"
+    return None
+
+
+def fall_tilt_tol(rad: float) -> float:
+    """`--fall_tilt RAD` as odk_fall_accumulate takes it: the sine of the lean, as the float32 the launch receives."""
+    return float(np.float32(np.sin(float(rad))))
+
+
+def fall_ring_order(n: int, ring: int) -> np.ndarray:
+    """The slots of a ring of `ring` that hold samples after `n` of them, oldest first: min(n, ring) slots, starting at slot n % ring once
+    n >= ring and at slot 0 before.  The one unrolling rule of `reduce_falls` and `fall_clips`."""
+    n, ring = int(n), int(ring)
+    start = n % ring if n >= ring else 0
+    return (start + np.arange(min(n, ring), dtype=np.int64)) % ring
+
+
+def fall_rows(acc: np.ndarray, ring: int, nq: int):
+    """(head [nenv, FALL_HEAD], slots [nenv, ring, FALL_SAMPLE + nq]) views of a fall accumulator whose rows may be wider than they need."""
+    acc = np.asarray(acc)
+    w = FALL_SAMPLE + int(nq)
+    nfl = FALL_HEAD + int(ring) * w
+    if acc.ndim != 2 or acc.shape[1] < nfl:
+        raise ValueError(f"a fall accumulator of ring {ring} and nq {nq} has rows of at least {nfl} floats, got {acc.shape}")
+    return acc[:, :FALL_HEAD], acc[:, FALL_HEAD:nfl].reshape(acc.shape[0], int(ring), w)
+
+
+def _quartiles(x: np.ndarray, scale: float = 1.0) -> Dict:
+    if not x.size:
+        return dict(q25=None, median=None, q75=None)
+    q = np.percentile(np.asarray(x, np.float64), [25, 50, 75]) * scale
+    return dict(q25=float(q[0]), median=float(q[1]), q75=float(q[2]))
+
+
+def _spread(x: np.ndarray, scale: float = 1.0) -> Dict:
+    x = np.asarray(x, np.float64)
+    return dict(min=float(x.min() * scale) if x.size else None, **_quartiles(x, scale), max=float(x.max() * scale) if x.size else None)
+
+
+def _mean_unit(v: np.ndarray) -> Optional[List[float]]:
+    """Mean of the unit vectors of the rows of v [k, 2] that have a direction; None without one."""
+    v = np.asarray(v, np.float64).reshape(-1, 2)
+    r = np.hypot(v[:, 0], v[:, 1])
+    ok = r > 0
+    if not ok.any():
+        return None
+    m = (v[ok] / r[ok, None]).mean(0)
+    return [float(m[0]), float(m[1])]
+
+
+def body_lean(quat: np.ndarray) -> np.ndarray:
+    """d = -(R(q)^T e_z)[0:2] for base quaternions [k, 4] (w x y z, normalised here): the planar part, in the base body's frame, of the
+    direction the body leans to -- +x forward, +y left.  A zero quaternion gives a zero d."""
+    q = np.asarray(quat, np.float64).reshape(-1, 4)
+    nrm = np.linalg.norm(q, axis=1, keepdims=True)
+    q = q / np.where(nrm > 0, nrm, 1.0)
+    w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    return -np.stack([2.0 * (x * z - w * y), 2.0 * (y * z + w * x)], axis=1)
+
+
+def reduce_falls(acc: np.ndarray, commands: Sequence, envs_per_block: int, dt: float, ring: int, nq: int) -> List[Dict]:
+    """One "falls" object per block of `envs_per_block` envs (a block per entry of `commands`: the command blocks of `command_blocks`, the
+    (command, push) cells of `cell_blocks` or the schedules of `schedule_blocks`), from the fall accumulator ([nenv, >= FALL_HEAD + ring *
+    (FALL_SAMPLE + nq)], include/odk.h ODK_FALL_*), in float64.  A fall is an env with FELL set; its ring is unrolled by `fall_ring_order`.
+    `episodes` the block's envs, `falls`, `fall_rate`; `fall_step` / `fall_time_s` = FALL_STEP (* dt): min, q25, median, q75, max over the
+    falls.  `direction`, from the last sample of each fall: shares of `forward`, `left`, `backward`, `right` -- the 90-degree sector of
+    atan2(d_y, d_x), d = `body_lean` of the sample's base quaternion qpos[3:7] -- and of `undetermined` (no sample: the fall ended step 0;
+    or |d| < 1e-6), `mean_unit_vector` of d over the determined falls and `world_mean_unit_vector` of the sample's up vector's (x, y).
+    `onset`: `samples` and `seconds` (q25, median, q75) from the last upright sample (LAST_UPRIGHT, lean within the tolerance) to the
+    termination, SAMPLES - LAST_UPRIGHT + 1, over the falls that were upright at some sample; `never_upright` the share of the falls that
+    never were; `support_at_onset` the shares of `left`, `right`, `both`, `none` of UPRIGHT_CONTACT over the former.  `saturated_before`:
+    the share of falls with S_SAT > 0 at a sample in the ring.  `tilt_peak_survivors`: `envs`, `mean` and `max` of TILT_PEAK over the
+    block's envs that did not fall.  `profile`: lists of length `ring`, entry k - 1 for the k-th last sample before the termination --
+    `count` of falls that have one, and over them the means of `tilt` = hypot(up_x, up_y), `root_height`, `roll_pitch_rate` =
+    hypot(gyro_x, gyro_y), `lin_error` and `saturated_actuators`; None where the count is 0.  A figure over an empty set is None."""
+    head, slots = fall_rows(acc, ring, nq)
+    head, slots = head.astype(np.float64), slots.astype(np.float64)
+    E, dt, ring = int(envs_per_block), float(dt), int(ring)
+    out = []
+    for c, _ in enumerate(commands):
+        H, S = head[c * E:(c + 1) * E], slots[c * E:(c + 1) * E]
+        fell = H[:, F_FELL] != 0
+        idx = np.flatnonzero(fell)
+        k = int(idx.size)
+        n = H[idx, F_SAMPLES].astype(np.int64)
+        share = lambda m: float(np.count_nonzero(m) / k) if k else None
+        # direction: the last sample of every fall that has one
+        has = n > 0
+        last = S[idx[has], (n[has] - 1) % ring]
+        d = body_lean(last[:, FALL_SAMPLE + 3:FALL_SAMPLE + 7])
+        det = np.hypot(d[:, 0], d[:, 1]) >= MIN_FALL_DIRECTION
+        sector = np.floor(((np.arctan2(d[:, 1], d[:, 0]) + np.pi / 4) % (2 * np.pi)) / (np.pi / 2)).astype(np.int64) % 4
+        direction = {name: share(det & (sector == i)) for i, name in enumerate(FALL_SECTORS)}
+        direction = dict(forward=direction["forward"], backward=direction["backward"], left=direction["left"], right=direction["right"],
+                         undetermined=float((k - np.count_nonzero(det)) / k) if k else None,
+                         mean_unit_vector=_mean_unit(d[det]), world_mean_unit_vector=_mean_unit(last[:, FS_UP:FS_UP + 2]))
+        # onset
+        lu = H[idx, F_LAST_UPRIGHT]
+        was = lu > 0
+        gap = n[was] - lu[was] + 1
+        cl, cr = H[idx[was], F_UPRIGHT_CONTACT] != 0, H[idx[was], F_UPRIGHT_CONTACT + 1] != 0
+        nw = int(np.count_nonzero(was))
+        sup = lambda m: float(np.count_nonzero(m) / nw) if nw else None
+        onset = dict(samples=_quartiles(gap), seconds=_quartiles(gap, dt), never_upright=share(~was),
+                     support_at_onset=dict(left=sup(cl & ~cr), right=sup(cr & ~cl), both=sup(cl & cr), none=sup(~cl & ~cr)))
+        # the rings in time order, aligned at the termination: column k - 1 is the k-th last sample
+        count = np.zeros(ring, np.int64)
+        sums = np.zeros((5, ring))
+        sat_any = np.zeros(k, bool)
+        for i, e in enumerate(idx):
+            r = S[e, fall_ring_order(n[i], ring)][::-1]
+            m = r.shape[0]
+            count[:m] += 1
+            sums[0, :m] += np.hypot(r[:, FS_UP], r[:, FS_UP + 1])
+            sums[1, :m] += r[:, FS_HEIGHT]
+            sums[2, :m] += np.hypot(r[:, FS_GYRO], r[:, FS_GYRO + 1])
+            sums[3, :m] += r[:, FS_LIN_ERR]
+            sums[4, :m] += r[:, FS_SAT]
+            sat_any[i] = bool((r[:, FS_SAT] > 0).any())
+        prof = lambda j: [float(sums[j, i] / count[i]) if count[i] else None for i in range(ring)]
+        surv = H[~fell, F_TILT_PEAK]
+        out.append(dict(
+            episodes=E, falls=k, fall_rate=float(k / E) if E else None,
+            fall_step=_spread(H[idx, F_STEP]), fall_time_s=_spread(H[idx, F_STEP], dt),
+            direction=direction, onset=onset, saturated_before=share(sat_any),
+            tilt_peak_survivors=dict(envs=int(surv.size), mean=_mean_or_none(surv), max=float(surv.max()) if surv.size else None),
+            profile=dict(count=[int(x) for x in count], tilt=prof(0), root_height=prof(1), roll_pitch_rate=prof(2), lin_error=prof(3),
+                         saturated_actuators=prof(4))))
+    return out
+
+
+FALL_KEYS = ("episodes", "falls", "fall_rate", "fall_step", "fall_time_s", "direction", "onset", "saturated_before", "tilt_peak_survivors", "profile")
+FALL_DIRECTION_KEYS = ("forward", "backward", "left", "right", "undetermined", "mean_unit_vector", "world_mean_unit_vector")
+FALL_PROFILE_KEYS = ("count", "tilt", "root_height", "roll_pitch_rate", "lin_error", "saturated_actuators")
+FALL_CLIP_KEYS = ("qpos", "valid", "steps", "env", "row", "fall_step", "command")
+
+
+def fall_clips(acc: np.ndarray, commands: Sequence[Sequence[float]], envs_per_block: int, ring: int, nq: int, max_per_block: int) -> Dict:
+    """The pre-fall clips `--save_falls` writes: the first `max_per_block` falls of every block (`reduce_falls`'s blocks, `commands[b]` the 7
+    command entries of block b), in env order.  `qpos` [k, ring, nq] float32 in time order (`fall_ring_order`), zero-padded at the FRONT:
+    clip i's real samples are qpos[i, ring - valid[i]:], the last one the step before the termination; `valid` [k] int32; `steps` [k, ring]
+    int32, the first-episode step index of every sample (-1 in the padding); `env` [k], `row` [k] (the block) and `fall_step` [k] int32;
+    `command` [k, 7] float32."""
+    head, slots = fall_rows(acc, ring, nq)
+    E, ring, nq = int(envs_per_block), int(ring), int(nq)
+    envs = [e for b, _ in enumerate(commands) for e in (b * E + np.flatnonzero(head[b * E:(b + 1) * E, F_FELL] != 0)[:int(max_per_block)])]
+    k = len(envs)
+    clips = dict(qpos=np.zeros((k, ring, nq), np.float32), valid=np.zeros(k, np.int32), steps=np.full((k, ring), -1, np.int32),
+                 env=np.asarray(envs, np.int32).reshape(k), row=np.zeros(k, np.int32), fall_step=np.zeros(k, np.int32),
+                 command=np.zeros((k, 7), np.float32))
+    for i, e in enumerate(envs):
+        r = slots[e, fall_ring_order(head[e, F_SAMPLES], ring)]
+        m = r.shape[0]
+        clips["valid"][i] = m
+        if m:
+            clips["qpos"][i, ring - m:] = r[:, FALL_SAMPLE:]
+            clips["steps"][i, ring - m:] = r[:, FS_STEP].astype(np.int32)
+        clips["row"][i] = e // E
+        clips["fall_step"][i] = int(head[e, F_STEP])
+        clips["command"][i] = np.asarray(commands[e // E], np.float32)[:7]
+    return clips
+
+
+def save_falls(path: str, clips: Dict, dt: float) -> None:
+    """`fall_clips` and the control step as an .npz: qpos[i, ring - valid[i]:] with dt has `--save_qpos`'s meaning."""
+    np.savez(path, dt=np.float64(dt), **clips)
+
+
 def reduce_tracking(acc: np.ndarray, commands: Sequence[Sequence[float]], envs_per_command: int) -> List[Dict]:
     """The per-command rows of the report from the accumulator ([nenv, 12], include/odk.h ODK_TRACK_*).  Velocity statistics are over
     the velocity samples of the block's envs (the steps of their first episode that did not end it), pooled; the fall rate is the
@@ -830,11 +1037,13 @@ class Tracker:
     -- a dict of `table` (`schedule_table`), `map` (`schedule_blocks`), `tolerance` (lin, ang) and `tail_after` -- the commands change inside
     the captured step: the Tracker keeps the table and the map on the device and owns a response accumulator; `reset` zeroes the
     accumulators and issues `odk_command_schedule_apply` once before the env's reset, and the step issues it again before the env step and
-    `odk_response_accumulate` next to the other accumulators.  The bound command tensor is then written by the Tracker."""
+    `odk_response_accumulate` next to the other accumulators.  The bound command tensor is then written by the Tracker.  With `falls` -- a
+    dict of `ring` (samples) and `tilt_tol` (the sine of the upright lean) -- it owns a fall recorder ([num_envs, fall_row_floats(ring)]) and
+    the torque limits, and the step gains `odk_fall_accumulate` next to the other accumulators."""
 
     def __init__(self, env, net, use_graph: bool = True, kicks=None, push_at: int = DEFAULT_PUSH_AT, push_tolerance=DEFAULT_PUSH_TOLERANCE,
                  gait: bool = False, posture: bool = False, posture_tolerance: float = DEFAULT_POSTURE_TOLERANCE,
-                 imitation: bool = False, schedule: Optional[Dict] = None):
+                 imitation: bool = False, schedule: Optional[Dict] = None, falls: Optional[Dict] = None):
         import torch
         self.env, self.net, self.torch = env, net, torch
         b = env.batch
@@ -865,6 +1074,12 @@ class Tracker:
             self.response_tolerance = tuple(float(x) for x in schedule.get("tolerance", DEFAULT_PUSH_TOLERANCE))
             self.response_tail_after = int(schedule.get("tail_after", DEFAULT_RESPONSE_TAIL_AFTER))
             self.response_acc = torch.zeros(env.num_envs, RESP_NACC, device=b.obs.device)
+        self.fall_acc = self.fall_ring = self.fall_tilt_tol = None
+        if falls is not None:
+            self.fall_ring, self.fall_tilt_tol = int(falls["ring"]), float(falls["tilt_tol"])
+            self.fall_acc = torch.zeros(env.num_envs, b.fall_row_floats(self.fall_ring), device=b.obs.device)
+            if self.torque_limit is None:
+                self.torque_limit = torch.from_numpy(torque_limits(env.mj_model)).to(b.obs.device)
         from .ppo.learner import fused_policy
         self.fp = fused_policy(net, env.num_envs)
         self.use_graph = use_graph
@@ -894,6 +1109,8 @@ class Tracker:
             b.imitation_accumulate(self.imitation_acc, self.acc, self.period_steps)
         if self.response_acc is not None:
             b.response_accumulate(self.response_acc, self.acc, self.sched, self.sched_map, *self.response_tolerance, self.response_tail_after)
+        if self.fall_acc is not None:
+            b.fall_accumulate(self.fall_acc, self.acc, self.fall_tilt_tol, self.fall_ring, self.torque_limit)
         b.tracking_accumulate(self.acc)
 
     def reset(self, seed: int):
@@ -911,6 +1128,8 @@ class Tracker:
             self.posture_acc.zero_()
         if self.imitation_acc is not None:
             self.imitation_acc.zero_()
+        if self.fall_acc is not None:
+            self.fall_acc.zero_()
         if self.fp is not None:
             self.fp.refresh()                       # its packed weight copy <- the current parameters
 
@@ -954,6 +1173,12 @@ def run(args, out=sys.stdout) -> Dict:
         why = imitation_refusal(args)
         if why:
             raise SystemExit(why)
+    why = falls_refusal(args)      # likewise
+    if why:
+        raise SystemExit(why)
+    falls = None
+    if getattr(args, "falls", False):
+        falls = dict(ring=int(getattr(args, "fall_ring", DEFAULT_FALL_RING)), tilt_tol=fall_tilt_tol(getattr(args, "fall_tilt", DEFAULT_FALL_TILT)))
     E = int(args.envs_per_command)
     n = len(commands) * max(len(pushes), 1) * E
     torch.cuda.set_device(args.device)
@@ -984,18 +1209,18 @@ def run(args, out=sys.stdout) -> Dict:
         cmd = torch.from_numpy(cmd_np).to(dev)
         env.set_commands(cmd)
         tr = Tracker(env, net, kicks=torch.from_numpy(kicks_np).to(dev), push_at=push_at, push_tolerance=tol, gait=gait, posture=posture,
-                     posture_tolerance=posture_tol, imitation=imitation)
+                     posture_tolerance=posture_tol, imitation=imitation, falls=falls)
     elif schedules is not None:
         resp_tol = response_tolerance(args)
         tail_after = int(getattr(args, "response_tail_after", DEFAULT_RESPONSE_TAIL_AFTER))
         cmd = torch.from_numpy(command_blocks(commands, E)).to(dev)      # segment 0's; the Tracker's apply launch rewrites it every step
         env.set_commands(cmd)
-        tr = Tracker(env, net, gait=gait, imitation=imitation,
+        tr = Tracker(env, net, gait=gait, imitation=imitation, falls=falls,
                      schedule=dict(table=schedule_table(schedules), map=schedule_blocks(len(schedules), E), tolerance=resp_tol, tail_after=tail_after))
     else:
         cmd = torch.from_numpy(command_blocks(commands, E)).to(dev)
         env.set_commands(cmd)
-        tr = Tracker(env, net, gait=gait, posture=posture, posture_tolerance=posture_tol, imitation=imitation)
+        tr = Tracker(env, net, gait=gait, posture=posture, posture_tolerance=posture_tol, imitation=imitation, falls=falls)
     nobs = env.observation_size["state"][0]
     T = int(args.episode_length)
     save_obs_path, save_qpos_path = getattr(args, "save_obs", None), getattr(args, "save_qpos", None)
@@ -1017,6 +1242,7 @@ def run(args, out=sys.stdout) -> Dict:
         posture_acc = tr.posture_acc.cpu().numpy() if posture else None
         imitation_acc = tr.imitation_acc.cpu().numpy() if imitation else None
         response_acc = tr.response_acc.cpu().numpy() if schedules is not None else None
+        fall_acc = tr.fall_acc.cpu().numpy() if falls else None
     rows = reduce_tracking(acc, commands, max(len(pushes), 1) * E)
     if pushes:
         for row, extra in zip(rows, reduce_pushes(push_acc, commands, pushes, E, float(env.dt))):
@@ -1047,6 +1273,19 @@ def run(args, out=sys.stdout) -> Dict:
             cells = [cell for row in rows for cell in row["pushes"]]
             for cell, g in zip(cells, reduce_imitation(imitation_acc, cells, E, float(env.dt), imap, imit_joint_names, period_steps)):
                 cell["imitation"] = g
+    if falls:
+        nq = int(env.batch.model.nq)
+        for row, g in zip(rows, reduce_falls(fall_acc, commands, max(len(pushes), 1) * E, float(env.dt), falls["ring"], nq)):
+            row["falls"] = g
+        blocks = rows
+        if pushes:      # and one per (command, push) cell, in `cell_blocks` order
+            blocks = [cell for row in rows for cell in row["pushes"]]
+            for cell, g in zip(blocks, reduce_falls(fall_acc, blocks, E, float(env.dt), falls["ring"], nq)):
+                cell["falls"] = g
+        if getattr(args, "save_falls", None):      # the clips of every row, or with pushes of every cell
+            block_cmds = [row["command"] for row in rows for _ in (row["pushes"] if pushes else [0])]
+            save_falls(args.save_falls, fall_clips(fall_acc, block_cmds, E, falls["ring"], nq,
+                                                   int(getattr(args, "save_falls_max", DEFAULT_SAVE_FALLS_MAX))), float(env.dt))
     settings = dict(checkpoint=args.checkpoint, env=args.env, task=args.task, xml=args.xml, cone=args.cone,
                     hfield_up_normals_only=bool(args.hfield_up_normals_only), envs_per_command=E, episode_length=T, seed=int(args.seed),
                     num_envs=n, dt=float(env.dt), policy="deterministic tanh(loc)", fused_policy=tr.fp is not None, graph=tr.graph is not None,
@@ -1064,6 +1303,10 @@ def run(args, out=sys.stdout) -> Dict:
         settings.update(posture=True, posture_tolerance=posture_tol)
     if imitation:
         settings.update(imitation_report=True, imitation_period_steps=period_steps)
+    if falls:
+        settings.update(falls=True, fall_ring=falls["ring"], fall_tilt=float(getattr(args, "fall_tilt", DEFAULT_FALL_TILT)),
+                        fall_tilt_tol=falls["tilt_tol"], save_falls=getattr(args, "save_falls", None),
+                        save_falls_max=int(getattr(args, "save_falls_max", DEFAULT_SAVE_FALLS_MAX)))
     report = make_report(settings, rows)
     if save_obs_path:
         save_obs(save_obs_path, obs_hist.cpu().numpy())
@@ -1135,6 +1378,22 @@ def build_parser() -> argparse.ArgumentParser:
                         "used against the reference's and their ratio; the reward's joint_pos, joint_vel and contact terms; per foot the contact "
                         "agreement, stance shares, touchdowns and the touchdown lag behind the reference's (negative: early); the planar speed error.  "
                         "The Joystick task with the imitation reward: the duck, or another robot with --reference_motion")
+    p.add_argument("--falls", action="store_true",
+                   help="add a \"falls\" object to every command row (push cell, schedule row): fall rate and fall step, the direction of the fall "
+                        "(forward / backward / left / right in the base body's frame, from the last recorded sample), the onset (time from the last "
+                        "upright sample to the termination, and the support foot then), the share of falls with a saturated actuator, how close the "
+                        "survivors came, and the mean profile of lean, height, roll/pitch rate, command error and saturation before the termination")
+    p.add_argument("--fall_ring", type=int, default=DEFAULT_FALL_RING, metavar="N",
+                   help=f"samples kept per env before the end of its first episode, 1 .. {FALL_MAX_RING} (50: one second at the duck's control step).  "
+                        "Device memory: (16 + N * (16 + nq)) floats per env, 61 MB for 8192 duck envs at the default; read by --falls only")
+    p.add_argument("--fall_tilt", type=float, default=DEFAULT_FALL_TILT, metavar="RAD",
+                   help="the lean (rad, 0 .. pi/2) up to which a sample counts as upright; the device compares the sine (BUILD-DEFINED default); "
+                        "read by --falls only")
+    p.add_argument("--save_falls", type=str, default=None, metavar="PATH",
+                   help="with --falls: the pre-fall clips of the first --save_falls_max falls of every row (with pushes: cell) as .npz -- qpos "
+                        "[k, ring, nq] in time order, zero-padded at the front, valid [k], steps, env, row, fall_step, command and dt; "
+                        "qpos[i, ring - valid[i]:] replays like --save_qpos")
+    p.add_argument("--save_falls_max", type=int, default=DEFAULT_SAVE_FALLS_MAX, metavar="K", help="clips kept per row (cell); read by --save_falls only")
     p.add_argument("--episode_length", type=int, default=1000)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--device", type=int, default=0)

@@ -1,0 +1,294 @@
+"""CPU checks of the fall report of `track --falls`: the C-ABI exports and the slot names, the ring's unrolling rule, the report's reduction
+of a hand-built fall accumulator (a fall at step 0, a truncated survivor, a fall that never was upright, falls forward, backward, to the
+left and to the right by their base quaternion, a saturated one, rings shorter than, as long as and several times wrapped around their
+length), the clips `--save_falls` writes, every refusal by its message, the flags' defaults and the tensor checks of `Batch.fall_accumulate`."""
+import ctypes
+import json
+import os
+import re
+import types
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+HEAD_SLOTS = dict(SAMPLES=0, FELL=1, STEP=2, LAST_UPRIGHT=3, UPRIGHT_CONTACT=4, TILT_PEAK=6)
+SAMPLE_SLOTS = dict(S_STEP=0, S_UP=1, S_GYRO=4, S_LINVEL=7, S_HEIGHT=10, S_CONTACT=11, S_LIN_ERR=13, S_ANG_ERR=14, S_SAT=15)
+HEAD, SAMPLE, MAX_RING = 16, 16, 64
+
+
+def test_libodk_exports_the_fall_recorder_and_the_header_names_its_slots():
+    from open_duck_playground_amd import engine, track
+    engine.build_library()
+    lib = ctypes.CDLL(engine.LIB_PATH)
+    for name in ("odk_fall_accumulate", "odk_fall_row_floats"):
+        assert hasattr(lib, name), name
+        assert name in engine.EXPORTED_SYMBOLS
+    text = open(os.path.join(ROOT, "include", "odk.h")).read()
+    for name, value in (("HEAD", HEAD), ("SAMPLE", SAMPLE), ("MAX_RING", MAX_RING)):
+        assert re.search(rf"#define ODK_FALL_{name} {value}\b", text), name
+        assert getattr(engine, "FALL_" + name) == value
+    names = {k: int(v) for k, v in re.findall(r"\bODK_FALL_([A-Z_]+) = (\d+)", text)}
+    assert names == {**HEAD_SLOTS, **SAMPLE_SLOTS}                # the header names these slots and no others
+    for name, slot in names.items():
+        assert getattr(engine, "FALL_" + name) == slot, name
+    # no two slots overlap, the head fits ODK_FALL_HEAD and a sample's scalars fill ODK_FALL_SAMPLE exactly
+    used = sorted(s + i for name, s in HEAD_SLOTS.items() for i in range(2 if name == "UPRIGHT_CONTACT" else 1))
+    assert len(set(used)) == len(used) and used[-1] < HEAD
+    width = dict(S_UP=3, S_GYRO=3, S_LINVEL=3, S_CONTACT=2)
+    assert sorted(s + i for name, s in SAMPLE_SLOTS.items() for i in range(width.get(name, 1))) == list(range(SAMPLE))
+    assert track.FALL_MAX_RING == MAX_RING and track.DEFAULT_FALL_RING == 50
+
+
+def test_the_unrolling_rule():
+    """A fall with n samples holds min(n, ring) of them; the oldest is in slot n % ring when n >= ring, otherwise in slot 0.  Checked against
+    a ring that was really written: sample s into slot s % ring."""
+    from open_duck_playground_amd import track
+    ring = 5
+    for n in (0, 1, ring - 1, ring, ring + 1, 3 * ring + 2):
+        held = np.full(ring, -1)
+        for s in range(n):
+            held[s % ring] = s
+        order = track.fall_ring_order(n, ring)
+        assert len(order) == min(n, ring)
+        np.testing.assert_array_equal(held[order], np.arange(max(n - ring, 0), n), err_msg=str(n))
+    np.testing.assert_array_equal(track.fall_ring_order(3, 5), [0, 1, 2])
+    np.testing.assert_array_equal(track.fall_ring_order(5, 5), [0, 1, 2, 3, 4])
+    np.testing.assert_array_equal(track.fall_ring_order(6, 5), [1, 2, 3, 4, 0])
+    np.testing.assert_array_equal(track.fall_ring_order(17, 5), [2, 3, 4, 0, 1])
+    np.testing.assert_array_equal(track.fall_ring_order(7, 1), [0])
+
+
+# ---- a hand-built accumulator: 12 envs in 2 rows of 6, ring 4, nq 9, dt 0.02, tilt_tol 0.3
+RING, NQ, DT, TOL, E = 4, 9, 0.02, 0.3, 6
+WIDTH = HEAD + RING * (SAMPLE + NQ) + 2      # two floats wider than a row needs: the reducers read the row's own part
+PITCH_FWD = [np.cos(0.25), 0.0, np.sin(0.25), 0.0]      # w x y z: 0.5 rad about +y, the nose goes down
+PITCH_BACK = [np.cos(0.25), 0.0, -np.sin(0.25), 0.0]
+ROLL_POS = [np.cos(0.25), np.sin(0.25), 0.0, 0.0]       # +0.5 rad about +x: the left side rises, the robot goes down to its right
+ROLL_NEG = [np.cos(0.25), -np.sin(0.25), 0.0, 0.0]
+IDENT = [1.0, 0.0, 0.0, 0.0]
+
+
+def _sample(e, s, up, quat=IDENT, contact=(1, 1), sat=0):
+    qpos = np.concatenate([[0.01 * s, 0.001 * e, 0.15], quat, [0.1 * e, -0.1 * s]])
+    return dict(step=s, up=up, gyro=(0.1 * (e + 1), 0.05 * s, 1.0), linvel=(0.1, 0.0, 0.0), height=0.15 - 0.002 * s, contact=contact,
+                lin=0.01 * (s + 1) * (e + 1), ang=0.3, sat=sat, qpos=qpos)
+
+
+def _row(samples, fell=None):
+    """What odk_fall_accumulate leaves after these samples (and, fell = t, a termination at step t without truncation)."""
+    r = np.zeros(WIDTH, np.float32)
+    for s, x in enumerate(samples):
+        slot = r[HEAD + (s % RING) * (SAMPLE + NQ):][:SAMPLE + NQ]
+        slot[:] = np.concatenate([[x["step"]], x["up"], x["gyro"], x["linvel"], [x["height"]], x["contact"], [x["lin"], x["ang"], x["sat"]], x["qpos"]])
+        tilt = np.hypot(np.float32(x["up"][0]), np.float32(x["up"][1]))
+        r[0] = s + 1
+        r[6] = max(r[6], np.float32(tilt))
+        if tilt <= TOL:
+            r[3] = s + 1
+            r[4:6] = x["contact"]
+    if fell is not None:
+        r[1], r[2] = 1, fell
+    r[-2:] = 9.0
+    return r
+
+
+def _build():
+    up_ok, up_off = (0.1, 0.0, 0.99), (0.0, 0.5, 0.87)
+    S = {
+        0: [],                                                                                    # falls in step 0: no sample
+        1: [_sample(1, s, (0.2, 0.0, 0.98)) for s in range(6)],                                   # truncated at step 6: a survivor
+        2: [_sample(2, s, up_off) for s in range(2)] + [_sample(2, 2, (0.6, 0.0, 0.8), PITCH_FWD)],                 # never upright, n < ring
+        3: [_sample(3, 0, up_ok), _sample(3, 1, up_ok, sat=2), _sample(3, 2, up_ok, contact=(1, 0)),
+            _sample(3, 3, (0.0, -0.5, 0.87), ROLL_POS)],                                                           # n == ring, saturated
+        4: [_sample(4, s, up_ok) for s in range(13)] + [_sample(4, 13, (-0.3, 0.4, 0.87), PITCH_BACK)],             # n == 3 ring + 2; upright up to its 13th
+        5: [_sample(5, s, (0.0, 0.4, 0.9)) for s in range(10)],                                   # still running: a survivor
+        6: [_sample(6, 0, up_ok, contact=(0, 1)), _sample(6, 1, (0.0, 0.6, 0.8), ROLL_NEG)],
+        7: [_sample(7, s, up_ok) for s in range(3)],
+        8: [_sample(8, s, up_ok) for s in range(3)],
+        9: [_sample(9, s, up_ok) for s in range(3)],
+        10: [_sample(10, s, up_ok) for s in range(3)],
+        11: [_sample(11, 0, (0.0, 0.0, 1.0), IDENT, contact=(0, 0))],                             # falls upright: no direction
+    }
+    fell = {0: 0, 2: 3, 3: 4, 4: 14, 6: 2, 11: 1}
+    acc = np.stack([_row(S[e], fell.get(e)) for e in range(12)])
+    return acc, S, fell
+
+
+COMMANDS = [[0.1, 0, 0, 0, 0, 0, 0], [0, 0, 0.5, 0, 0, 0, 0]]
+
+
+def test_falls_report_reduction():
+    from open_duck_playground_amd import track
+    acc, S, fell = _build()
+    rows = track.reduce_falls(acc, COMMANDS, E, DT, RING, NQ)
+    assert len(rows) == 2 and json.loads(json.dumps(rows)) == rows
+    ap = pytest.approx
+    for g in rows:
+        assert tuple(g) == track.FALL_KEYS and tuple(g["direction"]) == track.FALL_DIRECTION_KEYS and tuple(g["profile"]) == track.FALL_PROFILE_KEYS
+        assert all(len(g["profile"][k]) == RING for k in track.FALL_PROFILE_KEYS)
+    g = rows[0]                                     # falls: envs 0, 2, 3, 4 at steps 0, 3, 4, 14
+    assert g["episodes"] == 6 and g["falls"] == 4 and g["fall_rate"] == ap(4 / 6)
+    assert g["fall_step"] == dict(min=0.0, q25=ap(2.25), median=ap(3.5), q75=ap(6.5), max=14.0)
+    assert g["fall_time_s"] == dict(min=0.0, q25=ap(2.25 * DT), median=ap(3.5 * DT), q75=ap(6.5 * DT), max=ap(14 * DT))
+    d = g["direction"]
+    assert (d["forward"], d["backward"], d["left"], d["right"], d["undetermined"]) == (0.25, 0.25, 0.0, 0.25, 0.25)
+    assert d["mean_unit_vector"] == ap([0.0, -1 / 3], abs=1e-12)                   # (1, 0), (0, -1), (-1, 0)
+    assert d["world_mean_unit_vector"] == ap([(1 + 0 - 0.6) / 3, (0 - 1 + 0.8) / 3], abs=1e-6)
+    o = g["onset"]                                  # envs 3 (4 samples, last upright the 3rd) and 4 (14, the 13th): 2 and 2 steps before the termination
+    assert o["samples"] == dict(q25=ap(2.0), median=ap(2.0), q75=ap(2.0)) and o["seconds"]["median"] == ap(2 * DT)
+    assert o["never_upright"] == 0.5                # env 0 (no sample) and env 2
+    assert o["support_at_onset"] == dict(left=0.5, right=0.0, both=0.5, none=0.0)
+    assert g["saturated_before"] == 0.25            # env 3
+    assert g["tilt_peak_survivors"] == dict(envs=2, mean=ap(0.3), max=ap(0.4))     # envs 1 (0.2) and 5 (0.4)
+    _check_profile(g["profile"], [S[e] for e in (0, 2, 3, 4)], [3, 3, 3, 2])
+    assert g["profile"]["saturated_actuators"][2] == ap(2 / 3)                     # env 3's second sample is its third last
+
+    g = rows[1]                                     # falls: envs 6 (2 samples) and 11 (1)
+    assert g["falls"] == 2 and g["fall_rate"] == ap(2 / 6) and g["fall_step"]["median"] == 1.5 and g["fall_step"]["max"] == 2.0
+    d = g["direction"]
+    assert (d["forward"], d["backward"], d["left"], d["right"], d["undetermined"]) == (0.0, 0.0, 0.5, 0.0, 0.5)
+    assert d["mean_unit_vector"] == ap([0.0, 1.0], abs=1e-12) and d["world_mean_unit_vector"] == ap([0.0, 1.0], abs=1e-12)
+    o = g["onset"]                                  # env 6: upright at its 1st of 2 samples; env 11: at its only one
+    assert o["samples"]["median"] == 1.5 and o["never_upright"] == 0.0 and o["support_at_onset"] == dict(left=0.0, right=0.5, both=0.0, none=0.5)
+    assert g["saturated_before"] == 0.0 and g["tilt_peak_survivors"]["envs"] == 4 and g["tilt_peak_survivors"]["max"] == ap(0.1)
+    _check_profile(g["profile"], [S[6], S[11]], [2, 1, 0, 0])
+    assert g["profile"]["tilt"][2:] == [None, None] and g["profile"]["root_height"][3] is None
+
+    # a block nobody fell in: counts of 0, nothing to average
+    (g,) = track.reduce_falls(acc[7:11], COMMANDS[:1], 4, DT, RING, NQ)
+    assert g["falls"] == 0 and g["fall_rate"] == 0.0 and g["fall_step"]["median"] is None and g["saturated_before"] is None
+    assert all(v is None for v in g["direction"].values()) and g["onset"]["never_upright"] is None and g["onset"]["samples"]["median"] is None
+    assert g["profile"]["count"] == [0] * RING and g["profile"]["tilt"] == [None] * RING and g["tilt_peak_survivors"]["envs"] == 4
+    with pytest.raises(ValueError, match="rows of at least"):
+        track.reduce_falls(acc[:, :HEAD + RING * (SAMPLE + NQ) - 1], COMMANDS, E, DT, RING, NQ)
+
+
+def _check_profile(prof, falls, counts):
+    """Against the samples as they were given, in time order: the k-th last of every fall that kept that many."""
+    assert prof["count"] == counts and all(a >= b for a, b in zip(counts, counts[1:]))
+    f32 = lambda v: float(np.float32(v))
+    for k in range(1, RING + 1):
+        kept = [f[-k] for f in falls if min(len(f), RING) >= k]
+        assert len(kept) == counts[k - 1]
+        if not kept:
+            assert all(prof[name][k - 1] is None for name in prof if name != "count")
+            continue
+        want = dict(tilt=np.mean([np.hypot(f32(x["up"][0]), f32(x["up"][1])) for x in kept]), root_height=np.mean([f32(x["height"]) for x in kept]),
+                    roll_pitch_rate=np.mean([np.hypot(f32(x["gyro"][0]), f32(x["gyro"][1])) for x in kept]),
+                    lin_error=np.mean([f32(x["lin"]) for x in kept]), saturated_actuators=np.mean([x["sat"] for x in kept]))
+        for name, v in want.items():
+            assert prof[name][k - 1] == pytest.approx(v, rel=1e-12), (name, k)
+
+
+def test_body_lean_reads_the_base_quaternion():
+    from open_duck_playground_amd import track
+    d = track.body_lean(np.array([PITCH_FWD, PITCH_BACK, ROLL_POS, ROLL_NEG, IDENT, [0, 0, 0, 0], [2 * x for x in PITCH_FWD]]))
+    s = np.sin(0.5)
+    np.testing.assert_allclose(d, [[s, 0], [-s, 0], [0, -s], [0, s], [0, 0], [0, 0], [s, 0]], atol=1e-12)
+    # a yaw does not change the body-frame direction: yaw by 2 rad, then pitch forward
+    cy, sy = np.cos(1.0), np.sin(1.0)
+    w, x, y, z = PITCH_FWD
+    yawed = [cy * w - sy * z, cy * x - sy * y, cy * y + sy * x, cy * z + sy * w]      # (cy, 0, 0, sy) * q
+    np.testing.assert_allclose(track.body_lean(np.array([yawed])), [[s, 0]], atol=1e-12)
+
+
+def test_save_falls_layout_and_front_padding(tmp_path):
+    from open_duck_playground_amd import track
+    acc, S, fell = _build()
+    clips = track.fall_clips(acc, COMMANDS, E, RING, NQ, 2)      # the first two falls of every row, in env order
+    assert tuple(clips) == track.FALL_CLIP_KEYS
+    np.testing.assert_array_equal(clips["env"], [0, 2, 6, 11])
+    np.testing.assert_array_equal(clips["row"], [0, 0, 1, 1])
+    np.testing.assert_array_equal(clips["valid"], [0, 3, 2, 1])
+    np.testing.assert_array_equal(clips["fall_step"], [0, 3, 2, 1])
+    np.testing.assert_array_equal(clips["command"], np.float32([COMMANDS[0], COMMANDS[0], COMMANDS[1], COMMANDS[1]]))
+    np.testing.assert_array_equal(clips["steps"], [[-1, -1, -1, -1], [-1, 0, 1, 2], [-1, -1, 0, 1], [-1, -1, -1, 0]])
+    assert clips["qpos"].shape == (4, RING, NQ) and clips["qpos"].dtype == np.float32
+    for i, e in enumerate(clips["env"]):
+        m = int(clips["valid"][i])
+        np.testing.assert_array_equal(clips["qpos"][i, :RING - m], 0.0)
+        if m:
+            np.testing.assert_array_equal(clips["qpos"][i, RING - m:], np.float32([x["qpos"] for x in S[e][-m:]]))
+    full = track.fall_clips(acc, COMMANDS, E, RING, NQ, 16)
+    np.testing.assert_array_equal(full["env"], [0, 2, 3, 4, 6, 11])
+    np.testing.assert_array_equal(full["valid"], [0, 3, 4, 4, 2, 1])
+    np.testing.assert_array_equal(full["steps"][3], [10, 11, 12, 13])                   # 14 samples in a ring of 4: unrolled from slot 2
+    np.testing.assert_array_equal(full["qpos"][3], np.float32([x["qpos"] for x in S[4][-4:]]))
+    np.testing.assert_array_equal(full["qpos"][2], np.float32([x["qpos"] for x in S[3]]))
+    path = str(tmp_path / "falls.npz")
+    track.save_falls(path, clips, DT)
+    z = np.load(path)
+    assert sorted(z.files) == sorted(track.FALL_CLIP_KEYS + ("dt",)) and float(z["dt"]) == DT
+    for k in track.FALL_CLIP_KEYS:
+        np.testing.assert_array_equal(z[k], clips[k])
+    # nobody fell: empty arrays of the right shapes
+    none = track.fall_clips(acc[7:11], COMMANDS[:1], 4, RING, NQ, 16)
+    assert none["qpos"].shape == (0, RING, NQ) and none["steps"].shape == (0, RING) and none["command"].shape == (0, 7)
+
+
+REFUSALS = [
+    (["--save_falls", "f.npz"], "--save_falls writes the clips of the fall report: give --falls too"),
+    (["--falls", "--fall_ring", "0"], "--fall_ring is a number of samples from 1 to 64, got 0"),
+    (["--falls", "--fall_ring", "65"], "--fall_ring is a number of samples from 1 to 64, got 65"),
+    (["--falls", "--fall_ring", "-3"], "--fall_ring is a number of samples from 1 to 64"),
+    (["--falls", "--fall_tilt", "-0.1"], "--fall_tilt is a lean in radians: finite, >= 0 and at most pi / 2, got -0.1"),
+    (["--falls", "--fall_tilt", "nan"], "--fall_tilt is a lean in radians"),
+    (["--falls", "--fall_tilt", "inf"], "--fall_tilt is a lean in radians"),
+    (["--falls", "--fall_tilt", "2.0"], "at most pi / 2, got 2.0"),
+    (["--falls", "--save_falls", "f.npz", "--save_falls_max", "0"], "--save_falls_max is a number of clips >= 1, got 0"),
+]
+
+
+@pytest.mark.parametrize("flags,message", REFUSALS, ids=[str(i) for i in range(len(REFUSALS))])
+def test_refusals_say_what_is_wrong(flags, message):
+    """Each as `run` raises it: SystemExit before any batch is made (no GPU here, so getting that far would be another error)."""
+    from open_duck_playground_amd import track
+    args = track.build_parser().parse_args(["--checkpoint", "c.pt", "--command", "0", "0", "0"] + flags)
+    assert re.search(message, track.falls_refusal(args))
+    with pytest.raises(SystemExit, match=message):
+        track.run(args)
+
+
+def test_fall_command_line_flags_and_defaults():
+    """Without --falls the new flags sit at defaults that ask for nothing: no refusal, no Tracker argument, and `run` adds its settings
+    entries and its "falls" keys under `if falls:` only (the GPU suite compares the two reports)."""
+    import inspect
+    from open_duck_playground_amd import track
+    base = ["--checkpoint", "c.pt", "--command", "0", "0", "0"]
+    args = track.build_parser().parse_args(base)
+    assert args.falls is False and args.fall_ring == 50 and args.fall_tilt == 0.35 and args.save_falls is None and args.save_falls_max == 16
+    assert track.falls_refusal(args) is None
+    assert inspect.signature(track.Tracker.__init__).parameters["falls"].default is None
+    # an args object from before the flags (run reads them with getattr) is not refused either
+    assert track.falls_refusal(types.SimpleNamespace()) is None
+    args = track.build_parser().parse_args(base + ["--falls", "--fall_ring", "64", "--fall_tilt", "0", "--save_falls", "f.npz", "--save_falls_max", "3",
+                                                   "--gait", "--posture", "--imitation_report", "--push_grid", "magnitude=0:1:2"])
+    assert track.falls_refusal(args) is None and args.fall_ring == 64 and args.save_falls_max == 3
+    args = track.build_parser().parse_args(base + ["--falls", "--then", "0", "0", "0", "--switch_at", "10"])
+    assert track.falls_refusal(args) is None and len(track.schedules_from_args(args)) == 1
+    assert track.fall_tilt_tol(0.35) == float(np.float32(np.sin(0.35))) and track.fall_tilt_tol(0.0) == 0.0
+    help_text = " ".join(track.build_parser().format_help().split())
+    for word in ("--falls", "--fall_ring", "--fall_tilt", "--save_falls", "--save_falls_max", "61 MB", "zero-padded at the front"):
+        assert word in help_text, word
+
+
+def test_the_batch_method_rejects_bad_tensors():
+    """The tensor checks run before the library is touched, so a stand-in batch (no GPU) reaches them through the real method."""
+    import torch
+    from open_duck_playground_amd import engine
+    n, nq, ring = 8, 21, 4
+    nfl = HEAD + ring * (SAMPLE + nq)
+    stub = types.SimpleNamespace(nenv=n, device=0, model=types.SimpleNamespace(nu=14, nq=nq), commands=object(), fall_row_floats=lambda r: HEAD + int(r) * (SAMPLE + nq))
+    tacc, acc = torch.zeros(n, engine.TRACK_NACC), torch.zeros(n, nfl)
+    for t, what in ((np.zeros((n, nfl), np.float32), "expected a torch tensor"), (torch.zeros(n, nfl - 1), rf">= {nfl}"), (torch.zeros(n + 1, nfl), "shape"),
+                    (torch.zeros(n * nfl), "expected a torch tensor"), (torch.zeros(n, nfl, dtype=torch.float64), "dtype"),
+                    (torch.zeros(nfl + 3, n).t(), "contiguous"), (acc, "cuda:0"), (torch.zeros(n, nfl + 3), "cuda:0")):
+        with pytest.raises(engine.OdkError, match=what) as ei:
+            engine.Batch.fall_accumulate(stub, t, tacc, 0.3, ring)
+        assert "fall_accumulate: acc" in str(ei.value)
+    # the ring is checked by the real fall_row_floats before the library is asked
+    for bad in (0, 65, -1, 2.5, True):
+        with pytest.raises(engine.OdkError, match="fall_row_floats: ring"):
+            engine.Batch.fall_row_floats(stub, bad)
