@@ -250,6 +250,20 @@ int odk_tracking_accumulate(const odk_batch* b, const float* priv_dev, const flo
  * batch's device: ODK_ERR_INVALID, and the binding stays as it was. */
 int odk_batch_bind_pushes(odk_batch* b, const float* push_dev, int row_stride);
 
+/* Caller-given action delays (control latency as a controlled axis: the reference draws a 0..2-step delay per step, joystick.py:357-376, and
+ * a trained policy claims to tolerate every one of them).  delay_dev: [nenv, row_stride] device int32 on the batch's device, row e's first
+ * entry = the row of env e's action-history ring that its NEXT odk_step turns into motor targets: 0 the action just given, 1 the one before,
+ * 2 the one before that; row_stride >= 1.  NULL unbinds (the sampled delay again).  While bound:
+ *   - every odk_step reads env e's row where the sampled index entered (joystick.py:372-376), clamped in the kernel: a value above 2 is 2;
+ *   - a NEGATIVE row (-1, and any other negative value alike) means "sample, as unbound": one buffer can mix fixed and sampled envs;
+ *   - the delay's random draw is still made and dropped: the rng key and counter, the push, noise, command and reset streams are those of an
+ *     unbound run, and the ring keeps rolling as ever (a step with delay 2 applies the action given two steps earlier);
+ *   - odk_reset and the auto-reset do not read the delay (they clear the ring).
+ * The buffer stays the caller's and must outlive the binding.  The pointer is a kernel argument: a captured graph keeps the pointer it was
+ * captured with (and reads that buffer's current contents at every replay); bind before capturing.  row_stride < 1, or memory that is not
+ * device memory of the batch's device: ODK_ERR_INVALID, and the binding stays as it was. */
+int odk_batch_bind_action_delays(odk_batch* b, const int32_t* delay_dev, int row_stride);
+
 /* Push-recovery accumulator: one launch per evaluation step, graph-capturable, issued after odk_step and BEFORE odk_tracking_accumulate
  * (track_acc_dev [nenv, ODK_TRACK_NACC] is that function's accumulator: its ENDED slot then still says whether env e's first episode was
  * running when this step began, and its STEPS slot counts the first-episode steps before this one).  Env e's row of acc_dev

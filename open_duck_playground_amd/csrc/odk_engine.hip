@@ -40,6 +40,7 @@ struct odk_batch {
   int timing = 0; size_t timing_count = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> events; size_t ev_used = 0;   // timing: 0 off, n: every n-th launch
   const float* d_cmd = nullptr; int cmd_stride = 0;   // odk_batch_bind_commands (caller-owned device rows), null: sampled commands
   const float* d_push = nullptr; int push_stride = 0; // odk_batch_bind_pushes (caller-owned device rows), null: the sampled push
+  const int32_t* d_delay = nullptr; int delay_stride = 0;   // odk_batch_bind_action_delays (caller-owned device rows), null: the sampled delay
   XTerms* d_xt = nullptr; bool xt_on = false;         // odk_batch_set_reward_terms: the batch's device copy; passed to the kernels while some term is on
   float* d_xmet = nullptr;                             // odk_batch_bind_reward_metrics (caller-owned)
   int* d_imap = nullptr; bool imap_set = false;        // odk_batch_set_imitation_joints: the batch's device copy; set: a map was given (the duck's
@@ -234,6 +235,7 @@ static void base_args(odk_batch* b, KArgs& a, const odk_outputs* o) {
   a.dbg_lds = nullptr;
   a.cmd = b->d_cmd; a.cmd_stride = b->cmd_stride;
   a.push = b->d_push; a.push_stride = b->push_stride;
+  a.delay = b->d_delay; a.delay_stride = b->delay_stride;
   a.xt = b->xt_on ? b->d_xt : nullptr; a.xmet = b->xt_on ? b->d_xmet : nullptr;
   a.imap = b->d_imap;
   a.hslot = b->d_hslot;
@@ -316,6 +318,23 @@ extern "C" int odk_batch_bind_pushes(odk_batch* b, const float* push_dev, int ro
     return fail(ODK_ERR_INVALID, "odk_batch_bind_pushes: push_dev must be device memory of device %d (the batch's), it belongs to device %d", b->device,
                 at.device);
   b->d_push = push_dev; b->push_stride = row_stride;
+  return ODK_OK;
+}
+
+extern "C" int odk_batch_bind_action_delays(odk_batch* b, const int32_t* delay_dev, int row_stride) {
+  if (!b) return fail(ODK_ERR_INVALID, "null batch");
+  if (!delay_dev) { b->d_delay = nullptr; b->delay_stride = 0; return ODK_OK; }
+  if (row_stride < 1) return fail(ODK_ERR_INVALID, "odk_batch_bind_action_delays: a delay row holds 1 int32: row_stride %d < 1", row_stride);
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof(at));
+  if (hipPointerGetAttributes(&at, delay_dev) != hipSuccess) {
+    (void)hipGetLastError();   // a pointer the runtime does not know: not this call's error to leave behind
+    return fail(ODK_ERR_INVALID, "odk_batch_bind_action_delays: delay_dev is not device memory");
+  }
+  if (at.type != hipMemoryTypeDevice || at.device != b->device)
+    return fail(ODK_ERR_INVALID, "odk_batch_bind_action_delays: delay_dev must be device memory of device %d (the batch's), it belongs to device %d",
+                b->device, at.device);
+  b->d_delay = delay_dev; b->delay_stride = row_stride;
   return ODK_OK;
 }
 

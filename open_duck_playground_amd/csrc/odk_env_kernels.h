@@ -486,7 +486,7 @@ __device__ __forceinline__ void step_body(const KArgs& a) {
   uint32_t w0, w1, w2, w3;   // draws 0 | 1 (unused) and 2 | 3: two generator blocks
   threefry2x32(k0, k1, ctr, 0u, w0, w1);
   threefry2x32(k0, k1, ctr, 1u, w2, w3);
-  const int aidx = randint3((float)(w0 >> 8) * (1.0f / 16777216.0f));
+  int aidx = randint3((float)(w0 >> 8) * (1.0f / 16777216.0f));
   // ---- push (:381-398)
   const float theta = (float)(w2 >> 8) * (1.0f / 16777216.0f) * (2.0f * PI_F);
   const float mag = c.push_magnitude_range[0] + (float)(w3 >> 8) * (1.0f / 16777216.0f) * (c.push_magnitude_range[1] - c.push_magnitude_range[0]);
@@ -511,6 +511,10 @@ __device__ __forceinline__ void step_body(const KArgs& a) {
     INFO[RL.IMI] = i2f(imi);
     ACT[NU] = phase[0]; ACT[NU + 1] = phase[1];
     INFO[RL.EPSTEPS] = ep_steps;
+  }
+  if (a.delay) {   // bound action delays: env e's row names the ring row (draw 0 was taken and is dropped); a negative row keeps the sampled one
+    const int d = a.delay[(size_t)e * a.delay_stride];
+    if (d >= 0) aidx = d < 2 ? d : 2;
   }
   // ---- motor targets with speed limit (:404-417)
   for (int u = lane; u < NU; u += G) {

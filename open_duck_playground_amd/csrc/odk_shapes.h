@@ -98,6 +98,8 @@ struct KArgs {
   const int* hslot;   // [nu] Standing's head joints (odk_batch_set_head_joints): posture-command slot 0..3 of actuator u, -1 = not a head joint
   const float* push;  // [nenv][push_stride] bound pushes (odk_batch_bind_pushes): world-frame kick (dvx, dvy) of the next step, or null: the
   int push_stride;    // sampled push.  A uniform pointer test like cmd's, placed behind every older field
+  const int32_t* delay;   // [nenv][delay_stride] bound action delays (odk_batch_bind_action_delays): the action-history row 0..2 env e's step
+  int delay_stride;       // applies, negative: the sampled one; or null: every env samples.  A uniform pointer test, behind every older field
 };
 
 // DR buffer layout per env

@@ -103,6 +103,10 @@ class OdkError(RuntimeError):
     pass
 
 
+class OdkValueError(OdkError, ValueError):
+    """An argument refused before any launch (`check_action_delays`): an OdkError that `except ValueError` catches too."""
+
+
 POISON_LIB_PATH = os.path.join(_CSRC, "libodk_poison.so")   # the -DODK_POISON_LDS build (csrc/odk_poison.h): load it through ODK_LIB
 
 
@@ -169,6 +173,7 @@ def load_library() -> C.CDLL:
     L.odk_physics_step.argtypes = [P, P, C.c_int, P]
     L.odk_batch_bind_commands.argtypes = [P, P, C.c_int]
     L.odk_batch_bind_pushes.argtypes = [P, P, C.c_int]
+    L.odk_batch_bind_action_delays.argtypes = [P, P, C.c_int]
     L.odk_batch_set_reward_terms.argtypes = [P, C.POINTER(RewardTerms)]
     L.odk_batch_bind_reward_metrics.argtypes = [P, P]
     L.odk_batch_set_imitation_joints.argtypes = [P, C.POINTER(C.c_int32), C.c_int]
@@ -226,7 +231,7 @@ EXPORTED_SYMBOLS = (
     "odk_model_env_lds_floats", "odk_batch_create",
     "odk_batch_destroy", "odk_batch_set_config", "odk_batch_set_param", "odk_reset", "odk_step", "odk_physics_step",
     "odk_batch_bind_commands", "odk_batch_set_reward_terms", "odk_batch_bind_reward_metrics", "odk_batch_set_imitation_joints", "odk_batch_set_head_joints",
-    "odk_tracking_accumulate", "odk_batch_bind_pushes", "odk_push_accumulate", "odk_gait_accumulate", "odk_posture_accumulate",
+    "odk_tracking_accumulate", "odk_batch_bind_pushes", "odk_batch_bind_action_delays", "odk_push_accumulate", "odk_gait_accumulate", "odk_posture_accumulate",
     "odk_imitation_accumulate", "odk_command_schedule_apply", "odk_response_accumulate", "odk_fall_row_floats", "odk_fall_accumulate",
     "odk_batch_get_state", "odk_batch_set_state", "odk_batch_get_debug", "odk_set_debug_dump", "odk_batch_lds_size",
     "odk_batch_get_lds", "odk_lds_offset", "odk_batch_record_size", "odk_batch_get_records", "odk_batch_set_records", "odk_batch_timing", "odk_gae", "odk_ppo_head",
@@ -320,6 +325,26 @@ def check_pushes(push, nenv: int, device: int) -> None:
         raise OdkError("pushes: the tensor must be contiguous")
     if push.device.type != "cuda" or push.device.index != int(device):
         raise OdkError(f"pushes: the tensor must live on cuda:{device} (the env's device), got {push.device}")
+
+
+ACTION_DELAY_ROWS = 3      # the action-history ring: delay 0 (the action just given), 1, 2; a negative device row means "sample"
+
+
+def check_action_delays(delays, nenv: int, device: int) -> None:
+    """What `Batch.bind_action_delays` accepts: an int32 tensor on cuda:`device` with at least `nenv` rows -- [rows] or [rows, k], env e's
+    delay the first entry of row e -- and a row stride (in elements) of at least 1; raises ValueError (an OdkError too) otherwise, before
+    anything is launched.  The values are not read here: the kernel clamps them (include/odk.h)."""
+    import torch
+    if not torch.is_tensor(delays):
+        raise OdkValueError(f"action delays: expected a torch tensor or None, got {type(delays).__name__}")
+    if delays.dtype != torch.int32:
+        raise OdkValueError(f"action delays: dtype must be torch.int32, got {delays.dtype}")
+    if delays.device.type != "cuda" or delays.device.index != int(device):
+        raise OdkValueError(f"action delays: the tensor must live on cuda:{device} (the env's device), got {delays.device}")
+    if delays.dim() not in (1, 2) or int(delays.shape[0]) < int(nenv) or (delays.dim() == 2 and int(delays.shape[1]) < 1):
+        raise OdkValueError(f"action delays: shape must be (>= {nenv},) or (>= {nenv}, >= 1), got {tuple(delays.shape)}")
+    if int(delays.stride(0)) < 1:
+        raise OdkValueError(f"action delays: the row stride must be >= 1 element (one row per env), got {int(delays.stride(0))}")
 
 
 def check_accumulator(name: str, acc, nenv: int, ncol: int, device: int) -> None:
@@ -986,6 +1011,7 @@ class Batch:
                              self.truncation.data_ptr(), self.metrics.data_ptr())
         self.commands = None         # the tensor bound by bind_commands (kept alive while bound)
         self.pushes = None           # the tensor bound by bind_pushes (kept alive while bound)
+        self.action_delays = None    # the tensor bound by bind_action_delays (kept alive while bound)
         self.xmetrics = None         # [nenv, NXTERM] reward-library metrics, allocated by the first set_reward_terms that turns a term on
         self.reward_terms_on = False
         self.generation = 0          # advanced by every call that rewrites the per-env records (reset / step / set_records): `State.info` checks it
@@ -1037,6 +1063,21 @@ class Batch:
         check_pushes(push, self.nenv, self.device)
         _chk(self.L.odk_batch_bind_pushes(self._b, C.c_void_p(push.data_ptr()), int(push.shape[1])))
         self.pushes = push
+
+    def bind_action_delays(self, delays):
+        """Fix every env's action delay (`odk_batch_bind_action_delays`): `delays` is an int32 tensor on this batch's device with at least
+        nenv rows ([rows] or [rows, k]; `check_action_delays`), row e = the action-history row 0, 1 or 2 that env e's next step turns into
+        motor targets (0: the action just given), a negative value = the sampled delay for that env; None returns every env to the sampler.
+        The kernel clamps a value above 2 to 2.  The random streams stay those of an unbound run.  The batch keeps a reference to the tensor
+        while it is bound; write into it (stream-ordered) to change the delays; a captured graph keeps the buffer it was captured with, so
+        rebind only before capturing."""
+        if delays is None:
+            _chk(self.L.odk_batch_bind_action_delays(self._b, None, 0))
+            self.action_delays = None
+            return
+        check_action_delays(delays, self.nenv, self.device)
+        _chk(self.L.odk_batch_bind_action_delays(self._b, C.c_void_p(delays.data_ptr()), int(delays.stride(0))))
+        self.action_delays = delays
 
     def set_reward_terms(self, terms: Optional[RewardTerms]):
         """Reward-library terms of the step kernel (`odk_batch_set_reward_terms`): None or all scales 0 turns them off.  While some

@@ -444,6 +444,19 @@ class Joystick:
         """The tensor bound by `set_pushes`, or None."""
         return self._batch.pushes
 
+    def set_action_delays(self, delays) -> None:
+        """Fix the envs' action delay instead of drawing it every step (joystick.py:357-376 draws 0..2 control steps): `delays` is an
+        int32 tensor on the env's device with at least num_envs rows -- env e's delay in control steps, 0, 1 or 2; a negative value keeps
+        the sampled delay for that env -- or None to return every env to the sampler.  Every step reads env e's row as it is when that
+        launch runs; the random streams stay those of an unbound run.  The env holds a reference to the tensor while it is bound
+        (`Batch.bind_action_delays`).  Standing inherits this."""
+        self._batch.bind_action_delays(delays)
+
+    @property
+    def action_delays(self):
+        """The tensor bound by `set_action_delays`, or None."""
+        return self._batch.action_delays
+
     def step(self, state: State, action) -> State:
         """reference joystick.py:323 (+ Episode/AutoReset wrappers): one fused kernel launch."""
         self._batch.step(action)

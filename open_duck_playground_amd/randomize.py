@@ -48,6 +48,40 @@ def domain_randomize(model: Model, rng: np.random.Generator, num_envs: int) -> T
     return fields, in_axes
 
 
+def nominal_fields(model: Model, num_envs: int) -> Dict[str, np.ndarray]:
+    """The model's own values in `domain_randomize`'s layout (float64 [num_envs, ...], without the no-op geom friction): what `apply` hands
+    the engine for a plant that differs from the XML in nothing.  `scale_fields` builds a controlled plant on top of it."""
+    a = model.a
+    act_jnt = np.asarray(a["actuator_trnid"])
+    dof_addr = np.asarray(a["jnt_dofadr"])[act_jnt]
+    joint_addr = np.asarray(a["jnt_qposadr"])[act_jnt]
+    kp = np.asarray(a["actuator_gainprm0"], np.float64)
+    one = lambda v: np.repeat(np.asarray(v, np.float64).reshape(1, -1), int(num_envs), axis=0)
+    return {"body_ipos": one(np.asarray(a["body_ipos"])[TORSO_BODY_ID]), "dof_frictionloss": one(np.asarray(a["dof_frictionloss"])[dof_addr]),
+            "dof_armature": one(np.asarray(a["dof_armature"])[dof_addr]), "body_mass": one(a["body_mass"]),
+            "qpos0": one(np.asarray(a["qpos0"])[joint_addr]), "actuator_gainprm": one(kp), "actuator_biasprm": one(-kp)}
+
+
+# a plant's scale axes -> the fields they multiply (kp: gain and bias together, as `apply` hands the engine the gain alone and the kernels take
+# the bias from it; mass: the body masses alone -- inertias are not rescaled, randomize.py's semantics)
+SCALED_FIELDS = {"kp": ("actuator_gainprm", "actuator_biasprm"), "mass": ("body_mass",), "frictionloss": ("dof_frictionloss",),
+                 "armature": ("dof_armature",)}
+
+
+def scale_fields(fields: Dict[str, np.ndarray], scales: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+    """`fields` (nominal_fields or domain_randomize) with env e's row of every field of axis k multiplied by scales[k][e]; the other fields
+    (body_ipos, qpos0) are passed on.  The product is taken in float64 and rounded to float32 once, by `Batch.set_param`: a scale of exactly 1
+    leaves the float32 value the engine's own model holds."""
+    out = {k: np.array(v, np.float64) for k, v in fields.items()}
+    for axis, scale in scales.items():
+        if axis not in SCALED_FIELDS:
+            raise ValueError(f"unknown plant scale {axis!r} (one of {', '.join(SCALED_FIELDS)})")
+        sc = np.asarray(scale, np.float64).reshape(-1)
+        for k in SCALED_FIELDS[axis]:
+            out[k] = out[k] * sc.reshape((-1,) + (1,) * (out[k].ndim - 1))
+    return out
+
+
 def apply(batch: "engine.Batch", fields: Dict[str, np.ndarray]) -> None:
     batch.set_param(engine.PARAM_BODY_MASS, fields["body_mass"])
     batch.set_param(engine.PARAM_BODY_IPOS_TORSO, fields["body_ipos"])

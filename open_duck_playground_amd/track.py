@@ -97,6 +97,25 @@ a saturated actuator in the ring, how close the survivors came, and the mean pro
 saturation over the samples before the termination (`reduce_falls`).  `--save_falls PATH` writes the rings of the first
 `--save_falls_max` falls of every row (cell) as an .npz of clips that replay like `--save_qpos` (`fall_clips`).  `--falls` combines with
 every flag above.  Without it nothing changes.
+
+Plants (how much control latency and model error does it tolerate? -- the reference randomises kp, body masses, friction loss, armature
+and a 0..2-step action delay in training, so a trained policy claims robustness to them; here they are controlled axes):
+
+    python -m open_duck_playground_amd.track --checkpoint <ckpt> --command 0.1 0 0 --plant_grid kp=0.7:1.3:4,mass=0.9:1.2:3,delay=0:2:3
+    python -m open_duck_playground_amd.track --checkpoint <ckpt> --grid vx=-0.15:0.15:3 --plant kp=0.6,delay=2 --plant kp=1.0 --falls
+
+`--plant KEY=V[,KEY=V...]` (repeatable) and `--plant_grid` (a cross product, `--grid`'s syntax) name plants: `kp`, `mass`, `frictionloss`
+and `armature` are scales on the model's values (every actuator's gain, with the bias following; every body's mass, inertias NOT rescaled,
+as playground/common/randomize.py; the actuated dofs' friction loss and armature), `delay` is the action delay in control steps, 0, 1, 2 or
+`random` (the sampler, the default).  Every (command, plant) cell gets `--envs_per_command` envs, command blocks outermost (`plant_blocks`,
+the layout pushes use).  The host hands the engine nominal value times scale per env (`odk_batch_set_param`) and binds an int32 delay per env
+(`set_action_delays`, -1 for `random`); the captured step is the plain one.  Every command row gains "plants" -- per cell a whole command
+row of its own plus "plant" -- and "robustness": per swept axis, with the other axes at their value nearest nominal, the fall rate,
+RMS errors and episode reward against the axis, and "survived_range", the contiguous run of values around nominal whose fall rate stays
+within `--robust_fall_rate`.  `--gait`, `--falls`, `--imitation_report`, `--posture`, `--sequence` and `--then` combine with plants (one
+object per cell too); `--push` / `--push_grid` do not (a third cell axis).  `--randomize` applies the training-time `domain_randomize` draw
+to every env (seeded by `--seed`; a plant's scales multiply it), `--noise_level X` overrides `noise_config.level`.  Without these flags
+nothing changes.
 """
 from __future__ import annotations
 
@@ -256,6 +275,202 @@ def cell_blocks(commands: Sequence[Sequence[float]], pushes: Sequence[Dict], env
     cmd = command_blocks(commands, P * E)
     kicks = np.tile(np.repeat(np.asarray([p["push"] for p in pushes], np.float32).reshape(-1, 2), E, axis=0), (len(commands), 1))
     return cmd, kicks
+
+
+PLANT_SCALE_AXES = ("kp", "mass", "frictionloss", "armature")      # scales on the model's values (randomize.SCALED_FIELDS)
+PLANT_AXES = PLANT_SCALE_AXES + ("delay",)
+DELAY_RANDOM = "random"      # the sampled action delay: a device row of -1 (include/odk.h odk_batch_bind_action_delays)
+DELAY_VALUES = (0, 1, 2)
+DEFAULT_ROBUST_FALL_RATE = 0.05      # a REPORTING threshold the user sets (--robust_fall_rate), not a measured constant
+
+
+def nominal_plant() -> Dict:
+    """The plant the XML describes: every scale 1, the delay sampled."""
+    return {"kp": 1.0, "mass": 1.0, "frictionloss": 1.0, "armature": 1.0, "delay": DELAY_RANDOM}
+
+
+def _plant_value(flag: str, name: str, value) -> object:
+    """One axis value as a plant holds it: a finite scale > 0, or for `delay` 0, 1, 2 or "random"; ValueError otherwise."""
+    if name not in PLANT_AXES:
+        raise ValueError(f"{flag}: unknown axis {name!r} (one of {', '.join(PLANT_AXES)})")
+    if name == "delay":
+        if isinstance(value, str) and value.strip().lower() == DELAY_RANDOM:
+            return DELAY_RANDOM
+        try:
+            v = float(value)
+        except (TypeError, ValueError):
+            raise ValueError(f"{flag}: delay={value!r} is not 0, 1, 2 or {DELAY_RANDOM}")
+        if not np.isfinite(v) or v != round(v):
+            raise ValueError(f"{flag}: delay={value} is not a whole number of control steps (0, 1, 2 or {DELAY_RANDOM})")
+        if int(v) not in DELAY_VALUES:
+            raise ValueError(f"{flag}: delay={int(v)} is outside the action-history ring: 0, 1, 2 or {DELAY_RANDOM}")
+        return int(v)
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{flag}: {name}={value!r} is not a number")
+    if not np.isfinite(v) or v <= 0:
+        raise ValueError(f"{flag}: {name}={value} is not a finite scale > 0 (1 = the model's own value)")
+    return v
+
+
+def parse_plant(spec: str) -> Dict:
+    """`--plant kp=0.6,delay=2` -> a plant: `nominal_plant()` with the named axes replaced.  ValueError for an unknown axis, an axis given
+    twice, a scale that is not a finite number > 0, and a delay that is not 0, 1, 2 or `random`."""
+    plant, seen = nominal_plant(), []
+    for part in str(spec).split(","):
+        part = part.strip()
+        if not part:
+            continue
+        name, eq, value = part.partition("=")
+        name = name.strip()
+        if not eq:
+            raise ValueError(f"--plant: {part!r} is not KEY=VALUE")
+        if name in seen:
+            raise ValueError(f"--plant: axis {name!r} given twice")
+        plant[name] = _plant_value("--plant", name, value.strip())      # (an unknown axis is refused before it is stored)
+        seen.append(name)
+    if not seen:
+        raise ValueError("--plant: no axis given")
+    return plant
+
+
+def parse_plant_grid(spec: str) -> List[Dict]:
+    """`kp=0.7:1.3:4,mass=0.9:1.2:3,delay=0:2:3` -> the plants of the grid, with `--grid`'s conventions: each axis takes n values from a to
+    b (numpy.linspace, ends included), plants in itertools.product order of the axes as written (the last axis varies fastest), axes not
+    named stay nominal.  A `delay` axis must come out as whole numbers within 0..2."""
+    axes = []
+    for part in str(spec).split(","):
+        part = part.strip()
+        if not part:
+            continue
+        name, _, rng = part.partition("=")
+        name = name.strip()
+        if name not in PLANT_AXES:
+            raise ValueError(f"--plant_grid: unknown axis {name!r} (one of {', '.join(PLANT_AXES)})")
+        if any(name == a for a, _ in axes):
+            raise ValueError(f"--plant_grid: axis {name!r} given twice")
+        bits = rng.split(":")
+        if len(bits) != 3:
+            raise ValueError(f"--plant_grid: {part!r} is not {name}=start:stop:count")
+        try:
+            lo, hi, n = float(bits[0]), float(bits[1]), int(bits[2])
+        except ValueError:
+            raise ValueError(f"--plant_grid: {part!r} is not {name}=start:stop:count")
+        if n < 1:
+            raise ValueError(f"--plant_grid: {part!r} needs a count >= 1")
+        axes.append((name, [_plant_value("--plant_grid", name, v) for v in np.linspace(lo, hi, n).tolist()]))
+    if not axes:
+        raise ValueError("--plant_grid: no axis given")
+    plants = []
+    for combo in itertools.product(*[vals for _, vals in axes]):
+        plant = nominal_plant()
+        plant.update({name: v for (name, _), v in zip(axes, combo)})
+        plants.append(plant)
+    return plants
+
+
+def plants_from_args(args) -> List[Dict]:
+    """The plants the command line asks for (`--plant` in order, then `--plant_grid`'s), [] without a plant flag.  SystemExit with the reason
+    for a plant that cannot be parsed, for plants next to `--push` / `--push_grid` (a third cell axis) and for a `--robust_fall_rate`
+    outside 0..1 -- host work only, before any batch exists."""
+    specs, grid = getattr(args, "plant", None) or [], getattr(args, "plant_grid", None)
+    try:
+        plants = [parse_plant(s) for s in specs] + (parse_plant_grid(grid) if grid else [])
+    except ValueError as err:
+        raise SystemExit(str(err))
+    if plants and (getattr(args, "push", None) or getattr(args, "push_grid", None)):
+        raise SystemExit("--plant / --plant_grid do not combine with --push / --push_grid: (command, push, plant) would be a third cell axis; "
+                         "run the push sweep once per plant")
+    rate = float(getattr(args, "robust_fall_rate", DEFAULT_ROBUST_FALL_RATE))
+    if not (np.isfinite(rate) and 0.0 <= rate <= 1.0):
+        raise SystemExit(f"--robust_fall_rate is a fall rate: 0 .. 1, got {rate}")
+    return plants
+
+
+def plant_blocks(commands: Sequence[Sequence[float]], plants: Sequence[Dict], envs_per_cell: int):
+    """(cmd [n, 7] float32, scales {axis: [n] float64}, delays [n] int32) with n = len(commands) * len(plants) * envs_per_cell: cell (c, p)
+    drives envs (c * len(plants) + p) * envs_per_cell onwards -- `cell_blocks`' layout with plants where the pushes are.  `scales[axis][e]`
+    is env e's scale of that axis, `delays[e]` its bound delay row: 0, 1, 2, or -1 for `random`."""
+    E, P = int(envs_per_cell), len(plants)
+    cmd = command_blocks(commands, P * E)
+    tile = lambda per_plant, dtype: np.tile(np.repeat(np.asarray(per_plant, dtype), E), len(commands))
+    scales = {axis: tile([float(p[axis]) for p in plants], np.float64) for axis in PLANT_SCALE_AXES}
+    delays = tile([-1 if p["delay"] == DELAY_RANDOM else int(p["delay"]) for p in plants], np.int32)
+    return cmd, scales, delays
+
+
+def plant_fields(model, scales: Dict[str, np.ndarray], fields: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, np.ndarray]:
+    """What `randomize.apply` hands the engine for the envs of `plant_blocks`: the model's nominal values (`randomize.nominal_fields`; or
+    `fields`, a `domain_randomize` draw) times env e's scales.  Parameters no axis names stay nominal."""
+    from . import randomize
+    n = len(next(iter(scales.values())))
+    return randomize.scale_fields(fields if fields is not None else randomize.nominal_fields(model, n), scales)
+
+
+def _delay_order(v) -> float:
+    return -1.0 if v == DELAY_RANDOM else float(v)      # `random` sorts in front of the fixed delays
+
+
+def _nearest_nominal(axis: str, values: Sequence) -> object:
+    """The value of `values` nearest the nominal plant's: for a scale the one closest to 1 (the smaller of two equally close), for the delay
+    `random` if present, else the smallest."""
+    if axis == "delay":
+        return DELAY_RANDOM if DELAY_RANDOM in values else min(values)
+    return min(values, key=lambda v: (abs(float(v) - 1.0), float(v)))
+
+
+def survived_range(values: Sequence[float], fall_rates: Sequence[float], threshold: float, nominal: float = 1.0) -> Optional[List[float]]:
+    """[lo, hi]: the contiguous run of `values` around the one nearest `nominal` whose fall rate is at most `threshold`, or None when that
+    value itself fails (then nothing around nominal was survived).  The values are taken in increasing order; the run starts at the value
+    nearest `nominal` (the smaller of two equally near -- nominal need not be in the grid) and grows in both directions until the first
+    value whose fall rate exceeds the threshold: a failing value in the middle ends the run there, whatever passes beyond it."""
+    order = sorted(range(len(values)), key=lambda i: float(values[i]))
+    v = [float(values[i]) for i in order]
+    ok = [float(fall_rates[i]) <= float(threshold) for i in order]
+    if not v:
+        return None
+    k = min(range(len(v)), key=lambda i: (abs(v[i] - float(nominal)), v[i]))
+    if not ok[k]:
+        return None
+    lo = hi = k
+    while lo > 0 and ok[lo - 1]:
+        lo -= 1
+    while hi + 1 < len(v) and ok[hi + 1]:
+        hi += 1
+    return [v[lo], v[hi]]
+
+
+ROBUSTNESS_POINT_KEYS = ("value", "fall_rate", "rms_error_vx", "rms_error_vy", "rms_error_wz", "mean_episode_reward")
+
+
+def reduce_robustness(cells: Sequence[Dict], threshold: float) -> Dict:
+    """The "robustness" object of one command row from its plant cells (each a command row with "plant").  An axis is swept when the cells
+    hold more than one value of it.  Per swept axis, under its name: the cells whose OTHER axes sit at their value nearest nominal (scale
+    1; delay `random` if present, else the smallest), in increasing order of the axis (`random` first) -- `value`, `fall_rate`, the three
+    RMS errors and `mean_episode_reward` each.  `survived_range`: per swept axis `survived_range()` of those points at `threshold`; for
+    `delay` over the fixed delays, starting from the smallest (`random` is not a point on that line).  `robust_fall_rate` is the threshold."""
+    distinct = {a: [] for a in PLANT_AXES}
+    for cell in cells:
+        for a in PLANT_AXES:
+            if cell["plant"][a] not in distinct[a]:
+                distinct[a].append(cell["plant"][a])
+    swept = [a for a in PLANT_AXES if len(distinct[a]) > 1]
+    base = {a: _nearest_nominal(a, distinct[a]) for a in PLANT_AXES}
+    out: Dict = {"robust_fall_rate": float(threshold)}
+    ranges: Dict = {}
+    for axis in swept:
+        line = [c for c in cells if all(c["plant"][o] == base[o] for o in PLANT_AXES if o != axis)]
+        line.sort(key=lambda c: _delay_order(c["plant"][axis]) if axis == "delay" else float(c["plant"][axis]))
+        out[axis] = [dict(value=c["plant"][axis], **{k: c[k] for k in ROBUSTNESS_POINT_KEYS[1:]}) for c in line]
+        pts = [p for p in out[axis] if p["value"] != DELAY_RANDOM]
+        nominal = min(p["value"] for p in pts) if axis == "delay" and pts else 1.0
+        ranges[axis] = survived_range([p["value"] for p in pts], [p["fall_rate"] for p in pts], threshold, nominal)
+    out["survived_range"] = ranges
+    return out
+
+
+PLANT_ROW_KEYS = ("plants", "robustness")
 
 
 def _mean_or_none(x: np.ndarray) -> Optional[float]:
@@ -998,6 +1213,8 @@ def config_overrides(args) -> Dict:
         overrides["cone"] = args.cone
     overrides.update(imitation_overrides(args))
     overrides.update(head_joint_overrides(args))
+    if getattr(args, "noise_level", None) is not None:
+        overrides["noise_config.level"] = float(args.noise_level)
     return overrides
 
 
@@ -1039,11 +1256,13 @@ class Tracker:
     accumulators and issues `odk_command_schedule_apply` once before the env's reset, and the step issues it again before the env step and
     `odk_response_accumulate` next to the other accumulators.  The bound command tensor is then written by the Tracker.  With `falls` -- a
     dict of `ring` (samples) and `tilt_tol` (the sine of the upright lean) -- it owns a fall recorder ([num_envs, fall_row_floats(ring)]) and
-    the torque limits, and the step gains `odk_fall_accumulate` next to the other accumulators."""
+    the torque limits, and the step gains `odk_fall_accumulate` next to the other accumulators.  With `delays` ([num_envs] device int32, one
+    action delay per env: 0, 1, 2, or -1 for the sampled one) it binds them (`set_action_delays`) and keeps the tensor; the step itself is
+    unchanged.  Model parameters (`Batch.set_param`) are the caller's to set before `reset`."""
 
     def __init__(self, env, net, use_graph: bool = True, kicks=None, push_at: int = DEFAULT_PUSH_AT, push_tolerance=DEFAULT_PUSH_TOLERANCE,
                  gait: bool = False, posture: bool = False, posture_tolerance: float = DEFAULT_POSTURE_TOLERANCE,
-                 imitation: bool = False, schedule: Optional[Dict] = None, falls: Optional[Dict] = None):
+                 imitation: bool = False, schedule: Optional[Dict] = None, falls: Optional[Dict] = None, delays=None):
         import torch
         self.env, self.net, self.torch = env, net, torch
         b = env.batch
@@ -1056,6 +1275,10 @@ class Tracker:
             self.push_acc = torch.zeros(env.num_envs, PUSH_NACC, device=b.obs.device)
             self.counter = torch.full((), -1, dtype=torch.int64, device=b.obs.device)
             env.set_pushes(self.push_buf)
+        self.delays = None
+        if delays is not None:
+            self.delays = delays.to(device=b.obs.device, dtype=torch.int32).reshape(env.num_envs).contiguous()
+            env.set_action_delays(self.delays)
         self.gait_acc = self.torque_limit = None
         if gait:
             self.gait_acc = torch.zeros(env.num_envs, GAIT_NACC, device=b.obs.device)
@@ -1162,9 +1385,13 @@ def run(args, out=sys.stdout) -> Dict:
             commands += parse_grid(args.grid)
     if not commands:
         raise SystemExit("give at least one --command or a --grid")
+    plants = plants_from_args(args)      # [] without --plant / --plant_grid; refusals (pushes next to plants among them) before any batch work
     pushes = [push_row(p) for p in (getattr(args, "push", None) or [])]
     if getattr(args, "push_grid", None):
         pushes += parse_push_grid(args.push_grid)
+    ncell = max(len(pushes), 1) * max(len(plants), 1)      # cells per command (pushes and plants exclude each other)
+    cells_key = "pushes" if pushes else ("plants" if plants else None)
+    randomized = bool(getattr(args, "randomize", False))
     gait = bool(getattr(args, "gait", False))
     posture = bool(getattr(args, "posture", False))
     posture_tol = float(getattr(args, "posture_tolerance", DEFAULT_POSTURE_TOLERANCE))
@@ -1180,7 +1407,7 @@ def run(args, out=sys.stdout) -> Dict:
     if getattr(args, "falls", False):
         falls = dict(ring=int(getattr(args, "fall_ring", DEFAULT_FALL_RING)), tilt_tol=fall_tilt_tol(getattr(args, "fall_tilt", DEFAULT_FALL_TILT)))
     E = int(args.envs_per_command)
-    n = len(commands) * max(len(pushes), 1) * E
+    n = len(commands) * ncell * E
     torch.cuda.set_device(args.device)
     dev = torch.device("cuda", args.device)
     env = make_env(args, n, args.device)
@@ -1200,6 +1427,15 @@ def run(args, out=sys.stdout) -> Dict:
         except ValueError as err:
             raise SystemExit(str(err))
     net = load_networks(args.checkpoint, env, dev)
+    delays_t = None
+    if plants or randomized:      # per-env model parameters: the training-time draw, the plants' scales, or the one times the other
+        from . import randomize
+        fields = randomize.domain_randomize(env.mj_model, np.random.default_rng(int(args.seed)), n)[0] if randomized else None
+        if plants:
+            _, scales, delays_np = plant_blocks(commands, plants, E)
+            fields = plant_fields(env.mj_model, scales, fields)
+            delays_t = torch.from_numpy(delays_np).to(dev)
+        randomize.apply(env.batch, fields)
     if pushes:
         push_at = int(args.push_at)
         if push_at < 0:
@@ -1213,14 +1449,15 @@ def run(args, out=sys.stdout) -> Dict:
     elif schedules is not None:
         resp_tol = response_tolerance(args)
         tail_after = int(getattr(args, "response_tail_after", DEFAULT_RESPONSE_TAIL_AFTER))
-        cmd = torch.from_numpy(command_blocks(commands, E)).to(dev)      # segment 0's; the Tracker's apply launch rewrites it every step
+        cmd = torch.from_numpy(command_blocks(commands, ncell * E)).to(dev)      # segment 0's; the Tracker's apply launch rewrites it every step
         env.set_commands(cmd)
-        tr = Tracker(env, net, gait=gait, imitation=imitation, falls=falls,
-                     schedule=dict(table=schedule_table(schedules), map=schedule_blocks(len(schedules), E), tolerance=resp_tol, tail_after=tail_after))
+        tr = Tracker(env, net, gait=gait, imitation=imitation, falls=falls, delays=delays_t,
+                     schedule=dict(table=schedule_table(schedules), map=schedule_blocks(len(schedules), ncell * E), tolerance=resp_tol,
+                                   tail_after=tail_after))
     else:
-        cmd = torch.from_numpy(command_blocks(commands, E)).to(dev)
+        cmd = torch.from_numpy(command_blocks(commands, ncell * E)).to(dev)
         env.set_commands(cmd)
-        tr = Tracker(env, net, gait=gait, posture=posture, posture_tolerance=posture_tol, imitation=imitation, falls=falls)
+        tr = Tracker(env, net, gait=gait, posture=posture, posture_tolerance=posture_tol, imitation=imitation, falls=falls, delays=delays_t)
     nobs = env.observation_size["state"][0]
     T = int(args.episode_length)
     save_obs_path, save_qpos_path = getattr(args, "save_obs", None), getattr(args, "save_qpos", None)
@@ -1243,47 +1480,59 @@ def run(args, out=sys.stdout) -> Dict:
         imitation_acc = tr.imitation_acc.cpu().numpy() if imitation else None
         response_acc = tr.response_acc.cpu().numpy() if schedules is not None else None
         fall_acc = tr.fall_acc.cpu().numpy() if falls else None
-    rows = reduce_tracking(acc, commands, max(len(pushes), 1) * E)
+    rows = reduce_tracking(acc, commands, ncell * E)
     if pushes:
         for row, extra in zip(rows, reduce_pushes(push_acc, commands, pushes, E, float(env.dt))):
             row.update(extra)
+    if plants:      # one whole command row per (command, plant) cell, in `plant_blocks` order, plus the plant it ran on
+        cell_rows = reduce_tracking(acc, [c for c in commands for _ in plants], E)
+        for i, cell in enumerate(cell_rows):
+            cell["plant"] = dict(plants[i % len(plants)])
+        for c, row in enumerate(rows):
+            row["plants"] = cell_rows[c * len(plants):(c + 1) * len(plants)]
     if schedules is not None:
-        for row, sched, segs in zip(rows, schedules, reduce_response(response_acc, schedules, E, float(env.dt))):
+        for row, sched, segs in zip(rows, schedules, reduce_response(response_acc, schedules, ncell * E, float(env.dt))):
             row["schedule"] = [dict(start_step=int(seg["start_step"]), command=[float(x) for x in seg["command"]]) for seg in sched]
             row["segments"] = segs
+        if plants:      # and per (schedule, plant) cell
+            cells = [cell for row in rows for cell in row["plants"]]
+            cell_scheds = [sched for sched in schedules for _ in plants]
+            for cell, sched, segs in zip(cells, cell_scheds, reduce_response(response_acc, cell_scheds, E, float(env.dt))):
+                cell["schedule"] = [dict(start_step=int(seg["start_step"]), command=[float(x) for x in seg["command"]]) for seg in sched]
+                cell["segments"] = segs
     if gait:
-        for row, g in zip(rows, reduce_gait(gait_acc, commands, max(len(pushes), 1) * E, float(env.dt), env.mj_model)):
+        for row, g in zip(rows, reduce_gait(gait_acc, commands, ncell * E, float(env.dt), env.mj_model)):
             row["gait"] = g
-        if pushes:      # and one per (command, push) cell, in `cell_blocks` order
-            cells = [cell for row in rows for cell in row["pushes"]]
+        if cells_key:      # and one per (command, push) or (command, plant) cell, in `cell_blocks` order
+            cells = [cell for row in rows for cell in row[cells_key]]
             for cell, g in zip(cells, reduce_gait(gait_acc, cells, E, float(env.dt), env.mj_model)):
                 cell["gait"] = g
     if posture:
-        for row, g in zip(rows, reduce_posture(posture_acc, commands, max(len(pushes), 1) * E, float(env.dt), head_map, joint_names)):
+        for row, g in zip(rows, reduce_posture(posture_acc, commands, ncell * E, float(env.dt), head_map, joint_names)):
             row["posture"] = g
-        if pushes:      # and one per (command, push) cell, in `cell_blocks` order
-            cells = [cell for row in rows for cell in row["pushes"]]
-            cell_cmds = [row["command"] for row in rows for _ in row["pushes"]]
+        if cells_key:      # and one per cell
+            cells = [cell for row in rows for cell in row[cells_key]]
+            cell_cmds = [row["command"] for row in rows for _ in row[cells_key]]
             for cell, g in zip(cells, reduce_posture(posture_acc, cell_cmds, E, float(env.dt), head_map, joint_names)):
                 cell["posture"] = g
     if imitation:
-        for row, g in zip(rows, reduce_imitation(imitation_acc, commands, max(len(pushes), 1) * E, float(env.dt), imap, imit_joint_names, period_steps)):
+        for row, g in zip(rows, reduce_imitation(imitation_acc, commands, ncell * E, float(env.dt), imap, imit_joint_names, period_steps)):
             row["imitation"] = g
-        if pushes:      # and one per (command, push) cell, in `cell_blocks` order
-            cells = [cell for row in rows for cell in row["pushes"]]
+        if cells_key:      # and one per cell
+            cells = [cell for row in rows for cell in row[cells_key]]
             for cell, g in zip(cells, reduce_imitation(imitation_acc, cells, E, float(env.dt), imap, imit_joint_names, period_steps)):
                 cell["imitation"] = g
     if falls:
         nq = int(env.batch.model.nq)
-        for row, g in zip(rows, reduce_falls(fall_acc, commands, max(len(pushes), 1) * E, float(env.dt), falls["ring"], nq)):
+        for row, g in zip(rows, reduce_falls(fall_acc, commands, ncell * E, float(env.dt), falls["ring"], nq)):
             row["falls"] = g
         blocks = rows
-        if pushes:      # and one per (command, push) cell, in `cell_blocks` order
-            blocks = [cell for row in rows for cell in row["pushes"]]
+        if cells_key:      # and one per cell
+            blocks = [cell for row in rows for cell in row[cells_key]]
             for cell, g in zip(blocks, reduce_falls(fall_acc, blocks, E, float(env.dt), falls["ring"], nq)):
                 cell["falls"] = g
         if getattr(args, "save_falls", None):      # the clips of every row, or with pushes of every cell
-            block_cmds = [row["command"] for row in rows for _ in (row["pushes"] if pushes else [0])]
+            block_cmds = [row["command"] for row in rows for _ in (row[cells_key] if cells_key else [0])]
             save_falls(args.save_falls, fall_clips(fall_acc, block_cmds, E, falls["ring"], nq,
                                                    int(getattr(args, "save_falls_max", DEFAULT_SAVE_FALLS_MAX))), float(env.dt))
     settings = dict(checkpoint=args.checkpoint, env=args.env, task=args.task, xml=args.xml, cone=args.cone,
@@ -1297,6 +1546,20 @@ def run(args, out=sys.stdout) -> Dict:
         settings.update(sequence=getattr(args, "sequence", None), then=getattr(args, "then", None),
                         switch_at=int(getattr(args, "switch_at", DEFAULT_SWITCH_AT)) if getattr(args, "then", None) else None,
                         response_tolerance=list(resp_tol), response_tail_after=tail_after, schedules=len(schedules))
+    if plants:
+        robust = float(getattr(args, "robust_fall_rate", DEFAULT_ROBUST_FALL_RATE))
+        for row in rows:      # after every per-cell object is in place: the robustness lines read the cells' own figures
+            row["robustness"] = reduce_robustness(row["plants"], robust)
+        settings.update(plant=getattr(args, "plant", None), plant_grid=getattr(args, "plant_grid", None), plants_per_command=len(plants),
+                        robust_fall_rate=robust,
+                        plant_semantics="kp, mass, frictionloss, armature: scales on the model's values (kp: every actuator's gain, the bias "
+                                        "following; mass: every body's mass, inertias NOT rescaled, as the reference's randomize.py; frictionloss, "
+                                        "armature: the actuated dofs'); delay: action delay in control steps, 0 1 2 or random (the sampler); "
+                                        "--gait's cost_of_transport keeps the model's nominal mass")
+    if randomized:
+        settings.update(randomize=True)
+    if getattr(args, "noise_level", None) is not None:
+        settings.update(noise_level=float(args.noise_level))
     if gait:
         settings.update(gait=True)
     if posture:
@@ -1321,6 +1584,8 @@ def run(args, out=sys.stdout) -> Dict:
     env.set_commands(None)
     if pushes:
         env.set_pushes(None)
+    if delays_t is not None:
+        env.set_action_delays(None)
     return report
 
 
@@ -1338,13 +1603,29 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--command", nargs="+", type=float, action="append", metavar="V",
                    help="vx vy wz [neck_pitch head_pitch head_yaw head_roll]; repeat for more commands")
     p.add_argument("--grid", type=str, default=None, help="a grid of commands: vx=a:b:n,wz=c:d:m (axes vx vy wz neck_pitch head_pitch head_yaw head_roll)")
-    p.add_argument("--envs_per_command", type=int, default=128, help="envs per command, or per (command, push) cell when pushes are given")
+    p.add_argument("--envs_per_command", type=int, default=128, help="envs per command, or per (command, push) / (command, plant) cell when pushes / plants are given")
     p.add_argument("--push", nargs=2, type=float, action="append", metavar=("DVX", "DVY"),
                    help="a world-frame velocity kick in m/s, added once to the base's planar velocity; repeat for more pushes")
     p.add_argument("--push_grid", type=str, default=None, help="a grid of pushes: magnitude=a:b:n,direction=c:d:m (m/s; degrees, world frame, 0 = +x)")
     p.add_argument("--push_at", type=int, default=DEFAULT_PUSH_AT, help="the step of the first episode (0 = its first) at which the kick is applied, once")
     p.add_argument("--push_tolerance", nargs=2, type=float, default=list(DEFAULT_PUSH_TOLERANCE), metavar=("LIN", "ANG"),
                    help="recovery: planar velocity error (m/s) and yaw-rate error (rad/s) above which a step counts as not recovered (BUILD-DEFINED defaults)")
+    p.add_argument("--plant", type=str, action="append", metavar="KEY=V[,KEY=V...]",
+                   help="a plant: scales kp (every actuator's gain, the bias following), mass (every body's mass; inertias are NOT rescaled, as the "
+                        "reference's randomize.py), frictionloss and armature (the actuated dofs') on the model's values, and delay = 0, 1, 2 or "
+                        "random (the action delay in control steps; random, the default, is the sampler); axes not named stay nominal; repeat "
+                        "for more plants.  Every (command, plant) cell gets --envs_per_command envs; every command row gains \"plants\" and "
+                        "\"robustness\".  Not with --push / --push_grid")
+    p.add_argument("--plant_grid", type=str, default=None,
+                   help="a cross product of plants: kp=0.7:1.3:4,mass=0.9:1.2:3,delay=0:2:3 (--grid's syntax; axes kp mass frictionloss armature "
+                        "delay; a delay axis must come out as whole numbers within 0..2)")
+    p.add_argument("--robust_fall_rate", type=float, default=DEFAULT_ROBUST_FALL_RATE, metavar="RATE",
+                   help="robustness: the fall rate up to which a plant counts as survived in \"survived_range\" (a reporting threshold of the "
+                        "user's, not a measured constant); read with plants only")
+    p.add_argument("--randomize", action="store_true",
+                   help="apply the training-time domain randomisation (randomize.domain_randomize, seeded by --seed) to every env; a plant's "
+                        "scales multiply it")
+    p.add_argument("--noise_level", type=float, default=None, metavar="X", help="override noise_config.level (default: the env's own, 1.0)")
     p.add_argument("--sequence", type=str, action="append", metavar="SCHEDULE",
                    help="a command schedule: \"0: 0 0 0 | 150: 0.15 0 0 | 400: 0 0 0.5\" -- segments apart by |, each `start_step: vx vy wz "
                         "[neck_pitch head_pitch head_yaw head_roll]`, the first at step 0, at most 8; repeat for more schedules.  Each is one row of "

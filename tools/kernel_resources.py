@@ -16,11 +16,11 @@ for line in sys.stdin:
     if m and cur is not None:
         cur[m.group(1).strip()] = m.group(2)
 print("# make -C open_duck_playground_amd/csrc resource (hipcc -Rpass-analysis=kernel-resource-usage): kernel<Shape dims, lanes per env, floor> VGPRs AGPRs "
-      "scratch(B/lane) waves/SIMD SGPRs (SGPRs kept in VGPR lanes)")
+      "scratch(B/lane) waves/SIMD SGPRs (SGPRs kept in VGPR lanes) static LDS (B/block; the env kernels' LDS is dynamic, sized at launch)")
 for r in rows:
     m = re.search(r"(reset_kernel|step_kernel|physics_kernel)IN3odk5ShapeI(.*?)EEELi(\d+)ELi(\d+)", r["name"])
     if not m:
         continue
     dims = m.group(2).replace("ELi", ",").replace("Li", "").replace("ELb", ",b").replace("n1", "-1")
     print(f"{m.group(1):15s} Shape<{dims}> G={m.group(3)} HF={m.group(4)}  vgpr {r.get('VGPRs', '?'):>3s} agpr {r.get('AGPRs', '?'):>3s} scratch {r.get('ScratchSize', '?'):>3s} "
-          f"occupancy {r.get('Occupancy', '?')} sgpr {r.get('TotalSGPRs', '?')} (spilled to lanes: {r.get('SGPRs Spill', '?')})")
+          f"occupancy {r.get('Occupancy', '?')} sgpr {r.get('TotalSGPRs', '?')} (spilled to lanes: {r.get('SGPRs Spill', '?')}) lds {r.get('LDS Size', '?')}")
