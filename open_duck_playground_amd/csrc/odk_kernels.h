@@ -74,6 +74,10 @@ struct Shape {
   // Twin dofs (the backlash model, nv 30): solves run on the reduced tree -- twins merged into their main dof, which is
   // the 20-dof robot's own tree (DevModel::paired; reduced_rhs / reduced_expand below).
   static constexpr bool PAIRED = (NV_ == 30);
+  // Hinges on one body: two only where a backlash twin shares its joint's body.  The joint-slot loops of forward_env's pose sweep run to
+  // MAXJB and size their register arrays by it, so a shape without twins carries no second slot (its copies, zero fills and exec-mask
+  // bookkeeping); the BodySt record keeps both slots.  The loader refuses a body with more hinges than its shape's MAXJB (select_shape).
+  static constexpr int MAXJB = PAIRED ? 2 : 1;
   // <equality><joint> rows (DevModel::neq) are compiled into this shape's kernels: the third shape (tests/assets/tail_biped*.xml) -- the
   // duck's shapes have no equality and do not pay for the code
   static constexpr bool EQ = (NV_ == 21) || OPT_;      // (OPT_: a shape that asks for the optional constraint code -- equality rows, elliptic cones as a runtime switch)
@@ -1957,13 +1961,16 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
   ODK_PROF(0);
   // ---------------- P1: top-down level sweep (lane = body): pose, cdof, cvel, velocity part of cacc, local bias force
   {
-    float p[3] = {0, 0, 0}, q[4] = {1, 0, 0, 0}, cvel[6] = {0, 0, 0, 0, 0, 0}, cacc[6] = {0, 0, 0, 0, 0, 0};
-    if (bs.level == -1) {  // world / static bodies
-      for (int k = 0; k < 3; k++) p[k] = bs.pos[k];
-      for (int k = 0; k < 4; k++) q[k] = bs.quat[k];
+    float p[3], q[4], cvel[6] = {0, 0, 0, 0, 0, 0}, cacc[6] = {0, 0, 0, 0, 0, 0};
+    {  // world / static bodies: the record's pose, as selects on the loaded registers (a branch made this seven zero moves and seven copies)
+      const bool stat = bs.level == -1;
+      for (int k = 0; k < 3; k++) p[k] = stat ? bs.pos[k] : 0.0f;
+      for (int k = 0; k < 4; k++) q[k] = stat ? bs.quat[k] : (k == 0 ? 1.0f : 0.0f);
     }
-    // bodies above the serial chains (world side of the tree: base, trunk): one tree level per step
-    for (int lvl = 0; lvl <= m->max_nonpath_level; lvl++) {
+    // bodies above the serial chains (world side of the tree: base, trunk): one tree level per step.  (The bound is read once: as
+    // `lvl <= m->max_nonpath_level` it was loaded again in every iteration, with the full wait for the load right behind it.)
+    const int max_np = m->max_nonpath_level;
+    for (int lvl = 0; lvl <= max_np; lvl++) {
       if (bs.level == lvl && !bs.is_path) {
         if (lvl == 0) {  // floating base: free joint (mj_comVel free-joint rule)
           for (int k = 0; k < 3; k++) p[k] = ref[k];
@@ -1994,7 +2001,7 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
           p[0] = pp[0] + t[0]; p[1] = pp[1] + t[1]; p[2] = pp[2] + t[2];
           qmul(q, pq, bs.quat);
 #pragma unroll
-          for (int jj = 0; jj < 2; jj++) {
+          for (int jj = 0; jj < S::MAXJB; jj++) {
             if (jj < bs.njnt) {  // hinge at the body origin (jnt_pos == 0, checked at load)
               float axw[3], cd[6], dot[6];
               qrot(axw, q, bs.ax[jj]);
@@ -2033,9 +2040,9 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
     {
       const bool isp = bs.is_path != 0, head = bs.path_head != 0;
       // local transform of the body relative to its parent, and the frames in which its joint axes are given
-      float ql[4] = {bs.quat[0], bs.quat[1], bs.quat[2], bs.quat[3]}, qb[2][4];
+      float ql[4] = {bs.quat[0], bs.quat[1], bs.quat[2], bs.quat[3]}, qb[S::MAXJB][4];
 #pragma unroll
-      for (int jj = 0; jj < 2; jj++) {
+      for (int jj = 0; jj < S::MAXJB; jj++) {
 #pragma unroll
         for (int k = 0; k < 4; k++) qb[jj][k] = ql[k];
         if (jj < bs.njnt) {
@@ -2079,11 +2086,12 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
         if (isp && !head) { ppq[0] = uq[0]; ppq[1] = uq[1]; ppq[2] = uq[2]; ppq[3] = uq[3]; }
       }
       // joint twists about the base origin and the body's own velocity / acceleration increments
-      float cd[2][6], qv[2] = {0, 0}, cinc[6] = {0, 0, 0, 0, 0, 0};
+      float cd[S::MAXJB][6], qv[S::MAXJB], cinc[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
-      for (int jj = 0; jj < 2; jj++) {
+      for (int jj = 0; jj < S::MAXJB; jj++) {
 #pragma unroll
         for (int k = 0; k < 6; k++) cd[jj][k] = 0.0f;
+        qv[jj] = 0.0f;
         if (isp && jj < bs.njnt) {
           float qw[4], axw[3];
           qmul(qw, ppq, qb[jj]);
@@ -2128,7 +2136,7 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
       if (isp) {
         float vb[6] = {pcv[0], pcv[1], pcv[2], pcv[3], pcv[4], pcv[5]};
 #pragma unroll
-        for (int jj = 0; jj < 2; jj++) {
+        for (int jj = 0; jj < S::MAXJB; jj++) {
           if (jj < bs.njnt) {
             float dot[6];
             cross_motion(dot, vb, cd[jj]);
@@ -2155,17 +2163,16 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
       ODK_SYNC();
     }
     float acc[16];   // cinert (10) | local bias force (6) of this lane's body, then their subtree sums
+    if (bid >= 0 && bs.level < 0) {
 #pragma unroll
-    for (int k = 0; k < 16; k++) acc[k] = 0.0f;
-    if (bid >= 0) {
-      if (bs.level < 0) {
+      for (int k = 0; k < 3; k++) XPOS[k * NB + bid] = p[k];
 #pragma unroll
-        for (int k = 0; k < 3; k++) XPOS[k * NB + bid] = p[k];
+      for (int k = 0; k < 4; k++) XQUAT[k * NB + bid] = q[k];
 #pragma unroll
-        for (int k = 0; k < 4; k++) XQUAT[k * NB + bid] = q[k];
-#pragma unroll
-        for (int k = 0; k < 6; k++) { CVEL[k * NB + bid] = 0; CACC[k * NB + bid] = 0; }
-      }
+      for (int k = 0; k < 6; k++) { CVEL[k * NB + bid] = 0; CACC[k * NB + bid] = 0; }
+    }
+    {   // every lane (uniform control flow: no zero fill of acc in front of a branch, no exec-mask bookkeeping): a lane without a body
+        // is not `dyn`, so its sixteen values are the zeros they were
       // cinert about the base origin, local bias force
       float R[9];
       q2mat(R, q);
@@ -2184,7 +2191,7 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
         for (int j = 0; j < 3; j++) T[3 * i + j] = R[3 * i] * Ib[j] + R[3 * i + 1] * Ib[3 + j] + R[3 * i + 2] * Ib[6 + j];
       for (int i = 0; i < 3; i++)
         for (int j = 0; j < 3; j++) Iw[3 * i + j] = T[3 * i] * R[3 * j] + T[3 * i + 1] * R[3 * j + 1] + T[3 * i + 2] * R[3 * j + 2];
-      const float mb = MASS[bid], o2 = dot3(off, off);
+      const float mb = MASS[bid >= 0 ? bid : 0], o2 = dot3(off, off);
       float ci[10];
       ci[0] = Iw[0] + mb * (o2 - off[0] * off[0]);
       ci[1] = Iw[4] + mb * (o2 - off[1] * off[1]);
@@ -2946,6 +2953,9 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
       for (int q = 0; q < 27; q++) {
         float x = v[q];
         x += ODK_DPP(x, 0xB1, 0xF); x += ODK_DPP(x, 0x4E, 0xF); x += ODK_DPP(x, 0x141, 0xF); x += ODK_DPP(x, 0x140, 0xF);
+        // (only lane 0 of a row stores the sum: unpinned, the last add sinks under that branch and leaves its row_mirror read behind as a
+        // v_mov_b32_dpp -- two instructions where v_add_f32_dpp is one)
+        asm volatile("" : "+v"(x));
         v[q] = x;
       }
       if (on && (lane & 15) == 0) {

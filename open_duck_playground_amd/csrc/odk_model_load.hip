@@ -502,7 +502,20 @@ struct Load {
   int foot_cg[2], floor_cg, cg_type[4], cg_body[4], cg_prio[4];            // collision geoms: the two feet and the floor
   double cg_pos[12], cg_quat[16], cg_fric[12], cg_solref[8], cg_solimp[20], cg_solmix[4];
   bool shape_eq = false;                                                   // the chosen shape carries the optional constraint code (Shape::EQ)
+  int body_name[MAXB][32];                                                 // k_body_name: the bodies' names, one character per int (optional; for messages only)
+  bool has_names = false;
 };
+// a body as a refusal names it: 'name' (body 3), or body 3 for a blob without the name table
+std::string body_label(const Load& c, int b) {
+  std::string s;
+  if (c.has_names) {
+    s = "'";
+    for (int k = 0; k < 32 && c.body_name[b][k] > 0 && c.body_name[b][k] < 128; k++) s += (char)c.body_name[b][k];
+    s += "' (";
+  }
+  s += "body " + std::to_string(b);
+  return c.has_names ? s + ")" : s;
+}
 int missing(const Load& c) { return fail(ODK_ERR_INVALID, "odk_model_load: missing %s", c.B.missing.c_str()); }
 const char* const NO_EQ_ROWS = "equality rows are compiled into the third and fourth model shapes only (the duck's kernels carry none)";
 // solref / solimp of equality constraint k -> the row's impedance constants
@@ -590,6 +603,18 @@ int load_tree(Load& c) {
     if (m.jnt_pos[j][0] != 0.0f || m.jnt_pos[j][1] != 0.0f || m.jnt_pos[j][2] != 0.0f) return fail(ODK_ERR_UNSUPPORTED, "hinge joints must sit at their body origin (jnt_pos == 0)");
   }
   for (int b2 = 0; b2 < m.nb; b2++) if (m.body_jntnum[b2] > 2) return fail(ODK_ERR_UNSUPPORTED, "more than two joints on one body");
+  memset(c.body_name, 0, sizeof(c.body_name));
+  c.has_names = B.optI("k_body_name", &c.body_name[0][0], MAXB * 32) == m.nb * 32;
+  // Two hinges on one body are a joint and its backlash twin (same axis: build_reduced_tables) and nothing else: only the twin shape's
+  // kernels carry a second joint slot (Shape::MAXJB), so two independent hinges on one body are refused here, by the body's name
+  for (int b2 = 0; b2 < m.nb; b2++) {
+    if (b2 == m.base_body || m.body_jntnum[b2] != 2) continue;
+    const int j0 = m.body_jntadr[b2], j1 = j0 + 1;
+    if (j0 < 1 || j1 >= m.nj) return fail(ODK_ERR_INVALID, "body_jntadr of %s", body_label(c, b2).c_str());
+    if (m.jnt_axis[j0][0] != m.jnt_axis[j1][0] || m.jnt_axis[j0][1] != m.jnt_axis[j1][1] || m.jnt_axis[j0][2] != m.jnt_axis[j1][2])
+      return fail(ODK_ERR_UNSUPPORTED, "%s carries two hinge joints that are not a joint and its backlash twin: the kernels take one hinge per body (give the second hinge a body of its own)",
+                  body_label(c, b2).c_str());
+  }
   B.I("k_vdof_depth", m.vdof_depth, MAXV); B.I2("k_vdof_anc", &m.vdof_anc[0][0], MAXV, MAXV); B.I("k_vdof_Madr", m.vdof_Madr, MAXV);
   B.I2("k_vdof_anc_adr", &m.vdof_anc_adr[0][0], MAXV, MAXV); B.I("k_vdof_ndesc", m.vdof_ndesc, MAXV);
   B.I2("k_vdof_desc", &m.vdof_desc[0][0], MAXV, MAXV); B.I2("k_vdof_desc_adr", &m.vdof_desc_adr[0][0], MAXV, MAXV);
@@ -848,9 +873,9 @@ int select_shape(Load& c) {
   if (!fill_body_st(m)) return fail(ODK_ERR_UNSUPPORTED, "no body-to-lane layout: every serial body chain must fit in one 16-lane row and all %d bodies in 32 lanes", m.nb);
   int dt_max = 0, dv_max = 0;
   for (int d = 0; d < m.nv; d++) { dt_max = m.dof_depth[d] > dt_max ? m.dof_depth[d] : dt_max; dv_max = m.vdof_depth[d] > dv_max ? m.vdof_depth[d] : dv_max; }
-  int shape = -1, shape_cl = 5, shape_nch = 3;
+  int shape = -1, shape_cl = 5, shape_nch = 3, shape_maxjb = 1;
 #define X(i, S) if (shape < 0 && m.nq == S::NQ && m.nv == S::NV && m.nb == S::NB && m.nu == S::NU && m.nj == S::NJ && m.nM == S::NM && m.nH == S::NH && m.nrow == S::NROW && \
-                    dt_max <= S::DT && dv_max <= S::DV) { shape = i; shape_cl = S::CL; shape_nch = S::NCH; c.shape_eq = S::EQ; }
+                    dt_max <= S::DT && dv_max <= S::DV) { shape = i; shape_cl = S::CL; shape_nch = S::NCH; shape_maxjb = S::MAXJB; c.shape_eq = S::EQ; }
   ODK_SHAPES(X)
 #undef X
   c.mo.shape = shape;
@@ -859,6 +884,9 @@ int select_shape(Load& c) {
                 m.nq, m.nv, m.nb, m.nu, m.nj, m.nM, m.nH, m.nrow, dt_max, dv_max);
   for (int k = 0; k < m.nrchain; k++)
     if (m.rchain_len[k] > shape_cl) return fail(ODK_ERR_UNSUPPORTED, "a serial chain of %d (twin-merged) dofs: the kernels of this model shape solve chains of <= %d", m.rchain_len[k], shape_cl);
+  for (int b = 0; b < m.nb; b++)      // (the joint slots fill_body_st gave the body's lane: bodies below the floating base)
+    if (m.body_in_tree[b] && m.body_level[b] > 0 && m.body_jntnum[b] > shape_maxjb)
+      return fail(ODK_ERR_UNSUPPORTED, "%s carries %d hinge joints: the kernels of this model shape take %d per body", body_label(c, b).c_str(), m.body_jntnum[b], shape_maxjb);
   if (m.nrchain > shape_nch) return fail(ODK_ERR_UNSUPPORTED, "%d serial chains below the floating base: the kernels of this model shape solve <= %d", m.nrchain, shape_nch);
   if (!m.floor_is_plane && shape != 1) return fail(ODK_ERR_UNSUPPORTED, "height-field floors are built for the backlash model only");
   if (m.cone && m.foot_prim != 0)

@@ -77,7 +77,14 @@ class Model:
     def blob(self) -> bytes:
         """Wire format: compiled arrays + the kernels' static topology tables (tables.py)."""
         from .tables import build_kernel_tables
-        return pack_blob({**self.a, **build_kernel_tables(self.a)})
+        extra = {}
+        if "names_body" in self.a:      # the loader names a body it refuses (one character per int: the blob holds numbers only)
+            nm = np.zeros((self.nbody, 32), np.int32)
+            for i, s in enumerate(list(self.a["names_body"])[: self.nbody]):
+                b = str(s).encode("ascii", "replace")[:31]
+                nm[i, : len(b)] = list(b)
+            extra["k_body_name"] = nm
+        return pack_blob({**self.a, **build_kernel_tables(self.a), **extra})
 
     # name lookups (mj_name2id equivalents, base.py:136-152)
     def _id(self, table: str, name: str) -> int:

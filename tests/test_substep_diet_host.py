@@ -1,0 +1,151 @@
+"""Host-side checks of the substep diet (profiles/substep_diet): joint slots at compile time (Shape::MAXJB) and the ISA census tool.
+
+The env kernels of a shape without backlash twins carry ONE joint slot per body, so the loader must refuse -- with the body's name -- a model
+that puts two independent hinges on one body, and must go on taking every model that ships.  The census tool (tools/isa_overhead_census.py)
+is run on a listing of shape A's kernel set compiled here (CPU only, cross-compiled for gfx950)."""
+import glob
+import os
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ASSETS = os.path.join(ROOT, "tests", "assets")
+PARENT_P1_MOV = 161      # v_mov_b32_e32 in P1 of step_kernel<ShapeA,32,0>, one substep, at the commit before the diet (profiles/substep_diet/NOTES.md)
+PARENT_P1_VALU = 1237
+
+# Three moving bodies: a floating base and two one-body legs with box feet; the left leg carries TWO independent hinges (pitch and roll).
+TWO_HINGES = """<mujoco model="two_hinges_on_one_body">
+  <compiler angle="radian"/>
+  <option timestep="0.002" iterations="1" ls_iterations="5"><flag eulerdamp="disable"/></option>
+  <worldbody>
+    <body name="base" pos="0 0 0.3">
+      <freejoint name="floating_base"/>
+      <inertial pos="0 0 0" mass="1.0" fullinertia="0.01 0.01 0.01 0 0 0"/>
+      <site name="imu" pos="0 0 0.02"/>
+      <body name="left_ankle_block" pos="0 0.05 -0.05">
+        <inertial pos="0 0 -0.05" mass="0.2" fullinertia="0.001 0.001 0.0005 0 0 0"/>
+        <joint name="left_pitch" type="hinge" axis="0 1 0" range="-1 1" damping="0.1" armature="0.01"/>
+        {second}
+        <geom name="left_foot_box" type="box" pos="0 0 -0.1" size="0.04 0.02 0.01"/>
+        <site name="left_foot" pos="0 0 -0.1"/>
+      </body>
+      <body name="right_ankle_block" pos="0 -0.05 -0.05">
+        <inertial pos="0 0 -0.05" mass="0.2" fullinertia="0.001 0.001 0.0005 0 0 0"/>
+        <joint name="right_pitch" type="hinge" axis="0 1 0" range="-1 1" damping="0.1" armature="0.01"/>
+        <geom name="right_foot_box" type="box" pos="0 0 -0.1" size="0.04 0.02 0.01"/>
+        <site name="right_foot" pos="0 0 -0.1"/>
+      </body>
+    </body>
+    <body name="floor">
+      <geom name="floor" type="plane" size="0 0 0.05" contype="1" conaffinity="0" priority="1" friction="0.8"/>
+    </body>
+  </worldbody>
+  <actuator>
+    <position name="left_pitch" joint="left_pitch" kp="5" inheritrange="1"/>
+    {second_act}
+    <position name="right_pitch" joint="right_pitch" kp="5" inheritrange="1"/>
+  </actuator>
+  <sensor>
+    <gyro site="imu" name="gyro"/>
+    <velocimeter site="imu" name="local_linvel"/>
+    <accelerometer site="imu" name="accelerometer"/>
+    <framezaxis objtype="site" objname="imu" name="upvector"/>
+    <frameangvel objtype="site" objname="imu" name="global_angvel"/>
+    <framelinvel objtype="site" objname="right_foot" name="right_foot_global_linvel"/>
+    <framelinvel objtype="site" objname="left_foot" name="left_foot_global_linvel"/>
+  </sensor>
+  <keyframe><key name="home" qpos="0 0 0.3 1 0 0 0 {q}" ctrl="{q}"/></keyframe>
+</mujoco>
+"""
+
+
+def _shipped_models():
+    from open_duck_playground_amd.model import Model, load_task_model
+    for task in ("flat_terrain", "flat_terrain_backlash", "rough_terrain_backlash"):
+        yield task, load_task_model(task)
+    for path in sorted(glob.glob(os.path.join(ASSETS, "*.xml"))):
+        yield os.path.basename(path), Model.from_xml(path, sim_dt=0.002)
+
+
+def test_loader_accepts_every_shipped_model():
+    """Every model that ships and has a compiled shape still loads, with the hinge counts its shape's joint slots take: two on a body of the
+    backlash models only (a joint and its twin), one everywhere else.  (The assets without a kernel set are refused for THAT reason, as before:
+    toy_box_hopper.xml has no feet sites, biped12_neck.xml is the example of a robot whose shape is added with tools/new_shape.py.)"""
+    import numpy as np
+    from open_duck_playground_amd import engine
+    no_shape = {"toy_box_hopper.xml", "biped12_neck.xml"}
+    seen = 0
+    for name, model in _shipped_models():
+        if name in no_shape:
+            with pytest.raises((engine.OdkError, ValueError)) as ei:
+                engine.model_reduction(model)
+            assert "hinge" not in str(ei.value), (name, str(ei.value))
+            continue
+        red = engine.model_reduction(model)      # odk_model_load on the host
+        most = int(np.asarray(model.a["body_jntnum"])[2:].max())
+        assert most == (2 if red["paired"] else 1), (name, most, red["paired"])
+        seen += 1
+    assert seen >= 10
+
+
+def _write(tmp_path, second_hinge):
+    xml = TWO_HINGES.format(
+        second='<joint name="left_roll" type="hinge" axis="1 0 0" range="-1 1" damping="0.1" armature="0.01"/>' if second_hinge else "",
+        second_act='<position name="left_roll" joint="left_roll" kp="5" inheritrange="1"/>' if second_hinge else "",
+        q="0 0 0" if second_hinge else "0 0")
+    path = os.path.join(str(tmp_path), "two_hinges.xml" if second_hinge else "one_hinge.xml")
+    with open(path, "w") as f:
+        f.write(xml)
+    return path
+
+
+def test_loader_refuses_two_hinges_on_a_body_without_twins_by_name(tmp_path):
+    from open_duck_playground_amd import engine
+    from open_duck_playground_amd.model import Model
+    with pytest.raises(engine.OdkError, match=r"'left_ankle_block' \(body 2\) carries two hinge joints") as ei:
+        engine.model_reduction(Model.from_xml(_write(tmp_path, True), sim_dt=0.002))
+    assert "twin" in str(ei.value)
+    # the same robot with one hinge per body gets past that check: what refuses it is something else (a toy this small has neither the duck's
+    # sensor set nor a kernel set), and the message does not speak of hinges
+    with pytest.raises(engine.OdkError) as ei:
+        engine.model_reduction(Model.from_xml(_write(tmp_path, False), sim_dt=0.002))
+    assert "hinge" not in str(ei.value) and "left_ankle_block" not in str(ei.value)
+
+
+def test_shape_joint_slots():
+    """Shape::MAXJB as the kernels are compiled: 2 for the twin shape, 1 for every other one (read from the header, which static_asserts nothing
+    about it: the kernels' loops and the loader's refusal both go by this one constant)."""
+    src = open(os.path.join(ROOT, "open_duck_playground_amd", "csrc", "odk_kernels.h")).read()
+    assert "static constexpr int MAXJB = PAIRED ? 2 : 1;" in src
+    assert "jj < 2" not in src and "jj < S::MAXJB" in src
+
+
+@pytest.fixture(scope="module")
+def listing_a(tmp_path_factory):
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import isa_overhead_census as census
+    if not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.fail("hipcc is needed to compile the listing the census reads")
+    out = os.path.join(str(tmp_path_factory.mktemp("census")), "odk_env_A.s")
+    return census, census.compile_listing("A", out)
+
+
+def test_census_of_shape_a(listing_a):
+    census, listing = listing_a
+    stats = census.census(listing, "A")
+    phases = list(stats)
+    assert phases[0] == "pre" and "after 0" in phases and "after 10" in phases and phases[-1] == "after 17"
+    p1, force = stats["after 0"], stats["after 10"]
+    print("P1", dict(p1)); print("force", dict(force))
+    assert 0 < p1["mov"] < PARENT_P1_MOV, p1["mov"]
+    assert 0 < p1["valu"] < PARENT_P1_VALU, p1["valu"]
+    assert p1["mov"] == p1["mov_imm"] + p1["mov_vgpr"] + p1["mov_sgpr"]
+    # the K-block row sums end in fused v_add_f32_dpp row_mirror: no row_mirror read is left as a move in front of a plain add
+    assert force["unf_rm"] == 0, force["unf_rm"]
+    assert force["mov_dpp"] > 0      # (stage 1 stays v_mul / v_mov_b32_dpp quad_perm / v_fmac: an FMA contraction that fixes the bits)
+    # the tool's command line prints the same table
+    txt = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_overhead_census.py"), "A", "--listing", listing], check=True, capture_output=True, text=True).stdout
+    row = next(l for l in txt.splitlines() if l.startswith("after 0 "))
+    assert int(row.split()[2]) == p1["valu"] and "unf_rm" in txt.splitlines()[0] and any(l.startswith("substep") for l in txt.splitlines())
