@@ -1,5 +1,6 @@
-// odk_engine.hip -- the batch C-ABI of include/odk.h (libodk.so) + the accumulator kernels of the tracking / push / gait / posture / imitation / response / fall reports
-// and the command-schedule kernel.
+// odk_engine.hip -- the batch C-ABI of include/odk.h (libodk.so): create / destroy / configure, the binders and setters that own batch state,
+// reset / step / physics step and launch(), the state / record / debug getters and the step timing.  The evaluation reports' kernels and
+// entry points (odk_*_accumulate, odk_command_schedule_apply) are odk_reports.hip; both see the batch through odk_batch.h.
 //
 // Host side: device buffers, launches on the caller's stream (blob -> DevModel, odk_model_load and the model getters: odk_model_load.hip).  Device side:
 // the reset / step / physics-only kernels live in odk_env_kernels.h and are compiled one object per kernel set (odk_env_unit.hip); this file
@@ -8,46 +9,17 @@
 #include <stddef.h>
 
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <string>
 #include <vector>
 
 #include "../../include/odk.h"
-#include "odk_host.h"
+#include "odk_batch.h"
 #include "odk_shapes.h"
 
 using namespace odk;
 
-// the env kernels (reset / step / physics-only) and launch_sg: odk_env_kernels.h, one object per kernel set (odk_env_unit.hip)
-
-// ================================================================================================
-// host side
 // (the thread's error string, fail() and the whole model side -- blob parsing, table builders, odk_model_load, the odk_model_* getters -- live in
-// the host-only odk_model_load.hip; what follows is the batch API)
-#define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) return fail(ODK_ERR_HIP, "%s: %s", #x, hipGetErrorString(_e)); } while (0)
-
-struct odk_batch {
-  odk_model model;
-  int nenv, device, G;
-  odk_env_config cfg;
-  DevModel* d_model = nullptr; DevPRM h_prm; float* d_table = nullptr;
-  float* d_recs = nullptr; float* d_first = nullptr; float* d_dr = nullptr; float* d_dbg = nullptr; float* d_hfield = nullptr;
-  std::vector<float> h_dr; bool dr_enabled = false;
-  int rec_size, frec_size, lds_total, dr_size, env_lds;
-  static constexpr size_t ODK_TIMING_EVENT_PAIRS = 1024;
-  int timing = 0; size_t timing_count = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> events; size_t ev_used = 0;   // timing: 0 off, n: every n-th launch
-  const float* d_cmd = nullptr; int cmd_stride = 0;   // odk_batch_bind_commands (caller-owned device rows), null: sampled commands
-  const float* d_push = nullptr; int push_stride = 0; // odk_batch_bind_pushes (caller-owned device rows), null: the sampled push
-  const int32_t* d_delay = nullptr; int delay_stride = 0;   // odk_batch_bind_action_delays (caller-owned device rows), null: the sampled delay
-  XTerms* d_xt = nullptr; bool xt_on = false;         // odk_batch_set_reward_terms: the batch's device copy; passed to the kernels while some term is on
-  float* d_xmet = nullptr;                             // odk_batch_bind_reward_metrics (caller-owned)
-  int* d_imap = nullptr; bool imap_set = false;        // odk_batch_set_imitation_joints: the batch's device copy; set: a map was given (the duck's
-                                                       // shapes start with theirs)
-  int* d_hslot = nullptr; bool hmap_set = false;       // odk_batch_set_head_joints: per actuator, its posture-command slot (-1: none); set as d_imap
-};
-
+// the host-only odk_model_load.hip)
 
 extern "C" void odk_default_config(odk_env_config* c) {
   memset(c, 0, sizeof(*c));
@@ -424,616 +396,6 @@ extern "C" int odk_batch_set_head_joints(odk_batch* b, const int32_t* actuator, 
 extern "C" int odk_batch_bind_reward_metrics(odk_batch* b, float* dev) {
   if (!b) return fail(ODK_ERR_INVALID, "null batch");
   b->d_xmet = dev;
-  return ODK_OK;
-}
-
-// Velocity-tracking sums of one evaluation step (one thread per env): the achieved values are the noise-free privileged observation's
-// gyro (row offset nobs) and local linear velocity (nobs + 9), joystick.py:596-604 / standing.py:549-556
-__global__ void __launch_bounds__(256) tracking_kernel(const float* __restrict__ priv, int npriv, int nobs, const float* __restrict__ reward,
-                                                       const float* __restrict__ done, const float* __restrict__ trunc, const float* __restrict__ cmd,
-                                                       int cmd_stride, float* __restrict__ acc, int nenv) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= nenv) return;
-  float* A = acc + (size_t)e * ODK_TRACK_NACC;
-  if (A[ODK_TRACK_ENDED] != 0.0f) return;       // past its first episode (the Evaluator's `active`)
-  const float d = done[e];
-  A[ODK_TRACK_STEPS] += 1.0f;
-  A[ODK_TRACK_REWARD] += reward[e];
-  if (d != 0.0f) {   // the observation of a done step is the auto-reset's first one: no velocity sample
-    if (trunc[e] == 0.0f) A[ODK_TRACK_FALLS] += 1.0f;
-    A[ODK_TRACK_ENDED] = 1.0f;
-    return;
-  }
-  const float* P = priv + (size_t)e * npriv;
-  const float* C = cmd + (size_t)e * cmd_stride;
-  const float v[3] = {P[nobs + 9], P[nobs + 10], P[nobs + 2]};
-  A[ODK_TRACK_SAMPLES] += 1.0f;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const float err = v[k] - C[k];
-    A[ODK_TRACK_SUM + k] += v[k];
-    A[ODK_TRACK_SQERR + k] += err * err;
-  }
-}
-
-extern "C" int odk_tracking_accumulate(const odk_batch* b, const float* priv_dev, const float* reward_dev, const float* done_dev,
-                                       const float* truncation_dev, float* acc_dev, void* stream) {
-  if (!b || !priv_dev || !reward_dev || !done_dev || !truncation_dev || !acc_dev) return fail(ODK_ERR_INVALID, "null argument");
-  if (!b->d_cmd) return fail(ODK_ERR_INVALID, "odk_tracking_accumulate: no commands bound (odk_batch_bind_commands)");
-  int nobs, npriv;
-  obs_sizes_nu(b->model.h.nu, b->cfg.env_kind, &nobs, &npriv);
-  HIPCHK(hipSetDevice(b->device));
-  hipLaunchKernelGGL(tracking_kernel, dim3((b->nenv + 255) / 256), dim3(256), 0, (hipStream_t)stream, priv_dev, npriv, nobs, reward_dev, done_dev,
-                     truncation_dev, b->d_cmd, b->cmd_stride, acc_dev, b->nenv);
-  HIPCHK(hipGetLastError());
-  return ODK_OK;
-}
-
-// Push-recovery state of one evaluation step (one thread per env), issued between odk_step and odk_tracking_accumulate: the tracking
-// accumulator's ENDED slot still tells whether the env's first episode was running when this step began.  Achieved velocities as above.
-__global__ void __launch_bounds__(256) push_kernel(const float* __restrict__ priv, int npriv, int nobs, const float* __restrict__ done,
-                                                   const float* __restrict__ trunc, const float* __restrict__ cmd, int cmd_stride,
-                                                   const float* __restrict__ push, int push_stride, const float* __restrict__ track,
-                                                   float lin_tol, float ang_tol, float* __restrict__ acc, int nenv) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= nenv) return;
-  const float* T = track + (size_t)e * ODK_TRACK_NACC;
-  if (T[ODK_TRACK_ENDED] != 0.0f) return;       // past its first episode
-  float* A = acc + (size_t)e * ODK_PUSH_NACC;
-  const float* K = push + (size_t)e * push_stride;
-  bool pushed = A[ODK_PUSH_PUSHED] != 0.0f;
-  if (!pushed && (K[0] != 0.0f || K[1] != 0.0f)) {   // the step that just ran read this row: the pushed step
-    pushed = true;
-    A[ODK_PUSH_PUSHED] = 1.0f;
-    A[ODK_PUSH_PUSH_AT] = T[ODK_TRACK_STEPS];        // first-episode steps before this one
-  }
-  const float since = T[ODK_TRACK_STEPS] - A[ODK_PUSH_PUSH_AT] + 1.0f;   // steps from the pushed step to this one, counting both
-  if (done[e] != 0.0f) {   // ends the first episode; no velocity sample (the observation is the auto-reset's)
-    if (pushed && trunc[e] == 0.0f) { A[ODK_PUSH_FELL] = 1.0f; A[ODK_PUSH_STEPS_TO_FALL] = since; }
-    return;
-  }
-  const float* P = priv + (size_t)e * npriv;
-  const float* C = cmd + (size_t)e * cmd_stride;
-  const float ex = P[nobs + 9] - C[0], ey = P[nobs + 10] - C[1];
-  // the planar error through float64 (the squares are exact there, the root is correctly rounded, then one rounding to float32): a host
-  // restatement reproduces it, and with it LAST_OFF and the peaks, bit for bit whatever the compiler fuses
-  const float lin = (float)sqrt((double)ex * (double)ex + (double)ey * (double)ey), ang = fabsf(P[nobs + 2] - C[2]);
-  if (!pushed) {
-    // compensated (Kahan) sum: SUM stays within an ulp of the true sum however many samples come before the push; LOW keeps what SUM dropped
-    const float s = A[ODK_PUSH_PRE_LIN_ERR_SUM], y = lin + A[ODK_PUSH_PRE_LIN_ERR_LOW];
-    const float t = s + y;
-    A[ODK_PUSH_PRE_LIN_ERR_SUM] = t;
-    A[ODK_PUSH_PRE_LIN_ERR_LOW] = y - (t - s);
-    A[ODK_PUSH_PRE_SAMPLES] += 1.0f;
-    return;
-  }
-  if (lin > lin_tol || ang > ang_tol) A[ODK_PUSH_LAST_OFF] = since;
-  A[ODK_PUSH_PEAK_LIN_ERR] = fmaxf(A[ODK_PUSH_PEAK_LIN_ERR], lin);
-  A[ODK_PUSH_PEAK_ANG_ERR] = fmaxf(A[ODK_PUSH_PEAK_ANG_ERR], ang);
-}
-
-extern "C" int odk_push_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
-                                   const float* track_acc_dev, float lin_tol, float ang_tol, float* acc_dev, void* stream) {
-  if (!b || !priv_dev || !done_dev || !truncation_dev || !track_acc_dev || !acc_dev) return fail(ODK_ERR_INVALID, "null argument");
-  if (!b->d_cmd) return fail(ODK_ERR_INVALID, "odk_push_accumulate: no commands bound (odk_batch_bind_commands)");
-  if (!b->d_push) return fail(ODK_ERR_INVALID, "odk_push_accumulate: no pushes bound (odk_batch_bind_pushes)");
-  int nobs, npriv;
-  obs_sizes_nu(b->model.h.nu, b->cfg.env_kind, &nobs, &npriv);
-  HIPCHK(hipSetDevice(b->device));
-  hipLaunchKernelGGL(push_kernel, dim3((b->nenv + 255) / 256), dim3(256), 0, (hipStream_t)stream, priv_dev, npriv, nobs, done_dev, truncation_dev,
-                     b->d_cmd, b->cmd_stride, b->d_push, b->push_stride, track_acc_dev, lin_tol, ang_tol, acc_dev, b->nenv);
-  HIPCHK(hipGetLastError());
-  return ODK_OK;
-}
-
-// Gait and actuator-load sums of one evaluation step, issued between odk_step and odk_tracking_accumulate (the ENDED contract of push_kernel).
-// One 16-lane DPP row per env, lane = actuator, four envs per wave: the nu-wide reads of the privileged row and the per-actuator arrays of the
-// accumulator row (stride ODK_GAIT_STRIDE = 16) are contiguous 64-byte accesses, the per-env scalars are row sums (the four in-row butterfly
-// stages of greduce).  The 32 scalar slots are held two per lane (u and 16 + u); every lane computes the row-uniform terms and keeps its own.
-// Only a gait sample (first episode, not done) stores anything, so every other row keeps its bits.
-__device__ __forceinline__ float row_sum16(float x) {   // uniform control flow only
-  x += ODK_DPP(x, 0xB1, 0xF); x += ODK_DPP(x, 0x4E, 0xF); x += ODK_DPP(x, 0x141, 0xF); x += ODK_DPP(x, 0x140, 0xF);
-  return x;
-}
-__global__ void __launch_bounds__(256) gait_kernel(const float* __restrict__ priv, int npriv, int nobs, int nu, const float* __restrict__ done,
-                                                   const float* __restrict__ track, const float* __restrict__ limit, float* __restrict__ acc, int nenv) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int e = t >> 4, u = t & 15;
-  const bool sample = e < nenv && track[(size_t)(e < nenv ? e : 0) * ODK_TRACK_NACC + ODK_TRACK_ENDED] == 0.0f && done[e < nenv ? e : 0] == 0.0f;
-  const bool act = sample && u < nu;
-  const float* P = priv + (size_t)(sample ? e : 0) * npriv;   // row 0 for the rows that only take part in the row sums
-  float* A = acc + (size_t)(sample ? e : 0) * ODK_GAIT_NACC;
-  const float* Q = P + nobs;
-  // per actuator (0 in the lanes past nu and in the rows that are no sample)
-  const float a1 = act ? P[13 + 2 * nu + u] : 0.0f, a2 = act ? P[13 + 3 * nu + u] : 0.0f;
-  const float q = act ? Q[15 + u] : 0.0f, v = act ? Q[15 + nu + u] : 0.0f, f = act ? Q[16 + 2 * nu + u] : 0.0f;
-  const float lim = (act && limit) ? limit[u] : 0.0f;
-  const float af = fabsf(f), pw = fabsf(f * v), da = a1 - a2;
-  const float power = row_sum16(pw), arate = row_sum16(da * da);
-  if (!sample) return;
-  // per env (the same in the row's 16 lanes)
-  const float n0 = A[ODK_GAIT_SAMPLES];
-  const bool first = n0 == 0.0f;
-  const float h = Q[15 + 2 * nu];
-  float c[2], td[2], swing[2], slip[2], run[2];
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    const float* FV = Q + 18 + 3 * nu + 3 * k;
-    const bool con = Q[16 + 3 * nu + k] != 0.0f;
-    const float air = A[ODK_GAIT_AIR_RUN + k];
-    const bool touch = con && !first && A[ODK_GAIT_PREV_CONTACT + k] == 0.0f;
-    c[k] = con ? 1.0f : 0.0f;
-    td[k] = touch ? 1.0f : 0.0f;
-    swing[k] = touch ? air : 0.0f;               // the non-contact run that this touchdown ends
-    slip[k] = con ? hypotf(FV[0], FV[1]) : 0.0f;
-    run[k] = con ? 0.0f : air + 1.0f;
-  }
-  const float speed = hypotf(Q[9], Q[10]), wob = Q[0] * Q[0] + Q[1] * Q[1];
-  // scalar slot s: what it gains, or (bookkeeping) what it becomes
-  auto next = [&](int s, float old) {
-    float inc = 0.0f;
-    inc = s == ODK_GAIT_SAMPLES ? 1.0f : inc;
-    inc = s == ODK_GAIT_SPEED_SUM ? speed : inc;
-    inc = s == ODK_GAIT_ABS_POWER_SUM ? power : inc;
-    inc = s == ODK_GAIT_CONTACT ? c[0] : s == ODK_GAIT_CONTACT + 1 ? c[1] : inc;
-    inc = s == ODK_GAIT_DOUBLE ? c[0] * c[1] : inc;
-    inc = s == ODK_GAIT_FLIGHT ? (1.0f - c[0]) * (1.0f - c[1]) : inc;
-    inc = s == ODK_GAIT_TOUCHDOWNS ? td[0] : s == ODK_GAIT_TOUCHDOWNS + 1 ? td[1] : inc;
-    inc = s == ODK_GAIT_SWING_STEPS_SUM ? swing[0] : s == ODK_GAIT_SWING_STEPS_SUM + 1 ? swing[1] : inc;
-    inc = s == ODK_GAIT_SLIP_SUM ? slip[0] : s == ODK_GAIT_SLIP_SUM + 1 ? slip[1] : inc;
-    inc = s == ODK_GAIT_HEIGHT_SUM ? h : inc;
-    inc = s == ODK_GAIT_HEIGHT_SQ_SUM ? h * h : inc;
-    inc = s == ODK_GAIT_ROLLPITCH_RATE_SQ_SUM ? wob : inc;
-    inc = s == ODK_GAIT_ACTION_RATE_SUM ? arate : inc;
-    float nv = old + inc;
-    nv = s == ODK_GAIT_PREV_CONTACT ? c[0] : s == ODK_GAIT_PREV_CONTACT + 1 ? c[1] : nv;
-    nv = s == ODK_GAIT_AIR_RUN ? run[0] : s == ODK_GAIT_AIR_RUN + 1 ? run[1] : nv;
-    return nv;
-  };
-  const float s0 = next(u, A[u]), s1 = next(16 + u, A[16 + u]);
-  A[u] = s0;
-  A[16 + u] = s1;
-  if (u >= nu) return;
-  float* B = A + u;
-  B[ODK_GAIT_TORQUE_SQ] += f * f;
-  B[ODK_GAIT_TORQUE_PEAK] = fmaxf(B[ODK_GAIT_TORQUE_PEAK], af);
-  B[ODK_GAIT_VEL_PEAK] = fmaxf(B[ODK_GAIT_VEL_PEAK], fabsf(v));
-  B[ODK_GAIT_SAT] += (lim > 0.0f && af >= 0.99f * lim) ? 1.0f : 0.0f;
-  B[ODK_GAIT_ABS_POWER] += pw;
-  B[ODK_GAIT_RANGE_MIN] = first ? q : fminf(B[ODK_GAIT_RANGE_MIN], q);   // a zeroed row is no minimum: the first sample starts the range
-  B[ODK_GAIT_RANGE_MAX] = first ? q : fmaxf(B[ODK_GAIT_RANGE_MAX], q);
-}
-
-extern "C" int odk_gait_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
-                                   const float* track_acc_dev, const float* torque_limit_dev, float* acc_dev, void* stream) {
-  if (!b) return fail(ODK_ERR_INVALID, "odk_gait_accumulate: null batch");
-  if (!priv_dev) return fail(ODK_ERR_INVALID, "odk_gait_accumulate: null priv_dev");
-  if (!done_dev) return fail(ODK_ERR_INVALID, "odk_gait_accumulate: null done_dev");
-  if (!truncation_dev) return fail(ODK_ERR_INVALID, "odk_gait_accumulate: null truncation_dev");
-  if (!track_acc_dev) return fail(ODK_ERR_INVALID, "odk_gait_accumulate: null track_acc_dev");
-  if (!acc_dev) return fail(ODK_ERR_INVALID, "odk_gait_accumulate: null acc_dev");
-  const int nu = b->model.h.nu;
-  if (nu > ODK_GAIT_STRIDE) return fail(ODK_ERR_INVALID, "odk_gait_accumulate: the model has %d actuators, a row holds %d", nu, ODK_GAIT_STRIDE);
-  int nobs, npriv;
-  obs_sizes_nu(nu, b->cfg.env_kind, &nobs, &npriv);
-  HIPCHK(hipSetDevice(b->device));
-  const long long threads = (long long)b->nenv * 16;
-  hipLaunchKernelGGL(gait_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, priv_dev, npriv, nobs, nu, done_dev,
-                     track_acc_dev, torque_limit_dev, acc_dev, b->nenv);
-  HIPCHK(hipGetLastError());
-  return ODK_OK;
-}
-
-// Posture and stillness sums of one evaluation step, issued between odk_step and odk_tracking_accumulate (the ENDED contract of push_kernel), in
-// gait_kernel's layout: one 16-lane DPP row per env, lane = actuator, four envs per wave.  Every actuator lane loads its posture-command slot
-// (hslot[u], -1: a leg) and its home pose; the per-env scalars are row sums, held one per lane (lanes 0 .. 9), and the lane whose hslot is
-// k >= 0 owns slot k's entries of the four per-slot arrays.  Inputs, offsets into the env's privileged row (both tasks: build_obs_table):
-// gyro nobs | gravity nobs + 6 | local linvel nobs + 9 | joint angle minus default nobs + 15 + u | joint_vel nobs + 15 + nu + u | root height
-// nobs + 15 + 2 nu.  Only a sample (first episode, not done) stores anything, so every other row keeps its bits.
-__device__ __forceinline__ float planar32(float x, float y) {   // hypot through float64: a host restatement has its bits (push_kernel's `lin`)
-  return (float)sqrt((double)x * (double)x + (double)y * (double)y);
-}
-__global__ void __launch_bounds__(256) posture_kernel(const float* __restrict__ priv, int npriv, int nobs, int nu, const float* __restrict__ done,
-                                                      const float* __restrict__ track, const float* __restrict__ cmd, int cmd_stride,
-                                                      const int* __restrict__ hslot, const DevModel* __restrict__ m, float tol,
-                                                      float* __restrict__ acc, int nenv) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int e = t >> 4, u = t & 15;
-  const bool sample = e < nenv && track[(size_t)(e < nenv ? e : 0) * ODK_TRACK_NACC + ODK_TRACK_ENDED] == 0.0f && done[e < nenv ? e : 0] == 0.0f;
-  const bool act = sample && u < nu;
-  const float* P = priv + (size_t)(sample ? e : 0) * npriv;   // row 0 for the rows that only take part in the row sums
-  const float* C = cmd + (size_t)(sample ? e : 0) * cmd_stride;
-  float* A = acc + (size_t)(sample ? e : 0) * ODK_POSTURE_NACC;
-  const float* Q = P + nobs;
-  // per actuator (0 in the lanes past nu and in the rows that are no sample)
-  const int k = act ? hslot[u] : -1;
-  const bool head = k >= 0, leg = act && k < 0;
-  const float dq = act ? Q[15 + u] : 0.0f, v = act ? Q[15 + nu + u] : 0.0f;
-  const float angle = head ? dq + m->key_ctrl[u] : 0.0f;
-  const float err = head ? angle - C[3 + k] : 0.0f, aerr = fabsf(err), sq = err * err;
-  const float leg_pose = row_sum16(leg ? fabsf(dq) : 0.0f), leg_vel = row_sum16(leg ? fabsf(v) : 0.0f), head_sq = row_sum16(sq);
-  if (!sample) return;
-  // per env (the same in the row's 16 lanes)
-  const float n0 = A[ODK_POSTURE_SAMPLES];
-  const float drift = planar32(Q[9], Q[10]), tilt = planar32(Q[6], Q[7]);
-  const float yaw = Q[2] * Q[2], wob = Q[0] * Q[0] + Q[1] * Q[1], h = Q[15 + 2 * nu];
-  if (u < 10) {   // scalar slot u: what it gains, or (the peak) what it becomes
-    const float old = A[u];
-    float inc = 0.0f;
-    inc = u == ODK_POSTURE_SAMPLES ? 1.0f : inc;
-    inc = u == ODK_POSTURE_DRIFT_SPEED_SUM ? drift : inc;
-    inc = u == ODK_POSTURE_YAW_RATE_SQ_SUM ? yaw : inc;
-    inc = u == ODK_POSTURE_ROLLPITCH_RATE_SQ_SUM ? wob : inc;
-    inc = u == ODK_POSTURE_TILT_SUM ? tilt : inc;
-    inc = u == ODK_POSTURE_HEIGHT_SUM ? h : inc;
-    inc = u == ODK_POSTURE_LEG_POSE_SUM ? leg_pose : inc;
-    inc = u == ODK_POSTURE_LEG_VEL_SUM ? leg_vel : inc;
-    inc = u == ODK_POSTURE_HEAD_SQERR_SUM ? head_sq : inc;
-    A[u] = u == ODK_POSTURE_TILT_PEAK ? fmaxf(old, tilt) : old + inc;
-  }
-  if (!head) return;
-  float* B = A + k;
-  B[ODK_POSTURE_ANGLE_SUM] += angle;
-  B[ODK_POSTURE_ERR_SQ_SUM] += sq;
-  B[ODK_POSTURE_ERR_PEAK] = fmaxf(B[ODK_POSTURE_ERR_PEAK], aerr);
-  if (aerr > tol) B[ODK_POSTURE_LAST_OFF] = n0 + 1.0f;   // this sample's 1-based index
-}
-
-extern "C" int odk_posture_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
-                                      const float* track_acc_dev, float tol, float* acc_dev, void* stream) {
-  if (!b) return fail(ODK_ERR_INVALID, "odk_posture_accumulate: null batch");
-  if (!priv_dev) return fail(ODK_ERR_INVALID, "odk_posture_accumulate: null priv_dev");
-  if (!done_dev) return fail(ODK_ERR_INVALID, "odk_posture_accumulate: null done_dev");
-  if (!truncation_dev) return fail(ODK_ERR_INVALID, "odk_posture_accumulate: null truncation_dev");
-  if (!track_acc_dev) return fail(ODK_ERR_INVALID, "odk_posture_accumulate: null track_acc_dev");
-  if (!acc_dev) return fail(ODK_ERR_INVALID, "odk_posture_accumulate: null acc_dev");
-  if (!b->d_cmd) return fail(ODK_ERR_INVALID, "odk_posture_accumulate: no commands bound (odk_batch_bind_commands)");
-  if (!b->hmap_set)
-    return fail(ODK_ERR_INVALID, "odk_posture_accumulate: the batch has no head-joint map (odk_batch_set_head_joints; an all -1 map is a map)");
-  const int nu = b->model.h.nu;
-  if (nu > 16) return fail(ODK_ERR_INVALID, "odk_posture_accumulate: the model has %d actuators, a row holds 16", nu);
-  if (!std::isfinite(tol) || tol < 0.0f) return fail(ODK_ERR_INVALID, "odk_posture_accumulate: tol = %g (a finite tolerance >= 0, in radians)", (double)tol);
-  int nobs, npriv;
-  obs_sizes_nu(nu, b->cfg.env_kind, &nobs, &npriv);
-  HIPCHK(hipSetDevice(b->device));
-  const long long threads = (long long)b->nenv * 16;
-  hipLaunchKernelGGL(posture_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, priv_dev, npriv, nobs, nu, done_dev,
-                     track_acc_dev, b->d_cmd, b->cmd_stride, b->d_hslot, b->d_model, tol, acc_dev, b->nenv);
-  HIPCHK(hipGetLastError());
-  return ODK_OK;
-}
-
-// Imitation-fidelity sums of one evaluation step, issued between odk_step and odk_tracking_accumulate (the ENDED contract of push_kernel), in
-// gait_kernel's layout: one 16-lane DPP row per env, lane = actuator, four envs per wave.  Every actuator lane loads its frame joint through
-// the batch's imitation map (imap[u], -1: not compared) and its home pose; the two reward terms are row sums, the 32 scalar slots are held two
-// per lane (u and 16 + u) as gait's, and a compared lane owns entry u of the eight per-actuator arrays.  Inputs, offsets into the env's
-// privileged Joystick row (build_obs_table): command 6 | local linvel nobs + 9 | joint angle minus default nobs + 15 + u | joint_vel nobs + 15
-// + nu + u | contact nobs + 16 + 3 nu | the frame the reward read (O_REF) nobs + 26 + 3 nu.  Only a sample (first episode, not done) stores
-// anything, so every other row keeps its bits.
-__global__ void __launch_bounds__(256) imitation_kernel(const float* __restrict__ priv, int npriv, int nobs, int nu, const float* __restrict__ done,
-                                                        const float* __restrict__ track, const int* __restrict__ imap,
-                                                        const DevModel* __restrict__ m, int period, float* __restrict__ acc, int nenv) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int e = t >> 4, u = t & 15;
-  const bool sample = e < nenv && track[(size_t)(e < nenv ? e : 0) * ODK_TRACK_NACC + ODK_TRACK_ENDED] == 0.0f && done[e < nenv ? e : 0] == 0.0f;
-  const bool act = sample && u < nu;
-  const float* P = priv + (size_t)(sample ? e : 0) * npriv;   // row 0 for the rows that only take part in the row sums
-  float* A = acc + (size_t)(sample ? e : 0) * ODK_IMIT_NACC;
-  const float* Q = P + nobs;
-  const float* F = Q + 26 + 3 * nu;
-  // per actuator (0 in the lanes past nu, in the lanes the map leaves out and in the rows that are no sample)
-  const int ri = act ? imap[u] : -1;
-  const bool cmp = ri >= 0;
-  const float jq = cmp ? Q[15 + u] + m->key_ctrl[u] : 0.0f, rq = cmp ? F[ri] : 0.0f;
-  const float dp = jq - rq, dv = cmp ? Q[15 + nu + u] - F[16 + ri] : 0.0f;
-  const float sp = dp * dp, sv = dv * dv;
-  const float jpos = row_sum16(sp), jvel = row_sum16(sv);
-  if (!sample) return;
-  // per env (the same in the row's 16 lanes)
-  const bool first = A[ODK_IMIT_SAMPLES] == 0.0f;
-  const float gated = sqrtf(P[6] * P[6] + P[7] * P[7] + P[8] * P[8]) > 0.01f ? 1.0f : 0.0f;   // the reward's gate (step_kernel's cn)
-  const float sr = planar32(F[34], F[35]), ds = planar32(Q[9], Q[10]) - sr;
-  const float per = (float)period;
-  float c[2], r[2], both[2], ronly[2], fonly[2], rtd[2], td[2], lag[2], age[2];
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    const bool con = Q[16 + 3 * nu + k] != 0.0f, ref = F[32 + k] > 0.5f;
-    const bool rtouch = ref && !first && A[ODK_IMIT_PREV_REF + k] == 0.0f;
-    const float a0 = A[ODK_IMIT_REF_AGE + k];
-    const float a1 = rtouch ? 1.0f : (a0 > 0.0f ? a0 + 1.0f : 0.0f);   // the reference first: a touchdown in the same sample has lag 0
-    const bool touch = con && !first && A[ODK_IMIT_PREV_CONTACT + k] == 0.0f && a1 > 0.0f;
-    float l = a1 - 1.0f;
-    if (period > 0 && 2.0f * l > per) l -= per;                        // past half a period: early for the reference's next touchdown
-    c[k] = con ? 1.0f : 0.0f;
-    r[k] = ref ? 1.0f : 0.0f;
-    both[k] = (con && ref) ? 1.0f : 0.0f;
-    ronly[k] = (con && !ref) ? 1.0f : 0.0f;
-    fonly[k] = (!con && ref) ? 1.0f : 0.0f;
-    rtd[k] = rtouch ? 1.0f : 0.0f;
-    td[k] = touch ? 1.0f : 0.0f;
-    lag[k] = touch ? l : 0.0f;
-    age[k] = a1;
-  }
-  // scalar slot s: what it gains, or (bookkeeping) what it becomes
-  auto next = [&](int s, float old) {
-    float inc = 0.0f;
-    inc = s == ODK_IMIT_SAMPLES ? 1.0f : inc;
-    inc = s == ODK_IMIT_GATED ? gated : inc;
-    inc = s == ODK_IMIT_SPEED_ERR_SQ_SUM ? ds * ds : inc;
-    inc = s == ODK_IMIT_REF_SPEED_SUM ? sr : inc;
-    inc = s == ODK_IMIT_JOINT_POS_SQ_SUM ? jpos : inc;
-    inc = s == ODK_IMIT_JOINT_VEL_SQ_SUM ? jvel : inc;
-    inc = s == ODK_IMIT_BOTH ? both[0] : s == ODK_IMIT_BOTH + 1 ? both[1] : inc;
-    inc = s == ODK_IMIT_ROBOT_ONLY ? ronly[0] : s == ODK_IMIT_ROBOT_ONLY + 1 ? ronly[1] : inc;
-    inc = s == ODK_IMIT_REF_ONLY ? fonly[0] : s == ODK_IMIT_REF_ONLY + 1 ? fonly[1] : inc;
-    inc = s == ODK_IMIT_REF_TOUCHDOWNS ? rtd[0] : s == ODK_IMIT_REF_TOUCHDOWNS + 1 ? rtd[1] : inc;
-    inc = s == ODK_IMIT_TOUCHDOWNS ? td[0] : s == ODK_IMIT_TOUCHDOWNS + 1 ? td[1] : inc;
-    inc = s == ODK_IMIT_LAG_SUM ? lag[0] : s == ODK_IMIT_LAG_SUM + 1 ? lag[1] : inc;
-    inc = s == ODK_IMIT_LAG_ABS_SUM ? fabsf(lag[0]) : s == ODK_IMIT_LAG_ABS_SUM + 1 ? fabsf(lag[1]) : inc;
-    float nv = old + inc;
-    nv = s == ODK_IMIT_PREV_CONTACT ? c[0] : s == ODK_IMIT_PREV_CONTACT + 1 ? c[1] : nv;
-    nv = s == ODK_IMIT_PREV_REF ? r[0] : s == ODK_IMIT_PREV_REF + 1 ? r[1] : nv;
-    nv = s == ODK_IMIT_REF_AGE ? age[0] : s == ODK_IMIT_REF_AGE + 1 ? age[1] : nv;
-    return nv;
-  };
-  const float s0 = next(u, A[u]), s1 = next(16 + u, A[16 + u]);
-  A[u] = s0;
-  A[16 + u] = s1;
-  if (!cmp) return;
-  float* B = A + u;
-  B[ODK_IMIT_POS_ERR_SUM] += dp;
-  B[ODK_IMIT_POS_ERR_SQ] += sp;
-  B[ODK_IMIT_POS_ERR_PEAK] = fmaxf(B[ODK_IMIT_POS_ERR_PEAK], fabsf(dp));
-  B[ODK_IMIT_VEL_ERR_SQ] += sv;
-  B[ODK_IMIT_RANGE_MIN] = first ? jq : fminf(B[ODK_IMIT_RANGE_MIN], jq);   // a zeroed row is no minimum: the first sample starts the ranges
-  B[ODK_IMIT_RANGE_MAX] = first ? jq : fmaxf(B[ODK_IMIT_RANGE_MAX], jq);
-  B[ODK_IMIT_REF_RANGE_MIN] = first ? rq : fminf(B[ODK_IMIT_REF_RANGE_MIN], rq);
-  B[ODK_IMIT_REF_RANGE_MAX] = first ? rq : fmaxf(B[ODK_IMIT_REF_RANGE_MAX], rq);
-}
-
-extern "C" int odk_imitation_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
-                                        const float* track_acc_dev, int period_steps, float* acc_dev, void* stream) {
-  if (!b) return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: null batch");
-  if (!priv_dev) return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: null priv_dev");
-  if (!done_dev) return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: null done_dev");
-  if (!truncation_dev) return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: null truncation_dev");
-  if (!track_acc_dev) return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: null track_acc_dev");
-  if (!acc_dev) return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: null acc_dev");
-  if (b->cfg.env_kind != ODK_ENV_JOYSTICK)
-    return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: a Standing batch's privileged row has no reference-motion frame (env_kind = ODK_ENV_JOYSTICK only)");
-  if (!b->cfg.use_imitation)
-    return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: use_imitation = 0: the frame of the privileged row is all zeros, there is nothing to compare with");
-  if (!b->imap_set)
-    return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: the batch has no imitation joint map (odk_batch_set_imitation_joints)");
-  const int nu = b->model.h.nu;
-  if (nu > ODK_IMIT_STRIDE) return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: the model has %d actuators, a row holds %d", nu, ODK_IMIT_STRIDE);
-  if (period_steps < 0) return fail(ODK_ERR_INVALID, "odk_imitation_accumulate: period_steps = %d (the reference motion's nb_steps_in_period, or 0 for unfolded lags)", period_steps);
-  int nobs, npriv;
-  obs_sizes_nu(nu, b->cfg.env_kind, &nobs, &npriv);
-  HIPCHK(hipSetDevice(b->device));
-  const long long threads = (long long)b->nenv * 16;
-  hipLaunchKernelGGL(imitation_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, priv_dev, npriv, nobs, nu, done_dev,
-                     track_acc_dev, b->d_imap, b->d_model, period_steps, acc_dev, b->nenv);
-  HIPCHK(hipGetLastError());
-  return ODK_OK;
-}
-
-// Command schedules.  The segment of schedule row S ([nseg, ODK_SCHED_SEG_FLOATS]) in force at first-episode step t: the last one whose
-// start_step is <= t (segment 0 when none is: a table whose first start is not 0 is the caller's mistake, not an out-of-range index)
-__device__ __forceinline__ int sched_segment(const float* __restrict__ S, int nseg, float t) {
-  int k = 0;
-  for (int i = 1; i < nseg; i++) k = S[i * ODK_SCHED_SEG_FLOATS] <= t ? i : k;
-  return k;
-}
-__device__ __forceinline__ const float* sched_row(const float* __restrict__ sched, int nsched, int nseg, const int* __restrict__ sched_of_env, int e) {
-  const int s = min(max(sched_of_env[e], 0), nsched - 1);   // a map entry outside the table reads a valid row, never past it
-  return sched + (size_t)s * nseg * ODK_SCHED_SEG_FLOATS;
-}
-
-// The command of the step about to run (one thread per env), issued before odk_step: the tracking accumulator's STEPS slot is the clock.
-// An env past its first episode keeps the command of the step that ended it (STEPS - 1; STEPS >= 1 once ENDED is set).
-__global__ void __launch_bounds__(256) sched_apply_kernel(const float* __restrict__ sched, int nsched, int nseg, const int* __restrict__ sched_of_env,
-                                                          const float* __restrict__ track, float* __restrict__ cmd, int cmd_stride, int nenv) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= nenv) return;
-  const float* T = track + (size_t)e * ODK_TRACK_NACC;
-  const float t = T[ODK_TRACK_ENDED] != 0.0f ? T[ODK_TRACK_STEPS] - 1.0f : T[ODK_TRACK_STEPS];
-  const float* S = sched_row(sched, nsched, nseg, sched_of_env, e);
-  const float* G = S + sched_segment(S, nseg, t) * ODK_SCHED_SEG_FLOATS + 1;
-  float* C = cmd + (size_t)e * cmd_stride;
-#pragma unroll
-  for (int k = 0; k < 7; k++) C[k] = G[k];
-}
-
-static int sched_args_ok(const char* fn, const odk_batch* b, const float* sched_dev, int nsched, int nseg, const int32_t* sched_of_env_dev,
-                         const float* track_acc_dev) {
-  if (!b) return fail(ODK_ERR_INVALID, "%s: null batch", fn);
-  if (!sched_dev) return fail(ODK_ERR_INVALID, "%s: null sched_dev", fn);
-  if (!sched_of_env_dev) return fail(ODK_ERR_INVALID, "%s: null sched_of_env_dev", fn);
-  if (!track_acc_dev) return fail(ODK_ERR_INVALID, "%s: null track_acc_dev", fn);
-  if (!b->d_cmd) return fail(ODK_ERR_INVALID, "%s: no commands bound (odk_batch_bind_commands)", fn);
-  if (nseg < 1 || nseg > ODK_SCHED_MAX_SEGMENTS) return fail(ODK_ERR_INVALID, "%s: nseg = %d (a schedule has 1 .. %d segments)", fn, nseg, ODK_SCHED_MAX_SEGMENTS);
-  if (nsched < 1) return fail(ODK_ERR_INVALID, "%s: nsched = %d (at least one schedule)", fn, nsched);
-  return ODK_OK;
-}
-
-extern "C" int odk_command_schedule_apply(const odk_batch* b, const float* sched_dev, int nsched, int nseg, const int32_t* sched_of_env_dev,
-                                          const float* track_acc_dev, void* stream) {
-  if (int rc = sched_args_ok("odk_command_schedule_apply", b, sched_dev, nsched, nseg, sched_of_env_dev, track_acc_dev)) return rc;
-  HIPCHK(hipSetDevice(b->device));
-  // the bound buffer is the caller's own device memory, handed over read-only for the step kernels; this launch is the one writer
-  hipLaunchKernelGGL(sched_apply_kernel, dim3((b->nenv + 255) / 256), dim3(256), 0, (hipStream_t)stream, sched_dev, nsched, nseg, sched_of_env_dev,
-                     track_acc_dev, const_cast<float*>(b->d_cmd), b->cmd_stride, b->nenv);
-  HIPCHK(hipGetLastError());
-  return ODK_OK;
-}
-
-// Step-response state of one evaluation step (one thread per env), issued between odk_step and odk_tracking_accumulate (the ENDED / STEPS
-// contract of push_kernel): only the block of the segment in force at the step that just ran is touched.  Velocities and errors as
-// push_kernel's.  Contraction is off: every product is rounded before it is added, so a float32 host restatement has the sums' bits.
-__global__ void __launch_bounds__(256) response_kernel(const float* __restrict__ priv, int npriv, int nobs, const float* __restrict__ done,
-                                                       const float* __restrict__ trunc, const float* __restrict__ cmd, int cmd_stride,
-                                                       const float* __restrict__ track, const float* __restrict__ sched, int nsched, int nseg,
-                                                       const int* __restrict__ sched_of_env, float lin_tol, float ang_tol, float tail_after,
-                                                       float* __restrict__ acc, int nenv) {
-#pragma clang fp contract(off)
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= nenv) return;
-  const float* T = track + (size_t)e * ODK_TRACK_NACC;
-  if (T[ODK_TRACK_ENDED] != 0.0f) return;       // past its first episode
-  const float t = T[ODK_TRACK_STEPS];           // first-episode steps before the one that just ran: its index
-  const float* S = sched_row(sched, nsched, nseg, sched_of_env, e);
-  const int seg = sched_segment(S, nseg, t);
-  const float* G = S + seg * ODK_SCHED_SEG_FLOATS;
-  float* A = acc + (size_t)e * ODK_RESP_NACC + seg * ODK_RESP_STRIDE;
-  const float k = t - G[0] + 1.0f;              // 1-based index of this step among the steps of its segment
-  A[ODK_RESP_ENTERED] = 1.0f;
-  if (done[e] != 0.0f) {   // ends the first episode; no velocity sample (the observation is the auto-reset's)
-    if (trunc[e] == 0.0f) { A[ODK_RESP_FELL] = 1.0f; A[ODK_RESP_STEPS_TO_FALL] = k; }
-    return;
-  }
-  const float* P = priv + (size_t)e * npriv;
-  const float* C = cmd + (size_t)e * cmd_stride;
-  const float v[3] = {P[nobs + 9], P[nobs + 10], P[nobs + 2]};
-  const float ex = v[0] - C[0], ey = v[1] - C[1];
-  const float lin = (float)sqrt((double)ex * (double)ex + (double)ey * (double)ey), ang = fabsf(v[2] - C[2]);   // push_kernel's
-  A[ODK_RESP_SAMPLES] += 1.0f;
-  float first_in = A[ODK_RESP_FIRST_IN];
-  if (lin > lin_tol || ang > ang_tol) A[ODK_RESP_LAST_OFF] = k;
-  else if (first_in == 0.0f) A[ODK_RESP_FIRST_IN] = first_in = k;
-  if (first_in != 0.0f) {
-    A[ODK_RESP_PEAK_LIN_ERR] = fmaxf(A[ODK_RESP_PEAK_LIN_ERR], lin);
-    A[ODK_RESP_PEAK_ANG_ERR] = fmaxf(A[ODK_RESP_PEAK_ANG_ERR], ang);
-  }
-  const bool tail = k > tail_after;
-  if (tail) A[ODK_RESP_TAIL_SAMPLES] += 1.0f;
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    const float err = v[a] - C[a];
-    const float sq = err * err;
-    A[ODK_RESP_SUM + a] += v[a];
-    A[ODK_RESP_SQERR + a] += sq;
-    const float prev = seg > 0 ? S[(seg > 0 ? seg - 1 : 0) * ODK_SCHED_SEG_FLOATS + 1 + a] : 0.0f;   // segment 0: the episode starts at rest
-    const float dir = C[a] > prev ? 1.0f : (C[a] < prev ? -1.0f : 0.0f);
-    const float over = err * dir;
-    if (over > A[ODK_RESP_OVERSHOOT + a]) A[ODK_RESP_OVERSHOOT + a] = over;   // (a strict compare: a -0 product never replaces the zeroed slot's +0)
-    if (tail) A[ODK_RESP_TAIL_SUM + a] += v[a];
-  }
-}
-
-extern "C" int odk_response_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
-                                       const float* track_acc_dev, const float* sched_dev, int nsched, int nseg, const int32_t* sched_of_env_dev,
-                                       float lin_tol, float ang_tol, int tail_after, float* acc_dev, void* stream) {
-  const char* fn = "odk_response_accumulate";
-  if (!b) return fail(ODK_ERR_INVALID, "%s: null batch", fn);
-  if (!priv_dev) return fail(ODK_ERR_INVALID, "%s: null priv_dev", fn);
-  if (!done_dev) return fail(ODK_ERR_INVALID, "%s: null done_dev", fn);
-  if (!truncation_dev) return fail(ODK_ERR_INVALID, "%s: null truncation_dev", fn);
-  if (!acc_dev) return fail(ODK_ERR_INVALID, "%s: null acc_dev", fn);
-  if (int rc = sched_args_ok(fn, b, sched_dev, nsched, nseg, sched_of_env_dev, track_acc_dev)) return rc;
-  if (!std::isfinite(lin_tol) || lin_tol < 0.0f) return fail(ODK_ERR_INVALID, "%s: lin_tol = %g (a finite tolerance >= 0, in m/s)", fn, (double)lin_tol);
-  if (!std::isfinite(ang_tol) || ang_tol < 0.0f) return fail(ODK_ERR_INVALID, "%s: ang_tol = %g (a finite tolerance >= 0, in rad/s)", fn, (double)ang_tol);
-  if (tail_after < 0) return fail(ODK_ERR_INVALID, "%s: tail_after = %d (a number of steps >= 0)", fn, tail_after);
-  int nobs, npriv;
-  obs_sizes_nu(b->model.h.nu, b->cfg.env_kind, &nobs, &npriv);
-  HIPCHK(hipSetDevice(b->device));
-  hipLaunchKernelGGL(response_kernel, dim3((b->nenv + 255) / 256), dim3(256), 0, (hipStream_t)stream, priv_dev, npriv, nobs, done_dev, truncation_dev,
-                     b->d_cmd, b->cmd_stride, track_acc_dev, sched_dev, nsched, nseg, sched_of_env_dev, lin_tol, ang_tol, (float)tail_after, acc_dev,
-                     b->nenv);
-  HIPCHK(hipGetLastError());
-  return ODK_OK;
-}
-
-// Fall recorder of one evaluation step, issued between odk_step and odk_tracking_accumulate (the ENDED / STEPS contract of push_kernel), in
-// gait_kernel's layout: one 16-lane DPP row per env, four envs per wave.  For the saturation count lane = actuator (a row sum of 0 / 1 flags:
-// exact); for the stores lane = float: the 16 scalars of the ring slot are one contiguous 64-byte store of the row, the qpos copy from the
-// batch's record (offset 0 of the env's row of d_recs) is ceil(nq / 16) passes of consecutive lanes on consecutive floats, and the head's
-// slots are written by the lane of their number.  Only the slot of this sample and the head are stored to, and only during the first episode:
-// every other float keeps its bits.  Contraction is off and both hypots go through float64, so a host restatement has the row's bits.
-__global__ void __launch_bounds__(256) fall_kernel(const float* __restrict__ priv, int npriv, int nobs, int nu, const float* __restrict__ done,
-                                                   const float* __restrict__ trunc, const float* __restrict__ track, const float* __restrict__ cmd,
-                                                   int cmd_stride, const float* __restrict__ limit, const float* __restrict__ recs, int rec_size,
-                                                   int nq, float tilt_tol, int ring, float* __restrict__ acc, int row_stride, int nenv) {
-#pragma clang fp contract(off)
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int e = t >> 4, u = t & 15;
-  const int e0 = e < nenv ? e : 0;
-  const float* T = track + (size_t)e0 * ODK_TRACK_NACC;
-  const bool live = e < nenv && T[ODK_TRACK_ENDED] == 0.0f;       // the first episode was running when this step began
-  const bool sample = live && done[e0] == 0.0f;
-  const bool act = sample && u < nu;
-  const float* Q = priv + (size_t)(sample ? e : 0) * npriv + nobs;   // row 0 for the rows that only take part in the row sum
-  const float f = act ? Q[16 + 2 * nu + u] : 0.0f;
-  const float lim = (act && limit) ? limit[u] : 0.0f;
-  const float sat = row_sum16((lim > 0.0f && fabsf(f) >= 0.99f * lim) ? 1.0f : 0.0f);
-  if (!live) return;
-  float* A = acc + (size_t)e * row_stride;
-  const float step = T[ODK_TRACK_STEPS];                          // first-episode steps before the one that just ran: its index
-  if (!sample) {   // ends the first episode; no sample (the observation and the state are the auto-reset's)
-    if (trunc[e] == 0.0f && (u == ODK_FALL_FELL || u == ODK_FALL_STEP)) A[u] = u == ODK_FALL_FELL ? 1.0f : step;
-    return;
-  }
-  // per env (the same in the row's 16 lanes)
-  const float n0 = A[ODK_FALL_SAMPLES];
-  const float* C = cmd + (size_t)e * cmd_stride;
-  const float lin = planar32(Q[9] - C[0], Q[10] - C[1]), ang = fabsf(Q[2] - C[2]);   // push_kernel's
-  const float tilt = planar32(Q[6], Q[7]);                                            // posture_kernel's
-  const bool upright = tilt <= tilt_tol;
-  const float con[2] = {Q[16 + 3 * nu], Q[17 + 3 * nu]};
-  // lane u's scalar of the slot: a copy of the privileged row at `off`, or one of the four computed ones
-  int off = u + 5;                                                // S_UP: nobs + 6 ..
-  off = u >= ODK_FALL_S_GYRO ? u - ODK_FALL_S_GYRO : off;
-  off = u >= ODK_FALL_S_LINVEL ? u + 2 : off;                     // nobs + 9 ..
-  off = u == ODK_FALL_S_HEIGHT ? 15 + 2 * nu : off;
-  off = u >= ODK_FALL_S_CONTACT ? 16 + 3 * nu + (u - ODK_FALL_S_CONTACT) : off;
-  off = (u == ODK_FALL_S_STEP || u >= ODK_FALL_S_LIN_ERR) ? 0 : off;
-  float v = Q[off];
-  v = u == ODK_FALL_S_STEP ? step : v;
-  v = u == ODK_FALL_S_LIN_ERR ? lin : v;
-  v = u == ODK_FALL_S_ANG_ERR ? ang : v;
-  v = u == ODK_FALL_S_SAT ? sat : v;
-  const unsigned slot = (unsigned)(int)n0 % (unsigned)ring;       // (unsigned: a row the caller did not zero still lands inside its ring)
-  float* S = A + ODK_FALL_HEAD + (size_t)slot * (ODK_FALL_SAMPLE + nq);
-  S[u] = v;
-  const float* R = recs + (size_t)e * rec_size;
-  for (int j = u; j < nq; j += 16) S[ODK_FALL_SAMPLE + j] = R[j];
-  // the head: lane = slot
-  if (u == ODK_FALL_SAMPLES) A[u] = n0 + 1.0f;
-  if (u == ODK_FALL_LAST_UPRIGHT && upright) A[u] = n0 + 1.0f;   // this sample's 1-based number
-  if ((u == ODK_FALL_UPRIGHT_CONTACT || u == ODK_FALL_UPRIGHT_CONTACT + 1) && upright) A[u] = con[u - ODK_FALL_UPRIGHT_CONTACT];
-  if (u == ODK_FALL_TILT_PEAK) A[u] = fmaxf(A[u], tilt);
-}
-
-extern "C" int odk_fall_row_floats(const odk_batch* b, int ring) {
-  if (!b || ring < 1 || ring > ODK_FALL_MAX_RING) return -1;
-  return ODK_FALL_HEAD + ring * (ODK_FALL_SAMPLE + b->model.h.nq);
-}
-
-extern "C" int odk_fall_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
-                                   const float* track_acc_dev, const float* torque_limit_dev, float tilt_tol, int ring, float* acc_dev,
-                                   int row_stride, void* stream) {
-  const char* fn = "odk_fall_accumulate";
-  if (!b) return fail(ODK_ERR_INVALID, "%s: null batch", fn);
-  if (!priv_dev) return fail(ODK_ERR_INVALID, "%s: null priv_dev", fn);
-  if (!done_dev) return fail(ODK_ERR_INVALID, "%s: null done_dev", fn);
-  if (!truncation_dev) return fail(ODK_ERR_INVALID, "%s: null truncation_dev", fn);
-  if (!track_acc_dev) return fail(ODK_ERR_INVALID, "%s: null track_acc_dev", fn);
-  if (!acc_dev) return fail(ODK_ERR_INVALID, "%s: null acc_dev", fn);
-  if (!b->d_cmd) return fail(ODK_ERR_INVALID, "%s: no commands bound (odk_batch_bind_commands)", fn);
-  if (ring < 1 || ring > ODK_FALL_MAX_RING) return fail(ODK_ERR_INVALID, "%s: ring = %d (1 .. %d samples)", fn, ring, ODK_FALL_MAX_RING);
-  const int nu = b->model.h.nu, nq = b->model.h.nq, need = odk_fall_row_floats(b, ring);
-  if (row_stride < need) return fail(ODK_ERR_INVALID, "%s: row_stride = %d, a row of ring %d holds %d floats (odk_fall_row_floats)", fn, row_stride, ring, need);
-  if (nu > 16) return fail(ODK_ERR_INVALID, "%s: the model has %d actuators, a row holds 16", fn, nu);
-  if (!std::isfinite(tilt_tol) || tilt_tol < 0.0f)
-    return fail(ODK_ERR_INVALID, "%s: tilt_tol = %g (a finite sine of the lean >= 0)", fn, (double)tilt_tol);
-  int nobs, npriv;
-  obs_sizes_nu(nu, b->cfg.env_kind, &nobs, &npriv);
-  HIPCHK(hipSetDevice(b->device));
-  const long long threads = (long long)b->nenv * 16;
-  hipLaunchKernelGGL(fall_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, priv_dev, npriv, nobs, nu, done_dev,
-                     truncation_dev, track_acc_dev, b->d_cmd, b->cmd_stride, torque_limit_dev, b->d_recs, b->rec_size, nq, tilt_tol, ring, acc_dev,
-                     row_stride, b->nenv);
-  HIPCHK(hipGetLastError());
   return ODK_OK;
 }
 

@@ -20,6 +20,7 @@
 
 #define ODK_HOST_ONLY   // odk_kernels.h: shapes and compute_statics, no device table
 #include "odk_host.h"
+#include "odk_obs_layout.h"
 #include "odk_shapes.h"
 
 using namespace odk;
@@ -443,7 +444,10 @@ template <class S> static void build_obs_table(DevModel& m) {
   constexpr int NU = S::NU;
   constexpr RecLay RL = rec_lay(NU);
   constexpr int NOBS = obs_nobs(NU, false);
+  namespace PA = priv_at;   // the privileged tail's boundaries: odk_obs_layout.h, which the report kernels read the rows by
   static_assert(obs_npriv(NU, false) <= OBS_MAX && draw_count(NU) < 255 && 3 + NU <= 32, "ObsEnt");
+  static_assert(obs_npriv(NU, true) == obs_nobs(NU, true) + PA::ref_frame(NU) && obs_npriv(NU, false) == NOBS + PA::imitation_counter(NU) + 3 &&
+                obs_at::last_act(NU) + 4 * NU + 4 == NOBS, "odk_obs_layout.h");
   const int MISC = S::O_SCR + S::S_MISC, INFO = E::O_INFO, SENS = S::O_SENS;
   for (int kind = 0; kind < 2; kind++) {
     const bool standing = kind != 0;
@@ -470,21 +474,21 @@ template <class S> static void build_obs_table(DevModel& m) {
         else if (k < 13 + 6 * NU) e.a = INFO + RL.MT + k - 13 - 5 * NU;
         else if (k < 15 + 6 * NU) e.a = MISC + OBS_PARK_CON + k - 13 - 6 * NU;
         else if (k < 17 + 6 * NU) e.a = MISC + OBS_PARK_PHASE + k - 15 - 6 * NU;
-        else if (q < 3) e.a = SENS + m.adr_gyro + q;
-        else if (q < 6) e.a = SENS + m.adr_accelerometer + q - 3;
-        else if (q < 9) e.a = MISC + 10 + q - 6;
-        else if (q < 12) e.a = SENS + m.adr_local_linvel + q - 9;
-        else if (q < 15) e.a = SENS + m.adr_global_angvel + q - 12;
-        else if (q < 15 + NU) joint(q - 15);
-        else if (q < 15 + 2 * NU) e.a = S::O_QVEL + m.act_dofadr[q - 15 - NU];
-        else if (q == 15 + 2 * NU) e.a = S::O_QPOS + 2;
-        else if (q < 16 + 3 * NU) e.a = S::O_ACTF + q - 16 - 2 * NU;
-        else if (q < 18 + 3 * NU) e.a = MISC + OBS_PARK_CON + q - 16 - 3 * NU;
-        else if (q < 24 + 3 * NU) { const int t = q - 18 - 3 * NU; e.a = SENS + m.adr_foot_linvel[t >= 3 ? 1 : 0] + (t >= 3 ? t - 3 : t); }
-        else if (q < 26 + 3 * NU) e.a = INFO + RL.AIR + q - 24 - 3 * NU;
-        else if (q < 66 + 3 * NU) e.a = E::O_REF + q - 26 - 3 * NU;
-        else if (q == 66 + 3 * NU) e.a = MISC + OBS_PARK_IMI;
-        else e.a = MISC + OBS_PARK_PHASE + q - 67 - 3 * NU;
+        else if (q < PA::ACCELEROMETER) e.a = SENS + m.adr_gyro + q - PA::GYRO;
+        else if (q < PA::GRAVITY) e.a = SENS + m.adr_accelerometer + q - PA::ACCELEROMETER;
+        else if (q < PA::LOCAL_LINVEL) e.a = MISC + 10 + q - PA::GRAVITY;
+        else if (q < PA::GLOBAL_ANGVEL) e.a = SENS + m.adr_local_linvel + q - PA::LOCAL_LINVEL;
+        else if (q < PA::JOINT_POS) e.a = SENS + m.adr_global_angvel + q - PA::GLOBAL_ANGVEL;
+        else if (q < PA::joint_vel(NU)) joint(q - PA::JOINT_POS);
+        else if (q < PA::root_height(NU)) e.a = S::O_QVEL + m.act_dofadr[q - PA::joint_vel(NU)];
+        else if (q < PA::actuator_force(NU)) e.a = S::O_QPOS + 2;
+        else if (q < PA::contact(NU)) e.a = S::O_ACTF + q - PA::actuator_force(NU);
+        else if (q < PA::feet_linvel(NU)) e.a = MISC + OBS_PARK_CON + q - PA::contact(NU);
+        else if (q < PA::air_time(NU)) { const int t = q - PA::feet_linvel(NU); e.a = SENS + m.adr_foot_linvel[t >= 3 ? 1 : 0] + (t >= 3 ? t - 3 : t); }
+        else if (q < PA::ref_frame(NU)) e.a = INFO + RL.AIR + q - PA::air_time(NU);
+        else if (q < PA::imitation_counter(NU)) e.a = E::O_REF + q - PA::ref_frame(NU);
+        else if (q == PA::imitation_counter(NU)) e.a = MISC + OBS_PARK_IMI;
+        else e.a = MISC + OBS_PARK_PHASE + q - PA::imitation_counter(NU) - 1;
       }
       m.obs_tab[kind][ks] = e;
     }

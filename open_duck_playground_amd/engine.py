@@ -246,6 +246,16 @@ TRACK_ENDED, TRACK_STEPS, TRACK_SAMPLES, TRACK_FALLS, TRACK_REWARD, TRACK_SUM, T
 NCOMMAND = 7    # lin_vel_x, lin_vel_y, ang_vel_yaw, neck_pitch, head_pitch, head_yaw, head_roll
 
 
+def _check_placement(name: str, t, dtype, device: int) -> None:
+    """What every tensor argument's check ends with: the dtype, contiguous, on cuda:`device`."""
+    if t.dtype != dtype:
+        raise OdkError(f"{name}: dtype must be {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise OdkError(f"{name}: the tensor must be contiguous")
+    if t.device.type != "cuda" or t.device.index != int(device):
+        raise OdkError(f"{name}: the tensor must live on cuda:{device} (the env's device), got {t.device}")
+
+
 def check_commands(cmd, nenv: int, device: int) -> None:
     """What `Batch.bind_commands` accepts: a contiguous float32 [nenv, 7] tensor on cuda:`device`; raises OdkError otherwise."""
     import torch
@@ -253,12 +263,7 @@ def check_commands(cmd, nenv: int, device: int) -> None:
         raise OdkError(f"commands: expected a torch tensor or None, got {type(cmd).__name__}")
     if tuple(cmd.shape) != (int(nenv), NCOMMAND):
         raise OdkError(f"commands: shape must be ({nenv}, {NCOMMAND}), got {tuple(cmd.shape)}")
-    if cmd.dtype != torch.float32:
-        raise OdkError(f"commands: dtype must be torch.float32, got {cmd.dtype}")
-    if not cmd.is_contiguous():
-        raise OdkError("commands: the tensor must be contiguous")
-    if cmd.device.type != "cuda" or cmd.device.index != int(device):
-        raise OdkError(f"commands: the tensor must live on cuda:{device} (the env's device), got {cmd.device}")
+    _check_placement("commands", cmd, torch.float32, device)
 
 
 # odk_push_accumulate's per-env slots (include/odk.h ODK_PUSH_*)
@@ -319,12 +324,7 @@ def check_pushes(push, nenv: int, device: int) -> None:
         raise OdkError(f"pushes: expected a torch tensor or None, got {type(push).__name__}")
     if push.dim() != 2 or int(push.shape[0]) != int(nenv) or int(push.shape[1]) < 2:
         raise OdkError(f"pushes: shape must be ({nenv}, >= 2), got {tuple(push.shape)}")
-    if push.dtype != torch.float32:
-        raise OdkError(f"pushes: dtype must be torch.float32, got {push.dtype}")
-    if not push.is_contiguous():
-        raise OdkError("pushes: the tensor must be contiguous")
-    if push.device.type != "cuda" or push.device.index != int(device):
-        raise OdkError(f"pushes: the tensor must live on cuda:{device} (the env's device), got {push.device}")
+    _check_placement("pushes", push, torch.float32, device)
 
 
 ACTION_DELAY_ROWS = 3      # the action-history ring: delay 0 (the action just given), 1, 2; a negative device row means "sample"
@@ -348,18 +348,35 @@ def check_action_delays(delays, nenv: int, device: int) -> None:
 
 
 def check_accumulator(name: str, acc, nenv: int, ncol: int, device: int) -> None:
-    """An accumulator argument of `Batch.push_accumulate` / `Batch.gait_accumulate` / `Batch.posture_accumulate` / `Batch.imitation_accumulate` / `Batch.response_accumulate` / `Batch.fall_accumulate`: a contiguous float32 [nenv, ncol] tensor on cuda:`device`; OdkError otherwise."""
+    """An accumulator argument of one of `Batch`'s `*_accumulate` methods: a contiguous float32 [nenv, ncol] tensor on cuda:`device`; OdkError
+    otherwise."""
     import torch
     if not torch.is_tensor(acc):
         raise OdkError(f"{name}: expected a torch tensor, got {type(acc).__name__}")
     if tuple(acc.shape) != (int(nenv), int(ncol)):
         raise OdkError(f"{name}: shape must be ({nenv}, {ncol}), got {tuple(acc.shape)}")
-    if acc.dtype != torch.float32:
-        raise OdkError(f"{name}: dtype must be torch.float32, got {acc.dtype}")
-    if not acc.is_contiguous():
-        raise OdkError(f"{name}: the tensor must be contiguous")
-    if acc.device.type != "cuda" or acc.device.index != int(device):
-        raise OdkError(f"{name}: the tensor must live on cuda:{device} (the env's device), got {acc.device}")
+    _check_placement(name, acc, torch.float32, device)
+
+
+def _check_report(batch, name: str, acc, ncol: int, track_acc) -> None:
+    """A report's `acc` ([nenv, ncol]) and `track_acc`, as every `Batch.*_accumulate` checks them first."""
+    check_accumulator(f"{name}: acc", acc, batch.nenv, ncol, batch.device)
+    check_accumulator(f"{name}: track_acc", track_acc, batch.nenv, TRACK_NACC, batch.device)
+
+
+def _report_ptrs(batch, track_acc):
+    """What every odk_*_accumulate starts with behind the batch: priv, done, truncation, track_acc."""
+    return tuple(C.c_void_p(t.data_ptr()) for t in (batch.priv, batch.done, batch.truncation, track_acc))
+
+
+def _check_torque_limit(batch, name: str, t):
+    """`torque_limit` of `gait_accumulate` / `fall_accumulate`: None or float32 [nu] on the batch's device; returns the pointer argument."""
+    if t is None:
+        return None
+    if not hasattr(t, "dim") or t.dim() != 1:
+        raise OdkError(f"{name}: torque_limit: expected a 1-D torch tensor or None, got {type(t).__name__}")
+    check_accumulator(f"{name}: torque_limit", t.unsqueeze(0), 1, batch.model.nu, batch.device)      # as one row of [1, nu]
+    return C.c_void_p(t.data_ptr())
 
 
 def check_schedule(name: str, sched, sched_of_env, nenv: int, device: int):
@@ -372,22 +389,12 @@ def check_schedule(name: str, sched, sched_of_env, nenv: int, device: int):
         raise OdkError(f"{name}: sched: expected a torch tensor, got {type(sched).__name__}")
     if sched.dim() != 3 or int(sched.shape[0]) < 1 or not 1 <= int(sched.shape[1]) <= SCHED_MAX_SEGMENTS or int(sched.shape[2]) != SCHED_SEG_FLOATS:
         raise OdkError(f"{name}: sched: shape must be (nsched >= 1, 1 .. {SCHED_MAX_SEGMENTS}, {SCHED_SEG_FLOATS}), got {tuple(sched.shape)}")
-    if sched.dtype != torch.float32:
-        raise OdkError(f"{name}: sched: dtype must be torch.float32, got {sched.dtype}")
-    if not sched.is_contiguous():
-        raise OdkError(f"{name}: sched: the tensor must be contiguous")
-    if sched.device.type != "cuda" or sched.device.index != int(device):
-        raise OdkError(f"{name}: sched: the tensor must live on cuda:{device} (the env's device), got {sched.device}")
+    _check_placement(f"{name}: sched", sched, torch.float32, device)
     if not torch.is_tensor(sched_of_env):
         raise OdkError(f"{name}: sched_of_env: expected a torch tensor, got {type(sched_of_env).__name__}")
     if tuple(sched_of_env.shape) != (int(nenv),):
         raise OdkError(f"{name}: sched_of_env: shape must be ({nenv},), got {tuple(sched_of_env.shape)}")
-    if sched_of_env.dtype != torch.int32:
-        raise OdkError(f"{name}: sched_of_env: dtype must be torch.int32, got {sched_of_env.dtype}")
-    if not sched_of_env.is_contiguous():
-        raise OdkError(f"{name}: sched_of_env: the tensor must be contiguous")
-    if sched_of_env.device.type != "cuda" or sched_of_env.device.index != int(device):
-        raise OdkError(f"{name}: sched_of_env: the tensor must live on cuda:{device} (the env's device), got {sched_of_env.device}")
+    _check_placement(f"{name}: sched_of_env", sched_of_env, torch.int32, device)
     return int(sched.shape[0]), int(sched.shape[1])
 
 
@@ -1118,55 +1125,39 @@ class Batch:
     def push_accumulate(self, acc, track_acc, lin_tol: float, ang_tol: float):
         """One `odk_push_accumulate` launch over this step's outputs into `acc` ([nenv, PUSH_NACC] float32, zeroed before the first
         step), issued after `step` and BEFORE `tracking_accumulate(track_acc)`; needs bound commands and bound pushes."""
-        check_accumulator("push_accumulate: acc", acc, self.nenv, PUSH_NACC, self.device)
-        check_accumulator("push_accumulate: track_acc", track_acc, self.nenv, TRACK_NACC, self.device)
+        _check_report(self, "push_accumulate", acc, PUSH_NACC, track_acc)
         if self.commands is None:
             raise OdkError("push_accumulate: no commands bound (bind_commands)")
         if self.pushes is None:
             raise OdkError("push_accumulate: no pushes bound (bind_pushes)")
-        _chk(self.L.odk_push_accumulate(self._b, C.c_void_p(self.priv.data_ptr()), C.c_void_p(self.done.data_ptr()),
-                                        C.c_void_p(self.truncation.data_ptr()), C.c_void_p(track_acc.data_ptr()), float(lin_tol), float(ang_tol),
-                                        C.c_void_p(acc.data_ptr()), self._stream()))
+        _chk(self.L.odk_push_accumulate(self._b, *_report_ptrs(self, track_acc), float(lin_tol), float(ang_tol), C.c_void_p(acc.data_ptr()), self._stream()))
 
     def gait_accumulate(self, acc, track_acc, torque_limit=None):
         """One `odk_gait_accumulate` launch over this step's outputs into `acc` ([nenv, GAIT_NACC] float32, zeroed before the first step),
         issued after `step` and BEFORE `tracking_accumulate(track_acc)`.  `torque_limit`: float32 [nu] on the batch's device (an entry <= 0:
         that actuator never counts as saturated) or None (nobody does).  Needs neither bound commands nor bound pushes."""
-        check_accumulator("gait_accumulate: acc", acc, self.nenv, GAIT_NACC, self.device)
-        check_accumulator("gait_accumulate: track_acc", track_acc, self.nenv, TRACK_NACC, self.device)
-        if torque_limit is not None:
-            if not hasattr(torque_limit, "dim") or torque_limit.dim() != 1:
-                raise OdkError(f"gait_accumulate: torque_limit: expected a 1-D torch tensor or None, got {type(torque_limit).__name__}")
-            check_accumulator("gait_accumulate: torque_limit", torque_limit.unsqueeze(0), 1, self.model.nu, self.device)      # as one row of [1, nu]
-        _chk(self.L.odk_gait_accumulate(self._b, C.c_void_p(self.priv.data_ptr()), C.c_void_p(self.done.data_ptr()),
-                                        C.c_void_p(self.truncation.data_ptr()), C.c_void_p(track_acc.data_ptr()),
-                                        C.c_void_p(torque_limit.data_ptr()) if torque_limit is not None else None,
-                                        C.c_void_p(acc.data_ptr()), self._stream()))
+        _check_report(self, "gait_accumulate", acc, GAIT_NACC, track_acc)
+        limit = _check_torque_limit(self, "gait_accumulate", torque_limit)
+        _chk(self.L.odk_gait_accumulate(self._b, *_report_ptrs(self, track_acc), limit, C.c_void_p(acc.data_ptr()), self._stream()))
 
     def posture_accumulate(self, acc, track_acc, tol: float):
         """One `odk_posture_accumulate` launch over this step's outputs into `acc` ([nenv, POSTURE_NACC] float32, zeroed before the first
         step), issued after `step` and BEFORE `tracking_accumulate(track_acc)`.  `tol`: the head error in radians above which a sample counts
         as not settled (finite, >= 0).  Needs bound commands and a head-joint map (the duck has one; `set_head_joints` otherwise)."""
-        check_accumulator("posture_accumulate: acc", acc, self.nenv, POSTURE_NACC, self.device)
-        check_accumulator("posture_accumulate: track_acc", track_acc, self.nenv, TRACK_NACC, self.device)
+        _check_report(self, "posture_accumulate", acc, POSTURE_NACC, track_acc)
         if self.commands is None:
             raise OdkError("posture_accumulate: no commands bound (bind_commands)")
-        _chk(self.L.odk_posture_accumulate(self._b, C.c_void_p(self.priv.data_ptr()), C.c_void_p(self.done.data_ptr()),
-                                           C.c_void_p(self.truncation.data_ptr()), C.c_void_p(track_acc.data_ptr()), float(tol),
-                                           C.c_void_p(acc.data_ptr()), self._stream()))
+        _chk(self.L.odk_posture_accumulate(self._b, *_report_ptrs(self, track_acc), float(tol), C.c_void_p(acc.data_ptr()), self._stream()))
 
     def imitation_accumulate(self, acc, track_acc, period_steps: int):
         """One `odk_imitation_accumulate` launch over this step's outputs into `acc` ([nenv, IMIT_NACC] float32, zeroed before the first
         step), issued after `step` and BEFORE `tracking_accumulate(track_acc)`.  `period_steps`: the reference motion's nb_steps_in_period
         (touchdown lags past half of it count as early for the next cycle), or 0 for lags that are not folded.  A Joystick batch that runs
         the imitation reward with a joint map (the duck has one; `set_imitation_joints` otherwise); needs no bound commands."""
-        check_accumulator("imitation_accumulate: acc", acc, self.nenv, IMIT_NACC, self.device)
-        check_accumulator("imitation_accumulate: track_acc", track_acc, self.nenv, TRACK_NACC, self.device)
+        _check_report(self, "imitation_accumulate", acc, IMIT_NACC, track_acc)
         if int(period_steps) != period_steps:
             raise OdkError(f"imitation_accumulate: period_steps = {period_steps!r} (a whole number of steps)")
-        _chk(self.L.odk_imitation_accumulate(self._b, C.c_void_p(self.priv.data_ptr()), C.c_void_p(self.done.data_ptr()),
-                                             C.c_void_p(self.truncation.data_ptr()), C.c_void_p(track_acc.data_ptr()), int(period_steps),
-                                             C.c_void_p(acc.data_ptr()), self._stream()))
+        _chk(self.L.odk_imitation_accumulate(self._b, *_report_ptrs(self, track_acc), int(period_steps), C.c_void_p(acc.data_ptr()), self._stream()))
 
     def command_schedule_apply(self, sched, sched_of_env, track_acc):
         """One `odk_command_schedule_apply` launch, issued BEFORE `step`: env e's row of the bound command tensor becomes the command of the
@@ -1186,17 +1177,14 @@ class Batch:
         `command_schedule_apply` wrote this step's commands from.  `lin_tol` / `ang_tol`: the planar velocity error (m/s) and yaw-rate error
         (rad/s) up to which a sample counts as following the command (finite, >= 0); `tail_after`: the samples past this many steps of a
         segment are its steady state.  Needs bound commands."""
-        check_accumulator("response_accumulate: acc", acc, self.nenv, RESP_NACC, self.device)
-        check_accumulator("response_accumulate: track_acc", track_acc, self.nenv, TRACK_NACC, self.device)
+        _check_report(self, "response_accumulate", acc, RESP_NACC, track_acc)
         nsched, nseg = check_schedule("response_accumulate", sched, sched_of_env, self.nenv, self.device)
         if int(tail_after) != tail_after:
             raise OdkError(f"response_accumulate: tail_after = {tail_after!r} (a whole number of steps)")
         if self.commands is None:
             raise OdkError("response_accumulate: no commands bound (bind_commands)")
-        _chk(self.L.odk_response_accumulate(self._b, C.c_void_p(self.priv.data_ptr()), C.c_void_p(self.done.data_ptr()),
-                                            C.c_void_p(self.truncation.data_ptr()), C.c_void_p(track_acc.data_ptr()), C.c_void_p(sched.data_ptr()),
-                                            nsched, nseg, C.c_void_p(sched_of_env.data_ptr()), float(lin_tol), float(ang_tol), int(tail_after),
-                                            C.c_void_p(acc.data_ptr()), self._stream()))
+        _chk(self.L.odk_response_accumulate(self._b, *_report_ptrs(self, track_acc), C.c_void_p(sched.data_ptr()), nsched, nseg, C.c_void_p(sched_of_env.data_ptr()),
+                                            float(lin_tol), float(ang_tol), int(tail_after), C.c_void_p(acc.data_ptr()), self._stream()))
 
     def fall_row_floats(self, ring: int) -> int:
         """Floats of one env's row of the fall recorder with a ring of `ring` samples (`odk_fall_row_floats`): FALL_HEAD + ring * (FALL_SAMPLE +
@@ -1217,18 +1205,12 @@ class Batch:
         if not hasattr(acc, "dim") or acc.dim() != 2 or int(acc.shape[1]) < nfl:
             raise OdkError(f"fall_accumulate: acc: expected a torch tensor [{self.nenv}, >= {nfl}] (fall_row_floats({int(ring)})), got "
                            f"{tuple(acc.shape) if hasattr(acc, 'shape') else type(acc).__name__}")
-        check_accumulator("fall_accumulate: acc", acc, self.nenv, int(acc.shape[1]), self.device)
-        check_accumulator("fall_accumulate: track_acc", track_acc, self.nenv, TRACK_NACC, self.device)
-        if torque_limit is not None:
-            if not hasattr(torque_limit, "dim") or torque_limit.dim() != 1:
-                raise OdkError(f"fall_accumulate: torque_limit: expected a 1-D torch tensor or None, got {type(torque_limit).__name__}")
-            check_accumulator("fall_accumulate: torque_limit", torque_limit.unsqueeze(0), 1, self.model.nu, self.device)      # as one row of [1, nu]
+        _check_report(self, "fall_accumulate", acc, int(acc.shape[1]), track_acc)
+        limit = _check_torque_limit(self, "fall_accumulate", torque_limit)
         if self.commands is None:
             raise OdkError("fall_accumulate: no commands bound (bind_commands)")
-        _chk(self.L.odk_fall_accumulate(self._b, C.c_void_p(self.priv.data_ptr()), C.c_void_p(self.done.data_ptr()),
-                                        C.c_void_p(self.truncation.data_ptr()), C.c_void_p(track_acc.data_ptr()),
-                                        C.c_void_p(torque_limit.data_ptr()) if torque_limit is not None else None, float(tilt_tol), int(ring),
-                                        C.c_void_p(acc.data_ptr()), int(acc.shape[1]), self._stream()))
+        _chk(self.L.odk_fall_accumulate(self._b, *_report_ptrs(self, track_acc), limit, float(tilt_tol), int(ring), C.c_void_p(acc.data_ptr()), int(acc.shape[1]),
+                                        self._stream()))
 
     def physics_step(self, ctrl, n_substeps: int = 10):
         assert ctrl.is_cuda and ctrl.dtype == self.torch.float32 and ctrl.is_contiguous() and tuple(ctrl.shape) == (self.nenv, self.model.nu)

@@ -120,11 +120,12 @@ nothing changes.
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import itertools
 import json
 import pickle
 import sys
-from typing import Dict, List, Optional, Sequence
+from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
@@ -1242,71 +1243,149 @@ def load_networks(path: Optional[str], env, device):
     return net
 
 
-class Tracker:
-    """One tracking run on a bound command buffer: `step()` = policy + env step + accumulator, captured as one graph.  With `kicks`
-    ([num_envs, 2] device floats, one world-frame kick per env) it is policy + push write + env step + push accumulator + tracking
-    accumulator: the Tracker binds a push buffer of its own (`set_pushes`) that holds env e's kick during the step at which the device
+@dataclasses.dataclass
+class Report:
+    """One report of a Tracker.  `acc`: its zeroed accumulator ([num_envs, ncol] on the env's device); `launch(batch, track_acc)`: after the
+    step, before the tracking accumulator sets ENDED; `shown`: the accumulator and the device-side extras, by the Tracker attribute that shows
+    them.  For `run`: `reduce(acc_numpy, commands, envs_per_block)` gives one value per block of envs (`commands`: the blocks' commands), which
+    `put(block, value)` sets on its row or cell (default: under `key`), and `settings` are its entries of the report's.  `drives`: it sets what
+    the episode is given (pushes, commands), so its entries lead.  `run` reduces every report per row and once more per (command, push) or
+    (command, plant) cell, but the one whose row entries ARE the cells (key "pushes")."""
+    key: str
+    acc: object
+    launch: Callable
+    shown: Dict
+    reduce: Optional[Callable] = None
+    settings: Dict = dataclasses.field(default_factory=dict)
+    put: Optional[Callable] = None
+    zero: Optional[Callable] = None      # default: acc.zero_
+    drives: bool = False
+    before_reset: Callable = lambda batch, track_acc: None
+    before_step: Callable = lambda batch, track_acc: None
+
+
+def _zeros(env, ncol: int):
+    return env.batch.torch.zeros(env.num_envs, ncol, device=env.batch.obs.device)
+
+
+def _device_torque_limits(env):
+    return env.batch.torch.from_numpy(torque_limits(env.mj_model)).to(env.batch.obs.device)
+
+
+def push_report(env, kicks, push_at: int, tolerance, entries: Sequence[Dict] = (), envs_per_cell: int = 0, flags: Optional[Dict] = None) -> Report:
+    """`kicks` ([num_envs, 2], one world-frame kick per env): a bound push buffer that holds env e's kick during the step at which the device
     step counter -- the first-episode step, since first episodes start together at `reset` -- equals `push_at`, and zeros otherwise.
-    With `gait=True` it owns a gait accumulator and the model's torque limits on the device, and the step gains `odk_gait_accumulate`,
-    before the tracking accumulator.  With `posture=True` it owns a posture accumulator, and the step gains `odk_posture_accumulate`
-    (head error tolerance `posture_tolerance`, radians), next to gait's launch.  With `imitation=True` it owns an imitation accumulator, and
-    the step gains `odk_imitation_accumulate` there too (`period_steps`: the reference motion's, `imitation_joint_info`).  With `schedule`
-    -- a dict of `table` (`schedule_table`), `map` (`schedule_blocks`), `tolerance` (lin, ang) and `tail_after` -- the commands change inside
-    the captured step: the Tracker keeps the table and the map on the device and owns a response accumulator; `reset` zeroes the
-    accumulators and issues `odk_command_schedule_apply` once before the env's reset, and the step issues it again before the env step and
-    `odk_response_accumulate` next to the other accumulators.  The bound command tensor is then written by the Tracker.  With `falls` -- a
-    dict of `ring` (samples) and `tilt_tol` (the sine of the upright lean) -- it owns a fall recorder ([num_envs, fall_row_floats(ring)]) and
-    the torque limits, and the step gains `odk_fall_accumulate` next to the other accumulators.  With `delays` ([num_envs] device int32, one
-    action delay per env: 0, 1, 2, or -1 for the sampled one) it binds them (`set_action_delays`) and keeps the tensor; the step itself is
-    unchanged.  Model parameters (`Batch.set_param`) are the caller's to set before `reset`."""
+    For `run`: `entries`, the pushes of a command's cells, `envs_per_cell` envs each, and its `flags`."""
+    torch, acc = env.batch.torch, _zeros(env, PUSH_NACC)
+    kicks = kicks.to(device=acc.device, dtype=torch.float32).reshape(env.num_envs, 2).contiguous()
+    push_at, tol = int(push_at), (float(tolerance[0]), float(tolerance[1]))
+    buf, counter = torch.zeros_like(kicks), torch.full((), -1, dtype=torch.int64, device=acc.device)
+    env.set_pushes(buf)
+
+    def before_step(batch, track_acc):      # device ops only: the same graph replay serves every step
+        counter.add_(1)
+        torch.mul(kicks, (counter == push_at).to(kicks.dtype), out=buf)
+    return Report("pushes", acc, lambda b, t: b.push_accumulate(acc, t, *tol), dict(push_acc=acc, push_buf=buf, kicks=kicks, counter=counter),
+                  reduce=lambda a, cmds, _: reduce_pushes(a, cmds, entries, envs_per_cell, float(env.dt)),      # (a row's block is its cells)
+                  settings=dict(flags or {}, push_at=push_at, push_tolerance=list(tol), pushes_per_command=len(entries)),
+                  put=lambda row, extra: row.update(extra), zero=lambda: (acc.zero_(), buf.zero_(), counter.fill_(-1)), drives=True,
+                  before_step=before_step)
+
+
+def gait_report(env) -> Report:
+    acc, limit = _zeros(env, GAIT_NACC), _device_torque_limits(env)
+    return Report("gait", acc, lambda b, t: b.gait_accumulate(acc, t, limit), dict(gait_acc=acc, torque_limit=limit),
+                  reduce=lambda a, cmds, E: reduce_gait(a, cmds, E, float(env.dt), env.mj_model), settings=dict(gait=True))
+
+
+def posture_report(env, tolerance: float, head=None) -> Report:
+    """`tolerance`: the head error in radians; `head`: (head_map, joint_names) of `posture_head_map`, for `run`."""
+    acc, tol = _zeros(env, POSTURE_NACC), float(tolerance)
+    return Report("posture", acc, lambda b, t: b.posture_accumulate(acc, t, tol), dict(posture_acc=acc),
+                  reduce=lambda a, cmds, E: reduce_posture(a, cmds, E, float(env.dt), *head), settings=dict(posture=True, posture_tolerance=tol))
+
+
+def imitation_report(env, info=None) -> Report:
+    """`info`: (imap, joint_names, period_steps), `imitation_joint_info(env)` unless given."""
+    acc = _zeros(env, IMIT_NACC)
+    imap, names, period = info if info is not None else imitation_joint_info(env)
+    return Report("imitation", acc, lambda b, t: b.imitation_accumulate(acc, t, period), dict(imitation_acc=acc, period_steps=period),
+                  reduce=lambda a, cmds, E: reduce_imitation(a, cmds, E, float(env.dt), imap, names, period),
+                  settings=dict(imitation_report=True, imitation_period_steps=period))
+
+
+def response_report(env, schedule: Dict) -> Report:
+    """`schedule`: a dict of `table` (`schedule_table`), `map` (`schedule_blocks`), `tolerance` (lin, ang), `tail_after`, and for `run` the
+    `schedules` and its `flags`.  `odk_command_schedule_apply` writes the bound command tensor before the env's reset and before every step."""
+    torch, acc = env.batch.torch, _zeros(env, RESP_NACC)
+    table = torch.as_tensor(np.ascontiguousarray(schedule["table"], np.float32)).to(acc.device).contiguous()
+    smap = torch.as_tensor(np.ascontiguousarray(schedule["map"], np.int32)).to(acc.device).contiguous()
+    tol = tuple(float(x) for x in schedule.get("tolerance", DEFAULT_PUSH_TOLERANCE))
+    tail_after, schedules = int(schedule.get("tail_after", DEFAULT_RESPONSE_TAIL_AFTER)), schedule.get("schedules") or ()
+
+    def before_reset(batch, track_acc):      # the reset must find segment 0's command: a zeroed clock, one apply launch, then the env
+        track_acc.zero_()
+        acc.zero_()
+        batch.command_schedule_apply(table, smap, track_acc)
+
+    def reduce(a, cmds, E):      # the blocks: every schedule's, or each schedule's cells (as many blocks per schedule as `cmds` has per schedule)
+        scheds = [s for s in schedules for _ in range(len(cmds) // len(schedules))]
+        return list(zip(scheds, reduce_response(a, scheds, E, float(env.dt))))
+
+    def put(block, value):
+        block["schedule"] = [dict(start_step=int(seg["start_step"]), command=[float(x) for x in seg["command"]]) for seg in value[0]]
+        block["segments"] = value[1]
+    return Report("segments", acc, lambda b, t: b.response_accumulate(acc, t, table, smap, *tol, tail_after),
+                  dict(response_acc=acc, sched=table, sched_map=smap), reduce=reduce, put=put, drives=True, before_reset=before_reset,
+                  settings=dict(schedule.get("flags") or {}, response_tolerance=list(tol), response_tail_after=tail_after, schedules=len(schedules)),
+                  before_step=lambda b, t: b.command_schedule_apply(table, smap, t))      # the command of the step about to run; the clock is STEPS
+
+
+def fall_report(env, falls: Dict) -> Report:
+    """`falls`: a dict of `ring` (samples) and `tilt_tol` (the sine of the upright lean), and for `run`'s settings the flags `tilt`, `save`,
+    `save_max` as given.  The recorder is [num_envs, fall_row_floats(ring)]."""
+    ring, tilt_tol, nq = int(falls["ring"]), float(falls["tilt_tol"]), int(env.batch.model.nq)
+    acc, limit = _zeros(env, env.batch.fall_row_floats(ring)), _device_torque_limits(env)
+    return Report("falls", acc, lambda b, t: b.fall_accumulate(acc, t, tilt_tol, ring, limit), dict(fall_acc=acc, torque_limit=limit),
+                  reduce=lambda a, cmds, E: reduce_falls(a, cmds, E, float(env.dt), ring, nq),
+                  settings=dict(falls=True, fall_ring=ring, fall_tilt=falls.get("tilt"), fall_tilt_tol=tilt_tol, save_falls=falls.get("save"),
+                                save_falls_max=falls.get("save_max")))
+
+
+class Tracker:
+    """One tracking run on a bound command buffer: `step()` = policy + env step + the reports' accumulators + the tracking accumulator,
+    captured as one graph.  `reports`: the `Report`s the step carries, in launch order; or (never both) the switches that make them in this
+    order -- `kicks` with `push_at` / `push_tolerance`, `gait`, `posture` with `posture_tolerance`, `imitation`, `schedule` (the bound command
+    tensor is then written by the Tracker), `falls`.  A report's accumulator and device buffers are also the Tracker's attributes (below),
+    None without the report.  `delays` ([num_envs] device int32, one action delay per env: 0, 1, 2, or -1 for the sampled one) are bound
+    (`set_action_delays`) and kept; the step itself is unchanged.  Model parameters (`Batch.set_param`) are the caller's to set before `reset`."""
+    def _shown(name):      # what the first report that has `name` in its `shown` holds there
+        return property(lambda self: next((r.shown[name] for r in self.reports if name in r.shown), None))
+    push_acc, push_buf, kicks, counter = _shown("push_acc"), _shown("push_buf"), _shown("kicks"), _shown("counter")
+    gait_acc, posture_acc, imitation_acc, period_steps = _shown("gait_acc"), _shown("posture_acc"), _shown("imitation_acc"), _shown("period_steps")
+    response_acc, sched, sched_map, fall_acc, torque_limit = _shown("response_acc"), _shown("sched"), _shown("sched_map"), _shown("fall_acc"), _shown("torque_limit")
 
     def __init__(self, env, net, use_graph: bool = True, kicks=None, push_at: int = DEFAULT_PUSH_AT, push_tolerance=DEFAULT_PUSH_TOLERANCE,
                  gait: bool = False, posture: bool = False, posture_tolerance: float = DEFAULT_POSTURE_TOLERANCE,
-                 imitation: bool = False, schedule: Optional[Dict] = None, falls: Optional[Dict] = None, delays=None):
+                 imitation: bool = False, schedule: Optional[Dict] = None, falls: Optional[Dict] = None, delays=None, reports=None):
         import torch
         self.env, self.net, self.torch = env, net, torch
-        b = env.batch
-        self.acc = torch.zeros(env.num_envs, NACC, device=b.obs.device)
-        self.kicks = self.push_buf = self.push_acc = self.counter = None
-        if kicks is not None:
-            self.kicks = kicks.to(device=b.obs.device, dtype=torch.float32).reshape(env.num_envs, 2).contiguous()
-            self.push_at, self.push_tolerance = int(push_at), (float(push_tolerance[0]), float(push_tolerance[1]))
-            self.push_buf = torch.zeros_like(self.kicks)
-            self.push_acc = torch.zeros(env.num_envs, PUSH_NACC, device=b.obs.device)
-            self.counter = torch.full((), -1, dtype=torch.int64, device=b.obs.device)
-            env.set_pushes(self.push_buf)
+        self.acc = torch.zeros(env.num_envs, NACC, device=env.batch.obs.device)
+        if reports is not None and (kicks is not None or gait or posture or imitation or schedule is not None or falls is not None):
+            raise ValueError("Tracker: give the reports or the switches that make them, not both")
+        if reports is None:
+            reports = [make() for on, make in (
+                (kicks is not None, lambda: push_report(env, kicks, push_at, push_tolerance)), (gait, lambda: gait_report(env)),
+                (posture, lambda: posture_report(env, posture_tolerance)), (imitation, lambda: imitation_report(env)),
+                (schedule is not None, lambda: response_report(env, schedule)), (falls is not None, lambda: fall_report(env, falls))) if on]
+        self.reports = list(reports)
         self.delays = None
         if delays is not None:
-            self.delays = delays.to(device=b.obs.device, dtype=torch.int32).reshape(env.num_envs).contiguous()
+            self.delays = delays.to(device=self.acc.device, dtype=torch.int32).reshape(env.num_envs).contiguous()
             env.set_action_delays(self.delays)
-        self.gait_acc = self.torque_limit = None
-        if gait:
-            self.gait_acc = torch.zeros(env.num_envs, GAIT_NACC, device=b.obs.device)
-            self.torque_limit = torch.from_numpy(torque_limits(env.mj_model)).to(b.obs.device)
-        self.posture_acc, self.posture_tolerance = None, float(posture_tolerance)
-        if posture:
-            self.posture_acc = torch.zeros(env.num_envs, POSTURE_NACC, device=b.obs.device)
-        self.imitation_acc = self.period_steps = None
-        if imitation:
-            self.period_steps = imitation_joint_info(env)[2]
-            self.imitation_acc = torch.zeros(env.num_envs, IMIT_NACC, device=b.obs.device)
-        self.sched = self.sched_map = self.response_acc = None
-        if schedule is not None:
-            self.sched = torch.as_tensor(np.ascontiguousarray(schedule["table"], np.float32)).to(b.obs.device).contiguous()
-            self.sched_map = torch.as_tensor(np.ascontiguousarray(schedule["map"], np.int32)).to(b.obs.device).contiguous()
-            self.response_tolerance = tuple(float(x) for x in schedule.get("tolerance", DEFAULT_PUSH_TOLERANCE))
-            self.response_tail_after = int(schedule.get("tail_after", DEFAULT_RESPONSE_TAIL_AFTER))
-            self.response_acc = torch.zeros(env.num_envs, RESP_NACC, device=b.obs.device)
-        self.fall_acc = self.fall_ring = self.fall_tilt_tol = None
-        if falls is not None:
-            self.fall_ring, self.fall_tilt_tol = int(falls["ring"]), float(falls["tilt_tol"])
-            self.fall_acc = torch.zeros(env.num_envs, b.fall_row_floats(self.fall_ring), device=b.obs.device)
-            if self.torque_limit is None:
-                self.torque_limit = torch.from_numpy(torque_limits(env.mj_model)).to(b.obs.device)
         from .ppo.learner import fused_policy
         self.fp = fused_policy(net, env.num_envs)
-        self.use_graph = use_graph
-        self.graph = None
+        self.use_graph, self.graph = use_graph, None
 
     def actions(self, obs):
         """The deterministic policy: tanh(loc) of the policy head (Evaluator._one_step)."""
@@ -1316,43 +1395,20 @@ class Tracker:
     def _one_step(self):
         b = self.env.batch
         act = self.actions(b.obs)
-        if self.kicks is not None:                  # device ops only: the same graph replay serves every step
-            self.counter.add_(1)
-            self.torch.mul(self.kicks, (self.counter == self.push_at).to(self.kicks.dtype), out=self.push_buf)
-        if self.sched is not None:
-            b.command_schedule_apply(self.sched, self.sched_map, self.acc)      # the command of the step about to run; the clock is acc's STEPS
+        for r in self.reports:
+            r.before_step(b, self.acc)
         b.step(act)                                 # Joystick.step without the State wrapper (nothing here reads it)
-        if self.kicks is not None:
-            b.push_accumulate(self.push_acc, self.acc, *self.push_tolerance)      # before the tracking accumulator sets ENDED
-        if self.gait_acc is not None:
-            b.gait_accumulate(self.gait_acc, self.acc, self.torque_limit)         # likewise
-        if self.posture_acc is not None:
-            b.posture_accumulate(self.posture_acc, self.acc, self.posture_tolerance)
-        if self.imitation_acc is not None:
-            b.imitation_accumulate(self.imitation_acc, self.acc, self.period_steps)
-        if self.response_acc is not None:
-            b.response_accumulate(self.response_acc, self.acc, self.sched, self.sched_map, *self.response_tolerance, self.response_tail_after)
-        if self.fall_acc is not None:
-            b.fall_accumulate(self.fall_acc, self.acc, self.fall_tilt_tol, self.fall_ring, self.torque_limit)
+        for r in self.reports:
+            r.launch(b, self.acc)                   # before the tracking accumulator sets ENDED
         b.tracking_accumulate(self.acc)
 
     def reset(self, seed: int):
-        if self.sched is not None:                  # the reset must find segment 0's command: a zeroed clock, one apply launch, then the env
-            self.acc.zero_()
-            self.response_acc.zero_()
-            self.env.batch.command_schedule_apply(self.sched, self.sched_map, self.acc)
+        for r in self.reports:
+            r.before_reset(self.env.batch, self.acc)
         self.env.reset(int(seed))
         self.acc.zero_()
-        if self.kicks is not None:
-            self.push_acc.zero_(); self.push_buf.zero_(); self.counter.fill_(-1)
-        if self.gait_acc is not None:
-            self.gait_acc.zero_()
-        if self.posture_acc is not None:
-            self.posture_acc.zero_()
-        if self.imitation_acc is not None:
-            self.imitation_acc.zero_()
-        if self.fall_acc is not None:
-            self.fall_acc.zero_()
+        for r in self.reports:
+            (r.zero or r.acc.zero_)()
         if self.fp is not None:
             self.fp.refresh()                       # its packed weight copy <- the current parameters
 
@@ -1392,20 +1448,10 @@ def run(args, out=sys.stdout) -> Dict:
     ncell = max(len(pushes), 1) * max(len(plants), 1)      # cells per command (pushes and plants exclude each other)
     cells_key = "pushes" if pushes else ("plants" if plants else None)
     randomized = bool(getattr(args, "randomize", False))
-    gait = bool(getattr(args, "gait", False))
-    posture = bool(getattr(args, "posture", False))
-    posture_tol = float(getattr(args, "posture_tolerance", DEFAULT_POSTURE_TOLERANCE))
     imitation = bool(getattr(args, "imitation_report", False))
-    if imitation:      # before any batch work
-        why = imitation_refusal(args)
+    for why in (imitation_refusal(args) if imitation else None, falls_refusal(args)):      # before any batch work
         if why:
             raise SystemExit(why)
-    why = falls_refusal(args)      # likewise
-    if why:
-        raise SystemExit(why)
-    falls = None
-    if getattr(args, "falls", False):
-        falls = dict(ring=int(getattr(args, "fall_ring", DEFAULT_FALL_RING)), tilt_tol=fall_tilt_tol(getattr(args, "fall_tilt", DEFAULT_FALL_TILT)))
     E = int(args.envs_per_command)
     n = len(commands) * ncell * E
     torch.cuda.set_device(args.device)
@@ -1416,16 +1462,11 @@ def run(args, out=sys.stdout) -> Dict:
         print(motion.describe(), file=sys.stderr)      # stdout may carry the JSON report
     if hasattr(env, "describe_head_joints"):
         print(env.describe_head_joints(), file=sys.stderr)
-    if posture:
-        try:
-            head_map, joint_names = posture_head_map(env)
-        except ValueError as err:
-            raise SystemExit(str(err))
-    if imitation:
-        try:
-            imap, imit_joint_names, period_steps = imitation_joint_info(env)
-        except ValueError as err:
-            raise SystemExit(str(err))
+    try:      # what the reductions need of the robot, before the checkpoint is read
+        head = posture_head_map(env) if getattr(args, "posture", False) else None
+        imitation_info = imitation_joint_info(env) if imitation else None
+    except ValueError as err:
+        raise SystemExit(str(err))
     net = load_networks(args.checkpoint, env, dev)
     delays_t = None
     if plants or randomized:      # per-env model parameters: the training-time draw, the plants' scales, or the one times the other
@@ -1436,28 +1477,35 @@ def run(args, out=sys.stdout) -> Dict:
             fields = plant_fields(env.mj_model, scales, fields)
             delays_t = torch.from_numpy(delays_np).to(dev)
         randomize.apply(env.batch, fields)
+    cmd_np, kicks_np = cell_blocks(commands, pushes, E) if pushes else (command_blocks(commands, ncell * E), None)
+    cmd = torch.from_numpy(cmd_np).to(dev)      # with schedules: segment 0's; the Tracker's apply launch rewrites it every step
+    env.set_commands(cmd)
+    reports = []      # in launch order
     if pushes:
-        push_at = int(args.push_at)
-        if push_at < 0:
+        if int(args.push_at) < 0:
             raise SystemExit("--push_at is a step of the episode: >= 0")
-        tol = tuple(float(x) for x in args.push_tolerance)
-        cmd_np, kicks_np = cell_blocks(commands, pushes, E)
-        cmd = torch.from_numpy(cmd_np).to(dev)
-        env.set_commands(cmd)
-        tr = Tracker(env, net, kicks=torch.from_numpy(kicks_np).to(dev), push_at=push_at, push_tolerance=tol, gait=gait, posture=posture,
-                     posture_tolerance=posture_tol, imitation=imitation, falls=falls)
-    elif schedules is not None:
-        resp_tol = response_tolerance(args)
-        tail_after = int(getattr(args, "response_tail_after", DEFAULT_RESPONSE_TAIL_AFTER))
-        cmd = torch.from_numpy(command_blocks(commands, ncell * E)).to(dev)      # segment 0's; the Tracker's apply launch rewrites it every step
-        env.set_commands(cmd)
-        tr = Tracker(env, net, gait=gait, imitation=imitation, falls=falls, delays=delays_t,
-                     schedule=dict(table=schedule_table(schedules), map=schedule_blocks(len(schedules), ncell * E), tolerance=resp_tol,
-                                   tail_after=tail_after))
-    else:
-        cmd = torch.from_numpy(command_blocks(commands, ncell * E)).to(dev)
-        env.set_commands(cmd)
-        tr = Tracker(env, net, gait=gait, posture=posture, posture_tolerance=posture_tol, imitation=imitation, falls=falls, delays=delays_t)
+        reports.append(push_report(env, torch.from_numpy(kicks_np).to(dev), int(args.push_at), args.push_tolerance, entries=pushes, envs_per_cell=E,
+                                   flags=dict(push=getattr(args, "push", None), push_grid=getattr(args, "push_grid", None))))
+    if getattr(args, "gait", False):
+        reports.append(gait_report(env))
+    if head is not None:
+        reports.append(posture_report(env, getattr(args, "posture_tolerance", DEFAULT_POSTURE_TOLERANCE), head))
+    if imitation:
+        reports.append(imitation_report(env, imitation_info))
+    if schedules is not None:
+        then = getattr(args, "then", None)
+        reports.append(response_report(env, dict(
+            table=schedule_table(schedules), map=schedule_blocks(len(schedules), ncell * E), tolerance=response_tolerance(args),
+            tail_after=getattr(args, "response_tail_after", DEFAULT_RESPONSE_TAIL_AFTER), schedules=schedules,
+            flags=dict(sequence=getattr(args, "sequence", None), then=then, switch_at=int(getattr(args, "switch_at", DEFAULT_SWITCH_AT)) if then else None))))
+    falls = None
+    if getattr(args, "falls", False):      # (falls_refusal has seen the flags)
+        falls = dict(ring=int(getattr(args, "fall_ring", DEFAULT_FALL_RING)), tilt_tol=fall_tilt_tol(getattr(args, "fall_tilt", DEFAULT_FALL_TILT)),
+                     tilt=float(getattr(args, "fall_tilt", DEFAULT_FALL_TILT)), save=getattr(args, "save_falls", None),
+                     save_max=int(getattr(args, "save_falls_max", DEFAULT_SAVE_FALLS_MAX)))
+        reports.append(fall_report(env, falls))
+    tr = Tracker(env, net, delays=delays_t, reports=reports)
+    reports = sorted(reports, key=lambda r: not r.drives)      # the report's order: pushes and schedules first (a stable sort)
     nobs = env.observation_size["state"][0]
     T = int(args.episode_length)
     save_obs_path, save_qpos_path = getattr(args, "save_obs", None), getattr(args, "save_qpos", None)
@@ -1474,78 +1522,30 @@ def run(args, out=sys.stdout) -> Dict:
             if save_qpos_path:
                 qpos_hist.append(env.batch.get_state()[0][0].copy())
         acc = tr.acc.cpu().numpy()
-        push_acc = tr.push_acc.cpu().numpy() if pushes else None
-        gait_acc = tr.gait_acc.cpu().numpy() if gait else None
-        posture_acc = tr.posture_acc.cpu().numpy() if posture else None
-        imitation_acc = tr.imitation_acc.cpu().numpy() if imitation else None
-        response_acc = tr.response_acc.cpu().numpy() if schedules is not None else None
-        fall_acc = tr.fall_acc.cpu().numpy() if falls else None
+        accs = [r.acc.cpu().numpy() for r in reports]
     rows = reduce_tracking(acc, commands, ncell * E)
-    if pushes:
-        for row, extra in zip(rows, reduce_pushes(push_acc, commands, pushes, E, float(env.dt))):
-            row.update(extra)
     if plants:      # one whole command row per (command, plant) cell, in `plant_blocks` order, plus the plant it ran on
         cell_rows = reduce_tracking(acc, [c for c in commands for _ in plants], E)
         for i, cell in enumerate(cell_rows):
             cell["plant"] = dict(plants[i % len(plants)])
         for c, row in enumerate(rows):
             row["plants"] = cell_rows[c * len(plants):(c + 1) * len(plants)]
-    if schedules is not None:
-        for row, sched, segs in zip(rows, schedules, reduce_response(response_acc, schedules, ncell * E, float(env.dt))):
-            row["schedule"] = [dict(start_step=int(seg["start_step"]), command=[float(x) for x in seg["command"]]) for seg in sched]
-            row["segments"] = segs
-        if plants:      # and per (schedule, plant) cell
-            cells = [cell for row in rows for cell in row["plants"]]
-            cell_scheds = [sched for sched in schedules for _ in plants]
-            for cell, sched, segs in zip(cells, cell_scheds, reduce_response(response_acc, cell_scheds, E, float(env.dt))):
-                cell["schedule"] = [dict(start_step=int(seg["start_step"]), command=[float(x) for x in seg["command"]]) for seg in sched]
-                cell["segments"] = segs
-    if gait:
-        for row, g in zip(rows, reduce_gait(gait_acc, commands, ncell * E, float(env.dt), env.mj_model)):
-            row["gait"] = g
-        if cells_key:      # and one per (command, push) or (command, plant) cell, in `cell_blocks` order
+    for r, a in zip(reports, accs):      # per row, then per (command, push) or (command, plant) cell, in `cell_blocks` / `plant_blocks` order
+        put = r.put or (lambda block, value, key=r.key: block.__setitem__(key, value))
+        for row, value in zip(rows, r.reduce(a, commands, ncell * E)):
+            put(row, value)
+        if cells_key and r.key != cells_key:
             cells = [cell for row in rows for cell in row[cells_key]]
-            for cell, g in zip(cells, reduce_gait(gait_acc, cells, E, float(env.dt), env.mj_model)):
-                cell["gait"] = g
-    if posture:
-        for row, g in zip(rows, reduce_posture(posture_acc, commands, ncell * E, float(env.dt), head_map, joint_names)):
-            row["posture"] = g
-        if cells_key:      # and one per cell
-            cells = [cell for row in rows for cell in row[cells_key]]
-            cell_cmds = [row["command"] for row in rows for _ in row[cells_key]]
-            for cell, g in zip(cells, reduce_posture(posture_acc, cell_cmds, E, float(env.dt), head_map, joint_names)):
-                cell["posture"] = g
-    if imitation:
-        for row, g in zip(rows, reduce_imitation(imitation_acc, commands, ncell * E, float(env.dt), imap, imit_joint_names, period_steps)):
-            row["imitation"] = g
-        if cells_key:      # and one per cell
-            cells = [cell for row in rows for cell in row[cells_key]]
-            for cell, g in zip(cells, reduce_imitation(imitation_acc, cells, E, float(env.dt), imap, imit_joint_names, period_steps)):
-                cell["imitation"] = g
-    if falls:
-        nq = int(env.batch.model.nq)
-        for row, g in zip(rows, reduce_falls(fall_acc, commands, ncell * E, float(env.dt), falls["ring"], nq)):
-            row["falls"] = g
-        blocks = rows
-        if cells_key:      # and one per cell
-            blocks = [cell for row in rows for cell in row[cells_key]]
-            for cell, g in zip(blocks, reduce_falls(fall_acc, blocks, E, float(env.dt), falls["ring"], nq)):
-                cell["falls"] = g
-        if getattr(args, "save_falls", None):      # the clips of every row, or with pushes of every cell
-            block_cmds = [row["command"] for row in rows for _ in (row[cells_key] if cells_key else [0])]
-            save_falls(args.save_falls, fall_clips(fall_acc, block_cmds, E, falls["ring"], nq,
-                                                   int(getattr(args, "save_falls_max", DEFAULT_SAVE_FALLS_MAX))), float(env.dt))
+            for cell, value in zip(cells, r.reduce(a, [row["command"] for row in rows for _ in row[cells_key]], E)):
+                put(cell, value)
+    if falls and falls["save"]:      # the clips of every row, or with pushes / plants of every cell
+        block_cmds = [row["command"] for row in rows for _ in (row[cells_key] if cells_key else [0])]
+        save_falls(falls["save"], fall_clips(accs[[r.key for r in reports].index("falls")], block_cmds, E, falls["ring"], int(env.batch.model.nq), falls["save_max"]), float(env.dt))
     settings = dict(checkpoint=args.checkpoint, env=args.env, task=args.task, xml=args.xml, cone=args.cone,
                     hfield_up_normals_only=bool(args.hfield_up_normals_only), envs_per_command=E, episode_length=T, seed=int(args.seed),
                     num_envs=n, dt=float(env.dt), policy="deterministic tanh(loc)", fused_policy=tr.fp is not None, graph=tr.graph is not None,
                     reference_motion=getattr(args, "reference_motion", None), reference_motion_sha256=motion.sha256 if motion is not None else None)
-    if pushes:
-        settings.update(push=getattr(args, "push", None), push_grid=getattr(args, "push_grid", None), push_at=push_at,
-                        push_tolerance=list(tol), pushes_per_command=len(pushes))
-    if schedules is not None:
-        settings.update(sequence=getattr(args, "sequence", None), then=getattr(args, "then", None),
-                        switch_at=int(getattr(args, "switch_at", DEFAULT_SWITCH_AT)) if getattr(args, "then", None) else None,
-                        response_tolerance=list(resp_tol), response_tail_after=tail_after, schedules=len(schedules))
+    settings.update({k: v for r in reports if r.drives for k, v in r.settings.items()})
     if plants:
         robust = float(getattr(args, "robust_fall_rate", DEFAULT_ROBUST_FALL_RATE))
         for row in rows:      # after every per-cell object is in place: the robustness lines read the cells' own figures
@@ -1560,16 +1560,7 @@ def run(args, out=sys.stdout) -> Dict:
         settings.update(randomize=True)
     if getattr(args, "noise_level", None) is not None:
         settings.update(noise_level=float(args.noise_level))
-    if gait:
-        settings.update(gait=True)
-    if posture:
-        settings.update(posture=True, posture_tolerance=posture_tol)
-    if imitation:
-        settings.update(imitation_report=True, imitation_period_steps=period_steps)
-    if falls:
-        settings.update(falls=True, fall_ring=falls["ring"], fall_tilt=float(getattr(args, "fall_tilt", DEFAULT_FALL_TILT)),
-                        fall_tilt_tol=falls["tilt_tol"], save_falls=getattr(args, "save_falls", None),
-                        save_falls_max=int(getattr(args, "save_falls_max", DEFAULT_SAVE_FALLS_MAX)))
+    settings.update({k: v for r in reports if not r.drives for k, v in r.settings.items()})
     report = make_report(settings, rows)
     if save_obs_path:
         save_obs(save_obs_path, obs_hist.cpu().numpy())

@@ -37,7 +37,7 @@ def tree(tmp_path_factory):
     with open(os.path.join(dst, "odk_shapes_user.h"), "w") as f:
         f.write(USER_HEADER)
     products = outputs(tree)
-    assert products == sorted([f"odk_env_{s}.o" for s in SHIPPED_SETS + ["U0"]] + HOST_OBJECTS + ["odk_learner.o", "odk_mlp.o", "libodk.so"])
+    assert products == sorted([f"odk_env_{s}.o" for s in SHIPPED_SETS + ["U0"]] + HOST_OBJECTS + ["odk_reports.o", "odk_learner.o", "odk_mlp.o", "libodk.so"])
     for f in [p for p in products if p != "libodk.so"] + ["libodk.so"]:
         open(os.path.join(dst, f), "w").close()
     assert outputs(tree) == []
@@ -45,6 +45,7 @@ def tree(tmp_path_factory):
 
 
 def test_a_new_user_shape_compiles_its_own_kernel_set_and_the_host_objects(tree):
+    # (odk_reports.o is not among them: the report kernels include no odk_shapes.h)
     assert outputs(tree, "-W", "odk_shapes_user.h") == sorted(["odk_env_U0.o"] + HOST_OBJECTS + ["libodk.so"])
 
 
@@ -54,3 +55,7 @@ def test_an_edit_of_the_model_loader_compiles_one_object(tree):
 
 def test_an_edit_of_the_batch_api_compiles_no_env_kernel(tree):
     assert outputs(tree, "-W", "odk_engine.hip") == ["libodk.so", "odk_engine.o"]
+
+
+def test_an_edit_of_the_reports_compiles_one_object(tree):
+    assert outputs(tree, "-W", "odk_reports.hip") == ["libodk.so", "odk_reports.o"]

@@ -2,7 +2,7 @@
 """Are two builds' instruction streams the same, function by function?
 
     make -C open_duck_playground_amd/csrc -j8 engine.s      (before a change; keep it as old.s.  engine.s: the listings of every kernel set,
-    make -C open_duck_playground_amd/csrc -j8 engine.s       odk_env_<set>.s, and of odk_engine.hip's accumulator kernels, in one file; one set
+    make -C open_duck_playground_amd/csrc -j8 engine.s       odk_env_<set>.s, and of odk_reports.hip's accumulator kernels, odk_reports.s, in one file; one set
     python tools/isa_compare.py old.s engine.s [name-filter ...]      alone: make odk_env_B.s)
 
 For every function (kernel or out-of-line device function) present in both listings: the instruction lines with comments, labels and
