@@ -133,6 +133,13 @@ int odk_model_reduced(const odk_model* m, int* paired, int* nvr, int* nMr, int* 
 int odk_model_body_lanes(const odk_model* m, int lanes_per_env, int* out, int n);
 /* floats of LDS one env occupies in the fused step kernel (8 single-wave workgroups of two envs per CU need <= 2560) */
 int odk_model_env_lds_floats(const odk_model* m);
+/* The launch-invariant small integers of the substep as the plane-floor step kernel reads them (csrc/odk_model.h DevModel::hot_pk: three
+ * packed words, written at load; a value that does not fit its field is refused there by name) and, next to them, the twelve values they
+ * were packed from: foot_body[2], foot_nvert[2], foot_rchain_first[2], foot_rchain_len[2], ls_iterations, max_nonpath_level, np_count,
+ * foot_prim.  Layout: word 0 = foot_body * 4 in bytes 0 / 1, foot_nvert in bytes 2 / 3; word 1 = foot_rchain_first * 4 in bytes 0 / 1,
+ * foot_rchain_len in bits 16-19 / 20-23, ls_iterations in byte 3; word 2 = max_nonpath_level + 1, np_count, foot_prim in bytes 0 / 1 / 2.
+ * Host-only (no GPU needed). */
+int odk_model_hot_words(const odk_model* m, int* packed, int* fields);
 
 /* One batch of `nenv` environments resident on HIP device `device`.  `prm_table` is the host
  * [nx,ny,nth,40,16] float32 reference-motion table (poly_reference_motion.py), grids in float64. */

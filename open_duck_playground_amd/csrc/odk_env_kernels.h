@@ -13,7 +13,7 @@
 
 
 // the workgroup's copy of the shared tables (call with all 64 lanes; followed by a hand-off barrier at the caller)
-template <class S> __device__ __forceinline__ const int* load_shared(float* lds, int envs, const DevModel* m) {
+template <class S, bool HOT = false> __device__ __forceinline__ const int* load_shared(float* lds, int envs, const DevModel* m) {
   int* RT = reinterpret_cast<int*>(lds + envs * EnvL<S>::TOTAL);
   {
     constexpr int T = (S::NMR + 63) / 64;
@@ -29,6 +29,9 @@ template <class S> __device__ __forceinline__ const int* load_shared(float* lds,
   if (k < 3) { CT[k] = m->pair_mu[k]; CT[3 + k] = m->pair_invweight[k]; }
   if (k < 27) CT[6 + k] = m->pair_imp[k / 9][k % 9];
   if (k < 9) CT[33 + k] = m->plane_frame[k];
+  if constexpr (HOT && S::HOT_LDS) {   // the model's uniform floats of the substep (forward_env: HOTV; HOT: the kernel that reads them), where the shape's workgroup has the room
+    if (k < HOT_NF) SH[S::SH_HOT + k] = m->hot_f[k];
+  }
   return RT;
 }
 
@@ -431,7 +434,7 @@ __device__ __forceinline__ void step_body(const KArgs& a) {
   odk_poison_fill(lds, E::wg_floats(64 / G));   // env images, padding, shared tables -- which load_shared then writes)
   ODK_SYNC();
 #endif
-  const int* RT = load_shared<S>(lds, 64 / G, a.m);   // ordered before its first use by the ODK_SYNCs below
+  const int* RT = load_shared<S, HF == 0>(lds, 64 / G, a.m);   // (with the hot floats for the plane-floor kernel, which reads them) ordered before its first use by the ODK_SYNCs below
   const DevModel* m = a.m;
   const EnvCfg& c = a.cfg;
   float* INFO = L + E::O_INFO; float* ACT = L + E::O_ACT; float* CTRL = L + S::O_CTRL;

@@ -92,7 +92,7 @@ struct Shape {
   // workgroup-shared LDS tables behind the envs' images (odk_env_kernels.h load_shared): the packed reduced entries and the
   // contact-row constants.  (Friction-loss rows, actuator constants and the foot hull were tried there too: no gain, their
   // loads from the L2-resident model are already covered.)
-  static constexpr int SH_CT = NMR, SHARED = SH_CT + 42;
+  static constexpr int SH_CT = NMR, SH_HOT = SH_CT + 42;
   static constexpr int CL = CL_ >= 0 ? CL_ : ((NV_ == 20 || NV_ == 21 || PAIRED) ? 5 : 0);   // max (reduced) chain length for chain_solve: every compiled shape is a floating base + <= NCH serial chains of <= CL (reduced) dofs (0: generic path)
   static constexpr int NCH = NCH_;  // serial chains below the floating base that chain_solve eliminates: chain c on lanes 8 c .. 8 c + 6 (a biped with arms: 4)
   static_assert(NCH >= 1 && NCH <= 4, "chain_solve: one 8-lane group per chain, 32 lanes");
@@ -178,6 +178,12 @@ struct Shape {
   // imitation phase, both rounded up to whole float4s (the duck: 144 + 16)
   static constexpr int N_INFO = ((43 + 7 * NU + 3) / 4) * 4, N_ACT = ((NU + 2 + 3) / 4) * 4;
   static constexpr int ENV_STRIDE = TOTAL + N_INFO + N_ACT;   // floats between the images of the two envs of a workgroup (odk_shapes.h EnvL::TOTAL)
+  // The model's uniform floats of the substep (DevModel::hot_f) as a third shared table at SH_HOT, read by LDS broadcast instead of an L2
+  // round trip -- for a shape whose two-env workgroup has the room: the HOT_NF floats must not cost a workgroup per CU (160 KiB of LDS,
+  // 8 single-wave workgroups at most).  A shape without the room keeps the loads from the model.
+  static constexpr int wgs_per_cu(int floats) { return 163840 / (4 * floats) > 8 ? 8 : 163840 / (4 * floats); }
+  static constexpr bool HOT_LDS = wgs_per_cu(2 * ENV_STRIDE + SH_HOT + HOT_NF) == wgs_per_cu(2 * ENV_STRIDE + SH_HOT);
+  static constexpr int SHARED = SH_HOT + (HOT_LDS ? HOT_NF : 0);
 };
 
 // Phase timing (build with -DODK_PROFILE): lane 0 accumulates shader-clock deltas per phase into the
@@ -378,7 +384,11 @@ struct FlSt { float D, R, b; int dof; };
 
 // The same three records held over the whole launch instead (plane-floor kernels: ~40 registers are free there since round 3, and
 // each of these loads sat exposed right behind a phase hand-off in every substep)
-struct HotSt { ActSt as; FlSt fs; float vb[3]; };   // (the non-chain bodies' source lists the same way: +1 %, the limit rows' records: over the register budget)
+// ve: the 17th hull vertex of the lane's foot; pk: DevModel::hot_pk, the model's wave-uniform small integers as three packed words (held in
+// vector registers; forward_env makes them uniform once per substep and extracts every field on the scalar unit); np: the lane's record of
+// the subtree fold (DevModel::np_rec: the six sources, the target and the count as byte fields in two registers -- as eight plain registers
+// the lists had cost 1 %: profiles/load_waits/NOTES.md).  (The limit rows' records the same way: over the register budget.)
+struct HotSt { ActSt as; FlSt fs; float vb[3], ve[3]; int pk[HOT_NPK], np[2]; };
 
 // Device side: the lane's host-built record (DevModel::lane_st, filled by compute_statics below at model load)
 template <class S, int G>
@@ -462,8 +472,13 @@ __device__ __forceinline__ void load_hot(HotSt& h, const DevModel* __restrict__ 
   load_fl(h.fs, m, lane);
   const int f = (lane >> 4) & 1, j = lane & 15;   // plane-convex: foot f = 16-lane row f, lane j = hull vertex j
   const int jv = (lane < 32 && j < m->foot_nvert[f]) ? j : 0;
-  for (int k = 0; k < 3; k++) h.vb[k] = m->foot_vert[f][jv][k];
+  for (int k = 0; k < 3; k++) { h.vb[k] = m->foot_vert[f][jv][k]; h.ve[k] = m->foot_vert[f][16][k]; }
+  for (int k = 0; k < HOT_NPK; k++) h.pk[k] = m->hot_pk[k];
+  h.np[0] = m->np_rec[lane][0]; h.np[1] = m->np_rec[lane][1];
 }
+// a float of an LDS array at a BYTE offset (the packed records carry index * 4: no shift in front of the address add)
+__device__ __forceinline__ float& lds_at(float* base, int byte_off) { return *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + byte_off); }
+__device__ __forceinline__ const float& lds_at(const float* base, int byte_off) { return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off); }
 // packed entries of the reduced layouts (DevModel::R_ent / RH_ent), -1 beyond the layout
 __device__ __forceinline__ int load_rent(const DevModel* __restrict__ m, int p, int n) { const int e = m->R_ent[p < n ? p : 0]; return p < n ? e : -1; }
 __device__ __forceinline__ int load_rhent(const DevModel* __restrict__ m, int p, int n) { const int e = m->RH_ent[p < n ? p : 0]; return p < n ? e : -1; }
@@ -1919,6 +1934,21 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
   // Behind them (SH_CT): the contact-row constants -- pair_mu[3] | pair_invweight[3] | pair_imp[3][9] | plane_frame[9].
   const float* SH = reinterpret_cast<const float*>(RT);
   const float* CT = SH + S::SH_CT;
+  // The model's launch-invariant small integers and uniform floats (PRE: the plane-floor step kernel).  Integers: the fields of hot.pk.
+  // The three words ride through the launch in vector registers (held in scalar registers they added lane-spill pairs) and are made
+  // uniform HERE, behind an opaque copy: three v_readfirstlane per substep, every extract a scalar instruction of this substep, none
+  // lifted above the substep loop to occupy a register of its own.  Floats: the shared LDS table at SH_HOT where the shape has the room
+  // (Shape::HOT_LDS).  Without PRE every value is loaded from the model where it is used, as before -- the same instruction streams.
+  int hpk[HOT_NPK] = {0, 0, 0};
+  if constexpr (PRE) {
+#pragma unroll
+    for (int k = 0; k < HOT_NPK; k++) { int w = hot.pk[k]; asm volatile("" : "+v"(w)); hpk[k] = __builtin_amdgcn_readfirstlane(w); }
+  }
+  constexpr bool HOTF = PRE && S::HOT_LDS;
+  const float* HOTV = SH + S::SH_HOT;
+#define ODK_HOTI(F, expr) (PRE ? hot_value(hpk, F) : (expr))      // (PRE / HOTF are constants: the other arm is not compiled)
+#define ODK_HOTF(i, expr) (HOTF ? HOTV[i] : (expr))
+#define ODK_OBBC(f, k) ODK_HOTF(HOT_F_OBBC + 3 * (f) + (k), m->foot_obb_center[f][k])
   constexpr int NV = S::NV, NB = S::NB, NR = S::NVR;   // NR: reduced dofs = columns of CDOF / BUF6 / BUF6B
   using ST = Statics<S, G>;
   float* QPOS = L + S::O_QPOS; float* QVEL = L + S::O_QVEL; float* WARM = L + S::O_WARM; float* CTRL = L + S::O_CTRL;
@@ -1969,7 +1999,7 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
     }
     // bodies above the serial chains (world side of the tree: base, trunk): one tree level per step.  (The bound is read once: as
     // `lvl <= m->max_nonpath_level` it was loaded again in every iteration, with the full wait for the load right behind it.)
-    const int max_np = m->max_nonpath_level;
+    const int max_np = ODK_HOTI(HOT_NP_LEVELS, m->max_nonpath_level + 1) - 1;
     for (int lvl = 0; lvl <= max_np; lvl++) {
       if (bs.level == lvl && !bs.is_path) {
         if (lvl == 0) {  // floating base: free joint (mj_comVel free-joint rule)
@@ -2241,13 +2271,25 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
   {
     float* ACC = CFRC;
     static_assert(S::O_CRB == S::O_CFRC + 6 * NB, "cfrc | crb must be contiguous");
-    const int nnp = m->np_count;          // <= 2 * (G / 16), checked at load
+    const int nnp = ODK_HOTI(HOT_NP_COUNT, m->np_count);          // <= 2 * (G / 16), checked at load
     const int slot = lane >> 4, q = lane & 15;
     float t[2] = {0.0f, 0.0f};
+    // PRE: pass 0 reads the lane's packed record (HotSt::np: byte offsets of the six sources and of the target, the count) -- no load from
+    // the model; pass 1 runs only for a robot with more than G / 16 such bodies (none that ships) and keeps the loads
+    int np0 = 0, np1 = 0;
+    if constexpr (PRE) { np0 = hot.np[0]; np1 = hot.np[1]; asm volatile("" : "+v"(np0), "+v"(np1)); }
 #pragma unroll
     for (int pass = 0; pass < 2; pass++) {
       const int i = pass * (G / 16) + slot;
       if (i < nnp) {   // (skipped wave-wide for pass 1 when there are at most G / 16 such bodies)
+        if (PRE && pass == 0) {
+          const int ns = (int)((unsigned)np1 >> 24);
+          float x = 0.0f;
+#pragma unroll
+          for (int c = 0; c < 6; c++) { const float y = lds_at(ACC + q * NB, (int)(((unsigned)(c < 4 ? np0 : np1) >> (8 * (c & 3))) & 0xFFu)); x += c < ns ? y : 0.0f; }
+          t[pass] = x;
+          continue;
+        }
         const int ns = m->np_nsrc[i];
         int src[6];    // all list loads in flight together, then all LDS reads (np_nsrc <= 6, checked at load)
 #pragma unroll
@@ -2262,7 +2304,10 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
 #pragma unroll
     for (int pass = 0; pass < 2; pass++) {
       const int i = pass * (G / 16) + slot;
-      if (i < nnp) ACC[q * NB + m->np_body[i]] = t[pass];
+      if (i < nnp) {
+        if (PRE && pass == 0) lds_at(ACC + q * NB, (int)(((unsigned)np1 >> 16) & 0xFFu)) = t[pass];
+        else ACC[q * NB + m->np_body[i]] = t[pass];
+      }
     }
     ODK_SYNC();
   }
@@ -2399,7 +2444,7 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
   float fR[2][9], fP[2][3];
 #pragma unroll
   for (int f = 0; f < 2; f++) {
-    const int fb = m->foot_body[f];
+    const int fb = PRE ? (f ? hot_value(hpk, HOT_FOOT_BODY1) : hot_value(hpk, HOT_FOOT_BODY0)) : m->foot_body[f];
     float q[4];
     for (int k = 0; k < 4; k++) q[k] = XQUAT[k * NB + fb];
     for (int k = 0; k < 3; k++) fP[f][k] = XPOS[k * NB + fb];
@@ -2409,17 +2454,17 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
     // height-field floor (rough terrain; its own kernel instantiation): prisms of the cells under each foot, out of line
     if constexpr (HF == 2) { hfield_prim_floor<S, G>(L, m, hfield, lane); ODK_SYNC(); prim_contacts<S, G>(L, m, lane, false); }   // floor, then foot against foot
     else hfield_contacts<S, G>(L, m, hfield, lane);
-  } else if (m->foot_prim) {
+  } else if (ODK_HOTI(HOT_FOOT_PRIM, m->foot_prim)) {
     prim_contacts<S, G>(L, m, lane, true);   // sphere / capsule feet (model-uniform branch): floor and foot-foot contacts, out of line
   } else {
-  const float pn0[3] = {m->plane_n[0], m->plane_n[1], m->plane_n[2]};
+  const float pn0[3] = {ODK_HOTF(HOT_F_PLN, m->plane_n[0]), ODK_HOTF(HOT_F_PLN + 1, m->plane_n[1]), ODK_HOTF(HOT_F_PLN + 2, m->plane_n[2])};
   {
     // both feet at once: foot f = 16-lane row f of the env's lanes (vertices 0..15), the 17th vertex rides along in every lane
     const int f = (lane >> 4) & 1, j = lane & 15;
-    const int nvt = m->foot_nvert[f];
+    const int nvt = PRE ? (f ? hot_value(hpk, HOT_FOOT_NVERT1) : hot_value(hpk, HOT_FOOT_NVERT0)) : m->foot_nvert[f];
     const bool inrow = lane < 32;                    // G = 64: rows 2, 3 idle
     const bool has = inrow && j < nvt, has_e = inrow && nvt > 16;
-    float pn[3] = {pn0[0], pn0[1], pn0[2]}, pp[3] = {m->plane_pos[0], m->plane_pos[1], m->plane_pos[2]};
+    float pn[3] = {pn0[0], pn0[1], pn0[2]}, pp[3] = {ODK_HOTF(HOT_F_PLP, m->plane_pos[0]), ODK_HOTF(HOT_F_PLP + 1, m->plane_pos[1]), ODK_HOTF(HOT_F_PLP + 2, m->plane_pos[2])};
     float Rf[9], Pf[3];
 #pragma unroll
     for (int k = 0; k < 9; k++) Rf[k] = f ? fR[1][k] : fR[0][k];
@@ -2430,7 +2475,8 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
       const int jv = has ? j : 0;
       float vb[3];
       if constexpr (PRE) { vb[0] = hot.vb[0]; vb[1] = hot.vb[1]; vb[2] = hot.vb[2]; } else { vb[0] = m->foot_vert[f][jv][0]; vb[1] = m->foot_vert[f][jv][1]; vb[2] = m->foot_vert[f][jv][2]; }
-      const float ve[3] = {m->foot_vert[f][16][0], m->foot_vert[f][16][1], m->foot_vert[f][16][2]};
+      float ve[3];
+      if constexpr (PRE) { ve[0] = hot.ve[0]; ve[1] = hot.ve[1]; ve[2] = hot.ve[2]; } else { ve[0] = m->foot_vert[f][16][0]; ve[1] = m->foot_vert[f][16][1]; ve[2] = m->foot_vert[f][16][2]; }
 #pragma unroll
       for (int k = 0; k < 3; k++) {
         w[k] = Pf[k] + Rf[3 * k] * vb[0] + Rf[3 * k + 1] * vb[1] + Rf[3 * k + 2] * vb[2];
@@ -2460,17 +2506,17 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
   ODK_PROF(7);
   // foot-foot: bounding spheres first (a positive gap already means "inactive pair"); only when the spheres of some env
   // in the wave touch: oriented-box cull, 15 axes on 15 lanes (a positive box separation bounds the hulls' from below)
-  if (!m->foot_prim) {
+  if (!ODK_HOTI(HOT_FOOT_PRIM, m->foot_prim)) {
     float sep = -3.0e38f;
     float sph;
     {
       float dc[3];
       for (int k = 0; k < 3; k++) {
-        const float a1 = fP[0][k] + fR[0][3 * k] * m->foot_obb_center[0][0] + fR[0][3 * k + 1] * m->foot_obb_center[0][1] + fR[0][3 * k + 2] * m->foot_obb_center[0][2];
-        const float a2 = fP[1][k] + fR[1][3 * k] * m->foot_obb_center[1][0] + fR[1][3 * k + 1] * m->foot_obb_center[1][1] + fR[1][3 * k + 2] * m->foot_obb_center[1][2];
+        const float a1 = fP[0][k] + fR[0][3 * k] * ODK_OBBC(0, 0) + fR[0][3 * k + 1] * ODK_OBBC(0, 1) + fR[0][3 * k + 2] * ODK_OBBC(0, 2);
+        const float a2 = fP[1][k] + fR[1][3 * k] * ODK_OBBC(1, 0) + fR[1][3 * k + 1] * ODK_OBBC(1, 1) + fR[1][3 * k + 2] * ODK_OBBC(1, 2);
         dc[k] = a2 - a1;
       }
-      sph = sqrtf(dot3(dc, dc)) - m->foot_sphere_r[0] - m->foot_sphere_r[1];
+      sph = sqrtf(dot3(dc, dc)) - ODK_HOTF(HOT_F_SPHR, m->foot_sphere_r[0]) - ODK_HOTF(HOT_F_SPHR + 1, m->foot_sphere_r[1]);
     }
     float boxsep = -3.0e38f;
     if (__builtin_amdgcn_ballot_w64(!(sph > 0.0f)) != 0) {
@@ -2479,7 +2525,7 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
   #pragma unroll
         for (int f = 0; f < 2; f++) {
           float* cc = f ? c2 : c1; float* AA = f ? A2 : A1;
-          for (int k = 0; k < 3; k++) cc[k] = fP[f][k] + fR[f][3 * k] * m->foot_obb_center[f][0] + fR[f][3 * k + 1] * m->foot_obb_center[f][1] + fR[f][3 * k + 2] * m->foot_obb_center[f][2];
+          for (int k = 0; k < 3; k++) cc[k] = fP[f][k] + fR[f][3 * k] * ODK_OBBC(f, 0) + fR[f][3 * k + 1] * ODK_OBBC(f, 1) + fR[f][3 * k + 2] * ODK_OBBC(f, 2);
           for (int i = 0; i < 3; i++)
             for (int j = 0; j < 3; j++) AA[3 * i + j] = fR[f][3 * i] * m->foot_obb_axes[f][j] + fR[f][3 * i + 1] * m->foot_obb_axes[f][3 + j] + fR[f][3 * i + 2] * m->foot_obb_axes[f][6 + j];
         }
@@ -2666,7 +2712,7 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
   // foot-foot rows (32..47) are skipped wave-wide unless some env has a penetrating foot-foot contact (D = 0 rows
   // are never read again: the solver gates on D > 0 and on the same wave-uniform flag)
   const bool ff_rows = __builtin_amdgcn_ballot_w64(fminf(fminf(CDIST[8], CDIST[9]), fminf(CDIST[10], CDIST[11])) < 0.0f) != 0;
-  const bool prim_feet = !HF && m->foot_prim != 0;   // sphere / capsule feet: per-contact frames in S_FR (prim_contacts)
+  const bool prim_feet = !HF && ODK_HOTI(HOT_FOOT_PRIM, m->foot_prim) != 0;   // sphere / capsule feet: per-contact frames in S_FR (prim_contacts)
   const bool ell = S::CONE || (S::ELL && m->cone != 0);   // (wave-uniform; a compile-time constant for the duck's cone instantiations) elliptic friction cones
   for (int rc = lane; rc < S::NCROW; rc += G) {
     const int r = r0c + rc, c = rc >> 2, s = rc & 3, pair = c >> 2;
@@ -2693,11 +2739,11 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
     float D = 0, aref = 0;
     if (dist < 0) {
       float vel = 0;
-      const int b2 = m->foot_body[pair == 0 ? 0 : 1];  // geom2's body: left foot for pair 0, right foot otherwise
+      const int b2 = PRE ? (pair == 0 ? hot_value(hpk, HOT_FOOT_BODY0) : hot_value(hpk, HOT_FOOT_BODY1)) : m->foot_body[pair == 0 ? 0 : 1];  // geom2's body: left foot for pair 0, right foot otherwise
 #pragma unroll
       for (int k = 0; k < 6; k++) vel += wr[k] * CVEL[k * NB + b2];
       if (pair == 2) {
-        const int b1 = m->foot_body[0];
+        const int b1 = ODK_HOTI(HOT_FOOT_BODY0, m->foot_body[0]);
 #pragma unroll
         for (int k = 0; k < 6; k++) vel -= wr[k] * CVEL[k * NB + b1];
       }
@@ -2739,7 +2785,7 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
   auto foot_twist = [&](const float* V, int k, int f) -> float {
     float s = 0;
     if constexpr (S::CL > 0) {
-      const int c0 = f ? m->foot_rchain_first[1] : m->foot_rchain_first[0], cl = f ? m->foot_rchain_len[1] : m->foot_rchain_len[0];
+      const int c0 = f ? ODK_HOTI(HOT_RCHAIN_FIRST1, m->foot_rchain_first[1]) : ODK_HOTI(HOT_RCHAIN_FIRST0, m->foot_rchain_first[0]), cl = f ? ODK_HOTI(HOT_RCHAIN_LEN1, m->foot_rchain_len[1]) : ODK_HOTI(HOT_RCHAIN_LEN0, m->foot_rchain_len[0]);
       const float* cd = CDOF + k * NR;
 #pragma unroll
       for (int t = 0; t < 6; t++) s += cd[t] * V[t];
@@ -3034,7 +3080,7 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
     // 11 per foot at most.  Lane 11 f + idx computes column idx of foot f (36 FMAs) instead of every dof lane doing both
     // feet (72); the other columns of BUF6 / BUF6B are never read (hess_entry tests the foot masks).
     const int f = lane >= 6 + S::CL ? 1 : 0, idx = lane - (6 + S::CL) * f;
-    const int c0 = f ? m->foot_rchain_first[1] : m->foot_rchain_first[0], cl = f ? m->foot_rchain_len[1] : m->foot_rchain_len[0];
+    const int c0 = f ? ODK_HOTI(HOT_RCHAIN_FIRST1, m->foot_rchain_first[1]) : ODK_HOTI(HOT_RCHAIN_FIRST0, m->foot_rchain_first[0]), cl = f ? ODK_HOTI(HOT_RCHAIN_LEN1, m->foot_rchain_len[1]) : ODK_HOTI(HOT_RCHAIN_LEN0, m->foot_rchain_len[0]);
     const bool lane_on = lane < 2 * (6 + S::CL) && idx - 6 < cl;
     const int col = lane_on ? (idx < 6 ? idx : c0 + idx - 6) : 0;
     const bool on = lane_on && ((f ? c_act[1] : c_act[0]) || c_act[2]);
@@ -3252,7 +3298,7 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
       }
     }
   }
-  const float gtol = m->tolerance * m->ls_tolerance * sqrtf(sn) * m->meaninertia * (float)(NV > 1 ? NV : 1);
+  const float gtol = ODK_HOTF(HOT_F_TOL, m->tolerance) * ODK_HOTF(HOT_F_LSTOL, m->ls_tolerance) * sqrtf(sn) * ODK_HOTF(HOT_F_MEANI, m->meaninertia) * (float)(NV > 1 ? NV : 1);
   // Three step sizes at once.  The bracketing iterations only steer on the first and second derivative along the search, so
   // they evaluate those alone (COST = false: two sums per step size); the costs that pick the final step -- at lo, hi and 0 --
   // are one evaluation at the end (COST = true: one sum per step size, the quadratic combined per lane before the reduction).
@@ -3354,7 +3400,7 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
   if (e0[0] < p0_d0) { lo_a = al[0]; lo_d0 = e0[0]; lo_d1 = e1[0]; hi_a = 0; hi_d0 = p0_d0; hi_d1 = p0_d1; }
   else { hi_a = al[0]; hi_d0 = e0[0]; hi_d1 = e1[0]; lo_a = 0; lo_d0 = p0_d0; lo_d1 = p0_d1; }
   bool swap = true;
-  for (int it = 0; it < m->ls_iterations; it++) {
+  for (int it = 0; it < ODK_HOTI(HOT_LS_ITERATIONS, m->ls_iterations); it++) {   // (PRE: a scalar extract, never a load inside the line search)
     bool done = !swap || (lo_d0 < 0 && lo_d0 > -gtol) || (hi_d0 > 0 && hi_d0 < gtol);
     if (done) break;
     al[0] = lo_a - sdiv(lo_d0, lo_d1); al[1] = hi_a - sdiv(hi_d0, hi_d1); al[2] = 0.5f * (lo_a + hi_a);

@@ -28,6 +28,8 @@ constexpr int MAXSITE = 8;
 constexpr int MAXSENS = 16;
 constexpr int NCON = 12;     // 3 geom pairs x 4 contacts
 constexpr int NSENSD = 46;
+constexpr int HOT_NPK = 3, HOT_NF = 17;   // DevModel::hot_pk / hot_f
+constexpr int HOT_F_OBBC = 0, HOT_F_SPHR = 6, HOT_F_PLN = 8, HOT_F_PLP = 11, HOT_F_TOL = 14, HOT_F_LSTOL = 15, HOT_F_MEANI = 16;
 
 // Per-body constants of the kinematics / inertia sweeps, one record per LANE of an env (body-to-lane layout: every serial body
 // chain in consecutive lanes of one 16-lane row, so its scans are DPP row shifts; lanes without a body hold a "no body" record),
@@ -183,7 +185,25 @@ struct DevModel {
   float eq_poly[EQ_MAX][5], eq_imp[EQ_MAX][9], eq_invweight[EQ_MAX];
   // observation layouts, [0] Joystick, [1] Standing (last: every older field keeps its offset)
   alignas(16) ObsEnt obs_tab[2][OBS_MAX];
+  // Launch-invariant values the substep reads, packed at load (odk_model_load.hip pack_hot) so that the plane-floor step kernel takes them
+  // once per launch (odk_kernels.h load_hot / HotSt) instead of by a vector load a few instructions before its wait in every substep.
+  // (Behind every older field, as obs_tab was.)  Offsets that only feed an LDS address are stored as BYTE offsets (index * 4).
+  int hot_pk[HOT_NPK];      // wave-uniform small integers: the HOT_* fields below
+  int np_rec[64][2];        // per lane of an env, the subtree fold's pass-0 record of body i = lane >> 4 (zeros: no such body): [0] np_src[i][0..3] * 4, a byte
+                            // each; [1] np_src[i][4] * 4 | np_src[i][5] * 4 << 8 | np_body[i] * 4 << 16 | np_nsrc[i] << 24
+  float hot_f[HOT_NF];      // foot_obb_center[2][3] | foot_sphere_r[2] | plane_n[3] | plane_pos[3] | tolerance | ls_tolerance | meaninertia
 };
+// A field of hot_pk: word, first bit, width, and whether the stored value is the byte offset (value * 4)
+struct HotField { const char* name; int word, shift, bits, scale; };
+constexpr HotField HOT_FOOT_BODY0 = {"foot_body[0]", 0, 0, 8, 4}, HOT_FOOT_BODY1 = {"foot_body[1]", 0, 8, 8, 4};
+constexpr HotField HOT_FOOT_NVERT0 = {"foot_nvert[0]", 0, 16, 8, 1}, HOT_FOOT_NVERT1 = {"foot_nvert[1]", 0, 24, 8, 1};
+constexpr HotField HOT_RCHAIN_FIRST0 = {"foot_rchain_first[0]", 1, 0, 8, 4}, HOT_RCHAIN_FIRST1 = {"foot_rchain_first[1]", 1, 8, 8, 4};
+constexpr HotField HOT_RCHAIN_LEN0 = {"foot_rchain_len[0]", 1, 16, 4, 1}, HOT_RCHAIN_LEN1 = {"foot_rchain_len[1]", 1, 20, 4, 1};
+constexpr HotField HOT_LS_ITERATIONS = {"ls_iterations", 1, 24, 8, 1};
+constexpr HotField HOT_NP_LEVELS = {"max_nonpath_level + 1", 2, 0, 8, 1}, HOT_NP_COUNT = {"np_count", 2, 8, 8, 1}, HOT_FOOT_PRIM = {"foot_prim", 2, 16, 8, 1};
+// the value of a field, on either side (hot_stored: as stored, the byte offset of a scaled one)
+constexpr unsigned hot_stored(const int* pk, const HotField& f) { return ((unsigned)pk[f.word] >> f.shift) & ((1u << f.bits) - 1u); }
+constexpr int hot_value(const int* pk, const HotField& f) { return (int)(hot_stored(pk, f) / (unsigned)f.scale); }
 
 // Topology of a height-field prism (vertices 0..2 = top triangle counter-clockwise seen from above, 3..5 below them; faces: top,
 // bottom, the sides over the edges 0-1, 1-2, 2-0): unique edges (va, vb, face running va -> vb, face running vb -> va) and face

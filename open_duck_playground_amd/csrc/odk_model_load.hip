@@ -987,7 +987,51 @@ int build_statics(Load& c) {
 #undef X
   return 0;
 }
+
+// the launch-invariant values of the substep in their packed form (DevModel::hot_pk / np_rec / hot_f): a value that does not fit its field is refused by name
+int pack_hot(Load& c) {
+  DevModel& m = c.m;
+  const struct { const HotField& f; int v; } fields[] = {
+      {HOT_FOOT_BODY0, m.foot_body[0]},         {HOT_FOOT_BODY1, m.foot_body[1]},         {HOT_FOOT_NVERT0, m.foot_nvert[0]},     {HOT_FOOT_NVERT1, m.foot_nvert[1]},
+      {HOT_RCHAIN_FIRST0, m.foot_rchain_first[0]}, {HOT_RCHAIN_FIRST1, m.foot_rchain_first[1]}, {HOT_RCHAIN_LEN0, m.foot_rchain_len[0]}, {HOT_RCHAIN_LEN1, m.foot_rchain_len[1]},
+      {HOT_LS_ITERATIONS, m.ls_iterations},     {HOT_NP_LEVELS, m.max_nonpath_level + 1}, {HOT_NP_COUNT, m.np_count},             {HOT_FOOT_PRIM, m.foot_prim}};
+  for (int k = 0; k < HOT_NPK; k++) m.hot_pk[k] = 0;
+  for (const auto& e : fields) {
+    const long long stored = (long long)e.v * e.f.scale;
+    if (e.v < 0 || stored >= (1ll << e.f.bits))
+      return fail(ODK_ERR_UNSUPPORTED, "%s = %d does not fit the %d-bit field the step kernels read it from (0 .. %d)", e.f.name, e.v, e.f.bits,
+                  (int)(((1ll << e.f.bits) - 1) / e.f.scale));
+    m.hot_pk[e.f.word] |= (int)((unsigned)stored << e.f.shift);
+  }
+  for (int lane = 0; lane < 64; lane++) {
+    const int i = lane >> 4;
+    unsigned r0 = 0, r1 = 0;
+    if (i < m.np_count) {
+      const int* s = m.np_src[i];      // (bodies: < MAXB = 20, so every byte offset is below 80)
+      r0 = (unsigned)(s[0] * 4) | (unsigned)(s[1] * 4) << 8 | (unsigned)(s[2] * 4) << 16 | (unsigned)(s[3] * 4) << 24;
+      r1 = (unsigned)(s[4] * 4) | (unsigned)(s[5] * 4) << 8 | (unsigned)(m.np_body[i] * 4) << 16 | (unsigned)m.np_nsrc[i] << 24;
+    }
+    m.np_rec[lane][0] = (int)r0; m.np_rec[lane][1] = (int)r1;
+  }
+  for (int f = 0; f < 2; f++) {
+    for (int k = 0; k < 3; k++) m.hot_f[HOT_F_OBBC + 3 * f + k] = m.foot_obb_center[f][k];
+    m.hot_f[HOT_F_SPHR + f] = m.foot_sphere_r[f];
+  }
+  for (int k = 0; k < 3; k++) { m.hot_f[HOT_F_PLN + k] = m.plane_n[k]; m.hot_f[HOT_F_PLP + k] = m.plane_pos[k]; }
+  m.hot_f[HOT_F_TOL] = m.tolerance; m.hot_f[HOT_F_LSTOL] = m.ls_tolerance; m.hot_f[HOT_F_MEANI] = m.meaninertia;
+  return 0;
+}
 }  // namespace
+
+extern "C" int odk_model_hot_words(const odk_model* m, int* packed, int* fields) {
+  if (!m || !packed || !fields) return fail(ODK_ERR_INVALID, "odk_model_hot_words: bad arguments");
+  const DevModel& h = m->h;
+  for (int k = 0; k < HOT_NPK; k++) packed[k] = h.hot_pk[k];
+  const int v[12] = {h.foot_body[0], h.foot_body[1], h.foot_nvert[0], h.foot_nvert[1], h.foot_rchain_first[0], h.foot_rchain_first[1], h.foot_rchain_len[0], h.foot_rchain_len[1],
+                     h.ls_iterations, h.max_nonpath_level, h.np_count, h.foot_prim};
+  for (int k = 0; k < 12; k++) fields[k] = v[k];
+  return ODK_OK;
+}
 
 extern "C" int odk_model_load(const void* blob, uint64_t len, odk_model** out) {
   if (!blob || !out || len < 16 || memcmp(blob, "ODKM", 4) != 0) return fail(ODK_ERR_INVALID, "odk_model_load: not an ODKM blob");
@@ -997,7 +1041,8 @@ extern "C" int odk_model_load(const void* blob, uint64_t len, odk_model** out) {
   memset(&mo->h, 0, sizeof(mo->h));   // (padding too: the same blob always gives the same bytes)
   Load c{B, *mo, mo->h};
   int (*const stages[])(Load&) = {load_options, collect_equalities, load_tree,        load_actuators, load_rows,       load_feet,
-                                  load_floor,   load_sensors,       build_fold_lists, select_shape,   load_equalities, build_statics};
+                                  load_floor,   load_sensors,       build_fold_lists, select_shape,   load_equalities, build_statics,
+                                  pack_hot};
   for (auto stage : stages)
     if (const int err = stage(c)) return err;
   *out = mo.release();

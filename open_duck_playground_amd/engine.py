@@ -448,6 +448,27 @@ def model_reduction(model: Model) -> Dict:
         L.odk_model_free(h)
 
 
+HOT_FIELD_NAMES = ("foot_body0", "foot_body1", "foot_nvert0", "foot_nvert1", "foot_rchain_first0", "foot_rchain_first1", "foot_rchain_len0", "foot_rchain_len1",
+                   "ls_iterations", "max_nonpath_level", "np_count", "foot_prim")
+
+
+def model_hot_words(model: Model) -> Dict:
+    """The packed words the plane-floor step kernel reads the model's launch-invariant small integers from, and the values they were
+    packed from (odk_model_hot_words); host-only, no GPU."""
+    L = load_library()
+    L.odk_model_hot_words.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.odk_model_hot_words.restype = C.c_int
+    blob = model.blob()
+    h = C.c_void_p()
+    _chk(L.odk_model_load(blob, len(blob), C.byref(h)))
+    try:
+        packed, fields = (C.c_int * 3)(), (C.c_int * 12)()
+        _chk(L.odk_model_hot_words(h, packed, fields))
+        return dict(packed=[v & 0xFFFFFFFF for v in packed], fields=dict(zip(HOT_FIELD_NAMES, list(fields))))
+    finally:
+        L.odk_model_free(h)
+
+
 def model_body_lanes(model: Model, lanes_per_env: int) -> List[int]:
     """Body id of each of an env's `lanes_per_env` lanes in the kinematics / inertia sweeps, -1 for a lane without a body
     (odk_model_body_lanes); host-only, no GPU."""
