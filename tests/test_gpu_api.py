@@ -293,17 +293,19 @@ def test_evaluator_graph_replay_matches_plain_launches():
     assert a["eval/avg_episode_length"] <= 60 and a["eval/episode_reward"] > 0
 
 
-def test_lanes64_geometry_matches_default():
+@pytest.mark.parametrize("task", ["flat_terrain", "flat_terrain_backlash"])
+def test_lanes64_geometry_matches_default(task):
     """64 lanes per env (one env per wavefront) runs the same env step as the default 32-lane geometry: only the
     summation orders differ."""
     import torch
     from open_duck_playground_amd import engine
     from open_duck_playground_amd.model import load_task_model
-    model = load_task_model("flat_terrain")
+    model = load_task_model(task)
     outs = []
     for lanes in (32, 64):
         cfg = engine.default_config(); cfg.lanes_per_env = lanes
         b = engine.Batch(model, 40, cfg)
+        assert b.lanes_per_env == lanes, (task, lanes, b.lanes_per_env)
         b.reset(seed=3)
         g = torch.Generator(device="cuda").manual_seed(1)
         for _ in range(6):

@@ -4,7 +4,7 @@ env agrees with the CPU oracle env driven by the same command; a captured step g
 import numpy as np
 import pytest
 
-from test_gpu_env import ENV_BOUNDS, RESET_BOUNDS, SET_ASIDE, _ill_resets, _mk, _new_W, _errs, _obs_err, _resync, _step_and_compare
+from test_gpu_env import ENV_BOUNDS, RESET_BOUNDS, SET_ASIDE, _ids, _ill_resets, _lt, _mk, _new_W, _errs, _obs_err, _resync, _step_and_compare
 
 pytestmark = pytest.mark.gpu
 
@@ -134,14 +134,17 @@ def test_binding_moves_nothing_but_the_command(task, standing, dr):
     bu.close(); bb.close()
 
 
-@pytest.mark.parametrize("task,standing", [("flat_terrain", False), ("flat_terrain_backlash", False), ("flat_terrain", True)])
-def test_bound_commands_match_the_oracle_env(oracle_mod, parity_log, task, standing):
+BOUND_CASES = [("flat_terrain", False, 0), ("flat_terrain_backlash", False, 0), ("flat_terrain", True, 0), ("flat_terrain_backlash", False, 64)]
+
+
+@pytest.mark.parametrize("task,standing,lanes", BOUND_CASES, ids=_ids(BOUND_CASES))
+def test_bound_commands_match_the_oracle_env(oracle_mod, parity_log, task, standing, lanes):
     """The oracle env gets the bound row written into its `command` before every step (after reset: into its first observation's command
     slots as well, the auto-reset hands those back).  Reset: command slots equal the row, the rest within the reset bounds; steps: the
-    existing parity bounds and set-aside rules."""
+    existing parity bounds and set-aside rules.  The 64-lane case (one env per wave) is the kernel `track` runs its reports on."""
     def edit(cfg):
         cfg.episode_length = 25
-    torch, model, b, envs, keep = _mk(oracle_mod, task, 32, edit, standing=standing)
+    torch, model, b, envs, keep = _mk(oracle_mod, task, 32, edit, standing=standing, lanes=lanes)
     n = len(envs)
     nobs, npriv = b.nobs, b.npriv
     rows = _rows(n, 11, b.cfg)
@@ -181,7 +184,7 @@ def test_bound_commands_match_the_oracle_env(oracle_mod, parity_log, task, stand
         np.testing.assert_array_equal(b.obs.cpu().numpy()[:, CMD], rows)
     assert W["n_done"] > 0
     b.close()
-    tag = f"bound_commands/{task}/{'standing' if standing else 'joystick'}"
+    tag = f"bound_commands/{task}/{'standing' if standing else 'joystick'}{_lt(lanes)}"
     parity_log.check(tag + "/reset", dict(obs=RESET_BOUNDS["obs"], acc=RESET_BOUNDS["acc"]), **WR)
     parity_log.check(tag, {**ENV_BOUNDS, **SET_ASIDE}, **_errs(W))
 

@@ -48,6 +48,25 @@ def _set_aside(task):
     return SET_ASIDE_ROUGH if "rough" in task else SET_ASIDE
 
 
+# The two duck models' env kernels at 64 lanes per env (one env per wave: what `make_eval_env` and `track` run up to 1024 envs), added to a test's
+# cases with its 32-lane sibling's sizes, seeds and bounds.  `lanes` 0 is the engine's default (32); the existing cases keep their test ids and
+# parity keys, the 64-lane ones carry "lanes64" in both.
+LANES64 = [("flat_terrain", 64), ("flat_terrain_backlash", 64)]
+
+
+def _with_lanes64(tasks):
+    return [(t, 0) for t in tasks] + LANES64
+
+
+def _ids(cases):
+    """test ids of cases whose last entry is the lane count: the other entries as pytest joins them, then "-lanes64" where one is asked for"""
+    return ["-".join(str(x) for x in c[:-1]) + (f"-lanes{c[-1]}" if c[-1] else "") for c in cases]
+
+
+def _lt(lanes):
+    return f"/lanes{lanes}" if lanes else ""
+
+
 def _ill_resets(envs, model, nobs):
     """envs whose reset-time forward pass sits on a contact tie: the oracle's own accelerometer at the reset state moves by more
     than half the bound under 1e-6 noise on qpos.  Their first observation (which auto-reset hands back later) is not judged on
@@ -76,8 +95,9 @@ def _xml_model(xml):
     return Model.from_xml(os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets", xml), sim_dt=0.002)
 
 
-def _mk(oracle_mod, task, n, cfg_edit=None, standing=False, dr_fields=None, model_edit=None):
-    """`task`: a shipped task name, or the file name of a robot under tests/assets/ (a robot that is not the duck: no imitation reward)"""
+def _mk(oracle_mod, task, n, cfg_edit=None, standing=False, dr_fields=None, model_edit=None, lanes=0):
+    """`task`: a shipped task name, or the file name of a robot under tests/assets/ (a robot that is not the duck: no imitation reward); `n`: the
+    env count; `lanes`: lanes per env asked of the engine (0: its default) -- a hint to it, so a batch that does not run at that count fails here"""
     import torch
     from open_duck_playground_amd import engine, randomize
     from open_duck_playground_amd.model import load_task_model
@@ -91,7 +111,10 @@ def _mk(oracle_mod, task, n, cfg_edit=None, standing=False, dr_fields=None, mode
         cfg.use_imitation = 0
     if cfg_edit:
         cfg_edit(cfg)
+    if lanes:
+        cfg.lanes_per_env = lanes
     b = engine.Batch(model, n, cfg)
+    assert not lanes or b.lanes_per_env == lanes, (task, lanes, b.lanes_per_env)
     base = oracle_mod.OracleModel(model.blob())
     prm = oracle_mod.OraclePRM(engine.load_prm())
     oms = [base] * n
@@ -405,9 +428,12 @@ def _errs(W):
     return out
 
 
-@pytest.mark.parametrize("task", ["flat_terrain", "flat_terrain_backlash"])
-def test_reset_matches_oracle(oracle_mod, parity_log, task):
-    torch, model, b, envs, keep = _mk(oracle_mod, task, 32)
+RESET_CASES = _with_lanes64(["flat_terrain", "flat_terrain_backlash"])
+
+
+@pytest.mark.parametrize("task,lanes", RESET_CASES, ids=_ids(RESET_CASES))
+def test_reset_matches_oracle(oracle_mod, parity_log, task, lanes):
+    torch, model, b, envs, keep = _mk(oracle_mod, task, 32, lanes=lanes)
     b.reset(seed=5, env_id_offset=100)
     obs = b.obs.cpu().numpy(); priv = b.priv.cpu().numpy()
     qpos, qvel, warm = b.get_state()
@@ -424,17 +450,20 @@ def test_reset_matches_oracle(oracle_mod, parity_log, task):
         np.testing.assert_allclose(I["command"][i], e["command"], rtol=1e-6, atol=1e-7)
         assert int(I["push_interval_steps"][i]) == int(e.ints("push_interval_steps")[0])
     b.close()
-    parity_log.check(f"reset/{task}", RESET_BOUNDS, **W)
+    parity_log.check(f"reset/{task}{_lt(lanes)}", RESET_BOUNDS, **W)
 
 
-@pytest.mark.parametrize("task", ["flat_terrain", "flat_terrain_backlash", "rough_terrain_backlash"])
-def test_step_sequence_with_resync(oracle_mod, parity_log, task):
+STEP_CASES = _with_lanes64(["flat_terrain", "flat_terrain_backlash", "rough_terrain_backlash"])
+
+
+@pytest.mark.parametrize("task,lanes", STEP_CASES, ids=_ids(STEP_CASES))
+def test_step_sequence_with_resync(oracle_mod, parity_log, task, lanes):
     """60 env steps with random actions.  The physics state is re-synchronised from the oracle before every
     step (fp32-vs-fp64 chaos through contact would otherwise dominate), everything else -- info ring
     buffers, RNG counters, episode counters, auto-reset -- runs free on the GPU."""
     def edit(cfg):
         cfg.episode_length = 25   # exercise truncation + auto-reset
-    torch, model, b, envs, keep = _mk(oracle_mod, task, 32, edit)
+    torch, model, b, envs, keep = _mk(oracle_mod, task, 32, edit, lanes=lanes)
     n = len(envs)
     b.reset(seed=9)
     for i, e in enumerate(envs):
@@ -454,7 +483,7 @@ def test_step_sequence_with_resync(oracle_mod, parity_log, task):
         assert int(I["rng"][i, 2]) == int(e.ints("rng_ctr")[0])
         assert int(I["imitation_i"][i]) == int(e.ints("imitation_i")[0])
     b.close()
-    parity_log.check(f"env_step/{task}", {**ENV_BOUNDS, **_set_aside(task)}, **_errs(W))
+    parity_log.check(f"env_step/{task}{_lt(lanes)}", {**ENV_BOUNDS, **_set_aside(task)}, **_errs(W))
 
 
 @pytest.mark.parametrize("task", ["flat_terrain", "flat_terrain_backlash", "rough_terrain_backlash"])
@@ -481,12 +510,12 @@ def test_step_sequence_of_the_duck_with_elliptic_cones(oracle_mod, parity_log, t
     parity_log.check(f"env_step_elliptic/{task}", {**ENV_BOUNDS, **_set_aside(task)}, **_errs(W))
 
 
-@pytest.mark.parametrize("task", ["flat_terrain", "flat_terrain_backlash"])
-def test_in_step_command_resample(oracle_mod, parity_log, task):
+@pytest.mark.parametrize("task,lanes", RESET_CASES, ids=_ids(RESET_CASES))
+def test_in_step_command_resample(oracle_mod, parity_log, task, lanes):
     """sample_command inside step (joystick.py:456-466): info["step"] is preset to 499 / 500 / 123 on both sides through the raw
     record; the step that takes it past 500 must draw the same new command (same counter-RNG draws, incl. the all-zero
     branch) and reset the counter to 0, the others keep theirs, and the next step's obs carry the new command."""
-    torch, model, b, envs, keep = _mk(oracle_mod, task, 64)
+    torch, model, b, envs, keep = _mk(oracle_mod, task, 64, lanes=lanes)      # (64 ENVS; the lane count is the keyword)
     n = len(envs)
     b.reset(seed=13)
     for i, e in enumerate(envs):
@@ -520,12 +549,16 @@ def test_in_step_command_resample(oracle_mod, parity_log, task):
                 assert int(e.ints("step")[0]) == 0
     assert n_resampled >= n // 2 - 1 and W["n_done"] < n // 2
     b.close()
-    parity_log.rec(f"command_resample/{task}", None, resampled=n_resampled, all_zero_draws=n_zero)
-    parity_log.check(f"command_resample/{task}", {**ENV_BOUNDS, **SET_ASIDE}, **_errs(W))
+    parity_log.rec(f"command_resample/{task}{_lt(lanes)}", None, resampled=n_resampled, all_zero_draws=n_zero)
+    parity_log.check(f"command_resample/{task}{_lt(lanes)}", {**ENV_BOUNDS, **SET_ASIDE}, **_errs(W))
 
 
-@pytest.mark.parametrize("task,standing", [("flat_terrain_backlash", False), ("flat_terrain", False), ("rough_terrain_backlash", False), ("flat_terrain_backlash", True)])
-def test_env_step_with_domain_randomisation(oracle_mod, parity_log, task, standing):
+DR_CASES = [("flat_terrain_backlash", False, 0), ("flat_terrain", False, 0), ("rough_terrain_backlash", False, 0), ("flat_terrain_backlash", True, 0),
+            ("flat_terrain_backlash", False, 64), ("flat_terrain", False, 64)]
+
+
+@pytest.mark.parametrize("task,standing,lanes", DR_CASES, ids=_ids(DR_CASES))
+def test_env_step_with_domain_randomisation(oracle_mod, parity_log, task, standing, lanes):
     """randomize.py's per-env model fields through odk_reset / odk_step (not only the physics call): reset obs, then 30
     resynchronised env steps, obs / reward / metrics against oracle envs that each own a randomised copy of the model."""
     from open_duck_playground_amd import randomize
@@ -535,7 +568,7 @@ def test_env_step_with_domain_randomisation(oracle_mod, parity_log, task, standi
 
     def edit(cfg):
         cfg.episode_length = 20
-    torch, model, b, envs, keep = _mk(oracle_mod, task, n, edit, standing=standing, dr_fields=fields)
+    torch, model, b, envs, keep = _mk(oracle_mod, task, n, edit, standing=standing, dr_fields=fields, lanes=lanes)
     nobs, npriv = (85, 153) if standing else (101, 212)
     b.reset(seed=21)
     obs = b.obs.cpu().numpy(); priv = b.priv.cpu().numpy()
@@ -554,7 +587,7 @@ def test_env_step_with_domain_randomisation(oracle_mod, parity_log, task, standi
         act = rng.uniform(-1, 1, (n, 14)).astype(np.float32)
         _step_and_compare(torch, b, envs, act, nobs, npriv, t, W)
     b.close()
-    tag = f"env_step_dr/{task}/{'standing' if standing else 'joystick'}"
+    tag = f"env_step_dr/{task}/{'standing' if standing else 'joystick'}{_lt(lanes)}"
     parity_log.check(tag + "/reset", dict(obs=RESET_BOUNDS["obs"], acc=RESET_BOUNDS["acc"]), **WR)
     parity_log.check(tag, {**ENV_BOUNDS, **_set_aside(task)}, **_errs(W))
 
@@ -568,18 +601,21 @@ def test_domain_randomisation_changes_the_env_step(oracle_mod):
     model = load_task_model("flat_terrain_backlash")
     n = 32
     fields, _ = randomize.domain_randomize(model, np.random.default_rng(17), n)
-    outs = []
-    for dr in (False, True):
-        b = engine.Batch(model, n)
-        if dr:
-            randomize.apply(b, fields)
-        b.reset(seed=21)
-        g = torch.Generator(device="cuda").manual_seed(0)
-        for _ in range(3):
-            b.step(torch.empty(n, 14, device="cuda").uniform_(-1, 1, generator=g))
-        outs.append((b.priv.clone(), b.reward.clone()))
-        b.close()
-    assert float((outs[0][0] - outs[1][0]).abs().max()) > 1e-2 and float((outs[0][1] - outs[1][1]).abs().max()) > 1e-4
+    for lanes in (32, 64):      # the per-env block is loaded in other passes at 64 lanes per env (one env per wave)
+        outs = []
+        for dr in (False, True):
+            cfg = engine.default_config(); cfg.lanes_per_env = lanes
+            b = engine.Batch(model, n, cfg)
+            assert b.lanes_per_env == lanes, (lanes, b.lanes_per_env)
+            if dr:
+                randomize.apply(b, fields)
+            b.reset(seed=21)
+            g = torch.Generator(device="cuda").manual_seed(0)
+            for _ in range(3):
+                b.step(torch.empty(n, 14, device="cuda").uniform_(-1, 1, generator=g))
+            outs.append((b.priv.clone(), b.reward.clone()))
+            b.close()
+        assert float((outs[0][0] - outs[1][0]).abs().max()) > 1e-2 and float((outs[0][1] - outs[1][1]).abs().max()) > 1e-4, lanes
 
 
 def test_free_running_rollout_stays_close(oracle_mod, parity_log):
@@ -607,12 +643,12 @@ def test_free_running_rollout_stays_close(oracle_mod, parity_log):
                      median_qpos_abs=float(np.median(err)), frac_above_5e3=float((err >= 5e-3).mean()), max_qpos_abs=float(err.max()))
 
 
-@pytest.mark.parametrize("task", ["flat_terrain", "flat_terrain_backlash", "rough_terrain_backlash"])
-def test_standing_env_matches_oracle(oracle_mod, parity_log, task):
+@pytest.mark.parametrize("task,lanes", STEP_CASES, ids=_ids(STEP_CASES))
+def test_standing_env_matches_oracle(oracle_mod, parity_log, task, lanes):
     """Standing (reference standing.py): reset + 40 resynchronised steps; obs rows are 85 / 153 floats wide."""
     def edit(cfg):
         cfg.episode_length = 25
-    torch, model, b, envs, keep = _mk(oracle_mod, task, 32, edit, standing=True)
+    torch, model, b, envs, keep = _mk(oracle_mod, task, 32, edit, standing=True, lanes=lanes)
     n = len(envs)
     assert tuple(b.obs.shape) == (n, 85) and tuple(b.priv.shape) == (n, 153)
     b.reset(seed=11)
@@ -636,8 +672,8 @@ def test_standing_env_matches_oracle(oracle_mod, parity_log, task):
         _step_and_compare(torch, b, envs, act, 85, 153, t, W)
     assert W["n_done"] > 0
     b.close()
-    parity_log.check(f"standing/{task}/reset", dict(obs=RESET_BOUNDS["obs"], acc=RESET_BOUNDS["acc"], qvel=RESET_BOUNDS["qvel"]), **WR)
-    parity_log.check(f"standing/{task}", {**ENV_BOUNDS, **_set_aside(task)}, **_errs(W))
+    parity_log.check(f"standing/{task}{_lt(lanes)}/reset", dict(obs=RESET_BOUNDS["obs"], acc=RESET_BOUNDS["acc"], qvel=RESET_BOUNDS["qvel"]), **WR)
+    parity_log.check(f"standing/{task}{_lt(lanes)}", {**ENV_BOUNDS, **_set_aside(task)}, **_errs(W))
 
 
 def test_standing_python_env_surface():

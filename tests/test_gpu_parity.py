@@ -130,7 +130,7 @@ def _oracle_step(O, om, qpos, qvel, warm, ctrl, nsub):
     return d
 
 
-@pytest.mark.parametrize("task,lanes", [("flat_terrain", 32), ("flat_terrain", 64), ("flat_terrain_backlash", 32), ("rough_terrain_backlash", 32)])
+@pytest.mark.parametrize("task,lanes", [("flat_terrain", 32), ("flat_terrain", 64), ("flat_terrain_backlash", 32), ("rough_terrain_backlash", 32), ("flat_terrain_backlash", 64)])
 def test_one_substep_stages(torch_cuda, oracle_mod, parity_log, task, lanes):
     """One mjx.step from random states: every comparable intermediate and the integrated state."""
     from open_duck_playground_amd import engine
@@ -147,6 +147,7 @@ def test_one_substep_stages(torch_cuda, oracle_mod, parity_log, task, lanes):
     ctrl = np.asarray(model.a["key_ctrl"])[None] + rng.uniform(-0.4, 0.4, (n, 14))
     cfg = engine.default_config(); cfg.lanes_per_env = lanes
     b = engine.Batch(model, n, cfg)
+    assert b.lanes_per_env == lanes, (task, lanes, b.lanes_per_env)      # the lane count is a hint: this case did run the kernel it names
     b.set_state(qpos, qvel, warm)
     b.physics_step(torch.tensor(ctrl, dtype=torch.float32, device="cuda"), 1)
     gq, gv, gw = b.get_state()
@@ -441,6 +442,26 @@ def test_height_field_neighbour_with_touching_feet(torch_cuda, oracle_mod, parit
     parity_log.check("hfield_neighbour_touching_feet", dict(dist=6e-7, qpos=1e-5, qvel=4e-5, tie_fraction=0.15), tie_fraction=n_tie / n, **W)
 
 
+# the tasks whose env kernels exist at 64 lanes per env (one env per wave: csrc/odk_shapes.h ODK_ENV_SET_A / _B); the height field runs 32
+LANES64_TASKS = ("flat_terrain", "flat_terrain_backlash")
+
+
+def _ten_substeps_at_64_lanes(torch, model, qpos, qvel, warm, ctrl):
+    """(qpos, qvel) after ten substeps from the given start states through a second batch at 64 lanes per env: judged by the two ten-substep
+    tests against the oracle results, set-aside decisions and bounds of their 32-lane batch (the oracle work does not depend on the lane count)."""
+    from open_duck_playground_amd import engine
+    cfg = engine.default_config(); cfg.lanes_per_env = 64
+    b = engine.Batch(model, len(qpos), cfg)
+    try:
+        assert b.lanes_per_env == 64, b.lanes_per_env
+        b.set_state(qpos, qvel, warm)
+        b.physics_step(torch.tensor(ctrl, dtype=torch.float32, device="cuda"), 10)
+        gq, gv, _ = b.get_state()
+    finally:
+        b.close()
+    return gq, gv
+
+
 @pytest.mark.parametrize("task", ["flat_terrain", "flat_terrain_backlash", "rough_terrain_backlash"])
 def test_env_step_ten_substeps(torch_cuda, oracle_mod, parity_log, task):
     """mjx_env.step (10 substeps) from standing-ish states: state after one env step within 1e-4 relative.  448 states per model
@@ -462,7 +483,9 @@ def test_env_step_ten_substeps(torch_cuda, oracle_mod, parity_log, task):
     b.set_state(qpos, qvel, warm)
     b.physics_step(torch.tensor(ctrl, dtype=torch.float32, device="cuda"), 10)
     gq, gv, _ = b.get_state()
+    g64 = _ten_substeps_at_64_lanes(torch, model, qpos, qvel, warm, ctrl) if task in LANES64_TASKS else None
     wq = wv = wqn = wvn = 0.0
+    W64 = dict(qpos=0.0, qvel=0.0, qpos_normwise=0.0, qvel_normwise=0.0)
     prng = np.random.default_rng(98)
     n_ill = n_classified = 0
     why_ill = {}
@@ -498,13 +521,21 @@ def test_env_step_ten_substeps(torch_cuda, oracle_mod, parity_log, task):
         wq = max(wq, _rel(gq[e], q1, 1e-2).max())
         wv = max(wv, _rel(gv[e], v1, 1.0).max())
         wqn, wvn = max(wqn, _nw(gq[e], q1)), max(wvn, _nw(gv[e], v1))
+        if g64 is not None:      # the one-env-per-wave kernel from the same start state: the same oracle result, the same set-aside decision
+            for k, v in (("qpos", _rel(g64[0][e], q1, 1e-2).max()), ("qvel", _rel(g64[1][e], v1, 1.0).max()), ("qpos_normwise", _nw(g64[0][e], q1)), ("qvel_normwise", _nw(g64[1][e], v1))):
+                W64[k] = max(W64[k], float(v))
     print(task, "10 substeps: worst rel qpos", wq, "qvel", wv, "ill-conditioned:", n_ill, "of", n)
     print(task, "ill-conditioned states by the decision class that moves the oracle's own result (of", n_classified, "examined; a state may name several):", why_ill)
     parity_log.rec(f"ten_substeps/{task}", None, ill_examined=n_classified, **{"ill_by_" + k.split(" ")[0]: v for k, v in why_ill.items()})
     b.close()
     assert n - n_ill >= 150, (n, n_ill)
     parity_log.rec(f"ten_substeps/{task}", None, states=n, judged=n - n_ill)
+    if g64 is not None:
+        print(task, "10 substeps at 64 lanes per env:", W64)
+        parity_log.rec(f"ten_substeps/{task}/lanes64", TEN_BOUNDS, states=n, judged=n - n_ill, **W64)
     parity_log.check(f"ten_substeps/{task}", dict(TEN_BOUNDS, ill_fraction=TEN_ILL_RANDOM[task]), qpos=wq, qvel=wv, qpos_normwise=wqn, qvel_normwise=wvn, ill_fraction=n_ill / n)
+    if g64 is not None:
+        parity_log.check(f"ten_substeps/{task}/lanes64", dict(TEN_BOUNDS, ill_fraction=TEN_ILL_RANDOM[task]), ill_fraction=n_ill / n, **W64)
 
 
 # the share of RANDOM start states (joint noise +-0.3 rad, qvel sigma 0.6 rad/s) the oracle sets aside by its own sensitivity: measured + 10 points
@@ -530,6 +561,63 @@ def _conditioning(oracle_mod, om, q, v, w, c, q1, v1, prng, probes=6):
         if r[0] > 0.25 or (r[1] > 0.5 and r[1] > 15.0 * r[0]):
             return True
     return False
+
+
+def _rollout_state_referee(oracle_mod, model, om, cache, q, v, w, c, gq_e, gv_e, eq, evv, prng):
+    """A judged rollout state beyond the bound (`eq`, `evv`: the kernel's errors in qpos / qvel): the float64 oracle re-run with ONE class of its discrete
+    decisions biased to the runner-up (whole step, then single substeps), the oracle's float32 build, then float64 with rounding-level noise on the state.
+    Returns the name of the first run that lands on the kernel's state (`gq_e`, `gv_e`), or None.  `cache` keeps the float32 model between calls."""
+    verdict = None
+    # "lands on the kernel's state": within the bound -- or, for a flip early in the ten substeps (the two paths then part by ordinary float32
+    # error on a changed contact set), within 5 % of the discrepancy it explains
+    tol_q, tol_v = max(TEN_BOUNDS["qpos"], 0.05 * eq), max(TEN_BOUNDS["qvel"], 0.05 * evv)
+    lands = lambda dd: _rel(gq_e, np.array(dd["qpos"][: om.nq], np.float64), 1e-2).max() <= tol_q and _rel(gv_e, np.array(dd["qvel"][: om.nv], np.float64), 1.0).max() <= tol_v
+    for bit, name in ILL_CLASSES:
+        oracle_mod.set_tie_bias(bit, 2e-6, 1e-4)
+        try:
+            db = _oracle_step(oracle_mod, om, q, v, w, c, 10)
+        finally:
+            oracle_mod.set_tie_bias(0)
+        if lands(db):
+            verdict = name
+            break
+    if verdict is None:      # the same class in ONE substep only (a foot that rotates through a tie crosses it in one pass), bands 3e-7 / 2e-6
+        for eps, eps_rel in ((3e-7, 1e-5), (2e-6, 1e-4)):
+            for bit, name in ILL_CLASSES:
+                for k in range(10):
+                    oracle_mod.set_tie_bias(bit, eps, eps_rel, window=(k, k))
+                    try:
+                        db = _oracle_step(oracle_mod, om, q, v, w, c, 10)
+                    finally:
+                        oracle_mod.set_tie_bias(0)
+                    if lands(db):
+                        verdict = f"{name}/substep{k}"
+                        break
+                if verdict:
+                    break
+            if verdict:
+                break
+    if verdict is None:      # the oracle's float32 build: plain, then with one float32 rounding of noise on the state
+        if "om32" not in cache:
+            cache["om32"] = oracle_mod.OracleModel(model.blob(), f32=True)
+        om32 = cache["om32"]
+        for k in range(13):
+            amp = 0.0 if k == 0 else (1e-7 if k < 7 else 1e-6)
+            qp = (q + amp * prng.standard_normal(om.nq) * np.maximum(np.abs(q), 0.1)).astype(np.float32)
+            vp = (v + amp * prng.standard_normal(om.nv) * np.maximum(np.abs(v), 1.0)).astype(np.float32)
+            d32 = _oracle_step(oracle_mod, om32, qp, vp, w.astype(np.float32), c.astype(np.float32), 10)
+            if lands(d32):
+                verdict = "float32_oracle" + ("" if k == 0 else f"@{amp:g}")
+                break
+    if verdict is None:      # a discontinuity the six probes of `_conditioning` missed: float64 oracle, one float32 rounding of noise on the state
+        for k in range(192):      # (a flip that one direction in twenty finds: 64 trials per amplitude)
+            amp = (1e-7, 3e-7, 1e-6)[k // 64]
+            qp = q + amp * prng.standard_normal(om.nq) * np.maximum(np.abs(q), 0.1)
+            vp = v + 5 * amp * prng.standard_normal(om.nv) * np.maximum(np.abs(v), 1.0)
+            if lands(_oracle_step(oracle_mod, om, qp, vp, w, c, 10)):
+                verdict = f"float64_oracle_state_noise@{amp:g}"
+                break
+    return verdict
 
 
 @pytest.mark.parametrize("task", ["flat_terrain", "flat_terrain_backlash", "rough_terrain_backlash"])
@@ -578,11 +666,15 @@ def test_env_step_ten_substeps_on_rollout_states(torch_cuda, oracle_mod, parity_
     b.physics_step(torch.tensor(ctrl, dtype=torch.float32, device="cuda"), 10)
     gq, gv, _ = b.get_state()
     b.close()
-    wq = wv = wqn = wvn = 0.0
-    prng = np.random.default_rng(99)
-    n_ill = n_explained = n_unexplained = 0
-    ill_by_kind, why = {}, {}
-    om32, outliers = None, []
+    # the batches judged: the 32-lane one and, for the flat tasks, a second one at 64 lanes per env stepped from the same start states -- against the
+    # same oracle results and the same set-aside decisions (`prng` drives those and the 32-lane referee as before; the 64-lane referee draws from its own)
+    batches = [("", gq, gv, np.random.default_rng(99))]
+    if task in LANES64_TASKS:
+        batches.append(("/lanes64",) + _ten_substeps_at_64_lanes(torch, model, qpos, qvel, warm, ctrl) + (np.random.default_rng(199),))
+    prng = batches[0][3]
+    S = {tag: dict(wq=0.0, wv=0.0, wqn=0.0, wvn=0.0, n_explained=0, n_unexplained=0, why={}, outliers=[]) for tag, *_ in batches}
+    n_ill = 0
+    ill_by_kind, ref_cache = {}, {}
     for e in range(n):
         d = _oracle_step(oracle_mod, om, qpos[e], qvel[e], warm[e], ctrl[e], 10)
         q1, v1 = np.array(d["qpos"][: om.nq]), np.array(d["qvel"][: om.nv])
@@ -590,79 +682,44 @@ def test_env_step_ten_substeps_on_rollout_states(torch_cuda, oracle_mod, parity_
             n_ill += 1
             ill_by_kind[kind[e]] = ill_by_kind.get(kind[e], 0) + 1
             continue
-        eq, evv = _rel(gq[e], q1, 1e-2).max(), _rel(gv[e], v1, 1.0).max()
-        if eq > TEN_BOUNDS["qpos"] or evv > TEN_BOUNDS["qvel"]:      # referee: one decision class biased, does the oracle land on the kernel's state?
-            verdict = None
-            # "lands on the kernel's state": within the bound -- or, for a flip early in the ten substeps (the two paths then part by ordinary float32
-            # error on a changed contact set), within 5 % of the discrepancy it explains
-            tol_q, tol_v = max(TEN_BOUNDS["qpos"], 0.05 * eq), max(TEN_BOUNDS["qvel"], 0.05 * evv)
-            lands = lambda dd: _rel(gq[e], np.array(dd["qpos"][: om.nq], np.float64), 1e-2).max() <= tol_q and _rel(gv[e], np.array(dd["qvel"][: om.nv], np.float64), 1.0).max() <= tol_v
-            for bit, name in ILL_CLASSES:
-                oracle_mod.set_tie_bias(bit, 2e-6, 1e-4)
-                try:
-                    db = _oracle_step(oracle_mod, om, qpos[e], qvel[e], warm[e], ctrl[e], 10)
-                finally:
-                    oracle_mod.set_tie_bias(0)
-                if lands(db):
-                    verdict = name
-                    break
-            if verdict is None:      # the same class in ONE substep only (a foot that rotates through a tie crosses it in one pass), bands 3e-7 / 2e-6
-                for eps, eps_rel in ((3e-7, 1e-5), (2e-6, 1e-4)):
-                    for bit, name in ILL_CLASSES:
-                        for k in range(10):
-                            oracle_mod.set_tie_bias(bit, eps, eps_rel, window=(k, k))
-                            try:
-                                db = _oracle_step(oracle_mod, om, qpos[e], qvel[e], warm[e], ctrl[e], 10)
-                            finally:
-                                oracle_mod.set_tie_bias(0)
-                            if lands(db):
-                                verdict = f"{name}/substep{k}"
-                                break
-                        if verdict:
-                            break
-                    if verdict:
-                        break
-            if verdict is None:      # the oracle's float32 build: plain, then with one float32 rounding of noise on the state
-                if om32 is None:
-                    om32 = oracle_mod.OracleModel(model.blob(), f32=True)
-                for k in range(13):
-                    amp = 0.0 if k == 0 else (1e-7 if k < 7 else 1e-6)
-                    qp = (qpos[e] + amp * prng.standard_normal(om.nq) * np.maximum(np.abs(qpos[e]), 0.1)).astype(np.float32)
-                    vp = (qvel[e] + amp * prng.standard_normal(om.nv) * np.maximum(np.abs(qvel[e]), 1.0)).astype(np.float32)
-                    d32 = _oracle_step(oracle_mod, om32, qp, vp, warm[e].astype(np.float32), ctrl[e].astype(np.float32), 10)
-                    if lands(d32):
-                        verdict = "float32_oracle" + ("" if k == 0 else f"@{amp:g}")
-                        break
-            if verdict is None:      # a discontinuity the six probes of `_conditioning` missed: float64 oracle, one float32 rounding of noise on the state
-                for k in range(192):      # (a flip that one direction in twenty finds: 64 trials per amplitude)
-                    amp = (1e-7, 3e-7, 1e-6)[k // 64]
-                    qp = qpos[e] + amp * prng.standard_normal(om.nq) * np.maximum(np.abs(qpos[e]), 0.1)
-                    vp = qvel[e] + 5 * amp * prng.standard_normal(om.nv) * np.maximum(np.abs(qvel[e]), 1.0)
-                    if lands(_oracle_step(oracle_mod, om, qp, vp, warm[e], ctrl[e], 10)):
-                        verdict = f"float64_oracle_state_noise@{amp:g}"
-                        break
-            outliers.append(e)
-            print(f"[beyond the bound] {task} state {e} ({kind[e]}): qpos {eq:.2e} qvel {evv:.2e}; referee: {verdict}")
-            if verdict:
-                n_explained += 1; why[verdict] = why.get(verdict, 0) + 1
-            else:
-                n_unexplained += 1
-            continue
-        wq, wv = max(wq, eq), max(wv, evv)
-        wqn, wvn = max(wqn, _nw(gq[e], q1)), max(wvn, _nw(gv[e], v1))
-    if outliers:      # for replay on the CPU side (tools/replay_rollout_state.py)
+        for tag, bq, bv, ref_rng in batches:
+            s = S[tag]
+            eq, evv = _rel(bq[e], q1, 1e-2).max(), _rel(bv[e], v1, 1.0).max()
+            if eq > TEN_BOUNDS["qpos"] or evv > TEN_BOUNDS["qvel"]:      # referee: one decision class biased, does the oracle land on the kernel's state?
+                verdict = _rollout_state_referee(oracle_mod, model, om, ref_cache, qpos[e], qvel[e], warm[e], ctrl[e], bq[e], bv[e], eq, evv, ref_rng)
+                s["outliers"].append(e)
+                print(f"[beyond the bound] {task}{tag} state {e} ({kind[e]}): qpos {eq:.2e} qvel {evv:.2e}; referee: {verdict}")
+                if verdict:
+                    s["n_explained"] += 1; s["why"][verdict] = s["why"].get(verdict, 0) + 1
+                else:
+                    s["n_unexplained"] += 1
+                continue
+            s["wq"], s["wv"] = max(s["wq"], eq), max(s["wv"], evv)
+            s["wqn"], s["wvn"] = max(s["wqn"], _nw(bq[e], q1)), max(s["wvn"], _nw(bv[e], v1))
+    def keep(tag, outliers, bq, bv):      # for replay on the CPU side (tools/replay_rollout_state.py)
         out_dir = os.path.join(ROOT, "gpurun_out")
         os.makedirs(out_dir, exist_ok=True)
-        np.savez(os.path.join(out_dir, f"rollout_state_outliers_{task}.npz"), idx=np.array(outliers), qpos=qpos[outliers], qvel=qvel[outliers], warm=warm[outliers], ctrl=ctrl[outliers],
-                 gq=gq[outliers], gv=gv[outliers])
+        np.savez(os.path.join(out_dir, f"rollout_state_outliers_{task}{tag.replace('/', '_')}.npz"), idx=np.array(outliers), qpos=qpos[outliers], qvel=qvel[outliers], warm=warm[outliers],
+                 ctrl=ctrl[outliers], gq=bq[outliers], gv=bv[outliers])
+    for tag, bq, bv, _ in batches:
+        if S[tag]["outliers"]:
+            keep(tag, S[tag]["outliers"], bq, bv)
     kinds = {k: kind.count(k) for k in set(kind)}
     judged = n - n_ill
-    print(task, "10 substeps from rollout states: worst rel qpos", wq, "qvel", wv, "set aside:", n_ill, "of", n, ill_by_kind, "kinds", kinds, "explained", why, "unexplained", n_unexplained)
-    parity_log.rec(f"ten_substeps_rollout_states/{task}", None, states=n, judged=judged, **{"n_" + k: v for k, v in kinds.items()}, **{"ill_" + k: v for k, v in ill_by_kind.items()},
-                   **{"explained_by_" + k: v for k, v in why.items()})
+    for tag, *_ in batches:
+        s = S[tag]
+        print(task + tag, "10 substeps from rollout states: worst rel qpos", s["wq"], "qvel", s["wv"], "set aside:", n_ill, "of", n, ill_by_kind, "kinds", kinds, "explained", s["why"],
+              "unexplained", s["n_unexplained"])
+        parity_log.rec(f"ten_substeps_rollout_states/{task}{tag}", None, states=n, judged=judged, **{"n_" + k: v for k, v in kinds.items()}, **{"ill_" + k: v for k, v in ill_by_kind.items()},
+                       **{"explained_by_" + k: v for k, v in s["why"].items()})
     assert kinds.get("post_reset", 0) >= 32 and kinds.get("rollout", 0) >= 200
-    parity_log.check(f"ten_substeps_rollout_states/{task}", dict(TEN_BOUNDS, ill_fraction=0.10, explained_fraction=0.03 if "rough" in task else 0.01, unexplained=0), qpos=wq, qvel=wv, qpos_normwise=wqn,
-                     qvel_normwise=wvn, ill_fraction=n_ill / n, explained_fraction=n_explained / max(judged, 1), unexplained=n_unexplained)
+    bounds = dict(TEN_BOUNDS, ill_fraction=0.10, explained_fraction=0.03 if "rough" in task else 0.01, unexplained=0)
+    vals = {tag: dict(qpos=s["wq"], qvel=s["wv"], qpos_normwise=s["wqn"], qvel_normwise=s["wvn"], ill_fraction=n_ill / n, explained_fraction=s["n_explained"] / max(judged, 1),
+                      unexplained=s["n_unexplained"]) for tag, s in S.items()}
+    for tag in vals:      # both batches on record before either is judged
+        parity_log.rec(f"ten_substeps_rollout_states/{task}{tag}", bounds, **vals[tag])
+    for tag in vals:
+        parity_log.check(f"ten_substeps_rollout_states/{task}{tag}", bounds, **vals[tag])
 
 
 @pytest.mark.parametrize("task", ["flat_terrain", "flat_terrain_backlash", "rough_terrain_backlash"])
@@ -728,7 +785,7 @@ def test_the_duck_with_elliptic_cones(torch_cuda, oracle_mod, parity_log, task):
             engine.model_reduction(Model({**prim.a, "opt_cone": np.array([1], np.int32)}))
 
 
-@pytest.mark.parametrize("task,lanes", [("flat_terrain", 32), ("flat_terrain", 64), ("flat_terrain_backlash", 32)])
+@pytest.mark.parametrize("task,lanes", [("flat_terrain", 32), ("flat_terrain", 64), ("flat_terrain_backlash", 32), ("flat_terrain_backlash", 64)])
 def test_foot_foot_contacts(torch_cuda, oracle_mod, parity_log, task, lanes):
     """Feet pressed into each other (hip rolls inwards, robot lifted off the floor): the foot-foot SAT manifold,
     its contact rows and the coupled (virtual-tree) Hessian path against the oracle, one mjx.step."""
@@ -756,6 +813,7 @@ def test_foot_foot_contacts(torch_cuda, oracle_mod, parity_log, task, lanes):
     ctrl = np.stack([qpos[e, aq] for e in range(n)])
     cfg = engine.default_config(); cfg.lanes_per_env = lanes
     b = engine.Batch(model, n, cfg)
+    assert b.lanes_per_env == lanes, (task, lanes, b.lanes_per_env)
     b.set_state(qpos, qvel, warm)
     b.physics_step(torch.tensor(ctrl, dtype=torch.float32, device="cuda"), 1)
     gq, gv, _ = b.get_state()
@@ -1033,7 +1091,7 @@ def build_tables(model):
     return build_kernel_tables(model.a)
 
 
-@pytest.mark.parametrize("task,lanes", [("flat_terrain", 32), ("flat_terrain", 64), ("flat_terrain_backlash", 32), ("rough_terrain_backlash", 32)])
+@pytest.mark.parametrize("task,lanes", [("flat_terrain", 32), ("flat_terrain", 64), ("flat_terrain_backlash", 32), ("rough_terrain_backlash", 32), ("flat_terrain_backlash", 64)])
 def test_differential_sweep(torch_cuda, oracle_mod, parity_log, task, lanes):
     """A reduced run of tools/gpu_fuzz_parity.py: 768 random contact-rich states per model (leaning on one foot, near the home pose,
     feet pressed together in the air / on the floor -- next to a neighbour of another kind in the same wave --, airborne, far from the
@@ -1046,6 +1104,7 @@ def test_differential_sweep(torch_cuda, oracle_mod, parity_log, task, lanes):
     fz = importlib.util.module_from_spec(spec); spec.loader.exec_module(fz)
     n = 768
     stat, worst = fz.sweep(task, n, seed=123, lanes=lanes, nsub=1, dist_tol=3e-6 if "rough" in task else 1e-6)   # (8 m from the origin float32 positions carry 5e-7 m)
+    assert stat["lanes_per_env"] == lanes, (task, lanes, stat["lanes_per_env"])
     assert stat["in_contact"] > n // 2 and stat["foot_foot"] > n // 20 and stat["both_feet"] > n // 20, stat
     assert stat["unexplained"] == 0, stat
     parity_log.check(f"differential_sweep/{task}/lanes{lanes}", dict(dist=3e-6 if "rough" in task else 3e-7, qvel=1e-4, explained_fraction=0.01),

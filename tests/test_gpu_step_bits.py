@@ -2,16 +2,22 @@
 
 The instruction-count work on the env step kernels (fused final DPP stages, joint slots at compile time) may not change one bit of what a
 caller gets.  The recordings under tests/golden/step_bits_<case>.npz are the PARENT commit's outputs -- never the code under test -- for the
-three duck tasks at 32 lanes per env and flat_terrain at 64 lanes: 64 envs, 20 env steps, observation noise, pushes and auto-reset on,
+three duck tasks at 32 lanes per env and the two flat tasks at 64 lanes: 64 envs, 20 env steps, observation noise, pushes and auto-reset on,
 seeded random actions (numpy's PCG64 on the host, so the inputs are the same on every machine).
 
 Per step the recording holds the raw uint32 views of reward, done, truncation, metrics, qpos and qvel.  obs and priv (101 + 212 floats per
-env and step; the four recordings would be 5 MB, and a committed file stays far below 1 MiB) are held as two independent 32-bit
+env and step; the recordings would be 6 MB, and a committed file stays far below 1 MiB) are held as two independent 32-bit
 multiply-xorshift digests per env row and step over the row's uint32 view, plus the raw arrays of the last step: a changed bit in any row of
 any step changes that row's digests (a miss needs a simultaneous collision of both, 2^-64).  Every comparison is np.array_equal on integers.
 
-Regenerate (only ever from a build of the commit the change is measured against):
-    ODK_LIB=/path/to/parent/libodk.so python tests/test_gpu_step_bits.py --write
+The fifth recording, flat_terrain_backlash at 64 lanes (step_bits_flat_terrain_backlash_lanes64.npz), was added with the tests that hold the
+64-lane kernels to the oracle (profiles/lanes64): it is the output of the commit before THAT change, which edited no kernel, so it is this
+library's own output at that point, there for later changes to be measured against.  It is the size of the 32-lane recording of the same model
+(0.4 MB).
+
+Regenerate (only ever from a build of the commit the change is measured against); `--case` names the recordings to write (file name without
+`step_bits_` and `.npz`, repeatable) and leaves the others untouched, without it all are rewritten:
+    ODK_LIB=/path/to/parent/libodk.so python tests/test_gpu_step_bits.py --write [--case flat_terrain_backlash_lanes64]
 """
 import os
 import sys
@@ -23,7 +29,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-CASES = [("flat_terrain", 0), ("flat_terrain_backlash", 0), ("rough_terrain_backlash", 0), ("flat_terrain", 64)]
+CASES = [("flat_terrain", 0), ("flat_terrain_backlash", 0), ("rough_terrain_backlash", 0), ("flat_terrain", 64), ("flat_terrain_backlash", 64)]
 N_ENVS, N_STEPS = 64, 20
 RAW = ("reward", "done", "truncation", "metrics", "qpos", "qvel")
 DIGESTED = ("obs", "priv")
@@ -106,7 +112,13 @@ if __name__ == "__main__":
         raise SystemExit(__doc__)
     sys.path.insert(0, ROOT)
     os.makedirs(GOLDEN, exist_ok=True)
+    only = [sys.argv[i + 1] for i, a in enumerate(sys.argv[:-1]) if a == "--case"]
+    unknown = sorted(set(only) - {_case_name(*c) for c in CASES})
+    if unknown or sys.argv[-1] == "--case":
+        raise SystemExit(f"--case takes one of {[_case_name(*c) for c in CASES]}, got {unknown}")
     for task, lanes in CASES:
+        if only and _case_name(task, lanes) not in only:
+            continue
         r = run_case(task, lanes)
         path = os.path.join(GOLDEN, f"step_bits_{_case_name(task, lanes)}.npz")
         np.savez_compressed(path, **r)

@@ -76,6 +76,7 @@ def sweep(task, n=1024, seed=0, lanes=32, nsub=1, dist_tol=1e-6, verbose=True, v
         fields, _ = randomize.domain_randomize(model, np.random.default_rng(seed + 7), n)
     cfg = engine.default_config(); cfg.lanes_per_env = lanes if "rough" not in task else 32
     b = engine.Batch(model, n, cfg)
+    ran_lanes = b.lanes_per_env      # what the kernels run: cfg.lanes_per_env is a hint
     if dr:
         randomize.apply(b, fields)
     b.set_state(qpos, qvel, warm)
@@ -84,7 +85,7 @@ def sweep(task, n=1024, seed=0, lanes=32, nsub=1, dist_tol=1e-6, verbose=True, v
     img = b.lds_image(); o_cd = b.lds_offset("contact_dist")
     b.close()
     prng = np.random.default_rng(seed + 1)
-    stat = dict(ok=0, tie=0, f32_side=0, solver_branch=0, unexplained=0, in_contact=0, both_feet=0, foot_foot=0)
+    stat = dict(ok=0, tie=0, f32_side=0, solver_branch=0, unexplained=0, in_contact=0, both_feet=0, foot_foot=0, lanes_per_env=ran_lanes)
     worst = dict(dist=0.0, qvel=0.0)
     for e in range(n):
         om = _dr_model(model, om_base, fields, e) if dr else om_base
