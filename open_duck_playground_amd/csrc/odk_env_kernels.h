@@ -457,7 +457,7 @@ __device__ __forceinline__ void step_body(const KArgs& a) {
     ODK_SYNC();
   }
 #ifdef ODK_PROFILE
-  for (int k = lane; k < 36; k += G) L[S::O_SCR + S::S_PROF + k] = 0;
+  for (int k = lane; k < 40; k += G) L[S::O_SCR + S::S_PROF + k] = 0;
 #endif
   Statics<S, G> st;
   load_statics<S, G>(st, m, lane);
@@ -764,7 +764,7 @@ __global__ void __launch_bounds__(64) physics_kernel(KArgs a) {
   for (int u = lane; u < S::NU; u += G) L[S::O_CTRL + u] = a.action[(size_t)e * S::NU + u];
   load_params<S, G>(L, a.m, a.dr ? a.dr + (size_t)e * DRL<S>::SIZE : nullptr, lane);
 #ifdef ODK_PROFILE
-  for (int k = lane; k < 36; k += G) L[S::O_SCR + S::S_PROF + k] = 0;
+  for (int k = lane; k < 40; k += G) L[S::O_SCR + S::S_PROF + k] = 0;
 #endif
   ODK_SYNC();
   Statics<S, G> st;

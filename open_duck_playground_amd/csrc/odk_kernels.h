@@ -158,8 +158,9 @@ struct Shape {
   static constexpr int S_PROF = S_MISC + 16;   // [20] per-phase cycle counters (ODK_PROFILE builds)
   static constexpr int S_PROF2 = S_PROF + 20;  // [16] height-field contacts: hull setup, cull pass, register loads, pair loop, iterations, list length, -, -,
                                                //      then inside a pair: select + prism, face query, Gauss-map tests, passing pairs, faces / polygons, clip + manifold, merge
+  static constexpr int S_PROF3 = S_PROF2 + 16; // [4] line search: passes of the bracketing loop, summed over the forwards (lane 0)
 #ifdef ODK_PROFILE
-  static constexpr int N_SCR = S_PROF2 + 16;
+  static constexpr int N_SCR = S_PROF3 + 4;
 #else
   static constexpr int N_SCR = ((S_MISC + 16 + 3) / 4) * 4;      // no S_PROF slots outside profile builds (172 for chains of five)
 #endif
@@ -191,12 +192,15 @@ struct Shape {
 #ifdef ODK_PROFILE
 #define ODK_PROF(i) do { if (lane == 0) { long long _t = clock64(); SCR[S::S_PROF + (i)] += (float)(_t - _tprev); _tprev = _t; } } while (0)
 #define ODK_PROF_BEGIN() long long _tprev = clock64()
+#define ODK_LS_LOOP(tag) do { if (lane == 0 && (tag) == 0) SCR[S::S_PROF3] += 1.0f; } while (0)   // one pass of the line search's bracketing loop
 #elif defined(ODK_MARK)   // phase markers in the ISA listing (tools/isa_phase_stats.py): comments only
 #define ODK_PROF(i) asm volatile("; ODK_PHASE_END " #i ::: "memory")
 #define ODK_PROF_BEGIN() asm volatile("; ODK_PHASE_BEGIN" ::: "memory")
+#define ODK_LS_LOOP(tag) asm volatile("; LS_LOOP_" #tag ::: "memory")   // LS_LOOP_0 .. LS_LOOP_1: the loop body as a region of its own (tools/isa_select_census.py)
 #else
 #define ODK_PROF(i) do { } while (0)
 #define ODK_PROF_BEGIN() do { } while (0)
+#define ODK_LS_LOOP(tag) do { } while (0)
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -3302,7 +3306,21 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
   // Three step sizes at once.  The bracketing iterations only steer on the first and second derivative along the search, so
   // they evaluate those alone (COST = false: two sums per step size); the costs that pick the final step -- at lo, hi and 0 --
   // are one evaluation at the end (COST = true: one sum per step size, the quadratic combined per lane before the reduction).
-  auto ls_eval = [&](auto cost_tag, const float* al, float* cost, float* d0, float* d1) {
+  // The second derivative d1 = 2 t2 (+ MINVAL when t2 is zero) is only ever the divisor of a Newton step from a bracket end.  LEAN (the plane-floor
+  // step kernel, PRE): the bracket carries t2 and `curv` is evaluated where a step is taken -- two per pass instead of three, none for the pass that
+  // ends the search -- and the step has no guard against a zero divisor: d1 is never zero (t2 = +-0 gives MINVAL, and with f32 denormals kept, the
+  // kernels' float mode, doubling a non-zero t2 cannot give zero), so the guard was a compare and a select per step that never chose the zero.
+  // Every other kernel keeps the form it had (d1 formed for all three step sizes, the guarded step): the height-field step kernels sit at 256
+  // registers, and the lean form moved their allocation for a net loss (profiles/selects/NOTES.md 4).
+  constexpr bool LEAN = PRE;
+  auto curv = [](float t2) { return 2.0f * t2 + (t2 == 0.0f ? MINVAL_F : 0.0f); };
+  auto div_of = [&](float c) { if constexpr (LEAN) return curv(c); else return c; };   // the bracket's carried value -> the step's divisor
+  // (the pin: the product stays rounded on its own, as it was behind the guard's select -- bare, it contracts into the caller's subtraction)
+  auto sdiv = [](float a, float b) {   // Newton step of the 1-D search: 1 ulp is plenty
+    if constexpr (LEAN) { float q = a * __builtin_amdgcn_rcpf(b); asm volatile("" : "+v"(q)); return q; }
+    else return b == 0.0f ? 0.0f : a * __builtin_amdgcn_rcpf(b);
+  };
+  auto ls_eval = [&](auto cost_tag, const float* al, float* cost, float* d0, float* t2o) {
     constexpr bool COST = decltype(cost_tag)::value;
     // branch-free: a lane without a row of some kind holds D = 0 or f = jar = jv = 0 there, so its terms are exact zeros (the
     // divergent `if`s around them cost more exec-mask traffic than the few idle multiplies); an active quadratic row enters
@@ -3385,40 +3403,41 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
       for (int a = 0; a < 3; a++) {
         const float t1 = r[2 * a] + qg1, t2 = r[2 * a + 1] + qg2;
         d0[a] = 2.0f * al[a] * t2 + t1;
-        d1[a] = 2.0f * t2 + (t2 == 0.0f ? MINVAL_F : 0.0f);
+        t2o[a] = LEAN ? t2 : curv(t2);   // LEAN: half the second derivative, the divisor is made of it for the two step sizes that become a bracket end only
       }
     }
   };
   using Deriv = std::integral_constant<bool, false>; using Cost = std::integral_constant<bool, true>;
-  auto sdiv = [](float a, float b) { return b == 0.0f ? 0.0f : a * __builtin_amdgcn_rcpf(b); };   // Newton step of the 1-D search: 1 ulp is plenty
   float al[3] = {0, 0, 0}, cs[3], e0[3], e1[3];
   ls_eval(Deriv(), al, cs, e0, e1);   // three equal step sizes: the compiler folds them into one evaluation
-  const float p0_d0 = e0[0], p0_d1 = e1[0];
-  al[0] = -sdiv(p0_d0, p0_d1); al[1] = al[0]; al[2] = al[0];
+  const float p0_d0 = e0[0], p0_t2 = e1[0];
+  al[0] = -sdiv(p0_d0, div_of(p0_t2)); al[1] = al[0]; al[2] = al[0];
   ls_eval(Deriv(), al, cs, e0, e1);
-  float lo_a, lo_d0, lo_d1, hi_a, hi_d0, hi_d1;
-  if (e0[0] < p0_d0) { lo_a = al[0]; lo_d0 = e0[0]; lo_d1 = e1[0]; hi_a = 0; hi_d0 = p0_d0; hi_d1 = p0_d1; }
-  else { hi_a = al[0]; hi_d0 = e0[0]; hi_d1 = e1[0]; lo_a = 0; lo_d0 = p0_d0; lo_d1 = p0_d1; }
+  float lo_a, lo_d0, lo_t2, hi_a, hi_d0, hi_t2;
+  if (e0[0] < p0_d0) { lo_a = al[0]; lo_d0 = e0[0]; lo_t2 = e1[0]; hi_a = 0; hi_d0 = p0_d0; hi_t2 = p0_t2; }
+  else { hi_a = al[0]; hi_d0 = e0[0]; hi_t2 = e1[0]; lo_a = 0; lo_d0 = p0_d0; lo_t2 = p0_t2; }
   bool swap = true;
   for (int it = 0; it < ODK_HOTI(HOT_LS_ITERATIONS, m->ls_iterations); it++) {   // (PRE: a scalar extract, never a load inside the line search)
     bool done = !swap || (lo_d0 < 0 && lo_d0 > -gtol) || (hi_d0 > 0 && hi_d0 < gtol);
     if (done) break;
-    al[0] = lo_a - sdiv(lo_d0, lo_d1); al[1] = hi_a - sdiv(hi_d0, hi_d1); al[2] = 0.5f * (lo_a + hi_a);
+    ODK_LS_LOOP(0);
+    al[0] = lo_a - sdiv(lo_d0, div_of(lo_t2)); al[1] = hi_a - sdiv(hi_d0, div_of(hi_t2)); al[2] = 0.5f * (lo_a + hi_a);
     ls_eval(Deriv(), al, cs, e0, e1);
     // lo_next = 0, hi_next = 1, mid = 2
     const bool s1 = (lo_d0 > 0) || (lo_d0 < e0[0]);
-    if (s1) { lo_a = al[0]; lo_d0 = e0[0]; lo_d1 = e1[0]; }
+    if (s1) { lo_a = al[0]; lo_d0 = e0[0]; lo_t2 = e1[0]; }
     const bool s2 = (e0[2] < 0) && (lo_d0 < e0[2]);
-    if (s2) { lo_a = al[2]; lo_d0 = e0[2]; lo_d1 = e1[2]; }
+    if (s2) { lo_a = al[2]; lo_d0 = e0[2]; lo_t2 = e1[2]; }
     const bool s3 = (e0[1] < 0) && (lo_d0 < e0[1]);
-    if (s3) { lo_a = al[1]; lo_d0 = e0[1]; lo_d1 = e1[1]; }
+    if (s3) { lo_a = al[1]; lo_d0 = e0[1]; lo_t2 = e1[1]; }
     const bool s4 = (hi_d0 < 0) || (hi_d0 > e0[1]);
-    if (s4) { hi_a = al[1]; hi_d0 = e0[1]; hi_d1 = e1[1]; }
+    if (s4) { hi_a = al[1]; hi_d0 = e0[1]; hi_t2 = e1[1]; }
     const bool s5 = (e0[2] > 0) && (hi_d0 > e0[2]);
-    if (s5) { hi_a = al[2]; hi_d0 = e0[2]; hi_d1 = e1[2]; }
+    if (s5) { hi_a = al[2]; hi_d0 = e0[2]; hi_t2 = e1[2]; }
     const bool s6 = (e0[0] > 0) && (hi_d0 > e0[0]);
-    if (s6) { hi_a = al[0]; hi_d0 = e0[0]; hi_d1 = e1[0]; }
+    if (s6) { hi_a = al[0]; hi_d0 = e0[0]; hi_t2 = e1[0]; }
     swap = s1 || s2 || s3 || s4 || s5 || s6;
+    ODK_LS_LOOP(1);
   }
   al[0] = lo_a; al[1] = hi_a; al[2] = 0.0f;
   ls_eval(Cost(), al, cs, e0, e1);
@@ -3432,7 +3451,7 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
   }
   if constexpr (DBG) {   // solver diagnostics: debug image only (slots 8..12 belong to the env logic and are written below)
     if (lane == 0) { SCR[S::S_MISC + 13] = qg1; SCR[S::S_MISC + 14] = qg2; SCR[S::S_MISC + 15] = gauss; }
-    if (lane == 0) { SCR[S::S_MISC + 4] = p0_d0; SCR[S::S_MISC + 5] = p0_d1; SCR[S::S_MISC + 6] = p0_cost; SCR[S::S_MISC + 7] = gtol; }
+    if (lane == 0) { SCR[S::S_MISC + 4] = p0_d0; SCR[S::S_MISC + 5] = div_of(p0_t2); SCR[S::S_MISC + 6] = p0_cost; SCR[S::S_MISC + 7] = gtol; }
     if (lane == 0) { SCR[S::S_MISC + 1] = alpha; SCR[S::S_MISC + 2] = use_warm ? 1.0f : 0.0f; SCR[S::S_MISC + 3] = use_warm ? cost_w : cost_s; }
   }
   ODK_SYNC();

@@ -1,6 +1,7 @@
 """Per-phase shader-clock breakdown of the fused step kernel (needs the -DODK_PROFILE build):
     ODK_LIB=open_duck_playground_amd/csrc/libodk_prof.so python tools/gpu_phase_profile.py [task] [lanes] [nenv]
-Prints mean cycles per phase per env step (10 forwards), measured by lane 0 of every env."""
+Prints mean cycles per phase per env step (10 forwards), measured by lane 0 of every env, and the mean number of passes of the line
+search's bracketing loop per forward (the weight of the loop-body region in tools/isa_select_census.py --passes)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -41,6 +42,8 @@ for i in range(18):
     print(f"  {labels[i]:48s} {mean[i]:12,.0f}  {100 * mean[i] / tot:5.1f}%")
 print(f"  {'env-step prologue (kernel start -> first substep)':48s} {mean[18]:12,.0f}  {100 * mean[18] / tot:5.1f}% of the substeps' total")
 print(f"  {'env-step epilogue (last Euler -> kernel end)':48s} {mean[19]:12,.0f}  {100 * mean[19] / tot:5.1f}% of the substeps' total")
+passes = img[:, o + 36].astype(np.float64) / 10.0
+print(f"  line search: {passes.mean():.3f} passes of the bracketing loop per forward (lane 0's env; min {passes.min():.1f}, max {passes.max():.1f} over the envs)")
 if "rough" in task:
     print(f"  height-field contacts (per env step = 10 forwards): hull setup {prof2[0]:,.0f}  cull pass {prof2[1]:,.0f}  "
           f"pair loop {prof2[3]:,.0f} cycles; loop iterations {prof2[4] / 10:.2f} per forward (longest row of the wave), list length of foot 0 {prof2[5] / 10:.2f}, pairs of foot 0 given the full test {prof2[6] / 10:.2f}")

@@ -131,6 +131,155 @@ __global__ void __launch_bounds__(64) k(float* out, int iters) {
   out[blockIdx.x * 64 + lane] = s + idx + sgp;
 }
 
+// ---- selects measured alone, and what could stand in for one (profiles/selects/NOTES.md).
+// KIND 6 above declares a vcc clobber on each of its 64 statements, and the compiler answers every such statement with an `s_nop 0`: its row
+// is "select + s_nop 0, 64 statements", not the instruction.  Here one asm block holds the whole run of 64 (one clobber list, nothing the
+// compiler can put between two of them); the VOP3 forms take the mask as an SGPR-pair input.  Operands of every block:
+//   %0..%7 a[0..7] (read-write)   %8 b   %9 c   %10 per-lane mask (0 / ~0)   %11 0/1 weight   %12 the 0/1 lane flag   %13 SGPR-pair mask
+#define SB8(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7)
+#define SB64(X) SB8(X) SB8(X) SB8(X) SB8(X) SB8(X) SB8(X) SB8(X) SB8(X)
+#define SBLK(TEXT)                                                                                                                          \
+  asm volatile(TEXT : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7])                        \
+               : "v"(b), "v"(c), "v"(mk), "v"(w01), "v"(sel), "s"(smask)                                                                    \
+               : "vcc")
+#define SETVCC "v_cmp_eq_u32 vcc, 1, %12\n\t"
+#define FMA(i) "v_fma_f32 %" #i ", %" #i ", %8, %9\n\t"
+
+template <int KIND>
+__global__ void __launch_bounds__(64) ks(float* out, int iters) {
+  const int lane = threadIdx.x;
+  float a[8];
+  for (int i = 0; i < 8; i++) a[i] = 1.0f + 0.001f * (lane + i);
+  float b = 0.999f, c = 0.001f;
+  int sel = lane & 1;
+  asm volatile("" : "+v"(b), "+v"(c), "+v"(sel));   // operands stay in VGPRs
+  const unsigned mk = sel ? 0xFFFFFFFFu : 0u;
+  const float w01 = sel ? 1.0f : 0.0f;
+  const unsigned long long smask = __builtin_amdgcn_ballot_w64(sel != 0);
+  for (int it = 0; it < iters; it++) {
+    if (KIND == 0) {          // VOP2, mask in vcc, VGPR false operand, 8 independent chains
+#define X(i) "v_cndmask_b32 %" #i ", %" #i ", %8, vcc\n\t"
+      SBLK(SETVCC SB64(X));
+#undef X
+    } else if (KIND == 1) {   // VOP2, one dependent chain
+#define X(i) "v_cndmask_b32 %0, %0, %8, vcc\n\t"
+      SBLK(SETVCC SB64(X));
+#undef X
+    } else if (KIND == 2) {   // VOP2, inline-constant false operand
+#define X(i) "v_cndmask_b32 %" #i ", 0, %" #i ", vcc\n\t"
+      SBLK(SETVCC SB64(X));
+#undef X
+    } else if (KIND == 3) {   // literal false operand: a literal and vcc are two constant-bus reads, one too many for gfx9 in either encoding, so
+                              // the literal takes a v_mov_b32 of its own (32 groups of 2)
+#define X(i) "v_mov_b32 %" #i ", 0x3dcccccd\n\tv_cndmask_b32 %" #i ", %" #i ", %8, vcc\n\t"
+      SBLK(SETVCC SB8(X) SB8(X) SB8(X) SB8(X));
+#undef X
+    } else if (KIND == 4) {   // VOP3, mask in an SGPR pair, VGPR false operand, independent
+#define X(i) "v_cndmask_b32_e64 %" #i ", %" #i ", %8, %13\n\t"
+      SBLK(SB64(X));
+#undef X
+    } else if (KIND == 5) {   // VOP3, dependent
+#define X(i) "v_cndmask_b32_e64 %0, %0, %8, %13\n\t"
+      SBLK(SB64(X));
+#undef X
+    } else if (KIND == 6) {   // VOP3, inline-constant false operand (gfx9 has no literal in VOP3)
+#define X(i) "v_cndmask_b32_e64 %" #i ", 0, %" #i ", %13\n\t"
+      SBLK(SB64(X));
+#undef X
+    } else if (KIND == 7) {   // 1 select : 3 fma (16 + 48)
+#define X(i) "v_cndmask_b32 %" #i ", %" #i ", %8, vcc\n\t" FMA(i) FMA(i) FMA(i)
+      SBLK(SETVCC SB8(X) SB8(X));
+#undef X
+    } else if (KIND == 8) {   // 1 select : 7 fma (8 + 56)
+#define X(i) "v_cndmask_b32 %" #i ", %" #i ", %8, vcc\n\t" FMA(i) FMA(i) FMA(i) FMA(i) FMA(i) FMA(i) FMA(i)
+      SBLK(SETVCC SB8(X));
+#undef X
+    } else if (KIND == 9) {   // compare + select + 3 fma (16 groups of 5)
+#define X(i) "v_cmp_lt_f32 vcc, %" #i ", %8\n\tv_cndmask_b32 %" #i ", %" #i ", %9, vcc\n\t" FMA(i) FMA(i) FMA(i)
+      SBLK(SB8(X) SB8(X));
+#undef X
+    } else if (KIND == 10) {  // compare + select pairs alone (32 groups of 2)
+#define X(i) "v_cmp_lt_f32 vcc, %" #i ", %8\n\tv_cndmask_b32 %" #i ", %" #i ", %9, vcc\n\t"
+      SBLK(SB8(X) SB8(X) SB8(X) SB8(X));
+#undef X
+    } else if (KIND == 11) {  // the 64 fma of kinds 7..9 alone, in one block (the base line of the mixes)
+      SBLK(SB64(FMA));
+    } else if (KIND == 12) {  // v_cmp_lt_f32 to vcc (VOPC)
+#define X(i) "v_cmp_lt_f32 vcc, %" #i ", %8\n\t"
+      SBLK(SB64(X));
+#undef X
+    } else if (KIND == 13) {  // v_cmp_lt_f32 to an SGPR pair (VOP3)
+#define X(i) "v_cmp_lt_f32_e64 s[20:21], %" #i ", %8\n\t"
+      asm volatile(SB64(X) :: "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]), "v"(a[7]), "v"(b) : "s20", "s21");
+#undef X
+    } else if (KIND == 14) {  // v_and_b32 with a per-lane mask register
+#define X(i) "v_and_b32 %" #i ", %10, %" #i "\n\t"
+      SBLK(SB64(X));
+#undef X
+    } else if (KIND == 15) {  // v_bfi_b32 with a per-lane mask register: (mask & a) | (~mask & b)
+#define X(i) "v_bfi_b32 %" #i ", %10, %" #i ", %8\n\t"
+      SBLK(SB64(X));
+#undef X
+    } else if (KIND == 16) {  // v_fma_f32 with a 0/1 weight: a = w * b + a
+#define X(i) "v_fma_f32 %" #i ", %11, %8, %" #i "\n\t"
+      SBLK(SB64(X));
+#undef X
+    } else if (KIND == 17) {
+#define X(i) "v_max_f32 %" #i ", %" #i ", %8\n\t"
+      SBLK(SB64(X));
+#undef X
+    } else if (KIND == 18) {
+#define X(i) "v_min_f32 %" #i ", %" #i ", %8\n\t"
+      SBLK(SB64(X));
+#undef X
+    } else if (KIND == 19) {
+#define X(i) "v_med3_f32 %" #i ", %" #i ", %8, %9\n\t"
+      SBLK(SB64(X));
+#undef X
+    } else if (KIND == 20) {  // a mask from a sign bit
+#define X(i) "v_ashrrev_i32 %" #i ", 31, %" #i "\n\t"
+      SBLK(SB64(X));
+#undef X
+    } else if (KIND == 23) {  // two VOP2 selects back to back between two fma (16 groups of 4): does the second of a pair pay?
+#define X(i) "v_cndmask_b32 %" #i ", %" #i ", %8, vcc\n\tv_cndmask_b32 %" #i ", %" #i ", %9, vcc\n\t" FMA(i) FMA(i)
+      SBLK(SETVCC SB8(X) SB8(X));
+#undef X
+    } else if (KIND == 24) {  // VOP2 and VOP3 selects alternating (32 groups of 2)
+#define X(i) "v_cndmask_b32 %" #i ", %" #i ", %8, vcc\n\tv_cndmask_b32_e64 %" #i ", %" #i ", %9, %13\n\t"
+      SBLK(SETVCC SB8(X) SB8(X) SB8(X) SB8(X));
+#undef X
+    } else if (KIND == 25) {  // VOP2 select and v_mul_f32 alternating (32 groups of 2)
+#define X(i) "v_cndmask_b32 %" #i ", %" #i ", %8, vcc\n\tv_mul_f32 %" #i ", %" #i ", %8\n\t"
+      SBLK(SETVCC SB8(X) SB8(X) SB8(X) SB8(X));
+#undef X
+    } else if (KIND == 26) {  // 1 VOP3 select : 3 fma (16 + 48)
+#define X(i) "v_cndmask_b32_e64 %" #i ", %" #i ", %8, %13\n\t" FMA(i) FMA(i) FMA(i)
+      SBLK(SB8(X) SB8(X));
+#undef X
+    } else if (KIND == 27) {  // 1 v_and_b32 : 3 fma and 1 v_bfi_b32 : 3 fma, the mixes of the two bit-exact stand-ins
+#define X(i) "v_and_b32 %" #i ", %10, %" #i "\n\t" FMA(i) FMA(i) FMA(i)
+      SBLK(SB8(X) SB8(X));
+#undef X
+    } else if (KIND == 28) {
+#define X(i) "v_bfi_b32 %" #i ", %10, %" #i ", %8\n\t" FMA(i) FMA(i) FMA(i)
+      SBLK(SB8(X) SB8(X));
+#undef X
+    } else if (KIND == 21) {  // plain `if`, opaque condition, one move in the body: the compiler's own compare + exec narrowing + restore
+#define X(i) { int cc = sel; asm volatile("" : "+v"(cc)); if (cc) { a[i] = b; asm volatile("" : "+v"(a[i])); } }
+      REP8(X) REP8(X) REP8(X) REP8(X)
+#undef X
+    } else if (KIND == 22) {  // the same with four moves in the body
+#define X(i) { int cc = sel; asm volatile("" : "+v"(cc)); if (cc) { a[i] = b; a[(i + 1) & 7] = c; a[(i + 2) & 7] = b; a[(i + 3) & 7] = c; \
+                 asm volatile("" : "+v"(a[i]), "+v"(a[(i + 1) & 7]), "+v"(a[(i + 2) & 7]), "+v"(a[(i + 3) & 7])); } }
+      REP8(X) REP8(X) REP8(X) REP8(X)
+#undef X
+    }
+  }
+  float s = 0;
+  for (int i = 0; i < 8; i++) s += a[i];
+  out[blockIdx.x * 64 + lane] = s;
+}
+
 struct Kind { const char* name; int per_iter; void (*fn)(float*, int); };
 
 int main(int argc, char** argv) {
@@ -149,6 +298,16 @@ int main(int argc, char** argv) {
       {"ds_bpermute_b32", 64, k<10>}, {"v_permlane16_swap", 64, k<11>}, {"v_rcp_f32 indep", 64, k<12>}, {"v_mul_f32 indep", 64, k<13>},
       {"ds_read dep chain (latency)", 64, k<14>}, {"ds_write+ds_read+wait hand-off", 64, k<15>}, {"v_fma x2 pairs", 64, k<16>},
       {"v_mov_b32_dpp indep", 64, k<17>}, {"v_pk_mul_f32 indep", 64, k<18>}, {"v_add_u32 dep", 64, k<19>}, {"s_nop 0", 64, k<20>},
+      // selects alone and their alternatives (ks<>: one asm block per iteration; "grp": cycles per group, not per instruction)
+      {"cndmask vop2 vgpr indep", 64, ks<0>}, {"cndmask vop2 vgpr dep", 64, ks<1>}, {"cndmask vop2 inline indep", 64, ks<2>},
+      {"v_mov literal + cndmask vop2", 64, ks<3>}, {"cndmask vop3 vgpr indep", 64, ks<4>}, {"cndmask vop3 vgpr dep", 64, ks<5>},
+      {"cndmask vop3 inline indep", 64, ks<6>}, {"mix 1 cndmask : 3 fma", 64, ks<7>}, {"mix 1 cndmask : 7 fma", 64, ks<8>},
+      {"mix cmp+cndmask+3 fma", 80, ks<9>}, {"mix cmp+cndmask", 64, ks<10>}, {"v_fma_f32 indep (one block)", 64, ks<11>},
+      {"v_cmp_lt_f32 vcc", 64, ks<12>}, {"v_cmp_lt_f32 sgpr pair", 64, ks<13>}, {"v_and_b32 lane mask", 64, ks<14>},
+      {"v_bfi_b32 lane mask", 64, ks<15>}, {"v_fma_f32 0/1 weight", 64, ks<16>}, {"v_max_f32", 64, ks<17>}, {"v_min_f32", 64, ks<18>},
+      {"v_med3_f32", 64, ks<19>}, {"v_ashrrev_i32 31", 64, ks<20>}, {"grp: if { 1 v_mov }", 32, ks<21>}, {"grp: if { 4 v_mov }", 32, ks<22>},
+      {"mix 2 cndmask vop2 : 2 fma", 64, ks<23>}, {"cndmask vop2 / vop3 alternating", 64, ks<24>}, {"cndmask vop2 / v_mul alternating", 64, ks<25>},
+      {"mix 1 cndmask vop3 : 3 fma", 64, ks<26>}, {"mix 1 v_and_b32 : 3 fma", 64, ks<27>}, {"mix 1 v_bfi_b32 : 3 fma", 64, ks<28>},
   };
   hipEvent_t e0, e1;
   CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
