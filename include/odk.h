@@ -551,6 +551,81 @@ int odk_fall_accumulate(const odk_batch* b, const float* priv_dev, const float* 
                         const float* track_acc_dev, const float* torque_limit_dev /* [nu] or NULL */, float tilt_tol, int ring,
                         float* acc_dev /* [nenv, row_stride] */, int row_stride, void* stream);
 
+/* Paths and waypoints (where did it end up, and can something steer it: the odometry of every env, and a waypoint follower on top of the
+ * joystick command).  Three launches, one thread per env, graph-capturable, no LDS; they read the base pose from the batch's own state
+ * record (qpos at offset 0 of the env's row, as the fall recorder) and leave the step, reset and physics kernels alone.  Reset draws every
+ * env's own xy offset and yaw, so every pose quantity is expressed in the env's START FRAME: the base position and heading right after
+ * odk_reset.  Definitions, shared by the three:
+ *   pose             p = qpos[0:2] and the heading h of the base quaternion (w, x, y, z) = qpos[3:7]: hx = 1 - 2 (y y + z z),
+ *                    hy = 2 (x y + w z), divided by their length n = hypot(hx, hy) (through float64, one rounding to float32); n < 1e-6 (the
+ *                    base pitched onto its nose: no heading) gives h = (1, 0)
+ *   start-frame position of a pose against a stored start (sx, sy, shx, shy): r = p - s, xs = r . sh, ys = sh x r = shx ry - shy rx
+ *   start-frame heading   (c, s) = (sh . h, sh x h)
+ * Arithmetic is float32 + - * /, comparisons, fminf / fmaxf and that hypot; every product is rounded before it is added (no fused
+ * multiply-add), there is no atan2, sin or cos on the device, one thread owns an env's row and there are no atomics: a float32 host
+ * restatement has the bits, and a replay is deterministic.  A model whose first joint is not a free joint has no base pose:
+ * ODK_ERR_UNSUPPORTED.  Every other refusal is ODK_ERR_INVALID with the cause in odk_last_error, and nothing is launched.
+ *
+ * Env e's row of acc_dev [nenv, ODK_PATH_NACC]:
+ *   START_X, START_Y, START_HX, START_HY   the start pose (odk_path_begin)
+ *   X, Y, HX, HY     the pose at the last sample (odk_path_begin: the start pose)
+ *   LENGTH           sum over the samples of hypot(x - X, y - Y): the path length in metres
+ *   TURN             sum over the samples of HX hy - HY hx = sin(dpsi), the heading change between two samples.  At 50 Hz and |wz| <= 1 rad/s
+ *                    dpsi <= 0.02 rad, so the sum differs from the sum of dpsi (the heading change in radians, turns counted) by less than
+ *                    dpsi^2 / 6 < 1e-4 relative
+ *   SAMPLES          samples taken
+ *   FELL, FELL_LEG   1 when the first episode ended with done and no truncation, and the waypoint index (WP_INDEX) it was heading for
+ *   WP_INDEX         the waypoint the env is heading for: the number of waypoints reached so far
+ *   XTRACK_SAMPLES, XTRACK_SQ, XTRACK_PEAK   count of, sum of squares of and maximum of the cross-track distance (below)
+ *   GOAL_DIST        start-frame distance to the course's last waypoint at the latest sample taken while a waypoint was still ahead
+ *   REACHED[8]       per waypoint the 1-based index of the first-episode step at which it was reached; 0: not reached
+ * Slots past REACHED + 8 stay 0.
+ *
+ * odk_path_begin: issued after odk_reset.  Zeroes env e's row and stores the current pose in START_* and in X, Y, HX, HY.
+ *
+ * odk_path_accumulate: one launch per evaluation step, issued after odk_step and BEFORE odk_tracking_accumulate, with odk_push_accumulate's
+ * ENDED / STEPS contract (track_acc_dev [nenv, ODK_TRACK_NACC]).  An env past its first episode is not touched.  A done step takes no
+ * sample (the record is the auto-reset's state); with truncation 0 it sets FELL and FELL_LEG.  A sample step adds to LENGTH, TURN and
+ * SAMPLES and stores the new pose in X, Y, HX, HY.  With a course (course_dev not NULL) and i = WP_INDEX below the course's count it then
+ * takes dist, the start-frame distance to waypoint i, and the cross-track distance xt: from the start-frame position to the segment from
+ * waypoint i - 1 (the origin for i = 0) to waypoint i, the projection parameter clamped to 0 .. 1, a zero-length leg the distance to the
+ * point; XTRACK_SAMPLES += 1, XTRACK_SQ += xt xt, XTRACK_PEAK = max; GOAL_DIST = the distance to the last waypoint; and when
+ * dist <= radius, REACHED[i] = STEPS + 1 and WP_INDEX = i + 1: at most one waypoint per step.  course_dev NULL with ncourse 0 is the plain
+ * odometry mode; it needs no bound commands (nor does a course: the accumulator reads no command).  Refused: a null pointer (the message
+ * names the argument), course_dev without course_of_env_dev, course_dev NULL with ncourse != 0, ncourse < 1 with a course, a radius that
+ * is negative or not finite.
+ *
+ * Courses: course_dev is [ncourse, ODK_PATH_COURSE_FLOATS] device floats, a row the count and then up to ODK_PATH_MAX_WAYPOINTS points
+ * (x, y) in start-frame metres; course_of_env_dev [nenv] int32 is env e's course, clamped into 0 .. ncourse - 1 by the kernels, which also
+ * clamp the count into 0 .. ODK_PATH_MAX_WAYPOINTS: they never read outside the table.  The host cannot see device tables: their contents
+ * are the caller's to validate.
+ *
+ * odk_waypoint_command_apply: one launch, issued BEFORE odk_step: a pure-pursuit-like heading controller that writes entries 0..2 (vx, vy,
+ * wz) of env e's row of the BOUND command buffer (odk_command_schedule_apply's contract: binding the buffer says this launch may write
+ * it).  Entries 3 and beyond keep their bits, and so does any column past 6 of a wider row.  The row of an env whose ENDED is set is not
+ * written.  At clock 0 (STEPS == 0, not ENDED) the pose IS the start pose by definition -- position (0, 0), heading (1, 0) -- and neither
+ * the records nor START_* are read: the launch before odk_reset gives the reset's observation its command from stale records.  Otherwise
+ * the pose comes from the records against START_*.  With i = WP_INDEX: i == count, the course is finished: (0, 0, 0).  Else d = w_i -
+ * (xs, ys), dist = hypot(d); dist < 1e-6: f = 1, l = 0, otherwise f = (d . (c, s)) / dist and l = ((c, s) x d) / dist; turn = f >= 0 ? l :
+ * (l >= 0 ? 1 : -1) (a target exactly behind turns left); wz = clamp(heading_gain turn, +-turn_rate); vx = v_cruise max(f, 0), on the
+ * course's last waypoint times min(1, dist / slow_dist); vy = 0.  Refused: a null pointer (the message names the argument), no bound
+ * commands, ncourse < 1, slow_dist or heading_gain not finite and positive, v_cruise or turn_rate not finite and >= 0. */
+#define ODK_PATH_NACC 32
+#define ODK_PATH_MAX_WAYPOINTS 8
+#define ODK_PATH_COURSE_FLOATS (1 + 2 * ODK_PATH_MAX_WAYPOINTS)
+enum { ODK_PATH_START_X = 0, ODK_PATH_START_Y = 1, ODK_PATH_START_HX = 2, ODK_PATH_START_HY = 3, ODK_PATH_X = 4, ODK_PATH_Y = 5, ODK_PATH_HX = 6,
+       ODK_PATH_HY = 7, ODK_PATH_LENGTH = 8, ODK_PATH_TURN = 9, ODK_PATH_SAMPLES = 10, ODK_PATH_FELL = 11, ODK_PATH_FELL_LEG = 12,
+       ODK_PATH_WP_INDEX = 13, ODK_PATH_XTRACK_SAMPLES = 14, ODK_PATH_XTRACK_SQ = 15, ODK_PATH_XTRACK_PEAK = 16, ODK_PATH_GOAL_DIST = 17,
+       ODK_PATH_REACHED = 18 /* [8]; 26..31 stay 0 */ };
+int odk_path_begin(const odk_batch* b, float* acc_dev /* [nenv, ODK_PATH_NACC] */, void* stream);
+int odk_path_accumulate(const odk_batch* b, const float* done_dev, const float* truncation_dev, const float* track_acc_dev,
+                        const float* course_dev /* [ncourse, ODK_PATH_COURSE_FLOATS] or NULL */, int ncourse,
+                        const int32_t* course_of_env_dev /* [nenv] or NULL without a course */, float radius,
+                        float* acc_dev /* [nenv, ODK_PATH_NACC] */, void* stream);
+int odk_waypoint_command_apply(const odk_batch* b, const float* course_dev, int ncourse, const int32_t* course_of_env_dev,
+                               const float* track_acc_dev, const float* path_acc_dev, float v_cruise, float turn_rate, float heading_gain,
+                               float slow_dist, void* stream);
+
 /* mjx_env.step alone (physics only, n_substeps, ctrl = ctrl_dev [nenv, nu]); for parity tests */
 int odk_physics_step(odk_batch* b, const float* ctrl_dev, int n_substeps, void* stream);
 

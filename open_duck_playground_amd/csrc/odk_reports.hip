@@ -1,6 +1,7 @@
 // odk_reports.hip -- the evaluation reports of include/odk.h (libodk.so): the accumulator kernels of the tracking / push / gait / posture /
-// imitation / response / fall reports and the command-schedule kernel, with their C entry points.  They read finished observation rows
-// (odk_obs_layout.h) and the batch (odk_batch.h: read-only here; its state is odk_engine.hip's); no compiled shape.  gfx950 only, no CPU fallback.
+// imitation / response / fall / path reports, the command-schedule kernel and the waypoint follower, with their C entry points.  They read
+// finished observation rows (odk_obs_layout.h) and the batch (odk_batch.h: read-only here; its state is odk_engine.hip's); no compiled shape.
+// gfx950 only, no CPU fallback.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -602,6 +603,196 @@ extern "C" int odk_fall_accumulate(const odk_batch* b, const float* priv_dev, co
   hipLaunchKernelGGL(fall_kernel, g.grid, dim3(256), 0, (hipStream_t)stream, priv_dev, g.npriv, g.nobs, nu, done_dev,
                      truncation_dev, track_acc_dev, b->d_cmd, b->cmd_stride, torque_limit_dev, b->d_recs, b->rec_size, nq, tilt_tol, ring, acc_dev,
                      row_stride, b->nenv);
+  HIPCHK(hipGetLastError());
+  return ODK_OK;
+}
+
+// ---- paths and waypoints (include/odk.h "Paths and waypoints": the definitions these three kernels restate).  One thread per env, no LDS.
+// Contraction is off and the hypots go through float64, so a float32 host restatement has the bits.
+// The base pose from an env's state record (qpos at offset 0): position, and the heading vector of the base quaternion, normalised;
+// (1, 0) when the base is pitched onto its nose
+struct Pose { float x, y, hx, hy; };
+__device__ __forceinline__ Pose base_pose(const float* __restrict__ R) {
+#pragma clang fp contract(off)
+  const float w = R[3], x = R[4], y = R[5], z = R[6];
+  const float hx = 1.0f - 2.0f * (y * y + z * z), hy = 2.0f * (x * y + w * z);
+  const float n = planar32(hx, hy);
+  const bool none = n < 1e-6f;
+  Pose p; p.x = R[0]; p.y = R[1];
+  p.hx = none ? 1.0f : hx / n;
+  p.hy = none ? 0.0f : hy / n;
+  return p;
+}
+// a course's row of the table ([ncourse, ODK_PATH_COURSE_FLOATS]: count, then the points) and its count, both clamped as sched_row's map entry
+__device__ __forceinline__ const float* course_row(const float* __restrict__ course, int ncourse, const int* __restrict__ course_of_env, int e) {
+  const int c = min(max(course_of_env[e], 0), ncourse - 1);
+  return course + (size_t)c * ODK_PATH_COURSE_FLOATS;
+}
+__device__ __forceinline__ int course_count(const float* __restrict__ W) { return min(max((int)W[0], 0), ODK_PATH_MAX_WAYPOINTS); }
+
+// The start pose of every env, issued after odk_reset: the row zeroed, the pose in START_* and in the last-sample slots
+__global__ void __launch_bounds__(256) path_begin_kernel(const float* __restrict__ recs, int rec_size, float* __restrict__ acc, int nenv) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= nenv) return;
+  const Pose p = base_pose(recs + (size_t)e * rec_size);
+  float* A = acc + (size_t)e * ODK_PATH_NACC;
+#pragma unroll
+  for (int k = 0; k < ODK_PATH_NACC; k++) A[k] = 0.0f;
+  A[ODK_PATH_START_X] = p.x; A[ODK_PATH_START_Y] = p.y; A[ODK_PATH_START_HX] = p.hx; A[ODK_PATH_START_HY] = p.hy;
+  A[ODK_PATH_X] = p.x; A[ODK_PATH_Y] = p.y; A[ODK_PATH_HX] = p.hx; A[ODK_PATH_HY] = p.hy;
+}
+
+// Odometry and course progress of one evaluation step, issued between odk_step and odk_tracking_accumulate (the ENDED / STEPS contract of
+// push_kernel).  course == nullptr: the plain odometry mode
+__global__ void __launch_bounds__(256) path_kernel(const float* __restrict__ recs, int rec_size, const float* __restrict__ done,
+                                                   const float* __restrict__ trunc, const float* __restrict__ track,
+                                                   const float* __restrict__ course, int ncourse, const int* __restrict__ course_of_env,
+                                                   float radius, float* __restrict__ acc, int nenv) {
+#pragma clang fp contract(off)
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= nenv) return;
+  const float* T = track + (size_t)e * ODK_TRACK_NACC;
+  if (T[ODK_TRACK_ENDED] != 0.0f) return;       // past its first episode
+  float* A = acc + (size_t)e * ODK_PATH_NACC;
+  if (done[e] != 0.0f) {   // ends the first episode; no sample (the record is the auto-reset's state)
+    if (trunc[e] == 0.0f) { A[ODK_PATH_FELL] = 1.0f; A[ODK_PATH_FELL_LEG] = A[ODK_PATH_WP_INDEX]; }
+    return;
+  }
+  const Pose p = base_pose(recs + (size_t)e * rec_size);
+  A[ODK_PATH_LENGTH] += planar32(p.x - A[ODK_PATH_X], p.y - A[ODK_PATH_Y]);
+  A[ODK_PATH_TURN] += A[ODK_PATH_HX] * p.hy - A[ODK_PATH_HY] * p.hx;   // sin of the heading change since the last sample
+  A[ODK_PATH_SAMPLES] += 1.0f;
+  A[ODK_PATH_X] = p.x; A[ODK_PATH_Y] = p.y; A[ODK_PATH_HX] = p.hx; A[ODK_PATH_HY] = p.hy;
+  if (!course) return;
+  const float* W = course_row(course, ncourse, course_of_env, e);
+  const int count = course_count(W), i = max((int)A[ODK_PATH_WP_INDEX], 0);
+  if (i >= count) return;                       // the course is finished
+  const float shx = A[ODK_PATH_START_HX], shy = A[ODK_PATH_START_HY];
+  const float rx = p.x - A[ODK_PATH_START_X], ry = p.y - A[ODK_PATH_START_Y];
+  const float xs = rx * shx + ry * shy, ys = shx * ry - shy * rx;      // the start-frame position
+  const float wx = W[1 + 2 * i], wy = W[2 + 2 * i];
+  const float px = i > 0 ? W[2 * i - 1] : 0.0f, py = i > 0 ? W[2 * i] : 0.0f;   // where the leg starts: the waypoint before, or the origin
+  const float dist = planar32(wx - xs, wy - ys);
+  const float ax = wx - px, ay = wy - py, qx = xs - px, qy = ys - py;
+  const float len2 = ax * ax + ay * ay;
+  const float u = len2 > 0.0f ? fminf(fmaxf((qx * ax + qy * ay) / len2, 0.0f), 1.0f) : 0.0f;   // a zero-length leg: the distance to the point
+  const float xt = planar32(qx - u * ax, qy - u * ay);
+  A[ODK_PATH_XTRACK_SAMPLES] += 1.0f;
+  A[ODK_PATH_XTRACK_SQ] += xt * xt;
+  A[ODK_PATH_XTRACK_PEAK] = fmaxf(A[ODK_PATH_XTRACK_PEAK], xt);
+  A[ODK_PATH_GOAL_DIST] = planar32(W[2 * count - 1] - xs, W[2 * count] - ys);
+  if (dist <= radius) {   // at most one waypoint per step
+    A[ODK_PATH_REACHED + i] = T[ODK_TRACK_STEPS] + 1.0f;   // this step's 1-based index
+    A[ODK_PATH_WP_INDEX] = (float)(i + 1);
+  }
+}
+
+// The command of the step about to run from the env's course (one thread per env), issued before odk_step: steer towards waypoint WP_INDEX.
+// The tracking accumulator's STEPS slot is the clock: at 0 the pose is the start pose by definition, and nothing of the records is read
+__global__ void __launch_bounds__(256) waypoint_apply_kernel(const float* __restrict__ recs, int rec_size, const float* __restrict__ track,
+                                                             const float* __restrict__ path, const float* __restrict__ course, int ncourse,
+                                                             const int* __restrict__ course_of_env, float v_cruise, float turn_rate,
+                                                             float heading_gain, float slow_dist, float* __restrict__ cmd, int cmd_stride, int nenv) {
+#pragma clang fp contract(off)
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= nenv) return;
+  const float* T = track + (size_t)e * ODK_TRACK_NACC;
+  if (T[ODK_TRACK_ENDED] != 0.0f) return;       // past its first episode: the row keeps the command of the step that ended it
+  const float* A = path + (size_t)e * ODK_PATH_NACC;
+  const float* W = course_row(course, ncourse, course_of_env, e);
+  const int count = course_count(W);
+  float xs = 0.0f, ys = 0.0f, c = 1.0f, s = 0.0f;
+  int i = 0;
+  if (T[ODK_TRACK_STEPS] != 0.0f) {
+    const Pose p = base_pose(recs + (size_t)e * rec_size);
+    const float shx = A[ODK_PATH_START_HX], shy = A[ODK_PATH_START_HY];
+    const float rx = p.x - A[ODK_PATH_START_X], ry = p.y - A[ODK_PATH_START_Y];
+    xs = rx * shx + ry * shy; ys = shx * ry - shy * rx;
+    c = shx * p.hx + shy * p.hy; s = shx * p.hy - shy * p.hx;
+    i = min(max((int)A[ODK_PATH_WP_INDEX], 0), count);
+  }
+  float vx = 0.0f, wz = 0.0f;
+  if (i < count) {
+    const float dx = W[1 + 2 * i] - xs, dy = W[2 + 2 * i] - ys;
+    const float dist = planar32(dx, dy);
+    const bool on = dist < 1e-6f;
+    const float f = on ? 1.0f : (dx * c + dy * s) / dist, l = on ? 0.0f : (c * dy - s * dx) / dist;
+    const float turn = f >= 0.0f ? l : (l >= 0.0f ? 1.0f : -1.0f);   // a target exactly behind turns left
+    // (the clamps by comparison, not fminf / fmaxf: between +0 and -0 those may return either, a comparison keeps the bits a restatement has)
+    wz = heading_gain * turn;
+    wz = wz > turn_rate ? turn_rate : wz;
+    wz = wz < -turn_rate ? -turn_rate : wz;
+    vx = v_cruise * (f > 0.0f ? f : 0.0f);
+    if (i == count - 1) vx = vx * fminf(1.0f, dist / slow_dist);
+  }
+  float* C = cmd + (size_t)e * cmd_stride;
+  C[0] = vx; C[1] = 0.0f; C[2] = wz;
+}
+
+static int path_model_ok(const char* fn, const odk_batch* b) {
+  const DevModel& m = b->model.h;
+  bool floating = m.nq >= 7 && m.nv >= 6;
+  for (int d = 0; floating && d < 6; d++) floating = m.dof_jnt[d] < 0;   // dofs 0 .. 5 are no hinge's: the free joint's
+  return floating ? ODK_OK : fail(ODK_ERR_UNSUPPORTED, "%s: the model's first joint is not a free joint: there is no base pose at qpos[0:7]", fn);
+}
+static int finite_pos(const char* fn, const char* name, float v, const char* what) {
+  return std::isfinite(v) && v > 0.0f ? ODK_OK : fail(ODK_ERR_INVALID, "%s: %s = %g (a finite %s)", fn, name, (double)v, what);
+}
+
+extern "C" int odk_path_begin(const odk_batch* b, float* acc_dev, void* stream) {
+  const char* fn = "odk_path_begin";
+  if (!b) return fail(ODK_ERR_INVALID, "%s: null batch", fn);
+  if (!acc_dev) return fail(ODK_ERR_INVALID, "%s: null acc_dev", fn);
+  if (int rc = path_model_ok(fn, b)) return rc;
+  Launch g; if (int rc = launch_on(b, 1, &g)) return rc;
+  hipLaunchKernelGGL(path_begin_kernel, g.grid, dim3(256), 0, (hipStream_t)stream, b->d_recs, b->rec_size, acc_dev, b->nenv);
+  HIPCHK(hipGetLastError());
+  return ODK_OK;
+}
+
+extern "C" int odk_path_accumulate(const odk_batch* b, const float* done_dev, const float* truncation_dev, const float* track_acc_dev,
+                                   const float* course_dev, int ncourse, const int32_t* course_of_env_dev, float radius, float* acc_dev,
+                                   void* stream) {
+  const char* fn = "odk_path_accumulate";
+  if (!b) return fail(ODK_ERR_INVALID, "%s: null batch", fn);
+  if (!done_dev) return fail(ODK_ERR_INVALID, "%s: null done_dev", fn);
+  if (!truncation_dev) return fail(ODK_ERR_INVALID, "%s: null truncation_dev", fn);
+  if (!track_acc_dev) return fail(ODK_ERR_INVALID, "%s: null track_acc_dev", fn);
+  if (!acc_dev) return fail(ODK_ERR_INVALID, "%s: null acc_dev", fn);
+  if (course_dev && !course_of_env_dev) return fail(ODK_ERR_INVALID, "%s: null course_of_env_dev", fn);
+  if (!course_dev && ncourse != 0) return fail(ODK_ERR_INVALID, "%s: null course_dev with ncourse = %d (the odometry mode is NULL with 0)", fn, ncourse);
+  if (course_dev && ncourse < 1) return fail(ODK_ERR_INVALID, "%s: ncourse = %d (at least one course)", fn, ncourse);
+  if (int rc = finite_nonneg(fn, "radius", radius, "distance >= 0, in metres")) return rc;
+  if (int rc = path_model_ok(fn, b)) return rc;
+  Launch g; if (int rc = launch_on(b, 1, &g)) return rc;
+  hipLaunchKernelGGL(path_kernel, g.grid, dim3(256), 0, (hipStream_t)stream, b->d_recs, b->rec_size, done_dev, truncation_dev, track_acc_dev,
+                     course_dev, ncourse, course_of_env_dev, radius, acc_dev, b->nenv);
+  HIPCHK(hipGetLastError());
+  return ODK_OK;
+}
+
+extern "C" int odk_waypoint_command_apply(const odk_batch* b, const float* course_dev, int ncourse, const int32_t* course_of_env_dev,
+                                          const float* track_acc_dev, const float* path_acc_dev, float v_cruise, float turn_rate,
+                                          float heading_gain, float slow_dist, void* stream) {
+  const char* fn = "odk_waypoint_command_apply";
+  if (!b) return fail(ODK_ERR_INVALID, "%s: null batch", fn);
+  if (!course_dev) return fail(ODK_ERR_INVALID, "%s: null course_dev", fn);
+  if (!course_of_env_dev) return fail(ODK_ERR_INVALID, "%s: null course_of_env_dev", fn);
+  if (!track_acc_dev) return fail(ODK_ERR_INVALID, "%s: null track_acc_dev", fn);
+  if (!path_acc_dev) return fail(ODK_ERR_INVALID, "%s: null path_acc_dev", fn);
+  if (!b->d_cmd) return fail(ODK_ERR_INVALID, "%s: no commands bound (odk_batch_bind_commands)", fn);
+  if (b->cmd_stride < 3) return fail(ODK_ERR_INVALID, "%s: the bound command rows are %d floats apart, the launch writes 3", fn, b->cmd_stride);
+  if (ncourse < 1) return fail(ODK_ERR_INVALID, "%s: ncourse = %d (at least one course)", fn, ncourse);
+  if (int rc = finite_nonneg(fn, "v_cruise", v_cruise, "speed >= 0, in m/s")) return rc;
+  if (int rc = finite_nonneg(fn, "turn_rate", turn_rate, "yaw rate >= 0, in rad/s")) return rc;
+  if (int rc = finite_pos(fn, "heading_gain", heading_gain, "gain > 0, in rad/s per unit of the heading error's sine")) return rc;
+  if (int rc = finite_pos(fn, "slow_dist", slow_dist, "distance > 0, in metres")) return rc;
+  if (int rc = path_model_ok(fn, b)) return rc;
+  Launch g; if (int rc = launch_on(b, 1, &g)) return rc;
+  // the bound buffer is the caller's own device memory (odk_command_schedule_apply's contract); this launch is the one writer
+  hipLaunchKernelGGL(waypoint_apply_kernel, g.grid, dim3(256), 0, (hipStream_t)stream, b->d_recs, b->rec_size, track_acc_dev, path_acc_dev,
+                     course_dev, ncourse, course_of_env_dev, v_cruise, turn_rate, heading_gain, slow_dist, const_cast<float*>(b->d_cmd),
+                     b->cmd_stride, b->nenv);
   HIPCHK(hipGetLastError());
   return ODK_OK;
 }

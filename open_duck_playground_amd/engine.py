@@ -187,6 +187,9 @@ def load_library() -> C.CDLL:
     L.odk_response_accumulate.argtypes = [P, P, P, P, P, P, C.c_int, C.c_int, P, C.c_float, C.c_float, C.c_int, P, P]
     L.odk_fall_row_floats.argtypes = [P, C.c_int]
     L.odk_fall_accumulate.argtypes = [P, P, P, P, P, P, C.c_float, C.c_int, P, C.c_int, P]
+    L.odk_path_begin.argtypes = [P, P, P]
+    L.odk_path_accumulate.argtypes = [P, P, P, P, P, C.c_int, P, C.c_float, P, P]
+    L.odk_waypoint_command_apply.argtypes = [P, P, C.c_int, P, P, P, C.c_float, C.c_float, C.c_float, C.c_float, P]
     L.odk_batch_get_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_set_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_get_debug.argtypes = [P, FP, FP, FP, FP]
@@ -233,6 +236,7 @@ EXPORTED_SYMBOLS = (
     "odk_batch_bind_commands", "odk_batch_set_reward_terms", "odk_batch_bind_reward_metrics", "odk_batch_set_imitation_joints", "odk_batch_set_head_joints",
     "odk_tracking_accumulate", "odk_batch_bind_pushes", "odk_batch_bind_action_delays", "odk_push_accumulate", "odk_gait_accumulate", "odk_posture_accumulate",
     "odk_imitation_accumulate", "odk_command_schedule_apply", "odk_response_accumulate", "odk_fall_row_floats", "odk_fall_accumulate",
+    "odk_path_begin", "odk_path_accumulate", "odk_waypoint_command_apply",
     "odk_batch_get_state", "odk_batch_set_state", "odk_batch_get_debug", "odk_set_debug_dump", "odk_batch_lds_size",
     "odk_batch_get_lds", "odk_lds_offset", "odk_batch_record_size", "odk_batch_get_records", "odk_batch_set_records", "odk_batch_timing", "odk_gae", "odk_ppo_head",
     "odk_policy_sample", "odk_adam_clip", "odk_silu_bwd_colsum", "odk_colsum_partial", "odk_colsum_finalize", "odk_gather_rows", "odk_dw_gemm",
@@ -316,6 +320,14 @@ FALL_SAMPLES, FALL_FELL, FALL_STEP, FALL_LAST_UPRIGHT, FALL_UPRIGHT_CONTACT, FAL
 (FALL_S_STEP, FALL_S_UP, FALL_S_GYRO, FALL_S_LINVEL, FALL_S_HEIGHT, FALL_S_CONTACT, FALL_S_LIN_ERR, FALL_S_ANG_ERR, FALL_S_SAT) = (
     0, 1, 4, 7, 10, 11, 13, 14, 15)
 
+# odk_path_begin / odk_path_accumulate's per-env slots (include/odk.h ODK_PATH_*): the start pose, the last sample's pose, the odometry sums,
+# then the course progress; a course row of the table is its count and PATH_MAX_WAYPOINTS points (x, y) in start-frame metres
+PATH_NACC = 32
+PATH_MAX_WAYPOINTS = 8
+PATH_COURSE_FLOATS = 1 + 2 * PATH_MAX_WAYPOINTS
+(PATH_START_X, PATH_START_Y, PATH_START_HX, PATH_START_HY, PATH_X, PATH_Y, PATH_HX, PATH_HY, PATH_LENGTH, PATH_TURN, PATH_SAMPLES, PATH_FELL,
+ PATH_FELL_LEG, PATH_WP_INDEX, PATH_XTRACK_SAMPLES, PATH_XTRACK_SQ, PATH_XTRACK_PEAK, PATH_GOAL_DIST, PATH_REACHED) = range(19)
+
 
 def check_pushes(push, nenv: int, device: int) -> None:
     """What `Batch.bind_pushes` accepts: a contiguous float32 [nenv, >= 2] tensor on cuda:`device`; raises OdkError otherwise."""
@@ -396,6 +408,36 @@ def check_schedule(name: str, sched, sched_of_env, nenv: int, device: int):
         raise OdkError(f"{name}: sched_of_env: shape must be ({nenv},), got {tuple(sched_of_env.shape)}")
     _check_placement(f"{name}: sched_of_env", sched_of_env, torch.int32, device)
     return int(sched.shape[0]), int(sched.shape[1])
+
+
+def check_courses(name: str, course, course_of_env, nenv: int, device: int) -> int:
+    """The course arguments of `Batch.path_accumulate` / `Batch.waypoint_command_apply`: `course` a contiguous float32
+    [ncourse >= 1, PATH_COURSE_FLOATS] tensor and `course_of_env` a contiguous int32 [nenv] tensor, both on cuda:`device`; OdkError otherwise.
+    Returns ncourse.  The contents (a count of 1 .. PATH_MAX_WAYPOINTS, finite points, map entries in range) are the builder's to check:
+    track.course_table / track.schedule_blocks; the kernels clamp what they index with."""
+    import torch
+    if not torch.is_tensor(course):
+        raise OdkError(f"{name}: course: expected a torch tensor, got {type(course).__name__}")
+    if course.dim() != 2 or int(course.shape[0]) < 1 or int(course.shape[1]) != PATH_COURSE_FLOATS:
+        raise OdkError(f"{name}: course: shape must be (ncourse >= 1, {PATH_COURSE_FLOATS}), got {tuple(course.shape)}")
+    _check_placement(f"{name}: course", course, torch.float32, device)
+    if not torch.is_tensor(course_of_env):
+        raise OdkError(f"{name}: course_of_env: expected a torch tensor, got {type(course_of_env).__name__}")
+    if tuple(course_of_env.shape) != (int(nenv),):
+        raise OdkError(f"{name}: course_of_env: shape must be ({nenv},), got {tuple(course_of_env.shape)}")
+    _check_placement(f"{name}: course_of_env", course_of_env, torch.int32, device)
+    return int(course.shape[0])
+
+
+def check_path_parameter(name: str, what: str, value, positive: bool = False) -> float:
+    """A controller setting of the path launches: a finite number >= 0 (`positive`: > 0); OdkError otherwise.  Returns it as a float."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise OdkError(f"{name}: {what} = {value!r} is not a number")
+    if not np.isfinite(v) or v < 0 or (positive and v == 0):
+        raise OdkError(f"{name}: {what} = {value!r} (a finite number {'> 0' if positive else '>= 0'})")
+    return v
 
 
 def _chk(rc: int):
@@ -1232,6 +1274,44 @@ class Batch:
             raise OdkError("fall_accumulate: no commands bound (bind_commands)")
         _chk(self.L.odk_fall_accumulate(self._b, *_report_ptrs(self, track_acc), limit, float(tilt_tol), int(ring), C.c_void_p(acc.data_ptr()), int(acc.shape[1]),
                                         self._stream()))
+
+    def path_begin(self, acc):
+        """One `odk_path_begin` launch, issued after `reset`: env e's row of `acc` ([nenv, PATH_NACC] float32) is zeroed and takes the base
+        pose the reset left as its start pose (PATH_START_*) and as its last sample (PATH_X ..): every later pose quantity is in that frame."""
+        check_accumulator("path_begin: acc", acc, self.nenv, PATH_NACC, self.device)
+        _chk(self.L.odk_path_begin(self._b, C.c_void_p(acc.data_ptr()), self._stream()))
+
+    def path_accumulate(self, acc, track_acc, course=None, course_of_env=None, radius: float = 0.0):
+        """One `odk_path_accumulate` launch over this step's state into `acc` ([nenv, PATH_NACC] float32, begun by `path_begin`), issued
+        after `step` and BEFORE `tracking_accumulate(track_acc)`: path length, heading change and the last pose of every env in its first
+        episode.  `course` (float32 [ncourse, PATH_COURSE_FLOATS]: count, then the points in start-frame metres) with `course_of_env` (int32
+        [nenv]) adds the course progress: the waypoint reached within `radius` metres (finite, >= 0), the cross-track distance and the
+        distance to the goal.  Without a course it is the plain odometry.  Needs no bound commands."""
+        _check_report(self, "path_accumulate", acc, PATH_NACC, track_acc)
+        if course is None and course_of_env is not None:
+            raise OdkError("path_accumulate: course_of_env without a course")
+        ncourse = 0 if course is None else check_courses("path_accumulate", course, course_of_env, self.nenv, self.device)
+        radius = check_path_parameter("path_accumulate", "radius", radius)
+        _chk(self.L.odk_path_accumulate(self._b, C.c_void_p(self.done.data_ptr()), C.c_void_p(self.truncation.data_ptr()), C.c_void_p(track_acc.data_ptr()),
+                                        _ptr(course), ncourse, _ptr(course_of_env), radius, C.c_void_p(acc.data_ptr()), self._stream()))
+
+    def waypoint_command_apply(self, course, course_of_env, track_acc, path_acc, v_cruise: float, turn_rate: float, heading_gain: float,
+                               slow_dist: float):
+        """One `odk_waypoint_command_apply` launch, issued BEFORE `step`: entries 0..2 (vx, vy, wz) of env e's row of the bound command
+        tensor steer it towards waypoint PATH_WP_INDEX of its course -- forward at `v_cruise` (m/s, >= 0) times the cosine of the heading
+        error, turning at `heading_gain` (> 0) times its sine, clamped to `turn_rate` (rad/s, >= 0), slowing down inside `slow_dist`
+        (metres, > 0) of the last waypoint; zeros once the course is finished.  `track_acc`'s STEPS slot is the clock: a zeroed one takes the
+        start pose as the pose, what the launch before `reset` needs.  `path_acc`: `path_accumulate`'s.  Needs bound commands."""
+        ncourse = check_courses("waypoint_command_apply", course, course_of_env, self.nenv, self.device)
+        check_accumulator("waypoint_command_apply: track_acc", track_acc, self.nenv, TRACK_NACC, self.device)
+        check_accumulator("waypoint_command_apply: path_acc", path_acc, self.nenv, PATH_NACC, self.device)
+        fn = "waypoint_command_apply"
+        args = (check_path_parameter(fn, "v_cruise", v_cruise), check_path_parameter(fn, "turn_rate", turn_rate),
+                check_path_parameter(fn, "heading_gain", heading_gain, True), check_path_parameter(fn, "slow_dist", slow_dist, True))
+        if self.commands is None:
+            raise OdkError("waypoint_command_apply: no commands bound (bind_commands)")
+        _chk(self.L.odk_waypoint_command_apply(self._b, C.c_void_p(course.data_ptr()), ncourse, C.c_void_p(course_of_env.data_ptr()),
+                                               C.c_void_p(track_acc.data_ptr()), C.c_void_p(path_acc.data_ptr()), *args, self._stream()))
 
     def physics_step(self, ctrl, n_substeps: int = 10):
         assert ctrl.is_cuda and ctrl.dtype == self.torch.float32 and ctrl.is_contiguous() and tuple(ctrl.shape) == (self.nenv, self.model.nu)

@@ -116,6 +116,24 @@ within `--robust_fall_rate`.  `--gait`, `--falls`, `--imitation_report`, `--post
 object per cell too); `--push` / `--push_grid` do not (a third cell axis).  `--randomize` applies the training-time `domain_randomize` draw
 to every env (seeded by `--seed`; a plant's scales multiply it), `--noise_level X` overrides `noise_config.level`.  Without these flags
 nothing changes.
+
+Paths and waypoints (where did it end up, and can something steer it? -- every figure above is a velocity, a rate or a joint quantity):
+
+    python -m open_duck_playground_amd.track --checkpoint <ckpt> --command 0.15 0 0 --path
+    python -m open_duck_playground_amd.track --checkpoint <ckpt> --waypoints "0.5,0 | 0.5,0.5 | 0,0.5 | 0,0" --waypoints "1,0" --falls
+
+`--path` adds one launch (`odk_path_accumulate`) to the captured step, before the tracking accumulator, and one (`odk_path_begin`) after the
+reset.  They read the base pose from the batch's own state on the device and express it in each env's start frame, the pose right after
+the reset (which draws every env's own offset and yaw).  Every row (cell, schedule row) gains a "path" object: forward and lateral
+displacement, heading change, path length and straightness as mean and std over the envs, and for a row with one constant command the
+dead-reckoned `ideal` pose and the mean distance to it (`reduce_path`).  `--waypoints` (repeatable: one course of 1 to 8 points in
+start-frame metres each) makes every course a row of the report: `odk_waypoint_command_apply`, before the env step, steers each env towards
+its next waypoint by writing vx and wz of the bound command tensor -- the clock is the tracking accumulator's, the waypoint index the path
+accumulator's -- and the row gains "course": the share of envs that reached each waypoint and when, the cross-track error, the distance left
+to the goal, the path length against the course's and the falls by leg (`reduce_course`).  `--waypoint_radius`, `--waypoint_speed`,
+`--waypoint_turn_rate`, `--waypoint_gain` and `--waypoint_slow_dist` are the follower's settings.  `--waypoints` implies `--path`; it combines
+with plants, `--gait`, `--falls` and `--imitation_report`, and not with `--command` / `--grid` (the course is the command), `--sequence` /
+`--then` (two writers of the command tensor), pushes or `--posture`.  Without these flags nothing changes.
 """
 from __future__ import annotations
 
@@ -161,6 +179,12 @@ from .engine import (FALL_HEAD, FALL_SAMPLE, FALL_MAX_RING, FALL_SAMPLES as F_SA
                      FALL_LAST_UPRIGHT as F_LAST_UPRIGHT, FALL_UPRIGHT_CONTACT as F_UPRIGHT_CONTACT, FALL_TILT_PEAK as F_TILT_PEAK,
                      FALL_S_STEP as FS_STEP, FALL_S_UP as FS_UP, FALL_S_GYRO as FS_GYRO, FALL_S_HEIGHT as FS_HEIGHT, FALL_S_LIN_ERR as FS_LIN_ERR,
                      FALL_S_SAT as FS_SAT)      # ODK_FALL_*
+
+from .engine import (PATH_NACC, PATH_MAX_WAYPOINTS, PATH_COURSE_FLOATS, PATH_START_X as W_START_X, PATH_START_Y as W_START_Y,
+                     PATH_START_HX as W_START_HX, PATH_START_HY as W_START_HY, PATH_X as W_X, PATH_Y as W_Y, PATH_LENGTH as W_LENGTH,
+                     PATH_TURN as W_TURN, PATH_SAMPLES as W_SAMPLES, PATH_FELL as W_FELL, PATH_FELL_LEG as W_FELL_LEG, PATH_WP_INDEX as W_WP_INDEX,
+                     PATH_XTRACK_SAMPLES as W_XTRACK_SAMPLES, PATH_XTRACK_SQ as W_XTRACK_SQ, PATH_XTRACK_PEAK as W_XTRACK_PEAK,
+                     PATH_GOAL_DIST as W_GOAL_DIST, PATH_REACHED as W_REACHED)      # ODK_PATH_*
 
 COMMAND_KEYS = ("vx", "vy", "wz", "neck_pitch", "head_pitch", "head_yaw", "head_roll")   # the order of cmd_range (include/odk.h)
 NACC = 12
@@ -1160,6 +1184,210 @@ def save_falls(path: str, clips: Dict, dt: float) -> None:
     np.savez(path, dt=np.float64(dt), **clips)
 
 
+# BUILD-DEFINED defaults: controller settings of the waypoint follower, not measured constants (the reference has no follower).  A waypoint
+# counts as reached within 5 cm; the follower cruises at 0.1 m/s, turns at up to 0.6 rad/s with 2 rad/s per unit sine of the heading error,
+# and slows down inside 10 cm of the last waypoint
+DEFAULT_WAYPOINT_RADIUS = 0.05
+DEFAULT_WAYPOINT_SPEED = 0.1
+DEFAULT_WAYPOINT_TURN_RATE = 0.6
+DEFAULT_WAYPOINT_GAIN = 2.0
+DEFAULT_WAYPOINT_SLOW_DIST = 0.1
+
+
+def parse_waypoints(text: str) -> List[List[float]]:
+    """`--waypoints "0.5,0 | 0.5,0.5 | 0,0.5 | 0,0"` -> one course: its points [x, y] in start-frame metres, apart by `|`.  ValueError for
+    a point that is not `x,y`, a coordinate that is not a number, and (`check_course`) a course of no point or of more than 8."""
+    points = []
+    for part in str(text).split("|"):
+        if not part.strip():
+            continue
+        bits = part.split(",")
+        if len(bits) != 2:
+            raise ValueError(f"--waypoints: {part.strip()!r} is not `x,y`")
+        try:
+            points.append([float(bits[0]), float(bits[1])])
+        except ValueError:
+            raise ValueError(f"--waypoints: the point {part.strip()!r} is not two numbers")
+    check_course(points)
+    return points
+
+
+def check_course(points: Sequence[Sequence[float]]) -> None:
+    """What a course must satisfy before it reaches the device (the kernels cannot report it): 1 to 8 points of two finite float32 values.
+    ValueError with the reason."""
+    if not 1 <= len(points) <= PATH_MAX_WAYPOINTS:
+        raise ValueError(f"--waypoints: a course has 1 to {PATH_MAX_WAYPOINTS} points, this one has {len(points)}")
+    for i, p in enumerate(points):
+        v = np.asarray(p, np.float64).reshape(-1)
+        with np.errstate(over="ignore"):
+            fits = v.shape == (2,) and bool(np.all(np.isfinite(v.astype(np.float32))))
+        if not fits:
+            raise ValueError(f"--waypoints: point {i} is not two finite numbers: {list(p)}")
+
+
+def course_table(courses: Sequence[Sequence[Sequence[float]]]) -> np.ndarray:
+    """float32 [ncourse, 17] for `Batch.path_accumulate` / `Batch.waypoint_command_apply`: a row is the course's count, then its points
+    x0 y0 x1 y1 ..., zeros past the last.  Every course is checked (`check_course`)."""
+    if not courses:
+        raise ValueError("no course given")
+    tab = np.zeros((len(courses), PATH_COURSE_FLOATS), np.float32)
+    for i, pts in enumerate(courses):
+        check_course(pts)
+        tab[i, 0] = float(len(pts))
+        tab[i, 1:1 + 2 * len(pts)] = np.asarray(pts, np.float32).reshape(-1)
+    return tab
+
+
+def course_of_envs(course_map: np.ndarray, ncourse: int) -> np.ndarray:
+    """The course every env really follows: the map entry clamped into 0 .. ncourse - 1, as the kernels clamp it."""
+    return np.clip(np.asarray(course_map, np.int64), 0, int(ncourse) - 1)
+
+
+def course_length(points: Sequence[Sequence[float]]) -> float:
+    """Length of the polyline origin -> point 0 -> ... -> the last point, in float64."""
+    p = np.concatenate([np.zeros((1, 2)), np.asarray(points, np.float64).reshape(-1, 2)])
+    return float(np.hypot(*np.diff(p, axis=0).T).sum())
+
+
+def waypoint_limits_refusal(speed: float, turn_rate: float, cmd_range) -> Optional[str]:
+    """`--waypoint_speed` / `--waypoint_turn_rate` against the env's `cmd_range` (rows vx and wz; [lo, hi] each): the follower commands vx in
+    0 .. speed and wz in -turn_rate .. turn_rate, which the policy must have been trained on.  The reason, or None."""
+    vx, wz = [float(x) for x in cmd_range[0]], [float(x) for x in cmd_range[2]]
+    if float(speed) > vx[1]:
+        return f"--waypoint_speed {float(speed)} is beyond the env's command range for vx, {vx[0]} .. {vx[1]} m/s"
+    if float(turn_rate) > wz[1] or -float(turn_rate) < wz[0]:
+        return f"--waypoint_turn_rate {float(turn_rate)} is beyond the env's command range for wz, {wz[0]} .. {wz[1]} rad/s"
+    return None
+
+
+def waypoints_from_args(args) -> Optional[Dict]:
+    """The waypoint follower the command line asks for -- `courses` (one per `--waypoints`), `radius`, `speed`, `turn_rate`, `gain`,
+    `slow_dist` and the `flags` as given -- or None without `--waypoints`.  SystemExit with the reason for a course that cannot be parsed, a
+    setting that is not a finite number >= 0 (gain and slow-down distance: > 0), and for `--waypoints` next to `--sequence` / `--then` (two
+    writers of the command buffer), `--command` / `--grid` (the course is the command), pushes and `--posture` (one command per episode)
+    -- host work only, before any batch exists."""
+    texts = getattr(args, "waypoints", None) or []
+    if not texts:
+        return None
+    if getattr(args, "sequence", None) or getattr(args, "then", None):
+        raise SystemExit("--waypoints does not combine with --sequence / --then: the follower and the schedule would both write the command buffer")
+    if getattr(args, "command", None) or getattr(args, "grid", None):
+        raise SystemExit("--waypoints does not combine with --command / --grid: the course is the command (every --waypoints is one row of the report)")
+    if getattr(args, "push", None) or getattr(args, "push_grid", None):
+        raise SystemExit("--waypoints does not combine with --push / --push_grid: the push figures assume one command per episode")
+    if getattr(args, "posture", False):
+        raise SystemExit("--waypoints does not combine with --posture: its settle times assume one command per episode")
+    try:
+        courses = [parse_waypoints(t) for t in texts]
+    except ValueError as err:
+        raise SystemExit(str(err))
+    out = dict(courses=courses, flags=dict(waypoints=list(texts)))
+    for key, flag, default, positive in (("radius", "waypoint_radius", DEFAULT_WAYPOINT_RADIUS, False), ("speed", "waypoint_speed", DEFAULT_WAYPOINT_SPEED, False),
+                                         ("turn_rate", "waypoint_turn_rate", DEFAULT_WAYPOINT_TURN_RATE, False),
+                                         ("gain", "waypoint_gain", DEFAULT_WAYPOINT_GAIN, True), ("slow_dist", "waypoint_slow_dist", DEFAULT_WAYPOINT_SLOW_DIST, True)):
+        v = float(getattr(args, flag, default))
+        if not np.isfinite(v) or v < 0 or (positive and v == 0):
+            raise SystemExit(f"--{flag} is a finite number {'> 0' if positive else '>= 0'}, got {v}")
+        out[key] = v
+    return out
+
+
+def ideal_pose(command: Sequence[float], t) -> tuple:
+    """(x, y, psi) after holding the body-frame velocities `command[:3]` = (vx, vy, wz) for `t` seconds from the pose (0, 0, 0), in float64:
+    the arc x = (vx sin a - vy (1 - cos a)) / wz, y = (vx (1 - cos a) + vy sin a) / wz with a = wz t, written with sin(a) / a and
+    (1 - cos a) / a = sin(a / 2) * sin(a / 2) / (a / 2) so that wz -> 0 is the line (vx t, vy t) without a cancellation or a branch."""
+    vx, vy, wz = (float(x) for x in list(command)[:3])
+    t = np.asarray(t, np.float64)
+    a = wz * t
+    s = t * np.sinc(a / np.pi)                                 # sin(a) / wz
+    c = t * np.sin(0.5 * a) * np.sinc(0.5 * a / np.pi)         # (1 - cos a) / wz
+    return vx * s - vy * c, vx * c + vy * s, a
+
+
+def _mean_std(x: np.ndarray) -> Dict:
+    x = np.asarray(x, np.float64)
+    return dict(mean=float(x.mean()) if x.size else None, std=float(x.std()) if x.size else None)
+
+
+def path_frame(acc: np.ndarray) -> tuple:
+    """(forward, lateral) [nenv] float64: the start-frame displacement of every env at its last sample, from a path accumulator."""
+    a = np.asarray(acc, np.float64).reshape(-1, PATH_NACC)
+    rx, ry = a[:, W_X] - a[:, W_START_X], a[:, W_Y] - a[:, W_START_Y]
+    hx, hy = a[:, W_START_HX], a[:, W_START_HY]
+    return rx * hx + ry * hy, hx * ry - hy * rx
+
+
+def reduce_path(acc: np.ndarray, commands: Sequence, envs_per_block: int, dt: float, constant: bool = True) -> List[Dict]:
+    """One "path" object per block of `envs_per_block` envs (a block per entry of `commands`), from the path accumulator ([nenv, 32],
+    include/odk.h ODK_PATH_*), in float64.  Per env, then {mean, std} over the block: `forward_m` and `lateral_m`, the displacement at the
+    env's last sample in its start frame; `heading_change_rad` (TURN: the sum of the sines of the per-step heading changes, within 1e-4
+    relative of the heading change at 50 Hz and |wz| <= 1 rad/s); `path_length_m`; `straightness`, displacement over length, over the envs
+    that covered at least MIN_COT_DISTANCE (None when nobody did).  `samples`: the block's samples.  `constant`: every env of a block held
+    the block's one command throughout; then `ideal` is the block's mean dead-reckoned pose (`ideal_pose` over each env's own SAMPLES * dt)
+    and `error_vs_ideal_m` the mean distance from the env's displacement to its own ideal one; both None otherwise (schedules, courses)."""
+    a = np.asarray(acc, np.float64).reshape(-1, PATH_NACC)
+    fwd_all, lat_all = path_frame(a)
+    E, dt = int(envs_per_block), float(dt)
+    out = []
+    for c, cmd in enumerate(commands):
+        sl = slice(c * E, (c + 1) * E)
+        blk, fwd, lat = a[sl], fwd_all[sl], lat_all[sl]
+        length = blk[:, W_LENGTH]
+        moved = length >= MIN_COT_DISTANCE
+        g = dict(samples=int(round(float(blk[:, W_SAMPLES].sum()))), forward_m=_mean_std(fwd), lateral_m=_mean_std(lat),
+                 heading_change_rad=_mean_std(blk[:, W_TURN]), path_length_m=_mean_std(length),
+                 straightness=_mean_std(np.hypot(fwd[moved], lat[moved]) / length[moved]) if moved.any() else None, ideal=None, error_vs_ideal_m=None)
+        if constant:
+            ix, iy, ipsi = ideal_pose(cmd, blk[:, W_SAMPLES] * dt)
+            g["ideal"] = dict(forward_m=float(ix.mean()), lateral_m=float(iy.mean()), heading_change_rad=float(ipsi.mean()))
+            g["error_vs_ideal_m"] = float(np.hypot(fwd - ix, lat - iy).mean())
+        out.append(g)
+    return out
+
+
+def reduce_course(acc: np.ndarray, courses: Sequence[Sequence[Sequence[float]]], envs_per_block: int, dt: float) -> List[Dict]:
+    """One "course" object per block of `envs_per_block` envs (a block per entry of `courses`: the block's points), from the path
+    accumulator, in float64.  `points`; `completed_fraction`, the share of the envs that reached every waypoint; `waypoints`: per waypoint
+    its `point`, `reached_fraction` and `time_to_reach_s`, the median over the envs that reached it of the step at which they did, times
+    dt (None when nobody did); `cross_track_rms_m` / `cross_track_peak_m`, over the block's samples with a waypoint still ahead, the RMS
+    and the maximum of the distance to the leg being walked (None without such a sample); `final_goal_distance_m`, the mean over the
+    envs with such a sample of the distance to the last waypoint at the latest of them (a completer's: where it was when it reached the
+    goal); `length_ratio`, the mean over the completers of path length over the course's polyline length from the origin (None without a
+    completer or for a course of zero length); `falls_by_leg`: entry i counts the envs that fell heading for waypoint i, the last entry
+    those that fell after the course was finished."""
+    a = np.asarray(acc, np.float64).reshape(-1, PATH_NACC)
+    E, dt = int(envs_per_block), float(dt)
+    out = []
+    for c, pts in enumerate(courses):
+        blk, n = a[c * E:(c + 1) * E], len(pts)
+        done = blk[:, W_WP_INDEX] >= n
+        steps = blk[:, W_REACHED:W_REACHED + n]
+        wps = []
+        for i, p in enumerate(pts):
+            hit = steps[:, i] > 0
+            wps.append(dict(point=[float(x) for x in p], reached_fraction=float(hit.sum() / E),
+                            time_to_reach_s=float(np.median(steps[hit, i]) * dt) if hit.any() else None))
+        xn = blk[:, W_XTRACK_SAMPLES]
+        seen, total = xn > 0, float(xn.sum())
+        fell = blk[:, W_FELL] != 0
+        legs = np.clip(blk[fell, W_FELL_LEG].astype(np.int64), 0, n)
+        poly = course_length(pts)
+        out.append(dict(
+            points=[[float(x) for x in p] for p in pts], completed_fraction=float(done.sum() / E), waypoints=wps,
+            cross_track_rms_m=float(np.sqrt(blk[:, W_XTRACK_SQ].sum() / total)) if total > 0 else None,
+            cross_track_peak_m=float(blk[seen, W_XTRACK_PEAK].max()) if seen.any() else None,
+            final_goal_distance_m=_mean_or_none(blk[seen, W_GOAL_DIST]),
+            length_ratio=float((blk[done, W_LENGTH] / poly).mean()) if done.any() and poly > 0 else None,
+            falls_by_leg=[int((legs == i).sum()) for i in range(n + 1)]))
+    return out
+
+
+PATH_KEYS = ("samples", "forward_m", "lateral_m", "heading_change_rad", "path_length_m", "straightness", "ideal", "error_vs_ideal_m")
+COURSE_KEYS = ("points", "completed_fraction", "waypoints", "cross_track_rms_m", "cross_track_peak_m", "final_goal_distance_m", "length_ratio",
+               "falls_by_leg")
+COURSE_POINT_KEYS = ("point", "reached_fraction", "time_to_reach_s")
+
+
 def reduce_tracking(acc: np.ndarray, commands: Sequence[Sequence[float]], envs_per_command: int) -> List[Dict]:
     """The per-command rows of the report from the accumulator ([nenv, 12], include/odk.h ODK_TRACK_*).  Velocity statistics are over
     the velocity samples of the block's envs (the steps of their first episode that did not end it), pooled; the fall rate is the
@@ -1352,11 +1580,50 @@ def fall_report(env, falls: Dict) -> Report:
                                 save_falls_max=falls.get("save_max")))
 
 
+def path_report(env, constant: bool = True) -> Report:
+    """The odometry of every env in its start frame (`odk_path_begin` after the reset, `odk_path_accumulate` every step).  `constant`, for
+    `run`: every block holds one command throughout, so its "path" object carries the dead-reckoned `ideal`."""
+    acc = _zeros(env, PATH_NACC)
+    return Report("path", acc, lambda b, t: b.path_accumulate(acc, t), dict(path_acc=acc), zero=lambda: env.batch.path_begin(acc),
+                  reduce=lambda a, cmds, E: reduce_path(a, cmds, E, float(env.dt), constant), settings=dict(path=True))
+
+
+def waypoint_report(env, course: Dict) -> Report:
+    """`course`: a dict of `table` (`course_table`), `map` (`schedule_blocks`: env e's course), `radius`, `speed`, `turn_rate`, `gain`,
+    `slow_dist` (defaults: DEFAULT_WAYPOINT_*), and for `run` the `courses` and its `flags`.  `odk_waypoint_command_apply` writes entries
+    0..2 of the bound command tensor before the env's reset (a zeroed clock: the start pose) and before every step; the path accumulator
+    also follows the course."""
+    torch, acc = env.batch.torch, _zeros(env, PATH_NACC)
+    table = torch.as_tensor(np.ascontiguousarray(course["table"], np.float32)).to(acc.device).contiguous()
+    cmap = torch.as_tensor(np.ascontiguousarray(course["map"], np.int32)).to(acc.device).contiguous()
+    radius = float(course.get("radius", DEFAULT_WAYPOINT_RADIUS))
+    drive = (float(course.get("speed", DEFAULT_WAYPOINT_SPEED)), float(course.get("turn_rate", DEFAULT_WAYPOINT_TURN_RATE)),
+             float(course.get("gain", DEFAULT_WAYPOINT_GAIN)), float(course.get("slow_dist", DEFAULT_WAYPOINT_SLOW_DIST)))
+    courses = course.get("courses") or ()
+
+    def before_reset(batch, track_acc):      # the reset must find the first command: a zeroed clock, one apply launch, then the env
+        track_acc.zero_()
+        batch.waypoint_command_apply(table, cmap, track_acc, acc, *drive)
+
+    def reduce(a, cmds, E):      # the blocks: every course's, or each course's cells (as many blocks per course as `cmds` has per course)
+        cs = [c for c in courses for _ in range(len(cmds) // len(courses))]
+        return list(zip(reduce_path(a, cmds, E, float(env.dt), False), reduce_course(a, cs, E, float(env.dt))))
+
+    def put(block, value):
+        block["path"], block["course"] = value
+    return Report("path", acc, lambda b, t: b.path_accumulate(acc, t, table, cmap, radius), dict(path_acc=acc, course=table, course_map=cmap),
+                  reduce=reduce, put=put, zero=lambda: env.batch.path_begin(acc), drives=True, before_reset=before_reset,
+                  before_step=lambda b, t: b.waypoint_command_apply(table, cmap, t, acc, *drive),
+                  settings=dict(course.get("flags") or {}, path=True, waypoint_radius=radius, waypoint_speed=drive[0], waypoint_turn_rate=drive[1],
+                                waypoint_gain=drive[2], waypoint_slow_dist=drive[3], courses=len(courses)))
+
+
 class Tracker:
     """One tracking run on a bound command buffer: `step()` = policy + env step + the reports' accumulators + the tracking accumulator,
     captured as one graph.  `reports`: the `Report`s the step carries, in launch order; or (never both) the switches that make them in this
     order -- `kicks` with `push_at` / `push_tolerance`, `gait`, `posture` with `posture_tolerance`, `imitation`, `schedule` (the bound command
-    tensor is then written by the Tracker), `falls`.  A report's accumulator and device buffers are also the Tracker's attributes (below),
+    tensor is then written by the Tracker), `falls`, `path` or (never both) `waypoints` (`waypoint_report`'s dict: the follower writes the
+    bound command tensor).  A report's accumulator and device buffers are also the Tracker's attributes (below),
     None without the report.  `delays` ([num_envs] device int32, one action delay per env: 0, 1, 2, or -1 for the sampled one) are bound
     (`set_action_delays`) and kept; the step itself is unchanged.  Model parameters (`Batch.set_param`) are the caller's to set before `reset`."""
     def _shown(name):      # what the first report that has `name` in its `shown` holds there
@@ -1364,20 +1631,26 @@ class Tracker:
     push_acc, push_buf, kicks, counter = _shown("push_acc"), _shown("push_buf"), _shown("kicks"), _shown("counter")
     gait_acc, posture_acc, imitation_acc, period_steps = _shown("gait_acc"), _shown("posture_acc"), _shown("imitation_acc"), _shown("period_steps")
     response_acc, sched, sched_map, fall_acc, torque_limit = _shown("response_acc"), _shown("sched"), _shown("sched_map"), _shown("fall_acc"), _shown("torque_limit")
+    path_acc, course, course_map = _shown("path_acc"), _shown("course"), _shown("course_map")
 
     def __init__(self, env, net, use_graph: bool = True, kicks=None, push_at: int = DEFAULT_PUSH_AT, push_tolerance=DEFAULT_PUSH_TOLERANCE,
                  gait: bool = False, posture: bool = False, posture_tolerance: float = DEFAULT_POSTURE_TOLERANCE,
-                 imitation: bool = False, schedule: Optional[Dict] = None, falls: Optional[Dict] = None, delays=None, reports=None):
+                 imitation: bool = False, schedule: Optional[Dict] = None, falls: Optional[Dict] = None, delays=None, reports=None, path: bool = False,
+                 waypoints: Optional[Dict] = None):
         import torch
         self.env, self.net, self.torch = env, net, torch
         self.acc = torch.zeros(env.num_envs, NACC, device=env.batch.obs.device)
-        if reports is not None and (kicks is not None or gait or posture or imitation or schedule is not None or falls is not None):
+        if reports is not None and (kicks is not None or gait or posture or imitation or schedule is not None or falls is not None or path
+                                    or waypoints is not None):
             raise ValueError("Tracker: give the reports or the switches that make them, not both")
+        if path and waypoints is not None:
+            raise ValueError("Tracker: `waypoints` carries the path report: give one of `path` and `waypoints`")
         if reports is None:
             reports = [make() for on, make in (
                 (kicks is not None, lambda: push_report(env, kicks, push_at, push_tolerance)), (gait, lambda: gait_report(env)),
                 (posture, lambda: posture_report(env, posture_tolerance)), (imitation, lambda: imitation_report(env)),
-                (schedule is not None, lambda: response_report(env, schedule)), (falls is not None, lambda: fall_report(env, falls))) if on]
+                (schedule is not None, lambda: response_report(env, schedule)), (falls is not None, lambda: fall_report(env, falls)),
+                (path, lambda: path_report(env)), (waypoints is not None, lambda: waypoint_report(env, waypoints))) if on]
         self.reports = list(reports)
         self.delays = None
         if delays is not None:
@@ -1432,8 +1705,11 @@ class Tracker:
 
 def run(args, out=sys.stdout) -> Dict:
     import torch
+    way = waypoints_from_args(args)            # None without --waypoints; refusals before any batch work
     schedules = schedules_from_args(args)      # None without --sequence / --then; refusals before any batch work
-    if schedules is not None:
+    if way is not None:
+        commands = [[0.0] * 7 for _ in way["courses"]]      # a course row's `command`: the follower writes vx, vy, wz, the head entries stay 0
+    elif schedules is not None:
         commands = [list(s[0]["command"]) for s in schedules]      # a schedule row's `command` is segment 0's
     else:
         commands = [command_row(c) for c in (args.command or [])]
@@ -1462,6 +1738,10 @@ def run(args, out=sys.stdout) -> Dict:
         print(motion.describe(), file=sys.stderr)      # stdout may carry the JSON report
     if hasattr(env, "describe_head_joints"):
         print(env.describe_head_joints(), file=sys.stderr)
+    if way is not None:
+        why = waypoint_limits_refusal(way["speed"], way["turn_rate"], env.batch.cfg.cmd_range)
+        if why:
+            raise SystemExit(why)
     try:      # what the reductions need of the robot, before the checkpoint is read
         head = posture_head_map(env) if getattr(args, "posture", False) else None
         imitation_info = imitation_joint_info(env) if imitation else None
@@ -1504,6 +1784,10 @@ def run(args, out=sys.stdout) -> Dict:
                      tilt=float(getattr(args, "fall_tilt", DEFAULT_FALL_TILT)), save=getattr(args, "save_falls", None),
                      save_max=int(getattr(args, "save_falls_max", DEFAULT_SAVE_FALLS_MAX)))
         reports.append(fall_report(env, falls))
+    if way is not None:
+        reports.append(waypoint_report(env, dict(way, table=course_table(way["courses"]), map=schedule_blocks(len(way["courses"]), ncell * E))))
+    elif getattr(args, "path", False):
+        reports.append(path_report(env, constant=schedules is None))
     tr = Tracker(env, net, delays=delays_t, reports=reports)
     reports = sorted(reports, key=lambda r: not r.drives)      # the report's order: pushes and schedules first (a stable sort)
     nobs = env.observation_size["state"][0]
@@ -1666,6 +1950,28 @@ def build_parser() -> argparse.ArgumentParser:
                         "[k, ring, nq] in time order, zero-padded at the front, valid [k], steps, env, row, fall_step, command and dt; "
                         "qpos[i, ring - valid[i]:] replays like --save_qpos")
     p.add_argument("--save_falls_max", type=int, default=DEFAULT_SAVE_FALLS_MAX, metavar="K", help="clips kept per row (cell); read by --save_falls only")
+    p.add_argument("--path", action="store_true",
+                   help="add a \"path\" object to every command row (push cell, plant cell, schedule row): where did it end up?  The base pose is "
+                        "integrated on the device in each env's start frame (the pose right after the reset): forward and lateral displacement, heading "
+                        "change, path length and straightness, each as mean and std over the envs, and for a row with one constant command the "
+                        "dead-reckoned ideal pose and the mean distance to it.  Any robot, both tasks, every other flag")
+    p.add_argument("--waypoints", type=str, action="append", metavar="COURSE",
+                   help="a course for the waypoint follower: \"0.5,0 | 0.5,0.5 | 0,0.5 | 0,0\" -- 1 to 8 points x,y in metres in each env's start "
+                        "frame, apart by |; repeat for more courses.  Each is one row of the report with \"path\" and \"course\": per waypoint the "
+                        "share of envs that reached it and when, the cross-track error, the distance left to the goal, the path length against the "
+                        "course's and the falls by leg.  The follower writes vx and wz of the command inside the captured step.  A course that begins "
+                        "with a minus sign is written --waypoints=\"-0.05,0.05 | ...\" (argparse reads a bare one as a flag).  Implies --path; not "
+                        "with --command / --grid / --sequence / --then, pushes or --posture")
+    p.add_argument("--waypoint_radius", type=float, default=DEFAULT_WAYPOINT_RADIUS, metavar="M",
+                   help="the distance (m) within which a waypoint counts as reached (BUILD-DEFINED default, a controller setting)")
+    p.add_argument("--waypoint_speed", type=float, default=DEFAULT_WAYPOINT_SPEED, metavar="MPS",
+                   help="the follower's cruise speed (m/s, within the env's vx command range; BUILD-DEFINED default)")
+    p.add_argument("--waypoint_turn_rate", type=float, default=DEFAULT_WAYPOINT_TURN_RATE, metavar="RADPS",
+                   help="the follower's largest yaw-rate command (rad/s, within the env's wz command range; BUILD-DEFINED default)")
+    p.add_argument("--waypoint_gain", type=float, default=DEFAULT_WAYPOINT_GAIN, metavar="G",
+                   help="yaw-rate command per unit sine of the heading error (rad/s; BUILD-DEFINED default)")
+    p.add_argument("--waypoint_slow_dist", type=float, default=DEFAULT_WAYPOINT_SLOW_DIST, metavar="M",
+                   help="the distance (m) from the LAST waypoint inside which the speed command falls linearly to 0 (BUILD-DEFINED default)")
     p.add_argument("--episode_length", type=int, default=1000)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--device", type=int, default=0)
