@@ -626,6 +626,53 @@ int odk_waypoint_command_apply(const odk_batch* b, const float* course_dev, int 
                                const float* track_acc_dev, const float* path_acc_dev, float v_cruise, float turn_rate, float heading_gain,
                                float slow_dist, void* stream);
 
+/* Sensor faults: a stage between the observation the env kernels wrote and the policy that reads it, which makes the row look like what
+ * a faulty robot's sensors would deliver -- a tilted, biased, mis-scaled or late IMU, late, offset or quantised encoders, a foot switch
+ * that sticks.  One launch, a 16-lane row per env (lane = actuator for the joint columns, lanes 0..5 the IMU, lanes 6..7 the foot
+ * switches), graph-capturable, no LDS, no scratch.  It is OUT OF PLACE: obs_dev (the step's observation, [nenv, nobs]) is only read and
+ * obs_out_dev must not overlap it; the env kernels, the privileged row and with it every report keep their meaning under a fault.  nu,
+ * nobs and the env kind are the batch's.  The columns it touches (csrc/odk_obs_layout.h obs_at): gyro [3] at 0, accelerometer [3] at 3,
+ * joint positions [nu] at 13, joint velocities [nu] at 13 + nu, contacts [2] at 13 + 6 nu (Joystick) or 13 + 5 nu (Standing).  Every other
+ * column -- command, the three action memories, motor targets, phase -- is copied through bit for bit.
+ *
+ * Env e's row of fault_dev [nenv, ODK_SENSOR_NPRM]:
+ *   IMU_ROT[9]       row-major mounting rotation R, applied to gyro and accelerometer (built on the host: no sin / cos runs on the device)
+ *   GYRO_SCALE, GYRO_BIAS[3], ACC_SCALE, ACC_BIAS[3]   out = scale (R x) + bias
+ *   IMU_DELAY, JOINT_DELAY   whole steps; the kernel clamps them into 0 .. ODK_SENSOR_RING - 1 (NaN: 0) and drops a fraction.  IMU_DELAY
+ *                    covers gyro and accelerometer, JOINT_DELAY joint positions and velocities
+ *   ENC_QUANT        q > 0: position = q rintf(position / q), after the offset; otherwise off
+ *   CONTACT_MODE[2]  0 = pass through, 1 = stuck at 0, 2 = stuck at 1 (any other value passes through); left foot, then right foot
+ *   ENC_OFFSET[16]   per-actuator additive zero error on the joint-position columns
+ * Slots 22 .. 31 are not read.  The NOMINAL row is R = identity, both scales 1 and 0 elsewhere, and it hands back the input's bits for
+ * every value, -0.0, NaN and +-inf included: a stage whose parameters are nominal is skipped by a select, never computed (1 x + 0 would
+ * turn -0.0 into +0.0, 0 inf is NaN).  The stages, each with its own select: the rotation when R is not exactly the identity, a scale
+ * when it is not 1, a bias or an offset when it is not 0, the quantiser when q > 0.
+ *
+ * Env e's row of state_dev [nenv, ODK_SENSOR_NSTATE] (zeroed by the caller before an episode's first call): slot ODK_SENSOR_HEAD is the
+ * number of samples since the last refill (slots 1 .. 15 are not touched), then a ring of the last ODK_SENSOR_RING RAW samples of
+ * ODK_SENSOR_SAMPLE floats each: gyro [3] and accelerometer [3] at ODK_SENSOR_S_IMU (the ten floats behind them are not touched), joint
+ * positions [16] at ODK_SENSOR_S_JOINT_POS and joint velocities [16] at ODK_SENSOR_S_JOINT_VEL (0 in the entries past nu).  The ring holds
+ * raw values: its contents do not depend on the fault row.  Order per call: when HEAD is 0 or done_dev[e] != 0 (done_dev may be NULL) EVERY
+ * slot is filled with the current sample and HEAD becomes 1 -- the observation after a done step is the new episode's first one, and a
+ * delayed sensor then shows it, not zeros (BUILD-DEFINED: the reference zero-fills its imu_history, and a zero accelerometer is no
+ * plausible reading) -- otherwise the sample goes to slot HEAD mod ODK_SENSOR_RING and HEAD grows by 1 (a float: exact for 2^24 samples);
+ * then the sample `delay` slots back is taken; then rotation, scale and bias (IMU), or offset and quantiser (encoders).
+ * Arithmetic is float32 + * / and rintf with every product rounded before it is added (no fused multiply-add), R x summed left to right:
+ * a numpy restatement has every bit.  Refused (ODK_ERR_INVALID, nothing launched): a null pointer other than done_dev (the message names
+ * the argument), obs_out_dev overlapping obs_dev, a model with more than 16 actuators. */
+#define ODK_SENSOR_NPRM 48
+#define ODK_SENSOR_RING 8
+#define ODK_SENSOR_SAMPLE 48
+#define ODK_SENSOR_NSTATE (16 + ODK_SENSOR_RING * ODK_SENSOR_SAMPLE)
+enum { ODK_SENSOR_IMU_ROT = 0 /* [9] */, ODK_SENSOR_GYRO_SCALE = 9, ODK_SENSOR_GYRO_BIAS = 10 /* [3] */, ODK_SENSOR_ACC_SCALE = 13,
+       ODK_SENSOR_ACC_BIAS = 14 /* [3] */, ODK_SENSOR_IMU_DELAY = 17, ODK_SENSOR_JOINT_DELAY = 18, ODK_SENSOR_ENC_QUANT = 19,
+       ODK_SENSOR_CONTACT_MODE = 20 /* [2]; 22..31 are not read */, ODK_SENSOR_ENC_OFFSET = 32 /* [16] */ };
+enum { ODK_SENSOR_HEAD = 0 /* 1..15 are not touched */, ODK_SENSOR_RING_AT = 16 /* the ring's first slot */, ODK_SENSOR_S_IMU = 0 /* [6] */,
+       ODK_SENSOR_S_JOINT_POS = 16 /* [16] */, ODK_SENSOR_S_JOINT_VEL = 32 /* [16] */ };
+int odk_sensor_apply(const odk_batch* b, const float* obs_dev /* [nenv, nobs], the step's */, const float* done_dev /* may be NULL */,
+                     const float* fault_dev /* [nenv, ODK_SENSOR_NPRM] */, float* state_dev /* [nenv, ODK_SENSOR_NSTATE] */,
+                     float* obs_out_dev /* [nenv, nobs], must not alias obs_dev */, void* stream);
+
 /* mjx_env.step alone (physics only, n_substeps, ctrl = ctrl_dev [nenv, nu]); for parity tests */
 int odk_physics_step(odk_batch* b, const float* ctrl_dev, int n_substeps, void* stream);
 

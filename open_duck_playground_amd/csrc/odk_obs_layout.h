@@ -4,9 +4,13 @@
 #pragma once
 namespace odk {
 namespace obs_at {   // observed side, offsets into the row (both tasks)
+constexpr int GYRO = 0, ACCELEROMETER = 3;                       // [3] each
 constexpr int COMMAND = 6;                                       // [7]
+constexpr int JOINT_POS = 13;                                    // [nu] angle minus default
+constexpr int joint_vel(int nu) { return 13 + nu; }              // [nu]
 constexpr int last_act(int nu) { return 13 + 2 * nu; }           // [nu]
 constexpr int last_last_act(int nu) { return 13 + 3 * nu; }      // [nu]
+constexpr int contact(int nu, bool joystick) { return 13 + (joystick ? 6 : 5) * nu; }   // [2] left, right (Standing's row has no motor targets)
 }  // namespace obs_at
 namespace priv_at {   // privileged tail, offsets from the row's float nobs (both tasks up to the reference frame, which only Joystick has)
 constexpr int GYRO = 0, ACCELEROMETER = 3, GRAVITY = 6, LOCAL_LINVEL = 9, GLOBAL_ANGVEL = 12;   // [3] each

@@ -1,5 +1,5 @@
 // odk_reports.hip -- the evaluation reports of include/odk.h (libodk.so): the accumulator kernels of the tracking / push / gait / posture /
-// imitation / response / fall / path reports, the command-schedule kernel and the waypoint follower, with their C entry points.  They read
+// imitation / response / fall / path reports, the command-schedule kernel, the waypoint follower and the sensor-fault stage, with their C entry points.  They read
 // finished observation rows (odk_obs_layout.h) and the batch (odk_batch.h: read-only here; its state is odk_engine.hip's); no compiled shape.
 // gfx950 only, no CPU fallback.
 #include <hip/hip_runtime.h>
@@ -793,6 +793,107 @@ extern "C" int odk_waypoint_command_apply(const odk_batch* b, const float* cours
   hipLaunchKernelGGL(waypoint_apply_kernel, g.grid, dim3(256), 0, (hipStream_t)stream, b->d_recs, b->rec_size, track_acc_dev, path_acc_dev,
                      course_dev, ncourse, course_of_env_dev, v_cruise, turn_rate, heading_gain, slow_dist, const_cast<float*>(b->d_cmd),
                      b->cmd_stride, b->nenv);
+  HIPCHK(hipGetLastError());
+  return ODK_OK;
+}
+
+// ---- sensor faults (include/odk.h "Sensor faults": the definitions this kernel restates).  Not a report: the stage between the observation
+// the step wrote and the policy.  gait_kernel's layout -- a 16-lane row per env, four envs per wave -- without its row sums, so a row past
+// nenv leaves at once.  Lane = actuator for the joint columns and their ring entries (contiguous 64-byte accesses), lanes 0..5 carry gyro and
+// accelerometer, lanes 6..7 the foot switches, and the columns nothing touches go through in ceil(nobs / 16) passes of consecutive lanes on
+// consecutive floats: every float of the output row is stored exactly once.  The delayed sample is loaded before this call's sample is
+// stored, and from a slot this call does not store to (delay 0 and a refill take the current values from registers), so no lane reads what
+// this launch wrote.  Out of place, no LDS, no scratch; contraction is off and every nominal stage is a select, so a numpy restatement has the bits.
+__global__ void __launch_bounds__(256) sensor_kernel(const float* __restrict__ obs, int nobs, int nu, int contact_at, const float* __restrict__ done,
+                                                     const float* __restrict__ fault, float* __restrict__ state, float* __restrict__ out, int nenv) {
+#pragma clang fp contract(off)
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int e = t >> 4, u = t & 15;
+  if (e >= nenv) return;
+  const float* X = obs + (size_t)e * nobs;
+  const float* F = fault + (size_t)e * ODK_SENSOR_NPRM;
+  float* S = state + (size_t)e * ODK_SENSOR_NSTATE;
+  float* Y = out + (size_t)e * nobs;
+  const int jv_at = obs_at::joint_vel(nu);
+  // the columns nothing touches
+  for (int j = u; j < nobs; j += 16) {
+    const bool touched = j < obs_at::COMMAND || (j >= obs_at::JOINT_POS && j < jv_at + nu) || (j >= contact_at && j < contact_at + 2);
+    if (!touched) Y[j] = X[j];
+  }
+  // the ring (per env: the same in the row's 16 lanes)
+  const float n0 = S[ODK_SENSOR_HEAD];
+  const bool refill = n0 == 0.0f || (done && done[e] != 0.0f);
+  const int cur = refill ? 0 : (int)((unsigned)(int)n0 % (unsigned)ODK_SENSOR_RING);   // (unsigned: a row the caller did not zero still lands inside its ring)
+  const int di = (int)fminf(fmaxf(F[ODK_SENSOR_IMU_DELAY], 0.0f), (float)(ODK_SENSOR_RING - 1));
+  const int dj = (int)fminf(fmaxf(F[ODK_SENSOR_JOINT_DELAY], 0.0f), (float)(ODK_SENSOR_RING - 1));
+  float* R = S + ODK_SENSOR_RING_AT;
+  const float* Si = R + ((cur + ODK_SENSOR_RING - di) & (ODK_SENSOR_RING - 1)) * ODK_SENSOR_SAMPLE + ODK_SENSOR_S_IMU;   // the slot di steps back
+  const float* Sj = R + ((cur + ODK_SENSOR_RING - dj) & (ODK_SENSOR_RING - 1)) * ODK_SENSOR_SAMPLE;
+  const bool imu_now = refill || di == 0, joint_now = refill || dj == 0, imu = u < 6, act = u < nu;
+  // this step's raw sample, lane u's part (0 in the joint entries past nu), and the delayed one
+  const float raw_i = imu ? X[obs_at::GYRO + u] : 0.0f;
+  const float raw_p = act ? X[obs_at::JOINT_POS + u] : 0.0f, raw_v = act ? X[jv_at + u] : 0.0f;
+  const int base = u < 3 ? 0 : 3;                  // gyro or accelerometer: the vector lane u's component belongs to
+  const float* V = imu_now ? X + obs_at::GYRO + base : Si + base;
+  const float v0 = imu ? V[0] : 0.0f, v1 = imu ? V[1] : 0.0f, v2 = imu ? V[2] : 0.0f;
+  const float old_p = Sj[ODK_SENSOR_S_JOINT_POS + u], old_v = Sj[ODK_SENSOR_S_JOINT_VEL + u];
+  float p = joint_now ? raw_p : old_p;
+  const float v = joint_now ? raw_v : old_v;
+  for (int s = refill ? 0 : cur; s < (refill ? ODK_SENSOR_RING : cur + 1); s++) {
+    float* W = R + s * ODK_SENSOR_SAMPLE;
+    if (imu) W[ODK_SENSOR_S_IMU + u] = raw_i;
+    W[ODK_SENSOR_S_JOINT_POS + u] = raw_p;
+    W[ODK_SENSOR_S_JOINT_VEL + u] = raw_v;
+  }
+  if (u == ODK_SENSOR_HEAD) S[u] = refill ? 1.0f : n0 + 1.0f;
+  // the IMU: out = scale (R x) + bias, component i of its vector in lane u
+  if (imu) {
+    const int i = u - base;
+    bool ident = true;
+#pragma unroll
+    for (int k = 0; k < 9; k++) ident = ident && F[ODK_SENSOR_IMU_ROT + k] == ((k & 3) == 0 ? 1.0f : 0.0f);
+    const float* Ri = F + ODK_SENSOR_IMU_ROT + 3 * i;
+    const float rot = (Ri[0] * v0 + Ri[1] * v1) + Ri[2] * v2;
+    float r = ident ? (i == 0 ? v0 : (i == 1 ? v1 : v2)) : rot;
+    const float scale = F[base ? ODK_SENSOR_ACC_SCALE : ODK_SENSOR_GYRO_SCALE];
+    const float bias = F[(base ? ODK_SENSOR_ACC_BIAS : ODK_SENSOR_GYRO_BIAS) + i];
+    r = scale != 1.0f ? scale * r : r;
+    r = bias != 0.0f ? r + bias : r;
+    Y[obs_at::GYRO + u] = r;
+  }
+  // the encoders: offset, then the quantiser; the velocities are only late
+  if (act) {
+    const float off = F[ODK_SENSOR_ENC_OFFSET + u], q = F[ODK_SENSOR_ENC_QUANT];
+    p = off != 0.0f ? p + off : p;
+    p = q > 0.0f ? q * rintf(p / q) : p;
+    Y[obs_at::JOINT_POS + u] = p;
+    Y[jv_at + u] = v;
+  }
+  // the foot switches
+  if (u == 6 || u == 7) {
+    const float mode = F[ODK_SENSOR_CONTACT_MODE + u - 6], c = X[contact_at + u - 6];
+    Y[contact_at + u - 6] = mode == 1.0f ? 0.0f : (mode == 2.0f ? 1.0f : c);
+  }
+}
+
+extern "C" int odk_sensor_apply(const odk_batch* b, const float* obs_dev, const float* done_dev, const float* fault_dev, float* state_dev,
+                                float* obs_out_dev, void* stream) {
+  const char* fn = "odk_sensor_apply";
+  if (!b) return fail(ODK_ERR_INVALID, "%s: null batch", fn);
+  if (!obs_dev) return fail(ODK_ERR_INVALID, "%s: null obs_dev", fn);
+  if (!fault_dev) return fail(ODK_ERR_INVALID, "%s: null fault_dev", fn);
+  if (!state_dev) return fail(ODK_ERR_INVALID, "%s: null state_dev", fn);
+  if (!obs_out_dev) return fail(ODK_ERR_INVALID, "%s: null obs_out_dev", fn);
+  static_assert(ODK_SENSOR_S_JOINT_VEL + 16 == ODK_SENSOR_SAMPLE && ODK_SENSOR_ENC_OFFSET + 16 == ODK_SENSOR_NPRM &&
+                (ODK_SENSOR_RING & (ODK_SENSOR_RING - 1)) == 0, "one lane per actuator, a ring the mask wraps");
+  const int nu = b->model.h.nu;
+  if (int rc = fits_row16(fn, nu)) return rc;
+  Launch g; if (int rc = launch_on(b, 16, &g)) return rc;
+  const size_t n = (size_t)b->nenv * g.nobs;
+  if (obs_out_dev < obs_dev + n && obs_dev < obs_out_dev + n)
+    return fail(ODK_ERR_INVALID, "%s: obs_out_dev overlaps obs_dev (the stage is out of place: the step's observation is only read)", fn);
+  hipLaunchKernelGGL(sensor_kernel, g.grid, dim3(256), 0, (hipStream_t)stream, obs_dev, g.nobs, nu,
+                     obs_at::contact(nu, b->cfg.env_kind == ODK_ENV_JOYSTICK), done_dev, fault_dev, state_dev, obs_out_dev, b->nenv);
   HIPCHK(hipGetLastError());
   return ODK_OK;
 }

@@ -190,6 +190,7 @@ def load_library() -> C.CDLL:
     L.odk_path_begin.argtypes = [P, P, P]
     L.odk_path_accumulate.argtypes = [P, P, P, P, P, C.c_int, P, C.c_float, P, P]
     L.odk_waypoint_command_apply.argtypes = [P, P, C.c_int, P, P, P, C.c_float, C.c_float, C.c_float, C.c_float, P]
+    L.odk_sensor_apply.argtypes = [P, P, P, P, P, P, P]
     L.odk_batch_get_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_set_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_get_debug.argtypes = [P, FP, FP, FP, FP]
@@ -236,7 +237,7 @@ EXPORTED_SYMBOLS = (
     "odk_batch_bind_commands", "odk_batch_set_reward_terms", "odk_batch_bind_reward_metrics", "odk_batch_set_imitation_joints", "odk_batch_set_head_joints",
     "odk_tracking_accumulate", "odk_batch_bind_pushes", "odk_batch_bind_action_delays", "odk_push_accumulate", "odk_gait_accumulate", "odk_posture_accumulate",
     "odk_imitation_accumulate", "odk_command_schedule_apply", "odk_response_accumulate", "odk_fall_row_floats", "odk_fall_accumulate",
-    "odk_path_begin", "odk_path_accumulate", "odk_waypoint_command_apply",
+    "odk_path_begin", "odk_path_accumulate", "odk_waypoint_command_apply", "odk_sensor_apply",
     "odk_batch_get_state", "odk_batch_set_state", "odk_batch_get_debug", "odk_set_debug_dump", "odk_batch_lds_size",
     "odk_batch_get_lds", "odk_lds_offset", "odk_batch_record_size", "odk_batch_get_records", "odk_batch_set_records", "odk_batch_timing", "odk_gae", "odk_ppo_head",
     "odk_policy_sample", "odk_adam_clip", "odk_silu_bwd_colsum", "odk_colsum_partial", "odk_colsum_finalize", "odk_gather_rows", "odk_dw_gemm",
@@ -327,6 +328,37 @@ PATH_MAX_WAYPOINTS = 8
 PATH_COURSE_FLOATS = 1 + 2 * PATH_MAX_WAYPOINTS
 (PATH_START_X, PATH_START_Y, PATH_START_HX, PATH_START_HY, PATH_X, PATH_Y, PATH_HX, PATH_HY, PATH_LENGTH, PATH_TURN, PATH_SAMPLES, PATH_FELL,
  PATH_FELL_LEG, PATH_WP_INDEX, PATH_XTRACK_SAMPLES, PATH_XTRACK_SQ, PATH_XTRACK_PEAK, PATH_GOAL_DIST, PATH_REACHED) = range(19)
+
+# odk_sensor_apply's rows (include/odk.h ODK_SENSOR_*): a fault row of SENSOR_NPRM floats per env ([9] = row-major rotation, [3] = x, y, z,
+# [2] = left / right foot, [16] = per actuator), and a state row of SENSOR_NSTATE floats: the head, then a ring of SENSOR_RING raw samples
+# of SENSOR_SAMPLE floats (the SENSOR_S_* offsets inside one)
+SENSOR_NPRM = 48
+SENSOR_RING = 8
+SENSOR_SAMPLE = 48
+SENSOR_NSTATE = 16 + SENSOR_RING * SENSOR_SAMPLE
+(SENSOR_IMU_ROT, SENSOR_GYRO_SCALE, SENSOR_GYRO_BIAS, SENSOR_ACC_SCALE, SENSOR_ACC_BIAS, SENSOR_IMU_DELAY, SENSOR_JOINT_DELAY, SENSOR_ENC_QUANT,
+ SENSOR_CONTACT_MODE, SENSOR_ENC_OFFSET) = 0, 9, 10, 13, 14, 17, 18, 19, 20, 32
+SENSOR_HEAD, SENSOR_RING_AT, SENSOR_S_IMU, SENSOR_S_JOINT_POS, SENSOR_S_JOINT_VEL = 0, 16, 0, 16, 32
+
+
+def sensor_fault_rows(n: int) -> np.ndarray:
+    """[n, SENSOR_NPRM] float32 all-nominal fault rows to fill in: the identity rotation, both scales 1, zeros elsewhere.  `odk_sensor_apply`
+    hands back the input's bits under such a row."""
+    rows = np.zeros((int(n), SENSOR_NPRM), np.float32)
+    rows[:, SENSOR_IMU_ROT:SENSOR_IMU_ROT + 9] = np.eye(3, dtype=np.float32).reshape(9)
+    rows[:, SENSOR_GYRO_SCALE] = rows[:, SENSOR_ACC_SCALE] = 1.0
+    return rows
+
+
+def sensor_rotation(roll_deg: float, pitch_deg: float, yaw_deg: float) -> np.ndarray:
+    """The float32 [3, 3] mounting rotation of an IMU tilted by roll (about x), pitch (about y) and yaw (about z), in degrees:
+    R = Rx(roll)^T Ry(pitch)^T Rz(yaw)^T = (Rz Ry Rx)^T, the matrix that takes a base-frame vector into the frame of a sensor whose axes are
+    the base's turned by Rz Ry Rx.  Computed in float64 and rounded once; all zeros give the exact identity (a nominal row's)."""
+    r, p, y = (np.deg2rad(float(a)) for a in (roll_deg, pitch_deg, yaw_deg))
+    rx = np.array([[1, 0, 0], [0, np.cos(r), -np.sin(r)], [0, np.sin(r), np.cos(r)]])
+    ry = np.array([[np.cos(p), 0, np.sin(p)], [0, 1, 0], [-np.sin(p), 0, np.cos(p)]])
+    rz = np.array([[np.cos(y), -np.sin(y), 0], [np.sin(y), np.cos(y), 0], [0, 0, 1]])
+    return (rz @ ry @ rx).T.astype(np.float32)
 
 
 def check_pushes(push, nenv: int, device: int) -> None:
@@ -1312,6 +1344,35 @@ class Batch:
             raise OdkError("waypoint_command_apply: no commands bound (bind_commands)")
         _chk(self.L.odk_waypoint_command_apply(self._b, C.c_void_p(course.data_ptr()), ncourse, C.c_void_p(course_of_env.data_ptr()),
                                                C.c_void_p(track_acc.data_ptr()), C.c_void_p(path_acc.data_ptr()), *args, self._stream()))
+
+    @staticmethod
+    def sensor_fault_rows(n: int) -> np.ndarray:
+        """`sensor_fault_rows(n)`: [n, SENSOR_NPRM] float32 all-nominal fault rows to fill in."""
+        return sensor_fault_rows(n)
+
+    def sensor_apply(self, obs, done, fault, state, out):
+        """One `odk_sensor_apply` launch: `out` ([nenv, nobs] float32) <- `obs` (the step's observation, only read) as env e's faulty sensors
+        would deliver it -- `fault` ([nenv, SENSOR_NPRM], `sensor_fault_rows` to fill in) names the fault, `state` ([nenv, SENSOR_NSTATE], zeroed
+        before an episode's first call) holds the ring of raw samples the delays read, `done` ([nenv], or None) refills it.  Gyro,
+        accelerometer, joint positions and velocities and the two contacts are touched, every other column is copied bit for bit, and an
+        all-nominal `fault` copies the whole row bit for bit.  `out` must not share memory with `obs`."""
+        import torch
+        check_accumulator("sensor_apply: obs", obs, self.nenv, self.nobs, self.device)
+        check_accumulator("sensor_apply: out", out, self.nenv, self.nobs, self.device)
+        check_accumulator("sensor_apply: fault", fault, self.nenv, SENSOR_NPRM, self.device)
+        check_accumulator("sensor_apply: state", state, self.nenv, SENSOR_NSTATE, self.device)
+        if done is not None:
+            if not torch.is_tensor(done) or tuple(done.shape) != (self.nenv,):
+                raise OdkError(f"sensor_apply: done: expected a torch tensor of shape ({self.nenv},) or None, got "
+                               f"{tuple(done.shape) if hasattr(done, 'shape') else type(done).__name__}")
+            _check_placement("sensor_apply: done", done, torch.float32, self.device)
+        lo, hi = obs.data_ptr(), obs.data_ptr() + obs.numel() * 4
+        if out is obs or (out.data_ptr() < hi and lo < out.data_ptr() + out.numel() * 4):
+            raise OdkError("sensor_apply: out shares memory with obs (the stage is out of place: the step's observation is only read)")
+        if self.model.nu > 16:
+            raise OdkError(f"sensor_apply: the model has {self.model.nu} actuators, a row holds 16")
+        _chk(self.L.odk_sensor_apply(self._b, C.c_void_p(obs.data_ptr()), _ptr(done), C.c_void_p(fault.data_ptr()), C.c_void_p(state.data_ptr()),
+                                     C.c_void_p(out.data_ptr()), self._stream()))
 
     def physics_step(self, ctrl, n_substeps: int = 10):
         assert ctrl.is_cuda and ctrl.dtype == self.torch.float32 and ctrl.is_contiguous() and tuple(ctrl.shape) == (self.nenv, self.model.nu)

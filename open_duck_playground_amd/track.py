@@ -134,6 +134,24 @@ to the goal, the path length against the course's and the falls by leg (`reduce_
 `--waypoint_turn_rate`, `--waypoint_gain` and `--waypoint_slow_dist` are the follower's settings.  `--waypoints` implies `--path`; it combines
 with plants, `--gait`, `--falls` and `--imitation_report`, and not with `--command` / `--grid` (the course is the command), `--sequence` /
 `--then` (two writers of the command tensor), pushes or `--posture`.  Without these flags nothing changes.
+
+Sensor faults (what does it tolerate on the sensor side? -- a biased, tilted or late IMU, encoders with a zero error or a coarse step, a
+foot switch that sticks: everyday faults of this robot that training never showed the policy, see INTEGRATION.md "Sensor faults"):
+
+    python -m open_duck_playground_amd.track --checkpoint <ckpt> --command 0.1 0 0 --sensor_grid imu_delay=0:7:8,gyro_bias_y=-0.3:0.3:5 --falls
+    python -m open_duck_playground_amd.track --checkpoint <ckpt> --grid vx=-0.15:0.15:3 --sensor acc_bias_x=1.3 --sensor contact_left=off --sensor encoder_offset=0.05
+
+`--sensor KEY=V[,KEY=V...]` (repeatable) and `--sensor_grid` (a cross product, `--grid`'s syntax) name sensor settings (`sensors.SENSOR_KEYS`);
+every (command, sensor) cell gets `--envs_per_command` envs, command blocks outermost (`sensors.sensor_blocks`, the plants' layout).  One
+launch joins the captured step, in front of the policy: `odk_sensor_apply` reads the observation the env step wrote -- which stays what the
+policy trained on, the env's own noise included -- and writes what each env's faulty sensors would deliver into a tensor of the Tracker's,
+which the policy reads instead.  The env, physics and report kernels are untouched, and every report reads the noise-free privileged
+row, so each keeps its meaning: a fault changes what the policy sees, the reports measure what the robot then does.  Every command row
+gains "sensors" -- per cell a whole command row of its own plus "sensor", its settings -- and "sensor_robustness": `reduce_robustness` per
+swept key with the other keys nearest their nominal, `survived_range` around the key's own nominal (0, 1 for the scales, `ok` for the foot
+switches).  `--gait`, `--falls`, `--path`, `--posture`, `--imitation_report`, `--sequence` / `--then`, `--waypoints`, `--randomize` and
+`--noise_level` combine with it (one object per cell too); pushes and plants do not (a third cell axis).  `--save_obs` then saves the row
+the policy read.  Without these flags nothing changes.
 """
 from __future__ import annotations
 
@@ -185,6 +203,9 @@ from .engine import (PATH_NACC, PATH_MAX_WAYPOINTS, PATH_COURSE_FLOATS, PATH_STA
                      PATH_TURN as W_TURN, PATH_SAMPLES as W_SAMPLES, PATH_FELL as W_FELL, PATH_FELL_LEG as W_FELL_LEG, PATH_WP_INDEX as W_WP_INDEX,
                      PATH_XTRACK_SAMPLES as W_XTRACK_SAMPLES, PATH_XTRACK_SQ as W_XTRACK_SQ, PATH_XTRACK_PEAK as W_XTRACK_PEAK,
                      PATH_GOAL_DIST as W_GOAL_DIST, PATH_REACHED as W_REACHED)      # ODK_PATH_*
+
+from .engine import SENSOR_NPRM, SENSOR_NSTATE      # ODK_SENSOR_*
+from .sensors import nominal_sensor, sensor_order, sensors_from_args, sensor_blocks      # --sensor / --sensor_grid: the settings and their per-env fault rows
 
 COMMAND_KEYS = ("vx", "vy", "wz", "neck_pitch", "head_pitch", "head_yaw", "head_roll")   # the order of cmd_range (include/odk.h)
 NACC = 12
@@ -469,28 +490,57 @@ def survived_range(values: Sequence[float], fall_rates: Sequence[float], thresho
 ROBUSTNESS_POINT_KEYS = ("value", "fall_rate", "rms_error_vx", "rms_error_vy", "rms_error_wz", "mean_episode_reward")
 
 
-def reduce_robustness(cells: Sequence[Dict], threshold: float) -> Dict:
+def reduce_robustness(cells: Sequence[Dict], threshold: float, key: str = "plant", nominals: Optional[Dict] = None,
+                      order: Optional[Callable] = None) -> Dict:
     """The "robustness" object of one command row from its plant cells (each a command row with "plant").  An axis is swept when the cells
     hold more than one value of it.  Per swept axis, under its name: the cells whose OTHER axes sit at their value nearest nominal (scale
     1; delay `random` if present, else the smallest), in increasing order of the axis (`random` first) -- `value`, `fall_rate`, the three
     RMS errors and `mean_episode_reward` each.  `survived_range`: per swept axis `survived_range()` of those points at `threshold`; for
-    `delay` over the fixed delays, starting from the smallest (`random` is not a point on that line).  `robust_fall_rate` is the threshold."""
+    `delay` over the fixed delays, starting from the smallest (`random` is not a point on that line).  `robust_fall_rate` is the threshold.
+    For cells of another kind (the sensor cells: `key` "sensor"): `nominals`, every axis with its own nominal value, and `order(axis,
+    value)`, a value's place on its axis' line as a number (default: the value itself).  Nearest nominal and `survived_range` are then taken
+    around the axis's own nominal, and a range's ends are the values of its end points (a name for an axis whose values are names)."""
+    if nominals is not None:
+        return _reduce_robustness_around(cells, threshold, key, nominals, order or (lambda axis, v: float(v)))
     distinct = {a: [] for a in PLANT_AXES}
     for cell in cells:
         for a in PLANT_AXES:
-            if cell["plant"][a] not in distinct[a]:
-                distinct[a].append(cell["plant"][a])
+            if cell[key][a] not in distinct[a]:
+                distinct[a].append(cell[key][a])
     swept = [a for a in PLANT_AXES if len(distinct[a]) > 1]
     base = {a: _nearest_nominal(a, distinct[a]) for a in PLANT_AXES}
     out: Dict = {"robust_fall_rate": float(threshold)}
     ranges: Dict = {}
     for axis in swept:
-        line = [c for c in cells if all(c["plant"][o] == base[o] for o in PLANT_AXES if o != axis)]
-        line.sort(key=lambda c: _delay_order(c["plant"][axis]) if axis == "delay" else float(c["plant"][axis]))
-        out[axis] = [dict(value=c["plant"][axis], **{k: c[k] for k in ROBUSTNESS_POINT_KEYS[1:]}) for c in line]
+        line = [c for c in cells if all(c[key][o] == base[o] for o in PLANT_AXES if o != axis)]
+        line.sort(key=lambda c: _delay_order(c[key][axis]) if axis == "delay" else float(c[key][axis]))
+        out[axis] = [dict(value=c[key][axis], **{k: c[k] for k in ROBUSTNESS_POINT_KEYS[1:]}) for c in line]
         pts = [p for p in out[axis] if p["value"] != DELAY_RANDOM]
         nominal = min(p["value"] for p in pts) if axis == "delay" and pts else 1.0
         ranges[axis] = survived_range([p["value"] for p in pts], [p["fall_rate"] for p in pts], threshold, nominal)
+    out["survived_range"] = ranges
+    return out
+
+
+def _reduce_robustness_around(cells: Sequence[Dict], threshold: float, key: str, nominals: Dict, order: Callable) -> Dict:
+    """`reduce_robustness` for cells whose axes each have a nominal of their own (`nominals`, in the axes' order)."""
+    axes = tuple(nominals)
+    distinct = {a: [] for a in axes}
+    for cell in cells:
+        for a in axes:
+            if cell[key][a] not in distinct[a]:
+                distinct[a].append(cell[key][a])
+    swept = [a for a in axes if len(distinct[a]) > 1]
+    base = {a: min(distinct[a], key=lambda v, a=a: (abs(order(a, v) - order(a, nominals[a])), order(a, v))) for a in axes}
+    out: Dict = {"robust_fall_rate": float(threshold)}
+    ranges: Dict = {}
+    for axis in swept:
+        line = [c for c in cells if all(c[key][o] == base[o] for o in axes if o != axis)]
+        line.sort(key=lambda c: order(axis, c[key][axis]))
+        out[axis] = pts = [dict(value=c[key][axis], **{k: c[k] for k in ROBUSTNESS_POINT_KEYS[1:]}) for c in line]
+        at = [order(axis, p["value"]) for p in pts]
+        ends = survived_range(at, [p["fall_rate"] for p in pts], threshold, order(axis, nominals[axis]))
+        ranges[axis] = ends if ends is None else [pts[at.index(x)]["value"] for x in ends]
     out["survived_range"] = ranges
     return out
 
@@ -1625,7 +1675,11 @@ class Tracker:
     tensor is then written by the Tracker), `falls`, `path` or (never both) `waypoints` (`waypoint_report`'s dict: the follower writes the
     bound command tensor).  A report's accumulator and device buffers are also the Tracker's attributes (below),
     None without the report.  `delays` ([num_envs] device int32, one action delay per env: 0, 1, 2, or -1 for the sampled one) are bound
-    (`set_action_delays`) and kept; the step itself is unchanged.  Model parameters (`Batch.set_param`) are the caller's to set before `reset`."""
+    (`set_action_delays`) and kept; the step itself is unchanged.  Model parameters (`Batch.set_param`) are the caller's to set before `reset`.
+    `sensors`: dict(fault=<[num_envs, SENSOR_NPRM] float32, a fault row per env: `Batch.sensor_fault_rows`, `sensors.fault_row`>): the step
+    begins with `odk_sensor_apply` from the env's observation into `sensor_obs`, which the policy reads instead; `sensor_fault` (the caller's
+    own tensor when it is float32 on the env's device: writing it between steps is followed by the captured graph) and `sensor_state` (the
+    sample ring, zeroed by `reset`) are kept.  Without `sensors` the three are None and the launch sequence is the plain one."""
     def _shown(name):      # what the first report that has `name` in its `shown` holds there
         return property(lambda self: next((r.shown[name] for r in self.reports if name in r.shown), None))
     push_acc, push_buf, kicks, counter = _shown("push_acc"), _shown("push_buf"), _shown("kicks"), _shown("counter")
@@ -1636,10 +1690,15 @@ class Tracker:
     def __init__(self, env, net, use_graph: bool = True, kicks=None, push_at: int = DEFAULT_PUSH_AT, push_tolerance=DEFAULT_PUSH_TOLERANCE,
                  gait: bool = False, posture: bool = False, posture_tolerance: float = DEFAULT_POSTURE_TOLERANCE,
                  imitation: bool = False, schedule: Optional[Dict] = None, falls: Optional[Dict] = None, delays=None, reports=None, path: bool = False,
-                 waypoints: Optional[Dict] = None):
+                 waypoints: Optional[Dict] = None, sensors: Optional[Dict] = None):
         import torch
         self.env, self.net, self.torch = env, net, torch
         self.acc = torch.zeros(env.num_envs, NACC, device=env.batch.obs.device)
+        self.sensor_fault = self.sensor_state = self.sensor_obs = None
+        if sensors is not None:      # (a float32 tensor already on the device is kept as it is: the caller's later writes reach the step)
+            self.sensor_fault = torch.as_tensor(sensors["fault"]).to(device=self.acc.device, dtype=torch.float32).reshape(env.num_envs, SENSOR_NPRM).contiguous()
+            self.sensor_state = torch.zeros(env.num_envs, SENSOR_NSTATE, device=self.acc.device)
+            self.sensor_obs = torch.zeros_like(env.batch.obs)
         if reports is not None and (kicks is not None or gait or posture or imitation or schedule is not None or falls is not None or path
                                     or waypoints is not None):
             raise ValueError("Tracker: give the reports or the switches that make them, not both")
@@ -1667,7 +1726,11 @@ class Tracker:
 
     def _one_step(self):
         b = self.env.batch
-        act = self.actions(b.obs)
+        obs = b.obs
+        if self.sensor_fault is not None:      # what the faulty sensors deliver of the row the step wrote; the row itself is only read
+            b.sensor_apply(b.obs, b.done, self.sensor_fault, self.sensor_state, self.sensor_obs)
+            obs = self.sensor_obs
+        act = self.actions(obs)
         for r in self.reports:
             r.before_step(b, self.acc)
         b.step(act)                                 # Joystick.step without the State wrapper (nothing here reads it)
@@ -1682,6 +1745,8 @@ class Tracker:
         self.acc.zero_()
         for r in self.reports:
             (r.zero or r.acc.zero_)()
+        if self.sensor_state is not None:
+            self.sensor_state.zero_()               # an empty ring: the first call fills it with the reset's observation
         if self.fp is not None:
             self.fp.refresh()                       # its packed weight copy <- the current parameters
 
@@ -1721,8 +1786,9 @@ def run(args, out=sys.stdout) -> Dict:
     pushes = [push_row(p) for p in (getattr(args, "push", None) or [])]
     if getattr(args, "push_grid", None):
         pushes += parse_push_grid(args.push_grid)
-    ncell = max(len(pushes), 1) * max(len(plants), 1)      # cells per command (pushes and plants exclude each other)
-    cells_key = "pushes" if pushes else ("plants" if plants else None)
+    sensors = sensors_from_args(args)    # [] without --sensor / --sensor_grid; refusals (pushes or plants next to sensors among them) before any batch work
+    ncell = max(len(pushes), 1) * max(len(plants), 1) * max(len(sensors), 1)      # cells per command (pushes, plants and sensors exclude each other)
+    cells_key = "pushes" if pushes else ("plants" if plants else ("sensors" if sensors else None))
     randomized = bool(getattr(args, "randomize", False))
     imitation = bool(getattr(args, "imitation_report", False))
     for why in (imitation_refusal(args) if imitation else None, falls_refusal(args)):      # before any batch work
@@ -1788,7 +1854,8 @@ def run(args, out=sys.stdout) -> Dict:
         reports.append(waypoint_report(env, dict(way, table=course_table(way["courses"]), map=schedule_blocks(len(way["courses"]), ncell * E))))
     elif getattr(args, "path", False):
         reports.append(path_report(env, constant=schedules is None))
-    tr = Tracker(env, net, delays=delays_t, reports=reports)
+    fault_t = torch.from_numpy(sensor_blocks(len(commands), sensors, E, int(args.seed))).to(dev) if sensors else None
+    tr = Tracker(env, net, delays=delays_t, reports=reports, **(dict(sensors=dict(fault=fault_t)) if sensors else {}))
     reports = sorted(reports, key=lambda r: not r.drives)      # the report's order: pushes and schedules first (a stable sort)
     nobs = env.observation_size["state"][0]
     T = int(args.episode_length)
@@ -1802,7 +1869,8 @@ def run(args, out=sys.stdout) -> Dict:
         for t in range(T):
             tr.step()
             if obs_hist is not None:
-                obs_hist[t].copy_(env.batch.obs[0])          # env 0's observation, stream-ordered after the step
+                # env 0's observation, stream-ordered after the step; with sensor faults the row the policy read in this step
+                obs_hist[t].copy_(env.batch.obs[0] if tr.sensor_obs is None else tr.sensor_obs[0])
             if save_qpos_path:
                 qpos_hist.append(env.batch.get_state()[0][0].copy())
         acc = tr.acc.cpu().numpy()
@@ -1814,6 +1882,12 @@ def run(args, out=sys.stdout) -> Dict:
             cell["plant"] = dict(plants[i % len(plants)])
         for c, row in enumerate(rows):
             row["plants"] = cell_rows[c * len(plants):(c + 1) * len(plants)]
+    if sensors:      # the same per (command, sensor) cell, in `sensor_blocks` order, plus the cell's settings
+        cell_rows = reduce_tracking(acc, [c for c in commands for _ in sensors], E)
+        for i, cell in enumerate(cell_rows):
+            cell["sensor"] = dict(sensors[i % len(sensors)])
+        for c, row in enumerate(rows):
+            row["sensors"] = cell_rows[c * len(sensors):(c + 1) * len(sensors)]
     for r, a in zip(reports, accs):      # per row, then per (command, push) or (command, plant) cell, in `cell_blocks` / `plant_blocks` order
         put = r.put or (lambda block, value, key=r.key: block.__setitem__(key, value))
         for row, value in zip(rows, r.reduce(a, commands, ncell * E)):
@@ -1840,6 +1914,19 @@ def run(args, out=sys.stdout) -> Dict:
                                         "following; mass: every body's mass, inertias NOT rescaled, as the reference's randomize.py; frictionloss, "
                                         "armature: the actuated dofs'); delay: action delay in control steps, 0 1 2 or random (the sampler); "
                                         "--gait's cost_of_transport keeps the model's nominal mass")
+    if sensors:
+        robust = float(getattr(args, "robust_fall_rate", DEFAULT_ROBUST_FALL_RATE))
+        for row in rows:      # after every per-cell object is in place, as the plants'
+            row["sensor_robustness"] = reduce_robustness(row["sensors"], robust, key="sensor", nominals=nominal_sensor(), order=sensor_order)
+        settings.update(sensor=getattr(args, "sensor", None), sensor_grid=getattr(args, "sensor_grid", None), sensors_per_command=len(sensors),
+                        robust_fall_rate=robust,
+                        sensor_semantics="what the policy reads, not what the robot does: every report reads the noise-free privileged row.  "
+                                         "gyro / acc: out = scale * (R x) + bias, R the mounting rotation of imu_roll / pitch / yaw (degrees), "
+                                         "biases in rad/s and m/s^2; imu_delay / joint_delay: whole control steps, a ring of raw samples that a "
+                                         "new episode fills with its first observation; encoder_offset: every env draws each actuator's zero "
+                                         "error uniformly in +-X rad (seeded by --seed), encoder_quant: the position step in rad, after the "
+                                         "offset; contact_left / contact_right: ok, off (stuck at 0) or on (stuck at 1); the env's own noise is "
+                                         "in the row before the fault")
     if randomized:
         settings.update(randomize=True)
     if getattr(args, "noise_level", None) is not None:
@@ -1896,7 +1983,17 @@ def build_parser() -> argparse.ArgumentParser:
                         "delay; a delay axis must come out as whole numbers within 0..2)")
     p.add_argument("--robust_fall_rate", type=float, default=DEFAULT_ROBUST_FALL_RATE, metavar="RATE",
                    help="robustness: the fall rate up to which a plant counts as survived in \"survived_range\" (a reporting threshold of the "
-                        "user's, not a measured constant); read with plants only")
+                        "user's, not a measured constant); read with plants or sensor faults only")
+    p.add_argument("--sensor", type=str, action="append", metavar="KEY=V[,KEY=V...]",
+                   help="a sensor fault between the env's observation and the policy: gyro_bias_x|y|z (rad/s), gyro_scale, acc_bias_x|y|z (m/s^2), "
+                        "acc_scale, imu_roll|imu_pitch|imu_yaw (degrees: a tilted IMU mount), imu_delay, joint_delay (whole control steps, 0 .. 7), "
+                        "encoder_offset (rad: every env draws each actuator's zero error uniformly in +-X, seeded by --seed), encoder_quant (rad), "
+                        "contact_left|contact_right = ok|off|on (a foot switch that sticks); keys not named stay nominal; repeat for more settings.  "
+                        "Every (command, sensor) cell gets --envs_per_command envs; every command row gains \"sensors\" and \"sensor_robustness\".  "
+                        "Not with --push / --push_grid or --plant / --plant_grid")
+    p.add_argument("--sensor_grid", type=str, default=None,
+                   help="a cross product of sensor settings: imu_delay=0:7:8,gyro_bias_y=-0.3:0.3:5 (--grid's syntax; every key of --sensor but the "
+                        "contact ones; a delay axis must come out as whole numbers within 0..7)")
     p.add_argument("--randomize", action="store_true",
                    help="apply the training-time domain randomisation (randomize.domain_randomize, seeded by --seed) to every env; a plant's "
                         "scales multiply it")
