@@ -147,6 +147,11 @@ int odk_batch_create(const odk_model* m, const odk_env_config* cfg, int nenv, in
                      const double* dxs, int nx, const double* dys, int ny, const double* dths, int nth, const double* ranges6,
                      int nsteps_in_period, odk_batch** out);
 void odk_batch_destroy(odk_batch* b);
+/* Replaces the configuration of a live batch; the next odk_reset / odk_step uses it.  The config travels BY VALUE in the kernel arguments of
+ * every launch, so a captured graph keeps the config it was captured with: call this before capturing, or capture again.  `env_kind` is fixed
+ * at creation (it sets the output strides: ODK_ERR_INVALID for another kind) and so is the lane count (`lanes_per_env` is ignored here:
+ * odk_batch_lanes).  `push_interval_steps` is drawn at reset from `push_interval_range` / `ctrl_dt`: an env keeps the interval it drew under
+ * the old config, through auto-resets too, until the next odk_reset. */
 int odk_batch_set_config(odk_batch* b, const odk_env_config* cfg);
 
 /* domain_randomize: per-env model fields, host pointer, copied synchronously */

@@ -37,10 +37,12 @@ def task_to_model(task_name: str) -> Model:
 
 class Robot:
     """What a new robot's constants.py / base.py spell out (reference README.md:74-85), read off a compiled model instead: is it the duck, and
-    which actuated joints are leg joints (`JOINTS_ORDER_NO_HEAD`: the joints above a foot, in actuator order)."""
+    which actuated joints are leg joints (`JOINTS_ORDER_NO_HEAD`: the joints above a foot, in actuator order).  `leg_actuators`: the actuator
+    index of each of those joints, or None for the duck (whose per-actuator tables keep the reference's index-by-position, DESIGN BUG-COMPAT)."""
 
-    def __init__(self, is_open_duck: bool, joints_order_no_head):
+    def __init__(self, is_open_duck: bool, joints_order_no_head, leg_actuators=None):
         self.is_open_duck, self.joints_order_no_head = bool(is_open_duck), list(joints_order_no_head)
+        self.leg_actuators = None if leg_actuators is None else [int(u) for u in leg_actuators]
 
 
 def robot_of(model: Model) -> Robot:
@@ -57,4 +59,5 @@ def robot_of(model: Model) -> Robot:
             above.add(b); b = int(parent[b])
     jb = np.asarray(a["jnt_bodyid"]); trn = np.asarray(a["actuator_trnid"]).reshape(model.nu, -1)[:, 0]
     jn = [str(n) for n in a["names_jnt"]]
-    return Robot(False, [jn[int(j)] for j in trn if int(jb[int(j)]) in above])
+    legs = [u for u, j in enumerate(trn) if int(jb[int(j)]) in above]
+    return Robot(False, [jn[int(trn[u])] for u in legs], legs)

@@ -69,9 +69,11 @@ REWARD_SLOTS = ("tracking_lin_vel", "tracking_ang_vel", "torques", "action_rate"
 
 def to_engine_config(cfg: ConfigDict, autoreset: bool = True, lanes_per_env: int = 0, standing: bool = False,
                      reward_slots=REWARD_SLOTS, use_imitation: bool = USE_IMITATION_REWARD,
-                     use_motor_speed_limits: bool = USE_MOTOR_SPEED_LIMITS, joints_order_no_head=None) -> engine.EnvConfig:
+                     use_motor_speed_limits: bool = USE_MOTOR_SPEED_LIMITS, joints_order_no_head=None, leg_actuators=None) -> engine.EnvConfig:
     """reference config -> odk_env_config (include/odk.h).  `joints_order_no_head`: the robot's leg joints in actuator order (what a new robot's
-    constants.py sets, reference README.md:74-85); default: the duck's."""
+    constants.py sets, reference README.md:74-85); default: the duck's.  `leg_actuators` (constants.Robot.leg_actuators): the actuator index of
+    each of those joints -- the kernels index `qpos_noise_scale` by actuator, so a robot whose leg actuators are not the first ones (a tail between
+    the legs) needs it; None keeps the reference's index-by-position (the duck, BUG-COMPAT below)."""
     c = engine.default_config(standing)
     c.ctrl_dt, c.action_scale, c.dof_vel_scale = cfg.ctrl_dt, cfg.action_scale, cfg.dof_vel_scale
     c.max_motor_velocity = cfg.get("max_motor_velocity", 0.0)
@@ -81,8 +83,15 @@ def to_engine_config(cfg: ConfigDict, autoreset: bool = True, lanes_per_env: int
     c.noise_level, c.noise_gyro, c.noise_accelerometer = n.level, n.scales.gyro, n.scales.accelerometer
     c.noise_gravity, c.noise_joint_vel = n.scales.gravity, n.scales.joint_vel
     # BUG-COMPAT (joystick.py:184-200): indices taken on the 10-entry JOINTS_ORDER_NO_HEAD, written into the 14-entry array
+    # A robot that is not the duck: each leg joint's scale goes to that joint's ACTUATOR slot, every other actuator gets 0 (DESIGN, BUG-COMPAT list)
     scale = np.zeros(16, np.float32)
-    for idx, j in enumerate((constants.JOINTS_ORDER_NO_HEAD if joints_order_no_head is None else list(joints_order_no_head))[:16]):
+    legs = list(constants.JOINTS_ORDER_NO_HEAD if joints_order_no_head is None else joints_order_no_head)
+    slots = list(range(len(legs))) if leg_actuators is None else [int(u) for u in leg_actuators]
+    if len(slots) != len(legs):
+        raise ValueError(f"leg_actuators has {len(slots)} entries for {len(legs)} leg joints")
+    for idx, j in zip(slots, legs):
+        if not 0 <= idx < 16:
+            continue
         scale[idx] = n.scales.hip_pos if "_hip" in j else (n.scales.knee_pos if "_knee" in j else n.scales.ankle_pos)
     for i in range(16):
         c.qpos_noise_scale[i] = float(scale[i])
@@ -359,7 +368,7 @@ class Joystick:
     def _engine_config(self, autoreset: bool, lanes_per_env: int) -> engine.EnvConfig:
         imitation = USE_IMITATION_REWARD and (self._robot.is_open_duck or self._motion is not None)
         return to_engine_config(self._config, autoreset, lanes_per_env, use_imitation=imitation,
-                                joints_order_no_head=self._robot.joints_order_no_head)
+                                joints_order_no_head=self._robot.joints_order_no_head, leg_actuators=self._robot.leg_actuators)
 
     def _reward_slots(self):
         return REWARD_SLOTS

@@ -70,11 +70,14 @@ def head_joint_map(model, head_joints):
     return out
 
 
-def to_standing_engine_config(cfg: ConfigDict, autoreset: bool = True, lanes_per_env: int = 0, head_map=None) -> engine.EnvConfig:
+def to_standing_engine_config(cfg: ConfigDict, autoreset: bool = True, lanes_per_env: int = 0, head_map=None, joints_order_no_head=None,
+                              leg_actuators=None) -> engine.EnvConfig:
     """reference config -> odk_env_config for the Standing task; `head_map` (head_joint_map, or None: the model's default): a posture
-    command that no joint tracks keeps its draw, from the range [0, 0]."""
+    command that no joint tracks keeps its draw, from the range [0, 0].  `joints_order_no_head` / `leg_actuators`: as in `to_engine_config`
+    (the qpos noise scales of a robot that is not the duck, by actuator)."""
     c = to_engine_config(cfg, autoreset, lanes_per_env, standing=True, reward_slots=REWARD_SLOTS,
-                         use_imitation=USE_IMITATION_REWARD, use_motor_speed_limits=False)
+                         use_imitation=USE_IMITATION_REWARD, use_motor_speed_limits=False, joints_order_no_head=joints_order_no_head,
+                         leg_actuators=leg_actuators)
     for k, u in enumerate(head_map or ()):
         if u < 0:
             c.cmd_range[3 + k][0] = c.cmd_range[3 + k][1] = 0.0
@@ -122,7 +125,8 @@ class Standing(Joystick):
         return None if spec is None else head_joint_map(self._model, spec)
 
     def _engine_config(self, autoreset: bool, lanes_per_env: int) -> engine.EnvConfig:
-        return to_standing_engine_config(self._config, autoreset, lanes_per_env, self._head_map)
+        return to_standing_engine_config(self._config, autoreset, lanes_per_env, self._head_map,
+                                         joints_order_no_head=self._robot.joints_order_no_head, leg_actuators=self._robot.leg_actuators)
 
     def describe_head_joints(self) -> str:
         """The head-joint map in use, one line."""

@@ -124,11 +124,22 @@ def _mk(oracle_mod, task, n, cfg_edit=None, standing=False, dr_fields=None, mode
     envs = _Envs(oracle_mod.OracleEnv(oms[i], prm, standing=standing) for i in range(n))
     envs.f32 = _F32(oracle_mod, model, standing, dr_fields)
     for e in envs:
-        e.cfg["episode_length"][0] = cfg.episode_length
-        e.cfg["noise_level"][0] = cfg.noise_level
-        e.cfg["push_enable"][0] = cfg.push_enable
-        e.cfg["use_imitation"][0] = cfg.use_imitation
+        _cfg_to_oracle(cfg, e)
     return torch, model, b, envs, (base, prm, oms)
+
+
+def _cfg_to_oracle(cfg, e):
+    """every field of the engine config that the oracle env has (`_CFG_FIELDS`) into that env's config, so that whatever a `cfg_edit` changes
+    is honoured on both sides: the oracle computes in float64 from the float32 numbers the kernels are given (`cmd_range`: [7][2] -> flat 14).
+    An element whose engine value IS the float32 rounding of what the oracle env already holds is left alone -- at the defaults the oracle keeps
+    its own float64 numbers (0.02, not float32(0.02)), so a test that edits nothing computes what it computed before this copy existed."""
+    for nm in _CFG_FIELDS:
+        v = getattr(cfg, nm)
+        dst = e.cfg[nm]
+        src = np.array(v, dtype=np.float64).reshape(-1) if hasattr(v, "__len__") else np.array([v], np.float64)
+        assert src.shape == dst.shape, (nm, src.shape, dst.shape)
+        differs = src.astype(np.float32) != np.array(dst).astype(np.float32)
+        dst[differs] = src[differs]
 
 
 class _Envs(list):
