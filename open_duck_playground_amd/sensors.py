@@ -2,10 +2,11 @@
 (include/odk.h "Sensor faults"), and a numpy restatement of that kernel with its bits.  Host code only: no GPU, no torch."""
 from __future__ import annotations
 
-import itertools
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
+
+from .sweeps import parse_axis_grid, grid_rows, parse_key_values, cell_rows
 
 from .engine import (SENSOR_NPRM, SENSOR_NSTATE, SENSOR_RING, SENSOR_SAMPLE, SENSOR_IMU_ROT, SENSOR_GYRO_SCALE, SENSOR_GYRO_BIAS, SENSOR_ACC_SCALE,
                      SENSOR_ACC_BIAS, SENSOR_IMU_DELAY, SENSOR_JOINT_DELAY, SENSOR_ENC_QUANT, SENSOR_CONTACT_MODE, SENSOR_ENC_OFFSET, SENSOR_HEAD,
@@ -63,22 +64,7 @@ def sensor_value(flag: str, name: str, value) -> object:
 def parse_sensor(spec: str) -> Dict:
     """`--sensor gyro_bias_y=0.2,imu_delay=2,contact_left=off` -> a sensor setting: `nominal_sensor()` with the named keys replaced.
     ValueError for an unknown key, a key given twice and a value `sensor_value` refuses."""
-    sensor, seen = nominal_sensor(), []
-    for part in str(spec).split(","):
-        part = part.strip()
-        if not part:
-            continue
-        name, eq, value = part.partition("=")
-        name = name.strip()
-        if not eq:
-            raise ValueError(f"--sensor: {part!r} is not KEY=VALUE")
-        if name in seen:
-            raise ValueError(f"--sensor: key {name!r} given twice")
-        sensor[name] = sensor_value("--sensor", name, value.strip())      # (an unknown key is refused before it is stored)
-        seen.append(name)
-    if not seen:
-        raise ValueError("--sensor: no key given")
-    return sensor
+    return parse_key_values("--sensor", spec, nominal_sensor(), "key", sensor_value)
 
 
 def parse_sensor_grid(spec: str) -> List[Dict]:
@@ -86,36 +72,8 @@ def parse_sensor_grid(spec: str) -> List[Dict]:
     (numpy.linspace, ends included), settings in itertools.product order of the axes as written (the last axis varies fastest), keys not
     named stay nominal.  A delay axis must come out as whole numbers within the ring; a contact key is no grid axis (its values are names:
     give one `--sensor` per mode)."""
-    axes = []
-    for part in str(spec).split(","):
-        part = part.strip()
-        if not part:
-            continue
-        name, _, rng = part.partition("=")
-        name = name.strip()
-        if name not in SENSOR_KEYS:
-            raise ValueError(f"--sensor_grid: unknown key {name!r} (one of {', '.join(SENSOR_KEYS)})")
-        if name in CONTACT_KEYS:
-            raise ValueError(f"--sensor_grid: {name} takes {' / '.join(CONTACT_MODES)}, not a range: give one --sensor {name}=MODE per mode")
-        if any(name == a for a, _ in axes):
-            raise ValueError(f"--sensor_grid: key {name!r} given twice")
-        bits = rng.split(":")
-        try:
-            lo, hi, n = float(bits[0]), float(bits[1]), int(bits[2])
-            assert len(bits) == 3
-        except (ValueError, IndexError, AssertionError):
-            raise ValueError(f"--sensor_grid: {part!r} is not {name}=start:stop:count")
-        if n < 1:
-            raise ValueError(f"--sensor_grid: {part!r} needs a count >= 1")
-        axes.append((name, [sensor_value("--sensor_grid", name, v) for v in np.linspace(lo, hi, n).tolist()]))
-    if not axes:
-        raise ValueError("--sensor_grid: no key given")
-    out = []
-    for combo in itertools.product(*[vals for _, vals in axes]):
-        sensor = nominal_sensor()
-        sensor.update({name: v for (name, _), v in zip(axes, combo)})
-        out.append(sensor)
-    return out
+    no_axis = {k: f"{k} takes {' / '.join(CONTACT_MODES)}, not a range: give one --sensor {k}=MODE per mode" for k in CONTACT_KEYS}
+    return grid_rows(parse_axis_grid("--sensor_grid", spec, SENSOR_KEYS, "key", sensor_value, refused=no_axis), nominal_sensor())
 
 
 def sensors_from_args(args) -> List[Dict]:
@@ -160,8 +118,8 @@ def sensor_blocks(ncommands: int, sensors: Sequence[Dict], envs_per_cell: int, s
     E, S = int(envs_per_cell), len(sensors)
     n = int(ncommands) * S * E
     unit = np.random.default_rng(int(seed)).uniform(-1.0, 1.0, (n, 16))
-    rows = np.tile(np.repeat(np.stack([fault_row(s) for s in sensors]), E, axis=0), (int(ncommands), 1))
-    bound = np.tile(np.repeat(np.asarray([float(s["encoder_offset"]) for s in sensors], np.float64), E), int(ncommands))[:, None]
+    rows = cell_rows(np.stack([fault_row(s) for s in sensors]), ncommands, E)
+    bound = cell_rows(np.asarray([float(s["encoder_offset"]) for s in sensors], np.float64), ncommands, E)[:, None]
     rows[:, SENSOR_ENC_OFFSET:SENSOR_ENC_OFFSET + 16] = np.where(bound > 0, unit * bound, 0.0)      # (fault_row's product, for every env at once)
     return rows
 

@@ -157,7 +157,6 @@ from __future__ import annotations
 
 import argparse
 import dataclasses
-import itertools
 import json
 import pickle
 import sys
@@ -206,6 +205,7 @@ from .engine import (PATH_NACC, PATH_MAX_WAYPOINTS, PATH_COURSE_FLOATS, PATH_STA
 
 from .engine import SENSOR_NPRM, SENSOR_NSTATE      # ODK_SENSOR_*
 from .sensors import nominal_sensor, sensor_order, sensors_from_args, sensor_blocks      # --sensor / --sensor_grid: the settings and their per-env fault rows
+from .sweeps import parse_axis_grid, grid_rows, parse_key_values, cell_rows      # the syntaxes and the env layout every sweep flag shares
 
 COMMAND_KEYS = ("vx", "vy", "wz", "neck_pitch", "head_pitch", "head_yaw", "head_roll")   # the order of cmd_range (include/odk.h)
 NACC = 12
@@ -223,33 +223,8 @@ def command_row(values: Sequence[float]) -> List[float]:
 def parse_grid(spec: str) -> List[List[float]]:
     """`vx=a:b:n,wz=c:d:m` -> the command rows of the grid: each named axis takes n values from a to b (numpy.linspace, ends included),
     axes not named stay 0, rows in itertools.product order of the axes as written (the last axis varies fastest)."""
-    axes = []
-    for part in spec.split(","):
-        part = part.strip()
-        if not part:
-            continue
-        name, _, rng = part.partition("=")
-        name = name.strip()
-        if name not in COMMAND_KEYS:
-            raise ValueError(f"--grid: unknown axis {name!r} (one of {', '.join(COMMAND_KEYS)})")
-        if any(name == a for a, _ in axes):
-            raise ValueError(f"--grid: axis {name!r} given twice")
-        bits = rng.split(":")
-        if len(bits) != 3:
-            raise ValueError(f"--grid: {part!r} is not {name}=start:stop:count")
-        lo, hi, n = float(bits[0]), float(bits[1]), int(bits[2])
-        if n < 1:
-            raise ValueError(f"--grid: {part!r} needs a count >= 1")
-        axes.append((name, np.linspace(lo, hi, n).tolist()))
-    if not axes:
-        raise ValueError("--grid: no axis given")
-    rows = []
-    for combo in itertools.product(*[vals for _, vals in axes]):
-        row = [0.0] * 7
-        for (name, _), v in zip(axes, combo):
-            row[COMMAND_KEYS.index(name)] = float(v)
-        rows.append(row)
-    return rows
+    axes = parse_axis_grid("--grid", spec, COMMAND_KEYS)
+    return [[float(row[k]) for k in COMMAND_KEYS] for row in grid_rows(axes, dict.fromkeys(COMMAND_KEYS, 0.0))]
 
 
 def command_blocks(commands: Sequence[Sequence[float]], envs_per_command: int) -> np.ndarray:
@@ -283,44 +258,19 @@ def parse_push_grid(spec: str) -> List[Dict]:
     """`magnitude=a:b:n,direction=c:d:m` -> the pushes of the grid, with `--grid`'s conventions: each axis takes n values from a to b
     (numpy.linspace, ends included), rows in itertools.product order of the axes as written (the last axis varies fastest).  Magnitude in
     m/s (required), direction in degrees (0 when not named)."""
-    axes = []
-    for part in spec.split(","):
-        part = part.strip()
-        if not part:
-            continue
-        name, _, rng = part.partition("=")
-        name = name.strip()
-        if name not in PUSH_AXES:
-            raise ValueError(f"--push_grid: unknown axis {name!r} (one of {', '.join(PUSH_AXES)})")
-        if any(name == a for a, _ in axes):
-            raise ValueError(f"--push_grid: axis {name!r} given twice")
-        bits = rng.split(":")
-        if len(bits) != 3:
-            raise ValueError(f"--push_grid: {part!r} is not {name}=start:stop:count")
-        lo, hi, n = float(bits[0]), float(bits[1]), int(bits[2])
-        if n < 1:
-            raise ValueError(f"--push_grid: {part!r} needs a count >= 1")
+    def check(name, part, lo, hi):
         if name == "magnitude" and min(lo, hi) < 0:
             raise ValueError(f"--push_grid: {part!r}: a magnitude is >= 0 (turn the direction instead)")
-        axes.append((name, np.linspace(lo, hi, n).tolist()))
-    if not any(name == "magnitude" for name, _ in axes):
-        raise ValueError("--push_grid: no magnitude axis given")
-    rows = []
-    for combo in itertools.product(*[vals for _, vals in axes]):
-        cell = {"magnitude": 0.0, "direction": 0.0}
-        cell.update({name: float(v) for (name, _), v in zip(axes, combo)})
-        rows.append(push_entry(cell["magnitude"], cell["direction"]))
-    return rows
+    axes = parse_axis_grid("--push_grid", spec, PUSH_AXES, check=check, required="magnitude")
+    return [push_entry(cell["magnitude"], cell["direction"]) for cell in grid_rows(axes, {"magnitude": 0.0, "direction": 0.0})]
 
 
 def cell_blocks(commands: Sequence[Sequence[float]], pushes: Sequence[Dict], envs_per_cell: int):
     """(cmd [n, 7], kicks [n, 2]) float32 with n = len(commands) * len(pushes) * envs_per_cell: cell (c, p) drives envs
-    (c * len(pushes) + p) * envs_per_cell onwards -- command blocks outermost, so command c's envs stay one block of
+    (c * len(pushes) + p) * envs_per_cell onwards (`sweeps.cell_rows`) -- command blocks outermost, so command c's envs stay one block of
     len(pushes) * envs_per_cell (what `reduce_tracking` pools)."""
-    E, P = int(envs_per_cell), len(pushes)
-    cmd = command_blocks(commands, P * E)
-    kicks = np.tile(np.repeat(np.asarray([p["push"] for p in pushes], np.float32).reshape(-1, 2), E, axis=0), (len(commands), 1))
-    return cmd, kicks
+    cmd = command_blocks(commands, len(pushes) * int(envs_per_cell))
+    return cmd, cell_rows(np.asarray([p["push"] for p in pushes], np.float32).reshape(-1, 2), len(commands), envs_per_cell)
 
 
 PLANT_SCALE_AXES = ("kp", "mass", "frictionloss", "armature")      # scales on the model's values (randomize.SCALED_FIELDS)
@@ -363,57 +313,14 @@ def _plant_value(flag: str, name: str, value) -> object:
 def parse_plant(spec: str) -> Dict:
     """`--plant kp=0.6,delay=2` -> a plant: `nominal_plant()` with the named axes replaced.  ValueError for an unknown axis, an axis given
     twice, a scale that is not a finite number > 0, and a delay that is not 0, 1, 2 or `random`."""
-    plant, seen = nominal_plant(), []
-    for part in str(spec).split(","):
-        part = part.strip()
-        if not part:
-            continue
-        name, eq, value = part.partition("=")
-        name = name.strip()
-        if not eq:
-            raise ValueError(f"--plant: {part!r} is not KEY=VALUE")
-        if name in seen:
-            raise ValueError(f"--plant: axis {name!r} given twice")
-        plant[name] = _plant_value("--plant", name, value.strip())      # (an unknown axis is refused before it is stored)
-        seen.append(name)
-    if not seen:
-        raise ValueError("--plant: no axis given")
-    return plant
+    return parse_key_values("--plant", spec, nominal_plant(), "axis", _plant_value)
 
 
 def parse_plant_grid(spec: str) -> List[Dict]:
     """`kp=0.7:1.3:4,mass=0.9:1.2:3,delay=0:2:3` -> the plants of the grid, with `--grid`'s conventions: each axis takes n values from a to
     b (numpy.linspace, ends included), plants in itertools.product order of the axes as written (the last axis varies fastest), axes not
     named stay nominal.  A `delay` axis must come out as whole numbers within 0..2."""
-    axes = []
-    for part in str(spec).split(","):
-        part = part.strip()
-        if not part:
-            continue
-        name, _, rng = part.partition("=")
-        name = name.strip()
-        if name not in PLANT_AXES:
-            raise ValueError(f"--plant_grid: unknown axis {name!r} (one of {', '.join(PLANT_AXES)})")
-        if any(name == a for a, _ in axes):
-            raise ValueError(f"--plant_grid: axis {name!r} given twice")
-        bits = rng.split(":")
-        if len(bits) != 3:
-            raise ValueError(f"--plant_grid: {part!r} is not {name}=start:stop:count")
-        try:
-            lo, hi, n = float(bits[0]), float(bits[1]), int(bits[2])
-        except ValueError:
-            raise ValueError(f"--plant_grid: {part!r} is not {name}=start:stop:count")
-        if n < 1:
-            raise ValueError(f"--plant_grid: {part!r} needs a count >= 1")
-        axes.append((name, [_plant_value("--plant_grid", name, v) for v in np.linspace(lo, hi, n).tolist()]))
-    if not axes:
-        raise ValueError("--plant_grid: no axis given")
-    plants = []
-    for combo in itertools.product(*[vals for _, vals in axes]):
-        plant = nominal_plant()
-        plant.update({name: v for (name, _), v in zip(axes, combo)})
-        plants.append(plant)
-    return plants
+    return grid_rows(parse_axis_grid("--plant_grid", spec, PLANT_AXES, value=_plant_value), nominal_plant())
 
 
 def plants_from_args(args) -> List[Dict]:
@@ -438,9 +345,8 @@ def plant_blocks(commands: Sequence[Sequence[float]], plants: Sequence[Dict], en
     """(cmd [n, 7] float32, scales {axis: [n] float64}, delays [n] int32) with n = len(commands) * len(plants) * envs_per_cell: cell (c, p)
     drives envs (c * len(plants) + p) * envs_per_cell onwards -- `cell_blocks`' layout with plants where the pushes are.  `scales[axis][e]`
     is env e's scale of that axis, `delays[e]` its bound delay row: 0, 1, 2, or -1 for `random`."""
-    E, P = int(envs_per_cell), len(plants)
-    cmd = command_blocks(commands, P * E)
-    tile = lambda per_plant, dtype: np.tile(np.repeat(np.asarray(per_plant, dtype), E), len(commands))
+    cmd = command_blocks(commands, len(plants) * int(envs_per_cell))
+    tile = lambda per_plant, dtype: cell_rows(np.asarray(per_plant, dtype), len(commands), envs_per_cell)
     scales = {axis: tile([float(p[axis]) for p in plants], np.float64) for axis in PLANT_SCALE_AXES}
     delays = tile([-1 if p["delay"] == DELAY_RANDOM else int(p["delay"]) for p in plants], np.int32)
     return cmd, scales, delays
@@ -454,16 +360,9 @@ def plant_fields(model, scales: Dict[str, np.ndarray], fields: Optional[Dict[str
     return randomize.scale_fields(fields if fields is not None else randomize.nominal_fields(model, n), scales)
 
 
-def _delay_order(v) -> float:
-    return -1.0 if v == DELAY_RANDOM else float(v)      # `random` sorts in front of the fixed delays
-
-
-def _nearest_nominal(axis: str, values: Sequence) -> object:
-    """The value of `values` nearest the nominal plant's: for a scale the one closest to 1 (the smaller of two equally close), for the delay
-    `random` if present, else the smallest."""
-    if axis == "delay":
-        return DELAY_RANDOM if DELAY_RANDOM in values else min(values)
-    return min(values, key=lambda v: (abs(float(v) - 1.0), float(v)))
+def plant_order(axis: str, value) -> Optional[float]:
+    """Where a plant's `value` sits on its axis' line: the number itself, and None for `random`, which is no point among the fixed delays."""
+    return None if value == DELAY_RANDOM else float(value)
 
 
 def survived_range(values: Sequence[float], fall_rates: Sequence[float], threshold: float, nominal: float = 1.0) -> Optional[List[float]]:
@@ -499,31 +398,12 @@ def reduce_robustness(cells: Sequence[Dict], threshold: float, key: str = "plant
     `delay` over the fixed delays, starting from the smallest (`random` is not a point on that line).  `robust_fall_rate` is the threshold.
     For cells of another kind (the sensor cells: `key` "sensor"): `nominals`, every axis with its own nominal value, and `order(axis,
     value)`, a value's place on its axis' line as a number (default: the value itself).  Nearest nominal and `survived_range` are then taken
-    around the axis's own nominal, and a range's ends are the values of its end points (a name for an axis whose values are names)."""
-    if nominals is not None:
-        return _reduce_robustness_around(cells, threshold, key, nominals, order or (lambda axis, v: float(v)))
-    distinct = {a: [] for a in PLANT_AXES}
-    for cell in cells:
-        for a in PLANT_AXES:
-            if cell[key][a] not in distinct[a]:
-                distinct[a].append(cell[key][a])
-    swept = [a for a in PLANT_AXES if len(distinct[a]) > 1]
-    base = {a: _nearest_nominal(a, distinct[a]) for a in PLANT_AXES}
-    out: Dict = {"robust_fall_rate": float(threshold)}
-    ranges: Dict = {}
-    for axis in swept:
-        line = [c for c in cells if all(c[key][o] == base[o] for o in PLANT_AXES if o != axis)]
-        line.sort(key=lambda c: _delay_order(c[key][axis]) if axis == "delay" else float(c[key][axis]))
-        out[axis] = [dict(value=c[key][axis], **{k: c[k] for k in ROBUSTNESS_POINT_KEYS[1:]}) for c in line]
-        pts = [p for p in out[axis] if p["value"] != DELAY_RANDOM]
-        nominal = min(p["value"] for p in pts) if axis == "delay" and pts else 1.0
-        ranges[axis] = survived_range([p["value"] for p in pts], [p["fall_rate"] for p in pts], threshold, nominal)
-    out["survived_range"] = ranges
-    return out
-
-
-def _reduce_robustness_around(cells: Sequence[Dict], threshold: float, key: str, nominals: Dict, order: Callable) -> Dict:
-    """`reduce_robustness` for cells whose axes each have a nominal of their own (`nominals`, in the axes' order)."""
+    around the axis's own nominal, and a range's ends are the values of its end points (a name for an axis whose values are names).
+    The plants are that with `nominal_plant()` and `plant_order`, whose None says that `random` is on no line: such a value sorts first,
+    is nearest only to itself, and as a nominal leaves `survived_range` to start from the smallest point; their ranges' ends are numbers."""
+    plants = nominals is None
+    nominals = nominal_plant() if plants else nominals
+    order = order or (plant_order if plants else (lambda axis, v: float(v)))
     axes = tuple(nominals)
     distinct = {a: [] for a in axes}
     for cell in cells:
@@ -531,16 +411,21 @@ def _reduce_robustness_around(cells: Sequence[Dict], threshold: float, key: str,
             if cell[key][a] not in distinct[a]:
                 distinct[a].append(cell[key][a])
     swept = [a for a in axes if len(distinct[a]) > 1]
-    base = {a: min(distinct[a], key=lambda v, a=a: (abs(order(a, v) - order(a, nominals[a])), order(a, v))) for a in axes}
+
+    def far(a, v):      # (how far from the axis' nominal, the place): what is off the line is in front of it, and near only to itself
+        o, n = order(a, v), order(a, nominals[a])
+        return v != nominals[a], np.inf if None in (o, n) else abs(o - n), -np.inf if o is None else o
+    base = {a: min(distinct[a], key=lambda v, a=a: far(a, v)) for a in axes}
     out: Dict = {"robust_fall_rate": float(threshold)}
     ranges: Dict = {}
     for axis in swept:
         line = [c for c in cells if all(c[key][o] == base[o] for o in axes if o != axis)]
-        line.sort(key=lambda c: order(axis, c[key][axis]))
-        out[axis] = pts = [dict(value=c[key][axis], **{k: c[k] for k in ROBUSTNESS_POINT_KEYS[1:]}) for c in line]
-        at = [order(axis, p["value"]) for p in pts]
-        ends = survived_range(at, [p["fall_rate"] for p in pts], threshold, order(axis, nominals[axis]))
-        ranges[axis] = ends if ends is None else [pts[at.index(x)]["value"] for x in ends]
+        line.sort(key=lambda c: far(axis, c[key][axis])[2])
+        out[axis] = [dict(value=c[key][axis], **{k: c[k] for k in ROBUSTNESS_POINT_KEYS[1:]}) for c in line]
+        pts = [p for p in out[axis] if order(axis, p["value"]) is not None]
+        at, nominal = [order(axis, p["value"]) for p in pts], order(axis, nominals[axis])
+        ends = survived_range(at, [p["fall_rate"] for p in pts], threshold, min(at, default=0.0) if nominal is None else nominal)
+        ranges[axis] = ends if ends is None or plants else [pts[at.index(x)]["value"] for x in ends]
     out["survived_range"] = ranges
     return out
 
@@ -1527,8 +1412,8 @@ class Report:
     step, before the tracking accumulator sets ENDED; `shown`: the accumulator and the device-side extras, by the Tracker attribute that shows
     them.  For `run`: `reduce(acc_numpy, commands, envs_per_block)` gives one value per block of envs (`commands`: the blocks' commands), which
     `put(block, value)` sets on its row or cell (default: under `key`), and `settings` are its entries of the report's.  `drives`: it sets what
-    the episode is given (pushes, commands), so its entries lead.  `run` reduces every report per row and once more per (command, push) or
-    (command, plant) cell, but the one whose row entries ARE the cells (key "pushes")."""
+    the episode is given (pushes, commands), so its entries lead.  `report_rows` reduces every report per row and once more per cell of the
+    `CellAxis`, but the one whose row entries ARE the cells (key "pushes")."""
     key: str
     acc: object
     launch: Callable
@@ -1768,6 +1653,82 @@ class Tracker:
         self.graph.replay()
 
 
+@dataclasses.dataclass
+class CellAxis:
+    """What divides a command's envs into cells of `--envs_per_command` envs: the pushes, the plants or the sensor settings (they exclude
+    each other).  `row_key`: where a row holds its cells; `cells`: a dict per cell, in the layout's order.  `label_key`: a cell is a whole
+    command row of its own and holds its dict of `cells` there; None for the pushes, whose cells are their `Report`'s.  `robustness_key`:
+    where a row holds `reduce_robustness` of its cells at `threshold`, with `nominals` and `order`; None for none.  `settings`: the axis'
+    entries of the report's."""
+    row_key: str
+    cells: Sequence[Dict]
+    label_key: Optional[str] = None
+    robustness_key: Optional[str] = None
+    threshold: float = DEFAULT_ROBUST_FALL_RATE
+    nominals: Optional[Dict] = None
+    order: Optional[Callable] = None
+    settings: Dict = dataclasses.field(default_factory=dict)
+
+
+def cell_axis(args, pushes: Sequence[Dict], plants: Sequence[Dict], sensors: Sequence[Dict]) -> Optional[CellAxis]:
+    """The cell axis of a run from what its flags gave (at most one of the three is not empty: the `*_from_args` refusals), None without."""
+    robust = float(getattr(args, "robust_fall_rate", DEFAULT_ROBUST_FALL_RATE))
+    if pushes:
+        return CellAxis("pushes", pushes)      # (its settings are the push report's)
+    if plants:
+        return CellAxis("plants", plants, "plant", "robustness", robust, settings=dict(
+            plant=getattr(args, "plant", None), plant_grid=getattr(args, "plant_grid", None), plants_per_command=len(plants), robust_fall_rate=robust,
+            plant_semantics="kp, mass, frictionloss, armature: scales on the model's values (kp: every actuator's gain, the bias "
+                            "following; mass: every body's mass, inertias NOT rescaled, as the reference's randomize.py; frictionloss, "
+                            "armature: the actuated dofs'); delay: action delay in control steps, 0 1 2 or random (the sampler); "
+                            "--gait's cost_of_transport keeps the model's nominal mass"))
+    if sensors:
+        return CellAxis("sensors", sensors, "sensor", "sensor_robustness", robust, nominal_sensor(), sensor_order, settings=dict(
+            sensor=getattr(args, "sensor", None), sensor_grid=getattr(args, "sensor_grid", None), sensors_per_command=len(sensors), robust_fall_rate=robust,
+            sensor_semantics="what the policy reads, not what the robot does: every report reads the noise-free privileged row.  "
+                             "gyro / acc: out = scale * (R x) + bias, R the mounting rotation of imu_roll / pitch / yaw (degrees), "
+                             "biases in rad/s and m/s^2; imu_delay / joint_delay: whole control steps, a ring of raw samples that a "
+                             "new episode fills with its first observation; encoder_offset: every env draws each actuator's zero "
+                             "error uniformly in +-X rad (seeded by --seed), encoder_quant: the position step in rad, after the "
+                             "offset; contact_left / contact_right: ok, off (stuck at 0) or on (stuck at 1); the env's own noise is "
+                             "in the row before the fault"))
+    return None
+
+
+def block_commands(rows: Sequence[Dict], axis: Optional[CellAxis]) -> List[List[float]]:
+    """The command of every block of `envs_per_cell` envs, in env order: each row's, once per cell of the axis."""
+    return [row["command"] for row in rows for _ in (axis.cells if axis else [0])]
+
+
+def report_rows(acc: np.ndarray, reports: Sequence[tuple], commands: Sequence[Sequence[float]], axis: Optional[CellAxis], envs_per_cell: int) -> List[Dict]:
+    """The rows of the report, host arithmetic only.  `acc`: the tracking accumulator; `reports`: (`Report`, its accumulator as numpy) pairs
+    in the report's order, of which `key`, `reduce` and `put` are read; `commands`: one per row; `axis`: the cell axis or None.  A row is
+    `reduce_tracking` over its command's envs; with a labelled axis (plants, sensors) it then holds, under the axis' `row_key`, one whole
+    command row per cell of `envs_per_cell` envs (`sweeps.cell_rows`' order) with the cell's dict under `label_key`.  Every report then puts
+    its object on every row and, but the one whose row entries ARE the cells (pushes), on every cell; the robustness object comes last,
+    for its lines read the cells' own figures."""
+    E, P = int(envs_per_cell), len(axis.cells) if axis else 1
+    rows = reduce_tracking(acc, commands, P * E)
+    if axis and axis.label_key:
+        cells = reduce_tracking(acc, block_commands(rows, axis), E)
+        for i, cell in enumerate(cells):
+            cell[axis.label_key] = dict(axis.cells[i % P])
+        for c, row in enumerate(rows):
+            row[axis.row_key] = cells[c * P:(c + 1) * P]
+    for r, a in reports:
+        put = r.put or (lambda block, value, key=r.key: block.__setitem__(key, value))
+        for row, value in zip(rows, r.reduce(a, commands, P * E)):
+            put(row, value)
+        if axis and r.key != axis.row_key:
+            cells = [cell for row in rows for cell in row[axis.row_key]]
+            for cell, value in zip(cells, r.reduce(a, block_commands(rows, axis), E)):
+                put(cell, value)
+    if axis and axis.robustness_key:
+        for row in rows:
+            row[axis.robustness_key] = reduce_robustness(row[axis.row_key], axis.threshold, axis.label_key, axis.nominals, axis.order)
+    return rows
+
+
 def run(args, out=sys.stdout) -> Dict:
     import torch
     way = waypoints_from_args(args)            # None without --waypoints; refusals before any batch work
@@ -1787,8 +1748,8 @@ def run(args, out=sys.stdout) -> Dict:
     if getattr(args, "push_grid", None):
         pushes += parse_push_grid(args.push_grid)
     sensors = sensors_from_args(args)    # [] without --sensor / --sensor_grid; refusals (pushes or plants next to sensors among them) before any batch work
-    ncell = max(len(pushes), 1) * max(len(plants), 1) * max(len(sensors), 1)      # cells per command (pushes, plants and sensors exclude each other)
-    cells_key = "pushes" if pushes else ("plants" if plants else ("sensors" if sensors else None))
+    axis = cell_axis(args, pushes, plants, sensors)
+    ncell = len(axis.cells) if axis else 1      # cells per command
     randomized = bool(getattr(args, "randomize", False))
     imitation = bool(getattr(args, "imitation_report", False))
     for why in (imitation_refusal(args) if imitation else None, falls_refusal(args)):      # before any batch work
@@ -1875,58 +1836,17 @@ def run(args, out=sys.stdout) -> Dict:
                 qpos_hist.append(env.batch.get_state()[0][0].copy())
         acc = tr.acc.cpu().numpy()
         accs = [r.acc.cpu().numpy() for r in reports]
-    rows = reduce_tracking(acc, commands, ncell * E)
-    if plants:      # one whole command row per (command, plant) cell, in `plant_blocks` order, plus the plant it ran on
-        cell_rows = reduce_tracking(acc, [c for c in commands for _ in plants], E)
-        for i, cell in enumerate(cell_rows):
-            cell["plant"] = dict(plants[i % len(plants)])
-        for c, row in enumerate(rows):
-            row["plants"] = cell_rows[c * len(plants):(c + 1) * len(plants)]
-    if sensors:      # the same per (command, sensor) cell, in `sensor_blocks` order, plus the cell's settings
-        cell_rows = reduce_tracking(acc, [c for c in commands for _ in sensors], E)
-        for i, cell in enumerate(cell_rows):
-            cell["sensor"] = dict(sensors[i % len(sensors)])
-        for c, row in enumerate(rows):
-            row["sensors"] = cell_rows[c * len(sensors):(c + 1) * len(sensors)]
-    for r, a in zip(reports, accs):      # per row, then per (command, push) or (command, plant) cell, in `cell_blocks` / `plant_blocks` order
-        put = r.put or (lambda block, value, key=r.key: block.__setitem__(key, value))
-        for row, value in zip(rows, r.reduce(a, commands, ncell * E)):
-            put(row, value)
-        if cells_key and r.key != cells_key:
-            cells = [cell for row in rows for cell in row[cells_key]]
-            for cell, value in zip(cells, r.reduce(a, [row["command"] for row in rows for _ in row[cells_key]], E)):
-                put(cell, value)
-    if falls and falls["save"]:      # the clips of every row, or with pushes / plants of every cell
-        block_cmds = [row["command"] for row in rows for _ in (row[cells_key] if cells_key else [0])]
-        save_falls(falls["save"], fall_clips(accs[[r.key for r in reports].index("falls")], block_cmds, E, falls["ring"], int(env.batch.model.nq), falls["save_max"]), float(env.dt))
+    rows = report_rows(acc, list(zip(reports, accs)), commands, axis, E)
+    if falls and falls["save"]:      # the clips of every row, or with a cell axis of every cell
+        save_falls(falls["save"], fall_clips(accs[[r.key for r in reports].index("falls")], block_commands(rows, axis), E, falls["ring"],
+                                             int(env.batch.model.nq), falls["save_max"]), float(env.dt))
     settings = dict(checkpoint=args.checkpoint, env=args.env, task=args.task, xml=args.xml, cone=args.cone,
                     hfield_up_normals_only=bool(args.hfield_up_normals_only), envs_per_command=E, episode_length=T, seed=int(args.seed),
                     num_envs=n, dt=float(env.dt), policy="deterministic tanh(loc)", fused_policy=tr.fp is not None, graph=tr.graph is not None,
                     reference_motion=getattr(args, "reference_motion", None), reference_motion_sha256=motion.sha256 if motion is not None else None)
     settings.update({k: v for r in reports if r.drives for k, v in r.settings.items()})
-    if plants:
-        robust = float(getattr(args, "robust_fall_rate", DEFAULT_ROBUST_FALL_RATE))
-        for row in rows:      # after every per-cell object is in place: the robustness lines read the cells' own figures
-            row["robustness"] = reduce_robustness(row["plants"], robust)
-        settings.update(plant=getattr(args, "plant", None), plant_grid=getattr(args, "plant_grid", None), plants_per_command=len(plants),
-                        robust_fall_rate=robust,
-                        plant_semantics="kp, mass, frictionloss, armature: scales on the model's values (kp: every actuator's gain, the bias "
-                                        "following; mass: every body's mass, inertias NOT rescaled, as the reference's randomize.py; frictionloss, "
-                                        "armature: the actuated dofs'); delay: action delay in control steps, 0 1 2 or random (the sampler); "
-                                        "--gait's cost_of_transport keeps the model's nominal mass")
-    if sensors:
-        robust = float(getattr(args, "robust_fall_rate", DEFAULT_ROBUST_FALL_RATE))
-        for row in rows:      # after every per-cell object is in place, as the plants'
-            row["sensor_robustness"] = reduce_robustness(row["sensors"], robust, key="sensor", nominals=nominal_sensor(), order=sensor_order)
-        settings.update(sensor=getattr(args, "sensor", None), sensor_grid=getattr(args, "sensor_grid", None), sensors_per_command=len(sensors),
-                        robust_fall_rate=robust,
-                        sensor_semantics="what the policy reads, not what the robot does: every report reads the noise-free privileged row.  "
-                                         "gyro / acc: out = scale * (R x) + bias, R the mounting rotation of imu_roll / pitch / yaw (degrees), "
-                                         "biases in rad/s and m/s^2; imu_delay / joint_delay: whole control steps, a ring of raw samples that a "
-                                         "new episode fills with its first observation; encoder_offset: every env draws each actuator's zero "
-                                         "error uniformly in +-X rad (seeded by --seed), encoder_quant: the position step in rad, after the "
-                                         "offset; contact_left / contact_right: ok, off (stuck at 0) or on (stuck at 1); the env's own noise is "
-                                         "in the row before the fault")
+    if axis:
+        settings.update(axis.settings)
     if randomized:
         settings.update(randomize=True)
     if getattr(args, "noise_level", None) is not None:
