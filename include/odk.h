@@ -678,6 +678,58 @@ int odk_sensor_apply(const odk_batch* b, const float* obs_dev /* [nenv, nobs], t
                      const float* fault_dev /* [nenv, ODK_SENSOR_NPRM] */, float* state_dev /* [nenv, ODK_SENSOR_NSTATE] */,
                      float* obs_out_dev /* [nenv, nobs], must not alias obs_dev */, void* stream);
 
+/* Actuation faults: a stage between the policy's action and odk_step, which turns the action the policy asked for into the one the servos
+ * receive -- a gain error, a mis-indexed horn, command noise, a clamp, the runtime's low-pass filter, the servo's position resolution, a
+ * lost packet, a servo that drops off the bus.  One launch, a 16-lane row per env (lane = actuator), graph-capturable, no LDS, no scratch.
+ * It is OUT OF PLACE: act_dev (the policy's action, [nenv, nu]) is only read and act_out_dev must not overlap it; the caller hands
+ * act_out_dev to odk_step.  nu is the batch's.  Every entry of a fault row is in ACTION UNITS: the env turns an action into a target as
+ * default + action * action_scale, so a figure in radians is divided by action_scale on the host.
+ *
+ * Env e's row of fault_dev [nenv, ODK_ACT_NPRM], in stage order (x < y, x > y and x >= y are false for a NaN, so a NaN parameter leaves
+ * its stage off):
+ *   GAIN             a = gain a                                   when gain < 1 or gain > 1
+ *   OFFSET[16]       a = a + offset[lane]                         when offset < 0 or offset > 0
+ *   NOISE            a = a + A ((u + u) - 1), u of stream 1 + lane   when A > 0
+ *   LIMIT            a = fminf(fmaxf(a, -L), L)                   when L > 0
+ *   ALPHA            y = (alpha y_prev) + ((1 - alpha) a), FILT[lane] = y, a = y   when alpha > 0 (1 - alpha is formed on the device; with
+ *                    the filter off FILT keeps its value).  The reference's LowPassActionFilter, alpha = (1 / cutoff) / (dt + 1 / cutoff)
+ *   QUANT            a = q rintf(a / q)                           when q > 0
+ *   DROP_P, DROP_LEN packet loss, below
+ *   FREEZE_AT[16]    the actuator delivers its previous delivered value   when f >= 0 and the episode step >= f
+ *   SEED             a whole number in 0 .. 2^24 - 1: fminf(fmaxf(seed, 0), 16777215) (NaN: 0), a fraction dropped
+ * Slots 8 .. 15 are not read.  The NOMINAL row is GAIN 1, DROP_LEN 1, every FREEZE_AT -1 and 0 elsewhere, and it hands back the input's
+ * bits for every value, -0.0, NaN and +-inf included: every nominal stage is a select, never arithmetic.
+ *
+ * Env e's row of state_dev [nenv, ODK_ACT_NSTATE] (zeroed by the caller before an episode's first call): HEAD, the calls since the last
+ * refill = the episode step of the current call (a float: exact for 2^24 calls); EPISODE, the refill count; HOLD, the loss steps still to
+ * come; CALLS and DROPS, the calls and the calls whose packet was lost since the row was zeroed (a refill does not reset them); slots
+ * 5 .. 15 are not touched; FILT[16], the filter's state, and PREV[16], the action last delivered (entries past nu are not touched).
+ * Order per call:
+ *   1. refill, when HEAD is 0 or done_dev[e] != 0 (done_dev may be NULL): FILT and PREV count as 0 (the reference's last_action = 0:
+ *      action 0 is the default pose, where the episode starts), HOLD as 0, EPISODE grows by 1 and the step is 0;
+ *   2. gain, offset, noise, limit, filter, quantiser (the runtime's side of the bus);
+ *   3. packet loss, the same for the row's 16 lanes: HOLD > 0 -- lost, HOLD falls by 1; otherwise u(stream 0) < DROP_P -- lost, and
+ *      HOLD = fmaxf(DROP_LEN, 1) - 1.  A lost packet delivers PREV on every actuator.  FILT advances on a lost packet too: the runtime
+ *      does not know the bus dropped it;
+ *   4. freeze, per lane;
+ *   5. PREV = delivered (lanes below nu), HEAD + 1, CALLS + 1, DROPS + 1 if the packet was lost.
+ * Random numbers are stateless (a captured graph, an eager run and a host restatement agree), uint32 arithmetic only:
+ *   x = seed + 0x9E3779B9 env + 0x85EBCA6B episode + 0xC2B2AE35 step + 0x27D4EB2F stream   (mod 2^32; env = index in the batch, episode =
+ *       EPISODE after the refill, step = the episode step)
+ *   x ^= x >> 16; x *= 0x7FEB352D; x ^= x >> 15; x *= 0x846CA68B; x ^= x >> 16;  u = float(x >> 8) * 2^-24   (0 <= u < 1, exact)
+ * Arithmetic is float32 + - * / and rintf with every product rounded before it is added (no fused multiply-add): a numpy restatement has
+ * every bit.  Refused (ODK_ERR_INVALID, nothing launched): a null pointer other than done_dev (the message names the argument),
+ * act_out_dev overlapping act_dev, a model with more than 16 actuators. */
+#define ODK_ACT_NPRM 48
+#define ODK_ACT_NSTATE 48
+enum { ODK_ACT_GAIN = 0, ODK_ACT_NOISE = 1, ODK_ACT_LIMIT = 2, ODK_ACT_ALPHA = 3, ODK_ACT_QUANT = 4, ODK_ACT_DROP_P = 5, ODK_ACT_DROP_LEN = 6,
+       ODK_ACT_SEED = 7 /* 8..15 are not read */, ODK_ACT_OFFSET = 16 /* [16] */, ODK_ACT_FREEZE_AT = 32 /* [16] */ };
+enum { ODK_ACT_HEAD = 0, ODK_ACT_EPISODE = 1, ODK_ACT_HOLD = 2, ODK_ACT_CALLS = 3, ODK_ACT_DROPS = 4 /* 5..15 are not touched */,
+       ODK_ACT_FILT = 16 /* [16] */, ODK_ACT_PREV = 32 /* [16] */ };
+int odk_action_apply(const odk_batch* b, const float* act_dev /* [nenv, nu], the policy's, only read */, const float* done_dev /* may be NULL */,
+                     const float* fault_dev /* [nenv, ODK_ACT_NPRM] */, float* state_dev /* [nenv, ODK_ACT_NSTATE] */,
+                     float* act_out_dev /* [nenv, nu], must not overlap act_dev */, void* stream);
+
 /* mjx_env.step alone (physics only, n_substeps, ctrl = ctrl_dev [nenv, nu]); for parity tests */
 int odk_physics_step(odk_batch* b, const float* ctrl_dev, int n_substeps, void* stream);
 

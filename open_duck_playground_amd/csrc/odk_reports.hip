@@ -1,5 +1,5 @@
 // odk_reports.hip -- the evaluation reports of include/odk.h (libodk.so): the accumulator kernels of the tracking / push / gait / posture /
-// imitation / response / fall / path reports, the command-schedule kernel, the waypoint follower and the sensor-fault stage, with their C entry points.  They read
+// imitation / response / fall / path reports, the command-schedule kernel, the waypoint follower and the sensor-fault and actuation-fault stages, with their C entry points.  They read
 // finished observation rows (odk_obs_layout.h) and the batch (odk_batch.h: read-only here; its state is odk_engine.hip's); no compiled shape.
 // gfx950 only, no CPU fallback.
 #include <hip/hip_runtime.h>
@@ -894,6 +894,93 @@ extern "C" int odk_sensor_apply(const odk_batch* b, const float* obs_dev, const 
     return fail(ODK_ERR_INVALID, "%s: obs_out_dev overlaps obs_dev (the stage is out of place: the step's observation is only read)", fn);
   hipLaunchKernelGGL(sensor_kernel, g.grid, dim3(256), 0, (hipStream_t)stream, obs_dev, g.nobs, nu,
                      obs_at::contact(nu, b->cfg.env_kind == ODK_ENV_JOYSTICK), done_dev, fault_dev, state_dev, obs_out_dev, b->nenv);
+  HIPCHK(hipGetLastError());
+  return ODK_OK;
+}
+
+// ---- actuation faults (include/odk.h "Actuation faults": the definitions this kernel restates).  Not a report: the stage between the
+// policy's action and the env step.  sensor_kernel's geometry -- a 16-lane row per env, lane = actuator, four envs per wave, a row past
+// nenv leaves at once.  What is uniform over an env's row (the step count, the hold counter, the loss decision) every lane computes from
+// the same loads: no cross-lane traffic.  Every load of the state row comes before its first store, and a row sits inside one wave, so
+// lane 0's scalar stores follow every lane's loads.  Out of place, no LDS, no scratch; contraction is off and every nominal stage is a
+// select, so a numpy restatement has the bits.
+__device__ __forceinline__ float act_uniform(unsigned seed, unsigned env, unsigned episode, unsigned step, unsigned stream) {
+  unsigned x = seed + 0x9E3779B9u * env + 0x85EBCA6Bu * episode + 0xC2B2AE35u * step + 0x27D4EB2Fu * stream;
+  x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
+  return (float)(x >> 8) * 5.9604644775390625e-08f;      // 2^-24: exact, 0 <= u < 1
+}
+
+__global__ void __launch_bounds__(256) action_kernel(const float* __restrict__ act, int nu, const float* __restrict__ done,
+                                                     const float* __restrict__ fault, float* __restrict__ state, float* __restrict__ out, int nenv) {
+#pragma clang fp contract(off)
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int e = t >> 4, u = t & 15;
+  if (e >= nenv) return;
+  const float* F = fault + (size_t)e * ODK_ACT_NPRM;
+  float* S = state + (size_t)e * ODK_ACT_NSTATE;
+  const bool lane = u < nu;
+  // everything this call reads of the state row, before anything is stored
+  const float n0 = S[ODK_ACT_HEAD], ep0 = S[ODK_ACT_EPISODE], hold0 = S[ODK_ACT_HOLD], calls0 = S[ODK_ACT_CALLS], drops0 = S[ODK_ACT_DROPS];
+  const float filt0 = S[ODK_ACT_FILT + u], prev0 = S[ODK_ACT_PREV + u];
+  float a = lane ? act[(size_t)e * nu + u] : 0.0f;
+  // 1. the refill
+  const bool refill = n0 == 0.0f || (done && done[e] != 0.0f);
+  const float step = refill ? 0.0f : n0, episode = refill ? ep0 + 1.0f : ep0, hold = refill ? 0.0f : hold0;
+  const float y_prev = refill ? 0.0f : filt0, prev = refill ? 0.0f : prev0;
+  const unsigned seed = (unsigned)fminf(fmaxf(F[ODK_ACT_SEED], 0.0f), 16777215.0f);
+  const unsigned ue = (unsigned)e, uep = (unsigned)episode, ust = (unsigned)step;
+  // 2. the runtime's side: gain, offset, noise, limit, filter, quantiser
+  const float gain = F[ODK_ACT_GAIN], off = F[ODK_ACT_OFFSET + u], amp = F[ODK_ACT_NOISE], lim = F[ODK_ACT_LIMIT];
+  const float alpha = F[ODK_ACT_ALPHA], q = F[ODK_ACT_QUANT];
+  a = (gain < 1.0f || gain > 1.0f) ? gain * a : a;
+  a = (off < 0.0f || off > 0.0f) ? a + off : a;
+  const float un = act_uniform(seed, ue, uep, ust, 1u + (unsigned)u);
+  a = amp > 0.0f ? a + amp * ((un + un) - 1.0f) : a;
+  a = lim > 0.0f ? fminf(fmaxf(a, -lim), lim) : a;
+  const float y = (alpha * y_prev) + ((1.0f - alpha) * a);
+  const float filt = alpha > 0.0f ? y : y_prev;
+  a = alpha > 0.0f ? y : a;
+  a = q > 0.0f ? q * rintf(a / q) : a;
+  // 3. the bus: a lost packet, the same decision in the row's 16 lanes
+  const float u0 = act_uniform(seed, ue, uep, ust, 0u);
+  const bool held = hold > 0.0f, drawn = !held && u0 < F[ODK_ACT_DROP_P], lost = held || drawn;
+  const float hold1 = held ? hold - 1.0f : (drawn ? fmaxf(F[ODK_ACT_DROP_LEN], 1.0f) - 1.0f : hold);
+  a = lost ? prev : a;
+  // 4. the servo: off the bus from its step on
+  const float f = F[ODK_ACT_FREEZE_AT + u];
+  a = (f >= 0.0f && step >= f) ? prev : a;
+  // 5. the stores
+  if (lane) {
+    out[(size_t)e * nu + u] = a;
+    S[ODK_ACT_FILT + u] = filt;
+    S[ODK_ACT_PREV + u] = a;
+  }
+  if (u == 0) {
+    S[ODK_ACT_HEAD] = step + 1.0f;
+    S[ODK_ACT_EPISODE] = episode;
+    S[ODK_ACT_HOLD] = hold1;
+    S[ODK_ACT_CALLS] = calls0 + 1.0f;
+    S[ODK_ACT_DROPS] = lost ? drops0 + 1.0f : drops0;
+  }
+}
+
+extern "C" int odk_action_apply(const odk_batch* b, const float* act_dev, const float* done_dev, const float* fault_dev, float* state_dev,
+                                float* act_out_dev, void* stream) {
+  const char* fn = "odk_action_apply";
+  if (!b) return fail(ODK_ERR_INVALID, "%s: null batch", fn);
+  if (!act_dev) return fail(ODK_ERR_INVALID, "%s: null act_dev", fn);
+  if (!fault_dev) return fail(ODK_ERR_INVALID, "%s: null fault_dev", fn);
+  if (!state_dev) return fail(ODK_ERR_INVALID, "%s: null state_dev", fn);
+  if (!act_out_dev) return fail(ODK_ERR_INVALID, "%s: null act_out_dev", fn);
+  static_assert(ODK_ACT_OFFSET + 16 == ODK_ACT_FREEZE_AT && ODK_ACT_FREEZE_AT + 16 == ODK_ACT_NPRM && ODK_ACT_FILT + 16 == ODK_ACT_PREV &&
+                ODK_ACT_PREV + 16 == ODK_ACT_NSTATE, "one lane per actuator in every per-actuator array");
+  const int nu = b->model.h.nu;
+  if (int rc = fits_row16(fn, nu)) return rc;
+  Launch g; if (int rc = launch_on(b, 16, &g)) return rc;
+  const size_t n = (size_t)b->nenv * nu;
+  if (act_out_dev < act_dev + n && act_dev < act_out_dev + n)
+    return fail(ODK_ERR_INVALID, "%s: act_out_dev overlaps act_dev (the stage is out of place: the policy's action is only read)", fn);
+  hipLaunchKernelGGL(action_kernel, g.grid, dim3(256), 0, (hipStream_t)stream, act_dev, nu, done_dev, fault_dev, state_dev, act_out_dev, b->nenv);
   HIPCHK(hipGetLastError());
   return ODK_OK;
 }

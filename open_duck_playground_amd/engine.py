@@ -191,6 +191,7 @@ def load_library() -> C.CDLL:
     L.odk_path_accumulate.argtypes = [P, P, P, P, P, C.c_int, P, C.c_float, P, P]
     L.odk_waypoint_command_apply.argtypes = [P, P, C.c_int, P, P, P, C.c_float, C.c_float, C.c_float, C.c_float, P]
     L.odk_sensor_apply.argtypes = [P, P, P, P, P, P, P]
+    L.odk_action_apply.argtypes = [P, P, P, P, P, P, P]
     L.odk_batch_get_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_set_state.argtypes = [P, FP, FP, FP]
     L.odk_batch_get_debug.argtypes = [P, FP, FP, FP, FP]
@@ -237,7 +238,7 @@ EXPORTED_SYMBOLS = (
     "odk_batch_bind_commands", "odk_batch_set_reward_terms", "odk_batch_bind_reward_metrics", "odk_batch_set_imitation_joints", "odk_batch_set_head_joints",
     "odk_tracking_accumulate", "odk_batch_bind_pushes", "odk_batch_bind_action_delays", "odk_push_accumulate", "odk_gait_accumulate", "odk_posture_accumulate",
     "odk_imitation_accumulate", "odk_command_schedule_apply", "odk_response_accumulate", "odk_fall_row_floats", "odk_fall_accumulate",
-    "odk_path_begin", "odk_path_accumulate", "odk_waypoint_command_apply", "odk_sensor_apply",
+    "odk_path_begin", "odk_path_accumulate", "odk_waypoint_command_apply", "odk_sensor_apply", "odk_action_apply",
     "odk_batch_get_state", "odk_batch_set_state", "odk_batch_get_debug", "odk_set_debug_dump", "odk_batch_lds_size",
     "odk_batch_get_lds", "odk_lds_offset", "odk_batch_record_size", "odk_batch_get_records", "odk_batch_set_records", "odk_batch_timing", "odk_gae", "odk_ppo_head",
     "odk_policy_sample", "odk_adam_clip", "odk_silu_bwd_colsum", "odk_colsum_partial", "odk_colsum_finalize", "odk_gather_rows", "odk_dw_gemm",
@@ -347,6 +348,23 @@ def sensor_fault_rows(n: int) -> np.ndarray:
     rows = np.zeros((int(n), SENSOR_NPRM), np.float32)
     rows[:, SENSOR_IMU_ROT:SENSOR_IMU_ROT + 9] = np.eye(3, dtype=np.float32).reshape(9)
     rows[:, SENSOR_GYRO_SCALE] = rows[:, SENSOR_ACC_SCALE] = 1.0
+    return rows
+
+
+# odk_action_apply's rows (include/odk.h ODK_ACT_*): a fault row of ACT_NPRM floats per env, every entry in action units ([16] = per
+# actuator), and a state row of ACT_NSTATE floats: five scalars, the filter's state and the action last delivered
+ACT_NPRM = 48
+ACT_NSTATE = 48
+ACT_GAIN, ACT_NOISE, ACT_LIMIT, ACT_ALPHA, ACT_QUANT, ACT_DROP_P, ACT_DROP_LEN, ACT_SEED, ACT_OFFSET, ACT_FREEZE_AT = 0, 1, 2, 3, 4, 5, 6, 7, 16, 32
+ACT_HEAD, ACT_EPISODE, ACT_HOLD, ACT_CALLS, ACT_DROPS, ACT_FILT, ACT_PREV = 0, 1, 2, 3, 4, 16, 32
+
+
+def action_fault_rows(n: int) -> np.ndarray:
+    """[n, ACT_NPRM] float32 all-nominal fault rows to fill in: gain 1, a loss run of 1, no actuator ever frozen (-1), zeros elsewhere.
+    `odk_action_apply` hands back the input's bits under such a row."""
+    rows = np.zeros((int(n), ACT_NPRM), np.float32)
+    rows[:, ACT_GAIN] = rows[:, ACT_DROP_LEN] = 1.0
+    rows[:, ACT_FREEZE_AT:ACT_FREEZE_AT + 16] = -1.0
     return rows
 
 
@@ -1372,6 +1390,36 @@ class Batch:
         if self.model.nu > 16:
             raise OdkError(f"sensor_apply: the model has {self.model.nu} actuators, a row holds 16")
         _chk(self.L.odk_sensor_apply(self._b, C.c_void_p(obs.data_ptr()), _ptr(done), C.c_void_p(fault.data_ptr()), C.c_void_p(state.data_ptr()),
+                                     C.c_void_p(out.data_ptr()), self._stream()))
+
+    @staticmethod
+    def action_fault_rows(n: int) -> np.ndarray:
+        """`action_fault_rows(n)`: [n, ACT_NPRM] float32 all-nominal fault rows to fill in."""
+        return action_fault_rows(n)
+
+    def action_apply(self, act, done, fault, state, out):
+        """One `odk_action_apply` launch: `out` ([nenv, nu] float32, what `step` is then given) <- `act` (the policy's action, only read) as
+        env e's link to its servos would deliver it -- `fault` ([nenv, ACT_NPRM], `action_fault_rows` to fill in; action units) names the
+        fault, `state` ([nenv, ACT_NSTATE], zeroed before an episode's first call) holds the step and episode counts, the loss run, the
+        filter's state and the action last delivered, `done` ([nenv], or None) starts a new episode.  An all-nominal `fault` copies every
+        bit.  `out` must not share memory with `act`."""
+        import torch
+        nu = int(self.model.nu)
+        check_accumulator("action_apply: act", act, self.nenv, nu, self.device)
+        check_accumulator("action_apply: out", out, self.nenv, nu, self.device)
+        check_accumulator("action_apply: fault", fault, self.nenv, ACT_NPRM, self.device)
+        check_accumulator("action_apply: state", state, self.nenv, ACT_NSTATE, self.device)
+        if done is not None:
+            if not torch.is_tensor(done) or tuple(done.shape) != (self.nenv,):
+                raise OdkError(f"action_apply: done: expected a torch tensor of shape ({self.nenv},) or None, got "
+                               f"{tuple(done.shape) if hasattr(done, 'shape') else type(done).__name__}")
+            _check_placement("action_apply: done", done, torch.float32, self.device)
+        lo, hi = act.data_ptr(), act.data_ptr() + act.numel() * 4
+        if out is act or (out.data_ptr() < hi and lo < out.data_ptr() + out.numel() * 4):
+            raise OdkError("action_apply: out shares memory with act (the stage is out of place: the policy's action is only read)")
+        if nu > 16:
+            raise OdkError(f"action_apply: the model has {nu} actuators, a row holds 16")
+        _chk(self.L.odk_action_apply(self._b, C.c_void_p(act.data_ptr()), _ptr(done), C.c_void_p(fault.data_ptr()), C.c_void_p(state.data_ptr()),
                                      C.c_void_p(out.data_ptr()), self._stream()))
 
     def physics_step(self, ctrl, n_substeps: int = 10):
