@@ -7,6 +7,7 @@ if `csrc/libodk.so` is missing or no HIP device is visible.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -150,100 +151,103 @@ def load_library() -> C.CDLL:
     # hipSetDevice then reports "no ROCm-capable device" on a box whose GPU torch drives happily.
     import torch  # noqa: F401
     L = C.CDLL(LIB_PATH)
-    P, PP = C.c_void_p, C.POINTER(C.c_void_p)
-    FP, DP = C.POINTER(C.c_float), C.POINTER(C.c_double)
-    L.odk_last_error.restype = C.c_char_p
-    L.odk_default_config.argtypes = [C.POINTER(EnvConfig)]
-    L.odk_default_config_standing.argtypes = [C.POINTER(EnvConfig)]
-    L.odk_obs_sizes.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.odk_model_load.argtypes = [C.c_char_p, C.c_uint64, PP]
-    L.odk_model_free.argtypes = [P]
-    L.odk_model_dims.argtypes = [P] + [C.POINTER(C.c_int)] * 4
-    L.odk_model_obs_sizes.argtypes = [P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.odk_batch_lanes.argtypes = [P]
-    L.odk_model_reduced.argtypes = [P] + [C.POINTER(C.c_int)] * 6
-    L.odk_model_body_lanes.argtypes = [P, C.c_int, C.POINTER(C.c_int), C.c_int]
-    L.odk_model_env_lds_floats.argtypes = [P]
-    L.odk_batch_create.argtypes = [P, C.POINTER(EnvConfig), C.c_int, C.c_int, FP, DP, C.c_int, DP, C.c_int, DP, C.c_int, DP, C.c_int, PP]
-    L.odk_batch_destroy.argtypes = [P]
-    L.odk_batch_set_config.argtypes = [P, C.POINTER(EnvConfig)]
-    L.odk_batch_set_param.argtypes = [P, C.c_int, FP, C.c_int]
-    L.odk_reset.argtypes = [P, C.c_uint32, C.c_uint32, C.POINTER(Outputs), P]
-    L.odk_step.argtypes = [P, P, C.POINTER(Outputs), P]
-    L.odk_physics_step.argtypes = [P, P, C.c_int, P]
-    L.odk_batch_bind_commands.argtypes = [P, P, C.c_int]
-    L.odk_batch_bind_pushes.argtypes = [P, P, C.c_int]
-    L.odk_batch_bind_action_delays.argtypes = [P, P, C.c_int]
-    L.odk_batch_set_reward_terms.argtypes = [P, C.POINTER(RewardTerms)]
-    L.odk_batch_bind_reward_metrics.argtypes = [P, P]
-    L.odk_batch_set_imitation_joints.argtypes = [P, C.POINTER(C.c_int32), C.c_int]
-    L.odk_batch_set_head_joints.argtypes = [P, C.POINTER(C.c_int32), C.c_int]
-    L.odk_tracking_accumulate.argtypes = [P, P, P, P, P, P, P]
-    L.odk_push_accumulate.argtypes = [P, P, P, P, P, C.c_float, C.c_float, P, P]
-    L.odk_gait_accumulate.argtypes = [P, P, P, P, P, P, P, P]
-    L.odk_posture_accumulate.argtypes = [P, P, P, P, P, C.c_float, P, P]
-    L.odk_imitation_accumulate.argtypes = [P, P, P, P, P, C.c_int, P, P]
-    L.odk_command_schedule_apply.argtypes = [P, P, C.c_int, C.c_int, P, P, P]
-    L.odk_response_accumulate.argtypes = [P, P, P, P, P, P, C.c_int, C.c_int, P, C.c_float, C.c_float, C.c_int, P, P]
-    L.odk_fall_row_floats.argtypes = [P, C.c_int]
-    L.odk_fall_accumulate.argtypes = [P, P, P, P, P, P, C.c_float, C.c_int, P, C.c_int, P]
-    L.odk_path_begin.argtypes = [P, P, P]
-    L.odk_path_accumulate.argtypes = [P, P, P, P, P, C.c_int, P, C.c_float, P, P]
-    L.odk_waypoint_command_apply.argtypes = [P, P, C.c_int, P, P, P, C.c_float, C.c_float, C.c_float, C.c_float, P]
-    L.odk_sensor_apply.argtypes = [P, P, P, P, P, P, P]
-    L.odk_action_apply.argtypes = [P, P, P, P, P, P, P]
-    L.odk_batch_get_state.argtypes = [P, FP, FP, FP]
-    L.odk_batch_set_state.argtypes = [P, FP, FP, FP]
-    L.odk_batch_get_debug.argtypes = [P, FP, FP, FP, FP]
-    L.odk_set_debug_dump.argtypes = [C.c_int]
-    L.odk_batch_lds_size.argtypes = [P]
-    L.odk_batch_get_lds.argtypes = [P, FP]
-    L.odk_lds_offset.argtypes = [P, C.c_char_p]
-    L.odk_batch_record_size.argtypes = [P]
-    L.odk_batch_get_records.argtypes = [P, FP]
-    L.odk_batch_set_records.argtypes = [P, FP]
-    L.odk_batch_timing.argtypes = [P, C.c_int, FP, C.POINTER(C.c_int)]
-    L.odk_record_field.argtypes = [P, C.c_char_p] + [C.POINTER(C.c_int)] * 3
-    L.odk_gae.argtypes = [P, P, P, P, P, P, P, P, C.c_int, C.c_int, C.c_float, C.c_float, P]
-    L.odk_ppo_head.argtypes = [P] * 11 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, P]
-    L.odk_policy_sample.argtypes = [P, P, P, P, P, C.c_int, C.c_int, P]
-    L.odk_adam_clip.argtypes = [P, P, P, P, P, C.c_longlong] + [C.c_float] * 5 + [P]
-    L.odk_silu_bwd_colsum.argtypes = [P, P, P, P, P, C.c_int, C.c_int, P]
-    L.odk_colsum_partial.argtypes = [P, P, C.c_int, C.c_int, P]
-    L.odk_colsum_finalize.argtypes = [PP, PP, C.POINTER(C.c_int), C.c_int, C.c_int, P]
-    L.odk_dw_gemm.argtypes = [PP, PP, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_int), C.c_int, P, C.c_longlong, P,
-                              C.POINTER(GradFinish), P]
-    IP, LP = C.POINTER(C.c_int), C.POINTER(C.c_longlong)
-    L.odk_mlp_forward.argtypes = [C.POINTER(MlpDesc), C.c_int, P]
-    L.odk_mlp_backward.argtypes = [C.POINTER(MlpDesc), C.c_int, P]
-    L.odk_mlp_set_profile.argtypes = [P]
-    L.odk_mlp_set_profile.restype = None
-    L.odk_pack_weights.argtypes = [P, C.c_longlong, P, C.c_longlong, P, C.c_longlong, C.POINTER(WeightTableC), P]
-    L.odk_adam_clip_packed.argtypes = [P, P, P, P, P, C.c_longlong] + [C.c_float] * 5 + [P, C.c_longlong, P, C.c_longlong, C.POINTER(WeightTableC), C.c_int, P]
-    L.odk_adam_clip_packed_tail.argtypes = [P, P, P, P, P, C.c_longlong] + [C.c_float] * 5 + [P, C.c_longlong, P, C.c_longlong, C.POINTER(WeightTableC), C.c_int,
-                                            C.POINTER(StepTail), P]
-    L.odk_ppo_gae_head.argtypes = [C.POINTER(GaeHeadArgs), P]
-    L.odk_col_moments.argtypes = [P, C.c_longlong, C.c_int, C.c_int, P, P]
-    L.odk_moments_update.argtypes = [P, C.c_int, C.c_int, C.c_longlong, P, P, P, P, C.c_float, C.c_float, P]
-    L.odk_colsum_fold.argtypes = [PP, PP, IP, IP, C.c_int, P]
-    L.odk_gather_rows.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.c_int, P, C.c_int, C.c_longlong, P]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
 
-EXPORTED_SYMBOLS = (
-    "odk_last_error", "odk_default_config", "odk_default_config_standing", "odk_obs_sizes", "odk_model_load", "odk_model_free", "odk_model_dims", "odk_model_obs_sizes", "odk_batch_lanes", "odk_model_reduced", "odk_model_body_lanes",
-    "odk_model_env_lds_floats", "odk_batch_create",
-    "odk_batch_destroy", "odk_batch_set_config", "odk_batch_set_param", "odk_reset", "odk_step", "odk_physics_step",
-    "odk_batch_bind_commands", "odk_batch_set_reward_terms", "odk_batch_bind_reward_metrics", "odk_batch_set_imitation_joints", "odk_batch_set_head_joints",
-    "odk_tracking_accumulate", "odk_batch_bind_pushes", "odk_batch_bind_action_delays", "odk_push_accumulate", "odk_gait_accumulate", "odk_posture_accumulate",
-    "odk_imitation_accumulate", "odk_command_schedule_apply", "odk_response_accumulate", "odk_fall_row_floats", "odk_fall_accumulate",
-    "odk_path_begin", "odk_path_accumulate", "odk_waypoint_command_apply", "odk_sensor_apply", "odk_action_apply",
-    "odk_batch_get_state", "odk_batch_set_state", "odk_batch_get_debug", "odk_set_debug_dump", "odk_batch_lds_size",
-    "odk_batch_get_lds", "odk_lds_offset", "odk_batch_record_size", "odk_batch_get_records", "odk_batch_set_records", "odk_batch_timing", "odk_gae", "odk_ppo_head",
-    "odk_policy_sample", "odk_adam_clip", "odk_silu_bwd_colsum", "odk_colsum_partial", "odk_colsum_finalize", "odk_gather_rows", "odk_dw_gemm",
-    "odk_mlp_forward", "odk_mlp_backward", "odk_mlp_set_profile", "odk_pack_weights", "odk_adam_clip_packed", "odk_colsum_fold",
-    "odk_adam_clip_packed_tail", "odk_ppo_gae_head", "odk_col_moments", "odk_moments_update")
+def _signatures() -> Dict[str, tuple]:
+    """name -> (restype, argtypes) of every function include/odk.h declares, each once: what `load_library` binds and `EXPORTED_SYMBOLS`
+    lists.  tests/test_abi_host.py holds it to the header's prototypes: names, argument count and kind, return type, and a struct pointer as
+    POINTER(its Structure).  P: a device pointer, a stream or an opaque odk_model* / odk_batch*."""
+    I, F, LL, P, S = C.c_int, C.c_float, C.c_longlong, C.c_void_p, C.c_char_p
+    PP, FP, DP, IP, LP, I32P = (C.POINTER(t) for t in (C.c_void_p, C.c_float, C.c_double, C.c_int, C.c_longlong, C.c_int32))
+    CFG, OUTS, TABLE = C.POINTER(EnvConfig), C.POINTER(Outputs), C.POINTER(WeightTableC)
+    report = [P, P, P, P, P]                        # batch, priv, done, truncation, track_acc: how every report's accumulate starts
+    adam = [P, P, P, P, P, LL, F, F, F, F, F]       # params, grads, m, v, acc, n, lr, b1, b2, eps, max_grad_norm
+    packed = adam + [P, LL, P, LL, TABLE, I]        # + the two packed copies with their sizes, the table, norm_blocks
+    return {
+        "odk_last_error": (S, []),
+        "odk_default_config": (None, [CFG]),
+        "odk_default_config_standing": (None, [CFG]),
+        "odk_obs_sizes": (None, [I, IP, IP]),
+        "odk_model_load": (I, [S, C.c_uint64, PP]),
+        "odk_model_free": (None, [P]),
+        "odk_model_dims": (I, [P, IP, IP, IP, IP]),
+        "odk_model_obs_sizes": (I, [P, I, IP, IP]),
+        "odk_model_reduced": (I, [P, IP, IP, IP, IP, IP, IP]),
+        "odk_model_body_lanes": (I, [P, I, IP, I]),
+        "odk_model_env_lds_floats": (I, [P]),
+        "odk_model_hot_words": (I, [P, IP, IP]),
+        "odk_batch_create": (I, [P, CFG, I, I, FP, DP, I, DP, I, DP, I, DP, I, PP]),
+        "odk_batch_destroy": (None, [P]),
+        "odk_batch_set_config": (I, [P, CFG]),
+        "odk_batch_set_param": (I, [P, I, FP, I]),
+        "odk_reset": (I, [P, C.c_uint32, C.c_uint32, OUTS, P]),
+        "odk_step": (I, [P, P, OUTS, P]),
+        "odk_batch_bind_commands": (I, [P, P, I]),
+        "odk_batch_set_reward_terms": (I, [P, C.POINTER(RewardTerms)]),
+        "odk_batch_bind_reward_metrics": (I, [P, P]),
+        "odk_batch_set_imitation_joints": (I, [P, I32P, I]),
+        "odk_batch_set_head_joints": (I, [P, I32P, I]),
+        "odk_tracking_accumulate": (I, [P, P, P, P, P, P, P]),
+        "odk_batch_bind_pushes": (I, [P, P, I]),
+        "odk_batch_bind_action_delays": (I, [P, P, I]),
+        "odk_push_accumulate": (I, report + [F, F, P, P]),
+        "odk_gait_accumulate": (I, report + [P, P, P]),
+        "odk_posture_accumulate": (I, report + [F, P, P]),
+        "odk_imitation_accumulate": (I, report + [I, P, P]),
+        "odk_command_schedule_apply": (I, [P, P, I, I, P, P, P]),
+        "odk_response_accumulate": (I, report + [P, I, I, P, F, F, I, P, P]),
+        "odk_fall_row_floats": (I, [P, I]),
+        "odk_fall_accumulate": (I, report + [P, F, I, P, I, P]),
+        "odk_path_begin": (I, [P, P, P]),
+        "odk_path_accumulate": (I, [P, P, P, P, P, I, P, F, P, P]),
+        "odk_waypoint_command_apply": (I, [P, P, I, P, P, P, F, F, F, F, P]),
+        "odk_sensor_apply": (I, [P, P, P, P, P, P, P]),
+        "odk_action_apply": (I, [P, P, P, P, P, P, P]),
+        "odk_physics_step": (I, [P, P, I, P]),
+        "odk_batch_get_state": (I, [P, FP, FP, FP]),
+        "odk_batch_set_state": (I, [P, FP, FP, FP]),
+        "odk_batch_get_debug": (I, [P, FP, FP, FP, FP]),
+        "odk_set_debug_dump": (None, [I]),
+        "odk_batch_lds_size": (I, [P]),
+        "odk_batch_get_lds": (I, [P, FP]),
+        "odk_lds_offset": (I, [P, S]),
+        "odk_batch_lanes": (I, [P]),
+        "odk_batch_record_size": (I, [P]),
+        "odk_batch_get_records": (I, [P, FP]),
+        "odk_batch_set_records": (I, [P, FP]),
+        "odk_record_field": (I, [P, S, IP, IP, IP]),
+        "odk_gae": (I, [P, P, P, P, P, P, P, P, I, I, F, F, P]),
+        "odk_ppo_head": (I, [P] * 11 + [I, I, F, F, F, P]),
+        "odk_policy_sample": (I, [P, P, P, P, P, I, I, P]),
+        "odk_adam_clip": (I, adam + [P]),
+        "odk_silu_bwd_colsum": (I, [P, P, P, P, P, I, I, P]),
+        "odk_colsum_partial": (I, [P, P, I, I, P]),
+        "odk_colsum_finalize": (I, [PP, PP, IP, I, I, P]),
+        "odk_dw_gemm": (I, [PP, PP, IP, IP, LP, I, IP, I, P, LL, P, C.POINTER(GradFinish), P]),
+        "odk_mlp_forward": (I, [C.POINTER(MlpDesc), I, P]),
+        "odk_mlp_backward": (I, [C.POINTER(MlpDesc), I, P]),
+        "odk_dw_set_profile": (None, [P]),
+        "odk_mlp_set_profile": (None, [P]),
+        "odk_mlp_set_wg_profile": (None, [P]),
+        "odk_pack_weights": (I, [P, LL, P, LL, P, LL, TABLE, P]),
+        "odk_adam_clip_packed": (I, packed + [P]),
+        "odk_adam_clip_packed_tail": (I, packed + [C.POINTER(StepTail), P]),
+        "odk_ppo_gae_head": (I, [C.POINTER(GaeHeadArgs), P]),
+        "odk_col_moments": (I, [P, LL, I, I, P, P]),
+        "odk_moments_update": (I, [P, I, I, LL, P, P, P, P, F, F, P]),
+        "odk_colsum_fold": (I, [PP, PP, IP, IP, I, P]),
+        "odk_gather_rows": (I, [PP, PP, IP, LP, I, P, I, LL, P]),
+        "odk_batch_timing": (I, [P, I, FP, IP]),
+    }
+
+
+SIGNATURES = _signatures()
+EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
 
 # odk_tracking_accumulate's per-env slots (include/odk.h ODK_TRACK_*)
@@ -262,14 +266,20 @@ def _check_placement(name: str, t, dtype, device: int) -> None:
         raise OdkError(f"{name}: the tensor must live on cuda:{device} (the env's device), got {t.device}")
 
 
+def _check_tensor(name: str, t, dtype: str, device: int, want: str, shape_ok, or_none: str = "") -> None:
+    """What every `check_*` of a tensor argument does, in this order: a tensor at all, `shape_ok(tuple(t.shape))` (`want` says the shape in
+    words), then `_check_placement` with torch's `dtype`."""
+    import torch
+    if not torch.is_tensor(t):
+        raise OdkError(f"{name}: expected a torch tensor{or_none}, got {type(t).__name__}")
+    if not shape_ok(tuple(t.shape)):
+        raise OdkError(f"{name}: shape must be {want}, got {tuple(t.shape)}")
+    _check_placement(name, t, getattr(torch, dtype), device)
+
+
 def check_commands(cmd, nenv: int, device: int) -> None:
     """What `Batch.bind_commands` accepts: a contiguous float32 [nenv, 7] tensor on cuda:`device`; raises OdkError otherwise."""
-    import torch
-    if not torch.is_tensor(cmd):
-        raise OdkError(f"commands: expected a torch tensor or None, got {type(cmd).__name__}")
-    if tuple(cmd.shape) != (int(nenv), NCOMMAND):
-        raise OdkError(f"commands: shape must be ({nenv}, {NCOMMAND}), got {tuple(cmd.shape)}")
-    _check_placement("commands", cmd, torch.float32, device)
+    _check_tensor("commands", cmd, "float32", device, f"({nenv}, {NCOMMAND})", lambda s: s == (int(nenv), NCOMMAND), " or None")
 
 
 # odk_push_accumulate's per-env slots (include/odk.h ODK_PUSH_*)
@@ -381,12 +391,7 @@ def sensor_rotation(roll_deg: float, pitch_deg: float, yaw_deg: float) -> np.nda
 
 def check_pushes(push, nenv: int, device: int) -> None:
     """What `Batch.bind_pushes` accepts: a contiguous float32 [nenv, >= 2] tensor on cuda:`device`; raises OdkError otherwise."""
-    import torch
-    if not torch.is_tensor(push):
-        raise OdkError(f"pushes: expected a torch tensor or None, got {type(push).__name__}")
-    if push.dim() != 2 or int(push.shape[0]) != int(nenv) or int(push.shape[1]) < 2:
-        raise OdkError(f"pushes: shape must be ({nenv}, >= 2), got {tuple(push.shape)}")
-    _check_placement("pushes", push, torch.float32, device)
+    _check_tensor("pushes", push, "float32", device, f"({nenv}, >= 2)", lambda s: len(s) == 2 and s[0] == int(nenv) and s[1] >= 2, " or None")
 
 
 ACTION_DELAY_ROWS = 3      # the action-history ring: delay 0 (the action just given), 1, 2; a negative device row means "sample"
@@ -412,12 +417,7 @@ def check_action_delays(delays, nenv: int, device: int) -> None:
 def check_accumulator(name: str, acc, nenv: int, ncol: int, device: int) -> None:
     """An accumulator argument of one of `Batch`'s `*_accumulate` methods: a contiguous float32 [nenv, ncol] tensor on cuda:`device`; OdkError
     otherwise."""
-    import torch
-    if not torch.is_tensor(acc):
-        raise OdkError(f"{name}: expected a torch tensor, got {type(acc).__name__}")
-    if tuple(acc.shape) != (int(nenv), int(ncol)):
-        raise OdkError(f"{name}: shape must be ({nenv}, {ncol}), got {tuple(acc.shape)}")
-    _check_placement(name, acc, torch.float32, device)
+    _check_tensor(name, acc, "float32", device, f"({nenv}, {ncol})", lambda s: s == (int(nenv), int(ncol)))
 
 
 def _check_report(batch, name: str, acc, ncol: int, track_acc) -> None:
@@ -428,7 +428,7 @@ def _check_report(batch, name: str, acc, ncol: int, track_acc) -> None:
 
 def _report_ptrs(batch, track_acc):
     """What every odk_*_accumulate starts with behind the batch: priv, done, truncation, track_acc."""
-    return tuple(C.c_void_p(t.data_ptr()) for t in (batch.priv, batch.done, batch.truncation, track_acc))
+    return tuple(_ptr(t) for t in (batch.priv, batch.done, batch.truncation, track_acc))
 
 
 def _check_torque_limit(batch, name: str, t):
@@ -438,7 +438,14 @@ def _check_torque_limit(batch, name: str, t):
     if not hasattr(t, "dim") or t.dim() != 1:
         raise OdkError(f"{name}: torque_limit: expected a 1-D torch tensor or None, got {type(t).__name__}")
     check_accumulator(f"{name}: torque_limit", t.unsqueeze(0), 1, batch.model.nu, batch.device)      # as one row of [1, nu]
-    return C.c_void_p(t.data_ptr())
+    return _ptr(t)
+
+
+def _check_table_and_map(name: str, what: str, table, of_env, nenv: int, device: int, want: str, shape_ok) -> tuple:
+    """A float32 table, argument `what`, then the int32 [nenv] map `<what>_of_env` that gives every env a row of it; returns the table's shape."""
+    _check_tensor(f"{name}: {what}", table, "float32", device, want, shape_ok)
+    _check_tensor(f"{name}: {what}_of_env", of_env, "int32", device, f"({nenv},)", lambda s: s == (int(nenv),))
+    return tuple(int(n) for n in table.shape)
 
 
 def check_schedule(name: str, sched, sched_of_env, nenv: int, device: int):
@@ -446,18 +453,8 @@ def check_schedule(name: str, sched, sched_of_env, nenv: int, device: int):
     [nsched >= 1, 1 .. SCHED_MAX_SEGMENTS, SCHED_SEG_FLOATS] tensor and `sched_of_env` a contiguous int32 [nenv] tensor, both on cuda:`device`;
     OdkError otherwise.  Returns (nsched, nseg).  The contents (segment 0 at step 0, increasing starts, map entries in range) are the
     builder's to check: track.schedule_table / track.schedule_blocks."""
-    import torch
-    if not torch.is_tensor(sched):
-        raise OdkError(f"{name}: sched: expected a torch tensor, got {type(sched).__name__}")
-    if sched.dim() != 3 or int(sched.shape[0]) < 1 or not 1 <= int(sched.shape[1]) <= SCHED_MAX_SEGMENTS or int(sched.shape[2]) != SCHED_SEG_FLOATS:
-        raise OdkError(f"{name}: sched: shape must be (nsched >= 1, 1 .. {SCHED_MAX_SEGMENTS}, {SCHED_SEG_FLOATS}), got {tuple(sched.shape)}")
-    _check_placement(f"{name}: sched", sched, torch.float32, device)
-    if not torch.is_tensor(sched_of_env):
-        raise OdkError(f"{name}: sched_of_env: expected a torch tensor, got {type(sched_of_env).__name__}")
-    if tuple(sched_of_env.shape) != (int(nenv),):
-        raise OdkError(f"{name}: sched_of_env: shape must be ({nenv},), got {tuple(sched_of_env.shape)}")
-    _check_placement(f"{name}: sched_of_env", sched_of_env, torch.int32, device)
-    return int(sched.shape[0]), int(sched.shape[1])
+    return _check_table_and_map(name, "sched", sched, sched_of_env, nenv, device, f"(nsched >= 1, 1 .. {SCHED_MAX_SEGMENTS}, {SCHED_SEG_FLOATS})",
+                                lambda s: len(s) == 3 and s[0] >= 1 and 1 <= s[1] <= SCHED_MAX_SEGMENTS and s[2] == SCHED_SEG_FLOATS)[:2]
 
 
 def check_courses(name: str, course, course_of_env, nenv: int, device: int) -> int:
@@ -465,18 +462,8 @@ def check_courses(name: str, course, course_of_env, nenv: int, device: int) -> i
     [ncourse >= 1, PATH_COURSE_FLOATS] tensor and `course_of_env` a contiguous int32 [nenv] tensor, both on cuda:`device`; OdkError otherwise.
     Returns ncourse.  The contents (a count of 1 .. PATH_MAX_WAYPOINTS, finite points, map entries in range) are the builder's to check:
     track.course_table / track.schedule_blocks; the kernels clamp what they index with."""
-    import torch
-    if not torch.is_tensor(course):
-        raise OdkError(f"{name}: course: expected a torch tensor, got {type(course).__name__}")
-    if course.dim() != 2 or int(course.shape[0]) < 1 or int(course.shape[1]) != PATH_COURSE_FLOATS:
-        raise OdkError(f"{name}: course: shape must be (ncourse >= 1, {PATH_COURSE_FLOATS}), got {tuple(course.shape)}")
-    _check_placement(f"{name}: course", course, torch.float32, device)
-    if not torch.is_tensor(course_of_env):
-        raise OdkError(f"{name}: course_of_env: expected a torch tensor, got {type(course_of_env).__name__}")
-    if tuple(course_of_env.shape) != (int(nenv),):
-        raise OdkError(f"{name}: course_of_env: shape must be ({nenv},), got {tuple(course_of_env.shape)}")
-    _check_placement(f"{name}: course_of_env", course_of_env, torch.int32, device)
-    return int(course.shape[0])
+    return _check_table_and_map(name, "course", course, course_of_env, nenv, device, f"(ncourse >= 1, {PATH_COURSE_FLOATS})",
+                                lambda s: len(s) == 2 and s[0] >= 1 and s[1] == PATH_COURSE_FLOATS)[0]
 
 
 def check_path_parameter(name: str, what: str, value, positive: bool = False) -> float:
@@ -509,35 +496,36 @@ def obs_sizes(env_kind: int):
     return a.value, b.value
 
 
-def model_obs_sizes(model: Model, env_kind: int = 0):
-    """(nobs, npriv) of `model`'s env kernels (`odk_model_obs_sizes`): the reference's layout with the robot's actuator count; host-only."""
+@contextlib.contextmanager
+def _loaded_model(model: Model):
+    """(L, handle) of `model` loaded into the library for a host-only query, freed on the way out."""
     L = load_library()
     blob = model.blob()
     h = C.c_void_p()
     _chk(L.odk_model_load(blob, len(blob), C.byref(h)))
     try:
-        a, b = C.c_int(0), C.c_int(0)
-        _chk(L.odk_model_obs_sizes(h, int(env_kind), C.byref(a), C.byref(b)))
-        return a.value, b.value
+        yield L, h
     finally:
         L.odk_model_free(h)
 
 
+def model_obs_sizes(model: Model, env_kind: int = 0):
+    """(nobs, npriv) of `model`'s env kernels (`odk_model_obs_sizes`): the reference's layout with the robot's actuator count; host-only."""
+    with _loaded_model(model) as (L, h):
+        a, b = C.c_int(0), C.c_int(0)
+        _chk(L.odk_model_obs_sizes(h, int(env_kind), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+
 def model_reduction(model: Model) -> Dict:
     """The twin-dof reduction the kernels use for `model` (odk_model_reduced) + its LDS footprint; host-only, no GPU."""
-    L = load_library()
-    blob = model.blob()
-    h = C.c_void_p()
-    _chk(L.odk_model_load(blob, len(blob), C.byref(h)))
-    try:
+    with _loaded_model(model) as (L, h):
         ints = [C.c_int(0) for _ in range(4)]
         main, twin = (C.c_int * 32)(), (C.c_int * 32)()
         _chk(L.odk_model_reduced(h, *[C.byref(i) for i in ints], main, twin))
         nvr = ints[1].value
         return dict(paired=ints[0].value, nvr=nvr, nMr=ints[2].value, nHr=ints[3].value, main=list(main)[:nvr], twin=list(twin)[:nvr],
                     env_lds_floats=L.odk_model_env_lds_floats(h))
-    finally:
-        L.odk_model_free(h)
 
 
 HOT_FIELD_NAMES = ("foot_body0", "foot_body1", "foot_nvert0", "foot_nvert1", "foot_rchain_first0", "foot_rchain_first1", "foot_rchain_len0", "foot_rchain_len1",
@@ -547,33 +535,19 @@ HOT_FIELD_NAMES = ("foot_body0", "foot_body1", "foot_nvert0", "foot_nvert1", "fo
 def model_hot_words(model: Model) -> Dict:
     """The packed words the plane-floor step kernel reads the model's launch-invariant small integers from, and the values they were
     packed from (odk_model_hot_words); host-only, no GPU."""
-    L = load_library()
-    L.odk_model_hot_words.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.odk_model_hot_words.restype = C.c_int
-    blob = model.blob()
-    h = C.c_void_p()
-    _chk(L.odk_model_load(blob, len(blob), C.byref(h)))
-    try:
+    with _loaded_model(model) as (L, h):
         packed, fields = (C.c_int * 3)(), (C.c_int * 12)()
         _chk(L.odk_model_hot_words(h, packed, fields))
         return dict(packed=[v & 0xFFFFFFFF for v in packed], fields=dict(zip(HOT_FIELD_NAMES, list(fields))))
-    finally:
-        L.odk_model_free(h)
 
 
 def model_body_lanes(model: Model, lanes_per_env: int) -> List[int]:
     """Body id of each of an env's `lanes_per_env` lanes in the kinematics / inertia sweeps, -1 for a lane without a body
     (odk_model_body_lanes); host-only, no GPU."""
-    L = load_library()
-    blob = model.blob()
-    h = C.c_void_p()
-    _chk(L.odk_model_load(blob, len(blob), C.byref(h)))
-    try:
+    with _loaded_model(model) as (L, h):
         out = (C.c_int * lanes_per_env)()
         _chk(L.odk_model_body_lanes(h, int(lanes_per_env), out, lanes_per_env))
         return list(out)
-    finally:
-        L.odk_model_free(h)
 
 
 def load_prm() -> Dict[str, np.ndarray]:
@@ -590,6 +564,7 @@ def _dp(a: np.ndarray):
 
 
 def _stream(t):
+    """torch's current stream on `t.device`; `t`: a tensor or a `Batch`."""
     import torch
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
@@ -852,7 +827,7 @@ def col_moments(x, slices: int = 1024):
     rows, w = x.shape
     slices = max(1, min(int(slices), 1024, int(rows)))
     part = torch.empty(slices, 2, w, dtype=torch.float64, device=x.device)
-    _chk(load_library().odk_col_moments(_ptr(x), int(rows), int(w), slices, C.c_void_p(part.data_ptr()), _stream(x)))
+    _chk(load_library().odk_col_moments(_ptr(x), int(rows), int(w), slices, _ptr(part), _stream(x)))
     tot = part.sum(0)
     return tot[0], tot[1]
 
@@ -868,8 +843,8 @@ def running_stats_update(x, count, mean, summed_variance, std, std_min: float, s
     slices = max(1, min(int(slices), 1024, int(rows)))
     part = torch.empty(slices, 2, w, dtype=torch.float64, device=x.device)
     L = load_library()
-    _chk(L.odk_col_moments(_ptr(x), int(rows), int(w), slices, C.c_void_p(part.data_ptr()), _stream(x)))
-    _chk(L.odk_moments_update(C.c_void_p(part.data_ptr()), slices, int(w), int(rows), C.c_void_p(count.data_ptr()), _ptr(mean), _ptr(summed_variance), _ptr(std),
+    _chk(L.odk_col_moments(_ptr(x), int(rows), int(w), slices, _ptr(part), _stream(x)))
+    _chk(L.odk_moments_update(_ptr(part), slices, int(w), int(rows), _ptr(count), _ptr(mean), _ptr(summed_variance), _ptr(std),
                               float(std_min), float(std_max), _stream(x)))
 
 
@@ -1136,9 +1111,8 @@ class Batch:
         self.reward_terms_on = False
         self.generation = 0          # advanced by every call that rewrites the per-env records (reset / step / set_records): `State.info` checks it
 
-    # -- streams: calls are ordered on torch's current stream
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+    # -- streams: calls are ordered on torch's current stream (the module's `_stream`, as a method: it reads `self.device`)
+    _stream = _stream
 
     def set_config(self, cfg: EnvConfig):
         self.cfg = cfg
@@ -1155,7 +1129,7 @@ class Batch:
     def step(self, action):
         assert action.is_cuda and action.dtype == self.torch.float32 and action.is_contiguous() and tuple(action.shape) == (self.nenv, self.model.nu)
         self.generation += 1
-        _chk(self.L.odk_step(self._b, C.c_void_p(action.data_ptr()), C.byref(self._outs), self._stream()))
+        _chk(self.L.odk_step(self._b, _ptr(action), C.byref(self._outs), self._stream()))
 
     def bind_commands(self, cmd):
         """Drive every env with the caller's command (`odk_batch_bind_commands`): `cmd` is a contiguous float32 [nenv, 7] tensor on
@@ -1167,7 +1141,7 @@ class Batch:
             self.commands = None
             return
         check_commands(cmd, self.nenv, self.device)
-        _chk(self.L.odk_batch_bind_commands(self._b, C.c_void_p(cmd.data_ptr()), NCOMMAND))
+        _chk(self.L.odk_batch_bind_commands(self._b, _ptr(cmd), NCOMMAND))
         self.commands = cmd
 
     def bind_pushes(self, push):
@@ -1181,7 +1155,7 @@ class Batch:
             self.pushes = None
             return
         check_pushes(push, self.nenv, self.device)
-        _chk(self.L.odk_batch_bind_pushes(self._b, C.c_void_p(push.data_ptr()), int(push.shape[1])))
+        _chk(self.L.odk_batch_bind_pushes(self._b, _ptr(push), int(push.shape[1])))
         self.pushes = push
 
     def bind_action_delays(self, delays):
@@ -1196,7 +1170,7 @@ class Batch:
             self.action_delays = None
             return
         check_action_delays(delays, self.nenv, self.device)
-        _chk(self.L.odk_batch_bind_action_delays(self._b, C.c_void_p(delays.data_ptr()), int(delays.stride(0))))
+        _chk(self.L.odk_batch_bind_action_delays(self._b, _ptr(delays), int(delays.stride(0))))
         self.action_delays = delays
 
     def set_reward_terms(self, terms: Optional[RewardTerms]):
@@ -1206,7 +1180,7 @@ class Batch:
         on = terms is not None and any(float(terms.scale[i]) != 0.0 for i in range(NXTERM))
         if on and self.xmetrics is None:
             self.xmetrics = self.torch.zeros(self.nenv, NXTERM, dtype=self.torch.float32, device=self.torch.device("cuda", self.device))
-            _chk(self.L.odk_batch_bind_reward_metrics(self._b, C.c_void_p(self.xmetrics.data_ptr())))
+            _chk(self.L.odk_batch_bind_reward_metrics(self._b, _ptr(self.xmetrics)))
         _chk(self.L.odk_batch_set_reward_terms(self._b, C.byref(terms) if terms is not None else None))
         self.reward_terms_on = on
 
@@ -1231,9 +1205,7 @@ class Batch:
         assert acc.is_cuda and acc.dtype == torch.float32 and acc.is_contiguous() and tuple(acc.shape) == (self.nenv, TRACK_NACC)
         if self.commands is None:
             raise OdkError("tracking_accumulate: no commands bound (bind_commands)")
-        _chk(self.L.odk_tracking_accumulate(self._b, C.c_void_p(self.priv.data_ptr()), C.c_void_p(self.reward.data_ptr()),
-                                            C.c_void_p(self.done.data_ptr()), C.c_void_p(self.truncation.data_ptr()),
-                                            C.c_void_p(acc.data_ptr()), self._stream()))
+        _chk(self.L.odk_tracking_accumulate(self._b, _ptr(self.priv), _ptr(self.reward), _ptr(self.done), _ptr(self.truncation), _ptr(acc), self._stream()))
 
     def push_accumulate(self, acc, track_acc, lin_tol: float, ang_tol: float):
         """One `odk_push_accumulate` launch over this step's outputs into `acc` ([nenv, PUSH_NACC] float32, zeroed before the first
@@ -1243,7 +1215,7 @@ class Batch:
             raise OdkError("push_accumulate: no commands bound (bind_commands)")
         if self.pushes is None:
             raise OdkError("push_accumulate: no pushes bound (bind_pushes)")
-        _chk(self.L.odk_push_accumulate(self._b, *_report_ptrs(self, track_acc), float(lin_tol), float(ang_tol), C.c_void_p(acc.data_ptr()), self._stream()))
+        _chk(self.L.odk_push_accumulate(self._b, *_report_ptrs(self, track_acc), float(lin_tol), float(ang_tol), _ptr(acc), self._stream()))
 
     def gait_accumulate(self, acc, track_acc, torque_limit=None):
         """One `odk_gait_accumulate` launch over this step's outputs into `acc` ([nenv, GAIT_NACC] float32, zeroed before the first step),
@@ -1251,7 +1223,7 @@ class Batch:
         that actuator never counts as saturated) or None (nobody does).  Needs neither bound commands nor bound pushes."""
         _check_report(self, "gait_accumulate", acc, GAIT_NACC, track_acc)
         limit = _check_torque_limit(self, "gait_accumulate", torque_limit)
-        _chk(self.L.odk_gait_accumulate(self._b, *_report_ptrs(self, track_acc), limit, C.c_void_p(acc.data_ptr()), self._stream()))
+        _chk(self.L.odk_gait_accumulate(self._b, *_report_ptrs(self, track_acc), limit, _ptr(acc), self._stream()))
 
     def posture_accumulate(self, acc, track_acc, tol: float):
         """One `odk_posture_accumulate` launch over this step's outputs into `acc` ([nenv, POSTURE_NACC] float32, zeroed before the first
@@ -1260,7 +1232,7 @@ class Batch:
         _check_report(self, "posture_accumulate", acc, POSTURE_NACC, track_acc)
         if self.commands is None:
             raise OdkError("posture_accumulate: no commands bound (bind_commands)")
-        _chk(self.L.odk_posture_accumulate(self._b, *_report_ptrs(self, track_acc), float(tol), C.c_void_p(acc.data_ptr()), self._stream()))
+        _chk(self.L.odk_posture_accumulate(self._b, *_report_ptrs(self, track_acc), float(tol), _ptr(acc), self._stream()))
 
     def imitation_accumulate(self, acc, track_acc, period_steps: int):
         """One `odk_imitation_accumulate` launch over this step's outputs into `acc` ([nenv, IMIT_NACC] float32, zeroed before the first
@@ -1270,7 +1242,7 @@ class Batch:
         _check_report(self, "imitation_accumulate", acc, IMIT_NACC, track_acc)
         if int(period_steps) != period_steps:
             raise OdkError(f"imitation_accumulate: period_steps = {period_steps!r} (a whole number of steps)")
-        _chk(self.L.odk_imitation_accumulate(self._b, *_report_ptrs(self, track_acc), int(period_steps), C.c_void_p(acc.data_ptr()), self._stream()))
+        _chk(self.L.odk_imitation_accumulate(self._b, *_report_ptrs(self, track_acc), int(period_steps), _ptr(acc), self._stream()))
 
     def command_schedule_apply(self, sched, sched_of_env, track_acc):
         """One `odk_command_schedule_apply` launch, issued BEFORE `step`: env e's row of the bound command tensor becomes the command of the
@@ -1281,8 +1253,7 @@ class Batch:
         check_accumulator("command_schedule_apply: track_acc", track_acc, self.nenv, TRACK_NACC, self.device)
         if self.commands is None:
             raise OdkError("command_schedule_apply: no commands bound (bind_commands)")
-        _chk(self.L.odk_command_schedule_apply(self._b, C.c_void_p(sched.data_ptr()), nsched, nseg, C.c_void_p(sched_of_env.data_ptr()),
-                                               C.c_void_p(track_acc.data_ptr()), self._stream()))
+        _chk(self.L.odk_command_schedule_apply(self._b, _ptr(sched), nsched, nseg, _ptr(sched_of_env), _ptr(track_acc), self._stream()))
 
     def response_accumulate(self, acc, track_acc, sched, sched_of_env, lin_tol: float, ang_tol: float, tail_after: int):
         """One `odk_response_accumulate` launch over this step's outputs into `acc` ([nenv, RESP_NACC] float32, zeroed before the first step:
@@ -1296,8 +1267,8 @@ class Batch:
             raise OdkError(f"response_accumulate: tail_after = {tail_after!r} (a whole number of steps)")
         if self.commands is None:
             raise OdkError("response_accumulate: no commands bound (bind_commands)")
-        _chk(self.L.odk_response_accumulate(self._b, *_report_ptrs(self, track_acc), C.c_void_p(sched.data_ptr()), nsched, nseg, C.c_void_p(sched_of_env.data_ptr()),
-                                            float(lin_tol), float(ang_tol), int(tail_after), C.c_void_p(acc.data_ptr()), self._stream()))
+        _chk(self.L.odk_response_accumulate(self._b, *_report_ptrs(self, track_acc), _ptr(sched), nsched, nseg, _ptr(sched_of_env),
+                                            float(lin_tol), float(ang_tol), int(tail_after), _ptr(acc), self._stream()))
 
     def fall_row_floats(self, ring: int) -> int:
         """Floats of one env's row of the fall recorder with a ring of `ring` samples (`odk_fall_row_floats`): FALL_HEAD + ring * (FALL_SAMPLE +
@@ -1322,14 +1293,14 @@ class Batch:
         limit = _check_torque_limit(self, "fall_accumulate", torque_limit)
         if self.commands is None:
             raise OdkError("fall_accumulate: no commands bound (bind_commands)")
-        _chk(self.L.odk_fall_accumulate(self._b, *_report_ptrs(self, track_acc), limit, float(tilt_tol), int(ring), C.c_void_p(acc.data_ptr()), int(acc.shape[1]),
+        _chk(self.L.odk_fall_accumulate(self._b, *_report_ptrs(self, track_acc), limit, float(tilt_tol), int(ring), _ptr(acc), int(acc.shape[1]),
                                         self._stream()))
 
     def path_begin(self, acc):
         """One `odk_path_begin` launch, issued after `reset`: env e's row of `acc` ([nenv, PATH_NACC] float32) is zeroed and takes the base
         pose the reset left as its start pose (PATH_START_*) and as its last sample (PATH_X ..): every later pose quantity is in that frame."""
         check_accumulator("path_begin: acc", acc, self.nenv, PATH_NACC, self.device)
-        _chk(self.L.odk_path_begin(self._b, C.c_void_p(acc.data_ptr()), self._stream()))
+        _chk(self.L.odk_path_begin(self._b, _ptr(acc), self._stream()))
 
     def path_accumulate(self, acc, track_acc, course=None, course_of_env=None, radius: float = 0.0):
         """One `odk_path_accumulate` launch over this step's state into `acc` ([nenv, PATH_NACC] float32, begun by `path_begin`), issued
@@ -1342,8 +1313,8 @@ class Batch:
             raise OdkError("path_accumulate: course_of_env without a course")
         ncourse = 0 if course is None else check_courses("path_accumulate", course, course_of_env, self.nenv, self.device)
         radius = check_path_parameter("path_accumulate", "radius", radius)
-        _chk(self.L.odk_path_accumulate(self._b, C.c_void_p(self.done.data_ptr()), C.c_void_p(self.truncation.data_ptr()), C.c_void_p(track_acc.data_ptr()),
-                                        _ptr(course), ncourse, _ptr(course_of_env), radius, C.c_void_p(acc.data_ptr()), self._stream()))
+        _chk(self.L.odk_path_accumulate(self._b, _ptr(self.done), _ptr(self.truncation), _ptr(track_acc), _ptr(course), ncourse,
+                                        _ptr(course_of_env), radius, _ptr(acc), self._stream()))
 
     def waypoint_command_apply(self, course, course_of_env, track_acc, path_acc, v_cruise: float, turn_rate: float, heading_gain: float,
                                slow_dist: float):
@@ -1360,8 +1331,26 @@ class Batch:
                 check_path_parameter(fn, "heading_gain", heading_gain, True), check_path_parameter(fn, "slow_dist", slow_dist, True))
         if self.commands is None:
             raise OdkError("waypoint_command_apply: no commands bound (bind_commands)")
-        _chk(self.L.odk_waypoint_command_apply(self._b, C.c_void_p(course.data_ptr()), ncourse, C.c_void_p(course_of_env.data_ptr()),
-                                               C.c_void_p(track_acc.data_ptr()), C.c_void_p(path_acc.data_ptr()), *args, self._stream()))
+        _chk(self.L.odk_waypoint_command_apply(self._b, _ptr(course), ncourse, _ptr(course_of_env), _ptr(track_acc), _ptr(path_acc), *args,
+                                               self._stream()))
+
+    def _apply_stage(self, fn: str, src_name: str, src_what: str, src, ncol: int, done, fault, nprm: int, state, nstate: int, out):
+        """The out-of-place stages `sensor_apply` / `action_apply`: `out` <- `src` (both [nenv, ncol]) under `fault` ([nenv, nprm]) with `state`
+        ([nenv, nstate]) and `done` ([nenv] or None), refused in this order, then the one `odk_<fn>` launch."""
+        import torch
+        for what, t, n in ((src_name, src, ncol), ("out", out, ncol), ("fault", fault, nprm), ("state", state, nstate)):
+            check_accumulator(f"{fn}: {what}", t, self.nenv, n, self.device)
+        if done is not None:
+            if not torch.is_tensor(done) or tuple(done.shape) != (self.nenv,):
+                raise OdkError(f"{fn}: done: expected a torch tensor of shape ({self.nenv},) or None, got "
+                               f"{tuple(done.shape) if hasattr(done, 'shape') else type(done).__name__}")
+            _check_placement(f"{fn}: done", done, torch.float32, self.device)
+        lo, hi = src.data_ptr(), src.data_ptr() + src.numel() * 4
+        if out is src or (out.data_ptr() < hi and lo < out.data_ptr() + out.numel() * 4):
+            raise OdkError(f"{fn}: out shares memory with {src_name} (the stage is out of place: {src_what} is only read)")
+        if self.model.nu > 16:
+            raise OdkError(f"{fn}: the model has {self.model.nu} actuators, a row holds 16")
+        _chk(getattr(self.L, "odk_" + fn)(self._b, _ptr(src), _ptr(done), _ptr(fault), _ptr(state), _ptr(out), self._stream()))
 
     @staticmethod
     def sensor_fault_rows(n: int) -> np.ndarray:
@@ -1374,23 +1363,7 @@ class Batch:
         before an episode's first call) holds the ring of raw samples the delays read, `done` ([nenv], or None) refills it.  Gyro,
         accelerometer, joint positions and velocities and the two contacts are touched, every other column is copied bit for bit, and an
         all-nominal `fault` copies the whole row bit for bit.  `out` must not share memory with `obs`."""
-        import torch
-        check_accumulator("sensor_apply: obs", obs, self.nenv, self.nobs, self.device)
-        check_accumulator("sensor_apply: out", out, self.nenv, self.nobs, self.device)
-        check_accumulator("sensor_apply: fault", fault, self.nenv, SENSOR_NPRM, self.device)
-        check_accumulator("sensor_apply: state", state, self.nenv, SENSOR_NSTATE, self.device)
-        if done is not None:
-            if not torch.is_tensor(done) or tuple(done.shape) != (self.nenv,):
-                raise OdkError(f"sensor_apply: done: expected a torch tensor of shape ({self.nenv},) or None, got "
-                               f"{tuple(done.shape) if hasattr(done, 'shape') else type(done).__name__}")
-            _check_placement("sensor_apply: done", done, torch.float32, self.device)
-        lo, hi = obs.data_ptr(), obs.data_ptr() + obs.numel() * 4
-        if out is obs or (out.data_ptr() < hi and lo < out.data_ptr() + out.numel() * 4):
-            raise OdkError("sensor_apply: out shares memory with obs (the stage is out of place: the step's observation is only read)")
-        if self.model.nu > 16:
-            raise OdkError(f"sensor_apply: the model has {self.model.nu} actuators, a row holds 16")
-        _chk(self.L.odk_sensor_apply(self._b, C.c_void_p(obs.data_ptr()), _ptr(done), C.c_void_p(fault.data_ptr()), C.c_void_p(state.data_ptr()),
-                                     C.c_void_p(out.data_ptr()), self._stream()))
+        self._apply_stage("sensor_apply", "obs", "the step's observation", obs, self.nobs, done, fault, SENSOR_NPRM, state, SENSOR_NSTATE, out)
 
     @staticmethod
     def action_fault_rows(n: int) -> np.ndarray:
@@ -1403,28 +1376,11 @@ class Batch:
         fault, `state` ([nenv, ACT_NSTATE], zeroed before an episode's first call) holds the step and episode counts, the loss run, the
         filter's state and the action last delivered, `done` ([nenv], or None) starts a new episode.  An all-nominal `fault` copies every
         bit.  `out` must not share memory with `act`."""
-        import torch
-        nu = int(self.model.nu)
-        check_accumulator("action_apply: act", act, self.nenv, nu, self.device)
-        check_accumulator("action_apply: out", out, self.nenv, nu, self.device)
-        check_accumulator("action_apply: fault", fault, self.nenv, ACT_NPRM, self.device)
-        check_accumulator("action_apply: state", state, self.nenv, ACT_NSTATE, self.device)
-        if done is not None:
-            if not torch.is_tensor(done) or tuple(done.shape) != (self.nenv,):
-                raise OdkError(f"action_apply: done: expected a torch tensor of shape ({self.nenv},) or None, got "
-                               f"{tuple(done.shape) if hasattr(done, 'shape') else type(done).__name__}")
-            _check_placement("action_apply: done", done, torch.float32, self.device)
-        lo, hi = act.data_ptr(), act.data_ptr() + act.numel() * 4
-        if out is act or (out.data_ptr() < hi and lo < out.data_ptr() + out.numel() * 4):
-            raise OdkError("action_apply: out shares memory with act (the stage is out of place: the policy's action is only read)")
-        if nu > 16:
-            raise OdkError(f"action_apply: the model has {nu} actuators, a row holds 16")
-        _chk(self.L.odk_action_apply(self._b, C.c_void_p(act.data_ptr()), _ptr(done), C.c_void_p(fault.data_ptr()), C.c_void_p(state.data_ptr()),
-                                     C.c_void_p(out.data_ptr()), self._stream()))
+        self._apply_stage("action_apply", "act", "the policy's action", act, int(self.model.nu), done, fault, ACT_NPRM, state, ACT_NSTATE, out)
 
     def physics_step(self, ctrl, n_substeps: int = 10):
         assert ctrl.is_cuda and ctrl.dtype == self.torch.float32 and ctrl.is_contiguous() and tuple(ctrl.shape) == (self.nenv, self.model.nu)
-        _chk(self.L.odk_physics_step(self._b, C.c_void_p(ctrl.data_ptr()), n_substeps, self._stream()))
+        _chk(self.L.odk_physics_step(self._b, _ptr(ctrl), n_substeps, self._stream()))
 
     # -- synchronous host access (tests, checkpoints)
     def get_state(self):

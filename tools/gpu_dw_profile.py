@@ -1,12 +1,11 @@
 """Where and when each single-wave workgroup of the weight-gradient launch ran (odk_dw_set_profile):
     python tools/gpu_dw_profile.py     -> wave durations, launch span, waves per SIMD / CU / XCD"""
-import collections, ctypes as C, os, sys, torch
+import collections, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from open_duck_playground_amd import engine
 import numpy as np
 
 L = engine.load_library()
-L.odk_dw_set_profile.argtypes = [C.c_void_p]
 g = torch.Generator(device="cuda").manual_seed(0)
 specs = ((5120, 101, 28), (5376, 212, 1))
 tot, entries = 0, []

@@ -1,13 +1,12 @@
 """Per-workgroup timeline of the fused network launches (odk_mlp_set_wg_profile): how long a 16-sample tile takes, by how many
 tiles share its CU, and how the launch's span compares:   python tools/gpu_mlp_wg_profile.py [fwd|bwd]"""
-import collections, ctypes as C, os, sys, torch
+import collections, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from open_duck_playground_amd import engine
 
 which = sys.argv[1] if len(sys.argv) > 1 else "fwd"
 L = engine.load_library()
-L.odk_mlp_set_wg_profile.argtypes = [C.c_void_p]
 g = torch.Generator(device="cuda").manual_seed(0)
 specs = ((5120, 101, 28), (5376, 212, 1))
 tot, entries = 0, []
