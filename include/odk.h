@@ -730,6 +730,39 @@ int odk_action_apply(const odk_batch* b, const float* act_dev /* [nenv, nu], the
                      const float* fault_dev /* [nenv, ODK_ACT_NPRM] */, float* state_dev /* [nenv, ODK_ACT_NSTATE] */,
                      float* act_out_dev /* [nenv, nu], must not overlap act_dev */, void* stream);
 
+/* Fault resampling: training under sensor and actuation faults that are redrawn per episode.  At the start of each episode env e's row of
+ * the sensor fault table (odk_sensor_apply's fault_dev) and of the actuation fault table (odk_action_apply's) is rewritten from a small
+ * table of ranges, so that a rollout meets a new faulty robot every episode.  Issued BEFORE the two stages of the same step, with the same
+ * done_dev.  One launch, a 16-lane row per env with six slots per lane, graph-capturable, no LDS, no scratch.
+ *
+ * spec_dev [3][ODK_FAULT_NSLOT], only read: row 0 is lo, row 1 hi, row 2 the slot's kind.  Slot s < ODK_SENSOR_NPRM is slot s of the sensor
+ * row, slot s >= ODK_SENSOR_NPRM slot s - ODK_SENSOR_NPRM of the actuation row.  The kinds (a float holding 0, 1 or 2; any other value, a
+ * NaN included, counts as 0), with u the slot's draw:
+ *   ODK_FAULT_FIXED    lo's bits (a select, no arithmetic: NaN and -0.0 are kept)
+ *   ODK_FAULT_UNIFORM  lo + ((hi - lo) u)
+ *   ODK_FAULT_WHOLE    fminf(lo + floorf(((hi - lo) + 1) u), hi): the whole numbers lo .. hi, each as likely (whole steps, the actuation
+ *                      SEED); the clamp because the rounded product can reach the span
+ *   u = odk_action_apply's stateless draw with x = seed + 0x9E3779B9 (env_id_offset + e) + 0x85EBCA6B episode + 0x27D4EB2F (32 + s): step
+ *       0, episode = EPISODE after the redraw, stream 32 + s (the action stage draws from streams 0 .. 16).  An eager run, a captured
+ *       graph, ranks with their own env_id_offset and a host restatement agree.
+ *
+ * Env e's row of state_dev [nenv, ODK_FAULT_NSTATE] (zeroed by the caller before an episode's first call): HEAD, the calls since the row was
+ * zeroed, and EPISODE, the redraw count (floats: exact for 2^24); slots 2 and 3 are not touched.  Order per call: env e redraws when HEAD is
+ * 0 or done_dev[e] != 0 (done_dev may be NULL) -- the condition on which both stages refill, so with rows zeroed together a redraw and the
+ * stages' refills coincide; on a redraw EPISODE grows by 1 and all ODK_FAULT_NSLOT slots of env e are stored, the slots the stages do not
+ * read included; otherwise neither row of env e is touched; HEAD grows by 1 either way.  Both state loads come before the first store.
+ * Arithmetic is float32 + - * and floorf with every product rounded before it is added (no fused multiply-add): a numpy restatement has
+ * every bit.  Refused (ODK_ERR_INVALID, nothing launched): a null pointer other than done_dev (the message names the argument), the two
+ * fault tables overlapping each other or spec_dev. */
+#define ODK_FAULT_NSLOT (ODK_SENSOR_NPRM + ODK_ACT_NPRM)
+#define ODK_FAULT_NSTATE 4
+enum { ODK_FAULT_HEAD = 0, ODK_FAULT_EPISODE = 1 /* 2..3 are not touched */ };
+enum { ODK_FAULT_FIXED = 0, ODK_FAULT_UNIFORM = 1, ODK_FAULT_WHOLE = 2 };
+int odk_fault_resample(const odk_batch* b, const float* done_dev /* may be NULL */,
+                       const float* spec_dev /* [3][ODK_FAULT_NSLOT]: lo, hi, kind */, uint32_t seed, uint32_t env_id_offset,
+                       float* state_dev /* [nenv, ODK_FAULT_NSTATE] */, float* sensor_fault_dev /* [nenv, ODK_SENSOR_NPRM] */,
+                       float* act_fault_dev /* [nenv, ODK_ACT_NPRM] */, void* stream);
+
 /* mjx_env.step alone (physics only, n_substeps, ctrl = ctrl_dev [nenv, nu]); for parity tests */
 int odk_physics_step(odk_batch* b, const float* ctrl_dev, int n_substeps, void* stream);
 

@@ -984,3 +984,66 @@ extern "C" int odk_action_apply(const odk_batch* b, const float* act_dev, const 
   HIPCHK(hipGetLastError());
   return ODK_OK;
 }
+
+// ---- fault resampling (include/odk.h "Fault resampling": the definitions this kernel restates).  Not a report: at the start of each episode
+// env e's row of the sensor fault table and of the actuation fault table is redrawn from a table of ranges, so that training meets a new
+// faulty robot every episode.  The stages' geometry -- a 16-lane row per env, four envs per wave, a row past nenv leaves at once -- with six
+// slots per lane (lane u holds slots u, 16 + u, ..: every store of a row's 16 lanes is one contiguous 64 bytes, and a group of 16 slots lies
+// wholly in one of the two tables).  The two state loads come before the first store, and a row sits inside one wave, so lane 0's stores
+// follow every lane's loads.  No LDS, no scratch; the draws are act_uniform's (streams 32 .. 127), contraction is off and a FIXED slot is a
+// select, so a numpy restatement has the bits.
+__global__ void __launch_bounds__(256) fault_resample_kernel(const float* __restrict__ done, const float* __restrict__ spec, unsigned seed,
+                                                             unsigned env_id_offset, float* __restrict__ state, float* __restrict__ sensor_fault,
+                                                             float* __restrict__ act_fault, int nenv) {
+#pragma clang fp contract(off)
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int e = t >> 4, u = t & 15;
+  if (e >= nenv) return;
+  float* S = state + (size_t)e * ODK_FAULT_NSTATE;
+  const float n0 = S[ODK_FAULT_HEAD], ep0 = S[ODK_FAULT_EPISODE];
+  const bool redraw = n0 == 0.0f || (done && done[e] != 0.0f);
+  const float episode = redraw ? ep0 + 1.0f : ep0;
+  if (redraw) {
+    const unsigned ue = env_id_offset + (unsigned)e, uep = (unsigned)episode;
+#pragma unroll
+    for (int k = 0; k < ODK_FAULT_NSLOT / 16; k++) {
+      const int s = 16 * k + u;
+      const float lo = spec[s], hi = spec[ODK_FAULT_NSLOT + s], kind = spec[2 * ODK_FAULT_NSLOT + s];
+      const float r = act_uniform(seed, ue, uep, 0u, 32u + (unsigned)s);
+      const float uniform = lo + ((hi - lo) * r);
+      const float whole = fminf(lo + floorf(((hi - lo) + 1.0f) * r), hi);
+      const float v = kind == (float)ODK_FAULT_UNIFORM ? uniform : (kind == (float)ODK_FAULT_WHOLE ? whole : lo);
+      if (16 * k < ODK_SENSOR_NPRM) sensor_fault[(size_t)e * ODK_SENSOR_NPRM + s] = v;
+      else act_fault[(size_t)e * ODK_ACT_NPRM + (s - ODK_SENSOR_NPRM)] = v;
+    }
+  }
+  if (u == 0) {
+    S[ODK_FAULT_HEAD] = n0 + 1.0f;
+    S[ODK_FAULT_EPISODE] = episode;
+  }
+}
+
+extern "C" int odk_fault_resample(const odk_batch* b, const float* done_dev, const float* spec_dev, uint32_t seed, uint32_t env_id_offset,
+                                  float* state_dev, float* sensor_fault_dev, float* act_fault_dev, void* stream) {
+  const char* fn = "odk_fault_resample";
+  if (!b) return fail(ODK_ERR_INVALID, "%s: null batch", fn);
+  if (!spec_dev) return fail(ODK_ERR_INVALID, "%s: null spec_dev", fn);
+  if (!state_dev) return fail(ODK_ERR_INVALID, "%s: null state_dev", fn);
+  if (!sensor_fault_dev) return fail(ODK_ERR_INVALID, "%s: null sensor_fault_dev", fn);
+  if (!act_fault_dev) return fail(ODK_ERR_INVALID, "%s: null act_fault_dev", fn);
+  static_assert(ODK_FAULT_NSLOT == ODK_SENSOR_NPRM + ODK_ACT_NPRM && ODK_SENSOR_NPRM % 16 == 0 && ODK_ACT_NPRM % 16 == 0,
+                "six slots per lane, a group of 16 slots inside one table");
+  const float *sf = sensor_fault_dev, *af = act_fault_dev;
+  const size_t ns = (size_t)b->nenv * ODK_SENSOR_NPRM, na = (size_t)b->nenv * ODK_ACT_NPRM, nspec = 3 * (size_t)ODK_FAULT_NSLOT;
+  if (sf < af + na && af < sf + ns)
+    return fail(ODK_ERR_INVALID, "%s: sensor_fault_dev overlaps act_fault_dev (every slot of a row is stored once)", fn);
+  if (sf < spec_dev + nspec && spec_dev < sf + ns)
+    return fail(ODK_ERR_INVALID, "%s: sensor_fault_dev overlaps spec_dev (the ranges are only read)", fn);
+  if (af < spec_dev + nspec && spec_dev < af + na)
+    return fail(ODK_ERR_INVALID, "%s: act_fault_dev overlaps spec_dev (the ranges are only read)", fn);
+  Launch g; if (int rc = launch_on(b, 16, &g)) return rc;
+  hipLaunchKernelGGL(fault_resample_kernel, g.grid, dim3(256), 0, (hipStream_t)stream, done_dev, spec_dev, (unsigned)seed,
+                     (unsigned)env_id_offset, state_dev, sensor_fault_dev, act_fault_dev, b->nenv);
+  HIPCHK(hipGetLastError());
+  return ODK_OK;
+}

@@ -208,6 +208,7 @@ def _signatures() -> Dict[str, tuple]:
         "odk_waypoint_command_apply": (I, [P, P, I, P, P, P, F, F, F, F, P]),
         "odk_sensor_apply": (I, [P, P, P, P, P, P, P]),
         "odk_action_apply": (I, [P, P, P, P, P, P, P]),
+        "odk_fault_resample": (I, [P, P, P, C.c_uint32, C.c_uint32, P, P, P, P]),
         "odk_physics_step": (I, [P, P, I, P]),
         "odk_batch_get_state": (I, [P, FP, FP, FP]),
         "odk_batch_set_state": (I, [P, FP, FP, FP]),
@@ -376,6 +377,14 @@ def action_fault_rows(n: int) -> np.ndarray:
     rows[:, ACT_GAIN] = rows[:, ACT_DROP_LEN] = 1.0
     rows[:, ACT_FREEZE_AT:ACT_FREEZE_AT + 16] = -1.0
     return rows
+
+
+# odk_fault_resample's rows (include/odk.h ODK_FAULT_*): the spec is [3, FAULT_NSLOT] (lo, hi, kind), slot s < SENSOR_NPRM the sensor row's
+# slot s, the others the actuation row's slot s - SENSOR_NPRM; a state row of FAULT_NSTATE floats: the calls and the redraws
+FAULT_NSLOT = SENSOR_NPRM + ACT_NPRM
+FAULT_NSTATE = 4
+FAULT_HEAD, FAULT_EPISODE = 0, 1
+FAULT_FIXED, FAULT_UNIFORM, FAULT_WHOLE = 0, 1, 2
 
 
 def sensor_rotation(roll_deg: float, pitch_deg: float, yaw_deg: float) -> np.ndarray:
@@ -1377,6 +1386,28 @@ class Batch:
         filter's state and the action last delivered, `done` ([nenv], or None) starts a new episode.  An all-nominal `fault` copies every
         bit.  `out` must not share memory with `act`."""
         self._apply_stage("action_apply", "act", "the policy's action", act, int(self.model.nu), done, fault, ACT_NPRM, state, ACT_NSTATE, out)
+
+    def fault_resample(self, done, spec, seed: int, env_id_offset: int, state, sensor_fault, act_fault):
+        """One `odk_fault_resample` launch, issued BEFORE `sensor_apply` and `action_apply` of the same step with the same `done`: every env
+        whose `state` row ([nenv, FAULT_NSTATE], zeroed before an episode's first call) has HEAD 0 or whose `done` ([nenv], or None) is set
+        gets its rows of `sensor_fault` ([nenv, SENSOR_NPRM]) and `act_fault` ([nenv, ACT_NPRM]) redrawn from `spec` ([3, FAULT_NSLOT]: lo,
+        hi, kind = FAULT_FIXED / FAULT_UNIFORM / FAULT_WHOLE per slot); the other envs' rows keep their bits.  The draws are a stateless
+        hash of (`seed`, `env_id_offset` + e, the env's redraw count, the slot): both are whole numbers below 2^32."""
+        import torch
+        fn = "fault_resample"
+        for what, t, n in (("state", state, FAULT_NSTATE), ("sensor_fault", sensor_fault, SENSOR_NPRM), ("act_fault", act_fault, ACT_NPRM)):
+            check_accumulator(f"{fn}: {what}", t, self.nenv, n, self.device)
+        _check_tensor(f"{fn}: spec", spec, "float32", self.device, f"(3, {FAULT_NSLOT})", lambda s: s == (3, FAULT_NSLOT))
+        if done is not None:
+            if not torch.is_tensor(done) or tuple(done.shape) != (self.nenv,):
+                raise OdkError(f"{fn}: done: expected a torch tensor of shape ({self.nenv},) or None, got "
+                               f"{tuple(done.shape) if hasattr(done, 'shape') else type(done).__name__}")
+            _check_placement(f"{fn}: done", done, torch.float32, self.device)
+        for name, v in (("seed", seed), ("env_id_offset", env_id_offset)):
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < 1 << 32:
+                raise OdkError(f"{fn}: {name} = {v!r} (a whole number, 0 .. 2^32 - 1)")
+        _chk(self.L.odk_fault_resample(self._b, _ptr(done), _ptr(spec), int(seed), int(env_id_offset), _ptr(state), _ptr(sensor_fault),
+                                       _ptr(act_fault), self._stream()))
 
     def physics_step(self, ctrl, n_substeps: int = 10):
         assert ctrl.is_cuda and ctrl.dtype == self.torch.float32 and ctrl.is_contiguous() and tuple(ctrl.shape) == (self.nenv, self.model.nu)

@@ -398,6 +398,8 @@ class Joystick:
     def unwrapped(self): return self
     @property
     def batch(self) -> "engine.Batch": return self._batch
+    @property
+    def env_id_offset(self) -> int: return self._env_id_offset      # env e is env env_id_offset + e of the run (a rank's first env)
 
     def make_eval_env(self, num_envs: int = 128):
         """Sibling env for the Evaluator (brax wraps `eval_env or environment` a second time with num_eval_envs)."""

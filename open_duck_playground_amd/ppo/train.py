@@ -185,30 +185,37 @@ def make_learner(net, data, cfg, world: int = 1, group=None, **learner_kw):
 class _RolloutBuffers:
     """Time-major history of one unroll of an engine-backed env ([T, N, ...] per field) and the per-step snapshot launches: the
     env's output tensors are persistent, so step t's five snapshots (reward / done / truncation of step t, the observations
-    step t + 1 starts from) are ONE launch with fixed addresses instead of five `clone`s."""
+    step t + 1 starts from) are ONE launch with fixed addresses instead of five `clone`s.  With a fault stage (`staged`: its `sensor_obs`) the
+    `obs` history is what the policy read: step t's launch snapshots the stage's output of step t, not the env's row."""
 
-    def __init__(self, state, T: int, A: int):
+    def __init__(self, state, T: int, A: int, staged=None):
         from .. import engine
         obs, priv = state.obs["state"], state.obs["privileged_state"]
         N, dev = obs.shape[0], obs.device
         E = lambda *s: torch.empty(*s, device=dev)
         self.T, self.src = T, (obs.data_ptr(), priv.data_ptr(), state.reward.data_ptr(), state.done.data_ptr(), state.info["truncation"].data_ptr())
+        self.staged = None if staged is None else staged.data_ptr()
         self.shape = (N, obs.shape[1], priv.shape[1], A)
         self.buf = dict(obs=E(T, N, obs.shape[1]), priv=E(T, N, priv.shape[1]), raw_action=E(T, N, A), log_prob=E(T, N), reward=E(T, N), done=E(T, N),
                         truncation=E(T, N))
         self.action = E(N, A)
         b = self.buf
-        self.first = engine.MultiCopy([(obs, b["obs"][0]), (priv, b["priv"][0])])
+        self.first = engine.MultiCopy(([(obs, b["obs"][0])] if staged is None else []) + [(priv, b["priv"][0])])
         self.after = []
         for t in range(T):
             pairs = [(state.reward, b["reward"][t]), (state.done, b["done"][t]), (state.info["truncation"], b["truncation"][t])]
+            if staged is not None:
+                pairs += [(staged, b["obs"][t])]      # (still step t's: the stage writes it again only in step t + 1's `observe`)
+            elif t + 1 < T:
+                pairs += [(obs, b["obs"][t + 1])]
             if t + 1 < T:
-                pairs += [(obs, b["obs"][t + 1]), (priv, b["priv"][t + 1])]
+                pairs += [(priv, b["priv"][t + 1])]
             self.after.append(engine.MultiCopy(pairs))
 
-    def matches(self, state, T: int, A: int) -> bool:
+    def matches(self, state, T: int, A: int, staged=None) -> bool:
         obs, priv = state.obs["state"], state.obs["privileged_state"]
         return (T == self.T and self.shape == (obs.shape[0], obs.shape[1], priv.shape[1], A)
+                and self.staged == (None if staged is None else staged.data_ptr())
                 and self.src == (obs.data_ptr(), priv.data_ptr(), state.reward.data_ptr(), state.done.data_ptr(), state.info["truncation"].data_ptr()))
 
 
@@ -218,15 +225,17 @@ _ROLLOUT_BUFFERS = weakref.WeakKeyDictionary()
 
 
 @torch.no_grad()
-def _rollout_engine(env, net: PPONetworks, state, unroll_length: int, gen: torch.Generator, deterministic: bool):
+def _rollout_engine(env, net: PPONetworks, state, unroll_length: int, gen: torch.Generator, deterministic: bool, faults=None):
     """`rollout` for an engine-backed env on the GPU: per step the policy's whole-network launch (when the architecture allows),
-    the sampling launch writing straight into the history, the fused env-step launch and one snapshot launch."""
+    the sampling launch writing straight into the history, the fused env-step launch and one snapshot launch.  With `faults` three more:
+    the stage's resample and sensor launches in front of the policy, its action launch between the sampling and the env step."""
     from .. import engine
     from .learner import fused_policy
     T, A = unroll_length, net.action_size
     rb = _ROLLOUT_BUFFERS.get(net)
-    if rb is None or not rb.matches(state, T, A):
-        rb = _ROLLOUT_BUFFERS[net] = _RolloutBuffers(state, T, A)
+    staged = None if faults is None else faults.sensor_obs
+    if rb is None or not rb.matches(state, T, A, staged):
+        rb = _ROLLOUT_BUFFERS[net] = _RolloutBuffers(state, T, A, staged)
     N = state.obs["state"].shape[0]
     fp = fused_policy(net, N)
     if fp is not None:
@@ -235,9 +244,10 @@ def _rollout_engine(env, net: PPONetworks, state, unroll_length: int, gen: torch
     b = rb.buf
     rb.first()
     for t in range(T):
-        logits = fp(state.obs["state"]) if fp is not None else net.policy(net.norm_obs(state.obs["state"]))
+        obs = state.obs["state"] if faults is None else faults.observe(state.obs["state"], state.done)
+        logits = fp(obs) if fp is not None else net.policy(net.norm_obs(obs))
         engine.policy_sample(logits, noise[t], out=(b["raw_action"][t], rb.action, b["log_prob"][t]))
-        state = env.step(state, rb.action)
+        state = env.step(state, rb.action if faults is None else faults.deliver(rb.action, state.done))
         rb.after[t]()
     data = {k: v.transpose(0, 1).contiguous() for k, v in b.items()}
     data["last_priv"] = state.obs["privileged_state"].clone()
@@ -245,20 +255,24 @@ def _rollout_engine(env, net: PPONetworks, state, unroll_length: int, gen: torch
 
 
 @torch.no_grad()
-def rollout(env, net: PPONetworks, state, unroll_length: int, gen: torch.Generator, deterministic: bool = False, engine_path: bool = True):
+def rollout(env, net: PPONetworks, state, unroll_length: int, gen: torch.Generator, deterministic: bool = False, engine_path: bool = True,
+            faults=None):
     """brax acting.generate_unroll: returns ([B, T, ...] transition tensors, final state).  `engine_path` false forces the
-    generic loop below for an engine-backed env too (tests compare the two)."""
+    generic loop below for an engine-backed env too (tests compare the two).  `faults` (a fault_training.FaultStage of this env, or None):
+    the policy reads the stage's observation -- `obs` holds that row -- and the env steps with the action the stage delivers; `raw_action`
+    and `log_prob` stay the policy's, `priv`, reward, done and truncation the env's."""
     if engine_path and state.obs["state"].is_cuda and hasattr(env, "batch") and "truncation" in state.info:
-        return _rollout_engine(env, net, state, unroll_length, gen, deterministic)
+        return _rollout_engine(env, net, state, unroll_length, gen, deterministic, faults)
     keys = ("obs", "priv", "raw_action", "log_prob", "reward", "done", "truncation")
     buf = {k: [] for k in keys}
     for _ in range(unroll_length):
-        obs, priv = state.obs["state"].clone(), state.obs["privileged_state"].clone()
+        obs = (state.obs["state"] if faults is None else faults.observe(state.obs["state"], state.done)).clone()
+        priv = state.obs["privileged_state"].clone()
         loc, scale = net.dist_params(obs)
         raw = loc if deterministic else loc + scale * torch.randn(loc.shape, generator=gen, device=loc.device)
         logp = tanh_normal_log_prob(loc, scale, raw)
         action = torch.tanh(raw).contiguous()
-        state = env.step(state, action)
+        state = env.step(state, action if faults is None else faults.deliver(action, state.done))
         buf["obs"].append(obs); buf["priv"].append(priv); buf["raw_action"].append(raw); buf["log_prob"].append(logp)
         buf["reward"].append(state.reward.clone()); buf["done"].append(state.done.clone()); buf["truncation"].append(state.info["truncation"].clone())
     data = {k: torch.stack(v, 1) for k, v in buf.items()}
@@ -268,8 +282,10 @@ def rollout(env, net: PPONetworks, state, unroll_length: int, gen: torch.Generat
 
 def train(environment, num_timesteps: int, progress_fn: Optional[Callable] = None, policy_params_fn: Optional[Callable] = None,
           restore_checkpoint_path: Optional[str] = None, seed: int = 0, randomization_fn: Optional[Callable] = None,
-          log_path: Optional[str] = None, eval_env=None, **overrides):
-    """Trains on `environment` (a batched Joystick / Standing).  Returns (networks, metrics).
+          log_path: Optional[str] = None, eval_env=None, faults=None, **overrides):
+    """Trains on `environment` (a batched Joystick / Standing).  Returns (networks, metrics).  `faults` (a fault_training.FaultStage of
+    `environment`, or None): every rollout runs through the stage, whose state is zeroed after every reset of the env; the Evaluator stays
+    the nominal robot, so `eval/episode_reward` compares across runs.
 
     Epoch structure of brax ppo.train: `num_evals - 1` epochs of `ceil(num_timesteps / (epochs * env_steps_per_iter *
     num_resets_per_eval))` training steps, the env re-reset `num_resets_per_eval` times per epoch, one evaluation
@@ -329,6 +345,8 @@ def train(environment, num_timesteps: int, progress_fn: Optional[Callable] = Non
     if cfg["num_evals"] > 1 and evaluator is not None:
         metrics = report({})
     state = environment.reset(seed)
+    if faults is not None:
+        faults.reset()
     reset_count = 0
     meter = LossMeter()
     grp = dist.group.WORLD if world > 1 else None
@@ -336,7 +354,7 @@ def train(environment, num_timesteps: int, progress_fn: Optional[Callable] = Non
         t_epoch = time.time()
         for _ in range(resets):
             for _ in range(iters_per_epoch):
-                data, state = rollout(environment, net, state, cfg["unroll_length"], gen)
+                data, state = rollout(environment, net, state, cfg["unroll_length"], gen, faults=faults)
                 if cfg["normalize_observations"]:
                     net.norm_obs.update(data["obs"], grp); net.norm_priv.update(data["priv"], grp)
                 if learner is None and done_steps == 0:
@@ -346,6 +364,8 @@ def train(environment, num_timesteps: int, progress_fn: Optional[Callable] = Non
             if cfg["num_resets_per_eval"] > 0:
                 reset_count += 1
                 state = environment.reset(seed + 7919 * reset_count)
+                if faults is not None:
+                    faults.reset()
         loss_metrics = learner.metrics() if learner is not None else meter.mean(world, grp)
         if world > 1:
             assert_replicas_identical(net, grp)
@@ -396,7 +416,13 @@ def assert_replicas_identical(net: PPONetworks, group=None):
         raise RuntimeError(f"data-parallel replicas diverged: {bad} of {bits.numel()} parameter / normaliser words differ across ranks")
 
 
-def save_checkpoint(path: str, net: PPONetworks):
-    """(normalizer, policy, value) triple like the reference's orbax checkpoint (common/runner.py:68-76)."""
+def save_checkpoint(path: str, net: PPONetworks, fault_spec: Optional[Dict] = None):
+    """(normalizer, policy, value) triple like the reference's orbax checkpoint (common/runner.py:68-76).  `fault_spec`: the faults the
+    networks were trained under (fault_training.FaultStage.describe), stored beside them; a checkpoint trained without has no such key."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    torch.save({"networks": net.state_dict()}, path)
+    torch.save({"networks": net.state_dict(), **({} if fault_spec is None else {"fault_spec": fault_spec})}, path)
+
+
+def checkpoint_fault_spec(path: str) -> Optional[Dict]:
+    """The `fault_spec` a checkpoint was saved with, None for one trained without faults (and for every older file)."""
+    return torch.load(path, map_location="cpu").get("fault_spec")

@@ -147,6 +147,13 @@ class OpenDuckMiniV2Runner:
             print(self.env.reference_motion.describe())
         if hasattr(self.env, "describe_head_joints"):
             print(self.env.describe_head_joints())
+        # training under faults redrawn per episode (fault_training.py): a stage of the training env only -- the Evaluator stays the nominal robot
+        from . import fault_training
+        self.fault_spec = fault_training.spec_from_args(args)      # None without --train_sensor / --train_actuation: no stage at all
+        self.faults = None if self.fault_spec is None else fault_training.FaultStage(self.env, self.fault_spec, seed=args.seed)
+        if self.faults is not None:
+            import json
+            print(f"Training under faults: {json.dumps(self.faults.describe())}")
         self.action_size = self.env.action_size
         self.obs_size = int(self.env.observation_size["state"][0])
         # one generator per (seed, rank, stream): stream 0 = training envs, 1 = evaluation envs (ppo/train.py)
@@ -167,7 +174,7 @@ class OpenDuckMiniV2Runner:
         d = datetime.now().strftime("%Y_%m_%d_%H%M%S")
         path = f"{self.output_dir}/{d}_{current_step}.pt"
         print(f"Saving checkpoint (step: {current_step}): {path}")
-        self.ppo.save_checkpoint(path, net)
+        self.ppo.save_checkpoint(path, net, fault_spec=None if self.faults is None else self.faults.describe())
         from .export_onnx import export_onnx   # reference common/runner.py:77-84
         export_onnx(net, output_path=f"{self.output_dir}/{d}_{current_step}.onnx")
 
@@ -181,7 +188,7 @@ class OpenDuckMiniV2Runner:
             return self.ppo.train(self.env, num_timesteps=self.args.num_timesteps, progress_fn=self.progress_callback,
                                   policy_params_fn=self.policy_params_fn, restore_checkpoint_path=self.args.restore_checkpoint_path,
                                   seed=self.args.seed, randomization_fn=self.randomizer, log_path=os.path.join(self.output_dir, "metrics.jsonl"),
-                                  num_envs=self.args.num_envs)
+                                  faults=self.faults, num_envs=self.args.num_envs)
         finally:
             if self.writer is not None:
                 self.writer.close()
@@ -218,6 +225,16 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--reward_param", action="append", default=[], metavar="KEY=VALUE",
                         help="repeatable: a parameter of the library terms: base_height_target, max_foot_height, air_time_range=MIN,MAX, "
                              "pose_weights=W1,...,Wnu, soft_joint_pos_limit_factor")
+    parser.add_argument("--train_sensor", action="append", default=[], metavar="KEY=V|KEY=LO:HI[,...]",
+                        help="repeatable: train under a sensor fault between the env's observation and the policy, with track --sensor's keys "
+                             "and units.  KEY=V is fixed; KEY=LO:HI is redrawn per env at the start of every episode, uniformly (imu_delay / "
+                             "joint_delay: the whole steps LO .. HI).  encoder_offset=X redraws every actuator's zero error in +-X; the IMU "
+                             "mounting angles and the contact modes take one value.  e.g. imu_delay=0:3,acc_bias_x=1.3")
+    parser.add_argument("--train_actuation", action="append", default=[], metavar="KEY=V|KEY=LO:HI[,...]",
+                        help="repeatable: train under a fault between the policy's action and the servos, with track --actuation's keys and "
+                             "units, fixed or redrawn per episode as --train_sensor's.  cutoff=A:B draws the filter coefficient uniformly "
+                             "between the two cutoffs' (a range that holds 0 = off is refused); offset=X redraws every actuator's horn error "
+                             "in +-X; freeze and freeze_at take one value.  e.g. cutoff=15:40,drop=0:0.05")
     add_imitation_flags(parser)
     add_head_joint_flag(parser)
     return parser
@@ -227,6 +244,9 @@ def check_env_flags(parser, args) -> None:
     """Refuses a flag of another --env right after parsing, before any GPU or process-group set-up (argparse error, exit status 2)."""
     try:
         head_joint_overrides(args)
+        if getattr(args, "train_sensor", None) or getattr(args, "train_actuation", None):
+            from . import fault_training
+            fault_training.spec_from_args(args)
     except ValueError as e:
         parser.error(str(e))
 

@@ -1418,9 +1418,16 @@ def load_networks(path: Optional[str], env, device):
     nf = ppo_config()["network_factory"]
     net = PPONetworks(env.observation_size["state"][0], env.observation_size["privileged_state"][0], env.action_size,
                       nf["policy_hidden_layer_sizes"], nf["value_hidden_layer_sizes"]).to(device)
-    net.load_state_dict(torch.load(path, map_location=device)["networks"])      # ppo/train.py save_checkpoint
+    net.load_state_dict(torch.load(path, map_location=device)["networks"])      # ppo/train.py save_checkpoint (a `fault_spec` beside it is not read here)
     net.eval()
     return net
+
+
+def trained_under(path: Optional[str]):
+    """The faults a checkpoint was trained under (runner --train_sensor / --train_actuation: ppo/train.py save_checkpoint's `fault_spec`),
+    None for one trained on the nominal robot and for every file from before the key."""
+    from .ppo.train import checkpoint_fault_spec
+    return checkpoint_fault_spec(path)
 
 
 @dataclasses.dataclass
@@ -1898,7 +1905,7 @@ def run(args, out=sys.stdout) -> Dict:
     if falls and falls["save"]:      # the clips of every row, or with a cell axis of every cell
         save_falls(falls["save"], fall_clips(accs[[r.key for r in reports].index("falls")], block_commands(rows, axis), E, falls["ring"],
                                              int(env.batch.model.nq), falls["save_max"]), float(env.dt))
-    settings = dict(checkpoint=args.checkpoint, env=args.env, task=args.task, xml=args.xml, cone=args.cone,
+    settings = dict(checkpoint=args.checkpoint, trained_under=trained_under(args.checkpoint), env=args.env, task=args.task, xml=args.xml, cone=args.cone,
                     hfield_up_normals_only=bool(args.hfield_up_normals_only), envs_per_command=E, episode_length=T, seed=int(args.seed),
                     num_envs=n, dt=float(env.dt), policy="deterministic tanh(loc)", fused_policy=tr.fp is not None, graph=tr.graph is not None,
                     reference_motion=getattr(args, "reference_motion", None), reference_motion_sha256=motion.sha256 if motion is not None else None)

@@ -1,5 +1,7 @@
 """Full-PPO throughput (BASELINE.json configs[2]): flat_terrain_backlash + domain randomisation, 8192 envs,
-Appendix-G hyper-parameters; reports env-steps/s including the learner, and the rollout/learner split."""
+Appendix-G hyper-parameters; reports env-steps/s including the learner, and the rollout/learner split.
+    python tools/gpu_train_bench.py [task] [iters] [--train_sensor SPEC] [--train_actuation SPEC]
+With one of the two flags (runner's) the rollout runs through a fault_training.FaultStage: three more launches per step."""
 import os, sys, time, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -8,9 +10,20 @@ from open_duck_playground_amd import joystick
 from open_duck_playground_amd.ppo import train as T
 from open_duck_playground_amd.ppo.networks import PPONetworks
 
-task = sys.argv[1] if len(sys.argv) > 1 else "flat_terrain_backlash"
-iters = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+import argparse
+ap = argparse.ArgumentParser()
+ap.add_argument("task", nargs="?", default="flat_terrain_backlash")
+ap.add_argument("iters", nargs="?", type=int, default=5)
+ap.add_argument("--train_sensor", action="append", default=[])
+ap.add_argument("--train_actuation", action="append", default=[])
+args = ap.parse_args()
+task, iters = args.task, args.iters
+flags = {k: v for k, v in (("train_sensor", args.train_sensor), ("train_actuation", args.train_actuation)) if v}
 env = joystick.Joystick(task=task, num_envs=8192)
+faults = None
+if flags:
+    from open_duck_playground_amd import fault_training
+    faults = fault_training.FaultStage(env, fault_training.spec_from_args(args), seed=0)
 env.randomize(np.random.default_rng(0))
 cfg = T.ppo_config()
 dev = env.batch.obs.device
@@ -20,11 +33,13 @@ opt = torch.optim.Adam(net.parameters(), lr=cfg["learning_rate"], capturable=Tru
 learner = None
 gen = torch.Generator(device=dev); gen.manual_seed(0)
 state = env.reset(0)
+if faults is not None:
+    faults.reset()
 tr = tl = 0.0
 WARM = 2   # untimed: learner construction, library handles, selection file
 for it in range(iters + WARM):
     torch.cuda.synchronize(); t0 = time.perf_counter()
-    data, state = T.rollout(env, net, state, cfg["unroll_length"], gen)
+    data, state = T.rollout(env, net, state, cfg["unroll_length"], gen, faults=faults)
     torch.cuda.synchronize(); t1 = time.perf_counter()
     net.norm_obs.update(data["obs"]); net.norm_priv.update(data["priv"])
     if it == 0:
@@ -34,6 +49,6 @@ for it in range(iters + WARM):
     if it >= WARM:
         tr += t1 - t0; tl += t2 - t1
 steps = iters * 8192 * cfg["unroll_length"]
-print(json.dumps({"task": task, "iters": iters, "env_steps_per_s_total": steps / (tr + tl), "rollout_env_steps_per_s": steps / tr,
+print(json.dumps({"task": task, "iters": iters, "faults": None if faults is None else flags, "rollout_ms_per_step": 1e3 * tr / (iters * cfg["unroll_length"]), "env_steps_per_s_total": steps / (tr + tl), "rollout_env_steps_per_s": steps / tr,
                   "rollout_s_per_iter": tr / iters, "learner_s_per_iter": tl / iters, "last_loss": float(m["total_loss"]),
                   "reward_per_step": float(data["reward"].mean())}))
