@@ -763,6 +763,80 @@ int odk_fault_resample(const odk_batch* b, const float* done_dev /* may be NULL 
                        float* state_dev /* [nenv, ODK_FAULT_NSTATE] */, float* sensor_fault_dev /* [nenv, ODK_SENSOR_NPRM] */,
                        float* act_fault_dev /* [nenv, ODK_ACT_NPRM] */, void* stream);
 
+/* Command curriculum: training on commands drawn from a grid over (lin_vel_x, lin_vel_y, ang_vel_yaw) whose bins open as the policy learns
+ * to track inside their neighbours.  Two launches: odk_curriculum_step after every odk_step of a rollout (judges the stint that ends, draws
+ * the next command into the BOUND command buffer), odk_curriculum_update once per training iteration (promotes bins, rebuilds the cdf).
+ * Not reports: they sit next to the fault stages.  The step, reset and physics kernels are not involved.
+ *
+ * The grid: axis a (0 vx, 1 vy, 2 wz) has n[a] equal bins between lo[a] and hi[a], 1 <= n[a] <= ODK_CURR_MAX_AXIS, and
+ * nbins = n[0] n[1] n[2] <= ODK_CURR_MAX_BINS; bin (ix, iy, iz) has index (ix n[1] + iy) n[2] + iz.  width[a] = (hi[a] - lo[a]) / n[a] is
+ * computed by the caller (the device does not divide floats).
+ *
+ * Device arrays (the caller's; int32 so that neither the order of the atomics nor that of the scan can change a bit):
+ *   levels  int32 [nbins]      0 .. ODK_CURR_LMAX; a bin is drawn in proportion to its level
+ *   cdf     int32 [nbins]      inclusive prefix sums of levels
+ *   counts  int32 [nbins][2]   tries and successes since the bin was last judged
+ *   stats   int32 [4]          ODK_CURR_STAT_*: updates, bins judged, bins promoted, tries judged (running totals)
+ *   state   float [nenv, ODK_CURR_NSTATE]  per env (whole numbers are exact to 2^24): HEAD calls since the row was zeroed, EPISODE, STINT the
+ *           draws of this episode, STEP the steps of the stint, BIN the drawn bin (-1: the zero command), SAMPLES, SQLIN, SQYAW
+ *   the command buffer  float [nenv, 7]  the one bound with odk_batch_bind_commands, row stride 7
+ *
+ * odk_curriculum_step, env e (one thread per env, no LDS, no scratch, graph-capturable; every load of env e's state row, command row and
+ * velocities comes before its first store; float32 + - * with every product rounded before it is added):
+ *   first = HEAD == 0: draw only.  Otherwise, with d = done_dev[e] (0 when done_dev is NULL) and tr = truncation_dev[e] (likewise):
+ *   1. a velocity sample when d == 0 and STEP >= skip (a done step's observation is the next episode's): SAMPLES += 1,
+ *      SQLIN += (vx - cx)^2 + (vy - cy)^2, SQYAW += (wz - cwz)^2, with (vx, vy) = priv[nobs + 9 .. 10] (the local linear velocity),
+ *      wz = priv[nobs + 2] (the gyro) of the noise-free privileged tail and c env e's row of the command buffer: odk_tracking_accumulate's;
+ *   2. STEP += 1; the stint ends when d != 0 or STEP == period;
+ *   3. an ending stint with BIN >= 0 is judged: a fall (d != 0 and tr == 0) is a try and no success; otherwise, with SAMPLES >= min_samples,
+ *      a try, and a success when SQLIN <= (tol_lin tol_lin) SAMPLES and SQYAW <= (tol_yaw tol_yaw) SAMPLES; otherwise it is not counted.
+ *      A try is atomicAdd(counts[BIN][0], 1), a success atomicAdd(counts[BIN][1], 1);
+ *   4. a draw on a stint end and on the first call: EPISODE += 1 and STINT = 0 on the first call or d != 0; with
+ *      u_k = odk_action_apply's stateless draw of (seed, env_id_offset + e, EPISODE, STINT, stream 128 + k), total = cdf[nbins - 1]:
+ *        k = 0     the zero command when u < p_zero or total == 0: all seven entries 0, BIN = -1;
+ *        k = 1     t = min((int)(u (float)total), total - 1); BIN = the first bin with cdf[bin] > t (binary search);
+ *        k = 2..4  entry a = fminf(lo[a] + width[a] ((float)i_a + u), hi[a]);
+ *        k = 5..8  entry 3 + j = head_lo[j] + (head_hi[j] - head_lo[j]) u  (the batch config's cmd_range rows 3..6);
+ *      then STINT += 1, STEP = SAMPLES = SQLIN = SQYAW = 0;
+ *   5. HEAD += 1.  A drawn row is stored into the command buffer and into floats 6..12 of env e's row of obs_dev and of priv_patch_dev
+ *      (each may be NULL: not patched) -- what a bound step shows in those slots.  BUILD-DEFINED: the reference's mid-episode resample shows
+ *      the old command for one more step; here the policy's first action of a stint sees the command the next step's reward is judged by.
+ * Refused (ODK_ERR_INVALID, nothing launched): a null batch, curriculum, priv_dev, cdf_dev, counts_dev, state_dev or cmd_dev (by name);
+ * truncation_dev NULL while done_dev is not; a cmd_dev that is not the bound buffer (or a bound stride other than 7); n[a] or nbins out of
+ * range; period < 1, min_samples < 0 or skip < 0; any two of counts, state, cmd, obs, priv_patch overlapping, or one of them overlapping cdf.
+ *
+ * odk_curriculum_update (one workgroup of one wave; lane l walks bins l, 64 + l, ...): a bin is JUDGED when its tries >= min_tries and
+ * PROMOTED when also (float)successes >= promote_rate (float)tries.  level' = min(ODK_CURR_LMAX, level + P), P the number of promoted bins
+ * among the bin itself and its up to six neighbours one step along an axis (no wrap): gathered, not scattered.  Every new level is parked
+ * in cdf before any counter is zeroed or any level stored; then a judged bin's two counters go back to 0 (the others keep theirs), levels
+ * takes the new levels, cdf their inclusive prefix sums (a lane scan, no LDS), and stats advances by 1, the judged bins, the promoted bins
+ * and the judged bins' tries.  Refused: null pointers (by name), the grid out of range, min_tries < 1, two of the four arrays overlapping. */
+#define ODK_CURR_LMAX 5
+#define ODK_CURR_MAX_AXIS 16
+#define ODK_CURR_MAX_BINS 4096
+#define ODK_CURR_NSTATE 8
+enum { ODK_CURR_HEAD = 0, ODK_CURR_EPISODE = 1, ODK_CURR_STINT = 2, ODK_CURR_STEP = 3, ODK_CURR_BIN = 4, ODK_CURR_SAMPLES = 5,
+       ODK_CURR_SQLIN = 6, ODK_CURR_SQYAW = 7 };
+enum { ODK_CURR_STAT_UPDATES = 0, ODK_CURR_STAT_JUDGED = 1, ODK_CURR_STAT_PROMOTED = 2, ODK_CURR_STAT_TRIES = 3 };
+typedef struct {
+  float lo[3], hi[3];               /* the grid's ends per axis: vx, vy, wz */
+  int32_t n[3];                     /* bins per axis, 1 .. ODK_CURR_MAX_AXIS */
+  float width[3];                   /* (hi - lo) / n, computed by the caller */
+  float head_lo[4], head_hi[4];     /* cmd_range rows 3..6 */
+  float p_zero;                     /* share of all-zero commands */
+  int32_t period, skip, min_samples;/* steps per stint; steps of a stint before the first sample; samples a judged stint needs */
+  float tol_lin, tol_yaw;           /* RMS tolerances of a success: m/s (planar), rad/s */
+  int32_t min_tries;                /* tries that make a bin judged */
+  float promote_rate;               /* success share that promotes */
+  uint32_t seed, env_id_offset;
+} odk_curriculum;
+int odk_curriculum_step(const odk_batch* b, const odk_curriculum* c, const float* priv_dev /* [nenv, npriv], read */,
+                        const float* done_dev /* may be NULL */, const float* truncation_dev /* may be NULL with done_dev */,
+                        const int32_t* cdf_dev, int32_t* counts_dev, float* state_dev, float* cmd_dev /* the bound buffer */,
+                        float* obs_dev /* [nenv, nobs] or NULL */, float* priv_patch_dev /* [nenv, npriv] or NULL */, void* stream);
+int odk_curriculum_update(const odk_batch* b, const odk_curriculum* c, int32_t* levels_dev, int32_t* cdf_dev, int32_t* counts_dev,
+                          int32_t* stats_dev, void* stream);
+
 /* mjx_env.step alone (physics only, n_substeps, ctrl = ctrl_dev [nenv, nu]); for parity tests */
 int odk_physics_step(odk_batch* b, const float* ctrl_dev, int n_substeps, void* stream);
 

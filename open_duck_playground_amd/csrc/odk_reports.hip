@@ -1,5 +1,5 @@
 // odk_reports.hip -- the evaluation reports of include/odk.h (libodk.so): the accumulator kernels of the tracking / push / gait / posture /
-// imitation / response / fall / path reports, the command-schedule kernel, the waypoint follower and the sensor-fault and actuation-fault stages, with their C entry points.  They read
+// imitation / response / fall / path reports, the command-schedule kernel, the waypoint follower, the sensor-fault and actuation-fault stages, the fault resampling and the two command-curriculum kernels, with their C entry points.  They read
 // finished observation rows (odk_obs_layout.h) and the batch (odk_batch.h: read-only here; its state is odk_engine.hip's); no compiled shape.
 // gfx950 only, no CPU fallback.
 #include <hip/hip_runtime.h>
@@ -1044,6 +1044,216 @@ extern "C" int odk_fault_resample(const odk_batch* b, const float* done_dev, con
   Launch g; if (int rc = launch_on(b, 16, &g)) return rc;
   hipLaunchKernelGGL(fault_resample_kernel, g.grid, dim3(256), 0, (hipStream_t)stream, done_dev, spec_dev, (unsigned)seed,
                      (unsigned)env_id_offset, state_dev, sensor_fault_dev, act_fault_dev, b->nenv);
+  HIPCHK(hipGetLastError());
+  return ODK_OK;
+}
+
+// ---- command curriculum (include/odk.h "Command curriculum": the definitions these two kernels restate).  Not reports: the step kernel sits
+// behind odk_step in a training rollout, the update kernel runs once per training iteration.
+// curriculum_step_kernel: one thread per env, a row past nenv leaves at once.  Everything env e reads -- its state row, its command row, the
+// three velocities, done and truncation -- is loaded before its first store, and the patched columns (6 .. 12) are none of the columns
+// read, so priv may be the row that is patched.  The only traffic between envs is two integer atomics per judged stint: their order cannot
+// change a bit.  No LDS, no scratch (the grid is kernel-argument scalars, every index into it a compile-time constant); the draws are
+// act_uniform's streams 128 .. 136; contraction is off, so a numpy restatement has the bits.
+__global__ void __launch_bounds__(256) curriculum_step_kernel(const odk_curriculum c, int nbins, const float* priv, int npriv, int nobs,
+                                                              const float* __restrict__ done, const float* __restrict__ trunc,
+                                                              const int* __restrict__ cdf, int* __restrict__ counts, float* __restrict__ state,
+                                                              float* __restrict__ cmd, float* __restrict__ obs, float* priv_patch, int nenv) {
+#pragma clang fp contract(off)
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= nenv) return;
+  float* S = state + (size_t)e * ODK_CURR_NSTATE;
+  float* C = cmd + (size_t)e * 7;
+  const float* P = priv + (size_t)e * npriv + nobs;
+  const float head0 = S[ODK_CURR_HEAD], ep0 = S[ODK_CURR_EPISODE], stint0 = S[ODK_CURR_STINT], step0 = S[ODK_CURR_STEP], bin0 = S[ODK_CURR_BIN];
+  const float samp0 = S[ODK_CURR_SAMPLES], sql0 = S[ODK_CURR_SQLIN], sqy0 = S[ODK_CURR_SQYAW];
+  const float d = done ? done[e] : 0.0f, tr = trunc ? trunc[e] : 0.0f;
+  const float ex = P[priv_at::LOCAL_LINVEL] - C[0], ey = P[priv_at::LOCAL_LINVEL + 1] - C[1], ez = P[priv_at::GYRO + 2] - C[2];
+  const bool first = head0 == 0.0f, ended = !first && d != 0.0f;
+  // 1. the sample, 2. the step count
+  const bool sample = !first && d == 0.0f && step0 >= (float)c.skip;
+  const float samp = sample ? samp0 + 1.0f : samp0;
+  const float sql = sample ? sql0 + (ex * ex + ey * ey) : sql0, sqy = sample ? sqy0 + ez * ez : sqy0;
+  const float step = first ? step0 : step0 + 1.0f;
+  const bool end = ended || (!first && step == (float)c.period);
+  // 3. the judgement
+  if (end && bin0 >= 0.0f) {
+    const bool fall = ended && tr == 0.0f;
+    const bool counted = fall || samp >= (float)c.min_samples;
+    const bool success = !fall && counted && sql <= (c.tol_lin * c.tol_lin) * samp && sqy <= (c.tol_yaw * c.tol_yaw) * samp;
+    int* K = counts + 2 * (int)bin0;
+    if (counted) atomicAdd(K, 1);
+    if (success) atomicAdd(K + 1, 1);
+  }
+  const bool draw = first || end, fresh = first || ended;
+  const float episode = fresh ? ep0 + 1.0f : ep0, stint = fresh ? 0.0f : stint0;
+  S[ODK_CURR_HEAD] = head0 + 1.0f;
+  if (!draw) {
+    S[ODK_CURR_STEP] = step; S[ODK_CURR_SAMPLES] = samp; S[ODK_CURR_SQLIN] = sql; S[ODK_CURR_SQYAW] = sqy;
+    return;
+  }
+  // 4. the draw
+  const unsigned ue = c.env_id_offset + (unsigned)e, uep = (unsigned)episode, ust = (unsigned)stint;
+  const int total = cdf[nbins - 1];
+  float row[7];
+  float bin = -1.0f;
+  const bool zero = act_uniform(c.seed, ue, uep, ust, 128u) < c.p_zero || total <= 0;
+#pragma unroll
+  for (int k = 0; k < 7; k++) row[k] = 0.0f;
+  if (!zero) {
+    const int t = min((int)(act_uniform(c.seed, ue, uep, ust, 129u) * (float)total), total - 1);
+    int lo = 0, hi = nbins - 1;
+    while (lo < hi) {   // the first bin with cdf[bin] > t; cdf[nbins - 1] = total > t, so there is one
+      const int mid = (lo + hi) >> 1;
+      if (cdf[mid] > t) hi = mid; else lo = mid + 1;
+    }
+    bin = (float)lo;
+    const int i[3] = {lo / (c.n[1] * c.n[2]), (lo / c.n[2]) % c.n[1], lo % c.n[2]};
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+      row[a] = fminf(c.lo[a] + c.width[a] * ((float)i[a] + act_uniform(c.seed, ue, uep, ust, 130u + (unsigned)a)), c.hi[a]);
+#pragma unroll
+    for (int j = 0; j < 4; j++) row[3 + j] = c.head_lo[j] + (c.head_hi[j] - c.head_lo[j]) * act_uniform(c.seed, ue, uep, ust, 133u + (unsigned)j);
+  }
+  S[ODK_CURR_EPISODE] = episode; S[ODK_CURR_STINT] = stint + 1.0f; S[ODK_CURR_STEP] = 0.0f; S[ODK_CURR_BIN] = bin;
+  S[ODK_CURR_SAMPLES] = 0.0f; S[ODK_CURR_SQLIN] = 0.0f; S[ODK_CURR_SQYAW] = 0.0f;
+  float* O = obs ? obs + (size_t)e * nobs + obs_at::COMMAND : nullptr;
+  float* Q = priv_patch ? priv_patch + (size_t)e * npriv + obs_at::COMMAND : nullptr;
+#pragma unroll
+  for (int k = 0; k < 7; k++) {
+    C[k] = row[k];
+    if (O) O[k] = row[k];
+    if (Q) Q[k] = row[k];
+  }
+}
+
+static int curriculum_grid(const char* fn, const odk_curriculum* c, int* nbins) {
+  long long n = 1;
+  for (int a = 0; a < 3; a++) {
+    if (c->n[a] < 1 || c->n[a] > ODK_CURR_MAX_AXIS)
+      return fail(ODK_ERR_INVALID, "%s: n[%d] = %d (1 .. %d bins per axis)", fn, a, (int)c->n[a], ODK_CURR_MAX_AXIS);
+    n *= c->n[a];
+  }
+  if (n > ODK_CURR_MAX_BINS) return fail(ODK_ERR_INVALID, "%s: nbins = %lld (at most %d)", fn, n, ODK_CURR_MAX_BINS);
+  *nbins = (int)n;
+  return ODK_OK;
+}
+// the first pair of byte ranges that overlap, by name (a null range takes no part)
+struct Span { const char* name; const void* p; size_t bytes; };
+static int spans_apart(const char* fn, const Span* s, int n) {
+  for (int i = 0; i < n; i++)
+    for (int j = i + 1; j < n; j++) {
+      if (!s[i].p || !s[j].p) continue;
+      const char *a = (const char*)s[i].p, *b = (const char*)s[j].p;
+      if (a < b + s[j].bytes && b < a + s[i].bytes) return fail(ODK_ERR_INVALID, "%s: %s overlaps %s", fn, s[i].name, s[j].name);
+    }
+  return ODK_OK;
+}
+
+extern "C" int odk_curriculum_step(const odk_batch* b, const odk_curriculum* c, const float* priv_dev, const float* done_dev,
+                                   const float* truncation_dev, const int32_t* cdf_dev, int32_t* counts_dev, float* state_dev, float* cmd_dev,
+                                   float* obs_dev, float* priv_patch_dev, void* stream) {
+  const char* fn = "odk_curriculum_step";
+  const void* const p[7] = {b, c, priv_dev, cdf_dev, counts_dev, state_dev, cmd_dev};
+  static const char* const name[7] = {"batch", "curriculum", "priv_dev", "cdf_dev", "counts_dev", "state_dev", "cmd_dev"};
+  for (int i = 0; i < 7; i++) if (!p[i]) return fail(ODK_ERR_INVALID, "%s: null %s", fn, name[i]);
+  if (done_dev && !truncation_dev) return fail(ODK_ERR_INVALID, "%s: null truncation_dev (with a done_dev: a fall is a done step that is no truncation)", fn);
+  if (cmd_dev != b->d_cmd || b->cmd_stride != 7)
+    return fail(ODK_ERR_INVALID, "%s: cmd_dev is not the command buffer bound to the batch with row stride 7 (odk_batch_bind_commands)", fn);
+  int nbins;
+  if (int rc = curriculum_grid(fn, c, &nbins)) return rc;
+  if (c->period < 1) return fail(ODK_ERR_INVALID, "%s: period = %d (at least 1 step)", fn, (int)c->period);
+  if (c->skip < 0) return fail(ODK_ERR_INVALID, "%s: skip = %d (0 or more steps)", fn, (int)c->skip);
+  if (c->min_samples < 0) return fail(ODK_ERR_INVALID, "%s: min_samples = %d (0 or more)", fn, (int)c->min_samples);
+  Launch g; if (int rc = launch_on(b, 1, &g)) return rc;
+  const size_t n = (size_t)b->nenv;
+  // (a priv_dev that is also patched is the same rows: the columns read are none of the columns stored; any other takes part as a range of its own)
+  const Span s[7] = {{"counts_dev", counts_dev, 8 * (size_t)nbins}, {"state_dev", state_dev, 4 * n * ODK_CURR_NSTATE}, {"cmd_dev", cmd_dev, 4 * n * 7},
+                     {"obs_dev", obs_dev, 4 * n * g.nobs}, {"priv_patch_dev", priv_patch_dev, 4 * n * g.npriv}, {"cdf_dev", cdf_dev, 4 * (size_t)nbins},
+                     {"priv_dev", priv_patch_dev == priv_dev ? nullptr : priv_dev, 4 * n * g.npriv}};
+  if (int rc = spans_apart(fn, s, 7)) return rc;
+  hipLaunchKernelGGL(curriculum_step_kernel, g.grid, dim3(256), 0, (hipStream_t)stream, *c, nbins, priv_dev, g.npriv, g.nobs, done_dev,
+                     truncation_dev, (const int*)cdf_dev, (int*)counts_dev, state_dev, cmd_dev, obs_dev, priv_patch_dev, b->nenv);
+  HIPCHK(hipGetLastError());
+  return ODK_OK;
+}
+
+// curriculum_update_kernel: one wave.  Lane l walks bins l, 64 + l, ...  Pass 1 only reads counts and levels and parks every bin's new level in
+// cdf, which nothing reads before pass 2; the barrier between the passes puts every lane's reads of its neighbours' counters in front of the
+// first store that zeroes one or rewrites a level.  Pass 2 reads back its own stores only.  The prefix sums are a __shfl_up scan per 64 bins
+// with a running carry: no LDS.  All integers.
+__device__ __forceinline__ bool curriculum_promoted(const int* __restrict__ counts, int bin, int min_tries, float rate) {
+#pragma clang fp contract(off)
+  const int tries = counts[2 * bin], wins = counts[2 * bin + 1];
+  return tries >= min_tries && (float)wins >= rate * (float)tries;
+}
+__global__ void __launch_bounds__(64) curriculum_update_kernel(const odk_curriculum c, int nbins, int* levels, int* cdf, int* counts, int* stats) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x;
+  const int n1 = c.n[1], n2 = c.n[2], n0 = c.n[0];
+  const int chunks = (nbins + 63) >> 6;
+  int judged = 0, promoted = 0, tries_judged = 0;
+  for (int k = 0; k < chunks; k++) {
+    const int bin = k * 64 + lane;
+    if (bin >= nbins) continue;
+    const int iz = bin % n2, iy = (bin / n2) % n1, ix = bin / (n1 * n2);
+    const bool self = curriculum_promoted(counts, bin, c.min_tries, c.promote_rate);
+    int P = self ? 1 : 0;
+    if (ix > 0) P += curriculum_promoted(counts, bin - n1 * n2, c.min_tries, c.promote_rate) ? 1 : 0;
+    if (ix < n0 - 1) P += curriculum_promoted(counts, bin + n1 * n2, c.min_tries, c.promote_rate) ? 1 : 0;
+    if (iy > 0) P += curriculum_promoted(counts, bin - n2, c.min_tries, c.promote_rate) ? 1 : 0;
+    if (iy < n1 - 1) P += curriculum_promoted(counts, bin + n2, c.min_tries, c.promote_rate) ? 1 : 0;
+    if (iz > 0) P += curriculum_promoted(counts, bin - 1, c.min_tries, c.promote_rate) ? 1 : 0;
+    if (iz < n2 - 1) P += curriculum_promoted(counts, bin + 1, c.min_tries, c.promote_rate) ? 1 : 0;
+    cdf[bin] = min(ODK_CURR_LMAX, levels[bin] + P);
+    const int tries = counts[2 * bin];
+    if (tries >= c.min_tries) { judged++; tries_judged += tries; }
+    if (self) promoted++;
+  }
+  __syncthreads();
+  int carry = 0;
+  for (int k = 0; k < chunks; k++) {   // uniform: every lane takes part in the shuffles
+    const int bin = k * 64 + lane;
+    const bool in = bin < nbins;
+    int x = 0;
+    if (in) {
+      x = cdf[bin];
+      levels[bin] = x;
+      if (counts[2 * bin] >= c.min_tries) { counts[2 * bin] = 0; counts[2 * bin + 1] = 0; }
+    }
+#pragma unroll
+    for (int dlt = 1; dlt < 64; dlt <<= 1) {
+      const int y = __shfl_up(x, dlt, 64);
+      if (lane >= dlt) x += y;
+    }
+    if (in) cdf[bin] = carry + x;
+    carry += __shfl(x, 63, 64);
+  }
+#pragma unroll
+  for (int dlt = 32; dlt > 0; dlt >>= 1) {
+    judged += __shfl_down(judged, dlt, 64); promoted += __shfl_down(promoted, dlt, 64); tries_judged += __shfl_down(tries_judged, dlt, 64);
+  }
+  if (lane == 0) {
+    stats[ODK_CURR_STAT_UPDATES] += 1; stats[ODK_CURR_STAT_JUDGED] += judged; stats[ODK_CURR_STAT_PROMOTED] += promoted;
+    stats[ODK_CURR_STAT_TRIES] += tries_judged;
+  }
+}
+
+extern "C" int odk_curriculum_update(const odk_batch* b, const odk_curriculum* c, int32_t* levels_dev, int32_t* cdf_dev, int32_t* counts_dev,
+                                     int32_t* stats_dev, void* stream) {
+  const char* fn = "odk_curriculum_update";
+  const void* const p[6] = {b, c, levels_dev, cdf_dev, counts_dev, stats_dev};
+  static const char* const name[6] = {"batch", "curriculum", "levels_dev", "cdf_dev", "counts_dev", "stats_dev"};
+  for (int i = 0; i < 6; i++) if (!p[i]) return fail(ODK_ERR_INVALID, "%s: null %s", fn, name[i]);
+  int nbins;
+  if (int rc = curriculum_grid(fn, c, &nbins)) return rc;
+  if (c->min_tries < 1) return fail(ODK_ERR_INVALID, "%s: min_tries = %d (at least 1: a bin without a try is not judged)", fn, (int)c->min_tries);
+  const Span s[4] = {{"levels_dev", levels_dev, 4 * (size_t)nbins}, {"cdf_dev", cdf_dev, 4 * (size_t)nbins}, {"counts_dev", counts_dev, 8 * (size_t)nbins},
+                     {"stats_dev", stats_dev, 16}};
+  if (int rc = spans_apart(fn, s, 4)) return rc;
+  HIPCHK(hipSetDevice(b->device));
+  hipLaunchKernelGGL(curriculum_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *c, nbins, (int*)levels_dev, (int*)cdf_dev,
+                     (int*)counts_dev, (int*)stats_dev);
   HIPCHK(hipGetLastError());
   return ODK_OK;
 }

@@ -60,6 +60,14 @@ class RewardTerms(C.Structure):
                 ("air_time_range", C.c_float * 2), ("soft_joint_pos_limit_factor", C.c_float), ("pose_weight", C.c_float * 16)]
 
 
+class Curriculum(C.Structure):
+    """odk_curriculum (include/odk.h "Command curriculum"): the grid over (vx, vy, wz), the head ranges and the controller's settings."""
+    _fields_ = [("lo", C.c_float * 3), ("hi", C.c_float * 3), ("n", C.c_int32 * 3), ("width", C.c_float * 3), ("head_lo", C.c_float * 4),
+                ("head_hi", C.c_float * 4), ("p_zero", C.c_float), ("period", C.c_int32), ("skip", C.c_int32), ("min_samples", C.c_int32),
+                ("tol_lin", C.c_float), ("tol_yaw", C.c_float), ("min_tries", C.c_int32), ("promote_rate", C.c_float), ("seed", C.c_uint32),
+                ("env_id_offset", C.c_uint32)]
+
+
 class MlpDesc(C.Structure):
     """odk_mlp_desc (include/odk.h)."""
     _fields_ = [("x", C.c_void_p), ("in_mean", C.c_void_p), ("in_std", C.c_void_p), ("wf", C.c_void_p * 4), ("wb", C.c_void_p * 4), ("b", C.c_void_p * 4), ("xp", C.c_void_p), ("h", C.c_void_p * 3),
@@ -209,6 +217,8 @@ def _signatures() -> Dict[str, tuple]:
         "odk_sensor_apply": (I, [P, P, P, P, P, P, P]),
         "odk_action_apply": (I, [P, P, P, P, P, P, P]),
         "odk_fault_resample": (I, [P, P, P, C.c_uint32, C.c_uint32, P, P, P, P]),
+        "odk_curriculum_step": (I, [P, C.POINTER(Curriculum), P, P, P, P, P, P, P, P, P, P]),
+        "odk_curriculum_update": (I, [P, C.POINTER(Curriculum), P, P, P, P, P]),
         "odk_physics_step": (I, [P, P, I, P]),
         "odk_batch_get_state": (I, [P, FP, FP, FP]),
         "odk_batch_set_state": (I, [P, FP, FP, FP]),
@@ -385,6 +395,24 @@ FAULT_NSLOT = SENSOR_NPRM + ACT_NPRM
 FAULT_NSTATE = 4
 FAULT_HEAD, FAULT_EPISODE = 0, 1
 FAULT_FIXED, FAULT_UNIFORM, FAULT_WHOLE = 0, 1, 2
+
+
+# the command curriculum (include/odk.h ODK_CURR_*): a state row of CURR_NSTATE floats per env, the four running totals of `stats`
+CURR_LMAX, CURR_MAX_AXIS, CURR_MAX_BINS, CURR_NSTATE = 5, 16, 4096, 8
+CURR_HEAD, CURR_EPISODE, CURR_STINT, CURR_STEP, CURR_BIN, CURR_SAMPLES, CURR_SQLIN, CURR_SQYAW = range(8)
+CURR_STAT_UPDATES, CURR_STAT_JUDGED, CURR_STAT_PROMOTED, CURR_STAT_TRIES = range(4)
+CURR_STREAM0 = 128      # draw k of a stint comes from stream CURR_STREAM0 + k of the action stage's hash (the fault rows' end at 127)
+
+
+def curriculum_nbins(cur) -> int:
+    """The bin count of a `Curriculum`; OdkError, by name, for an axis outside 1 .. CURR_MAX_AXIS bins or more than CURR_MAX_BINS bins."""
+    n = [int(v) for v in cur.n]
+    for a, v in enumerate(n):
+        if not 1 <= v <= CURR_MAX_AXIS:
+            raise OdkError(f"curriculum: n[{a}] = {v} (1 .. {CURR_MAX_AXIS} bins per axis)")
+    if n[0] * n[1] * n[2] > CURR_MAX_BINS:
+        raise OdkError(f"curriculum: nbins = {n[0] * n[1] * n[2]} (at most {CURR_MAX_BINS})")
+    return n[0] * n[1] * n[2]
 
 
 def sensor_rotation(roll_deg: float, pitch_deg: float, yaw_deg: float) -> np.ndarray:
@@ -1408,6 +1436,58 @@ class Batch:
                 raise OdkError(f"{fn}: {name} = {v!r} (a whole number, 0 .. 2^32 - 1)")
         _chk(self.L.odk_fault_resample(self._b, _ptr(done), _ptr(spec), int(seed), int(env_id_offset), _ptr(state), _ptr(sensor_fault),
                                        _ptr(act_fault), self._stream()))
+
+    def _curriculum_ints(self, fn: str, cur, **arrays) -> int:
+        """The checks the two curriculum launches share: `cur` a `Curriculum` with a grid in range, every array a contiguous int32 tensor of
+        its shape on the batch's device.  Returns nbins."""
+        if not isinstance(cur, Curriculum):
+            raise OdkError(f"{fn}: curriculum: expected an engine.Curriculum, got {type(cur).__name__}")
+        try:
+            nbins = curriculum_nbins(cur)
+        except OdkError as e:
+            raise OdkError(f"{fn}: {e}")
+        shapes = dict(levels=(nbins,), cdf=(nbins,), counts=(nbins, 2), stats=(4,))
+        for what, t in arrays.items():
+            _check_tensor(f"{fn}: {what}", t, "int32", self.device, str(shapes[what]), lambda s, w=shapes[what]: s == w)
+        return nbins
+
+    def curriculum_step(self, cur, priv, done, truncation, cdf, counts, state, cmd, obs=None, patch_priv: bool = True):
+        """One `odk_curriculum_step` launch, issued AFTER `step`: per env the velocity sample of the step against the command it ran under,
+        the judgement of a stint that ends (integer atomics on `counts` [nbins, 2]) and the draw of the next command from `cdf` ([nbins]
+        int32) into `cmd` -- which must be the tensor bound with `bind_commands` -- and into floats 6 .. 12 of `obs` ([nenv, nobs] or
+        None) and, with `patch_priv`, of `priv` ([nenv, npriv]: the step's privileged observation, whose noise-free velocities are read).
+        `state`: [nenv, CURR_NSTATE], zeroed before the first call, on which every env draws.  `done` / `truncation`: [nenv], or both None
+        (no stint ends but by `period`)."""
+        import torch
+        fn = "curriculum_step"
+        self._curriculum_ints(fn, cur, cdf=cdf, counts=counts)
+        check_accumulator(f"{fn}: state", state, self.nenv, CURR_NSTATE, self.device)
+        check_accumulator(f"{fn}: priv", priv, self.nenv, self.npriv, self.device)
+        if obs is not None:
+            check_accumulator(f"{fn}: obs", obs, self.nenv, self.nobs, self.device)
+        _check_tensor(f"{fn}: cmd", cmd, "float32", self.device, f"({self.nenv}, {NCOMMAND})", lambda s: s == (self.nenv, NCOMMAND))
+        if self.commands is None or cmd.data_ptr() != self.commands.data_ptr():
+            raise OdkError(f"{fn}: cmd is not the tensor bound to the batch (bind_commands)")
+        if (done is None) != (truncation is None):
+            raise OdkError(f"{fn}: done and truncation come together: both tensors or both None")
+        for what, t in (("done", done), ("truncation", truncation)):
+            if t is not None:
+                _check_tensor(f"{fn}: {what}", t, "float32", self.device, f"({self.nenv},)", lambda s: s == (self.nenv,), " or None")
+        for name, lo in (("period", 1), ("skip", 0), ("min_samples", 0)):
+            if int(getattr(cur, name)) < lo:
+                raise OdkError(f"{fn}: {name} = {int(getattr(cur, name))} (at least {lo})")
+        _chk(self.L.odk_curriculum_step(self._b, C.byref(cur), _ptr(priv), _ptr(done), _ptr(truncation), _ptr(cdf), _ptr(counts), _ptr(state),
+                                        _ptr(cmd), _ptr(obs), _ptr(priv) if patch_priv else None, self._stream()))
+
+    def curriculum_update(self, cur, levels, cdf, counts, stats):
+        """One `odk_curriculum_update` launch (one wave): judges every bin of `counts` with `min_tries` tries, raises `levels` ([nbins] int32)
+        by the promoted bins among a bin and its axis neighbours up to CURR_LMAX, zeroes the judged counters, rebuilds `cdf` as the
+        inclusive prefix sums and advances `stats` ([4] int32)."""
+        fn = "curriculum_update"
+        self._curriculum_ints(fn, cur, levels=levels, cdf=cdf, counts=counts, stats=stats)
+        if int(cur.min_tries) < 1:
+            raise OdkError(f"{fn}: min_tries = {int(cur.min_tries)} (at least 1)")
+        _chk(self.L.odk_curriculum_update(self._b, C.byref(cur), _ptr(levels), _ptr(cdf), _ptr(counts), _ptr(stats), self._stream()))
 
     def physics_step(self, ctrl, n_substeps: int = 10):
         assert ctrl.is_cuda and ctrl.dtype == self.torch.float32 and ctrl.is_contiguous() and tuple(ctrl.shape) == (self.nenv, self.model.nu)

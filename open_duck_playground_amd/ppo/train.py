@@ -225,10 +225,11 @@ _ROLLOUT_BUFFERS = weakref.WeakKeyDictionary()
 
 
 @torch.no_grad()
-def _rollout_engine(env, net: PPONetworks, state, unroll_length: int, gen: torch.Generator, deterministic: bool, faults=None):
+def _rollout_engine(env, net: PPONetworks, state, unroll_length: int, gen: torch.Generator, deterministic: bool, faults=None, curriculum=None):
     """`rollout` for an engine-backed env on the GPU: per step the policy's whole-network launch (when the architecture allows),
     the sampling launch writing straight into the history, the fused env-step launch and one snapshot launch.  With `faults` three more:
-    the stage's resample and sensor launches in front of the policy, its action launch between the sampling and the env step."""
+    the stage's resample and sensor launches in front of the policy, its action launch between the sampling and the env step.  With
+    `curriculum` one more, between the env step and the snapshot: the snapshot then carries the patched command slots."""
     from .. import engine
     from .learner import fused_policy
     T, A = unroll_length, net.action_size
@@ -248,6 +249,8 @@ def _rollout_engine(env, net: PPONetworks, state, unroll_length: int, gen: torch
         logits = fp(obs) if fp is not None else net.policy(net.norm_obs(obs))
         engine.policy_sample(logits, noise[t], out=(b["raw_action"][t], rb.action, b["log_prob"][t]))
         state = env.step(state, rb.action if faults is None else faults.deliver(rb.action, state.done))
+        if curriculum is not None:
+            curriculum.after_step(state)
         rb.after[t]()
     data = {k: v.transpose(0, 1).contiguous() for k, v in b.items()}
     data["last_priv"] = state.obs["privileged_state"].clone()
@@ -256,13 +259,15 @@ def _rollout_engine(env, net: PPONetworks, state, unroll_length: int, gen: torch
 
 @torch.no_grad()
 def rollout(env, net: PPONetworks, state, unroll_length: int, gen: torch.Generator, deterministic: bool = False, engine_path: bool = True,
-            faults=None):
+            faults=None, curriculum=None):
     """brax acting.generate_unroll: returns ([B, T, ...] transition tensors, final state).  `engine_path` false forces the
     generic loop below for an engine-backed env too (tests compare the two).  `faults` (a fault_training.FaultStage of this env, or None):
     the policy reads the stage's observation -- `obs` holds that row -- and the env steps with the action the stage delivers; `raw_action`
-    and `log_prob` stay the policy's, `priv`, reward, done and truncation the env's."""
+    and `log_prob` stay the policy's, `priv`, reward, done and truncation the env's.  `curriculum` (a command_curriculum.CommandCurriculum
+    of this env, or None): its `after_step` runs right behind every env step, so the `obs` / `priv` rows of step t + 1 (and a fault stage's
+    next `observe`) carry the command it drew."""
     if engine_path and state.obs["state"].is_cuda and hasattr(env, "batch") and "truncation" in state.info:
-        return _rollout_engine(env, net, state, unroll_length, gen, deterministic, faults)
+        return _rollout_engine(env, net, state, unroll_length, gen, deterministic, faults, curriculum)
     keys = ("obs", "priv", "raw_action", "log_prob", "reward", "done", "truncation")
     buf = {k: [] for k in keys}
     for _ in range(unroll_length):
@@ -273,6 +278,8 @@ def rollout(env, net: PPONetworks, state, unroll_length: int, gen: torch.Generat
         logp = tanh_normal_log_prob(loc, scale, raw)
         action = torch.tanh(raw).contiguous()
         state = env.step(state, action if faults is None else faults.deliver(action, state.done))
+        if curriculum is not None:
+            curriculum.after_step(state)
         buf["obs"].append(obs); buf["priv"].append(priv); buf["raw_action"].append(raw); buf["log_prob"].append(logp)
         buf["reward"].append(state.reward.clone()); buf["done"].append(state.done.clone()); buf["truncation"].append(state.info["truncation"].clone())
     data = {k: torch.stack(v, 1) for k, v in buf.items()}
@@ -282,10 +289,13 @@ def rollout(env, net: PPONetworks, state, unroll_length: int, gen: torch.Generat
 
 def train(environment, num_timesteps: int, progress_fn: Optional[Callable] = None, policy_params_fn: Optional[Callable] = None,
           restore_checkpoint_path: Optional[str] = None, seed: int = 0, randomization_fn: Optional[Callable] = None,
-          log_path: Optional[str] = None, eval_env=None, faults=None, **overrides):
+          log_path: Optional[str] = None, eval_env=None, faults=None, curriculum=None, **overrides):
     """Trains on `environment` (a batched Joystick / Standing).  Returns (networks, metrics).  `faults` (a fault_training.FaultStage of
     `environment`, or None): every rollout runs through the stage, whose state is zeroed after every reset of the env; the Evaluator stays
-    the nominal robot, so `eval/episode_reward` compares across runs.
+    the nominal robot, so `eval/episode_reward` compares across runs.  `curriculum` (a command_curriculum.CommandCurriculum of
+    `environment`, or None): it draws the training commands -- `reset` after every reset of the env, `after_step` in the rollout, `update`
+    once per iteration after the rollout -- and the metrics gain `training/curriculum_coverage`, `_mean_level` and `_promotions`; the
+    Evaluator's env keeps its nominal sampled commands.
 
     Epoch structure of brax ppo.train: `num_evals - 1` epochs of `ceil(num_timesteps / (epochs * env_steps_per_iter *
     num_resets_per_eval))` training steps, the env re-reset `num_resets_per_eval` times per epoch, one evaluation
@@ -347,6 +357,8 @@ def train(environment, num_timesteps: int, progress_fn: Optional[Callable] = Non
     state = environment.reset(seed)
     if faults is not None:
         faults.reset()
+    if curriculum is not None:
+        curriculum.reset(state)
     reset_count = 0
     meter = LossMeter()
     grp = dist.group.WORLD if world > 1 else None
@@ -354,7 +366,9 @@ def train(environment, num_timesteps: int, progress_fn: Optional[Callable] = Non
         t_epoch = time.time()
         for _ in range(resets):
             for _ in range(iters_per_epoch):
-                data, state = rollout(environment, net, state, cfg["unroll_length"], gen, faults=faults)
+                data, state = rollout(environment, net, state, cfg["unroll_length"], gen, faults=faults, curriculum=curriculum)
+                if curriculum is not None:
+                    curriculum.update(grp)
                 if cfg["normalize_observations"]:
                     net.norm_obs.update(data["obs"], grp); net.norm_priv.update(data["priv"], grp)
                 if learner is None and done_steps == 0:
@@ -366,6 +380,8 @@ def train(environment, num_timesteps: int, progress_fn: Optional[Callable] = Non
                 state = environment.reset(seed + 7919 * reset_count)
                 if faults is not None:
                     faults.reset()
+                if curriculum is not None:
+                    curriculum.reset(state)
         loss_metrics = learner.metrics() if learner is not None else meter.mean(world, grp)
         if world > 1:
             assert_replicas_identical(net, grp)
@@ -378,7 +394,8 @@ def train(environment, num_timesteps: int, progress_fn: Optional[Callable] = Non
         epoch_time = time.time() - t_epoch
         training_metrics = {"training/sps": iters_per_epoch * resets * steps_per_iter / epoch_time, "training/walltime": time.time() - t0,
                             "training/unroll_reward": float(m[0]), "training/done_rate": float(m[1]),
-                            **{f"training/{k}": float(v) for k, v in loss_metrics.items()}}
+                            **{f"training/{k}": float(v) for k, v in loss_metrics.items()},
+                            **({} if curriculum is None else {f"training/curriculum_{k}": v for k, v in curriculum.metrics().items()})}
         metrics = report(training_metrics)
         if rank == 0 and policy_params_fn:
             policy_params_fn(done_steps, net)
@@ -416,13 +433,20 @@ def assert_replicas_identical(net: PPONetworks, group=None):
         raise RuntimeError(f"data-parallel replicas diverged: {bad} of {bits.numel()} parameter / normaliser words differ across ranks")
 
 
-def save_checkpoint(path: str, net: PPONetworks, fault_spec: Optional[Dict] = None):
+def save_checkpoint(path: str, net: PPONetworks, fault_spec: Optional[Dict] = None, command_curriculum: Optional[Dict] = None):
     """(normalizer, policy, value) triple like the reference's orbax checkpoint (common/runner.py:68-76).  `fault_spec`: the faults the
-    networks were trained under (fault_training.FaultStage.describe), stored beside them; a checkpoint trained without has no such key."""
+    networks were trained under (fault_training.FaultStage.describe), stored beside them; a checkpoint trained without has no such key.
+    `command_curriculum`: likewise the command curriculum's state (command_curriculum.CommandCurriculum.describe)."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    torch.save({"networks": net.state_dict(), **({} if fault_spec is None else {"fault_spec": fault_spec})}, path)
+    torch.save({"networks": net.state_dict(), **({} if fault_spec is None else {"fault_spec": fault_spec}),
+                **({} if command_curriculum is None else {"command_curriculum": command_curriculum})}, path)
 
 
 def checkpoint_fault_spec(path: str) -> Optional[Dict]:
     """The `fault_spec` a checkpoint was saved with, None for one trained without faults (and for every older file)."""
     return torch.load(path, map_location="cpu").get("fault_spec")
+
+
+def checkpoint_command_curriculum(path: str) -> Optional[Dict]:
+    """The `command_curriculum` a checkpoint was saved with, None for one trained without (and for every older file)."""
+    return torch.load(path, map_location="cpu").get("command_curriculum")

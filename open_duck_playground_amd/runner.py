@@ -154,6 +154,13 @@ class OpenDuckMiniV2Runner:
         if self.faults is not None:
             import json
             print(f"Training under faults: {json.dumps(self.faults.describe())}")
+        # the command curriculum (command_curriculum.py): it draws the training env's commands -- the Evaluator keeps the nominal sampled ones
+        from . import command_curriculum
+        self.curriculum_spec = command_curriculum.spec_from_args(args, self.env)      # None without --command_curriculum: every launch is as before
+        self.curriculum = None if self.curriculum_spec is None else command_curriculum.CommandCurriculum(self.env, self.curriculum_spec, seed=args.seed)
+        if self.curriculum is not None:
+            import json
+            print(f"Command curriculum: {json.dumps(self.curriculum_spec)}")
         self.action_size = self.env.action_size
         self.obs_size = int(self.env.observation_size["state"][0])
         # one generator per (seed, rank, stream): stream 0 = training envs, 1 = evaluation envs (ppo/train.py)
@@ -174,7 +181,8 @@ class OpenDuckMiniV2Runner:
         d = datetime.now().strftime("%Y_%m_%d_%H%M%S")
         path = f"{self.output_dir}/{d}_{current_step}.pt"
         print(f"Saving checkpoint (step: {current_step}): {path}")
-        self.ppo.save_checkpoint(path, net, fault_spec=None if self.faults is None else self.faults.describe())
+        self.ppo.save_checkpoint(path, net, fault_spec=None if self.faults is None else self.faults.describe(),
+                                 command_curriculum=None if self.curriculum is None else self.curriculum.describe())
         from .export_onnx import export_onnx   # reference common/runner.py:77-84
         export_onnx(net, output_path=f"{self.output_dir}/{d}_{current_step}.onnx")
 
@@ -188,7 +196,7 @@ class OpenDuckMiniV2Runner:
             return self.ppo.train(self.env, num_timesteps=self.args.num_timesteps, progress_fn=self.progress_callback,
                                   policy_params_fn=self.policy_params_fn, restore_checkpoint_path=self.args.restore_checkpoint_path,
                                   seed=self.args.seed, randomization_fn=self.randomizer, log_path=os.path.join(self.output_dir, "metrics.jsonl"),
-                                  faults=self.faults, num_envs=self.args.num_envs)
+                                  faults=self.faults, curriculum=self.curriculum, num_envs=self.args.num_envs)
         finally:
             if self.writer is not None:
                 self.writer.close()
@@ -235,6 +243,25 @@ def build_parser() -> argparse.ArgumentParser:
                              "units, fixed or redrawn per episode as --train_sensor's.  cutoff=A:B draws the filter coefficient uniformly "
                              "between the two cutoffs' (a range that holds 0 = off is refused); offset=X redraws every actuator's horn error "
                              "in +-X; freeze and freeze_at take one value.  e.g. cutoff=15:40,drop=0:0.05")
+    parser.add_argument("--command_curriculum", type=str, default=None, metavar="AXIS=LO:HI:BINS[,...]",
+                        help="--env joystick: train on commands drawn from a grid over vx, vy, wz whose bins open as the policy tracks well inside "
+                             "their neighbours (an axis not named keeps the env's range with one bin; at most 16 bins per axis, 4096 in all).  "
+                             "e.g. vx=-0.15:0.222:8,vy=-0.2:0.2:4,wz=-1.1:1.2:8 (a grid beyond the reference-motion table is refused while the "
+                             "imitation reward is on: --curriculum_allow_clipped_reference)")
+    parser.add_argument("--curriculum_start", type=str, default=None, metavar="AXIS=LO:HI[,...]",
+                        help="the range whose bins are open from the start (those whose centre lies inside it; default: the env config's command "
+                             "ranges).  A start that covers the whole grid is uniform sampling over the grid")
+    parser.add_argument("--curriculum_allow_clipped_reference", action="store_true",
+                        help="take a grid wider than the reference-motion table while the imitation reward is on (a warning instead of a refusal)")
+    from .command_curriculum import SETTINGS as curriculum_settings
+    for key, what in (("period", "steps per command (a stint)"), ("skip", "steps of a stint before its first velocity sample"),
+                      ("min_samples", "samples a stint needs to be judged"), ("min_tries", "judged stints a bin needs before it can promote"),
+                      ("promote_rate", "share of successful stints that promotes a bin's neighbourhood"),
+                      ("tol_lin", "planar RMS velocity error of a successful stint, m/s"),
+                      ("tol_yaw", "yaw-rate RMS error of a successful stint, rad/s"), ("p_zero", "share of all-zero commands")):
+        whole = isinstance(curriculum_settings[key], int)
+        parser.add_argument(f"--curriculum_{key}", type=int if whole else float, default=None,
+                            help=f"command curriculum: {what} (default {curriculum_settings[key]})")
     add_imitation_flags(parser)
     add_head_joint_flag(parser)
     return parser
@@ -247,6 +274,10 @@ def check_env_flags(parser, args) -> None:
         if getattr(args, "train_sensor", None) or getattr(args, "train_actuation", None):
             from . import fault_training
             fault_training.spec_from_args(args)
+        from . import command_curriculum
+        if command_curriculum.spec_from_args(args) is not None and args.env != "joystick":
+            raise ValueError(f"--command_curriculum belongs to --env joystick: the {args.env} task has no velocity commands to track "
+                             "(its commands are head postures)")
     except ValueError as e:
         parser.error(str(e))
 

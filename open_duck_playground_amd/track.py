@@ -1430,6 +1430,15 @@ def trained_under(path: Optional[str]):
     return checkpoint_fault_spec(path)
 
 
+def trained_with_curriculum(path: Optional[str]):
+    """The command curriculum a checkpoint was trained with (runner --command_curriculum: ppo/train.py save_checkpoint's
+    `command_curriculum`), None for every other checkpoint."""
+    if not path:
+        return None
+    from .ppo.train import checkpoint_command_curriculum
+    return checkpoint_command_curriculum(path)
+
+
 @dataclasses.dataclass
 class Report:
     """One report of a Tracker.  `acc`: its zeroed accumulator ([num_envs, ncol] on the env's device); `launch(batch, track_acc)`: after the
@@ -1909,6 +1918,9 @@ def run(args, out=sys.stdout) -> Dict:
                     hfield_up_normals_only=bool(args.hfield_up_normals_only), envs_per_command=E, episode_length=T, seed=int(args.seed),
                     num_envs=n, dt=float(env.dt), policy="deterministic tanh(loc)", fused_policy=tr.fp is not None, graph=tr.graph is not None,
                     reference_motion=getattr(args, "reference_motion", None), reference_motion_sha256=motion.sha256 if motion is not None else None)
+    with_curriculum = trained_with_curriculum(args.checkpoint)
+    if with_curriculum is not None:      # only then: every other checkpoint keeps its keys
+        settings.update(trained_with_curriculum=with_curriculum)
     settings.update({k: v for r in reports if r.drives for k, v in r.settings.items()})
     if axis:
         settings.update(axis.settings)

@@ -22,7 +22,7 @@ for r in rows:
     m = re.search(r"(reset_kernel|step_kernel|physics_kernel)IN3odk5ShapeI(.*?)EEELi(\d+)ELi(\d+)", r["name"])
     if not m:
         # a kernel with no compiled shape (odk_reports.hip's: `python tools/kernel_resources.py action_kernel` names the ones to print)
-        k = re.match(r"_Z\d+([a-z_]+_kernel)P", r["name"])
+        k = re.match(r"_Z\d+([a-z_]+_kernel)(?:P|\d)", r["name"])      # (first parameter a pointer, or a struct by value)
         if k and k.group(1) in sys.argv[1:]:
             print(f"{k.group(1):15s} vgpr {r.get('VGPRs', '?'):>3s} agpr {r.get('AGPRs', '?'):>3s} scratch {r.get('ScratchSize', '?'):>3s} "
                   f"occupancy {r.get('Occupancy', '?')} sgpr {r.get('TotalSGPRs', '?')} (spilled to lanes: {r.get('SGPRs Spill', '?')}) lds {r.get('LDS Size', '?')}")
