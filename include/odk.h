@@ -837,6 +837,50 @@ int odk_curriculum_step(const odk_batch* b, const odk_curriculum* c, const float
 int odk_curriculum_update(const odk_batch* b, const odk_curriculum* c, int32_t* levels_dev, int32_t* cdf_dev, int32_t* counts_dev,
                           int32_t* stats_dev, void* stream);
 
+/* Log replay (which plant is the real robot: the actions of a recorded observation log -- mujoco_infer.py's mujoco_saved_obs.pkl, or the
+ * robot runtime's -- are replayed through a batch whose envs are candidate plants, and each env's joints are scored against what the log's
+ * encoders recorded).  Two launches beside the step kernel, both one 16-lane row per env (lane = actuator, four envs per wave), no LDS, no
+ * scratch, graph-capturable, every product rounded before it is added: a float32 host restatement has their bits.  They know one table
+ * layout and no task.
+ *
+ * The table log_dev [nrow, ODK_LOG_ROW(nu)] (the caller's device floats; the host cannot see them, their contents are the caller's to
+ * validate).  Row k is what the log shows after control step k, all of it taken from the log's observation row k + 1:
+ *   ODK_LOG_COMMAND [7]   the command
+ *   ODK_LOG_ACTION [nu]   last_act: the action a_k that step k applies (row k of the log was saved before the policy computed a_k)
+ *   log_pos(nu) [nu]      joint position minus default, radians
+ *   log_vel(nu) [nu]      joint velocity AS THE OBSERVATION HOLDS IT (rad/s times dof_vel_scale): the logged float32 itself.  BUILD-DEFINED:
+ *                         dividing it by dof_vel_scale = 0.05 on the host is not invertible in float32 (x 0.05 maps five neighbouring
+ *                         floats onto four), so a plant replayed on its own log would not score 0; the kernel multiplies instead
+ *   log_gyro(nu) [3], log_accel(nu) [3], log_contact(nu) [2]
+ * with log_pos(nu) = 7 + nu, log_vel = 7 + 2 nu, log_gyro = 7 + 3 nu, log_accel = 10 + 3 nu, log_contact = 13 + 3 nu.
+ *
+ * odk_log_apply: issued BEFORE odk_step.  The tracking accumulator is the clock, exactly as odk_command_schedule_apply reads it: t = STEPS
+ * of env e (STEPS - 1 once ENDED is set), k = min(max(t, 0), nrow - 1).  Lane u < nu stores action_dev[e][u] = row k's action u, lanes
+ * 0..6 store entries 0..6 of env e's row of the BOUND command buffer from row k's command.  A pure function of its inputs.
+ * ODK_ERR_INVALID, nothing launched: a null pointer (by name), no bound commands, nrow < 1, a model with more than 16 actuators.
+ *
+ * odk_replay_accumulate: issued after odk_step and BEFORE odk_tracking_accumulate (odk_push_accumulate's ENDED / STEPS contract: STEPS is
+ * the index k of the step that just ran).  A sample is odk_gait_accumulate's (first episode, not done) with k < nrow; an env whose first
+ * episode has ended or whose clock has passed the end of the table keeps every bit of its row.  acc_dev [nenv, 16, ODK_REPLAY_NSLOT],
+ * zeroed by the caller: lane u owns the slots of [e][u].  With Q the noise-free privileged tail of priv_dev (float nobs onwards) and L
+ * row k of the table, per sample:
+ *   lane u < nu   dp = Q[15 + u] - L[log_pos + u];  POS_ERR_SUM += dp;  POS_ERR_SQ += dp dp;  POS_ERR_PEAK = max(POS_ERR_PEAK, |dp|);
+ *                 dv = Q[15 + nu + u] dof_vel_scale - L[log_vel + u]  (the batch config's dof_vel_scale);  VEL_ERR_SQ += dv dv
+ *   lane u < 3    GYRO_ERR_SQ += (Q[u] - L[log_gyro + u])^2;  ACCEL_ERR_SQ += (Q[3 + u] - L[log_accel + u])^2
+ *   lane u < 2    CONTACT_AGREE += 1 when (Q[16 + 3 nu + u] != 0) == (L[log_contact + u] > 0.5)
+ *   lane 0        SAMPLES += 1
+ * ODK_ERR_INVALID, nothing launched: a null pointer (by name), nrow < 1, a model with more than 16 actuators. */
+#define ODK_LOG_ROW(nu) (15 + 3 * (nu))
+#define ODK_REPLAY_NSLOT 8
+enum { ODK_LOG_COMMAND = 0, ODK_LOG_ACTION = 7 };
+enum { ODK_REPLAY_POS_ERR_SUM = 0, ODK_REPLAY_POS_ERR_SQ = 1, ODK_REPLAY_VEL_ERR_SQ = 2, ODK_REPLAY_POS_ERR_PEAK = 3, ODK_REPLAY_GYRO_ERR_SQ = 4,
+       ODK_REPLAY_ACCEL_ERR_SQ = 5, ODK_REPLAY_CONTACT_AGREE = 6, ODK_REPLAY_SAMPLES = 7 };
+int odk_log_apply(const odk_batch* b, const float* log_dev, int nrow, const float* track_acc_dev, float* action_dev /* [nenv, nu] out */,
+                  void* stream);
+int odk_replay_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
+                          const float* track_acc_dev, const float* log_dev, int nrow, float* acc_dev /* [nenv, 16, ODK_REPLAY_NSLOT] */,
+                          void* stream);
+
 /* mjx_env.step alone (physics only, n_substeps, ctrl = ctrl_dev [nenv, nu]); for parity tests */
 int odk_physics_step(odk_batch* b, const float* ctrl_dev, int n_substeps, void* stream);
 

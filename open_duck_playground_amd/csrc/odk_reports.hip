@@ -1,5 +1,5 @@
 // odk_reports.hip -- the evaluation reports of include/odk.h (libodk.so): the accumulator kernels of the tracking / push / gait / posture /
-// imitation / response / fall / path reports, the command-schedule kernel, the waypoint follower, the sensor-fault and actuation-fault stages, the fault resampling and the two command-curriculum kernels, with their C entry points.  They read
+// imitation / response / fall / path reports, the command-schedule kernel, the waypoint follower, the sensor-fault and actuation-fault stages, the fault resampling, the two command-curriculum kernels and the two log-replay kernels, with their C entry points.  They read
 // finished observation rows (odk_obs_layout.h) and the batch (odk_batch.h: read-only here; its state is odk_engine.hip's); no compiled shape.
 // gfx950 only, no CPU fallback.
 #include <hip/hip_runtime.h>
@@ -1254,6 +1254,92 @@ extern "C" int odk_curriculum_update(const odk_batch* b, const odk_curriculum* c
   HIPCHK(hipSetDevice(b->device));
   hipLaunchKernelGGL(curriculum_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *c, nbins, (int*)levels_dev, (int*)cdf_dev,
                      (int*)counts_dev, (int*)stats_dev);
+  HIPCHK(hipGetLastError());
+  return ODK_OK;
+}
+
+// ---- log replay (include/odk.h "Log replay": the table layout and the definitions these two kernels restate).  One 16-lane row per env,
+// lane = actuator, no LDS, no row sums.  Contraction is off, so a float32 host restatement has the bits.
+namespace log_at {   // offsets into a row of the table, after ODK_LOG_COMMAND [7] and ODK_LOG_ACTION [nu]
+__host__ __device__ constexpr int pos(int nu) { return 7 + nu; }
+__host__ __device__ constexpr int vel(int nu) { return 7 + 2 * nu; }
+__host__ __device__ constexpr int gyro(int nu) { return 7 + 3 * nu; }
+__host__ __device__ constexpr int accel(int nu) { return 10 + 3 * nu; }
+__host__ __device__ constexpr int contact(int nu) { return 13 + 3 * nu; }
+}  // namespace log_at
+static_assert(log_at::contact(ODK_NU) + 2 == ODK_LOG_ROW(ODK_NU), "the contacts end the row");
+
+// The action and the command of the step about to run, issued before odk_step: sched_apply_kernel's clock (STEPS, STEPS - 1 once ENDED is
+// set), clamped into the table.  (The clamp is taken on the float: whatever the slot holds, the row read lies inside the table.)
+__global__ void __launch_bounds__(256) log_apply_kernel(const float* __restrict__ log, int nrow, int nu, const float* __restrict__ track,
+                                                        float* __restrict__ action, float* __restrict__ cmd, int cmd_stride, int nenv) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x, e = t >> 4, u = t & 15;
+  if (e >= nenv) return;
+  const float* T = track + (size_t)e * ODK_TRACK_NACC;
+  const float s = T[ODK_TRACK_ENDED] != 0.0f ? T[ODK_TRACK_STEPS] - 1.0f : T[ODK_TRACK_STEPS];
+  const int k = (int)fminf(fmaxf(s, 0.0f), (float)(nrow - 1));
+  const float* L = log + (size_t)k * ODK_LOG_ROW(nu);
+  if (u < nu) action[(size_t)e * nu + u] = L[ODK_LOG_ACTION + u];
+  if (u < 7) cmd[(size_t)e * cmd_stride + u] = L[ODK_LOG_COMMAND + u];
+}
+
+extern "C" int odk_log_apply(const odk_batch* b, const float* log_dev, int nrow, const float* track_acc_dev, float* action_dev, void* stream) {
+  const char* fn = "odk_log_apply";
+  const void* const p[4] = {b, log_dev, track_acc_dev, action_dev};
+  static const char* const name[4] = {"batch", "log_dev", "track_acc_dev", "action_dev"};
+  for (int i = 0; i < 4; i++) if (!p[i]) return fail(ODK_ERR_INVALID, "%s: null %s", fn, name[i]);
+  if (!b->d_cmd) return fail(ODK_ERR_INVALID, "%s: no commands bound (odk_batch_bind_commands)", fn);
+  if (nrow < 1) return fail(ODK_ERR_INVALID, "%s: nrow = %d (a table has at least one row)", fn, nrow);
+  const int nu = b->model.h.nu;
+  if (int rc = fits_row16(fn, nu)) return rc;
+  Launch g; if (int rc = launch_on(b, 16, &g)) return rc;
+  // the bound buffer is the caller's own device memory (odk_command_schedule_apply's note): this launch is the one writer
+  hipLaunchKernelGGL(log_apply_kernel, g.grid, dim3(256), 0, (hipStream_t)stream, log_dev, nrow, nu, track_acc_dev, action_dev,
+                     const_cast<float*>(b->d_cmd), b->cmd_stride, b->nenv);
+  HIPCHK(hipGetLastError());
+  return ODK_OK;
+}
+
+// Residuals of one replayed step against the table's row of that step, issued between odk_step and odk_tracking_accumulate (the ENDED /
+// STEPS contract of push_kernel).  Lane u owns the ODK_REPLAY_NSLOT floats of [e][u]; only a sample inside the table stores anything.
+__global__ void __launch_bounds__(256) replay_kernel(const float* __restrict__ priv, int npriv, int nobs, int nu, const float* __restrict__ done,
+                                                     const float* __restrict__ track, const float* __restrict__ log, int nrow, float vel_scale,
+                                                     float* __restrict__ acc, int nenv) {
+#pragma clang fp contract(off)
+  const Row16 th = row16(priv, npriv, nobs, nu, done, track, nenv);
+  const int u = th.u;
+  const float s = track[th.row * ODK_TRACK_NACC + ODK_TRACK_STEPS];      // first-episode steps before the one that just ran: its index
+  if (!th.sample || !(s >= 0.0f && s < (float)nrow)) return;
+  const float *Q = th.Q, *L = log + (size_t)(int)s * ODK_LOG_ROW(nu);
+  float* A = acc + (th.row * 16 + u) * ODK_REPLAY_NSLOT;
+  if (u < nu) {
+    const float dp = Q[priv_at::JOINT_POS + u] - L[log_at::pos(nu) + u];
+    const float dv = Q[priv_at::joint_vel(nu) + u] * vel_scale - L[log_at::vel(nu) + u];
+    A[ODK_REPLAY_POS_ERR_SUM] += dp;
+    A[ODK_REPLAY_POS_ERR_SQ] += dp * dp;
+    A[ODK_REPLAY_VEL_ERR_SQ] += dv * dv;
+    A[ODK_REPLAY_POS_ERR_PEAK] = fmaxf(A[ODK_REPLAY_POS_ERR_PEAK], fabsf(dp));
+  }
+  if (u < 3) {
+    const float dg = Q[priv_at::GYRO + u] - L[log_at::gyro(nu) + u], da = Q[priv_at::ACCELEROMETER + u] - L[log_at::accel(nu) + u];
+    A[ODK_REPLAY_GYRO_ERR_SQ] += dg * dg;
+    A[ODK_REPLAY_ACCEL_ERR_SQ] += da * da;
+  }
+  if (u < 2) A[ODK_REPLAY_CONTACT_AGREE] += ((Q[priv_at::contact(nu) + u] != 0.0f) == (L[log_at::contact(nu) + u] > 0.5f)) ? 1.0f : 0.0f;
+  if (u == 0) A[ODK_REPLAY_SAMPLES] += 1.0f;
+}
+
+extern "C" int odk_replay_accumulate(const odk_batch* b, const float* priv_dev, const float* done_dev, const float* truncation_dev,
+                                     const float* track_acc_dev, const float* log_dev, int nrow, float* acc_dev, void* stream) {
+  const char* fn = "odk_replay_accumulate";
+  if (int rc = null_args(fn, b, priv_dev, done_dev, truncation_dev, track_acc_dev, acc_dev)) return rc;
+  if (!log_dev) return fail(ODK_ERR_INVALID, "%s: null log_dev", fn);
+  if (nrow < 1) return fail(ODK_ERR_INVALID, "%s: nrow = %d (a table has at least one row)", fn, nrow);
+  const int nu = b->model.h.nu;
+  if (int rc = fits_row16(fn, nu)) return rc;
+  Launch g; if (int rc = launch_on(b, 16, &g)) return rc;
+  hipLaunchKernelGGL(replay_kernel, g.grid, dim3(256), 0, (hipStream_t)stream, priv_dev, g.npriv, g.nobs, nu, done_dev, track_acc_dev,
+                     log_dev, nrow, b->cfg.dof_vel_scale, acc_dev, b->nenv);
   HIPCHK(hipGetLastError());
   return ODK_OK;
 }

@@ -219,6 +219,8 @@ def _signatures() -> Dict[str, tuple]:
         "odk_fault_resample": (I, [P, P, P, C.c_uint32, C.c_uint32, P, P, P, P]),
         "odk_curriculum_step": (I, [P, C.POINTER(Curriculum), P, P, P, P, P, P, P, P, P, P]),
         "odk_curriculum_update": (I, [P, C.POINTER(Curriculum), P, P, P, P, P]),
+        "odk_log_apply": (I, [P, P, I, P, P, P]),
+        "odk_replay_accumulate": (I, report + [P, I, P, P]),
         "odk_physics_step": (I, [P, P, I, P]),
         "odk_batch_get_state": (I, [P, FP, FP, FP]),
         "odk_batch_set_state": (I, [P, FP, FP, FP]),
@@ -413,6 +415,33 @@ def curriculum_nbins(cur) -> int:
     if n[0] * n[1] * n[2] > CURR_MAX_BINS:
         raise OdkError(f"curriculum: nbins = {n[0] * n[1] * n[2]} (at most {CURR_MAX_BINS})")
     return n[0] * n[1] * n[2]
+
+
+# log replay (include/odk.h ODK_LOG_* / ODK_REPLAY_*): a table row of log_row(nu) floats -- command [7], action [nu], then the log_* offsets
+# below -- and odk_replay_accumulate's slots, REPLAY_NSLOT per lane of [nenv, 16, REPLAY_NSLOT]
+LOG_COMMAND, LOG_ACTION = 0, 7
+REPLAY_NSLOT = 8
+(REPLAY_POS_ERR_SUM, REPLAY_POS_ERR_SQ, REPLAY_VEL_ERR_SQ, REPLAY_POS_ERR_PEAK, REPLAY_GYRO_ERR_SQ, REPLAY_ACCEL_ERR_SQ, REPLAY_CONTACT_AGREE,
+ REPLAY_SAMPLES) = range(8)
+
+
+def log_row(nu: int) -> int:
+    """ODK_LOG_ROW(nu): the floats of a row of the replay table."""
+    return 15 + 3 * int(nu)
+
+
+def log_offsets(nu: int) -> Dict[str, int]:
+    """Where the fields of a table row start (include/odk.h "Log replay")."""
+    nu = int(nu)
+    return {"command": LOG_COMMAND, "action": LOG_ACTION, "pos": 7 + nu, "vel": 7 + 2 * nu, "gyro": 7 + 3 * nu, "accel": 10 + 3 * nu,
+            "contact": 13 + 3 * nu}
+
+
+def check_log_table(name: str, log, nu: int, device: int) -> int:
+    """The table argument of `Batch.log_apply` / `Batch.replay_accumulate`: a contiguous float32 [nrow >= 1, log_row(nu)] tensor on
+    cuda:`device`; OdkError otherwise.  Returns nrow."""
+    _check_tensor(f"{name}: log", log, "float32", device, f"(nrow >= 1, {log_row(nu)})", lambda s: len(s) == 2 and s[0] >= 1 and s[1] == log_row(nu))
+    return int(log.shape[0])
 
 
 def sensor_rotation(roll_deg: float, pitch_deg: float, yaw_deg: float) -> np.ndarray:
@@ -1488,6 +1517,27 @@ class Batch:
         if int(cur.min_tries) < 1:
             raise OdkError(f"{fn}: min_tries = {int(cur.min_tries)} (at least 1)")
         _chk(self.L.odk_curriculum_update(self._b, C.byref(cur), _ptr(levels), _ptr(cdf), _ptr(counts), _ptr(stats), self._stream()))
+
+    def log_apply(self, log, track_acc, action):
+        """One `odk_log_apply` launch, issued BEFORE `step`: `action` ([nenv, nu] float32, what `step` is then given) and entries 0..6 of the
+        bound command tensor become the action and the command of row min(k, nrow - 1) of `log` ([nrow, log_row(nu)] float32), k the
+        first-episode step about to run (`track_acc`'s STEPS slot, `command_schedule_apply`'s clock).  Needs bound commands."""
+        nrow = check_log_table("log_apply", log, self.model.nu, self.device)
+        check_accumulator("log_apply: track_acc", track_acc, self.nenv, TRACK_NACC, self.device)
+        check_accumulator("log_apply: action", action, self.nenv, self.model.nu, self.device)
+        if self.commands is None:
+            raise OdkError("log_apply: no commands bound (bind_commands)")
+        _chk(self.L.odk_log_apply(self._b, _ptr(log), nrow, _ptr(track_acc), _ptr(action), self._stream()))
+
+    def replay_accumulate(self, acc, track_acc, log):
+        """One `odk_replay_accumulate` launch over this step's outputs into `acc` ([nenv, 16, REPLAY_NSLOT] float32, zeroed before the first
+        step), issued after `step` and BEFORE `tracking_accumulate(track_acc)`: the residuals of the step that just ran against its row of
+        `log`, the table `log_apply` took the step's action from.  Needs no bound commands."""
+        _check_tensor("replay_accumulate: acc", acc, "float32", self.device, f"({self.nenv}, 16, {REPLAY_NSLOT})",
+                      lambda s: s == (self.nenv, 16, REPLAY_NSLOT))
+        check_accumulator("replay_accumulate: track_acc", track_acc, self.nenv, TRACK_NACC, self.device)
+        nrow = check_log_table("replay_accumulate", log, self.model.nu, self.device)
+        _chk(self.L.odk_replay_accumulate(self._b, *_report_ptrs(self, track_acc), _ptr(log), nrow, _ptr(acc), self._stream()))
 
     def physics_step(self, ctrl, n_substeps: int = 10):
         assert ctrl.is_cuda and ctrl.dtype == self.torch.float32 and ctrl.is_contiguous() and tuple(ctrl.shape) == (self.nenv, self.model.nu)
