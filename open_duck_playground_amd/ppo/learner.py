@@ -10,7 +10,7 @@ element-wise ops, so under an autograd engine it is launch-bound.  Here one step
     partial sums of the gradient norm), clip + Adam (which also refreshes the packed weight copies the kernels read);
     data-parallel: an RCCL all-reduce of the flat gradient (and the norm in its own launch) before the clip + Adam.
 
-Other architectures (and ODK_LEARNER_FUSED=0) run the library path: one hipBLASLt GEMM per layer with the activation /
+Other architectures run the library path: one hipBLASLt GEMM per layer with the activation /
 bias-gradient kernels between them, policy and value networks as two parallel branches of the graph.
 
 Parameters live in ONE flat fp32 buffer (the modules' `.data` are views of it, so the rollout policy sees
@@ -22,6 +22,7 @@ from __future__ import annotations
 import os
 import weakref
 import tempfile
+from functools import partial
 from typing import Dict
 
 import torch
@@ -155,7 +156,7 @@ def tune_inference_shapes(net: PPONetworks, rows) -> None:
         _tunable(False)
 
 
-_FUSED_MLP = os.environ.get("ODK_LEARNER_FUSED", "1") == "1"   # whole-network forward / backward-data launches (csrc/odk_mlp.hip; 0: one library GEMM per layer)
+_FUSED_MLP = True   # whole-network forward / backward-data launches (csrc/odk_mlp.hip); tests set it False: one library GEMM per layer
 
 
 class _FlatMLP:
@@ -242,8 +243,41 @@ class _FlatMLP:
         self.fold()
 
 
+def _fork_join(side, on_current, on_side):
+    """Library path: the policy and value networks are independent until the loss head, so their chains are two branches of the
+    captured graph -- `on_side` on the stream `side`, forked from the current stream and joined back into it around `on_current`."""
+    cur = torch.cuda.current_stream()
+    side.wait_stream(cur)
+    with torch.cuda.stream(side):
+        on_side()
+    on_current()
+    cur.wait_stream(side)
+
+
+def _gae_then_head(s, zp, vals, noise, vs, adv, stats, dlogits, dvalues, losses, cfg, grad_scale):
+    """Gathered forms: `odk_gae` over the static minibatch `s`, then the loss head (`odk_ppo_head`: the four losses and the gradients
+    w.r.t. the logits `zp` and the values).  `vals` [n + B]: the value network's output for the minibatch's rows, then its bootstrap rows."""
+    B, T = vs.shape
+    n = B * T
+    baseline, boot = vals[:n], vals[n:]
+    engine.gae(s["truncation"], s["termination"], s["reward"], baseline.view(B, T), boot, cfg["gae_lambda"], cfg["discounting"],
+               vs=vs, adv=adv, stats=stats)
+    engine.ppo_head(zp, s["raw_action"].view(n, -1), s["log_prob"].view(n), adv.view(n), stats if cfg["normalize_advantage"] else None,
+                    vs.view(n), baseline, noise, dlogits, dvalues, losses, cfg["clipping_epsilon"], cfg["entropy_cost"], grad_scale)
+
+
 class FlatLearner:
+    """The minibatch step in one of three forms, chosen once in `__init__` from the networks' shapes and the minibatch's size; each form
+    is the list of launches `_loss_and_grads` runs (`_launches`) plus the clip + Adam launch of `_update`:
+
+        indexed + fused network kernels (the reference configuration), gathered + fused (minibatches past the limits below),
+        gathered + library GEMMs (other architectures, minibatches of fewer than 128 rows)."""
     KEYS = ("obs", "priv", "raw_action", "log_prob", "reward", "termination", "truncation")
+    # the indexed form's limits are `odk_ppo_gae_head`'s (csrc/odk_learner.hip refuses B * T > 5120, its LDS staging, and B > 1024, its
+    # trajectory-number table): larger minibatches run the gathered form
+    INDEXED_MAX_ROWS, INDEXED_MAX_TRAJ = 5120, 1024
+    STEPS_PER_GRAPH = 32   # indexed form: consecutive minibatch steps captured as one graph (`_capture`)
+    NOISE_POOL = 128       # minibatch steps per noise refill (= steps per training step in the reference configuration)
 
     def __init__(self, net: PPONetworks, cfg: Dict, B: int, T: int, world: int = 1, group=None, use_graph: bool = True,
                  split_update=None, fused_norm: bool = True, capture_allreduce=None, n_traj: int = None):
@@ -275,28 +309,31 @@ class FlatLearner:
         z = lambda *s: torch.zeros(*s, device=dev)
         self.vs, self.adv, self.stats = z(B, T), z(B, T), z(2)
         self.dlogits, self.dval_all = z(n, 2 * A), z(n + B, 1)
+        self.losses = z(4)                          # running SUMS of (total, policy, value, entropy) over the steps since metrics()
         fused = self.policy.fused_ok() and self.value.fused_ok() and n >= 128   # (the weight-gradient launch wants >= 8 rows per slice)
         self.split_update = world > 1 if split_update is None else bool(split_update)
         if capture_allreduce is None:
             capture_allreduce = os.environ.get("ODK_LEARNER_CAPTURE_ALLREDUCE") == "1"
         self.capture_allreduce = bool(capture_allreduce) and self.split_update and use_graph and (world > 1 or group is not None)
+        self._fused_norm, self._n_par = fused_norm, n_par
+        self.fused = self.gae_head = None
         # INDEXED form of the step (round 5): no gathered copy of the minibatch exists.  The rollout stays resident (`self.roll`), the
         # training step's whole shuffle is a device array of trajectory indices (`self.sched`, one B-slice per minibatch step) with a
         # device-side cursor that the clip + Adam launch advances, the entropy noise of all steps sits in a pool indexed by the same
         # cursor: the forward launch and the fused GAE + head launch read their rows THROUGH the indices, and 128 minibatch steps are
         # 128 graph replays with nothing between them.  (Minibatches beyond the fused GAE + head launch's LDS: the gathered form.)
-        self.indexed = fused and n <= 5120 and B <= 1024 and os.environ.get("ODK_LEARNER_INDEXED", "1") == "1"
+        self.indexed = fused and n <= self.INDEXED_MAX_ROWS and B <= self.INDEXED_MAX_TRAJ
         self._host_cursor, self._host_steps = 0, 0
+        self._adam_tail = {}                        # what the clip + Adam launch does for the indexed form besides the update
         if self.indexed:
             self.steps_cap = max(self.NOISE_POOL, int(cfg.get("num_minibatches", 1)) * int(cfg.get("num_updates_per_batch", 1)))
             self.sched = torch.zeros(self.steps_cap * B, dtype=torch.int64, device=dev)
             self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
             self._pool = z(self.steps_cap, n, A)
             self.loss_partials = z((n + engine.GAE_HEAD_SAMPLES - 1) // engine.GAE_HEAD_SAMPLES, 4)     # the head's per-workgroup sums, folded by the Adam launch
+            self._adam_tail = dict(cursor=self.cursor, loss_partials=self.loss_partials, losses=self.losses)
             self._alloc_rollout(int(n_traj) if n_traj else B * int(cfg.get("num_minibatches", 1)), od, pd, A)
-            rows = dict(row_idx=self.sched, cursor=self.cursor, traj_len=T, n_main=n, n_traj=self.cap)
-            self.policy.bind(self.roll["obs"].view(self.cap * T, od), self.dlogits, True, n, rows)
-            self.value.bind(self.roll["priv"].view(self.cap * T, pd), self.dval_all, True, n + B, dict(rows, x_tail=self.roll["last_priv"]))
+            self._bind_indexed()
         else:
             self.priv_all = z(n + B, pd)                # minibatch privileged obs, then the bootstrap rows
             self.static = dict(obs=z(B, T, od), priv=self.priv_all[:n].view(B, T, pd), last_priv=self.priv_all[n:], raw_action=z(B, T, A),
@@ -304,31 +341,45 @@ class FlatLearner:
             self._noise = z(n, A)
             self.policy.bind(self.static["obs"].view(n, -1), self.dlogits, fused)
             self.value.bind(self.priv_all, self.dval_all, fused)
-        # whole-network launches (csrc/odk_mlp.hip): forward of both networks = 1 launch, backward-data of both = 1 launch, the
-        # weight gradients of all 8 layers = 1 + its finishing launch; the kernels read the weights from packed copies (16-byte
-        # pieces along the reduction index) that the Adam launch keeps current
-        self.fused = None
-        self._fused_norm = fused_norm
-        if fused:
-            self._n_par = n_par
-            self._build_fused()
-            self.sync_weights()
-        self.losses = z(4)                          # running SUMS of (total, policy, value, entropy) over the steps since metrics()
-        self.gae_head = None
-        if self.indexed:
-            self.gae_head = engine.GaeHead(self.policy.zs[-1], self.value.zs[-1].view(-1), self.roll, self._pool, self.sched, self.cursor, self.dlogits,
-                                           self.dval_all.view(-1), self.losses, B, T, cfg, 1.0 / self.world, adv=self.adv.view(-1), vs=self.vs.view(-1),
-                                           stats=self.stats, loss_partials=self.loss_partials)
+            head = partial(_gae_then_head, self.static, self.policy.zs[-1], self.value.zs[-1].view(-1), self._noise, self.vs, self.adv, self.stats,
+                           self.dlogits, self.dval_all[:n].view(n), self.losses, cfg, 1.0 / world)
+            if fused:                                   # forward -> GAE, loss head -> backward-data -> weight gradients
+                self._build_fused()
+                self._launches = [self.fused.forward, head, self.fused.backward, self.dw_all]
+            else:                                       # library path: the weight-gradient GEMMs sit inside each network's backward chain
+                side = torch.cuda.Stream()
+                self._launches = [partial(_fork_join, side, self.policy.forward, self.value.forward), head,
+                                  partial(_fork_join, side, self.policy.backward, self.value.backward)]
+        self.sync_weights()
+        # what a step moves and the capture's warm-up steps put back (the losses start again from zero instead)
+        self._step_state = [self.flat_p, self.m, self.v, self.acc] + ([self.cursor] if self.indexed else [])
         self.nsteps = 0
         self.graph_a = self.graph_b = self.graph_k = None
+        k_graph = self.indexed and use_graph and self.STEPS_PER_GRAPH > 1 and (not self.split_update or self.capture_allreduce)
+        self.K = self.STEPS_PER_GRAPH if k_graph else 0     # steps of `graph_k` (`_capture`); 0: none
         self._gather = None; self._gather_src = ()
-        self.side = torch.cuda.Stream() if (not fused and os.environ.get("ODK_LEARNER_BRANCHES", "1") == "1") else None   # library path: policy || value
         self.sample_noise = True                    # plain-launch path only: tests inject self.noise instead
         self._gpool, self._pool_k = None, 0
         if use_graph:
             self._capture()
 
+    def _bind_indexed(self):
+        """The indexed form's descriptors over the resident rollout: in `__init__`, and again when `_fit_rollout` has replaced it."""
+        B, T, n, r = self.B, self.T, self.B * self.T, self.roll
+        rows = dict(row_idx=self.sched, cursor=self.cursor, traj_len=T, n_main=n, n_traj=self.cap)
+        self.policy.bind(r["obs"].view(self.cap * T, -1), self.dlogits, True, n, rows)
+        self.value.bind(r["priv"].view(self.cap * T, -1), self.dval_all, True, n + B, dict(rows, x_tail=r["last_priv"]))
+        self._build_fused()
+        self.gae_head = engine.GaeHead(self.policy.zs[-1], self.value.zs[-1].view(-1), r, self._pool, self.sched, self.cursor, self.dlogits,
+                                       self.dval_all.view(-1), self.losses, B, T, self.cfg, 1.0 / self.world, adv=self.adv.view(-1),
+                                       vs=self.vs.view(-1), stats=self.stats, loss_partials=self.loss_partials)
+        # rows through the schedule (no gathered copy) -> GAE + advantage statistics + loss head, one launch -> backward-data -> weight gradients
+        self._launches = [self.fused.forward, self.gae_head, self.fused.backward, self.dw_all]
+
     def _build_fused(self):
+        """Whole-network launches (csrc/odk_mlp.hip): forward of both networks = 1 launch, backward-data of both = 1 launch, the weight
+        gradients of all 8 layers = 1 + its finishing launch; the kernels read the weights from packed copies (16-byte pieces along
+        the reduction index) that the Adam launch keeps current."""
         dev = self.flat_p.device
         kslices = 8       # workspace slices of the weight-gradient launch (each folded from two waves inside the kernel)
         if getattr(self, "dw_ws", None) is None:
@@ -359,53 +410,9 @@ class FlatLearner:
     # ---- the step, as plain stream-ordered launches (captured below) ----
     @torch.no_grad()
     def _loss_and_grads(self):
-        B, T, n, cfg = self.B, self.T, self.B * self.T, self.cfg
-        if self.indexed:
-            self.fused.forward()          # rows through the schedule: no gathered copy
-            self.gae_head()               # GAE + advantage statistics + loss head, one launch
-            self.fused.backward()
-            self.dw_all()                 # weight gradients; its finishing launch: slice fold + bias gradients (+ the norm's partial sums)
-            return
-        s = self.static
-        if self.fused is not None:
-            self.fused.forward()
-            zp, vals = self.policy.zs[-1], self.value.zs[-1].view(-1)
-            baseline, boot = vals[:n], vals[n:]
-            engine.gae(s["truncation"], s["termination"], s["reward"], baseline.view(B, T), boot, cfg["gae_lambda"], cfg["discounting"],
-                       vs=self.vs, adv=self.adv, stats=self.stats)
-            engine.ppo_head(zp, s["raw_action"].view(n, -1), s["log_prob"].view(n), self.adv.view(n),
-                            self.stats if cfg["normalize_advantage"] else None, self.vs.view(n), baseline, self.noise, self.dlogits,
-                            self.dval_all[:n].view(n), self.losses, cfg["clipping_epsilon"], cfg["entropy_cost"], 1.0 / self.world)
-            self.fused.backward()
-            self.dw_all()     # weight gradients; its finishing launch: slice fold + bias gradients (+ the norm's partial sums)
-            return
-        # policy and value networks are independent until the loss head: two branches of the captured graph
-        cur = torch.cuda.current_stream()
-        if self.side is not None:
-            self.side.wait_stream(cur)
-            with torch.cuda.stream(self.side):
-                zv = self.value.forward()
-            zp = self.policy.forward()
-            cur.wait_stream(self.side)
-        else:
-            zp = self.policy.forward()
-            zv = self.value.forward()
-        vals = zv.view(-1)
-        baseline, boot = vals[:n], vals[n:]
-        engine.gae(s["truncation"], s["termination"], s["reward"], baseline.view(B, T), boot, cfg["gae_lambda"], cfg["discounting"],
-                   vs=self.vs, adv=self.adv, stats=self.stats)
-        engine.ppo_head(zp, s["raw_action"].view(n, -1), s["log_prob"].view(n), self.adv.view(n),
-                        self.stats if cfg["normalize_advantage"] else None, self.vs.view(n), baseline, self.noise, self.dlogits,
-                        self.dval_all[:n].view(n), self.losses, cfg["clipping_epsilon"], cfg["entropy_cost"], 1.0 / self.world)
-        if self.side is not None:
-            self.side.wait_stream(cur)
-            with torch.cuda.stream(self.side):
-                self.value.backward()
-            self.policy.backward()
-            cur.wait_stream(self.side)
-        else:
-            self.policy.backward()
-            self.value.backward()
+        """Forward of both networks -> GAE + loss head -> backward-data + weight gradients: the launches of this learner's form."""
+        for launch in self._launches:
+            launch()
 
     @torch.no_grad()
     def _draw_noise(self):
@@ -436,15 +443,10 @@ class FlatLearner:
         had_graph = self.graph_a is not None
         self.graph_a = self.graph_b = self.graph_k = None
         self._alloc_rollout(N, od, pd, A)
-        n, B, T = self.B * self.T, self.B, self.T
-        rows = dict(row_idx=self.sched, cursor=self.cursor, traj_len=T, n_main=n, n_traj=self.cap)
-        self.policy.bind(self.roll["obs"].view(self.cap * T, od), self.dlogits, True, n, rows)
-        self.value.bind(self.roll["priv"].view(self.cap * T, pd), self.dval_all, True, n + B, dict(rows, x_tail=self.roll["last_priv"]))
-        self._build_fused()
-        self.gae_head = engine.GaeHead(self.policy.zs[-1], self.value.zs[-1].view(-1), self.roll, self._pool, self.sched, self.cursor, self.dlogits,
-                                       self.dval_all.view(-1), self.losses, B, T, self.cfg, 1.0 / self.world, adv=self.adv.view(-1), vs=self.vs.view(-1),
-                                       stats=self.stats, loss_partials=self.loss_partials)
+        self._bind_indexed()
         if had_graph:
+            self.cursor.zero_()                     # (the new graphs start at the head of the schedule, like the first ones)
+            self._host_cursor = 0
             self._capture()
 
     @torch.no_grad()
@@ -463,14 +465,12 @@ class FlatLearner:
             # collectives a replay issues: every rank must make the same choice, i.e. hold the same (K, schedule length).  One tiny all-reduce per
             # schedule (one per training step) -- a mismatch would otherwise show up as a hang inside a captured collective.
             import torch.distributed as dist
-            mine = torch.tensor([float(getattr(self, "K", 0)), float(steps)], device=self.sched.device)
+            mine = torch.tensor([float(self.K), float(steps)], device=self.sched.device)
             lo, hi = mine.clone(), mine.clone()
             dist.all_reduce(lo, op=dist.ReduceOp.MIN, group=self.group); dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=self.group)
             if not (torch.equal(lo, mine) and torch.equal(hi, mine)):
                 raise engine.OdkError(f"FlatLearner (captured all-reduce): ranks disagree on (steps per graph, schedule length): mine {mine.tolist()}, "
                                       f"min {lo.tolist()}, max {hi.tolist()}")
-
-    NOISE_POOL = 128   # minibatch steps per refill (= steps per training step in the reference configuration)
 
     @torch.no_grad()
     def _noise_block(self):
@@ -491,11 +491,10 @@ class FlatLearner:
 
     @torch.no_grad()
     def _update(self):
-        if self.fused is not None:
+        if self.fused is not None:                  # (indexed form: the launch also advances the cursor and folds the head's loss sums)
             engine.adam_clip_packed(self.flat_p, self.flat_g, self.m, self.v, self.acc, self.packed_f, self.packed_b, self.wtable,
                                     self.cfg["learning_rate"], self.cfg.get("max_grad_norm") or 0.0, norm_blocks=self.dw_all.norm_blocks,
-                                    cursor=self.cursor if self.indexed else None, loss_partials=self.loss_partials if self.indexed else None,
-                                    losses=self.losses if self.indexed else None)
+                                    **self._adam_tail)
         else:
             engine.adam_clip(self.flat_p, self.flat_g, self.m, self.v, self.acc, self.cfg["learning_rate"], self.cfg.get("max_grad_norm") or 0.0)
 
@@ -507,7 +506,7 @@ class FlatLearner:
             engine.pack_weights(self.flat_p, self.packed_f, self.packed_b, self.wtable)
 
     def _capture(self):
-        keep = [t.clone() for t in (self.flat_p, self.m, self.v, self.acc)]
+        keep = [t.clone() for t in self._step_state]
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         # (no library GEMM is captured on the whole-network path: leave PyTorch's process-wide TunableOp switch alone there)
@@ -522,13 +521,10 @@ class FlatLearner:
         torch.cuda.current_stream().wait_stream(side)
         if tuned:
             _tunable(False)                         # keep the selected kernels, never tune inside a capture
-        for t, k in zip((self.flat_p, self.m, self.v, self.acc), keep):
-            t.copy_(k)                              # the warm-up steps must not train
+        for t, k in zip(self._step_state, keep):
+            t.copy_(k)                              # the warm-up steps must not train (nor, indexed form, advance the cursor)
         self.sync_weights()
         self.losses.zero_()
-        if self.indexed:
-            self.cursor.zero_()                     # (the warm-up steps advanced it)
-            self._host_cursor = 0
         # With a live process group its watchdog thread polls events while collectives are outstanding; under the default (global) capture
         # mode such a query from ANOTHER thread aborts the capture ("operation not permitted when stream is capturing": seen on the
         # one-rank RCCL group once 33 steps were captured instead of one).  So: nothing outstanding when the capture starts, and the
@@ -549,12 +545,10 @@ class FlatLearner:
                 self._update()
         # K consecutive steps as ONE graph (indexed form: every step's launches are the same nodes -- the cursor moves on the device): a
         # replay per step left ~8 us of idle GPU between two graphs (the gather launch used to sit there), K = 32 leaves none
-        self.graph_k, self.K = None, 0
-        K = int(os.environ.get("ODK_LEARNER_STEPS_PER_GRAPH", "32"))
-        if self.indexed and K > 1 and (not self.split_update or self.capture_allreduce):
-            self.graph_k, self.K = torch.cuda.CUDAGraph(), K
+        if self.K:
+            self.graph_k = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph_k, **cap):
-                for _ in range(K):
+                for _ in range(self.K):
                     self._loss_and_grads()
                     if self.capture_allreduce:
                         import torch.distributed as dist
@@ -603,16 +597,13 @@ class FlatLearner:
     def step(self):
         """One clipped-Adam step on the loaded minibatch.  The loss head ADDS this step's (total, policy, value, entropy)
         to `self.losses` (no sync); `metrics()` turns the sums into means."""
-        if self.indexed:
-            if self._host_cursor >= self._host_steps:
-                raise engine.OdkError("FlatLearner.step: the schedule is used up (load_minibatch / set_schedule first)")
-            if self.graph_a is None and self.sample_noise:
-                self._draw_noise()                     # (before the cursor's host mirror moves: `noise` is the slot under it)
+        if self.indexed and self._host_cursor >= self._host_steps:
+            raise engine.OdkError("FlatLearner.step: the schedule is used up (load_minibatch / set_schedule first)")
         if self.graph_a is not None:
-            self.graph_a.replay()                       # (its entropy noise came with load_minibatch)
+            self.graph_a.replay()                       # (its entropy noise came with load_minibatch / set_schedule)
         else:
-            if self.sample_noise and not self.indexed:
-                self._draw_noise()
+            if self.sample_noise:
+                self._draw_noise()                      # (before the cursor's host mirror moves below: `noise` is the slot under it)
             self._loss_and_grads()
             if not self.split_update:
                 self._update()
@@ -628,8 +619,7 @@ class FlatLearner:
             else:
                 self._update()
         self.nsteps += 1
-        if self.indexed:
-            self._host_cursor += 1
+        self._host_cursor += 1                          # (read by the indexed form only: the gathered form has no schedule to run out)
         if _DEBUG_NONFINITE:
             self._debug_check()
         return self.losses

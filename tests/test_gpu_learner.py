@@ -144,12 +144,16 @@ def test_fused_mlp_two_networks_one_launch_and_adam_keeps_the_packed_copies():
     assert torch.equal(table.fwd_view(pf, 1), _packed_reference(p2[4160:4160 + 840].view(40, 21).t()))
 
 
-@pytest.mark.parametrize("normalize_advantage, N, fused", [(True, 64, True), (False, 64, True), (True, 1024, True), (True, 64, False),
-                                                          (True, 64, None)])
-def test_flat_learner_gradients_match_autograd(normalize_advantage, N, fused, monkeypatch):
+@pytest.mark.parametrize("normalize_advantage, N, Tn, fused", [(True, 64, 20, True), (False, 64, 20, True), (True, 1024, 20, True), (True, 64, 20, False),
+                                                              (True, 64, 20, None), (True, 64, 321, True), (True, 4100, 4, True)],
+                         ids=["True-64-True", "False-64-True", "True-1024-True", "True-64-False", "True-64-None",      # (Tn = 20 is not part of an id)
+                              "True-64-T321-True", "True-4100-T4-True"])
+def test_flat_learner_gradients_match_autograd(normalize_advantage, N, Tn, fused, monkeypatch):
     """loss scalars and every parameter gradient of the captured step == autograd of ppo_loss (same entropy noise): on the
     whole-network kernels (csrc/odk_mlp.hip; N = 1024: the reference minibatch, 256 x 20 rows), on the library path (one GEMM
-    per layer: `fused` false), and for an architecture the fused kernels are not built for (`fused` None: falls back)."""
+    per layer: `fused` false), and for an architecture the fused kernels are not built for (`fused` None: falls back).  The last
+    two cases each cross ONE limit of the indexed form (odk_ppo_gae_head's) and so run gathered + fused: 16 x 321 = 5136 > 5120
+    rows of 16 <= 1024 trajectories; 1025 > 1024 trajectories in 1025 x 4 = 4100 <= 5120 rows."""
     from open_duck_playground_amd.ppo import learner as LM
     from open_duck_playground_amd.ppo import train as T
     from open_duck_playground_amd.ppo.learner import FlatLearner, prepare_rollout
@@ -160,7 +164,7 @@ def test_flat_learner_gradients_match_autograd(normalize_advantage, N, fused, mo
         monkeypatch.setattr(LM, "_FUSED_MLP", False)
     net = (PPONetworks(101, 212, 14) if fused is not None else PPONetworks(101, 212, 14, policy_hidden=(256, 128), value_hidden=(256, 256, 64))).to(dev)
     cfg = T.ppo_config(); cfg["normalize_advantage"] = normalize_advantage
-    Tn, nmb = 20, 4
+    nmb = 4
     data = _fake_rollout(N, Tn, dev)
     net.norm_obs.update(data["obs"]); net.norm_priv.update(data["priv"])
     ref = copy.deepcopy(net)
@@ -168,6 +172,7 @@ def test_flat_learner_gradients_match_autograd(normalize_advantage, N, fused, mo
     idx = torch.arange(3, 3 + N // nmb, device=dev)
     lr.load_minibatch(prepare_rollout(net, data, cfg), idx)
     assert (lr.fused is not None) == (fused is True)            # the reference architecture runs on the fused network kernels
+    assert lr.indexed == (fused is True and (N // nmb) * Tn <= 5120 and N // nmb <= 1024)   # (the kernel's limits, in numbers)
     lr._draw_noise(); lr._loss_and_grads()
     mb = {k: v[idx] for k, v in data.items()}
     mb["noise"] = lr.noise.view(N // nmb, Tn, 14).clone()
@@ -199,8 +204,8 @@ def test_indexed_step_equals_the_gathered_step(monkeypatch):
     N, Tn = 64, 20
     data = _fake_rollout(N, Tn, dev, seed=9)
     nets, lrs = [], []
-    for indexed in ("1", "0"):
-        monkeypatch.setenv("ODK_LEARNER_INDEXED", indexed)
+    for max_rows in (FlatLearner.INDEXED_MAX_ROWS, 0):              # the indexed form, then (no minibatch within the limit) the gathered one
+        monkeypatch.setattr(FlatLearner, "INDEXED_MAX_ROWS", max_rows)
         torch.manual_seed(4)
         n = PPONetworks(101, 212, 14).to(dev)
         n.norm_obs.update(data["obs"]); n.norm_priv.update(data["priv"])
@@ -238,8 +243,8 @@ def test_indexed_step_equals_the_gathered_step(monkeypatch):
     a.load_minibatch(prep, bad)
     a._loss_and_grads()
     assert not torch.isfinite(a.last_step_losses()).all()
-    # K steps as one graph: `run` == the same steps one by one (two fresh learners, K = 4 through the environment)
-    monkeypatch.setenv("ODK_LEARNER_INDEXED", "1"); monkeypatch.setenv("ODK_LEARNER_STEPS_PER_GRAPH", "4")
+    # K steps as one graph: `run` == the same steps one by one (two fresh learners, K = 4 through the class constant)
+    monkeypatch.undo(); monkeypatch.setattr(FlatLearner, "STEPS_PER_GRAPH", 4)
     pair = []
     for _ in range(2):
         torch.manual_seed(4)

@@ -389,8 +389,8 @@ def test_indexed_step_equals_the_gathered_step_at_sixteen_actions(monkeypatch):
     N, Tn = 64, 20
     data = _fake_rollout(N, Tn, dev, obs, priv, A, seed=9)
     nets, lrs = [], []
-    for indexed in ("1", "0"):
-        monkeypatch.setenv("ODK_LEARNER_INDEXED", indexed)
+    for max_rows in (FlatLearner.INDEXED_MAX_ROWS, 0):              # the indexed form, then (no minibatch within the limit) the gathered one
+        monkeypatch.setattr(FlatLearner, "INDEXED_MAX_ROWS", max_rows)
         torch.manual_seed(4)
         n = PPONetworks(obs, priv, A).to(dev)
         n.norm_obs.update(data["obs"]); n.norm_priv.update(data["priv"])
