@@ -10,6 +10,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import os
+import re
 import subprocess
 from typing import Dict, List, Optional
 
@@ -19,19 +20,94 @@ from .model import Model, asset_path
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("ODK_LIB", os.path.join(_CSRC, "libodk.so"))  # ODK_LIB: e.g. the -DODK_PROFILE build
+POISON_LIB_PATH = os.path.join(_CSRC, "libodk_poison.so")   # the -DODK_POISON_LDS build (csrc/odk_poison.h): load it through ODK_LIB
 
-NOBS, NPRIV, NMETRIC, NU = 101, 212, 8, 14      # the duck's sizes; a Batch reports its model's own (nobs, npriv, model.nu)
-ADAM_ACC_FLOATS = 2 + 1024   # ODK_ADAM_ACC_FLOATS (include/odk.h)
+
+class OdkError(RuntimeError):
+    pass
+
+
+class OdkValueError(OdkError, ValueError):
+    """An argument refused before any launch (`check_action_delays`): an OdkError that `except ValueError` catches too."""
+
+
+def library_sources() -> list:
+    """The files a library in csrc/ is built from (what build_library and the poison tests call stale against)."""
+    srcs = [os.path.join(_CSRC, f) for f in sorted(os.listdir(_CSRC)) if f.endswith((".hip", ".h", ".inc")) or f == "Makefile"]
+    srcs.append(os.path.join(_CSRC, "..", "..", "include", "odk.h"))
+    return srcs
+
+
+_FLOAT = r"(?:\d+\.\d*|\.\d+)(?:[eE][+-]?\d+)?|\d+[eE][+-]?\d+"
+_TOKEN = re.compile(rf"\s*(?:({_FLOAT})f?(?![\w.])|(\d+)(?![\w.])|(ODK_\w+)|([-+*()]))")
+
+
+def header_constants(text: Optional[str] = None) -> Dict[str, object]:
+    """name (without ODK_) -> int or float of every constant include/odk.h (or `text`) gives a value: object-like `#define ODK_NAME body`
+    and enum entries `ODK_NAME = body`, in the order they stand.  A body is made of integer and float literals (a trailing f allowed),
+    ODK_ names defined before it, + - * and parentheses: all integers give an int, anything else a float.  A define without a body and a
+    function-like macro are skipped; a name given a value twice, a name used before its definition, any other character or operator and
+    an enum entry without `= value` are an OdkError that names the constant."""
+    if text is None:
+        path = os.path.normpath(library_sources()[-1])
+        try:
+            with open(path) as f:
+                text = f.read()
+        except OSError as e:
+            raise OdkError(f"{path}: cannot read the header ({e.strerror})")
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    vals: Dict[str, object] = {}
+
+    def give(name: str, body: str) -> None:
+        if name[4:] in vals:
+            raise OdkError(f"{name}: given a value twice")
+        expr, at = "", 0
+        while body[at:].strip():
+            m = _TOKEN.match(body, at)
+            if not m:
+                raise OdkError(f"{name}: cannot read '{body.strip()}' at '{body[at:].strip()}' (literals, earlier ODK_ names, + - * and parentheses only)")
+            flt, integer, ref, op = m.groups()
+            if ref and ref[4:] not in vals:
+                raise OdkError(f"{name}: refers to {ref}, which is not defined before it")
+            expr += f"({vals[ref[4:]]!r})" if ref else flt or integer or op
+            at = m.end()
+        try:
+            v = eval(expr, {"__builtins__": {}})       # expr: nothing but the tokens checked above
+        except (SyntaxError, TypeError):
+            v = None
+        if type(v) not in (int, float):
+            raise OdkError(f"{name}: '{body.strip()}' is not an expression")
+        vals[name[4:]] = v
+
+    for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(ODK_\w+)(.*)$|\benum\b[^{;]*\{([^}]*)\}", text, re.M):
+        name, body, block = m.groups()
+        if name:
+            if body.strip() and not body.startswith("("):      # neither `#define ODK_H` nor `#define ODK_LOG_ROW(nu) ...`
+                give(name, body)
+            continue
+        for entry in filter(None, (e.strip() for e in block.split(","))):
+            name, eq, body = (s.strip() for s in entry.partition("="))
+            if not re.fullmatch(r"ODK_\w+", name) or not body:
+                raise OdkError(f"{name or entry}: an enum entry must read `ODK_NAME = value`, got '{entry}'")
+            give(name, body)
+    return vals
+
+
+# Every constant of include/odk.h -- sizes, strides, accumulator slots, status codes -- as a module global under its name without ODK_
+# (GAIT_NACC, SENSOR_NSTATE, ERR_INVALID ...): the header is their one definition, and a new slot is an enum entry there and nothing else.
+_HEADER = header_constants()
+globals().update(_HEADER)
+
+# What the header does not say.
+NCOMMAND = 7    # lin_vel_x, lin_vel_y, ang_vel_yaw, neck_pitch, head_pitch, head_yaw, head_roll
+MLP_HIDDEN = (MLP_H1, MLP_H2, MLP_H3)     # the hidden widths the fused network kernels are built for
+MLP_MAX_OUT = 32
+CURR_STREAM0 = 128      # draw k of a stint comes from stream CURR_STREAM0 + k of the action stage's hash (the fault rows' end at 127)
 METRIC_NAMES = ("reward/tracking_lin_vel", "reward/tracking_ang_vel", "cost/torques", "cost/action_rate", "cost/stand_still",
                 "reward/alive", "reward/imitation", "swing_peak")
-
-# reward-library terms of the step kernel (include/odk.h odk_xterm): scale keys of reward_config.scales, in column order of Batch.xmetrics;
+# reward-library terms of the step kernel (enum odk_xterm): scale keys of reward_config.scales, in column order of Batch.xmetrics;
 # each is the function of the same name in reference playground/common/rewards.py (cost_* / reward_*)
-XTERM_NAMES = ("lin_vel_z", "ang_vel_xy", "orientation", "base_height", "energy", "joint_pos_limits", "termination", "pose", "feet_slip",
-               "feet_clearance", "feet_height", "feet_air_time")
-NXTERM = len(XTERM_NAMES)
-
-PARAM_BODY_MASS, PARAM_BODY_IPOS_TORSO, PARAM_DOF_FRICTIONLOSS, PARAM_DOF_ARMATURE, PARAM_QPOS0, PARAM_KP = range(6)
+XTERM_NAMES = tuple(k[6:].lower() for k in sorted((k for k in _HEADER if k.startswith("XTERM_")), key=_HEADER.get))
 
 
 class EnvConfig(C.Structure):
@@ -81,9 +157,6 @@ class StepTail(C.Structure):
     _fields_ = [("cursor_dev", C.c_void_p), ("loss_partials_dev", C.c_void_p), ("n_loss_partials", C.c_int), ("losses_dev", C.c_void_p)]
 
 
-GAE_HEAD_SAMPLES = 32     # ODK_GAE_HEAD_SAMPLES: samples per workgroup of odk_ppo_gae_head (= entries of its loss partials per 32 samples)
-
-
 class GaeHeadArgs(C.Structure):
     """odk_gae_head_args (include/odk.h)."""
     _fields_ = [(k, C.c_void_p) for k in ("logits", "values", "raw_action", "old_log_prob", "reward", "termination", "truncation", "noise", "row_idx", "cursor",
@@ -102,28 +175,6 @@ class WeightTableC(C.Structure):
     """odk_weight_table (include/odk.h)."""
     _fields_ = [("count", C.c_int), ("off", C.c_longlong * 8), ("rows", C.c_int * 8), ("cols", C.c_int * 8), ("fwd_off", C.c_longlong * 8),
                 ("bwd_off", C.c_longlong * 8)]
-
-
-MLP_HIDDEN = (512, 256, 128)     # ODK_MLP_H1..3: the hidden widths the fused network kernels are built for
-MLP_MAX_IN, MLP_MAX_OUT, MLP_TILE = 224, 32, 16
-
-
-class OdkError(RuntimeError):
-    pass
-
-
-class OdkValueError(OdkError, ValueError):
-    """An argument refused before any launch (`check_action_delays`): an OdkError that `except ValueError` catches too."""
-
-
-POISON_LIB_PATH = os.path.join(_CSRC, "libodk_poison.so")   # the -DODK_POISON_LDS build (csrc/odk_poison.h): load it through ODK_LIB
-
-
-def library_sources() -> list:
-    """The files a library in csrc/ is built from (what build_library and the poison tests call stale against)."""
-    srcs = [os.path.join(_CSRC, f) for f in sorted(os.listdir(_CSRC)) if f.endswith((".hip", ".h", ".inc")) or f == "Makefile"]
-    srcs.append(os.path.join(_CSRC, "..", "..", "include", "odk.h"))
-    return srcs
 
 
 def build_library(force: bool = False, poison: bool = False) -> str:
@@ -263,12 +314,6 @@ SIGNATURES = _signatures()
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
 
-# odk_tracking_accumulate's per-env slots (include/odk.h ODK_TRACK_*)
-TRACK_NACC = 12
-TRACK_ENDED, TRACK_STEPS, TRACK_SAMPLES, TRACK_FALLS, TRACK_REWARD, TRACK_SUM, TRACK_SQERR = 0, 1, 2, 3, 4, 5, 8
-NCOMMAND = 7    # lin_vel_x, lin_vel_y, ang_vel_yaw, neck_pitch, head_pitch, head_yaw, head_roll
-
-
 def _check_placement(name: str, t, dtype, device: int) -> None:
     """What every tensor argument's check ends with: the dtype, contiguous, on cuda:`device`."""
     if t.dtype != dtype:
@@ -295,76 +340,6 @@ def check_commands(cmd, nenv: int, device: int) -> None:
     _check_tensor("commands", cmd, "float32", device, f"({nenv}, {NCOMMAND})", lambda s: s == (int(nenv), NCOMMAND), " or None")
 
 
-# odk_push_accumulate's per-env slots (include/odk.h ODK_PUSH_*)
-PUSH_NACC = 10
-(PUSH_PUSHED, PUSH_PUSH_AT, PUSH_FELL, PUSH_STEPS_TO_FALL, PUSH_LAST_OFF, PUSH_PEAK_LIN_ERR, PUSH_PEAK_ANG_ERR, PUSH_PRE_LIN_ERR_SUM,
- PUSH_PRE_SAMPLES, PUSH_PRE_LIN_ERR_LOW) = range(10)
-
-
-# odk_gait_accumulate's per-env slots (include/odk.h ODK_GAIT_*): scalars, [2] = left / right foot, then per-actuator arrays GAIT_STRIDE apart
-GAIT_NACC = 144
-GAIT_STRIDE = 16
-(GAIT_SAMPLES, GAIT_SPEED_SUM, GAIT_ABS_POWER_SUM, GAIT_CONTACT, GAIT_DOUBLE, GAIT_FLIGHT, GAIT_TOUCHDOWNS, GAIT_SWING_STEPS_SUM, GAIT_SLIP_SUM,
- GAIT_HEIGHT_SUM, GAIT_HEIGHT_SQ_SUM, GAIT_ROLLPITCH_RATE_SQ_SUM, GAIT_ACTION_RATE_SUM, GAIT_PREV_CONTACT, GAIT_AIR_RUN) = (
-    0, 1, 2, 3, 5, 6, 7, 9, 11, 13, 14, 15, 16, 17, 19)
-GAIT_TORQUE_SQ, GAIT_TORQUE_PEAK, GAIT_VEL_PEAK, GAIT_SAT, GAIT_ABS_POWER, GAIT_RANGE_MIN, GAIT_RANGE_MAX = 32, 48, 64, 80, 96, 112, 128
-
-
-# odk_posture_accumulate's per-env slots (include/odk.h ODK_POSTURE_*): scalars, then per-slot arrays of 4 (neck_pitch, head_pitch, head_yaw, head_roll)
-POSTURE_NACC = 32
-(POSTURE_SAMPLES, POSTURE_DRIFT_SPEED_SUM, POSTURE_YAW_RATE_SQ_SUM, POSTURE_ROLLPITCH_RATE_SQ_SUM, POSTURE_TILT_SUM, POSTURE_TILT_PEAK,
- POSTURE_HEIGHT_SUM, POSTURE_LEG_POSE_SUM, POSTURE_LEG_VEL_SUM, POSTURE_HEAD_SQERR_SUM) = range(10)
-POSTURE_ANGLE_SUM, POSTURE_ERR_SQ_SUM, POSTURE_ERR_PEAK, POSTURE_LAST_OFF = 16, 20, 24, 28
-
-# odk_imitation_accumulate's per-env slots (include/odk.h ODK_IMIT_*): scalars ([2] = left, right foot), then per-actuator arrays, entry u at SLOT + u
-IMIT_NACC = 160
-IMIT_STRIDE = 16
-IMIT_SAMPLES, IMIT_GATED, IMIT_SPEED_ERR_SQ_SUM, IMIT_REF_SPEED_SUM, IMIT_JOINT_POS_SQ_SUM, IMIT_JOINT_VEL_SQ_SUM = range(6)
-(IMIT_BOTH, IMIT_ROBOT_ONLY, IMIT_REF_ONLY, IMIT_REF_TOUCHDOWNS, IMIT_TOUCHDOWNS, IMIT_LAG_SUM, IMIT_LAG_ABS_SUM, IMIT_PREV_CONTACT, IMIT_PREV_REF,
- IMIT_REF_AGE) = range(6, 26, 2)
-(IMIT_POS_ERR_SUM, IMIT_POS_ERR_SQ, IMIT_POS_ERR_PEAK, IMIT_VEL_ERR_SQ, IMIT_RANGE_MIN, IMIT_RANGE_MAX, IMIT_REF_RANGE_MIN,
- IMIT_REF_RANGE_MAX) = range(32, 160, 16)
-
-# command schedules (include/odk.h ODK_SCHED_*): up to SCHED_MAX_SEGMENTS segments of SCHED_SEG_FLOATS floats (start_step, then the 7 command entries);
-# unused trailing segments start at SCHED_NEVER
-SCHED_MAX_SEGMENTS = 8
-SCHED_SEG_FLOATS = 8
-SCHED_NEVER = 1.0e9
-# odk_response_accumulate's slots (include/odk.h ODK_RESP_*): one block of RESP_STRIDE floats per segment, [3] = vx, vy, wz
-RESP_STRIDE = 24
-RESP_NACC = SCHED_MAX_SEGMENTS * RESP_STRIDE
-(RESP_ENTERED, RESP_SAMPLES, RESP_FELL, RESP_STEPS_TO_FALL, RESP_FIRST_IN, RESP_LAST_OFF, RESP_PEAK_LIN_ERR, RESP_PEAK_ANG_ERR) = range(8)
-RESP_SUM, RESP_SQERR, RESP_OVERSHOOT, RESP_TAIL_SAMPLES, RESP_TAIL_SUM = 8, 11, 14, 17, 18
-
-# odk_fall_accumulate's row (include/odk.h ODK_FALL_*): FALL_HEAD head floats, then a ring of slots of FALL_SAMPLE scalars + nq qpos floats;
-# [2] = left / right foot, [3] = x, y, z
-FALL_HEAD = 16
-FALL_SAMPLE = 16
-FALL_MAX_RING = 64
-FALL_SAMPLES, FALL_FELL, FALL_STEP, FALL_LAST_UPRIGHT, FALL_UPRIGHT_CONTACT, FALL_TILT_PEAK = 0, 1, 2, 3, 4, 6
-(FALL_S_STEP, FALL_S_UP, FALL_S_GYRO, FALL_S_LINVEL, FALL_S_HEIGHT, FALL_S_CONTACT, FALL_S_LIN_ERR, FALL_S_ANG_ERR, FALL_S_SAT) = (
-    0, 1, 4, 7, 10, 11, 13, 14, 15)
-
-# odk_path_begin / odk_path_accumulate's per-env slots (include/odk.h ODK_PATH_*): the start pose, the last sample's pose, the odometry sums,
-# then the course progress; a course row of the table is its count and PATH_MAX_WAYPOINTS points (x, y) in start-frame metres
-PATH_NACC = 32
-PATH_MAX_WAYPOINTS = 8
-PATH_COURSE_FLOATS = 1 + 2 * PATH_MAX_WAYPOINTS
-(PATH_START_X, PATH_START_Y, PATH_START_HX, PATH_START_HY, PATH_X, PATH_Y, PATH_HX, PATH_HY, PATH_LENGTH, PATH_TURN, PATH_SAMPLES, PATH_FELL,
- PATH_FELL_LEG, PATH_WP_INDEX, PATH_XTRACK_SAMPLES, PATH_XTRACK_SQ, PATH_XTRACK_PEAK, PATH_GOAL_DIST, PATH_REACHED) = range(19)
-
-# odk_sensor_apply's rows (include/odk.h ODK_SENSOR_*): a fault row of SENSOR_NPRM floats per env ([9] = row-major rotation, [3] = x, y, z,
-# [2] = left / right foot, [16] = per actuator), and a state row of SENSOR_NSTATE floats: the head, then a ring of SENSOR_RING raw samples
-# of SENSOR_SAMPLE floats (the SENSOR_S_* offsets inside one)
-SENSOR_NPRM = 48
-SENSOR_RING = 8
-SENSOR_SAMPLE = 48
-SENSOR_NSTATE = 16 + SENSOR_RING * SENSOR_SAMPLE
-(SENSOR_IMU_ROT, SENSOR_GYRO_SCALE, SENSOR_GYRO_BIAS, SENSOR_ACC_SCALE, SENSOR_ACC_BIAS, SENSOR_IMU_DELAY, SENSOR_JOINT_DELAY, SENSOR_ENC_QUANT,
- SENSOR_CONTACT_MODE, SENSOR_ENC_OFFSET) = 0, 9, 10, 13, 14, 17, 18, 19, 20, 32
-SENSOR_HEAD, SENSOR_RING_AT, SENSOR_S_IMU, SENSOR_S_JOINT_POS, SENSOR_S_JOINT_VEL = 0, 16, 0, 16, 32
-
-
 def sensor_fault_rows(n: int) -> np.ndarray:
     """[n, SENSOR_NPRM] float32 all-nominal fault rows to fill in: the identity rotation, both scales 1, zeros elsewhere.  `odk_sensor_apply`
     hands back the input's bits under such a row."""
@@ -372,14 +347,6 @@ def sensor_fault_rows(n: int) -> np.ndarray:
     rows[:, SENSOR_IMU_ROT:SENSOR_IMU_ROT + 9] = np.eye(3, dtype=np.float32).reshape(9)
     rows[:, SENSOR_GYRO_SCALE] = rows[:, SENSOR_ACC_SCALE] = 1.0
     return rows
-
-
-# odk_action_apply's rows (include/odk.h ODK_ACT_*): a fault row of ACT_NPRM floats per env, every entry in action units ([16] = per
-# actuator), and a state row of ACT_NSTATE floats: five scalars, the filter's state and the action last delivered
-ACT_NPRM = 48
-ACT_NSTATE = 48
-ACT_GAIN, ACT_NOISE, ACT_LIMIT, ACT_ALPHA, ACT_QUANT, ACT_DROP_P, ACT_DROP_LEN, ACT_SEED, ACT_OFFSET, ACT_FREEZE_AT = 0, 1, 2, 3, 4, 5, 6, 7, 16, 32
-ACT_HEAD, ACT_EPISODE, ACT_HOLD, ACT_CALLS, ACT_DROPS, ACT_FILT, ACT_PREV = 0, 1, 2, 3, 4, 16, 32
 
 
 def action_fault_rows(n: int) -> np.ndarray:
@@ -391,21 +358,6 @@ def action_fault_rows(n: int) -> np.ndarray:
     return rows
 
 
-# odk_fault_resample's rows (include/odk.h ODK_FAULT_*): the spec is [3, FAULT_NSLOT] (lo, hi, kind), slot s < SENSOR_NPRM the sensor row's
-# slot s, the others the actuation row's slot s - SENSOR_NPRM; a state row of FAULT_NSTATE floats: the calls and the redraws
-FAULT_NSLOT = SENSOR_NPRM + ACT_NPRM
-FAULT_NSTATE = 4
-FAULT_HEAD, FAULT_EPISODE = 0, 1
-FAULT_FIXED, FAULT_UNIFORM, FAULT_WHOLE = 0, 1, 2
-
-
-# the command curriculum (include/odk.h ODK_CURR_*): a state row of CURR_NSTATE floats per env, the four running totals of `stats`
-CURR_LMAX, CURR_MAX_AXIS, CURR_MAX_BINS, CURR_NSTATE = 5, 16, 4096, 8
-CURR_HEAD, CURR_EPISODE, CURR_STINT, CURR_STEP, CURR_BIN, CURR_SAMPLES, CURR_SQLIN, CURR_SQYAW = range(8)
-CURR_STAT_UPDATES, CURR_STAT_JUDGED, CURR_STAT_PROMOTED, CURR_STAT_TRIES = range(4)
-CURR_STREAM0 = 128      # draw k of a stint comes from stream CURR_STREAM0 + k of the action stage's hash (the fault rows' end at 127)
-
-
 def curriculum_nbins(cur) -> int:
     """The bin count of a `Curriculum`; OdkError, by name, for an axis outside 1 .. CURR_MAX_AXIS bins or more than CURR_MAX_BINS bins."""
     n = [int(v) for v in cur.n]
@@ -415,14 +367,6 @@ def curriculum_nbins(cur) -> int:
     if n[0] * n[1] * n[2] > CURR_MAX_BINS:
         raise OdkError(f"curriculum: nbins = {n[0] * n[1] * n[2]} (at most {CURR_MAX_BINS})")
     return n[0] * n[1] * n[2]
-
-
-# log replay (include/odk.h ODK_LOG_* / ODK_REPLAY_*): a table row of log_row(nu) floats -- command [7], action [nu], then the log_* offsets
-# below -- and odk_replay_accumulate's slots, REPLAY_NSLOT per lane of [nenv, 16, REPLAY_NSLOT]
-LOG_COMMAND, LOG_ACTION = 0, 7
-REPLAY_NSLOT = 8
-(REPLAY_POS_ERR_SUM, REPLAY_POS_ERR_SQ, REPLAY_VEL_ERR_SQ, REPLAY_POS_ERR_PEAK, REPLAY_GYRO_ERR_SQ, REPLAY_ACCEL_ERR_SQ, REPLAY_CONTACT_AGREE,
- REPLAY_SAMPLES) = range(8)
 
 
 def log_row(nu: int) -> int:

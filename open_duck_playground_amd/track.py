@@ -179,6 +179,9 @@ from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
+from .engine import (TRACK_NACC as NACC, TRACK_ENDED as ENDED, TRACK_STEPS as STEPS, TRACK_SAMPLES as SAMPLES, TRACK_FALLS as FALLS,
+                     TRACK_REWARD as REWARD, TRACK_SUM as SUM, TRACK_SQERR as SQERR)      # ODK_TRACK_*
+
 from .engine import (PUSH_NACC, PUSH_PUSHED as P_PUSHED, PUSH_PUSH_AT as P_PUSH_AT, PUSH_FELL as P_FELL, PUSH_STEPS_TO_FALL as P_STEPS_TO_FALL,
                      PUSH_LAST_OFF as P_LAST_OFF, PUSH_PEAK_LIN_ERR as P_PEAK_LIN, PUSH_PEAK_ANG_ERR as P_PEAK_ANG, PUSH_PRE_LIN_ERR_SUM as P_PRE_SUM,
                      PUSH_PRE_SAMPLES as P_PRE_SAMPLES, PUSH_PRE_LIN_ERR_LOW as P_PRE_LOW)      # include/odk.h ODK_PUSH_*: one definition, engine.py's
@@ -225,8 +228,6 @@ from .actuation import nominal_actuation, actuation_order, actuations_from_args,
 from .sweeps import parse_axis_grid, grid_rows, parse_key_values, cell_rows      # the syntaxes and the env layout every sweep flag shares
 
 COMMAND_KEYS = ("vx", "vy", "wz", "neck_pitch", "head_pitch", "head_yaw", "head_roll")   # the order of cmd_range (include/odk.h)
-NACC = 12
-ENDED, STEPS, SAMPLES, FALLS, REWARD, SUM, SQERR = 0, 1, 2, 3, 4, 5, 8      # include/odk.h ODK_TRACK_*
 
 
 def command_row(values: Sequence[float]) -> List[float]:

@@ -1,17 +1,20 @@
 """engine.SIGNATURES, the one ctypes declaration of every C entry point, held to the prototypes of include/odk.h: names, argument count and
-kind, return type, and a struct pointer bound as a pointer to that struct's Structure.  Host-only: reads the header's text and the table,
-needs neither libodk.so nor a device."""
+kind, return type, and a struct pointer bound as a pointer to that struct's Structure; and every Structure held to its struct's layout as
+the host C compiler sees it: size, and each field's offset and size.  Host-only: reads the header's text and the table, needs neither
+libodk.so nor a device."""
 import ctypes as C
 import os
 import re
+import shlex
+import subprocess
 
 from conftest import ROOT
 from open_duck_playground_amd import engine
 
 SCALARS = {"long long": C.c_longlong, "uint64_t": C.c_uint64, "uint32_t": C.c_uint32, "double": C.c_double, "float": C.c_float, "int": C.c_int}
 STRUCTS = {"odk_env_config": engine.EnvConfig, "odk_outputs": engine.Outputs, "odk_reward_terms": engine.RewardTerms,
-           "odk_mlp_desc": engine.MlpDesc, "odk_step_tail": engine.StepTail, "odk_gae_head_args": engine.GaeHeadArgs,
-           "odk_grad_finish": engine.GradFinish, "odk_weight_table": engine.WeightTableC}
+           "odk_curriculum": engine.Curriculum, "odk_mlp_desc": engine.MlpDesc, "odk_step_tail": engine.StepTail,
+           "odk_gae_head_args": engine.GaeHeadArgs, "odk_grad_finish": engine.GradFinish, "odk_weight_table": engine.WeightTableC}
 
 
 def stripped_header() -> str:
@@ -97,6 +100,8 @@ def test_signature_table_agrees_with_the_header():
         ["odk_default_config", "odk_default_config_standing", "odk_obs_sizes", "odk_model_free", "odk_batch_destroy", "odk_set_debug_dump",
          "odk_dw_set_profile", "odk_mlp_set_profile", "odk_mlp_set_wg_profile"])
     assert {s for _, _, structs in protos.values() for s in structs if s} == set(STRUCTS)      # every struct of the map is met in a prototype
+    assert set(re.findall(r"\btypedef\s+struct\s*\w*\s*\{[^{}]*\}\s*(odk_\w+)\s*;", stripped_header())) == set(STRUCTS)     # and the header defines no other
+    assert {v for v in vars(engine).values() if isinstance(v, type) and issubclass(v, C.Structure)} == set(STRUCTS.values())
     assert mismatches(engine.SIGNATURES, protos) == []
 
 
@@ -117,3 +122,46 @@ def test_the_comparison_reports_a_broken_entry_by_name():
     assert "not declared" in broken("odk_nothing", lambda t: t.__setitem__("odk_nothing", (C.c_int, [])))
     assert "restype" in broken("odk_model_free", lambda t: t.__setitem__("odk_model_free", (C.c_int, t["odk_model_free"][1])))
     assert "odk_outputs" in broken("odk_reset", lambda t: t["odk_reset"][1].__setitem__(3, C.c_void_p))        # a struct pointer left bare
+
+
+def header_layout(structs: dict, workdir) -> dict:
+    """What the host C compiler ($CC, else cc) makes of include/odk.h's structs: "odk_x" -> (sizeof,) and "odk_x.field" -> (offsetof, sizeof)
+    for every field the map's Structures name, printed by a program generated from their `_fields_` and compiled in `workdir`."""
+    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "odk.h"', "int main(void) {"]
+    for cname, S in structs.items():
+        lines.append(f'  printf("{cname} %zu\\n", sizeof({cname}));')
+        lines += [f'  printf("{cname}.{f} %zu %zu\\n", offsetof({cname}, {f}), sizeof((({cname}*)0)->{f}));' for f, *_ in S._fields_]
+    src, exe = os.path.join(str(workdir), "layout.c"), os.path.join(str(workdir), "layout")
+    with open(src, "w") as f:
+        f.write("\n".join(lines + ["  return 0;", "}", ""]))
+    cc = shlex.split(os.environ.get("CC") or "cc")
+    subprocess.run(cc + ["-I", os.path.join(ROOT, "include"), src, "-o", exe], check=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
+    return {words[0]: tuple(int(w) for w in words[1:]) for words in (line.split() for line in out.splitlines())}
+
+
+def layout_mismatches(structs: dict, layout: dict) -> list:
+    """Every disagreement between the Structures of a struct map and a `header_layout`, one line each, `struct` or `struct.field` first."""
+    bad = []
+    for cname, S in structs.items():
+        if (C.sizeof(S),) != layout[cname]:
+            bad.append(f"{cname}: sizeof {C.sizeof(S)} against the header's {layout[cname][0]}")
+        for f, *_ in S._fields_:
+            have = (getattr(S, f).offset, getattr(S, f).size)
+            if have != layout[f"{cname}.{f}"]:
+                bad.append(f"{cname}.{f}: (offset, size) {have} against the header's {layout[f'{cname}.{f}']}")
+    return bad
+
+
+def test_every_structure_has_its_structs_layout_and_a_swapped_pair_is_reported_by_name(tmp_path):
+    layout = header_layout(STRUCTS, tmp_path)
+    assert len(layout) == len(STRUCTS) + sum(len(S._fields_) for S in STRUCTS.values()) == 9 + 121
+    assert layout_mismatches(STRUCTS, layout) == []
+
+    fields = list(engine.Curriculum._fields_)
+    i, j = (next(k for k, f in enumerate(fields) if f[0] == name) for name in ("tol_lin", "tol_yaw"))      # two floats, side by side
+    fields[i], fields[j] = fields[j], fields[i]
+    swapped = type("Curriculum", (C.Structure,), {"_fields_": fields})
+    assert C.sizeof(swapped) == C.sizeof(engine.Curriculum)
+    bad = layout_mismatches({**STRUCTS, "odk_curriculum": swapped}, layout)
+    assert sorted(line.split(":")[0] for line in bad) == ["odk_curriculum.tol_lin", "odk_curriculum.tol_yaw"], bad

@@ -32,11 +32,12 @@ def test_libodk_exports_the_three_launches_and_the_header_names_their_slots():
         assert hasattr(poison, name), name
         assert name in engine.EXPORTED_SYMBOLS
         assert re.search(rf"\bint {name}\(const odk_batch\* b,", text), name
-    assert re.search(rf"#define ODK_PATH_NACC {NACC}\b", text) and engine.PATH_NACC == NACC
-    assert re.search(rf"#define ODK_PATH_MAX_WAYPOINTS {MAX_WP}\b", text) and engine.PATH_MAX_WAYPOINTS == MAX_WP
-    assert "#define ODK_PATH_COURSE_FLOATS (1 + 2 * ODK_PATH_MAX_WAYPOINTS)" in text and engine.PATH_COURSE_FLOATS == COURSE_FLOATS
-    names = {k: int(v) for k, v in re.findall(r"\bODK_PATH_([A-Z_]+) = (\d+)", text)}
-    assert names == SLOTS                                         # the header names these slots and no others
+    names = {k[5:]: v for k, v in engine.header_constants().items() if k.startswith("PATH_")}
+    assert names.pop("NACC") == NACC and engine.PATH_NACC == NACC
+    assert names.pop("MAX_WAYPOINTS") == MAX_WP and engine.PATH_MAX_WAYPOINTS == MAX_WP
+    assert "#define ODK_PATH_COURSE_FLOATS (1 + 2 * ODK_PATH_MAX_WAYPOINTS)" in text
+    assert names.pop("COURSE_FLOATS") == COURSE_FLOATS and engine.PATH_COURSE_FLOATS == COURSE_FLOATS
+    assert names == SLOTS                                        # the header names these slots and no others
     for name, slot in names.items():
         assert getattr(engine, "PATH_" + name) == slot, name
     used = sorted(s + i for name, s in SLOTS.items() for i in range(MAX_WP if name == "REACHED" else 1))

@@ -28,16 +28,16 @@ def test_libodk_exports_the_schedule_and_response_kernels_and_the_header_names_t
         assert hasattr(lib, name), name
         assert name in engine.EXPORTED_SYMBOLS
     text = open(os.path.join(ROOT, "include", "odk.h")).read()
-    assert re.search(rf"#define ODK_SCHED_MAX_SEGMENTS {MAX_SEGMENTS}\b", text) and re.search(r"#define ODK_SCHED_SEG_FLOATS 8\b", text)
-    assert re.search(rf"#define ODK_RESP_STRIDE {STRIDE}\b", text)
+    header = engine.header_constants()
+    assert header["SCHED_MAX_SEGMENTS"] == MAX_SEGMENTS and header["SCHED_SEG_FLOATS"] == 8
+    assert header["RESP_STRIDE"] == STRIDE and header["RESP_NACC"] == NACC
     assert re.search(r"#define ODK_RESP_NACC \(ODK_SCHED_MAX_SEGMENTS \* ODK_RESP_STRIDE\)", text)
-    never = re.search(r"#define ODK_SCHED_NEVER ([0-9.e+]+)f\b", text)
-    assert never and float(never.group(1)) == engine.SCHED_NEVER
+    assert re.search(r"#define ODK_SCHED_NEVER [0-9.e+]+f\b", text) and header["SCHED_NEVER"] == engine.SCHED_NEVER == 1.0e9
     assert np.float32(engine.SCHED_NEVER) > 2.0 ** 24          # above every step count a float32 counter can reach
     assert engine.SCHED_MAX_SEGMENTS == track.SCHED_MAX_SEGMENTS == MAX_SEGMENTS and engine.SCHED_SEG_FLOATS == 8
     assert engine.RESP_STRIDE == track.RESP_STRIDE == STRIDE and engine.RESP_NACC == track.RESP_NACC == NACC
-    names = re.findall(r"ODK_RESP_([A-Z_]+) = (\d+)", text)
-    assert {k: int(v) for k, v in names} == SLOTS                # the header names these slots and no others
+    names = {k[5:]: v for k, v in header.items() if k.startswith("RESP_") and k not in ("RESP_STRIDE", "RESP_NACC")}
+    assert names == SLOTS                # the header names these slots and no others
     for name, slot in SLOTS.items():
         assert getattr(engine, "RESP_" + name) == slot, name
     # no two slots overlap, and a block fits its stride

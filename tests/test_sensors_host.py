@@ -22,10 +22,9 @@ def test_libodk_exports_the_launch_and_engine_mirrors_every_slot():
     assert hasattr(lib, "odk_sensor_apply") and "odk_sensor_apply" in engine.EXPORTED_SYMBOLS
     text = open(os.path.join(ROOT, "include", "odk.h")).read()
     assert re.search(r"\bint odk_sensor_apply\(const odk_batch\* b, const float\* obs_dev", text)
-    names = {k: int(v) for k, v in re.findall(r"\bODK_SENSOR_([A-Z_]+) = (\d+)", text)}
-    names.update({k: int(v) for k, v in re.findall(r"#define ODK_SENSOR_([A-Z_]+) (\d+)\b", text)})
+    names = {k[7:]: v for k, v in engine.header_constants().items() if k.startswith("SENSOR_")}
     assert "#define ODK_SENSOR_NSTATE (16 + ODK_SENSOR_RING * ODK_SENSOR_SAMPLE)" in text
-    names["NSTATE"] = 16 + names["RING"] * names["SAMPLE"]
+    assert names["NSTATE"] == 16 + names["RING"] * names["SAMPLE"]
     assert set(names) == set(re.findall(r"\bODK_SENSOR_([A-Z_]+)\b", text)), "a name the header mentions has no value here"
     assert len(names) == 19
     for name, v in names.items():
