@@ -103,24 +103,32 @@ def _snapshot(b):
     return out
 
 
+def _config(engine, spec, lanes, standing, config):
+    """The env config of one configuration (tests/neighbours_cases.py runs the same two): "defaults", or "everything" = noise, sampled
+    pushes every 5 .. 15 env steps, episodes of 8 steps, the duck's imitation reward (the bound rows, the DR rows and the reward terms
+    are the caller's: _run_env below)."""
+    robot = isinstance(spec, str) and spec.endswith(".xml")
+    cfg = engine.default_config(standing)
+    cfg.lanes_per_env = lanes
+    if robot:
+        cfg.use_imitation = 0
+    if config == "everything":
+        cfg.noise_level = 1.0
+        cfg.push_enable = 1.0
+        cfg.push_interval_range[0] = 0.1; cfg.push_interval_range[1] = 0.3      # a sampled push every 5 .. 15 env steps
+        cfg.episode_length = 8
+        if not robot and not standing:
+            cfg.use_imitation = 1
+    return cfg
+
+
 def _run_env(torch, engine, spec, lanes, standing, config):
     """One configuration -> ({array name: [launch, ...] stack}, launch labels, facts for the product run's own assertions)."""
     from open_duck_playground_amd import randomize
     model = _model(spec)
     robot = isinstance(spec, str) and spec.endswith(".xml")
-    duck = not robot
-    cfg = engine.default_config(standing)
-    cfg.lanes_per_env = lanes
-    if robot:
-        cfg.use_imitation = 0
+    cfg = _config(engine, spec, lanes, standing, config)
     everything = config == "everything"
-    if everything:
-        cfg.noise_level = 1.0
-        cfg.push_enable = 1.0
-        cfg.push_interval_range[0] = 0.1; cfg.push_interval_range[1] = 0.3      # a sampled push every 5 .. 15 env steps
-        cfg.episode_length = 8
-        if duck and not standing:
-            cfg.use_imitation = 1
     b = engine.Batch(model, NENV, cfg)
     L = engine.load_library()
     n, nu = NENV, model.nu

@@ -74,31 +74,35 @@ def test_short_ppo_training_runs():
 
 
 def test_env_sharding_is_invisible():
-    """Multi-GPU partition: rank r owns envs [r N, (r+1) N) via env_id_offset.  Two half-batches with
-    offsets 0 / 24 must reproduce one 48-env batch bit for bit (same per-env RNG streams, no cross-env coupling);
-    also covers an env count that is not a multiple of the 2 envs per workgroup."""
+    """Multi-GPU partition: rank r owns envs [r N, (r+1) N) via env_id_offset.  Two part-batches must reproduce one 49-env
+    batch bit for bit (same per-env RNG streams; 49 is not a multiple of the 2 envs per workgroup).  Split 24 | 25 (offsets 0 / 24): every env
+    keeps its slot and its wave partner in both runs, so this case holds the streams and the offsets and is BLIND to a leak between partners.
+    Split 25 | 24 (offsets 0 / 25, an odd offset): every env of the second part sits in the other slot beside another partner, and env 24 beside
+    the dead slot instead of env 25 -- here a coupling between the envs of a wave shows (tests/test_gpu_neighbours.py holds that property
+    by itself, at chosen neighbours)."""
     import torch
     from open_duck_playground_amd import engine
     from open_duck_playground_amd.model import load_task_model
     model = load_task_model("flat_terrain")
-    whole = engine.Batch(model, 49)
-    parts = [engine.Batch(model, 24), engine.Batch(model, 25)]
-    whole.reset(seed=7, env_id_offset=0)
-    parts[0].reset(seed=7, env_id_offset=0); parts[1].reset(seed=7, env_id_offset=24)
-    g = torch.Generator(device="cuda").manual_seed(0)
-    for _ in range(12):
-        act = torch.empty(49, 14, device="cuda").uniform_(-1, 1, generator=g)
-        whole.step(act)
-        parts[0].step(act[:24].contiguous()); parts[1].step(act[24:].contiguous())
-    for name in ("obs", "priv", "reward", "done", "truncation", "metrics"):
-        w = getattr(whole, name)
-        p = torch.cat([getattr(parts[0], name), getattr(parts[1], name)])
-        assert torch.equal(w, p), name
-    qw = whole.get_state(); qp = [b.get_state() for b in parts]
-    for k in range(3):
-        assert np.array_equal(qw[k], np.concatenate([qp[0][k], qp[1][k]]))
-    for b in [whole] + parts:
-        b.close()
+    for first in (24, 25):
+        whole = engine.Batch(model, 49)
+        parts = [engine.Batch(model, first), engine.Batch(model, 49 - first)]
+        whole.reset(seed=7, env_id_offset=0)
+        parts[0].reset(seed=7, env_id_offset=0); parts[1].reset(seed=7, env_id_offset=first)
+        g = torch.Generator(device="cuda").manual_seed(0)
+        for _ in range(12):
+            act = torch.empty(49, 14, device="cuda").uniform_(-1, 1, generator=g)
+            whole.step(act)
+            parts[0].step(act[:first].contiguous()); parts[1].step(act[first:].contiguous())
+        for name in ("obs", "priv", "reward", "done", "truncation", "metrics"):
+            w = getattr(whole, name)
+            p = torch.cat([getattr(parts[0], name), getattr(parts[1], name)])
+            assert torch.equal(w, p), (first, name)
+        qw = whole.get_state(); qp = [b.get_state() for b in parts]
+        for k in range(3):
+            assert np.array_equal(qw[k], np.concatenate([qp[0][k], qp[1][k]])), (first, k)
+        for b in [whole] + parts:
+            b.close()
 
 
 def test_nan_state_terminates_and_resets_cleanly():

@@ -1112,6 +1112,29 @@ def test_differential_sweep(torch_cuda, oracle_mod, parity_log, task, lanes):
 
 
 
+def _robot_states(oracle_mod, model, om, n=64, seed=41):
+    """The random states of _robot_through_the_physics_kernels (CPU only; tests/neighbours_cases.py draws its robot pools from it): the key pose
+    with the base tilted, a quarter of the robots airborne, every joint moved by up to 0.3 rad (some past their limits), the others settled on
+    the floor.  -> (the generator, for the caller's later draws; qpos; qvel; warm; ctrl)"""
+    rng = np.random.default_rng(seed)
+    nv = model.nv
+    qpos = np.tile(np.asarray(model.a["key_qpos"], np.float64), (n, 1)); qvel = np.zeros((n, nv))
+    air = rng.uniform(size=n) < 0.25
+    for e in range(n):
+        qpos[e, 0:2] += rng.uniform(-0.05, 0.05, 2)
+        ax = rng.normal(size=3); ax /= np.linalg.norm(ax); ang = rng.uniform(-1.0, 1.0) if air[e] else rng.uniform(-0.2, 0.2)
+        qpos[e, 3:7] = np.concatenate([[np.cos(ang / 2)], np.sin(ang / 2) * ax])
+        for j in range(1, model.njnt):
+            a_, (lo, hi) = model.a["jnt_qposadr"][j], model.a["jnt_range"][j]
+            qpos[e, a_] = np.clip(qpos[e, a_] + rng.uniform(-0.3, 0.3), lo - 0.02, hi + 0.02)      # some joints past their limits
+        qpos[e, 2] = rng.uniform(0.5, 0.8) if air[e] else qpos[e, 2]
+        qvel[e, :3] = rng.normal(0, 0.3, 3); qvel[e, 3:6] = rng.normal(0, 1.0, 3); qvel[e, 6:] = rng.normal(0, 2.0, nv - 6)
+    qpos = _settle_on_terrain(oracle_mod, om, qpos, rng, air)      # (any floor: moves the base so that the deepest contact is 0.3 ... 3 mm)
+    warm = rng.normal(0, 5.0, (n, nv))
+    ctrl = np.asarray(model.a["key_ctrl"])[None] + rng.uniform(-0.4, 0.4, (n, model.nu))
+    return rng, qpos, qvel, warm, ctrl
+
+
 def _robot_through_the_physics_kernels(torch_cuda, oracle_mod, parity_log, xml, tag, eq_active=None, cone=False, overrides=None, dims=(22, 21, 15, 19, 16), red_dims=(21, 156, 181), ill_bound=0.5):
     """(body of the two tests below)  SURVEY 8(f).3 / reference README.md:74-85 ("adding a robot"): tests/assets/tail_biped.xml -- a biped with a five-link tail,
     written for this test: 21 dofs, 15 position actuators, 19 bodies, box feet, its own masses / lengths / axes / gains -- compiled by
@@ -1136,22 +1159,8 @@ def _robot_through_the_physics_kernels(torch_cuda, oracle_mod, parity_log, xml, 
     # equality rows come first in the oracle's row order (connects 3 rows each, welds 6, joints 1); the kernels keep theirs beside the row arrays
     ne_rows = 0 if eq_active is None else int(sum(a * {0: 3, 1: 6, 2: 1}[int(t)] for a, t in zip(eq_active, np.asarray(model.a["eq_type"]).reshape(-1))))
     n = 64
-    rng = np.random.default_rng(41)
     nq, nv, nb = model.nq, model.nv, model.nbody
-    qpos = np.tile(np.asarray(model.a["key_qpos"], np.float64), (n, 1)); qvel = np.zeros((n, nv))
-    air = rng.uniform(size=n) < 0.25
-    for e in range(n):
-        qpos[e, 0:2] += rng.uniform(-0.05, 0.05, 2)
-        ax = rng.normal(size=3); ax /= np.linalg.norm(ax); ang = rng.uniform(-1.0, 1.0) if air[e] else rng.uniform(-0.2, 0.2)
-        qpos[e, 3:7] = np.concatenate([[np.cos(ang / 2)], np.sin(ang / 2) * ax])
-        for j in range(1, model.njnt):
-            a_, (lo, hi) = model.a["jnt_qposadr"][j], model.a["jnt_range"][j]
-            qpos[e, a_] = np.clip(qpos[e, a_] + rng.uniform(-0.3, 0.3), lo - 0.02, hi + 0.02)      # some joints past their limits
-        qpos[e, 2] = rng.uniform(0.5, 0.8) if air[e] else qpos[e, 2]
-        qvel[e, :3] = rng.normal(0, 0.3, 3); qvel[e, 3:6] = rng.normal(0, 1.0, 3); qvel[e, 6:] = rng.normal(0, 2.0, nv - 6)
-    qpos = _settle_on_terrain(oracle_mod, om, qpos, rng, air)      # (any floor: moves the base so that the deepest contact is 0.3 ... 3 mm)
-    warm = rng.normal(0, 5.0, (n, nv))
-    ctrl = np.asarray(model.a["key_ctrl"])[None] + rng.uniform(-0.4, 0.4, (n, model.nu))
+    rng, qpos, qvel, warm, ctrl = _robot_states(oracle_mod, model, om, n)
     b = engine.Batch(model, n)
     ctrl_t = torch.tensor(ctrl, dtype=torch.float32, device="cuda")
     b.set_state(qpos, qvel, warm)
