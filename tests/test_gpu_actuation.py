@@ -8,10 +8,9 @@ import os
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+import report_cases as RC
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ASSETS = os.path.join(ROOT, "tests", "assets")
+pytestmark = pytest.mark.gpu
 
 # robot, nu, Standing?
 CASES = {"duck": ("flat_terrain", 14, False), "duck_standing": ("flat_terrain", 14, True), "biped12": ("biped12.xml", 12, False),
@@ -32,7 +31,7 @@ def _batch(case, n):
     robot, nu, standing = CASES[case]
     cfg = engine.default_config(standing)
     if robot.endswith(".xml"):
-        model = Model.from_xml(os.path.join(ASSETS, robot))
+        model = Model.from_xml(os.path.join(RC.ASSETS, robot))
         cfg.use_imitation = 0
     else:
         model = load_task_model(robot)
@@ -224,23 +223,13 @@ def test_the_binding_and_the_entry_refuse_by_name():
 E_T, T_T = 16, 20
 
 
-def _checkpoint(tmp_path):
-    import torch
-    from open_duck_playground_amd.ppo.networks import PPONetworks
-    from open_duck_playground_amd.ppo.train import save_checkpoint
-    torch.manual_seed(0)
-    ckpt = str(tmp_path / "fresh.pt")
-    save_checkpoint(ckpt, PPONetworks(101, 212, 14))
-    return ckpt
-
-
 @pytest.fixture(scope="module")
 def rig(tmp_path_factory):
     """One duck env of 2 * E_T = 32 envs under two commands and a randomly initialised policy, shared by the Tracker tests; each builds its
     Trackers one after the other and never steps an older one again."""
     import torch
     from open_duck_playground_amd import track
-    ckpt = _checkpoint(tmp_path_factory.mktemp("actuation"))
+    ckpt = RC.fresh_checkpoint(tmp_path_factory.mktemp("actuation"))
     args = track.build_parser().parse_args(["--checkpoint", ckpt, "--command", "0", "0", "0", "--seed", "1"])
     env = track.make_env(args, 2 * E_T, 0)
     net = track.load_networks(ckpt, env, torch.device("cuda", 0))
@@ -316,7 +305,7 @@ def test_drop_one_hands_the_step_zeros(rig, monkeypatch):
 
 def test_track_actuation_sweep_end_to_end(tmp_path):
     from open_duck_playground_amd import actuation, track
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     out = tmp_path / "report.json"
     args = track.build_parser().parse_args(["--checkpoint", ckpt, "--envs_per_command", "16", "--episode_length", "12", "--seed", "1", "--falls",
                                             "--command", "0.1", "0", "0", "--actuation_grid", "cutoff=5:40:3,drop=0:0.2:2", "--output", str(out)])
@@ -355,7 +344,7 @@ def test_track_actuation_combines_with_the_other_flags(tmp_path, flags, keys):
     from open_duck_playground_amd.ppo.networks import PPONetworks
     from open_duck_playground_amd.ppo.train import save_checkpoint
     standing = "standing" in flags
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     if standing:
         torch.manual_seed(0)
         save_checkpoint(ckpt, PPONetworks(85, 153, 14))

@@ -11,7 +11,6 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 SENTINEL = 7.0
-ERR_INVALID = -1      # include/odk.h ODK_ERR_INVALID
 HEAD = [(-0.34, 1.1), (-0.78, 0.78), (-1.5, 1.5), (-0.5, 0.5)]
 N, CALLS, GUARD = 70, 40, 3
 BOUNDARY, NANS = 5, 6      # the env that sits on both `<=`, the env whose velocities are NaN
@@ -199,7 +198,7 @@ def test_update_kernel_has_the_restatements_bits(shape):
         for got, want, what in ((levels, w_levels, "levels"), (cdf, w_cdf, "cdf"), (counts, w_counts, "counts"), (stats, w_stats, "stats")):
             _same(got, want, what, update)
         assert (w_levels >= before).all() and (w_levels > before).any() and np.array_equal(w_cdf, np.cumsum(w_levels)) and w_counts[0].tolist() == [0, 0]
-    assert w_stats[0] == 6 and w_stats[2] > 1 and (nbins == 1 or ((w_counts[:, 0] > 0).any() and (w_levels == 5).any()))
+    assert w_stats[E.CURR_STAT_UPDATES] == 6 and w_stats[E.CURR_STAT_PROMOTED] > 1 and (nbins == 1 or ((w_counts[:, 0] > 0).any() and (w_levels == 5).any()))
     for t in g:
         assert (t[-4:] == 77).all()
 
@@ -262,34 +261,34 @@ def test_the_binding_and_the_entries_refuse_by_name():
                         (4, "truncation_dev")):
             args = full()
             args[k] = None
-            assert L.odk_curriculum_step(*args) == ERR_INVALID and f"odk_curriculum_step: null {name}" in last(), name
+            assert L.odk_curriculum_step(*args) == E.ERR_INVALID and f"odk_curriculum_step: null {name}" in last(), name
         args = full()
         args[8] = slot(cmd, 7)
-        assert L.odk_curriculum_step(*args) == ERR_INVALID and "odk_curriculum_step: cmd_dev is not the command buffer bound to the batch" in last()
+        assert L.odk_curriculum_step(*args) == E.ERR_INVALID and "odk_curriculum_step: cmd_dev is not the command buffer bound to the batch" in last()
         many = step_struct()
         many.n[1] = 0
         args = full(); args[1] = C.byref(many)
-        assert L.odk_curriculum_step(*args) == ERR_INVALID and "odk_curriculum_step: n[1] = 0" in last()
+        assert L.odk_curriculum_step(*args) == E.ERR_INVALID and "odk_curriculum_step: n[1] = 0" in last()
         args = full(); args[1] = C.byref(wide)
-        assert L.odk_curriculum_step(*args) == ERR_INVALID and "odk_curriculum_step: n[0] = 17" in last()
+        assert L.odk_curriculum_step(*args) == E.ERR_INVALID and "odk_curriculum_step: n[0] = 17" in last()
         for k, where, message in ((7, at(cmd, 7 * n - 1), "state_dev overlaps cmd_dev"), (9, at(cmd, 1), "cmd_dev overlaps obs_dev"),
                                   (6, at(state, 8 * n - 1), "counts_dev overlaps state_dev"), (10, at(obs, b.nobs * n - 1), "obs_dev overlaps priv_patch_dev"),
                                   (5, at(counts, 7), "counts_dev overlaps cdf_dev"), (2, at(state, 0), "state_dev overlaps priv_dev")):
             args = full()
             args[k] = where
-            assert L.odk_curriculum_step(*args) == ERR_INVALID and f"odk_curriculum_step: {message}" in last(), message
+            assert L.odk_curriculum_step(*args) == E.ERR_INVALID and f"odk_curriculum_step: {message}" in last(), message
         ufull = lambda: [b._b, C.byref(cur), P(levels), P(cdf), P(counts), P(stats), None]
         for k, name in ((0, "batch"), (1, "curriculum"), (2, "levels_dev"), (3, "cdf_dev"), (4, "counts_dev"), (5, "stats_dev")):
             args = ufull()
             args[k] = None
-            assert L.odk_curriculum_update(*args) == ERR_INVALID and f"odk_curriculum_update: null {name}" in last(), name
+            assert L.odk_curriculum_update(*args) == E.ERR_INVALID and f"odk_curriculum_update: null {name}" in last(), name
         for k, where, message in ((3, at(levels, 3), "levels_dev overlaps cdf_dev"), (2, at(counts, 7), "levels_dev overlaps counts_dev"),
                                   (5, at(cdf, 3), "cdf_dev overlaps stats_dev")):
             args = ufull()
             args[k] = where
-            assert L.odk_curriculum_update(*args) == ERR_INVALID and f"odk_curriculum_update: {message}" in last(), message
+            assert L.odk_curriculum_update(*args) == E.ERR_INVALID and f"odk_curriculum_update: {message}" in last(), message
         args = ufull(); args[1] = C.byref(few)
-        assert L.odk_curriculum_update(*args) == ERR_INVALID and "odk_curriculum_update: min_tries = 0" in last()
+        assert L.odk_curriculum_update(*args) == E.ERR_INVALID and "odk_curriculum_update: min_tries = 0" in last()
         torch.cuda.synchronize()
         assert (big == SENTINEL).all()
     finally:
@@ -367,7 +366,7 @@ def test_a_rollout_carries_the_curriculums_commands(faulty, fast):
 
 def test_a_tiny_training_run_with_the_curriculum(tmp_path):
     import torch
-    from open_duck_playground_amd import track
+    from open_duck_playground_amd import engine as E, track
     from open_duck_playground_amd.ppo import train as T
     env = _env(episode_length=30)
     cur = _curriculum(env, seed=0, min_tries=2, tol_lin=10.0, tol_yaw=10.0)      # every stint that does not fall is a success: bins promote
@@ -379,8 +378,8 @@ def test_a_tiny_training_run_with_the_curriculum(tmp_path):
         assert f"training/curriculum_{k}" in metrics, k
     rows = [json.loads(l) for l in open(log)]
     assert rows and "training/curriculum_coverage" in rows[-1] and 0.5 <= rows[-1]["training/curriculum_coverage"] <= 1.0
-    assert int(cur.stats[0]) == 2, "one update per training iteration"
-    assert (cur.state[:, 0] == 1).all() and (cur.state[:, 1] == 1).all(), "train resets the curriculum after the epoch's reset of the env"
+    assert int(cur.stats[E.CURR_STAT_UPDATES]) == 2, "one update per training iteration"
+    assert (cur.state[:, E.CURR_HEAD] == 1).all() and (cur.state[:, E.CURR_EPISODE] == 1).all(), "train resets the curriculum after the epoch's reset of the env"
     # the checkpoint carries it, and track reads it
     path = str(tmp_path / "curriculum.pt")
     T.save_checkpoint(path, net, command_curriculum=cur.describe())

@@ -8,7 +8,6 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-ODK_ERR_INVALID = -1         # include/odk.h
 N = 64
 OUTPUTS = ("obs", "priv", "reward", "done", "truncation", "metrics")
 # (task or robot file, Standing, lanes per env)
@@ -289,10 +288,10 @@ def test_refusals_launch_nothing():
             env.set_action_delays(t)
         assert isinstance(err.value, engine.OdkError)
         assert env.action_delays is None
-    assert L.odk_batch_bind_action_delays(b._b, C.c_void_p(good.data_ptr()), 0) == ODK_ERR_INVALID
+    assert L.odk_batch_bind_action_delays(b._b, C.c_void_p(good.data_ptr()), 0) == engine.ERR_INVALID
     assert "row_stride 0 < 1" in L.odk_last_error().decode()
     host = np.ones(N, np.int32)
-    assert L.odk_batch_bind_action_delays(b._b, host.ctypes.data_as(C.c_void_p), 1) == ODK_ERR_INVALID
+    assert L.odk_batch_bind_action_delays(b._b, host.ctypes.data_as(C.c_void_p), 1) == engine.ERR_INVALID
     assert "device memory" in L.odk_last_error().decode()
     torch.cuda.synchronize()
     np.testing.assert_array_equal(b.records().view(np.int32), before)

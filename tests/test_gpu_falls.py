@@ -6,28 +6,17 @@ CPU oracle so that envs fall early, fall late and survive, eager and from a capt
 One refusal of the C entry has no test: a model with more than 16 actuators.  No such model loads (MAXU = 16 in csrc/odk_model.h: the
 loader refuses it by name), so no batch of one exists to hand to the call."""
 import json
-import os
 
 import numpy as np
 import pytest
 
+import report_cases as RC
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ASSETS = os.path.join(ROOT, "tests", "assets")
-ODK_ERR_INVALID = -1         # include/odk.h
+G = RC.HEADER         # include/odk.h's constants, by engine's names
 
-# include/odk.h ODK_FALL_*
-HEAD, SAMPLE, MAX_RING = 16, 16, 64
-SAMPLES, FELL, STEP, LAST_UPRIGHT, UPRIGHT_CONTACT, TILT_PEAK = 0, 1, 2, 3, 4, 6
-S_STEP, S_UP, S_GYRO, S_LINVEL, S_HEIGHT, S_CONTACT, S_LIN_ERR, S_ANG_ERR, S_SAT = 0, 1, 4, 7, 10, 11, 13, 14, 15
 f32 = np.float32
-
-
-def planar32(x, y):
-    """hypot through float64 with one rounding to float32, as the kernels form it"""
-    x, y = np.float64(x), np.float64(y)
-    return f32(np.sqrt(x * x + y * y))
 
 
 def restate(priv, done, trunc, qpos, cmd, nobs, nu, nq, limit, tol, ring, acc0):
@@ -37,7 +26,7 @@ def restate(priv, done, trunc, qpos, cmd, nobs, nu, nq, limit, tol, ring, acc0):
     [T, *acc0.shape], STEPS [n], ENDED [n])."""
     T, n = done.shape
     A = np.array(acc0, f32)
-    w = SAMPLE + nq
+    w = G.FALL_SAMPLE + nq
     ended, steps = np.zeros(n, bool), np.zeros(n, f32)
     lim = None if limit is None else np.asarray(limit, f32)
     snaps = []
@@ -49,36 +38,29 @@ def restate(priv, done, trunc, qpos, cmd, nobs, nu, nq, limit, tol, ring, acc0):
             steps[e] += 1
             if done[t, e] != 0:
                 if trunc[t, e] == 0:
-                    R[FELL], R[STEP] = 1, st
+                    R[G.FALL_FELL], R[G.FALL_STEP] = 1, st
                 ended[e] = True
                 continue
             Q, C = priv[t, e, nobs:], cmd[t, e]
-            s = int(R[SAMPLES])
-            S = R[HEAD + (s % ring) * w:][:w]
-            S[S_STEP] = st
-            S[S_UP:S_UP + 3], S[S_GYRO:S_GYRO + 3], S[S_LINVEL:S_LINVEL + 3] = Q[6:9], Q[0:3], Q[9:12]
-            S[S_HEIGHT] = Q[15 + 2 * nu]
-            S[S_CONTACT:S_CONTACT + 2] = Q[16 + 3 * nu:18 + 3 * nu]
-            S[S_LIN_ERR] = planar32(f32(Q[9] - C[0]), f32(Q[10] - C[1]))
-            S[S_ANG_ERR] = np.abs(f32(Q[2] - C[2]))
+            s = int(R[G.FALL_SAMPLES])
+            S = R[G.FALL_HEAD + (s % ring) * w:][:w]
+            S[G.FALL_S_STEP] = st
+            S[G.FALL_S_UP:G.FALL_S_UP + 3], S[G.FALL_S_GYRO:G.FALL_S_GYRO + 3], S[G.FALL_S_LINVEL:G.FALL_S_LINVEL + 3] = Q[6:9], Q[0:3], Q[9:12]
+            S[G.FALL_S_HEIGHT] = Q[15 + 2 * nu]
+            S[G.FALL_S_CONTACT:G.FALL_S_CONTACT + 2] = Q[16 + 3 * nu:18 + 3 * nu]
+            S[G.FALL_S_LIN_ERR] = RC.planar32(f32(Q[9] - C[0]), f32(Q[10] - C[1]))
+            S[G.FALL_S_ANG_ERR] = np.abs(f32(Q[2] - C[2]))
             force = np.abs(Q[16 + 2 * nu:16 + 3 * nu])
-            S[S_SAT] = 0 if lim is None else np.count_nonzero((lim > 0) & (force >= f32(0.99) * lim))
-            S[SAMPLE:] = qpos[t, e]
-            tilt = planar32(Q[6], Q[7])
-            R[SAMPLES] = s + 1
-            R[TILT_PEAK] = max(R[TILT_PEAK], tilt)
+            S[G.FALL_S_SAT] = 0 if lim is None else np.count_nonzero((lim > 0) & (force >= f32(0.99) * lim))
+            S[G.FALL_SAMPLE:] = qpos[t, e]
+            tilt = RC.planar32(Q[6], Q[7])
+            R[G.FALL_SAMPLES] = s + 1
+            R[G.FALL_TILT_PEAK] = max(R[G.FALL_TILT_PEAK], tilt)
             if tilt <= tol:
-                R[LAST_UPRIGHT] = s + 1
-                R[UPRIGHT_CONTACT:UPRIGHT_CONTACT + 2] = S[S_CONTACT:S_CONTACT + 2]
+                R[G.FALL_LAST_UPRIGHT] = s + 1
+                R[G.FALL_UPRIGHT_CONTACT:G.FALL_UPRIGHT_CONTACT + 2] = S[G.FALL_S_CONTACT:G.FALL_S_CONTACT + 2]
         snaps.append(A.copy())
     return np.stack(snaps), steps, ended
-
-
-def _robot_env(robot, n, **kw):
-    from open_duck_playground_amd import joystick
-    if robot.endswith(".xml"):
-        return joystick.Joystick(xml_path=os.path.join(ASSETS, robot), num_envs=n, **kw)
-    return joystick.Joystick(task=robot, num_envs=n, **kw)
 
 
 N_SYN, T_SYN, RING_SYN = 300, 11, 4
@@ -86,7 +68,33 @@ TOL_SYN = f32(0.3)
 # first episodes by e % 8: running at the end | fall in step 0 | fall with `ring` samples | with ring + 1 | after two wraps (10 samples) |
 # truncation in step 0 | truncation at step 6 | running at the end
 END_AT = (T_SYN + 1, 0, RING_SYN, RING_SYN + 1, 10, 0, 6, T_SYN + 1)
-WITH_TRUNC = (False, False, False, False, False, True, True, False)
+TRUNCATED = (5, 6)
+E_TIE = 7                 # runs to the end: exactly the tolerance is upright, one ulp above is not
+
+
+def synthetic_inputs(nobs, npriv, nu, nq, limits):
+    """The host half of the synthetic test, a function of the sizes alone: (priv [T, n, npriv], done, trunc [T, n], qpos [T, n, nq], cmd
+    [n, 7], end_at [n], limit [nu] or None)."""
+    n, T = N_SYN, T_SYN
+    rng = np.random.default_rng(7 + nq)
+    priv = rng.normal(0.0, 1.0, (T, n, npriv)).astype(f32)
+    priv[:, :, nobs + 6:nobs + 8] *= f32(0.3)                                       # leans on both sides of the tolerance
+    priv[:, :, nobs + 16 + 3 * nu:nobs + 18 + 3 * nu] = rng.integers(0, 2, (T, n, 2))
+    priv[2, E_TIE, nobs + 6:nobs + 8] = (TOL_SYN, 0.0)
+    priv[3, E_TIE, nobs + 6:nobs + 8] = (0.0, np.nextafter(TOL_SYN, f32(1)))
+    priv[4:, E_TIE, nobs + 6] = 1.0
+    qpos = rng.normal(0.0, 1.0, (T, n, nq)).astype(f32)
+    cmd = rng.uniform(-0.3, 0.3, (n, 7)).astype(f32)
+    end_at, done, trunc, _ = RC.first_episodes(rng, T, n, END_AT, TRUNCATED)
+    limit = None
+    if limits:
+        limit = np.ones(nu, f32)
+        limit[1], limit[2], limit[3], limit[4] = 0.0, 0.5, 100.0, -1.0             # never counted; saturates often; never reached; never counted
+        fcol = nobs + 16 + 2 * nu
+        priv[1, 0, fcol] = f32(0.99) * f32(1.0)                                    # exactly at the threshold: counted
+        priv[1, 8, fcol] = -np.nextafter(f32(0.99) * f32(1.0), f32(0))             # one ulp under it: not counted
+        priv[:, :, fcol + 1] = 50.0                                                # a large force on the actuator without a limit
+    return priv, done, trunc, qpos, cmd, end_at, limit
 
 
 @pytest.mark.parametrize("robot,nu,limits", [("flat_terrain", 14, "given"), ("flat_terrain_backlash", 14, None), ("biped_arms.xml", 16, "given")])
@@ -96,49 +104,23 @@ def test_every_float_equals_a_numpy_restatement_on_synthetic_rows(robot, nu, lim
     tracking accumulator.  The accumulator is 3 floats wider than a row and 2 rows longer than the batch, filled with 9.0 there; after every
     step it equals the restatement as int32 everywhere, and the fall launch leaves the tracking accumulator's bits alone."""
     import torch
-    from open_duck_playground_amd import engine
-    n, T, ring = N_SYN, T_SYN, RING_SYN
-    env = _robot_env(robot, n)
+    n, T, ring, e_tie = N_SYN, T_SYN, RING_SYN, E_TIE
+    env = RC.robot_env(robot, n)
     b = env.batch
     nobs, npriv, nq = b.nobs, b.npriv, int(b.model.nq)
     assert b.model.nu == nu and nobs + 18 + 3 * nu <= npriv
     if robot == "flat_terrain_backlash":
         assert nq > 21 and nq % 16 != 0          # more than one pass of the qpos copy, the last one partly idle
     rf = b.fall_row_floats(ring)
-    assert rf == HEAD + ring * (SAMPLE + nq)
-    rng = np.random.default_rng(7 + nq)
-    priv = rng.normal(0.0, 1.0, (T, n, npriv)).astype(f32)
-    priv[:, :, nobs + 6:nobs + 8] *= f32(0.3)                                       # leans on both sides of the tolerance
-    priv[:, :, nobs + 16 + 3 * nu:nobs + 18 + 3 * nu] = rng.integers(0, 2, (T, n, 2))
-    e_tie = 7                                                                      # runs to the end: exactly the tolerance is upright, one ulp above is not
-    priv[2, e_tie, nobs + 6:nobs + 8] = (TOL_SYN, 0.0)
-    priv[3, e_tie, nobs + 6:nobs + 8] = (0.0, np.nextafter(TOL_SYN, f32(1)))
-    priv[4:, e_tie, nobs + 6] = 1.0
-    qpos = rng.normal(0.0, 1.0, (T, n, nq)).astype(f32)
-    cmd = rng.uniform(-0.3, 0.3, (n, 7)).astype(f32)
-    end_at = np.array([END_AT[e % 8] for e in range(n)])
-    with_trunc = np.array([WITH_TRUNC[e % 8] for e in range(n)])
-    done = (rng.uniform(size=(T, n)) < 0.1).astype(f32)                            # stray done flags after the end must not matter ...
-    for e in range(n):
-        done[:min(end_at[e], T), e] = 0.0                                          # ... and none before it
-        if end_at[e] < T:
-            done[end_at[e], e] = 1.0
-    trunc = (done * with_trunc[None]).astype(f32)
-    limit = None
-    if limits:
-        limit = np.ones(nu, f32)
-        limit[1], limit[2], limit[3], limit[4] = 0.0, 0.5, 100.0, -1.0             # never counted; saturates often; never reached; never counted
-        fcol = nobs + 16 + 2 * nu
-        priv[1, 0, fcol] = f32(0.99) * f32(1.0)                                    # exactly at the threshold: counted
-        priv[1, 8, fcol] = -np.nextafter(f32(0.99) * f32(1.0), f32(0))             # one ulp under it: not counted
-        priv[:, :, fcol + 1] = 50.0                                                # a large force on the actuator without a limit
+    assert rf == G.FALL_HEAD + ring * (G.FALL_SAMPLE + nq)
+    priv, done, trunc, qpos, cmd, end_at, limit = synthetic_inputs(nobs, npriv, nu, nq, limits)
     acc0 = np.full((n + 2, rf + 3), 9.0, f32)
     acc0[:n, :rf] = 0.0
     want, steps, ended = restate(priv, done, trunc, qpos, np.broadcast_to(cmd, (T, n, 7)), nobs, nu, nq, limit, TOL_SYN, ring, acc0)
 
     big = torch.tensor(acc0, device="cuda")
     acc = big[:n]
-    tacc = torch.zeros(n, engine.TRACK_NACC, device="cuda")
+    tacc = torch.zeros(n, G.TRACK_NACC, device="cuda")
     b.bind_commands(torch.tensor(cmd, device="cuda"))
     b.reward.zero_()
     lim_dev = None if limit is None else torch.tensor(limit, device="cuda")
@@ -152,34 +134,35 @@ def test_every_float_equals_a_numpy_restatement_on_synthetic_rows(robot, nu, lim
         b.tracking_accumulate(tacc)
         np.testing.assert_array_equal(big.cpu().numpy().view(np.int32), want[t].view(np.int32), err_msg=f"step {t}")
     got, tr = big.cpu().numpy(), tacc.cpu().numpy()
-    np.testing.assert_array_equal(tr[:, engine.TRACK_STEPS], steps)
-    np.testing.assert_array_equal(tr[:, engine.TRACK_ENDED] != 0, ended)
+    np.testing.assert_array_equal(tr[:, G.TRACK_STEPS], steps)
+    np.testing.assert_array_equal(tr[:, G.TRACK_ENDED] != 0, ended)
     np.testing.assert_array_equal(got[n:], 9.0)
     np.testing.assert_array_equal(got[:, rf:], 9.0)
 
     # the run covers what it claims to
     row = lambda e: got[e, :rf]
-    assert {int(x) for x in got[:n, SAMPLES]} == {0, ring, ring + 1, 6, 10, T}
+    assert {int(x) for x in got[:n, G.FALL_SAMPLES]} == {0, ring, ring + 1, 6, 10, T}
     for e in range(16):
         k, r = e % 8, row(e)
-        assert r[SAMPLES] == min(end_at[e], T) and np.all(r[7:HEAD] == 0.0)
-        assert r[FELL] == (end_at[e] < T and not with_trunc[e]) and r[STEP] == (end_at[e] if r[FELL] else 0)
+        assert r[G.FALL_SAMPLES] == min(end_at[e], T) and np.all(r[G.FALL_TILT_PEAK + 1:G.FALL_HEAD] == 0.0)
+        assert r[G.FALL_FELL] == (end_at[e] < T and k not in TRUNCATED) and r[G.FALL_STEP] == (end_at[e] if r[G.FALL_FELL] else 0)
         if k in (1, 5):                                                            # ended in step 0: nothing but the fall's two slots
-            assert np.all(np.delete(r, [FELL, STEP]) == 0.0)
-        order = np.array([(s % ring) for s in range(max(int(r[SAMPLES]) - ring, 0), int(r[SAMPLES]))], np.int64)
-        slots = r[HEAD:].reshape(ring, SAMPLE + nq)
-        np.testing.assert_array_equal(slots[order, S_STEP], np.arange(max(int(r[SAMPLES]) - ring, 0), int(r[SAMPLES])))
-        np.testing.assert_array_equal(slots[order, SAMPLE:], qpos[int(r[SAMPLES]) - len(order):int(r[SAMPLES]), e])
+            assert np.all(np.delete(r, [G.FALL_FELL, G.FALL_STEP]) == 0.0)
+        order = np.array([(s % ring) for s in range(max(int(r[G.FALL_SAMPLES]) - ring, 0), int(r[G.FALL_SAMPLES]))], np.int64)
+        slots = r[G.FALL_HEAD:].reshape(ring, G.FALL_SAMPLE + nq)
+        np.testing.assert_array_equal(slots[order, G.FALL_S_STEP], np.arange(max(int(r[G.FALL_SAMPLES]) - ring, 0), int(r[G.FALL_SAMPLES])))
+        np.testing.assert_array_equal(slots[order, G.FALL_SAMPLE:], qpos[int(r[G.FALL_SAMPLES]) - len(order):int(r[G.FALL_SAMPLES]), e])
     tie = want[:, e_tie]
-    assert tie[2, LAST_UPRIGHT] == 3 and tie[3, LAST_UPRIGHT] == 3 and tie[3, SAMPLES] == 4 and tie[-1, LAST_UPRIGHT] == 3 and tie[-1, TILT_PEAK] >= 1.0
-    np.testing.assert_array_equal(tie[-1, UPRIGHT_CONTACT:UPRIGHT_CONTACT + 2], priv[2, e_tie, nobs + 16 + 3 * nu:nobs + 18 + 3 * nu])
-    sat = got[:n, HEAD:rf].reshape(n, ring, SAMPLE + nq)[:, :, S_SAT]
+    assert tie[2, G.FALL_LAST_UPRIGHT] == 3 and tie[3, G.FALL_LAST_UPRIGHT] == 3 and tie[3, G.FALL_SAMPLES] == 4
+    assert tie[-1, G.FALL_LAST_UPRIGHT] == 3 and tie[-1, G.FALL_TILT_PEAK] >= 1.0
+    np.testing.assert_array_equal(tie[-1, G.FALL_UPRIGHT_CONTACT:G.FALL_UPRIGHT_CONTACT + 2], priv[2, e_tie, nobs + 16 + 3 * nu:nobs + 18 + 3 * nu])
+    sat = got[:n, G.FALL_HEAD:rf].reshape(n, ring, G.FALL_SAMPLE + nq)[:, :, G.FALL_S_SAT]
     if limit is None:
         assert np.all(sat == 0.0)
     else:
-        assert sat.max() >= 3 and want[1, 0, HEAD + (SAMPLE + nq) + S_SAT] >= 1 and np.all(sat == np.round(sat)) and sat.max() <= nu - 3
-    lu = got[:n, LAST_UPRIGHT]
-    assert (lu == 0).any() and (lu == got[:n, SAMPLES]).any() and ((lu > 0) & (lu < got[:n, SAMPLES])).any()
+        assert sat.max() >= 3 and want[1, 0, G.FALL_HEAD + (G.FALL_SAMPLE + nq) + G.FALL_S_SAT] >= 1 and np.all(sat == np.round(sat)) and sat.max() <= nu - 3
+    lu = got[:n, G.FALL_LAST_UPRIGHT]
+    assert (lu == 0).any() and (lu == got[:n, G.FALL_SAMPLES]).any() and ((lu > 0) & (lu < got[:n, G.FALL_SAMPLES])).any()
     b.bind_commands(None)
     b.close()
 
@@ -200,7 +183,7 @@ def _rollout(graph):
     import torch
     from open_duck_playground_amd import engine, track
     n, T, ring = ROLL_N, ROLL_T, ROLL_RING
-    env = _robot_env("flat_terrain", n, config_overrides={"episode_length": ROLL_EPISODE})
+    env = RC.robot_env("flat_terrain", n, config_overrides={"episode_length": ROLL_EPISODE})
     b = env.batch
     nq = int(b.model.nq)
     cmd = torch.tensor(np.tile(f32([0.1, 0, 0, 0, 0, 0, 0]), (n, 1)), device="cuda")
@@ -267,57 +250,27 @@ def test_a_real_rollout_eager_and_captured():
     acc0 = np.zeros_like(e["acc"])
     want, steps, ended = restate(priv, done, trunc, qpos, np.broadcast_to(e["cmd"], (ROLL_T, n, 7)), e["nobs"], e["nu"], nq, e["limit"], f32(e["tol"]), ring, acc0)
     got = e["acc"]
-    fell, ns = got[:, FELL] != 0, got[:, SAMPLES]
+    fell, ns = got[:, G.FALL_FELL] != 0, got[:, G.FALL_SAMPLES]
     late, early, never = int((fell & (ns > ring)).sum()), int((fell & (ns < ring)).sum()), int((~fell).sum())
     print(f"falls after more than {ring} samples: {late}, with fewer: {early}, never fell: {never}; truncated: {int((ended & ~fell).sum())}")
     assert late >= 4 and early >= 1 and never >= 4, (late, early, never)
-    np.testing.assert_array_equal(e["tacc"][:, 1], steps)
+    np.testing.assert_array_equal(e["tacc"][:, G.TRACK_STEPS], steps)
     np.testing.assert_array_equal(got.view(np.int32), want[-1].view(np.int32))
     assert (ended & ~fell).any()                      # somebody was truncated: nothing written at that done step
-    np.testing.assert_array_equal(got[fell, STEP], ns[fell])      # every step before the termination was a sample
-    assert (got[:, HEAD:].reshape(n, ring, SAMPLE + nq)[:, :, S_SAT] > 0).any() and (got[:, LAST_UPRIGHT] > 0).any()
+    np.testing.assert_array_equal(got[fell, G.FALL_STEP], ns[fell])      # every step before the termination was a sample
+    assert (got[:, G.FALL_HEAD:].reshape(n, ring, G.FALL_SAMPLE + nq)[:, :, G.FALL_S_SAT] > 0).any() and (got[:, G.FALL_LAST_UPRIGHT] > 0).any()
     g = _rollout(graph=True)
     np.testing.assert_array_equal(g["acc"].view(np.int32), got.view(np.int32))
     np.testing.assert_array_equal(g["tacc"].view(np.int32), e["tacc"].view(np.int32))
 
 
 # ---- track --falls
-def _checkpoint(tmp_path):
-    import torch
-    from open_duck_playground_amd.ppo.networks import PPONetworks
-    from open_duck_playground_amd.ppo.train import save_checkpoint
-    torch.manual_seed(0)
-    ckpt = str(tmp_path / "fresh.pt")
-    save_checkpoint(ckpt, PPONetworks(101, 212, 14))
-    return ckpt
-
-
 def _run(track, monkeypatch, argv, eager=False):
-    """track.run with its Tracker caught; eager: no graph, and after every step the step's privileged rows, flags, qpos and bound command rows.
-    Returns (report, tracker, recording)."""
-    real = track.Tracker
-    caught, hist = [], []
-
-    class Caught(real):
-        def __init__(self, *a, **k):
-            if eager:
-                k["use_graph"] = False
-            super().__init__(*a, **k)
-            caught.append(self)
-
-        def step(self):
-            super().step()
-            if eager:
-                bb = self.env.batch
-                hist.append((bb.priv.cpu().numpy(), bb.done.cpu().numpy(), bb.truncation.cpu().numpy(), bb.get_state()[0], bb.commands.cpu().numpy()))
-
-    monkeypatch.setattr(track, "Tracker", Caught)
-    try:
-        rep = track.run(track.build_parser().parse_args(argv))
-    finally:
-        monkeypatch.setattr(track, "Tracker", real)
-    assert len(caught) == 1
-    return rep, caught[0], hist
+    """RC.run_track recording, after every step, the step's privileged rows, flags, qpos and bound command rows."""
+    def after_step(tr, _):
+        b = tr.env.batch
+        return RC.step_outputs(tr) + (b.get_state()[0], b.commands.cpu().numpy())
+    return RC.run_track(track, monkeypatch, argv, eager, after_step=after_step)
 
 
 TRACK_RING = 8
@@ -329,10 +282,10 @@ def _restate_run(track, rep, tr, hist):
     got = tr.fall_acc.cpu().numpy()
     st = rep["settings"]
     assert st["falls"] is True and st["fall_ring"] == TRACK_RING and st["fall_tilt"] == 0.35 and st["fall_tilt_tol"] == float(f32(np.sin(0.35)))
-    assert got.shape == (st["num_envs"], HEAD + TRACK_RING * (SAMPLE + int(b.model.nq)))
+    assert got.shape == (st["num_envs"], G.FALL_HEAD + TRACK_RING * (G.FALL_SAMPLE + int(b.model.nq)))
     want, steps, ended = restate(priv, done, trunc, qpos, cmd, b.nobs, 14, int(b.model.nq), track.torque_limits(tr.env.mj_model), f32(st["fall_tilt_tol"]),
                                  TRACK_RING, np.zeros_like(got))
-    np.testing.assert_array_equal(tr.acc.cpu().numpy()[:, 1], steps)
+    np.testing.assert_array_equal(tr.acc.cpu().numpy()[:, G.TRACK_STEPS], steps)
     np.testing.assert_array_equal(got.view(np.int32), want[-1].view(np.int32))
     return want[-1], qpos, cmd
 
@@ -340,13 +293,13 @@ def _restate_run(track, rep, tr, hist):
 def _check_clips(path, want, qpos_hist, blocks, E, nq, keep):
     """The saved clips are the recorded qpos of those envs at those steps, bit for bit; `blocks`: the rows or cells, in order."""
     z = np.load(path)
-    fell = want[:, FELL] != 0
+    fell = want[:, G.FALL_FELL] != 0
     envs = [e for k in range(len(blocks)) for e in (k * E + np.flatnonzero(fell[k * E:(k + 1) * E])[:keep])]
     np.testing.assert_array_equal(z["env"], envs)
     assert z["qpos"].shape == (len(envs), TRACK_RING, nq) and z["qpos"].dtype == np.float32
     for i, e in enumerate(envs):
         m, t = int(z["valid"][i]), int(z["fall_step"][i])
-        assert m == min(int(want[e, SAMPLES]), TRACK_RING) and t == want[e, STEP] == want[e, SAMPLES] and z["row"][i] == e // E
+        assert m == min(int(want[e, G.FALL_SAMPLES]), TRACK_RING) and t == want[e, G.FALL_STEP] == want[e, G.FALL_SAMPLES] and z["row"][i] == e // E
         np.testing.assert_array_equal(z["steps"][i], [-1] * (TRACK_RING - m) + list(range(t - m, t)))
         np.testing.assert_array_equal(z["qpos"][i, :TRACK_RING - m], 0.0)
         np.testing.assert_array_equal(z["qpos"][i, TRACK_RING - m:].view(np.int32), qpos_hist[t - m:t, e].view(np.int32))      # hist[s]: the state step s left
@@ -360,7 +313,7 @@ def test_track_falls_end_to_end(tmp_path, monkeypatch):
     recorded qpos; the graph run has the eager run's bits and objects; the same arguments without --falls give the same report minus the
     "falls" keys and the settings entries, and the same tracking bits."""
     from open_duck_playground_amd import engine, track
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     E, T = 32, 80
     out, clips = tmp_path / "report.json", str(tmp_path / "falls.npz")
     argv = ["--checkpoint", ckpt, "--command", "0.15", "0", "0", "--command", "0", "0", "1.0", "--envs_per_command", str(E), "--episode_length", str(T),
@@ -404,7 +357,7 @@ def test_track_falls_end_to_end(tmp_path, monkeypatch):
 def test_track_falls_with_a_push_grid(tmp_path, monkeypatch):
     """2 commands x (2 magnitudes x 2 directions) x 32 envs, kicked at step 5, 40 steps: one object per cell and one per row, clips per cell."""
     from open_duck_playground_amd import track
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     E, T = 32, 40
     clips = str(tmp_path / "falls.npz")
     argv = ["--checkpoint", ckpt, "--command", "0.15", "0", "0", "--command", "0", "0", "1.0", "--envs_per_command", str(E), "--episode_length", str(T),
@@ -431,7 +384,7 @@ def test_track_falls_with_a_push_grid(tmp_path, monkeypatch):
 def test_track_falls_under_a_command_schedule(tmp_path, monkeypatch):
     """--then 0 0 0 --switch_at 10: the command errors in the ring are against the command in force at each sample's step."""
     from open_duck_playground_amd import track
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     E, T = 32, 40
     argv = ["--checkpoint", ckpt, "--command", "0.15", "0", "0", "--command", "0", "0", "1.0", "--then", "0", "0", "0", "--switch_at", "10",
             "--envs_per_command", str(E), "--episode_length", str(T), "--seed", "1", "--output", str(tmp_path / "r.json"),
@@ -447,14 +400,14 @@ def test_track_falls_under_a_command_schedule(tmp_path, monkeypatch):
     np.testing.assert_array_equal(cmd[9, :, :3], np.repeat(froms, E, axis=0))     # the recording itself: the from-command up to step 9 ...
     np.testing.assert_array_equal(cmd[10:, :, :3], 0.0)                           # ... and 0 0 0 from step 10
     priv = np.stack([h[0] for h in hist])
-    slots = want[:, HEAD:].reshape(2 * E, TRACK_RING, SAMPLE + nq)
+    slots = want[:, G.FALL_HEAD:].reshape(2 * E, TRACK_RING, G.FALL_SAMPLE + nq)
     before = after = 0
     for e in range(2 * E):
-        for S in slots[e][:min(int(want[e, SAMPLES]), TRACK_RING)]:
-            t = int(S[S_STEP])
+        for S in slots[e][:min(int(want[e, G.FALL_SAMPLES]), TRACK_RING)]:
+            t = int(S[G.FALL_S_STEP])
             c = froms[e // E] if t < 10 else f32([0, 0, 0])
             Q = priv[t, e, nobs:]
-            assert S[S_LIN_ERR] == planar32(f32(Q[9] - c[0]), f32(Q[10] - c[1])) and S[S_ANG_ERR] == np.abs(f32(Q[2] - c[2])), (e, t)
+            assert S[G.FALL_S_LIN_ERR] == RC.planar32(f32(Q[9] - c[0]), f32(Q[10] - c[1])) and S[G.FALL_S_ANG_ERR] == np.abs(f32(Q[2] - c[2])), (e, t)
             before, after = before + (t < 10), after + (t >= 10)
     print("ring samples before / after the switch:", before, after)
     assert after > 0
@@ -471,9 +424,9 @@ def test_refusals_launch_nothing():
     env.reset(1)
     b.step(torch.zeros(n, 14, device="cuda"))
     rf = b.fall_row_floats(ring)
-    assert rf == L.odk_fall_row_floats(b._b, ring) == HEAD + ring * (SAMPLE + int(b.model.nq))
-    assert L.odk_fall_row_floats(b._b, 0) < 0 and L.odk_fall_row_floats(b._b, MAX_RING + 1) < 0 and L.odk_fall_row_floats(None, ring) < 0
-    assert L.odk_fall_row_floats(b._b, MAX_RING) == HEAD + MAX_RING * (SAMPLE + int(b.model.nq))
+    assert rf == L.odk_fall_row_floats(b._b, ring) == G.FALL_HEAD + ring * (G.FALL_SAMPLE + int(b.model.nq))
+    assert L.odk_fall_row_floats(b._b, 0) < 0 and L.odk_fall_row_floats(b._b, G.FALL_MAX_RING + 1) < 0 and L.odk_fall_row_floats(None, ring) < 0
+    assert L.odk_fall_row_floats(b._b, G.FALL_MAX_RING) == G.FALL_HEAD + G.FALL_MAX_RING * (G.FALL_SAMPLE + int(b.model.nq))
     acc = torch.full((n, rf), 9.0, device="cuda")
     tacc = torch.zeros(n, engine.TRACK_NACC, device="cuda")
     lim = torch.ones(14, device="cuda")
@@ -487,7 +440,7 @@ def test_refusals_launch_nothing():
                                      a["acc_dev"], stride, b._stream())
 
     def refused(what, **kw):
-        assert raw(**kw) == ODK_ERR_INVALID, what
+        assert raw(**kw) == G.ERR_INVALID, what
         msg = L.odk_last_error().decode()
         assert "odk_fall_accumulate" in msg and what in msg, msg
 
@@ -498,7 +451,7 @@ def test_refusals_launch_nothing():
         refused(null, null=null)
     refused("batch", batch=None)
     refused("ring = 0", ring=0)
-    refused(f"ring = {MAX_RING + 1}", ring=MAX_RING + 1)
+    refused(f"ring = {G.FALL_MAX_RING + 1}", ring=G.FALL_MAX_RING + 1)
     refused("ring = -1", ring=-1)
     refused(f"row_stride = {rf - 1}", stride=rf - 1)
     refused("row_stride", ring=ring + 1)                       # the same row is too short for a longer ring
@@ -506,7 +459,7 @@ def test_refusals_launch_nothing():
     refused("tilt_tol", tol=float("nan"))
     refused("tilt_tol", tol=float("inf"))
     # the Python surface: OdkErrors before anything is launched
-    bad = [(torch.full((n, rf - 1), 9.0, device="cuda"), tacc, 0.3, ring, lim), (acc, tacc, 0.3, 0, lim), (acc, tacc, 0.3, MAX_RING + 1, lim),
+    bad = [(torch.full((n, rf - 1), 9.0, device="cuda"), tacc, 0.3, ring, lim), (acc, tacc, 0.3, 0, lim), (acc, tacc, 0.3, G.FALL_MAX_RING + 1, lim),
            (acc, tacc, -1.0, ring, lim), (acc, tacc, float("nan"), ring, lim), (acc.cpu(), tacc, 0.3, ring, lim), (acc, tacc.cpu(), 0.3, ring, lim),
            (acc, tacc, 0.3, ring, torch.ones(13, device="cuda")), (acc, tacc, 0.3, ring, np.ones(14, np.float32)), (acc.double(), tacc, 0.3, ring, lim)]
     for args in bad:
@@ -523,6 +476,6 @@ def test_refusals_launch_nothing():
     b.fall_accumulate(acc, tacc, 0.3, ring)
     b.fall_accumulate(acc, tacc, 0.3, ring, lim)
     torch.cuda.synchronize()
-    assert float(acc[:, SAMPLES].sum()) > 0.0
+    assert float(acc[:, G.FALL_SAMPLES].sum()) > 0.0
     b.bind_commands(None)
     b.close()

@@ -12,7 +12,6 @@ pytestmark = pytest.mark.gpu
 
 CALLS = 12
 SENTINEL = 7.0
-ERR_INVALID = -1      # include/odk.h ODK_ERR_INVALID
 
 
 def bits(a):
@@ -139,7 +138,7 @@ def test_the_binding_and_the_entry_refuse_by_name():
     for k, name in ((0, "batch"), (2, "spec_dev"), (5, "state_dev"), (6, "sensor_fault_dev"), (7, "act_fault_dev")):
         args = [b._b, None, P(spec), 1, 2, P(state), P(sf), P(af), None]
         args[k] = None
-        assert L.odk_fault_resample(*args) == ERR_INVALID and f"odk_fault_resample: null {name}" in L.odk_last_error().decode()
+        assert L.odk_fault_resample(*args) == E.ERR_INVALID and f"odk_fault_resample: null {name}" in L.odk_last_error().decode()
     rows = n * 48
     both = torch.full((2 * rows + 3 * E.FAULT_NSLOT - 2,), SENTINEL, device="cuda")      # one allocation: what overlaps what is ours to say
     at = lambda k: C.c_void_p(both.data_ptr() + 4 * k)
@@ -150,7 +149,7 @@ def test_the_binding_and_the_entry_refuse_by_name():
                                     (at(0), [at(3 * E.FAULT_NSLOT - 1), P(af)], "sensor_fault_dev overlaps spec_dev"),
                                     (at(rows - 1), [P(sf), at(0)], "act_fault_dev overlaps spec_dev")):
         rc = L.odk_fault_resample(b._b, None, spec_p, 1, 2, P(state), *tables, None)
-        assert rc == ERR_INVALID and f"odk_fault_resample: {message}" in L.odk_last_error().decode(), message
+        assert rc == E.ERR_INVALID and f"odk_fault_resample: {message}" in L.odk_last_error().decode(), message
     torch.cuda.synchronize()
     assert (sf == SENTINEL).all() and (af == SENTINEL).all() and (both == SENTINEL).all() and not state.any()
     assert np.array_equal(bits(spec.cpu().numpy()), bits(kernel_spec()))

@@ -2,33 +2,24 @@
 against a float64 numpy restatement on synthetic privileged rows (three robots: nu 14, 15 and 16; a tail wave; a partial block), the report
 of a real run against the same restatement over the recorded outputs, eager against graph, with and without pushes, and the refusals."""
 import json
-import os
 
 import numpy as np
 import pytest
 
+import report_cases as RC
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ASSETS = os.path.join(ROOT, "tests", "assets")
-ODK_ERR_INVALID = -1         # include/odk.h
-
-# include/odk.h ODK_GAIT_*
-(SAMPLES, SPEED_SUM, ABS_POWER_SUM, CONTACT, DOUBLE, FLIGHT, TOUCHDOWNS, SWING_STEPS_SUM, SLIP_SUM, HEIGHT_SUM, HEIGHT_SQ_SUM, ROLLPITCH_RATE_SQ_SUM,
- ACTION_RATE_SUM, PREV_CONTACT, AIR_RUN) = (0, 1, 2, 3, 5, 6, 7, 9, 11, 13, 14, 15, 16, 17, 19)
-TORQUE_SQ, TORQUE_PEAK, VEL_PEAK, SAT, ABS_POWER, RANGE_MIN, RANGE_MAX = 32, 48, 64, 80, 96, 112, 128
-NACC = 144
-# float32 running sums of non-negative terms (the rest of the row is counts, maxima, minima and bookkeeping: exact)
-SUM_SCALARS = (SPEED_SUM, ABS_POWER_SUM, SLIP_SUM, SLIP_SUM + 1, HEIGHT_SUM, HEIGHT_SQ_SUM, ROLLPITCH_RATE_SQ_SUM, ACTION_RATE_SUM)
-SUM_ARRAYS = (TORQUE_SQ, ABS_POWER)
+G = RC.HEADER         # include/odk.h's constants, by engine's names
 
 
 def restate(priv, done, ended, nobs, nu, limit):
     """odk_gait_accumulate restated in float64 over float32 inputs: priv [T, n, npriv], done [T, n], ended [T, n] (the tracking accumulator's
     ENDED column as the launch of step t saw it), limit [nu] float32 or None.  Returns the [n, 144] accumulator."""
     T, n = done.shape
-    A = np.zeros((n, NACC), np.float64)
+    A = np.zeros((n, G.GAIT_NACC), np.float64)
     lim32 = None if limit is None else np.float32(limit)
+    lanes = lambda slot: slice(slot, slot + nu)      # a per-actuator array's live entries
     for e in range(n):
         prev, air, N = [False, False], [0, 0], 0
         R = A[e]
@@ -42,67 +33,45 @@ def restate(priv, done, ended, nobs, nu, limit):
             q, v, h, f = Q[15:15 + nu], Q[15 + nu:15 + 2 * nu], Q[15 + 2 * nu], Q[16 + 2 * nu:16 + 3 * nu]
             con = Q[16 + 3 * nu:18 + 3 * nu] != 0
             fv = Q[18 + 3 * nu:24 + 3 * nu].reshape(2, 3)
-            R[SAMPLES] += 1
-            R[SPEED_SUM] += np.hypot(Q[9], Q[10])
-            R[ABS_POWER_SUM] += np.abs(f * v).sum()
-            R[DOUBLE] += con[0] and con[1]
-            R[FLIGHT] += (not con[0]) and (not con[1])
+            R[G.GAIT_SAMPLES] += 1
+            R[G.GAIT_SPEED_SUM] += np.hypot(Q[9], Q[10])
+            R[G.GAIT_ABS_POWER_SUM] += np.abs(f * v).sum()
+            R[G.GAIT_DOUBLE] += con[0] and con[1]
+            R[G.GAIT_FLIGHT] += (not con[0]) and (not con[1])
             for k in range(2):
                 if con[k]:
-                    R[CONTACT + k] += 1
-                    R[SLIP_SUM + k] += np.hypot(fv[k, 0], fv[k, 1])
+                    R[G.GAIT_CONTACT + k] += 1
+                    R[G.GAIT_SLIP_SUM + k] += np.hypot(fv[k, 0], fv[k, 1])
                     if N > 0 and not prev[k]:
-                        R[TOUCHDOWNS + k] += 1
-                        R[SWING_STEPS_SUM + k] += air[k]
+                        R[G.GAIT_TOUCHDOWNS + k] += 1
+                        R[G.GAIT_SWING_STEPS_SUM + k] += air[k]
                     air[k] = 0
                 else:
                     air[k] += 1
                 prev[k] = bool(con[k])
-                R[PREV_CONTACT + k], R[AIR_RUN + k] = prev[k], air[k]
-            R[HEIGHT_SUM] += h
-            R[HEIGHT_SQ_SUM] += h * h
-            R[ROLLPITCH_RATE_SQ_SUM] += Q[0] * Q[0] + Q[1] * Q[1]
-            R[ACTION_RATE_SUM] += ((a1 - a2) ** 2).sum()
-            R[TORQUE_SQ:TORQUE_SQ + nu] += f * f
-            R[TORQUE_PEAK:TORQUE_PEAK + nu] = np.maximum(R[TORQUE_PEAK:TORQUE_PEAK + nu], np.abs(f))
-            R[VEL_PEAK:VEL_PEAK + nu] = np.maximum(R[VEL_PEAK:VEL_PEAK + nu], np.abs(v))
+                R[G.GAIT_PREV_CONTACT + k], R[G.GAIT_AIR_RUN + k] = prev[k], air[k]
+            R[G.GAIT_HEIGHT_SUM] += h
+            R[G.GAIT_HEIGHT_SQ_SUM] += h * h
+            R[G.GAIT_ROLLPITCH_RATE_SQ_SUM] += Q[0] * Q[0] + Q[1] * Q[1]
+            R[G.GAIT_ACTION_RATE_SUM] += ((a1 - a2) ** 2).sum()
+            R[lanes(G.GAIT_TORQUE_SQ)] += f * f
+            R[lanes(G.GAIT_TORQUE_PEAK)] = np.maximum(R[lanes(G.GAIT_TORQUE_PEAK)], np.abs(f))
+            R[lanes(G.GAIT_VEL_PEAK)] = np.maximum(R[lanes(G.GAIT_VEL_PEAK)], np.abs(v))
             if lim32 is not None:      # the comparison as the kernel makes it, in float32
                 f32 = np.abs(P32[nobs + 16 + 2 * nu:nobs + 16 + 3 * nu])
-                R[SAT:SAT + nu] += (lim32 > 0) & (f32 >= np.float32(0.99) * lim32)
-            R[ABS_POWER:ABS_POWER + nu] += np.abs(f * v)
-            R[RANGE_MIN:RANGE_MIN + nu] = q if N == 0 else np.minimum(R[RANGE_MIN:RANGE_MIN + nu], q)
-            R[RANGE_MAX:RANGE_MAX + nu] = q if N == 0 else np.maximum(R[RANGE_MAX:RANGE_MAX + nu], q)
+                R[lanes(G.GAIT_SAT)] += (lim32 > 0) & (f32 >= np.float32(0.99) * lim32)
+            R[lanes(G.GAIT_ABS_POWER)] += np.abs(f * v)
+            R[lanes(G.GAIT_RANGE_MIN)] = q if N == 0 else np.minimum(R[lanes(G.GAIT_RANGE_MIN)], q)
+            R[lanes(G.GAIT_RANGE_MAX)] = q if N == 0 else np.maximum(R[lanes(G.GAIT_RANGE_MAX)], q)
             N += 1
     return A
 
 
 def compare(got, want, nu, label):
-    """Counts, peaks, ranges and bookkeeping exact; every float32 running sum within (N + 4) * 2^-23 relative of the float64 sum, N the env's
-    sample count: N sequential float32 additions of non-negative terms (2^-24 each) and terms that carry at most a few roundings of
-    their own (a product, a root, a 16-lane tree sum: under 4 * 2^-23 together)."""
-    got = got.astype(np.float64)
-    sum_cols = list(SUM_SCALARS) + [s + u for s in SUM_ARRAYS for u in range(nu)]
-    exact_cols = [c for c in range(NACC) if c not in sum_cols]
-    worst = 0.0
-    N = want[:, SAMPLES]
-    for c in sum_cols:
-        bound = (N + 4) * 2.0 ** -23 * want[:, c]
-        err = np.abs(got[:, c] - want[:, c])
-        worst = max(worst, float(np.max(err / np.maximum(bound, 1e-300))))
-    print(f"{label}: float32 sums, worst error / bound {worst:.3f}")
-    for c in exact_cols:
-        np.testing.assert_array_equal(got[:, c], want[:, c], err_msg=f"{label}: slot {c}")
-    for c in sum_cols:
-        bound = (N + 4) * 2.0 ** -23 * want[:, c]
-        err = np.abs(got[:, c] - want[:, c])
-        assert np.all(err <= bound), (label, c, float(err.max()), float(bound[np.argmax(err - bound)]))
-
-
-def _robot_env(robot, n):
-    from open_duck_playground_amd import joystick
-    if robot == "duck":
-        return joystick.Joystick(task="flat_terrain", num_envs=n)
-    return joystick.Joystick(xml_path=os.path.join(ASSETS, robot), num_envs=n)
+    """Counts, peaks, ranges and bookkeeping exact; the float32 running sums, all of non-negative terms, within RC.compare_sums' bound."""
+    sums = [G.GAIT_SPEED_SUM, G.GAIT_ABS_POWER_SUM, G.GAIT_SLIP_SUM, G.GAIT_SLIP_SUM + 1, G.GAIT_HEIGHT_SUM, G.GAIT_HEIGHT_SQ_SUM,
+            G.GAIT_ROLLPITCH_RATE_SQ_SUM, G.GAIT_ACTION_RATE_SUM] + [s + u for s in (G.GAIT_TORQUE_SQ, G.GAIT_ABS_POWER) for u in range(nu)]
+    RC.compare_sums(got, want, G.GAIT_SAMPLES, {c: want[:, c] for c in sums}, label)
 
 
 CONTACT_HEAD = [0, 1, 1, 0, 1, 0, 1, 0, 1, 1, 0, 0, 0, 1]     # a touchdown on the second sample, then back-to-back swings of length 1, then one of 3
@@ -115,13 +84,46 @@ def test_every_slot_matches_a_numpy_restatement_on_synthetic_rows(robot, nu, nul
     (CONTACT_HEAD then random; never; always; random), first episodes end at step 0, mid-run or never, by done with and without truncation,
     and the test sets the tracking accumulator's ENDED column as odk_tracking_accumulate would have."""
     import torch
-    from open_duck_playground_amd import engine
-    n, T = 37, 24
-    env = _robot_env(robot, n)
+    n, T = N_ENVS, T_STEPS
+    env = RC.robot_env(robot, n)
     b = env.batch
     assert b.model.nu == nu
     nobs, npriv = b.nobs, b.npriv
     assert tuple(b.priv.shape) == (n, npriv) and nobs + 24 + 3 * nu <= npriv
+    priv, done, trunc, ended, end_at, limit = synthetic_inputs(nobs, npriv, nu, null_limit)
+    want = restate(priv, done, ended, nobs, nu, limit)
+
+    lim_dev = None if limit is None else torch.tensor(limit, device="cuda")
+    got, guard_tail, snaps = RC.drive_rows(b, lambda acc, tacc: b.gait_accumulate(acc, tacc, lim_dev), G.GAIT_NACC, priv, done, trunc, ended)
+    compare(got, want, nu, f"{robot} nu={nu}")
+    np.testing.assert_array_equal(guard_tail, 7.0)
+    RC.assert_frozen_after_end(snaps, end_at)
+    # the run covers what it claims to
+    N = want[:, G.GAIT_SAMPLES]
+    assert set(N.astype(int)) == {0, 11, 17, T}
+    assert np.all(got[N == 0] == 0.0)
+    first = [e for e in range(n) if e % 4 == 0 and N[e] >= 11]      # left foot on the scripted sequence
+    assert first and all(want[e, G.GAIT_TOUCHDOWNS] >= 4 and want[e, G.GAIT_SWING_STEPS_SUM] >= 4 for e in first)
+    never = [e for e in range(n) if e % 4 == 1 and N[e] > 0]
+    assert never and all(want[e, G.GAIT_CONTACT] == 0 and want[e, G.GAIT_TOUCHDOWNS] == 0 and want[e, G.GAIT_AIR_RUN] == N[e] for e in never)
+    always = [e for e in range(n) if e % 4 == 2 and N[e] > 0]
+    assert always and all(want[e, G.GAIT_CONTACT] == N[e] and want[e, G.GAIT_TOUCHDOWNS] == 0 and want[e, G.GAIT_AIR_RUN] == 0 for e in always)
+    assert (want[:, G.GAIT_DOUBLE] > 0).any() and (want[:, G.GAIT_FLIGHT] > 0).any()
+    SAT = G.GAIT_SAT
+    if null_limit:
+        assert np.all(got[:, SAT:SAT + G.GAIT_STRIDE] == 0.0)
+    else:
+        assert want[0, SAT] >= 1 and np.all(want[:, SAT + 1] == 0) and np.all(want[:, SAT + 3] == 0) and want[:, SAT + 2].sum() > want[:, SAT].sum()
+    b.close()
+
+
+N_ENVS, T_STEPS = 37, 24
+
+
+def synthetic_inputs(nobs, npriv, nu, null_limit):
+    """The host half of the synthetic test, a function of the sizes alone: (priv [T, n, npriv], done, trunc, ended [T, n], end_at [n], limit
+    [nu] or None)."""
+    n, T = N_ENVS, T_STEPS
     rng = np.random.default_rng(100 + nu)
     priv = rng.normal(0.0, 1.0, (T, n, npriv)).astype(np.float32)
     priv[:, :, nobs + 15 + 2 * nu] = rng.uniform(0.1, 0.2, (T, n)).astype(np.float32)          # a root height is positive
@@ -133,15 +135,7 @@ def test_every_slot_matches_a_numpy_restatement_on_synthetic_rows(robot, nu, nul
         for k, s in enumerate((e % 4, (e // 4) % 4)):
             priv[:, e, nobs + 16 + 3 * nu + k] = rng.integers(0, 2, T) if s == 3 else scripts[s]
     # first episodes: never ending; done at step 0 without / with truncation; done mid-run without / with truncation
-    end_at = np.array([(T + 1, 0, 0, 11, 17)[e % 5] for e in range(n)])
-    with_trunc = np.array([e % 5 in (2, 4) for e in range(n)])
-    done = (rng.uniform(size=(T, n)) < 0.1).astype(np.float32)       # stray done flags after the end must not matter ...
-    for e in range(n):
-        done[:min(end_at[e], T), e] = 0.0                            # ... and none before it
-        if end_at[e] < T:
-            done[end_at[e], e] = 1.0
-    trunc = (done * with_trunc[None]).astype(np.float32)
-    ended = (np.arange(T)[:, None] > end_at[None]).astype(np.float32)
+    end_at, done, trunc, ended = RC.first_episodes(rng, T, n, ends=(T + 1, 0, 0, 11, 17), truncated=(2, 4))
     limit = None
     if not null_limit:
         limit = np.ones(nu, np.float32)
@@ -151,85 +145,7 @@ def test_every_slot_matches_a_numpy_restatement_on_synthetic_rows(robot, nu, nul
         priv[1, 0, fcol] = sat                                       # exactly at the threshold: counted
         priv[1, 4, fcol] = -np.nextafter(sat, np.float32(0))         # one ulp under it: not counted
         priv[2, 0, fcol + 1] = 50.0                                  # a large force on the actuator without a limit
-    want = restate(priv, done, ended, nobs, nu, limit)
-
-    guard = torch.full((n + 3, NACC), 7.0, device="cuda")            # rows past the batch: the tail wave's idle rows must not touch them
-    acc = guard[:n]
-    acc.zero_()
-    tacc = torch.zeros(n, engine.TRACK_NACC, device="cuda")
-    lim_dev = None if limit is None else torch.tensor(limit, device="cuda")
-    priv_d, done_d, trunc_d, ended_d = (torch.tensor(x, device="cuda") for x in (priv, done, trunc, ended))
-    snaps = []
-    for t in range(T):
-        b.priv.copy_(priv_d[t]); b.done.copy_(done_d[t]); b.truncation.copy_(trunc_d[t])
-        tacc[:, engine.TRACK_ENDED] = ended_d[t]
-        b.gait_accumulate(acc, tacc, lim_dev)
-        snaps.append(acc.clone())
-    torch.cuda.synchronize()
-    got = acc.cpu().numpy()
-    compare(got, want, nu, f"{robot} nu={nu}")
-    np.testing.assert_array_equal(guard[n:].cpu().numpy(), 7.0)
-    # rows of envs past their first episode keep their bits: what step end_at - 1 left is what every later step leaves
-    snaps = torch.stack(snaps).cpu().numpy().view(np.int32)
-    for e in range(n):
-        if end_at[e] >= T:
-            continue
-        frozen = snaps[end_at[e] - 1, e] if end_at[e] > 0 else np.zeros(NACC, np.int32)
-        for t in range(end_at[e], T):
-            np.testing.assert_array_equal(snaps[t, e], frozen, err_msg=f"env {e} step {t}")
-    # the run covers what it claims to
-    N = want[:, SAMPLES]
-    assert set(N.astype(int)) == {0, 11, 17, T}
-    assert np.all(got[N == 0] == 0.0)
-    first = [e for e in range(n) if e % 4 == 0 and N[e] >= 11]      # left foot on the scripted sequence
-    assert first and all(want[e, TOUCHDOWNS] >= 4 and want[e, SWING_STEPS_SUM] >= 4 for e in first)
-    never = [e for e in range(n) if e % 4 == 1 and N[e] > 0]
-    assert never and all(want[e, CONTACT] == 0 and want[e, TOUCHDOWNS] == 0 and want[e, AIR_RUN] == N[e] for e in never)
-    always = [e for e in range(n) if e % 4 == 2 and N[e] > 0]
-    assert always and all(want[e, CONTACT] == N[e] and want[e, TOUCHDOWNS] == 0 and want[e, AIR_RUN] == 0 for e in always)
-    assert (want[:, DOUBLE] > 0).any() and (want[:, FLIGHT] > 0).any()
-    if null_limit:
-        assert np.all(got[:, SAT:SAT + 16] == 0.0)
-    else:
-        assert want[0, SAT] >= 1 and np.all(want[:, SAT + 1] == 0) and np.all(want[:, SAT + 3] == 0) and want[:, SAT + 2].sum() > want[:, SAT].sum()
-    b.close()
-
-
-def _checkpoint(tmp_path):
-    import torch
-    from open_duck_playground_amd.ppo.networks import PPONetworks
-    from open_duck_playground_amd.ppo.train import save_checkpoint
-    torch.manual_seed(0)
-    ckpt = str(tmp_path / "fresh.pt")
-    save_checkpoint(ckpt, PPONetworks(101, 212, 14))
-    return ckpt
-
-
-def _run(track, monkeypatch, argv, eager=False):
-    """track.run with its Tracker caught; eager: no graph, and the step's outputs recorded after every step.  Returns (report, tracker, recording)."""
-    real = track.Tracker
-    caught, hist = [], []
-
-    class Caught(real):
-        def __init__(self, *a, **k):
-            if eager:
-                k["use_graph"] = False
-            super().__init__(*a, **k)
-            caught.append(self)
-
-        def step(self):
-            super().step()
-            if eager:
-                bb = self.env.batch
-                hist.append((bb.priv.cpu().numpy(), bb.done.cpu().numpy(), bb.truncation.cpu().numpy()))
-
-    monkeypatch.setattr(track, "Tracker", Caught)
-    try:
-        rep = track.run(track.build_parser().parse_args(argv))
-    finally:
-        monkeypatch.setattr(track, "Tracker", real)
-    assert len(caught) == 1
-    return rep, caught[0], hist
+    return priv, done, trunc, ended, end_at, limit
 
 
 def test_track_gait_end_to_end(tmp_path, monkeypatch):
@@ -237,12 +153,12 @@ def test_track_gait_end_to_end(tmp_path, monkeypatch):
     restatement and `reduce_gait`, reproduces the accumulator (the bounds of the synthetic test) and the report; the graph run's gait
     accumulator has the eager run's bits; without --gait the tracking accumulator has the same bits and the report its old keys."""
     from open_duck_playground_amd import engine, track
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     E, T = 8, 40
     out = tmp_path / "report.json"
     argv = ["--checkpoint", ckpt, "--command", "0.1", "0", "0", "--command", "0", "0", "0.5", "--envs_per_command", str(E), "--episode_length", str(T),
             "--seed", "1", "--output", str(out)]
-    rep_e, tr_e, hist = _run(track, monkeypatch, argv + ["--gait"], eager=True)
+    rep_e, tr_e, hist = RC.run_track(track, monkeypatch, argv + ["--gait"], eager=True)
     assert not rep_e["settings"]["graph"] and rep_e["settings"]["gait"] is True and len(hist) == T
     priv, done = np.stack([h[0] for h in hist]), np.stack([h[1] for h in hist])
     ended = np.concatenate([np.zeros((1, 2 * E)), (np.cumsum(done != 0, 0) > 0)[:-1]]).astype(np.float32)
@@ -253,8 +169,8 @@ def test_track_gait_end_to_end(tmp_path, monkeypatch):
     got_e = tr_e.gait_acc.cpu().numpy()
     compare(got_e, want, 14, "track --gait, eager")
     track_e = tr_e.acc.cpu().numpy()
-    np.testing.assert_array_equal(got_e[:, SAMPLES], track_e[:, engine.TRACK_SAMPLES])     # a gait sample is a velocity sample
-    assert got_e[:, SAMPLES].sum() > 0
+    np.testing.assert_array_equal(got_e[:, engine.GAIT_SAMPLES], track_e[:, engine.TRACK_SAMPLES])     # a gait sample is a velocity sample
+    assert got_e[:, engine.GAIT_SAMPLES].sum() > 0
 
     # the report is reduce_gait of that accumulator; against the restatement every figure is a ratio of two sums (or its root): twice the sum bound
     tol = 2 * (T + 4) * 2.0 ** -23
@@ -278,7 +194,7 @@ def test_track_gait_end_to_end(tmp_path, monkeypatch):
     assert json.load(open(out)) == json.loads(json.dumps(rep_e))
 
     # the graph: one more launch in the captured step, the same bits
-    rep_g, tr_g, _ = _run(track, monkeypatch, argv + ["--gait"])
+    rep_g, tr_g, _ = RC.run_track(track, monkeypatch, argv + ["--gait"])
     assert rep_g["settings"]["graph"]
     np.testing.assert_array_equal(tr_g.gait_acc.cpu().numpy().view(np.int32), got_e.view(np.int32))
     np.testing.assert_array_equal(tr_g.acc.cpu().numpy().view(np.int32), track_e.view(np.int32))
@@ -288,7 +204,7 @@ def test_track_gait_end_to_end(tmp_path, monkeypatch):
     calls = []
     real = engine.Batch.gait_accumulate
     monkeypatch.setattr(engine.Batch, "gait_accumulate", lambda self, *a, **k: (calls.append(1), real(self, *a, **k))[1])
-    rep_p, tr_p, _ = _run(track, monkeypatch, argv)
+    rep_p, tr_p, _ = RC.run_track(track, monkeypatch, argv)
     assert calls == [] and tr_p.gait_acc is None and tr_p.torque_limit is None
     np.testing.assert_array_equal(tr_p.acc.cpu().numpy().view(np.int32), track_e.view(np.int32))
     assert tuple(rep_p) == track.REPORT_KEYS and "gait" not in rep_p["settings"]
@@ -315,12 +231,12 @@ def _flatten(g):
 def test_track_gait_with_a_push_grid(tmp_path, monkeypatch):
     """One command, two pushes, 4 envs per cell: every cell and the command row get a "gait" object, the cells' samples add up to the row's,
     and the push and tracking accumulators have the bits of a run without --gait."""
-    from open_duck_playground_amd import track
-    ckpt = _checkpoint(tmp_path)
+    from open_duck_playground_amd import engine, track
+    ckpt = RC.fresh_checkpoint(tmp_path)
     argv = ["--checkpoint", ckpt, "--command", "0.1", "0", "0", "--push", "0", "0", "--push", "1.5", "0", "--push_at", "10", "--envs_per_command", "4",
             "--episode_length", "40", "--seed", "2", "--output", str(tmp_path / "r.json")]
-    rep_g, tr_g, _ = _run(track, monkeypatch, argv + ["--gait"])
-    rep_p, tr_p, _ = _run(track, monkeypatch, argv)
+    rep_g, tr_g, _ = RC.run_track(track, monkeypatch, argv + ["--gait"])
+    rep_p, tr_p, _ = RC.run_track(track, monkeypatch, argv)
     assert rep_g["settings"]["gait"] is True and "gait" not in rep_p["settings"]
     (row,), (plain,) = rep_g["commands"], rep_p["commands"]
     assert tuple(row) == track.ROW_KEYS + track.PUSH_ROW_KEYS + ("gait",) and tuple(plain) == track.ROW_KEYS + track.PUSH_ROW_KEYS
@@ -331,7 +247,7 @@ def test_track_gait_with_a_push_grid(tmp_path, monkeypatch):
     assert sum(c["gait"]["samples"] for c in row["pushes"]) == row["gait"]["samples"] == row["velocity_samples"] > 0
     np.testing.assert_array_equal(tr_g.push_acc.cpu().numpy().view(np.int32), tr_p.push_acc.cpu().numpy().view(np.int32))
     np.testing.assert_array_equal(tr_g.acc.cpu().numpy().view(np.int32), tr_p.acc.cpu().numpy().view(np.int32))
-    assert tuple(tr_g.gait_acc.shape) == (8, NACC) and tr_p.gait_acc is None
+    assert tuple(tr_g.gait_acc.shape) == (8, engine.GAIT_NACC) and tr_p.gait_acc is None
 
 
 def test_refusals_launch_nothing():
@@ -352,10 +268,10 @@ def test_refusals_launch_nothing():
     for null in ("acc_dev", "priv_dev", "done_dev", "truncation_dev", "track_acc_dev"):
         a = {k: (None if k == null else C.c_void_p(v)) for k, v in good.items()}
         rc = L.odk_gait_accumulate(b._b, a["priv_dev"], a["done_dev"], a["truncation_dev"], a["track_acc_dev"], a["torque_limit_dev"], a["acc_dev"], b._stream())
-        assert rc == ODK_ERR_INVALID, null
+        assert rc == engine.ERR_INVALID, null
         msg = L.odk_last_error().decode()
         assert "odk_gait_accumulate" in msg and null in msg, msg
-    assert L.odk_gait_accumulate(None, *[C.c_void_p(v) for v in good.values()], b._stream()) == ODK_ERR_INVALID
+    assert L.odk_gait_accumulate(None, *[C.c_void_p(v) for v in good.values()], b._stream()) == engine.ERR_INVALID
     assert "batch" in L.odk_last_error().decode()
     # the Python surface: bad accumulators and bad limits are OdkErrors before anything is launched
     bad = [(torch.zeros(n, engine.GAIT_NACC - 1, device="cuda"), tacc, lim), (torch.zeros(n, engine.GAIT_NACC), tacc, lim), (acc.double(), tacc, lim),

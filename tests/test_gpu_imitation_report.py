@@ -14,29 +14,14 @@ import pickle
 import numpy as np
 import pytest
 
+import report_cases as RC
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ASSETS = os.path.join(ROOT, "tests", "assets")
-ODK_ERR_INVALID = -1         # include/odk.h
+G = RC.HEADER         # include/odk.h's constants, by engine's names
 
-# include/odk.h ODK_IMIT_*
-SAMPLES, GATED, SPEED_ERR_SQ_SUM, REF_SPEED_SUM, JOINT_POS_SQ_SUM, JOINT_VEL_SQ_SUM = range(6)
-BOTH, ROBOT_ONLY, REF_ONLY, REF_TOUCHDOWNS, TOUCHDOWNS, LAG_SUM, LAG_ABS_SUM, PREV_CONTACT, PREV_REF, REF_AGE = range(6, 26, 2)
-POS_ERR_SUM, POS_ERR_SQ, POS_ERR_PEAK, VEL_ERR_SQ, RANGE_MIN, RANGE_MAX, REF_RANGE_MIN, REF_RANGE_MAX = range(32, 160, 16)
-NACC, STRIDE = 160, 16
-# float32 running sums of non-negative terms; POS_ERR_SUM is the one signed sum; the rest of the row is counts, peaks, ranges, bookkeeping
-# and the integer lag sums: exact
-SUM_SCALARS = (SPEED_ERR_SQ_SUM, REF_SPEED_SUM, JOINT_POS_SQ_SUM, JOINT_VEL_SQ_SUM)
-SUM_ARRAYS = (POS_ERR_SQ, VEL_ERR_SQ)
 DUCK_MAP = [0, 1, 2, 3, 4, -1, -1, -1, -1, 11, 12, 13, 14, 15]
 PERIOD = 12
-
-
-def planar32(x, y):
-    """the kernel's hypot: float64 squares (exact for float32 inputs) and root, one rounding to float32"""
-    x, y = np.float64(x), np.float64(y)
-    return np.float32(np.sqrt(x * x + y * y))
 
 
 def restate(priv, done, ended, nobs, nu, imap, kc, period):
@@ -45,9 +30,10 @@ def restate(priv, done, ended, nobs, nu, imap, kc, period):
     the command gate and the contact thresholds are float32, in the kernel's order; the sums are float64.  Returns the [n, 160]
     accumulator, per actuator the sum of |dp| (the scale of POS_ERR_SUM's bound) and what the data exercised: folded lags below zero, lags
     above zero, lags of zero, and robot touchdowns before any reference touchdown (not counted)."""
+    planar32 = RC.planar32
     T, n = done.shape
-    A = np.zeros((n, NACC), np.float64)
-    absdp = np.zeros((n, STRIDE), np.float64)
+    A = np.zeros((n, G.IMIT_NACC), np.float64)
+    absdp = np.zeros((n, G.IMIT_STRIDE), np.float64)
     seen = dict(negative=0, positive=0, zero=0, before_reference=0)
     kc = np.asarray(kc, np.float32)
     imap = np.asarray(imap)
@@ -62,76 +48,66 @@ def restate(priv, done, ended, nobs, nu, imap, kc, period):
             P = priv[t, e]
             Q = P[nobs:]
             F = Q[26 + 3 * nu:]
-            first = R[SAMPLES] == 0
-            R[SAMPLES] += 1
+            first = R[G.IMIT_SAMPLES] == 0
+            R[G.IMIT_SAMPLES] += 1
             c = P[6:9]
             cn = np.sqrt(f32(f32(c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]))
-            R[GATED] += 1.0 if cn > f32(0.01) else 0.0
+            R[G.IMIT_GATED] += 1.0 if cn > f32(0.01) else 0.0
             sr = planar32(F[34], F[35])
             ds = f32(planar32(Q[9], Q[10]) - sr)
-            R[SPEED_ERR_SQ_SUM] += np.float64(ds) ** 2
-            R[REF_SPEED_SUM] += np.float64(sr)
+            R[G.IMIT_SPEED_ERR_SQ_SUM] += np.float64(ds) ** 2
+            R[G.IMIT_REF_SPEED_SUM] += np.float64(sr)
             jq = (Q[15 + us] + kc[us]).astype(f32)                # float32 + float32: one rounding, as the kernel's
             rq = F[ri]
             dp = (jq - rq).astype(f32)
             dv = (Q[15 + nu + us] - F[16 + ri]).astype(f32)
             dp64, dv64, jq64, rq64 = (x.astype(np.float64) for x in (dp, dv, jq, rq))
-            R[JOINT_POS_SQ_SUM] += (dp64 ** 2).sum()
-            R[JOINT_VEL_SQ_SUM] += (dv64 ** 2).sum()
-            R[POS_ERR_SUM + us] += dp64
+            R[G.IMIT_JOINT_POS_SQ_SUM] += (dp64 ** 2).sum()
+            R[G.IMIT_JOINT_VEL_SQ_SUM] += (dv64 ** 2).sum()
+            R[G.IMIT_POS_ERR_SUM + us] += dp64
             absdp[e, us] += np.abs(dp64)
-            R[POS_ERR_SQ + us] += dp64 ** 2
-            R[POS_ERR_PEAK + us] = np.maximum(R[POS_ERR_PEAK + us], np.abs(dp64))
-            R[VEL_ERR_SQ + us] += dv64 ** 2
-            R[RANGE_MIN + us] = jq64 if first else np.minimum(R[RANGE_MIN + us], jq64)
-            R[RANGE_MAX + us] = jq64 if first else np.maximum(R[RANGE_MAX + us], jq64)
-            R[REF_RANGE_MIN + us] = rq64 if first else np.minimum(R[REF_RANGE_MIN + us], rq64)
-            R[REF_RANGE_MAX + us] = rq64 if first else np.maximum(R[REF_RANGE_MAX + us], rq64)
+            R[G.IMIT_POS_ERR_SQ + us] += dp64 ** 2
+            R[G.IMIT_POS_ERR_PEAK + us] = np.maximum(R[G.IMIT_POS_ERR_PEAK + us], np.abs(dp64))
+            R[G.IMIT_VEL_ERR_SQ + us] += dv64 ** 2
+            R[G.IMIT_RANGE_MIN + us] = jq64 if first else np.minimum(R[G.IMIT_RANGE_MIN + us], jq64)
+            R[G.IMIT_RANGE_MAX + us] = jq64 if first else np.maximum(R[G.IMIT_RANGE_MAX + us], jq64)
+            R[G.IMIT_REF_RANGE_MIN + us] = rq64 if first else np.minimum(R[G.IMIT_REF_RANGE_MIN + us], rq64)
+            R[G.IMIT_REF_RANGE_MAX + us] = rq64 if first else np.maximum(R[G.IMIT_REF_RANGE_MAX + us], rq64)
             for f in range(2):
                 con, ref = bool(Q[16 + 3 * nu + f] != 0), bool(F[32 + f] > f32(0.5))
-                R[BOTH + f] += con and ref
-                R[ROBOT_ONLY + f] += con and not ref
-                R[REF_ONLY + f] += (not con) and ref
-                if ref and not first and R[PREV_REF + f] == 0:      # the reference first
-                    R[REF_TOUCHDOWNS + f] += 1
-                    R[REF_AGE + f] = 1
-                elif R[REF_AGE + f] > 0:
-                    R[REF_AGE + f] += 1
-                if con and not first and R[PREV_CONTACT + f] == 0:
-                    if R[REF_AGE + f] > 0:
-                        lag = R[REF_AGE + f] - 1
+                R[G.IMIT_BOTH + f] += con and ref
+                R[G.IMIT_ROBOT_ONLY + f] += con and not ref
+                R[G.IMIT_REF_ONLY + f] += (not con) and ref
+                if ref and not first and R[G.IMIT_PREV_REF + f] == 0:      # the reference first
+                    R[G.IMIT_REF_TOUCHDOWNS + f] += 1
+                    R[G.IMIT_REF_AGE + f] = 1
+                elif R[G.IMIT_REF_AGE + f] > 0:
+                    R[G.IMIT_REF_AGE + f] += 1
+                if con and not first and R[G.IMIT_PREV_CONTACT + f] == 0:
+                    if R[G.IMIT_REF_AGE + f] > 0:
+                        lag = R[G.IMIT_REF_AGE + f] - 1
                         if period > 0 and 2 * lag > period:
                             lag -= period
-                        R[TOUCHDOWNS + f] += 1
-                        R[LAG_SUM + f] += lag
-                        R[LAG_ABS_SUM + f] += abs(lag)
+                        R[G.IMIT_TOUCHDOWNS + f] += 1
+                        R[G.IMIT_LAG_SUM + f] += lag
+                        R[G.IMIT_LAG_ABS_SUM + f] += abs(lag)
                         seen["negative" if lag < 0 else "positive" if lag > 0 else "zero"] += 1
                     else:
                         seen["before_reference"] += 1
-                R[PREV_CONTACT + f] = con
-                R[PREV_REF + f] = ref
+                R[G.IMIT_PREV_CONTACT + f] = con
+                R[G.IMIT_PREV_REF + f] = ref
     return A, absdp, seen
 
 
 def compare(got, want, absdp, label):
-    """Counts, peaks, ranges, bookkeeping and the lag sums exact; every float32 running sum of non-negative terms within (N + 4) * 2^-23
-    relative of the float64 sum, N the env's sample count (the bound derived in tests/test_gpu_gait.py::compare: N sequential float32
-    additions, 2^-24 each, and terms that carry at most a few roundings of their own -- a product, a 16-lane tree sum: under 4 * 2^-23
-    together); the signed POS_ERR_SUM within (N + 4) * 2^-23 * sum |dp|."""
-    got = got.astype(np.float64)
-    N = want[:, SAMPLES]
-    sum_cols = list(SUM_SCALARS) + [s + u for s in SUM_ARRAYS for u in range(STRIDE)]
-    signed_cols = [POS_ERR_SUM + u for u in range(STRIDE)]
-    exact_cols = [c for c in range(NACC) if c not in sum_cols + signed_cols]
-    bounds = {c: (N + 4) * 2.0 ** -23 * want[:, c] for c in sum_cols}
-    bounds.update({POS_ERR_SUM + u: (N + 4) * 2.0 ** -23 * absdp[:, u] for u in range(STRIDE)})
-    worst = max(float(np.max(np.abs(got[:, c] - want[:, c]) / np.maximum(b, 1e-300))) for c, b in bounds.items())
-    print(f"{label}: float32 sums, worst error / bound {worst:.3f}")
-    for c in exact_cols:
-        np.testing.assert_array_equal(got[:, c], want[:, c], err_msg=f"{label}: slot {c}")
-    for c, b in bounds.items():
-        err = np.abs(got[:, c] - want[:, c])
-        assert np.all(err <= b), (label, c, float(err.max()), float(b[np.argmax(err - b)]))
+    """Counts, peaks, ranges, bookkeeping and the integer lag sums exact; the float32 running sums within RC.compare_sums' bound: of
+    non-negative terms but for POS_ERR_SUM, the one signed sum, whose scale is sum |dp|."""
+    lanes = range(G.IMIT_STRIDE)
+    sums = [G.IMIT_SPEED_ERR_SQ_SUM, G.IMIT_REF_SPEED_SUM, G.IMIT_JOINT_POS_SQ_SUM, G.IMIT_JOINT_VEL_SQ_SUM]
+    sums += [s + u for s in (G.IMIT_POS_ERR_SQ, G.IMIT_VEL_ERR_SQ) for u in lanes]
+    scales = {c: want[:, c] for c in sums}
+    scales.update({G.IMIT_POS_ERR_SUM + u: absdp[:, u] for u in lanes})
+    RC.compare_sums(got, want, G.IMIT_SAMPLES, scales, label)
 
 
 def _entry(coeffs_lowest_first, period, fps):
@@ -161,7 +137,7 @@ def _batch(robot, nu, n, tmp, imap):
         model = load_task_model("flat_terrain")
         b = engine.Batch(model, n, cfg)
     else:
-        model = Model.from_xml(os.path.join(ASSETS, robot))
+        model = Model.from_xml(os.path.join(RC.ASSETS, robot))
         motion = ReferenceMotion.from_pickle(_write_synthetic(os.path.join(tmp, f"{robot}.pkl"), nu, seed=nu))
         b = engine.Batch(model, n, cfg, prm=motion.prm())
         if imap is not None:
@@ -203,65 +179,52 @@ def synthetic_rows(rng, T, n, nobs, npriv, nu):
     return priv
 
 
+def synthetic_inputs(nobs, npriv, nu):
+    """The host half of `synthetic`, a function of the sizes alone: 70 envs, 40 steps of `synthetic_rows`; first episodes end at step 0,
+    mid-run or never, by done with and without truncation.  Returns (priv [T, n, npriv], done, trunc, ended [T, n], end_at [n])."""
+    n, T = N_ENVS, T_STEPS
+    rng = np.random.default_rng(500 + nu)
+    priv = synthetic_rows(rng, T, n, nobs, npriv, nu)
+    # first episodes: never ending; done at step 0 without / with truncation; done mid-run without / with truncation
+    end_at, done, trunc, ended = RC.first_episodes(rng, T, n, ends=(T + 1, 0, 0, 23, 31), truncated=(2, 4))
+    return priv, done, trunc, ended, end_at
+
+
 @functools.lru_cache(maxsize=None)
 def synthetic(case):
-    """One run per case, shared by the tests below: 70 envs, 40 steps of seeded random privileged rows written straight into the batch's
-    buffers -- no odk_step.  First episodes end at step 0, mid-run or never, by done with and without truncation, and the run sets the
-    tracking accumulator's ENDED column as odk_tracking_accumulate would have."""
+    """One run per case, shared by the tests below: `synthetic_inputs` written straight into the batch's buffers -- no odk_step --, the
+    tracking accumulator's ENDED column set as odk_tracking_accumulate would have."""
     import tempfile
-    import torch
     from open_duck_playground_amd import engine
     robot, nu, given, period = CASES[case]
-    n, T = N_ENVS, T_STEPS
+    n = N_ENVS
     with tempfile.TemporaryDirectory() as tmp:
         model, b = _batch(robot, nu, n, tmp, given)
     imap = DUCK_MAP if given is None else list(given)
     nobs, npriv = b.nobs, b.npriv
     assert tuple(b.priv.shape) == (n, npriv) and nobs + 26 + 3 * nu + 40 <= npriv
-    kc = np.asarray(model.a["key_ctrl"], np.float64).reshape(-1)[:nu].astype(np.float32)
-    rng = np.random.default_rng(500 + nu)
-    priv = synthetic_rows(rng, T, n, nobs, npriv, nu)
-    # first episodes: never ending; done at step 0 without / with truncation; done mid-run without / with truncation
-    end_at = np.array([(T + 1, 0, 0, 23, 31)[e % 5] for e in range(n)])
-    with_trunc = np.array([e % 5 in (2, 4) for e in range(n)])
-    done = (rng.uniform(size=(T, n)) < 0.1).astype(np.float32)       # stray done flags after the end must not matter ...
-    for e in range(n):
-        done[:min(end_at[e], T), e] = 0.0                            # ... and none before it
-        if end_at[e] < T:
-            done[end_at[e], e] = 1.0
-    trunc = (done * with_trunc[None]).astype(np.float32)
-    ended = (np.arange(T)[:, None] > end_at[None]).astype(np.float32)
+    kc = RC.home_pose(model, nu)
+    priv, done, trunc, ended, end_at = synthetic_inputs(nobs, npriv, nu)
     want, absdp, seen = restate(priv, done, ended, nobs, nu, imap, kc, period)
-
-    guard = torch.full((n + 3, NACC), 7.0, device="cuda")            # rows past the batch: the last wave's idle rows must not touch them
-    acc = guard[:n]
-    acc.zero_()
-    tacc = torch.zeros(n, engine.TRACK_NACC, device="cuda")
-    priv_d, done_d, trunc_d, ended_d = (torch.tensor(x, device="cuda") for x in (priv, done, trunc, ended))
-    snaps = []
-    for t in range(T):
-        b.priv.copy_(priv_d[t]); b.done.copy_(done_d[t]); b.truncation.copy_(trunc_d[t])
-        tacc[:, engine.TRACK_ENDED] = ended_d[t]
-        b.imitation_accumulate(acc, tacc, period)
-        snaps.append(acc.clone())
-    torch.cuda.synchronize()
-    res = dict(got=acc.cpu().numpy(), want=want, absdp=absdp, seen=seen, guard=guard[n:].cpu().numpy(), snaps=torch.stack(snaps).cpu().numpy(),
-               imap=imap, end_at=end_at, nu=nu, period=period)
+    got, guard_tail, snaps = RC.drive_rows(b, lambda acc, tacc: b.imitation_accumulate(acc, tacc, period), engine.IMIT_NACC, priv, done, trunc, ended)
+    res = dict(got=got, want=want, absdp=absdp, seen=seen, guard=guard_tail, snaps=snaps, imap=imap, end_at=end_at, nu=nu, period=period)
     b.close()
     return res
 
 
 @pytest.mark.parametrize("case", list(CASES))
 def test_every_slot_matches_a_numpy_restatement_on_synthetic_rows(case):
+    GATED, LAG_SUM, LAG_ABS_SUM, REF_TOUCHDOWNS, TOUCHDOWNS = G.IMIT_GATED, G.IMIT_LAG_SUM, G.IMIT_LAG_ABS_SUM, G.IMIT_REF_TOUCHDOWNS, G.IMIT_TOUCHDOWNS
+    POS_ERR_SQ, RANGE_MIN, RANGE_MAX, REF_RANGE_MIN, REF_RANGE_MAX = G.IMIT_POS_ERR_SQ, G.IMIT_RANGE_MIN, G.IMIT_RANGE_MAX, G.IMIT_REF_RANGE_MIN, G.IMIT_REF_RANGE_MAX
     r = synthetic(case)
     got, want, imap, seen, nu = r["got"], r["want"], r["imap"], r["seen"], r["nu"]
     compare(got, want, r["absdp"], f"{case} nu={nu}")
     np.testing.assert_array_equal(r["guard"], 7.0)
     # the run covers what it claims to
-    N = want[:, SAMPLES]
+    N = want[:, G.IMIT_SAMPLES]
     assert set(N.astype(int)) == {0, 23, 31, T_STEPS}
     assert np.all(got[N == 0] == 0.0)
-    assert np.all(got[:, 26:32] == 0.0)                                # no slot lives there
+    assert np.all(got[:, G.IMIT_REF_AGE + 2:G.IMIT_POS_ERR_SUM] == 0.0)      # no slot lives there
     print(f"{case}: lags {seen}")
     assert seen["positive"] > 20 and seen["zero"] > 0 and seen["before_reference"] > 0
     if r["period"] > 0:
@@ -278,8 +241,8 @@ def test_every_slot_matches_a_numpy_restatement_on_synthetic_rows(case):
     assert np.all(got[whole][:, [REF_TOUCHDOWNS, REF_TOUCHDOWNS + 1, TOUCHDOWNS, TOUCHDOWNS + 1]] >= 2)
     assert 0 < got[N > 0, GATED].min() and np.all(got[N > 0, GATED] < N[N > 0])      # both sides of the gate in every env
     live = N > 0
-    for u in range(STRIDE):
-        cols = [s + u for s in (POS_ERR_SUM, POS_ERR_SQ, POS_ERR_PEAK, VEL_ERR_SQ, RANGE_MIN, RANGE_MAX, REF_RANGE_MIN, REF_RANGE_MAX)]
+    for u in range(G.IMIT_STRIDE):
+        cols = [s + u for s in (G.IMIT_POS_ERR_SUM, POS_ERR_SQ, G.IMIT_POS_ERR_PEAK, G.IMIT_VEL_ERR_SQ, RANGE_MIN, RANGE_MAX, REF_RANGE_MIN, REF_RANGE_MAX)]
         if u >= nu or imap[u] < 0:
             assert np.all(got[:, cols] == 0.0), u                      # a lane past nu, or an actuator the map leaves out, stays 0
         else:
@@ -296,17 +259,10 @@ def test_a_row_that_is_no_sample_keeps_its_bits(case):
     from open_duck_playground_amd import engine
     r = synthetic(case)
     snaps, end_at = r["snaps"].view(np.int32), r["end_at"]
-    checked = 0
-    for e in range(N_ENVS):
-        if end_at[e] >= T_STEPS:
-            continue
-        frozen = snaps[end_at[e] - 1, e] if end_at[e] > 0 else np.zeros(NACC, np.int32)
-        for t in range(end_at[e], T_STEPS):
-            np.testing.assert_array_equal(snaps[t, e], frozen, err_msg=f"env {e} step {t}")
-            checked += 1
-    assert checked > 100
+    assert RC.assert_frozen_after_end(snaps, end_at) > 100
     e = int(np.argmax(end_at > T_STEPS))      # while a live row changes at every step
-    assert all(snaps[t, e, SAMPLES] != snaps[t - 1, e, SAMPLES] for t in range(1, T_STEPS))
+    S, NACC = engine.IMIT_SAMPLES, engine.IMIT_NACC
+    assert all(snaps[t, e, S] != snaps[t - 1, e, S] for t in range(1, T_STEPS))
 
     robot, nu, given, period = CASES[case]
     n = N_ENVS
@@ -331,45 +287,6 @@ def test_a_row_that_is_no_sample_keeps_its_bits(case):
     b.close()
 
 
-def _checkpoint(tmp_path, sizes=(101, 212, 14), name="fresh.pt"):
-    import torch
-    from open_duck_playground_amd.ppo.networks import PPONetworks
-    from open_duck_playground_amd.ppo.train import save_checkpoint
-    torch.manual_seed(0)
-    ckpt = str(tmp_path / name)
-    save_checkpoint(ckpt, PPONetworks(*sizes))
-    return ckpt
-
-
-def _run(track, monkeypatch, argv, eager=False):
-    """track.run with its Tracker caught; eager: no graph, and per step the ENDED column the step's launches saw and the step's outputs.
-    Returns (report, tracker, recording)."""
-    real = track.Tracker
-    caught, hist = [], []
-
-    class Caught(real):
-        def __init__(self, *a, **k):
-            if eager:
-                k["use_graph"] = False
-            super().__init__(*a, **k)
-            caught.append(self)
-
-        def step(self):
-            ended = self.acc[:, 0].cpu().numpy() if eager else None      # ODK_TRACK_ENDED, before this step's tracking launch sets it
-            super().step()
-            if eager:
-                bb = self.env.batch
-                hist.append((bb.priv.cpu().numpy(), bb.done.cpu().numpy(), ended))
-
-    monkeypatch.setattr(track, "Tracker", Caught)
-    try:
-        rep = track.run(track.build_parser().parse_args(argv))
-    finally:
-        monkeypatch.setattr(track, "Tracker", real)
-    assert len(caught) == 1
-    return rep, caught[0], hist
-
-
 EXACT_FIELDS = ("samples", "gated_share", "period_steps", "joint", "frame_joint", "peak_error", "range", "reference_range", "amplitude_ratio", "foot",
                 "contact_agreement", "stance_share", "reference_stance_share", "touchdowns", "reference_touchdowns", "touchdown_lag_steps",
                 "touchdown_lag_s", "touchdown_lag_abs_steps", "contact_term")
@@ -382,13 +299,13 @@ def test_track_imitation_report_end_to_end(tmp_path, monkeypatch):
     accumulator has the same bits and the report its old keys."""
     from open_duck_playground_amd import engine, track
     from open_duck_playground_amd.reference_motion import ReferenceMotion
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     E, T = 8, 60
     out = tmp_path / "report.json"
     argv = ["--checkpoint", ckpt, "--command", "0.1", "0", "0", "--command", "0", "0", "0", "--envs_per_command", str(E), "--episode_length", str(T),
             "--seed", "1", "--output", str(out)]
     on = ["--imitation_report"]
-    rep_e, tr_e, hist = _run(track, monkeypatch, argv + on, eager=True)
+    rep_e, tr_e, hist = RC.run_track_with_ended(track, monkeypatch, argv + on, eager=True)
     period = ReferenceMotion.from_npz().nb_steps_in_period
     assert not rep_e["settings"]["graph"] and rep_e["settings"]["imitation_report"] is True and len(hist) == T
     assert rep_e["settings"]["imitation_period_steps"] == tr_e.period_steps == period > 0
@@ -404,6 +321,7 @@ def test_track_imitation_report_end_to_end(tmp_path, monkeypatch):
     got_e = tr_e.imitation_acc.cpu().numpy()
     compare(got_e, want, absdp, "track --imitation_report, eager")
     track_e = tr_e.acc.cpu().numpy()
+    SAMPLES, GATED = engine.IMIT_SAMPLES, engine.IMIT_GATED
     np.testing.assert_array_equal(got_e[:, SAMPLES], track_e[:, engine.TRACK_SAMPLES])     # an imitation sample is a velocity sample
     assert got_e[:, SAMPLES].sum() > 0
     # the command gate: block 0 moves, block 1 stands
@@ -439,7 +357,7 @@ def test_track_imitation_report_end_to_end(tmp_path, monkeypatch):
     assert json.load(open(out)) == json.loads(json.dumps(rep_e))
 
     # the graph: one more launch in the captured step, the same bits
-    rep_g, tr_g, _ = _run(track, monkeypatch, argv + on)
+    rep_g, tr_g, _ = RC.run_track_with_ended(track, monkeypatch, argv + on)
     assert rep_g["settings"]["graph"]
     np.testing.assert_array_equal(tr_g.imitation_acc.cpu().numpy().view(np.int32), got_e.view(np.int32))
     np.testing.assert_array_equal(tr_g.acc.cpu().numpy().view(np.int32), track_e.view(np.int32))
@@ -449,7 +367,7 @@ def test_track_imitation_report_end_to_end(tmp_path, monkeypatch):
     calls = []
     real = engine.Batch.imitation_accumulate
     monkeypatch.setattr(engine.Batch, "imitation_accumulate", lambda self, *a, **k: (calls.append(1), real(self, *a, **k))[1])
-    rep_p, tr_p, _ = _run(track, monkeypatch, argv)
+    rep_p, tr_p, _ = RC.run_track_with_ended(track, monkeypatch, argv)
     assert calls == [] and tr_p.imitation_acc is None
     np.testing.assert_array_equal(tr_p.acc.cpu().numpy().view(np.int32), track_e.view(np.int32))
     assert tuple(rep_p) == track.REPORT_KEYS and "imitation_report" not in rep_p["settings"]
@@ -463,12 +381,12 @@ def test_track_imitation_report_with_a_push_gait_and_posture(tmp_path, monkeypat
     """One command, two pushes, 4 envs per cell, --gait --posture: every cell and the command row get an "imitation" object, the cells'
     samples add up to the row's, and the other objects and the push, gait, posture and tracking accumulators are those of a run without
     the flag."""
-    from open_duck_playground_amd import track
-    ckpt = _checkpoint(tmp_path)
+    from open_duck_playground_amd import engine, track
+    ckpt = RC.fresh_checkpoint(tmp_path)
     argv = ["--checkpoint", ckpt, "--command", "0.1", "0", "0", "--push", "0", "0", "--push", "1.5", "0", "--push_at", "10", "--envs_per_command", "4",
             "--episode_length", "40", "--seed", "2", "--gait", "--posture", "--output", str(tmp_path / "r.json")]
-    rep_s, tr_s, _ = _run(track, monkeypatch, argv + ["--imitation_report"])
-    rep_p, tr_p, _ = _run(track, monkeypatch, argv)
+    rep_s, tr_s, _ = RC.run_track_with_ended(track, monkeypatch, argv + ["--imitation_report"])
+    rep_p, tr_p, _ = RC.run_track_with_ended(track, monkeypatch, argv)
     assert rep_s["settings"]["imitation_report"] is True and "imitation_report" not in rep_p["settings"]
     (row,), (plain,) = rep_s["commands"], rep_p["commands"]
     assert tuple(row) == track.ROW_KEYS + track.PUSH_ROW_KEYS + ("gait", "posture", "imitation")
@@ -483,7 +401,7 @@ def test_track_imitation_report_with_a_push_gait_and_posture(tmp_path, monkeypat
     assert row["imitation"]["samples"] == row["gait"]["samples"] == row["posture"]["samples"]
     for name in ("push_acc", "gait_acc", "posture_acc", "acc"):
         np.testing.assert_array_equal(getattr(tr_s, name).cpu().numpy().view(np.int32), getattr(tr_p, name).cpu().numpy().view(np.int32), err_msg=name)
-    assert tuple(tr_s.imitation_acc.shape) == (8, NACC) and tr_p.imitation_acc is None
+    assert tuple(tr_s.imitation_acc.shape) == (8, engine.IMIT_NACC) and tr_p.imitation_acc is None
 
 
 def test_a_captured_graph_follows_a_later_joint_map(tmp_path):
@@ -494,7 +412,7 @@ def test_a_captured_graph_follows_a_later_joint_map(tmp_path):
     map_a = [11, 10, -1, 8, 7, 6, 5, 4, -1, 2, 1, 0]
     map_b = [-1, 3, 9, -1, 0, 1, 2, 15, 14, -1, 12, 5]
     model, b = _batch("biped12.xml", nu, n, str(tmp_path), map_a)
-    kc = np.asarray(model.a["key_ctrl"], np.float64).reshape(-1)[:nu].astype(np.float32)
+    kc = RC.home_pose(model, nu)
     rng = np.random.default_rng(77)
     T = 6
     priv = synthetic_rows(rng, T, n, b.nobs, b.npriv, nu)
@@ -502,7 +420,7 @@ def test_a_captured_graph_follows_a_later_joint_map(tmp_path):
     done[3, ::4] = 1.0
     ended = np.concatenate([np.zeros((1, n)), (np.cumsum(done != 0, 0) > 0)[:-1]]).astype(np.float32)
     priv_d, done_d, ended_d = (torch.tensor(x, device="cuda") for x in (priv, done, ended))
-    acc = torch.zeros(n, NACC, device="cuda")
+    acc = torch.zeros(n, engine.IMIT_NACC, device="cuda")
     tacc = torch.zeros(n, engine.TRACK_NACC, device="cuda")
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
@@ -528,7 +446,7 @@ def test_a_captured_graph_follows_a_later_joint_map(tmp_path):
         got = replayed()
         compare(got, want, absdp, f"graph, {label}")
         for u in range(nu):
-            assert (got[:, POS_ERR_SQ + u].max() > 0) == (imap[u] >= 0), (label, u)
+            assert (got[:, engine.IMIT_POS_ERR_SQ + u].max() > 0) == (imap[u] >= 0), (label, u)
     b.close()
 
 
@@ -559,12 +477,12 @@ def test_refusals_launch_nothing(tmp_path):
     # each null pointer, by name
     for null in ("acc_dev", "priv_dev", "done_dev", "truncation_dev", "track_acc_dev"):
         rc, msg = raw(b, null=null)
-        assert rc == ODK_ERR_INVALID and "odk_imitation_accumulate" in msg and null in msg, (null, msg)
+        assert rc == engine.ERR_INVALID and "odk_imitation_accumulate" in msg and null in msg, (null, msg)
     rc, msg = raw(None)
-    assert rc == ODK_ERR_INVALID and "odk_imitation_accumulate" in msg and "batch" in msg
+    assert rc == engine.ERR_INVALID and "odk_imitation_accumulate" in msg and "batch" in msg
     # a negative period
     rc, msg = raw(b, period=-1)
-    assert rc == ODK_ERR_INVALID and "period_steps = -1" in msg, msg
+    assert rc == engine.ERR_INVALID and "period_steps = -1" in msg, msg
     with pytest.raises(engine.OdkError, match="odk_imitation_accumulate: period_steps = -3"):
         b.imitation_accumulate(acc, tacc, -3)
     # bad tensors are OdkErrors before anything is launched
@@ -579,19 +497,19 @@ def test_refusals_launch_nothing(tmp_path):
     cfg.use_imitation = 0
     b.set_config(cfg)
     rc, msg = raw(b)
-    assert rc == ODK_ERR_INVALID and "use_imitation = 0" in msg, msg
+    assert rc == engine.ERR_INVALID and "use_imitation = 0" in msg, msg
     with pytest.raises(engine.OdkError, match="odk_imitation_accumulate: use_imitation = 0"):
         b.imitation_accumulate(acc, tacc, PERIOD)
     b.set_config(engine.default_config())
     # the Standing task: no frame in the row
     st = engine.Batch(duck, n, engine.default_config(standing=True))
     rc, msg = raw(st)
-    assert rc == ODK_ERR_INVALID and "Standing" in msg and "frame" in msg, msg
+    assert rc == engine.ERR_INVALID and "Standing" in msg and "frame" in msg, msg
     st.close()
     # a robot that is not the duck, before it is given a map
     _, other = _batch("biped12.xml", 12, n, str(tmp_path), None)
     rc, msg = raw(other)
-    assert rc == ODK_ERR_INVALID and "no imitation joint map" in msg and "odk_batch_set_imitation_joints" in msg, msg
+    assert rc == engine.ERR_INVALID and "no imitation joint map" in msg and "odk_batch_set_imitation_joints" in msg, msg
     with pytest.raises(engine.OdkError, match="no imitation joint map"):
         other.imitation_accumulate(acc, tacc, PERIOD)
     torch.cuda.synchronize()
@@ -602,7 +520,8 @@ def test_refusals_launch_nothing(tmp_path):
     other.imitation_accumulate(acc, tacc, 0)
     torch.cuda.synchronize()
     got = acc.cpu().numpy()
-    assert np.all(got[:, SAMPLES] == 1.0) and np.all(got[:, 32:] == 0.0) and np.all(got[:, JOINT_POS_SQ_SUM] == 0.0)
+    SAMPLES, JOINT_POS_SQ_SUM = engine.IMIT_SAMPLES, engine.IMIT_JOINT_POS_SQ_SUM
+    assert np.all(got[:, SAMPLES] == 1.0) and np.all(got[:, engine.IMIT_POS_ERR_SUM:] == 0.0) and np.all(got[:, JOINT_POS_SQ_SUM] == 0.0)
     other.close()
     acc.zero_()
     b.imitation_accumulate(acc, tacc, PERIOD)

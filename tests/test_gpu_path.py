@@ -12,22 +12,12 @@ import json
 import numpy as np
 import pytest
 
+import report_cases as RC
+
 pytestmark = pytest.mark.gpu
 
-ODK_ERR_INVALID = -1         # include/odk.h
+G = RC.HEADER         # include/odk.h's constants: G.PATH_*, G.TRACK_*
 f32 = np.float32
-
-# include/odk.h ODK_PATH_*
-NACC, MAX_WP, COURSE_FLOATS = 32, 8, 17
-(START_X, START_Y, START_HX, START_HY, X, Y, HX, HY, LENGTH, TURN, SAMPLES, FELL, FELL_LEG, WP_INDEX, XTRACK_SAMPLES, XTRACK_SQ, XTRACK_PEAK,
- GOAL_DIST, REACHED) = range(19)
-T_NACC, T_ENDED, T_STEPS = 12, 0, 1
-
-
-def planar32(x, y):
-    """hypot through float64 with one rounding to float32, as the kernels form it"""
-    x, y = np.float64(x), np.float64(y)
-    return f32(np.sqrt(x * x + y * y))
 
 
 def pose32(q):
@@ -35,7 +25,7 @@ def pose32(q):
     w, x, y, z = (f32(v) for v in q[3:7])
     hx = f32(1) - f32(2) * (y * y + z * z)
     hy = f32(2) * (x * y + w * z)
-    n = planar32(hx, hy)
+    n = RC.planar32(hx, hy)
     if n < f32(1e-6):
         return f32(q[0]), f32(q[1]), f32(1), f32(0)
     return f32(q[0]), f32(q[1]), f32(hx / n), f32(hy / n)
@@ -47,21 +37,21 @@ def begin32(qpos, acc0):
     for e in range(len(qpos)):
         p = pose32(qpos[e])
         A[e] = 0
-        A[e, START_X:START_X + 4] = p
-        A[e, X:X + 4] = p
+        A[e, G.PATH_START_X:G.PATH_START_X + 4] = p
+        A[e, G.PATH_X:G.PATH_X + 4] = p
     return A
 
 
 def course_of(tab, cmap, e):
     """(count, points [8, 2]) of env e's course, the map entry and the count clamped as the kernels clamp them"""
     W = tab[min(max(int(cmap[e]), 0), len(tab) - 1)]
-    return min(max(int(W[0]), 0), MAX_WP), W[1:].reshape(MAX_WP, 2)
+    return min(max(int(W[0]), 0), G.PATH_MAX_WAYPOINTS), W[1:].reshape(G.PATH_MAX_WAYPOINTS, 2)
 
 
 def start_frame(A, p):
     """(xs, ys): the start-frame position of pose p against row A's start"""
-    shx, shy = A[START_HX], A[START_HY]
-    rx, ry = f32(p[0] - A[START_X]), f32(p[1] - A[START_Y])
+    shx, shy = A[G.PATH_START_HX], A[G.PATH_START_HY]
+    rx, ry = f32(p[0] - A[G.PATH_START_X]), f32(p[1] - A[G.PATH_START_Y])
     return f32(f32(rx * shx) + f32(ry * shy)), f32(f32(shx * ry) - f32(shy * rx))
 
 
@@ -76,62 +66,62 @@ def accumulate32(A, steps, ended, qpos, done, trunc, tab, cmap, radius):
         steps[e] += f32(1)
         if done[e] != 0:
             if trunc[e] == 0:
-                R[FELL], R[FELL_LEG] = f32(1), R[WP_INDEX]
+                R[G.PATH_FELL], R[G.PATH_FELL_LEG] = f32(1), R[G.PATH_WP_INDEX]
             ended[e] = True
             continue
         p = pose32(qpos[e])
-        R[LENGTH] = f32(R[LENGTH] + planar32(f32(p[0] - R[X]), f32(p[1] - R[Y])))
-        R[TURN] = f32(R[TURN] + f32(f32(R[HX] * p[3]) - f32(R[HY] * p[2])))
-        R[SAMPLES] = f32(R[SAMPLES] + f32(1))
-        R[X:X + 4] = p
+        R[G.PATH_LENGTH] = f32(R[G.PATH_LENGTH] + RC.planar32(f32(p[0] - R[G.PATH_X]), f32(p[1] - R[G.PATH_Y])))
+        R[G.PATH_TURN] = f32(R[G.PATH_TURN] + f32(f32(R[G.PATH_HX] * p[3]) - f32(R[G.PATH_HY] * p[2])))
+        R[G.PATH_SAMPLES] = f32(R[G.PATH_SAMPLES] + f32(1))
+        R[G.PATH_X:G.PATH_X + 4] = p
         if tab is None:
             continue
         count, pts = course_of(tab, cmap, e)
-        i = max(int(R[WP_INDEX]), 0)
+        i = max(int(R[G.PATH_WP_INDEX]), 0)
         if i >= count:
             continue
         xs, ys = start_frame(R, p)
         wx, wy = pts[i]
         px, py = pts[i - 1] if i > 0 else (f32(0), f32(0))
-        dist = planar32(f32(wx - xs), f32(wy - ys))
+        dist = RC.planar32(f32(wx - xs), f32(wy - ys))
         ax, ay, qx, qy = f32(wx - px), f32(wy - py), f32(xs - px), f32(ys - py)
         len2 = f32(f32(ax * ax) + f32(ay * ay))
         u = f32(0)
         if len2 > 0:
             u = f32(f32(f32(qx * ax) + f32(qy * ay)) / len2)
             u = min(max(u, f32(0)), f32(1))
-        xt = planar32(f32(qx - f32(u * ax)), f32(qy - f32(u * ay)))
-        R[XTRACK_SAMPLES] = f32(R[XTRACK_SAMPLES] + f32(1))
-        R[XTRACK_SQ] = f32(R[XTRACK_SQ] + f32(xt * xt))
-        R[XTRACK_PEAK] = max(R[XTRACK_PEAK], xt)
+        xt = RC.planar32(f32(qx - f32(u * ax)), f32(qy - f32(u * ay)))
+        R[G.PATH_XTRACK_SAMPLES] = f32(R[G.PATH_XTRACK_SAMPLES] + f32(1))
+        R[G.PATH_XTRACK_SQ] = f32(R[G.PATH_XTRACK_SQ] + f32(xt * xt))
+        R[G.PATH_XTRACK_PEAK] = max(R[G.PATH_XTRACK_PEAK], xt)
         gx, gy = pts[count - 1]
-        R[GOAL_DIST] = planar32(f32(gx - xs), f32(gy - ys))
+        R[G.PATH_GOAL_DIST] = RC.planar32(f32(gx - xs), f32(gy - ys))
         if dist <= radius:
-            R[REACHED + i] = f32(st + f32(1))
-            R[WP_INDEX] = f32(i + 1)
+            R[G.PATH_REACHED + i] = f32(st + f32(1))
+            R[G.PATH_WP_INDEX] = f32(i + 1)
 
 
 def command32(Trow, A, q, count, pts, v_cruise, turn_rate, gain, slow_dist):
     """odk_waypoint_command_apply for one env: ((vx, vy, wz) or None for a row that is not written, the set of branches taken)."""
     v_cruise, turn_rate, gain, slow_dist = f32(v_cruise), f32(turn_rate), f32(gain), f32(slow_dist)
-    if Trow[T_ENDED] != 0:
+    if Trow[G.TRACK_ENDED] != 0:
         return None, {"ended"}
     took = set()
     xs = ys = s = f32(0)
     c, i = f32(1), 0
-    if Trow[T_STEPS] != 0:
+    if Trow[G.TRACK_STEPS] != 0:
         p = pose32(q)
         xs, ys = start_frame(A, p)
-        shx, shy = A[START_HX], A[START_HY]
+        shx, shy = A[G.PATH_START_HX], A[G.PATH_START_HY]
         c = f32(f32(shx * p[2]) + f32(shy * p[3]))
         s = f32(f32(shx * p[3]) - f32(shy * p[2]))
-        i = min(max(int(A[WP_INDEX]), 0), count)
+        i = min(max(int(A[G.PATH_WP_INDEX]), 0), count)
     else:
         took.add("clock0")
     if i >= count:
         return (f32(0), f32(0), f32(0)), took | {"finished"}
     dx, dy = f32(pts[i][0] - xs), f32(pts[i][1] - ys)
-    dist = planar32(dx, dy)
+    dist = RC.planar32(dx, dy)
     if dist < f32(1e-6):
         f, l = f32(1), f32(0)
         took.add("on_target")
@@ -166,8 +156,7 @@ BRANCHES = {"ended", "clock0", "finished", "on_target", "ahead", "ahead_left", "
 
 
 def _duck(n, **overrides):
-    from open_duck_playground_amd import joystick
-    return joystick.Joystick(task="flat_terrain", num_envs=n, config_overrides=overrides or None)
+    return RC.robot_env("duck", n, config_overrides=overrides or None)
 
 
 def quat(yaw=0.0, pitch=0.0, roll=0.0):
@@ -198,7 +187,7 @@ def test_begin_takes_the_start_pose_of_every_env():
             qpos[e, 0:2] = rng.uniform(-2, 2, 2)
             qpos[e, 3:7] = quat(yaw if k in (1, 3, 5) else 0.0, np.pi / 2 if k >= 4 else (pitch if k in (2, 3) else 0.0), roll if k in (2, 3) else 0.0)
     b.set_state(qpos)
-    acc0 = np.full((n + 2, NACC), 9.0, f32)
+    acc0 = np.full((n + 2, G.PATH_NACC), 9.0, f32)
     want = begin32(qpos, acc0)
     big = torch.tensor(acc0, device="cuda")
     b.path_begin(big[:n])
@@ -207,11 +196,11 @@ def test_begin_takes_the_start_pose_of_every_env():
     np.testing.assert_array_equal(got.view(np.int32), want.view(np.int32))
     np.testing.assert_array_equal(got[n:], 9.0)
     # the placement covers what it claims to
-    h = want[:n, START_HX:START_HX + 2]
+    h = want[:n, G.PATH_START_HX:G.PATH_START_HX + 2]
     np.testing.assert_allclose(np.hypot(h[:, 0], h[:, 1]), 1.0, atol=1e-6)
     degenerate = np.arange(n) % 6 >= 4
     np.testing.assert_array_equal(h[degenerate], np.tile(f32([1, 0]), (degenerate.sum(), 1)))
-    assert np.all(h[np.arange(n) % 6 == 1, 1] != 0) and np.all(want[:n, 8:] == 0) and np.all(want[:n, X:X + 4] == want[:n, :4])
+    assert np.all(h[np.arange(n) % 6 == 1, 1] != 0) and np.all(want[:n, G.PATH_LENGTH:] == 0) and np.all(want[:n, G.PATH_X:G.PATH_X + 4] == want[:n, G.PATH_START_X:G.PATH_START_X + 4])
     tilted = np.arange(n) % 6 == 2      # no yaw: pitch shortens the heading vector, roll does not move it; normalised it stays +x
     np.testing.assert_allclose(h[tilted], np.tile(f32([1, 0]), (tilted.sum(), 1)), atol=1e-6)
     b.close()
@@ -230,22 +219,22 @@ def _synthetic_states():
     n = N_SYN
     rng = np.random.default_rng(5)
     courses = [[[0.5, 0.25]], [[0.5, 0.0], [0.5, 0.5], [-0.25, 0.5]], [[0.25 * (k + 1), 0.125 * (k % 3)] for k in range(8)]]
-    tab = np.zeros((3, COURSE_FLOATS), f32)
+    tab = np.zeros((3, G.PATH_COURSE_FLOATS), f32)
     for c, pts in enumerate(courses):
         tab[c, 0] = len(pts)
         tab[c, 1:1 + 2 * len(pts)] = f32(pts).reshape(-1)
     cmap = np.array([e % 3 for e in range(n)], np.int32)
     cmap[290:] = [-1, 7, 3, -5, 100, -1, 7, 3, -5, 100]                       # outside 0 .. 2: clamped, never read past the table
-    tacc = np.zeros((n, T_NACC), f32)
-    tacc[:, 2:] = rng.normal(size=(n, T_NACC - 2)).astype(f32)               # the other slots are not the launch's business
-    pacc = rng.normal(size=(n, NACC)).astype(f32)                            # nor are the path accumulator's sums
+    tacc = np.zeros((n, G.TRACK_NACC), f32)
+    tacc[:, G.TRACK_SAMPLES:] = rng.normal(size=(n, G.TRACK_NACC - G.TRACK_SAMPLES)).astype(f32)      # the other slots are not the launch's business
+    pacc = rng.normal(size=(n, G.PATH_NACC)).astype(f32)                            # nor are the path accumulator's sums
     qpos7 = np.zeros((n, 7))
     for e in range(n):
         name, bearing, dist, which = CASES[(e // 3) % len(CASES)]
         count, pts = course_of(tab, cmap, e)
         i = {"last": count - 1, "first": 0, "count": count, None: (e // (3 * len(CASES))) % count}[which]
-        tacc[e, T_STEPS], tacc[e, T_ENDED] = (0.0 if name == "clock0" else 1.0 + e % 7), (1.0 if name == "ended" else 0.0)
-        pacc[e, WP_INDEX] = i
+        tacc[e, G.TRACK_STEPS], tacc[e, G.TRACK_ENDED] = (0.0 if name == "clock0" else 1.0 + e % 7), (1.0 if name == "ended" else 0.0)
+        pacc[e, G.PATH_WP_INDEX] = i
         exact = name in EXACT
         yaw0, s0 = (0.0, np.zeros(2)) if exact else (rng.uniform(-np.pi, np.pi), rng.uniform(-1, 1, 2))
         psi = 0.0 if exact else rng.uniform(-np.pi, np.pi)                    # the start-frame heading
@@ -259,7 +248,7 @@ def _synthetic_states():
         tilt = (0.0, 0.0) if exact else rng.uniform(-0.2, 0.2, 2)
         qpos7[e, 3:7] = quat(yaw0 + psi, *tilt)
         start = (s0[0], s0[1], np.cos(yaw0), np.sin(yaw0))
-        pacc[e, START_X:START_X + 4] = np.nan if name == "clock0" else f32(start)      # at clock 0 the start slots are not read
+        pacc[e, G.PATH_START_X:G.PATH_START_X + 4] = np.nan if name == "clock0" else f32(start)      # at clock 0 the start slots are not read
     return dict(tab=tab, cmap=cmap, tacc=tacc, pacc=pacc, qpos7=qpos7.astype(f32))
 
 
@@ -353,7 +342,7 @@ def test_accumulate_over_a_real_rollout():
     n, T = ROLL_N, ROLL_T
     env = _duck(n, episode_length=ROLL_EPISODE)
     b = env.batch
-    tab = np.zeros((1, COURSE_FLOATS), f32)
+    tab = np.zeros((1, G.PATH_COURSE_FLOATS), f32)
     tab[0, 0], tab[0, 1:7] = 3, f32(COURSE).reshape(-1)
     cmap = np.zeros(n, np.int32)
     tab_d, cmap_d = torch.tensor(tab, device="cuda"), torch.tensor(cmap, device="cuda")
@@ -361,12 +350,12 @@ def test_accumulate_over_a_real_rollout():
     push, kicks = torch.zeros(n, 2, device="cuda"), torch.tensor(_kicks(), device="cuda")
     b.bind_pushes(push)
     env.reset(ROLL_SEED)
-    acc_c, acc_o = torch.full((n, NACC), 7.0, device="cuda"), torch.full((n, NACC), 7.0, device="cuda")
+    acc_c, acc_o = torch.full((n, G.PATH_NACC), 7.0, device="cuda"), torch.full((n, G.PATH_NACC), 7.0, device="cuda")
     tacc = torch.zeros(n, engine.TRACK_NACC, device="cuda")
     b.path_begin(acc_c)
     b.path_begin(acc_o)
     torch.cuda.synchronize()
-    want_c = begin32(b.get_state()[0], np.full((n, NACC), 7.0, f32))
+    want_c = begin32(b.get_state()[0], np.full((n, G.PATH_NACC), 7.0, f32))
     want_o = want_c.copy()
     np.testing.assert_array_equal(acc_c.cpu().numpy().view(np.int32), want_c.view(np.int32))
     steps_c, ended_c, steps_o, ended_o = np.zeros(n, f32), np.zeros(n, bool), np.zeros(n, f32), np.zeros(n, bool)
@@ -387,17 +376,17 @@ def test_accumulate_over_a_real_rollout():
             np.testing.assert_array_equal(acc_c.cpu().numpy().view(np.int32), want_c.view(np.int32), err_msg=f"course, step {t}")
             np.testing.assert_array_equal(acc_o.cpu().numpy().view(np.int32), want_o.view(np.int32), err_msg=f"odometry, step {t}")
     got, odo, tr = acc_c.cpu().numpy(), acc_o.cpu().numpy(), tacc.cpu().numpy()
-    np.testing.assert_array_equal(tr[:, T_STEPS], steps_c)
-    fell, first, all3 = got[:, FELL] != 0, got[:, REACHED] > 0, got[:, WP_INDEX] == 3
+    np.testing.assert_array_equal(tr[:, G.TRACK_STEPS], steps_c)
+    fell, first, all3 = got[:, G.PATH_FELL] != 0, got[:, G.PATH_REACHED] > 0, got[:, G.PATH_WP_INDEX] == 3
     print(f"fell {int(fell.sum())}, survived {int((~fell).sum())}, reached the first point {int(first.sum())}, the second "
-          f"{int((got[:, REACHED + 1] > 0).sum())}, all three {int(all3.sum())}")
+          f"{int((got[:, G.PATH_REACHED + 1] > 0).sum())}, all three {int(all3.sum())}")
     assert fell.sum() >= 4 and (~fell).sum() >= 4 and first.sum() >= 4 and all3.sum() >= 1
-    assert np.all(ended_c) and (got[fell, FELL_LEG] > 0).any() and (got[fell, FELL_LEG] == 0).any()
+    assert np.all(ended_c) and (got[fell, G.PATH_FELL_LEG] > 0).any() and (got[fell, G.PATH_FELL_LEG] == 0).any()
     # the odometry slots do not depend on the course, and without one the course slots stay 0
-    np.testing.assert_array_equal(odo[:, :FELL + 1].view(np.int32), got[:, :FELL + 1].view(np.int32))
-    assert np.all(odo[:, FELL_LEG:] == 0) and np.all(got[:, REACHED + 3:] == 0)
-    assert np.all(got[:, SAMPLES] == tr[:, 2]) and got[:, LENGTH].max() > 0.2 and np.all(got[:, XTRACK_SAMPLES] <= got[:, SAMPLES])
-    reached = got[:, REACHED:REACHED + 3]
+    np.testing.assert_array_equal(odo[:, :G.PATH_FELL + 1].view(np.int32), got[:, :G.PATH_FELL + 1].view(np.int32))
+    assert np.all(odo[:, G.PATH_FELL_LEG:] == 0) and np.all(got[:, G.PATH_REACHED + 3:] == 0)
+    assert np.all(got[:, G.PATH_SAMPLES] == tr[:, G.TRACK_SAMPLES]) and got[:, G.PATH_LENGTH].max() > 0.2 and np.all(got[:, G.PATH_XTRACK_SAMPLES] <= got[:, G.PATH_SAMPLES])
+    reached = got[:, G.PATH_REACHED:G.PATH_REACHED + 3]
     assert np.all((reached[:, 1] == 0) | (reached[:, 1] > reached[:, 0])) and np.all((reached[:, 2] == 0) | (reached[:, 2] > reached[:, 1]))
     b.bind_pushes(None)
     b.bind_commands(None)
@@ -458,7 +447,7 @@ def test_the_closed_loop_eager_captured_and_replayed():
         np.testing.assert_array_equal(e["obs"][t].view(np.int32), e["cmds"][t].view(np.int32), err_msg=f"step {t}")
     assert len({c.tobytes() for c in e["cmds"]}) > LOOP_T // 2 and np.all(e["cmds"][:, :, 1] == 0) and np.all(e["cmds"][:, :, 3:] == 0)
     assert np.abs(e["cmds"][:, :, 2]).max() <= f32(0.6) and e["cmds"][:, :, 0].max() < 0.1001 and e["cmds"][:, :, 0].min() >= 0
-    assert e["path_acc"][:, SAMPLES].sum() > 0 and e["gait_acc"].any() and e["fall_acc"].any()
+    assert e["path_acc"][:, G.PATH_SAMPLES].sum() > 0 and e["gait_acc"].any() and e["fall_acc"].any()
     g = _closed_loop(track, "graph")
     assert g["graph"]
     for k in ("at_reset", "cmds", "obs", "acc", "path_acc", "gait_acc", "fall_acc"):
@@ -480,69 +469,39 @@ def test_the_closed_loop_eager_captured_and_replayed():
 
 
 # ---- track --path / --waypoints
-def _checkpoint(tmp_path):
-    import torch
-    from open_duck_playground_amd.ppo.networks import PPONetworks
-    from open_duck_playground_amd.ppo.train import save_checkpoint
-    torch.manual_seed(0)
-    ckpt = str(tmp_path / "fresh.pt")
-    save_checkpoint(ckpt, PPONetworks(101, 212, 14))
-    return ckpt
-
-
 def _run(track, monkeypatch, argv, eager=False):
-    """track.run with its Tracker caught; eager: no graph, and the state after the reset and the flags and state after every step.
-    Returns (report, tracker, recording)."""
+    """RC.run_track recording the state after the reset and the flags and state after every step."""
     import torch
-    real = track.Tracker
-    caught, hist = [], []
 
-    class Caught(real):
-        def __init__(self, *a, **k):
-            if eager:
-                k["use_graph"] = False
-            super().__init__(*a, **k)
-            caught.append(self)
+    def after_reset(tr):
+        torch.cuda.synchronize()
+        return tr.env.batch.get_state()[0]
 
-        def reset(self, seed):
-            super().reset(seed)
-            if eager:
-                torch.cuda.synchronize()
-                hist.append(self.env.batch.get_state()[0])
+    def after_step(tr, _):
+        b = tr.env.batch
+        return b.done.cpu().numpy(), b.truncation.cpu().numpy(), b.get_state()[0]
 
-        def step(self):
-            super().step()
-            if eager:
-                bb = self.env.batch
-                hist.append((bb.done.cpu().numpy(), bb.truncation.cpu().numpy(), bb.get_state()[0]))
-
-    monkeypatch.setattr(track, "Tracker", Caught)
-    try:
-        rep = track.run(track.build_parser().parse_args(argv))
-    finally:
-        monkeypatch.setattr(track, "Tracker", real)
-    assert len(caught) == 1
-    return rep, caught[0], hist
+    return RC.run_track(track, monkeypatch, argv, eager, after_step=after_step, after_reset=after_reset)
 
 
 def test_track_path_equals_the_reduction_of_the_restatement(tmp_path, monkeypatch):
     """`--path` on two `--command` rows, 8 envs each, 40 steps: the eager run's recording pushed through the restatement has the path
     accumulator's bits, so each row's "path" is `reduce_path` of it; the captured run has the same bits and rows."""
     from open_duck_playground_amd import track
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     E, T = 8, 40
     cmds = [[0.1, 0.0, 0.0], [0.0, 0.05, 0.5]]
     argv = ["--checkpoint", ckpt, "--command", *map(str, cmds[0]), "--command", *map(str, cmds[1]), "--envs_per_command", str(E), "--episode_length", str(T),
             "--seed", "3", "--path", "--output", str(tmp_path / "r.json")]
     rep, tr, hist = _run(track, monkeypatch, argv, eager=True)
     assert len(hist) == T + 1 and rep["settings"]["path"] is True and not rep["settings"]["graph"]
-    want = begin32(hist[0], np.zeros((2 * E, NACC), f32))
+    want = begin32(hist[0], np.zeros((2 * E, G.PATH_NACC), f32))
     steps, ended = np.zeros(2 * E, f32), np.zeros(2 * E, bool)
     for done, trunc, qpos in hist[1:]:
         accumulate32(want, steps, ended, qpos, done, trunc, None, None, 0.0)
     got = tr.path_acc.cpu().numpy()
     np.testing.assert_array_equal(got.view(np.int32), want.view(np.int32))
-    assert got[:, SAMPLES].sum() > 0 and tr.course is None
+    assert got[:, G.PATH_SAMPLES].sum() > 0 and tr.course is None
     rows = [track.command_row(c) for c in cmds]
     ref = track.reduce_path(want, rows, E, rep["settings"]["dt"])
     for row, cmd, path in zip(rep["commands"], rows, ref):
@@ -559,7 +518,7 @@ def test_track_waypoints_has_the_pinned_keys(tmp_path, monkeypatch):
     """Two courses, 8 envs each, with `--gait`: every row has the old keys, then "path" and "course" (the follower drives, so they lead),
     then "gait"; `ideal` is None; the settings carry the follower's."""
     from open_duck_playground_amd import track
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     courses = ["0.1,0 | 0.1,0.1 | 0,0.1", "-0.05,0.05"]
     # (a course that begins with a minus sign goes in with `=`: argparse reads a bare one as a flag)
     argv = ["--checkpoint", ckpt, "--waypoints", courses[0], "--waypoints=" + courses[1], "--envs_per_command", "8", "--episode_length", "40", "--seed", "3",
@@ -576,7 +535,7 @@ def test_track_waypoints_has_the_pinned_keys(tmp_path, monkeypatch):
         assert tuple(row["course"]) == track.COURSE_KEYS and row["course"]["points"] == pts and len(row["course"]["falls_by_leg"]) == len(pts) + 1
         assert len(row["course"]["waypoints"]) == len(pts) and all(tuple(w) == track.COURSE_POINT_KEYS for w in row["course"]["waypoints"])
         assert 0.0 <= row["course"]["completed_fraction"] <= 1.0 and row["course"]["cross_track_rms_m"] is not None
-    assert tuple(tr.course.shape) == (2, COURSE_FLOATS) and tuple(tr.path_acc.shape) == (16, NACC)
+    assert tuple(tr.course.shape) == (2, G.PATH_COURSE_FLOATS) and tuple(tr.path_acc.shape) == (16, G.PATH_NACC)
     np.testing.assert_array_equal(tr.course_map.cpu().numpy(), np.repeat(np.arange(2), 8))
     np.testing.assert_array_equal(tr.course.cpu().numpy(), track.course_table([track.parse_waypoints(c) for c in courses]))
     # a speed beyond the env's command range is refused once the env exists, naming the range
@@ -589,7 +548,7 @@ def test_no_flag_means_no_launch_and_the_old_report(tmp_path, monkeypatch):
     run with the Tracker built by hand without the reports."""
     import torch
     from open_duck_playground_amd import engine, track
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     E, T, seed = 8, 40, 5
     calls = []
     for name in ("path_begin", "path_accumulate", "waypoint_command_apply"):
@@ -630,9 +589,9 @@ def test_refusals_launch_nothing():
     b = env.batch
     env.reset(1)
     b.step(torch.zeros(n, 14, device="cuda"))
-    acc = torch.full((n, NACC), 3.0, device="cuda")
+    acc = torch.full((n, G.PATH_NACC), 3.0, device="cuda")
     tacc = torch.zeros(n, engine.TRACK_NACC, device="cuda")
-    tab = torch.zeros(2, COURSE_FLOATS, device="cuda")
+    tab = torch.zeros(2, G.PATH_COURSE_FLOATS, device="cuda")
     tab[:, 0], tab[:, 1] = 1.0, 0.5
     cmap = torch.zeros(n, dtype=torch.int32, device="cuda")
     cmd = torch.full((n, 7), 9.0, device="cuda")
@@ -661,7 +620,7 @@ def test_refusals_launch_nothing():
     # no commands bound: the follower needs them, the accumulator does not
     assert b.commands is None
     rc, msg = apply(b._b)
-    assert rc == ODK_ERR_INVALID and "odk_waypoint_command_apply: no commands bound (odk_batch_bind_commands)" in msg, msg
+    assert rc == G.ERR_INVALID and "odk_waypoint_command_apply: no commands bound (odk_batch_bind_commands)" in msg, msg
     with pytest.raises(engine.OdkError, match="waypoint_command_apply: no commands bound"):
         b.waypoint_command_apply(tab, cmap, tacc, acc, 0.1, 0.6, 2.0, 0.1)
     b.bind_commands(cmd)
@@ -671,31 +630,31 @@ def test_refusals_launch_nothing():
                             ("odk_waypoint_command_apply", apply, ("course_dev", "course_of_env_dev", "track_acc_dev", "path_acc_dev"))):
         for null in names:
             rc, msg = call(b._b, null=null)
-            assert rc == ODK_ERR_INVALID and f"{fn}: null {null}" in msg, (fn, null, msg)
+            assert rc == G.ERR_INVALID and f"{fn}: null {null}" in msg, (fn, null, msg)
         rc, msg = call(None)
-        assert rc == ODK_ERR_INVALID and f"{fn}: null batch" in msg, msg
+        assert rc == G.ERR_INVALID and f"{fn}: null batch" in msg, msg
     # ncourse outside its range: with a course at least one, without one exactly 0
     for bad in (0, -2):
         rc, msg = accumulate(b._b, ncourse=bad)
-        assert rc == ODK_ERR_INVALID and "odk_path_accumulate: ncourse" in msg, (bad, msg)
+        assert rc == G.ERR_INVALID and "odk_path_accumulate: ncourse" in msg, (bad, msg)
         rc, msg = apply(b._b, ncourse=bad)
-        assert rc == ODK_ERR_INVALID and "odk_waypoint_command_apply: ncourse" in msg, (bad, msg)
+        assert rc == G.ERR_INVALID and "odk_waypoint_command_apply: ncourse" in msg, (bad, msg)
     rc, msg = accumulate(b._b, ncourse=2, course=False)
-    assert rc == ODK_ERR_INVALID and "null course_dev with ncourse = 2" in msg, msg
+    assert rc == G.ERR_INVALID and "null course_dev with ncourse = 2" in msg, msg
     # a parameter that is negative or not finite; a gain or a slow-down distance of 0
     for bad in (-0.1, float("nan"), float("inf")):
         rc, msg = accumulate(b._b, radius=bad)
-        assert rc == ODK_ERR_INVALID and "odk_path_accumulate: radius" in msg, (bad, msg)
+        assert rc == G.ERR_INVALID and "odk_path_accumulate: radius" in msg, (bad, msg)
         with pytest.raises(engine.OdkError, match="path_accumulate: radius"):
             b.path_accumulate(acc, tacc, tab, cmap, bad)
         for key, name in (("v", "v_cruise"), ("rate", "turn_rate"), ("gain", "heading_gain"), ("slow", "slow_dist")):
             rc, msg = apply(b._b, **{key: bad})
-            assert rc == ODK_ERR_INVALID and f"odk_waypoint_command_apply: {name}" in msg, (name, bad, msg)
+            assert rc == G.ERR_INVALID and f"odk_waypoint_command_apply: {name}" in msg, (name, bad, msg)
         with pytest.raises(engine.OdkError, match="waypoint_command_apply: turn_rate"):
             b.waypoint_command_apply(tab, cmap, tacc, acc, 0.1, bad, 2.0, 0.1)
     for key, name in (("gain", "heading_gain"), ("slow", "slow_dist")):
         rc, msg = apply(b._b, **{key: 0.0})
-        assert rc == ODK_ERR_INVALID and name in msg, (name, msg)
+        assert rc == G.ERR_INVALID and name in msg, (name, msg)
     with pytest.raises(engine.OdkError, match="waypoint_command_apply: slow_dist"):
         b.waypoint_command_apply(tab, cmap, tacc, acc, 0.1, 0.6, 2.0, 0.0)
     # a course count outside its range never reaches the device: the builder refuses it
@@ -729,7 +688,7 @@ def test_refusals_launch_nothing():
     b.waypoint_command_apply(tab, cmap, tacc, acc, 0.1, 0.6, 2.0, 0.1)
     torch.cuda.synchronize()
     got = acc.cpu().numpy()
-    assert np.all(got[:, SAMPLES] == 1.0) and np.all(got[:, XTRACK_SAMPLES] == 1.0) and np.all(got[:, REACHED + 1:] == 0.0)
+    assert np.all(got[:, G.PATH_SAMPLES] == 1.0) and np.all(got[:, G.PATH_XTRACK_SAMPLES] == 1.0) and np.all(got[:, G.PATH_REACHED + 1:] == 0.0)
     np.testing.assert_array_equal(cmd.cpu().numpy()[:, 3:], 9.0)
     np.testing.assert_array_equal(cmd.cpu().numpy()[:, :3], np.tile(f32([0.1, 0, 0]), (n, 1)))      # clock 0: the point (0.5, 0) is dead ahead
     b.bind_commands(None)

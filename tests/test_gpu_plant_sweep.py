@@ -6,19 +6,11 @@ import json
 import numpy as np
 import pytest
 
+import report_cases as RC
+
 pytestmark = pytest.mark.gpu
 
 E, T = 16, 40
-
-
-def _checkpoint(tmp_path):
-    import torch
-    from open_duck_playground_amd.ppo.networks import PPONetworks
-    from open_duck_playground_amd.ppo.train import save_checkpoint
-    torch.manual_seed(0)
-    ckpt = str(tmp_path / "fresh.pt")
-    save_checkpoint(ckpt, PPONetworks(101, 212, 14))
-    return ckpt
 
 
 def _argv(ckpt, *extra):
@@ -52,7 +44,7 @@ def test_track_without_plant_flags_is_the_report_of_before(tmp_path, monkeypatch
     """no --plant*, --randomize or --noise_level: no parameter is set, no delay bound, and the report is the one `reduce_tracking` gives
     for a plain Tracker run of the same layout and seed -- keys, settings and every figure"""
     from open_duck_playground_amd import engine, track
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     calls = []
     for name in ("bind_action_delays", "set_param"):
         real = getattr(engine.Batch, name)
@@ -80,7 +72,7 @@ def test_a_cell_is_the_plant_it_names(tmp_path):
     all-ones cell with delay=random equals the corresponding block of a run with no plant at all, bit for bit."""
     import torch
     from open_duck_playground_amd import engine, track
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     args = track.build_parser().parse_args(_argv(ckpt, "--plant", "kp=0.6,delay=2", "--plant", "kp=1.0", "--output", str(tmp_path / "r.json")))
     kept = []
     real_tracker = track.Tracker
@@ -130,7 +122,7 @@ def test_a_cell_is_the_plant_it_names(tmp_path):
 
 def test_track_plant_sweep_end_to_end(tmp_path):
     from open_duck_playground_amd import track
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     out = tmp_path / "report.json"
     args = track.build_parser().parse_args(_argv(ckpt, "--plant_grid", "kp=0.5:1.0:2,delay=0:2:3", "--gait", "--falls", "--output", str(out)))
     rep = track.run(args)

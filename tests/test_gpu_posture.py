@@ -16,25 +16,13 @@ import os
 import numpy as np
 import pytest
 
+import report_cases as RC
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ASSETS = os.path.join(ROOT, "tests", "assets")
-ODK_ERR_INVALID = -1         # include/odk.h
+G = RC.HEADER         # include/odk.h's constants, by engine's names
 
-# include/odk.h ODK_POSTURE_*
-SAMPLES, DRIFT_SPEED_SUM, YAW_RATE_SQ_SUM, ROLLPITCH_RATE_SQ_SUM, TILT_SUM, TILT_PEAK, HEIGHT_SUM, LEG_POSE_SUM, LEG_VEL_SUM, HEAD_SQERR_SUM = range(10)
-ANGLE_SUM, ERR_SQ_SUM, ERR_PEAK, LAST_OFF = 16, 20, 24, 28
-NACC = 32
-# float32 running sums of non-negative terms; ANGLE_SUM is the one signed sum; the rest of the row is counts, peaks and LAST_OFF: exact
-SUM_SCALARS = (DRIFT_SPEED_SUM, YAW_RATE_SQ_SUM, ROLLPITCH_RATE_SQ_SUM, TILT_SUM, HEIGHT_SUM, LEG_POSE_SUM, LEG_VEL_SUM, HEAD_SQERR_SUM)
 TOL = 0.1
-
-
-def planar32(x, y):
-    """the kernel's hypot: float64 squares (exact for float32 inputs) and root, one rounding to float32"""
-    x, y = np.float64(x), np.float64(y)
-    return np.float32(np.sqrt(x * x + y * y))
 
 
 def restate(priv, done, ended, cmd, nobs, nu, hmap, kc, tol):
@@ -43,7 +31,7 @@ def restate(priv, done, ended, cmd, nobs, nu, hmap, kc, tol):
     and its comparison with `tol` are float32, in the kernel's order; the sums are float64.  Returns the [n, 32] accumulator and, per slot,
     the sum of |angle| (the scale of ANGLE_SUM's bound)."""
     T, n = done.shape
-    A = np.zeros((n, NACC), np.float64)
+    A = np.zeros((n, G.POSTURE_NACC), np.float64)
     absang = np.zeros((n, 4), np.float64)
     tol32 = np.float32(tol)
     kc = np.asarray(kc, np.float32)
@@ -57,59 +45,41 @@ def restate(priv, done, ended, cmd, nobs, nu, hmap, kc, tol):
             P32 = priv[t, e]
             Q = P32[nobs:].astype(np.float64)
             dq, v = Q[15:15 + nu], Q[15 + nu:15 + 2 * nu]
-            N = R[SAMPLES]
-            R[SAMPLES] += 1
-            R[DRIFT_SPEED_SUM] += planar32(P32[nobs + 9], P32[nobs + 10])
-            R[YAW_RATE_SQ_SUM] += Q[2] * Q[2]
-            R[ROLLPITCH_RATE_SQ_SUM] += Q[0] * Q[0] + Q[1] * Q[1]
-            tilt = planar32(P32[nobs + 6], P32[nobs + 7])
-            R[TILT_SUM] += tilt
-            R[TILT_PEAK] = max(R[TILT_PEAK], float(tilt))
-            R[HEIGHT_SUM] += Q[15 + 2 * nu]
-            R[LEG_POSE_SUM] += np.abs(dq[leg]).sum()
-            R[LEG_VEL_SUM] += np.abs(v[leg]).sum()
+            N = R[G.POSTURE_SAMPLES]
+            R[G.POSTURE_SAMPLES] += 1
+            R[G.POSTURE_DRIFT_SPEED_SUM] += RC.planar32(P32[nobs + 9], P32[nobs + 10])
+            R[G.POSTURE_YAW_RATE_SQ_SUM] += Q[2] * Q[2]
+            R[G.POSTURE_ROLLPITCH_RATE_SQ_SUM] += Q[0] * Q[0] + Q[1] * Q[1]
+            tilt = RC.planar32(P32[nobs + 6], P32[nobs + 7])
+            R[G.POSTURE_TILT_SUM] += tilt
+            R[G.POSTURE_TILT_PEAK] = max(R[G.POSTURE_TILT_PEAK], float(tilt))
+            R[G.POSTURE_HEIGHT_SUM] += Q[15 + 2 * nu]
+            R[G.POSTURE_LEG_POSE_SUM] += np.abs(dq[leg]).sum()
+            R[G.POSTURE_LEG_VEL_SUM] += np.abs(v[leg]).sum()
             for k, u in enumerate(hmap):
                 if u < 0:
                     continue
                 angle = np.float32(P32[nobs + 15 + u] + kc[u])          # float32 + float32: one rounding, as the kernel's
                 err = np.float32(angle - cmd[e, 3 + k])
                 sq = np.float64(err) * np.float64(err)
-                R[ANGLE_SUM + k] += angle
+                R[G.POSTURE_ANGLE_SUM + k] += angle
                 absang[e, k] += abs(np.float64(angle))
-                R[ERR_SQ_SUM + k] += sq
-                R[HEAD_SQERR_SUM] += sq
-                R[ERR_PEAK + k] = max(R[ERR_PEAK + k], float(np.abs(err)))
+                R[G.POSTURE_ERR_SQ_SUM + k] += sq
+                R[G.POSTURE_HEAD_SQERR_SUM] += sq
+                R[G.POSTURE_ERR_PEAK + k] = max(R[G.POSTURE_ERR_PEAK + k], float(np.abs(err)))
                 if np.abs(err) > tol32:
-                    R[LAST_OFF + k] = N + 1
+                    R[G.POSTURE_LAST_OFF + k] = N + 1
     return A, absang
 
 
 def compare(got, want, absang, label):
-    """Counts, peaks and LAST_OFF exact; every float32 running sum of non-negative terms within (N + 4) * 2^-23 relative of the float64 sum,
-    N the env's sample count (the bound derived in tests/test_gpu_gait.py::compare: N sequential float32 additions, 2^-24 each, and terms
-    that carry at most a few roundings of their own -- a product, a root, a 16-lane tree sum: under 4 * 2^-23 together); the signed
-    ANGLE_SUM within (N + 4) * 2^-23 * sum |angle|."""
-    got = got.astype(np.float64)
-    N = want[:, SAMPLES]
-    sum_cols = list(SUM_SCALARS) + [ERR_SQ_SUM + k for k in range(4)]
-    angle_cols = [ANGLE_SUM + k for k in range(4)]
-    exact_cols = [c for c in range(NACC) if c not in sum_cols + angle_cols]
-    bounds = {c: (N + 4) * 2.0 ** -23 * want[:, c] for c in sum_cols}
-    bounds.update({ANGLE_SUM + k: (N + 4) * 2.0 ** -23 * absang[:, k] for k in range(4)})
-    worst = max(float(np.max(np.abs(got[:, c] - want[:, c]) / np.maximum(b, 1e-300))) for c, b in bounds.items())
-    print(f"{label}: float32 sums, worst error / bound {worst:.3f}")
-    for c in exact_cols:
-        np.testing.assert_array_equal(got[:, c], want[:, c], err_msg=f"{label}: slot {c}")
-    for c, b in bounds.items():
-        err = np.abs(got[:, c] - want[:, c])
-        assert np.all(err <= b), (label, c, float(err.max()), float(b[np.argmax(err - b)]))
-
-
-def _robot_env(robot, n):
-    from open_duck_playground_amd import joystick
-    if robot == "duck":
-        return joystick.Joystick(task="flat_terrain", num_envs=n)
-    return joystick.Joystick(xml_path=os.path.join(ASSETS, robot), num_envs=n)
+    """Counts, peaks and LAST_OFF exact; the float32 running sums within RC.compare_sums' bound: of non-negative terms but for ANGLE_SUM,
+    the one signed sum, whose scale is sum |angle|."""
+    sums = [G.POSTURE_DRIFT_SPEED_SUM, G.POSTURE_YAW_RATE_SQ_SUM, G.POSTURE_ROLLPITCH_RATE_SQ_SUM, G.POSTURE_TILT_SUM, G.POSTURE_HEIGHT_SUM,
+            G.POSTURE_LEG_POSE_SUM, G.POSTURE_LEG_VEL_SUM, G.POSTURE_HEAD_SQERR_SUM] + [G.POSTURE_ERR_SQ_SUM + k for k in range(4)]
+    scales = {c: want[:, c] for c in sums}
+    scales.update({G.POSTURE_ANGLE_SUM + k: absang[:, k] for k in range(4)})
+    RC.compare_sums(got, want, G.POSTURE_SAMPLES, scales, label)
 
 
 # robot, nu, the map given to Batch.set_head_joints (None: the batch's default)
@@ -123,41 +93,19 @@ N_ENVS, T_STEPS = 37, 24
 OFF_UNTIL = 7         # patterns 1 and 2: outside the tolerance over the steps before this one
 
 
-@functools.lru_cache(maxsize=None)
-def synthetic(case):
-    """One run per case, shared by the tests below: 37 envs (two full waves of four rows ... and a tail wave with one live row), 24 steps of
-    seeded random privileged rows and command rows written straight into the batch's buffers -- no odk_step.  First episodes end at step 0,
-    mid-run or never, by done with and without truncation, and the run sets the tracking accumulator's ENDED column as
-    odk_tracking_accumulate would have.  The head error of slot k in env e follows pattern (e + k) % 3: 0 never outside the tolerance; 1
-    outside over the first 7 steps, then inside; 2 like 1 and outside again at the env's last sample.  |err| is below 0.08 inside and in
-    0.15 .. 0.5 outside: at least 0.02 from tol = 0.1, so the float32 comparison cannot tie."""
-    import torch
-    from open_duck_playground_amd import engine
-    robot, nu, given = CASES[case]
+def synthetic_inputs(nobs, npriv, nu, hmap, kc):
+    """The host half of `synthetic`, a function of the sizes, the head-joint map and the home pose alone: 37 envs, 24 steps of seeded random
+    privileged rows and command rows.  First episodes end at step 0, mid-run or never, by done with and without truncation.  The head error
+    of slot k in env e follows pattern (e + k) % 3: 0 never outside the tolerance; 1 outside over the first 7 steps, then inside; 2 like 1
+    and outside again at the env's last sample.  |err| is below 0.08 inside and in 0.15 .. 0.5 outside: at least 0.02 from tol = 0.1, so
+    the float32 comparison cannot tie.  Returns (priv [T, n, npriv], done, trunc, ended [T, n], cmd [n, 7], end_at [n], pattern [n, 4])."""
     n, T = N_ENVS, T_STEPS
-    env = _robot_env(robot, n)
-    b = env.batch
-    assert b.model.nu == nu
-    if given is not None:
-        b.set_head_joints(given)
-    hmap = [5, 6, 7, 8] if given is None else list(given)
-    nobs, npriv = b.nobs, b.npriv
-    assert tuple(b.priv.shape) == (n, npriv) and nobs + 16 + 2 * nu <= npriv
-    kc = np.asarray(env.mj_model.a["key_ctrl"], np.float64).reshape(-1)[:nu].astype(np.float32)
     rng = np.random.default_rng(300 + nu)
     priv = rng.normal(0.0, 1.0, (T, n, npriv)).astype(np.float32)
     priv[:, :, nobs + 15 + 2 * nu] = rng.uniform(0.1, 0.2, (T, n)).astype(np.float32)          # a root height is positive
     cmd = rng.uniform(-1.0, 1.0, (n, 7)).astype(np.float32)
     # first episodes: never ending; done at step 0 without / with truncation; done mid-run without / with truncation
-    end_at = np.array([(T + 1, 0, 0, 11, 17)[e % 5] for e in range(n)])
-    with_trunc = np.array([e % 5 in (2, 4) for e in range(n)])
-    done = (rng.uniform(size=(T, n)) < 0.1).astype(np.float32)       # stray done flags after the end must not matter ...
-    for e in range(n):
-        done[:min(end_at[e], T), e] = 0.0                            # ... and none before it
-        if end_at[e] < T:
-            done[end_at[e], e] = 1.0
-    trunc = (done * with_trunc[None]).astype(np.float32)
-    ended = (np.arange(T)[:, None] > end_at[None]).astype(np.float32)
+    end_at, done, trunc, ended = RC.first_episodes(rng, T, n, ends=(T + 1, 0, 0, 11, 17), truncated=(2, 4))
     last_sample = np.minimum(end_at, T) - 1
     pattern = np.array([[(e + k) % 3 for k in range(4)] for e in range(n)])
     for k, u in enumerate(hmap):
@@ -172,23 +120,32 @@ def synthetic(case):
             mag = np.where(out, rng.uniform(0.15, 0.5, T), rng.uniform(0.0, 0.08, T)) * rng.choice([-1.0, 1.0], T)
             target = (cmd[e, 3 + k] + mag.astype(np.float32)).astype(np.float32)
             priv[:, e, nobs + 15 + u] = (target - kc[u]).astype(np.float32)
-    want, absang = restate(priv, done, ended, cmd, nobs, nu, hmap, kc, TOL)
+    return priv, done, trunc, ended, cmd, end_at, pattern
 
-    guard = torch.full((n + 3, NACC), 7.0, device="cuda")            # rows past the batch: the tail wave's idle rows must not touch them
-    acc = guard[:n]
-    acc.zero_()
-    tacc = torch.zeros(n, engine.TRACK_NACC, device="cuda")
+
+@functools.lru_cache(maxsize=None)
+def synthetic(case):
+    """One run per case, shared by the tests below: `synthetic_inputs` written straight into the batch's buffers -- no odk_step -- of 37 envs
+    (two full waves of four rows ... and a tail wave with one live row), the tracking accumulator's ENDED column set as
+    odk_tracking_accumulate would have."""
+    import torch
+    from open_duck_playground_amd import engine
+    robot, nu, given = CASES[case]
+    n = N_ENVS
+    env = RC.robot_env(robot, n)
+    b = env.batch
+    assert b.model.nu == nu
+    if given is not None:
+        b.set_head_joints(given)
+    hmap = [5, 6, 7, 8] if given is None else list(given)
+    nobs, npriv = b.nobs, b.npriv
+    assert tuple(b.priv.shape) == (n, npriv) and nobs + 16 + 2 * nu <= npriv
+    kc = RC.home_pose(env.mj_model, nu)
+    priv, done, trunc, ended, cmd, end_at, pattern = synthetic_inputs(nobs, npriv, nu, hmap, kc)
+    want, absang = restate(priv, done, ended, cmd, nobs, nu, hmap, kc, TOL)
     b.bind_commands(torch.tensor(cmd, device="cuda"))
-    priv_d, done_d, trunc_d, ended_d = (torch.tensor(x, device="cuda") for x in (priv, done, trunc, ended))
-    snaps = []
-    for t in range(T):
-        b.priv.copy_(priv_d[t]); b.done.copy_(done_d[t]); b.truncation.copy_(trunc_d[t])
-        tacc[:, engine.TRACK_ENDED] = ended_d[t]
-        b.posture_accumulate(acc, tacc, TOL)
-        snaps.append(acc.clone())
-    torch.cuda.synchronize()
-    res = dict(got=acc.cpu().numpy(), want=want, absang=absang, guard=guard[n:].cpu().numpy(), snaps=torch.stack(snaps).cpu().numpy(), hmap=hmap,
-               end_at=end_at, pattern=pattern, nu=nu)
+    got, guard_tail, snaps = RC.drive_rows(b, lambda acc, tacc: b.posture_accumulate(acc, tacc, TOL), engine.POSTURE_NACC, priv, done, trunc, ended)
+    res = dict(got=got, want=want, absang=absang, guard=guard_tail, snaps=snaps, hmap=hmap, end_at=end_at, pattern=pattern, nu=nu)
     b.bind_commands(None)
     b.close()
     return res
@@ -196,18 +153,19 @@ def synthetic(case):
 
 @pytest.mark.parametrize("case", list(CASES))
 def test_every_slot_matches_a_numpy_restatement_on_synthetic_rows(case):
+    HEAD_SQERR_SUM, ANGLE_SUM, ERR_PEAK, LAST_OFF = G.POSTURE_HEAD_SQERR_SUM, G.POSTURE_ANGLE_SUM, G.POSTURE_ERR_PEAK, G.POSTURE_LAST_OFF
     r = synthetic(case)
     got, want, hmap, pattern = r["got"], r["want"], r["hmap"], r["pattern"]
     compare(got, want, r["absang"], f"{case} nu={r['nu']}")
     np.testing.assert_array_equal(r["guard"], 7.0)
     # the run covers what it claims to
-    N = want[:, SAMPLES]
+    N = want[:, G.POSTURE_SAMPLES]
     assert set(N.astype(int)) == {0, 11, 17, T_STEPS}
     assert np.all(got[N == 0] == 0.0)
-    assert np.all(got[:, 10:16] == 0.0)                                # no slot lives there
+    assert np.all(got[:, HEAD_SQERR_SUM + 1:ANGLE_SUM] == 0.0)         # no slot lives there
     live = N > 0
     for k, u in enumerate(hmap):
-        cols = [s + k for s in (ANGLE_SUM, ERR_SQ_SUM, ERR_PEAK, LAST_OFF)]
+        cols = [s + k for s in (ANGLE_SUM, G.POSTURE_ERR_SQ_SUM, ERR_PEAK, LAST_OFF)]
         if u < 0:
             assert np.all(got[:, cols] == 0.0)                         # an unmapped slot stays 0
             continue
@@ -221,68 +179,24 @@ def test_every_slot_matches_a_numpy_restatement_on_synthetic_rows(case):
         assert np.all(got[:, HEAD_SQERR_SUM] == 0.0) and np.all(got[:, ANGLE_SUM:] == 0.0)
     else:
         assert np.all(got[live, HEAD_SQERR_SUM] > 0.0)
-    assert np.all(got[live, LEG_POSE_SUM] > 0.0) and np.all(got[live, LEG_VEL_SUM] > 0.0) and np.all(got[live, TILT_PEAK] > 0.0)
+    assert np.all(got[live, G.POSTURE_LEG_POSE_SUM] > 0.0) and np.all(got[live, G.POSTURE_LEG_VEL_SUM] > 0.0)
+    assert np.all(got[live, G.POSTURE_TILT_PEAK] > 0.0)
 
 
 @pytest.mark.parametrize("case", list(CASES))
 def test_a_row_that_is_no_sample_keeps_its_bits(case):
     """Rows of envs past their first episode (and of the done step that ends it): what step end_at - 1 left is what every later step leaves."""
+    from open_duck_playground_amd import engine
     r = synthetic(case)
     snaps, end_at = r["snaps"].view(np.int32), r["end_at"]
-    checked = 0
-    for e in range(N_ENVS):
-        if end_at[e] >= T_STEPS:
-            continue
-        frozen = snaps[end_at[e] - 1, e] if end_at[e] > 0 else np.zeros(NACC, np.int32)
-        for t in range(end_at[e], T_STEPS):
-            np.testing.assert_array_equal(snaps[t, e], frozen, err_msg=f"env {e} step {t}")
-            checked += 1
-    assert checked > 100
+    assert RC.assert_frozen_after_end(snaps, end_at) > 100
     # while a live row changes at every step
     e = int(np.argmax(end_at > T_STEPS))
-    assert all(snaps[t, e, SAMPLES] != snaps[t - 1, e, SAMPLES] for t in range(1, T_STEPS))
+    S = engine.POSTURE_SAMPLES
+    assert all(snaps[t, e, S] != snaps[t - 1, e, S] for t in range(1, T_STEPS))
 
 
 ENV_SIZES = {"joystick": (101, 212, 14), "standing": (85, 153, 14)}      # the duck's observation / privileged / action sizes
-
-
-def _checkpoint(tmp_path, sizes, name="fresh.pt"):
-    import torch
-    from open_duck_playground_amd.ppo.networks import PPONetworks
-    from open_duck_playground_amd.ppo.train import save_checkpoint
-    torch.manual_seed(0)
-    ckpt = str(tmp_path / name)
-    save_checkpoint(ckpt, PPONetworks(*sizes))
-    return ckpt
-
-
-def _run(track, monkeypatch, argv, eager=False):
-    """track.run with its Tracker caught; eager: no graph, and per step the ENDED column the step's launches saw and the step's outputs.
-    Returns (report, tracker, recording)."""
-    real = track.Tracker
-    caught, hist = [], []
-
-    class Caught(real):
-        def __init__(self, *a, **k):
-            if eager:
-                k["use_graph"] = False
-            super().__init__(*a, **k)
-            caught.append(self)
-
-        def step(self):
-            ended = self.acc[:, 0].cpu().numpy() if eager else None      # ODK_TRACK_ENDED, before this step's tracking launch sets it
-            super().step()
-            if eager:
-                bb = self.env.batch
-                hist.append((bb.priv.cpu().numpy(), bb.done.cpu().numpy(), ended))
-
-    monkeypatch.setattr(track, "Tracker", Caught)
-    try:
-        rep = track.run(track.build_parser().parse_args(argv))
-    finally:
-        monkeypatch.setattr(track, "Tracker", real)
-    assert len(caught) == 1
-    return rep, caught[0], hist
 
 
 def _flatten(g):
@@ -305,13 +219,13 @@ def test_track_posture_end_to_end(tmp_path, monkeypatch, env_name):
     and tracking accumulators have the eager run's bits; without --posture the tracking accumulator has the same bits and the report its
     old keys."""
     from open_duck_playground_amd import engine, track
-    ckpt = _checkpoint(tmp_path, ENV_SIZES[env_name])
+    ckpt = RC.fresh_checkpoint(tmp_path, ENV_SIZES[env_name])
     E, T, tol = 8, 40, 0.15
     out = tmp_path / "report.json"
     argv = ["--checkpoint", ckpt, "--env", env_name, "--command", "0", "0", "0", "0.3", "0.2", "-0.5", "0.1", "--command", "0.05", "0", "0", "-0.2", "0", "0.8",
             "0", "--envs_per_command", str(E), "--episode_length", str(T), "--seed", "1", "--output", str(out)]
     on = ["--posture", "--posture_tolerance", str(tol)]
-    rep_e, tr_e, hist = _run(track, monkeypatch, argv + on, eager=True)
+    rep_e, tr_e, hist = RC.run_track_with_ended(track, monkeypatch, argv + on, eager=True)
     assert not rep_e["settings"]["graph"] and rep_e["settings"]["posture"] is True and rep_e["settings"]["posture_tolerance"] == tol and len(hist) == T
     priv, done, ended = (np.stack([h[i] for h in hist]) for i in range(3))
     np.testing.assert_array_equal(ended, np.concatenate([np.zeros((1, 2 * E)), (np.cumsum(done != 0, 0) > 0)[:-1]]))
@@ -325,8 +239,8 @@ def test_track_posture_end_to_end(tmp_path, monkeypatch, env_name):
     got_e = tr_e.posture_acc.cpu().numpy()
     compare(got_e, want, absang, f"track --posture --env {env_name}, eager")
     track_e = tr_e.acc.cpu().numpy()
-    np.testing.assert_array_equal(got_e[:, SAMPLES], track_e[:, engine.TRACK_SAMPLES])     # a posture sample is a velocity sample
-    assert got_e[:, SAMPLES].sum() > 0
+    np.testing.assert_array_equal(got_e[:, engine.POSTURE_SAMPLES], track_e[:, engine.TRACK_SAMPLES])     # a posture sample is a velocity sample
+    assert got_e[:, engine.POSTURE_SAMPLES].sum() > 0
 
     # the report is reduce_posture of that accumulator; against the restatement the exact slots give equal figures and every mean is a ratio
     # of two sums (or its root): twice the sum bound -- for the signed mean_angle at the scale of the mean |angle|
@@ -353,7 +267,7 @@ def test_track_posture_end_to_end(tmp_path, monkeypatch, env_name):
     assert json.load(open(out)) == json.loads(json.dumps(rep_e))
 
     # the graph: one more launch in the captured step, the same bits
-    rep_g, tr_g, _ = _run(track, monkeypatch, argv + on)
+    rep_g, tr_g, _ = RC.run_track_with_ended(track, monkeypatch, argv + on)
     assert rep_g["settings"]["graph"]
     np.testing.assert_array_equal(tr_g.posture_acc.cpu().numpy().view(np.int32), got_e.view(np.int32))
     np.testing.assert_array_equal(tr_g.acc.cpu().numpy().view(np.int32), track_e.view(np.int32))
@@ -363,7 +277,7 @@ def test_track_posture_end_to_end(tmp_path, monkeypatch, env_name):
     calls = []
     real = engine.Batch.posture_accumulate
     monkeypatch.setattr(engine.Batch, "posture_accumulate", lambda self, *a, **k: (calls.append(1), real(self, *a, **k))[1])
-    rep_p, tr_p, _ = _run(track, monkeypatch, argv + ["--posture_tolerance", "0.3"])
+    rep_p, tr_p, _ = RC.run_track_with_ended(track, monkeypatch, argv + ["--posture_tolerance", "0.3"])
     assert calls == [] and tr_p.posture_acc is None
     np.testing.assert_array_equal(tr_p.acc.cpu().numpy().view(np.int32), track_e.view(np.int32))
     assert tuple(rep_p) == track.REPORT_KEYS and "posture" not in rep_p["settings"] and "posture_tolerance" not in rep_p["settings"]
@@ -376,12 +290,12 @@ def test_track_posture_end_to_end(tmp_path, monkeypatch, env_name):
 def test_track_posture_with_a_push_grid_and_gait(tmp_path, monkeypatch):
     """One command, a push grid of two magnitudes, 4 envs per cell, --gait: every cell and the command row get a "posture" object, the cells'
     samples add up to the row's, and the push, gait and tracking accumulators have the bits of a run without --posture."""
-    from open_duck_playground_amd import track
-    ckpt = _checkpoint(tmp_path, ENV_SIZES["joystick"])
+    from open_duck_playground_amd import engine, track
+    ckpt = RC.fresh_checkpoint(tmp_path, ENV_SIZES["joystick"])
     argv = ["--checkpoint", ckpt, "--command", "0.1", "0", "0", "0.2", "0", "0.4", "0", "--push_grid", "magnitude=0:1.5:2", "--push_at", "10",
             "--envs_per_command", "4", "--episode_length", "40", "--seed", "2", "--gait", "--output", str(tmp_path / "r.json")]
-    rep_s, tr_s, _ = _run(track, monkeypatch, argv + ["--posture"])
-    rep_p, tr_p, _ = _run(track, monkeypatch, argv)
+    rep_s, tr_s, _ = RC.run_track_with_ended(track, monkeypatch, argv + ["--posture"])
+    rep_p, tr_p, _ = RC.run_track_with_ended(track, monkeypatch, argv)
     assert rep_s["settings"]["posture"] is True and rep_s["settings"]["posture_tolerance"] == track.DEFAULT_POSTURE_TOLERANCE
     assert "posture" not in rep_p["settings"]
     (row,), (plain,) = rep_s["commands"], rep_p["commands"]
@@ -394,7 +308,7 @@ def test_track_posture_with_a_push_grid_and_gait(tmp_path, monkeypatch):
     assert sum(c["posture"]["samples"] for c in row["pushes"]) == row["posture"]["samples"] == row["velocity_samples"] > 0
     for name in ("push_acc", "gait_acc", "acc"):
         np.testing.assert_array_equal(getattr(tr_s, name).cpu().numpy().view(np.int32), getattr(tr_p, name).cpu().numpy().view(np.int32), err_msg=name)
-    assert tuple(tr_s.posture_acc.shape) == (8, NACC) and tr_p.posture_acc is None
+    assert tuple(tr_s.posture_acc.shape) == (8, engine.POSTURE_NACC) and tr_p.posture_acc is None
 
 
 def test_track_posture_standing_on_another_robot(tmp_path, monkeypatch):
@@ -402,11 +316,11 @@ def test_track_posture_standing_on_another_robot(tmp_path, monkeypatch):
     are the map's, the unmapped slots are absent and their accumulator entries 0.  The Joystick task on that robot has no map: --posture
     says so and points to Standing's flag."""
     from open_duck_playground_amd import track
-    xml = os.path.join(ASSETS, "tail_biped.xml")
-    ckpt = _checkpoint(tmp_path, (90, 161, 15))                      # Standing's sizes at nu = 15
+    xml = os.path.join(RC.ASSETS, "tail_biped.xml")
+    ckpt = RC.fresh_checkpoint(tmp_path, (90, 161, 15))                      # Standing's sizes at nu = 15
     argv = ["--checkpoint", ckpt, "--env", "standing", "--xml", xml, "--head_joints", "neck_pitch=tail_pitch_1,head_roll=tail_roll", "--command", "0", "0", "0",
             "0.3", "0", "0", "-0.2", "--envs_per_command", "8", "--episode_length", "20", "--seed", "3", "--output", str(tmp_path / "r.json"), "--posture"]
-    rep, tr, _ = _run(track, monkeypatch, argv)
+    rep, tr, _ = RC.run_track_with_ended(track, monkeypatch, argv)
     assert tr.env.head_joints == [6, -1, -1, 9]
     (row,) = rep["commands"]
     g = row["posture"]
@@ -415,9 +329,9 @@ def test_track_posture_standing_on_another_robot(tmp_path, monkeypatch):
     assert g["neck_pitch"]["command"] == pytest.approx(0.3) and g["head_roll"]["command"] == pytest.approx(-0.2)
     assert g["samples"] == row["velocity_samples"] > 0 and g["stillness"]["root_height_mean"] > 0
     acc = tr.posture_acc.cpu().numpy()
-    for s in (ANGLE_SUM, ERR_SQ_SUM, ERR_PEAK, LAST_OFF):
+    for s in (G.POSTURE_ANGLE_SUM, G.POSTURE_ERR_SQ_SUM, G.POSTURE_ERR_PEAK, G.POSTURE_LAST_OFF):
         assert np.all(acc[:, [s + 1, s + 2]] == 0.0)
-    assert np.all(acc[acc[:, SAMPLES] > 0][:, [ERR_SQ_SUM, ERR_SQ_SUM + 3]] > 0.0)
+    assert np.all(acc[acc[:, G.POSTURE_SAMPLES] > 0][:, [G.POSTURE_ERR_SQ_SUM, G.POSTURE_ERR_SQ_SUM + 3]] > 0.0)
     with pytest.raises(SystemExit, match="no head-joint map.*--env standing --head_joints"):
         track.run(track.build_parser().parse_args(["--checkpoint", ckpt, "--xml", xml, "--command", "0", "0", "0", "--envs_per_command", "8",
                                                    "--episode_length", "5", "--posture"]))
@@ -446,20 +360,20 @@ def test_refusals_launch_nothing():
     # no commands bound: the C call and the Python surface
     assert b.commands is None
     rc, msg = raw(b._b)
-    assert rc == ODK_ERR_INVALID and "odk_posture_accumulate" in msg and "no commands bound" in msg, msg
+    assert rc == engine.ERR_INVALID and "odk_posture_accumulate" in msg and "no commands bound" in msg, msg
     with pytest.raises(engine.OdkError, match="posture_accumulate: no commands bound"):
         b.posture_accumulate(acc, tacc, 0.1)
     b.bind_commands(torch.zeros(n, 7, device="cuda"))
     # each null pointer, by name
     for null in ("acc_dev", "priv_dev", "done_dev", "truncation_dev", "track_acc_dev"):
         rc, msg = raw(b._b, null=null)
-        assert rc == ODK_ERR_INVALID and "odk_posture_accumulate" in msg and null in msg, (null, msg)
+        assert rc == engine.ERR_INVALID and "odk_posture_accumulate" in msg and null in msg, (null, msg)
     rc, msg = raw(None)
-    assert rc == ODK_ERR_INVALID and "batch" in msg
+    assert rc == engine.ERR_INVALID and "batch" in msg
     # a tolerance that is negative or not finite
     for tol in (-0.1, float("nan"), float("inf")):
         rc, msg = raw(b._b, tol=tol)
-        assert rc == ODK_ERR_INVALID and "tol" in msg, (tol, msg)
+        assert rc == engine.ERR_INVALID and "tol" in msg, (tol, msg)
         with pytest.raises(engine.OdkError, match="tol"):
             b.posture_accumulate(acc, tacc, tol)
     # bad tensors are OdkErrors before anything is launched
@@ -478,7 +392,7 @@ def test_refusals_launch_nothing():
     b.close()
 
     # a Joystick batch of a robot that is not the duck has no head-joint map until it is given one; an all -1 map is a map
-    other = joystick.Joystick(xml_path=os.path.join(ASSETS, "tail_biped.xml"), num_envs=n)
+    other = joystick.Joystick(xml_path=os.path.join(RC.ASSETS, "tail_biped.xml"), num_envs=n)
     ob = other.batch
     other.reset(1)
     ob.step(torch.zeros(n, 15, device="cuda"))
@@ -492,7 +406,8 @@ def test_refusals_launch_nothing():
     ob.posture_accumulate(acc, tacc, 0.1)
     torch.cuda.synchronize()
     got = acc.cpu().numpy()
-    assert got[:, SAMPLES].sum() > 0 and np.all(got[:, HEAD_SQERR_SUM] == 0.0) and np.all(got[:, ANGLE_SUM:] == 0.0)
-    assert np.all(got[got[:, SAMPLES] > 0, HEIGHT_SUM] > 0.0)
+    S = engine.POSTURE_SAMPLES
+    assert got[:, S].sum() > 0 and np.all(got[:, engine.POSTURE_HEAD_SQERR_SUM] == 0.0) and np.all(got[:, engine.POSTURE_ANGLE_SUM:] == 0.0)
+    assert np.all(got[got[:, S] > 0, engine.POSTURE_HEIGHT_SUM] > 0.0)
     ob.bind_commands(None)
     ob.close()

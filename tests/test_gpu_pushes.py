@@ -7,11 +7,12 @@ import json
 import numpy as np
 import pytest
 
+import report_cases as RC
 from test_gpu_env import ENV_BOUNDS, SET_ASIDE, _errs, _ill_resets, _mk, _new_W, _resync, _step_and_compare
 
 pytestmark = pytest.mark.gpu
 
-ODK_ERR_INVALID = -1         # include/odk.h
+G = RC.HEADER                # include/odk.h's constants: G.PUSH_*
 PARITY_STEPS = 40
 PARITY_EPISODE = 25          # every env truncates at its 25th step: the steps after it start from the auto-reset's state
 # (task, standing, domain randomisation, seed of reset / actions / kicks).  The set-aside share of a case is decided by the oracle alone
@@ -302,20 +303,21 @@ def _restate(priv, done, trunc, cmd, rows, nobs, lin_tol, ang_tol):
     largest pre-push term per env)."""
     T, n = done.shape
     f = np.float32
-    A = np.zeros((n, 10), np.float64)
+    A = np.zeros((n, G.PUSH_NACC), np.float64)
     big = np.zeros(n, np.float64)
     for e in range(n):
         ended, steps, pushed = False, 0, False
+        R = A[e]
         for t in range(T):
             if ended:
                 break
             if not pushed and (rows[t, e, 0] != 0 or rows[t, e, 1] != 0):
                 pushed = True
-                A[e, 0], A[e, 1] = 1, steps
-            since = steps - A[e, 1] + 1
+                R[G.PUSH_PUSHED], R[G.PUSH_PUSH_AT] = 1, steps
+            since = steps - R[G.PUSH_PUSH_AT] + 1
             if done[t, e] != 0:
                 if pushed and trunc[t, e] == 0:
-                    A[e, 2], A[e, 3] = 1, since
+                    R[G.PUSH_FELL], R[G.PUSH_STEPS_TO_FALL] = 1, since
                 ended = True
                 continue
             P = priv[t, e]
@@ -323,12 +325,12 @@ def _restate(priv, done, trunc, cmd, rows, nobs, lin_tol, ang_tol):
             lin = f(np.sqrt(np.float64(ex) * np.float64(ex) + np.float64(ey) * np.float64(ey)))
             ang = np.abs(f(P[nobs + 2] - cmd[e, 2]))
             if not pushed:
-                A[e, 7] += float(lin); A[e, 8] += 1
+                R[G.PUSH_PRE_LIN_ERR_SUM] += float(lin); R[G.PUSH_PRE_SAMPLES] += 1
                 big[e] = max(big[e], float(lin))
             else:
                 if lin > f(lin_tol) or ang > f(ang_tol):
-                    A[e, 4] = since
-                A[e, 5], A[e, 6] = max(A[e, 5], float(lin)), max(A[e, 6], float(ang))
+                    R[G.PUSH_LAST_OFF] = since
+                R[G.PUSH_PEAK_LIN_ERR], R[G.PUSH_PEAK_ANG_ERR] = max(R[G.PUSH_PEAK_LIN_ERR], float(lin)), max(R[G.PUSH_PEAK_ANG_ERR], float(ang))
             steps += 1
     return A, big
 
@@ -374,21 +376,21 @@ def test_accumulator_matches_a_numpy_restatement():
         priv.append(b.priv.cpu().numpy()); done.append(b.done.cpu().numpy()); trunc.append(b.truncation.cpu().numpy())
     got = acc.cpu().numpy()
     want, big = _restate(np.stack(priv), np.stack(done), np.stack(trunc), cmd_np, rows, b.nobs, lin_tol, ang_tol)
-    names = ("PUSHED", "PUSH_AT", "FELL", "STEPS_TO_FALL", "LAST_OFF", "PEAK_LIN_ERR", "PEAK_ANG_ERR", "PRE_LIN_ERR_SUM", "PRE_SAMPLES")
-    for k in (0, 1, 2, 3, 4, 8, 5, 6):
-        np.testing.assert_array_equal(got[:, k].astype(np.float64), want[:, k], err_msg=names[k])
-    bound = want[:, 8] * 2.0 ** -23 * big
-    err = np.abs(got[:, 7].astype(np.float64) - want[:, 7])
+    for name in ("PUSHED", "PUSH_AT", "FELL", "STEPS_TO_FALL", "LAST_OFF", "PRE_SAMPLES", "PEAK_LIN_ERR", "PEAK_ANG_ERR"):
+        k = getattr(G, "PUSH_" + name)
+        np.testing.assert_array_equal(got[:, k].astype(np.float64), want[:, k], err_msg=name)
+    bound = want[:, G.PUSH_PRE_SAMPLES] * 2.0 ** -23 * big
+    err = np.abs(got[:, G.PUSH_PRE_LIN_ERR_SUM].astype(np.float64) - want[:, G.PUSH_PRE_LIN_ERR_SUM])
     print(f"pre-push sum: worst error {err.max():.3e}, worst error / bound {np.max(err / np.maximum(bound, 1e-300)):.3f}")
     assert np.all(err <= bound), (err.max(), bound[np.argmax(err - bound)])
     # the run covers what it claims to
-    pushed, fell = want[:, 0] != 0, want[:, 2] != 0
+    pushed, fell = want[:, G.PUSH_PUSHED] != 0, want[:, G.PUSH_FELL] != 0
     ta = tacc.cpu().numpy()
     assert ta[:, engine.TRACK_ENDED].all()
     never = ~pushed & (kicks.any(1))                  # kicked only after the first episode was over
     assert never.sum() > 0 and (~kicks.any(1) & ~pushed).sum() == n // 8
-    assert fell.sum() > 0 and (pushed & ~fell).sum() > 0 and (want[:, 4] > 0).sum() > 0
-    assert np.all(want[pushed, 1] == at[pushed])
+    assert fell.sum() > 0 and (pushed & ~fell).sum() > 0 and (want[:, G.PUSH_LAST_OFF] > 0).sum() > 0
+    assert np.all(want[pushed, G.PUSH_PUSH_AT] == at[pushed])
     # a fall counted here is one of the tracking accumulator's falls
     assert np.all(ta[fell, engine.TRACK_FALLS] == 1)
     b.close()
@@ -419,22 +421,22 @@ def test_refusals_launch_nothing():
         env.set_pushes(push if bind_p else None)
         with pytest.raises(engine.OdkError, match=f"no {what} bound"):
             b.push_accumulate(acc, tacc, 0.05, 0.2)
-        assert raw_accumulate() == ODK_ERR_INVALID
+        assert raw_accumulate() == engine.ERR_INVALID
         msg = L.odk_last_error().decode()
         assert "odk_push_accumulate" in msg and f"no {what} bound" in msg, msg
     env.set_commands(cmd); env.set_pushes(None)
     # bad stride, bad shapes, bad device
-    assert L.odk_batch_bind_pushes(b._b, C.c_void_p(push.data_ptr()), 1) == ODK_ERR_INVALID
+    assert L.odk_batch_bind_pushes(b._b, C.c_void_p(push.data_ptr()), 1) == engine.ERR_INVALID
     assert "row_stride 1 < 2" in L.odk_last_error().decode()
     host = np.ones((n, 2), np.float32)
-    assert L.odk_batch_bind_pushes(b._b, host.ctypes.data_as(C.c_void_p), 2) == ODK_ERR_INVALID
+    assert L.odk_batch_bind_pushes(b._b, host.ctypes.data_as(C.c_void_p), 2) == engine.ERR_INVALID
     assert "device memory" in L.odk_last_error().decode()
     bad = [torch.ones(n, 1, device="cuda"), torch.ones(n + 1, 2, device="cuda"), torch.ones(n, 2, device="cuda", dtype=torch.float64),
            torch.ones(2, n, device="cuda").t(), torch.ones(n, 2), host]
     if torch.cuda.device_count() > 1:
         other = torch.ones(n, 2, device="cuda:1")
         bad.append(other)
-        assert L.odk_batch_bind_pushes(b._b, C.c_void_p(other.data_ptr()), 2) == ODK_ERR_INVALID
+        assert L.odk_batch_bind_pushes(b._b, C.c_void_p(other.data_ptr()), 2) == engine.ERR_INVALID
         assert "device 0" in L.odk_last_error().decode()
     for t in bad:
         with pytest.raises(engine.OdkError):
@@ -443,7 +445,7 @@ def test_refusals_launch_nothing():
     # every refusal left the binding as it was (none): the accumulator still refuses, and a step applies no kick
     with pytest.raises(engine.OdkError, match="no pushes bound"):
         b.push_accumulate(acc, tacc, 0.05, 0.2)
-    for t in (torch.zeros(n, 9, device="cuda"), torch.zeros(n, engine.PUSH_NACC), acc.double()):
+    for t in (torch.zeros(n, engine.PUSH_NACC - 1, device="cuda"), torch.zeros(n, engine.PUSH_NACC), acc.double()):
         with pytest.raises(engine.OdkError):
             b.push_accumulate(t, tacc, 0.05, 0.2)
     torch.cuda.synchronize()
@@ -460,19 +462,9 @@ def test_refusals_launch_nothing():
     b.close()
 
 
-def _checkpoint(tmp_path):
-    import torch
-    from open_duck_playground_amd.ppo.networks import PPONetworks
-    from open_duck_playground_amd.ppo.train import save_checkpoint
-    torch.manual_seed(0)
-    ckpt = str(tmp_path / "fresh.pt")
-    save_checkpoint(ckpt, PPONetworks(101, 212, 14))
-    return ckpt
-
-
 def test_track_without_push_flags_is_the_report_of_before(tmp_path, monkeypatch):
     from open_duck_playground_amd import engine, track
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     calls = []
     for name in ("bind_pushes", "push_accumulate"):
         real = getattr(engine.Batch, name)
@@ -500,7 +492,7 @@ def test_track_without_push_flags_is_the_report_of_before(tmp_path, monkeypatch)
 
 def test_track_push_sweep_end_to_end(tmp_path):
     from open_duck_playground_amd import track
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     out = tmp_path / "report.json"
     E, T = 32, 120
     args = track.build_parser().parse_args(["--checkpoint", ckpt, "--command", "0", "0", "0", "--command", "0.1", "0", "0", "--envs_per_command", str(E),

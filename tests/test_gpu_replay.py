@@ -159,7 +159,7 @@ def own_log():
 
 def test_a_plant_replayed_on_its_own_log_scores_zero(own_log):
     """one env per cell of the 60-cell grid: the true cell's score is exactly 0.0, every other cell's is > 0, no cell falls"""
-    from open_duck_playground_amd import replay
+    from open_duck_playground_amd import engine, replay
     rows, grid, true = own_log
     r = replay.Replayer(rows, "flat_terrain", "joystick", len(grid))
     scores, lasted, steps, acc, _ = r.evaluate(replay.plant_columns(grid, r.n))
@@ -169,7 +169,7 @@ def test_a_plant_replayed_on_its_own_log_scores_zero(own_log):
     assert scores[true] == 0.0
     others = np.delete(scores, true)
     assert (others > 0).all(), others.min()
-    assert (acc[true, :14, 3] == 0).all()      # the peak residual of every joint
+    assert (acc[true, :14, engine.REPLAY_POS_ERR_PEAK] == 0).all()      # the peak residual of every joint
 
 
 def test_the_oracle_log_is_fitted_to_its_true_cell():

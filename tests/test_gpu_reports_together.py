@@ -4,7 +4,7 @@ random-weight policy, 6 envs -- the second wave of the 16-lane kernels is half e
 import numpy as np
 import pytest
 
-from test_gpu_falls import _checkpoint
+import report_cases as RC
 
 pytestmark = pytest.mark.gpu
 
@@ -48,7 +48,7 @@ def test_pushes_gait_posture_imitation_and_falls_together_are_each_alone(tmp_pat
     report by itself, and each other report next to it alone."""
     import torch
     from open_duck_playground_amd import engine
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     pushes = dict(kicks=torch.from_numpy(KICKS), push_at=PUSH_AT)
     each = dict(gait=dict(gait=True), posture=dict(posture=True, posture_tolerance=0.05), imitation=dict(imitation=True),
                 fall=dict(falls=dict(ring=8, tilt_tol=0.3)))
@@ -70,7 +70,7 @@ def test_schedule_response_and_falls_together_are_each_alone(tmp_path):
     """Schedules exclude pushes.  The schedule is part of the episode, so every Tracker carries it (and with it the response report): the
     response report is compared alone; falls next to it IS the together run, so here falls is held only captured against eager."""
     from open_duck_playground_amd import track
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     schedules = track.then_schedules([track.command_row([0, 0, 0]), track.command_row([0.1, 0, 0])], [track.command_row([0, 0, 1.0])], 8)
     schedule = dict(table=track.schedule_table(schedules), map=track.schedule_blocks(len(schedules), N // 2), tolerance=(0.05, 0.2), tail_after=4)
     falls = dict(ring=8, tilt_tol=0.3)

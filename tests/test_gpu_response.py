@@ -12,13 +12,11 @@ import functools
 import numpy as np
 import pytest
 
+import report_cases as RC
+
 pytestmark = pytest.mark.gpu
 
-ODK_ERR_INVALID = -1         # include/odk.h
-# include/odk.h ODK_RESP_* / ODK_SCHED_* / ODK_TRACK_*
-ENTERED, SAMPLES, FELL, STEPS_TO_FALL, FIRST_IN, LAST_OFF, PEAK_LIN, PEAK_ANG, SUM, SQERR, OVERSHOOT, TAIL_SAMPLES, TAIL_SUM = 0, 1, 2, 3, 4, 5, 6, 7, 8, 11, 14, 17, 18
-STRIDE, NACC, NEVER = 24, 192, np.float32(1.0e9)
-T_ENDED, T_STEPS, T_NACC = 0, 1, 12
+G = RC.HEADER         # include/odk.h's constants: G.RESP_*, G.SCHED_*, G.TRACK_*
 f32 = np.float32
 
 
@@ -32,10 +30,10 @@ def segment_of(S, t):
 
 
 def table(*schedules):
-    """[nsched, nseg, 8] float32 from lists of (start, 7 floats), padded with NEVER"""
+    """[nsched, nseg, 8] float32 from lists of (start, 7 floats), padded with ODK_SCHED_NEVER"""
     nseg = max(len(s) for s in schedules)
-    tab = np.zeros((len(schedules), nseg, 8), f32)
-    tab[:, :, 0] = NEVER
+    tab = np.zeros((len(schedules), nseg, G.SCHED_SEG_FLOATS), f32)
+    tab[:, :, 0] = f32(G.SCHED_NEVER)
     for i, s in enumerate(schedules):
         for k, (at, cmd) in enumerate(s):
             tab[i, k, 0] = at
@@ -44,8 +42,7 @@ def table(*schedules):
 
 
 def _duck(n):
-    from open_duck_playground_amd import joystick
-    return joystick.Joystick(task="flat_terrain", num_envs=n)
+    return RC.robot_env("duck", n)
 
 
 def test_schedule_apply_on_synthetic_clocks():
@@ -64,15 +61,15 @@ def test_schedule_apply_on_synthetic_clocks():
     assert 3 * len(cand) * 2 <= 290
     smap = np.array([e % 3 for e in range(n)], np.int32)
     smap[290:] = [-1, 7, 3, -5, 100, -1, 7, 3, -5, 100]                      # outside 0 .. 2: clamped, never read past the table
-    tacc = np.zeros((n, T_NACC), f32)
-    tacc[:, T_STEPS] = [cand[(e // 3) % len(cand)] for e in range(n)]
-    tacc[:, T_ENDED] = [1.0 if (e // (3 * len(cand))) % 2 == 1 and tacc[e, T_STEPS] >= 1 else 0.0 for e in range(n)]
-    tacc[:, 2:] = rng.normal(size=(n, T_NACC - 2)).astype(f32)                # the other slots are not the launch's business
-    assert tacc[:, T_ENDED].sum() > 40 and (tacc[:, T_ENDED] == 0).sum() > 100
+    tacc = np.zeros((n, G.TRACK_NACC), f32)
+    tacc[:, G.TRACK_STEPS] = [cand[(e // 3) % len(cand)] for e in range(n)]
+    tacc[:, G.TRACK_ENDED] = [1.0 if (e // (3 * len(cand))) % 2 == 1 and tacc[e, G.TRACK_STEPS] >= 1 else 0.0 for e in range(n)]
+    tacc[:, G.TRACK_SAMPLES:] = rng.normal(size=(n, G.TRACK_NACC - G.TRACK_SAMPLES)).astype(f32)      # the other slots are not the launch's business
+    assert tacc[:, G.TRACK_ENDED].sum() > 40 and (tacc[:, G.TRACK_ENDED] == 0).sum() > 100
     want = np.zeros((n, 7), f32)
     for e in range(n):
         S = tab[min(max(int(smap[e]), 0), 2)]
-        t = tacc[e, T_STEPS] - 1 if tacc[e, T_ENDED] != 0 else tacc[e, T_STEPS]
+        t = tacc[e, G.TRACK_STEPS] - 1 if tacc[e, G.TRACK_ENDED] != 0 else tacc[e, G.TRACK_STEPS]
         want[e] = S[segment_of(S, t), 1:]
     # every segment of every schedule is somebody's, and an ENDED row at a boundary differs from a live one
     assert {tuple(w) for w in want} == {tuple(c) for c in cmds}
@@ -88,7 +85,7 @@ def test_schedule_apply_on_synthetic_clocks():
     np.testing.assert_array_equal(cmd.cpu().numpy().view(np.int32), want.view(np.int32))
     np.testing.assert_array_equal(guard[n:].cpu().numpy(), 9.0)
     np.testing.assert_array_equal(tacc_d.cpu().numpy().view(np.int32), tacc.view(np.int32))      # the clock is read, not written
-    b.command_schedule_apply(tab_d, smap_d, torch.zeros(n, T_NACC, device="cuda"))
+    b.command_schedule_apply(tab_d, smap_d, torch.zeros(n, G.TRACK_NACC, device="cuda"))
     torch.cuda.synchronize()
     seg0 = np.stack([tab[min(max(int(s), 0), 2), 0, 1:] for s in smap])
     np.testing.assert_array_equal(cmd.cpu().numpy().view(np.int32), seg0.view(np.int32))
@@ -112,7 +109,7 @@ def restate(priv, done, trunc, tab, smap, nobs, lin_tol, ang_tol, tail_after, en
     (STEPS, ENDED: odk_tracking_accumulate's rule) carried along.  Every operation is one float32 operation, in the kernel's order; the
     planar error goes through float64.  Returns the [n, 192] accumulator and the final (steps, ended)."""
     T, n = done.shape
-    A = np.zeros((n, NACC), f32)
+    A = np.zeros((n, G.RESP_NACC), f32)
     ended = np.zeros(n, bool) if ended0 is None else np.array(ended0, bool)
     steps = np.zeros(n, f32) if steps0 is None else np.array(steps0, f32)
     lin_tol, ang_tol, tail_after = f32(lin_tol), f32(ang_tol), f32(tail_after)
@@ -123,38 +120,38 @@ def restate(priv, done, trunc, tab, smap, nobs, lin_tol, ang_tol, tail_after, en
                 continue
             S = tab[min(max(int(smap[e]), 0), len(tab) - 1)]
             seg = segment_of(S, steps[e])
-            B = A[e, seg * STRIDE:(seg + 1) * STRIDE]
+            B = A[e, seg * G.RESP_STRIDE:(seg + 1) * G.RESP_STRIDE]
             k = f32(f32(steps[e] - S[seg, 0]) + one)
             steps[e] += one
-            B[ENTERED] = one
+            B[G.RESP_ENTERED] = one
             if done[t, e] != 0:
                 ended[e] = True
                 if trunc[t, e] == 0:
-                    B[FELL], B[STEPS_TO_FALL] = one, k
+                    B[G.RESP_FELL], B[G.RESP_STEPS_TO_FALL] = one, k
                 continue
             Cm = S[seg, 1:]
             v = priv[t, e, [nobs + 9, nobs + 10, nobs + 2]]
             ex, ey = np.float64(f32(v[0] - Cm[0])), np.float64(f32(v[1] - Cm[1]))
             lin, ang = f32(np.sqrt(ex * ex + ey * ey)), f32(abs(f32(v[2] - Cm[2])))
-            B[SAMPLES] += one
+            B[G.RESP_SAMPLES] += one
             if lin > lin_tol or ang > ang_tol:
-                B[LAST_OFF] = k
-            elif B[FIRST_IN] == 0:
-                B[FIRST_IN] = k
-            if B[FIRST_IN] != 0:
-                B[PEAK_LIN], B[PEAK_ANG] = max(B[PEAK_LIN], lin), max(B[PEAK_ANG], ang)
+                B[G.RESP_LAST_OFF] = k
+            elif B[G.RESP_FIRST_IN] == 0:
+                B[G.RESP_FIRST_IN] = k
+            if B[G.RESP_FIRST_IN] != 0:
+                B[G.RESP_PEAK_LIN_ERR], B[G.RESP_PEAK_ANG_ERR] = max(B[G.RESP_PEAK_LIN_ERR], lin), max(B[G.RESP_PEAK_ANG_ERR], ang)
             tail = k > tail_after
             if tail:
-                B[TAIL_SAMPLES] += one
+                B[G.RESP_TAIL_SAMPLES] += one
             for a in range(3):
                 err = f32(v[a] - Cm[a])
-                B[SUM + a] = f32(B[SUM + a] + v[a])
-                B[SQERR + a] = f32(B[SQERR + a] + f32(err * err))
+                B[G.RESP_SUM + a] = f32(B[G.RESP_SUM + a] + v[a])
+                B[G.RESP_SQERR + a] = f32(B[G.RESP_SQERR + a] + f32(err * err))
                 prev = S[seg - 1, 1 + a] if seg > 0 else f32(0)
                 d = f32(1) if Cm[a] > prev else (f32(-1) if Cm[a] < prev else f32(0))
-                B[OVERSHOOT + a] = max(B[OVERSHOOT + a], f32(err * d))
+                B[G.RESP_OVERSHOOT + a] = max(B[G.RESP_OVERSHOOT + a], f32(err * d))
                 if tail:
-                    B[TAIL_SUM + a] = f32(B[TAIL_SUM + a] + v[a])
+                    B[G.RESP_TAIL_SUM + a] = f32(B[G.RESP_TAIL_SUM + a] + v[a])
     return A, steps, ended
 
 
@@ -231,7 +228,7 @@ def synthetic():
     r = synthetic_inputs(b.nobs, b.npriv)
     priv, done, trunc, tab, smap = r["priv"], r["done"], r["trunc"], r["tab"], r["smap"]
 
-    guard = torch.full((n + 3, NACC), 7.0, device="cuda")          # rows past the batch stay as they are
+    guard = torch.full((n + 3, G.RESP_NACC), 7.0, device="cuda")          # rows past the batch stay as they are
     acc = guard[:n]
     acc[:PRE_ENDED].zero_()
     tacc = torch.zeros(n, engine.TRACK_NACC, device="cuda")
@@ -259,16 +256,16 @@ def synthetic():
 def test_every_slot_equals_a_float32_restatement_bit_for_bit():
     r = synthetic()
     got, want, tab, smap, pattern = r["got"], r["want"], r["tab"], r["smap"], r["pattern"]
-    np.testing.assert_array_equal(r["tacc"][:, T_STEPS], r["steps"])
-    np.testing.assert_array_equal(r["tacc"][:, T_ENDED] != 0, r["ended"])
-    for s, name in ((ENTERED, "ENTERED"), (SAMPLES, "SAMPLES"), (FELL, "FELL"), (STEPS_TO_FALL, "STEPS_TO_FALL"), (FIRST_IN, "FIRST_IN"), (LAST_OFF, "LAST_OFF"),
-                    (PEAK_LIN, "PEAK_LIN_ERR"), (PEAK_ANG, "PEAK_ANG_ERR"), (TAIL_SAMPLES, "TAIL_SAMPLES")):
-        np.testing.assert_array_equal(got[:, s::STRIDE].view(np.int32), want[:, s::STRIDE].view(np.int32), err_msg=name)
+    np.testing.assert_array_equal(r["tacc"][:, G.TRACK_STEPS], r["steps"])
+    np.testing.assert_array_equal(r["tacc"][:, G.TRACK_ENDED] != 0, r["ended"])
+    for s, name in ((G.RESP_ENTERED, "ENTERED"), (G.RESP_SAMPLES, "SAMPLES"), (G.RESP_FELL, "FELL"), (G.RESP_STEPS_TO_FALL, "STEPS_TO_FALL"), (G.RESP_FIRST_IN, "FIRST_IN"), (G.RESP_LAST_OFF, "LAST_OFF"),
+                    (G.RESP_PEAK_LIN_ERR, "PEAK_LIN_ERR"), (G.RESP_PEAK_ANG_ERR, "PEAK_ANG_ERR"), (G.RESP_TAIL_SAMPLES, "TAIL_SAMPLES")):
+        np.testing.assert_array_equal(got[:, s::G.RESP_STRIDE].view(np.int32), want[:, s::G.RESP_STRIDE].view(np.int32), err_msg=name)
     np.testing.assert_array_equal(got.view(np.int32), want.view(np.int32))          # the sums too: fixed order, float32, no fused multiply-add
     np.testing.assert_array_equal(r["guard"], 7.0)
 
     # the run covers what it claims to
-    blk = lambda e, seg: got[e, seg * STRIDE:(seg + 1) * STRIDE]
+    blk = lambda e, seg: got[e, seg * G.RESP_STRIDE:(seg + 1) * G.RESP_STRIDE]
     live = np.arange(N_SYN) != PRE_ENDED
     seg_len = {0: [7, 12, 21], 1: [19, 21], 2: [40]}
     for e in range(N_SYN):
@@ -276,38 +273,39 @@ def test_every_slot_equals_a_float32_restatement_bit_for_bit():
             continue
         s, p = int(smap[e]), int(pattern[e])
         nseg = len(seg_len[s])
-        assert np.all(got[e, nseg * STRIDE:] == 0.0)                                 # no block beyond the schedule's segments is touched
-        assert np.all(got[e].reshape(8, STRIDE)[:, 21:] == 0.0)                      # no slot lives there
+        assert np.all(got[e, nseg * G.RESP_STRIDE:] == 0.0)                                 # no block beyond the schedule's segments is touched
+        assert np.all(got[e].reshape(G.SCHED_MAX_SEGMENTS, G.RESP_STRIDE)[:, G.RESP_TAIL_SUM + 3:] == 0.0)      # no slot lives there
         for seg in range(nseg):
             B, L = blk(e, seg), seg_len[s][seg]
             if p == 0:
-                assert B[FIRST_IN] == 0 and B[LAST_OFF] == B[SAMPLES] == L and B[PEAK_LIN] == 0 and B[PEAK_ANG] == 0
+                assert B[G.RESP_FIRST_IN] == 0 and B[G.RESP_LAST_OFF] == B[G.RESP_SAMPLES] == L and B[G.RESP_PEAK_LIN_ERR] == 0 and B[G.RESP_PEAK_ANG_ERR] == 0
             if p == 1:
-                assert B[FIRST_IN] == 1 and B[LAST_OFF] == 0 and B[SAMPLES] == L and 0 < B[PEAK_LIN] < LIN_TOL
-                assert B[TAIL_SAMPLES] == L - TAIL_AFTER > 0
+                assert B[G.RESP_FIRST_IN] == 1 and B[G.RESP_LAST_OFF] == 0 and B[G.RESP_SAMPLES] == L and 0 < B[G.RESP_PEAK_LIN_ERR] < LIN_TOL
+                assert B[G.RESP_TAIL_SAMPLES] == L - TAIL_AFTER > 0
             if p == 2:
-                assert B[FIRST_IN] == 1 and B[LAST_OFF] == 4 and B[PEAK_LIN] > LIN_TOL and B[PEAK_ANG] > ANG_TOL
+                assert B[G.RESP_FIRST_IN] == 1 and B[G.RESP_LAST_OFF] == 4 and B[G.RESP_PEAK_LIN_ERR] > LIN_TOL and B[G.RESP_PEAK_ANG_ERR] > ANG_TOL
             if p == 3:      # exactly the tolerance is inside; one ulp above is outside
-                assert B[FIRST_IN] == 1 and B[LAST_OFF] == L - L % 2 and B[PEAK_LIN] > LIN_TOL and B[PEAK_ANG] > ANG_TOL
+                assert B[G.RESP_FIRST_IN] == 1 and B[G.RESP_LAST_OFF] == L - L % 2 and B[G.RESP_PEAK_LIN_ERR] > LIN_TOL and B[G.RESP_PEAK_ANG_ERR] > ANG_TOL
     first = lambda p, s: next(e for e in range(N_SYN) if pattern[e] == p and smap[e] == s and live[e])
     e = first(3, 2)                                                                   # a one-sample look at the tie itself
-    one = r["snaps"][0, e, :STRIDE]
-    assert one[FIRST_IN] == 1 and one[LAST_OFF] == 0 and one[PEAK_LIN] == f32(LIN_TOL) and one[PEAK_ANG] == f32(ANG_TOL)
+    one = r["snaps"][0, e, :G.RESP_STRIDE]
+    assert one[G.RESP_FIRST_IN] == 1 and one[G.RESP_LAST_OFF] == 0 and one[G.RESP_PEAK_LIN_ERR] == f32(LIN_TOL) and one[G.RESP_PEAK_ANG_ERR] == f32(ANG_TOL)
     e = first(4, 0)                                                                   # the fall at step 10: segment 1 (steps 7 ..), its 4th step
-    assert blk(e, 1)[FELL] == 1 and blk(e, 1)[STEPS_TO_FALL] == 4 and blk(e, 1)[SAMPLES] == 3 and blk(e, 0)[FELL] == 0 and blk(e, 2)[ENTERED] == 0
+    assert blk(e, 1)[G.RESP_FELL] == 1 and blk(e, 1)[G.RESP_STEPS_TO_FALL] == 4 and blk(e, 1)[G.RESP_SAMPLES] == 3 and blk(e, 0)[G.RESP_FELL] == 0 and blk(e, 2)[G.RESP_ENTERED] == 0
     e = first(4, 1)
-    assert blk(e, 0)[FELL] == 1 and blk(e, 0)[STEPS_TO_FALL] == 11 and blk(e, 0)[SAMPLES] == 10
+    assert blk(e, 0)[G.RESP_FELL] == 1 and blk(e, 0)[G.RESP_STEPS_TO_FALL] == 11 and blk(e, 0)[G.RESP_SAMPLES] == 10
     e = first(5, 0)                                                                   # the truncation at step 25: no fall
-    assert blk(e, 2)[ENTERED] == 1 and blk(e, 2)[FELL] == 0 and blk(e, 2)[STEPS_TO_FALL] == 0 and blk(e, 2)[SAMPLES] == 6
+    assert blk(e, 2)[G.RESP_ENTERED] == 1 and blk(e, 2)[G.RESP_FELL] == 0 and blk(e, 2)[G.RESP_STEPS_TO_FALL] == 0 and blk(e, 2)[G.RESP_SAMPLES] == 6
     e = first(6, 0)                                                                   # done at step 0: entered, fell, no sample
-    assert blk(e, 0)[ENTERED] == 1 and blk(e, 0)[FELL] == 1 and blk(e, 0)[STEPS_TO_FALL] == 1 and np.all(blk(e, 0)[[SAMPLES, FIRST_IN, LAST_OFF] + list(range(6, 21))] == 0)
+    assert blk(e, 0)[G.RESP_ENTERED] == 1 and blk(e, 0)[G.RESP_FELL] == 1 and blk(e, 0)[G.RESP_STEPS_TO_FALL] == 1 
+    assert np.all(blk(e, 0)[[G.RESP_SAMPLES, G.RESP_FIRST_IN, G.RESP_LAST_OFF] + list(range(G.RESP_PEAK_LIN_ERR, G.RESP_TAIL_SUM + 3))] == 0)
     # overshoot: segment 0's unchanged axes keep 0; an axis that changed downwards overshoots below the command
     e = first(7, 0)
-    assert np.all(blk(e, 0)[OVERSHOOT:OVERSHOOT + 3] == 0.0)                          # 0 0 0 from rest: nothing changed
-    assert blk(e, 1)[OVERSHOOT] > 0 and blk(e, 1)[OVERSHOOT + 1] > 0 and blk(e, 1)[OVERSHOOT + 2] == 0      # vx up, vy down, wz unchanged
-    assert blk(e, 2)[OVERSHOOT] == 0 and blk(e, 2)[OVERSHOOT + 1] > 0 and blk(e, 2)[OVERSHOOT + 2] > 0      # vx unchanged, vy up, wz up
+    assert np.all(blk(e, 0)[G.RESP_OVERSHOOT:G.RESP_OVERSHOOT + 3] == 0.0)                          # 0 0 0 from rest: nothing changed
+    assert blk(e, 1)[G.RESP_OVERSHOOT] > 0 and blk(e, 1)[G.RESP_OVERSHOOT + 1] > 0 and blk(e, 1)[G.RESP_OVERSHOOT + 2] == 0      # vx up, vy down, wz unchanged
+    assert blk(e, 2)[G.RESP_OVERSHOOT] == 0 and blk(e, 2)[G.RESP_OVERSHOOT + 1] > 0 and blk(e, 2)[G.RESP_OVERSHOOT + 2] > 0      # vx unchanged, vy up, wz up
     e = first(7, 1)
-    assert blk(e, 1)[OVERSHOOT] > 0 and blk(e, 1)[OVERSHOOT + 1] == 0 and blk(e, 1)[OVERSHOOT + 2] == 0     # vx 0.125 -> -0.125
+    assert blk(e, 1)[G.RESP_OVERSHOOT] > 0 and blk(e, 1)[G.RESP_OVERSHOOT + 1] == 0 and blk(e, 1)[G.RESP_OVERSHOOT + 2] == 0     # vx 0.125 -> -0.125
     # the command buffer followed the schedules while the first episode ran, and froze where it ended
     for t in (0, 6, 7, 18, 19, 39):
         for e in (first(1, 0), first(1, 1), first(1, 2)):
@@ -333,7 +331,7 @@ def test_a_row_past_its_first_episode_keeps_its_bits():
     e = next(e for e in range(N_SYN) if r["pattern"][e] == 1 and r["smap"][e] == 0)
     for t in range(1, T_SYN):
         seg = segment_of(r["tab"][0], t)
-        changed = np.nonzero((snaps[t, e] != snaps[t - 1, e]).reshape(8, STRIDE).any(1))[0]
+        changed = np.nonzero((snaps[t, e] != snaps[t - 1, e]).reshape(G.SCHED_MAX_SEGMENTS, G.RESP_STRIDE).any(1))[0]
         assert list(changed) == [seg], (t, changed)
 
 
@@ -367,11 +365,11 @@ def test_the_step_follows_the_schedule():
         torch.cuda.synchronize()
         want = np.zeros((n, 7), f32)
         for e in range(n):
-            tt = clock[e, T_STEPS] - 1 if clock[e, T_ENDED] != 0 else clock[e, T_STEPS]
+            tt = clock[e, G.TRACK_STEPS] - 1 if clock[e, G.TRACK_ENDED] != 0 else clock[e, G.TRACK_STEPS]
             seg = segment_of(tab[smap[e]], tt)
             want[e] = tab[smap[e], seg, 1:]
-            if clock[e, T_ENDED] == 0:
-                assert clock[e, T_STEPS] == t and seg == (t >= 5)
+            if clock[e, G.TRACK_ENDED] == 0:
+                assert clock[e, G.TRACK_STEPS] == t and seg == (t >= 5)
                 seen.add((t, seg))
         np.testing.assert_array_equal(b.records()[:, off:off + 7].view(np.int32), want.view(np.int32), err_msg=f"record, step {t}")
         np.testing.assert_array_equal(b.obs[:, 6:13].cpu().numpy().view(np.int32), want.view(np.int32), err_msg=f"obs, step {t}")
@@ -380,60 +378,19 @@ def test_the_step_follows_the_schedule():
     b.close()
 
 
-ENV_SIZES = (101, 212, 14)      # the duck's observation / privileged / action sizes (Joystick)
-
-
-def _checkpoint(tmp_path, name="fresh.pt"):
-    import torch
-    from open_duck_playground_amd.ppo.networks import PPONetworks
-    from open_duck_playground_amd.ppo.train import save_checkpoint
-    torch.manual_seed(0)
-    ckpt = str(tmp_path / name)
-    save_checkpoint(ckpt, PPONetworks(*ENV_SIZES))
-    return ckpt
-
-
-def _run(track, monkeypatch, argv, eager=False):
-    """track.run with its Tracker caught; eager: no graph, and per step the step's privileged rows, done and truncation flags.
-    Returns (report, tracker, recording)."""
-    real = track.Tracker
-    caught, hist = [], []
-
-    class Caught(real):
-        def __init__(self, *a, **k):
-            if eager:
-                k["use_graph"] = False
-            super().__init__(*a, **k)
-            caught.append(self)
-
-        def step(self):
-            super().step()
-            if eager:
-                bb = self.env.batch
-                hist.append((bb.priv.cpu().numpy(), bb.done.cpu().numpy(), bb.truncation.cpu().numpy()))
-
-    monkeypatch.setattr(track, "Tracker", Caught)
-    try:
-        rep = track.run(track.build_parser().parse_args(argv))
-    finally:
-        monkeypatch.setattr(track, "Tracker", real)
-    assert len(caught) == 1
-    return rep, caught[0], hist
-
-
 def test_track_sequences_end_to_end(tmp_path, monkeypatch):
     """A randomly initialised policy on the duck, two sequences, 8 envs each, 60 steps.  The eager run's recording, pushed through the
     float32 restatement, has the accumulator's bits, so every figure of `segments` is `reduce_response` of the restatement; the graph
     run has the eager run's bits and report."""
     import json
     from open_duck_playground_amd import engine, track
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     E, T = 8, 60
     out = tmp_path / "report.json"
     seqs = ["0: 0 0 0 | 20: 0.1 0 0 | 40: 0 0 0.5", "0: 0.1 0 0.3 | 30: -0.1 0.05 0.3 0.2"]
     argv = ["--checkpoint", ckpt, "--sequence", seqs[0], "--sequence", seqs[1], "--envs_per_command", str(E), "--episode_length", str(T),
             "--response_tail_after", "10", "--seed", "1", "--output", str(out)]
-    rep_e, tr_e, hist = _run(track, monkeypatch, argv, eager=True)
+    rep_e, tr_e, hist = RC.run_track(track, monkeypatch, argv, eager=True)
     st = rep_e["settings"]
     assert not st["graph"] and st["sequence"] == seqs and st["then"] is None and st["response_tail_after"] == 10 and st["schedules"] == 2
     assert st["response_tolerance"] == list(track.DEFAULT_PUSH_TOLERANCE) and len(hist) == T
@@ -444,8 +401,8 @@ def test_track_sequences_end_to_end(tmp_path, monkeypatch):
     got_e, track_e = tr_e.response_acc.cpu().numpy(), tr_e.acc.cpu().numpy()
     np.testing.assert_array_equal(track_e[:, engine.TRACK_STEPS], steps)
     np.testing.assert_array_equal(got_e.view(np.int32), want.view(np.int32))
-    np.testing.assert_array_equal(got_e[:, SAMPLES::STRIDE].sum(1), track_e[:, engine.TRACK_SAMPLES])      # the segments share out the velocity samples
-    assert got_e[:, SAMPLES].sum() > 0 and got_e[:, 2 * STRIDE + SAMPLES].sum() > 0
+    np.testing.assert_array_equal(got_e[:, G.RESP_SAMPLES::G.RESP_STRIDE].sum(1), track_e[:, engine.TRACK_SAMPLES])      # the segments share out the velocity samples
+    assert got_e[:, G.RESP_SAMPLES].sum() > 0 and got_e[:, 2 * G.RESP_STRIDE + G.RESP_SAMPLES].sum() > 0
 
     ref = track.reduce_response(want, schedules, E, st["dt"])
     assert len(rep_e["commands"]) == 2
@@ -460,7 +417,7 @@ def test_track_sequences_end_to_end(tmp_path, monkeypatch):
     assert json.load(open(out)) == json.loads(json.dumps(rep_e))
 
     # the graph: two more launches in the captured step, the same bits
-    rep_g, tr_g, _ = _run(track, monkeypatch, argv)
+    rep_g, tr_g, _ = RC.run_track(track, monkeypatch, argv)
     assert rep_g["settings"]["graph"]
     np.testing.assert_array_equal(tr_g.response_acc.cpu().numpy().view(np.int32), got_e.view(np.int32))
     np.testing.assert_array_equal(tr_g.acc.cpu().numpy().view(np.int32), track_e.view(np.int32))
@@ -471,11 +428,11 @@ def test_track_sequences_end_to_end(tmp_path, monkeypatch):
 def test_track_then_gives_the_transition_matrix_and_combines_with_gait(tmp_path, monkeypatch):
     """`--command` x2, `--then` x2, `--switch_at 30`: four rows, from-commands outermost; with `--gait` every schedule row has a gait object."""
     from open_duck_playground_amd import track
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     argv = ["--checkpoint", ckpt, "--command", "0.1", "0", "0", "--command", "0", "0", "0.5", "--then", "0", "0", "0", "--then", "0.05", "0.05", "0",
             "--switch_at", "30", "--envs_per_command", "8", "--episode_length", "60", "--response_tail_after", "10", "--seed", "2", "--gait",
             "--output", str(tmp_path / "r.json")]
-    rep, tr, _ = _run(track, monkeypatch, argv)
+    rep, tr, _ = RC.run_track(track, monkeypatch, argv)
     st = rep["settings"]
     assert st["switch_at"] == 30 and st["schedules"] == 4 and st["num_envs"] == 32 and st["gait"] is True and st["graph"]
     froms, thens = [[0.1, 0, 0] + [0.0] * 4, [0, 0, 0.5] + [0.0] * 4], [[0.0] * 7, [0.05, 0.05, 0] + [0.0] * 4]
@@ -486,7 +443,7 @@ def test_track_then_gives_the_transition_matrix_and_combines_with_gait(tmp_path,
         assert row["schedule"] == [dict(start_step=0, command=froms[i // 2]), dict(start_step=30, command=thens[i % 2])]
         assert [g["command"] for g in row["segments"]] == [froms[i // 2], thens[i % 2]]
         assert tuple(row["gait"]) == track.GAIT_KEYS and row["gait"]["samples"] == row["velocity_samples"] > 0
-    assert tuple(tr.response_acc.shape) == (32, NACC) and tuple(tr.sched.shape) == (4, 2, 8)
+    assert tuple(tr.response_acc.shape) == (32, G.RESP_NACC) and tuple(tr.sched.shape) == (4, 2, 8)
     np.testing.assert_array_equal(tr.sched_map.cpu().numpy(), np.repeat(np.arange(4), 8))
 
 
@@ -494,18 +451,18 @@ def test_a_one_segment_sequence_is_the_plain_command_and_no_flag_means_no_launch
     """`--sequence "0: 0.1 0 0"` gives, key by key and bit for bit, the ROW_KEYS values of `--command 0.1 0 0` with the same seed.  The
     run without a schedule flag calls neither new Batch method, allocates no schedule tensor and has exactly the old keys."""
     from open_duck_playground_amd import engine, track
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     tail = ["--envs_per_command", "8", "--episode_length", "40", "--seed", "5", "--output", str(tmp_path / "r.json")]
     calls = []
     for name in ("command_schedule_apply", "response_accumulate"):
         real = getattr(engine.Batch, name)
         monkeypatch.setattr(engine.Batch, name, lambda self, *a, _real=real, _name=name, **k: (calls.append(_name), _real(self, *a, **k))[1])
-    rep_p, tr_p, _ = _run(track, monkeypatch, ["--checkpoint", ckpt, "--command", "0.1", "0", "0"] + tail)
+    rep_p, tr_p, _ = RC.run_track(track, monkeypatch, ["--checkpoint", ckpt, "--command", "0.1", "0", "0"] + tail)
     assert calls == []
     assert tr_p.sched is None and tr_p.sched_map is None and tr_p.response_acc is None
     assert tuple(rep_p) == track.REPORT_KEYS and all(tuple(r) == track.ROW_KEYS for r in rep_p["commands"])
     assert not [k for k in rep_p["settings"] if k in ("sequence", "then", "switch_at", "response_tolerance", "response_tail_after", "schedules")]
-    rep_s, tr_s, _ = _run(track, monkeypatch, ["--checkpoint", ckpt, "--sequence", "0: 0.1 0 0"] + tail)
+    rep_s, tr_s, _ = RC.run_track(track, monkeypatch, ["--checkpoint", ckpt, "--sequence", "0: 0.1 0 0"] + tail)
     # one apply launch at the reset, then per step one of each: the first step runs eagerly, the second is captured, the rest are replays
     assert calls.count("command_schedule_apply") == 3 and calls.count("response_accumulate") == 2 and rep_s["settings"]["graph"]
     (a,), (s,) = rep_p["commands"], rep_s["commands"]
@@ -550,7 +507,7 @@ def test_refusals_launch_nothing():
     assert b.commands is None
     for fn, call in (("odk_command_schedule_apply", apply), ("odk_response_accumulate", resp)):
         rc, msg = call(b._b)
-        assert rc == ODK_ERR_INVALID and fn in msg and "no commands bound" in msg, msg
+        assert rc == G.ERR_INVALID and fn in msg and "no commands bound" in msg, msg
     with pytest.raises(engine.OdkError, match="command_schedule_apply: no commands bound"):
         b.command_schedule_apply(tab, smap, tacc)
     with pytest.raises(engine.OdkError, match="response_accumulate: no commands bound"):
@@ -559,29 +516,29 @@ def test_refusals_launch_nothing():
     # each null pointer, by name
     for null in ("sched_dev", "sched_of_env_dev", "track_acc_dev"):
         rc, msg = apply(b._b, null=null)
-        assert rc == ODK_ERR_INVALID and "odk_command_schedule_apply" in msg and null in msg, (null, msg)
+        assert rc == G.ERR_INVALID and "odk_command_schedule_apply" in msg and null in msg, (null, msg)
     for null in ("priv_dev", "done_dev", "truncation_dev", "track_acc_dev", "sched_dev", "sched_of_env_dev", "acc_dev"):
         rc, msg = resp(b._b, null=null)
-        assert rc == ODK_ERR_INVALID and "odk_response_accumulate" in msg and null in msg, (null, msg)
+        assert rc == G.ERR_INVALID and "odk_response_accumulate" in msg and null in msg, (null, msg)
     for call in (apply, resp):
         rc, msg = call(None)
-        assert rc == ODK_ERR_INVALID and "batch" in msg
+        assert rc == G.ERR_INVALID and "batch" in msg
         for nseg in (0, -1, 9):
             rc, msg = call(b._b, nseg=nseg)
-            assert rc == ODK_ERR_INVALID and "nseg" in msg, (nseg, msg)
+            assert rc == G.ERR_INVALID and "nseg" in msg, (nseg, msg)
         for nsched in (0, -3):
             rc, msg = call(b._b, nsched=nsched)
-            assert rc == ODK_ERR_INVALID and "nsched" in msg, (nsched, msg)
+            assert rc == G.ERR_INVALID and "nsched" in msg, (nsched, msg)
     # a tolerance that is negative or not finite, a negative tail
     for bad in (-0.1, float("nan"), float("inf")):
         rc, msg = resp(b._b, lin=bad)
-        assert rc == ODK_ERR_INVALID and "lin_tol" in msg, (bad, msg)
+        assert rc == G.ERR_INVALID and "lin_tol" in msg, (bad, msg)
         rc, msg = resp(b._b, ang=bad)
-        assert rc == ODK_ERR_INVALID and "ang_tol" in msg, (bad, msg)
+        assert rc == G.ERR_INVALID and "ang_tol" in msg, (bad, msg)
         with pytest.raises(engine.OdkError, match="lin_tol"):
             b.response_accumulate(acc, tacc, tab, smap, bad, 0.2, 10)
     rc, msg = resp(b._b, tail=-1)
-    assert rc == ODK_ERR_INVALID and "tail_after" in msg, msg
+    assert rc == G.ERR_INVALID and "tail_after" in msg, msg
     # bad tensors are OdkErrors before anything is launched
     for args in ((tab[:, :, :7].contiguous(), smap, tacc), (tab.cpu(), smap, tacc), (tab, smap.long(), tacc), (tab, smap[:-1], tacc), (tab, smap, tacc.cpu())):
         with pytest.raises(engine.OdkError, match="command_schedule_apply"):
@@ -600,6 +557,6 @@ def test_refusals_launch_nothing():
     torch.cuda.synchronize()
     np.testing.assert_array_equal(cmd.cpu().numpy(), f32(0.1))
     got = acc.cpu().numpy()
-    assert np.all(got[:, ENTERED] == 1.0) and np.all(got[:, STRIDE:] == 3.0)
+    assert np.all(got[:, G.RESP_ENTERED] == 1.0) and np.all(got[:, G.RESP_STRIDE:] == 3.0)
     b.bind_commands(None)
     b.close()

@@ -8,10 +8,9 @@ import os
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+import report_cases as RC
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ASSETS = os.path.join(ROOT, "tests", "assets")
+pytestmark = pytest.mark.gpu
 
 # robot, nu, Standing?, nobs
 CASES = {"duck": ("flat_terrain", 14, False, 101), "duck_standing": ("flat_terrain", 14, True, 85),
@@ -33,7 +32,7 @@ def _batch(case, n):
     robot, nu, standing, nobs = CASES[case]
     cfg = engine.default_config(standing)
     if robot.endswith(".xml"):
-        model = Model.from_xml(os.path.join(ASSETS, robot))
+        model = Model.from_xml(os.path.join(RC.ASSETS, robot))
         cfg.use_imitation = 0
     else:
         model = load_task_model(robot)
@@ -205,23 +204,13 @@ def test_the_binding_refuses_by_name():
 E_T, T_T = 16, 20
 
 
-def _checkpoint(tmp_path):
-    import torch
-    from open_duck_playground_amd.ppo.networks import PPONetworks
-    from open_duck_playground_amd.ppo.train import save_checkpoint
-    torch.manual_seed(0)
-    ckpt = str(tmp_path / "fresh.pt")
-    save_checkpoint(ckpt, PPONetworks(101, 212, 14))
-    return ckpt
-
-
 @pytest.fixture(scope="module")
 def rig(tmp_path_factory):
     """One duck env of 2 * E_T envs under two commands and a randomly initialised policy, shared by the Tracker tests; each builds its
     Trackers one after the other and never steps an older one again."""
     import torch
     from open_duck_playground_amd import track
-    ckpt = _checkpoint(tmp_path_factory.mktemp("sensors"))
+    ckpt = RC.fresh_checkpoint(tmp_path_factory.mktemp("sensors"))
     args = track.build_parser().parse_args(["--checkpoint", ckpt, "--command", "0", "0", "0", "--seed", "1"])
     env = track.make_env(args, 2 * E_T, 0)
     net = track.load_networks(ckpt, env, torch.device("cuda", 0))
@@ -301,7 +290,7 @@ def test_the_captured_graph_follows_the_fault_tensor(rig):
 
 def test_track_sensor_sweep_end_to_end(tmp_path):
     from open_duck_playground_amd import sensors, track
-    ckpt = _checkpoint(tmp_path)
+    ckpt = RC.fresh_checkpoint(tmp_path)
     base = ["--checkpoint", ckpt, "--envs_per_command", "2", "--episode_length", "8", "--seed", "1", "--falls"]
     out = tmp_path / "report.json"
     args = track.build_parser().parse_args(base + ["--command", "0.1", "0", "0", "--sensor_grid", "imu_delay=0:2:3", "--sensor", "gyro_bias_y=0.2",

@@ -45,6 +45,64 @@ def test_every_header_constant_is_an_engine_global_and_the_other_way_round():
     assert [consts["XTERM_" + n.upper()] for n in engine.XTERM_NAMES] == list(range(12))
 
 
+# The numbers of the report accumulators' slots, as the GPU tests (tests/test_gpu_*.py) had them typed out before they took them from
+# engine: the kernels and those tests read one header, so a renumbered slot passes both and fails here.  Per accumulator: the row length
+# and (slot, offset, width), width the floats the slot takes (a pair per foot, an array per actuator lane, ...).
+SLOTS = {
+    "TRACK": (12, [("ENDED", 0, 1), ("STEPS", 1, 1), ("SAMPLES", 2, 1)]),
+    "PUSH": (10, [("PUSHED", 0, 1), ("PUSH_AT", 1, 1), ("FELL", 2, 1), ("STEPS_TO_FALL", 3, 1), ("LAST_OFF", 4, 1), ("PEAK_LIN_ERR", 5, 1),
+                  ("PEAK_ANG_ERR", 6, 1), ("PRE_LIN_ERR_SUM", 7, 1), ("PRE_SAMPLES", 8, 1)]),
+    "GAIT": (144, [("SAMPLES", 0, 1), ("SPEED_SUM", 1, 1), ("ABS_POWER_SUM", 2, 1), ("CONTACT", 3, 2), ("DOUBLE", 5, 1), ("FLIGHT", 6, 1),
+                   ("TOUCHDOWNS", 7, 2), ("SWING_STEPS_SUM", 9, 2), ("SLIP_SUM", 11, 2), ("HEIGHT_SUM", 13, 1), ("HEIGHT_SQ_SUM", 14, 1),
+                   ("ROLLPITCH_RATE_SQ_SUM", 15, 1), ("ACTION_RATE_SUM", 16, 1), ("PREV_CONTACT", 17, 2), ("AIR_RUN", 19, 2),
+                   ("TORQUE_SQ", 32, 16), ("TORQUE_PEAK", 48, 16), ("VEL_PEAK", 64, 16), ("SAT", 80, 16), ("ABS_POWER", 96, 16),
+                   ("RANGE_MIN", 112, 16), ("RANGE_MAX", 128, 16)]),
+    "POSTURE": (32, [("SAMPLES", 0, 1), ("DRIFT_SPEED_SUM", 1, 1), ("YAW_RATE_SQ_SUM", 2, 1), ("ROLLPITCH_RATE_SQ_SUM", 3, 1), ("TILT_SUM", 4, 1),
+                     ("TILT_PEAK", 5, 1), ("HEIGHT_SUM", 6, 1), ("LEG_POSE_SUM", 7, 1), ("LEG_VEL_SUM", 8, 1), ("HEAD_SQERR_SUM", 9, 1),
+                     ("ANGLE_SUM", 16, 4), ("ERR_SQ_SUM", 20, 4), ("ERR_PEAK", 24, 4), ("LAST_OFF", 28, 4)]),
+    "IMIT": (160, [("SAMPLES", 0, 1), ("GATED", 1, 1), ("SPEED_ERR_SQ_SUM", 2, 1), ("REF_SPEED_SUM", 3, 1), ("JOINT_POS_SQ_SUM", 4, 1),
+                   ("JOINT_VEL_SQ_SUM", 5, 1), ("BOTH", 6, 2), ("ROBOT_ONLY", 8, 2), ("REF_ONLY", 10, 2), ("REF_TOUCHDOWNS", 12, 2),
+                   ("TOUCHDOWNS", 14, 2), ("LAG_SUM", 16, 2), ("LAG_ABS_SUM", 18, 2), ("PREV_CONTACT", 20, 2), ("PREV_REF", 22, 2),
+                   ("REF_AGE", 24, 2), ("POS_ERR_SUM", 32, 16), ("POS_ERR_SQ", 48, 16), ("POS_ERR_PEAK", 64, 16), ("VEL_ERR_SQ", 80, 16),
+                   ("RANGE_MIN", 96, 16), ("RANGE_MAX", 112, 16), ("REF_RANGE_MIN", 128, 16), ("REF_RANGE_MAX", 144, 16)]),
+    # one segment's block of the step-response row; the row is SCHED_MAX_SEGMENTS of them
+    "RESP": (24, [("ENTERED", 0, 1), ("SAMPLES", 1, 1), ("FELL", 2, 1), ("STEPS_TO_FALL", 3, 1), ("FIRST_IN", 4, 1), ("LAST_OFF", 5, 1),
+                  ("PEAK_LIN_ERR", 6, 1), ("PEAK_ANG_ERR", 7, 1), ("SUM", 8, 3), ("SQERR", 11, 3), ("OVERSHOOT", 14, 3), ("TAIL_SAMPLES", 17, 1),
+                  ("TAIL_SUM", 18, 3)]),
+    # the head of a fall-recorder row, and one sample of its ring (FALL_S_*) ahead of the sample's qpos
+    "FALL": (16, [("SAMPLES", 0, 1), ("FELL", 1, 1), ("STEP", 2, 1), ("LAST_UPRIGHT", 3, 1), ("UPRIGHT_CONTACT", 4, 2), ("TILT_PEAK", 6, 1)]),
+    "FALL_S": (16, [("STEP", 0, 1), ("UP", 1, 3), ("GYRO", 4, 3), ("LINVEL", 7, 3), ("HEIGHT", 10, 1), ("CONTACT", 11, 2), ("LIN_ERR", 13, 1),
+                    ("ANG_ERR", 14, 1), ("SAT", 15, 1)]),
+    "PATH": (32, [("START_X", 0, 1), ("START_Y", 1, 1), ("START_HX", 2, 1), ("START_HY", 3, 1), ("X", 4, 1), ("Y", 5, 1), ("HX", 6, 1), ("HY", 7, 1),
+                  ("LENGTH", 8, 1), ("TURN", 9, 1), ("SAMPLES", 10, 1), ("FELL", 11, 1), ("FELL_LEG", 12, 1), ("WP_INDEX", 13, 1),
+                  ("XTRACK_SAMPLES", 14, 1), ("XTRACK_SQ", 15, 1), ("XTRACK_PEAK", 16, 1), ("GOAL_DIST", 17, 1), ("REACHED", 18, 8)]),
+}
+# the row lengths by the header's names, and what else those tests had as a literal
+SIZES = {"ERR_INVALID": -1, "TRACK_NACC": 12, "PUSH_NACC": 10, "GAIT_NACC": 144, "GAIT_STRIDE": 16, "POSTURE_NACC": 32, "IMIT_NACC": 160,
+         "IMIT_STRIDE": 16, "RESP_STRIDE": 24, "RESP_NACC": 192, "SCHED_MAX_SEGMENTS": 8, "SCHED_SEG_FLOATS": 8, "SCHED_NEVER": 1.0e9, "FALL_HEAD": 16,
+         "FALL_SAMPLE": 16, "FALL_MAX_RING": 64, "PATH_NACC": 32, "PATH_MAX_WAYPOINTS": 8, "PATH_COURSE_FLOATS": 17, "CURR_HEAD": 0, "CURR_EPISODE": 1,
+         "CURR_STAT_UPDATES": 0, "CURR_STAT_PROMOTED": 2, "REPLAY_POS_ERR_PEAK": 3}
+ROW_LENGTH = {"RESP": "RESP_STRIDE", "FALL": "FALL_HEAD", "FALL_S": "FALL_SAMPLE"}      # the others: <accumulator>_NACC
+
+
+def test_the_report_slots_keep_the_numbers_the_gpu_tests_were_written_against():
+    consts = engine.header_constants()
+    for name, v in SIZES.items():
+        assert consts[name] == v and type(consts[name]) is type(v), f"include/odk.h ODK_{name} = {consts[name]!r}, the tests were written against {v!r}"
+    assert consts["RESP_NACC"] == consts["RESP_STRIDE"] * consts["SCHED_MAX_SEGMENTS"]
+    assert consts["PATH_COURSE_FLOATS"] == 1 + 2 * consts["PATH_MAX_WAYPOINTS"]
+    for acc, (length, slots) in SLOTS.items():
+        assert SIZES[ROW_LENGTH.get(acc, acc + "_NACC")] == length
+        taken = {}
+        for slot, at, width in slots:
+            name = f"{acc}_{slot}"
+            assert consts[name] == at, f"include/odk.h ODK_{name} = {consts[name]}, the tests were written against {at}"
+            assert at >= 0 and at + width <= length, f"ODK_{name}: {at} .. {at + width - 1} does not end within the row's {length} floats"
+            for c in range(at, at + width):
+                assert c not in taken, f"ODK_{name} and ODK_{taken[c]} overlap at float {c}"
+                taken[c] = name
+
+
 def test_the_grammar_on_synthetic_text():
     text = """
     #ifndef ODK_H
