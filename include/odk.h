@@ -891,7 +891,7 @@ int odk_batch_set_state(odk_batch* b, const float* qpos, const float* qvel, cons
  * contact_dist [nenv,12], qacc [nenv,nv]  (any may be NULL) */
 int odk_batch_get_debug(odk_batch* b, float* sensordata, float* actuator_force, float* contact_dist, float* qacc);
 /* debug: LDS image (floats) of every env's last forward pass, taken at reset / physics_step and, when
- * odk_set_debug_dump(1), at step; odk_lds_offset names the arrays inside it (csrc/odk_kernels.h Shape) */
+ * odk_set_debug_dump(1), at step; odk_lds_offset names the arrays inside it (csrc/odk_shape.h Shape) */
 void odk_set_debug_dump(int on);
 int odk_batch_lds_size(const odk_batch* b);
 int odk_batch_get_lds(odk_batch* b, float* host_image);

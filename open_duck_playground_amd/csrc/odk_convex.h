@@ -10,6 +10,11 @@
 // are two rows, i.e. they share every instruction.  Geometry sits in LDS that is dead between the inertia and the constraint
 // phases; topology tables (face polygons, unique edges with their two faces) are built at model load (odk_model_load.hip).
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include "odk_algebra.h"
+#include "odk_lanes.h"
+#include "odk_model.h"
 
 namespace odk {
 

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "odk_shapes.h"
+#include "odk_kernels.h"
 #include "odk_poison.h"
 
 // per-env HBM records, observation strides, random-draw streams, the env logic's LDS floats (EnvL), the kernels' arguments (KArgs, XTerms, DRL)

@@ -1,4 +1,5 @@
-// odk_kernels.h -- device code of the fused env step (odk_env_kernels.h; the host-only model loader takes Shape and compute_statics from it).
+// odk_kernels.h -- device code of the fused env step, for odk_env_kernels.h alone, on top of the layers it includes: odk_shape.h (EnvCfg,
+// Shape, Statics, compute_statics: also the host code's), odk_lanes.h (ODK_SYNC, DPP reductions: also the report kernels'), odk_algebra.h, odk_convex.h.
 //
 // Geometry: one workgroup = one wavefront (64 lanes) = 64/G environments, G lanes per env
 // (G = 32 or 64).  Every per-env array lives in LDS for the whole env step; HBM is touched once at
@@ -36,425 +37,17 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "odk_model.h"
+#include "odk_algebra.h"
+#include "odk_convex.h"
+#include "odk_lanes.h"
+#include "odk_shape.h"
 
 namespace odk {
 
-// One workgroup == one wavefront: DS (LDS) instructions of a wave are issued and serviced in order, so
-// cross-lane hand-offs through LDS need no s_barrier and no s_waitcnt -- only a compiler barrier that keeps
-// the LDS accesses in program order (and stops values being cached in registers across the hand-off).
-// NOTE: never put __restrict__ on an LDS pointer: with noalias the optimiser may treat the barrier as not
-// touching that memory and reuse a value loaded before another lane's store.
-#define ODK_SYNC() asm volatile("" ::: "memory")
-
-constexpr float MINVAL_F = 1e-15f;
-constexpr float PI_F = 3.14159265358979323846f;
-
-struct EnvCfg {  // device copy of odk_env_config
-  float ctrl_dt, action_scale, dof_vel_scale, max_motor_velocity;
-  float noise_level, noise_gyro, noise_accelerometer, noise_gravity, noise_joint_vel;
-  float qpos_noise_scale[16];
-  float reward_scales[7];
-  float tracking_sigma;
-  float push_enable, push_interval_range[2], push_magnitude_range[2];
-  float cmd_range[7][2];
-  int use_imitation, use_motor_speed_limits, autoreset, episode_length, n_substeps;
-  int kind, nobs, npriv;   // env kind (0 Joystick, 1 Standing) and its output row strides
-  float reset_base_qvel;
-};
-
-// ------------------------------------------------------------------------------------------------
-// LDS layout (floats), per environment.  Component-major (SoA) arrays: X[k * N + item].
-template <int NQ_, int NV_, int NB_, int NU_, int NJ_, int NM_, int NH_, int NROW_, int DT_, int DV_, bool CONE_ = false, int CL_ = -1, bool OPT_ = false, int NCH_ = 3>
-struct Shape {
-  static constexpr int NQ = NQ_, NV = NV_, NB = NB_, NU = NU_, NJ = NJ_, NM = NM_, NH = NH_, NROW = NROW_;
-  static constexpr int DT = DT_;    // max dof depth, kinematic tree
-  static constexpr int DV = DV_;    // max dof depth, virtual (Hessian) tree
-  static constexpr int NCROW = 48;  // contact rows
-  // Twin dofs (the backlash model, nv 30): solves run on the reduced tree -- twins merged into their main dof, which is
-  // the 20-dof robot's own tree (DevModel::paired; reduced_rhs / reduced_expand below).
-  static constexpr bool PAIRED = (NV_ == 30);
-  // Hinges on one body: two only where a backlash twin shares its joint's body.  The joint-slot loops of forward_env's pose sweep run to
-  // MAXJB and size their register arrays by it, so a shape without twins carries no second slot (its copies, zero fills and exec-mask
-  // bookkeeping); the BodySt record keeps both slots.  The loader refuses a body with more hinges than its shape's MAXJB (select_shape).
-  static constexpr int MAXJB = PAIRED ? 2 : 1;
-  // <equality><joint> rows (DevModel::neq) are compiled into this shape's kernels: the third shape (tests/assets/tail_biped*.xml) -- the
-  // duck's shapes have no equality and do not pay for the code
-  static constexpr bool EQ = (NV_ == 21) || OPT_;      // (OPT_: a shape that asks for the optional constraint code -- equality rows, elliptic cones as a runtime switch)
-  // <option cone="elliptic"> (DevModel::cone) is compiled into the same shape's kernels: a contact's four row lanes hold normal | tangent 1 |
-  // tangent 2 | nothing instead of the four pyramid edges, and the cost of a contact is the cone's (odk_kernels.h "elliptic cones")
-  static constexpr bool CONE = CONE_;                   // an instantiation that is ONLY launched for cone = 1 models: the pyramid code is compiled out
-  static constexpr bool ELL = (NV_ == 21) || CONE_ || OPT_;    // (the duck's shapes: their own instantiations with CONE_ = true, launched for models with cone = 1 only)
-  static constexpr int NVR = PAIRED ? 20 : NV_;    // reduced dofs
-  static constexpr int NMR = PAIRED ? 145 : NM_;   // entries of the reduced tree layout
-  static constexpr int NHR = PAIRED ? 170 : NH_;   // entries of the reduced virtual-tree layout
-  static constexpr int DVR = PAIRED ? 15 : DV_;    // max dof depth, reduced virtual tree
-  // workgroup-shared LDS tables behind the envs' images (odk_env_kernels.h load_shared): the packed reduced entries and the
-  // contact-row constants.  (Friction-loss rows, actuator constants and the foot hull were tried there too: no gain, their
-  // loads from the L2-resident model are already covered.)
-  static constexpr int SH_CT = NMR, SH_HOT = SH_CT + 42;
-  static constexpr int CL = CL_ >= 0 ? CL_ : ((NV_ == 20 || NV_ == 21 || PAIRED) ? 5 : 0);   // max (reduced) chain length for chain_solve: every compiled shape is a floating base + <= NCH serial chains of <= CL (reduced) dofs (0: generic path)
-  static constexpr int NCH = NCH_;  // serial chains below the floating base that chain_solve eliminates: chain c on lanes 8 c .. 8 c + 6 (a biped with arms: 4)
-  static_assert(NCH >= 1 && NCH <= 4, "chain_solve: one 8-lane group per chain, 32 lanes");
-  // persistent over the env step
-  static constexpr int O_QPOS = 0;
-  static constexpr int O_QVEL = O_QPOS + NQ;
-  static constexpr int O_WARM = O_QVEL + NV;
-  static constexpr int O_CTRL = O_WARM + NV;
-  // per-env effective model parameters (domain randomisation lands here)
-  static constexpr int O_Q0 = O_CTRL + NU;     // qpos0
-  static constexpr int O_MASS = O_Q0 + NQ;     // body_mass
-  static constexpr int O_ARM = O_MASS + NB;    // dof_armature
-  static constexpr int O_FRL = O_ARM + NV;     // dof_frictionloss
-  static constexpr int O_KP = O_FRL + NV;      // actuator kp
-  static constexpr int O_IPOS1 = O_KP + NU;    // body_ipos[1]
-  // tree sweeps (component-major by body)
-  static constexpr int O_XPOS = O_IPOS1 + 3;         // [3][NB]
-  static constexpr int O_XQUAT = O_XPOS + 3 * NB;    // [4][NB]
-  static constexpr int O_CVEL = O_XQUAT + 4 * NB;    // [6][NB]
-  static constexpr int O_CACC = O_CVEL + 6 * NB;     // [6][NB] velocity-dependent part of cacc (gravity folded in)
-  static constexpr int O_CFRC = O_CACC + 6 * NB;     // [6][NB] local then subtree-accumulated bias force
-  static constexpr int O_CRB = O_CFRC + 6 * NB;      // [10][NB] cinert then composite inertia
-  // matrix work runs on the REDUCED dofs (twins merged, DevModel::paired): one motion column per reduced dof
-  static constexpr int O_CDOF = O_CRB + 10 * NB;     // [6][NVR]
-  static constexpr int O_BUF6 = O_CDOF + 6 * NVR;    // [6][NVR] crb*cdof -> K_L*cdof
-  static constexpr int O_BUF6B = O_BUF6 + 6 * NVR;   // [6][NVR] K_R*cdof
-  static constexpr int O_M = O_BUF6B + 6 * NVR;      // [NMR] sparse reduced inertia (rows by ancestor depth; twin pairs: no armature)
-  static constexpr int O_HL = O_M + NMR;             // [NHR] reduced inertia / Hessian with the diagonal terms, and its factor
-  // dof vectors
-  static constexpr int O_QFS = O_HL + NHR;           // qfrc_smooth
-  static constexpr int O_QAS = O_QFS + NV;           // qacc_smooth
-  static constexpr int O_X = O_QAS + NV;             // current qacc iterate
-  static constexpr int O_MA = O_X + NV;              // scratch: per-dof friction-row hand-over
-  static constexpr int O_GRAD = O_MA + NV;           // search direction
-  static constexpr int O_MV = O_GRAD + NV;           // scratch: per-dof friction-row hand-over
-  // constraint rows
-  static constexpr int O_D = O_MV + NV;              // efc_D (0 = structurally inactive row)
-  static constexpr int O_AREF = O_D + NROW;
-  static constexpr int O_JAR = O_AREF + NROW;        // J qacc - aref (contact rows)
-  static constexpr int O_JV = O_JAR + NROW;          // J search (scratch: candidate Jaref, forces, Hessian diagonal addend)
-  static constexpr int O_SC = O_JAR;                 // [2][NJ] sin/cos of the half joint angles: P0 -> P1 only, ALIASES jar (born in P9)
-  static_assert(2 * NJ <= NROW, "sin/cos must fit in the jar rows");
-  // [NCROW][6] contact row wrenches [r x dir; dir]: ALIAS cfrc|crb, which are dead once the bias forces and M entries exist (P3/P4; W is
-  // born in P8) -- where that region is large enough (18 bodies); a smaller robot gets its own floats behind the image
-  static constexpr bool W_FITS = 6 * NCROW <= 16 * NB;
-  static constexpr int O_CDIST = O_JV + NROW;        // [12]
-  static constexpr int O_CR = O_CDIST + NCON;        // [12][3] contact position relative to the base origin
-  static constexpr int O_SCR = O_CR + 3 * NCON;      // scratch: foot twists, wrenches, 6x6 blocks, sensor inputs
-  // scratch sub-offsets
-  static constexpr int S_VF = 0;      // [2][6] foot twist of the current vector
-  static constexpr int S_FF = 12;     // [2][6] foot wrench sums
-  static constexpr int S_K = 24;      // [3][36] K_L, K_R, K_X
-  static constexpr int S_FR = S_K;    // [8][9] frames of the floor contacts (height field / primitive feet): contact phase -> row phase only, ALIASES
-                                      // the K blocks (born in the solver).  NOT in the row arrays: the foot-foot routine's hull copies live there.
-  static constexpr int S_VF2 = 132;   // [2][6] second foot twist (warmstart candidate)
-  static constexpr int S_FFX = 144;   // [6] wrench sum of the foot-foot rows
-  static constexpr int S_EQ = 150;    // [EQ_MAX] equality rows: the Hessian's off-diagonal addend -D c (force phase -> Hessian entries; the solve's scratch runs over it afterwards)
-  // the chain solve's scratch starts at S_K and takes NCH CL 7 + 27 floats (three chains: 156 for chains of five, up to S_MISC; 177 for chains of six;
-  // four chains of six: 219): it runs over
-  // S_VF2 / S_FFX / S_EQ, which are dead by then -- but never over the misc scalars, which the env kernels' epilogue reads (foot heights, gravity)
-  static constexpr int S_SOLVE_END = S_K + 7 * NCH * CL + 27;
-  static constexpr int S_MISC = S_SOLVE_END > 156 ? S_SOLVE_END : 156;  // misc scalars (16)
-  static constexpr int S_PROF = S_MISC + 16;   // [20] per-phase cycle counters (ODK_PROFILE builds)
-  static constexpr int S_PROF2 = S_PROF + 20;  // [16] height-field contacts: hull setup, cull pass, register loads, pair loop, iterations, list length, -, -,
-                                               //      then inside a pair: select + prism, face query, Gauss-map tests, passing pairs, faces / polygons, clip + manifold, merge
-  static constexpr int S_PROF3 = S_PROF2 + 16; // [4] line search: passes of the bracketing loop, summed over the forwards (lane 0)
-#ifdef ODK_PROFILE
-  static constexpr int N_SCR = S_PROF3 + 4;
-#else
-  static constexpr int N_SCR = ((S_MISC + 16 + 3) / 4) * 4;      // no S_PROF slots outside profile builds (172 for chains of five)
-#endif
-  static constexpr int O_SENS = O_JV;                // sensordata[46]: born after the line search (P10, last substep only), ALIASES jv
-  static_assert(NSENSD <= NROW, "sensordata must fit in the jv rows");
-  static constexpr int O_ACTF = O_SCR + N_SCR;       // actuator_force
-  static constexpr int O_QACC = O_X;                 // qacc of the last forward == final iterate
-  // path rows of shapes with EQ (<equality><connect | weld>, DevModel::neqp): wrenches [EQP_ROWS][12] | J [EQP_ROWS][NV] | D | aref | residual
-  static constexpr int O_EQP = ((O_ACTF + NU + 3) / 4) * 4;
-  static constexpr int EQP_W = 0, EQP_J = 12 * EQP_ROWS, EQP_D = EQP_J + EQP_ROWS * NV, EQP_AREF = EQP_D + EQP_ROWS, EQP_POS = EQP_AREF + EQP_ROWS;
-  static constexpr int N_EQP = EQ ? ((EQP_POS + EQP_ROWS + 3) / 4) * 4 : 0;
-  static constexpr int O_WX = O_EQP + N_EQP;         // the contact row wrenches of a robot with fewer than 18 bodies
-  static constexpr int O_W = W_FITS ? O_CFRC : O_WX;
-  static constexpr int TOTAL = O_WX + (W_FITS ? 0 : 6 * NCROW);
-  // the env logic's floats behind the physics image (odk_shapes.h EnvL): the carried info (43 + 7 NU floats, rec_lay) and this step's action + the
-  // imitation phase, both rounded up to whole float4s (the duck: 144 + 16)
-  static constexpr int N_INFO = ((43 + 7 * NU + 3) / 4) * 4, N_ACT = ((NU + 2 + 3) / 4) * 4;
-  static constexpr int ENV_STRIDE = TOTAL + N_INFO + N_ACT;   // floats between the images of the two envs of a workgroup (odk_shapes.h EnvL::TOTAL)
-  // The model's uniform floats of the substep (DevModel::hot_f) as a third shared table at SH_HOT, read by LDS broadcast instead of an L2
-  // round trip -- for a shape whose two-env workgroup has the room: the HOT_NF floats must not cost a workgroup per CU (160 KiB of LDS,
-  // 8 single-wave workgroups at most).  A shape without the room keeps the loads from the model.
-  static constexpr int wgs_per_cu(int floats) { return 163840 / (4 * floats) > 8 ? 8 : 163840 / (4 * floats); }
-  static constexpr bool HOT_LDS = wgs_per_cu(2 * ENV_STRIDE + SH_HOT + HOT_NF) == wgs_per_cu(2 * ENV_STRIDE + SH_HOT);
-  static constexpr int SHARED = SH_HOT + (HOT_LDS ? HOT_NF : 0);
-};
-
-// Phase timing (build with -DODK_PROFILE): lane 0 accumulates shader-clock deltas per phase into the
-// scratch area, which the debug LDS image carries out.  Zero cost when the macro is off.
-#ifdef ODK_PROFILE
-#define ODK_PROF(i) do { if (lane == 0) { long long _t = clock64(); SCR[S::S_PROF + (i)] += (float)(_t - _tprev); _tprev = _t; } } while (0)
-#define ODK_PROF_BEGIN() long long _tprev = clock64()
-#define ODK_LS_LOOP(tag) do { if (lane == 0 && (tag) == 0) SCR[S::S_PROF3] += 1.0f; } while (0)   // one pass of the line search's bracketing loop
-#elif defined(ODK_MARK)   // phase markers in the ISA listing (tools/isa_phase_stats.py): comments only
-#define ODK_PROF(i) asm volatile("; ODK_PHASE_END " #i ::: "memory")
-#define ODK_PROF_BEGIN() asm volatile("; ODK_PHASE_BEGIN" ::: "memory")
-#define ODK_LS_LOOP(tag) asm volatile("; LS_LOOP_" #tag ::: "memory")   // LS_LOOP_0 .. LS_LOOP_1: the loop body as a region of its own (tools/isa_select_census.py)
-#else
-#define ODK_PROF(i) do { } while (0)
-#define ODK_PROF_BEGIN() do { } while (0)
-#define ODK_LS_LOOP(tag) do { } while (0)
-#endif
-
-// ------------------------------------------------------------------------------------------------
-// Cross-lane all-reduce over the G lanes of one env with DPP (no LDS traffic): xor-1 / xor-2 quad permutes,
-// row_half_mirror, row_mirror give every lane its 16-lane row total; rows are then combined with row_bcast15
-// (/31) and the group total is read back with v_readlane.  MUST be called in uniform control flow.
-// old = 0 with bound_ctrl lets the compiler fold the permute into the consuming VALU op (v_add_f32_dpp ...): one
-// instruction per butterfly stage, no copies, no hazard nops.  (All four patterns read only enabled in-row lanes.)
-#define ODK_DPP(v, ctrl, rmask) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, rmask, 0xF, true))
-struct OpSum { static __device__ __forceinline__ float f(float a, float b) { return a + b; } };
-struct OpMax { static __device__ __forceinline__ float f(float a, float b) { return fmaxf(a, b); } };
-struct OpMin { static __device__ __forceinline__ float f(float a, float b) { return fminf(a, b); } };
-typedef unsigned int odk_u2 __attribute__((ext_vector_type(2)));
-template <int G, class Op> __device__ __forceinline__ float greduce(float v) {
-  v = Op::f(v, ODK_DPP(v, 0xB1, 0xF));    // quad_perm [1,0,3,2]
-  v = Op::f(v, ODK_DPP(v, 0x4E, 0xF));    // quad_perm [2,3,0,1]
-  v = Op::f(v, ODK_DPP(v, 0x141, 0xF));   // row_half_mirror
-  v = Op::f(v, ODK_DPP(v, 0x140, 0xF));   // row_mirror: every lane holds its row's total
-  // gfx950 v_permlane16_swap: rows (r0 r1 r2 r3),(s0 s1 s2 s3) -> (r0 s0 r2 s2),(r1 s1 r3 s3); with both operands = v the
-  // two results are (x0 x0 x2 x2) and (x1 x1 x3 x3): their combination is the 32-lane group total in every lane.
-  const unsigned iv = __float_as_uint(v);
-  const odk_u2 h = __builtin_amdgcn_permlane16_swap(iv, iv, false, false);
-  v = Op::f(__uint_as_float(h[0]), __uint_as_float(h[1]));
-  if (G == 64) {   // v_permlane32_swap: halves (lo hi),(lo hi) -> (lo lo),(hi hi)
-    const unsigned iw = __float_as_uint(v);
-    const odk_u2 w = __builtin_amdgcn_permlane32_swap(iw, iw, false, false);
-    v = Op::f(__uint_as_float(w[0]), __uint_as_float(w[1]));
-  }
-  return v;
-}
-template <int G> __device__ __forceinline__ float gsum(float v) { return greduce<G, OpSum>(v); }
-// Chain scans of forward_env (P1 / P2), step si = 0, 1, 2 shifts by 2^si lanes: row_shr (lane l reads lane l - 2^si) and
-// row_shl (l + 2^si) inside the lane's 16-lane row, 0 from beyond the row's edge (bound_ctrl).  The host's body-to-lane
-// layout keeps every serial body chain inside one row.  Uniform control flow only; si must fold to a constant.
-__device__ __forceinline__ float row_shr(float v, int si) { return si == 0 ? ODK_DPP(v, 0x111, 0xF) : si == 1 ? ODK_DPP(v, 0x112, 0xF) : ODK_DPP(v, 0x114, 0xF); }
-__device__ __forceinline__ float row_shl(float v, int si) { return si == 0 ? ODK_DPP(v, 0x101, 0xF) : si == 1 ? ODK_DPP(v, 0x102, 0xF) : ODK_DPP(v, 0x104, 0xF); }
-// N sums at once (G = 32): the four in-row butterfly stages on the VALU as above, then the two rows are exchanged by
-// ds_swizzle (xor 16 inside each 32-lane group: the LDS crossbar, no memory access and no VALU slot) instead of
-// v_permlane16_swap (~8 cycles of VALU issue each); the N swizzles are in flight together, so their latency is paid once.
-template <int G, int N> __device__ __forceinline__ void gsum_n(float* v) {
-  if constexpr (G == 32) {
-    float o[N];
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-      float x = v[i];
-      x += ODK_DPP(x, 0xB1, 0xF); x += ODK_DPP(x, 0x4E, 0xF); x += ODK_DPP(x, 0x141, 0xF); x += ODK_DPP(x, 0x140, 0xF);
-      v[i] = x;
-      o[i] = __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(x), 0x401F));   // bit mode: and 0x1F, or 0, xor 0x10
-    }
-#pragma unroll
-    for (int i = 0; i < N; i++) v[i] += o[i];
-  } else {
-#pragma unroll
-    for (int i = 0; i < N; i++) v[i] = gsum<G>(v[i]);
-  }
-}
-// max / min / argmax run on order-preserving unsigned keys: integer v_max_u32 / v_min_u32 fold the DPP permute into the
-// op (float max needs a canonicalising v_max x, x per stage under IEEE mode, and then the permute stays a separate mov)
-__device__ __forceinline__ unsigned fkey(float v) { const unsigned b = __float_as_uint(v); return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
-__device__ __forceinline__ float fkey_inv(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)); }
-#define ODK_DPPU(v, ctrl) ((unsigned)__builtin_amdgcn_update_dpp(0, (int)(v), ctrl, 0xF, 0xF, true))
-template <int G, bool MAX> __device__ __forceinline__ unsigned greduce_u(unsigned v) {
-  auto op = [](unsigned a, unsigned b) { return MAX ? (a > b ? a : b) : (a < b ? a : b); };
-  v = op(v, ODK_DPPU(v, 0xB1));
-  v = op(v, ODK_DPPU(v, 0x4E));
-  v = op(v, ODK_DPPU(v, 0x141));
-  v = op(v, ODK_DPPU(v, 0x140));
-  const odk_u2 h = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-  v = op(h[0], h[1]);
-  if (G == 64) {
-    const odk_u2 w = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-    v = op(w[0], w[1]);
-  }
-  return v;
-}
-template <int G> __device__ __forceinline__ float gmax(float v) { return fkey_inv(greduce_u<G, true>(fkey(v))); }
-template <int G> __device__ __forceinline__ float gmin(float v) { return fkey_inv(greduce_u<G, false>(fkey(v))); }
-// argmax, lowest index wins ties (jnp.argmax semantics): max of the values, then min index among the maxima
-template <int G> __device__ __forceinline__ int gargmax(float v, int i) {
-  const unsigned k = fkey(v);
-  const unsigned mx = greduce_u<G, true>(k);
-  return (int)greduce_u<G, false>(k == mx ? (unsigned)i : 0x7FFFFFFFu);
-}
-// value held by lane j (uniform j < G) of this env's lane group, via v_readlane (no LDS)
-template <int G> __device__ __forceinline__ float bcast(float v, int j) {
-  const int iv = __float_as_int(v);
-  if (G == 64) return __int_as_float(__builtin_amdgcn_readlane(iv, j));
-  const int lo = __builtin_amdgcn_readlane(iv, j), hi = __builtin_amdgcn_readlane(iv, j + 32);
-  return __int_as_float((threadIdx.x & 32) ? hi : lo);
-}
-// uniform integer static of lane j (identical in every env of the wave)
-__device__ __forceinline__ int ubcast(int v, int j) { return __builtin_amdgcn_readlane(v, j); }
-
-__device__ __forceinline__ void cross3(float* r, const float* a, const float* b) {
-  float x = a[1] * b[2] - a[2] * b[1], y = a[2] * b[0] - a[0] * b[2], z = a[0] * b[1] - a[1] * b[0];
-  r[0] = x; r[1] = y; r[2] = z;
-}
-__device__ __forceinline__ float dot3(const float* a, const float* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-__device__ __forceinline__ void qmul(float* r, const float* a, const float* b) {
-  float w = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
-  float x = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
-  float y = a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1];
-  float z = a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0];
-  r[0] = w; r[1] = x; r[2] = y; r[3] = z;
-}
-__device__ __forceinline__ void qnormalize(float* q) {   // v_rsq_f32 (1 ulp) instead of IEEE sqrt + division (~20 instructions)
-  const float n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
-  if (n2 < MINVAL_F * MINVAL_F) { q[0] = 1; q[1] = q[2] = q[3] = 0; return; }
-  const float inv = __builtin_amdgcn_rsqf(n2);
-  q[0] *= inv; q[1] *= inv; q[2] *= inv; q[3] *= inv;
-}
-__device__ __forceinline__ void qrot(float* r, const float* q, const float* v) {  // r = R(q) v
-  float t[3], u[3] = {q[1], q[2], q[3]}, c[3];
-  cross3(t, u, v);
-  t[0] *= 2; t[1] *= 2; t[2] *= 2;
-  cross3(c, u, t);
-  r[0] = v[0] + q[0] * t[0] + c[0]; r[1] = v[1] + q[0] * t[1] + c[1]; r[2] = v[2] + q[0] * t[2] + c[2];
-}
-__device__ __forceinline__ void q2mat(float* m, const float* q) {
-  float w = q[0], x = q[1], y = q[2], z = q[3];
-  m[0] = w * w + x * x - y * y - z * z; m[1] = 2 * (x * y - w * z); m[2] = 2 * (x * z + w * y);
-  m[3] = 2 * (x * y + w * z); m[4] = w * w - x * x + y * y - z * z; m[5] = 2 * (y * z - w * x);
-  m[6] = 2 * (x * z - w * y); m[7] = 2 * (y * z + w * x); m[8] = w * w - x * x - y * y + z * z;
-}
-// spatial inertia (10: Ixx Iyy Izz Ixy Ixz Iyz mcx mcy mcz m) times motion [ang; lin] (mju_mulInertVec)
-__device__ __forceinline__ void inert_mul(float* res, const float* i, const float* v) {
-  res[0] = i[0] * v[0] + i[3] * v[1] + i[4] * v[2] - i[8] * v[4] + i[7] * v[5];
-  res[1] = i[3] * v[0] + i[1] * v[1] + i[5] * v[2] + i[8] * v[3] - i[6] * v[5];
-  res[2] = i[4] * v[0] + i[5] * v[1] + i[2] * v[2] - i[7] * v[3] + i[6] * v[4];
-  res[3] = i[8] * v[1] - i[7] * v[2] + i[9] * v[3];
-  res[4] = i[6] * v[2] - i[8] * v[0] + i[9] * v[4];
-  res[5] = i[7] * v[0] - i[6] * v[1] + i[9] * v[5];
-}
-__device__ __forceinline__ void cross_motion(float* res, const float* vel, const float* v) {  // mju_crossMotion
-  float a[3], b[3];
-  cross3(res, vel, v);
-  cross3(a, vel, v + 3);
-  cross3(b, vel + 3, v);
-  res[3] = a[0] + b[0]; res[4] = a[1] + b[1]; res[5] = a[2] + b[2];
-}
-
-// ---- RNG: threefry2x32-20, stream definition shared with oracle/odk_oracle_env.c
-__device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-__device__ inline void threefry2x32(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t& o0, uint32_t& o1) {
-  const int R[8] = {13, 15, 26, 6, 17, 29, 16, 24};
-  uint32_t ks[3] = {k0, k1, 0x1BD11BDAu ^ k0 ^ k1};
-  uint32_t x0 = c0 + ks[0], x1 = c1 + ks[1];
-#pragma unroll
-  for (int blk = 0; blk < 5; blk++) {
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      x0 += x1;
-      x1 = rotl32(x1, R[(blk & 1) * 4 + r]);
-      x1 ^= x0;
-    }
-    x0 += ks[(blk + 1) % 3];
-    x1 += ks[(blk + 2) % 3] + (uint32_t)(blk + 1);
-  }
-  o0 = x0; o1 = x1;
-}
-__device__ inline float rng_uniform(uint32_t k0, uint32_t k1, uint32_t ctr, uint32_t idx) {
-  uint32_t a, b;
-  threefry2x32(k0, k1, ctr, idx >> 1, a, b);
-  return (float)(((idx & 1) ? b : a) >> 8) * (1.0f / 16777216.0f);
-}
-__device__ __forceinline__ int randint3(float u) { int i = (int)(u * 3.0f); return i > 2 ? 2 : i; }
-
-// ------------------------------------------------------------------------------------------------
-// Per-lane static data, loaded once per launch.  A lane plays several roles (body `lane`, dof `lane`,
-// joint `lane`, hull vertex `lane`, a few matrix entries and constraint rows); roles beyond the
-// model's counts are disabled by their flags.
-// Persistent part: what the factor / solve / solver phases need all the time (kept small: register pressure
-// decides whether two wavefronts fit on a SIMD).
-template <class S, int G>
-struct Statics : LaneSt {   // (data members: odk_model.h LaneSt)
-  static constexpr int NME = (S::NMR + G - 1) / G;  // reduced inertia entries per lane
-  static constexpr int NHE = (S::NHR + G - 1) / G;  // reduced virtual-tree Hessian entries per lane
-  static_assert((S::NVR + 1) / 2 <= 16, "LaneSt::m_adr");
-};
-// Phase-local statics: fetched from the model (L1/L2-resident, one batch of loads per phase and substep)
-// right where they are used, so they do not occupy registers for the rest of the substep.
-// (BodySt: odk_model.h -- the per-body records are part of the device model)
-struct ActSt { float bias2, clo, chi, flo, fhi; int climited, flimited; };
-struct FlSt { float D, R, b; int dof; };
-
-// The same three records held over the whole launch instead (plane-floor kernels: ~40 registers are free there since round 3, and
-// each of these loads sat exposed right behind a phase hand-off in every substep)
-// ve: the 17th hull vertex of the lane's foot; pk: DevModel::hot_pk, the model's wave-uniform small integers as three packed words (held in
-// vector registers; forward_env makes them uniform once per substep and extracts every field on the scalar unit); np: the lane's record of
-// the subtree fold (DevModel::np_rec: the six sources, the target and the count as byte fields in two registers -- as eight plain registers
-// the lists had cost 1 %: profiles/load_waits/NOTES.md).  (The limit rows' records the same way: over the register budget.)
-struct HotSt { ActSt as; FlSt fs; float vb[3], ve[3]; int pk[HOT_NPK], np[2]; };
-
-// Device side: the lane's host-built record (DevModel::lane_st, filled by compute_statics below at model load)
+// Device side: the lane's host-built record (DevModel::lane_st, filled by compute_statics -- odk_shape.h -- at model load)
 template <class S, int G>
 __device__ __forceinline__ void load_statics(Statics<S, G>& st, const DevModel* __restrict__ m, int lane) {
   static_cast<LaneSt&>(st) = m->lane_st[lane];
-}
-template <class S>
-__host__ __device__ inline void compute_statics(LaneSt& st, const DevModel* m, int lane) {
-  {
-    const bool on = lane >= 1 && lane < S::NJ;
-    st.j_qadr = on ? m->jnt_qposadr[on ? lane : 0] : -1;
-    st.j_dadr = m->jnt_dofadr[on ? lane : 0];
-  }
-  {
-    st.cs_pk = 0;
-    const int c = lane >> 3;
-    if (c < S::NCH && c < m->nrchain) {
-      const int f = m->rchain_first[c];
-      st.cs_pk = m->rchain_len[c] | (m->red_depth[f] << 3) | (f << 8) | (m->red_Madr[f] << 14);
-    }
-    int tb = 0, tb2 = 0;
-    if (lane < 21) { while ((tb + 1) * (tb + 2) / 2 <= lane) tb++; tb2 = lane - tb * (tb + 1) / 2; }
-    else if (lane < 27) { tb = lane - 21; tb2 = 6; }
-    st.cs_pk |= (tb << 24) | (tb2 << 27);
-  }
-  st.ch_first = 0; st.ch_len = 0;
-  for (int c = 0; c < 4; c++)
-    if (c < m->nrchain && lane >= m->rchain_first[c] && lane < m->rchain_first[c] + m->rchain_len[c]) { st.ch_first = m->rchain_first[c]; st.ch_len = m->rchain_len[c]; }
-  {
-    const int r = lane < S::NVR ? lane : 0;
-    st.r_on = lane < S::NVR;
-    st.r_depth = m->red_depth[r]; st.r_Madr = m->red_Madr[r]; st.r_ancmask = m->red_ancmask[r]; st.r_descmask = m->red_descmask[r];
-    st.r_foot = st.r_on ? m->red_foot[r] : 0;
-    if (!st.r_on) { st.r_ancmask = 0; st.r_descmask = 0; st.r_depth = 0; }
-    // dofs are numbered parents first: j < lane can only be an ancestor of this lane's dof (entry in this lane's row, column
-    // depth_j), j > lane only a descendant (entry in j's row, column depth_lane), j == lane the diagonal.  Unrelated pairs
-    // (and lanes past the reduced dofs) point at CDOF[0][0], the angular x component of the base's x translation: always 0.
-    const int rel = st.r_ancmask | st.r_descmask | (st.r_on ? (1 << r) : 0);
-    for (int jp = 0; jp < (S::NVR + 1) / 2; jp++) {
-      int pk = 0;
-      for (int h = 0; h < 2; h++) {
-        const int j = 2 * jp + h;
-        int off = S::O_CDOF * 4;
-        if (j < S::NVR && ((rel >> j) & 1)) off = (S::O_M + (j < r ? st.r_Madr + m->red_depth[j] : m->red_Madr[j] + st.r_depth)) * 4;
-        pk |= off << (16 * h);
-      }
-      st.m_adr[jp] = pk;
-    }
-  }
-  const int i = lane < S::NV ? lane : 0;
-  st.d_on = lane < S::NV;
-  st.d_body = m->dof_body[i];
-  st.d_act = st.d_on ? m->dof_act[i] : -1;
-  st.d_flrow = st.d_on ? m->dof_flrow[i] : -1;
-  st.d_limrow = st.d_on ? m->dof_limrow[i] : -1;
-  st.d_foot = st.d_on ? (m->foot_dofmask[0][i] | (m->foot_dofmask[1][i] << 1)) : 0;
-  st.d_damping = m->dof_damping[i];
-  st.d_lim_on = st.d_limrow >= 0;
-  st.d_qadr = m->dof_qadr[i];
-  st.d_lo = m->dof_range[i][0]; st.d_hi = m->dof_range[i][1];
-  st.d_tkind = (S::PAIRED && st.d_on) ? m->dof_tkind[i] : 0;
-  st.d_red = S::PAIRED ? m->dof_red[i] : i;   // column of this dof's motion vector in CDOF / BUF6
 }
 template <int G>
 __device__ __forceinline__ void load_body(BodySt& b, const DevModel* __restrict__ m, int lane) {
@@ -886,11 +479,6 @@ __device__ __forceinline__ void row_params(const float* P, float pos, float invw
 //   flags bit0: compute sensordata / debug outputs (last substep only)
 // mjx collision_convex._manifold_points: 4 support points of approximately maximal area among the vertices within
 // 1e-3 of the deepest one (lane = vertex; `n` = contact normal)
-// area measures below 1e-7 m^2 count as zero (oracle manifold_points AREA0: collinear / coincident candidates tie like in exact
-// arithmetic instead of by rounding residue)
-__device__ __forceinline__ float area0(float v) { return v < 1e-7f ? 0.0f : v; }
-// last manifold point: values within AREA_TIE of the maximum count as the maximum, the lowest index wins (oracle manifold_points)
-constexpr float AREA_TIE = 1e-7f;
 template <int G>
 __device__ __forceinline__ void select4(const float* w, bool has, float sup, int nvt, const float* n, int* idx, int lane) {
   const float smax = gmax<G>(sup);
@@ -916,15 +504,6 @@ __device__ __forceinline__ void select4(const float* w, bool has, float sup, int
   idx[3] = best == 0x7FFFFFFFu ? 0 : (int)(best >= (unsigned)nvt ? best - (unsigned)nvt : best);
 }
 
-// 16-lane row reductions on unsigned keys (the first four butterfly stages of greduce_u: every lane ends with its row's value)
-template <bool MAX> __device__ __forceinline__ unsigned rreduce_u(unsigned v) {
-  auto op = [](unsigned a, unsigned b) { return MAX ? (a > b ? a : b) : (a < b ? a : b); };
-  v = op(v, ODK_DPPU(v, 0xB1));
-  v = op(v, ODK_DPPU(v, 0x4E));
-  v = op(v, ODK_DPPU(v, 0x141));
-  v = op(v, ODK_DPPU(v, 0x140));
-  return v;
-}
 // _manifold_points for BOTH feet at once: foot f lives in the 16-lane row f (lane = 16 f + vertex, vertices 0..15) and
 // every lane of the row also carries the hull's 17th vertex (index 16) itself, so all arg-max steps are row-local DPP
 // reductions and the two feet share every instruction.  we / supe: the extra vertex (has_e: the hull has one).
@@ -981,10 +560,6 @@ __device__ __forceinline__ void select4_rows(const float* w, bool has, float sup
   const unsigned best = ri < ide ? ri : ide;
   idx[3] = best == 0x7FFFFFFFu ? 0 : (int)(best >= (unsigned)nvt ? best - (unsigned)nvt : best);
 }
-
-}  // namespace odk
-#include "odk_convex.h"
-namespace odk {
 
 // Foot-foot (mesh-mesh) contacts: mjx convex_convex on the two hulls in the world frame (odk_convex.h), worked on by the first
 // 16-lane row of every env whose boxes overlap; the other rows (and envs whose boxes are separated: `overlap` false) run along
@@ -1049,12 +624,8 @@ __device__ __noinline__ void foot_foot_sat(float* L, const DevModel* __restrict_
 // registers over the whole loop.  LDS: hull vertices / face normals in the height field's frame in cfrc | crb; per row the prism's
 // vertices + the two polygons of the face contact in BUF6 / BUF6B; per row prism list, running best four, current four in
 // D | aref | jar | jv; at the end the eight contact frames go to jv ([8][9], read by the constraint-row phase).
-#ifdef ODK_HOST_ONLY   // (the model loader: a translation unit without a device image has nothing to register the table with)
-extern const HfAssign ODK_HF_ASSIGN;
-#else
 // (inline: several objects of libodk.so include this header, and only those with a height-field kernel -- the one reader -- emit the table)
 inline __constant__ HfAssign ODK_HF_ASSIGN = make_hf_assign();
-#endif
 // index into that table from the four rows' open-entry counts (one byte each), each capped at four
 __host__ __device__ __forceinline__ int hf_assign_index(unsigned n_pk) {
   const unsigned c0 = min(n_pk & 255u, 4u), c1 = min((n_pk >> 8) & 255u, 4u), c2 = min((n_pk >> 16) & 255u, 4u), c3 = min(n_pk >> 24, 4u);
@@ -3529,6 +3100,10 @@ __device__ __forceinline__ void forward_env(float* L, const int* RT, const DevMo
   }
   ODK_PROF(17);
 }
+
+#undef ODK_HOTI
+#undef ODK_HOTF
+#undef ODK_OBBC
 
 // mjx forward.euler (eulerdamp disabled): qvel += dt qacc; qpos integrated with the NEW qvel
 template <class S, int G>

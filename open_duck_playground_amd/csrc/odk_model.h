@@ -41,7 +41,7 @@ struct BodySt {
   int body;   // the lane's body id (its column in the LDS body images), -1: no body.  40 dwords (child: up to four, -1 past the body's last)
 };
 
-// Per-lane statics of the step kernels (odk_kernels.h Statics = this + compile-time counts), host-built per lane like the body
+// Per-lane statics of the step kernels (odk_shape.h Statics = this + compile-time counts), host-built per lane like the body
 // records: compute_statics runs on the host once per model, the kernels copy their lane's record.
 struct LaneSt {
   int j_qadr, j_dadr;                    // joint role (sin/cos phase, Euler)
@@ -186,7 +186,7 @@ struct DevModel {
   // observation layouts, [0] Joystick, [1] Standing (last: every older field keeps its offset)
   alignas(16) ObsEnt obs_tab[2][OBS_MAX];
   // Launch-invariant values the substep reads, packed at load (odk_model_load.hip pack_hot) so that the plane-floor step kernel takes them
-  // once per launch (odk_kernels.h load_hot / HotSt) instead of by a vector load a few instructions before its wait in every substep.
+  // once per launch (odk_kernels.h load_hot, odk_shape.h HotSt) instead of by a vector load a few instructions before its wait in every substep.
   // (Behind every older field, as obs_tab was.)  Offsets that only feed an LDS address are stored as BYTE offsets (index * 4).
   int hot_pk[HOT_NPK];      // wave-uniform small integers: the HOT_* fields below
   int np_rec[64][2];        // per lane of an env, the subtree fold's pass-0 record of body i = lane >> 4 (zeros: no such body): [0] np_src[i][0..3] * 4, a byte

@@ -18,7 +18,6 @@
 #include <string>
 #include <vector>
 
-#define ODK_HOST_ONLY   // odk_kernels.h: shapes and compute_statics, no device table
 #include "odk_host.h"
 #include "odk_obs_layout.h"
 #include "odk_shapes.h"

@@ -8,7 +8,7 @@
 
 #include "../../include/odk.h"
 #include "odk_batch.h"
-#include "odk_kernels.h"   // ODK_DPP
+#include "odk_lanes.h"   // ODK_DPP
 #include "odk_obs_layout.h"
 
 using namespace odk;

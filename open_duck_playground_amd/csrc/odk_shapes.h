@@ -3,8 +3,10 @@
 // logic's LDS floats, the kernels' arguments, the `using Shape...` lines, ODK_SHAPES, the list every per-shape dispatch goes through, and the
 // kernel sets (ODK_ENV_SET_...), one object per shape.  A new robot's three lines go in HERE.
 #pragma once
+#include <hip/hip_runtime.h>
+
 #include "../../include/odk.h"
-#include "odk_kernels.h"
+#include "odk_shape.h"
 
 using namespace odk;   // (both includers' own; the generated odk_shapes_user.h names Shape<...> unqualified)
 
@@ -117,7 +119,7 @@ using ShapeBE = Shape<31, 30, 18, 14, 25, 285, 385, 86, 15, 25, true>;
 // box feet): reset / step / physics kernels -- the env kernels' task logic is joystick.py's with the robot's own tables (rec_lay, obs_nobs: sized
 // by Shape::NU; actuators, default pose, sites and sensor addresses from the ModelBlob), the imitation reward with a joint map of its own (odk_batch_set_imitation_joints), Standing
 // with head joints of its own (odk_batch_set_head_joints).  What adding it
-// took: this line, the dispatch lines below that name it (tools/new_shape.py prints them for an XML), and nothing in odk_kernels.h beyond
+// took: this line, the dispatch lines below that name it (tools/new_shape.py prints them for an XML), and nothing in odk_shape.h beyond
 // admitting nv = 21 to the chain solver.
 using ShapeC = Shape<22, 21, 19, 15, 16, 156, 181, 78, 10, 15>;
 // A second one (tests/assets/biped12.xml): a biped with SIX-dof legs (hip yaw / roll / pitch, knee, ankle pitch / roll), 18 dofs, 12 actuators,

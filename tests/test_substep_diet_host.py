@@ -117,9 +117,11 @@ def test_loader_refuses_two_hinges_on_a_body_without_twins_by_name(tmp_path):
 def test_shape_joint_slots():
     """Shape::MAXJB as the kernels are compiled: 2 for the twin shape, 1 for every other one (read from the header, which static_asserts nothing
     about it: the kernels' loops and the loader's refusal both go by this one constant)."""
-    src = open(os.path.join(ROOT, "open_duck_playground_amd", "csrc", "odk_kernels.h")).read()
-    assert "static constexpr int MAXJB = PAIRED ? 2 : 1;" in src
-    assert "jj < 2" not in src and "jj < S::MAXJB" in src
+    csrc = os.path.join(ROOT, "open_duck_playground_amd", "csrc")
+    shape = open(os.path.join(csrc, "odk_shape.h")).read()        # Shape<>
+    forward = open(os.path.join(csrc, "odk_kernels.h")).read()   # forward_env: the pose sweep's joint-slot loops
+    assert "static constexpr int MAXJB = PAIRED ? 2 : 1;" in shape
+    assert "jj < 2" not in forward and "jj < S::MAXJB" in forward
 
 
 @pytest.fixture(scope="module")
